@@ -13,7 +13,12 @@ torch.distributed over RCCL is used only for the barrier and the max-over-ranks 
 `instance_steps_per_s` is printed beside it.  The workload mixes the three amplitude classes of SURVEY.md
 section 8d (s = 0.3 / 1.0 / 3.0, interleaved by instance index); per-class rates are in `classes`.
 
-The oracle (oracle/) is used here only as the checker (`u_err_inf`) and as the `cpu_baseline` leg.
+A plain run sets up, warms up, times exactly K steps (one region), writes the outputs of the last timed step when --dump-outputs
+DIR is given and prints the result line.  Everything else -- rooflines and per-kernel times, the checker, the secondary figures,
+the CPU baseline, the library's own RCCL communicator -- runs only with --full (each leg can still be left out with its --no-*
+option there).
+
+The oracle (oracle/) is used here only as the checker (`u_err_inf`) and as the `cpu_baseline` leg, both under --full.
 """
 import argparse
 import json
@@ -44,6 +49,27 @@ def make_x0(wl, first_instance, count, amplitude=None, seed=0x5EED0002):
         amp = np.array(AMPLITUDES)[(np.arange(first_instance, first_instance + count) % 3)]
         return np.ascontiguousarray(xi * amp[:, None])
     return np.ascontiguousarray(xi * amplitude)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_NAMES = ("x", "e_x", "u", "e_u", "status")
+
+
+def write_outputs(dirname, results, seed=0x5EED00D0):
+    """--dump-outputs: what a caller of the timed path receives from its last step (get_results: x, e_x, u, e_u, status), one
+    DIR/<name>.npy per array in float64.  A batch whose arrays exceed DUMP_LIMIT_BYTES in all is cut to a fixed, seeded sample of
+    instances (the same rows of every array), whose indices go to DIR/instance_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(results[k], dtype=np.float64) for k in DUMP_NAMES}
+    batch = arrays["status"].shape[0]
+    per_instance = sum(a.nbytes for a in arrays.values()) // batch + 8
+    room = DUMP_LIMIT_BYTES - 1024 * (len(arrays) + 1)   # (.npy headers)
+    if per_instance * batch > room:
+        keep = np.sort(np.random.default_rng(seed).choice(batch, room // per_instance, replace=False))
+        arrays = {k: np.ascontiguousarray(a[keep]) for k, a in arrays.items()}
+        arrays["instance_index"] = keep.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def time_steps(solver, opts, steps, barrier):
@@ -247,17 +273,19 @@ def single_process(args):
     run(300)
     run(args.warmup)
     elapsed = run(args.steps)
-    r = g.get_results(want=("u0", "status"))
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, g.get_results(want=DUMP_NAMES))
     out = {"metric": "MPC steps/s (batch=4096, nx=12, nu=4, N=30)", "value": n * args.steps / elapsed,
            "unit": "batch-steps/s (one step = 4096 instance QP solves)", "instance_steps_per_s": batch * args.steps / elapsed,
            "n_gpus": n, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
            "config": {"workload": "configs[1] shards (configs[2] at 8 GPUs): hover-linearised quadrotor nx=12 nu=4 N=30, 4096 instances per "
                                   "GPU, shared model, cold start every step", "launch": "single process, almpc_group (one handle per device)",
-                      "devices": devices, "global_batch": batch, "seed": hex(seed), "setup_ramp_steps": 300},
-           "status_counts": np.bincount(r["status"], minlength=3).tolist()}
+                      "devices": devices, "global_batch": batch, "seed": hex(seed), "setup_ramp_steps": 300}}
+    if args.full:
+        out["status_counts"] = np.bincount(g.get_results(want=("u0", "status"))["status"], minlength=3).tolist()
     g.close()
-    if not args.no_relin:
+    if args.full and not args.no_relin:
         # BASELINE configs[3] through the group (almpc_group_relin_fnn_*): 1024 instances per device, re-linearised every step
         bq, nq, mq, Nq = 1024 * n, 4, 2, 20
         W_in, W_h, b_h, W_out = wl.synthetic_fnn_weights(nq, mq)
@@ -347,6 +375,13 @@ def main():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="plumbing check: spawn / rendezvous / barrier / reductions and the JSON line, no solver (value is null); "
                          "the only mode that runs without a GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: rooflines and per-kernel times, the oracle checker, the secondary figures, the CPU "
+                         "baseline, the library's RCCL communicator and further timed regions (value_runs); the --no-* options "
+                         "leave legs of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the results of the last one (x, e_x, u, e_u, status of rank 0's instances) "
+                         "as DIR/<name>.npy in float64")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -392,7 +427,7 @@ def main():
     X0 = make_x0(wl, first, BATCH_PER_GPU, seed=seed)
     ndev = int(os.environ.get("ALMPC_NUM_DEVICES", "0"))  # test hook: fold ranks onto fewer devices (with ALMPC_DIST_BACKEND=gloo)
     dev_index = (local_rank % ndev) if ndev > 0 else local_rank
-    solver = capi.Solver(NX, NU, N_HORIZON, BATCH_PER_GPU, device=dev_index, timing=True)
+    solver = capi.Solver(NX, NU, N_HORIZON, BATCH_PER_GPU, device=dev_index, timing=args.full)   # (HIP events: --full only)
     rho = args.rho if args.rho is not None else (45.0 if args.rho_profile == "stiffness" else 0.1)
     design_kw = dict(rho=rho, rho_profile=args.rho_profile)
     solver.design_shared(p.A, p.B, p.Q, p.R, p.S, None, p.u_min, p.u_max, **design_kw)
@@ -404,7 +439,7 @@ def main():
     # agree through the launcher's process group whether everybody has it, and the run goes on without it otherwise.
     lib_comm = None
     force_exit = False
-    if ranks.backend != "gloo" and os.environ.get("ALMPC_BENCH_NO_LIB_COMM") != "1":
+    if args.full and ranks.backend != "gloo" and os.environ.get("ALMPC_BENCH_NO_LIB_COMM") != "1":
         import threading
         state = {}
 
@@ -447,20 +482,53 @@ def main():
     RAMP_STEPS = 300
     # setup, not part of the W warm-up steps: a fresh box starts with the GPU in a low power state and the code objects unloaded; a
     # few milliseconds of the workload bring clocks and caches to the steady state the metric is about
-    solver.timing_set_stride(1 << 30)
+    if args.full:
+        solver.timing_set_stride(1 << 30)
     time_steps(solver, opts, RAMP_STEPS, barrier)
-    solver.timing_set_stride(TIMING_STRIDE)
+    if args.full:
+        solver.timing_set_stride(TIMING_STRIDE)
     time_steps(solver, opts, args.warmup, barrier)
-    # The timed region (exactly --steps steps between barrier + synchronize on both sides, maximum over the ranks) is run
-    # TIMED_REPEATS times back to back; `value` is the MEDIAN region, `value_runs` lists all of them.  (At the driver's --steps 20 one
-    # region is 1.3 ms of wall clock: one sample.  A long region -- >= 256 steps -- is already an average and is timed once.)
+    # The timed region: exactly --steps steps between barrier + synchronize on both sides, maximum over the ranks; `value` and
+    # `ms_per_step` are this region's.  --full times TIMED_REPEATS - 1 more regions of the same length right after it (`value_runs`
+    # lists all of them: at --steps 20 one region is 1.3 ms of wall clock; a long region -- >= 256 steps -- is already an average).
     TIMED_REPEATS = 5 if args.steps < 256 else 1
     region_s, tsamp = [], []
-    for _ in range(TIMED_REPEATS):
-        solver.timing_reset(args.steps)
+    for i_region in range(TIMED_REPEATS if args.full else 1):
+        if args.full:
+            solver.timing_reset(args.steps)
         region_s.append(max_over_ranks(time_steps(solver, opts, args.steps, barrier)))
-        tsamp += [float(v) for v in solver.timing_samples()["polish_ms"]]   # the event pairs around k_step_fused inside the timed regions, one per sampled step
-    elapsed = float(np.median(region_s))
+        if i_region == 0 and args.dump_outputs and rank == 0:   # (every step of the region computes the same: cold start, same x0)
+            write_outputs(args.dump_outputs, solver.get_results(want=DUMP_NAMES))
+        if args.full:
+            tsamp += [float(v) for v in solver.timing_samples()["polish_ms"]]   # the event pairs around k_step_fused inside the timed regions, one per sampled step
+    elapsed = region_s[0]
+    inst_steps_per_s = pkg.sharding.aggregate_rate(BATCH_PER_GPU, args.steps, elapsed, world)
+    out = {
+        "metric": "MPC steps/s (batch=4096, nx=12, nu=4, N=30)",
+        "value": inst_steps_per_s / BATCH_PER_GPU,
+        "unit": "batch-steps/s (one step = 4096 instance QP solves)",
+        "instance_steps_per_s": inst_steps_per_s,
+        "n_gpus": world, "rccl_ranks": joined, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "value_note": f"one timed region of exactly {args.steps} steps (barrier + synchronize on both sides, maximum over ranks)",
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "configs[1]: hover-linearised quadrotor nx=12 nu=4 N=30, 4096 instances per GPU, shared model, "
+                               "x0 amplitude classes 0.3/1.0/3.0 interleaved, cold start every step",
+                   "batch_per_gpu": BATCH_PER_GPU, "global_batch": world * BATCH_PER_GPU, "seed": hex(seed),
+                   "setup_ramp_steps": RAMP_STEPS, "setup_ramp_note": "untimed steps of the same workload before the W warm-up steps (clock ramp and "
+                                                                     "code-object load of a fresh box); not part of `warmup`",
+                   "admm_max_iter": int(opts.max_iter), "check_every": int(opts.check_every), "polish": int(opts.polish),
+                   "rho": opts.rho, "rho_profile": args.rho_profile, "eps": opts.eps_abs, "warm_state_kept": False, "parallelism": f"instances sharded over {world} GPU(s), 16-instance tile per workgroup"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        solver.close()
+        ranks.close()
+        return
+    out["value_runs"] = [world * args.steps / t for t in region_s]
+    out["value_note"] += f"; value_runs = it and the {len(region_s) - 1} region(s) of the same length timed right after it"
     tsum = solver.timing_summary()
     res = solver.get_results(want=("u", "status", "iters", "polish_iters"))
     # more event pairs around the same kernel right after the timed region (same workload, every 2nd of 64 steps): the roofline's kernel
@@ -507,26 +575,6 @@ def main():
             comm_line = {"error": got.get("err", "unknown")}
     elif lib_comm is not None:
         comm_line = {"error": lib_comm}
-    inst_steps_per_s = pkg.sharding.aggregate_rate(BATCH_PER_GPU, args.steps, elapsed, world)
-    out = {
-        "metric": "MPC steps/s (batch=4096, nx=12, nu=4, N=30)",
-        "value": inst_steps_per_s / BATCH_PER_GPU,
-        "unit": "batch-steps/s (one step = 4096 instance QP solves)",
-        "instance_steps_per_s": inst_steps_per_s,
-        "n_gpus": world, "rccl_ranks": joined, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "value_runs": [world * args.steps / t for t in region_s],
-        "value_note": f"median of {TIMED_REPEATS} timed region(s) of exactly {args.steps} steps each (barrier + synchronize on both sides, maximum over ranks); value_runs = every region",
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "configs[1]: hover-linearised quadrotor nx=12 nu=4 N=30, 4096 instances per GPU, shared model, "
-                               "x0 amplitude classes 0.3/1.0/3.0 interleaved, cold start every step",
-                   "batch_per_gpu": BATCH_PER_GPU, "global_batch": world * BATCH_PER_GPU, "seed": hex(seed),
-                   "setup_ramp_steps": RAMP_STEPS, "setup_ramp_note": "untimed steps of the same workload before the W warm-up steps (clock ramp and "
-                                                                     "code-object load of a fresh box); not part of `warmup`",
-                   "admm_max_iter": int(opts.max_iter), "check_every": int(opts.check_every), "polish": int(opts.polish),
-                   "rho": opts.rho, "rho_profile": args.rho_profile, "eps": opts.eps_abs, "warm_state_kept": False, "parallelism": f"instances sharded over {world} GPU(s), 16-instance tile per workgroup"},
-    }
     if comm_line is not None:
         out["rccl_in_library"] = comm_line   # ranks / unsolved / max iterations all-reduced by libalmpc.so's own communicator
     if rank == 0:

@@ -97,7 +97,7 @@ def _run_bench(extra, env_extra):
 def test_bench_gpus_2_spawns_two_ranks(capi):
     """`python bench.py --gpus 2` with no launcher: two ranks (folded onto the one GPU of this box, gloo for the barrier) each solve
     their own 4096-instance shard through the HIP library; the line says n_gpus 2 and carries a real throughput."""
-    r = _run_bench(["--gpus", "2", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-classes", "--no-pipelined",
+    r = _run_bench(["--gpus", "2", "--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-classes", "--no-pipelined",
                     "--no-closed-loop", "--no-batched-models", "--no-sqp", "--no-relin", "--no-structured"], {"ALMPC_DIST_BACKEND": "gloo", "ALMPC_NUM_DEVICES": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -115,6 +115,33 @@ def test_bench_refuses_more_ranks_than_gpus():
     r = _run_bench(["--gpus", str(have + 1), "--steps", "2", "--warmup", "1"], {})
     assert r.returncode != 0
     assert "GPU(s) visible" in r.stderr and not any(ln.startswith("{") for ln in r.stdout.splitlines())
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_dumps_its_last_step(pkg, capi, mo, tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps and prints the headline line without the --full figures;
+    --dump-outputs writes what its last timed step computed: x, e_x, u, e_u, status in float64, within 64 MB, from the seeded
+    inputs (stage 1 of x is the benchmark's x0), every instance certified optimal."""
+    import bench
+    import importlib
+    r = _run_bench(["--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / "out")], {})
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == 7 and out["warmup"] == 2 and out["n_gpus"] == 1
+    assert out["value"] > 0 and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert abs(out["ms_per_step"] - 1e3 / out["value"]) <= 1e-9 * out["ms_per_step"]
+    assert not {"roofline", "u_err_inf", "solver", "classes", "cpu_baseline", "value_runs"} & set(out)
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == sorted(k + ".npy" for k in ("x", "e_x", "u", "e_u", "status"))
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in files) <= 64 << 20
+    d = {f[:-4]: np.load(tmp_path / "out" / f) for f in files}
+    assert all(a.dtype == np.float64 for a in d.values())
+    assert d["x"].shape == (4096, 12, 31) and d["u"].shape == (4096, 4, 30) and d["status"].shape == (4096,)
+    d["status"] = d["status"].astype(np.int32)
+    wl = importlib.import_module(pkg.__name__ + ".workloads")
+    _certify(mo, mo.quadrotor(), bench.make_x0(wl, 0, 4096), d, range(0, 4096, 257))
 
 
 @pytest.mark.timeout(900)

@@ -103,32 +103,96 @@ def test_workloads_module_matches_the_oracle_generators(pkg, mo):
         assert np.array_equal(getattr(qf, k), getattr(qfo, k)), k
 
 
+def test_bench_dump_outputs_cap_and_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float64 .npy per result array; a batch beyond the size cap is cut to a fixed, seeded sample of
+    instances (the same rows of every array, indices in instance_index.npy) that fits the cap."""
+    import bench
+    rng = np.random.default_rng(3)
+    b, n, m, N = 500, 3, 2, 4
+    res = {"x": rng.standard_normal((b, n, N + 1)), "e_x": rng.standard_normal((b, n, N + 1)), "u": rng.standard_normal((b, m, N)),
+           "e_u": rng.standard_normal((b, m, N)), "status": rng.integers(0, 3, b).astype(np.int32), "iters": np.zeros(b, np.int32)}
+    bench.write_outputs(str(tmp_path / "all"), res)
+    assert sorted(os.listdir(tmp_path / "all")) == ["e_u.npy", "e_x.npy", "status.npy", "u.npy", "x.npy"]
+    for k in bench.DUMP_NAMES:
+        a = np.load(tmp_path / "all" / (k + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, res[k])
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100_000)
+    for d in ("s1", "s2"):
+        bench.write_outputs(str(tmp_path / d), res)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= 100_000
+    idx = np.load(tmp_path / "s1" / "instance_index.npy").astype(np.int64)
+    assert 0 < len(idx) < b and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "instance_index.npy"))
+    for k in bench.DUMP_NAMES:
+        assert np.array_equal(np.load(tmp_path / "s1" / (k + ".npy")), res[k][idx].astype(np.float64))
+
+
+def _reference_stand_in(patch_text, golden):
+    """The reference's files as far as the patch knows them: every preimage line of every hunk (context and removed lines) at its own
+    line number, a comment line wherever the patch carries none, as many lines as the reference file has (tests/golden)."""
+    import re
+    out, cur, old = {}, None, 0
+    for ln in patch_text.splitlines():
+        if ln.startswith("diff --git"):
+            path = ln.split(" b/")[1].strip()
+            cur = [f"# reference line {k + 1}" for k in range(golden[path]["lines"])] if path in golden else None
+            if cur is not None:
+                out[path] = cur
+        elif cur is None or ln.startswith(("index ", "--- ", "+++ ")):
+            continue
+        elif ln.startswith("@@"):
+            old = int(re.match(r"@@ -(\d+)", ln).group(1)) - 1
+        elif ln.startswith((" ", "-")):
+            assert old < len(cur), "hunk beyond the end of the reference file"
+            cur[old] = ln[1:]
+            old += 1
+    return {path: "\n".join(lines) + "\n" for path, lines in out.items()}
+
+
 def test_reference_side_patch_applies_to_the_reference(tmp_path):
     """julia/reference_hip.patch (the reference-side edits of INTEGRATION.md as an actual diff: hip_solver_def tag, "hip" in
     _IMPLEMENTATION_SOLVER_LIST, the design branches of the linear-system AND the black-box method to
     _model_predictive_control_design_hip, batch-sized result arrays, the dispatch in update_initialization! / calculate!, and the
-    shim itself as src/hip/AlmpcHIP.jl) applies cleanly to the reference's own files and is what julia/make_reference_patch.py
-    produces from the current shim.  Build container only: the GPU box has no /root/reference."""
+    shim itself as src/hip/AlmpcHIP.jl) was made against the reference's own files (its preimage blobs are the ones
+    tests/golden/reference_files.json records), applies cleanly, and is what julia/make_reference_patch.py produces from the current
+    shim.  The reference's files are stood in for by the preimage lines the patch itself carries."""
     import importlib.util
-    import shutil
+    import json
+    import re
     import subprocess
-    ref = "/root/reference"
-    if not os.path.isdir(ref):
-        pytest.skip("no reference checkout here")
+    with open(os.path.join(ROOT, "tests", "golden", "reference_files.json")) as f:
+        golden = json.load(f)["files"]
     files = ["src/types/types.jl", "src/sub/solver_selection.jl", "src/sub/design_mpc.jl", "src/main/computation_mpc.jl",
              "src/AutomationLabsModelPredictiveControl.jl"]
-    for f in files:
-        os.makedirs(os.path.dirname(tmp_path / f), exist_ok=True)
-        shutil.copy(os.path.join(ref, f), tmp_path / f)
+    assert sorted(golden) == sorted(files)
     patch = os.path.join(ROOT, "julia", "reference_hip.patch")
+    patch_text = open(patch).read()
     touched = {ln.split(" b/")[1].strip() for ln in open(patch) if ln.startswith("diff --git")}
     assert touched == set(files) | {"src/hip/AlmpcHIP.jl"}
-    r = subprocess.run(["git", "apply", "--check", "--verbose", patch], cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    # the preimage of every edited file is the reference's blob; the added shim is julia/AlmpcHIP.jl's blob
+    index = dict(re.findall(r"^diff --git a/\S+ b/(\S+)\n(?:new file mode \d+\n)?index (\S+)", patch_text, re.M))
+    assert sorted(index) == sorted(touched)
+    for f in files:
+        assert golden[f]["git_blob"].startswith(index[f].split("..")[0]), f
+    shim_blob = subprocess.check_output(["git", "hash-object", os.path.join(ROOT, "julia", "AlmpcHIP.jl")], text=True).strip()
+    assert index["src/hip/AlmpcHIP.jl"].startswith("0000000..") and shim_blob.startswith(index["src/hip/AlmpcHIP.jl"].split("..")[1])
+    ref = tmp_path / "reference"
+    for f, text in _reference_stand_in(patch_text, golden).items():
+        os.makedirs(os.path.dirname(ref / f), exist_ok=True)
+        with open(ref / f, "w") as fo:
+            fo.write(text)
+        assert len(text.splitlines()) == golden[f]["lines"], f
+    work = tmp_path / "patched"
+    for f in files:
+        os.makedirs(os.path.dirname(work / f), exist_ok=True)
+        with open(work / f, "w") as fo:
+            fo.write(open(ref / f).read())
+    r = subprocess.run(["git", "apply", "--check", "--verbose", patch], cwd=work, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert r.returncode == 0, r.stderr
-    subprocess.check_call(["git", "apply", patch], cwd=tmp_path)
-    sel = open(tmp_path / "src/sub/solver_selection.jl").read()
+    subprocess.check_call(["git", "apply", patch], cwd=work)
+    sel = open(work / "src/sub/solver_selection.jl").read()
     assert "hip = hip_solver_def()," in sel
-    design = open(tmp_path / "src/sub/design_mpc.jl").read()
+    design = open(work / "src/sub/design_mpc.jl").read()
     assert "AlmpcHIP.design_hip(" in design
     # both design methods branch to the GPU design: the linear-system one and the black-box one (SURVEY.md section 8a-10)
     assert design.count("if mpc_solver isa hip_solver_def") == 2
@@ -137,11 +201,14 @@ def test_reference_side_patch_applies_to_the_reference(tmp_path):
     assert "_memory_allocation_initialization_results_hip(" in design and "(horizon + 1) * batch" in design
     # the shim travels with the patch, identical to julia/AlmpcHIP.jl
     shim = open(os.path.join(ROOT, "julia", "AlmpcHIP.jl")).read()
-    assert open(tmp_path / "src/hip/AlmpcHIP.jl").read() == shim
+    assert open(work / "src/hip/AlmpcHIP.jl").read() == shim
     spec = importlib.util.spec_from_file_location("make_reference_patch", os.path.join(ROOT, "julia", "make_reference_patch.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    assert mod.build(ref) == open(patch).read(), "julia/reference_hip.patch is stale: run python julia/make_reference_patch.py"
+    # (blob ids and the function names git puts after a hunk's line numbers come from lines the stand-in does not have)
+    def hunks(text):
+        return [re.sub(r"^(@@ [^@]* @@).*", r"\1", ln) for ln in text.splitlines() if not ln.startswith("index ")]
+    assert hunks(mod.build(str(ref))) == hunks(patch_text), "julia/reference_hip.patch is stale: run python julia/make_reference_patch.py"
     # every ccall in the shim names a symbol the header declares
     import re
     hdr = open(os.path.join(ROOT, "include", "almpc.h")).read()
