@@ -75,6 +75,10 @@ def load():
     L.almpc_sqp_fnn_set_step_rule.argtypes = [_hp, ctypes.c_int]
     L.almpc_sqp_fnn_set_step_rule.restype = ctypes.c_int
     L.almpc_sqp_fnn_skipped.restype = ctypes.c_int
+    L.almpc_sqp_fnn_solve.argtypes = [_hp, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, _ip, _ip, _dp]
+    L.almpc_sqp_fnn_solve.restype = ctypes.c_int
+    L.almpc_sqp_fnn_set_hessian.argtypes = [_hp, ctypes.c_int]
+    L.almpc_sqp_fnn_set_hessian.restype = ctypes.c_int
     L.almpc_get_design_instance.restype = ctypes.c_int
     L.almpc_set_reference.argtypes = [_hp, _dp, _dp, ctypes.c_int]
     L.almpc_set_terminal_equality.argtypes = [_hp, ctypes.c_int]
@@ -145,7 +149,7 @@ def load():
     L.almpc_group_get_results.argtypes = [_hp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
     # group forms of everything a handle can do
     for nm_ in ("almpc_group_set_terminal_equality", "almpc_group_set_rho_profile", "almpc_group_set_structured_fallback",
-                "almpc_group_sqp_fnn_set_structured", "almpc_group_sqp_fnn_set_step_rule"):
+                "almpc_group_sqp_fnn_set_structured", "almpc_group_sqp_fnn_set_step_rule", "almpc_group_sqp_fnn_set_hessian"):
         getattr(L, nm_).argtypes = [_hp, ctypes.c_int]
     L.almpc_group_set_state_box.argtypes = [_hp, _dp, _dp]
     L.almpc_group_design_batched.argtypes = [_hp] + [_dp] * 6 + [ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_double]
@@ -158,6 +162,7 @@ def load():
     L.almpc_group_sqp_fnn_start.argtypes = [_hp, _dp, _dp]
     L.almpc_group_sqp_fnn_iterate.argtypes = [_hp, ctypes.c_int, ctypes.c_double, ctypes.POINTER(almpc_opts), _dp, _dp]
     L.almpc_group_sqp_fnn_skipped.argtypes = [_hp, _ip]
+    L.almpc_group_sqp_fnn_solve.argtypes = [_hp, ctypes.c_int, ctypes.c_double, ctypes.POINTER(almpc_opts), _ip, _ip, _dp]
     L.almpc_group_x0_staging.argtypes = [_hp, ctypes.POINTER(_dp)]
     L.almpc_group_update_initialization_staged.argtypes = [_hp, ctypes.POINTER(_dp)]
     L.almpc_group_get_results_async.argtypes = [_hp, ctypes.c_uint32]
@@ -165,7 +170,7 @@ def load():
     for nm_ in ("almpc_group_set_terminal_equality", "almpc_group_set_rho_profile", "almpc_group_set_structured_fallback", "almpc_group_set_state_box",
                 "almpc_group_design_batched", "almpc_group_relin_fnn_setup", "almpc_group_relin_fnn_step", "almpc_group_relin_fnn_step_async",
                 "almpc_group_relin_fnn_advance", "almpc_group_advance_plant", "almpc_group_sqp_fnn_set_structured", "almpc_group_sqp_fnn_set_step_rule",
-                "almpc_group_sqp_fnn_setup", "almpc_group_sqp_fnn_start", "almpc_group_sqp_fnn_iterate", "almpc_group_sqp_fnn_skipped",
+                "almpc_group_sqp_fnn_setup", "almpc_group_sqp_fnn_start", "almpc_group_sqp_fnn_iterate", "almpc_group_sqp_fnn_skipped", "almpc_group_sqp_fnn_solve", "almpc_group_sqp_fnn_set_hessian",
                 "almpc_group_x0_staging", "almpc_group_update_initialization_staged", "almpc_group_get_results_async", "almpc_group_get_results_wait"):
         getattr(L, nm_).restype = ctypes.c_int
     L.almpc_set_start_from.argtypes = [_hp, _hp]
@@ -247,6 +252,7 @@ def dare(A, B, Q, R):
 
 
 FNN_ACTIVATIONS = {"identity": 0, "relu": 1, "tanh": 2, "sigmoid": 3, "swish": 4}
+SQP_HESSIANS = {"gauss_newton": 0, "exact": 1}   # almpc_sqp_fnn_set_hessian
 
 
 def fnn_linearize(W_in, W_h, b_h, W_out, x, u, act="relu", device=0, want_f=False):
@@ -482,6 +488,21 @@ class Solver:
         self._check(self.L.almpc_sqp_fnn_iterate(self.h, int(iters), float(step_scale), ctypes.byref(opts) if opts is not None else None,
                                                  _ptr(st), _ptr(de)))
         return st, de
+
+    def sqp_fnn_solve(self, max_iters, tol, opts=None, step_rule="merit"):
+        """Solve to a tolerance (almpc_sqp_fnn_solve): at most max_iters iterations, each instance frozen once its iterate passes the
+        first-order test (zero defects, projected adjoint-gradient residual <= tol).  -> dict(status (batch,) int32: 0 converged,
+        1 iteration limit, 2 skipped, 3 infeasible QP; iters (batch,) int32; kkt (batch,) residual of the last test).
+        The step rule is a setting of the handle and stays in force: a later sqp_fnn_iterate sets its own (default "fixed")."""
+        self._check(self.L.almpc_sqp_fnn_set_step_rule(self.h, {"fixed": 0, "merit": 1}[step_rule]))
+        st, it, kk = np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch)
+        self._check(self.L.almpc_sqp_fnn_solve(self.h, int(max_iters), float(tol), ctypes.byref(opts) if opts is not None else None,
+                                               st.ctypes.data_as(_ip), it.ctypes.data_as(_ip), _ptr(kk)))
+        return dict(status=st, iters=it, kkt=kk)
+
+    def sqp_fnn_set_hessian(self, mode):
+        """Hessian of the loop's QPs: "gauss_newton" (default) or "exact" (almpc_sqp_fnn_set_hessian); stays in force."""
+        self._check(self.L.almpc_sqp_fnn_set_hessian(self.h, SQP_HESSIANS[mode]))
 
     def sqp_fnn_skipped(self):
         out = np.zeros(self.batch, dtype=np.int32)
@@ -784,6 +805,16 @@ class Group:
         self._check(self.L.almpc_group_sqp_fnn_iterate(self.g, int(iters), float(step_scale), None if opts is None else ctypes.byref(opts),
                                                        _ptr(st), _ptr(de)))
         return st, de
+
+    def sqp_fnn_solve(self, max_iters, tol, opts=None, step_rule="merit"):
+        self._check(self.L.almpc_group_sqp_fnn_set_step_rule(self.g, {"fixed": 0, "merit": 1}[step_rule]))
+        st, it, kk = np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch)
+        self._check(self.L.almpc_group_sqp_fnn_solve(self.g, int(max_iters), float(tol), None if opts is None else ctypes.byref(opts),
+                                                     st.ctypes.data_as(_ip), it.ctypes.data_as(_ip), _ptr(kk)))
+        return dict(status=st, iters=it, kkt=kk)
+
+    def sqp_fnn_set_hessian(self, mode):
+        self._check(self.L.almpc_group_sqp_fnn_set_hessian(self.g, SQP_HESSIANS[mode]))
 
     def sqp_fnn_skipped(self):
         sk = np.zeros(self.batch, dtype=np.int32)

@@ -256,7 +256,11 @@ def _design_blackbox_nonlinear(system, horizon, sample_time, references, weights
     (src/sub/solver_selection.jl:100-104).  Here the same NLP goes through the device-resident SQP loop (almpc_sqp_fnn_*).
     Keys of this build: mpc_sqp_iterations (outer iterations per calculate!, default 10), mpc_sqp_step (step length, default 1),
     mpc_sqp_step_rule ("merit": steps safeguarded by the l1 merit function, default; "fixed"),
-    mpc_sqp_warm_start (start each calculate! from the previous inputs shifted by one stage, default True)."""
+    mpc_sqp_warm_start (start each calculate! from the previous inputs shifted by one stage, default True),
+    mpc_sqp_hessian ("gauss_newton", default, or "exact": the exact Lagrangian Hessian in every QP of the loop),
+    mpc_sqp_tolerance (None, default: a fixed mpc_sqp_iterations per calculate!; a number: solve every instance to that first-order
+    residual in at most mpc_sqp_iterations full steps, almpc_sqp_fnn_solve -- an instance left at the iteration limit raises
+    ArithmeticError unless mpc_allow_unsolved; modeler.last_sqp_status / last_sqp_iters / last_sqp_kkt record the outcome)."""
     D = _DEFAULT_PARAMETERS_MODEL_PREDICTIVE_CONTROL
     solver_name = kws.get("mpc_solver", D["mpc_solver"])
     if solver_name not in _IMPLEMENTATION_SOLVER_LIST:
@@ -273,6 +277,15 @@ def _design_blackbox_nonlinear(system, horizon, sample_time, references, weights
     x_ref, u_ref = np.asarray(references.x, dtype=np.float64), np.asarray(references.u, dtype=np.float64)
     if x_ref.shape != (n, horizon + 1) or u_ref.shape != (m, horizon):
         raise ValueError("references must be n x (N+1) and m x N")
+    tol = kws.get("mpc_sqp_tolerance", None)
+    if tol is not None:
+        tol = float(tol)
+        if not tol > 0.0:
+            raise ValueError("mpc_sqp_tolerance must be > 0 (or None)")
+        if float(kws.get("mpc_sqp_step", 1.0)) != 1.0:
+            raise ValueError("mpc_sqp_tolerance solves with full steps (under mpc_sqp_step_rule): mpc_sqp_step must be 1")
+        if float(np.asarray(weights.R, dtype=np.float64).reshape(m, m)[0, 0]) == 0.0:
+            raise ValueError("mpc_sqp_tolerance: the first-order residual scales the gradient by 1 / (2 R_aa): R must not be 0")
     sopt = dict(kws.get("mpc_solver_options", {}))
     solver = _capi.Solver(n, m, horizon, batch, device=int(kws.get("mpc_device", 0)), timing=bool(kws.get("mpc_timing", False)))
     solver.sqp_fnn_setup(f.W_in, f.W_h, f.b_h, f.W_out, x_ref, u_ref, weights.Q, weights.R, weights.S, P, system.U.low, system.U.high,
@@ -281,11 +294,21 @@ def _design_blackbox_nonlinear(system, horizon, sample_time, references, weights
                          xmin=system.X.low if state_box else None, xmax=system.X.high if state_box else None,
                          terminal="equality" if terminal == "equality" else "none",
                          qp_solver=kws.get("mpc_sqp_qp_solver", "condensed"))   # "structured": every QP through k_riccati
+    hess = kws.get("mpc_sqp_hessian", "gauss_newton")
+    if hess not in _capi.SQP_HESSIANS:
+        solver.close()
+        raise ValueError(f"mpc_sqp_hessian must be one of {sorted(_capi.SQP_HESSIANS)}")
+    try:
+        solver.sqp_fnn_set_hessian(hess)
+    except _capi.AlmpcError:
+        solver.close()
+        raise
     mod = HipModeler(solver, _capi.default_opts(**sopt), batch)
     mod.allow_unsolved = bool(kws.get("mpc_allow_unsolved", False))
     mod.sqp = dict(iterations=int(kws.get("mpc_sqp_iterations", 10)), step=float(kws.get("mpc_sqp_step", 1.0)),
                    warm_start=bool(kws.get("mpc_sqp_warm_start", True)), u_prev=None,
-                   step_rule=kws.get("mpc_sqp_step_rule", "merit"))
+                   step_rule=kws.get("mpc_sqp_step_rule", "merit"), tolerance=tol)
+    mod.last_sqp_status = mod.last_sqp_iters = mod.last_sqp_kkt = None
     tuning = ModelPredictiveControlTuning(mod, references, horizon, weights, TerminalIngredient(terminal, np.array(P)),
                                           float(sample_time), int(kws.get("mpc_max_time", D["mpc_max_time"])))
     shape = (lambda *s: s) if batch == 1 else (lambda *s: (batch, *s))
@@ -375,7 +398,13 @@ def calculate(C: ModelPredictiveControlController) -> None:
     check the solver status and lets JuMP.value throw when no solution exists; here a non-finite instance
     raises ArithmeticError, and per-instance status/iterations are kept on the modeler."""
     mod: HipModeler = C.tuning.modeler
-    if getattr(mod, "sqp", None) is not None:
+    if getattr(mod, "sqp", None) is not None and mod.sqp.get("tolerance") is not None:
+        out = mod.solver.sqp_fnn_solve(mod.sqp["iterations"], mod.sqp["tolerance"], mod.opts, step_rule=mod.sqp["step_rule"])
+        mod.last_sqp_status, mod.last_sqp_iters, mod.last_sqp_kkt = out["status"], out["iters"], out["kkt"]
+        if np.any(out["status"] != 0) and not getattr(mod, "allow_unsolved", False):   # as the status-1 rule below
+            raise ArithmeticError(f"calculate!: {int((out['status'] != 0).sum())} instance(s) not solved to mpc_sqp_tolerance in "
+                                  "mpc_sqp_iterations iterations (mpc_allow_unsolved = True returns the iterate; modeler.last_sqp_status says which)")
+    elif getattr(mod, "sqp", None) is not None:
         mod.last_sqp_history = mod.solver.sqp_fnn_iterate(mod.sqp["iterations"], mod.sqp["step"], mod.opts, step_rule=mod.sqp["step_rule"])
     elif getattr(mod, "relinearize", None) is not None:
         mod.solver.relin_fnn_step(mod.opts)

@@ -128,6 +128,14 @@ struct almpc_handle {
                                      // (no condensed design at all: no Hessian build, no inverse, no m N <= 128 limit)
         unsigned long long* stats = nullptr;  // [iters][2]
         int stats_cap = 0;
+        // almpc_sqp_fnn_solve: per-instance done | iters | verdict words and the live count ([3 batch + 1]), last residuals [batch],
+        // and a pinned ring of live counts the host reads two iterations behind the device
+        int* sv = nullptr;
+        double* kkt = nullptr;
+        int* live_pin = nullptr;
+        // almpc_sqp_fnn_set_hessian: 0 Gauss-Newton, 1 exact Lagrangian Hessian (multipliers [batch][N][n], stage blocks [batch][N][(n+m)^2])
+        int hessian = 0;
+        double *lam = nullptr, *Wlag = nullptr;
     } sqp;
     // per-step re-linearisation of a black-box Fnn model on the device (almpc_relin_fnn_*, BASELINE configs[3])
     struct Relin {
@@ -318,9 +326,11 @@ void free_all(almpc_handle* h) {
                     h->dXmax, h->dRowTraj, h->dRowEq, h->dRowXidx, h->dRowState, h->dRowMap, h->dGhatE, h->dWinvE, h->lA, h->lB, h->lC, h->lE, h->bA, h->bB, h->bMinv, h->bG, h->bHs, h->bFs,
                     h->bVs, h->bD, h->bRho, h->bH, h->bF, h->bPhi, h->bGk, h->bGam, h->bW, h->bWP, h->bP, h->bFlag, h->bQ, h->dOverflow, h->dOvfSinv, h->dVsPlain, h->dPlain, h->dS0Basis, h->wQ, h->wR, h->wS,
                     h->sqp.W_in, h->sqp.W_h, h->sqp.b_h, h->sqp.W_out, h->sqp.A, h->sqp.B, h->sqp.c, h->sqp.fval, h->sqp.ebar,
-                    h->sqp.qadd, h->sqp.xref, h->sqp.uref, h->sqp.Q, h->sqp.R, h->sqp.S, h->sqp.bad, h->sqp.stats, h->sqp.mer, h->sqp.xback, h->sqp.uback, h->sqp.dxback, h->sqp.vback};
+                    h->sqp.qadd, h->sqp.xref, h->sqp.uref, h->sqp.Q, h->sqp.R, h->sqp.S, h->sqp.bad, h->sqp.stats, h->sqp.mer, h->sqp.xback, h->sqp.uback, h->sqp.dxback, h->sqp.vback,
+                    h->sqp.sv, h->sqp.kkt, h->sqp.lam, h->sqp.Wlag};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    if (h->sqp.live_pin) (void)hipHostFree(h->sqp.live_pin);
     for (void* p : {(void*)h->relin.W_in, (void*)h->relin.W_h, (void*)h->relin.b_h, (void*)h->relin.W_out, (void*)h->relin.ulin,
                     (void*)h->relin.Q, (void*)h->relin.R, (void*)h->relin.S, (void*)h->relin.gS, (void*)h->relin.u0, (void*)h->relin.xnext, (void*)h->relin.Ascr, (void*)h->relin.Bscr})
         if (p) (void)hipFree(p);
@@ -2323,14 +2333,16 @@ int almpc_sqp_fnn_setup(almpc_handle* h, int H, int L, int activation, const dou
         if (rc_ != ALMPC_OK) return rc_;
     }
     almpc_handle::Sqp& q = h->sqp;
-    const int keep_rule = q.step_rule, keep_structured = q.structured_qp;
+    const int keep_rule = q.step_rule, keep_structured = q.structured_qp, keep_hessian = q.hessian;
     void* old[] = {q.W_in, q.W_h, q.b_h, q.W_out, q.A, q.B, q.c, q.fval, q.ebar, q.qadd, q.xref, q.uref, q.Q, q.R, q.S, q.bad, q.stats, q.mer, q.xback, q.uback, q.dxback, q.vback,
-                   h->dXref, h->dUref, h->dFS, h->dV0S};
+                   q.sv, q.kkt, q.lam, q.Wlag, h->dXref, h->dUref, h->dFS, h->dV0S};
     for (void* p_ : old)
         if (p_) (void)hipFree(p_);
+    if (q.live_pin) (void)hipHostFree(q.live_pin);
     q = almpc_handle::Sqp();
     q.step_rule = keep_rule;
     q.structured_qp = keep_structured;
+    q.hessian = keep_hessian;
     h->dXref = h->dUref = h->dFS = h->dV0S = nullptr;
     h->ref_cap[0] = h->ref_cap[1] = h->ref_cap[2] = 0;
     auto up = [&](double** d, const double* src, size_t cnt) -> hipError_t {
@@ -2473,19 +2485,106 @@ int almpc_sqp_fnn_start(almpc_handle* h, const double* x0, const double* u_guess
     return ALMPC_OK;
 }
 
+// almpc_sqp_fnn_solve's part of the loop (null for almpc_sqp_fnn_iterate): the stopping test and the frozen instances
+struct SqpSolveCtl {
+    double tol;
+    int *done, *iters, *verdict, *live;   // device, see almpc_handle::Sqp::sv
+    double* kkt;
+    int* live_pin;                        // pinned [4]
+    hipEvent_t ev[4];
+};
+
+static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_opts* opts, double* step_inf, double* defect_inf,
+                    const SqpSolveCtl* sv);
+
+// what the exact-Hessian mode covers: the condensed route with an input box only, smooth activations, nz <= 128, the per-wave LDS
+// scratch of k_fnn_lag_hessian within 64 KB for four waves
+static int sqp_exact_check(almpc_handle* h) {
+    const almpc_handle::Sqp& q = h->sqp;
+    if (q.structured_qp || h->structured) return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian: the condensed QP route only");
+    if (h->mc > 0) return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian: no state rows (their multipliers would enter the adjoint)");
+    if (q.act == 1) return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian: relu makes the NLP non-smooth");
+    if (h->nz > 128) return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian: nz <= 128");
+    if (4 * fnn_hess_wave_doubles(h->n, h->m, q.H, q.L) * sizeof(double) > 64 * 1024 ||
+        sqp_exact_lds_doubles(h->n, h->m, h->nz) * sizeof(double) > 64 * 1024)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian: the network / stage scratch must fit 64 KB of LDS");
+    return ALMPC_OK;
+}
+
+int almpc_sqp_fnn_set_hessian(almpc_handle* h, int mode) {
+    if (!h) return ALMPC_ERR_INVALID;
+    if (mode != 0 && mode != 1) return fail(h, ALMPC_ERR_INVALID, "sqp_fnn_set_hessian: 0 (Gauss-Newton) or 1 (exact)");
+    if (mode == 1 && h->sqp.ready) { const int rc = sqp_exact_check(h); if (rc != ALMPC_OK) return rc; }
+    h->sqp.hessian = mode;
+    return ALMPC_OK;
+}
+
 int almpc_sqp_fnn_iterate(almpc_handle* h, int iters, double step_scale, const almpc_opts* opts, double* step_inf, double* defect_inf) {
     if (!h) return ALMPC_ERR_INVALID;
     almpc_handle::Sqp& q = h->sqp;
     if (!q.ready || !q.started) return fail(h, ALMPC_ERR_NOT_DESIGNED, "sqp_fnn_iterate needs sqp_fnn_setup and sqp_fnn_start");
     if (iters < 1 || !(step_scale > 0.0 && step_scale <= 1.0)) return fail(h, ALMPC_ERR_INVALID, "sqp_fnn_iterate: iters >= 1, 0 < step_scale <= 1");
+    return sqp_loop(h, iters, step_scale, opts, step_inf, defect_inf, nullptr);
+}
+
+// Solve to a tolerance: at the top of every iteration k_sqp_kkt tests each live instance at its iterate (after the linearisation, which
+// computes the network outputs and Jacobians there anyway) and freezes those that pass; k_sqp_prepare and k_sqp_step leave a frozen
+// instance alone, so its iterate and results stay bit-identical from then on.  The live count is copied into a pinned ring after
+// every test and read by the host two iterations later (the device has more than an iteration queued by then: no bubble); the loop
+// ends when it reaches 0 or after max_iters iterations, followed by one last test at the final iterate.
+int almpc_sqp_fnn_solve(almpc_handle* h, int max_iters, double tol, const almpc_opts* opts, int32_t* status, int32_t* iters, double* kkt) {
+    if (!h) return ALMPC_ERR_INVALID;
+    almpc_handle::Sqp& q = h->sqp;
+    if (!q.ready || !q.started) return fail(h, ALMPC_ERR_NOT_DESIGNED, "sqp_fnn_solve needs sqp_fnn_setup and sqp_fnn_start");
+    if (max_iters < 1 || !(tol > 0.0)) return fail(h, ALMPC_ERR_INVALID, "sqp_fnn_solve: max_iters >= 1, tol > 0");
+    if (!q.useR) return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_solve: the stopping test scales the gradient by 1 / (2 R_aa): R[0,0] must not be 0");
+    if (h->m > 64) return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_solve: m <= 64 (one lane per input in the adjoint walk)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t b = (size_t)h->batch;
+    hipStream_t st = h->stream;
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (!q.sv) { HIP_TRY(h, dalloc(&q.sv, 3 * b + 1)); HIP_TRY(h, dalloc(&q.kkt, b)); }
+    if (!q.live_pin) HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&q.live_pin), 4 * sizeof(int), hipHostMallocDefault));
+    SqpSolveCtl sv;
+    sv.tol = tol; sv.done = q.sv; sv.iters = q.sv + b; sv.verdict = q.sv + 2 * b; sv.live = q.sv + 3 * b; sv.kkt = q.kkt;
+    sv.live_pin = q.live_pin;
+    {
+        std::vector<int> init(3 * b + 1, 0);
+        for (size_t i = 0; i < b; ++i) init[2 * b + i] = 1;   // verdict: iteration limit unless converged / skipped
+        init[3 * b] = (int)b;
+        HIP_TRY(h, hipMemcpy(q.sv, init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    for (auto& e : sv.ev) e = nullptr;
+    int rc = ALMPC_OK;
+    for (auto& e : sv.ev)
+        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { rc = fail(h, ALMPC_ERR_HIP, "sqp_fnn_solve: hipEventCreate"); break; }
+    if (rc == ALMPC_OK) rc = sqp_loop(h, max_iters, 1.0, opts, nullptr, nullptr, &sv);
+    for (auto& e : sv.ev)
+        if (e) (void)hipEventDestroy(e);
+    if (rc != ALMPC_OK) return rc;
+    std::vector<int> w(3 * b);
+    std::vector<double> r(b);
+    HIP_TRY(h, hipMemcpy(w.data(), q.sv, w.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(r.data(), q.kkt, b * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < b; ++i) {
+        if (status) status[i] = w[i] ? 0 : w[2 * b + i];
+        if (iters) iters[i] = w[b + i];
+        if (kkt) kkt[i] = r[i];
+    }
+    return ALMPC_OK;
+}
+
+static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_opts* opts, double* step_inf, double* defect_inf,
+                    const SqpSolveCtl* sv) {
+    almpc_handle::Sqp& q = h->sqp;
     HIP_TRY(h, hipSetDevice(h->device));
     const int n = h->n, m = h->m, N = h->N, nz = h->nz, nzs = h->nzs;
     const size_t b = (size_t)h->batch;
     hipStream_t st = h->stream;
-    if (q.stats_cap < iters) {
+    if (q.stats_cap < iters || !q.stats) {
         if (q.stats) { HIP_TRY(h, hipStreamSynchronize(st)); (void)hipFree(q.stats); q.stats = nullptr; }
-        HIP_TRY(h, dalloc(&q.stats, (size_t)2 * iters));
-        q.stats_cap = iters;
+        HIP_TRY(h, dalloc(&q.stats, (size_t)2 * std::max(iters, 1)));
+        q.stats_cap = std::max(iters, 1);
     }
     HIP_TRY(h, hipMemsetAsync(q.stats, 0, (size_t)2 * iters * sizeof(unsigned long long), st));
     const DesignStrides ds = batched_strides(h, q.sP != 0);
@@ -2503,18 +2602,71 @@ int almpc_sqp_fnn_iterate(almpc_handle* h, int iters, double step_scale, const a
     sp.v = h->dEu; sp.flag = h->bFlag; sp.status = h->dStatus; sp.bad = q.bad; sp.stats = q.stats; sp.step_scale = step_scale;
     sp.x = h->dX; sp.ex = h->dEx; sp.u = h->dU; sp.eu = h->dEu; sp.adaptive = q.step_rule; sp.mu = q.mu; sp.Q = q.Q; sp.P = h->bP; sp.sP = q.sP; sp.mer = q.mer;
     sp.xback = q.xback; sp.uback = q.uback; sp.dxback = q.dxback; sp.vback = q.vback;
+    SqpKktParams kp;
+    if (sv) {
+        sp.done = sv->done; sp.verdict = sv->verdict;
+        kp.n = n; kp.m = m; kp.N = N; kp.nz = nz; kp.useS = q.useS;
+        kp.xref = q.xref; kp.uref = q.uref; kp.Q = q.Q; kp.R = q.R; kp.S = q.S; kp.P = h->bP; kp.sP = q.sP;
+        kp.umin = h->dUmin; kp.umax = h->dUmax; kp.xbar = h->dXref; kp.ubar = h->dUref; kp.fval = q.fval; kp.A = q.A; kp.B = q.B;
+        kp.tol = sv->tol; kp.it = 0; kp.done = sv->done; kp.iters = sv->iters; kp.kkt = sv->kkt; kp.live = sv->live;
+        if (step_lds > 64 * 1024) HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sqp_kkt), (size_t)(step_lds)));
+    }
+    // the stopping test at the top of iteration `it` (the Jacobians and network outputs at the iterate are in q.A, q.B, q.fval)
+    auto kkt_test = [&](int it) -> hipError_t {
+        kp.it = it;
+        hipLaunchKernelGGL(k_sqp_kkt, dim3((unsigned)b), dim3(256), step_lds, st, kp);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(sv->live_pin + (it & 3), sv->live, sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipEventRecord(sv->ev[it & 3], st);
+        return e;
+    };
+    bool all_done = false;
     DesignLtvParams lp;
     lp.n = n; lp.m = m; lp.N = N; lp.nz = nz; lp.useR = q.useR; lp.useS = q.useS;
     lp.A = q.A; lp.B = q.B; lp.c = q.c; lp.ebar = q.ebar; lp.P = h->bP; lp.sP = q.sP; lp.Q = q.Q; lp.R = q.R; lp.S = q.S;
     lp.qadd = q.qadd; lp.H = h->bH; lp.q = h->bQ;
+    const bool exact = q.hessian == 1;
+    FnnHessParams hp;
+    SqpExactParams xp;
+    size_t hess_lds = 0, exact_lds = 0;
+    if (exact) {
+        { const int rc_ = sqp_exact_check(h); if (rc_ != ALMPC_OK) return rc_; }
+        if (!q.lam) { HIP_TRY(h, dalloc(&q.lam, b * N * (size_t)n)); HIP_TRY(h, dalloc(&q.Wlag, b * N * (size_t)(n + m) * (n + m))); }
+        if (!sv) {   // the multipliers only: the walk of k_sqp_kkt without the test
+            kp.n = n; kp.m = m; kp.N = N; kp.nz = nz; kp.useS = q.useS;
+            kp.xref = q.xref; kp.uref = q.uref; kp.Q = q.Q; kp.R = q.R; kp.S = q.S; kp.P = h->bP; kp.sP = q.sP;
+            kp.umin = h->dUmin; kp.umax = h->dUmax; kp.xbar = h->dXref; kp.ubar = h->dUref; kp.fval = q.fval; kp.A = q.A; kp.B = q.B;
+            kp.tol = 0.0; kp.it = 0; kp.done = nullptr; kp.iters = nullptr; kp.kkt = nullptr; kp.live = nullptr;
+            if (step_lds > 64 * 1024) HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sqp_kkt), (size_t)(step_lds)));
+        }
+        kp.lam = q.lam;
+        hp.n = n; hp.m = m; hp.H = q.H; hp.L = q.L; hp.act = q.act; hp.N = N; hp.batch = h->batch;
+        hp.W_in = q.W_in; hp.W_h = q.W_h; hp.b_h = q.b_h; hp.W_out = q.W_out; hp.xbar = h->dXref; hp.ubar = h->dUref; hp.lam = q.lam;
+        hp.done = sv ? sv->done : nullptr; hp.W = q.Wlag;
+        xp.n = n; xp.m = m; xp.N = N; xp.nz = nz; xp.A = q.A; xp.B = q.B; xp.c = q.c; xp.W = q.Wlag; xp.ubar = h->dUref;
+        xp.umin = h->dUmin; xp.umax = h->dUmax; xp.done = sv ? sv->done : nullptr; xp.H = h->bH; xp.q = h->bQ;
+        hess_lds = 4 * fnn_hess_wave_doubles(n, m, q.H, q.L) * sizeof(double);
+        exact_lds = sqp_exact_lds_doubles(n, m, nz) * sizeof(double);
+    }
     // register-tile design kernel: scaling, scaled gradient and the flag reset ride along as its tail (three launches less per iteration)
-    const bool ltv_scales = ltv_reg_path(h) && nz <= 128 && !q.structured_qp && !getenv("ALMPC_DBG_SPLIT_SCALE");
+    // (not in exact mode: k_sqp_exact_qp changes H and q after the design, the factor then scales them)
+    const bool ltv_scales = !exact && ltv_reg_path(h) && nz <= 128 && !q.structured_qp && !getenv("ALMPC_DBG_SPLIT_SCALE");
     if (ltv_scales) { lp.sc_d = h->bD; lp.sc_Hs = h->bHs; lp.sc_fS = h->dFS; lp.sc_flag = h->bFlag; lp.nzs = nzs; }
     // ... and k_sqp_prepare as its head (its outputs are that kernel's inputs): a fourth launch less
     const bool prep_in_design = ltv_scales && !getenv("ALMPC_DBG_SPLIT_PREPARE");
     if (prep_in_design) { lp.prep_on = 1; lp.prep = sp; }
     for (int it = 0; it < iters; ++it) {
+        if (sv && it >= 2) {   // every live instance had converged at the top of iteration it - 2: the rest is frozen work
+            HIP_TRY(h, hipEventSynchronize(sv->ev[(it - 2) & 3]));
+            if (sv->live_pin[(it - 2) & 3] == 0) { all_done = true; break; }
+        }
         HIP_TRY(h, launch_fnn_jacobian(fp, h->num_cus, st));
+        if (sv) HIP_TRY(h, kkt_test(it));
+        if (exact) {   // multipliers (from the test above, or the walk alone), then the stage Lagrangian Hessians at the iterate
+            if (!sv) hipLaunchKernelGGL(k_sqp_kkt, dim3((unsigned)b), dim3(256), step_lds, st, kp);
+            hipLaunchKernelGGL(k_fnn_lag_hessian, dim3((unsigned)((b * N + 3) / 4)), dim3(256), hess_lds, st, hp);
+            HIP_TRY(h, hipGetLastError());
+        }
         if (!prep_in_design) hipLaunchKernelGGL(k_sqp_prepare, dim3((unsigned)b), dim3(256), 0, st, sp);
         if (!ltv_scales) HIP_TRY(h, hipMemsetAsync(h->bFlag, 0, b * sizeof(int), st));
         if (q.structured_qp) {   // the QP in its stage-wise form for every instance; start: v = 0 (working set = the iterate's inputs on a bound)
@@ -2536,6 +2688,11 @@ int almpc_sqp_fnn_iterate(almpc_handle* h, int iters, double step_scale, const a
             continue;
         }
         HIP_TRY(h, launch_design_ltv(h, lp, st));
+        if (exact) {   // H, q of the exact QP (an instance whose result is not positive definite is flagged by the factor and, with the
+                       // structured fallback on, takes the Gauss-Newton QP in its stage-wise form)
+            hipLaunchKernelGGL(k_sqp_exact_qp, dim3((unsigned)b), dim3(256), exact_lds, st, xp);
+            HIP_TRY(h, hipGetLastError());
+        }
         h->skip_admm = (q.guess_from_iterate && q.since_start > 0) ? 1 : 0;
         // (with the scaling in the design kernel's tail fS_i exists before the inverse: v0S_i = -G_i fS_i comes out of the inverse's launch)
         const bool v0_in_inverse = ltv_scales && design_inverse_makes_v(nz);
@@ -2563,6 +2720,11 @@ int almpc_sqp_fnn_iterate(almpc_handle* h, int iters, double step_scale, const a
         hipLaunchKernelGGL(k_sqp_step, dim3((unsigned)b), dim3(256), step_lds, st, sp);
         HIP_TRY(h, hipGetLastError());
     }
+    if (sv && !all_done) {   // the last test, at the final iterate
+        HIP_TRY(h, launch_fnn_jacobian(fp, h->num_cus, st));
+        HIP_TRY(h, kkt_test(iters));
+    }
+    if (sv) return almpc_synchronize(h);   // (per-instance verdicts instead of ALMPC_ERR_NUMERIC; no histories)
     std::vector<unsigned long long> stats((size_t)2 * iters);
     std::vector<int> bad(b);
     HIP_TRY(h, hipMemcpyAsync(stats.data(), q.stats, stats.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));

@@ -473,6 +473,19 @@ int almpc_group_sqp_fnn_iterate(almpc_group* g, int iters, double step_scale, co
     }
     return rc;
 }
+int almpc_group_sqp_fnn_set_hessian(almpc_group* g, int mode) {
+    if (!g) return ALMPC_ERR_INVALID;
+    for (size_t i = 0; i < g->hs.size(); ++i) { const int rc = almpc_sqp_fnn_set_hessian(g->hs[i], mode); if (rc != ALMPC_OK) return gfail(g, rc, (int)i); }
+    return ALMPC_OK;
+}
+int almpc_group_sqp_fnn_solve(almpc_group* g, int max_iters, double tol, const almpc_opts* opts, int32_t* status, int32_t* iters, double* kkt) {
+    if (!g) return ALMPC_ERR_INVALID;
+    return group_fanout(g, [&](int i) {
+        const size_t f = (size_t)g->first[i];
+        return almpc_sqp_fnn_solve(g->hs[i], max_iters, tol, opts, status ? status + f : nullptr, iters ? iters + f : nullptr,
+                                   kkt ? kkt + f : nullptr);
+    });
+}
 int almpc_group_sqp_fnn_skipped(almpc_group* g, int32_t* skipped) {
     if (!g || !skipped) return ALMPC_ERR_INVALID;
     for (size_t i = 0; i < g->hs.size(); ++i) { const int rc = almpc_sqp_fnn_skipped(g->hs[i], skipped + g->first[i]); if (rc != ALMPC_OK) return gfail(g, rc, (int)i); }

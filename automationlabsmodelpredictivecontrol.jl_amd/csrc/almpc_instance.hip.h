@@ -979,6 +979,10 @@ struct SqpParams {
     double* xback; double* uback;   // [batch][(N+1) n], [batch][nz]: last accepted point
     double* dxback; double* vback;  // its step (dx of every stage, v), so that a rejected trial can be re-taken shorter
     double *x, *ex, *u, *eu;    // result buffers: the iterate after the update
+    // almpc_sqp_fnn_solve only (null otherwise): done[i] != 0 freezes instance i (k_sqp_kkt set it: no merit test, no update, its
+    // iterate and results stay bit-identical); verdict[i] = 2 (skipped) / 3 (infeasible QP) when an iteration of it was skipped
+    const int* done = nullptr;
+    int* verdict = nullptr;
 };
 
 // Before the QP: defects, state errors and the input part of the gradient, one workgroup per instance.
@@ -996,7 +1000,7 @@ __device__ inline void sqp_prepare_body(const SqpParams& p, const size_t i) {
     const int tid = threadIdx.x < 256 ? (int)threadIdx.x : 0x3fffffff, nthr = 256;   // (threads beyond 256 only meet the barriers)
     double* xbw = p.xbar + i * (size_t)(N + 1) * n;
     double* ubw = p.ubar + i * (size_t)nz;
-    if (p.adaptive) {
+    if (p.adaptive && !(p.done && p.done[i])) {   // (a frozen instance keeps its iterate: uniform per workgroup)
         __shared__ double red[8];
         __shared__ int reject;
         double part = 0.0;

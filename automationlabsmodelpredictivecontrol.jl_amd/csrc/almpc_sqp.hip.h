@@ -75,10 +75,12 @@ inline __global__ __launch_bounds__(256) void k_sqp_step(SqpParams p) {
     }
     __syncthreads();
     if (tid == 0) {
-        const int redo_ = p.adaptive && p.mer[4 * i + 2] != 0.0;   // trial point rejected in k_sqp_prepare: this QP is void
-        const int bad = !redo_ && ((red[8] + red[9] + red[10] + red[11] != 0.0) || p.flag[i] != 0 || p.status[i] == 2 || p.status[i] == 3);
-        skip = bad || redo_;
+        const int frozen = p.done && p.done[i];   // converged in almpc_sqp_fnn_solve: never updated again
+        const int redo_ = !frozen && p.adaptive && p.mer[4 * i + 2] != 0.0;   // trial point rejected in k_sqp_prepare: this QP is void
+        const int bad = !frozen && !redo_ && ((red[8] + red[9] + red[10] + red[11] != 0.0) || p.flag[i] != 0 || p.status[i] == 2 || p.status[i] == 3);
+        skip = frozen || bad || redo_;
         if (bad) p.bad[i] = 1;
+        if (bad && p.verdict) p.verdict[i] = p.status[i] == 3 ? 3 : 2;
         else if (!redo_) {
             atomicMax(p.stats + 0, (unsigned long long)__double_as_longlong(fmax(fmax(red[0], red[1]), fmax(red[2], red[3]))));
             atomicMax(p.stats + 1, (unsigned long long)__double_as_longlong(fmax(fmax(red[4], red[5]), fmax(red[6], red[7]))));
@@ -140,6 +142,384 @@ inline __global__ __launch_bounds__(256) void k_sqp_step(SqpParams p) {
         }
         p.u[i * (size_t)nz + t] = uv;
         p.eu[i * (size_t)nz + t] = uv - p.uref[t];
+    }
+}
+
+// Stopping test of almpc_sqp_fnn_solve at the top of an iteration, at the iterate (xbar, ubar), on the network outputs and Jacobians
+// the iteration's linearisation has just computed there; one workgroup per instance.
+//     lam_N = 2 P e_N,  G_k = 2 R eu_k + B_k' lam_{k+1} (+ input-rate terms),  lam_k = 2 Q e_k + A_k' lam_{k+1}
+//     residual = |U - clip(U - G / (2 R_aa))|_inf   (tests/sqp_solve_ref.py; with zero defects: the oracle's nlp_kkt_residual)
+// An instance converges when max |f(x_k, u_k) - x_{k+1}| <= 1e-10 and residual <= tol: done[i] = 1, iters[i] = the iteration, and the
+// live count goes down by one.  The adjoint recursion is a dependent chain of N stages walked backwards as k_sqp_step walks forwards:
+// [A_k | B_k | 2 Q e_k] of `chunk` stages staged in LDS by the whole workgroup, then wave 0 alone, lane j < n owning lam_j and the
+// previous lam read from the lanes (v_readlane), no barrier per stage.
+struct SqpKktParams {
+    int n, m, N, nz, useS;
+    const double* xref; const double* uref;   // [(N+1)][n], [N][m]
+    const double* Q; const double* R; const double* S; const double* P; long sP;   // symmetrised
+    const double* umin; const double* umax;
+    const double* xbar; const double* ubar;   // [batch][(N+1)][n], [batch][N][m]
+    const double* fval;                       // [batch][N][n] network outputs at (xbar_k, ubar_k)
+    const double* A; const double* B;         // [batch][N][n*n], [batch][N][n*m]
+    double tol;
+    int it;                                   // iteration about to start (= QP iterations taken so far)
+    int* done; int* iters; double* kkt;       // [batch]; done null: no test, the multipliers only (exact Hessian in iterate)
+    int* live;                                // instances not yet converged
+    double* lam = nullptr;                    // [batch][N][n] or null: lam_{k+1}, the multiplier of stage k's dynamics
+};
+
+inline __global__ __launch_bounds__(256) void k_sqp_kkt(SqpKktParams p) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const size_t i = blockIdx.x;
+    if (p.done && p.done[i]) return;   // frozen: nothing of it changes any more (uniform per workgroup)
+    const int n = p.n, m = p.m, N = p.N, nz = p.nz, tid = threadIdx.x, nn = n * n, nm = n * m, E = nn + nm + n;
+    const int CH = sqp_step_chunk(n, m, N);
+    double* stage = smem;                       // [CH][E]: A_k | B_k | 2 Q e_k (2 P e_N is lam_N)
+    double* gs = stage + (size_t)CH * E;        // [nz] G_k, stage by stage
+    double* red = gs + nz;                      // [16]
+    const double* xb = p.xbar + i * (size_t)(N + 1) * n;
+    const double* ub = p.ubar + i * (size_t)nz;
+    const double* fv = p.fval + i * (size_t)N * n;
+    const double* Ag = p.A + i * N * (size_t)nn;
+    const double* Bg = p.B + i * N * (size_t)nm;
+    const double* Pm = p.P + i * p.sP;
+    double dmax = 0.0;
+    for (int t = tid; t < N * n; t += 256) {
+        const double d = fabs(fv[t] - xb[n + t]);
+        dmax = fmax(dmax, d == d ? d : 1.79e308);   // (a NaN defect never converges)
+    }
+    dmax = wave_max(dmax);
+    if ((tid & 63) == 0) red[tid >> 6] = dmax;
+    // lam_N = 2 P e_N, wave 0 lane j < n
+    const int lj = tid < n ? tid : 0;
+    double lam = 0.0;
+    if (tid < 64) {
+        for (int c2 = 0; c2 < n; ++c2) lam += Pm[(size_t)c2 * n + lj] * (xb[(size_t)N * n + c2] - p.xref[(size_t)N * n + c2]);
+        lam *= 2.0;
+    }
+    int top = N;   // stages [0, top) not walked yet
+    while (top > 0) {
+        const int k0 = top - CH > 0 ? top - CH : 0, cnt = top - k0;
+        __syncthreads();                        // the previous chunk has been consumed
+        for (int t = tid; t < cnt * E; t += 256) {
+            const int k = k0 + t / E, e = t % E;
+            double v;
+            if (e < nn) v = Ag[(size_t)k * nn + e];
+            else if (e < nn + nm) v = Bg[(size_t)k * nm + e - nn];
+            else {   // 2 Q e_k (stage 0: x_0 is fixed, no term)
+                const int r = e - nn - nm;
+                double s = 0.0;
+                if (k > 0)
+                    for (int c2 = 0; c2 < n; ++c2) s += p.Q[(size_t)c2 * n + r] * (xb[(size_t)k * n + c2] - p.xref[(size_t)k * n + c2]);
+                v = 2.0 * s;
+            }
+            stage[t] = v;
+        }
+        __syncthreads();
+        if (tid < 64) {
+            for (int kk = cnt - 1; kk >= 0; --kk) {
+                const double* A = stage + (size_t)kk * E;
+                const double* B = A + nn;
+                double g = 0.0, s = A[nn + nm + lj];
+                for (int c2 = 0; c2 < n; ++c2) {
+                    const double l = readlane_d(lam, c2);
+                    g += B[(size_t)(tid < m ? tid : 0) * n + c2] * l;   // (B_k' lam_{k+1})_a, lane a < m
+                    s += A[(size_t)lj * n + c2] * l;                    // (A_k' lam_{k+1})_j, lane j < n
+                }
+                if (tid < m) gs[(size_t)(k0 + kk) * m + tid] = g;
+                if (p.lam && tid < n) p.lam[(i * N + k0 + kk) * (size_t)n + tid] = lam;
+                lam = s;
+            }
+        }
+        top = k0;
+    }
+    __syncthreads();
+    // G = 2 R eu + B' lam (+ 2 D'S D u): the projected residual in the Jacobi-scaled coordinates of nlp_kkt_residual
+    double r = 0.0;
+    for (int t = tid; t < nz; t += 256) {
+        const int k = t / m, a = t % m;
+        double g = gs[t], s = 0.0;
+        for (int c2 = 0; c2 < m; ++c2) s += p.R[(size_t)c2 * m + a] * (ub[k * m + c2] - p.uref[k * m + c2]);
+        g += 2.0 * s;
+        if (p.useS) {
+            double s2 = 0.0;
+            for (int c2 = 0; c2 < m; ++c2) {
+                const double sac = p.S[(size_t)c2 * m + a];
+                if (k + 1 < N) s2 += sac * (ub[k * m + c2] - ub[(k + 1) * m + c2]);
+                if (k > 0) s2 -= sac * (ub[(k - 1) * m + c2] - ub[k * m + c2]);
+            }
+            g += 2.0 * s2;
+        }
+        const double u = ub[t], sc = 1.0 / fmax(2.0 * p.R[(size_t)a * m + a], 1e-12);
+        const double proj = fmin(fmax(u - sc * g, p.umin[a]), p.umax[a]);
+        const double d = fabs(u - proj);
+        r = fmax(r, d == d ? d : 1.79e308);
+    }
+    r = wave_max(r);
+    if ((tid & 63) == 0) red[4 + (tid >> 6)] = r;
+    __syncthreads();
+    if (tid == 0 && p.done) {
+        const double dm = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+        const double rr = fmax(fmax(red[4], red[5]), fmax(red[6], red[7]));
+        p.kkt[i] = rr;
+        p.iters[i] = p.it;
+        if (dm <= 1e-10 && rr <= p.tol) {
+            p.done[i] = 1;
+            atomicSub(p.live, 1);
+        }
+    }
+}
+
+// Exact-Hessian mode (almpc_sqp_fnn_set_hessian): the stage Lagrangian Hessian of the Fnn layout at every (instance, stage),
+//     W_k = d^2/dz^2 (lam_{k+1}' f(z_k)) = sum_j M_j' diag(ybar_j * act''(a_j)) M_j,   z = [x; u]
+// M_j = d a_j / d z the forward Jacobian chain (as k_fnn_jacobian forms it), ybar_j the adjoint of act(a_j) from W_out' lam.  One
+// wave per point, four per workgroup, each with its own LDS scratch (fnn_hess_wave_doubles); weights read through the cache.
+// Entries are summed as (M_r M_c) c so that W_k is exactly symmetric.  tests/sqp_exact_ref.py::stage_hessian restates it.
+__device__ __forceinline__ void fnn_act2(int act, double a, double& d1, double& d2) {
+    switch (act) {
+        case 2: { const double t = tanh(a); d1 = 1.0 - t * t; d2 = -2.0 * t * d1; break; }
+        case 3: { const double s = 1.0 / (1.0 + exp(-a)); d1 = s * (1.0 - s); d2 = d1 * (1.0 - 2.0 * s); break; }
+        case 4: { const double s = 1.0 / (1.0 + exp(-a)); d1 = s * (1.0 + a * (1.0 - s)); d2 = s * (1.0 - s) * (2.0 + a * (1.0 - 2.0 * s)); break; }
+        case 1: d1 = a > 0.0 ? 1.0 : 0.0; d2 = 0.0; break;
+        default: d1 = 1.0; d2 = 0.0; break;
+    }
+}
+__host__ __device__ inline size_t fnn_hess_wave_doubles(int n, int m, int H, int L) {
+    const size_t nin = (size_t)n + m;
+    return nin + 3 * (size_t)H + (size_t)H * nin + 2 * (size_t)L * H + (size_t)L * H * nin;
+}
+struct FnnHessParams {
+    int n, m, H, L, act, N, batch;
+    const double* W_in; const double* W_h; const double* b_h; const double* W_out;   // layout of FnnParams
+    const double* xbar; const double* ubar;   // [batch][(N+1)][n], [batch][N][m]
+    const double* lam;                        // [batch][N][n]
+    const int* done;                          // [batch] or null: frozen instances are skipped
+    double* W;                                // [batch][N][(n+m)^2] column-major
+};
+
+inline __global__ __launch_bounds__(256) void k_fnn_lag_hessian(FnnHessParams p) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int n = p.n, m = p.m, H = p.H, L = p.L, nin = n + m, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double* z = smem + (size_t)wv * fnn_hess_wave_doubles(n, m, H, L);
+    double* y = z + nin;                  // [H]
+    double* yb = y + H;                   // [H]
+    double* t = yb + H;                   // [H]
+    double* J = t + H;                    // [H][nin] row-major: d y / d z
+    double* Aa = J + (size_t)H * nin;     // [L][H] pre-activations
+    double* Cc = Aa + (size_t)L * H;      // [L][H] ybar * act''
+    double* M = Cc + (size_t)L * H;       // [L][H][nin] d a_l / d z
+    const long pt = (long)blockIdx.x * 4 + wv;
+    if (pt >= (long)p.batch * p.N) return;   // (wave-uniform; no workgroup barrier below)
+    const long inst = pt / p.N;
+    const int k = (int)(pt % p.N);
+    if (p.done && p.done[inst]) return;
+    auto wsync = []() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
+    for (int c = lane; c < nin; c += 64)
+        z[c] = c < n ? p.xbar[(inst * (p.N + 1) + k) * n + c] : p.ubar[(inst * p.N + k) * m + c - n];
+    wsync();
+    for (int i = lane; i < H; i += 64) {
+        double s = 0.0;
+        for (int c = 0; c < nin; ++c) s += p.W_in[(size_t)c * H + i] * z[c];
+        y[i] = s;
+    }
+    for (int e = lane; e < H * nin; e += 64) J[e] = p.W_in[(size_t)(e % nin) * H + e / nin];
+    wsync();
+    for (int l = 0; l < L; ++l) {
+        const double* W = p.W_h + (size_t)l * H * H;
+        for (int i = lane; i < H; i += 64) {
+            double s = p.b_h[(size_t)l * H + i];
+            for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * y[j];
+            Aa[l * H + i] = s;
+        }
+        for (int e = lane; e < H * nin; e += 64) {
+            const int i = e / nin, c = e % nin;
+            double s = 0.0;
+            for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * J[(size_t)j * nin + c];
+            M[((size_t)l * H + i) * nin + c] = s;
+        }
+        wsync();
+        for (int i = lane; i < H; i += 64) {
+            double val, der;
+            fnn_act(p.act, Aa[l * H + i], val, der);
+            y[i] = val;
+        }
+        for (int e = lane; e < H * nin; e += 64) {
+            double val, der;
+            fnn_act(p.act, Aa[l * H + e / nin], val, der);
+            J[e] = M[(size_t)l * H * nin + e] * der;
+        }
+        wsync();
+    }
+    const double* lam = p.lam + (inst * p.N + k) * (size_t)n;
+    for (int i = lane; i < H; i += 64) {
+        double s = 0.0;
+        for (int r = 0; r < n; ++r) s += p.W_out[(size_t)i * n + r] * lam[r];
+        yb[i] = s;
+    }
+    wsync();
+    for (int l = L - 1; l >= 0; --l) {
+        const double* W = p.W_h + (size_t)l * H * H;
+        for (int i = lane; i < H; i += 64) {
+            double d1, d2;
+            fnn_act2(p.act, Aa[l * H + i], d1, d2);
+            Cc[l * H + i] = yb[i] * d2;
+            t[i] = yb[i] * d1;
+        }
+        wsync();
+        for (int j = lane; j < H; j += 64) {
+            double s = 0.0;
+            for (int i = 0; i < H; ++i) s += W[(size_t)j * H + i] * t[i];
+            yb[j] = s;
+        }
+        wsync();
+    }
+    double* Wo = p.W + pt * (size_t)nin * nin;
+    for (int e = lane; e < nin * nin; e += 64) {
+        const int r = e % nin, c = e / nin;
+        double s = 0.0;
+        for (int l = 0; l < L; ++l)
+            for (int i = 0; i < H; ++i) {
+                const double* Mi = M + ((size_t)l * H + i) * nin;
+                s += (Mi[r] * Mi[c]) * Cc[l * H + i];
+            }
+        Wo[e] = s;
+    }
+}
+
+// The exact condensed QP from the Gauss-Newton one k_design_ltv has just written (unscaled H, q), one workgroup per instance:
+//     H += sum_k M_k' W_k M_k,  q += sum_k M_k' W_k [g_k; 0],  M_k = [Gam_k; E_k]  (dx_k = Gam_k v + g_k, E_k selects v_k)
+// Gam_k, g_k are propagated stage by stage in LDS (Gam_0 = 0, g_0 = 0); every thread keeps its entries of the update in registers
+// (entries a <= b only: H stays exactly symmetric).  Then the inertia rule: delta = max(0, max_a sum_{b != a} |H_ab| - H_aa)
+// (Gershgorin bound of the result) on the diagonal of every input that sits on a bound at the iterate.  nz <= 128.
+constexpr int SQP_EXACT_REGS = 64;   // 128^2 / 256 entries per thread
+struct SqpExactParams {
+    int n, m, N, nz;
+    const double* A; const double* B; const double* c;   // [batch][N][n*n], [batch][N][n*m], [batch][N][n] (defects)
+    const double* W;                                     // [batch][N][(n+m)^2]
+    const double* ubar; const double* umin; const double* umax;
+    const int* done;                                     // [batch] or null
+    double* H; double* q;                                // [batch][nz*nz] column-major, [batch][nz]
+};
+__host__ __device__ inline size_t sqp_exact_lds_doubles(int n, int m, int nz) {
+    const size_t nin = (size_t)n + m;
+    return 2 * (size_t)n * nz + 2 * (size_t)n + nin * nz + nin + nin * nin + (size_t)n * n + (size_t)n * m + n + 8;
+}
+
+inline __global__ __launch_bounds__(256) void k_sqp_exact_qp(SqpExactParams p) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const size_t i = blockIdx.x;
+    if (p.done && p.done[i]) return;
+    const int n = p.n, m = p.m, N = p.N, nz = p.nz, nin = n + m, tid = threadIdx.x, nn = n * n, nm = n * m;
+    double* G = smem;                        // [n][nz] Gam_k (row-major)
+    double* Gn = G + (size_t)n * nz;
+    double* g = Gn + (size_t)n * nz;         // [n]
+    double* gn = g + n;
+    double* T = gn + n;                      // [nin][nz] W_k M_k
+    double* tg = T + (size_t)nin * nz;       // [nin] W_k [g_k; 0]
+    double* Wk = tg + nin;                   // [nin][nin] column-major
+    double* Ak = Wk + (size_t)nin * nin;
+    double* Bk = Ak + nn;
+    double* ck = Bk + nm;
+    double* red = ck + n;                    // [8]
+    double acc[SQP_EXACT_REGS];
+#pragma unroll
+    for (int j = 0; j < SQP_EXACT_REGS; ++j) acc[j] = 0.0;
+    double qacc = 0.0;
+    for (int t = tid; t < n * nz; t += 256) G[t] = 0.0;
+    for (int t = tid; t < n; t += 256) g[t] = 0.0;
+    for (int k = 0; k < N; ++k) {
+        for (int t = tid; t < nin * nin; t += 256) Wk[t] = p.W[(i * N + k) * (size_t)nin * nin + t];
+        for (int t = tid; t < nn; t += 256) Ak[t] = p.A[(i * N + k) * (size_t)nn + t];
+        for (int t = tid; t < nm; t += 256) Bk[t] = p.B[(i * N + k) * (size_t)nm + t];
+        for (int t = tid; t < n; t += 256) ck[t] = p.c[(i * N + k) * (size_t)n + t];
+        __syncthreads();
+        for (int t = tid; t < nin * nz; t += 256) {   // T = W_k M_k
+            const int r = t / nz, col = t % nz, kc = col - k * m;
+            double s = 0.0;
+            for (int s2 = 0; s2 < n; ++s2) s += Wk[(size_t)s2 * nin + r] * G[(size_t)s2 * nz + col];
+            if (kc >= 0 && kc < m) s += Wk[(size_t)(n + kc) * nin + r];
+            T[t] = s;
+        }
+        for (int r = tid; r < nin; r += 256) {
+            double s = 0.0;
+            for (int s2 = 0; s2 < n; ++s2) s += Wk[(size_t)s2 * nin + r] * g[s2];
+            tg[r] = s;
+        }
+        for (int t = tid; t < n * nz; t += 256) {     // Gam_{k+1} = A_k Gam_k + B_k E_k
+            const int r = t / nz, col = t % nz, kc = col - k * m;
+            double s = 0.0;
+            for (int s2 = 0; s2 < n; ++s2) s += Ak[(size_t)s2 * n + r] * G[(size_t)s2 * nz + col];
+            if (kc >= 0 && kc < m) s += Bk[(size_t)kc * n + r];
+            Gn[t] = s;
+        }
+        for (int r = tid; r < n; r += 256) {
+            double s = ck[r];
+            for (int s2 = 0; s2 < n; ++s2) s += Ak[(size_t)s2 * n + r] * g[s2];
+            gn[r] = s;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < SQP_EXACT_REGS; ++j) {
+            const int e = tid + 256 * j;
+            if (e < nz * nz) {
+                const int a = e % nz, b = e / nz;
+                if (a <= b) {
+                    double s = 0.0;
+                    for (int r = 0; r < n; ++r) s += G[(size_t)r * nz + a] * T[(size_t)r * nz + b];
+                    const int ka = a - k * m;
+                    if (ka >= 0 && ka < m) s += T[(size_t)(n + ka) * nz + b];
+                    acc[j] += s;
+                }
+            }
+        }
+        if (tid < nz) {
+            double s = 0.0;
+            for (int r = 0; r < n; ++r) s += G[(size_t)r * nz + tid] * tg[r];
+            const int ka = tid - k * m;
+            if (ka >= 0 && ka < m) s += tg[n + ka];
+            qacc += s;
+        }
+        __syncthreads();
+        for (int t = tid; t < n * nz; t += 256) G[t] = Gn[t];
+        for (int t = tid; t < n; t += 256) g[t] = gn[t];
+        // (the next stage's loads follow; its first barrier orders these copies before their use)
+    }
+    double* Hi = p.H + i * (size_t)nz * nz;
+#pragma unroll
+    for (int j = 0; j < SQP_EXACT_REGS; ++j) {
+        const int e = tid + 256 * j;
+        if (e < nz * nz) {
+            const int a = e % nz, b = e / nz;
+            if (a <= b) {
+                const double v = Hi[(size_t)b * nz + a] + acc[j];
+                acc[j] = v;
+                Hi[(size_t)b * nz + a] = v;
+                Hi[(size_t)a * nz + b] = v;
+            }
+        }
+    }
+    if (tid < nz) p.q[i * (size_t)nz + tid] += qacc;
+    __syncthreads();   // (H of this instance written by the workgroup: visible to it from here on)
+    double dl = 0.0;
+    for (int a = tid; a < nz; a += 256) {   // row sums in a fixed order: the shift is reproducible bit for bit
+        double sa = 0.0;
+        for (int b = 0; b < nz; ++b) sa += b == a ? 0.0 : fabs(Hi[(size_t)a * nz + b]);
+        dl = fmax(dl, sa - Hi[(size_t)a * nz + a]);
+    }
+    dl = wave_max(dl);
+    if ((tid & 63) == 0) red[tid >> 6] = dl;
+    __syncthreads();
+    const double delta = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    if (delta > 0.0) {
+#pragma unroll
+        for (int j = 0; j < SQP_EXACT_REGS; ++j) {
+            const int e = tid + 256 * j;
+            if (e < nz * nz && e % nz == e / nz) {
+                const int a = e % nz;
+                const double u = p.ubar[i * (size_t)nz + a];
+                if (u <= p.umin[a % m] || u >= p.umax[a % m]) Hi[(size_t)a * nz + a] = acc[j] + delta;
+            }
+        }
     }
 }
 

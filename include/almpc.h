@@ -285,6 +285,32 @@ int almpc_sqp_fnn_start(almpc_handle* h, const double* x0, const double* u_guess
 int almpc_sqp_fnn_iterate(almpc_handle* h, int iters, double step_scale, const almpc_opts* opts, double* step_inf,
                           double* defect_inf);
 int almpc_sqp_fnn_skipped(almpc_handle* h, int32_t* skipped /* [batch], 1 = some iteration was skipped */);
+/*
+ * Solve to a tolerance instead of a fixed count: at most max_iters (>= 1) iterations of the loop above (full steps under the handle's
+ * step rule), with a first-order stopping test per instance at the top of every iteration, at its iterate:
+ *     max_k |f(x_k, u_k) - x_{k+1}|_inf <= 1e-10  and  |U - clip(U - G / (2 R_aa))|_inf <= tol,
+ * G the adjoint gradient of the cost at the iterate (with zero defects: the gradient of the single-shooting NLP).  An instance that
+ * passes is frozen: no later iteration changes it (its results are bit-identical whatever max_iters is); the call returns when
+ * every instance is frozen or max_iters iterations have run (then one last test at the final iterate).  Per instance (nullable):
+ *     status  0 converged, 1 iteration limit, 2 an iteration was skipped (see iterate) and it did not converge, 3 the same with an
+ *             infeasible QP (state rows)
+ *     iters   QP iterations taken before the test that froze it (max_iters when it did not converge)
+ *     kkt     the residual of its last test
+ * Skipped iterations are reported in `status`, not as ALMPC_ERR_NUMERIC.  ALMPC_ERR_UNSUPPORTED when R[0,0] == 0 (the residual
+ * divides by 2 R_aa) or m > 64.  almpc_get_results afterwards returns the iterate as after iterate.
+ */
+/*
+ * Hessian of every QP of the loop (iterate and solve): ALMPC_SQP_HESSIAN_GAUSS_NEWTON (default) or ALMPC_SQP_HESSIAN_EXACT, the
+ * exact Lagrangian Hessian: the stage blocks W_k = d^2/dz^2 (lam_{k+1}' f(z_k)) with the multipliers of the adjoint walk at the
+ * iterate, condensed into H and q, plus the Gershgorin bound of the result on the diagonal of every input on a bound at the iterate.
+ * An instance whose shifted Hessian is still not positive definite takes that iteration with the Gauss-Newton QP (structured
+ * fallback; without it the iteration is skipped).  ALMPC_ERR_UNSUPPORTED for EXACT with state rows, the structured QP route, relu,
+ * nz > 128 (checked here once set up, else at the next iterate / solve).
+ */
+enum { ALMPC_SQP_HESSIAN_GAUSS_NEWTON = 0, ALMPC_SQP_HESSIAN_EXACT = 1 };
+int almpc_sqp_fnn_set_hessian(almpc_handle* h, int mode);
+int almpc_sqp_fnn_solve(almpc_handle* h, int max_iters, double tol, const almpc_opts* opts, int32_t* status, int32_t* iters,
+                        double* kkt);
 /* Step rule of almpc_sqp_fnn_iterate.  0 (default): every instance takes steps of length `step_scale` (full Gauss-Newton steps
  * are not globally convergent: they can end in a cycle when the tracking residual is large).  1: safeguarded by the l1 merit
  * function phi = J + mu |f(x,u) - x+|_1 (mu = 2 max(|P|, |Q|)), tested a posteriori with the network outputs the next
@@ -476,6 +502,10 @@ int almpc_group_sqp_fnn_start(almpc_group* g, const double* x0, const double* u_
 int almpc_group_sqp_fnn_iterate(almpc_group* g, int iters, double step_scale, const almpc_opts* opts, double* step_inf,
                                 double* defect_inf);
 int almpc_group_sqp_fnn_skipped(almpc_group* g, int32_t* skipped);
+int almpc_group_sqp_fnn_set_hessian(almpc_group* g, int mode);
+/* almpc_sqp_fnn_solve on every device at the same time; status / iters / kkt [batch] (nullable) */
+int almpc_group_sqp_fnn_solve(almpc_group* g, int max_iters, double tol, const almpc_opts* opts, int32_t* status, int32_t* iters,
+                              double* kkt);
 /* host-facing path of the group: slots[i] = handle i's pinned x0 buffer ([count_i][n], almpc_x0_staging) -> write the shard's states
  * there -> almpc_group_update_initialization_staged(g, slots) (no copy);  read-back by ticket as almpc_get_results_async / _wait, the
  * arrays of _wait being those of almpc_group_get_results */

@@ -8,7 +8,7 @@
 # solver tag "hip" next to osqp/scip/ipopt/auto (src/sub/solver_selection.jl:9-14).
 module AlmpcHIP
 
-export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_state_rows!, design_batched!, design_sqp_fnn!, sqp_start!, sqp_iterate!,
+export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_state_rows!, design_batched!, design_sqp_fnn!, sqp_start!, sqp_iterate!, sqp_solve!, set_sqp_hessian!,
        design_relin_fnn!, relin_step!, relin_advance!, update_initialization!, calculate!, read_results!,
        _model_predictive_control_computation, comm_unique_id, comm_init!, comm_summary, comm_allgather_first_input,
        calculate_async!, synchronize!, relin_step_async!, advance_plant!, start_from!, update_initialization_device!, device_results, set_step_fusion!,
@@ -18,7 +18,7 @@ export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_s
        HipGroup, group_design_hip, group_handle, group_shard, group_update_initialization!, group_calculate!, group_calculate_async!,
        group_synchronize!, group_read_results!, group_set_state_rows!, group_set_rho_profile!, group_set_structured_fallback!,
        group_design_batched!, group_design_relin_fnn!, group_relin_step!, group_relin_advance!, group_advance_plant!, group_design_sqp_fnn!,
-       group_sqp_start!, group_sqp_iterate!, group_sqp_skipped, group_x0_staging, group_update_initialization_staged!, group_results_async,
+       group_sqp_start!, group_sqp_iterate!, group_sqp_solve!, group_set_sqp_hessian!, group_sqp_skipped, group_x0_staging, group_update_initialization_staged!, group_results_async,
        group_results_wait!
 
 const libalmpc = get(ENV, "ALMPC_LIB", "libalmpc.so")
@@ -180,6 +180,25 @@ function sqp_iterate!(mod::HipModeler, iters::Integer; step::Float64 = 1.0, meri
     check(mod.handle, ccall((:almpc_sqp_fnn_iterate, libalmpc), Cint, (Ptr{Cvoid}, Cint, Cdouble, Ref{AlmpcOpts}, Ptr{Float64}, Ptr{Float64}),
                             mod.handle, iters, step, o, st, de))
     return st, de
+end
+
+"""
+    sqp_solve!(mod, max_iters, tol; merit_safeguard = true) -> (status, iters, kkt)
+
+Solve to a first-order tolerance (`almpc_sqp_fnn_solve`): at most `max_iters` full steps, every instance frozen once its iterate
+has zero defects and a projected adjoint-gradient residual <= `tol`.  Per instance: status 0 converged, 1 iteration limit,
+2 skipped, 3 infeasible QP; QP iterations taken; residual of the last test.
+"""
+"Hessian of the SQP loop's QPs: `:gauss_newton` (default) or `:exact` (`almpc_sqp_fnn_set_hessian`)"
+set_sqp_hessian!(mod::HipModeler, mode::Symbol) =
+    check(mod.handle, ccall((:almpc_sqp_fnn_set_hessian, libalmpc), Cint, (Ptr{Cvoid}, Cint), mod.handle, mode === :exact ? 1 : 0))
+function sqp_solve!(mod::HipModeler, max_iters::Integer, tol::Float64; merit_safeguard::Bool = true)
+    check(mod.handle, ccall((:almpc_sqp_fnn_set_step_rule, libalmpc), Cint, (Ptr{Cvoid}, Cint), mod.handle, merit_safeguard ? 1 : 0))
+    st, it, kk = Vector{Int32}(undef, mod.batch), Vector{Int32}(undef, mod.batch), Vector{Float64}(undef, mod.batch)
+    o = Ref(mod.opts)
+    check(mod.handle, ccall((:almpc_sqp_fnn_solve, libalmpc), Cint, (Ptr{Cvoid}, Cint, Cdouble, Ref{AlmpcOpts}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+                            mod.handle, max_iters, tol, o, st, it, kk))
+    return st, it, kk
 end
 
 # update_initialization!(C, x0): x0 is a Vector (batch 1) or an n x batch Matrix (src/main/computation_mpc.jl:17-29)
@@ -670,6 +689,16 @@ function group_sqp_iterate!(g::HipGroup, iters::Integer; step::Float64 = 1.0, me
     gcheck(g.group, ccall((:almpc_group_sqp_fnn_iterate, libalmpc), Cint, (Ptr{Cvoid}, Cint, Cdouble, Ref{AlmpcOpts}, Ptr{Float64}, Ptr{Float64}),
                           g.group, iters, step, o, st, de))
     return st, de
+end
+group_set_sqp_hessian!(g::HipGroup, mode::Symbol) =
+    gcheck(g.group, ccall((:almpc_group_sqp_fnn_set_hessian, libalmpc), Cint, (Ptr{Cvoid}, Cint), g.group, mode === :exact ? 1 : 0))
+function group_sqp_solve!(g::HipGroup, max_iters::Integer, tol::Float64; merit_safeguard::Bool = true)
+    gcheck(g.group, ccall((:almpc_group_sqp_fnn_set_step_rule, libalmpc), Cint, (Ptr{Cvoid}, Cint), g.group, merit_safeguard ? 1 : 0))
+    st, it, kk = Vector{Int32}(undef, g.batch), Vector{Int32}(undef, g.batch), Vector{Float64}(undef, g.batch)
+    o = Ref(g.opts)
+    gcheck(g.group, ccall((:almpc_group_sqp_fnn_solve, libalmpc), Cint, (Ptr{Cvoid}, Cint, Cdouble, Ref{AlmpcOpts}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+                          g.group, max_iters, tol, o, st, it, kk))
+    return st, it, kk
 end
 function group_sqp_skipped(g::HipGroup)
     sk = Vector{Int32}(undef, g.batch)
