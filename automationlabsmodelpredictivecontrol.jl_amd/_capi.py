@@ -252,11 +252,24 @@ def dare(A, B, Q, R):
 
 
 FNN_ACTIVATIONS = {"identity": 0, "relu": 1, "tanh": 2, "sigmoid": 3, "swish": 4}
+# network kinds in the Fnn weight layout (include/almpc.h ALMPC_NET_*): only the hidden-layer recurrence differs
+NET_KINDS = {"fnn", "resnet", "polynet"}
+_NET_CODES = {"fnn": 0, "resnet": 1, "polynet": 2}
+
+
+def net_code(net="fnn", act="relu"):
+    """ALMPC_NET_CODE(kind, activation): the `activation` argument of the network calls (a bare activation for an Fnn)."""
+    if net not in NET_KINDS:
+        raise ValueError(f"net must be one of {sorted(NET_KINDS)}, not {net!r}")
+    return (_NET_CODES[net] << 8) | FNN_ACTIVATIONS[act]
+
+
 SQP_HESSIANS = {"gauss_newton": 0, "exact": 1}   # almpc_sqp_fnn_set_hessian
 
 
-def fnn_linearize(W_in, W_h, b_h, W_out, x, u, act="relu", device=0, want_f=False):
-    """Batched Jacobians of an Fnn model on the GPU: x (batch, n), u (batch, m) -> A (batch, n, n), B (batch, n, m)."""
+def fnn_linearize(W_in, W_h, b_h, W_out, x, u, act="relu", device=0, want_f=False, net="fnn"):
+    """Batched Jacobians of a network model on the GPU: x (batch, n), u (batch, m) -> A (batch, n, n), B (batch, n, m).
+    net: "fnn", "resnet" or "polynet" (NET_KINDS), all in the Fnn weight layout."""
     L = load()
     W_in, W_out = np.asfortranarray(W_in, dtype=np.float64), np.asfortranarray(W_out, dtype=np.float64)
     H, nin = W_in.shape
@@ -269,7 +282,7 @@ def fnn_linearize(W_in, W_h, b_h, W_out, x, u, act="relu", device=0, want_f=Fals
     u = np.ascontiguousarray(np.atleast_2d(u), dtype=np.float64)
     batch = x.shape[0]
     A = np.empty((batch, n, n)); B = np.empty((batch, m, n)); f = np.empty((batch, n)) if want_f else None
-    rc = L.almpc_fnn_linearize(int(device), n, m, H, nl, FNN_ACTIVATIONS[act], _ptr(W_in), _ptr(Wh), _ptr(bh), _ptr(W_out),
+    rc = L.almpc_fnn_linearize(int(device), n, m, H, nl, net_code(net, act), _ptr(W_in), _ptr(Wh), _ptr(bh), _ptr(W_out),
                                batch, _ptr(x), _ptr(u), _ptr(A), _ptr(B), _ptr(f))
     if rc != ALMPC_OK:
         raise AlmpcError(rc, "almpc_fnn_linearize")
@@ -390,8 +403,8 @@ class Solver:
                                             _ptr(S), _ptr(P), p_inst, _ptr(umin), _ptr(umax), float(rho), float(sigma)))
 
     def sqp_fnn_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu", rho=0.1,
-                      sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", qp_solver="condensed"):
-        """SQP outer loop for an Fnn model (almpc_sqp_fnn_*): network as in fnn_linearize, x_ref (n, N+1) / u_ref (m, N) or None,
+                      sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", qp_solver="condensed", net="fnn"):
+        """SQP outer loop for a network model (almpc_sqp_fnn_*): network (and net) as in fnn_linearize, x_ref (n, N+1) / u_ref (m, N) or None,
         P (n, n) or (batch, n, n).  qp_solver: "condensed" (default) or "structured" (every QP through k_riccati, no condensed design).  xmin / xmax: the state box of the reference's NLP branch
         (.../fnn/mpc_modeler_implementation_fnn.jl:146-153) as rows of every iteration's QP; terminal = "equality"."""
         n, m, N, b = self.n, self.m, self.N, self.batch
@@ -415,14 +428,14 @@ class Solver:
             P = _colmajor(P, (n, n))
         umin = np.ascontiguousarray(umin, dtype=np.float64).reshape(m)
         umax = np.ascontiguousarray(umax, dtype=np.float64).reshape(m)
-        self._check(self.L.almpc_sqp_fnn_setup(self.h, H, nl, FNN_ACTIVATIONS[act], _ptr(W_in), _ptr(Wh), _ptr(bh), _ptr(W_out), _ptr(xr),
+        self._check(self.L.almpc_sqp_fnn_setup(self.h, H, nl, net_code(net, act), _ptr(W_in), _ptr(Wh), _ptr(bh), _ptr(W_out), _ptr(xr),
                                                _ptr(ur), _ptr(Q), _ptr(R), _ptr(S), _ptr(P), p_inst, _ptr(umin), _ptr(umax), float(rho),
                                                float(sigma)))
 
     def relin_fnn_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu", rho=0.1,
-                        sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none"):
-        """Device-resident per-step re-linearisation of an Fnn model (almpc_relin_fnn_*, BASELINE configs[3]): network as in
-        fnn_linearize, shared x_ref (n, N+1) / u_ref (m, N) or None, shared P (n, n); xmin / xmax / terminal as in design_batched."""
+                        sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", net="fnn"):
+        """Device-resident per-step re-linearisation of a network model (almpc_relin_fnn_*, BASELINE configs[3]): network (and net)
+        as in fnn_linearize, shared x_ref (n, N+1) / u_ref (m, N) or None, shared P (n, n); xmin / xmax / terminal as in design_batched."""
         n, m, N = self.n, self.m, self.N
         self._state_rows(xmin, xmax, terminal)
         self._check(self.L.almpc_set_rho_profile(self.h, {"scalar": 0, "stiffness": 1}[rho_profile]))
@@ -438,7 +451,7 @@ class Solver:
         P = _colmajor(P, (n, n))
         umin = np.ascontiguousarray(umin, dtype=np.float64).reshape(m)
         umax = np.ascontiguousarray(umax, dtype=np.float64).reshape(m)
-        self._check(self.L.almpc_relin_fnn_setup(self.h, H, nl, FNN_ACTIVATIONS[act], _ptr(W_in), _ptr(Wh), _ptr(bh), _ptr(W_out), _ptr(xr),
+        self._check(self.L.almpc_relin_fnn_setup(self.h, H, nl, net_code(net, act), _ptr(W_in), _ptr(Wh), _ptr(bh), _ptr(W_out), _ptr(xr),
                                                  _ptr(ur), _ptr(Q), _ptr(R), _ptr(S), _ptr(P), _ptr(umin), _ptr(umax), float(rho),
                                                  float(sigma)))
 
@@ -745,7 +758,7 @@ class Group:
         self._check(self.L.almpc_group_design_batched(self.g, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(S), _ptr(P), p_inst, _ptr(umin),
                                                       _ptr(umax), float(rho), float(sigma)))
 
-    def _fnn_args(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, act, p_batched):
+    def _fnn_args(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, act, p_batched, net="fnn"):
         n, m, N = self.n, self.m, self.N
         W_in = np.asarray(W_in, dtype=np.float64)
         H = W_in.shape[0]
@@ -764,13 +777,13 @@ class Group:
         arrs = [_colmajor(W_in, (H, n + m)), Wh, bh, _colmajor(W_out, (n, H)), xr, ur, _colmajor(Q, (n, n)), _colmajor(R, (m, m)),
                 None if S is None else _colmajor(S, (m, m)), P,
                 np.ascontiguousarray(umin, dtype=np.float64).reshape(m), np.ascontiguousarray(umax, dtype=np.float64).reshape(m)]
-        return H, nl, FNN_ACTIVATIONS[act], arrs, p_inst
+        return H, nl, net_code(net, act), arrs, p_inst
 
     def relin_fnn_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu", rho=0.1,
-                        sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none"):
+                        sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", net="fnn"):
         self._state_rows(xmin, xmax, terminal)
         self._check(self.L.almpc_group_set_rho_profile(self.g, {"scalar": 0, "stiffness": 1}[rho_profile]))
-        H, nl, a, arrs, _ = self._fnn_args(W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, act, False)
+        H, nl, a, arrs, _ = self._fnn_args(W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, act, False, net)
         self._keep = arrs
         self._check(self.L.almpc_group_relin_fnn_setup(self.g, H, nl, a, *[_ptr(v) for v in arrs], float(rho), float(sigma)))
 
@@ -785,11 +798,11 @@ class Group:
         self._check(self.L.almpc_group_advance_plant(self.g))
 
     def sqp_fnn_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu", rho=0.1,
-                      sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", qp_solver="condensed"):
+                      sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", qp_solver="condensed", net="fnn"):
         self._state_rows(xmin, xmax, terminal)
         self._check(self.L.almpc_group_set_rho_profile(self.g, {"scalar": 0, "stiffness": 1}[rho_profile]))
         self._check(self.L.almpc_group_sqp_fnn_set_structured(self.g, 1 if qp_solver == "structured" else 0))
-        H, nl, a, arrs, p_inst = self._fnn_args(W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, act, True)
+        H, nl, a, arrs, p_inst = self._fnn_args(W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, act, True, net)
         self._keep = arrs
         ptrs = [_ptr(v) for v in arrs]
         self._check(self.L.almpc_group_sqp_fnn_setup(self.g, H, nl, a, *ptrs[:10], p_inst, ptrs[10], ptrs[11], float(rho), float(sigma)))

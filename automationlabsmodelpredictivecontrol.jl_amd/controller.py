@@ -29,7 +29,7 @@ from . import _capi
 from .sharding import shard_range  # noqa: F401  (re-exported)
 
 __all__ = [
-    "Hyperrectangle", "ConstrainedLinearControlDiscreteSystem", "ConstrainedBlackBoxControlDiscreteSystem", "Fnn",
+    "Hyperrectangle", "ConstrainedLinearControlDiscreteSystem", "ConstrainedBlackBoxControlDiscreteSystem", "Fnn", "ResNet", "PolyNet", "Icnn",
     "proceed_system_linearization", "ReferencesStateInput", "WeightsCoefficient",
     "TerminalIngredient", "ModelPredictiveControlTuning", "ModelPredictiveControlResults",
     "ModelPredictiveControlController", "proceed_controller", "_design_reference_mpc",
@@ -80,6 +80,47 @@ class Fnn:
 
 
 @dataclasses.dataclass
+class ResNet(Fnn):
+    """Residual network in the Fnn layout (.../resnet/mpc_modeler_implementation_resnet.jl:123-142): hidden layer
+    y' = y + act(W_h[l] y + b_h[l]).  Also the model tag AutomationLabsSystems.ResNet()."""
+
+
+@dataclasses.dataclass
+class PolyNet(Fnn):
+    """PolyNet in the Fnn layout (.../polynet/mpc_modeler_implementation_polynet.jl:123-151): hidden layer p = act(W_h[l] y + b_h[l]),
+    y' = y + p + act(W_h[l] p + b_h[l]) -- the same weights twice.  Also the model tag AutomationLabsSystems.PolyNet()."""
+
+
+@dataclasses.dataclass
+class Icnn(Fnn):
+    """Input-convex network: the reference models it with the Fnn equations (its modeler is the Fnn file with the tag changed,
+    get_activation_function treats it as an Fnn: src/sub/design_mpc.jl:472-483).  Runs on the Fnn kernels."""
+
+
+# model family -> network kind of the library (_capi.NET_KINDS), by EXACT type: a subclass of Fnn is not silently an Fnn
+_NET_OF_MODEL = {Fnn: "fnn", Icnn: "fnn", ResNet: "resnet", PolyNet: "polynet"}
+_MODEL_REFUSALS = {
+    "DenseNet": "its layer widths grow (y_j has j H rows), which does not fit the [L] H x H weight layout",
+    "Rbf": "its NLP modeler reuses the Fnn layer equations without the deviation and reference constraints: there is no "
+           "well-defined network to restate",
+    "NeuralODE": "its integrator lives in AutomationLabsSystems, outside the reference",
+    "Rknn1": "its integrator lives in AutomationLabsSystems, outside the reference",
+    "Rknn2": "its integrator lives in AutomationLabsSystems, outside the reference",
+    "Rknn4": "its integrator lives in AutomationLabsSystems, outside the reference",
+}
+
+
+def _net_kind(f) -> str:
+    """Network kind of a black-box model: "fnn" (Fnn, Icnn), "resnet" or "polynet"; NotImplementedError for any other family."""
+    kind = _NET_OF_MODEL.get(type(f))
+    if kind is None:
+        name = type(f).__name__
+        why = _MODEL_REFUSALS.get(name, "only the Fnn, Icnn, ResNet and PolyNet families are built")
+        raise NotImplementedError(f"black-box model family {name!r} is not supported: {why}")
+    return kind
+
+
+@dataclasses.dataclass
 class ConstrainedBlackBoxControlDiscreteSystem:
     """Stand-in for MathematicalSystems.ConstrainedBlackBoxControlDiscreteSystem(f, statedim, inputdim, X, U)."""
     f: Fnn
@@ -95,7 +136,7 @@ def proceed_system_linearization(system: ConstrainedBlackBoxControlDiscreteSyste
     Computed on the GPU (k_fnn_jacobian)."""
     f = system.f
     A, B = _capi.fnn_linearize(f.W_in, f.W_h, f.b_h, f.W_out, np.asarray(state, dtype=np.float64).reshape(1, -1),
-                               np.asarray(input, dtype=np.float64).reshape(1, -1), act=f.act, device=device)
+                               np.asarray(input, dtype=np.float64).reshape(1, -1), act=f.act, device=device, net=_net_kind(f))
     return ConstrainedLinearControlDiscreteSystem(A[0], B[0], system.X, system.U)
 
 
@@ -206,7 +247,7 @@ def _model_predictive_control_design(system, horizon: int, sample_time: int, ref
 
 def _design_blackbox(system: ConstrainedBlackBoxControlDiscreteSystem, horizon: int, sample_time: int,
                      references: ReferencesStateInput, **kws_):
-    """Black-box (Fnn) model, LinearProgramming branch (src/sub/design_mpc.jl:143-225 ->
+    """Black-box (Fnn, Icnn, ResNet, PolyNet) model, LinearProgramming branch (src/sub/design_mpc.jl:143-225 ->
     .../fnn/mpc_modeler_implementation_fnn.jl:23-58): dynamics linearised at the FIRST reference, terminal weight
     P = DARE at the linearisation about the LAST reference (src/sub/design_mpc.jl:312-327), then the linear path.
 
@@ -218,8 +259,7 @@ def _design_blackbox(system: ConstrainedBlackBoxControlDiscreteSystem, horizon: 
     lin_mode = kws.get("mpc_linearization", "reference")
     if lin_mode not in ("reference", "step"):
         raise ValueError("mpc_linearization must be 'reference' or 'step'")
-    if not isinstance(system.f, Fnn):
-        raise NotImplementedError("only the Fnn model family is built (SURVEY.md section 2, components 8-14 are out of scope)")
+    net = _net_kind(system.f)   # Fnn, Icnn, ResNet, PolyNet; the other families raise NotImplementedError with the reason
     dev = int(kws.get("mpc_device", 0))
     x_ref, u_ref = np.asarray(references.x, dtype=np.float64), np.asarray(references.u, dtype=np.float64)
     lin_first = proceed_system_linearization(system, x_ref[:, 0], u_ref[:, 0], device=dev)
@@ -242,7 +282,7 @@ def _design_blackbox(system: ConstrainedBlackBoxControlDiscreteSystem, horizon: 
             mod.solver._check(mod.solver.L.almpc_set_structured_fallback(mod.solver.h, 0))
         # device-resident pipeline (almpc_relin_fnn_*): Jacobians -> per-instance designs -> step, no host pointers per step
         mod.solver.relin_fnn_setup(f.W_in, f.W_h, f.b_h, f.W_out, references.x, references.u, weights.Q, weights.R, weights.S, np.array(P),
-                                   system.U.low, system.U.high, act=f.act, rho=float(sopt.get("rho", 0.1)),
+                                   system.U.low, system.U.high, act=f.act, net=net, rho=float(sopt.get("rho", 0.1)),
                                    sigma=float(sopt.get("sigma", 1e-6)), rho_profile=kws.get("mpc_rho_profile", "scalar"),
                                    xmin=system.X.low if state_box else None, xmax=system.X.high if state_box else None,
                                    terminal="equality" if term_eq else "none")
@@ -251,7 +291,7 @@ def _design_blackbox(system: ConstrainedBlackBoxControlDiscreteSystem, horizon: 
 
 
 def _design_blackbox_nonlinear(system, horizon, sample_time, references, weights, P, kws):
-    """Black-box (Fnn) model, NonLinearProgramming branch (.../fnn/mpc_modeler_implementation_fnn.jl:73-189): the network itself
+    """Black-box (Fnn, Icnn, ResNet, PolyNet) model, NonLinearProgramming branch (.../fnn/mpc_modeler_implementation_fnn.jl:73-189): the network itself
     is the equality constraint x[:,k+1] = fnn(x[:,k], u[:,k]) and the reference gives the NLP to Ipopt
     (src/sub/solver_selection.jl:100-104).  Here the same NLP goes through the device-resident SQP loop (almpc_sqp_fnn_*).
     Keys of this build: mpc_sqp_iterations (outer iterations per calculate!, default 10), mpc_sqp_step (step length, default 1),
@@ -289,7 +329,7 @@ def _design_blackbox_nonlinear(system, horizon, sample_time, references, weights
     sopt = dict(kws.get("mpc_solver_options", {}))
     solver = _capi.Solver(n, m, horizon, batch, device=int(kws.get("mpc_device", 0)), timing=bool(kws.get("mpc_timing", False)))
     solver.sqp_fnn_setup(f.W_in, f.W_h, f.b_h, f.W_out, x_ref, u_ref, weights.Q, weights.R, weights.S, P, system.U.low, system.U.high,
-                         act=f.act, rho=float(sopt.get("rho", 0.1)), sigma=float(sopt.get("sigma", 1e-6)),
+                         act=f.act, net=_net_kind(f), rho=float(sopt.get("rho", 0.1)), sigma=float(sopt.get("sigma", 1e-6)),
                          rho_profile=kws.get("mpc_rho_profile", "scalar"),
                          xmin=system.X.low if state_box else None, xmax=system.X.high if state_box else None,
                          terminal="equality" if terminal == "equality" else "none",

@@ -112,7 +112,7 @@ struct almpc_handle {
     // SQP outer loop for a black-box Fnn model (almpc_sqp_fnn_*): the network, the stage data of the current linearisation
     struct Sqp {
         bool ready = false, started = false;
-        int H = 0, L = 0, act = 0, useR = 0, useS = 0;
+        int H = 0, L = 0, act = 0, net = 0, useR = 0, useS = 0;   // act: activation 0..4, net: NET_* (decode_net)
         long sP = 0;
         double *W_in = nullptr, *W_h = nullptr, *b_h = nullptr, *W_out = nullptr;
         double *A = nullptr, *B = nullptr, *c = nullptr, *fval = nullptr, *ebar = nullptr, *qadd = nullptr;
@@ -140,7 +140,7 @@ struct almpc_handle {
     // per-step re-linearisation of a black-box Fnn model on the device (almpc_relin_fnn_*, BASELINE configs[3])
     struct Relin {
         bool ready = false;
-        int H = 0, L = 0, act = 0, useR = 0, useS = 0;
+        int H = 0, L = 0, act = 0, net = 0, useR = 0, useS = 0;
         double *W_in = nullptr, *W_h = nullptr, *b_h = nullptr, *W_out = nullptr;
         double *ulin = nullptr;   // [batch][m] linearisation input of every instance (the first input reference)
         double *Q = nullptr, *R = nullptr, *S = nullptr;
@@ -1502,29 +1502,49 @@ DesignStrides batched_strides(const almpc_handle* h, bool p_inst) {
     return ds;
 }
 
-// Jacobians of an Fnn at p.batch points: wave-per-point build when weights + 4 waves' buffers fit 64 KB of LDS, else one workgroup
-// per point.
-hipError_t launch_fnn_jacobian(const FnnParams& p, int num_cus, hipStream_t st) {
+// The network code of the calls that take an activation (include/almpc.h: ALMPC_NET_CODE(kind, act) = kind << 8 | act; a bare
+// activation 0..4 is an Fnn): false for an unknown kind or activation.
+static bool decode_net(int code, int* net, int* act) {
+    if (code < 0) return false;
+    const int k = code >> 8, a = code & 0xff;
+    if (k > NET_POLYNET || a > 4) return false;
+    *net = k;
+    *act = a;
+    return true;
+}
+static const char* net_name(int net) { return net == NET_RESNET ? "ResNet" : (net == NET_POLYNET ? "PolyNet" : "Fnn"); }
+
+// Jacobians of the network (kind net: NET_*) at p.batch points: wave-per-point build when weights + 4 waves' buffers fit 64 KB of
+// LDS, else one workgroup per point (the caller has checked fnn_wg_lds_doubles against 160 KB).
+hipError_t launch_fnn_jacobian(const FnnParams& p, int net, int num_cus, hipStream_t st) {
     const size_t nin = (size_t)p.n + p.m;
     // small networks (H (n + m) <= 192 entries of the Jacobian being propagated): two points per wave, one per half-wave
     // (four points per wave, a quarter-wave each: measured no better, 0.305 against 0.303 ms per SQP iteration)
     const int ppw = ((size_t)p.H * nin <= 192 && !getenv("ALMPC_FNN_ONE_POINT_PER_WAVE")) ? 2 : 1;
-    const size_t lw = fnn_w_lds_doubles(p.n, p.m, p.H, p.L, ppw) * sizeof(double);
+    const size_t lw = fnn_w_lds_doubles(p.n, p.m, p.H, p.L, ppw, net) * sizeof(double);
     if (lw <= 64 * 1024 && !getenv("ALMPC_FNN_WG")) {
         int wgs = (p.batch + FNN_W_WAVES * ppw - 1) / (FNN_W_WAVES * ppw);
         const int cap = num_cus * 8;  // 32 waves per CU: a point is a latency chain on one wave (18 us); 16 waves per CU took 55 us for the
                                       // 12800 points of an SQP iteration, 32 take 48 (52 workgroups per CU: 49.5)
         if (wgs > cap) wgs = cap;
-        if (ppw == 2) hipLaunchKernelGGL((k_fnn_jacobian_w<32>), dim3(wgs), dim3(64 * FNN_W_WAVES), lw, st, p);
-        else hipLaunchKernelGGL((k_fnn_jacobian_w<64>), dim3(wgs), dim3(64 * FNN_W_WAVES), lw, st, p);
+        const dim3 g(wgs), blk(64 * FNN_W_WAVES);
+        if (net == NET_RESNET) {
+            if (ppw == 2) hipLaunchKernelGGL((k_net_jacobian_w<NET_RESNET, 32>), g, blk, lw, st, p);
+            else hipLaunchKernelGGL((k_net_jacobian_w<NET_RESNET, 64>), g, blk, lw, st, p);
+        } else if (net == NET_POLYNET) {
+            if (ppw == 2) hipLaunchKernelGGL((k_net_jacobian_w<NET_POLYNET, 32>), g, blk, lw, st, p);
+            else hipLaunchKernelGGL((k_net_jacobian_w<NET_POLYNET, 64>), g, blk, lw, st, p);
+        } else if (ppw == 2) hipLaunchKernelGGL((k_fnn_jacobian_w<32>), g, blk, lw, st, p);
+        else hipLaunchKernelGGL((k_fnn_jacobian_w<64>), g, blk, lw, st, p);
         return hipGetLastError();
     }
-    const size_t lds = (2 * (size_t)p.H + 2 * (size_t)p.H * nin + nin) * sizeof(double);
+    const size_t lds = fnn_wg_lds_doubles(p.n, p.m, p.H, net) * sizeof(double);
+    void (*kern)(FnnParams) = net == NET_RESNET ? k_net_jacobian<NET_RESNET> : (net == NET_POLYNET ? k_net_jacobian<NET_POLYNET> : k_fnn_jacobian);
     if (lds > 64 * 1024) {
-        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_fnn_jacobian), (size_t)(lds));
+        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), (size_t)(lds));
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_fnn_jacobian, dim3(p.batch), dim3(256), lds, st, p);
+    hipLaunchKernelGGL(kern, dim3(p.batch), dim3(256), lds, st, p);
     return hipGetLastError();
 }
 
@@ -1581,8 +1601,10 @@ hipError_t launch_design_ltv(almpc_handle* h, const DesignLtvParams& lp, hipStre
     return hipGetLastError();
 }
 
-// whether k_design_instance_t can linearise the network itself (LDS route with room for the weights and one wave's scratch)
-bool design_fuses_fnn(const almpc_handle* h, int H, int L) {
+// whether k_design_instance_t can linearise the network itself (LDS route with room for the weights and one wave's scratch).  An Fnn
+// only: a ResNet / PolyNet is linearised by k_net_jacobian_w in front of the design (the design kernel keeps its Fnn head and code).
+bool design_fuses_fnn(const almpc_handle* h, int H, int L, int net) {
+    if (net != NET_FNN) return false;
     const size_t lds = (design_instance_lds_doubles(h->n, h->m, h->N) + fnn_weights_doubles(h->n, h->m, H, L) + fnn_wave_scratch_doubles(h->n, h->m, H)) * sizeof(double);
     return lds <= 160 * 1024 && !getenv("ALMPC_DBG_SPLIT_JACOBIAN");
 }
@@ -1903,12 +1925,12 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
 namespace {
 // almpc_relin_fnn_setup on an ALMPC_FLAG_STRUCTURED handle: network, references and weights on the device, the per-instance model and
 // terminal-weight slots, and the stage-wise solver's per-instance set-up (records per stage: the terminal weight is the caller's P).
-int relin_setup_structured(almpc_handle* h, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
+int relin_setup_structured(almpc_handle* h, int H, int L, int net, int activation, const double* W_in, const double* W_h, const double* b_h,
                            const double* W_out, const double* xref, const double* uref, const double* Q, const double* R, const double* S,
                            const double* P, const double* umin, const double* umax) {
     const int n = h->n, m = h->m, N = h->N, nz = h->nz;
     const size_t b = (size_t)h->batch, nin = (size_t)n + m;
-    if ((2 * (size_t)H + 2 * (size_t)H * nin + nin) * sizeof(double) > 160 * 1024)
+    if (fnn_wg_lds_doubles(n, m, H, net) * sizeof(double) > 160 * 1024)
         return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup: the network's forward-mode Jacobian must fit the 160 KB of LDS");
     for (int i = 0; i < m; ++i)
         if (!(umin[i] <= umax[i])) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: umin > umax");
@@ -1966,7 +1988,7 @@ int relin_setup_structured(almpc_handle* h, int H, int L, int activation, const 
     h->has_box = h->boxmin.empty() ? 0 : 1;
     for (auto& e : q.ev)
         if (!e) HIP_TRY(h, hipEventCreate(&e));
-    q.H = H; q.L = L; q.act = activation; q.have_prev = false; q.useR = Rm[0] != 0.0; q.useS = useS;
+    q.H = H; q.L = L; q.act = activation; q.net = net; q.have_prev = false; q.useR = Rm[0] != 0.0; q.useS = useS;
     if (!q.u0) HIP_TRY(h, dalloc(&q.u0, b * m));
     if (!q.xnext) HIP_TRY(h, dalloc(&q.xnext, b * n));
     h->r_has_step = false;
@@ -2051,12 +2073,14 @@ int almpc_relin_fnn_setup(almpc_handle* h, int H, int L, int activation, const d
     if (H < 1 || L < 0 || !W_in || !W_out || (L > 0 && (!W_h || !b_h)) || !Q || !R || !P || !umin || !umax)
         return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: null pointer or bad network shape (P must be given: the terminal weight "
                                           "comes from the linearisation at the last reference, src/sub/design_mpc.jl:312-327)");
-    if (activation < 0 || activation > 4) return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup: activation must be 0..4");
-    if (h->structured) return relin_setup_structured(h, H, L, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, umin, umax);
+    int net = NET_FNN;
+    if (!decode_net(activation, &net, &activation))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup: activation must be ALMPC_NET_CODE(kind 0..2, activation 0..4)");
+    if (h->structured) return relin_setup_structured(h, H, L, net, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, umin, umax);
     if (!(rho > 0.0) || !(sigma >= 0.0)) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: rho must be > 0 and sigma >= 0");
     const int n = h->n, m = h->m, N = h->N, nz = h->nz;
     const size_t b = (size_t)h->batch, nin = (size_t)n + m;
-    if ((2 * (size_t)H + 2 * (size_t)H * nin + nin) * sizeof(double) > 160 * 1024)
+    if (fnn_wg_lds_doubles(n, m, H, net) * sizeof(double) > 160 * 1024)
         return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup: the network's forward-mode Jacobian must fit the 160 KB of LDS");
     for (int i = 0; i < m; ++i)
         if (!(umin[i] <= umax[i])) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: umin > umax");
@@ -2117,7 +2141,7 @@ int almpc_relin_fnn_setup(almpc_handle* h, int H, int L, int activation, const d
     h->xref_stride = 0; h->uref_stride = 0; h->fS_stride = nz;
     for (auto& e : q.ev)
         if (!e) HIP_TRY(h, hipEventCreate(&e));
-    q.H = H; q.L = L; q.act = activation; q.have_prev = false;
+    q.H = H; q.L = L; q.act = activation; q.net = net; q.have_prev = false;
     if (!q.u0) HIP_TRY(h, dalloc(&q.u0, b * m));
     if (!q.xnext) HIP_TRY(h, dalloc(&q.xnext, b * n));
     h->P = Pm; h->hS = Sm; h->useS = q.useS;
@@ -2168,7 +2192,7 @@ int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
         // unconstrained problem (k_sgains) -> the stage-wise dual active set (k_sdual), warm-started from the previous step's inputs
         // shifted by one stage when opts->warm_start is set.  No Hessian is formed: the reference's Fnn-LP delegation has no horizon
         // limit (.../fnn/mpc_modeler_implementation_fnn.jl:23-58) and neither has this route.
-        HIP_TRY(h, launch_fnn_jacobian(fp, h->num_cus, st));
+        HIP_TRY(h, launch_fnn_jacobian(fp, q.net, h->num_cus, st));
         if (timing) HIP_TRY(h, hipEventRecord(q.ev[1], st));
         HIP_TRY(h, launch_sgains(h, 0));
         if (timing) HIP_TRY(h, hipEventRecord(q.ev[2], st));
@@ -2183,8 +2207,8 @@ int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
         if (timing) HIP_TRY(h, hipEventRecord(q.ev[3], st));
         return ALMPC_OK;
     }
-    const bool fuse_jac = design_fuses_fnn(h, q.H, q.L);   // the design kernel's workgroups linearise their own instance
-    if (!fuse_jac) HIP_TRY(h, launch_fnn_jacobian(fp, h->num_cus, st));
+    const bool fuse_jac = design_fuses_fnn(h, q.H, q.L, q.net);   // the design kernel's workgroups linearise their own instance
+    if (!fuse_jac) HIP_TRY(h, launch_fnn_jacobian(fp, q.net, h->num_cus, st));
     if (timing) HIP_TRY(h, hipEventRecord(q.ev[1], st));
     // 2. the reference's QP for every (A_i, B_i): H_i, F_i, scaling, inverses, V_i; reference-dependent vectors.  A warm step
     // (opts.warm_start = 1 after a solved step) takes its working-set guess from the previous step's inputs shifted by one stage
@@ -2253,7 +2277,7 @@ int almpc_relin_fnn_advance(almpc_handle* h) {
     // lazily deferred redo of that step still needs)
     if (!q.Ascr) { HIP_TRY(h, dalloc(&q.Ascr, (size_t)h->batch * n * n)); HIP_TRY(h, dalloc(&q.Bscr, (size_t)h->batch * n * m)); }
     fp.A = q.Ascr; fp.B = q.Bscr; fp.f = q.xnext;
-    HIP_TRY(h, launch_fnn_jacobian(fp, h->num_cus, st));
+    HIP_TRY(h, launch_fnn_jacobian(fp, q.net, h->num_cus, st));
     if (h->io.x0_slot >= 0) {   // a pinned x0 slot was read once more by the forward pass: free for the host only after it
         HIP_TRY(h, hipEventRecord(h->io.ev_used[h->io.x0_slot], st));
         h->io.used_pending[h->io.x0_slot] = true;
@@ -2288,7 +2312,9 @@ int almpc_sqp_fnn_setup(almpc_handle* h, int H, int L, int activation, const dou
     drop_lazy_redo(h);
     if (H < 1 || L < 0 || !W_in || !W_out || (L > 0 && (!W_h || !b_h)) || !Q || !R || !P || !umin || !umax)
         return fail(h, ALMPC_ERR_INVALID, "sqp_fnn_setup: null pointer or bad network shape (P must be given)");
-    if (activation < 0 || activation > 4) return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_setup: activation must be 0..4");
+    int net = NET_FNN;
+    if (!decode_net(activation, &net, &activation))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_setup: activation must be ALMPC_NET_CODE(kind 0..2, activation 0..4)");
     if (!(rho > 0.0) || !(sigma >= 0.0)) return fail(h, ALMPC_ERR_INVALID, "sqp_fnn_setup: rho must be > 0 and sigma >= 0");
     const int n = h->n, m = h->m, N = h->N, nz = h->nz, nzs = h->nzs;
     const size_t b = (size_t)h->batch, nin = (size_t)n + m;
@@ -2385,7 +2411,7 @@ int almpc_sqp_fnn_setup(almpc_handle* h, int H, int L, int activation, const dou
         HIP_TRY(h, hipMemset(h->bA, 0, b * n * n * sizeof(double)));
         HIP_TRY(h, hipMemset(h->bB, 0, b * n * m * sizeof(double)));
     }
-    q.H = H; q.L = L; q.act = activation; q.useR = Rm[0] != 0.0; q.useS = q.useR && Sm[0] != 0.0; q.sP = p_inst ? (long)n * n : 0;
+    q.H = H; q.L = L; q.act = activation; q.net = net; q.useR = Rm[0] != 0.0; q.useS = q.useR && Sm[0] != 0.0; q.sP = p_inst ? (long)n * n : 0;
     h->P.assign(Pall.begin(), Pall.begin() + (size_t)n * n);
     h->hS = Sm;
     h->useS = q.useS;
@@ -2469,8 +2495,9 @@ int almpc_sqp_fnn_start(almpc_handle* h, const double* x0, const double* u_guess
     rp.n = n; rp.m = m; rp.H = q.H; rp.L = q.L; rp.act = q.act; rp.N = N;
     rp.W_in = q.W_in; rp.W_h = q.W_h; rp.b_h = q.b_h; rp.W_out = q.W_out; rp.x0 = h->dX0; rp.ubar = h->dUref; rp.xbar = h->dXref;
     const size_t l = (2 * (size_t)q.H + n + m) * sizeof(double);
-    if (l > 64 * 1024) HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_fnn_rollout), (size_t)(l)));
-    hipLaunchKernelGGL(k_fnn_rollout, dim3((unsigned)b), dim3(256), l, st, rp);
+    void (*roll)(FnnRolloutParams) = q.net == NET_RESNET ? k_net_rollout<NET_RESNET> : (q.net == NET_POLYNET ? k_net_rollout<NET_POLYNET> : k_fnn_rollout);
+    if (l > 64 * 1024) HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(roll), (size_t)(l)));
+    hipLaunchKernelGGL(roll, dim3((unsigned)b), dim3(256), l, st, rp);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemsetAsync(q.bad, 0, b * sizeof(int), st));
     {
@@ -2505,8 +2532,10 @@ static int sqp_exact_check(almpc_handle* h) {
     if (h->mc > 0) return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian: no state rows (their multipliers would enter the adjoint)");
     if (q.act == 1) return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian: relu makes the NLP non-smooth");
     if (h->nz > 128) return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian: nz <= 128");
-    if (4 * fnn_hess_wave_doubles(h->n, h->m, q.H, q.L) * sizeof(double) > 64 * 1024 ||
-        sqp_exact_lds_doubles(h->n, h->m, h->nz) * sizeof(double) > 64 * 1024)
+    if (4 * fnn_hess_wave_doubles(h->n, h->m, q.H, q.L, q.net) * sizeof(double) > 64 * 1024)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, std::string("sqp exact Hessian: the ") + net_name(q.net) +
+                                                  " network's per-wave scratch (its activation sites' Jacobians) must fit 16 KB of LDS");
+    if (sqp_exact_lds_doubles(h->n, h->m, h->nz) * sizeof(double) > 64 * 1024)
         return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian: the network / stage scratch must fit 64 KB of LDS");
     return ALMPC_OK;
 }
@@ -2645,7 +2674,7 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
         hp.done = sv ? sv->done : nullptr; hp.W = q.Wlag;
         xp.n = n; xp.m = m; xp.N = N; xp.nz = nz; xp.A = q.A; xp.B = q.B; xp.c = q.c; xp.W = q.Wlag; xp.ubar = h->dUref;
         xp.umin = h->dUmin; xp.umax = h->dUmax; xp.done = sv ? sv->done : nullptr; xp.H = h->bH; xp.q = h->bQ;
-        hess_lds = 4 * fnn_hess_wave_doubles(n, m, q.H, q.L) * sizeof(double);
+        hess_lds = 4 * fnn_hess_wave_doubles(n, m, q.H, q.L, q.net) * sizeof(double);
         exact_lds = sqp_exact_lds_doubles(n, m, nz) * sizeof(double);
     }
     // register-tile design kernel: scaling, scaled gradient and the flag reset ride along as its tail (three launches less per iteration)
@@ -2660,11 +2689,13 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
             HIP_TRY(h, hipEventSynchronize(sv->ev[(it - 2) & 3]));
             if (sv->live_pin[(it - 2) & 3] == 0) { all_done = true; break; }
         }
-        HIP_TRY(h, launch_fnn_jacobian(fp, h->num_cus, st));
+        HIP_TRY(h, launch_fnn_jacobian(fp, q.net, h->num_cus, st));
         if (sv) HIP_TRY(h, kkt_test(it));
         if (exact) {   // multipliers (from the test above, or the walk alone), then the stage Lagrangian Hessians at the iterate
             if (!sv) hipLaunchKernelGGL(k_sqp_kkt, dim3((unsigned)b), dim3(256), step_lds, st, kp);
-            hipLaunchKernelGGL(k_fnn_lag_hessian, dim3((unsigned)((b * N + 3) / 4)), dim3(256), hess_lds, st, hp);
+            void (*hk)(FnnHessParams) = q.net == NET_RESNET ? k_net_lag_hessian<NET_RESNET>
+                                                          : (q.net == NET_POLYNET ? k_net_lag_hessian<NET_POLYNET> : k_fnn_lag_hessian);
+            hipLaunchKernelGGL(hk, dim3((unsigned)((b * N + 3) / 4)), dim3(256), hess_lds, st, hp);
             HIP_TRY(h, hipGetLastError());
         }
         if (!prep_in_design) hipLaunchKernelGGL(k_sqp_prepare, dim3((unsigned)b), dim3(256), 0, st, sp);
@@ -2721,7 +2752,7 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
         HIP_TRY(h, hipGetLastError());
     }
     if (sv && !all_done) {   // the last test, at the final iterate
-        HIP_TRY(h, launch_fnn_jacobian(fp, h->num_cus, st));
+        HIP_TRY(h, launch_fnn_jacobian(fp, q.net, h->num_cus, st));
         HIP_TRY(h, kkt_test(iters));
     }
     if (sv) return almpc_synchronize(h);   // (per-instance verdicts instead of ALMPC_ERR_NUMERIC; no histories)
@@ -3492,10 +3523,10 @@ int almpc_fnn_linearize(int device_id, int n, int m, int H, int L, int activatio
                         double* B, double* f) {
     if (n < 1 || m < 1 || H < 1 || L < 0 || batch < 1 || !W_in || !W_out || !x || !u || !A || !B || (L > 0 && (!W_h || !b_h)))
         return ALMPC_ERR_INVALID;
-    if (activation < 0 || activation > 4) return ALMPC_ERR_UNSUPPORTED;
+    int net = NET_FNN;
+    if (!decode_net(activation, &net, &activation)) return ALMPC_ERR_UNSUPPORTED;
     const size_t nin = (size_t)n + m;
-    const size_t lds = (2 * (size_t)H + 2 * (size_t)H * nin + nin) * sizeof(double);
-    if (lds > 160 * 1024) return ALMPC_ERR_UNSUPPORTED;
+    if (fnn_wg_lds_doubles(n, m, H, net) * sizeof(double) > 160 * 1024) return ALMPC_ERR_UNSUPPORTED;
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || device_id < 0 || device_id >= count) return ALMPC_ERR_NO_DEVICE;
     if (hipSetDevice(device_id) != hipSuccess) return ALMPC_ERR_HIP;
@@ -3519,7 +3550,7 @@ int almpc_fnn_linearize(int device_id, int n, int m, int H, int L, int activatio
     if (rc == ALMPC_OK) {
         hipDeviceProp_t prop;
         const int cus = hipGetDeviceProperties(&prop, device_id) == hipSuccess ? prop.multiProcessorCount : 256;
-        if (launch_fnn_jacobian(p, cus, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = ALMPC_ERR_HIP;
+        if (launch_fnn_jacobian(p, net, cus, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = ALMPC_ERR_HIP;
     }
     if (rc == ALMPC_OK) {
         if (hipMemcpy(A, p.A, (size_t)batch * n * n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||

@@ -5,10 +5,20 @@
 // src/sub/design_mpc.jl:319-326), for the Fnn layout the reference reads from Flux.params (.../fnn/...:88-107, 127-144):
 //     y1 = W_in [x;u] (no bias, no activation);  yj = act(W_h[j-2] y(j-1) + b_h[j-2]);  x+ = W_out y(L+1) (no bias).
 // One workgroup (256 threads) per linearisation point; the H x (n+m) forward-mode Jacobian lives in LDS.
+//
+// The same weight layout serves the ResNet and PolyNet families (.../resnet/...:131-140, .../polynet/...:132-148); only the hidden
+// layer differs (W = W_h[l], b = b_h[l], a = W y + b):
+//     Fnn      y' = act(a)                                           J' = diag(act'(a)) W J
+//     ResNet   y' = y + act(a)                                       J' = J + diag(act'(a)) W J
+//     PolyNet  p = act(a1), y' = y + p + act(W p + b)  (same W, b)   P = diag(act'(a1)) W J,  J' = J + P + diag(act'(a2)) W P
+// ResNet and PolyNet run in kernels templated on the kind (k_net_*<NET_*>); the Fnn kernels keep their names and their code
+// (and so their ISA: DESIGN.md, "ResNet and PolyNet models").
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace almpc {
+
+constexpr int NET_FNN = 0, NET_RESNET = 1, NET_POLYNET = 2;   // include/almpc.h ALMPC_NET_*
 
 struct FnnParams {
     int n, m, H, L, act;  // act: 0 identity, 1 relu, 2 tanh, 3 sigmoid, 4 swish (x*sigmoid(x)): NNlib's names
@@ -34,6 +44,12 @@ __device__ __forceinline__ void fnn_act(int act, double a, double& val, double& 
         case 4: { const double s = 1.0 / (1.0 + exp(-a)); val = a * s; der = s * (1.0 + a * (1.0 - s)); break; }
         default: val = a; der = 1.0; break;
     }
+}
+
+// LDS of the workgroup build: y, yn | J, Jn | z (+ p: PolyNet)
+__host__ __device__ inline size_t fnn_wg_lds_doubles(int n, int m, int H, int net = NET_FNN) {
+    const size_t nin = (size_t)n + m;
+    return 2 * (size_t)H + 2 * (size_t)H * nin + nin + (net == NET_POLYNET ? (size_t)H : 0);
 }
 
 inline __global__ __launch_bounds__(256) void k_fnn_jacobian(FnnParams p) {
@@ -97,16 +113,111 @@ inline __global__ __launch_bounds__(256) void k_fnn_jacobian(FnnParams p) {
         }
 }
 
+// ResNet / PolyNet (a kernel of its own: k_fnn_jacobian above keeps its name and its code)
+template <int NET>
+__global__ __launch_bounds__(256) void k_net_jacobian(FnnParams p) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int n = p.n, m = p.m, H = p.H, nin = n + m;
+    double* y = smem;             // [H]
+    double* yn = y + H;           // [H]
+    double* J = yn + H;           // [H][nin]  (row-major: J[i*nin + c])
+    double* Jn = J + (size_t)H * nin;
+    double* z = Jn + (size_t)H * nin;  // [nin]
+    double* pv = z + nin;         // [H] PolyNet: p = act(a1)
+    const int inst = blockIdx.x;
+    const double* xp = p.x + (size_t)(inst / p.ppi) * p.xs_group + (size_t)(inst % p.ppi) * n;
+    const double* up = p.u + (size_t)(inst / p.ppi) * p.us_group + (size_t)(inst % p.ppi) * m;
+    for (int t = threadIdx.x; t < nin; t += blockDim.x) z[t] = t < n ? xp[t] : up[t - n];
+    __syncthreads();
+    for (int i = threadIdx.x; i < H; i += blockDim.x) {
+        double s = 0.0;
+        for (int c = 0; c < nin; ++c) s += p.W_in[(size_t)c * H + i] * z[c];
+        y[i] = s;
+    }
+    for (int t = threadIdx.x; t < H * nin; t += blockDim.x) J[t] = p.W_in[(size_t)(t % nin) * H + t / nin];
+    __syncthreads();
+    for (int l = 0; l < p.L; ++l) {
+        const double* W = p.W_h + (size_t)l * H * H;
+        const double* b = p.b_h + (size_t)l * H;
+        for (int i = threadIdx.x; i < H; i += blockDim.x) {
+            double s = b[i];
+            for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * y[j];
+            yn[i] = s;  // pre-activation
+        }
+        __syncthreads();
+        for (int t = threadIdx.x; t < H * nin; t += blockDim.x) {
+            const int i = t / nin, c = t % nin;
+            double s = 0.0;
+            for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * J[(size_t)j * nin + c];
+            double val, der;
+            fnn_act(p.act, yn[i], val, der);
+            if constexpr (NET == NET_RESNET) Jn[t] = J[t] + (der == 0.0 ? 0.0 : der * s);
+            else Jn[t] = der == 0.0 ? 0.0 : der * s;   // (PolyNet: P)
+        }
+        __syncthreads();
+        if constexpr (NET == NET_POLYNET) {
+            for (int i = threadIdx.x; i < H; i += blockDim.x) {
+                double val, der;
+                fnn_act(p.act, yn[i], val, der);
+                pv[i] = val;
+            }
+            __syncthreads();
+            for (int i = threadIdx.x; i < H; i += blockDim.x) {
+                double s = b[i];
+                for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * pv[j];
+                yn[i] = s;  // second pre-activation a2 (a1 is not read any more)
+            }
+            __syncthreads();
+            for (int t = threadIdx.x; t < H * nin; t += blockDim.x) {   // (J[t] is read and written by its own thread only)
+                const int i = t / nin, c = t % nin;
+                double s = 0.0;
+                for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * Jn[(size_t)j * nin + c];
+                double val, der;
+                fnn_act(p.act, yn[i], val, der);
+                J[t] = J[t] + Jn[t] + (der == 0.0 ? 0.0 : der * s);
+            }
+            for (int i = threadIdx.x; i < H; i += blockDim.x) {
+                double val, der;
+                fnn_act(p.act, yn[i], val, der);
+                y[i] = y[i] + pv[i] + val;
+            }
+            __syncthreads();
+        } else {
+            for (int i = threadIdx.x; i < H; i += blockDim.x) {
+                double val, der;
+                fnn_act(p.act, yn[i], val, der);
+                if constexpr (NET == NET_RESNET) y[i] = y[i] + val;
+                else y[i] = val;
+            }
+            for (int t = threadIdx.x; t < H * nin; t += blockDim.x) J[t] = Jn[t];
+            __syncthreads();
+        }
+    }
+    for (int t = threadIdx.x; t < n * nin; t += blockDim.x) {
+        const int i = t % n, c = t / n;
+        double s = 0.0;
+        for (int j = 0; j < H; ++j) s += p.W_out[(size_t)j * n + i] * J[(size_t)j * nin + c];
+        if (c < n) p.A[(size_t)inst * n * n + (size_t)c * n + i] = s;
+        else p.B[(size_t)inst * n * m + (size_t)(c - n) * n + i] = s;
+    }
+    if (p.f)
+        for (int i = threadIdx.x; i < n; i += blockDim.x) {
+            double s = 0.0;
+            for (int j = 0; j < H; ++j) s += p.W_out[(size_t)j * n + i] * y[j];
+            p.f[(size_t)inst * n + i] = s;
+        }
+}
+
 // Wave-per-point build for small networks (the SQP loop linearises batch x N points per iteration): the weights are staged in
 // LDS once per workgroup and shared by its 4 waves, every wave walks its own points with wave-local LDS buffers and no
 // workgroup barrier inside the loop.  Same arithmetic, same summation order as k_fnn_jacobian (bit-identical results).
 constexpr int FNN_W_WAVES = 4;
 
 // (ppw: points per wave and pass, 1 or 2: see fnn_jacobian_point)
-__host__ __device__ inline size_t fnn_w_lds_doubles(int n, int m, int H, int L, int ppw = 1) {
+__host__ __device__ inline size_t fnn_w_lds_doubles(int n, int m, int H, int L, int ppw = 1, int net = NET_FNN) {
     const size_t nin = (size_t)n + m;
     const size_t weights = (size_t)H * nin + (size_t)L * H * H + (size_t)L * H + (size_t)n * H;
-    const size_t per_wave = 2 * (size_t)H + 2 * (size_t)H * nin + nin;
+    const size_t per_wave = 2 * (size_t)H + 2 * (size_t)H * nin + nin + (net == NET_POLYNET ? (size_t)H : 0);
     return weights + FNN_W_WAVES * ppw * per_wave;
 }
 
@@ -125,7 +236,10 @@ __device__ __forceinline__ void fnn_stage_weights(const FnnParams& p, double* sm
 __host__ __device__ inline size_t fnn_weights_doubles(int n, int m, int H, int L) {
     return (size_t)H * (n + m) + (size_t)L * H * H + (size_t)L * H + (size_t)n * H;
 }
-__host__ __device__ inline size_t fnn_wave_scratch_doubles(int n, int m, int H) { return 2 * (size_t)H + 2 * (size_t)H * (n + m) + (n + m); }
+// (PolyNet: one H vector more, p)
+__host__ __device__ inline size_t fnn_wave_scratch_doubles(int n, int m, int H, int net = NET_FNN) {
+    return 2 * (size_t)H + 2 * (size_t)H * (n + m) + (n + m) + (net == NET_POLYNET ? (size_t)H : 0);
+}
 
 // Jacobians (and value) of the network at ONE point by ONE wave: weights staged at `wsm` (fnn_stage_weights), `y` = the wave's own
 // scratch (fnn_wave_scratch_doubles).  Also the tail of nothing and the head of k_design_instance_t in the re-linearisation
@@ -133,7 +247,7 @@ __host__ __device__ inline size_t fnn_wave_scratch_doubles(int n, int m, int H) 
 // LW: lanes per point (64: the wave works on one point; 32: each half-wave on its own -- small networks leave most lanes of a wave
 // idle, and a point is a latency chain: two at a time halve the passes).  inst_ may lie beyond the batch (its half then computes on
 // point 0 and stores nothing); lane: the lane within the point's LW lanes; y: the point's own scratch.
-template <int LW = 64>
+template <int LW = 64, int NET = NET_FNN>
 __device__ __forceinline__ void fnn_jacobian_point(const FnnParams& p, int inst_, int lane, const double* wsm, double* y) {
     const bool valid = inst_ < p.batch;
     const int inst = valid ? inst_ : 0;
@@ -146,6 +260,7 @@ __device__ __forceinline__ void fnn_jacobian_point(const FnnParams& p, int inst_
     double* J = yn + H;                               // [H][nin] row-major
     double* Jn = J + (size_t)H * nin;
     double* z = Jn + (size_t)H * nin;
+    double* pv = z + nin;                             // [H] PolyNet: p = act(a1)
     auto wsync = []() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
     {
         const double* xp = p.x + (size_t)(inst / p.ppi) * p.xs_group + (size_t)(inst % p.ppi) * n;
@@ -174,16 +289,47 @@ __device__ __forceinline__ void fnn_jacobian_point(const FnnParams& p, int inst_
                 for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * J[(size_t)j * nin + c];
                 double val, der;
                 fnn_act(p.act, yn[i], val, der);
-                Jn[t] = der == 0.0 ? 0.0 : der * s;
+                if constexpr (NET == NET_RESNET) Jn[t] = J[t] + (der == 0.0 ? 0.0 : der * s);
+                else Jn[t] = der == 0.0 ? 0.0 : der * s;   // (PolyNet: P)
             }
             wsync();
-            for (int i = lane; i < H; i += LW) {
-                double val, der;
-                fnn_act(p.act, yn[i], val, der);
-                y[i] = val;
+            if constexpr (NET == NET_POLYNET) {   // (as fnn_jacobian_wg)
+                for (int i = lane; i < H; i += LW) {
+                    double val, der;
+                    fnn_act(p.act, yn[i], val, der);
+                    pv[i] = val;
+                }
+                wsync();
+                for (int i = lane; i < H; i += LW) {
+                    double s = b[i];
+                    for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * pv[j];
+                    yn[i] = s;
+                }
+                wsync();
+                for (int t = lane; t < H * nin; t += LW) {
+                    const int i = t / nin, c = t % nin;
+                    double s = 0.0;
+                    for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * Jn[(size_t)j * nin + c];
+                    double val, der;
+                    fnn_act(p.act, yn[i], val, der);
+                    J[t] = J[t] + Jn[t] + (der == 0.0 ? 0.0 : der * s);
+                }
+                for (int i = lane; i < H; i += LW) {
+                    double val, der;
+                    fnn_act(p.act, yn[i], val, der);
+                    y[i] = y[i] + pv[i] + val;
+                }
+                wsync();
+            } else {
+                for (int i = lane; i < H; i += LW) {
+                    double val, der;
+                    fnn_act(p.act, yn[i], val, der);
+                    if constexpr (NET == NET_RESNET) y[i] = y[i] + val;
+                    else y[i] = val;
+                }
+                for (int t = lane; t < H * nin; t += LW) J[t] = Jn[t];
+                wsync();
             }
-            for (int t = lane; t < H * nin; t += LW) J[t] = Jn[t];
-            wsync();
         }
         for (int t = lane; t < n * nin; t += LW) {
             const int i = t % n, c = t / n;
@@ -214,6 +360,19 @@ __global__ __launch_bounds__(64 * FNN_W_WAVES) void k_fnn_jacobian_w(FnnParams p
     const int stride = gridDim.x * FNN_W_WAVES * PPW;
     for (int i0 = (blockIdx.x * FNN_W_WAVES + wv) * PPW; i0 < p.batch; i0 += stride)   // (uniform trip count per wave: i0, not i0 + sub)
         fnn_jacobian_point<LW>(p, i0 + sub, hl, smem, y);
+}
+// the same for a ResNet / PolyNet (a kernel of its own: k_fnn_jacobian_w keeps its name and its code)
+template <int NET, int LW>
+__global__ __launch_bounds__(64 * FNN_W_WAVES) void k_net_jacobian_w(FnnParams p) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int PPW = 64 / LW;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, sub = lane / LW, hl = lane % LW;
+    double* y = smem + fnn_weights_doubles(p.n, p.m, p.H, p.L) + (size_t)(wv * PPW + sub) * fnn_wave_scratch_doubles(p.n, p.m, p.H, NET);
+    fnn_stage_weights(p, smem);
+    __syncthreads();
+    const int stride = gridDim.x * FNN_W_WAVES * PPW;
+    for (int i0 = (blockIdx.x * FNN_W_WAVES + wv) * PPW; i0 < p.batch; i0 += stride)
+        fnn_jacobian_point<LW, NET>(p, i0 + sub, hl, smem, y);
 }
 
 }  // namespace almpc

@@ -284,9 +284,10 @@ __device__ __forceinline__ void fnn_act2(int act, double a, double& d1, double& 
         default: d1 = 1.0; d2 = 0.0; break;
     }
 }
-__host__ __device__ inline size_t fnn_hess_wave_doubles(int n, int m, int H, int L) {
-    const size_t nin = (size_t)n + m;
-    return nin + 3 * (size_t)H + (size_t)H * nin + 2 * (size_t)L * H + (size_t)L * H * nin;
+// (activation sites: L, PolyNet 2 L -- a1 and a2 of every layer)
+__host__ __device__ inline size_t fnn_hess_wave_doubles(int n, int m, int H, int L, int net = NET_FNN) {
+    const size_t nin = (size_t)n + m, S = net == NET_POLYNET ? 2 * (size_t)L : (size_t)L;
+    return nin + 3 * (size_t)H + (size_t)H * nin + 2 * S * H + S * H * nin;
 }
 struct FnnHessParams {
     int n, m, H, L, act, N, batch;
@@ -378,6 +379,158 @@ inline __global__ __launch_bounds__(256) void k_fnn_lag_hessian(FnnHessParams p)
         const int r = e % nin, c = e / nin;
         double s = 0.0;
         for (int l = 0; l < L; ++l)
+            for (int i = 0; i < H; ++i) {
+                const double* Mi = M + ((size_t)l * H + i) * nin;
+                s += (Mi[r] * Mi[c]) * Cc[l * H + i];
+            }
+        Wo[e] = s;
+    }
+}
+
+// ResNet: one site per layer, y' = y + act(a):  J' = J + diag(act') M,  ybar = ybar' + W' (act' .* ybar'),  site weight ybar' act''.
+// PolyNet: two sites per layer, a1 = W y + b and a2 = W p + b (p = act(a1), M2 = W diag(act'(a1)) M1, J' = J + diag(act'(a1)) M1 +
+// diag(act'(a2)) M2); backwards  pbar = ybar' + W' (act'(a2) .* ybar'),  ybar = ybar' + W' (act'(a1) .* pbar),  site weights
+// ybar' act''(a2) and pbar act''(a1).  Site s of layer l is l (Fnn, ResNet) or 2 l + {0, 1} (PolyNet).
+template <int NET>
+__global__ __launch_bounds__(256) void k_net_lag_hessian(FnnHessParams p) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int SPL = NET == NET_POLYNET ? 2 : 1;   // sites per layer
+    const int n = p.n, m = p.m, H = p.H, L = p.L, S = SPL * L, nin = n + m, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double* z = smem + (size_t)wv * fnn_hess_wave_doubles(n, m, H, L, NET);
+    double* y = z + nin;                  // [H]
+    double* yb = y + H;                   // [H]
+    double* t = yb + H;                   // [H]
+    double* J = t + H;                    // [H][nin] row-major: d y / d z
+    double* Aa = J + (size_t)H * nin;     // [S][H] pre-activations
+    double* Cc = Aa + (size_t)S * H;      // [S][H] ybar * act''
+    double* M = Cc + (size_t)S * H;       // [S][H][nin] d a_s / d z
+    const long pt = (long)blockIdx.x * 4 + wv;
+    if (pt >= (long)p.batch * p.N) return;   // (wave-uniform; no workgroup barrier below)
+    const long inst = pt / p.N;
+    const int k = (int)(pt % p.N);
+    if (p.done && p.done[inst]) return;
+    auto wsync = []() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
+    for (int c = lane; c < nin; c += 64)
+        z[c] = c < n ? p.xbar[(inst * (p.N + 1) + k) * n + c] : p.ubar[(inst * p.N + k) * m + c - n];
+    wsync();
+    for (int i = lane; i < H; i += 64) {
+        double s = 0.0;
+        for (int c = 0; c < nin; ++c) s += p.W_in[(size_t)c * H + i] * z[c];
+        y[i] = s;
+    }
+    for (int e = lane; e < H * nin; e += 64) J[e] = p.W_in[(size_t)(e % nin) * H + e / nin];
+    wsync();
+    for (int l = 0; l < L; ++l) {
+        const double* W = p.W_h + (size_t)l * H * H;
+        const int s1 = SPL * l;
+        for (int i = lane; i < H; i += 64) {
+            double s = p.b_h[(size_t)l * H + i];
+            for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * y[j];
+            Aa[s1 * H + i] = s;
+        }
+        for (int e = lane; e < H * nin; e += 64) {
+            const int i = e / nin, c = e % nin;
+            double s = 0.0;
+            for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * J[(size_t)j * nin + c];
+            M[((size_t)s1 * H + i) * nin + c] = s;
+        }
+        wsync();
+        if constexpr (NET == NET_POLYNET) {   // t = p = act(a1), yb = act'(a1) (yb is free until the backward pass)
+            for (int i = lane; i < H; i += 64) {
+                double val, der;
+                fnn_act(p.act, Aa[s1 * H + i], val, der);
+                t[i] = val;
+                yb[i] = der;
+            }
+            wsync();
+            const double* M1 = M + (size_t)s1 * H * nin;
+            for (int i = lane; i < H; i += 64) {
+                double s = p.b_h[(size_t)l * H + i];
+                for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * t[j];
+                Aa[(s1 + 1) * H + i] = s;
+            }
+            for (int e = lane; e < H * nin; e += 64) {
+                const int i = e / nin, c = e % nin;
+                double s = 0.0;
+                for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * (yb[j] * M1[(size_t)j * nin + c]);
+                M[((size_t)(s1 + 1) * H + i) * nin + c] = s;
+            }
+            wsync();
+            for (int i = lane; i < H; i += 64) {
+                double val, der;
+                fnn_act(p.act, Aa[(s1 + 1) * H + i], val, der);
+                y[i] = y[i] + t[i] + val;
+            }
+            for (int e = lane; e < H * nin; e += 64) {
+                double val, der;
+                fnn_act(p.act, Aa[(s1 + 1) * H + e / nin], val, der);
+                J[e] = J[e] + yb[e / nin] * M1[e] + M[(size_t)(s1 + 1) * H * nin + e] * der;
+            }
+            wsync();
+        } else {
+            for (int i = lane; i < H; i += 64) {
+                double val, der;
+                fnn_act(p.act, Aa[s1 * H + i], val, der);
+                if constexpr (NET == NET_RESNET) y[i] = y[i] + val;
+                else y[i] = val;
+            }
+            for (int e = lane; e < H * nin; e += 64) {
+                double val, der;
+                fnn_act(p.act, Aa[s1 * H + e / nin], val, der);
+                if constexpr (NET == NET_RESNET) J[e] = J[e] + M[(size_t)s1 * H * nin + e] * der;
+                else J[e] = M[(size_t)s1 * H * nin + e] * der;
+            }
+            wsync();
+        }
+    }
+    const double* lam = p.lam + (inst * p.N + k) * (size_t)n;
+    for (int i = lane; i < H; i += 64) {
+        double s = 0.0;
+        for (int r = 0; r < n; ++r) s += p.W_out[(size_t)i * n + r] * lam[r];
+        yb[i] = s;
+    }
+    wsync();
+    for (int l = L - 1; l >= 0; --l) {
+        const double* W = p.W_h + (size_t)l * H * H;
+        const int s1 = SPL * l;
+        // ob: the adjoint of the site act(a_{s1}) -- ybar' (Fnn, ResNet) or pbar (PolyNet, in y: the forward values are not read again)
+        double* ob = yb;
+        if constexpr (NET == NET_POLYNET) {
+            for (int i = lane; i < H; i += 64) {
+                double d1, d2;
+                fnn_act2(p.act, Aa[(s1 + 1) * H + i], d1, d2);
+                Cc[(s1 + 1) * H + i] = yb[i] * d2;
+                t[i] = yb[i] * d1;
+            }
+            wsync();
+            for (int j = lane; j < H; j += 64) {
+                double s = 0.0;
+                for (int i = 0; i < H; ++i) s += W[(size_t)j * H + i] * t[i];
+                y[j] = yb[j] + s;
+            }
+            wsync();
+            ob = y;
+        }
+        for (int i = lane; i < H; i += 64) {
+            double d1, d2;
+            fnn_act2(p.act, Aa[s1 * H + i], d1, d2);
+            Cc[s1 * H + i] = ob[i] * d2;
+            t[i] = ob[i] * d1;
+        }
+        wsync();
+        for (int j = lane; j < H; j += 64) {
+            double s = 0.0;
+            for (int i = 0; i < H; ++i) s += W[(size_t)j * H + i] * t[i];
+            if constexpr (NET == NET_FNN) yb[j] = s;
+            else yb[j] = yb[j] + s;
+        }
+        wsync();
+    }
+    double* Wo = p.W + pt * (size_t)nin * nin;
+    for (int e = lane; e < nin * nin; e += 64) {
+        const int r = e % nin, c = e / nin;
+        double s = 0.0;
+        for (int l = 0; l < S; ++l)
             for (int i = 0; i < H; ++i) {
                 const double* Mi = M + ((size_t)l * H + i) * nin;
                 s += (Mi[r] * Mi[c]) * Cc[l * H + i];
@@ -523,7 +676,7 @@ inline __global__ __launch_bounds__(256) void k_sqp_exact_qp(SqpExactParams p) {
     }
 }
 
-// Single-shooting start: xbar_0 = x0, xbar_{k+1} = fnn(xbar_k, ubar_k).  One workgroup per instance, thread i owns neuron i.
+// Single-shooting start: xbar_0 = x0, xbar_{k+1} = net(xbar_k, ubar_k).  One workgroup per instance, thread i owns neuron i.
 struct FnnRolloutParams {
     int n, m, H, L, act, N;
     const double* W_in; const double* W_h; const double* b_h; const double* W_out;
@@ -568,6 +721,69 @@ inline __global__ __launch_bounds__(256) void k_fnn_rollout(FnnRolloutParams p) 
             }
             __syncthreads();
             for (int i = threadIdx.x; i < H; i += blockDim.x) y[i] = yn[i];
+            __syncthreads();
+        }
+        for (int i = threadIdx.x; i < n; i += blockDim.x) {
+            double s = 0.0;
+            for (int j = 0; j < H; ++j) s += p.W_out[(size_t)j * n + i] * y[j];
+            z[i] = s;
+            xb[(size_t)(k + 1) * n + i] = s;
+        }
+        __syncthreads();
+    }
+}
+
+// ResNet / PolyNet (k_fnn_rollout keeps its name and its code)
+template <int NET>
+__global__ __launch_bounds__(256) void k_net_rollout(FnnRolloutParams p) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int n = p.n, m = p.m, H = p.H, nin = n + m;
+    double* y = smem;        // [H]
+    double* yn = y + H;      // [H]
+    double* z = yn + H;      // [nin]
+    const size_t inst = blockIdx.x;
+    double* xb = p.xbar + inst * (size_t)(p.N + 1) * n;
+    const double* ub = p.ubar + inst * (size_t)p.N * m;
+    for (int t = threadIdx.x; t < n; t += blockDim.x) {
+        const double v = p.x0[inst * n + t];
+        z[t] = v;
+        xb[t] = v;
+    }
+    __syncthreads();
+    for (int k = 0; k < p.N; ++k) {
+        for (int t = threadIdx.x; t < m; t += blockDim.x) z[n + t] = ub[k * m + t];
+        __syncthreads();
+        for (int i = threadIdx.x; i < H; i += blockDim.x) {
+            double s = 0.0;
+            for (int c = 0; c < nin; ++c) s += p.W_in[(size_t)c * H + i] * z[c];
+            y[i] = s;
+        }
+        __syncthreads();
+        for (int l = 0; l < p.L; ++l) {
+            const double* W = p.W_h + (size_t)l * H * H;
+            const double* b = p.b_h + (size_t)l * H;
+            for (int i = threadIdx.x; i < H; i += blockDim.x) {
+                double s = b[i];
+                for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * y[j];
+                double val, der;
+                fnn_act(p.act, s, val, der);
+                yn[i] = val;   // (PolyNet: p)
+            }
+            __syncthreads();
+            if constexpr (NET == NET_POLYNET) {   // y' = y + p + act(W p + b): thread i reads p, writes its own y_i
+                for (int i = threadIdx.x; i < H; i += blockDim.x) {
+                    double s = b[i];
+                    for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * yn[j];
+                    double val, der;
+                    fnn_act(p.act, s, val, der);
+                    y[i] = y[i] + yn[i] + val;
+                }
+            } else {
+                for (int i = threadIdx.x; i < H; i += blockDim.x) {
+                    if constexpr (NET == NET_RESNET) y[i] = y[i] + yn[i];
+                    else y[i] = yn[i];
+                }
+            }
             __syncthreads();
         }
         for (int i = threadIdx.x; i < n; i += blockDim.x) {

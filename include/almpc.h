@@ -266,7 +266,7 @@ int almpc_get_gradient_instance(almpc_handle* h, int instance, double* q);
  * The first iteration after `start` finds its working-set guess by ADMM, the following ones take it from the iterate (inputs
  * that sit on a bound) and skip the ADMM phase and its KKT inverse; the exact finish makes the two equivalent.
  *
- *   setup    network in the layout of almpc_fnn_linearize, shared references xref n*(N+1) / uref m*N (NULL: zeros), weights,
+ *   setup    network in the layout of almpc_fnn_linearize (`activation`: a network code, ALMPC_NET_CODE), shared references xref n*(N+1) / uref m*N (NULL: zeros), weights,
  *            P (required; shared or per instance), input box, ADMM rho/sigma.  Replaces any earlier design of the handle.
  *   start    x0 [batch][n]; u_guess [batch][N][m] or NULL (the input reference); both clipped to the box.  The state
  *            trajectory starts as the network's own rollout from x0 (zero defects).
@@ -305,7 +305,8 @@ int almpc_sqp_fnn_skipped(almpc_handle* h, int32_t* skipped /* [batch], 1 = some
  * iterate, condensed into H and q, plus the Gershgorin bound of the result on the diagonal of every input on a bound at the iterate.
  * An instance whose shifted Hessian is still not positive definite takes that iteration with the Gauss-Newton QP (structured
  * fallback; without it the iteration is skipped).  ALMPC_ERR_UNSUPPORTED for EXACT with state rows, the structured QP route, relu,
- * nz > 128 (checked here once set up, else at the next iterate / solve).
+ * nz > 128, or a network whose per-wave scratch (n + m + 3 H + H (n + m) + S H (n + m + 2) doubles, S = L activation sites, 2 L for
+ * a PolyNet) exceeds 16 KB (checked here once set up, else at the next iterate / solve).
  */
 enum { ALMPC_SQP_HESSIAN_GAUSS_NEWTON = 0, ALMPC_SQP_HESSIAN_EXACT = 1 };
 int almpc_sqp_fnn_set_hessian(almpc_handle* h, int mode);
@@ -335,7 +336,7 @@ int almpc_sqp_fnn_set_structured(almpc_handle* h, int on);
  * Jacobians A_i, B_i = d fnn / d(x, u) at (x0_i, u_ref[:,1]) written straight into the handle's per-instance model slots
  * (k_fnn_jacobian) -> the reference's QP for every (A_i, B_i) (the design kernels of almpc_design_batched) -> the step.  No host
  * pointer is touched: x0 comes from almpc_update_initialization(_device), results as after almpc_calculate.
- *   setup   network in the layout of almpc_fnn_linearize; xref n*(N+1), uref m*N shared (NULL: zeros); weights; P n*n (required:
+ *   setup   network in the layout of almpc_fnn_linearize (`activation`: a network code, ALMPC_NET_CODE); xref n*(N+1), uref m*N shared (NULL: zeros); weights; P n*n (required:
  *           the reference takes the terminal weight from the linearisation at the LAST reference, src/sub/design_mpc.jl:312-327 --
  *           almpc_fnn_linearize + almpc_dare); input box; rho, sigma.  Replaces any earlier design of the handle.
  *   step    opts as almpc_calculate.  An instance whose condensed Hessian comes out without a positive diagonal / pivot (flagged by
@@ -558,13 +559,29 @@ int almpc_timing_samples(almpc_handle* h, int cap, int* count, float* ms_admm, f
 int almpc_dare(int n, int m, const double* A, const double* B, const double* Q, const double* R, double* P);
 
 /*
+ * Network code: the `activation` argument of almpc_fnn_linearize, almpc_relin_fnn_setup, almpc_sqp_fnn_setup and their
+ * almpc_group_* forms is ALMPC_NET_CODE(kind, activation).  The kinds share the weight layout below and differ in the hidden layer
+ * (a = W_h[l] y + b_h[l]):
+ *     ALMPC_NET_FNN      y' = act(a)                                   (.../fnn/mpc_modeler_implementation_fnn.jl:131-140)
+ *     ALMPC_NET_RESNET   y' = y + act(a)                               (.../resnet/mpc_modeler_implementation_resnet.jl:131-140)
+ *     ALMPC_NET_POLYNET  p = act(a), y' = y + p + act(W_h[l] p + b_h[l]), the same weights twice
+ *                                                                      (.../polynet/mpc_modeler_implementation_polynet.jl:132-148)
+ * A bare activation 0..4 is ALMPC_NET_CODE(ALMPC_NET_FNN, activation): the codes of old keep their meaning.  An Icnn is an Fnn.
+ * An unknown kind or activation: ALMPC_ERR_UNSUPPORTED.
+ */
+#define ALMPC_NET_FNN 0
+#define ALMPC_NET_RESNET 1
+#define ALMPC_NET_POLYNET 2
+#define ALMPC_NET_CODE(kind, act) (((kind) << 8) | (act))
+
+/*
  * Batched linearisation of a black-box Fnn model on the GPU: for each of `batch` points (x_i, u_i) the Jacobians
  * A_i = df/dx (n x n), B_i = df/du (n x m), both column-major, and optionally f_i = f(x_i, u_i).  Stands in for
  * AutomationLabsSystems.proceed_system_linearization (.../fnn/mpc_modeler_implementation_fnn.jl:42-46).  Layout as the
  * reference reads it from Flux.params (.../fnn/...:88-107): W_in H x (n+m) without bias or activation, L hidden layers
  * (W_h[l] H x H, b_h[l] H) with `activation` (0 identity, 1 relu, 2 tanh, 3 sigmoid, 4 swish; the
  * reference takes whatever NNlib function sits at f[2][1].sigma, src/sub/design_mpc.jl:472-483), W_out n x H without bias; all column-major.
- * Host pointers; synchronous.
+ * `activation` is a network code (ALMPC_NET_CODE above): ResNet and PolyNet models in the same layout.  Host pointers; synchronous.
  */
 int almpc_fnn_linearize(int device_id, int n, int m, int H, int L, int activation, const double* W_in,
                         const double* W_h, const double* b_h, const double* W_out, int batch, const double* x,

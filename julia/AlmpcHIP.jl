@@ -23,6 +23,11 @@ export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_s
 
 const libalmpc = get(ENV, "ALMPC_LIB", "libalmpc.so")
 
+# Network code of the calls that take an activation (include/almpc.h ALMPC_NET_CODE): kind << 8 | activation.  The kinds share the
+# Fnn weight layout and differ in the hidden layer: :fnn (also Icnn), :resnet y' = y + act(a), :polynet p = act(a), y' = y + p + act(W p + b).
+const NET_KINDS = Dict(:fnn => 0, :resnet => 1, :polynet => 2)
+net_code(net::Symbol, activation::Integer) = (NET_KINDS[net] << 8) | Int(activation)
+
 struct hip_solver_def end            # new tag, to be made <: AbstractSolvers in src/types/types.jl:162-192
 
 Base.@kwdef struct AlmpcOpts         # mirrors `almpc_opts` (72 bytes)
@@ -153,19 +158,20 @@ end
 
 NonLinearProgramming branch for an Fnn model (src/sub/model_modeler_implementation/fnn/mpc_modeler_implementation_fnn.jl:73-189,
 which the reference solves with Ipopt): the same NLP by Gauss-Newton SQP on the device.  `W_in` H x (n+m), `W_h` H x H x L,
-`b_h` H x L, `W_out` n x H as read from Flux.params (:88-107); `activation` 0 identity, 1 relu, 2 tanh, 3 sigmoid, 4 swish.
+`b_h` H x L, `W_out` n x H as read from Flux.params (:88-107); `activation` 0 identity, 1 relu, 2 tanh, 3 sigmoid, 4 swish;
+keyword `net` (:fnn, :resnet, :polynet) the network kind in the same layout (`net_code`).
 Then per step:  `sqp_start!(mod, x0)`;  `sqp_iterate!(mod, iters)`;  results through `calculate!`'s readers (`almpc_get_results`).
 """
 function design_sqp_fnn!(mod::HipModeler, W_in::Matrix{Float64}, W_h::Array{Float64,3}, b_h::Matrix{Float64}, W_out::Matrix{Float64},
                          activation::Integer, Q::Matrix{Float64}, R::Matrix{Float64}, S::Matrix{Float64}, P::Matrix{Float64},
-                         umin::Vector{Float64}, umax::Vector{Float64}; x_ref::Matrix{Float64}, u_ref::Matrix{Float64},
+                         umin::Vector{Float64}, umax::Vector{Float64}; x_ref::Matrix{Float64}, u_ref::Matrix{Float64}, net::Symbol = :fnn,
                          structured_qp::Bool = false)
     # structured_qp: every iteration's QP in the multiple-shooting form (k_riccati) instead of the condensed one
     check(mod.handle, ccall((:almpc_sqp_fnn_set_structured, libalmpc), Cint, (Ptr{Cvoid}, Cint), mod.handle, structured_qp ? 1 : 0))
     check(mod.handle, ccall((:almpc_sqp_fnn_setup, libalmpc), Cint,
                    (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
-                   mod.handle, size(W_in, 1), size(W_h, 3), activation, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, 0, umin, umax,
+                   mod.handle, size(W_in, 1), size(W_h, 3), net_code(net, activation), W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, 0, umin, umax,
                    mod.opts.rho, mod.opts.sigma))
     return mod
 end
@@ -345,11 +351,11 @@ BASELINE configs[3]: the black-box model is re-linearised at every instance's ow
 """
 function design_relin_fnn!(mod::HipModeler, W_in::Matrix{Float64}, W_h::Array{Float64,3}, b_h::Matrix{Float64}, W_out::Matrix{Float64},
                            activation::Integer, Q::Matrix{Float64}, R::Matrix{Float64}, S::Matrix{Float64}, P::Matrix{Float64},
-                           umin::Vector{Float64}, umax::Vector{Float64}; x_ref::Matrix{Float64}, u_ref::Matrix{Float64})
+                           umin::Vector{Float64}, umax::Vector{Float64}; x_ref::Matrix{Float64}, u_ref::Matrix{Float64}, net::Symbol = :fnn)
     check(mod.handle, ccall((:almpc_relin_fnn_setup, libalmpc), Cint,
                    (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
-                   mod.handle, size(W_in, 1), size(W_h, 3), activation, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax,
+                   mod.handle, size(W_in, 1), size(W_h, 3), net_code(net, activation), W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax,
                    mod.opts.rho, mod.opts.sigma))
     return mod
 end
@@ -469,13 +475,13 @@ function design_ltv!(mod::HipModeler, A_all::Array{Float64,4}, B_all::Array{Floa
 end
 "Jacobians (A_i, B_i) and values of an Fnn at `x` (n x batch), `u` (m x batch) on device `device` (the batched `proceed_system_linearization`)"
 function fnn_linearize(W_in::Matrix{Float64}, W_h::Array{Float64,3}, b_h::Matrix{Float64}, W_out::Matrix{Float64}, activation::Integer,
-                       x::Matrix{Float64}, u::Matrix{Float64}; device::Integer = 0)
+                       x::Matrix{Float64}, u::Matrix{Float64}; device::Integer = 0, net::Symbol = :fnn)
     n, m, b = size(x, 1), size(u, 1), size(x, 2)
     A, B, f = Array{Float64,3}(undef, n, n, b), Array{Float64,3}(undef, n, m, b), Matrix{Float64}(undef, n, b)
     rc = ccall((:almpc_fnn_linearize, libalmpc), Cint,
                (Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64},
                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
-               device, n, m, size(W_in, 1), size(W_h, 3), activation, W_in, W_h, b_h, W_out, b, x, u, A, B, f)
+               device, n, m, size(W_in, 1), size(W_h, 3), net_code(net, activation), W_in, W_h, b_h, W_out, b, x, u, A, B, f)
     rc == 0 || error("almpc_fnn_linearize failed ($rc)")
     return A, B, f
 end
@@ -643,11 +649,11 @@ end
 "`design_relin_fnn!` on every device (BASELINE configs[3]); then `group_relin_step!`, `group_relin_advance!`"
 function group_design_relin_fnn!(g::HipGroup, W_in::Matrix{Float64}, W_h::Array{Float64,3}, b_h::Matrix{Float64}, W_out::Matrix{Float64},
                                  activation::Integer, Q::Matrix{Float64}, R::Matrix{Float64}, S::Matrix{Float64}, P::Matrix{Float64},
-                                 umin::Vector{Float64}, umax::Vector{Float64}; x_ref::Matrix{Float64}, u_ref::Matrix{Float64})
+                                 umin::Vector{Float64}, umax::Vector{Float64}; x_ref::Matrix{Float64}, u_ref::Matrix{Float64}, net::Symbol = :fnn)
     gcheck(g.group, ccall((:almpc_group_relin_fnn_setup, libalmpc), Cint,
                    (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
-                   g.group, size(W_in, 1), size(W_h, 3), activation, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax,
+                   g.group, size(W_in, 1), size(W_h, 3), net_code(net, activation), W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax,
                    g.opts.rho, g.opts.sigma))
     return g
 end
@@ -667,13 +673,13 @@ group_advance_plant!(g::HipGroup) = gcheck(g.group, ccall((:almpc_group_advance_
 "`design_sqp_fnn!` on every device (BASELINE configs[4]); `P` n x n or n x n x batch"
 function group_design_sqp_fnn!(g::HipGroup, W_in::Matrix{Float64}, W_h::Array{Float64,3}, b_h::Matrix{Float64}, W_out::Matrix{Float64},
                                activation::Integer, Q::Matrix{Float64}, R::Matrix{Float64}, S::Matrix{Float64}, P::Array{Float64},
-                               umin::Vector{Float64}, umax::Vector{Float64}; x_ref::Matrix{Float64}, u_ref::Matrix{Float64},
+                               umin::Vector{Float64}, umax::Vector{Float64}; x_ref::Matrix{Float64}, u_ref::Matrix{Float64}, net::Symbol = :fnn,
                                structured_qp::Bool = false)
     gcheck(g.group, ccall((:almpc_group_sqp_fnn_set_structured, libalmpc), Cint, (Ptr{Cvoid}, Cint), g.group, structured_qp ? 1 : 0))
     gcheck(g.group, ccall((:almpc_group_sqp_fnn_setup, libalmpc), Cint,
                    (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
-                   g.group, size(W_in, 1), size(W_h, 3), activation, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, ndims(P) == 3 ? 1 : 0,
+                   g.group, size(W_in, 1), size(W_h, 3), net_code(net, activation), W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, ndims(P) == 3 ? 1 : 0,
                    umin, umax, g.opts.rho, g.opts.sigma))
     return g
 end

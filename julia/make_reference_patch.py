@@ -25,7 +25,7 @@ EDITS = [
 
     ("src/types/types.jl", 'struct auto_solver_def <: AbstractSolvers end\n', "after",
      '\n"""\n    hip\nBatched condensed-QP solve on an AMD MI355X through libalmpc.so (src/hip/AlmpcHIP.jl): the linear method on a linear system, and\n'
-     'black-box Fnn systems by linearisation (linear method) or Gauss-Newton SQP (non linear method).\n"""\n'
+     'black-box Fnn, Icnn, ResNet and PolyNet systems by linearisation (linear method) or Gauss-Newton SQP (non linear method).\n"""\n'
      'struct hip_solver_def <: AbstractSolvers end\n'),
 
     ("src/sub/solver_selection.jl", '    auto = auto_solver_def(),\n', "after", '    hip = hip_solver_def(),\n'),
@@ -186,19 +186,32 @@ function _model_predictive_control_design_hip(
     return ModelPredictiveControlController(system, tuning, initialization, computation_results)
 end
 
-# activation code of libalmpc.so for the function get_activation_function returns (f[2][1].σ)
-function _hip_activation_code(sigma)
-    sigma === identity && return 0
-    sigma === Flux.relu && return 1
-    sigma === tanh && return 2
-    (sigma === Flux.sigmoid || sigma === Flux.σ) && return 3
-    sigma === Flux.swish && return 4
-    error("mpc_solver = \\"hip\\": activation $(sigma) is not one of identity, relu, tanh, sigmoid, swish")
+# network kind of libalmpc.so (ALMPC_NET_*): the families in the Fnn weight layout; an Icnn is an Fnn (get_activation_function)
+_hip_net_kind(::Union{AutomationLabsSystems.Fnn, AutomationLabsSystems.Icnn}) = 0
+_hip_net_kind(::AutomationLabsSystems.ResNet) = 1
+_hip_net_kind(::AutomationLabsSystems.PolyNet) = 2
+
+# network code of libalmpc.so (ALMPC_NET_CODE) for the model type and the function get_activation_function returns (f[2][1].σ)
+function _hip_activation_code(sigma, model_type)
+    act = if sigma === identity
+        0
+    elseif sigma === Flux.relu
+        1
+    elseif sigma === tanh
+        2
+    elseif sigma === Flux.sigmoid || sigma === Flux.σ
+        3
+    elseif sigma === Flux.swish
+        4
+    else
+        error("mpc_solver = \\"hip\\": activation $(sigma) is not one of identity, relu, tanh, sigmoid, swish")
+    end
+    return (_hip_net_kind(model_type) << 8) | act
 end
 
 """
     _model_predictive_control_design_hip
-Black-box Fnn systems on the GPU. The weights are read from `Flux.params(system.f)` exactly as the NonLinearProgramming modeler does
+Black-box Fnn, Icnn, ResNet and PolyNet systems on the GPU (the network kind goes into the activation code). The weights are read from `Flux.params(system.f)` exactly as the NonLinearProgramming modeler does
 (mpc_modeler_implementation_fnn.jl): first layer without bias, hidden layers with bias and activation, last layer without bias.
 * LinearProgramming: Jacobians at `references.x[:, begin], references.u[:, begin]` (the LinearProgramming delegate) for the dynamics
   and at `[:, end]` for P (`_create_terminal_ingredient`), both by `AlmpcHIP.fnn_linearize`, then the linear design; with
@@ -208,7 +221,7 @@ Black-box Fnn systems on the GPU. The weights are read from `Flux.params(system.
 """
 function _model_predictive_control_design_hip(
     method::AbstractImplementation,
-    model_type::AutomationLabsSystems.Fnn,
+    model_type::Union{AutomationLabsSystems.Fnn, AutomationLabsSystems.Icnn, AutomationLabsSystems.ResNet, AutomationLabsSystems.PolyNet},
     system::MathematicalSystems.ConstrainedBlackBoxControlDiscreteSystem,
     horizon::Int,
     sample_time::Int,
@@ -251,7 +264,7 @@ function _model_predictive_control_design_hip(
         W_h[:, :, j] = nn_weights[i]
         b_h[:, j] = nn_weights[i+1]
     end
-    activation = _hip_activation_code(get_activation_function(model_type, system))
+    activation = _hip_activation_code(get_activation_function(model_type, system), model_type)
 
     batch = get(kws, :mpc_batch, 1)
     device = get(kws, :mpc_device, 0)
