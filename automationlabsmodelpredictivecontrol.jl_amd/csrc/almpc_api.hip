@@ -42,6 +42,7 @@
 #include <limits>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 using namespace almpc;
@@ -1513,9 +1514,19 @@ static bool decode_net(int code, int* net, int* act) {
     return true;
 }
 static const char* net_name(int net) { return net == NET_RESNET ? "ResNet" : (net == NET_POLYNET ? "PolyNet" : "Fnn"); }
+// The instantiation of a network kernel for the kind net (NET_*, from decode_net): pick(std::integral_constant<int, NET>()) at
+// NET = net, as in  with_net(net, [](auto k) { return k_fnn_rollout<k>; })
+template <class Pick>
+static auto with_net(int net, Pick pick) {
+    switch (net) {
+        case NET_RESNET: return pick(std::integral_constant<int, NET_RESNET>());
+        case NET_POLYNET: return pick(std::integral_constant<int, NET_POLYNET>());
+        default: return pick(std::integral_constant<int, NET_FNN>());
+    }
+}
 
 // Jacobians of the network (kind net: NET_*) at p.batch points: wave-per-point build when weights + 4 waves' buffers fit 64 KB of
-// LDS, else one workgroup per point (the caller has checked fnn_wg_lds_doubles against 160 KB).
+// LDS, else one workgroup per point (the caller has checked fnn_wave_scratch_doubles against 160 KB).
 hipError_t launch_fnn_jacobian(const FnnParams& p, int net, int num_cus, hipStream_t st) {
     const size_t nin = (size_t)p.n + p.m;
     // small networks (H (n + m) <= 192 entries of the Jacobian being propagated): two points per wave, one per half-wave
@@ -1528,18 +1539,12 @@ hipError_t launch_fnn_jacobian(const FnnParams& p, int net, int num_cus, hipStre
                                       // 12800 points of an SQP iteration, 32 take 48 (52 workgroups per CU: 49.5)
         if (wgs > cap) wgs = cap;
         const dim3 g(wgs), blk(64 * FNN_W_WAVES);
-        if (net == NET_RESNET) {
-            if (ppw == 2) hipLaunchKernelGGL((k_net_jacobian_w<NET_RESNET, 32>), g, blk, lw, st, p);
-            else hipLaunchKernelGGL((k_net_jacobian_w<NET_RESNET, 64>), g, blk, lw, st, p);
-        } else if (net == NET_POLYNET) {
-            if (ppw == 2) hipLaunchKernelGGL((k_net_jacobian_w<NET_POLYNET, 32>), g, blk, lw, st, p);
-            else hipLaunchKernelGGL((k_net_jacobian_w<NET_POLYNET, 64>), g, blk, lw, st, p);
-        } else if (ppw == 2) hipLaunchKernelGGL((k_fnn_jacobian_w<32>), g, blk, lw, st, p);
-        else hipLaunchKernelGGL((k_fnn_jacobian_w<64>), g, blk, lw, st, p);
+        void (*kern)(FnnParams) = with_net(net, [ppw](auto k) { return ppw == 2 ? k_fnn_jacobian_w<32, k> : k_fnn_jacobian_w<64, k>; });
+        hipLaunchKernelGGL(kern, g, blk, lw, st, p);
         return hipGetLastError();
     }
-    const size_t lds = fnn_wg_lds_doubles(p.n, p.m, p.H, net) * sizeof(double);
-    void (*kern)(FnnParams) = net == NET_RESNET ? k_net_jacobian<NET_RESNET> : (net == NET_POLYNET ? k_net_jacobian<NET_POLYNET> : k_fnn_jacobian);
+    const size_t lds = fnn_wave_scratch_doubles(p.n, p.m, p.H, net) * sizeof(double);
+    void (*kern)(FnnParams) = with_net(net, [](auto k) { return k_fnn_jacobian<k>; });
     if (lds > 64 * 1024) {
         const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), (size_t)(lds));
         if (e != hipSuccess) return e;
@@ -1602,7 +1607,7 @@ hipError_t launch_design_ltv(almpc_handle* h, const DesignLtvParams& lp, hipStre
 }
 
 // whether k_design_instance_t can linearise the network itself (LDS route with room for the weights and one wave's scratch).  An Fnn
-// only: a ResNet / PolyNet is linearised by k_net_jacobian_w in front of the design (the design kernel keeps its Fnn head and code).
+// only: a ResNet / PolyNet is linearised by k_fnn_jacobian_w in front of the design (the design kernel keeps its Fnn head and code).
 bool design_fuses_fnn(const almpc_handle* h, int H, int L, int net) {
     if (net != NET_FNN) return false;
     const size_t lds = (design_instance_lds_doubles(h->n, h->m, h->N) + fnn_weights_doubles(h->n, h->m, H, L) + fnn_wave_scratch_doubles(h->n, h->m, H)) * sizeof(double);
@@ -1930,7 +1935,7 @@ int relin_setup_structured(almpc_handle* h, int H, int L, int net, int activatio
                            const double* P, const double* umin, const double* umax) {
     const int n = h->n, m = h->m, N = h->N, nz = h->nz;
     const size_t b = (size_t)h->batch, nin = (size_t)n + m;
-    if (fnn_wg_lds_doubles(n, m, H, net) * sizeof(double) > 160 * 1024)
+    if (fnn_wave_scratch_doubles(n, m, H, net) * sizeof(double) > 160 * 1024)
         return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup: the network's forward-mode Jacobian must fit the 160 KB of LDS");
     for (int i = 0; i < m; ++i)
         if (!(umin[i] <= umax[i])) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: umin > umax");
@@ -2080,7 +2085,7 @@ int almpc_relin_fnn_setup(almpc_handle* h, int H, int L, int activation, const d
     if (!(rho > 0.0) || !(sigma >= 0.0)) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: rho must be > 0 and sigma >= 0");
     const int n = h->n, m = h->m, N = h->N, nz = h->nz;
     const size_t b = (size_t)h->batch, nin = (size_t)n + m;
-    if (fnn_wg_lds_doubles(n, m, H, net) * sizeof(double) > 160 * 1024)
+    if (fnn_wave_scratch_doubles(n, m, H, net) * sizeof(double) > 160 * 1024)
         return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup: the network's forward-mode Jacobian must fit the 160 KB of LDS");
     for (int i = 0; i < m; ++i)
         if (!(umin[i] <= umax[i])) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: umin > umax");
@@ -2495,7 +2500,7 @@ int almpc_sqp_fnn_start(almpc_handle* h, const double* x0, const double* u_guess
     rp.n = n; rp.m = m; rp.H = q.H; rp.L = q.L; rp.act = q.act; rp.N = N;
     rp.W_in = q.W_in; rp.W_h = q.W_h; rp.b_h = q.b_h; rp.W_out = q.W_out; rp.x0 = h->dX0; rp.ubar = h->dUref; rp.xbar = h->dXref;
     const size_t l = (2 * (size_t)q.H + n + m) * sizeof(double);
-    void (*roll)(FnnRolloutParams) = q.net == NET_RESNET ? k_net_rollout<NET_RESNET> : (q.net == NET_POLYNET ? k_net_rollout<NET_POLYNET> : k_fnn_rollout);
+    void (*roll)(FnnRolloutParams) = with_net(q.net, [](auto k) { return k_fnn_rollout<k>; });
     if (l > 64 * 1024) HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(roll), (size_t)(l)));
     hipLaunchKernelGGL(roll, dim3((unsigned)b), dim3(256), l, st, rp);
     HIP_TRY(h, hipGetLastError());
@@ -2693,8 +2698,7 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
         if (sv) HIP_TRY(h, kkt_test(it));
         if (exact) {   // multipliers (from the test above, or the walk alone), then the stage Lagrangian Hessians at the iterate
             if (!sv) hipLaunchKernelGGL(k_sqp_kkt, dim3((unsigned)b), dim3(256), step_lds, st, kp);
-            void (*hk)(FnnHessParams) = q.net == NET_RESNET ? k_net_lag_hessian<NET_RESNET>
-                                                          : (q.net == NET_POLYNET ? k_net_lag_hessian<NET_POLYNET> : k_fnn_lag_hessian);
+            void (*hk)(FnnHessParams) = with_net(q.net, [](auto k) { return k_fnn_lag_hessian<k>; });
             hipLaunchKernelGGL(hk, dim3((unsigned)((b * N + 3) / 4)), dim3(256), hess_lds, st, hp);
             HIP_TRY(h, hipGetLastError());
         }
@@ -3526,7 +3530,7 @@ int almpc_fnn_linearize(int device_id, int n, int m, int H, int L, int activatio
     int net = NET_FNN;
     if (!decode_net(activation, &net, &activation)) return ALMPC_ERR_UNSUPPORTED;
     const size_t nin = (size_t)n + m;
-    if (fnn_wg_lds_doubles(n, m, H, net) * sizeof(double) > 160 * 1024) return ALMPC_ERR_UNSUPPORTED;
+    if (fnn_wave_scratch_doubles(n, m, H, net) * sizeof(double) > 160 * 1024) return ALMPC_ERR_UNSUPPORTED;
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || device_id < 0 || device_id >= count) return ALMPC_ERR_NO_DEVICE;
     if (hipSetDevice(device_id) != hipSuccess) return ALMPC_ERR_HIP;

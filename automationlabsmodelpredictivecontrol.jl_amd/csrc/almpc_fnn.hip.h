@@ -11,8 +11,8 @@
 //     Fnn      y' = act(a)                                           J' = diag(act'(a)) W J
 //     ResNet   y' = y + act(a)                                       J' = J + diag(act'(a)) W J
 //     PolyNet  p = act(a1), y' = y + p + act(W p + b)  (same W, b)   P = diag(act'(a1)) W J,  J' = J + P + diag(act'(a2)) W P
-// ResNet and PolyNet run in kernels templated on the kind (k_net_*<NET_*>); the Fnn kernels keep their names and their code
-// (and so their ISA: DESIGN.md, "ResNet and PolyNet models").
+// Every network kernel takes the kind as a template parameter (NET_*): the ResNet and PolyNet steps are `if constexpr` branches, and
+// the NET_FNN instantiations compile to the Fnn arithmetic alone ("ResNet and PolyNet models").
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -46,76 +46,18 @@ __device__ __forceinline__ void fnn_act(int act, double a, double& val, double& 
     }
 }
 
-// LDS of the workgroup build: y, yn | J, Jn | z (+ p: PolyNet)
-__host__ __device__ inline size_t fnn_wg_lds_doubles(int n, int m, int H, int net = NET_FNN) {
-    const size_t nin = (size_t)n + m;
-    return 2 * (size_t)H + 2 * (size_t)H * nin + nin + (net == NET_POLYNET ? (size_t)H : 0);
+// weights staged in LDS by the wave build (fnn_stage_weights): Win | Wh | bh | Wout
+__host__ __device__ inline size_t fnn_weights_doubles(int n, int m, int H, int L) {
+    return (size_t)H * (n + m) + (size_t)L * H * H + (size_t)L * H + (size_t)n * H;
+}
+// scratch of one point: y, yn | J, Jn | z (+ p: PolyNet) -- one wave's in the wave build, the whole LDS of k_fnn_jacobian
+__host__ __device__ inline size_t fnn_wave_scratch_doubles(int n, int m, int H, int net = NET_FNN) {
+    return 2 * (size_t)H + 2 * (size_t)H * (n + m) + (n + m) + (net == NET_POLYNET ? (size_t)H : 0);
 }
 
-inline __global__ __launch_bounds__(256) void k_fnn_jacobian(FnnParams p) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int n = p.n, m = p.m, H = p.H, nin = n + m;
-    double* y = smem;             // [H]
-    double* yn = y + H;           // [H]
-    double* J = yn + H;           // [H][nin]  (row-major: J[i*nin + c])
-    double* Jn = J + (size_t)H * nin;
-    double* z = Jn + (size_t)H * nin;  // [nin]
-    const int inst = blockIdx.x;
-    const double* xp = p.x + (size_t)(inst / p.ppi) * p.xs_group + (size_t)(inst % p.ppi) * n;
-    const double* up = p.u + (size_t)(inst / p.ppi) * p.us_group + (size_t)(inst % p.ppi) * m;
-    for (int t = threadIdx.x; t < nin; t += blockDim.x) z[t] = t < n ? xp[t] : up[t - n];
-    __syncthreads();
-    for (int i = threadIdx.x; i < H; i += blockDim.x) {
-        double s = 0.0;
-        for (int c = 0; c < nin; ++c) s += p.W_in[(size_t)c * H + i] * z[c];
-        y[i] = s;
-    }
-    for (int t = threadIdx.x; t < H * nin; t += blockDim.x) J[t] = p.W_in[(size_t)(t % nin) * H + t / nin];
-    __syncthreads();
-    for (int l = 0; l < p.L; ++l) {
-        const double* W = p.W_h + (size_t)l * H * H;
-        const double* b = p.b_h + (size_t)l * H;
-        for (int i = threadIdx.x; i < H; i += blockDim.x) {
-            double s = b[i];
-            for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * y[j];
-            yn[i] = s;  // pre-activation
-        }
-        __syncthreads();
-        for (int t = threadIdx.x; t < H * nin; t += blockDim.x) {
-            const int i = t / nin, c = t % nin;
-            double s = 0.0;
-            for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * J[(size_t)j * nin + c];
-            double val, der;
-            fnn_act(p.act, yn[i], val, der);
-            Jn[t] = der == 0.0 ? 0.0 : der * s;
-        }
-        __syncthreads();
-        for (int i = threadIdx.x; i < H; i += blockDim.x) {
-            double val, der;
-            fnn_act(p.act, yn[i], val, der);
-            y[i] = val;
-        }
-        for (int t = threadIdx.x; t < H * nin; t += blockDim.x) J[t] = Jn[t];
-        __syncthreads();
-    }
-    for (int t = threadIdx.x; t < n * nin; t += blockDim.x) {
-        const int i = t % n, c = t / n;
-        double s = 0.0;
-        for (int j = 0; j < H; ++j) s += p.W_out[(size_t)j * n + i] * J[(size_t)j * nin + c];
-        if (c < n) p.A[(size_t)inst * n * n + (size_t)c * n + i] = s;
-        else p.B[(size_t)inst * n * m + (size_t)(c - n) * n + i] = s;
-    }
-    if (p.f)
-        for (int i = threadIdx.x; i < n; i += blockDim.x) {
-            double s = 0.0;
-            for (int j = 0; j < H; ++j) s += p.W_out[(size_t)j * n + i] * y[j];
-            p.f[(size_t)inst * n + i] = s;
-        }
-}
-
-// ResNet / PolyNet (a kernel of its own: k_fnn_jacobian above keeps its name and its code)
+// The workgroup build: one workgroup per point, its LDS one point's scratch (fnn_wave_scratch_doubles)
 template <int NET>
-__global__ __launch_bounds__(256) void k_net_jacobian(FnnParams p) {
+__global__ __launch_bounds__(256) void k_fnn_jacobian(FnnParams p) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int n = p.n, m = p.m, H = p.H, nin = n + m;
     double* y = smem;             // [H]
@@ -215,10 +157,7 @@ constexpr int FNN_W_WAVES = 4;
 
 // (ppw: points per wave and pass, 1 or 2: see fnn_jacobian_point)
 __host__ __device__ inline size_t fnn_w_lds_doubles(int n, int m, int H, int L, int ppw = 1, int net = NET_FNN) {
-    const size_t nin = (size_t)n + m;
-    const size_t weights = (size_t)H * nin + (size_t)L * H * H + (size_t)L * H + (size_t)n * H;
-    const size_t per_wave = 2 * (size_t)H + 2 * (size_t)H * nin + nin + (net == NET_POLYNET ? (size_t)H : 0);
-    return weights + FNN_W_WAVES * ppw * per_wave;
+    return fnn_weights_doubles(n, m, H, L) + FNN_W_WAVES * ppw * fnn_wave_scratch_doubles(n, m, H, net);
 }
 
 // weights of the network into LDS (all threads of the workgroup; the caller synchronises): Win | Wh | bh | Wout
@@ -232,13 +171,6 @@ __device__ __forceinline__ void fnn_stage_weights(const FnnParams& p, double* sm
     for (int t = threadIdx.x; t < L * H * H; t += blockDim.x) Wh[t] = p.W_h[t];
     for (int t = threadIdx.x; t < L * H; t += blockDim.x) bh[t] = p.b_h[t];
     for (int t = threadIdx.x; t < n * H; t += blockDim.x) Wout[t] = p.W_out[t];
-}
-__host__ __device__ inline size_t fnn_weights_doubles(int n, int m, int H, int L) {
-    return (size_t)H * (n + m) + (size_t)L * H * H + (size_t)L * H + (size_t)n * H;
-}
-// (PolyNet: one H vector more, p)
-__host__ __device__ inline size_t fnn_wave_scratch_doubles(int n, int m, int H, int net = NET_FNN) {
-    return 2 * (size_t)H + 2 * (size_t)H * (n + m) + (n + m) + (net == NET_POLYNET ? (size_t)H : 0);
 }
 
 // Jacobians (and value) of the network at ONE point by ONE wave: weights staged at `wsm` (fnn_stage_weights), `y` = the wave's own
@@ -293,7 +225,7 @@ __device__ __forceinline__ void fnn_jacobian_point(const FnnParams& p, int inst_
                 else Jn[t] = der == 0.0 ? 0.0 : der * s;   // (PolyNet: P)
             }
             wsync();
-            if constexpr (NET == NET_POLYNET) {   // (as fnn_jacobian_wg)
+            if constexpr (NET == NET_POLYNET) {   // (as k_fnn_jacobian)
                 for (int i = lane; i < H; i += LW) {
                     double val, der;
                     fnn_act(p.act, yn[i], val, der);
@@ -349,29 +281,16 @@ __device__ __forceinline__ void fnn_jacobian_point(const FnnParams& p, int inst_
     }
 }
 
-template <int LW>
+template <int LW, int NET = NET_FNN>
 __global__ __launch_bounds__(64 * FNN_W_WAVES) void k_fnn_jacobian_w(FnnParams p) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int PPW = 64 / LW;   // points per wave and pass
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, sub = lane / LW, hl = lane % LW;
-    double* y = smem + fnn_weights_doubles(p.n, p.m, p.H, p.L) + (size_t)(wv * PPW + sub) * fnn_wave_scratch_doubles(p.n, p.m, p.H);
-    fnn_stage_weights(p, smem);
-    __syncthreads();
-    const int stride = gridDim.x * FNN_W_WAVES * PPW;
-    for (int i0 = (blockIdx.x * FNN_W_WAVES + wv) * PPW; i0 < p.batch; i0 += stride)   // (uniform trip count per wave: i0, not i0 + sub)
-        fnn_jacobian_point<LW>(p, i0 + sub, hl, smem, y);
-}
-// the same for a ResNet / PolyNet (a kernel of its own: k_fnn_jacobian_w keeps its name and its code)
-template <int NET, int LW>
-__global__ __launch_bounds__(64 * FNN_W_WAVES) void k_net_jacobian_w(FnnParams p) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    constexpr int PPW = 64 / LW;
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, sub = lane / LW, hl = lane % LW;
     double* y = smem + fnn_weights_doubles(p.n, p.m, p.H, p.L) + (size_t)(wv * PPW + sub) * fnn_wave_scratch_doubles(p.n, p.m, p.H, NET);
     fnn_stage_weights(p, smem);
     __syncthreads();
     const int stride = gridDim.x * FNN_W_WAVES * PPW;
-    for (int i0 = (blockIdx.x * FNN_W_WAVES + wv) * PPW; i0 < p.batch; i0 += stride)
+    for (int i0 = (blockIdx.x * FNN_W_WAVES + wv) * PPW; i0 < p.batch; i0 += stride)   // (uniform trip count per wave: i0, not i0 + sub)
         fnn_jacobian_point<LW, NET>(p, i0 + sub, hl, smem, y);
 }
 

@@ -270,10 +270,11 @@ inline __global__ __launch_bounds__(256) void k_sqp_kkt(SqpKktParams p) {
     }
 }
 
-// Exact-Hessian mode (almpc_sqp_fnn_set_hessian): the stage Lagrangian Hessian of the Fnn layout at every (instance, stage),
+// Exact-Hessian mode (almpc_sqp_fnn_set_hessian): the stage Lagrangian Hessian of the network at every (instance, stage),
 //     W_k = d^2/dz^2 (lam_{k+1}' f(z_k)) = sum_j M_j' diag(ybar_j * act''(a_j)) M_j,   z = [x; u]
-// M_j = d a_j / d z the forward Jacobian chain (as k_fnn_jacobian forms it), ybar_j the adjoint of act(a_j) from W_out' lam.  One
-// wave per point, four per workgroup, each with its own LDS scratch (fnn_hess_wave_doubles); weights read through the cache.
+// M_j = d a_j / d z the forward Jacobian chain (as k_fnn_jacobian forms it), ybar_j the adjoint of act(a_j) from W_out' lam (the
+// ResNet and PolyNet sites: below; the kind is the kernel's template parameter).  One wave per point, four per workgroup, each with
+// its own LDS scratch (fnn_hess_wave_doubles); weights read through the cache.
 // Entries are summed as (M_r M_c) c so that W_k is exactly symmetric.  tests/sqp_exact_ref.py::stage_hessian restates it.
 __device__ __forceinline__ void fnn_act2(int act, double a, double& d1, double& d2) {
     switch (act) {
@@ -298,101 +299,12 @@ struct FnnHessParams {
     double* W;                                // [batch][N][(n+m)^2] column-major
 };
 
-inline __global__ __launch_bounds__(256) void k_fnn_lag_hessian(FnnHessParams p) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int n = p.n, m = p.m, H = p.H, L = p.L, nin = n + m, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    double* z = smem + (size_t)wv * fnn_hess_wave_doubles(n, m, H, L);
-    double* y = z + nin;                  // [H]
-    double* yb = y + H;                   // [H]
-    double* t = yb + H;                   // [H]
-    double* J = t + H;                    // [H][nin] row-major: d y / d z
-    double* Aa = J + (size_t)H * nin;     // [L][H] pre-activations
-    double* Cc = Aa + (size_t)L * H;      // [L][H] ybar * act''
-    double* M = Cc + (size_t)L * H;       // [L][H][nin] d a_l / d z
-    const long pt = (long)blockIdx.x * 4 + wv;
-    if (pt >= (long)p.batch * p.N) return;   // (wave-uniform; no workgroup barrier below)
-    const long inst = pt / p.N;
-    const int k = (int)(pt % p.N);
-    if (p.done && p.done[inst]) return;
-    auto wsync = []() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
-    for (int c = lane; c < nin; c += 64)
-        z[c] = c < n ? p.xbar[(inst * (p.N + 1) + k) * n + c] : p.ubar[(inst * p.N + k) * m + c - n];
-    wsync();
-    for (int i = lane; i < H; i += 64) {
-        double s = 0.0;
-        for (int c = 0; c < nin; ++c) s += p.W_in[(size_t)c * H + i] * z[c];
-        y[i] = s;
-    }
-    for (int e = lane; e < H * nin; e += 64) J[e] = p.W_in[(size_t)(e % nin) * H + e / nin];
-    wsync();
-    for (int l = 0; l < L; ++l) {
-        const double* W = p.W_h + (size_t)l * H * H;
-        for (int i = lane; i < H; i += 64) {
-            double s = p.b_h[(size_t)l * H + i];
-            for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * y[j];
-            Aa[l * H + i] = s;
-        }
-        for (int e = lane; e < H * nin; e += 64) {
-            const int i = e / nin, c = e % nin;
-            double s = 0.0;
-            for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * J[(size_t)j * nin + c];
-            M[((size_t)l * H + i) * nin + c] = s;
-        }
-        wsync();
-        for (int i = lane; i < H; i += 64) {
-            double val, der;
-            fnn_act(p.act, Aa[l * H + i], val, der);
-            y[i] = val;
-        }
-        for (int e = lane; e < H * nin; e += 64) {
-            double val, der;
-            fnn_act(p.act, Aa[l * H + e / nin], val, der);
-            J[e] = M[(size_t)l * H * nin + e] * der;
-        }
-        wsync();
-    }
-    const double* lam = p.lam + (inst * p.N + k) * (size_t)n;
-    for (int i = lane; i < H; i += 64) {
-        double s = 0.0;
-        for (int r = 0; r < n; ++r) s += p.W_out[(size_t)i * n + r] * lam[r];
-        yb[i] = s;
-    }
-    wsync();
-    for (int l = L - 1; l >= 0; --l) {
-        const double* W = p.W_h + (size_t)l * H * H;
-        for (int i = lane; i < H; i += 64) {
-            double d1, d2;
-            fnn_act2(p.act, Aa[l * H + i], d1, d2);
-            Cc[l * H + i] = yb[i] * d2;
-            t[i] = yb[i] * d1;
-        }
-        wsync();
-        for (int j = lane; j < H; j += 64) {
-            double s = 0.0;
-            for (int i = 0; i < H; ++i) s += W[(size_t)j * H + i] * t[i];
-            yb[j] = s;
-        }
-        wsync();
-    }
-    double* Wo = p.W + pt * (size_t)nin * nin;
-    for (int e = lane; e < nin * nin; e += 64) {
-        const int r = e % nin, c = e / nin;
-        double s = 0.0;
-        for (int l = 0; l < L; ++l)
-            for (int i = 0; i < H; ++i) {
-                const double* Mi = M + ((size_t)l * H + i) * nin;
-                s += (Mi[r] * Mi[c]) * Cc[l * H + i];
-            }
-        Wo[e] = s;
-    }
-}
-
 // ResNet: one site per layer, y' = y + act(a):  J' = J + diag(act') M,  ybar = ybar' + W' (act' .* ybar'),  site weight ybar' act''.
 // PolyNet: two sites per layer, a1 = W y + b and a2 = W p + b (p = act(a1), M2 = W diag(act'(a1)) M1, J' = J + diag(act'(a1)) M1 +
 // diag(act'(a2)) M2); backwards  pbar = ybar' + W' (act'(a2) .* ybar'),  ybar = ybar' + W' (act'(a1) .* pbar),  site weights
 // ybar' act''(a2) and pbar act''(a1).  Site s of layer l is l (Fnn, ResNet) or 2 l + {0, 1} (PolyNet).
 template <int NET>
-__global__ __launch_bounds__(256) void k_net_lag_hessian(FnnHessParams p) {
+__global__ __launch_bounds__(256) void k_fnn_lag_hessian(FnnHessParams p) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int SPL = NET == NET_POLYNET ? 2 : 1;   // sites per layer
     const int n = p.n, m = p.m, H = p.H, L = p.L, S = SPL * L, nin = n + m, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -676,7 +588,8 @@ inline __global__ __launch_bounds__(256) void k_sqp_exact_qp(SqpExactParams p) {
     }
 }
 
-// Single-shooting start: xbar_0 = x0, xbar_{k+1} = net(xbar_k, ubar_k).  One workgroup per instance, thread i owns neuron i.
+// Single-shooting start: xbar_0 = x0, xbar_{k+1} = net(xbar_k, ubar_k) for a network of kind NET (the template parameter).  One
+// workgroup per instance, thread i owns neuron i.
 struct FnnRolloutParams {
     int n, m, H, L, act, N;
     const double* W_in; const double* W_h; const double* b_h; const double* W_out;
@@ -685,57 +598,8 @@ struct FnnRolloutParams {
     double* xbar;         // [batch][(N+1)][n]
 };
 
-inline __global__ __launch_bounds__(256) void k_fnn_rollout(FnnRolloutParams p) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int n = p.n, m = p.m, H = p.H, nin = n + m;
-    double* y = smem;        // [H]
-    double* yn = y + H;      // [H]
-    double* z = yn + H;      // [nin]
-    const size_t inst = blockIdx.x;
-    double* xb = p.xbar + inst * (size_t)(p.N + 1) * n;
-    const double* ub = p.ubar + inst * (size_t)p.N * m;
-    for (int t = threadIdx.x; t < n; t += blockDim.x) {
-        const double v = p.x0[inst * n + t];
-        z[t] = v;
-        xb[t] = v;
-    }
-    __syncthreads();
-    for (int k = 0; k < p.N; ++k) {
-        for (int t = threadIdx.x; t < m; t += blockDim.x) z[n + t] = ub[k * m + t];
-        __syncthreads();
-        for (int i = threadIdx.x; i < H; i += blockDim.x) {
-            double s = 0.0;
-            for (int c = 0; c < nin; ++c) s += p.W_in[(size_t)c * H + i] * z[c];
-            y[i] = s;
-        }
-        __syncthreads();
-        for (int l = 0; l < p.L; ++l) {
-            const double* W = p.W_h + (size_t)l * H * H;
-            const double* b = p.b_h + (size_t)l * H;
-            for (int i = threadIdx.x; i < H; i += blockDim.x) {
-                double s = b[i];
-                for (int j = 0; j < H; ++j) s += W[(size_t)j * H + i] * y[j];
-                double val, der;
-                fnn_act(p.act, s, val, der);
-                yn[i] = val;
-            }
-            __syncthreads();
-            for (int i = threadIdx.x; i < H; i += blockDim.x) y[i] = yn[i];
-            __syncthreads();
-        }
-        for (int i = threadIdx.x; i < n; i += blockDim.x) {
-            double s = 0.0;
-            for (int j = 0; j < H; ++j) s += p.W_out[(size_t)j * n + i] * y[j];
-            z[i] = s;
-            xb[(size_t)(k + 1) * n + i] = s;
-        }
-        __syncthreads();
-    }
-}
-
-// ResNet / PolyNet (k_fnn_rollout keeps its name and its code)
 template <int NET>
-__global__ __launch_bounds__(256) void k_net_rollout(FnnRolloutParams p) {
+__global__ __launch_bounds__(256) void k_fnn_rollout(FnnRolloutParams p) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int n = p.n, m = p.m, H = p.H, nin = n + m;
     double* y = smem;        // [H]
