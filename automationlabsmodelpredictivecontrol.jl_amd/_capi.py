@@ -67,6 +67,8 @@ def load():
     L.almpc_sqp_fnn_setup.argtypes = [_hp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_dp] * 10 + [ctypes.c_int, _dp, _dp,
                                                                                                      ctypes.c_double, ctypes.c_double]
     L.almpc_sqp_fnn_setup.restype = ctypes.c_int
+    L.almpc_sqp_densenet_setup.argtypes = L.almpc_sqp_fnn_setup.argtypes
+    L.almpc_sqp_densenet_setup.restype = ctypes.c_int
     L.almpc_sqp_fnn_start.argtypes = [_hp, _dp, _dp]
     L.almpc_sqp_fnn_start.restype = ctypes.c_int
     L.almpc_sqp_fnn_iterate.argtypes = [_hp, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, _dp, _dp]
@@ -111,6 +113,8 @@ def load():
     L.almpc_set_structured_fallback.argtypes = [_hp, ctypes.c_int]
     L.almpc_relin_fnn_setup.argtypes = [_hp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_dp] * 12 + [ctypes.c_double, ctypes.c_double]
     L.almpc_relin_fnn_setup.restype = ctypes.c_int
+    L.almpc_relin_densenet_setup.argtypes = L.almpc_relin_fnn_setup.argtypes
+    L.almpc_relin_densenet_setup.restype = ctypes.c_int
     L.almpc_relin_fnn_step.argtypes = [_hp, ctypes.POINTER(almpc_opts)]
     L.almpc_relin_fnn_step_async.argtypes = [_hp, ctypes.POINTER(almpc_opts)]
     L.almpc_relin_fnn_timing.argtypes = [_hp, _fp, _fp, _fp]
@@ -121,6 +125,8 @@ def load():
     L.almpc_comm_allgather_first_input.argtypes = [_hp, _dp, ctypes.POINTER(_dp)]
     L.almpc_fnn_linearize.argtypes = [ctypes.c_int] * 6 + [_dp] * 4 + [ctypes.c_int] + [_dp] * 5
     L.almpc_fnn_linearize.restype = ctypes.c_int
+    L.almpc_densenet_linearize.argtypes = L.almpc_fnn_linearize.argtypes
+    L.almpc_densenet_linearize.restype = ctypes.c_int
     L.almpc_debug_poison_lds.restype = ctypes.c_int
     L.almpc_timing_summary.argtypes = [_hp, ctypes.POINTER(ctypes.c_int)] + [_dp] * 4
     # host-facing step path (pinned staging, copy streams) and one-process multi-GPU groups
@@ -159,6 +165,8 @@ def load():
     L.almpc_group_relin_fnn_advance.argtypes = [_hp]
     L.almpc_group_advance_plant.argtypes = [_hp]
     L.almpc_group_sqp_fnn_setup.argtypes = [_hp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_dp] * 10 + [ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_double]
+    L.almpc_group_relin_densenet_setup.argtypes = L.almpc_group_relin_fnn_setup.argtypes
+    L.almpc_group_sqp_densenet_setup.argtypes = L.almpc_group_sqp_fnn_setup.argtypes
     L.almpc_group_sqp_fnn_start.argtypes = [_hp, _dp, _dp]
     L.almpc_group_sqp_fnn_iterate.argtypes = [_hp, ctypes.c_int, ctypes.c_double, ctypes.POINTER(almpc_opts), _dp, _dp]
     L.almpc_group_sqp_fnn_skipped.argtypes = [_hp, _ip]
@@ -170,7 +178,7 @@ def load():
     for nm_ in ("almpc_group_set_terminal_equality", "almpc_group_set_rho_profile", "almpc_group_set_structured_fallback", "almpc_group_set_state_box",
                 "almpc_group_design_batched", "almpc_group_relin_fnn_setup", "almpc_group_relin_fnn_step", "almpc_group_relin_fnn_step_async",
                 "almpc_group_relin_fnn_advance", "almpc_group_advance_plant", "almpc_group_sqp_fnn_set_structured", "almpc_group_sqp_fnn_set_step_rule",
-                "almpc_group_sqp_fnn_setup", "almpc_group_sqp_fnn_start", "almpc_group_sqp_fnn_iterate", "almpc_group_sqp_fnn_skipped", "almpc_group_sqp_fnn_solve", "almpc_group_sqp_fnn_set_hessian",
+                "almpc_group_sqp_fnn_setup", "almpc_group_relin_densenet_setup", "almpc_group_sqp_densenet_setup", "almpc_group_sqp_fnn_start", "almpc_group_sqp_fnn_iterate", "almpc_group_sqp_fnn_skipped", "almpc_group_sqp_fnn_solve", "almpc_group_sqp_fnn_set_hessian",
                 "almpc_group_x0_staging", "almpc_group_update_initialization_staged", "almpc_group_get_results_async", "almpc_group_get_results_wait"):
         getattr(L, nm_).restype = ctypes.c_int
     L.almpc_set_start_from.argtypes = [_hp, _hp]
@@ -267,6 +275,38 @@ def net_code(net="fnn", act="relu"):
 SQP_HESSIANS = {"gauss_newton": 0, "exact": 1}   # almpc_sqp_fnn_set_hessian
 
 
+def _pack_densenet(W_in, W_h, b_h, W_out, n=None, m=None):
+    """The DenseNet buffers of include/almpc.h: W_in (H, n+m), W_h[l] (H, (l+1) H) packed column-major one after another, b_h[l] (H,),
+    W_out (n, (L+1) H).  ValueError on any shape that does not fit (n, m: the handle's, when given).  -> H, L, W_in, W_h, b_h, W_out"""
+    W_in, W_out = np.asfortranarray(W_in, dtype=np.float64), np.asfortranarray(W_out, dtype=np.float64)
+    if W_in.ndim != 2 or W_out.ndim != 2:
+        raise ValueError("DenseNet: W_in and W_out must be matrices")
+    H, nin = W_in.shape
+    W_h, b_h = [np.asarray(w, dtype=np.float64) for w in W_h], [np.asarray(v, dtype=np.float64) for v in b_h]
+    nl = len(W_h)
+    if len(b_h) != nl:
+        raise ValueError(f"DenseNet: {nl} hidden weight blocks but {len(b_h)} bias vectors")
+    for l, (w, v) in enumerate(zip(W_h, b_h)):
+        if w.shape != (H, (l + 1) * H):
+            raise ValueError(f"DenseNet: W_h[{l}] must be {(H, (l + 1) * H)}, got {w.shape}")
+        if v.shape != (H,):
+            raise ValueError(f"DenseNet: b_h[{l}] must be {(H,)}, got {v.shape}")
+    if W_out.shape[1] != (nl + 1) * H:
+        raise ValueError(f"DenseNet: W_out must have (L+1) H = {(nl + 1) * H} columns, got {W_out.shape}")
+    if (n is not None and W_out.shape[0] != n) or (m is not None and nin != n + m) or nin <= W_out.shape[0]:
+        raise ValueError(f"DenseNet: W_in {W_in.shape} and W_out {W_out.shape} do not fit n = {n}, m = {m}")
+    Wh = np.concatenate([w.ravel(order="F") for w in W_h]) if nl else np.zeros(1)
+    bh = np.ascontiguousarray(np.stack(b_h)) if nl else np.zeros((1, 1))
+    return H, nl, W_in, Wh, bh, W_out
+
+
+def _densenet_act(act):
+    """the bare activation code of the almpc_*densenet* calls"""
+    if act not in FNN_ACTIVATIONS:
+        raise ValueError(f"act must be one of {sorted(FNN_ACTIVATIONS)}, not {act!r}")
+    return FNN_ACTIVATIONS[act]
+
+
 def fnn_linearize(W_in, W_h, b_h, W_out, x, u, act="relu", device=0, want_f=False, net="fnn"):
     """Batched Jacobians of a network model on the GPU: x (batch, n), u (batch, m) -> A (batch, n, n), B (batch, n, m).
     net: "fnn", "resnet" or "polynet" (NET_KINDS), all in the Fnn weight layout."""
@@ -287,6 +327,26 @@ def fnn_linearize(W_in, W_h, b_h, W_out, x, u, act="relu", device=0, want_f=Fals
     if rc != ALMPC_OK:
         raise AlmpcError(rc, "almpc_fnn_linearize")
     A, B = A.transpose(0, 2, 1), B.transpose(0, 2, 1)  # column-major buffers -> (batch, row, col)
+    return (A, B, f) if want_f else (A, B)
+
+
+def densenet_linearize(W_in, W_h, b_h, W_out, x, u, act="relu", device=0, want_f=False):
+    """fnn_linearize for a DenseNet (almpc_densenet_linearize): W_h a list of (H, (l+1) H) blocks, W_out (n, (L+1) H)."""
+    x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+    u = np.ascontiguousarray(np.atleast_2d(u), dtype=np.float64)
+    H, nl, W_in, Wh, bh, W_out = _pack_densenet(W_in, W_h, b_h, W_out, x.shape[1], u.shape[1])
+    n, m = x.shape[1], u.shape[1]
+    batch = x.shape[0]
+    if u.shape[0] != batch:
+        raise ValueError("x and u must hold the same number of points")
+    code = _densenet_act(act)
+    L = load()
+    A = np.empty((batch, n, n)); B = np.empty((batch, m, n)); f = np.empty((batch, n)) if want_f else None
+    rc = L.almpc_densenet_linearize(int(device), n, m, H, nl, code, _ptr(W_in), _ptr(Wh), _ptr(bh), _ptr(W_out),
+                                    batch, _ptr(x), _ptr(u), _ptr(A), _ptr(B), _ptr(f))
+    if rc != ALMPC_OK:
+        raise AlmpcError(rc, "almpc_densenet_linearize")
+    A, B = A.transpose(0, 2, 1), B.transpose(0, 2, 1)
     return (A, B, f) if want_f else (A, B)
 
 
@@ -407,15 +467,27 @@ class Solver:
         """SQP outer loop for a network model (almpc_sqp_fnn_*): network (and net) as in fnn_linearize, x_ref (n, N+1) / u_ref (m, N) or None,
         P (n, n) or (batch, n, n).  qp_solver: "condensed" (default) or "structured" (every QP through k_riccati, no condensed design).  xmin / xmax: the state box of the reference's NLP branch
         (.../fnn/mpc_modeler_implementation_fnn.jl:146-153) as rows of every iteration's QP; terminal = "equality"."""
-        n, m, N, b = self.n, self.m, self.N, self.batch
-        self._state_rows(xmin, xmax, terminal)
-        self._check(self.L.almpc_sqp_fnn_set_structured(self.h, 1 if qp_solver == "structured" else 0))
-        self._check(self.L.almpc_set_rho_profile(self.h, {"scalar": 0, "stiffness": 1}[rho_profile]))
         W_in, W_out = np.asfortranarray(W_in, dtype=np.float64), np.asfortranarray(W_out, dtype=np.float64)
         H = W_in.shape[0]
         nl = len(W_h)
         Wh = np.ascontiguousarray(np.stack([np.asfortranarray(W, dtype=np.float64).T for W in W_h])) if nl else np.zeros((1, 1, 1))
         bh = np.ascontiguousarray(np.stack([np.asarray(v, dtype=np.float64) for v in b_h])) if nl else np.zeros((1, 1))
+        self._sqp_setup(self.L.almpc_sqp_fnn_setup, H, nl, net_code(net, act), W_in, Wh, bh, W_out, x_ref, u_ref, Q, R, S, P, umin, umax,
+                        rho, sigma, rho_profile, xmin, xmax, terminal, qp_solver)
+
+    def sqp_densenet_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu",
+                           rho=0.1, sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", qp_solver="condensed"):
+        """sqp_fnn_setup for a DenseNet (almpc_sqp_densenet_setup; network as in densenet_linearize); then the sqp_fnn_* calls."""
+        H, nl, W_in, Wh, bh, W_out = _pack_densenet(W_in, W_h, b_h, W_out, self.n, self.m)
+        self._sqp_setup(self.L.almpc_sqp_densenet_setup, H, nl, _densenet_act(act), W_in, Wh, bh, W_out, x_ref, u_ref, Q, R, S, P, umin,
+                        umax, rho, sigma, rho_profile, xmin, xmax, terminal, qp_solver)
+
+    def _sqp_setup(self, setup, H, nl, code, W_in, Wh, bh, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, rho, sigma, rho_profile, xmin,
+                   xmax, terminal, qp_solver):
+        n, m, N, b = self.n, self.m, self.N, self.batch
+        self._state_rows(xmin, xmax, terminal)
+        self._check(self.L.almpc_sqp_fnn_set_structured(self.h, 1 if qp_solver == "structured" else 0))
+        self._check(self.L.almpc_set_rho_profile(self.h, {"scalar": 0, "stiffness": 1}[rho_profile]))
         xr = None if x_ref is None else np.ascontiguousarray(np.asarray(x_ref, dtype=np.float64).reshape(n, N + 1).T)
         ur = None if u_ref is None else np.ascontiguousarray(np.asarray(u_ref, dtype=np.float64).reshape(m, N).T)
         Q, R = _colmajor(Q, (n, n)), _colmajor(R, (m, m))
@@ -428,22 +500,33 @@ class Solver:
             P = _colmajor(P, (n, n))
         umin = np.ascontiguousarray(umin, dtype=np.float64).reshape(m)
         umax = np.ascontiguousarray(umax, dtype=np.float64).reshape(m)
-        self._check(self.L.almpc_sqp_fnn_setup(self.h, H, nl, net_code(net, act), _ptr(W_in), _ptr(Wh), _ptr(bh), _ptr(W_out), _ptr(xr),
-                                               _ptr(ur), _ptr(Q), _ptr(R), _ptr(S), _ptr(P), p_inst, _ptr(umin), _ptr(umax), float(rho),
-                                               float(sigma)))
+        self._check(setup(self.h, H, nl, code, _ptr(W_in), _ptr(Wh), _ptr(bh), _ptr(W_out), _ptr(xr), _ptr(ur), _ptr(Q), _ptr(R), _ptr(S),
+                          _ptr(P), p_inst, _ptr(umin), _ptr(umax), float(rho), float(sigma)))
 
     def relin_fnn_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu", rho=0.1,
                         sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", net="fnn"):
         """Device-resident per-step re-linearisation of a network model (almpc_relin_fnn_*, BASELINE configs[3]): network (and net)
         as in fnn_linearize, shared x_ref (n, N+1) / u_ref (m, N) or None, shared P (n, n); xmin / xmax / terminal as in design_batched."""
-        n, m, N = self.n, self.m, self.N
-        self._state_rows(xmin, xmax, terminal)
-        self._check(self.L.almpc_set_rho_profile(self.h, {"scalar": 0, "stiffness": 1}[rho_profile]))
         W_in, W_out = np.asfortranarray(W_in, dtype=np.float64), np.asfortranarray(W_out, dtype=np.float64)
         H = W_in.shape[0]
         nl = len(W_h)
         Wh = np.ascontiguousarray(np.stack([np.asfortranarray(W, dtype=np.float64).T for W in W_h])) if nl else np.zeros((1, 1, 1))
         bh = np.ascontiguousarray(np.stack([np.asarray(v, dtype=np.float64) for v in b_h])) if nl else np.zeros((1, 1))
+        self._relin_setup(self.L.almpc_relin_fnn_setup, H, nl, net_code(net, act), W_in, Wh, bh, W_out, x_ref, u_ref, Q, R, S, P, umin,
+                          umax, rho, sigma, rho_profile, xmin, xmax, terminal)
+
+    def relin_densenet_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu",
+                             rho=0.1, sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none"):
+        """relin_fnn_setup for a DenseNet (almpc_relin_densenet_setup; network as in densenet_linearize); then the relin_fnn_* calls."""
+        H, nl, W_in, Wh, bh, W_out = _pack_densenet(W_in, W_h, b_h, W_out, self.n, self.m)
+        self._relin_setup(self.L.almpc_relin_densenet_setup, H, nl, _densenet_act(act), W_in, Wh, bh, W_out, x_ref, u_ref, Q, R, S, P,
+                          umin, umax, rho, sigma, rho_profile, xmin, xmax, terminal)
+
+    def _relin_setup(self, setup, H, nl, code, W_in, Wh, bh, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, rho, sigma, rho_profile, xmin,
+                     xmax, terminal):
+        n, m, N = self.n, self.m, self.N
+        self._state_rows(xmin, xmax, terminal)
+        self._check(self.L.almpc_set_rho_profile(self.h, {"scalar": 0, "stiffness": 1}[rho_profile]))
         xr = None if x_ref is None else np.ascontiguousarray(np.asarray(x_ref, dtype=np.float64).reshape(n, N + 1).T)
         ur = None if u_ref is None else np.ascontiguousarray(np.asarray(u_ref, dtype=np.float64).reshape(m, N).T)
         Q, R = _colmajor(Q, (n, n)), _colmajor(R, (m, m))
@@ -451,9 +534,8 @@ class Solver:
         P = _colmajor(P, (n, n))
         umin = np.ascontiguousarray(umin, dtype=np.float64).reshape(m)
         umax = np.ascontiguousarray(umax, dtype=np.float64).reshape(m)
-        self._check(self.L.almpc_relin_fnn_setup(self.h, H, nl, net_code(net, act), _ptr(W_in), _ptr(Wh), _ptr(bh), _ptr(W_out), _ptr(xr),
-                                                 _ptr(ur), _ptr(Q), _ptr(R), _ptr(S), _ptr(P), _ptr(umin), _ptr(umax), float(rho),
-                                                 float(sigma)))
+        self._check(setup(self.h, H, nl, code, _ptr(W_in), _ptr(Wh), _ptr(bh), _ptr(W_out), _ptr(xr), _ptr(ur), _ptr(Q), _ptr(R), _ptr(S),
+                          _ptr(P), _ptr(umin), _ptr(umax), float(rho), float(sigma)))
 
     def relin_fnn_step(self, opts: almpc_opts | None = None, sync=True):
         fn = self.L.almpc_relin_fnn_step if sync else self.L.almpc_relin_fnn_step_async
@@ -762,10 +844,13 @@ class Group:
         n, m, N = self.n, self.m, self.N
         W_in = np.asarray(W_in, dtype=np.float64)
         H = W_in.shape[0]
-        W_h = [np.asarray(w, dtype=np.float64) for w in W_h]
-        nl = len(W_h)
-        Wh = np.ascontiguousarray(np.stack([w.T for w in W_h])) if nl else None
-        bh = np.ascontiguousarray(np.stack([np.asarray(v, dtype=np.float64) for v in b_h])) if nl else None
+        if net == "densenet":   # (the DenseNet layout and a bare activation: the *_densenet_setup calls)
+            H, nl, W_in, Wh, bh, W_out = _pack_densenet(W_in, W_h, b_h, W_out, n, m)
+        else:
+            W_h = [np.asarray(w, dtype=np.float64) for w in W_h]
+            nl = len(W_h)
+            Wh = np.ascontiguousarray(np.stack([w.T for w in W_h])) if nl else None
+            bh = np.ascontiguousarray(np.stack([np.asarray(v, dtype=np.float64) for v in b_h])) if nl else None
         xr = np.ascontiguousarray(np.asarray(x_ref, dtype=np.float64).reshape(n, N + 1).T)
         ur = np.ascontiguousarray(np.asarray(u_ref, dtype=np.float64).reshape(m, N).T)
         P = np.asarray(P, dtype=np.float64)
@@ -774,10 +859,10 @@ class Group:
             P = np.ascontiguousarray(P.reshape(self.batch, n, n).transpose(0, 2, 1)); p_inst = 1
         else:
             P = _colmajor(P, (n, n))
-        arrs = [_colmajor(W_in, (H, n + m)), Wh, bh, _colmajor(W_out, (n, H)), xr, ur, _colmajor(Q, (n, n)), _colmajor(R, (m, m)),
+        arrs = [_colmajor(W_in, (H, n + m)), Wh, bh, _colmajor(W_out, (n, H * (nl + 1 if net == "densenet" else 1))), xr, ur, _colmajor(Q, (n, n)), _colmajor(R, (m, m)),
                 None if S is None else _colmajor(S, (m, m)), P,
                 np.ascontiguousarray(umin, dtype=np.float64).reshape(m), np.ascontiguousarray(umax, dtype=np.float64).reshape(m)]
-        return H, nl, net_code(net, act), arrs, p_inst
+        return H, nl, _densenet_act(act) if net == "densenet" else net_code(net, act), arrs, p_inst
 
     def relin_fnn_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu", rho=0.1,
                         sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", net="fnn"):
@@ -786,6 +871,15 @@ class Group:
         H, nl, a, arrs, _ = self._fnn_args(W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, act, False, net)
         self._keep = arrs
         self._check(self.L.almpc_group_relin_fnn_setup(self.g, H, nl, a, *[_ptr(v) for v in arrs], float(rho), float(sigma)))
+
+    def relin_densenet_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu",
+                             rho=0.1, sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none"):
+        """almpc_group_relin_densenet_setup: Solver.relin_densenet_setup on every device."""
+        self._state_rows(xmin, xmax, terminal)
+        self._check(self.L.almpc_group_set_rho_profile(self.g, {"scalar": 0, "stiffness": 1}[rho_profile]))
+        H, nl, a, arrs, _ = self._fnn_args(W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, act, False, "densenet")
+        self._keep = arrs
+        self._check(self.L.almpc_group_relin_densenet_setup(self.g, H, nl, a, *[_ptr(v) for v in arrs], float(rho), float(sigma)))
 
     def relin_fnn_step(self, opts: almpc_opts | None = None, sync=True):
         fn = self.L.almpc_group_relin_fnn_step if sync else self.L.almpc_group_relin_fnn_step_async
@@ -806,6 +900,18 @@ class Group:
         self._keep = arrs
         ptrs = [_ptr(v) for v in arrs]
         self._check(self.L.almpc_group_sqp_fnn_setup(self.g, H, nl, a, *ptrs[:10], p_inst, ptrs[10], ptrs[11], float(rho), float(sigma)))
+
+    def sqp_densenet_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu",
+                           rho=0.1, sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", qp_solver="condensed"):
+        """almpc_group_sqp_densenet_setup: Solver.sqp_densenet_setup on every device."""
+        self._state_rows(xmin, xmax, terminal)
+        self._check(self.L.almpc_group_set_rho_profile(self.g, {"scalar": 0, "stiffness": 1}[rho_profile]))
+        self._check(self.L.almpc_group_sqp_fnn_set_structured(self.g, 1 if qp_solver == "structured" else 0))
+        H, nl, a, arrs, p_inst = self._fnn_args(W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, act, True, "densenet")
+        self._keep = arrs
+        ptrs = [_ptr(v) for v in arrs]
+        self._check(self.L.almpc_group_sqp_densenet_setup(self.g, H, nl, a, *ptrs[:10], p_inst, ptrs[10], ptrs[11], float(rho),
+                                                          float(sigma)))
 
     def sqp_fnn_start(self, x0, u_guess=None):
         x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(self.batch, self.n)

@@ -21,6 +21,7 @@ Every solve goes through libalmpc.so (HIP); there is no CPU path in this module.
 from __future__ import annotations
 
 import dataclasses
+import functools
 from typing import Any, Optional
 
 import numpy as np
@@ -29,7 +30,7 @@ from . import _capi
 from .sharding import shard_range  # noqa: F401  (re-exported)
 
 __all__ = [
-    "Hyperrectangle", "ConstrainedLinearControlDiscreteSystem", "ConstrainedBlackBoxControlDiscreteSystem", "Fnn", "ResNet", "PolyNet", "Icnn",
+    "Hyperrectangle", "ConstrainedLinearControlDiscreteSystem", "ConstrainedBlackBoxControlDiscreteSystem", "Fnn", "ResNet", "PolyNet", "Icnn", "DenseNet",
     "proceed_system_linearization", "ReferencesStateInput", "WeightsCoefficient",
     "TerminalIngredient", "ModelPredictiveControlTuning", "ModelPredictiveControlResults",
     "ModelPredictiveControlController", "proceed_controller", "_design_reference_mpc",
@@ -97,10 +98,25 @@ class Icnn(Fnn):
     get_activation_function treats it as an Fnn: src/sub/design_mpc.jl:472-483).  Runs on the Fnn kernels."""
 
 
-# model family -> network kind of the library (_capi.NET_KINDS), by EXACT type: a subclass of Fnn is not silently an Fnn
-_NET_OF_MODEL = {Fnn: "fnn", Icnn: "fnn", ResNet: "resnet", PolyNet: "polynet"}
+@dataclasses.dataclass
+class DenseNet:
+    """DenseNet (.../densenet/mpc_modeler_implementation_densenet.jl:85-161): y_1 = W_in [x; u] (no bias, no activation),
+    y_{l+2} = [act(W_h[l] y_{l+1} + b_h[l]); y_{l+1}] -- the new features first, so W_h[l] is H x (l+1) H and its column c multiplies
+    entry c of y_{l+1} (newest first) --, x+ = W_out y_{L+1} with W_out n x (L+1) H (no bias).  The Fnn field names in the DenseNet
+    shapes (include/almpc.h); its own calls (_capi.densenet_linearize, *_densenet_setup), not the Fnn layout.
+    Also the model tag AutomationLabsSystems.DenseNet()."""
+    W_in: np.ndarray
+    W_h: list
+    b_h: list
+    W_out: np.ndarray
+    act: str = "relu"
+
+
+# model family -> network kind of the library (_capi.NET_KINDS, and "densenet": its own calls), by EXACT type: a subclass of Fnn is not
+# silently an Fnn
+_NET_OF_MODEL = {Fnn: "fnn", Icnn: "fnn", ResNet: "resnet", PolyNet: "polynet", DenseNet: "densenet"}
 _MODEL_REFUSALS = {
-    "DenseNet": "its layer widths grow (y_j has j H rows), which does not fit the [L] H x H weight layout",
+    "DenseNet": "its layer widths grow (y_j has j H rows), which an [L] H x H Fnn layout cannot hold: use controller.DenseNet",
     "Rbf": "its NLP modeler reuses the Fnn layer equations without the deviation and reference constraints: there is no "
            "well-defined network to restate",
     "NeuralODE": "its integrator lives in AutomationLabsSystems, outside the reference",
@@ -111,11 +127,12 @@ _MODEL_REFUSALS = {
 
 
 def _net_kind(f) -> str:
-    """Network kind of a black-box model: "fnn" (Fnn, Icnn), "resnet" or "polynet"; NotImplementedError for any other family."""
+    """Network kind of a black-box model: "fnn" (Fnn, Icnn), "resnet", "polynet" or "densenet"; NotImplementedError for any other
+    family."""
     kind = _NET_OF_MODEL.get(type(f))
     if kind is None:
         name = type(f).__name__
-        why = _MODEL_REFUSALS.get(name, "only the Fnn, Icnn, ResNet and PolyNet families are built")
+        why = _MODEL_REFUSALS.get(name, "only the Fnn, Icnn, ResNet, PolyNet and DenseNet families are built")
         raise NotImplementedError(f"black-box model family {name!r} is not supported: {why}")
     return kind
 
@@ -135,8 +152,12 @@ def proceed_system_linearization(system: ConstrainedBlackBoxControlDiscreteSyste
     src/sub/design_mpc.jl:319-326): the linear system (A, B) = Jacobians of f at (x, u), same constraint sets.
     Computed on the GPU (k_fnn_jacobian)."""
     f = system.f
-    A, B = _capi.fnn_linearize(f.W_in, f.W_h, f.b_h, f.W_out, np.asarray(state, dtype=np.float64).reshape(1, -1),
-                               np.asarray(input, dtype=np.float64).reshape(1, -1), act=f.act, device=device, net=_net_kind(f))
+    x, u = np.asarray(state, dtype=np.float64).reshape(1, -1), np.asarray(input, dtype=np.float64).reshape(1, -1)
+    net = _net_kind(f)
+    if net == "densenet":
+        A, B = _capi.densenet_linearize(f.W_in, f.W_h, f.b_h, f.W_out, x, u, act=f.act, device=device)
+    else:
+        A, B = _capi.fnn_linearize(f.W_in, f.W_h, f.b_h, f.W_out, x, u, act=f.act, device=device, net=net)
     return ConstrainedLinearControlDiscreteSystem(A[0], B[0], system.X, system.U)
 
 
@@ -247,7 +268,7 @@ def _model_predictive_control_design(system, horizon: int, sample_time: int, ref
 
 def _design_blackbox(system: ConstrainedBlackBoxControlDiscreteSystem, horizon: int, sample_time: int,
                      references: ReferencesStateInput, **kws_):
-    """Black-box (Fnn, Icnn, ResNet, PolyNet) model, LinearProgramming branch (src/sub/design_mpc.jl:143-225 ->
+    """Black-box (Fnn, Icnn, ResNet, PolyNet, DenseNet) model, LinearProgramming branch (src/sub/design_mpc.jl:143-225 ->
     .../fnn/mpc_modeler_implementation_fnn.jl:23-58): dynamics linearised at the FIRST reference, terminal weight
     P = DARE at the linearisation about the LAST reference (src/sub/design_mpc.jl:312-327), then the linear path.
 
@@ -259,7 +280,7 @@ def _design_blackbox(system: ConstrainedBlackBoxControlDiscreteSystem, horizon: 
     lin_mode = kws.get("mpc_linearization", "reference")
     if lin_mode not in ("reference", "step"):
         raise ValueError("mpc_linearization must be 'reference' or 'step'")
-    net = _net_kind(system.f)   # Fnn, Icnn, ResNet, PolyNet; the other families raise NotImplementedError with the reason
+    net = _net_kind(system.f)   # Fnn, Icnn, ResNet, PolyNet, DenseNet; the other families raise NotImplementedError with the reason
     dev = int(kws.get("mpc_device", 0))
     x_ref, u_ref = np.asarray(references.x, dtype=np.float64), np.asarray(references.u, dtype=np.float64)
     lin_first = proceed_system_linearization(system, x_ref[:, 0], u_ref[:, 0], device=dev)
@@ -281,17 +302,18 @@ def _design_blackbox(system: ConstrainedBlackBoxControlDiscreteSystem, horizon: 
         if not kws.get("mpc_structured_fallback", True):
             mod.solver._check(mod.solver.L.almpc_set_structured_fallback(mod.solver.h, 0))
         # device-resident pipeline (almpc_relin_fnn_*): Jacobians -> per-instance designs -> step, no host pointers per step
-        mod.solver.relin_fnn_setup(f.W_in, f.W_h, f.b_h, f.W_out, references.x, references.u, weights.Q, weights.R, weights.S, np.array(P),
-                                   system.U.low, system.U.high, act=f.act, net=net, rho=float(sopt.get("rho", 0.1)),
-                                   sigma=float(sopt.get("sigma", 1e-6)), rho_profile=kws.get("mpc_rho_profile", "scalar"),
-                                   xmin=system.X.low if state_box else None, xmax=system.X.high if state_box else None,
-                                   terminal="equality" if term_eq else "none")
+        setup = mod.solver.relin_densenet_setup if net == "densenet" else functools.partial(mod.solver.relin_fnn_setup, net=net)
+        setup(f.W_in, f.W_h, f.b_h, f.W_out, references.x, references.u, weights.Q, weights.R, weights.S, np.array(P),
+              system.U.low, system.U.high, act=f.act, rho=float(sopt.get("rho", 0.1)),
+              sigma=float(sopt.get("sigma", 1e-6)), rho_profile=kws.get("mpc_rho_profile", "scalar"),
+              xmin=system.X.low if state_box else None, xmax=system.X.high if state_box else None,
+              terminal="equality" if term_eq else "none")
         mod.relinearize = dict(system=system, device=dev)
     return C
 
 
 def _design_blackbox_nonlinear(system, horizon, sample_time, references, weights, P, kws):
-    """Black-box (Fnn, Icnn, ResNet, PolyNet) model, NonLinearProgramming branch (.../fnn/mpc_modeler_implementation_fnn.jl:73-189): the network itself
+    """Black-box (Fnn, Icnn, ResNet, PolyNet, DenseNet) model, NonLinearProgramming branch (.../fnn/mpc_modeler_implementation_fnn.jl:73-189): the network itself
     is the equality constraint x[:,k+1] = fnn(x[:,k], u[:,k]) and the reference gives the NLP to Ipopt
     (src/sub/solver_selection.jl:100-104).  Here the same NLP goes through the device-resident SQP loop (almpc_sqp_fnn_*).
     Keys of this build: mpc_sqp_iterations (outer iterations per calculate!, default 10), mpc_sqp_step (step length, default 1),
@@ -328,12 +350,14 @@ def _design_blackbox_nonlinear(system, horizon, sample_time, references, weights
             raise ValueError("mpc_sqp_tolerance: the first-order residual scales the gradient by 1 / (2 R_aa): R must not be 0")
     sopt = dict(kws.get("mpc_solver_options", {}))
     solver = _capi.Solver(n, m, horizon, batch, device=int(kws.get("mpc_device", 0)), timing=bool(kws.get("mpc_timing", False)))
-    solver.sqp_fnn_setup(f.W_in, f.W_h, f.b_h, f.W_out, x_ref, u_ref, weights.Q, weights.R, weights.S, P, system.U.low, system.U.high,
-                         act=f.act, net=_net_kind(f), rho=float(sopt.get("rho", 0.1)), sigma=float(sopt.get("sigma", 1e-6)),
-                         rho_profile=kws.get("mpc_rho_profile", "scalar"),
-                         xmin=system.X.low if state_box else None, xmax=system.X.high if state_box else None,
-                         terminal="equality" if terminal == "equality" else "none",
-                         qp_solver=kws.get("mpc_sqp_qp_solver", "condensed"))   # "structured": every QP through k_riccati
+    net = _net_kind(f)
+    setup = solver.sqp_densenet_setup if net == "densenet" else functools.partial(solver.sqp_fnn_setup, net=net)
+    setup(f.W_in, f.W_h, f.b_h, f.W_out, x_ref, u_ref, weights.Q, weights.R, weights.S, P, system.U.low, system.U.high,
+          act=f.act, rho=float(sopt.get("rho", 0.1)), sigma=float(sopt.get("sigma", 1e-6)),
+          rho_profile=kws.get("mpc_rho_profile", "scalar"),
+          xmin=system.X.low if state_box else None, xmax=system.X.high if state_box else None,
+          terminal="equality" if terminal == "equality" else "none",
+          qp_solver=kws.get("mpc_sqp_qp_solver", "condensed"))   # "structured": every QP through k_riccati
     hess = kws.get("mpc_sqp_hessian", "gauss_newton")
     if hess not in _capi.SQP_HESSIANS:
         solver.close()

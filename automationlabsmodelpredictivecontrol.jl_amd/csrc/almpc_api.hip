@@ -1513,7 +1513,22 @@ static bool decode_net(int code, int* net, int* act) {
     *act = a;
     return true;
 }
-static const char* net_name(int net) { return net == NET_RESNET ? "ResNet" : (net == NET_POLYNET ? "PolyNet" : "Fnn"); }
+// The kind and activation of a network setup call: an ALMPC_NET_CODE (the *_fnn_* calls, dense false) or a bare activation 0..4 (the
+// *_densenet_* calls: NET_DENSENET has no network code, its weight layout is its own)
+static bool setup_net(bool dense, int code, int* net, int* act) {
+    if (!dense) return decode_net(code, net, act);
+    if (code < 0 || code > 4) return false;
+    *net = NET_DENSENET;
+    *act = code;
+    return true;
+}
+static const char* net_name(int net) {
+    return net == NET_RESNET ? "ResNet" : (net == NET_POLYNET ? "PolyNet" : (net == NET_DENSENET ? "DenseNet" : "Fnn"));
+}
+// Element counts of the W_h and W_out arrays of a network of kind net: [L] H x H and n x H in the Fnn layout, the DenseNet's
+// growing blocks (include/almpc.h)
+static size_t net_wh_doubles(int net, int H, int L) { return net == NET_DENSENET ? densenet_wh_offset(H, L) : (size_t)L * H * H; }
+static size_t net_wout_doubles(int net, int n, int H, int L) { return (size_t)n * H * (net == NET_DENSENET ? L + 1 : 1); }
 // The instantiation of a network kernel for the kind net (NET_*, from decode_net): pick(std::integral_constant<int, NET>()) at
 // NET = net, as in  with_net(net, [](auto k) { return k_fnn_rollout<k>; })
 template <class Pick>
@@ -1521,6 +1536,7 @@ static auto with_net(int net, Pick pick) {
     switch (net) {
         case NET_RESNET: return pick(std::integral_constant<int, NET_RESNET>());
         case NET_POLYNET: return pick(std::integral_constant<int, NET_POLYNET>());
+        case NET_DENSENET: return pick(std::integral_constant<int, NET_DENSENET>());
         default: return pick(std::integral_constant<int, NET_FNN>());
     }
 }
@@ -1543,7 +1559,7 @@ hipError_t launch_fnn_jacobian(const FnnParams& p, int net, int num_cus, hipStre
         hipLaunchKernelGGL(kern, g, blk, lw, st, p);
         return hipGetLastError();
     }
-    const size_t lds = fnn_wave_scratch_doubles(p.n, p.m, p.H, net) * sizeof(double);
+    const size_t lds = fnn_wave_scratch_doubles(p.n, p.m, p.H, p.L, net) * sizeof(double);
     void (*kern)(FnnParams) = with_net(net, [](auto k) { return k_fnn_jacobian<k>; });
     if (lds > 64 * 1024) {
         const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), (size_t)(lds));
@@ -1610,7 +1626,7 @@ hipError_t launch_design_ltv(almpc_handle* h, const DesignLtvParams& lp, hipStre
 // only: a ResNet / PolyNet is linearised by k_fnn_jacobian_w in front of the design (the design kernel keeps its Fnn head and code).
 bool design_fuses_fnn(const almpc_handle* h, int H, int L, int net) {
     if (net != NET_FNN) return false;
-    const size_t lds = (design_instance_lds_doubles(h->n, h->m, h->N) + fnn_weights_doubles(h->n, h->m, H, L) + fnn_wave_scratch_doubles(h->n, h->m, H)) * sizeof(double);
+    const size_t lds = (design_instance_lds_doubles(h->n, h->m, h->N) + fnn_weights_doubles(h->n, h->m, H, L) + fnn_wave_scratch_doubles(h->n, h->m, H, L)) * sizeof(double);
     return lds <= 160 * 1024 && !getenv("ALMPC_DBG_SPLIT_JACOBIAN");
 }
 
@@ -1630,7 +1646,7 @@ hipError_t launch_batched_design(almpc_handle* h, const DesignStrides& ds, int u
     size_t fnn_off = 0;
     if (fuse_fnn) {   // (the caller has checked design_fuses_fnn)
         fnn_off = design_instance_lds_doubles(n, m, N);
-        inst_lds += (fnn_weights_doubles(n, m, fuse_fnn->H, fuse_fnn->L) + fnn_wave_scratch_doubles(n, m, fuse_fnn->H)) * sizeof(double);
+        inst_lds += (fnn_weights_doubles(n, m, fuse_fnn->H, fuse_fnn->L) + fnn_wave_scratch_doubles(n, m, fuse_fnn->H, fuse_fnn->L)) * sizeof(double);
     }
     if (inst_lds > 160 * 1024) {   // (the LDS route below clears the flags itself)
         e = hipMemsetAsync(h->bFlag, 0, (size_t)h->batch * sizeof(int), st);
@@ -1935,7 +1951,7 @@ int relin_setup_structured(almpc_handle* h, int H, int L, int net, int activatio
                            const double* P, const double* umin, const double* umax) {
     const int n = h->n, m = h->m, N = h->N, nz = h->nz;
     const size_t b = (size_t)h->batch, nin = (size_t)n + m;
-    if (fnn_wave_scratch_doubles(n, m, H, net) * sizeof(double) > 160 * 1024)
+    if (fnn_wave_scratch_doubles(n, m, H, L, net) * sizeof(double) > 160 * 1024)
         return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup: the network's forward-mode Jacobian must fit the 160 KB of LDS");
     for (int i = 0; i < m; ++i)
         if (!(umin[i] <= umax[i])) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: umin > umax");
@@ -1970,8 +1986,8 @@ int relin_setup_structured(almpc_handle* h, int H, int L, int net, int activatio
     std::vector<double> ul(b * m);
     for (size_t i = 0; i < b; ++i)
         for (int a = 0; a < m; ++a) ul[i * m + a] = ur[a];  // every instance linearises at the first input reference
-    HIP_TRY(h, up(&q.W_in, W_in, (size_t)H * nin)); HIP_TRY(h, up(&q.W_h, W_h, (size_t)L * H * H)); HIP_TRY(h, up(&q.b_h, b_h, (size_t)L * H));
-    HIP_TRY(h, up(&q.W_out, W_out, (size_t)n * H)); HIP_TRY(h, up(&q.ulin, ul.data(), ul.size()));
+    HIP_TRY(h, up(&q.W_in, W_in, (size_t)H * nin)); HIP_TRY(h, up(&q.W_h, W_h, net_wh_doubles(net, H, L))); HIP_TRY(h, up(&q.b_h, b_h, (size_t)L * H));
+    HIP_TRY(h, up(&q.W_out, W_out, net_wout_doubles(net, n, H, L))); HIP_TRY(h, up(&q.ulin, ul.data(), ul.size()));
     if (!h->bA) HIP_TRY(h, dalloc(&h->bA, b * n * n));
     if (!h->bB) HIP_TRY(h, dalloc(&h->bB, b * n * m));
     if (!h->bP) HIP_TRY(h, dalloc(&h->bP, b * n * n));
@@ -2070,22 +2086,25 @@ int almpc_get_gradient_instance(almpc_handle* h, int instance, double* q) {
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Per-step re-linearisation of a black-box Fnn model, resident on the device (BASELINE configs[3]; include/almpc.h).
-int almpc_relin_fnn_setup(almpc_handle* h, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
-                          const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
-                          const double* S, const double* P, const double* umin, const double* umax, double rho, double sigma) {
+// (dense: almpc_relin_densenet_setup, activation a bare code; else almpc_relin_fnn_setup, activation an ALMPC_NET_CODE)
+static int relin_net_setup(almpc_handle* h, bool dense, int H, int L, int activation, const double* W_in, const double* W_h,
+                           const double* b_h, const double* W_out, const double* xref, const double* uref, const double* Q,
+                           const double* R, const double* S, const double* P, const double* umin, const double* umax, double rho,
+                           double sigma) {
     if (!h) return ALMPC_ERR_INVALID;
     drop_lazy_redo(h);
     if (H < 1 || L < 0 || !W_in || !W_out || (L > 0 && (!W_h || !b_h)) || !Q || !R || !P || !umin || !umax)
         return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: null pointer or bad network shape (P must be given: the terminal weight "
                                           "comes from the linearisation at the last reference, src/sub/design_mpc.jl:312-327)");
     int net = NET_FNN;
-    if (!decode_net(activation, &net, &activation))
-        return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup: activation must be ALMPC_NET_CODE(kind 0..2, activation 0..4)");
+    if (!setup_net(dense, activation, &net, &activation))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, dense ? "relin_densenet_setup: activation must be 0..4"
+                                                    : "relin_fnn_setup: activation must be ALMPC_NET_CODE(kind 0..2, activation 0..4)");
     if (h->structured) return relin_setup_structured(h, H, L, net, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, umin, umax);
     if (!(rho > 0.0) || !(sigma >= 0.0)) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: rho must be > 0 and sigma >= 0");
     const int n = h->n, m = h->m, N = h->N, nz = h->nz;
     const size_t b = (size_t)h->batch, nin = (size_t)n + m;
-    if (fnn_wave_scratch_doubles(n, m, H, net) * sizeof(double) > 160 * 1024)
+    if (fnn_wave_scratch_doubles(n, m, H, L, net) * sizeof(double) > 160 * 1024)
         return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup: the network's forward-mode Jacobian must fit the 160 KB of LDS");
     for (int i = 0; i < m; ++i)
         if (!(umin[i] <= umax[i])) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: umin > umax");
@@ -2129,8 +2148,8 @@ int almpc_relin_fnn_setup(almpc_handle* h, int H, int L, int activation, const d
     std::vector<double> ul(b * m);
     for (size_t i = 0; i < b; ++i)
         for (int a = 0; a < m; ++a) ul[i * m + a] = ur[a];  // every instance linearises at the first input reference
-    HIP_TRY(h, up(&q.W_in, W_in, (size_t)H * nin)); HIP_TRY(h, up(&q.W_h, W_h, (size_t)L * H * H)); HIP_TRY(h, up(&q.b_h, b_h, (size_t)L * H));
-    HIP_TRY(h, up(&q.W_out, W_out, (size_t)n * H)); HIP_TRY(h, up(&q.ulin, ul.data(), ul.size()));
+    HIP_TRY(h, up(&q.W_in, W_in, (size_t)H * nin)); HIP_TRY(h, up(&q.W_h, W_h, net_wh_doubles(net, H, L))); HIP_TRY(h, up(&q.b_h, b_h, (size_t)L * H));
+    HIP_TRY(h, up(&q.W_out, W_out, net_wout_doubles(net, n, H, L))); HIP_TRY(h, up(&q.ulin, ul.data(), ul.size()));
     HIP_TRY(h, up(&q.Q, Qm.data(), Qm.size())); HIP_TRY(h, up(&q.R, Rm.data(), Rm.size())); HIP_TRY(h, up(&q.S, Sm.data(), Sm.size()));
     HIP_TRY(h, up(&q.gS, gS.data(), gS.size()));
     HIP_TRY(h, hipMemcpy(h->bP, Pm.data(), Pm.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -2175,6 +2194,16 @@ int almpc_relin_fnn_setup(almpc_handle* h, int H, int L, int activation, const d
     }
     q.ready = true;
     return ALMPC_OK;
+}
+int almpc_relin_fnn_setup(almpc_handle* h, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
+                          const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
+                          const double* S, const double* P, const double* umin, const double* umax, double rho, double sigma) {
+    return relin_net_setup(h, false, H, L, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, umin, umax, rho, sigma);
+}
+int almpc_relin_densenet_setup(almpc_handle* h, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
+                               const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
+                               const double* S, const double* P, const double* umin, const double* umax, double rho, double sigma) {
+    return relin_net_setup(h, true, H, L, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, umin, umax, rho, sigma);
 }
 
 int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
@@ -2309,17 +2338,19 @@ int almpc_relin_fnn_timing(almpc_handle* h, float* ms_jacobian, float* ms_design
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // SQP outer loop for a black-box Fnn model, resident on the device (see almpc_sqp.hip.h and include/almpc.h).
-int almpc_sqp_fnn_setup(almpc_handle* h, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
-                        const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
-                        const double* S, const double* P, int P_per_instance, const double* umin, const double* umax, double rho,
-                        double sigma) {
+// (dense: almpc_sqp_densenet_setup, activation a bare code; else almpc_sqp_fnn_setup, activation an ALMPC_NET_CODE)
+static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activation, const double* W_in, const double* W_h,
+                         const double* b_h, const double* W_out, const double* xref, const double* uref, const double* Q,
+                         const double* R, const double* S, const double* P, int P_per_instance, const double* umin, const double* umax,
+                         double rho, double sigma) {
     if (!h) return ALMPC_ERR_INVALID;
     drop_lazy_redo(h);
     if (H < 1 || L < 0 || !W_in || !W_out || (L > 0 && (!W_h || !b_h)) || !Q || !R || !P || !umin || !umax)
         return fail(h, ALMPC_ERR_INVALID, "sqp_fnn_setup: null pointer or bad network shape (P must be given)");
     int net = NET_FNN;
-    if (!decode_net(activation, &net, &activation))
-        return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_setup: activation must be ALMPC_NET_CODE(kind 0..2, activation 0..4)");
+    if (!setup_net(dense, activation, &net, &activation))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, dense ? "sqp_densenet_setup: activation must be 0..4"
+                                                    : "sqp_fnn_setup: activation must be ALMPC_NET_CODE(kind 0..2, activation 0..4)");
     if (!(rho > 0.0) || !(sigma >= 0.0)) return fail(h, ALMPC_ERR_INVALID, "sqp_fnn_setup: rho must be > 0 and sigma >= 0");
     const int n = h->n, m = h->m, N = h->N, nz = h->nz, nzs = h->nzs;
     const size_t b = (size_t)h->batch, nin = (size_t)n + m;
@@ -2333,7 +2364,7 @@ int almpc_sqp_fnn_setup(almpc_handle* h, int H, int L, int activation, const dou
     const bool sq_struct = h->sqp.structured_qp != 0;
     if (!sq_struct && !ltv_supported(h))
         return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_setup: nz <= 128, or nz^2 + 3 n nz doubles must fit the 160 KB of LDS");
-    if ((2 * (size_t)H + 2 * (size_t)H * nin + nin) * sizeof(double) > 160 * 1024)
+    if ((net == NET_DENSENET ? fnn_wave_scratch_doubles(n, m, H, L, net) : 2 * (size_t)H + 2 * (size_t)H * nin + nin) * sizeof(double) > 160 * 1024)
         return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_setup: the network's forward-mode Jacobian must fit the 160 KB of LDS");
     for (int i = 0; i < m; ++i)
         if (!(umin[i] <= umax[i])) return fail(h, ALMPC_ERR_INVALID, "sqp_fnn_setup: umin > umax");
@@ -2384,8 +2415,8 @@ int almpc_sqp_fnn_setup(almpc_handle* h, int H, int L, int activation, const dou
     std::vector<double> xr((size_t)n * (N + 1), 0.0), ur((size_t)nz, 0.0);
     if (xref) xr.assign(xref, xref + xr.size());
     if (uref) ur.assign(uref, uref + ur.size());
-    HIP_TRY(h, up(&q.W_in, W_in, (size_t)H * nin)); HIP_TRY(h, up(&q.W_h, W_h, (size_t)L * H * H)); HIP_TRY(h, up(&q.b_h, b_h, (size_t)L * H));
-    HIP_TRY(h, up(&q.W_out, W_out, (size_t)n * H));
+    HIP_TRY(h, up(&q.W_in, W_in, (size_t)H * nin)); HIP_TRY(h, up(&q.W_h, W_h, net_wh_doubles(net, H, L))); HIP_TRY(h, up(&q.b_h, b_h, (size_t)L * H));
+    HIP_TRY(h, up(&q.W_out, W_out, net_wout_doubles(net, n, H, L)));
     HIP_TRY(h, up(&q.A, nullptr, b * N * n * n)); HIP_TRY(h, up(&q.B, nullptr, b * N * n * m)); HIP_TRY(h, up(&q.c, nullptr, b * N * n));
     HIP_TRY(h, up(&q.fval, nullptr, b * N * n)); HIP_TRY(h, up(&q.ebar, nullptr, b * N * n)); HIP_TRY(h, up(&q.qadd, nullptr, b * nz));
     HIP_TRY(h, up(&q.xref, xr.data(), xr.size())); HIP_TRY(h, up(&q.uref, ur.data(), ur.size()));
@@ -2470,6 +2501,20 @@ int almpc_sqp_fnn_setup(almpc_handle* h, int H, int L, int activation, const dou
     q.ready = true; q.started = false;
     return ALMPC_OK;
 }
+int almpc_sqp_fnn_setup(almpc_handle* h, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
+                        const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
+                        const double* S, const double* P, int P_per_instance, const double* umin, const double* umax, double rho,
+                        double sigma) {
+    return sqp_net_setup(h, false, H, L, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, P_per_instance, umin, umax, rho,
+                         sigma);
+}
+int almpc_sqp_densenet_setup(almpc_handle* h, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
+                             const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
+                             const double* S, const double* P, int P_per_instance, const double* umin, const double* umax, double rho,
+                             double sigma) {
+    return sqp_net_setup(h, true, H, L, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, P_per_instance, umin, umax, rho,
+                         sigma);
+}
 
 int almpc_sqp_fnn_start(almpc_handle* h, const double* x0, const double* u_guess) {
     if (!h || !x0) return h ? fail(h, ALMPC_ERR_INVALID, "sqp_fnn_start: null x0") : ALMPC_ERR_INVALID;
@@ -2499,7 +2544,7 @@ int almpc_sqp_fnn_start(almpc_handle* h, const double* x0, const double* u_guess
     FnnRolloutParams rp;
     rp.n = n; rp.m = m; rp.H = q.H; rp.L = q.L; rp.act = q.act; rp.N = N;
     rp.W_in = q.W_in; rp.W_h = q.W_h; rp.b_h = q.b_h; rp.W_out = q.W_out; rp.x0 = h->dX0; rp.ubar = h->dUref; rp.xbar = h->dXref;
-    const size_t l = (2 * (size_t)q.H + n + m) * sizeof(double);
+    const size_t l = fnn_rollout_lds_doubles(n, m, q.H, q.L, q.net) * sizeof(double);
     void (*roll)(FnnRolloutParams) = with_net(q.net, [](auto k) { return k_fnn_rollout<k>; });
     if (l > 64 * 1024) HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(roll), (size_t)(l)));
     hipLaunchKernelGGL(roll, dim3((unsigned)b), dim3(256), l, st, rp);
@@ -3522,15 +3567,16 @@ int almpc_dare(int n, int m, const double* A, const double* B, const double* Q, 
     return ALMPC_OK;
 }
 
-int almpc_fnn_linearize(int device_id, int n, int m, int H, int L, int activation, const double* W_in, const double* W_h,
-                        const double* b_h, const double* W_out, int batch, const double* x, const double* u, double* A,
-                        double* B, double* f) {
+// (dense: almpc_densenet_linearize, activation a bare code; else almpc_fnn_linearize, activation an ALMPC_NET_CODE)
+static int net_linearize(bool dense, int device_id, int n, int m, int H, int L, int activation, const double* W_in, const double* W_h,
+                         const double* b_h, const double* W_out, int batch, const double* x, const double* u, double* A,
+                         double* B, double* f) {
     if (n < 1 || m < 1 || H < 1 || L < 0 || batch < 1 || !W_in || !W_out || !x || !u || !A || !B || (L > 0 && (!W_h || !b_h)))
         return ALMPC_ERR_INVALID;
     int net = NET_FNN;
-    if (!decode_net(activation, &net, &activation)) return ALMPC_ERR_UNSUPPORTED;
+    if (!setup_net(dense, activation, &net, &activation)) return ALMPC_ERR_UNSUPPORTED;
     const size_t nin = (size_t)n + m;
-    if (fnn_wave_scratch_doubles(n, m, H, net) * sizeof(double) > 160 * 1024) return ALMPC_ERR_UNSUPPORTED;
+    if (fnn_wave_scratch_doubles(n, m, H, L, net) * sizeof(double) > 160 * 1024) return ALMPC_ERR_UNSUPPORTED;
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || device_id < 0 || device_id >= count) return ALMPC_ERR_NO_DEVICE;
     if (hipSetDevice(device_id) != hipSuccess) return ALMPC_ERR_HIP;
@@ -3546,8 +3592,8 @@ int almpc_fnn_linearize(int device_id, int n, int m, int H, int L, int activatio
     FnnParams p;
     p.n = n; p.m = m; p.H = H; p.L = L; p.act = activation; p.batch = batch;
     p.ppi = 1; p.xs_group = n; p.us_group = m;
-    p.W_in = up(W_in, (size_t)H * nin); p.W_h = up(W_h, (size_t)L * H * H); p.b_h = up(b_h, (size_t)L * H);
-    p.W_out = up(W_out, (size_t)n * H); p.x = up(x, (size_t)batch * n); p.u = up(u, (size_t)batch * m);
+    p.W_in = up(W_in, (size_t)H * nin); p.W_h = up(W_h, net_wh_doubles(net, H, L)); p.b_h = up(b_h, (size_t)L * H);
+    p.W_out = up(W_out, net_wout_doubles(net, n, H, L)); p.x = up(x, (size_t)batch * n); p.u = up(u, (size_t)batch * m);
     p.A = up(nullptr, (size_t)batch * n * n); p.B = up(nullptr, (size_t)batch * n * m); p.f = f ? up(nullptr, (size_t)batch * n) : nullptr;
     int rc = ALMPC_OK;
     if (!p.W_in || !p.W_h || !p.b_h || !p.W_out || !p.x || !p.u || !p.A || !p.B || (f && !p.f)) rc = ALMPC_ERR_HIP;
@@ -3564,6 +3610,16 @@ int almpc_fnn_linearize(int device_id, int n, int m, int H, int L, int activatio
     }
     for (void* b : bufs) (void)hipFree(b);
     return rc;
+}
+int almpc_fnn_linearize(int device_id, int n, int m, int H, int L, int activation, const double* W_in, const double* W_h,
+                        const double* b_h, const double* W_out, int batch, const double* x, const double* u, double* A,
+                        double* B, double* f) {
+    return net_linearize(false, device_id, n, m, H, L, activation, W_in, W_h, b_h, W_out, batch, x, u, A, B, f);
+}
+int almpc_densenet_linearize(int device_id, int n, int m, int H, int L, int activation, const double* W_in, const double* W_h,
+                             const double* b_h, const double* W_out, int batch, const double* x, const double* u, double* A,
+                             double* B, double* f) {
+    return net_linearize(true, device_id, n, m, H, L, activation, W_in, W_h, b_h, W_out, batch, x, u, A, B, f);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -408,6 +408,16 @@ int almpc_group_relin_fnn_setup(almpc_group* g, int H, int L, int activation, co
         return almpc_relin_fnn_setup(g->hs[i], H, L, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, umin, umax, rho, sigma);
     });
 }
+int almpc_group_relin_densenet_setup(almpc_group* g, int H, int L, int activation, const double* W_in, const double* W_h,
+                                     const double* b_h, const double* W_out, const double* xref, const double* uref, const double* Q,
+                                     const double* R, const double* S, const double* P, const double* umin, const double* umax, double rho,
+                                     double sigma) {
+    if (!g) return ALMPC_ERR_INVALID;
+    return group_fanout(g, [&](int i) {
+        return almpc_relin_densenet_setup(g->hs[i], H, L, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, umin, umax, rho,
+                                          sigma);
+    });
+}
 int almpc_group_relin_fnn_step_async(almpc_group* g, const almpc_opts* opts) {
     if (!g) return ALMPC_ERR_INVALID;
     for (size_t i = 0; i < g->hs.size(); ++i) { const int rc = almpc_relin_fnn_step_async(g->hs[i], opts); if (rc != ALMPC_OK) return gfail(g, rc, (int)i); }
@@ -448,6 +458,17 @@ int almpc_group_sqp_fnn_setup(almpc_group* g, int H, int L, int activation, cons
     return group_fanout(g, [&](int i) {
         return almpc_sqp_fnn_setup(g->hs[i], H, L, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S,
                                    P_per_instance ? P + (size_t)g->first[i] * nn : P, P_per_instance, umin, umax, rho, sigma);
+    });
+}
+int almpc_group_sqp_densenet_setup(almpc_group* g, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
+                                   const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
+                                   const double* S, const double* P, int P_per_instance, const double* umin, const double* umax,
+                                   double rho, double sigma) {
+    if (!g || !P) return ALMPC_ERR_INVALID;
+    const size_t nn = (size_t)g->n * g->n;
+    return group_fanout(g, [&](int i) {
+        return almpc_sqp_densenet_setup(g->hs[i], H, L, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S,
+                                        P_per_instance ? P + (size_t)g->first[i] * nn : P, P_per_instance, umin, umax, rho, sigma);
     });
 }
 int almpc_group_sqp_fnn_start(almpc_group* g, const double* x0, const double* u_guess) {

@@ -285,9 +285,10 @@ __device__ __forceinline__ void fnn_act2(int act, double a, double& d1, double& 
         default: d1 = 1.0; d2 = 0.0; break;
     }
 }
-// (activation sites: L, PolyNet 2 L -- a1 and a2 of every layer)
+// (activation sites: L, PolyNet 2 L -- a1 and a2 of every layer; DenseNet: y, ybar and J have (L+1) H rows)
 __host__ __device__ inline size_t fnn_hess_wave_doubles(int n, int m, int H, int L, int net = NET_FNN) {
     const size_t nin = (size_t)n + m, S = net == NET_POLYNET ? 2 * (size_t)L : (size_t)L;
+    if (net == NET_DENSENET) return nin + (2 * (size_t)(L + 1) + 1) * H + (size_t)(L + 1) * H * nin + 2 * S * H + S * H * nin;
     return nin + 3 * (size_t)H + (size_t)H * nin + 2 * S * H + S * H * nin;
 }
 struct FnnHessParams {
@@ -299,12 +300,103 @@ struct FnnHessParams {
     double* W;                                // [batch][N][(n+m)^2] column-major
 };
 
+// DenseNet (one site per hidden layer, a_l = W_h[l] y_{l+1} + b_h[l], M_l = W_h[l] J_{l+1}): the adjoint of Y starts at W_out' lam and
+// walks back one layer at a time: the site weight is ybar_new act''(a_l) (ybar_new: the adjoint of the H rows layer l appended), and
+// ybar_old += W_h[l]' (act'(a_l) .* ybar_new) lands on the rows the layer read (the layer's rows of Y are not read again).
+// Scratch per wave: z | Y, ybar [(L+1) H] | t [H] | J [(L+1) H][nin] | Aa, Cc [L][H] | M [L][H][nin] (fnn_hess_wave_doubles).
+__device__ __forceinline__ void densenet_lag_hessian(const FnnHessParams& p) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int n = p.n, m = p.m, H = p.H, L = p.L, nin = n + m, R = (L + 1) * H, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double* z = smem + (size_t)wv * fnn_hess_wave_doubles(n, m, H, L, NET_DENSENET);
+    double* Y = z + nin;                  // [R] append order, as k_fnn_jacobian<NET_DENSENET>
+    double* yb = Y + R;                   // [R]
+    double* t = yb + R;                   // [H]
+    double* J = t + H;                    // [R][nin] row-major: d Y / d z
+    double* Aa = J + (size_t)R * nin;     // [L][H] pre-activations
+    double* Cc = Aa + (size_t)L * H;      // [L][H] ybar_new * act''
+    double* M = Cc + (size_t)L * H;       // [L][H][nin] d a_l / d z
+    const long pt = (long)blockIdx.x * 4 + wv;
+    if (pt >= (long)p.batch * p.N) return;   // (wave-uniform; no workgroup barrier below)
+    const long inst = pt / p.N;
+    const int k = (int)(pt % p.N);
+    if (p.done && p.done[inst]) return;
+    auto wsync = []() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
+    for (int c = lane; c < nin; c += 64)
+        z[c] = c < n ? p.xbar[(inst * (p.N + 1) + k) * n + c] : p.ubar[(inst * p.N + k) * m + c - n];
+    wsync();
+    for (int i = lane; i < H; i += 64) {
+        double s = 0.0;
+        for (int c = 0; c < nin; ++c) s += p.W_in[(size_t)c * H + i] * z[c];
+        Y[i] = s;
+    }
+    for (int e = lane; e < H * nin; e += 64) J[e] = p.W_in[(size_t)(e % nin) * H + e / nin];
+    wsync();
+    for (int l = 0; l < L; ++l) {
+        const double* W = p.W_h + densenet_wh_offset(H, l);
+        for (int i = lane; i < H; i += 64) Aa[l * H + i] = densenet_dot(p.b_h[(size_t)l * H + i], W, H, i, Y, 1, H, l + 1);
+        for (int e = lane; e < H * nin; e += 64) {
+            const int i = e / nin, c = e % nin;
+            M[((size_t)l * H + i) * nin + c] = densenet_dot(0.0, W, H, i, J + c, nin, H, l + 1);
+        }
+        wsync();
+        for (int i = lane; i < H; i += 64) {
+            double val, der;
+            fnn_act(p.act, Aa[l * H + i], val, der);
+            Y[(l + 1) * H + i] = val;
+        }
+        for (int e = lane; e < H * nin; e += 64) {
+            double val, der;
+            fnn_act(p.act, Aa[l * H + e / nin], val, der);
+            J[(size_t)(l + 1) * H * nin + e] = M[(size_t)l * H * nin + e] * der;
+        }
+        wsync();
+    }
+    const double* lam = p.lam + (inst * p.N + k) * (size_t)n;
+    for (int e = lane; e < R; e += 64) {   // Y row e = (block q, j) is column (L - q) H + j of W_out
+        const int c = (L - e / H) * H + e % H;
+        double s = 0.0;
+        for (int r = 0; r < n; ++r) s += p.W_out[(size_t)c * n + r] * lam[r];
+        yb[e] = s;
+    }
+    wsync();
+    for (int l = L - 1; l >= 0; --l) {
+        const double* W = p.W_h + densenet_wh_offset(H, l);
+        const double* ob = yb + (size_t)(l + 1) * H;   // ybar_new
+        for (int i = lane; i < H; i += 64) {
+            double d1, d2;
+            fnn_act2(p.act, Aa[l * H + i], d1, d2);
+            Cc[l * H + i] = ob[i] * d2;
+            t[i] = ob[i] * d1;
+        }
+        wsync();
+        for (int c = lane; c < (l + 1) * H; c += 64) {   // column c of W_h[l] read Y row (l - c / H) H + c % H
+            double s = 0.0;
+            for (int i = 0; i < H; ++i) s += W[(size_t)c * H + i] * t[i];
+            const int e = (l - c / H) * H + c % H;
+            yb[e] = yb[e] + s;
+        }
+        wsync();
+    }
+    double* Wo = p.W + pt * (size_t)nin * nin;
+    for (int e = lane; e < nin * nin; e += 64) {
+        const int r = e % nin, c = e / nin;
+        double s = 0.0;
+        for (int l = 0; l < L; ++l)
+            for (int i = 0; i < H; ++i) {
+                const double* Mi = M + ((size_t)l * H + i) * nin;
+                s += (Mi[r] * Mi[c]) * Cc[l * H + i];
+            }
+        Wo[e] = s;
+    }
+}
+
 // ResNet: one site per layer, y' = y + act(a):  J' = J + diag(act') M,  ybar = ybar' + W' (act' .* ybar'),  site weight ybar' act''.
 // PolyNet: two sites per layer, a1 = W y + b and a2 = W p + b (p = act(a1), M2 = W diag(act'(a1)) M1, J' = J + diag(act'(a1)) M1 +
 // diag(act'(a2)) M2); backwards  pbar = ybar' + W' (act'(a2) .* ybar'),  ybar = ybar' + W' (act'(a1) .* pbar),  site weights
 // ybar' act''(a2) and pbar act''(a1).  Site s of layer l is l (Fnn, ResNet) or 2 l + {0, 1} (PolyNet).
 template <int NET>
 __global__ __launch_bounds__(256) void k_fnn_lag_hessian(FnnHessParams p) {
+    if constexpr (NET == NET_DENSENET) return densenet_lag_hessian(p);   // (its own body, above)
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int SPL = NET == NET_POLYNET ? 2 : 1;   // sites per layer
     const int n = p.n, m = p.m, H = p.H, L = p.L, S = SPL * L, nin = n + m, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -597,9 +689,56 @@ struct FnnRolloutParams {
     const double* ubar;   // [batch][N][m]
     double* xbar;         // [batch][(N+1)][n]
 };
+// LDS of k_fnn_rollout: y, yn | z (DenseNet: Y [(L+1) H] | z)
+__host__ __device__ inline size_t fnn_rollout_lds_doubles(int n, int m, int H, int L, int net = NET_FNN) {
+    return (net == NET_DENSENET ? (size_t)(L + 1) * H : 2 * (size_t)H) + n + m;
+}
+
+// DenseNet rollout: Y [(L+1) H] in append order, z [nin] (fnn_rollout_lds_doubles); every layer appends its H rows, one barrier each
+__device__ __forceinline__ void densenet_rollout(const FnnRolloutParams& p) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int n = p.n, m = p.m, H = p.H, L = p.L, nin = n + m;
+    double* Y = smem;                          // [(L+1) H]
+    double* z = Y + (size_t)(L + 1) * H;       // [nin]
+    const size_t inst = blockIdx.x;
+    double* xb = p.xbar + inst * (size_t)(p.N + 1) * n;
+    const double* ub = p.ubar + inst * (size_t)p.N * m;
+    for (int t = threadIdx.x; t < n; t += blockDim.x) {
+        const double v = p.x0[inst * n + t];
+        z[t] = v;
+        xb[t] = v;
+    }
+    __syncthreads();
+    for (int k = 0; k < p.N; ++k) {
+        for (int t = threadIdx.x; t < m; t += blockDim.x) z[n + t] = ub[k * m + t];
+        __syncthreads();
+        for (int i = threadIdx.x; i < H; i += blockDim.x) {
+            double s = 0.0;
+            for (int c = 0; c < nin; ++c) s += p.W_in[(size_t)c * H + i] * z[c];
+            Y[i] = s;
+        }
+        __syncthreads();
+        for (int l = 0; l < L; ++l) {
+            const double* W = p.W_h + densenet_wh_offset(H, l);
+            for (int i = threadIdx.x; i < H; i += blockDim.x) {
+                double val, der;
+                fnn_act(p.act, densenet_dot(p.b_h[(size_t)l * H + i], W, H, i, Y, 1, H, l + 1), val, der);
+                Y[(size_t)(l + 1) * H + i] = val;
+            }
+            __syncthreads();
+        }
+        for (int i = threadIdx.x; i < n; i += blockDim.x) {
+            const double s = densenet_dot(0.0, p.W_out, n, i, Y, 1, H, L + 1);
+            z[i] = s;
+            xb[(size_t)(k + 1) * n + i] = s;
+        }
+        __syncthreads();
+    }
+}
 
 template <int NET>
 __global__ __launch_bounds__(256) void k_fnn_rollout(FnnRolloutParams p) {
+    if constexpr (NET == NET_DENSENET) return densenet_rollout(p);   // (its own body, above)
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int n = p.n, m = p.m, H = p.H, nin = n + m;
     double* y = smem;        // [H]

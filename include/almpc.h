@@ -281,6 +281,12 @@ int almpc_sqp_fnn_setup(almpc_handle* h, int H, int L, int activation, const dou
                         const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
                         const double* S, const double* P, int P_per_instance, const double* umin, const double* umax, double rho,
                         double sigma);
+/* almpc_sqp_fnn_setup for a DenseNet (weight layout and `activation`: almpc_densenet_linearize); the other almpc_sqp_fnn_* calls
+ * then run it */
+int almpc_sqp_densenet_setup(almpc_handle* h, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
+                             const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
+                             const double* S, const double* P, int P_per_instance, const double* umin, const double* umax, double rho,
+                             double sigma);
 int almpc_sqp_fnn_start(almpc_handle* h, const double* x0, const double* u_guess);
 int almpc_sqp_fnn_iterate(almpc_handle* h, int iters, double step_scale, const almpc_opts* opts, double* step_inf,
                           double* defect_inf);
@@ -355,6 +361,11 @@ int almpc_sqp_fnn_set_structured(almpc_handle* h, int on);
 int almpc_relin_fnn_setup(almpc_handle* h, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
                           const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
                           const double* S, const double* P, const double* umin, const double* umax, double rho, double sigma);
+/* almpc_relin_fnn_setup for a DenseNet (weight layout and `activation`: almpc_densenet_linearize), condensed or structured handle;
+ * the other almpc_relin_fnn_* calls then run it */
+int almpc_relin_densenet_setup(almpc_handle* h, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
+                               const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
+                               const double* S, const double* P, const double* umin, const double* umax, double rho, double sigma);
 int almpc_relin_fnn_step(almpc_handle* h, const almpc_opts* opts);
 int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts);
 int almpc_relin_fnn_advance(almpc_handle* h);
@@ -487,6 +498,10 @@ int almpc_group_design_batched(almpc_group* g, const double* A_batch, const doub
 int almpc_group_relin_fnn_setup(almpc_group* g, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
                                 const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
                                 const double* S, const double* P, const double* umin, const double* umax, double rho, double sigma);
+int almpc_group_relin_densenet_setup(almpc_group* g, int H, int L, int activation, const double* W_in, const double* W_h,
+                                     const double* b_h, const double* W_out, const double* xref, const double* uref, const double* Q,
+                                     const double* R, const double* S, const double* P, const double* umin, const double* umax, double rho,
+                                     double sigma);
 int almpc_group_relin_fnn_step(almpc_group* g, const almpc_opts* opts);
 int almpc_group_relin_fnn_step_async(almpc_group* g, const almpc_opts* opts);
 int almpc_group_relin_fnn_advance(almpc_group* g);
@@ -499,6 +514,10 @@ int almpc_group_sqp_fnn_setup(almpc_group* g, int H, int L, int activation, cons
                               const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
                               const double* S, const double* P, int P_per_instance, const double* umin, const double* umax, double rho,
                               double sigma);
+int almpc_group_sqp_densenet_setup(almpc_group* g, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
+                                   const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
+                                   const double* S, const double* P, int P_per_instance, const double* umin, const double* umax,
+                                   double rho, double sigma);
 int almpc_group_sqp_fnn_start(almpc_group* g, const double* x0, const double* u_guess);
 int almpc_group_sqp_fnn_iterate(almpc_group* g, int iters, double step_scale, const almpc_opts* opts, double* step_inf,
                                 double* defect_inf);
@@ -586,6 +605,23 @@ int almpc_dare(int n, int m, const double* A, const double* B, const double* Q, 
 int almpc_fnn_linearize(int device_id, int n, int m, int H, int L, int activation, const double* W_in,
                         const double* W_h, const double* b_h, const double* W_out, int batch, const double* x,
                         const double* u, double* A, double* B, double* f);
+
+/*
+ * DenseNet (.../densenet/mpc_modeler_implementation_densenet.jl:85-161): its layer widths grow, so it has its own weight layout and
+ * its own setup calls (almpc_densenet_linearize, almpc_relin_densenet_setup, almpc_sqp_densenet_setup and their almpc_group_*
+ * forms) instead of a network code; `activation` is a bare code 0..4 (anything else: ALMPC_ERR_UNSUPPORTED).  With z = [x; u]:
+ *     y_1 = W_in z,   y_{l+2} = [act(W_h[l] y_{l+1} + b_h[l]); y_{l+1}]  (l = 0..L-1: the new features first),   x+ = W_out y_{L+1}
+ * so y_{l+1} has (l+1) H rows.  Column-major:
+ *     W_in   H x (n+m)
+ *     W_h    L blocks; block l is H x (l+1) H at offset H^2 l (l+1) / 2; its column c multiplies entry c of y_{l+1} (newest first)
+ *     b_h    [L][H]
+ *     W_out  n x (L+1) H
+ * After setup the handle runs every other call of its family as for an Fnn.  Exact-Hessian mode has the per-wave scratch budget
+ * of almpc_sqp_fnn_set_hessian (y, its adjoint and d y / d z have (L+1) H rows).
+ */
+int almpc_densenet_linearize(int device_id, int n, int m, int H, int L, int activation, const double* W_in,
+                             const double* W_h, const double* b_h, const double* W_out, int batch, const double* x,
+                             const double* u, double* A, double* B, double* f);
 
 /*
  * Multi-GPU: one process per GPU, each with its own handle on its contiguous shard of the batch; instances never interact, so no

@@ -27,6 +27,10 @@ const libalmpc = get(ENV, "ALMPC_LIB", "libalmpc.so")
 # Fnn weight layout and differ in the hidden layer: :fnn (also Icnn), :resnet y' = y + act(a), :polynet p = act(a), y' = y + p + act(W p + b).
 const NET_KINDS = Dict(:fnn => 0, :resnet => 1, :polynet => 2)
 net_code(net::Symbol, activation::Integer) = (NET_KINDS[net] << 8) | Int(activation)
+# net = :densenet: a DenseNet (y_{l+1} = [act(W_h[l] y_l + b_h[l]); y_l], new features first) has its own weight layout and its own
+# setup calls (the almpc_*densenet* entry points, a bare `activation`), not a network code.  `W_h` is then a vector of the L blocks,
+# block l H x l H (1-based), packed column-major one after another (include/almpc.h); `W_out` is n x (L+1) H.
+densenet_pack(W_h::AbstractVector{<:AbstractMatrix}) = isempty(W_h) ? zeros(1) : Vector{Float64}(reduce(vcat, vec.(W_h)))
 
 struct hip_solver_def end            # new tag, to be made <: AbstractSolvers in src/types/types.jl:162-192
 
@@ -159,15 +163,23 @@ end
 NonLinearProgramming branch for an Fnn model (src/sub/model_modeler_implementation/fnn/mpc_modeler_implementation_fnn.jl:73-189,
 which the reference solves with Ipopt): the same NLP by Gauss-Newton SQP on the device.  `W_in` H x (n+m), `W_h` H x H x L,
 `b_h` H x L, `W_out` n x H as read from Flux.params (:88-107); `activation` 0 identity, 1 relu, 2 tanh, 3 sigmoid, 4 swish;
-keyword `net` (:fnn, :resnet, :polynet) the network kind in the same layout (`net_code`).
+keyword `net` (:fnn, :resnet, :polynet) the network kind in the same layout (`net_code`), or :densenet (`densenet_pack`).
 Then per step:  `sqp_start!(mod, x0)`;  `sqp_iterate!(mod, iters)`;  results through `calculate!`'s readers (`almpc_get_results`).
 """
-function design_sqp_fnn!(mod::HipModeler, W_in::Matrix{Float64}, W_h::Array{Float64,3}, b_h::Matrix{Float64}, W_out::Matrix{Float64},
+function design_sqp_fnn!(mod::HipModeler, W_in::Matrix{Float64}, W_h::Union{Array{Float64,3},Vector{Matrix{Float64}}}, b_h::Matrix{Float64}, W_out::Matrix{Float64},
                          activation::Integer, Q::Matrix{Float64}, R::Matrix{Float64}, S::Matrix{Float64}, P::Matrix{Float64},
                          umin::Vector{Float64}, umax::Vector{Float64}; x_ref::Matrix{Float64}, u_ref::Matrix{Float64}, net::Symbol = :fnn,
                          structured_qp::Bool = false)
     # structured_qp: every iteration's QP in the multiple-shooting form (k_riccati) instead of the condensed one
     check(mod.handle, ccall((:almpc_sqp_fnn_set_structured, libalmpc), Cint, (Ptr{Cvoid}, Cint), mod.handle, structured_qp ? 1 : 0))
+    if net === :densenet
+        check(mod.handle, ccall((:almpc_sqp_densenet_setup, libalmpc), Cint,
+                       (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                        Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
+                       mod.handle, size(W_in, 1), length(W_h), activation, W_in, densenet_pack(W_h), b_h, W_out, x_ref, u_ref, Q, R, S, P, 0,
+                       umin, umax, mod.opts.rho, mod.opts.sigma))
+        return mod
+    end
     check(mod.handle, ccall((:almpc_sqp_fnn_setup, libalmpc), Cint,
                    (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
@@ -349,9 +361,17 @@ BASELINE configs[3]: the black-box model is re-linearised at every instance's ow
 (`almpc_relin_fnn_*`).  `P` as the reference takes it: DARE at the linearisation about the LAST reference
 (src/sub/design_mpc.jl:312-327).  Then per step: `update_initialization!(mod, X0)`; `relin_step!(mod)`; `read_results!`.
 """
-function design_relin_fnn!(mod::HipModeler, W_in::Matrix{Float64}, W_h::Array{Float64,3}, b_h::Matrix{Float64}, W_out::Matrix{Float64},
-                           activation::Integer, Q::Matrix{Float64}, R::Matrix{Float64}, S::Matrix{Float64}, P::Matrix{Float64},
+function design_relin_fnn!(mod::HipModeler, W_in::Matrix{Float64}, W_h::Union{Array{Float64,3},Vector{Matrix{Float64}}}, b_h::Matrix{Float64},
+                           W_out::Matrix{Float64}, activation::Integer, Q::Matrix{Float64}, R::Matrix{Float64}, S::Matrix{Float64}, P::Matrix{Float64},
                            umin::Vector{Float64}, umax::Vector{Float64}; x_ref::Matrix{Float64}, u_ref::Matrix{Float64}, net::Symbol = :fnn)
+    if net === :densenet
+        check(mod.handle, ccall((:almpc_relin_densenet_setup, libalmpc), Cint,
+                       (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                        Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
+                       mod.handle, size(W_in, 1), length(W_h), activation, W_in, densenet_pack(W_h), b_h, W_out, x_ref, u_ref, Q, R, S, P,
+                       umin, umax, mod.opts.rho, mod.opts.sigma))
+        return mod
+    end
     check(mod.handle, ccall((:almpc_relin_fnn_setup, libalmpc), Cint,
                    (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
@@ -474,10 +494,18 @@ function design_ltv!(mod::HipModeler, A_all::Array{Float64,4}, B_all::Array{Floa
     return mod
 end
 "Jacobians (A_i, B_i) and values of an Fnn at `x` (n x batch), `u` (m x batch) on device `device` (the batched `proceed_system_linearization`)"
-function fnn_linearize(W_in::Matrix{Float64}, W_h::Array{Float64,3}, b_h::Matrix{Float64}, W_out::Matrix{Float64}, activation::Integer,
-                       x::Matrix{Float64}, u::Matrix{Float64}; device::Integer = 0, net::Symbol = :fnn)
+function fnn_linearize(W_in::Matrix{Float64}, W_h::Union{Array{Float64,3},Vector{Matrix{Float64}}}, b_h::Matrix{Float64}, W_out::Matrix{Float64},
+                       activation::Integer, x::Matrix{Float64}, u::Matrix{Float64}; device::Integer = 0, net::Symbol = :fnn)
     n, m, b = size(x, 1), size(u, 1), size(x, 2)
     A, B, f = Array{Float64,3}(undef, n, n, b), Array{Float64,3}(undef, n, m, b), Matrix{Float64}(undef, n, b)
+    if net === :densenet
+        rc = ccall((:almpc_densenet_linearize, libalmpc), Cint,
+                   (Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                   device, n, m, size(W_in, 1), length(W_h), activation, W_in, densenet_pack(W_h), b_h, W_out, b, x, u, A, B, f)
+        rc == 0 || error("almpc_densenet_linearize failed ($rc)")
+        return A, B, f
+    end
     rc = ccall((:almpc_fnn_linearize, libalmpc), Cint,
                (Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64},
                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
@@ -647,9 +675,17 @@ function group_design_batched!(g::HipGroup, A_batch::Array{Float64,3}, B_batch::
 end
 
 "`design_relin_fnn!` on every device (BASELINE configs[3]); then `group_relin_step!`, `group_relin_advance!`"
-function group_design_relin_fnn!(g::HipGroup, W_in::Matrix{Float64}, W_h::Array{Float64,3}, b_h::Matrix{Float64}, W_out::Matrix{Float64},
-                                 activation::Integer, Q::Matrix{Float64}, R::Matrix{Float64}, S::Matrix{Float64}, P::Matrix{Float64},
+function group_design_relin_fnn!(g::HipGroup, W_in::Matrix{Float64}, W_h::Union{Array{Float64,3},Vector{Matrix{Float64}}}, b_h::Matrix{Float64},
+                                 W_out::Matrix{Float64}, activation::Integer, Q::Matrix{Float64}, R::Matrix{Float64}, S::Matrix{Float64}, P::Matrix{Float64},
                                  umin::Vector{Float64}, umax::Vector{Float64}; x_ref::Matrix{Float64}, u_ref::Matrix{Float64}, net::Symbol = :fnn)
+    if net === :densenet
+        gcheck(g.group, ccall((:almpc_group_relin_densenet_setup, libalmpc), Cint,
+                       (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                        Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
+                       g.group, size(W_in, 1), length(W_h), activation, W_in, densenet_pack(W_h), b_h, W_out, x_ref, u_ref, Q, R, S, P,
+                       umin, umax, g.opts.rho, g.opts.sigma))
+        return g
+    end
     gcheck(g.group, ccall((:almpc_group_relin_fnn_setup, libalmpc), Cint,
                    (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
@@ -671,11 +707,19 @@ group_relin_advance!(g::HipGroup) = gcheck(g.group, ccall((:almpc_group_relin_fn
 group_advance_plant!(g::HipGroup) = gcheck(g.group, ccall((:almpc_group_advance_plant, libalmpc), Cint, (Ptr{Cvoid},), g.group))
 
 "`design_sqp_fnn!` on every device (BASELINE configs[4]); `P` n x n or n x n x batch"
-function group_design_sqp_fnn!(g::HipGroup, W_in::Matrix{Float64}, W_h::Array{Float64,3}, b_h::Matrix{Float64}, W_out::Matrix{Float64},
+function group_design_sqp_fnn!(g::HipGroup, W_in::Matrix{Float64}, W_h::Union{Array{Float64,3},Vector{Matrix{Float64}}}, b_h::Matrix{Float64}, W_out::Matrix{Float64},
                                activation::Integer, Q::Matrix{Float64}, R::Matrix{Float64}, S::Matrix{Float64}, P::Array{Float64},
                                umin::Vector{Float64}, umax::Vector{Float64}; x_ref::Matrix{Float64}, u_ref::Matrix{Float64}, net::Symbol = :fnn,
                                structured_qp::Bool = false)
     gcheck(g.group, ccall((:almpc_group_sqp_fnn_set_structured, libalmpc), Cint, (Ptr{Cvoid}, Cint), g.group, structured_qp ? 1 : 0))
+    if net === :densenet
+        gcheck(g.group, ccall((:almpc_group_sqp_densenet_setup, libalmpc), Cint,
+                       (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                        Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
+                       g.group, size(W_in, 1), length(W_h), activation, W_in, densenet_pack(W_h), b_h, W_out, x_ref, u_ref, Q, R, S, P,
+                       ndims(P) == 3 ? 1 : 0, umin, umax, g.opts.rho, g.opts.sigma))
+        return g
+    end
     gcheck(g.group, ccall((:almpc_group_sqp_fnn_setup, libalmpc), Cint,
                    (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
