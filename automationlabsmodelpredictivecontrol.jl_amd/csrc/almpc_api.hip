@@ -77,8 +77,6 @@ struct almpc_handle {
     bool state_valid = true;      // xs / ys hold the ADMM state of the last step (a warm start may use them)
     int num_cus = 256;            // persistent-grid size of k_polish<true>
     int polish_no_glds = 0;       // diagnostic: force the G-through-L2 build (ALMPC_POLISH_NO_GLDS=1)
-    int skip_admm = 0;            // transient (SQP iterations after the first): guess from the iterate, no ADMM phase, no KKT inverse;
-                                  // 2 (re-linearisation pipeline, warm steps): guess = the previous step's inputs shifted by one stage
     int fuse_step = 1;            // one kernel per step when the shape allows (almpc_set_step_fusion / ALMPC_NO_FUSED_STEP=1)
     double* dSglobal = nullptr;  // polish scratch for working sets beyond 32 rows
     int32_t* dStartRows = nullptr;   // [batch][65] row list of a guessed working set whose inverse sits in dSglobal (k_guess_iterate_ws)
@@ -155,27 +153,28 @@ struct almpc_handle {
     // structured (Riccati) solve: the handle's only solver (ALMPC_FLAG_STRUCTURED) or the fallback for instances the condensed path
     // leaves unsolved (almpc_set_structured_fallback)
     bool structured = false;
-    // lazy redo (fallback == 2 on the shared-model, input-box-only path, whose steps are tens of microseconds and leave an instance
-    // unsolved only in corner cases): the finish counts such instances into a host-visible word; the redo kernels are launched at the
-    // next host sync point only when the count has moved -- no extra launch on the step path (measured: two idle redo launches cost
-    // 14 us per 61 us step)
-    int* hUnsolved = nullptr;      // pinned host word
-    int* dUnsolved = nullptr;      // the device's address of it
-    int unsolved_seen = 0;
-    bool lazy_pending = false;
-    bool redo_x0_from_results = false;   // set around the launches of a lazy redo: x0 = stage 1 of the step's own x (the caller may have
-                                         // handed over the next x0 since)
-    // Gated redo (round 5): where results leave without a synchronous host look -- the asynchronous tickets (almpc_get_results_async)
-    // and the device-resident loops (almpc_advance_plant, almpc_relin_fnn_advance) -- the redo launches are enqueued behind the step
-    // with a GATE: the finish of step s stores s in dRedoGate when it leaves an instance undecided, and a gated launch returns at once
-    // unless the word holds its step's number.  Every read path hands out "solution or verdict" (src/main/computation_mpc.jl:41-53)
-    // at the cost of two (three with per-instance stage records) empty launches per step on those paths only.
-    int* dRedoGate = nullptr;
-    int step_serial = 0;                 // number of the last enqueued step (1, 2, ...)
-    bool redo_gate_on = false;           // set around the launches of a gated redo
-    bool redo_expected = false;          // the last synchronous look found undecided instances (see wait_and_settle)
-    bool redo_predicted = false;         // set around the launches of a gated redo that is EXPECTED to have work (tier policy of a plain redo)
-    bool flag_in_finish = false;   // transient (re-linearisation step): the finish turns a flagged design into ALMPC_NON_FINITE itself
+    // Redo of the instances a condensed step leaves undecided (fallback == 2 on the shared-model / input-box-only path, whose steps are
+    // tens of microseconds and leave an instance unsolved only in corner cases).  The finish counts such instances into a pinned word
+    // and stores the step's number in the gate word; the redo kernels are launched only when there is work -- no extra launch on the
+    // step path (measured: two idle redo launches cost 14 us per 61 us step).  Transitions:
+    //  - a step (run_step) numbers itself (step_serial += 1) and, if its redo is deferred, sets lazy_pending;
+    //  - resolve_lazy_redo (a synchronous look, stream idle): clears lazy_pending; if the count moved since unsolved_seen, takes the new
+    //    count and redoes the undecided instances now; redo_expected = whether it moved;
+    //  - enqueue_gated_redo (tickets, almpc_advance_plant, almpc_relin_fnn_advance: results leave without a host look): enqueues the
+    //    redo behind the step GATED -- a gated launch returns at once unless the gate word holds its step's number -- and clears
+    //    lazy_pending.  Every read path hands out "solution or verdict" (src/main/computation_mpc.jl:41-53) at the cost of two (three
+    //    with per-instance stage records) empty launches per step on those paths only;
+    //  - wait_and_settle: when redo_expected, the gated redo goes out before the wait (predicted), then the count is taken as above;
+    //  - drop_lazy_redo (a new design): clears lazy_pending and redo_expected, takes the count.
+    struct Redo {
+        int* hUnsolved = nullptr;      // pinned host word: instances left undecided, counted by the finishes
+        int* dUnsolved = nullptr;      // the device's address of it
+        int* dGate = nullptr;          // gate word: number of the last step that left an instance undecided
+        int unsolved_seen = 0;         // the count at the last look
+        int step_serial = 0;           // number of the last enqueued step (1, 2, ...)
+        bool lazy_pending = false;     // the last step's redo is deferred and not yet settled
+        bool expected = false;         // the last synchronous look found undecided instances (see wait_and_settle)
+    } redo;
     int fallback = 2;   // 0 off, 1 asked for (a design it cannot serve is an error), 2 default: on wherever the stage-wise solvers cover the design
     double *rQ = nullptr, *rR = nullptr, *rP = nullptr, *rKst = nullptr, *rPst = nullptr;   // device copies of Q, R (branch rule applied), shared P; gain scratch
     double* rGuess = nullptr;   // [batch][N][m] start of the next structured solve (almpc_set_start_from / opts.warm_start), else nullptr
@@ -207,7 +206,7 @@ struct almpc_handle {
         int32_t* start_ws = nullptr;   // [batch][64] working sets the state-row finish of the LAST step gave up with (PolishGenParams::redo_ws)
         bool start_ws_fresh = false;   // ... written by the last enqueued step (cleared by every step that does not run that finish)
         double* sinv_glb = nullptr; size_t sinv_cap = 0;   // third tier: Sinv of 128 x 129 per wave of its grid
-        double* ghat = nullptr; size_t ghat_cap = 0; bool ghat_ready = false, ghat_building = false, ghat_wanted = false;   // shared model: cached sweep responses [TP][TP] (k_sdual: SdualParams::ghat)
+        double* ghat = nullptr; size_t ghat_cap = 0; bool ghat_ready = false, ghat_wanted = false;   // shared model: cached sweep responses [TP][TP] (k_sdual: SdualParams::ghat)
         std::vector<double> S;               // symmetrised S (base terms of time-varying input references)
         // reachability screen of the state box (k_state_box_screen): tables of the shared model and references, verdicts per instance
         double *scr_phi = nullptr, *scr_g = nullptr, *scr_rm = nullptr, *scr_rp = nullptr;
@@ -344,8 +343,8 @@ void free_all(almpc_handle* h) {
         if (p) (void)hipFree(p);
     if (h->ev_guess) (void)hipEventDestroy(h->ev_guess);
     if (h->ev_guess_done) (void)hipEventDestroy(h->ev_guess_done);
-    if (h->hUnsolved) (void)hipHostFree(h->hUnsolved);
-    if (h->dRedoGate) (void)hipFree(h->dRedoGate);
+    if (h->redo.hUnsolved) (void)hipHostFree(h->redo.hUnsolved);
+    if (h->redo.dGate) (void)hipFree(h->redo.dGate);
     for (auto& e : h->ev)
         if (e) (void)hipEventDestroy(e);
     h->ev.clear();
@@ -459,8 +458,16 @@ bool riccati_shape_ok(const almpc_handle* h) {
     return h->n <= 32 && h->m <= 16 && (long)h->m * h->N <= 1024 && riccati_lds_doubles(h->n, h->m, h->N) * sizeof(double) <= 160 * 1024;
 }
 
+// What a launch of the stage-wise solvers is for, beyond the plain solve (by value: a nested launch does not inherit it)
+struct SolveMode {
+    bool x0_from_results = false;   // a deferred redo: x0 = stage 1 of the step's own x (the caller may have handed over the next x0 since)
+    bool gated = false;             // enqueued behind the step: returns at once unless the step left an instance undecided (almpc_handle::Redo)
+    bool predicted = false;         // a gated redo that is EXPECTED to have work (tier policy of a plain redo)
+    bool build_ghat = false;        // k_sdual's build of the cached responses (sdual_build_ghat): never gated
+};
+
 // k_riccati over the batch (filter = 0) or over the instances whose status is not 0 (filter = 1, start = the step's own result)
-hipError_t launch_riccati(almpc_handle* h, int filter, const double* guess, int max_iter) {
+hipError_t launch_riccati(almpc_handle* h, int filter, const double* guess, int max_iter, SolveMode mode = {}) {
     RiccatiParams rp;
     rp.n = h->n; rp.m = h->m; rp.N = h->N; rp.batch = h->batch;
     const bool pi = h->batched && !h->structured ? true : h->batched;
@@ -472,8 +479,8 @@ hipError_t launch_riccati(almpc_handle* h, int filter, const double* guess, int 
     rp.umin = h->dUmin; rp.umax = h->dUmax;
     rp.uref = h->dUref; rp.uref_stride = h->uref_stride; rp.xref = h->dXref; rp.xref_stride = h->xref_stride;
     rp.x0 = h->dX0; rp.x0_stride = h->n; rp.uguess = guess; rp.filter = filter; rp.Kst = h->rKst; rp.Pst = h->rPst;
-    if (h->redo_x0_from_results) { rp.x0 = h->dX; rp.x0_stride = (long)h->n * (h->N + 1); }   // (lazy redo: see resolve_lazy_redo)
-    if (h->redo_gate_on) { rp.gate = h->dRedoGate; rp.gate_val = h->step_serial; }
+    if (mode.x0_from_results) { rp.x0 = h->dX; rp.x0_stride = (long)h->n * (h->N + 1); }
+    if (mode.gated) { rp.gate = h->redo.dGate; rp.gate_val = h->redo.step_serial; }
     rp.x = h->dX; rp.ex = h->dEx; rp.u = h->dU; rp.eu = h->dEu; rp.status = h->dStatus; rp.piters = h->dPiters;
     rp.max_iter = max_iter > 0 ? max_iter : 20 * h->N * h->m + 50;
     rp.tol = 1e-9;
@@ -531,7 +538,8 @@ bool sdual_shape_ok(int n, int m, int N, bool useS) {
 
 // Stage records of a SHARED model on the device (host Riccati, design time), state box / terminal equality / S of the design.
 // Rm: the reference's branch rule applied (zeros when R[1,1] == 0); Sm null: no input-rate term.
-hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int max_iter, bool single_launch = false, int first_tier = 0);
+hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int max_iter, bool single_launch = false, int first_tier = 0,
+                        SolveMode mode = {});
 hipError_t sdual_build_ghat(almpc_handle* h);
 
 int sdual_setup_shared(almpc_handle* h, const hm::mat& Am, const hm::mat& Bm, const hm::mat& Qm, const hm::mat& Rm, const hm::mat* Sm,
@@ -601,9 +609,9 @@ hipError_t sdual_build_ghat(almpc_handle* h) {
     }
     hipError_t e = hipMemsetAsync(sd.ghat, 0, TP * TP * sizeof(double), h->stream);
     if (e != hipSuccess) return e;
-    sd.ghat_building = true;
-    e = launch_sdual(h, 0, nullptr, 0);
-    sd.ghat_building = false;
+    SolveMode build;
+    build.build_ghat = true;
+    e = launch_sdual(h, 0, nullptr, 0, false, 0, build);
     if (e != hipSuccess) return e;
     sd.ghat_ready = true;
     return hipSuccess;
@@ -697,7 +705,7 @@ int sdual_setup_batched(almpc_handle* h, const hm::mat& Qm, const hm::mat& Rm, c
 
 // k_sgains over the handle's per-instance models (bA, bB; terminal weights bP, shared or per instance): all instances
 // (filter 0) or the ones the condensed step left unsolved (filter 1)
-hipError_t launch_sgains(almpc_handle* h, int filter) {
+hipError_t launch_sgains(almpc_handle* h, int filter, SolveMode mode = {}) {
     const almpc_handle::Sd& sd = h->sd;
     SgainsParams gp;
     std::memset(&gp, 0, sizeof(gp));
@@ -712,7 +720,7 @@ hipError_t launch_sgains(almpc_handle* h, int filter) {
     gp.rec = sd.rec; gp.rec_stride = sd.rec_stride;
     gp.pc = nullptr; gp.ct = nullptr; gp.pc_stride = 0;
     gp.bad = sd.bad;
-    if (h->redo_gate_on) { gp.gate = h->dRedoGate; gp.gate_val = h->step_serial; }
+    if (mode.gated) { gp.gate = h->redo.dGate; gp.gate_val = h->redo.step_serial; }
     if (sd.sqp) {   // the QP of the current SQP iteration: stage models, defects, state errors and input gradient of the loop
         const almpc_handle::Sqp& q = h->sqp;
         const long N = h->N;
@@ -816,9 +824,9 @@ hipError_t launch_sdual_t(almpc_handle* h, SdualParams sp, int tier0, int tier1)
 
 // k_sdual over the batch (filter 0), over the instances whose status is not 0 (filter 1: redo after the condensed path), start from
 // `guess` (inputs [batch][N][m]) when given
-hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int max_iter, bool single_launch, int first_tier) {
+hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int max_iter, bool single_launch, int first_tier, SolveMode mode) {
     if (!h->sd.ready) return hipErrorInvalidValue;
-    if (h->sd.ghat_wanted && !h->sd.ghat_ready && !h->sd.ghat_building && !h->sd.per_instance && !h->sd.sqp) {   // first use on a condensed handle
+    if (h->sd.ghat_wanted && !h->sd.ghat_ready && !mode.build_ghat && !h->sd.per_instance && !h->sd.sqp) {   // first use on a condensed handle
         const hipError_t eb = sdual_build_ghat(h);
         if (eb != hipSuccess) return eb;
     }
@@ -834,8 +842,8 @@ hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int ma
     sp.xbref = h->dXref; sp.xbref_stride = h->xref_stride;
     sp.eqt = sd.has_eq ? h->dXref + (size_t)h->N * h->n : nullptr; sp.eqt_stride = h->xref_stride;   // x_N = x_ref_N
     sp.x0 = h->dX0; sp.x0_stride = h->n; sp.xref = h->dXref; sp.xref_stride = h->xref_stride;
-    if (h->redo_x0_from_results) { sp.x0 = h->dX; sp.x0_stride = (long)h->n * (h->N + 1); }   // (lazy redo: see resolve_lazy_redo)
-    if (h->redo_gate_on) { sp.gate = h->dRedoGate; sp.gate_val = h->step_serial; }
+    if (mode.x0_from_results) { sp.x0 = h->dX; sp.x0_stride = (long)h->n * (h->N + 1); }
+    if (mode.gated) { sp.gate = h->redo.dGate; sp.gate_val = h->redo.step_serial; }
     sp.uguess = guess; sp.filter = filter; sp.flag = nullptr; sp.v_only = 0;
     if (filter == 1 && sd.start_ws && sd.start_ws_fresh && !sd.sqp) sp.start_ws = sd.start_ws;   // (the redo behind a state-row finish)
     sp.x = h->dX; sp.ex = h->dEx; sp.u = h->dU; sp.eu = h->dEu; sp.status = h->dStatus; sp.piters = h->dPiters;
@@ -850,7 +858,7 @@ hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int ma
     sp.ovf = sd.ovf; sp.only_ovf = 0; sp.wsave = sd.wsave;
     sp.gbad = sd.per_instance ? sd.bad : nullptr;
     sp.ghat = (sd.ghat_ready && !sd.per_instance && !sd.sqp && sd.rec_stride == 0) ? sd.ghat : nullptr;
-    if (sd.ghat_building) {   // design time: the waves walk the coordinates (no instance data is read)
+    if (mode.build_ghat) {   // design time: the waves walk the coordinates (no instance data is read)
         const int TP = sdual_tp(sd.NT, sd.MC, h->N);
         sp.build_ghat = 1; sp.ghat_out = sd.ghat; sp.ghat = nullptr;
         sp.batch = TP < 2048 ? TP : 2048;
@@ -865,7 +873,7 @@ hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int ma
     sp.rows_state = (sd.has_box || sd.has_eq) ? 1 : 0;
     // state box of a shared model with shared references, every instance solved from scratch: the reachability screen first (one
     // table kernel per design / reference change, one small launch per solve) -- instances it certifies infeasible never reach a sweep
-    if (sd.has_box && !sd.ghat_building && !sd.per_instance && !sd.sqp && filter == 0 && first_tier == 0 && sp.x0 && h->uref_stride == 0 &&
+    if (sd.has_box && !mode.build_ghat && !sd.per_instance && !sd.sqp && filter == 0 && first_tier == 0 && sp.x0 && h->uref_stride == 0 &&
         h->xref_stride == 0 && h->dA && h->dB && !getenv("ALMPC_SDUAL_NO_SCREEN")) {
         almpc_handle::Sd& sdw = h->sd;
         const size_t n_ = (size_t)h->n, m_ = (size_t)h->m, N_ = (size_t)h->N;
@@ -901,14 +909,14 @@ hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int ma
     // single launch (the redo behind a condensed step: few instances, occupancy does not matter): the 128-row build when its Sinv fits
     // LDS beside the trajectories, else the 64-row one.  first_tier 1: starts that are known to hold many rows
     int tier0 = first_tier, tier1 = 3;
-    if (sd.ghat_building) tier1 = 0;
+    if (mode.build_ghat) tier1 = 0;
     if (single_launch) {
         int NT_ = sd.NT, MC_ = sd.MC;
         const bool fits128 = (size_t)sdual_lds_doubles(NT_, MC_, h->N, SD_WCAP4, true) * sizeof(double) <= 160 * 1024;
         // (round 5: the 64-row build first -- one working-set position per lane: its Sinv products, borderings and column streams are
         // cheaper per change than the 128-row build's -- and the 128-row build only for what outgrows it, which costs little since the
         // tiers hand over their inverse; ALMPC_SDUAL_REDO_128=1: the one 128-row launch of round 4)
-        tier0 = (fits128 && (getenv("ALMPC_SDUAL_REDO_128") || (h->redo_gate_on && !h->redo_predicted))) ? 2 : 1;   // (a gated redo that is not expected to have work: one launch)
+        tier0 = (fits128 && (getenv("ALMPC_SDUAL_REDO_128") || (mode.gated && !mode.predicted))) ? 2 : 1;   // (a gated redo that is not expected to have work: one launch)
         tier1 = fits128 ? 2 : 1;
     }
     // the redo's start (the finish's working set + the terminal-equality rows) with its inverse, built in registers from the cached
@@ -953,43 +961,44 @@ hipError_t stream_wait_polling(almpc_handle* h) {
     return hipStreamSynchronize(h->stream);
 }
 
-// Lazy redo (see almpc_handle::hUnsolved): called where the host is about to look at results and the stream is idle.  If the finish of
+// Lazy redo (see almpc_handle::Redo): called where the host is about to look at results and the stream is idle.  If the finish of
 // a step since the last look left instances unsolved, the stage-wise solvers redo them now (from the step's own result).
 int resolve_lazy_redo(almpc_handle* h) {
-    if (!h->lazy_pending) return ALMPC_OK;
-    h->lazy_pending = false;
-    if (!h->hUnsolved) return ALMPC_OK;
-    const int cur = *reinterpret_cast<volatile int*>(h->hUnsolved);
-    h->redo_expected = cur != h->unsolved_seen;
-    if (cur == h->unsolved_seen) return ALMPC_OK;
-    h->unsolved_seen = cur;
-    h->redo_x0_from_results = true;
-    struct Reset { almpc_handle* h; ~Reset() { h->redo_x0_from_results = false; } } reset_{h};
+    almpc_handle::Redo& r = h->redo;
+    if (!r.lazy_pending) return ALMPC_OK;
+    r.lazy_pending = false;
+    if (!r.hUnsolved) return ALMPC_OK;
+    const int cur = *reinterpret_cast<volatile int*>(r.hUnsolved);
+    r.expected = cur != r.unsolved_seen;
+    if (cur == r.unsolved_seen) return ALMPC_OK;
+    r.unsolved_seen = cur;
+    SolveMode mode;
+    mode.x0_from_results = true;
     if (h->sd.ready) {
-        if (h->sd.per_instance) HIP_TRY(h, launch_sgains(h, 1));   // (the last step's models are still in the model slots)
-        HIP_TRY(h, launch_sdual(h, 1, h->dU, 0, true));
+        if (h->sd.per_instance) HIP_TRY(h, launch_sgains(h, 1, mode));   // (the last step's models are still in the model slots)
+        HIP_TRY(h, launch_sdual(h, 1, h->dU, 0, true, 0, mode));
     }
-    if (h->mc == 0 && !h->useS && h->rKst) HIP_TRY(h, launch_riccati(h, 1, h->dU, 0));
+    if (h->mc == 0 && !h->useS && h->rKst) HIP_TRY(h, launch_riccati(h, 1, h->dU, 0, mode));
     HIP_TRY(h, stream_wait_polling(h));   // (a redo is 0.1 - 0.4 ms of kernels: the blocking wait's wake-up alone was seen to double that)
     return ALMPC_OK;
 }
 
-// Gated redo behind the last enqueued step (no host look, no synchronisation): see almpc_handle::dRedoGate.  Called where the step's
+// Gated redo behind the last enqueued step (no host look, no synchronisation): see almpc_handle::Redo.  Called where the step's
 // results are about to be consumed without a synchronous call; does nothing unless a lazily deferred redo is pending.
-int enqueue_gated_redo(almpc_handle* h) {
-    if (!h->lazy_pending || !h->dRedoGate || getenv("ALMPC_NO_GATED_REDO")) return ALMPC_OK;
-    h->redo_x0_from_results = true; h->redo_gate_on = true;
-    struct Reset { almpc_handle* h; ~Reset() { h->redo_x0_from_results = false; h->redo_gate_on = false; } } reset_{h};
+int enqueue_gated_redo(almpc_handle* h, bool predicted = false) {
+    if (!h->redo.lazy_pending || !h->redo.dGate || getenv("ALMPC_NO_GATED_REDO")) return ALMPC_OK;
+    SolveMode mode;
+    mode.x0_from_results = true; mode.gated = true; mode.predicted = predicted;
     // As few launches as possible: an empty gated launch still costs 3 - 4 us of stream time on a 60 us step.  An input box alone
     // (no state rows, no S): the primal Riccati active set by itself -- it is the solver that needs no certificate from another one
     // (slower per instance than the dual method, but what it gets here is rare) --, ONE launch.  Otherwise the dual method's
     // 128-row build in one launch (+ the stage records of per-instance models).
-    if (h->mc == 0 && !h->useS && h->rKst) HIP_TRY(h, launch_riccati(h, 1, h->dU, 0));
+    if (h->mc == 0 && !h->useS && h->rKst) HIP_TRY(h, launch_riccati(h, 1, h->dU, 0, mode));
     else if (h->sd.ready) {
-        if (h->sd.per_instance) HIP_TRY(h, launch_sgains(h, 1));
-        HIP_TRY(h, launch_sdual(h, 1, h->dU, 0, true));
+        if (h->sd.per_instance) HIP_TRY(h, launch_sgains(h, 1, mode));
+        HIP_TRY(h, launch_sdual(h, 1, h->dU, 0, true, 0, mode));
     }
-    h->lazy_pending = false;   // (this step is settled on the stream; a later synchronous look has nothing left to do for it)
+    h->redo.lazy_pending = false;   // (this step is settled on the stream; a later synchronous look has nothing left to do for it)
     return ALMPC_OK;
 }
 
@@ -999,20 +1008,19 @@ int enqueue_gated_redo(almpc_handle* h) {
 // on the stream GATED behind the step before the wait -- it runs without the host in between if the step left anything, and costs two
 // idle launches if it did not.  The look itself then only reads the count, to know what to expect of the next step.
 int wait_and_settle(almpc_handle* h, bool blocking_only = false) {
+    almpc_handle::Redo& r = h->redo;
     bool predicted = false;
-    if (h->lazy_pending && h->redo_expected && h->dRedoGate && h->hUnsolved && !getenv("ALMPC_NO_PREDICTED_REDO")) {
-        h->redo_predicted = true;
-        const int rc = enqueue_gated_redo(h);
-        h->redo_predicted = false;
+    if (r.lazy_pending && r.expected && r.dGate && r.hUnsolved && !getenv("ALMPC_NO_PREDICTED_REDO")) {
+        const int rc = enqueue_gated_redo(h, true);
         if (rc != ALMPC_OK) return rc;
-        predicted = !h->lazy_pending;
+        predicted = !r.lazy_pending;
     }
     if (blocking_only) HIP_TRY(h, hipStreamSynchronize(h->stream));
     else HIP_TRY(h, stream_wait_polling(h));
     if (predicted) {
-        const int cur = *reinterpret_cast<volatile int*>(h->hUnsolved);
-        h->redo_expected = cur != h->unsolved_seen;
-        h->unsolved_seen = cur;
+        const int cur = *reinterpret_cast<volatile int*>(r.hUnsolved);
+        r.expected = cur != r.unsolved_seen;
+        r.unsolved_seen = cur;
         return ALMPC_OK;
     }
     return resolve_lazy_redo(h);
@@ -1020,9 +1028,22 @@ int wait_and_settle(almpc_handle* h, bool blocking_only = false) {
 
 // A new design voids a redo that was deferred for a step of the previous one (its models, references and results are about to go)
 void drop_lazy_redo(almpc_handle* h) {
-    h->lazy_pending = false;
-    h->redo_expected = false;
-    if (h->hUnsolved) h->unsolved_seen = *reinterpret_cast<volatile int*>(h->hUnsolved);
+    h->redo.lazy_pending = false;
+    h->redo.expected = false;
+    if (h->redo.hUnsolved) h->redo.unsolved_seen = *reinterpret_cast<volatile int*>(h->redo.hUnsolved);
+}
+
+// Lanes of the rollout fused into a finish: g lanes per trajectory row, cpl columns per lane (a power of two); fits: the trajectory
+// fits the finish's 32 x 32 buffer with at most 8 columns per lane
+struct RollGeom { int g = 1, cpl = 1; bool fits = false; };
+RollGeom roll_geom(const almpc_handle* h) {
+    RollGeom r;
+    while (2 * r.g * h->n <= 64) r.g *= 2;
+    const int C = h->n + h->m;
+    r.cpl = (C + r.g - 1) / r.g;
+    r.fits = (size_t)(h->N + 1) * C <= 32 * 32 && r.cpl <= 8;
+    r.cpl = r.cpl <= 1 ? 1 : (r.cpl <= 2 ? 2 : (r.cpl <= 4 ? 4 : 8));
+    return r;
 }
 
 // Table of the state rows' s0 (PolishGenParams::s0_basis) for a shared design: after the design and after every change of the shared
@@ -1030,18 +1051,14 @@ void drop_lazy_redo(almpc_handle* h) {
 int build_s0_basis(almpc_handle* h) {
     h->s0_basis_ok = false;
     if (h->mc <= 0 || h->batched || h->ltv || h->structured || !h->dVsPlain || !h->dRowTraj || getenv("ALMPC_NO_S0_BASIS")) return ALMPC_OK;
-    int roll_g = 1;
-    while (2 * roll_g * h->n <= 64) roll_g *= 2;
-    const int roll_C = h->n + h->m;
-    int roll_cpl = (roll_C + roll_g - 1) / roll_g;
-    if (!((size_t)(h->N + 1) * roll_C <= 32 * 32 && roll_cpl <= 8)) return ALMPC_OK;
-    roll_cpl = roll_cpl <= 1 ? 1 : (roll_cpl <= 2 ? 2 : (roll_cpl <= 4 ? 4 : 8));
+    const RollGeom roll = roll_geom(h);
+    if (!roll.fits) return ALMPC_OK;
     if (!h->dS0Basis) HIP_TRY(h, dalloc(&h->dS0Basis, (size_t)(h->n + 1) * h->Rs));
     S0BasisParams bp;
-    bp.n = h->n; bp.m = h->m; bp.N = h->N; bp.nz = h->nz; bp.nzs = h->nzs; bp.R = h->R; bp.Rs = h->Rs; bp.roll_g = roll_g; bp.roll_cpl = roll_cpl;
+    bp.n = h->n; bp.m = h->m; bp.N = h->N; bp.nz = h->nz; bp.nzs = h->nzs; bp.R = h->R; bp.Rs = h->Rs; bp.roll_g = roll.g; bp.roll_cpl = roll.cpl;
     bp.A = h->dA; bp.B = h->dB; bp.Vs = h->dVsPlain; bp.v0S = (h->dV0S && h->fS_stride == 0) ? h->dV0S : nullptr; bp.dvec = h->dD;
     bp.row_traj = h->dRowTraj; bp.out = h->dS0Basis;
-    hipLaunchKernelGGL(k_s0_basis, dim3((unsigned)(h->n + 1)), dim3(64), (size_t)(h->N + 1) * roll_C * sizeof(double), h->stream, bp);
+    hipLaunchKernelGGL(k_s0_basis, dim3((unsigned)(h->n + 1)), dim3(64), (size_t)(h->N + 1) * (h->n + h->m) * sizeof(double), h->stream, bp);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->s0_basis_ok = true;
@@ -1454,13 +1471,14 @@ int ensure_batched_alloc(almpc_handle* h) {
 // (scaled: the producer of H_i has done the scaling as its own tail)
 // (with_v: also V_i = -G_i F'_i -- inside the first inverse's launch where that kernel can, else by launch_neg_gm_batched)
 // (v1M / v1Out: instead of V_i, ONE column per instance -- the SQP iteration's v0S_i = -G_i fS_i, [batch][nz] each)
-void launch_batched_factor(almpc_handle* h, const DesignStrides& ds, double rho, double sigma, hipStream_t st, bool scaled = false, bool with_v = false,
-                           const double* v1M = nullptr, double* v1Out = nullptr) {
+// (no_admm: the solve that follows has no ADMM phase -- its guess comes from elsewhere, StepMode::guess -- and needs no KKT inverse)
+void launch_batched_factor(almpc_handle* h, const DesignStrides& ds, double rho, double sigma, hipStream_t st, bool no_admm, bool scaled = false,
+                           bool with_v = false, const double* v1M = nullptr, double* v1Out = nullptr) {
     const int n = h->n, nz = h->nz, nzs = h->nzs;
     const unsigned gb = (unsigned)h->batch;
     if (!scaled) hipLaunchKernelGGL(k_design_scale, dim3(1, gb), dim3(256), 0, st, nz, nzs, n, h->bH, h->bF, h->bD, h->bHs, h->bFs, h->bFlag, ds);
     const size_t inv_lds = 520 * sizeof(double);
-    if (!v1M && !h->skip_admm && h->rho_mode == 0 && design_inverse_makes_rho(nz, nzs) && nz <= 64 && design_inverse_makes_v(nz) && !getenv("ALMPC_DBG_SPLIT_INVERSES")) {
+    if (!v1M && !no_admm && h->rho_mode == 0 && design_inverse_makes_rho(nz, nzs) && nz <= 64 && design_inverse_makes_v(nz) && !getenv("ALMPC_DBG_SPLIT_INVERSES")) {
         // scalar rho: the ADMM's KKT inverse does not need G_i -- both inverses, the penalty profile and V_i in ONE launch
         h->minv_packed = false;
         launch_design_inverse(dim3(1, gb), inv_lds, st, nz, nzs, h->bHs, 0.0, (const double*)nullptr, h->bG, h->bFlag, ds.Hs, ds.rho, ds.G, 1L,
@@ -1478,7 +1496,7 @@ void launch_batched_factor(almpc_handle* h, const DesignStrides& ds, double rho,
         launch_design_inverse(dim3(1, gb), inv_lds, st, nz, nzs, h->bHs, 0.0, (const double*)nullptr, h->bG, h->bFlag, ds.Hs, 0L, ds.G, 1L);
         if (with_v) launch_neg_gm_batched(st, gb, nz, nzs, n, h->bG, h->bFs, h->bVs, ds.G, ds.Fs);
     }
-    if (h->skip_admm) return;  // no ADMM phase in this solve: its KKT inverse is not needed
+    if (no_admm) return;
     h->minv_packed = design_inverse_can_pack(nz);   // the ADMM's KKT inverse as its packed triangle: half the stream of k_admm_inst
     const long sMinv = h->minv_packed ? packed_tri_doubles(nz) : ds.Minv;
     if (design_inverse_makes_rho(nz, nzs))   // the penalty profile is made inside the inverse's own launch
@@ -1635,7 +1653,7 @@ bool design_fuses_fnn(const almpc_handle* h, int H, int L, int net) {
 // fuse_fnn: the models are linearisations of this network at fuse_fnn->x / u (re-linearisation pipeline): done by the design kernel's
 // own workgroups when *fused comes back true -- else the caller launches the Jacobians first
 hipError_t launch_batched_design(almpc_handle* h, const DesignStrides& ds, int useR, int useS, const double* dQ, const double* dR,
-                                 const double* dS, double rho, double sigma, const FnnParams* fuse_fnn = nullptr) {
+                                 const double* dS, double rho, double sigma, bool no_admm, const FnnParams* fuse_fnn = nullptr) {
     const int n = h->n, m = h->m, N = h->N, nz = h->nz, nzs = h->nzs, nrb = h->nrb;
     const int njf = (n + 15) / 16, ps = 16 * njf, gs = nzs;
     const int kr = ((n * N + HESS_KC - 1) / HESS_KC) * HESS_KC;
@@ -1690,7 +1708,7 @@ hipError_t launch_batched_design(almpc_handle* h, const DesignStrides& ds, int u
     if (e != hipSuccess) return e;
     DesignStrides ds2 = ds;
     ds2.h_symmetric = (inst_lds <= 160 * 1024) ? 1 : 0;   // (the LDS route writes both halves of H_i from one value)
-    launch_batched_factor(h, ds2, rho, sigma, st, scaled, true);
+    launch_batched_factor(h, ds2, rho, sigma, st, no_admm, scaled, true);
     return hipGetLastError();
 }
 
@@ -1861,7 +1879,7 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
             e = launch_design_ltv(h, lp, st);
         }
         if (e == hipSuccess && h->mc > 0) {   // (needs G_i, d_i: the factor step comes first when there are state rows)
-            launch_batched_factor(h, ds, rho, sigma, st);
+            launch_batched_factor(h, ds, rho, sigma, st, false);
             e = launch_ghat_inst(h, dAll, dBll);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(st);  // the staging buffers are released right away
@@ -1873,11 +1891,11 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
         }
         (void)hipFree(dAll); (void)hipFree(dBll); (void)hipFree(dC); (void)hipFree(dE); (void)hipFree(dQa);
         if (e != hipSuccess) { release(); return fail(h, ALMPC_ERR_HIP, std::string("design_ltv: ") + hipGetErrorString(e)); }
-        if (h->mc == 0) launch_batched_factor(h, ds, rho, sigma, st);
+        if (h->mc == 0) launch_batched_factor(h, ds, rho, sigma, st, false);
         launch_neg_gm_batched(st, gb, nz, nzs, n, h->bG, h->bFs, h->bVs, ds.G, ds.Fs);
         BTRY(hipGetLastError());
     } else {
-        BTRY(launch_batched_design(h, ds, useR, useS, dQ, dR, dS, rho, sigma));
+        BTRY(launch_batched_design(h, ds, useR, useS, dQ, dR, dS, rho, sigma, false));
         if (h->mc > 0) BTRY(launch_ghat_inst(h, nullptr, nullptr));
     }
     tr("kernels queued");
@@ -2018,6 +2036,565 @@ int relin_setup_structured(almpc_handle* h, int H, int L, int net, int activatio
     if (rc_ref != ALMPC_OK) { h->designed = false; return rc_ref; }
     q.ready = true;
     return ALMPC_OK;
+}
+
+// ---- the step (almpc_calculate_async, and the SQP loop / re-linearisation pipeline on their own designs) -------------------------
+
+// Where the working-set guess of a per-instance step comes from: the ADMM phase, or -- no ADMM phase, no KKT inverse in the design --
+// the SQP loop's iterate, or the previous step's inputs shifted by one stage (warm steps of the re-linearisation pipeline)
+enum class Guess { Admm, FromIterate, ShiftInputs };
+struct StepMode {
+    Guess guess = Guess::Admm;
+    bool fold_flag = false;        // (re-linearisation step) the finish turns a flagged design into ALMPC_NON_FINITE itself
+};
+
+// Timing events of a step (ALMPC_FLAG_TIMING): 0 start, 1 end of the ADMM phase, 2 end of the finish, 3 end.  Event 0 is recorded in
+// front of the step's first launch -- unless the step turns out to be ONE kernel: then only the pair around that kernel is recorded
+// (an event record costs ~3.5 us of stream time: four of them are 5 % of such a step)
+struct StepTimer {
+    hipEvent_t* ev = nullptr;   // null: this step is not timed
+    hipStream_t st = nullptr;
+    bool started = false;
+    hipError_t open(almpc_handle* h) {
+        st = h->stream;
+        if (!(h->flags & ALMPC_FLAG_TIMING) || (h->step_count++ % (size_t)h->timing_stride) != 0) return hipSuccess;
+        if (h->ev.size() < 4 * (h->ev_used + 1)) {
+            const size_t old = h->ev.size();
+            h->ev.resize(old + 4 * 64, nullptr);
+            for (size_t i = old; i < h->ev.size(); ++i) {
+                const hipError_t e = hipEventCreate(&h->ev[i]);
+                if (e != hipSuccess) return e;
+            }
+        }
+        ev = &h->ev[4 * h->ev_used];
+        if (h->ev_two.size() < h->ev_used + 1) h->ev_two.resize(h->ev_used + 64, 0);
+        return hipSuccess;
+    }
+    hipError_t start() {
+        if (!ev || started) return hipSuccess;
+        started = true;
+        return hipEventRecord(ev[0], st);
+    }
+    hipError_t mark(int i) const { return ev ? hipEventRecord(ev[i], st) : hipSuccess; }
+    hipError_t close(almpc_handle* h) const {
+        if (!ev) return hipSuccess;
+        if (started) {
+            const hipError_t e = hipEventRecord(ev[3], st);
+            if (e != hipSuccess) return e;
+        }
+        h->ev_two[h->ev_used] = started ? 0 : 1;
+        h->ev_used += 1;
+        return hipSuccess;
+    }
+};
+
+// What every route of one condensed step shares
+struct Step {
+    almpc_handle* h;
+    almpc_opts o;
+    StepMode mode;
+    bool keep_state, lazy_redo;
+    StepTimer t;
+    RollGeom roll;
+    RolloutParams rp;
+};
+
+// Operands of the per-instance ADMM (k_admm_inst, k_step_inst_wave, the guess kernels): the handle's per-instance models, or with
+// `shared` the dense shared design [Minv | H' | F' | V] that every instance reads (operand strides 0)
+AdmmInstParams admm_inst_params(const almpc_handle* h, const almpc_opts& o, bool shared) {
+    AdmmInstParams ip;
+    ip.nz = h->nz; ip.n = h->n; ip.m = h->m; ip.batch = h->batch; ip.nzs = h->nzs;
+    if (shared) {
+        const size_t mm = (size_t)h->nz * h->nzs, fv = (size_t)h->n * h->nzs;
+        ip.Minv = h->dPlain; ip.Hs = h->dPlain + mm; ip.Fs = h->dPlain + 2 * mm; ip.Vs = h->dPlain + 2 * mm + fv;
+        ip.dvec = h->dD; ip.rhovec = h->dRho;
+        ip.mat_stride = 0; ip.fv_stride = 0; ip.vec_stride = 0; ip.fs_stride = h->fS_stride;
+    } else {
+        ip.Minv = h->bMinv; ip.Hs = h->bHs; ip.Fs = h->bFs; ip.Vs = h->bVs; ip.dvec = h->bD; ip.rhovec = h->bRho;
+        ip.mat_stride = (long)h->nz * h->nzs; ip.fv_stride = (long)h->n * h->nzs; ip.vec_stride = h->nzs; ip.fs_stride = h->nz;
+    }
+    ip.fS = h->dFS; ip.v0S = h->dV0S; ip.umin = h->dUmin; ip.umax = h->dUmax;
+    ip.uref = h->dUref; ip.uref_stride = h->uref_stride; ip.xref = h->dXref; ip.xref_stride = h->xref_stride; ip.x0 = h->dX0;
+    ip.xs = h->dXs; ip.zs = h->dZs; ip.ys = h->dYs; ip.v0 = h->dV0; ip.status = h->dStatus; ip.iters = h->dIters;
+    ip.piters = h->dPiters; ip.perm = h->dPerm;
+    ip.sigma = o.sigma; ip.alpha = o.alpha; ip.eps_abs = o.eps_abs; ip.eps_rel = o.eps_rel;
+    ip.max_iter = o.max_iter; ip.check_every = o.check_every; ip.warm = o.warm_start ? 1 : 0;
+    return ip;
+}
+
+// Operands of the shared model's ADMM tile kernel (k_admm, the ADMM phase of k_step_fused)
+AdmmParams admm_params(const almpc_handle* h, const almpc_opts& o, bool keep_state) {
+    AdmmParams ap;
+    ap.nz = h->nz; ap.n = h->n; ap.m = h->m; ap.batch = h->batch; ap.nzs = h->nzs;
+    ap.MinvFrag = h->dMinvFrag; ap.VFrag = h->dVFrag; ap.v0S = h->dV0S; ap.v0S_stride = h->fS_stride; ap.HFrag = h->dHFrag; ap.FFrag = h->dFFrag; ap.ksf = h->ksf;
+    ap.dvec = h->dD; ap.rhovec = h->dRho; ap.umin = h->dUmin; ap.umax = h->dUmax;
+    ap.uref = h->dUref; ap.uref_stride = h->uref_stride; ap.xref = h->dXref; ap.xref_stride = h->xref_stride;
+    ap.fS = h->dFS; ap.fS_stride = h->fS_stride; ap.x0 = h->dX0;
+    ap.xs = h->dXs; ap.zs = h->dZs; ap.ys = h->dYs; ap.v0 = h->dV0; ap.status = h->dStatus; ap.iters = h->dIters;
+    ap.piters = h->dPiters;
+    ap.perm = h->dPerm;
+    ap.rho = o.rho; ap.sigma = o.sigma; ap.alpha = o.alpha; ap.eps_abs = o.eps_abs; ap.eps_rel = o.eps_rel;
+    ap.max_iter = o.max_iter; ap.check_every = o.check_every; ap.warm = o.warm_start ? 1 : 0;
+    ap.keep_state = keep_state ? 1 : 0; ap.yflags = h->dYflags;
+    return ap;
+}
+
+size_t admm_lds_bytes(const almpc_handle* h) {
+    return ((size_t)2 * h->nzs * TILE + (size_t)h->nrb * 8 * TILE + (size_t)4 * h->ksf * TILE) * sizeof(double);
+}
+
+// The rollout of every instance from its inputs rp.w: x, e_x, u, e_u
+RolloutParams rollout_params(const almpc_handle* h) {
+    RolloutParams rp;
+    rp.n = h->n; rp.m = h->m; rp.N = h->N; rp.batch = h->batch; rp.nzs = h->nzs; rp.A = h->batched ? h->bA : h->dA; rp.B = h->batched ? h->bB : h->dB;
+    rp.dvec = h->dD; rp.w = h->dZs; rp.x0 = h->dX0; rp.xref = h->dXref; rp.xref_stride = h->xref_stride;
+    rp.uref = h->dUref; rp.uref_stride = h->uref_stride; rp.umin = h->dUmin; rp.umax = h->dUmax; rp.x = h->dX; rp.ex = h->dEx; rp.u = h->dU; rp.eu = h->dEu;
+    return rp;
+}
+
+// LDS layout of the input-box finish (k_polish*, k_step_*)
+struct PolishLayout {
+    PolishShared SL;                 // workgroup-shared part
+    bool fused = false;              // the rollout runs in the finish's tail
+    int fuse_rollout = 0;            // PolishParams::fuse_rollout
+    int per_wave = 0;                // doubles per wave
+    int wave_const_off = -1;         // per-instance models: the wave's copy of d_i | [A_i B_i] behind its buffers
+    int sg_shared_off = -1;          // the workgroup-shared second-tier slot, or -1
+    size_t g_lds = 0;                // doubles of G in LDS (rows packed to an even stride)
+    size_t l_glds = 0, l_step = 0;   // bytes of k_polish<true> (G in LDS), of k_step_fused
+};
+
+PolishLayout polish_layout(const almpc_handle* h, const RollGeom& roll) {
+    PolishLayout L;
+    const bool blocked = !h->batched && h->roll_s > 0;   // shared model: blocked rollout, no trajectory buffer
+    L.fused = roll.fits || blocked;   // (rollout fused into the tail of the finish when its trajectory buffer fits the wave's LDS slot)
+    L.fuse_rollout = L.fused ? (h->ltv ? 2 : (blocked ? 3 : 1)) : 0;
+    int per_wave = POLISH_LDS_MIN_PER_WAVE;
+    if (L.fused && !blocked && (h->N + 1) * (h->n + h->m) > per_wave) per_wave = (h->N + 1) * (h->n + h->m);
+    per_wave = (per_wave + 1) & ~1;
+    if (h->batched) {
+        L.wave_const_off = per_wave;
+        per_wave += (h->nzs + h->n * (h->n + h->m) + 1) & ~1;
+    }
+    L.per_wave = per_wave;
+    // G in LDS when it fits beside the buffers of 8 waves (gfx950: 160 KB per workgroup)
+    L.SL = polish_shared_layout(h->n, h->m, h->N, h->nz, h->nzs, L.fuse_rollout);
+    L.g_lds = (size_t)h->nz * ((h->nz + 1) & ~1);
+    L.l_glds = (L.g_lds + L.SL.total + (size_t)POLISH_WAVES_GLDS * per_wave + 2) * sizeof(double);
+    // workgroup-shared second-tier slot (working sets beyond 32 rows) behind the queue words, if the 160 KB allow it
+    const size_t slot = (size_t)POLISH_SG_SHARED_CAP * 64 * sizeof(double);
+    if (L.l_glds + slot <= 160 * 1024 && !h->batched && !getenv("ALMPC_POLISH_SG_GLOBAL")) {
+        L.sg_shared_off = (int)(L.SL.total + (size_t)POLISH_WAVES_GLDS * per_wave + 2);
+        L.l_glds += slot;
+    }
+    // one kernel for the whole step: [G | union(ADMM buffers, finish buffers)]
+    L.l_step = L.l_glds - L.g_lds * sizeof(double);
+    if (admm_lds_bytes(h) > L.l_step) L.l_step = admm_lds_bytes(h);
+    L.l_step += L.g_lds * sizeof(double);
+    return L;
+}
+
+// The finish's parameters on the standard layout (the routes adjust the LDS offsets of their kernel)
+PolishParams polish_params(const Step& s, const PolishLayout& L) {
+    const almpc_handle* h = s.h;
+    PolishParams pp;
+    pp.nz = h->nz; pp.m = h->m; pp.batch = h->batch; pp.nzs = h->nzs;
+    pp.G = h->batched ? h->bG : h->dG; pp.dvec = h->batched ? h->bD : h->dD;
+    pp.G_stride = h->batched ? (long)h->nz * h->nzs : 0; pp.d_stride = h->batched ? (long)h->nzs : 0;
+    pp.A_stride = h->batched ? (long)h->n * h->n : 0; pp.B_stride = h->batched ? (long)h->n * h->m : 0;
+    pp.wave_const_off = L.wave_const_off; pp.sg_off = 0; pp.g_off = 0; pp.sg_shared_off = L.sg_shared_off;
+    pp.umin = h->dUmin; pp.umax = h->dUmax; pp.uref = h->dUref; pp.uref_stride = h->uref_stride;
+    pp.zs = h->dZs; pp.ys = h->dYs; pp.v0 = h->dV0; pp.w = h->dW; pp.status = h->dStatus; pp.piters = h->dPiters;
+    pp.yflags = s.keep_state ? nullptr : h->dYflags; pp.yflag_words = h->nrb;
+    pp.sglobal = h->dSglobal; pp.perm = h->dPerm; pp.ntiles = (h->batch + 15) / 16;
+    pp.max_iter = s.o.polish_max_iter > 0 ? s.o.polish_max_iter : 2 * h->nz + 50;
+    pp.dflag = s.mode.fold_flag ? h->bFlag : nullptr;
+    if (s.lazy_redo) { pp.unsolved = h->redo.dUnsolved; pp.redo_gate = h->redo.dGate; pp.step_serial = h->redo.step_serial; }
+    pp.fuse_rollout = L.fuse_rollout; pp.roll_g = s.roll.g; pp.roll_cpl = s.roll.cpl; pp.roll = s.rp;
+    pp.rollM = h->dRollM; pp.roll_s = h->roll_s; pp.roll_nb = h->roll_nb;
+    pp.lds_per_wave = L.per_wave;
+    return pp;
+}
+
+enum class Route { StateRows, FusedShared, WaveShared, WaveInst, TwoLaunch, NoPolish };
+
+Route pick_route(const Step& s, const PolishLayout& L) {
+    const almpc_handle* h = s.h;
+    if (h->mc > 0) return Route::StateRows;
+    if (!s.o.polish) return Route::NoPolish;
+    if (!h->batched && h->fuse_step && POLISH_WAVES_GLDS == 8 && !h->polish_no_glds && h->nrb == 8 && (h->ks == 30 || h->ks == 32) && L.fused &&
+        L.l_step <= 160 * 1024)
+        return Route::FusedShared;
+    // small SHARED problems in small batches (configs[0], the reference's own test sizes: one instance, N 5 - 15, m 2 -> nz 10 - 30;
+    // round 5): the two-launch path gives them a 16-instance MFMA tile they cannot fill and two launch ramps.  ONE kernel, one wave per
+    // instance -- k_step_inst_wave with operand strides of zero: every wave reads the same dense Minv / F' / V (a few KB, L1 / L2
+    // resident), runs the ADMM iterations from registers and then the single-wave finish (G through L1: 13 KB at nz 40).  Measured
+    // (tools/time_small_shared.py, QTP fixture, N 5 / N 20, us per step): batch 1 16.9 / 21.8 against 29.7 / 33.1, batch 64 20 / 45
+    // against 43 / 56, batch 512 30 / 58 against 44 / 58; from 2048 instances on a wave per 10 - 40-row problem wastes the machine
+    // (63 / 113 against 45 / 70 us; 65,536: 1.8 / 2.3 ms against 0.32 / 0.68 ms): up to two instances per CU take this path, larger
+    // batches the tile path.
+    const char* no_sw = getenv("ALMPC_NO_SHARED_WAVE");
+    const char* sw_max = getenv("ALMPC_SHARED_WAVE_MAX_BATCH");
+    if (!h->batched && h->nzs <= 64 && L.fused && h->dPlain && !h->ltv && !(no_sw && no_sw[0] == '1') &&
+        (long)h->batch <= (sw_max ? atol(sw_max) : (long)2 * h->num_cus) && ((size_t)L.SL.total + (size_t)L.per_wave) * sizeof(double) <= 64 * 1024)
+        return Route::WaveShared;
+    // small per-instance problems (BASELINE configs[3]): ONE wave per instance for the whole step -- ADMM with the KKT inverse in
+    // registers, then the single-wave finish with G_i in the wave's LDS (the second-tier Sinv, rarely needed at these sizes, stays in the
+    // global scratch: with its 32 KB per wave only three waves would fit a CU)
+    const char* no_iw = getenv("ALMPC_NO_INST_WAVE");
+    if (h->batched && s.mode.guess == Guess::Admm && h->nzs <= 64 && L.fused && !(no_iw && no_iw[0] == '1') &&
+        ((size_t)L.SL.total + (size_t)L.per_wave + (size_t)h->nz * h->nzs) * sizeof(double) <= 64 * 1024)
+        return Route::WaveInst;
+    return Route::TwoLaunch;
+}
+
+template <bool PACKED>
+hipError_t launch_admm_inst(const AdmmInstParams& ip, int wgs, size_t lds, hipStream_t st) {
+    if (lds > 64 * 1024) {
+        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_admm_inst<PACKED>), lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((k_admm_inst<PACKED>), dim3(wgs), dim3(ADMM_INST_THREADS), lds, st, ip);
+    return hipGetLastError();
+}
+
+// The ADMM phase (the shared model's tile kernel, or k_admm_inst on per-instance models) or the per-instance guess that replaces it
+// (StepMode::guess), between timing events 0 and 1.  *guess_ws: k_guess_iterate_ws also left the inverse of the guessed working set
+// (installed by k_polish_sgl<1>)
+int step_admm_or_guess(Step& s, bool* guess_ws = nullptr) {
+    almpc_handle* h = s.h;
+    hipStream_t st = h->stream;
+    HIP_TRY(h, s.t.start());
+    if (!h->batched) {
+        HIP_TRY(h, launch_admm(h->nrb, h->ks, admm_params(h, s.o, s.keep_state), (h->batch + TILE - 1) / TILE, admm_lds_bytes(h), st));
+        HIP_TRY(h, s.t.mark(1));
+        return ALMPC_OK;
+    }
+    AdmmInstParams ip = admm_inst_params(h, s.o, false);
+    if (s.mode.guess == Guess::ShiftInputs) {
+        hipLaunchKernelGGL(k_guess_shift, dim3((h->batch + 3) / 4), dim3(256), 0, st, ip, (const double*)h->dU, h->N);
+    } else if (s.mode.guess == Guess::FromIterate && h->nzs <= 128 && h->nzs > 64 && h->batch <= 2 * h->num_cus && h->dSglobal && h->bG &&
+               !getenv("ALMPC_NO_GUESS_WS")) {
+        // the guess of an SQP iteration AND the inverse of its working set (33..64 of the inputs on a bound), four waves per instance
+        if (!h->dStartRows) HIP_TRY(h, dalloc(&h->dStartRows, (size_t)h->batch * 65));
+        GuessWsParams gw;
+        gw.G = h->bG; gw.G_stride = (long)h->nz * h->nzs; gw.sinv = h->dSglobal; gw.rows = h->dStartRows;
+        hipLaunchKernelGGL(k_guess_iterate_ws, dim3((unsigned)h->batch), dim3(256), 0, st, ip, gw);
+        if (guess_ws) *guess_ws = true;
+    } else if (s.mode.guess == Guess::FromIterate) {
+        hipLaunchKernelGGL(k_guess_iterate, dim3((h->batch + 3) / 4), dim3(256), 0, st, ip);
+    } else {
+        // KKT inverse in LDS; persistent grid: as many workgroups as fit the CUs at once -- register bound: 2 x 256 threads at up to 256
+        // VGPRs each fill the CU's register file
+        const bool packed = h->minv_packed;
+        const size_t l = admm_inst_lds_doubles(h->nz, h->nzs, h->m, packed) * sizeof(double);
+        const int wgs = h->num_cus * 2 > h->batch ? h->batch : h->num_cus * 2;
+        ip.minv_stride = packed ? packed_tri_doubles(h->nz) : 0;
+        HIP_TRY(h, packed ? launch_admm_inst<true>(ip, wgs, l, st) : launch_admm_inst<false>(ip, wgs, l, st));
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, s.t.mark(1));
+    return ALMPC_OK;
+}
+
+// The rollout on its own, behind a finish that did not run it in its tail
+int step_rollout(Step& s) {
+    almpc_handle* h = s.h;
+    RolloutParams& rp = s.rp;
+    const size_t per_wave = (size_t)h->n * (h->N + 1) + h->nz, shared = (size_t)h->n * h->n + (size_t)h->n * h->m;
+    if (h->batched) { rp.A_stride = (long)h->n * h->n; rp.B_stride = (long)h->n * h->m; rp.d_stride = h->nzs; rp.dvec = h->bD; }
+    if (!h->batched && (shared + 4 * per_wave) * sizeof(double) <= 60 * 1024) {
+        const size_t l = (shared + 4 * per_wave) * sizeof(double);
+        hipLaunchKernelGGL((k_rollout<4>), dim3((h->batch + 3) / 4), dim3(256), l, h->stream, rp);
+    } else {  // long horizons with many states: one instance per workgroup, LDS beyond the 64 KiB default
+        const size_t l = (shared + per_wave) * sizeof(double);
+        HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_rollout<1>), l));
+        hipLaunchKernelGGL((k_rollout<1>), dim3(h->batch), dim3(64), l, h->stream, rp);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return ALMPC_OK;
+}
+
+template <int NP>
+hipError_t launch_polish_gen(const almpc_handle* h, const PolishGenParams& gp) {
+    // first launch: working sets up to 32 rows, every instance; second launch: the instances the first one flagged, up to 64 rows
+    const size_t l32 = (size_t)PGEN_WAVES * pgen_lds_per_wave(32) * sizeof(double);
+    const size_t l64 = (size_t)pgen_coop_lds_doubles() * sizeof(double);   // (wave 0's buffers + job word + three partial sums)
+    hipLaunchKernelGGL((k_polish_gen<NP>), dim3((h->batch + PGEN_WAVES - 1) / PGEN_WAVES), dim3(64 * PGEN_WAVES), l32, h->stream, gp);
+    const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_polish_gen64<NP>), l64);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_polish_gen64<NP>), dim3(3 * h->num_cus < h->batch ? 3 * h->num_cus : h->batch), dim3(64 * (PGEN_HELPERS + 1)), l64,
+                       h->stream, gp);
+    return hipGetLastError();
+}
+
+// State rows (state box / terminal equality): the ADMM phase or a guess, then the state-row finish k_polish_gen + k_polish_gen64 with
+// the rollout in its tail
+int step_state_rows(Step& s) {
+    almpc_handle* h = s.h;
+    const almpc_opts& o = s.o;
+    if (!s.roll.fits) return fail(h, ALMPC_ERR_UNSUPPORTED, "calculate: state rows need the fused rollout (n + m <= 8 * lanes-per-row)");
+    if (h->batched && !h->ghat_inst) return fail(h, ALMPC_ERR_NOT_DESIGNED, "calculate: state rows without their per-instance matrices");
+    const bool sq = h->sqp.ready;
+    if (h->ltv && !(sq ? h->sqp.A && h->sqp.B : h->lA && h->lB))
+        return fail(h, ALMPC_ERR_NOT_DESIGNED, "calculate: state rows of a time-varying design without its stage models");
+    { const int rc = step_admm_or_guess(s); if (rc != ALMPC_OK) return rc; }
+    PolishGenParams gp;
+    gp.nz = h->nz; gp.mc = h->mc; gp.R = h->R; gp.Rs = h->Rs; gp.m = h->m; gp.n = h->n; gp.N = h->N; gp.batch = h->batch; gp.nzs = h->nzs;
+    if (h->ltv) {
+        gp.ltv = 1;
+        gp.ltvA = sq ? h->sqp.A : h->lA; gp.ltvB = sq ? h->sqp.B : h->lB; gp.ltvC = sq ? h->sqp.c : h->lC;
+        if (h->terminal_eq) { gp.eq_off = (sq ? h->sqp.ebar : h->lE) + (size_t)(h->N - 1) * h->n; gp.eq_stride = (long)h->N * h->n; }
+    }
+    if (h->batched) {
+        gp.Ghat_stride = (long)h->R * h->Rs; gp.gnorm_stride = h->Rs; gp.d_stride = h->nzs;
+        gp.A_stride = (long)h->n * h->n; gp.B_stride = (long)h->n * h->m;
+    }
+    if (!h->batched && h->roll_s > 0) { gp.rollM = h->dRollM; gp.roll_s = h->roll_s; gp.roll_nb = h->roll_nb; }
+    if (h->eq_proj && !h->batched) { gp.eq_proj = 1; gp.eq0 = h->R - h->n; gp.ne = h->n; gp.GhatE = h->dGhatE; gp.WinvE = h->dWinvE; }
+    gp.Ghat = h->dGhat; gp.gnorm = h->dGnorm; gp.row_traj = h->dRowTraj; gp.row_eq = h->dRowEq; gp.row_xidx = h->dRowXidx;
+    gp.row_state = h->dRowState; gp.xmin = h->dXmin; gp.xmax = h->dXmax; gp.has_box = h->has_box;
+    gp.dvec = h->batched ? h->bD : h->dD; gp.umin = h->dUmin; gp.umax = h->dUmax; gp.uref = h->dUref; gp.uref_stride = h->uref_stride;
+    gp.zs = h->dZs; gp.ys = h->dYs; gp.v0 = h->dV0; gp.status = h->dStatus; gp.piters = h->dPiters;
+    gp.max_iter = o.polish_max_iter > 0 ? o.polish_max_iter : 20 * h->R + 50;
+    gp.roll_g = s.roll.g; gp.roll_cpl = s.roll.cpl; gp.roll = s.rp;
+    if (!h->dOverflow) HIP_TRY(h, dalloc(&h->dOverflow, (size_t)h->batch * 33 + 2));   // list, then [batch][32] working sets
+    HIP_TRY(h, hipMemsetAsync(h->dOverflow, 0, 2 * sizeof(int32_t), h->stream));
+    if (!h->dOvfSinv) HIP_TRY(h, dalloc(&h->dOvfSinv, (size_t)h->batch * (32 * 32 + 32)));
+    gp.ovf = h->dOverflow; gp.ovf_ws = h->dOverflow + 2 + h->batch; gp.ovf_sinv = h->dOvfSinv;
+    if (s.lazy_redo) { gp.unsolved = h->redo.dUnsolved; gp.redo_gate = h->redo.dGate; gp.step_serial = h->redo.step_serial; }
+    if (h->fallback && !h->ltv && h->sd.ready && !h->sd.sqp && !getenv("ALMPC_NO_REDO_START")) {   // a stage-wise redo may follow: it starts from what this finish gives up with
+        if (!h->sd.start_ws) HIP_TRY(h, dalloc(&h->sd.start_ws, (size_t)h->batch * 64));
+        gp.redo_ws = h->sd.start_ws; gp.redo_sp = h->sd.NT + h->sd.MC; gp.redo_nt = h->sd.NT;
+        h->sd.start_ws_fresh = true;
+    }
+    if (h->s0_basis_ok && !h->batched && !h->ltv && h->fS_stride == 0) gp.s0_basis = h->dS0Basis;   // (shared model, shared references)
+    switch (h->np_pairs) {
+        case 1: HIP_TRY(h, launch_polish_gen<1>(h, gp)); break;
+        case 2: HIP_TRY(h, launch_polish_gen<2>(h, gp)); break;
+        case 3: HIP_TRY(h, launch_polish_gen<3>(h, gp)); break;
+        default: HIP_TRY(h, launch_polish_gen<4>(h, gp)); break;
+    }
+    HIP_TRY(h, s.t.mark(2));
+    return ALMPC_OK;
+}
+
+template <int KS>
+hipError_t launch_step_fused(const AdmmParams& ap, const PolishParams& pp, size_t lds, hipStream_t st) {
+    const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_step_fused<8, KS>), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_step_fused<8, KS>), dim3(pp.ntiles), dim3(512), lds, st, ap, pp);
+    return hipGetLastError();
+}
+
+// Shared model, ONE kernel for the whole step (k_step_fused): the tile is 8 waves and [G | union(ADMM buffers, finish buffers)] fits LDS
+int step_fused_shared(Step& s, const PolishLayout& L) {
+    almpc_handle* h = s.h;
+    const AdmmParams ap = admm_params(h, s.o, s.keep_state);
+    const PolishParams pp = polish_params(s, L);
+    HIP_TRY(h, s.t.mark(1));   // (no boundary between the phases to time: admm_ms reads 0)
+    HIP_TRY(h, h->ks == 30 ? launch_step_fused<30>(ap, pp, L.l_step, h->stream) : launch_step_fused<32>(ap, pp, L.l_step, h->stream));
+    HIP_TRY(h, s.t.mark(2));
+    return ALMPC_OK;
+}
+
+template <int NZC>
+hipError_t launch_step_inst_wave_t(const almpc_handle* h, const AdmmInstParams& ip, const PolishParams& pp, size_t lds) {
+    const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_step_inst_wave<NZC>), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_step_inst_wave<NZC>), dim3((unsigned)h->batch), dim3(64), lds, h->stream, ip, pp);
+    return hipGetLastError();
+}
+
+// ONE wave per instance for the whole step (k_step_inst_wave): the ADMM iterations from registers, then the single-wave finish.  shared:
+// every wave reads the shared model's dense operands; else the wave's own per-instance model, with G_i in the wave's LDS
+int step_wave(Step& s, const PolishLayout& L, bool shared) {
+    almpc_handle* h = s.h;
+    if (shared) HIP_TRY(h, s.t.start());
+    const AdmmInstParams ip = admm_inst_params(h, s.o, shared);
+    PolishParams pp = polish_params(s, L);
+    if (shared) { pp.yflags = nullptr; pp.yflag_words = 0; }   // (this ADMM phase hands over y itself)
+    const size_t wave = (size_t)L.per_wave + (shared ? 0 : (size_t)h->nz * h->nzs);
+    const size_t lds = ((size_t)L.SL.total + wave) * sizeof(double);
+    pp.sg_off = -1; pp.g_off = shared ? 0 : L.per_wave;
+    pp.lds_per_wave = (int)wave;
+    pp.direct = 1;
+    HIP_TRY(h, s.t.mark(1));   // (a one-kernel step on per-instance models: no boundary between the phases to time, admm_ms reads 0)
+    if (h->nzs <= 16) HIP_TRY(h, launch_step_inst_wave_t<16>(h, ip, pp, lds));
+    else if (h->nzs <= 32) HIP_TRY(h, launch_step_inst_wave_t<32>(h, ip, pp, lds));
+    else if (h->nzs <= 48) HIP_TRY(h, launch_step_inst_wave_t<48>(h, ip, pp, lds));
+    else HIP_TRY(h, launch_step_inst_wave_t<64>(h, ip, pp, lds));
+    HIP_TRY(h, s.t.mark(2));
+    return ALMPC_OK;
+}
+
+template <int START>
+hipError_t launch_polish_sgl(const PolishParams& pp, size_t lds, hipStream_t st) {
+    const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_polish_sgl<START>), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_polish_sgl<START>), dim3(pp.ntiles * 16), dim3(64), lds, st, pp);
+    return hipGetLastError();
+}
+
+// Two launches: the ADMM phase or a guess, then the finish -- k_polish<true> (shared model, G in LDS), k_polish_sgl<0|1> (small batches of
+// per-instance models: single-wave workgroups with G_i and the second-tier Sinv in LDS; <1>: from the guess's working set and inverse)
+// or k_polish<false> (G through L2); the rollout in the finish's tail where it fits, else behind it
+int step_two_launch(Step& s, const PolishLayout& L) {
+    almpc_handle* h = s.h;
+    hipStream_t st = h->stream;
+    if (h->batched && !L.fused) return fail(h, ALMPC_ERR_UNSUPPORTED, "calculate: per-instance models need the fused rollout (n + m <= 8 * lanes-per-row)");
+    bool guess_ws = false;
+    { const int rc = step_admm_or_guess(s, &guess_ws); if (rc != ALMPC_OK) return rc; }
+    PolishParams pp = polish_params(s, L);
+    const size_t sgl_wave = (size_t)L.per_wave + POLISH_GLB_PER_INST + (size_t)h->nz * h->nzs;
+    const size_t l_sgl = ((size_t)L.SL.total + sgl_wave) * sizeof(double);
+    if (L.l_glds <= 160 * 1024 && !h->polish_no_glds && !h->batched) {
+        HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_polish<true>), L.l_glds));
+        const int wgs = pp.ntiles > h->num_cus ? h->num_cus : pp.ntiles;   // one ADMM tile (16 instances) per workgroup and round
+        hipLaunchKernelGGL((k_polish<true>), dim3(wgs), dim3(64 * POLISH_WAVES_GLDS), L.l_glds, st, pp);
+    } else if (h->batched && h->batch <= 2 * h->num_cus && l_sgl <= 160 * 1024 && !getenv("ALMPC_POLISH_SG_GLOBAL")) {
+        pp.sg_off = L.per_wave;
+        pp.g_off = L.per_wave + POLISH_GLB_PER_INST;
+        pp.lds_per_wave = (int)sgl_wave;
+        if (guess_ws) pp.start_rows = h->dStartRows;
+        HIP_TRY(h, guess_ws ? launch_polish_sgl<1>(pp, l_sgl, st) : launch_polish_sgl<0>(pp, l_sgl, st));
+    } else {
+        const size_t l = ((size_t)L.SL.total + (size_t)POLISH_WAVES * L.per_wave) * sizeof(double);
+        HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_polish<false>), l));
+        hipLaunchKernelGGL((k_polish<false>), dim3((pp.ntiles * 16 + POLISH_WAVES - 1) / POLISH_WAVES), dim3(64 * POLISH_WAVES), l, st, pp);
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, s.t.mark(2));
+    if (L.fused) return ALMPC_OK;
+    s.rp.w = h->dW;
+    return step_rollout(s);
+}
+
+// No polish: the ADMM phase, then the rollout of its iterate
+int step_no_polish(Step& s) {
+    { const int rc = step_admm_or_guess(s); if (rc != ALMPC_OK) return rc; }
+    HIP_TRY(s.h, s.t.mark(2));
+    return step_rollout(s);
+}
+
+// Structured handle: the stage-wise active-set solve is the whole step (polish_max_iter caps its working-set changes)
+int step_structured(almpc_handle* h, const almpc_opts& o) {
+    const double* guess = nullptr;
+    if (h->guess_ready) { guess = h->rGuess; h->guess_ready = false; }   // almpc_set_start_from: consumed by this step
+    else if (o.warm_start && h->r_has_step) {   // receding horizon: the previous step's inputs shifted by one stage (the last stage repeated)
+        if (!h->rGuess) HIP_TRY(h, dalloc(&h->rGuess, (size_t)h->batch * h->nz));
+        const long cnt = (long)h->batch * h->nz;
+        hipLaunchKernelGGL(k_guess_from_inputs, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, h->batch, h->m, h->N, h->N, 1,
+                           (const double*)h->dU, (const double*)h->dUref, h->uref_stride, h->rGuess);
+        HIP_TRY(h, hipGetLastError());
+        guess = h->rGuess;
+    }
+    if (h->sd.ready) {
+        HIP_TRY(h, launch_sdual(h, 0, guess, o.polish_max_iter));
+        // safety net (input box only, S = 0): what the dual method left without a certificate goes to the primal Riccati active set
+        if (!h->sd.has_box && !h->sd.has_eq && !h->sd.useS && h->rKst) HIP_TRY(h, launch_riccati(h, 1, h->dU, 0));
+    } else
+        HIP_TRY(h, launch_riccati(h, 0, guess, o.polish_max_iter));
+    h->r_has_step = true;
+    return ALMPC_OK;
+}
+
+// Structured fallback: instances the condensed path left without a certificate (status != 0: an active-set finish that ran into its cap,
+// a non-finite or indefinite condensed problem) are redone in the multiple-shooting form, from the step's own result -- deferred
+// (almpc_handle::Redo) or right behind the step
+int step_redo(Step& s) {
+    almpc_handle* h = s.h;
+    if (s.lazy_redo) {
+        h->redo.lazy_pending = true;   // (resolve_lazy_redo at the next host sync point)
+        return ALMPC_OK;
+    }
+    if (!h->fallback || h->ltv || !s.o.polish) return ALMPC_OK;
+    if (h->sd.ready && !getenv("ALMPC_DBG_NO_SDUAL_FB")) {
+        if (h->sd.per_instance) HIP_TRY(h, launch_sgains(h, 1));   // (stage records of the unsolved instances only, from the models of this step)
+        HIP_TRY(h, launch_sdual(h, 1, h->dU, 0, true));
+    }
+    if (h->mc == 0 && !h->useS && h->rKst && !getenv("ALMPC_DBG_NO_PRIMAL_NET")) HIP_TRY(h, launch_riccati(h, 1, h->dU, 0));
+    return ALMPC_OK;
+}
+
+// The pinned count and the gate word of the redo (almpc_handle::Redo): at the first step that defers its redo
+hipError_t ensure_unsolved_word(almpc_handle* h) {
+    almpc_handle::Redo& r = h->redo;
+    if (r.hUnsolved) return hipSuccess;
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&r.hUnsolved), sizeof(int), hipHostMallocMapped);
+    if (e != hipSuccess) { r.hUnsolved = nullptr; return e; }
+    *r.hUnsolved = 0; r.unsolved_seen = 0;
+    if ((e = dalloc(&r.dGate, 1)) != hipSuccess) return e;
+    if ((e = hipMemset(r.dGate, 0, sizeof(int))) != hipSuccess) return e;   // (step numbers start at 1)
+    return hipHostGetDevicePointer(reinterpret_cast<void**>(&r.dUnsolved), r.hUnsolved, 0);
+}
+
+// One step on checked options: the route is picked here, on every call (it depends on almpc_set_step_fusion, the reference strides,
+// the options and the switches read at call time)
+int run_step(almpc_handle* h, const almpc_opts& o, StepMode mode) {
+    // ALMPC_OPT_NO_WARM_STATE: shared-model steps with the polish on (the polish needs only the signs of y); ignored elsewhere
+    const bool keep_state = !((o.reserved[0] & ALMPC_OPT_NO_WARM_STATE) && !h->batched && o.polish && h->mc == 0);
+    if (o.warm_start && !h->state_valid)
+        return fail(h, ALMPC_ERR_INVALID, "calculate: warm_start = 1, but the previous step ran with ALMPC_OPT_NO_WARM_STATE (no ADMM state was kept)");
+    // default redo of unsolved instances on the shared-model / input-box-only path: lazily, at the next host sync (almpc_handle::Redo)
+    // (every condensed path that is not the SQP loop ends in a finish that does the counting -- polish_body for an input box,
+    // polish_gen_body with state rows --: shared model, per-instance models, re-linearisation pipeline.  Infeasible instances keep
+    // their verdict and are not counted; what is counted is rare -- a handful of edge-of-feasibility instances in 4096 -- and a
+    // stage-wise solve of one of them takes about a millisecond, which an eager redo would put behind every step)
+    const bool lazy_redo = h->fallback == 2 && !h->structured && !h->ltv && o.polish != 0 &&
+                           (h->sd.ready || (h->mc == 0 && h->rKst)) && !getenv("ALMPC_EAGER_REDO");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->io.big_copy_pending) {   // an asynchronous read-back straight from the result buffers: this step overwrites them
+        HIP_TRY(h, hipStreamWaitEvent(h->stream, h->io.ev_big, 0));
+        h->io.big_copy_pending = false;
+    }
+    h->redo.step_serial += 1;
+    h->sd.start_ws_fresh = false;
+    int rc = ALMPC_OK;
+    if (h->structured) {
+        rc = step_structured(h, o);
+    } else {
+        Step s{h, o, mode, keep_state, lazy_redo, StepTimer(), roll_geom(h), rollout_params(h)};
+        HIP_TRY(h, s.t.open(h));
+        if (h->batched && mode.guess != Guess::Admm && !o.polish) return fail(h, ALMPC_ERR_INVALID, "calculate: the SQP loop needs opts.polish = 1");
+        if (h->mc > 0 && !o.polish)
+            return fail(h, ALMPC_ERR_UNSUPPORTED, "calculate: problems with state rows (state box / terminal equality) need opts.polish = 1");
+        if (lazy_redo) HIP_TRY(h, ensure_unsolved_word(h));
+        const PolishLayout L = polish_layout(h, s.roll);
+        switch (pick_route(s, L)) {
+            case Route::StateRows: rc = step_state_rows(s); break;
+            case Route::FusedShared: rc = step_fused_shared(s, L); break;
+            case Route::WaveShared: rc = step_wave(s, L, true); break;
+            case Route::WaveInst: rc = step_wave(s, L, false); break;
+            case Route::TwoLaunch: rc = step_two_launch(s, L); break;
+            case Route::NoPolish: rc = step_no_polish(s); break;
+        }
+        if (rc == ALMPC_OK) rc = step_redo(s);
+        if (rc == ALMPC_OK) HIP_TRY(h, s.t.close(h));
+    }
+    if (rc != ALMPC_OK) return rc;
+    h->state_valid = keep_state;   // (recorded only here: every launch of the step went out)
+    if (h->io.x0_slot >= 0) {      // the x0 slot of an asynchronous update is free again once this step has finished
+        HIP_TRY(h, hipEventRecord(h->io.ev_used[h->io.x0_slot], h->stream));
+        h->io.used_pending[h->io.x0_slot] = true;
+    }
+    return ALMPC_OK;
+}
+
+// almpc_calculate_async in the given mode: the options checked against the design, then the step
+int calculate_checked(almpc_handle* h, const almpc_opts* user, StepMode mode) {
+    if (!h) return ALMPC_ERR_INVALID;
+    if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, "calculate before design");
+    almpc_opts o;
+    almpc_default_opts(&o);
+    if (user) o = *user;
+    if (o.rho == 0.0) o.rho = h->rho;
+    if (o.sigma == 0.0) o.sigma = h->sigma;
+    if (o.rho != h->rho || o.sigma != h->sigma)
+        return fail(h, ALMPC_ERR_INVALID, "calculate: rho/sigma differ from the design values (the shared KKT inverse is built for them)");
+    if (o.max_iter < 1 || o.check_every < 1 || !(o.alpha > 0.0 && o.alpha < 2.0) || !(o.eps_abs >= 0.0) || !(o.eps_rel >= 0.0))
+        return fail(h, ALMPC_ERR_INVALID, "calculate: bad options");
+    return run_step(h, o, mode);
 }
 }  // namespace
 
@@ -2248,11 +2825,10 @@ int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
     // (opts.warm_start = 1 after a solved step) takes its working-set guess from the previous step's inputs shifted by one stage
     // instead of an ADMM phase, and the design then needs one inverse (G_i) instead of two
     const bool warm = opts && opts->warm_start && q.have_prev && (!opts || opts->polish);
-    h->skip_admm = warm ? 2 : 0;
     const DesignStrides ds = batched_strides(h, false);
     {
-        const hipError_t e_ = launch_batched_design(h, ds, q.useR, q.useS, q.Q, q.R, q.S, h->rho, h->sigma, fuse_jac ? &fp : nullptr);
-        if (e_ != hipSuccess) { h->skip_admm = 0; return fail(h, ALMPC_ERR_HIP, std::string("relin design: ") + hipGetErrorString(e_)); }
+        const hipError_t e_ = launch_batched_design(h, ds, q.useR, q.useS, q.Q, q.R, q.S, h->rho, h->sigma, warm, fuse_jac ? &fp : nullptr);
+        if (e_ != hipSuccess) return fail(h, ALMPC_ERR_HIP, std::string("relin design: ") + hipGetErrorString(e_));
     }
     if (h->mc > 0) HIP_TRY(h, launch_ghat_inst(h, nullptr, nullptr));
     if (q.useS) {
@@ -2270,14 +2846,13 @@ int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
     o2.warm_start = 0;   // (the per-instance ADMM's own warm start is not what a warm step of this pipeline means)
     // an instance whose design was flagged gets ALMPC_NON_FINITE: by the finish itself when it is polish_body (input box only), else by
     // a launch of its own behind the step
-    const bool fold_flag = h->mc == 0 && o2.polish != 0;
-    h->flag_in_finish = fold_flag;
-    const int rc = almpc_calculate_async(h, &o2);
-    h->flag_in_finish = false;
-    h->skip_admm = 0;
+    StepMode mode;
+    mode.guess = warm ? Guess::ShiftInputs : Guess::Admm;
+    mode.fold_flag = h->mc == 0 && o2.polish != 0;
+    const int rc = calculate_checked(h, &o2, mode);
     if (rc != ALMPC_OK) { h->designed = false; return rc; }   // (no step ran on this step's designs: the handle is not left "designed")
     q.have_prev = true;
-    if (!fold_flag) {
+    if (!mode.fold_flag) {
         hipLaunchKernelGGL(k_flag_to_status, dim3((h->batch + 255) / 256), dim3(256), 0, st, h->batch, h->bFlag, h->dStatus);
         HIP_TRY(h, hipGetLastError());
     }
@@ -2773,17 +3348,17 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
             hipLaunchKernelGGL(k_sqp_exact_qp, dim3((unsigned)b), dim3(256), exact_lds, st, xp);
             HIP_TRY(h, hipGetLastError());
         }
-        h->skip_admm = (q.guess_from_iterate && q.since_start > 0) ? 1 : 0;
+        StepMode mode;
+        mode.guess = (q.guess_from_iterate && q.since_start > 0) ? Guess::FromIterate : Guess::Admm;
         // (with the scaling in the design kernel's tail fS_i exists before the inverse: v0S_i = -G_i fS_i comes out of the inverse's launch)
         const bool v0_in_inverse = ltv_scales && design_inverse_makes_v(nz);
-        launch_batched_factor(h, ds, h->rho, h->sigma, st, ltv_scales, false, v0_in_inverse ? h->dFS : nullptr, h->dV0S);
+        launch_batched_factor(h, ds, h->rho, h->sigma, st, mode.guess != Guess::Admm, ltv_scales, false, v0_in_inverse ? h->dFS : nullptr, h->dV0S);
         if (h->mc > 0) HIP_TRY(h, launch_ghat_inst(h, q.A, q.B));
         if (!ltv_scales) hipLaunchKernelGGL(k_fs_scale, dim3(256), dim3(256), 0, st, h->batch, nz, nzs, h->bQ, (long)nz, h->bD, h->dFS);
         if (!v0_in_inverse) hipLaunchKernelGGL(k_neg_gm, dim3(1, (unsigned)b), dim3(256), 0, st, nz, nzs, 1, nz, h->bG, h->dFS, h->dV0S, (long)nz * nzs, (long)nz);
         HIP_TRY(h, hipGetLastError());
         h->designed = true;
-        const int rc = almpc_calculate_async(h, opts);
-        h->skip_admm = 0;
+        const int rc = calculate_checked(h, opts, mode);
         if (rc != ALMPC_OK) return rc;
         // structured fallback: an instance whose condensed Hessian came out indefinite to working precision (open-loop unstable
         // linearisation over the horizon) or whose QP was left unsolved gets this iteration's QP solved in its stage-wise form
@@ -2981,435 +3556,7 @@ int almpc_update_initialization_device(almpc_handle* h, const double* d_x0) {
     return ALMPC_OK;
 }
 
-int almpc_calculate_async(almpc_handle* h, const almpc_opts* user) {
-    if (!h) return ALMPC_ERR_INVALID;
-    if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, "calculate before design");
-    almpc_opts o;
-    almpc_default_opts(&o);
-    if (user) o = *user;
-    if (o.rho == 0.0) o.rho = h->rho;
-    if (o.sigma == 0.0) o.sigma = h->sigma;
-    if (o.rho != h->rho || o.sigma != h->sigma)
-        return fail(h, ALMPC_ERR_INVALID, "calculate: rho/sigma differ from the design values (the shared KKT inverse is built for them)");
-    if (o.max_iter < 1 || o.check_every < 1 || !(o.alpha > 0.0 && o.alpha < 2.0) || !(o.eps_abs >= 0.0) || !(o.eps_rel >= 0.0))
-        return fail(h, ALMPC_ERR_INVALID, "calculate: bad options");
-    // ALMPC_OPT_NO_WARM_STATE: shared-model steps with the polish on (the polish needs only the signs of y); ignored elsewhere
-    const bool keep_state = !((o.reserved[0] & ALMPC_OPT_NO_WARM_STATE) && !h->batched && o.polish && h->mc == 0);
-    if (o.warm_start && !h->state_valid)
-        return fail(h, ALMPC_ERR_INVALID, "calculate: warm_start = 1, but the previous step ran with ALMPC_OPT_NO_WARM_STATE (no ADMM state was kept)");
-    // default redo of unsolved instances on the shared-model / input-box-only path: lazily, at the next host sync (see hUnsolved)
-    // (every condensed path that is not the SQP loop ends in a finish that does the counting -- polish_body for an input box,
-    // polish_gen_body with state rows --: shared model, per-instance models, re-linearisation pipeline.  Infeasible instances keep
-    // their verdict and are not counted; what is counted is rare -- a handful of edge-of-feasibility instances in 4096 -- and a
-    // stage-wise solve of one of them takes about a millisecond, which an eager redo would put behind every step)
-    const bool lazy_redo = h->fallback == 2 && !h->structured && !h->ltv && o.polish != 0 &&
-                           (h->sd.ready || (h->mc == 0 && h->rKst)) && !getenv("ALMPC_EAGER_REDO");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (h->io.big_copy_pending) {   // an asynchronous read-back straight from the result buffers: this step overwrites them
-        HIP_TRY(h, hipStreamWaitEvent(h->stream, h->io.ev_big, 0));
-        h->io.big_copy_pending = false;
-    }
-    auto ensure_unsolved_word = [&]() -> hipError_t {   // the host-visible counter of the lazy redo
-        if (h->hUnsolved) return hipSuccess;
-        hipError_t e_ = hipHostMalloc(reinterpret_cast<void**>(&h->hUnsolved), sizeof(int), hipHostMallocMapped);
-        if (e_ != hipSuccess) { h->hUnsolved = nullptr; return e_; }
-        *h->hUnsolved = 0; h->unsolved_seen = 0;
-        e_ = dalloc(&h->dRedoGate, 1);
-        if (e_ != hipSuccess) return e_;
-        e_ = hipMemset(h->dRedoGate, 0, sizeof(int));   // (step numbers start at 1)
-        if (e_ != hipSuccess) return e_;
-        return hipHostGetDevicePointer(reinterpret_cast<void**>(&h->dUnsolved), h->hUnsolved, 0);
-    };
-    h->step_serial += 1;
-    h->sd.start_ws_fresh = false;
-    auto io_step_done = [&]() -> int {   // the x0 slot of an asynchronous update is free again once this step has finished
-        h->state_valid = keep_state;     // (recorded only here: every launch of the step went out)
-        if (h->io.x0_slot >= 0) {
-            HIP_TRY(h, hipEventRecord(h->io.ev_used[h->io.x0_slot], h->stream));
-            h->io.used_pending[h->io.x0_slot] = true;
-        }
-        return ALMPC_OK;
-    };
-    if (h->structured) {   // the Riccati active-set solve is the whole step (polish_max_iter caps its working-set changes)
-        const double* guess = nullptr;
-        if (h->guess_ready) { guess = h->rGuess; h->guess_ready = false; }   // almpc_set_start_from: consumed by this step
-        else if (o.warm_start && h->r_has_step) {   // receding horizon: the previous step's inputs shifted by one stage (the last stage repeated)
-            if (!h->rGuess) HIP_TRY(h, dalloc(&h->rGuess, (size_t)h->batch * h->nz));
-            const long cnt = (long)h->batch * h->nz;
-            hipLaunchKernelGGL(k_guess_from_inputs, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, h->batch, h->m, h->N, h->N, 1,
-                               (const double*)h->dU, (const double*)h->dUref, h->uref_stride, h->rGuess);
-            HIP_TRY(h, hipGetLastError());
-            guess = h->rGuess;
-        }
-        if (h->sd.ready) {
-            HIP_TRY(h, launch_sdual(h, 0, guess, o.polish_max_iter));
-            // safety net (input box only, S = 0): what the dual method left without a certificate goes to the primal Riccati active set
-            if (!h->sd.has_box && !h->sd.has_eq && !h->sd.useS && h->rKst) HIP_TRY(h, launch_riccati(h, 1, h->dU, 0));
-        } else
-            HIP_TRY(h, launch_riccati(h, 0, guess, o.polish_max_iter));
-        h->r_has_step = true;
-        return io_step_done();
-    }
-    const bool timing = (h->flags & ALMPC_FLAG_TIMING) != 0 && (h->step_count++ % (size_t)h->timing_stride) == 0;
-    hipStream_t st = h->stream;
-    hipEvent_t* ev = nullptr;
-    if (timing) {
-        if (h->ev.size() < 4 * (h->ev_used + 1)) {
-            const size_t old = h->ev.size();
-            h->ev.resize(old + 4 * 64, nullptr);
-            for (size_t i = old; i < h->ev.size(); ++i) HIP_TRY(h, hipEventCreate(&h->ev[i]));
-        }
-        ev = &h->ev[4 * h->ev_used];
-        if (h->ev_two.size() < h->ev_used + 1) h->ev_two.resize(h->ev_used + 64, 0);
-    }
-    // event 0 (start of the step) is recorded in front of the step's first launch -- unless the step turns out to be ONE kernel: then
-    // only the pair around that kernel is recorded (an event record costs ~3.5 us of stream time: four of them are 5 % of such a step)
-    bool ev0_done = false;
-    auto ev0 = [&]() -> hipError_t {
-        if (!timing || ev0_done) return hipSuccess;
-        ev0_done = true;
-        return hipEventRecord(ev[0], st);
-    };
-
-    AdmmInstParams ip;
-    bool guess_ws = false;       // this step's guess came with the inverse of its working set (k_guess_iterate_ws)
-    bool inst_pending = false;   // per-instance ADMM not launched yet: small problems go out fused with their finish (k_step_inst_wave)
-    if (h->batched) {  // per-instance models: one workgroup per instance, KKT inverse in LDS
-        ip.nz = h->nz; ip.n = h->n; ip.m = h->m; ip.batch = h->batch; ip.nzs = h->nzs;
-        ip.Minv = h->bMinv; ip.Hs = h->bHs; ip.Fs = h->bFs; ip.Vs = h->bVs; ip.dvec = h->bD; ip.rhovec = h->bRho;
-        ip.fS = h->dFS; ip.v0S = h->dV0S; ip.umin = h->dUmin; ip.umax = h->dUmax;
-        ip.uref = h->dUref; ip.uref_stride = h->uref_stride; ip.xref = h->dXref; ip.xref_stride = h->xref_stride; ip.x0 = h->dX0;
-        ip.xs = h->dXs; ip.zs = h->dZs; ip.ys = h->dYs; ip.v0 = h->dV0; ip.status = h->dStatus; ip.iters = h->dIters;
-        ip.piters = h->dPiters; ip.perm = h->dPerm;
-        ip.sigma = o.sigma; ip.alpha = o.alpha; ip.eps_abs = o.eps_abs; ip.eps_rel = o.eps_rel;
-        ip.max_iter = o.max_iter; ip.check_every = o.check_every; ip.warm = o.warm_start ? 1 : 0;
-        ip.mat_stride = (long)h->nz * h->nzs; ip.fv_stride = (long)h->n * h->nzs; ip.vec_stride = h->nzs; ip.fs_stride = h->nz;
-        if (h->skip_admm) {
-            if (!o.polish) return fail(h, ALMPC_ERR_INVALID, "calculate: the SQP loop needs opts.polish = 1");
-            HIP_TRY(h, ev0());
-            if (h->skip_admm == 2) hipLaunchKernelGGL(k_guess_shift, dim3((h->batch + 3) / 4), dim3(256), 0, st, ip, (const double*)h->dU, h->N);
-            else if (h->nzs <= 128 && h->nzs > 64 && h->batch <= 2 * h->num_cus && h->dSglobal && h->bG && !getenv("ALMPC_NO_GUESS_WS")) {
-                // the guess of an SQP iteration AND the inverse of its working set (33..64 of the inputs on a bound), four waves per
-                // instance: k_guess_iterate_ws; installed by k_polish_sgl<1> below
-                if (!h->dStartRows) HIP_TRY(h, dalloc(&h->dStartRows, (size_t)h->batch * 65));
-                GuessWsParams gw;
-                gw.G = h->bG; gw.G_stride = (long)h->nz * h->nzs; gw.sinv = h->dSglobal; gw.rows = h->dStartRows;
-                hipLaunchKernelGGL(k_guess_iterate_ws, dim3((unsigned)h->batch), dim3(256), 0, st, ip, gw);
-                guess_ws = true;
-            } else hipLaunchKernelGGL(k_guess_iterate, dim3((h->batch + 3) / 4), dim3(256), 0, st, ip);
-            HIP_TRY(h, hipGetLastError());
-        } else {
-            inst_pending = true;
-        }
-    }
-    auto flush_admm_inst = [&]() -> int {   // the two-launch path of per-instance models: k_admm_inst on its own
-        if (!inst_pending) return ALMPC_OK;
-        inst_pending = false;
-        HIP_TRY(h, ev0());
-        const bool packed = h->minv_packed;
-        const size_t l = admm_inst_lds_doubles(h->nz, h->nzs, h->m, packed) * sizeof(double);
-        if (l > 64 * 1024)
-            HIP_TRY(h, ensure_dyn_lds(packed ? reinterpret_cast<const void*>(k_admm_inst<true>) : reinterpret_cast<const void*>(k_admm_inst<false>), (size_t)(l)));
-        // persistent grid: as many workgroups as fit the CUs at once (LDS bound; 512 threads each, at most 4 per CU)
-        const int per_cu = 2;  // register bound: 2 x 256 threads at up to 256 VGPRs each fill the CU's register file
-        int wgs = h->num_cus * per_cu;
-        if (wgs > h->batch) wgs = h->batch;
-        ip.minv_stride = packed ? packed_tri_doubles(h->nz) : 0;
-        if (packed) hipLaunchKernelGGL((k_admm_inst<true>), dim3(wgs), dim3(ADMM_INST_THREADS), l, st, ip);
-        else hipLaunchKernelGGL((k_admm_inst<false>), dim3(wgs), dim3(ADMM_INST_THREADS), l, st, ip);
-        HIP_TRY(h, hipGetLastError());
-        return ALMPC_OK;
-    };
-    AdmmParams ap;
-    bool admm_pending = false;  // shared-model ADMM not launched yet: it may go out fused with the polish (k_step_fused)
-    const int admm_grid = (h->batch + TILE - 1) / TILE;
-    const size_t admm_lds = ((size_t)2 * h->nzs * TILE + (size_t)h->nrb * 8 * TILE + (size_t)4 * h->ksf * TILE) * sizeof(double);
-    if (!h->batched) {
-    ap.nz = h->nz; ap.n = h->n; ap.m = h->m; ap.batch = h->batch; ap.nzs = h->nzs;
-    ap.MinvFrag = h->dMinvFrag; ap.VFrag = h->dVFrag; ap.v0S = h->dV0S; ap.v0S_stride = h->fS_stride; ap.HFrag = h->dHFrag; ap.FFrag = h->dFFrag; ap.ksf = h->ksf;
-    ap.dvec = h->dD; ap.rhovec = h->dRho; ap.umin = h->dUmin; ap.umax = h->dUmax;
-    ap.uref = h->dUref; ap.uref_stride = h->uref_stride; ap.xref = h->dXref; ap.xref_stride = h->xref_stride;
-    ap.fS = h->dFS; ap.fS_stride = h->fS_stride; ap.x0 = h->dX0;
-    ap.xs = h->dXs; ap.zs = h->dZs; ap.ys = h->dYs; ap.v0 = h->dV0; ap.status = h->dStatus; ap.iters = h->dIters;
-    ap.piters = h->dPiters;
-    ap.perm = h->dPerm;
-    ap.rho = o.rho; ap.sigma = o.sigma; ap.alpha = o.alpha; ap.eps_abs = o.eps_abs; ap.eps_rel = o.eps_rel;
-    ap.max_iter = o.max_iter; ap.check_every = o.check_every; ap.warm = o.warm_start ? 1 : 0;
-    ap.keep_state = keep_state ? 1 : 0; ap.yflags = h->dYflags;
-    admm_pending = true;
-    }
-    auto flush_admm = [&]() -> int {  // the two-kernel path: ADMM on its own
-        { const int rci_ = flush_admm_inst(); if (rci_ != ALMPC_OK) return rci_; }
-        HIP_TRY(h, ev0());
-        if (admm_pending) {
-            admm_pending = false;
-            HIP_TRY(h, launch_admm(h->nrb, h->ks, ap, admm_grid, admm_lds, st));
-        }
-        if (timing) HIP_TRY(h, hipEventRecord(ev[1], st));
-        return ALMPC_OK;
-    };
-
-    RolloutParams rp;
-    rp.n = h->n; rp.m = h->m; rp.N = h->N; rp.batch = h->batch; rp.nzs = h->nzs; rp.A = h->batched ? h->bA : h->dA; rp.B = h->batched ? h->bB : h->dB;
-    rp.dvec = h->dD; rp.w = h->dZs; rp.x0 = h->dX0; rp.xref = h->dXref; rp.xref_stride = h->xref_stride;
-    rp.uref = h->dUref; rp.uref_stride = h->uref_stride; rp.umin = h->dUmin; rp.umax = h->dUmax; rp.x = h->dX; rp.ex = h->dEx; rp.u = h->dU; rp.eu = h->dEu;
-    bool fused = false;
-    if (h->mc > 0 && !o.polish)
-        return fail(h, ALMPC_ERR_UNSUPPORTED, "calculate: problems with state rows (state box / terminal equality) need opts.polish = 1");
-    int roll_g = 1;
-    while (2 * roll_g * h->n <= 64) roll_g *= 2;
-    const int roll_C = h->n + h->m;
-    int roll_cpl = (roll_C + roll_g - 1) / roll_g;
-    const bool roll_fits = (size_t)(h->N + 1) * roll_C <= 32 * 32 && roll_cpl <= 8;
-    roll_cpl = roll_cpl <= 1 ? 1 : (roll_cpl <= 2 ? 2 : (roll_cpl <= 4 ? 4 : 8));
-    if (h->mc > 0) {
-        if (!roll_fits) return fail(h, ALMPC_ERR_UNSUPPORTED, "calculate: state rows need the fused rollout (n + m <= 8 * lanes-per-row)");
-        { const int rc_ = flush_admm(); if (rc_ != ALMPC_OK) return rc_; }
-        PolishGenParams gp;
-        gp.nz = h->nz; gp.mc = h->mc; gp.R = h->R; gp.Rs = h->Rs; gp.m = h->m; gp.n = h->n; gp.N = h->N; gp.batch = h->batch; gp.nzs = h->nzs;
-        if (h->batched && !h->ghat_inst) return fail(h, ALMPC_ERR_NOT_DESIGNED, "calculate: state rows without their per-instance matrices");
-        if (h->ltv) {
-            const bool sq = h->sqp.ready;
-            gp.ltv = 1;
-            gp.ltvA = sq ? h->sqp.A : h->lA; gp.ltvB = sq ? h->sqp.B : h->lB; gp.ltvC = sq ? h->sqp.c : h->lC;
-            if (!gp.ltvA || !gp.ltvB) return fail(h, ALMPC_ERR_NOT_DESIGNED, "calculate: state rows of a time-varying design without its stage models");
-            if (h->terminal_eq) { gp.eq_off = (sq ? h->sqp.ebar : h->lE) + (size_t)(h->N - 1) * h->n; gp.eq_stride = (long)h->N * h->n; }
-        }
-        if (h->batched) {
-            gp.Ghat_stride = (long)h->R * h->Rs; gp.gnorm_stride = h->Rs; gp.d_stride = h->nzs;
-            gp.A_stride = (long)h->n * h->n; gp.B_stride = (long)h->n * h->m;
-        }
-        if (!h->batched && h->roll_s > 0) { gp.rollM = h->dRollM; gp.roll_s = h->roll_s; gp.roll_nb = h->roll_nb; }
-        if (h->eq_proj && !h->batched) { gp.eq_proj = 1; gp.eq0 = h->R - h->n; gp.ne = h->n; gp.GhatE = h->dGhatE; gp.WinvE = h->dWinvE; }
-        gp.Ghat = h->dGhat; gp.gnorm = h->dGnorm; gp.row_traj = h->dRowTraj; gp.row_eq = h->dRowEq; gp.row_xidx = h->dRowXidx;
-        gp.row_state = h->dRowState; gp.xmin = h->dXmin; gp.xmax = h->dXmax; gp.has_box = h->has_box;
-        gp.dvec = h->batched ? h->bD : h->dD; gp.umin = h->dUmin; gp.umax = h->dUmax; gp.uref = h->dUref; gp.uref_stride = h->uref_stride;
-        gp.zs = h->dZs; gp.ys = h->dYs; gp.v0 = h->dV0; gp.status = h->dStatus; gp.piters = h->dPiters;
-        gp.max_iter = o.polish_max_iter > 0 ? o.polish_max_iter : 20 * h->R + 50;
-        gp.roll_g = roll_g; gp.roll_cpl = roll_cpl; gp.roll = rp;
-        if (!h->dOverflow) HIP_TRY(h, dalloc(&h->dOverflow, (size_t)h->batch * 33 + 2));   // list, then [batch][32] working sets
-        HIP_TRY(h, hipMemsetAsync(h->dOverflow, 0, 2 * sizeof(int32_t), st));
-        if (!h->dOvfSinv) HIP_TRY(h, dalloc(&h->dOvfSinv, (size_t)h->batch * (32 * 32 + 32)));
-        gp.ovf = h->dOverflow; gp.ovf_ws = h->dOverflow + 2 + h->batch; gp.ovf_sinv = h->dOvfSinv;
-        if (lazy_redo) { HIP_TRY(h, ensure_unsolved_word()); gp.unsolved = h->dUnsolved; gp.redo_gate = h->dRedoGate; gp.step_serial = h->step_serial; }
-        if (h->fallback && !h->ltv && h->sd.ready && !h->sd.sqp && !getenv("ALMPC_NO_REDO_START")) {   // a stage-wise redo may follow: it starts from what this finish gives up with
-            if (!h->sd.start_ws) HIP_TRY(h, dalloc(&h->sd.start_ws, (size_t)h->batch * 64));
-            gp.redo_ws = h->sd.start_ws; gp.redo_sp = h->sd.NT + h->sd.MC; gp.redo_nt = h->sd.NT;
-            h->sd.start_ws_fresh = true;
-        }
-        if (h->s0_basis_ok && !h->batched && !h->ltv && h->fS_stride == 0) gp.s0_basis = h->dS0Basis;   // (shared model, shared references)
-        const dim3 grid((h->batch + PGEN_WAVES - 1) / PGEN_WAVES), block(64 * PGEN_WAVES);
-        // first launch: working sets up to 32 rows, every instance; second launch: the instances the first one flagged, up to 64 rows
-        const size_t l32 = (size_t)PGEN_WAVES * pgen_lds_per_wave(32) * sizeof(double);
-        const size_t l64 = (size_t)pgen_coop_lds_doubles() * sizeof(double);   // (wave 0's buffers + job word + three partial sums)
-#define PGEN_LAUNCH(NP_)                                                                                                         \
-    do {                                                                                                                         \
-        hipLaunchKernelGGL((k_polish_gen<NP_>), grid, block, l32, st, gp);                                                       \
-        HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_polish_gen64<NP_>), l64));                                     \
-        hipLaunchKernelGGL((k_polish_gen64<NP_>), dim3(3 * h->num_cus < h->batch ? 3 * h->num_cus : h->batch), dim3(64 * (PGEN_HELPERS + 1)), l64, st, gp); \
-    } while (0)
-        switch (h->np_pairs) {
-            case 1: PGEN_LAUNCH(1); break;
-            case 2: PGEN_LAUNCH(2); break;
-            case 3: PGEN_LAUNCH(3); break;
-            default: PGEN_LAUNCH(4); break;
-        }
-#undef PGEN_LAUNCH
-        HIP_TRY(h, hipGetLastError());
-        fused = true;
-    } else if (o.polish) {
-        PolishParams pp;
-        pp.nz = h->nz; pp.m = h->m; pp.batch = h->batch; pp.nzs = h->nzs;
-        pp.G = h->batched ? h->bG : h->dG; pp.dvec = h->batched ? h->bD : h->dD;
-        pp.G_stride = h->batched ? (long)h->nz * h->nzs : 0; pp.d_stride = h->batched ? (long)h->nzs : 0;
-        pp.A_stride = h->batched ? (long)h->n * h->n : 0; pp.B_stride = h->batched ? (long)h->n * h->m : 0;
-        pp.wave_const_off = -1; pp.sg_off = 0; pp.g_off = 0; pp.sg_shared_off = -1;
-        pp.umin = h->dUmin; pp.umax = h->dUmax; pp.uref = h->dUref; pp.uref_stride = h->uref_stride;
-        pp.zs = h->dZs; pp.ys = h->dYs; pp.v0 = h->dV0; pp.w = h->dW; pp.status = h->dStatus; pp.piters = h->dPiters;
-        pp.yflags = keep_state ? nullptr : h->dYflags; pp.yflag_words = h->nrb;
-        pp.sglobal = h->dSglobal; pp.perm = h->dPerm; pp.ntiles = (h->batch + 15) / 16;
-        pp.max_iter = o.polish_max_iter > 0 ? o.polish_max_iter : 2 * h->nz + 50;
-        pp.dflag = h->flag_in_finish ? h->bFlag : nullptr;
-        if (lazy_redo) {
-            HIP_TRY(h, ensure_unsolved_word());
-            pp.unsolved = h->dUnsolved; pp.redo_gate = h->dRedoGate; pp.step_serial = h->step_serial;
-        }
-        // rollout fused into the tail of the polish when its trajectory buffer fits the wave's LDS slot
-        fused = roll_fits;
-        const bool blocked = !h->batched && h->roll_s > 0;   // shared model: blocked rollout, no trajectory buffer
-        if (blocked) fused = true;
-        pp.fuse_rollout = fused ? (h->ltv ? 2 : (blocked ? 3 : 1)) : 0; pp.roll_g = roll_g; pp.roll_cpl = roll_cpl; pp.roll = rp;
-        pp.rollM = h->dRollM; pp.roll_s = h->roll_s; pp.roll_nb = h->roll_nb;
-        int per_wave = POLISH_LDS_MIN_PER_WAVE;
-        if (fused && !blocked && (h->N + 1) * (h->n + h->m) > per_wave) per_wave = (h->N + 1) * (h->n + h->m);
-        per_wave = (per_wave + 1) & ~1;
-        if (h->batched) {  // the wave's private copy of d_i | [A_i B_i] sits behind its buffers
-            if (!fused) return fail(h, ALMPC_ERR_UNSUPPORTED, "calculate: per-instance models need the fused rollout (n + m <= 8 * lanes-per-row)");
-            pp.wave_const_off = per_wave;
-            per_wave += (h->nzs + h->n * (h->n + h->m) + 1) & ~1;
-        }
-        pp.lds_per_wave = per_wave;
-        // G in LDS when it fits beside the buffers of 8 waves (gfx950: 160 KB per workgroup)
-        const PolishShared SL = polish_shared_layout(h->n, h->m, h->N, h->nz, h->nzs, pp.fuse_rollout);
-        const size_t g_lds = (size_t)h->nz * ((h->nz + 1) & ~1);  // doubles: rows of G packed to an even stride
-        size_t l_glds = (g_lds + SL.total + (size_t)POLISH_WAVES_GLDS * per_wave + 2) * sizeof(double);
-        // workgroup-shared second-tier slot (working sets beyond 32 rows) behind the queue words, if the 160 KB allow it
-        pp.sg_shared_off = -1;
-        {
-            const size_t slot = (size_t)POLISH_SG_SHARED_CAP * 64 * sizeof(double);
-            if (l_glds + slot <= 160 * 1024 && !h->batched && !getenv("ALMPC_POLISH_SG_GLOBAL")) {
-                pp.sg_shared_off = (int)(SL.total + (size_t)POLISH_WAVES_GLDS * per_wave + 2);
-                l_glds += slot;
-            }
-        }
-        // one kernel for the whole step when the tile is 8 waves and [G | union(ADMM buffers, polish buffers)] fits LDS
-        size_t l_step = l_glds - g_lds * sizeof(double);
-        if (admm_lds > l_step) l_step = admm_lds;
-        l_step += g_lds * sizeof(double);
-        const bool step_fused = admm_pending && h->fuse_step && POLISH_WAVES_GLDS == 8 && !h->polish_no_glds && h->nrb == 8 && (h->ks == 30 || h->ks == 32) &&
-                                fused && l_step <= 160 * 1024;
-        if (step_fused) {
-            admm_pending = false;
-            if (timing) HIP_TRY(h, hipEventRecord(ev[1], st));  // no boundary between the phases to time: admm_ms reads 0
-            if (h->ks == 30) {
-                HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_step_fused<8, 30>), (size_t)(l_step)));
-                hipLaunchKernelGGL((k_step_fused<8, 30>), dim3(pp.ntiles), dim3(512), l_step, st, ap, pp);
-            } else {
-                HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_step_fused<8, 32>), (size_t)(l_step)));
-                hipLaunchKernelGGL((k_step_fused<8, 32>), dim3(pp.ntiles), dim3(512), l_step, st, ap, pp);
-            }
-                } else if (admm_pending && !h->batched && h->nzs <= 64 && fused && h->dPlain && !h->ltv &&
-                           !(getenv("ALMPC_NO_SHARED_WAVE") && getenv("ALMPC_NO_SHARED_WAVE")[0] == '1') &&
-                           (long)h->batch <= (getenv("ALMPC_SHARED_WAVE_MAX_BATCH") ? atol(getenv("ALMPC_SHARED_WAVE_MAX_BATCH")) : (long)2 * h->num_cus) &&
-                           ((size_t)SL.total + (size_t)per_wave) * sizeof(double) <= 64 * 1024) {
-            // small SHARED problems in small batches (configs[0], the reference's own test sizes: one instance, N 5 - 15, m 2 -> nz
-            // 10 - 30; round 5): the two-launch path gives them a 16-instance MFMA tile they cannot fill and two launch ramps.  ONE
-            // kernel, one wave per instance -- k_step_inst_wave with operand strides of zero: every wave reads the same dense
-            // Minv / F' / V (a few KB, L1 / L2 resident), runs the ADMM iterations from registers and then the single-wave finish
-            // (G through L1: 13 KB at nz 40).  Measured (tools/time_small_shared.py, QTP fixture, N 5 / N 20, us per step): batch 1
-            // 16.9 / 21.8 against 29.7 / 33.1, batch 64 20 / 45 against 43 / 56, batch 512 30 / 58 against 44 / 58; from 2048
-            // instances on a wave per 10 - 40-row problem wastes the machine (63 / 113 against 45 / 70 us; 65,536: 1.8 / 2.3 ms
-            // against 0.32 / 0.68 ms): up to two instances per CU take this path, larger batches the tile path.
-            admm_pending = false;
-            HIP_TRY(h, ev0());
-            const size_t mm = (size_t)h->nz * h->nzs, fv = (size_t)h->n * h->nzs;
-            ip.nz = h->nz; ip.n = h->n; ip.m = h->m; ip.batch = h->batch; ip.nzs = h->nzs;
-            ip.Minv = h->dPlain; ip.Hs = h->dPlain + mm; ip.Fs = h->dPlain + 2 * mm; ip.Vs = h->dPlain + 2 * mm + fv;
-            ip.dvec = h->dD; ip.rhovec = h->dRho;
-            ip.mat_stride = 0; ip.fv_stride = 0; ip.vec_stride = 0; ip.fs_stride = h->fS_stride;
-            ip.fS = h->dFS; ip.v0S = h->dV0S; ip.umin = h->dUmin; ip.umax = h->dUmax;
-            ip.uref = h->dUref; ip.uref_stride = h->uref_stride; ip.xref = h->dXref; ip.xref_stride = h->xref_stride; ip.x0 = h->dX0;
-            ip.xs = h->dXs; ip.zs = h->dZs; ip.ys = h->dYs; ip.v0 = h->dV0; ip.status = h->dStatus; ip.iters = h->dIters;
-            ip.piters = h->dPiters; ip.perm = h->dPerm;
-            ip.sigma = o.sigma; ip.alpha = o.alpha; ip.eps_abs = o.eps_abs; ip.eps_rel = o.eps_rel;
-            ip.max_iter = o.max_iter; ip.check_every = o.check_every; ip.warm = o.warm_start ? 1 : 0;
-            pp.yflags = nullptr; pp.yflag_words = 0;   // (this ADMM phase hands over y itself)
-            const size_t l_sgl = ((size_t)SL.total + (size_t)per_wave) * sizeof(double);
-            pp.sg_off = -1; pp.g_off = 0;
-            pp.lds_per_wave = per_wave;
-            pp.direct = 1;
-            if (timing) HIP_TRY(h, hipEventRecord(ev[1], st));
-#define STEP_SHARED(NZC_)                                                                                            \
-    do {                                                                                                             \
-        HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_step_inst_wave<NZC_>), l_sgl));                    \
-        hipLaunchKernelGGL((k_step_inst_wave<NZC_>), dim3((unsigned)h->batch), dim3(64), l_sgl, st, ip, pp);         \
-    } while (0)
-            if (h->nzs <= 16) STEP_SHARED(16);
-            else if (h->nzs <= 32) STEP_SHARED(32);
-            else if (h->nzs <= 48) STEP_SHARED(48);
-            else STEP_SHARED(64);
-#undef STEP_SHARED
-                } else if (inst_pending && h->nzs <= 64 && fused && !(getenv("ALMPC_NO_INST_WAVE") && getenv("ALMPC_NO_INST_WAVE")[0] == '1') &&
-                           ((size_t)SL.total + (size_t)per_wave + (size_t)h->nz * h->nzs) * sizeof(double) <= 64 * 1024) {
-            // small per-instance problems (BASELINE configs[3]): ONE wave per instance for the whole step -- ADMM with the KKT
-            // inverse in registers, then the single-wave finish with G_i in the wave's LDS (the second-tier Sinv, rarely needed at
-            // these sizes, stays in the global scratch: with its 32 KB per wave only three waves would fit a CU)
-            inst_pending = false;
-            const size_t sgl_wave = (size_t)per_wave + (size_t)h->nz * h->nzs;
-            const size_t l_sgl = ((size_t)SL.total + sgl_wave) * sizeof(double);
-            pp.sg_off = -1;
-            pp.g_off = per_wave;
-            pp.lds_per_wave = (int)sgl_wave;
-            pp.direct = 1;
-            if (timing) HIP_TRY(h, hipEventRecord(ev[1], st));  // no boundary between the phases to time: admm_ms reads 0
-#define STEP_INST(NZC_)                                                                                              \
-    do {                                                                                                             \
-        HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_step_inst_wave<NZC_>), l_sgl));                    \
-        hipLaunchKernelGGL((k_step_inst_wave<NZC_>), dim3((unsigned)h->batch), dim3(64), l_sgl, st, ip, pp);         \
-    } while (0)
-            if (h->nzs <= 16) STEP_INST(16);
-            else if (h->nzs <= 32) STEP_INST(32);
-            else if (h->nzs <= 48) STEP_INST(48);
-            else STEP_INST(64);
-#undef STEP_INST
-                } else {
-        { const int rc_ = flush_admm(); if (rc_ != ALMPC_OK) return rc_; }
-        if (l_glds <= 160 * 1024 && !h->polish_no_glds && !h->batched) {
-            HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_polish<true>), (size_t)(l_glds)));
-            int wgs = pp.ntiles;  // one ADMM tile (16 instances) per workgroup and round
-            if (wgs > h->num_cus) wgs = h->num_cus;
-            hipLaunchKernelGGL((k_polish<true>), dim3(wgs), dim3(64 * POLISH_WAVES_GLDS), l_glds, st, pp);
-        } else {
-            const size_t l = ((size_t)SL.total + (size_t)POLISH_WAVES * per_wave) * sizeof(double);
-            // small batches of per-instance models: single-wave workgroups with G_i and the second-tier Sinv in LDS
-            const size_t sgl_wave = (size_t)per_wave + POLISH_GLB_PER_INST + (size_t)h->nz * h->nzs;
-            const size_t l_sgl = ((size_t)SL.total + sgl_wave) * sizeof(double);
-            if (h->batched && h->batch <= 2 * h->num_cus && l_sgl <= 160 * 1024 && !getenv("ALMPC_POLISH_SG_GLOBAL")) {
-                pp.sg_off = per_wave;
-                pp.g_off = per_wave + POLISH_GLB_PER_INST;
-                pp.lds_per_wave = (int)sgl_wave;
-                if (guess_ws) {
-                    pp.start_rows = h->dStartRows;
-                    HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_polish_sgl<1>), (size_t)(l_sgl)));
-                    hipLaunchKernelGGL((k_polish_sgl<1>), dim3(pp.ntiles * 16), dim3(64), l_sgl, st, pp);
-                } else {
-                HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_polish_sgl<0>), (size_t)(l_sgl)));
-                hipLaunchKernelGGL((k_polish_sgl<0>), dim3(pp.ntiles * 16), dim3(64), l_sgl, st, pp);
-                }
-            } else {
-            HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_polish<false>), l));
-            hipLaunchKernelGGL((k_polish<false>), dim3((pp.ntiles * 16 + POLISH_WAVES - 1) / POLISH_WAVES), dim3(64 * POLISH_WAVES), l, st, pp);
-            }
-        }
-        }
-        HIP_TRY(h, hipGetLastError());
-        rp.w = h->dW;
-    } else {
-        const int rc_ = flush_admm();
-        if (rc_ != ALMPC_OK) return rc_;
-    }
-    if (timing) HIP_TRY(h, hipEventRecord(ev[2], st));
-
-    if (!fused) {
-        const size_t per_wave = (size_t)h->n * (h->N + 1) + h->nz, shared = (size_t)h->n * h->n + (size_t)h->n * h->m;
-        if (h->batched) { rp.A_stride = (long)h->n * h->n; rp.B_stride = (long)h->n * h->m; rp.d_stride = h->nzs; rp.dvec = h->bD; }
-        if (!h->batched && (shared + 4 * per_wave) * sizeof(double) <= 60 * 1024) {
-            const size_t l = (shared + 4 * per_wave) * sizeof(double);
-            hipLaunchKernelGGL((k_rollout<4>), dim3((h->batch + 3) / 4), dim3(256), l, st, rp);
-        } else {  // long horizons with many states: one instance per workgroup, LDS beyond the 64 KiB default
-            const size_t l = (shared + per_wave) * sizeof(double);
-            HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_rollout<1>), (size_t)(l)));
-            hipLaunchKernelGGL((k_rollout<1>), dim3(h->batch), dim3(64), l, st, rp);
-        }
-        HIP_TRY(h, hipGetLastError());
-    }
-    // structured fallback: instances the condensed path left without a certificate (status != 0: an active-set finish that ran into
-    // its cap, a non-finite or indefinite condensed problem) are redone in the multiple-shooting form, from the step's own result
-    if (lazy_redo) h->lazy_pending = true;   // (resolve_lazy_redo at the next host sync point)
-    else if (h->fallback && !h->ltv && o.polish) {
-        if (h->sd.ready && !getenv("ALMPC_DBG_NO_SDUAL_FB")) {
-            if (h->sd.per_instance) HIP_TRY(h, launch_sgains(h, 1));   // (stage records of the unsolved instances only, from the models of this step)
-            HIP_TRY(h, launch_sdual(h, 1, h->dU, 0, true));
-        }
-        if (h->mc == 0 && !h->useS && h->rKst && !getenv("ALMPC_DBG_NO_PRIMAL_NET")) HIP_TRY(h, launch_riccati(h, 1, h->dU, 0));
-    }
-    if (timing) {
-        if (ev0_done) HIP_TRY(h, hipEventRecord(ev[3], st));
-        h->ev_two[h->ev_used] = ev0_done ? 0 : 1;
-        h->ev_used += 1;
-    }
-    return io_step_done();
-}
+int almpc_calculate_async(almpc_handle* h, const almpc_opts* user) { return calculate_checked(h, user, StepMode()); }
 
 int almpc_synchronize(almpc_handle* h) {
     if (!h) return ALMPC_ERR_INVALID;

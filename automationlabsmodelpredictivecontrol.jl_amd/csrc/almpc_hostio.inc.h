@@ -264,7 +264,7 @@ int almpc_host_results(almpc_handle* h, int ticket, const double** x, const doub
 
 int almpc_get_first_input(almpc_handle* h, double* u0) {
     if (!h || !u0) return h ? fail(h, ALMPC_ERR_INVALID, "get_first_input: null u0") : ALMPC_ERR_INVALID;
-    if (h->lazy_pending) {   // (synchronous getter: settle a lazily deferred redo before the first inputs are packed)
+    if (h->redo.lazy_pending) {   // (synchronous getter: settle a lazily deferred redo before the first inputs are packed)
         HIP_TRY(h, hipSetDevice(h->device));
         const int rc_ = wait_and_settle(h, true);
         if (rc_ != ALMPC_OK) return rc_;
@@ -580,7 +580,7 @@ int almpc_group_get_results(almpc_group* g, double* x, double* e_x, double* u, d
                           (polish_iters ? ALMPC_WANT_POLISH_ITERS : 0);
     if (!want) return ALMPC_OK;
     for (size_t i = 0; i < g->hs.size(); ++i)   // (a synchronous look at the results: a lazily deferred redo is settled first, per device)
-        if (g->hs[i]->lazy_pending) { const int rc = almpc_synchronize(g->hs[i]); if (rc != ALMPC_OK) return gfail(g, rc, (int)i); }
+        if (g->hs[i]->redo.lazy_pending) { const int rc = almpc_synchronize(g->hs[i]); if (rc != ALMPC_OK) return gfail(g, rc, (int)i); }
     for (size_t i = 0; i < g->hs.size(); ++i) {
         g->tickets[i] = almpc_get_results_async(g->hs[i], want);
         if (g->tickets[i] < 0) return gfail(g, g->tickets[i], (int)i);

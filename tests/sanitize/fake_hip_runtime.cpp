@@ -1,19 +1,47 @@
 // Stand-in for libamdhip64 in the CPU sanitizer build of the library's HOST half (tests/test_sanitizers.py): "device" memory is
 // calloc'd host memory (so every hipMemcpy / hipMemset of the launch logic is bounds-checked by AddressSanitizer), streams and events
 // are dummy objects, kernel launches do nothing.  Only what csrc/almpc_api.hip links against.  Test infrastructure, never shipped.
+// fake_hip_trace_to(path): every launch from then on appends one line to `path`: the launching stream's creation ordinal (0: the null
+// stream), the demangled kernel name, grid, block and dynamic LDS bytes.
 #include <hip/hip_runtime_api.h>
 
+#include <cxxabi.h>
+
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <mutex>
+#include <string>
 
 namespace {
 struct Cfg { dim3 grid, block; size_t shmem; hipStream_t stream; };
 thread_local Cfg g_cfg;
-long g_launches = 0;
+// (function-local: the library's module constructor registers its kernels before this file's globals would be constructed)
+struct State {
+    std::mutex mu;   // (a group designs its handles on host threads of their own)
+    long launches = 0;
+    int streams = 0;
+    std::map<const void*, int> stream_ord;
+    std::map<const void*, std::string> kernel_name;
+    FILE* trace = nullptr;
+};
+State& S() { static State s; return s; }
 }
 
 extern "C" {
-long fake_hip_launch_count() { return g_launches; }
+long fake_hip_launch_count() { State& g = S(); std::lock_guard<std::mutex> l(g.mu); return g.launches; }
+int fake_hip_trace_to(const char* path) {
+    State& g = S(); std::lock_guard<std::mutex> l(g.mu);
+    if (g.trace) std::fclose(g.trace);
+    g.trace = std::fopen(path, "w");
+    return g.trace ? 0 : 1;
+}
+void fake_hip_trace_close() {
+    State& g = S(); std::lock_guard<std::mutex> l(g.mu);
+    if (g.trace) std::fclose(g.trace);
+    g.trace = nullptr;
+}
 
 hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
@@ -42,8 +70,17 @@ hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipSt
 hipError_t hipMemset(void* d, int v, size_t n) { std::memset(d, v, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { std::memset(d, v, n); return hipSuccess; }
 
-hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = reinterpret_cast<hipStream_t>(std::malloc(8)); return hipSuccess; }
-hipError_t hipStreamDestroy(hipStream_t s) { std::free(s); return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
+    *s = reinterpret_cast<hipStream_t>(std::malloc(8));
+    State& g = S(); std::lock_guard<std::mutex> l(g.mu);
+    g.stream_ord[*s] = ++g.streams;
+    return hipSuccess;
+}
+hipError_t hipStreamDestroy(hipStream_t s) {
+    { State& g = S(); std::lock_guard<std::mutex> l(g.mu); g.stream_ord.erase(s); }
+    std::free(s);
+    return hipSuccess;
+}
 hipError_t hipStreamQuery(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
@@ -56,12 +93,37 @@ hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.01f; return hipSuccess; }
 
 hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
-hipError_t hipLaunchKernel(const void*, dim3, dim3, void**, size_t, hipStream_t) { ++g_launches; return hipSuccess; }
+hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void**, size_t sh, hipStream_t st) {
+    State& g = S(); std::lock_guard<std::mutex> l(g.mu);
+    ++g.launches;
+    if (g.trace) {
+        const auto k = g.kernel_name.find(f);
+        const auto o = g.stream_ord.find(st);
+        std::fprintf(g.trace, "%d %s grid %u %u %u block %u %u %u lds %zu\n", st && o != g.stream_ord.end() ? o->second : 0,
+                     k != g.kernel_name.end() ? k->second.c_str() : "?", grid.x, grid.y, grid.z, block.x, block.y, block.z, sh);
+    }
+    return hipSuccess;
+}
 
 // what hip-clang's host stubs and module constructor call
 void** __hipRegisterFatBinary(const void*) { static void* h[1]; return h; }
 void __hipUnregisterFatBinary(void**) {}
-void __hipRegisterFunction(void**, const void*, char*, const char*, unsigned, void*, void*, void*, void*, int*) {}
+void __hipRegisterFunction(void**, const void* host_fn, char*, const char* device_name, unsigned, void*, void*, void*, void*, int*) {
+    int ok = -1;
+    char* d = abi::__cxa_demangle(device_name, nullptr, nullptr, &ok);
+    std::string name = ok == 0 && d ? d : device_name;
+    std::free(d);
+    if (name.compare(0, 5, "void ") == 0) name.erase(0, 5);   // (return type of a template)
+    if (!name.empty() && name.back() == ')') {                 // (parameter list)
+        int depth = 0;
+        for (size_t i = name.size(); i-- > 0;) {
+            depth += name[i] == ')' ? 1 : (name[i] == '(' ? -1 : 0);
+            if (depth == 0) { name.erase(i); break; }
+        }
+    }
+    State& g = S(); std::lock_guard<std::mutex> l(g.mu);
+    g.kernel_name[host_fn] = name;
+}
 void __hipRegisterVar(void**, void*, char*, const char*, int, size_t, int, int) {}
 hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t sh, hipStream_t st) { g_cfg = {g, b, sh, st}; return hipSuccess; }
 hipError_t __hipPopCallConfiguration(dim3* g, dim3* b, size_t* sh, hipStream_t* st) { *g = g_cfg.grid; *b = g_cfg.block; *sh = g_cfg.shmem; *st = g_cfg.stream; return hipSuccess; }

@@ -4,14 +4,21 @@
 // copies, launch-parameter set-up and every host-side readback of the C ABI, for a shared, a state-row, a per-instance, a structured,
 // a re-linearised and an SQP handle, single and as a group, synchronous and through tickets.  The "results" are zeros (no kernel
 // ran): the point is that no call touches memory it does not own.  Prints "host logic ok: <launches> launches".
+// With a path argument the fake runtime writes every launch there (stream ordinal, kernel, grid, block, LDS: the launch trace that
+// tests/golden/host_launch_trace.txt pins); the handles below reach every kernel of the step path at least once.
 #include "../../include/almpc.h"
 
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <string>
 #include <vector>
 
 extern "C" long fake_hip_launch_count();
+extern "C" int fake_hip_trace_to(const char* path);
+extern "C" void fake_hip_trace_close();
+extern char** environ;
 
 #define CK(call)                                                                                             \
     do {                                                                                                     \
@@ -72,7 +79,14 @@ static int step_and_read(almpc_handle* h, int n, int m, int N, int batch, bool t
     return 0;
 }
 
-int main() {
+int main(int argc, char** argv) {
+    {   // the switches are read at call time: none may come in from the caller's environment
+        std::vector<std::string> inherited;
+        for (char** e = environ; *e; ++e)
+            if (std::strncmp(*e, "ALMPC_", 6) == 0) inherited.emplace_back(*e, std::strchr(*e, '=') - *e);
+        for (const std::string& name : inherited) unsetenv(name.c_str());
+    }
+    if (argc > 1 && fake_hip_trace_to(argv[1])) { std::fprintf(stderr, "cannot write %s\n", argv[1]); return 1; }
     almpc_handle* h = nullptr;
     // ---- shared model, input box; then state box + terminal equality + S on the same handle; closed loop on the device
     {
@@ -111,6 +125,13 @@ int main() {
         std::vector<double> xz((size_t)n * (N + 1), 0.0), uz((size_t)m * N, 0.0);
         CK(almpc_set_reference(h, xz.data(), uz.data(), 0));
         if (step_and_read(h, n, m, N, batch, true)) return 1;
+        almpc_opts o;
+        almpc_default_opts(&o);
+        CK(almpc_set_step_fusion(h, 0));   // two launches: ADMM, then k_polish<true>
+        CK(almpc_calculate(h, &o));
+        o.polish = 0;                      // no polish: ADMM + k_rollout<4>
+        CK(almpc_calculate(h, &o));
+        CK(almpc_set_step_fusion(h, 1));
         std::vector<double> Ab((size_t)batch * n * n), Bb((size_t)batch * n * m);
         for (int i = 0; i < batch; ++i) {
             for (size_t t = 0; t < p.A.size(); ++t) Ab[(size_t)i * n * n + t] = p.A[t];
@@ -133,6 +154,45 @@ int main() {
         std::vector<double> xz((size_t)n * (N + 1), 0.0), uz((size_t)m * N, 0.0);
         CK(almpc_set_reference(h, xz.data(), uz.data(), 0));
         if (step_and_read(h, n, m, N, batch, true)) return 1;
+        almpc_opts o;
+        almpc_default_opts(&o);
+        o.warm_start = 1;   // receding-horizon start from the previous inputs (k_guess_from_inputs)
+        CK(almpc_calculate(h, &o));
+        almpc_destroy(h); h = nullptr;
+    }
+    // ---- shared model, nz = 80, G through L2 (k_polish<false>), redo enqueued behind the step (ALMPC_EAGER_REDO)
+    {
+        const int n = 4, m = 2, N = 40, batch = 20;
+        const Plant p = chain(n, m);
+        setenv("ALMPC_POLISH_NO_GLDS", "1", 1);   // (read at handle creation)
+        CK(almpc_create(&h, n, m, N, batch, 0, 0));
+        unsetenv("ALMPC_POLISH_NO_GLDS");
+        CK(almpc_design_shared(h, p.A.data(), p.B.data(), p.Q.data(), p.R.data(), nullptr, nullptr, p.umin.data(), p.umax.data(), nullptr, nullptr, 0.1, 1e-6));
+        std::vector<double> xz((size_t)n * (N + 1), 0.0), uz((size_t)m * N, 0.0);
+        CK(almpc_set_reference(h, xz.data(), uz.data(), 0));
+        setenv("ALMPC_EAGER_REDO", "1", 1);
+        if (step_and_read(h, n, m, N, batch, false)) return 1;
+        unsetenv("ALMPC_EAGER_REDO");
+        almpc_destroy(h); h = nullptr;
+    }
+    // ---- per-instance models, nz = 40, no polish: k_admm_inst with the full inverse, then k_rollout<1>
+    {
+        const int n = 4, m = 2, N = 20, batch = 9;
+        const Plant p = chain(n, m);
+        CK(almpc_create(&h, n, m, N, batch, 0, 0));
+        std::vector<double> Ab((size_t)batch * n * n), Bb((size_t)batch * n * m);
+        for (int i = 0; i < batch; ++i) {
+            for (size_t t = 0; t < p.A.size(); ++t) Ab[(size_t)i * n * n + t] = p.A[t];
+            for (size_t t = 0; t < p.B.size(); ++t) Bb[(size_t)i * n * m + t] = p.B[t] * (1.0 + 0.01 * i);
+        }
+        CK(almpc_design_batched(h, Ab.data(), Bb.data(), p.Q.data(), p.R.data(), nullptr, nullptr, 0, p.umin.data(), p.umax.data(), 0.1, 1e-6));
+        std::vector<double> xz((size_t)n * (N + 1), 0.0), uz((size_t)m * N, 0.0), x0((size_t)batch * n, 0.25);
+        CK(almpc_set_reference(h, xz.data(), uz.data(), 0));
+        CK(almpc_update_initialization(h, x0.data()));
+        almpc_opts o;
+        almpc_default_opts(&o);
+        o.polish = 0;
+        CK(almpc_calculate(h, &o));
         almpc_destroy(h); h = nullptr;
     }
     // ---- re-linearisation pipeline and SQP loop on a small network
@@ -166,6 +226,22 @@ int main() {
         CK(almpc_sqp_fnn_skipped(h, sk.data()));
         almpc_destroy(h); h = nullptr;
     }
+    // ---- SQP loop with nz = 80: the first iteration's ADMM + k_polish_sgl<0>, then k_guess_iterate_ws + k_polish_sgl<1>
+    {
+        const int n = 4, m = 2, N = 40, batch = 11, Hn = 8, L = 2;
+        const Plant p = chain(n, m);
+        std::vector<double> W_in((size_t)Hn * (n + m), 0.05), W_h((size_t)L * Hn * Hn, 0.02), b_h((size_t)L * Hn, 0.01), W_out((size_t)n * Hn, 0.1);
+        std::vector<double> P((size_t)n * n, 0.0), xr((size_t)n * (N + 1), 0.0), ur((size_t)m * N, 0.0), x0((size_t)batch * n, 0.1);
+        for (int i = 0; i < n; ++i) P[(size_t)i * n + i] = 150.0;
+        CK(almpc_create(&h, n, m, N, batch, 0, 0));
+        CK(almpc_sqp_fnn_setup(h, Hn, L, 1, W_in.data(), W_h.data(), b_h.data(), W_out.data(), xr.data(), ur.data(), p.Q.data(), p.R.data(), nullptr,
+                               P.data(), 0, p.umin.data(), p.umax.data(), 0.1, 1e-6));
+        CK(almpc_sqp_fnn_start(h, x0.data(), nullptr));
+        std::vector<double> si(3), di(3);
+        const int rc = almpc_sqp_fnn_iterate(h, 3, 1.0, nullptr, si.data(), di.data());
+        if (rc != ALMPC_OK && rc != ALMPC_ERR_NUMERIC) { std::fprintf(stderr, "sqp iterate -> %d (%s)\n", rc, almpc_last_error(h)); return 1; }
+        almpc_destroy(h); h = nullptr;
+    }
     // ---- a group of three handles (all on the one fake device): uneven shards, tickets
     {
         almpc_group* g = nullptr;
@@ -187,6 +263,7 @@ int main() {
         CKG(almpc_group_advance_plant(g));
         almpc_group_destroy(g);
     }
+    fake_hip_trace_close();
     std::printf("host logic ok: %ld launches\n", fake_hip_launch_count());
     return 0;
 }

@@ -172,6 +172,75 @@ def test_ticket_and_device_resident_paths_never_hand_out_an_undecided_instance(c
     s.close(); ref.close()
 
 
+@pytest.mark.parametrize("read", ("ticket", "advance_plant"))
+def test_a_gated_first_redo_builds_the_cached_responses(capi, mo, monkeypatch, read):
+    """The same contract with a state box and the terminal equality on a shared model: the redo is k_sdual, whose cached responses
+    (SdualParams::ghat) are built at the first redo of a design.  Here that first redo is a gated one behind a step that left nothing
+    undecided (read through a ticket, or behind almpc_advance_plant); the build itself must not be gated, or the table stays empty and
+    every later redo on the design reads zeros.  Step 2, capped so that instances are left undecided and read the same way, must
+    equal the sweep-only redo (ALMPC_SDUAL_NO_GHAT, read at design time) and the exact oracle."""
+    q = mo.quadrotor(30)
+    xmax = np.array([1, 1, 1, .5, .5, .5, .1, .1, .1, .1, .1, .1]) * 3.0
+    p = mo.make_problem(q.A, q.B, 30, q.u_min, q.u_max, x_min=-xmax, x_max=xmax, terminal="equality")
+    batch = 128
+    X1 = np.clip(mo.quadrotor_x0_batch(batch, 0.3), -0.99 * xmax, 0.99 * xmax)
+    X2 = np.clip(mo.quadrotor_x0_batch(batch, 1.0, first_instance=batch), -0.99 * xmax, 0.99 * xmax)
+    capped = capi.default_opts(polish_max_iter=2)
+
+    def solver(**kw):
+        s = capi.Solver(p.n, p.m, p.N, batch, device=0, **kw)
+        s.design_shared(p.A, p.B, p.Q, p.R, p.S, None, p.u_min, p.u_max, xmin=p.x_min, xmax=p.x_max, terminal="equality")
+        s.set_reference(p.x_ref, p.u_ref)
+        return s
+
+    # step 1 leaves nothing undecided, step 2 leaves instances undecided when nobody redoes them
+    off = solver(structured_fallback=False)
+    st = []
+    for X0, o in ((X1, None), (X2, capped)):
+        off.update_initialization(X0); off.calculate(o)
+        st.append(off.get_results(want=("status",))["status"])
+    off.close()
+    assert not np.any(st[0] == 1)
+    undecided = np.flatnonzero(st[1] == 1)
+    assert len(undecided) >= 4
+
+    def run():
+        s = solver()
+        s.update_initialization(X1)
+        s.calculate(sync=False)
+        if read == "ticket":
+            r1 = s.get_results_wait(s.get_results_async(want=("status",)), want=("status",))
+        else:
+            s.advance_plant()
+            r1 = s.get_results(want=("status",))
+        s.update_initialization(X2)
+        s.calculate(capped, sync=False)
+        if read == "ticket":
+            r2 = s.get_results_wait(s.get_results_async(want=("u", "status")), want=("u", "status"))
+        else:
+            s.advance_plant()
+            r2 = s.get_results(want=("u", "status"))
+        s.close()
+        return r1, r2
+
+    monkeypatch.setenv("ALMPC_SDUAL_NO_GHAT", "1")
+    sweeps = run()
+    monkeypatch.delenv("ALMPC_SDUAL_NO_GHAT")
+    cached = run()
+    for a, b in zip(cached, sweeps):
+        assert set(np.unique(a["status"])) <= {0, 3}
+        assert np.array_equal(a["status"], b["status"])
+    a, b = cached[1], sweeps[1]
+    ok = a["status"] == 0
+    assert np.abs(a["u"][ok] - b["u"][ok]).max() <= U_TOL
+    for i in undecided[:4]:
+        try:
+            e = mo.solve_mpc_exact(p, X2[i])
+            assert a["status"][i] == 0 and np.abs(a["u"][i] - e["u"]).max() <= U_TOL, i
+        except ValueError:
+            assert a["status"][i] == 3, i
+
+
 def test_full_read_back_then_next_step_does_not_race(capi, mo):
     """x / e_x / u / e_u are read straight from the result buffers: the next step must wait for that read-back."""
     p = mo.quadrotor()

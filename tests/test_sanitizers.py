@@ -4,6 +4,7 @@ purge, adds and removes of the polish and the rollout, and the library's design-
 exit cleanly (-fno-sanitize-recover=all turns any report into a failure) and reproduce the regular build's numbers."""
 import os
 import subprocess
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -87,8 +88,14 @@ def test_host_launch_logic_of_the_c_abi_under_asan_ubsan(tmp_path):
     subprocess.check_call([clang, "-std=c++17"] + SAN + ["-c", str(tmp_path / "fatbin.cpp"), "-o", o])
     exe = str(tmp_path / "host_logic_san")
     subprocess.check_call([clang] + SAN + ["-o", exe] + objs + [o, "-lpthread", "-ldl"])
-    r = _run([exe])
+    trace = tmp_path / "launches.txt"
+    r = _run([exe, str(trace)])
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     assert "ERROR" not in r.stderr and "runtime error" not in r.stderr
     assert "host logic ok" in r.stdout
     assert int(r.stdout.split("ok:")[1].split()[0]) > 150   # kernel launches were reached on every path
+    # the launch sequence (stream, kernel, grid, block, LDS) is pinned: a change of launches on purpose regenerates the golden file.
+    # Handles of a group launch from threads of their own: the lines are ordered stably by the stream's creation ordinal.
+    lines = sorted(trace.read_text().splitlines(), key=lambda line: int(line.split()[0]))
+    golden = (Path(ROOT) / "tests" / "golden" / "host_launch_trace.txt").read_text().splitlines()
+    assert lines == golden, next(f"line {i + 1}: {a!r} != golden {b!r}" for i, (a, b) in enumerate(zip(lines + [""] * len(golden), golden + [""] * len(lines))) if a != b)
