@@ -81,6 +81,10 @@ def load():
     L.almpc_sqp_fnn_solve.restype = ctypes.c_int
     L.almpc_sqp_fnn_set_hessian.argtypes = [_hp, ctypes.c_int]
     L.almpc_sqp_fnn_set_hessian.restype = ctypes.c_int
+    L.almpc_sqp_fnn_set_row_multipliers.argtypes = [_hp, ctypes.c_int]
+    L.almpc_sqp_fnn_set_row_multipliers.restype = ctypes.c_int
+    L.almpc_sqp_fnn_state_multipliers.argtypes = [_hp, _dp]
+    L.almpc_sqp_fnn_state_multipliers.restype = ctypes.c_int
     L.almpc_get_design_instance.restype = ctypes.c_int
     L.almpc_set_reference.argtypes = [_hp, _dp, _dp, ctypes.c_int]
     L.almpc_set_terminal_equality.argtypes = [_hp, ctypes.c_int]
@@ -155,7 +159,8 @@ def load():
     L.almpc_group_get_results.argtypes = [_hp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
     # group forms of everything a handle can do
     for nm_ in ("almpc_group_set_terminal_equality", "almpc_group_set_rho_profile", "almpc_group_set_structured_fallback",
-                "almpc_group_sqp_fnn_set_structured", "almpc_group_sqp_fnn_set_step_rule", "almpc_group_sqp_fnn_set_hessian"):
+                "almpc_group_sqp_fnn_set_structured", "almpc_group_sqp_fnn_set_step_rule", "almpc_group_sqp_fnn_set_hessian",
+                "almpc_group_sqp_fnn_set_row_multipliers"):
         getattr(L, nm_).argtypes = [_hp, ctypes.c_int]
     L.almpc_group_set_state_box.argtypes = [_hp, _dp, _dp]
     L.almpc_group_design_batched.argtypes = [_hp] + [_dp] * 6 + [ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_double]
@@ -170,6 +175,7 @@ def load():
     L.almpc_group_sqp_fnn_start.argtypes = [_hp, _dp, _dp]
     L.almpc_group_sqp_fnn_iterate.argtypes = [_hp, ctypes.c_int, ctypes.c_double, ctypes.POINTER(almpc_opts), _dp, _dp]
     L.almpc_group_sqp_fnn_skipped.argtypes = [_hp, _ip]
+    L.almpc_group_sqp_fnn_state_multipliers.argtypes = [_hp, _dp]
     L.almpc_group_sqp_fnn_solve.argtypes = [_hp, ctypes.c_int, ctypes.c_double, ctypes.POINTER(almpc_opts), _ip, _ip, _dp]
     L.almpc_group_x0_staging.argtypes = [_hp, ctypes.POINTER(_dp)]
     L.almpc_group_update_initialization_staged.argtypes = [_hp, ctypes.POINTER(_dp)]
@@ -179,6 +185,7 @@ def load():
                 "almpc_group_design_batched", "almpc_group_relin_fnn_setup", "almpc_group_relin_fnn_step", "almpc_group_relin_fnn_step_async",
                 "almpc_group_relin_fnn_advance", "almpc_group_advance_plant", "almpc_group_sqp_fnn_set_structured", "almpc_group_sqp_fnn_set_step_rule",
                 "almpc_group_sqp_fnn_setup", "almpc_group_relin_densenet_setup", "almpc_group_sqp_densenet_setup", "almpc_group_sqp_fnn_start", "almpc_group_sqp_fnn_iterate", "almpc_group_sqp_fnn_skipped", "almpc_group_sqp_fnn_solve", "almpc_group_sqp_fnn_set_hessian",
+                "almpc_group_sqp_fnn_set_row_multipliers", "almpc_group_sqp_fnn_state_multipliers",
                 "almpc_group_x0_staging", "almpc_group_update_initialization_staged", "almpc_group_get_results_async", "almpc_group_get_results_wait"):
         getattr(L, nm_).restype = ctypes.c_int
     L.almpc_set_start_from.argtypes = [_hp, _hp]
@@ -599,6 +606,18 @@ class Solver:
         """Hessian of the loop's QPs: "gauss_newton" (default) or "exact" (almpc_sqp_fnn_set_hessian); stays in force."""
         self._check(self.L.almpc_sqp_fnn_set_hessian(self.h, SQP_HESSIANS[mode]))
 
+    def sqp_fnn_set_row_multipliers(self, on):
+        """State rows (state box, terminal equality) in the loop's stopping test and exact Hessian: the finishes hand the row multipliers
+        of every iteration's QP out (almpc_sqp_fnn_set_row_multipliers; default off, stays in force)."""
+        self._check(self.L.almpc_sqp_fnn_set_row_multipliers(self.h, 1 if on else 0))
+
+    def sqp_fnn_state_multipliers(self):
+        """-> (batch, n, N): multiplier of the row of x_{k+1}[i] at [:, i, k] in each instance's last solved QP (> 0 upper bound, < 0 lower
+        bound, free on a terminal-equality row, 0 outside the working set); zeros with the switch off or without state rows."""
+        mu = np.zeros((self.batch, self.N, self.n))
+        self._check(self.L.almpc_sqp_fnn_state_multipliers(self.h, _ptr(mu)))
+        return np.ascontiguousarray(mu.transpose(0, 2, 1))
+
     def sqp_fnn_skipped(self):
         out = np.zeros(self.batch, dtype=np.int32)
         self._check(self.L.almpc_sqp_fnn_skipped(self.h, out.ctypes.data_as(_ip)))
@@ -934,6 +953,14 @@ class Group:
 
     def sqp_fnn_set_hessian(self, mode):
         self._check(self.L.almpc_group_sqp_fnn_set_hessian(self.g, SQP_HESSIANS[mode]))
+
+    def sqp_fnn_set_row_multipliers(self, on):
+        self._check(self.L.almpc_group_sqp_fnn_set_row_multipliers(self.g, 1 if on else 0))
+
+    def sqp_fnn_state_multipliers(self):
+        mu = np.zeros((self.batch, self.N, self.n))
+        self._check(self.L.almpc_group_sqp_fnn_state_multipliers(self.g, _ptr(mu)))
+        return np.ascontiguousarray(mu.transpose(0, 2, 1))
 
     def sqp_fnn_skipped(self):
         sk = np.zeros(self.batch, dtype=np.int32)

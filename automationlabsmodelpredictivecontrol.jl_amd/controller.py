@@ -322,7 +322,11 @@ def _design_blackbox_nonlinear(system, horizon, sample_time, references, weights
     mpc_sqp_hessian ("gauss_newton", default, or "exact": the exact Lagrangian Hessian in every QP of the loop),
     mpc_sqp_tolerance (None, default: a fixed mpc_sqp_iterations per calculate!; a number: solve every instance to that first-order
     residual in at most mpc_sqp_iterations full steps, almpc_sqp_fnn_solve -- an instance left at the iteration limit raises
-    ArithmeticError unless mpc_allow_unsolved; modeler.last_sqp_status / last_sqp_iters / last_sqp_kkt record the outcome)."""
+    ArithmeticError unless mpc_allow_unsolved; modeler.last_sqp_status / last_sqp_iters / last_sqp_kkt record the outcome).
+    With mpc_state_constraint or mpc_terminal_ingredient = "equality" (condensed QP route) the multipliers of those rows are switched on
+    (almpc_sqp_fnn_set_row_multipliers): they are part of the stopping test and of the exact Hessian's Lagrangian, so both
+    mpc_sqp_tolerance and mpc_sqp_hessian = "exact" work with constrained states; modeler.last_sqp_state_multipliers holds them
+    ((batch, n, N): the row of x[:, k+1] at [:, :, k]) after a tolerance solve."""
     D = _DEFAULT_PARAMETERS_MODEL_PREDICTIVE_CONTROL
     solver_name = kws.get("mpc_solver", D["mpc_solver"])
     if solver_name not in _IMPLEMENTATION_SOLVER_LIST:
@@ -358,6 +362,9 @@ def _design_blackbox_nonlinear(system, horizon, sample_time, references, weights
           xmin=system.X.low if state_box else None, xmax=system.X.high if state_box else None,
           terminal="equality" if terminal == "equality" else "none",
           qp_solver=kws.get("mpc_sqp_qp_solver", "condensed"))   # "structured": every QP through k_riccati
+    state_rows = (state_box or terminal == "equality") and kws.get("mpc_sqp_qp_solver", "condensed") == "condensed"
+    if state_rows:   # (before set_hessian: the exact mode takes state rows only with their multipliers)
+        solver.sqp_fnn_set_row_multipliers(True)
     hess = kws.get("mpc_sqp_hessian", "gauss_newton")
     if hess not in _capi.SQP_HESSIANS:
         solver.close()
@@ -371,8 +378,8 @@ def _design_blackbox_nonlinear(system, horizon, sample_time, references, weights
     mod.allow_unsolved = bool(kws.get("mpc_allow_unsolved", False))
     mod.sqp = dict(iterations=int(kws.get("mpc_sqp_iterations", 10)), step=float(kws.get("mpc_sqp_step", 1.0)),
                    warm_start=bool(kws.get("mpc_sqp_warm_start", True)), u_prev=None,
-                   step_rule=kws.get("mpc_sqp_step_rule", "merit"), tolerance=tol)
-    mod.last_sqp_status = mod.last_sqp_iters = mod.last_sqp_kkt = None
+                   step_rule=kws.get("mpc_sqp_step_rule", "merit"), tolerance=tol, state_rows=state_rows)
+    mod.last_sqp_status = mod.last_sqp_iters = mod.last_sqp_kkt = mod.last_sqp_state_multipliers = None
     tuning = ModelPredictiveControlTuning(mod, references, horizon, weights, TerminalIngredient(terminal, np.array(P)),
                                           float(sample_time), int(kws.get("mpc_max_time", D["mpc_max_time"])))
     shape = (lambda *s: s) if batch == 1 else (lambda *s: (batch, *s))
@@ -465,6 +472,8 @@ def calculate(C: ModelPredictiveControlController) -> None:
     if getattr(mod, "sqp", None) is not None and mod.sqp.get("tolerance") is not None:
         out = mod.solver.sqp_fnn_solve(mod.sqp["iterations"], mod.sqp["tolerance"], mod.opts, step_rule=mod.sqp["step_rule"])
         mod.last_sqp_status, mod.last_sqp_iters, mod.last_sqp_kkt = out["status"], out["iters"], out["kkt"]
+        if mod.sqp.get("state_rows"):
+            mod.last_sqp_state_multipliers = mod.solver.sqp_fnn_state_multipliers()
         if np.any(out["status"] != 0) and not getattr(mod, "allow_unsolved", False):   # as the status-1 rule below
             raise ArithmeticError(f"calculate!: {int((out['status'] != 0).sum())} instance(s) not solved to mpc_sqp_tolerance in "
                                   "mpc_sqp_iterations iterations (mpc_allow_unsolved = True returns the iterate; modeler.last_sqp_status says which)")

@@ -135,6 +135,10 @@ struct almpc_handle {
         // almpc_sqp_fnn_set_hessian: 0 Gauss-Newton, 1 exact Lagrangian Hessian (multipliers [batch][N][n], stage blocks [batch][N][(n+m)^2])
         int hessian = 0;
         double *lam = nullptr, *Wlag = nullptr;
+        // almpc_sqp_fnn_set_row_multipliers: the finishes hand out the state-row multipliers of every iteration's QP ([batch][N][n], zero
+        // until the first solved QP); the stopping test and the exact Hessian take them into the adjoint.  Allocated when the handle has state rows.
+        int row_mult = 0;
+        double* smu = nullptr;
     } sqp;
     // per-step re-linearisation of a black-box Fnn model on the device (almpc_relin_fnn_*, BASELINE configs[3])
     struct Relin {
@@ -327,7 +331,7 @@ void free_all(almpc_handle* h) {
                     h->bVs, h->bD, h->bRho, h->bH, h->bF, h->bPhi, h->bGk, h->bGam, h->bW, h->bWP, h->bP, h->bFlag, h->bQ, h->dOverflow, h->dOvfSinv, h->dVsPlain, h->dPlain, h->dS0Basis, h->wQ, h->wR, h->wS,
                     h->sqp.W_in, h->sqp.W_h, h->sqp.b_h, h->sqp.W_out, h->sqp.A, h->sqp.B, h->sqp.c, h->sqp.fval, h->sqp.ebar,
                     h->sqp.qadd, h->sqp.xref, h->sqp.uref, h->sqp.Q, h->sqp.R, h->sqp.S, h->sqp.bad, h->sqp.stats, h->sqp.mer, h->sqp.xback, h->sqp.uback, h->sqp.dxback, h->sqp.vback,
-                    h->sqp.sv, h->sqp.kkt, h->sqp.lam, h->sqp.Wlag};
+                    h->sqp.sv, h->sqp.kkt, h->sqp.lam, h->sqp.Wlag, h->sqp.smu};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->sqp.live_pin) (void)hipHostFree(h->sqp.live_pin);
@@ -539,7 +543,7 @@ bool sdual_shape_ok(int n, int m, int N, bool useS) {
 // Stage records of a SHARED model on the device (host Riccati, design time), state box / terminal equality / S of the design.
 // Rm: the reference's branch rule applied (zeros when R[1,1] == 0); Sm null: no input-rate term.
 hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int max_iter, bool single_launch = false, int first_tier = 0,
-                        SolveMode mode = {});
+                        SolveMode mode = {}, RowMultOut rmult = {});
 hipError_t sdual_build_ghat(almpc_handle* h);
 
 int sdual_setup_shared(almpc_handle* h, const hm::mat& Am, const hm::mat& Bm, const hm::mat& Qm, const hm::mat& Rm, const hm::mat* Sm,
@@ -824,7 +828,8 @@ hipError_t launch_sdual_t(almpc_handle* h, SdualParams sp, int tier0, int tier1)
 
 // k_sdual over the batch (filter 0), over the instances whose status is not 0 (filter 1: redo after the condensed path), start from
 // `guess` (inputs [batch][N][m]) when given
-hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int max_iter, bool single_launch, int first_tier, SolveMode mode) {
+hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int max_iter, bool single_launch, int first_tier, SolveMode mode,
+                        RowMultOut rmult) {
     if (!h->sd.ready) return hipErrorInvalidValue;
     if (h->sd.ghat_wanted && !h->sd.ghat_ready && !mode.build_ghat && !h->sd.per_instance && !h->sd.sqp) {   // first use on a condensed handle
         const hipError_t eb = sdual_build_ghat(h);
@@ -854,6 +859,7 @@ hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int ma
         sp.eqt = sd.has_eq ? q.xref + (size_t)h->N * h->n : nullptr; sp.eqt_stride = 0;
         sp.x0 = nullptr; sp.xref = nullptr; sp.xref_stride = 0;
         sp.flag = h->bFlag; sp.v_only = 1;
+        sp.rows = rmult;
     }
     sp.ovf = sd.ovf; sp.only_ovf = 0; sp.wsave = sd.wsave;
     sp.gbad = sd.per_instance ? sd.bad : nullptr;
@@ -2046,6 +2052,7 @@ enum class Guess { Admm, FromIterate, ShiftInputs };
 struct StepMode {
     Guess guess = Guess::Admm;
     bool fold_flag = false;        // (re-linearisation step) the finish turns a flagged design into ALMPC_NON_FINITE itself
+    RowMultOut rows;               // (SQP loop with almpc_sqp_fnn_set_row_multipliers) the state-row finish hands its multipliers out
 };
 
 // Timing events of a step (ALMPC_FLAG_TIMING): 0 start, 1 end of the ADMM phase, 2 end of the finish, 3 end.  Event 0 is recorded in
@@ -2369,6 +2376,7 @@ int step_state_rows(Step& s) {
         h->sd.start_ws_fresh = true;
     }
     if (h->s0_basis_ok && !h->batched && !h->ltv && h->fS_stride == 0) gp.s0_basis = h->dS0Basis;   // (shared model, shared references)
+    if (s.mode.rows.mu && sq) { gp.rows = s.mode.rows; gp.rows_map = h->dRowMap; }
     switch (h->np_pairs) {
         case 1: HIP_TRY(h, launch_polish_gen<1>(h, gp)); break;
         case 2: HIP_TRY(h, launch_polish_gen<2>(h, gp)); break;
@@ -2970,9 +2978,9 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
         if (rc_ != ALMPC_OK) return rc_;
     }
     almpc_handle::Sqp& q = h->sqp;
-    const int keep_rule = q.step_rule, keep_structured = q.structured_qp, keep_hessian = q.hessian;
+    const int keep_rule = q.step_rule, keep_structured = q.structured_qp, keep_hessian = q.hessian, keep_rows = q.row_mult;
     void* old[] = {q.W_in, q.W_h, q.b_h, q.W_out, q.A, q.B, q.c, q.fval, q.ebar, q.qadd, q.xref, q.uref, q.Q, q.R, q.S, q.bad, q.stats, q.mer, q.xback, q.uback, q.dxback, q.vback,
-                   q.sv, q.kkt, q.lam, q.Wlag, h->dXref, h->dUref, h->dFS, h->dV0S};
+                   q.sv, q.kkt, q.lam, q.Wlag, q.smu, h->dXref, h->dUref, h->dFS, h->dV0S};
     for (void* p_ : old)
         if (p_) (void)hipFree(p_);
     if (q.live_pin) (void)hipHostFree(q.live_pin);
@@ -2980,6 +2988,7 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
     q.step_rule = keep_rule;
     q.structured_qp = keep_structured;
     q.hessian = keep_hessian;
+    q.row_mult = keep_rows;
     h->dXref = h->dUref = h->dFS = h->dV0S = nullptr;
     h->ref_cap[0] = h->ref_cap[1] = h->ref_cap[2] = 0;
     auto up = [&](double** d, const double* src, size_t cnt) -> hipError_t {
@@ -3091,6 +3100,16 @@ int almpc_sqp_densenet_setup(almpc_handle* h, int H, int L, int activation, cons
                          sigma);
 }
 
+// The row multipliers' buffer, once the switch is on and the handle has state rows (zero: no QP solved yet)
+static int sqp_rows_buffer(almpc_handle* h) {
+    almpc_handle::Sqp& q = h->sqp;
+    if (!q.row_mult || h->mc == 0 || q.smu) return ALMPC_OK;
+    const size_t cnt = (size_t)h->batch * h->N * h->n;
+    HIP_TRY(h, dalloc(&q.smu, cnt));
+    HIP_TRY(h, hipMemset(q.smu, 0, cnt * sizeof(double)));
+    return ALMPC_OK;
+}
+
 int almpc_sqp_fnn_start(almpc_handle* h, const double* x0, const double* u_guess) {
     if (!h || !x0) return h ? fail(h, ALMPC_ERR_INVALID, "sqp_fnn_start: null x0") : ALMPC_ERR_INVALID;
     almpc_handle::Sqp& q = h->sqp;
@@ -3125,6 +3144,8 @@ int almpc_sqp_fnn_start(almpc_handle* h, const double* x0, const double* u_guess
     hipLaunchKernelGGL(roll, dim3((unsigned)b), dim3(256), l, st, rp);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemsetAsync(q.bad, 0, b * sizeof(int), st));
+    { const int rc_ = sqp_rows_buffer(h); if (rc_ != ALMPC_OK) return rc_; }
+    if (q.smu) HIP_TRY(h, hipMemsetAsync(q.smu, 0, b * N * (size_t)n * sizeof(double), st));   // (no QP solved yet)
     {
         std::vector<double> d0(4 * b, 0.0);
         for (size_t i = 0; i < b; ++i) { d0[4 * i] = 1.0; d0[4 * i + 1] = std::numeric_limits<double>::infinity(); }
@@ -3149,12 +3170,16 @@ struct SqpSolveCtl {
 static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_opts* opts, double* step_inf, double* defect_inf,
                     const SqpSolveCtl* sv);
 
-// what the exact-Hessian mode covers: the condensed route with an input box only, smooth activations, nz <= 128, the per-wave LDS
-// scratch of k_fnn_lag_hessian within 64 KB for four waves
+// what the exact-Hessian mode covers: the condensed route, smooth activations, nz <= 128, the per-wave LDS scratch of k_fnn_lag_hessian
+// within 64 KB for four waves; state rows only with their multipliers handed out (almpc_sqp_fnn_set_row_multipliers) and the stage-wise
+// solvers behind the loop (an iteration whose shifted exact Hessian is indefinite takes the Gauss-Newton QP through k_sgains + k_sdual)
 static int sqp_exact_check(almpc_handle* h) {
     const almpc_handle::Sqp& q = h->sqp;
     if (q.structured_qp || h->structured) return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian: the condensed QP route only");
-    if (h->mc > 0) return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian: no state rows (their multipliers would enter the adjoint)");
+    if (h->mc > 0 && !q.row_mult) return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian: no state rows (their multipliers would enter the adjoint)");
+    if (h->mc > 0 && !(h->fallback && h->sd.ready && h->sd.sqp))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian with state rows: needs the stage-wise fallback (k_sgains + k_sdual) for the "
+                                              "iterations whose exact Hessian is indefinite; it is off or the shape is outside it");
     if (q.act == 1) return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian: relu makes the NLP non-smooth");
     if (h->nz > 128) return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian: nz <= 128");
     if (4 * fnn_hess_wave_doubles(h->n, h->m, q.H, q.L, q.net) * sizeof(double) > 64 * 1024)
@@ -3274,6 +3299,16 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
         if (e == hipSuccess) e = hipEventRecord(sv->ev[it & 3], st);
         return e;
     };
+    // state rows with almpc_sqp_fnn_set_row_multipliers: whichever finish decides an instance's QP hands its row multipliers out, and the
+    // adjoint walk of k_sqp_kkt (the stopping test, the multipliers of the exact Hessian) takes them in
+    RowMultOut rows;
+    if (q.row_mult && h->mc > 0) {
+        if (q.structured_qp)
+            return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp row multipliers: the condensed QP route only (the stage-wise route of "
+                                                  "almpc_sqp_fnn_set_structured / ALMPC_FLAG_STRUCTURED does not hand them out)");
+        { const int rc_ = sqp_rows_buffer(h); if (rc_ != ALMPC_OK) return rc_; }
+        rows.mu = q.smu; rows.done = sv ? sv->done : nullptr; rows.mer = q.step_rule ? q.mer : nullptr;
+    }
     bool all_done = false;
     DesignLtvParams lp;
     lp.n = n; lp.m = m; lp.N = N; lp.nz = nz; lp.useR = q.useR; lp.useS = q.useS;
@@ -3301,6 +3336,10 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
         xp.umin = h->dUmin; xp.umax = h->dUmax; xp.done = sv ? sv->done : nullptr; xp.H = h->bH; xp.q = h->bQ;
         hess_lds = 4 * fnn_hess_wave_doubles(n, m, q.H, q.L, q.net) * sizeof(double);
         exact_lds = sqp_exact_lds_doubles(n, m, nz) * sizeof(double);
+    }
+    if (rows.mu) {
+        kp.mu = q.smu; kp.term_eq = h->terminal_eq ? 1 : 0;
+        if (h->has_box) { kp.xmin = h->dXmin; kp.xmax = h->dXmax; }
     }
     // register-tile design kernel: scaling, scaled gradient and the flag reset ride along as its tail (three launches less per iteration)
     // (not in exact mode: k_sqp_exact_qp changes H and q after the design, the factor then scales them)
@@ -3350,6 +3389,7 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
         }
         StepMode mode;
         mode.guess = (q.guess_from_iterate && q.since_start > 0) ? Guess::FromIterate : Guess::Admm;
+        mode.rows = rows;
         // (with the scaling in the design kernel's tail fS_i exists before the inverse: v0S_i = -G_i fS_i comes out of the inverse's launch)
         const bool v0_in_inverse = ltv_scales && design_inverse_makes_v(nz);
         launch_batched_factor(h, ds, h->rho, h->sigma, st, mode.guess != Guess::Admm, ltv_scales, false, v0_in_inverse ? h->dFS : nullptr, h->dV0S);
@@ -3367,7 +3407,7 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
             // (an iterate holds half of its inputs on bounds; a saturated unstable linearisation is where the dual method has no
             // certificate) --, ONE idle launch per iteration instead of three; with state rows / S: k_sgains + k_sdual
             const bool primal_only = h->mc == 0 && !q.useS && h->rKst && !getenv("ALMPC_SQP_REDO_DUAL_FIRST");
-            if (h->sd.ready && !primal_only) { HIP_TRY(h, launch_sgains(h, 2)); HIP_TRY(h, launch_sdual(h, 2, nullptr, 0, true)); }
+            if (h->sd.ready && !primal_only) { HIP_TRY(h, launch_sgains(h, 2)); HIP_TRY(h, launch_sdual(h, 2, nullptr, 0, true, 0, {}, rows)); }
             if (h->mc == 0 && !q.useS && h->rKst) HIP_TRY(h, launch_riccati(h, 2, nullptr, 0));
         }
         q.since_start += 1;
@@ -3413,6 +3453,26 @@ int almpc_sqp_fnn_set_step_rule(almpc_handle* h, int rule) {
     if (!h) return ALMPC_ERR_INVALID;
     if (rule != 0 && rule != 1) return fail(h, ALMPC_ERR_INVALID, "sqp_fnn_set_step_rule: 0 (fixed step) or 1 (merit-function safeguard)");
     h->sqp.step_rule = rule;
+    return ALMPC_OK;
+}
+
+int almpc_sqp_fnn_set_row_multipliers(almpc_handle* h, int on) {
+    if (!h) return ALMPC_ERR_INVALID;
+    h->sqp.row_mult = on ? 1 : 0;
+    return ALMPC_OK;
+}
+
+int almpc_sqp_fnn_state_multipliers(almpc_handle* h, double* mu) {
+    if (!h || !mu) return ALMPC_ERR_INVALID;
+    if (!h->sqp.ready) return fail(h, ALMPC_ERR_NOT_DESIGNED, "sqp_fnn_state_multipliers before sqp_fnn_setup");
+    const size_t cnt = (size_t)h->batch * h->N * h->n;
+    if (!h->sqp.smu) {   // switch off, no state rows, or nothing started yet: no row has a multiplier
+        std::fill(mu, mu + cnt, 0.0);
+        return ALMPC_OK;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(mu, h->sqp.smu, cnt * sizeof(double), hipMemcpyDeviceToHost));
     return ALMPC_OK;
 }
 

@@ -507,6 +507,19 @@ int almpc_group_sqp_fnn_solve(almpc_group* g, int max_iters, double tol, const a
                                    kkt ? kkt + f : nullptr);
     });
 }
+int almpc_group_sqp_fnn_set_row_multipliers(almpc_group* g, int on) {
+    if (!g) return ALMPC_ERR_INVALID;
+    for (size_t i = 0; i < g->hs.size(); ++i) { const int rc = almpc_sqp_fnn_set_row_multipliers(g->hs[i], on); if (rc != ALMPC_OK) return gfail(g, rc, (int)i); }
+    return ALMPC_OK;
+}
+int almpc_group_sqp_fnn_state_multipliers(almpc_group* g, double* mu) {
+    if (!g || !mu) return ALMPC_ERR_INVALID;
+    for (size_t i = 0; i < g->hs.size(); ++i) {
+        const int rc = almpc_sqp_fnn_state_multipliers(g->hs[i], mu + (size_t)g->first[i] * g->N * g->n);
+        if (rc != ALMPC_OK) return gfail(g, rc, (int)i);
+    }
+    return ALMPC_OK;
+}
 int almpc_group_sqp_fnn_skipped(almpc_group* g, int32_t* skipped) {
     if (!g || !skipped) return ALMPC_ERR_INVALID;
     for (size_t i = 0; i < g->hs.size(); ++i) { const int rc = almpc_sqp_fnn_skipped(g->hs[i], skipped + g->first[i]); if (rc != ALMPC_OK) return gfail(g, rc, (int)i); }

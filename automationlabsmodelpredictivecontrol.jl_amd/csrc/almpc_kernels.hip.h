@@ -663,6 +663,20 @@ __device__ __forceinline__ void wave_fence_lds() {  // order this wave's LDS wri
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// State-row multipliers of the QP a state-row finish (polish_gen_body, k_sdual) has just decided, handed out for the SQP loop's stopping
+// test and exact Hessian (almpc_sqp_fnn_set_row_multipliers).  Signed as oracle/mpc_oracle.py::solve_qp_dual_active_set has them: > 0 on
+// an upper bound, < 0 on a lower bound, free on a terminal-equality row, 0 outside the working set; in the units of the gradient of J
+// (unscaled row of dx).  The finish zeroes the instance's slice and scatters its working set's multipliers when it SOLVED the QP and the
+// iteration counts for the instance; otherwise the slice keeps the multipliers of the instance's last solved QP.
+struct RowMultOut {
+    double* mu = nullptr;          // [batch][N][n], entry (k, i): the row of x_{k+1}[i]; null: no export (every path but the switch)
+    const int* done = nullptr;     // [batch] or null: != 0 frozen by almpc_sqp_fnn_solve
+    const double* mer = nullptr;   // [batch][4] or null: step rule 1, [2] != 0: the trial point was rejected, this QP is void
+};
+__device__ __forceinline__ bool row_mult_live(const RowMultOut& r, int inst) {
+    return r.mu != nullptr && !(r.done && r.done[inst] != 0) && !(r.mer && r.mer[4 * (size_t)inst + 2] != 0.0);
+}
+
 // One wave per instance.  nz <= 128: lane l holds rows l and l+64 of the instance vectors ("row-distributed").
 // "Position-distributed" quantities (row index, bound, side, multiplier lam, bordering vectors) live in registers,
 // position i of the working set W on lane i.  Sinv = (G_WW)^-1 is stored column-major (S[c*LD + r]: a sweep over

@@ -83,6 +83,10 @@ struct PolishGenParams {
     int max_iter;
     int roll_g, roll_cpl;
     RolloutParams roll;
+    // the SQP loop's row multipliers (RowMultOut, csrc/almpc_kernels.hip.h; rows.mu null: nothing of it runs) and the table that finds a
+    // slot's row: [N*n], state (stage k+2, i) at k*n + i -> state-row index 0..mc-1, or -1 (GhatInstParams::rowmap)
+    RowMultOut rows;
+    const int* rows_map = nullptr;
 };
 
 // one instance per workgroup of the first launch: a CU's eight slots are refilled instance by instance (with four per workgroup a slot
@@ -891,6 +895,25 @@ __device__ __forceinline__ void polish_gen_body(const PolishGenParams& p, double
         }
     }
     wave_fence_lds();
+    if (p.rows.mu && fin == 0 && st_in != 2 && row_mult_live(p.rows, inst)) {   // (wave-uniform)
+        // lam of the working set's state rows, by row through LDS (rowbuf is free now), then the instance's whole slice in one pass of
+        // plain stores: zero where the row is outside the working set.  lam is the multiplier of the unscaled row of dx (the scaling is
+        // in the variables only).
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            d2 v; v[0] = 0.0; v[1] = 0.0;
+            *reinterpret_cast<d2*>(rowbuf + 2 * lane + 128 * q) = v;
+        }
+        wave_fence_lds();
+        if (lowhalf && pos < k && wrow >= nz) rowbuf[wrow] = lam;
+        wave_fence_lds();
+        double* mo = p.rows.mu + (size_t)inst * N * n;
+        for (int t = lane; t < N * n; t += 64) {
+            const int r = p.rows_map[t];
+            mo[t] = r >= 0 ? rowbuf[nz + r] : 0.0;
+        }
+        wave_fence_lds();
+    }
     {
         const int r0 = 2 * lane, r1 = 2 * lane + 1;
         const int rc = (r0 < nzs) ? r0 : 0;

@@ -84,6 +84,8 @@ struct SdualParams {
     // count carries SDUAL_START_BUILT lists the COMPLETE start (terminal-equality rows first, dependent rows left out) and its inverse is
     // here (packed lower triangle): the working set is installed as it stands, no response and no bordering per row
     const double* start_inv = nullptr;
+    // the SQP loop's row multipliers (RowMultOut, csrc/almpc_kernels.hip.h; rows.mu null: nothing of it runs)
+    RowMultOut rows;
 };
 constexpr int SDUAL_START_BUILT = 1 << 16;
 
@@ -1105,11 +1107,34 @@ __global__ __launch_bounds__(64 * SDUAL_WAVES, 2) void k_sdual(SdualParams p) {
         const int st_out = bad ? 2 : status;
         if (p.ovf && lane == 0) p.ovf[inst] = (overflow && !bad) ? 1 + (nW < SDUAL_WSAVE ? nW : SDUAL_WSAVE) : 0;
         if (p.ovf_gate && overflow && !bad && lane == 0) *p.ovf_gate = p.ovf_gate_val;
+        const bool hand_out = p.rows.mu && st_out == 0 && row_mult_live(p.rows, inst);   // (wave-uniform)
+        if (hand_out) {
+            // lam of the working set by coordinate through LDS (w is free now), then the state coordinates of stages 1..N as the instance's
+            // whole slice: zero where the row is outside the working set.  The source of a row is 0.5 lam on a cost with sources 2 w't:
+            // lam itself is the multiplier in the units of the gradient of J.
+            for (int t = lane; t < TP; t += 64) w[t] = 0.0;
+            sd_fence();
+#pragma unroll
+            for (int sl = 0; sl < PPL; ++sl)
+                if (sl * 64 + lane < nW) w[Wrow[sl]] = lam[sl];
+            sd_fence();
+            double* mo = p.rows.mu + (size_t)inst * N * n;
+            for (int t = lane; t < N * n; t += 64) {
+                const int k = t / n, i = t - k * n;
+                mo[t] = w[(k + 1) * SP + i];
+            }
+        }
         for (int t = lane; t < N * m; t += 64) {
             const int k = t / m, a = t - k * m;
             const double ur = urg[t];
             const double ua = s[k * SP + NT + a];   // absolute
-            const double uu = (bad || st_out == 3) ? ua : fmin(fmax(ua, p.umin[a]), p.umax[a]);
+            double uu = (bad || st_out == 3) ? ua : fmin(fmax(ua, p.umin[a]), p.umax[a]);
+            if (hand_out) {   // an input row of the working set sits ON its bound, exactly (as k_polish_gen leaves it): the row values come
+                              // out of a sweep, a rounding error off -- and the exact Hessian's inertia rule tests u == bound
+                const double lm = w[k * SP + NT + a];
+                if (lm > 0.0) uu = p.umax[a];
+                else if (lm < 0.0) uu = p.umin[a];
+            }
             if (!p.v_only) p.u[(size_t)inst * N * m + t] = uu;
             p.eu[(size_t)inst * N * m + t] = uu - ur;
         }

@@ -153,6 +153,11 @@ inline __global__ __launch_bounds__(256) void k_sqp_step(SqpParams p) {
 // live count goes down by one.  The adjoint recursion is a dependent chain of N stages walked backwards as k_sqp_step walks forwards:
 // [A_k | B_k | 2 Q e_k] of `chunk` stages staged in LDS by the whole workgroup, then wave 0 alone, lane j < n owning lam_j and the
 // previous lam read from the lanes (v_readlane), no barrier per stage.
+// With state rows and their multipliers mu handed out by the finishes (RowMultOut; `mu` below not null):
+//     lam_N = 2 P e_N + mu_N,   lam_k = 2 Q e_k + A_k' lam_{k+1} + mu_k      (mu_k rides in the 2 Q e_k slot of the staged chunk)
+// and the residual is the maximum of the projected residual above with that adjoint, the complementarity |x - bound| over the box rows
+// with mu != 0 (side by sign), the primal violation of the box, and |x_{N+1} - x_ref| under the terminal equality (whose rows replace
+// the box rows of that stage).  tests/sqp_rows_ref.py restates it.
 struct SqpKktParams {
     int n, m, N, nz, useS;
     const double* xref; const double* uref;   // [(N+1)][n], [N][m]
@@ -166,6 +171,9 @@ struct SqpKktParams {
     int* done; int* iters; double* kkt;       // [batch]; done null: no test, the multipliers only (exact Hessian in iterate)
     int* live;                                // instances not yet converged
     double* lam = nullptr;                    // [batch][N][n] or null: lam_{k+1}, the multiplier of stage k's dynamics
+    const double* mu = nullptr;               // [batch][N][n] or null: multipliers of the state rows, entry (k, i) the row of x_{k+1}[i]
+    const double* xmin = nullptr; const double* xmax = nullptr;   // [n] state box or null (read with mu only)
+    int term_eq = 0;                          // the rows of stage N + 1 are the terminal equality
 };
 
 inline __global__ __launch_bounds__(256) void k_sqp_kkt(SqpKktParams p) {
@@ -183,6 +191,7 @@ inline __global__ __launch_bounds__(256) void k_sqp_kkt(SqpKktParams p) {
     const double* Ag = p.A + i * N * (size_t)nn;
     const double* Bg = p.B + i * N * (size_t)nm;
     const double* Pm = p.P + i * p.sP;
+    const double* mug = p.mu ? p.mu + i * (size_t)N * n : nullptr;
     double dmax = 0.0;
     for (int t = tid; t < N * n; t += 256) {
         const double d = fabs(fv[t] - xb[n + t]);
@@ -196,6 +205,7 @@ inline __global__ __launch_bounds__(256) void k_sqp_kkt(SqpKktParams p) {
     if (tid < 64) {
         for (int c2 = 0; c2 < n; ++c2) lam += Pm[(size_t)c2 * n + lj] * (xb[(size_t)N * n + c2] - p.xref[(size_t)N * n + c2]);
         lam *= 2.0;
+        if (mug) lam += mug[(size_t)(N - 1) * n + lj];
     }
     int top = N;   // stages [0, top) not walked yet
     while (top > 0) {
@@ -212,6 +222,7 @@ inline __global__ __launch_bounds__(256) void k_sqp_kkt(SqpKktParams p) {
                 if (k > 0)
                     for (int c2 = 0; c2 < n; ++c2) s += p.Q[(size_t)c2 * n + r] * (xb[(size_t)k * n + c2] - p.xref[(size_t)k * n + c2]);
                 v = 2.0 * s;
+                if (mug && k > 0) v += mug[(size_t)(k - 1) * n + r];
             }
             stage[t] = v;
         }
@@ -254,6 +265,21 @@ inline __global__ __launch_bounds__(256) void k_sqp_kkt(SqpKktParams p) {
         const double proj = fmin(fmax(u - sc * g, p.umin[a]), p.umax[a]);
         const double d = fabs(u - proj);
         r = fmax(r, d == d ? d : 1.79e308);
+    }
+    if (mug) {   // state rows: complementarity and primal feasibility at the iterate
+        for (int t = tid; t < N * n; t += 256) {
+            const int c2 = t % n;
+            const double x = xb[n + t], mv = mug[t];
+            double d = 0.0;
+            if (p.term_eq && t >= (N - 1) * n) d = fabs(x - p.xref[n + t]);
+            else if (p.xmin) {
+                const double lo = p.xmin[c2], hi = p.xmax[c2];
+                d = fmax(fmax(x - hi, lo - x), 0.0);
+                if (mv > 0.0) d = fmax(d, fabs(x - hi));
+                else if (mv < 0.0) d = fmax(d, fabs(x - lo));
+            }
+            r = fmax(r, d == d ? d : 1.79e308);
+        }
     }
     r = wave_max(r);
     if ((tid & 63) == 0) red[4 + (tid >> 6)] = r;

@@ -205,7 +205,8 @@ int almpc_set_start_from(almpc_handle* h, almpc_handle* src);
  * almpc_set_terminal_equality these designs then build one constraint-space matrix per instance (k_ghat_inst) and the step's exact
  * finish is the dual active-set kernel of the shared-model state rows with per-instance operands.  Time-varying designs and the SQP
  * loop: the box is on xbar + dx, the terminal equality reads xbar + dx = x_ref at stage N+1; an SQP iteration whose QP is infeasible
- * is skipped for that instance (almpc_sqp_fnn_skipped) -- there is no elastic mode.  Structured handles (ALMPC_FLAG_STRUCTURED) take the
+ * is skipped for that instance (almpc_sqp_fnn_skipped) -- there is no elastic mode.  The SQP loop's stopping test and exact Hessian
+ * need the multipliers of these rows: almpc_sqp_fnn_set_row_multipliers below.  Structured handles (ALMPC_FLAG_STRUCTURED) take the
  * same calls: there the rows are coordinates of the stage-wise trajectory (k_sdual), no constraint-space matrix is built.
  */
 int almpc_set_state_box(almpc_handle* h, const double* xmin, const double* xmax);
@@ -304,20 +305,39 @@ int almpc_sqp_fnn_skipped(almpc_handle* h, int32_t* skipped /* [batch], 1 = some
  *     kkt     the residual of its last test
  * Skipped iterations are reported in `status`, not as ALMPC_ERR_NUMERIC.  ALMPC_ERR_UNSUPPORTED when R[0,0] == 0 (the residual
  * divides by 2 R_aa) or m > 64.  almpc_get_results afterwards returns the iterate as after iterate.
+ * State rows (almpc_set_state_box, almpc_set_terminal_equality): the test above knows nothing of their multipliers and never passes
+ * at a solution with an active row -- switch almpc_sqp_fnn_set_row_multipliers on.  Then G is the gradient of the Lagrangian
+ * (lam_N = 2 P e_N + mu_N, lam_k = 2 Q e_k + A_k' lam_{k+1} + mu_k) and the residual is the maximum of the projected residual above,
+ * the complementarity |x - bound| over the box rows with mu != 0, the violation of the box, and |x_{N+1} - x_ref| under the terminal
+ * equality.  An x0 outside the box is status 3 at the first iteration.
  */
 /*
  * Hessian of every QP of the loop (iterate and solve): ALMPC_SQP_HESSIAN_GAUSS_NEWTON (default) or ALMPC_SQP_HESSIAN_EXACT, the
  * exact Lagrangian Hessian: the stage blocks W_k = d^2/dz^2 (lam_{k+1}' f(z_k)) with the multipliers of the adjoint walk at the
  * iterate, condensed into H and q, plus the Gershgorin bound of the result on the diagonal of every input on a bound at the iterate.
  * An instance whose shifted Hessian is still not positive definite takes that iteration with the Gauss-Newton QP (structured
- * fallback; without it the iteration is skipped).  ALMPC_ERR_UNSUPPORTED for EXACT with state rows, the structured QP route, relu,
- * nz > 128, or a network whose per-wave scratch (n + m + 3 H + H (n + m) + S H (n + m + 2) doubles, S = L activation sites, 2 L for
+ * fallback; without it the iteration is skipped).  State rows are linear and add no curvature, but their multipliers are part of lam:
+ * EXACT with state rows needs almpc_sqp_fnn_set_row_multipliers switched on and the stage-wise fallback available (the Gauss-Newton QP
+ * of an indefinite iteration then goes through k_sgains + k_sdual).  ALMPC_ERR_UNSUPPORTED for EXACT with state rows otherwise, the
+ * structured QP route, relu, nz > 128, or a network whose per-wave scratch (n + m + 3 H + H (n + m) + S H (n + m + 2) doubles, S = L activation sites, 2 L for
  * a PolyNet) exceeds 16 KB (checked here once set up, else at the next iterate / solve).
  */
 enum { ALMPC_SQP_HESSIAN_GAUSS_NEWTON = 0, ALMPC_SQP_HESSIAN_EXACT = 1 };
 int almpc_sqp_fnn_set_hessian(almpc_handle* h, int mode);
 int almpc_sqp_fnn_solve(almpc_handle* h, int max_iters, double tol, const almpc_opts* opts, int32_t* status, int32_t* iters,
                         double* kkt);
+/*
+ * Multipliers of the state rows.  With the switch on (default off; before or after setup, stays in force) whichever exact finish decides
+ * an instance's QP of an iteration -- k_polish_gen / k_polish_gen64, or k_sdual behind them -- writes the multipliers of its state rows
+ * out: mu [batch][N][n], entry (k, i) the row of x_{k+1}[i], k = 0..N-1; > 0 on an upper bound, < 0 on a lower bound, free on a
+ * terminal-equality row, 0 outside the working set; in the units of the gradient of the cost (multiplier of the unscaled row).  An
+ * instance whose iteration was void (step rule 1), skipped or frozen keeps those of its last solved QP; zero before the first.
+ * almpc_sqp_fnn_solve and the exact Hessian then work with state rows (see there).  On a handle without state rows the switch
+ * changes nothing and the read-back gives zeros; with it off every launch is what it was.  The condensed QP route only: with state rows on
+ * the stage-wise route (almpc_sqp_fnn_set_structured, ALMPC_FLAG_STRUCTURED) iterate and solve return ALMPC_ERR_UNSUPPORTED while the switch is on.
+ */
+int almpc_sqp_fnn_set_row_multipliers(almpc_handle* h, int on);
+int almpc_sqp_fnn_state_multipliers(almpc_handle* h, double* mu /* [batch][N][n], after iterate / solve */);
 /* Step rule of almpc_sqp_fnn_iterate.  0 (default): every instance takes steps of length `step_scale` (full Gauss-Newton steps
  * are not globally convergent: they can end in a cycle when the tracking residual is large).  1: safeguarded by the l1 merit
  * function phi = J + mu |f(x,u) - x+|_1 (mu = 2 max(|P|, |Q|)), tested a posteriori with the network outputs the next
@@ -523,6 +543,8 @@ int almpc_group_sqp_fnn_iterate(almpc_group* g, int iters, double step_scale, co
                                 double* defect_inf);
 int almpc_group_sqp_fnn_skipped(almpc_group* g, int32_t* skipped);
 int almpc_group_sqp_fnn_set_hessian(almpc_group* g, int mode);
+int almpc_group_sqp_fnn_set_row_multipliers(almpc_group* g, int on);
+int almpc_group_sqp_fnn_state_multipliers(almpc_group* g, double* mu /* [batch][N][n] */);
 /* almpc_sqp_fnn_solve on every device at the same time; status / iters / kkt [batch] (nullable) */
 int almpc_group_sqp_fnn_solve(almpc_group* g, int max_iters, double tol, const almpc_opts* opts, int32_t* status, int32_t* iters,
                               double* kkt);

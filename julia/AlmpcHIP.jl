@@ -8,7 +8,7 @@
 # solver tag "hip" next to osqp/scip/ipopt/auto (src/sub/solver_selection.jl:9-14).
 module AlmpcHIP
 
-export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_state_rows!, design_batched!, design_sqp_fnn!, sqp_start!, sqp_iterate!, sqp_solve!, set_sqp_hessian!,
+export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_state_rows!, design_batched!, design_sqp_fnn!, sqp_start!, sqp_iterate!, sqp_solve!, set_sqp_hessian!, set_sqp_row_multipliers!, state_multipliers,
        design_relin_fnn!, relin_step!, relin_advance!, update_initialization!, calculate!, read_results!,
        _model_predictive_control_computation, comm_unique_id, comm_init!, comm_summary, comm_allgather_first_input,
        calculate_async!, synchronize!, relin_step_async!, advance_plant!, start_from!, update_initialization_device!, device_results, set_step_fusion!,
@@ -18,7 +18,7 @@ export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_s
        HipGroup, group_design_hip, group_handle, group_shard, group_update_initialization!, group_calculate!, group_calculate_async!,
        group_synchronize!, group_read_results!, group_set_state_rows!, group_set_rho_profile!, group_set_structured_fallback!,
        group_design_batched!, group_design_relin_fnn!, group_relin_step!, group_relin_advance!, group_advance_plant!, group_design_sqp_fnn!,
-       group_sqp_start!, group_sqp_iterate!, group_sqp_solve!, group_set_sqp_hessian!, group_sqp_skipped, group_x0_staging, group_update_initialization_staged!, group_results_async,
+       group_sqp_start!, group_sqp_iterate!, group_sqp_solve!, group_set_sqp_hessian!, group_set_sqp_row_multipliers!, group_state_multipliers, group_sqp_skipped, group_x0_staging, group_update_initialization_staged!, group_results_async,
        group_results_wait!
 
 const libalmpc = get(ENV, "ALMPC_LIB", "libalmpc.so")
@@ -210,6 +210,15 @@ has zero defects and a projected adjoint-gradient residual <= `tol`.  Per instan
 "Hessian of the SQP loop's QPs: `:gauss_newton` (default) or `:exact` (`almpc_sqp_fnn_set_hessian`)"
 set_sqp_hessian!(mod::HipModeler, mode::Symbol) =
     check(mod.handle, ccall((:almpc_sqp_fnn_set_hessian, libalmpc), Cint, (Ptr{Cvoid}, Cint), mod.handle, mode === :exact ? 1 : 0))
+"State rows in the SQP loop's stopping test and exact Hessian: the finishes hand the row multipliers of every QP out (`almpc_sqp_fnn_set_row_multipliers`, default off)"
+set_sqp_row_multipliers!(mod::HipModeler, on::Bool = true) =
+    check(mod.handle, ccall((:almpc_sqp_fnn_set_row_multipliers, libalmpc), Cint, (Ptr{Cvoid}, Cint), mod.handle, on ? 1 : 0))
+"Multipliers of the state rows in each instance's last solved QP, `Array{Float64,3}(n, N, batch)`: `[i, k, b]` belongs to the row of `x[i, k+1]`"
+function state_multipliers(mod::HipModeler)
+    mu = Array{Float64,3}(undef, mod.n, mod.N, mod.batch)
+    check(mod.handle, ccall((:almpc_sqp_fnn_state_multipliers, libalmpc), Cint, (Ptr{Cvoid}, Ptr{Float64}), mod.handle, mu))
+    return mu
+end
 function sqp_solve!(mod::HipModeler, max_iters::Integer, tol::Float64; merit_safeguard::Bool = true)
     check(mod.handle, ccall((:almpc_sqp_fnn_set_step_rule, libalmpc), Cint, (Ptr{Cvoid}, Cint), mod.handle, merit_safeguard ? 1 : 0))
     st, it, kk = Vector{Int32}(undef, mod.batch), Vector{Int32}(undef, mod.batch), Vector{Float64}(undef, mod.batch)
@@ -742,6 +751,13 @@ function group_sqp_iterate!(g::HipGroup, iters::Integer; step::Float64 = 1.0, me
 end
 group_set_sqp_hessian!(g::HipGroup, mode::Symbol) =
     gcheck(g.group, ccall((:almpc_group_sqp_fnn_set_hessian, libalmpc), Cint, (Ptr{Cvoid}, Cint), g.group, mode === :exact ? 1 : 0))
+group_set_sqp_row_multipliers!(g::HipGroup, on::Bool = true) =
+    gcheck(g.group, ccall((:almpc_group_sqp_fnn_set_row_multipliers, libalmpc), Cint, (Ptr{Cvoid}, Cint), g.group, on ? 1 : 0))
+function group_state_multipliers(g::HipGroup)
+    mu = Array{Float64,3}(undef, g.n, g.N, g.batch)
+    gcheck(g.group, ccall((:almpc_group_sqp_fnn_state_multipliers, libalmpc), Cint, (Ptr{Cvoid}, Ptr{Float64}), g.group, mu))
+    return mu
+end
 function group_sqp_solve!(g::HipGroup, max_iters::Integer, tol::Float64; merit_safeguard::Bool = true)
     gcheck(g.group, ccall((:almpc_group_sqp_fnn_set_step_rule, libalmpc), Cint, (Ptr{Cvoid}, Cint), g.group, merit_safeguard ? 1 : 0))
     st, it, kk = Vector{Int32}(undef, g.batch), Vector{Int32}(undef, g.batch), Vector{Float64}(undef, g.batch)
