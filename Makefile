@@ -15,6 +15,7 @@ ORACLE   := oracle/_build/libalmpc_oracle.so  # generic name; oracle/c_oracle.py
 TUS      := api tu_step tu_polish_gen tu_instance tu_design_a tu_design_b tu_sdual_a tu_sdual_b tu_sdual_c
 OBJS     := $(patsubst %,$(OBJDIR)/almpc_%.o,$(TUS))
 H_K      := $(CS)/almpc_kernels.hip.h
+H_D      := $(CS)/almpc_design.hip.h $(CS)/almpc_switches.h
 H_ALL    := $(wildcard $(CS)/*.h) $(wildcard $(CS)/instances/*.inc) include/almpc.h
 
 all: lib oracle
@@ -29,9 +30,9 @@ $(LIB): $(OBJS)
 $(OBJDIR)/almpc_api.o:           $(H_ALL)
 $(OBJDIR)/almpc_tu_step.o:       $(H_K) $(CS)/instances/step.inc
 $(OBJDIR)/almpc_tu_polish_gen.o: $(H_K) $(CS)/almpc_polish_gen.hip.h $(CS)/instances/polish_gen.inc
-$(OBJDIR)/almpc_tu_instance.o:   $(H_K) $(CS)/almpc_instance.hip.h $(CS)/almpc_design.hip.h $(CS)/almpc_fnn.hip.h $(CS)/instances/instance.inc
-$(OBJDIR)/almpc_tu_design_a.o:   $(H_K) $(CS)/almpc_instance.hip.h $(CS)/almpc_design.hip.h $(CS)/almpc_fnn.hip.h $(CS)/instances/design_a.inc
-$(OBJDIR)/almpc_tu_design_b.o:   $(H_K) $(CS)/almpc_design.hip.h $(CS)/almpc_riccati.hip.h $(CS)/almpc_fnn.hip.h $(CS)/instances/design_b.inc
+$(OBJDIR)/almpc_tu_instance.o:   $(H_K) $(CS)/almpc_instance.hip.h $(H_D) $(CS)/almpc_fnn.hip.h $(CS)/instances/instance.inc
+$(OBJDIR)/almpc_tu_design_a.o:   $(H_K) $(CS)/almpc_instance.hip.h $(H_D) $(CS)/almpc_fnn.hip.h $(CS)/instances/design_a.inc
+$(OBJDIR)/almpc_tu_design_b.o:   $(H_K) $(H_D) $(CS)/almpc_riccati.hip.h $(CS)/almpc_fnn.hip.h $(CS)/instances/design_b.inc
 $(OBJDIR)/almpc_tu_sdual_a.o:    $(H_K) $(CS)/almpc_riccati.hip.h $(CS)/almpc_sdual.hip.h $(CS)/instances/sdual_a.inc
 $(OBJDIR)/almpc_tu_sdual_b.o:    $(H_K) $(CS)/almpc_riccati.hip.h $(CS)/almpc_sdual.hip.h $(CS)/instances/sdual_b.inc
 $(OBJDIR)/almpc_tu_sdual_c.o:    $(H_K) $(CS)/almpc_riccati.hip.h $(CS)/almpc_sdual.hip.h $(CS)/instances/sdual_c.inc

@@ -14,6 +14,7 @@
 #include "almpc_riccati.hip.h"
 #include "almpc_sdual.hip.h"
 #include "almpc_host_math.h"
+#include "almpc_switches.h"
 #include "../../include/almpc.h"
 
 // The heavy kernel templates are compiled by their own translation units (almpc_tu_*.hip, one per kernel family, built in parallel);
@@ -76,8 +77,8 @@ struct almpc_handle {
     uint32_t* dYflags = nullptr;  // [batch][nrb] signs of the ADMM multipliers (steps run with ALMPC_OPT_NO_WARM_STATE)
     bool state_valid = true;      // xs / ys hold the ADMM state of the last step (a warm start may use them)
     int num_cus = 256;            // persistent-grid size of k_polish<true>
-    int polish_no_glds = 0;       // diagnostic: force the G-through-L2 build (ALMPC_POLISH_NO_GLDS=1)
-    int fuse_step = 1;            // one kernel per step when the shape allows (almpc_set_step_fusion / ALMPC_NO_FUSED_STEP=1)
+    Switches sw;                  // the ALMPC_* diagnostic switches as almpc_create found them (csrc/almpc_switches.h): fixed for the handle's life
+    int fuse_step = 1;            // one kernel per step when the shape allows (almpc_set_step_fusion; starts off with ALMPC_NO_FUSED_STEP=1)
     double* dSglobal = nullptr;  // polish scratch for working sets beyond 32 rows
     int32_t* dStartRows = nullptr;   // [batch][65] row list of a guessed working set whose inverse sits in dSglobal (k_guess_iterate_ws)
     // state rows (state box / terminal equality): constraint-space data for k_polish_gen
@@ -122,7 +123,6 @@ struct almpc_handle {
         double mu = 0.0;          // merit weight of the defects
         int step_rule = 0;        // 0 fixed step, 1 merit-function safeguard (almpc_sqp_fnn_set_step_rule)
         long since_start = 0;     // iterations since almpc_sqp_fnn_start: the first one gets its guess from ADMM, the others from the iterate
-        int guess_from_iterate = 1;  // diagnostic: ALMPC_SQP_ADMM_ALWAYS=1 keeps the ADMM phase in every iteration
         int structured_qp = 0;       // almpc_sqp_fnn_set_structured: every iteration's QP goes to k_riccati in its stage-wise form
                                      // (no condensed design at all: no Hessian build, no inverse, no m N <= 128 limit)
         unsigned long long* stats = nullptr;  // [iters][2]
@@ -235,7 +235,6 @@ struct almpc_handle {
         // (393 KB over the link at its START, tools/dbg_x0_home.py), the upload costs three HIP calls and a copy-engine latency per step:
         // measured 11.7 k (upload) against 12.8 k (in place) batch-steps/s on the pipelined first-move loop, 8.3 k against 10.4 k serial
         hipStream_t s_in = nullptr;
-        bool upload = false;
         double* dX0dev[IO_DEPTH] = {nullptr, nullptr};
         hipEvent_t ev_in[IO_DEPTH] = {nullptr, nullptr};
         // x0 ring: pinned host slots the kernels read in place (dX0 = the device's address of the slot); h->dX0 points at the latest
@@ -516,9 +515,9 @@ hipError_t launch_riccati(almpc_handle* h, int filter, const double* guess, int 
         if (e_ != hipSuccess) return e_;                                                                       \
         hipLaunchKernelGGL((k_riccati_t<NC_, MC_>), dim3(wgs), dim3(64 * waves), lds, h->stream, rp);          \
     } while (0)
-    if (h->n == 12 && h->m == 4 && !getenv("ALMPC_RICCATI_GENERIC")) RICCATI_LAUNCH(12, 4);
-    else if (h->n == 4 && h->m == 2 && !getenv("ALMPC_RICCATI_GENERIC")) RICCATI_LAUNCH(4, 2);
-    else if (h->n == 2 && h->m == 1 && !getenv("ALMPC_RICCATI_GENERIC")) RICCATI_LAUNCH(2, 1);
+    if (h->n == 12 && h->m == 4 && !h->sw.riccati_generic) RICCATI_LAUNCH(12, 4);
+    else if (h->n == 4 && h->m == 2 && !h->sw.riccati_generic) RICCATI_LAUNCH(4, 2);
+    else if (h->n == 2 && h->m == 1 && !h->sw.riccati_generic) RICCATI_LAUNCH(2, 1);
     else RICCATI_LAUNCH(0, 0);
 #undef RICCATI_LAUNCH
     return hipGetLastError();
@@ -589,7 +588,7 @@ int sdual_setup_shared(almpc_handle* h, const hm::mat& Am, const hm::mat& Bm, co
     // where k_sdual is only the redo of what a step leaves undecided, at the first redo -- most such handles (the headline path) never
     // leave an instance undecided and should not pay TP^2 doubles and one sweep per coordinate at every design
     sd.ghat_ready = false;
-    sd.ghat_wanted = !getenv("ALMPC_SDUAL_NO_GHAT");
+    sd.ghat_wanted = !h->sw.sdual_no_ghat;
     if (sd.ghat_wanted && (h->flags & ALMPC_FLAG_STRUCTURED)) {
         HIP_TRY(h, sdual_build_ghat(h));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -758,7 +757,7 @@ hipError_t launch_sdual_t(almpc_handle* h, SdualParams sp, int tier0, int tier1)
     // SD_WCAP2 rows; tier 2: SD_WCAP4 rows, two working-set positions per lane (mostly infeasible instances whose verdict needs that
     // many rows); tier 3: the same with Sinv in a global scratch, for shapes whose trajectories leave no room for it in LDS.
     // (tier0 = tier1 = 1: ONE launch with room for SD_WCAP2 rows -- the redo of the few instances a condensed step left unsolved)
-    if (tier1 > tier0 && sp.wsave && !sp.build_ghat && !getenv("ALMPC_SDUAL_NO_SINV_HANDOVER")) {   // tiers hand each other the inverse of their working set
+    if (tier1 > tier0 && sp.wsave && !sp.build_ghat && !h->sw.sdual_no_sinv_handover) {   // tiers hand each other the inverse of their working set
         if (!h->sd.sinv_save) {
             const hipError_t e_ = dalloc(&h->sd.sinv_save, (size_t)h->batch * sdual_sinv_doubles(SDUAL_SINV_SAVE));
             if (e_ != hipSuccess) return e_;
@@ -792,7 +791,7 @@ hipError_t launch_sdual_t(almpc_handle* h, SdualParams sp, int tier0, int tier1)
         hipError_t e;
         const size_t lds_gh = lds + (size_t)(NT + MC) * (sdual_rec_row(NT, MC) + 2) * sizeof(double);   // (+ the workgroup's copy of a stage-invariant record, rows padded)
         // cached responses: the build whose sweeps fetch their records stage by stage and whose column stream runs four times deeper (see k_sdual)
-        const bool gh = sp.ghat != nullptr && lds_gh <= 160 * 1024 && !getenv("ALMPC_SDUAL_NO_GH");
+        const bool gh = sp.ghat != nullptr && lds_gh <= 160 * 1024 && !h->sw.sdual_no_gh;
         if (tier < 2) {
             const void* kf = gh ? reinterpret_cast<const void*>(k_sdual<NT, MC, 1, false, true>) : reinterpret_cast<const void*>(k_sdual<NT, MC, 1, false, false>);
             e = ensure_dyn_lds(kf, gh ? lds_gh : lds);
@@ -880,7 +879,7 @@ hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int ma
     // state box of a shared model with shared references, every instance solved from scratch: the reachability screen first (one
     // table kernel per design / reference change, one small launch per solve) -- instances it certifies infeasible never reach a sweep
     if (sd.has_box && !mode.build_ghat && !sd.per_instance && !sd.sqp && filter == 0 && first_tier == 0 && sp.x0 && h->uref_stride == 0 &&
-        h->xref_stride == 0 && h->dA && h->dB && !getenv("ALMPC_SDUAL_NO_SCREEN")) {
+        h->xref_stride == 0 && h->dA && h->dB && !h->sw.sdual_no_screen) {
         almpc_handle::Sd& sdw = h->sd;
         const size_t n_ = (size_t)h->n, m_ = (size_t)h->m, N_ = (size_t)h->N;
         hipError_t e;
@@ -922,12 +921,12 @@ hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int ma
         // (round 5: the 64-row build first -- one working-set position per lane: its Sinv products, borderings and column streams are
         // cheaper per change than the 128-row build's -- and the 128-row build only for what outgrows it, which costs little since the
         // tiers hand over their inverse; ALMPC_SDUAL_REDO_128=1: the one 128-row launch of round 4)
-        tier0 = (fits128 && (getenv("ALMPC_SDUAL_REDO_128") || (mode.gated && !mode.predicted))) ? 2 : 1;   // (a gated redo that is not expected to have work: one launch)
+        tier0 = (fits128 && (h->sw.sdual_redo_128 || (mode.gated && !mode.predicted))) ? 2 : 1;   // (a gated redo that is not expected to have work: one launch)
         tier1 = fits128 ? 2 : 1;
     }
     // the redo's start (the finish's working set + the terminal-equality rows) with its inverse, built in registers from the cached
     // responses before the solve: k_sdual_start (csrc/almpc_sdual.hip.h)
-    if (sp.start_ws && sp.ghat && tier0 >= 1 && !getenv("ALMPC_SDUAL_NO_START_BUILD")) {
+    if (sp.start_ws && sp.ghat && tier0 >= 1 && !h->sw.sdual_no_start_build) {
         almpc_handle::Sd& sdw = h->sd;
         if (!sdw.start_inv) {
             const hipError_t e_ = dalloc(&sdw.start_inv, (size_t)h->batch * sdual_sinv_doubles(SDUAL_SINV_SAVE));
@@ -992,7 +991,7 @@ int resolve_lazy_redo(almpc_handle* h) {
 // Gated redo behind the last enqueued step (no host look, no synchronisation): see almpc_handle::Redo.  Called where the step's
 // results are about to be consumed without a synchronous call; does nothing unless a lazily deferred redo is pending.
 int enqueue_gated_redo(almpc_handle* h, bool predicted = false) {
-    if (!h->redo.lazy_pending || !h->redo.dGate || getenv("ALMPC_NO_GATED_REDO")) return ALMPC_OK;
+    if (!h->redo.lazy_pending || !h->redo.dGate || h->sw.no_gated_redo) return ALMPC_OK;
     SolveMode mode;
     mode.x0_from_results = true; mode.gated = true; mode.predicted = predicted;
     // As few launches as possible: an empty gated launch still costs 3 - 4 us of stream time on a 60 us step.  An input box alone
@@ -1016,7 +1015,7 @@ int enqueue_gated_redo(almpc_handle* h, bool predicted = false) {
 int wait_and_settle(almpc_handle* h, bool blocking_only = false) {
     almpc_handle::Redo& r = h->redo;
     bool predicted = false;
-    if (r.lazy_pending && r.expected && r.dGate && r.hUnsolved && !getenv("ALMPC_NO_PREDICTED_REDO")) {
+    if (r.lazy_pending && r.expected && r.dGate && r.hUnsolved && !h->sw.no_predicted_redo) {
         const int rc = enqueue_gated_redo(h, true);
         if (rc != ALMPC_OK) return rc;
         predicted = !r.lazy_pending;
@@ -1056,7 +1055,7 @@ RollGeom roll_geom(const almpc_handle* h) {
 // references (v0S).  Leaves s0_basis_ok false where the table does not apply (the finish then rolls v0 out).
 int build_s0_basis(almpc_handle* h) {
     h->s0_basis_ok = false;
-    if (h->mc <= 0 || h->batched || h->ltv || h->structured || !h->dVsPlain || !h->dRowTraj || getenv("ALMPC_NO_S0_BASIS")) return ALMPC_OK;
+    if (h->mc <= 0 || h->batched || h->ltv || h->structured || !h->dVsPlain || !h->dRowTraj || h->sw.no_s0_basis) return ALMPC_OK;
     const RollGeom roll = roll_geom(h);
     if (!roll.fits) return ALMPC_OK;
     if (!h->dS0Basis) HIP_TRY(h, dalloc(&h->dS0Basis, (size_t)(h->n + 1) * h->Rs));
@@ -1104,6 +1103,8 @@ int almpc_create(almpc_handle** out, int n, int m, int N, int batch, int device_
     if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return ALMPC_ERR_NO_DEVICE;
     if (device_id < 0 || device_id >= count) return ALMPC_ERR_NO_DEVICE;
     almpc_handle* h = new almpc_handle();
+    h->sw = read_switches();
+    h->fuse_step = h->sw.no_fused_step ? 0 : 1;
     h->n = n; h->m = m; h->N = N; h->batch = batch; h->device = device_id; h->flags = flags;
     h->structured = structured;
     h->nz = m * N;
@@ -1128,10 +1129,6 @@ int almpc_create(almpc_handle** out, int n, int m, int N, int batch, int device_
         int cus = 0;
         TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id));
         if (cus > 0) h->num_cus = cus;
-        const char* e = getenv("ALMPC_POLISH_NO_GLDS");
-        h->polish_no_glds = (e && e[0] == '1') ? 1 : 0;
-        const char* e2 = getenv("ALMPC_NO_FUSED_STEP");
-        h->fuse_step = (e2 && e2[0] == '1') ? 0 : 1;
     }
     const size_t fr = (size_t)h->nrb * h->ks * 64, b = (size_t)batch;
     if (structured) {   // no condensed matrices: models, references, inputs / outputs and the gain scratch only
@@ -1274,7 +1271,7 @@ int almpc_design_shared(almpc_handle* h, const double* A, const double* B, const
         if (Rm[0] == 0.0) std::fill(Rb.begin(), Rb.end(), 0.0);
         if (useS) Sm.assign(S, S + (size_t)m * m);
         h->sd.ready = false;
-        if (sdual_shape_ok(n, m, N, useS) && !getenv("ALMPC_STRUCTURED_PRIMAL")) {
+        if (sdual_shape_ok(n, m, N, useS) && !h->sw.structured_primal) {
             // the stage-wise dual active set (k_sdual): input box, state box, terminal equality, input-rate weight
             const int rc_ = sdual_setup_shared(h, Am, Bm, Qm, Rb, useS ? &Sm : nullptr, Pm, xmin, xmax, h->terminal_eq != 0);
             if (rc_ != ALMPC_OK) return rc_;
@@ -1337,7 +1334,7 @@ int almpc_design_shared(almpc_handle* h, const double* A, const double* B, const
                                   rowsel, h->Rs, h->dGhat, h->dGnorm, h->rho_mode, h->dRho, rowsel.empty() ? nullptr : h->dVsPlain,
                                   h->nzs <= 64 ? h->dPlain : nullptr);
     if (rc != ALMPC_OK) return rc;
-    if (h->terminal_eq && h->mc >= n && !getenv("ALMPC_NO_EQ_PROJECTION")) {
+    if (h->terminal_eq && h->mc >= n && !h->sw.no_eq_projection) {
         // the n terminal-equality rows (the last n state rows) are in every working set: eliminate them here, once
         const int ne = n, eq0 = h->R - n, Rs = h->Rs;
         std::vector<double> GE((size_t)ne * Rs), GEE((size_t)ne * ne), Y;
@@ -1378,7 +1375,7 @@ int almpc_design_shared(almpc_handle* h, const double* A, const double* B, const
         // [A^j B, ..., A B, B (stages t = 0..j), 0 ... | A^(j+1)]  (design-time host math, n x n products)
         int sblk = std::min(N, std::min(64 / n, ROLL_SMX / m));
         h->roll_s = 0;
-        if (sblk >= 1 && n <= ROLL_NX && !getenv("ALMPC_ROLLOUT_STAGEWISE")) {
+        if (sblk >= 1 && n <= ROLL_NX && !h->sw.rollout_stagewise) {
             std::vector<double> M((size_t)(ROLL_SMX + ROLL_NX) * 64, 0.0);
             std::vector<hm::mat> Apow(sblk + 1), ApB(sblk);  // A^j, A^j B
             Apow[0] = hm::eye(n);
@@ -1484,33 +1481,33 @@ void launch_batched_factor(almpc_handle* h, const DesignStrides& ds, double rho,
     const unsigned gb = (unsigned)h->batch;
     if (!scaled) hipLaunchKernelGGL(k_design_scale, dim3(1, gb), dim3(256), 0, st, nz, nzs, n, h->bH, h->bF, h->bD, h->bHs, h->bFs, h->bFlag, ds);
     const size_t inv_lds = 520 * sizeof(double);
-    if (!v1M && !no_admm && h->rho_mode == 0 && design_inverse_makes_rho(nz, nzs) && nz <= 64 && design_inverse_makes_v(nz) && !getenv("ALMPC_DBG_SPLIT_INVERSES")) {
+    if (!v1M && !no_admm && h->rho_mode == 0 && design_inverse_makes_rho(h->sw, nz, nzs) && nz <= 64 && design_inverse_makes_v(h->sw, nz) && !h->sw.dbg_split_inverses) {
         // scalar rho: the ADMM's KKT inverse does not need G_i -- both inverses, the penalty profile and V_i in ONE launch
         h->minv_packed = false;
-        launch_design_inverse(dim3(1, gb), inv_lds, st, nz, nzs, h->bHs, 0.0, (const double*)nullptr, h->bG, h->bFlag, ds.Hs, ds.rho, ds.G, 1L,
+        launch_design_inverse(h->sw, dim3(1, gb), inv_lds, st, nz, nzs, h->bHs, 0.0, (const double*)nullptr, h->bG, h->bFlag, ds.Hs, ds.rho, ds.G, 1L,
                               (const double*)nullptr, 0L, 0, rho, h->bRho, with_v ? h->bFs : nullptr, h->bVs, ds.Fs, n, h->bMinv, ds.Minv, sigma);
         return;
     }
-    if (v1M && design_inverse_makes_v(nz))   // one column per instance from the rows / columns of G_i the inverse still holds
-        launch_design_inverse(dim3(1, gb), inv_lds, st, nz, nzs, h->bHs, 0.0, (const double*)nullptr, h->bG, h->bFlag, ds.Hs, 0L, ds.G, 1L,
+    if (v1M && design_inverse_makes_v(h->sw, nz))   // one column per instance from the rows / columns of G_i the inverse still holds
+        launch_design_inverse(h->sw, dim3(1, gb), inv_lds, st, nz, nzs, h->bHs, 0.0, (const double*)nullptr, h->bG, h->bFlag, ds.Hs, 0L, ds.G, 1L,
                               (const double*)nullptr, 0L, 0, 0.0, (double*)nullptr, v1M, v1Out, (long)nz, 1, (double*)nullptr, 0L, 0.0, nz);
-    else if (with_v && nz <= 64 && design_inverse_makes_v(nz))   // V_i = -G_i F'_i from the rows of G_i the inverse's wave still holds (the
+    else if (with_v && nz <= 64 && design_inverse_makes_v(h->sw, nz))   // V_i = -G_i F'_i from the rows of G_i the inverse's wave still holds (the
                                                                   // column-split kernel: measured slower than k_neg_gm_cols for n columns)
-        launch_design_inverse(dim3(1, gb), inv_lds, st, nz, nzs, h->bHs, 0.0, (const double*)nullptr, h->bG, h->bFlag, ds.Hs, 0L, ds.G, 1L,
+        launch_design_inverse(h->sw, dim3(1, gb), inv_lds, st, nz, nzs, h->bHs, 0.0, (const double*)nullptr, h->bG, h->bFlag, ds.Hs, 0L, ds.G, 1L,
                               (const double*)nullptr, 0L, 0, 0.0, (double*)nullptr, h->bFs, h->bVs, ds.Fs, n);
     else {
-        launch_design_inverse(dim3(1, gb), inv_lds, st, nz, nzs, h->bHs, 0.0, (const double*)nullptr, h->bG, h->bFlag, ds.Hs, 0L, ds.G, 1L);
+        launch_design_inverse(h->sw, dim3(1, gb), inv_lds, st, nz, nzs, h->bHs, 0.0, (const double*)nullptr, h->bG, h->bFlag, ds.Hs, 0L, ds.G, 1L);
         if (with_v) launch_neg_gm_batched(st, gb, nz, nzs, n, h->bG, h->bFs, h->bVs, ds.G, ds.Fs);
     }
     if (no_admm) return;
-    h->minv_packed = design_inverse_can_pack(nz);   // the ADMM's KKT inverse as its packed triangle: half the stream of k_admm_inst
+    h->minv_packed = design_inverse_can_pack(h->sw, nz);   // the ADMM's KKT inverse as its packed triangle: half the stream of k_admm_inst
     const long sMinv = h->minv_packed ? packed_tri_doubles(nz) : ds.Minv;
-    if (design_inverse_makes_rho(nz, nzs))   // the penalty profile is made inside the inverse's own launch
-        launch_design_inverse(dim3(1, gb), inv_lds, st, nz, nzs, h->bHs, sigma, (const double*)nullptr, h->bMinv, h->bFlag, ds.Hs, ds.rho, ds.Minv, 1L,
+    if (design_inverse_makes_rho(h->sw, nz, nzs))   // the penalty profile is made inside the inverse's own launch
+        launch_design_inverse(h->sw, dim3(1, gb), inv_lds, st, nz, nzs, h->bHs, sigma, (const double*)nullptr, h->bMinv, h->bFlag, ds.Hs, ds.rho, ds.Minv, 1L,
                               h->bG, ds.G, h->rho_mode, rho, h->bRho);
     else {
         hipLaunchKernelGGL(k_design_rho, dim3(1, gb), dim3(256), 0, st, nz, nzs, h->rho_mode, rho, h->bG, h->bRho, ds.G, ds.rho);
-        launch_design_inverse(dim3(1, gb), inv_lds, st, nz, nzs, h->bHs, sigma, (const double*)h->bRho, h->bMinv, h->bFlag, ds.Hs, ds.rho, sMinv, 1L,
+        launch_design_inverse(h->sw, dim3(1, gb), inv_lds, st, nz, nzs, h->bHs, sigma, (const double*)h->bRho, h->bMinv, h->bFlag, ds.Hs, ds.rho, sMinv, 1L,
                               (const double*)nullptr, 0L, 0, 0.0, (double*)nullptr, (const double*)nullptr, (double*)nullptr, 0L, 0, (double*)nullptr, 0L, 0.0, 0,
                               h->minv_packed ? 1 : 0);
     }
@@ -1567,13 +1564,13 @@ static auto with_net(int net, Pick pick) {
 
 // Jacobians of the network (kind net: NET_*) at p.batch points: wave-per-point build when weights + 4 waves' buffers fit 64 KB of
 // LDS, else one workgroup per point (the caller has checked fnn_wave_scratch_doubles against 160 KB).
-hipError_t launch_fnn_jacobian(const FnnParams& p, int net, int num_cus, hipStream_t st) {
+hipError_t launch_fnn_jacobian(const Switches& sw, const FnnParams& p, int net, int num_cus, hipStream_t st) {
     const size_t nin = (size_t)p.n + p.m;
     // small networks (H (n + m) <= 192 entries of the Jacobian being propagated): two points per wave, one per half-wave
     // (four points per wave, a quarter-wave each: measured no better, 0.305 against 0.303 ms per SQP iteration)
-    const int ppw = ((size_t)p.H * nin <= 192 && !getenv("ALMPC_FNN_ONE_POINT_PER_WAVE")) ? 2 : 1;
+    const int ppw = ((size_t)p.H * nin <= 192 && !sw.fnn_one_point_per_wave) ? 2 : 1;
     const size_t lw = fnn_w_lds_doubles(p.n, p.m, p.H, p.L, ppw, net) * sizeof(double);
-    if (lw <= 64 * 1024 && !getenv("ALMPC_FNN_WG")) {
+    if (lw <= 64 * 1024 && !sw.fnn_wg) {
         int wgs = (p.batch + FNN_W_WAVES * ppw - 1) / (FNN_W_WAVES * ppw);
         const int cap = num_cus * 8;  // 32 waves per CU: a point is a latency chain on one wave (18 us); 16 waves per CU took 55 us for the
                                       // 12800 points of an SQP iteration, 32 take 48 (52 workgroups per CU: 49.5)
@@ -1597,7 +1594,7 @@ hipError_t launch_fnn_jacobian(const FnnParams& p, int net, int num_cus, hipStre
 bool ltv_reg_path(const almpc_handle* h) {
     const int n = h->n, m = h->m;
     return h->nz <= LTV_REG_NZ && n * n + n * m <= 1024 - n && design_ltv_reg_lds_doubles(n, m, h->N) * sizeof(double) <= 160 * 1024 &&
-           !getenv("ALMPC_LTV_LDS");
+           !h->sw.ltv_lds;
 }
 
 bool ltv_supported(const almpc_handle* h) {
@@ -1606,17 +1603,9 @@ bool ltv_supported(const almpc_handle* h) {
 
 template <int NC>
 hipError_t launch_design_ltv_reg(almpc_handle* h, const DesignLtvParams& lp, size_t lds, hipStream_t st) {
-    // 8 x 8 register tiles on 256 threads (ALMPC_LTV_T8=1): measured SLOWER (SQP iteration 0.392 against 0.348 ms): the stage is bound
-    // by the latency of its dependent LDS steps, which 16 waves hide better than four, not by LDS bytes
-    const bool t8 = NC > 0 && h->n * h->n + h->n * h->m <= 256 - h->n && getenv("ALMPC_LTV_T8");
-    if (t8) {
-        if (lds > 64 * 1024) {
-            const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_design_ltv_reg<NC, 8>), (size_t)(lds));
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((k_design_ltv_reg<NC, 8>), dim3((unsigned)h->batch), dim3(256), lds, st, lp);
-        return hipGetLastError();
-    }
+    // 4 x 4 register tiles on 1024 threads.  (8 x 8 tiles on 256 threads, k_design_ltv_reg<NC, 8>, were measured SLOWER -- SQP iteration
+    // 0.392 against 0.348 ms: the stage is bound by the latency of its dependent LDS steps, which 16 waves hide better than four, not by
+    // LDS bytes -- and are not instantiated)
     if (lds > 64 * 1024) {
         const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_design_ltv_reg<NC, 4>), (size_t)(lds));
         if (e != hipSuccess) return e;
@@ -1651,7 +1640,7 @@ hipError_t launch_design_ltv(almpc_handle* h, const DesignLtvParams& lp, hipStre
 bool design_fuses_fnn(const almpc_handle* h, int H, int L, int net) {
     if (net != NET_FNN) return false;
     const size_t lds = (design_instance_lds_doubles(h->n, h->m, h->N) + fnn_weights_doubles(h->n, h->m, H, L) + fnn_wave_scratch_doubles(h->n, h->m, H, L)) * sizeof(double);
-    return lds <= 160 * 1024 && !getenv("ALMPC_DBG_SPLIT_JACOBIAN");
+    return lds <= 160 * 1024 && !h->sw.dbg_split_jacobian;
 }
 
 // The per-instance design from DEVICE-resident operands (bA, bB, bP; weights dQ, dR, dS): prediction matrices, H_i and F_i,
@@ -1683,7 +1672,7 @@ hipError_t launch_batched_design(almpc_handle* h, const DesignStrides& ds, int u
         dp.n = n; dp.m = m; dp.N = N; dp.nz = nz; dp.useR = useR; dp.useS = useS;
         dp.A = h->bA; dp.B = h->bB; dp.P = h->bP; dp.sA = ds.A; dp.sB = ds.B; dp.sP = ds.P;
         dp.Q = dQ; dp.R = dR; dp.S = dS; dp.H = h->bH; dp.F = h->bF; dp.sH = ds.H; dp.sF = ds.F;
-        if (nz <= 128 && design_instance_lds_doubles(n, m, N) >= 128 && !getenv("ALMPC_DBG_SPLIT_SCALE")) {   // the scaling rides along (k_design_scale's body, one launch less)
+        if (nz <= 128 && design_instance_lds_doubles(n, m, N) >= 128 && !h->sw.dbg_split_scale) {   // the scaling rides along (k_design_scale's body, one launch less)
             dp.d = h->bD; dp.Hs = h->bHs; dp.Fs = h->bFs; dp.sd = ds.d; dp.sHs = ds.Hs; dp.sFs = ds.Fs; dp.nzs = nzs;
         }
         scaled = dp.Hs != nullptr;
@@ -1758,7 +1747,7 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
         const double* bxmin = h->boxmin.empty() ? nullptr : h->boxmin.data();
         const double* bxmax = h->boxmax.empty() ? nullptr : h->boxmax.data();
         h->sd.ready = false;
-        if (sdual_shape_ok(n, m, N, useS) && !getenv("ALMPC_STRUCTURED_PRIMAL")) {
+        if (sdual_shape_ok(n, m, N, useS) && !h->sw.structured_primal) {
             const int rc_ = sdual_setup_batched(h, Qm, Rm, useS ? &Sm : nullptr, P == nullptr && !useS, bxmin, bxmax, h->terminal_eq != 0);
             if (rc_ != ALMPC_OK) return rc_;
             HIP_TRY(h, launch_sgains(h, 0));
@@ -1789,7 +1778,7 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
     h->sqp.ready = h->sqp.started = false;
     h->relin.ready = false;
     // ALMPC_DESIGN_TRACE=1: host-side time between the marks below on stderr (where a design call spends its wall clock)
-    const bool trace_ = getenv("ALMPC_DESIGN_TRACE") != nullptr;
+    const bool trace_ = h->sw.design_trace;
     auto t_mark_ = std::chrono::steady_clock::now();
     auto tr = [&](const char* what) {
         if (!trace_) return;
@@ -2190,7 +2179,7 @@ PolishLayout polish_layout(const almpc_handle* h, const RollGeom& roll) {
     L.l_glds = (L.g_lds + L.SL.total + (size_t)POLISH_WAVES_GLDS * per_wave + 2) * sizeof(double);
     // workgroup-shared second-tier slot (working sets beyond 32 rows) behind the queue words, if the 160 KB allow it
     const size_t slot = (size_t)POLISH_SG_SHARED_CAP * 64 * sizeof(double);
-    if (L.l_glds + slot <= 160 * 1024 && !h->batched && !getenv("ALMPC_POLISH_SG_GLOBAL")) {
+    if (L.l_glds + slot <= 160 * 1024 && !h->batched && !h->sw.polish_sg_global) {
         L.sg_shared_off = (int)(L.SL.total + (size_t)POLISH_WAVES_GLDS * per_wave + 2);
         L.l_glds += slot;
     }
@@ -2229,7 +2218,7 @@ Route pick_route(const Step& s, const PolishLayout& L) {
     const almpc_handle* h = s.h;
     if (h->mc > 0) return Route::StateRows;
     if (!s.o.polish) return Route::NoPolish;
-    if (!h->batched && h->fuse_step && POLISH_WAVES_GLDS == 8 && !h->polish_no_glds && h->nrb == 8 && (h->ks == 30 || h->ks == 32) && L.fused &&
+    if (!h->batched && h->fuse_step && POLISH_WAVES_GLDS == 8 && !h->sw.polish_no_glds && h->nrb == 8 && (h->ks == 30 || h->ks == 32) && L.fused &&
         L.l_step <= 160 * 1024)
         return Route::FusedShared;
     // small SHARED problems in small batches (configs[0], the reference's own test sizes: one instance, N 5 - 15, m 2 -> nz 10 - 30;
@@ -2240,16 +2229,13 @@ Route pick_route(const Step& s, const PolishLayout& L) {
     // against 43 / 56, batch 512 30 / 58 against 44 / 58; from 2048 instances on a wave per 10 - 40-row problem wastes the machine
     // (63 / 113 against 45 / 70 us; 65,536: 1.8 / 2.3 ms against 0.32 / 0.68 ms): up to two instances per CU take this path, larger
     // batches the tile path.
-    const char* no_sw = getenv("ALMPC_NO_SHARED_WAVE");
-    const char* sw_max = getenv("ALMPC_SHARED_WAVE_MAX_BATCH");
-    if (!h->batched && h->nzs <= 64 && L.fused && h->dPlain && !h->ltv && !(no_sw && no_sw[0] == '1') &&
-        (long)h->batch <= (sw_max ? atol(sw_max) : (long)2 * h->num_cus) && ((size_t)L.SL.total + (size_t)L.per_wave) * sizeof(double) <= 64 * 1024)
+    if (!h->batched && h->nzs <= 64 && L.fused && h->dPlain && !h->ltv && !h->sw.no_shared_wave &&
+        (long)h->batch <= h->sw.shared_wave_max_batch.value_or((long)2 * h->num_cus) && ((size_t)L.SL.total + (size_t)L.per_wave) * sizeof(double) <= 64 * 1024)
         return Route::WaveShared;
     // small per-instance problems (BASELINE configs[3]): ONE wave per instance for the whole step -- ADMM with the KKT inverse in
     // registers, then the single-wave finish with G_i in the wave's LDS (the second-tier Sinv, rarely needed at these sizes, stays in the
     // global scratch: with its 32 KB per wave only three waves would fit a CU)
-    const char* no_iw = getenv("ALMPC_NO_INST_WAVE");
-    if (h->batched && s.mode.guess == Guess::Admm && h->nzs <= 64 && L.fused && !(no_iw && no_iw[0] == '1') &&
+    if (h->batched && s.mode.guess == Guess::Admm && h->nzs <= 64 && L.fused && !h->sw.no_inst_wave &&
         ((size_t)L.SL.total + (size_t)L.per_wave + (size_t)h->nz * h->nzs) * sizeof(double) <= 64 * 1024)
         return Route::WaveInst;
     return Route::TwoLaunch;
@@ -2281,7 +2267,7 @@ int step_admm_or_guess(Step& s, bool* guess_ws = nullptr) {
     if (s.mode.guess == Guess::ShiftInputs) {
         hipLaunchKernelGGL(k_guess_shift, dim3((h->batch + 3) / 4), dim3(256), 0, st, ip, (const double*)h->dU, h->N);
     } else if (s.mode.guess == Guess::FromIterate && h->nzs <= 128 && h->nzs > 64 && h->batch <= 2 * h->num_cus && h->dSglobal && h->bG &&
-               !getenv("ALMPC_NO_GUESS_WS")) {
+               !h->sw.no_guess_ws) {
         // the guess of an SQP iteration AND the inverse of its working set (33..64 of the inputs on a bound), four waves per instance
         if (!h->dStartRows) HIP_TRY(h, dalloc(&h->dStartRows, (size_t)h->batch * 65));
         GuessWsParams gw;
@@ -2370,7 +2356,7 @@ int step_state_rows(Step& s) {
     if (!h->dOvfSinv) HIP_TRY(h, dalloc(&h->dOvfSinv, (size_t)h->batch * (32 * 32 + 32)));
     gp.ovf = h->dOverflow; gp.ovf_ws = h->dOverflow + 2 + h->batch; gp.ovf_sinv = h->dOvfSinv;
     if (s.lazy_redo) { gp.unsolved = h->redo.dUnsolved; gp.redo_gate = h->redo.dGate; gp.step_serial = h->redo.step_serial; }
-    if (h->fallback && !h->ltv && h->sd.ready && !h->sd.sqp && !getenv("ALMPC_NO_REDO_START")) {   // a stage-wise redo may follow: it starts from what this finish gives up with
+    if (h->fallback && !h->ltv && h->sd.ready && !h->sd.sqp && !h->sw.no_redo_start) {   // a stage-wise redo may follow: it starts from what this finish gives up with
         if (!h->sd.start_ws) HIP_TRY(h, dalloc(&h->sd.start_ws, (size_t)h->batch * 64));
         gp.redo_ws = h->sd.start_ws; gp.redo_sp = h->sd.NT + h->sd.MC; gp.redo_nt = h->sd.NT;
         h->sd.start_ws_fresh = true;
@@ -2456,11 +2442,11 @@ int step_two_launch(Step& s, const PolishLayout& L) {
     PolishParams pp = polish_params(s, L);
     const size_t sgl_wave = (size_t)L.per_wave + POLISH_GLB_PER_INST + (size_t)h->nz * h->nzs;
     const size_t l_sgl = ((size_t)L.SL.total + sgl_wave) * sizeof(double);
-    if (L.l_glds <= 160 * 1024 && !h->polish_no_glds && !h->batched) {
+    if (L.l_glds <= 160 * 1024 && !h->sw.polish_no_glds && !h->batched) {
         HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_polish<true>), L.l_glds));
         const int wgs = pp.ntiles > h->num_cus ? h->num_cus : pp.ntiles;   // one ADMM tile (16 instances) per workgroup and round
         hipLaunchKernelGGL((k_polish<true>), dim3(wgs), dim3(64 * POLISH_WAVES_GLDS), L.l_glds, st, pp);
-    } else if (h->batched && h->batch <= 2 * h->num_cus && l_sgl <= 160 * 1024 && !getenv("ALMPC_POLISH_SG_GLOBAL")) {
+    } else if (h->batched && h->batch <= 2 * h->num_cus && l_sgl <= 160 * 1024 && !h->sw.polish_sg_global) {
         pp.sg_off = L.per_wave;
         pp.g_off = L.per_wave + POLISH_GLB_PER_INST;
         pp.lds_per_wave = (int)sgl_wave;
@@ -2517,11 +2503,11 @@ int step_redo(Step& s) {
         return ALMPC_OK;
     }
     if (!h->fallback || h->ltv || !s.o.polish) return ALMPC_OK;
-    if (h->sd.ready && !getenv("ALMPC_DBG_NO_SDUAL_FB")) {
+    if (h->sd.ready && !h->sw.dbg_no_sdual_fb) {
         if (h->sd.per_instance) HIP_TRY(h, launch_sgains(h, 1));   // (stage records of the unsolved instances only, from the models of this step)
         HIP_TRY(h, launch_sdual(h, 1, h->dU, 0, true));
     }
-    if (h->mc == 0 && !h->useS && h->rKst && !getenv("ALMPC_DBG_NO_PRIMAL_NET")) HIP_TRY(h, launch_riccati(h, 1, h->dU, 0));
+    if (h->mc == 0 && !h->useS && h->rKst && !h->sw.dbg_no_primal_net) HIP_TRY(h, launch_riccati(h, 1, h->dU, 0));
     return ALMPC_OK;
 }
 
@@ -2538,7 +2524,7 @@ hipError_t ensure_unsolved_word(almpc_handle* h) {
 }
 
 // One step on checked options: the route is picked here, on every call (it depends on almpc_set_step_fusion, the reference strides,
-// the options and the switches read at call time)
+// the options and the handle's switches)
 int run_step(almpc_handle* h, const almpc_opts& o, StepMode mode) {
     // ALMPC_OPT_NO_WARM_STATE: shared-model steps with the polish on (the polish needs only the signs of y); ignored elsewhere
     const bool keep_state = !((o.reserved[0] & ALMPC_OPT_NO_WARM_STATE) && !h->batched && o.polish && h->mc == 0);
@@ -2550,7 +2536,7 @@ int run_step(almpc_handle* h, const almpc_opts& o, StepMode mode) {
     // their verdict and are not counted; what is counted is rare -- a handful of edge-of-feasibility instances in 4096 -- and a
     // stage-wise solve of one of them takes about a millisecond, which an eager redo would put behind every step)
     const bool lazy_redo = h->fallback == 2 && !h->structured && !h->ltv && o.polish != 0 &&
-                           (h->sd.ready || (h->mc == 0 && h->rKst)) && !getenv("ALMPC_EAGER_REDO");
+                           (h->sd.ready || (h->mc == 0 && h->rKst)) && !h->sw.eager_redo;
     HIP_TRY(h, hipSetDevice(h->device));
     if (h->io.big_copy_pending) {   // an asynchronous read-back straight from the result buffers: this step overwrites them
         HIP_TRY(h, hipStreamWaitEvent(h->stream, h->io.ev_big, 0));
@@ -2811,7 +2797,7 @@ int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
         // unconstrained problem (k_sgains) -> the stage-wise dual active set (k_sdual), warm-started from the previous step's inputs
         // shifted by one stage when opts->warm_start is set.  No Hessian is formed: the reference's Fnn-LP delegation has no horizon
         // limit (.../fnn/mpc_modeler_implementation_fnn.jl:23-58) and neither has this route.
-        HIP_TRY(h, launch_fnn_jacobian(fp, q.net, h->num_cus, st));
+        HIP_TRY(h, launch_fnn_jacobian(h->sw, fp, q.net, h->num_cus, st));
         if (timing) HIP_TRY(h, hipEventRecord(q.ev[1], st));
         HIP_TRY(h, launch_sgains(h, 0));
         if (timing) HIP_TRY(h, hipEventRecord(q.ev[2], st));
@@ -2827,7 +2813,7 @@ int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
         return ALMPC_OK;
     }
     const bool fuse_jac = design_fuses_fnn(h, q.H, q.L, q.net);   // the design kernel's workgroups linearise their own instance
-    if (!fuse_jac) HIP_TRY(h, launch_fnn_jacobian(fp, q.net, h->num_cus, st));
+    if (!fuse_jac) HIP_TRY(h, launch_fnn_jacobian(h->sw, fp, q.net, h->num_cus, st));
     if (timing) HIP_TRY(h, hipEventRecord(q.ev[1], st));
     // 2. the reference's QP for every (A_i, B_i): H_i, F_i, scaling, inverses, V_i; reference-dependent vectors.  A warm step
     // (opts.warm_start = 1 after a solved step) takes its working-set guess from the previous step's inputs shifted by one stage
@@ -2894,7 +2880,7 @@ int almpc_relin_fnn_advance(almpc_handle* h) {
     // lazily deferred redo of that step still needs)
     if (!q.Ascr) { HIP_TRY(h, dalloc(&q.Ascr, (size_t)h->batch * n * n)); HIP_TRY(h, dalloc(&q.Bscr, (size_t)h->batch * n * m)); }
     fp.A = q.Ascr; fp.B = q.Bscr; fp.f = q.xnext;
-    HIP_TRY(h, launch_fnn_jacobian(fp, q.net, h->num_cus, st));
+    HIP_TRY(h, launch_fnn_jacobian(h->sw, fp, q.net, h->num_cus, st));
     if (h->io.x0_slot >= 0) {   // a pinned x0 slot was read once more by the forward pass: free for the host only after it
         HIP_TRY(h, hipEventRecord(h->io.ev_used[h->io.x0_slot], st));
         h->io.used_pending[h->io.x0_slot] = true;
@@ -3154,7 +3140,6 @@ int almpc_sqp_fnn_start(almpc_handle* h, const double* x0, const double* u_guess
     }
     q.started = true;
     q.since_start = 0;
-    { const char* e = getenv("ALMPC_SQP_ADMM_ALWAYS"); q.guess_from_iterate = (e && e[0] == '1') ? 0 : 1; }
     return ALMPC_OK;
 }
 
@@ -3343,17 +3328,17 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
     }
     // register-tile design kernel: scaling, scaled gradient and the flag reset ride along as its tail (three launches less per iteration)
     // (not in exact mode: k_sqp_exact_qp changes H and q after the design, the factor then scales them)
-    const bool ltv_scales = !exact && ltv_reg_path(h) && nz <= 128 && !q.structured_qp && !getenv("ALMPC_DBG_SPLIT_SCALE");
+    const bool ltv_scales = !exact && ltv_reg_path(h) && nz <= 128 && !q.structured_qp && !h->sw.dbg_split_scale;
     if (ltv_scales) { lp.sc_d = h->bD; lp.sc_Hs = h->bHs; lp.sc_fS = h->dFS; lp.sc_flag = h->bFlag; lp.nzs = nzs; }
     // ... and k_sqp_prepare as its head (its outputs are that kernel's inputs): a fourth launch less
-    const bool prep_in_design = ltv_scales && !getenv("ALMPC_DBG_SPLIT_PREPARE");
+    const bool prep_in_design = ltv_scales && !h->sw.dbg_split_prepare;
     if (prep_in_design) { lp.prep_on = 1; lp.prep = sp; }
     for (int it = 0; it < iters; ++it) {
         if (sv && it >= 2) {   // every live instance had converged at the top of iteration it - 2: the rest is frozen work
             HIP_TRY(h, hipEventSynchronize(sv->ev[(it - 2) & 3]));
             if (sv->live_pin[(it - 2) & 3] == 0) { all_done = true; break; }
         }
-        HIP_TRY(h, launch_fnn_jacobian(fp, q.net, h->num_cus, st));
+        HIP_TRY(h, launch_fnn_jacobian(h->sw, fp, q.net, h->num_cus, st));
         if (sv) HIP_TRY(h, kkt_test(it));
         if (exact) {   // multipliers (from the test above, or the walk alone), then the stage Lagrangian Hessians at the iterate
             if (!sv) hipLaunchKernelGGL(k_sqp_kkt, dim3((unsigned)b), dim3(256), step_lds, st, kp);
@@ -3388,10 +3373,10 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
             HIP_TRY(h, hipGetLastError());
         }
         StepMode mode;
-        mode.guess = (q.guess_from_iterate && q.since_start > 0) ? Guess::FromIterate : Guess::Admm;
+        mode.guess = (!h->sw.sqp_admm_always && q.since_start > 0) ? Guess::FromIterate : Guess::Admm;
         mode.rows = rows;
         // (with the scaling in the design kernel's tail fS_i exists before the inverse: v0S_i = -G_i fS_i comes out of the inverse's launch)
-        const bool v0_in_inverse = ltv_scales && design_inverse_makes_v(nz);
+        const bool v0_in_inverse = ltv_scales && design_inverse_makes_v(h->sw, nz);
         launch_batched_factor(h, ds, h->rho, h->sigma, st, mode.guess != Guess::Admm, ltv_scales, false, v0_in_inverse ? h->dFS : nullptr, h->dV0S);
         if (h->mc > 0) HIP_TRY(h, launch_ghat_inst(h, q.A, q.B));
         if (!ltv_scales) hipLaunchKernelGGL(k_fs_scale, dim3(256), dim3(256), 0, st, h->batch, nz, nzs, h->bQ, (long)nz, h->bD, h->dFS);
@@ -3406,7 +3391,7 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
             // input box without S: the primal Riccati active set alone -- the solver this loop's stage-wise QP route uses for such problems
             // (an iterate holds half of its inputs on bounds; a saturated unstable linearisation is where the dual method has no
             // certificate) --, ONE idle launch per iteration instead of three; with state rows / S: k_sgains + k_sdual
-            const bool primal_only = h->mc == 0 && !q.useS && h->rKst && !getenv("ALMPC_SQP_REDO_DUAL_FIRST");
+            const bool primal_only = h->mc == 0 && !q.useS && h->rKst && !h->sw.sqp_redo_dual_first;
             if (h->sd.ready && !primal_only) { HIP_TRY(h, launch_sgains(h, 2)); HIP_TRY(h, launch_sdual(h, 2, nullptr, 0, true, 0, {}, rows)); }
             if (h->mc == 0 && !q.useS && h->rKst) HIP_TRY(h, launch_riccati(h, 2, nullptr, 0));
         }
@@ -3416,7 +3401,7 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
         HIP_TRY(h, hipGetLastError());
     }
     if (sv && !all_done) {   // the last test, at the final iterate
-        HIP_TRY(h, launch_fnn_jacobian(fp, q.net, h->num_cus, st));
+        HIP_TRY(h, launch_fnn_jacobian(h->sw, fp, q.net, h->num_cus, st));
         HIP_TRY(h, kkt_test(iters));
     }
     if (sv) return almpc_synchronize(h);   // (per-instance verdicts instead of ALMPC_ERR_NUMERIC; no histories)
@@ -3778,6 +3763,7 @@ int almpc_dare(int n, int m, const double* A, const double* B, const double* Q, 
 static int net_linearize(bool dense, int device_id, int n, int m, int H, int L, int activation, const double* W_in, const double* W_h,
                          const double* b_h, const double* W_out, int batch, const double* x, const double* u, double* A,
                          double* B, double* f) {
+    const Switches sw = read_switches();   // (no handle: the switches of this call)
     if (n < 1 || m < 1 || H < 1 || L < 0 || batch < 1 || !W_in || !W_out || !x || !u || !A || !B || (L > 0 && (!W_h || !b_h)))
         return ALMPC_ERR_INVALID;
     int net = NET_FNN;
@@ -3807,7 +3793,7 @@ static int net_linearize(bool dense, int device_id, int n, int m, int H, int L, 
     if (rc == ALMPC_OK) {
         hipDeviceProp_t prop;
         const int cus = hipGetDeviceProperties(&prop, device_id) == hipSuccess ? prop.multiProcessorCount : 256;
-        if (launch_fnn_jacobian(p, net, cus, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = ALMPC_ERR_HIP;
+        if (launch_fnn_jacobian(sw, p, net, cus, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = ALMPC_ERR_HIP;
     }
     if (rc == ALMPC_OK) {
         if (hipMemcpy(A, p.A, (size_t)batch * n * n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||

@@ -14,6 +14,7 @@
 //   k_pack_frags             dense -> MFMA A-fragment layout used by k_admm
 #pragma once
 #include "almpc_kernels.hip.h"
+#include "almpc_switches.h"
 
 #include <string>
 #include <vector>
@@ -797,28 +798,27 @@ __global__ __launch_bounds__(64 * (128 / CW)) void k_design_inverse_c32(int nz, 
 
 // launcher: the smallest register tile that holds the matrix
 // whether launch_design_inverse makes the ADMM penalty profile itself (rho_G given): the one-wave kernel does, the others need k_design_rho first
-inline bool design_inverse_makes_rho(int nz, int nzs) { return nz <= 64 && nzs <= 64 && !getenv("ALMPC_INV_TILE") && !getenv("ALMPC_NO_RHO_FUSION"); }
+inline bool design_inverse_makes_rho(const Switches& sw, int nz, int nzs) { return nz <= 64 && nzs <= 64 && !sw.inv_tile && !sw.no_rho_fusion; }
 // (the one-wave-per-matrix kernel can also form V = -Out vM from the rows it holds: see there)
 // whether launch_design_inverse can write the packed lower triangle (the column-split kernel, 64 < nz <= 128)
-inline bool design_inverse_can_pack(int nz) { return nz > 64 && nz <= 128 && (nz & 1) == 0 && !getenv("ALMPC_INV_TILE") && !getenv("ALMPC_NO_PACKED_MINV"); }
-inline bool design_inverse_makes_v(int nz) { return nz <= 128 && !getenv("ALMPC_INV_TILE") && !getenv("ALMPC_DBG_SPLIT_NEGGM"); }   // (one-wave and column-split kernels)
-inline void launch_design_inverse(dim3 grid, size_t lds, hipStream_t st, int nz, int nzs, const double* Hs, double cshift, const double* dshift,
+inline bool design_inverse_can_pack(const Switches& sw, int nz) { return nz > 64 && nz <= 128 && (nz & 1) == 0 && !sw.inv_tile && !sw.no_packed_minv; }
+inline bool design_inverse_makes_v(const Switches& sw, int nz) { return nz <= 128 && !sw.inv_tile && !sw.dbg_split_neggm; }   // (one-wave and column-split kernels)
+inline void launch_design_inverse(const Switches& sw, dim3 grid, size_t lds, hipStream_t st, int nz, int nzs, const double* Hs, double cshift, const double* dshift,
                                   double* Out, int* flag, long sHs, long sShift, long sOut, long sFlag,
                                   const double* rho_G = nullptr, long sRhoG = 0, int rho_mode = 0, double rho = 0.0, double* rho_out = nullptr,
                                   const double* vM = nullptr, double* vOut = nullptr, long sV = 0, int vcols = 0,
                                   double* Out2 = nullptr, long sOut2 = 0, double cshift2 = 0.0, int vld = 0, int packed_out = 0) {
     // (packed_out: only the column-split kernel writes the packed triangle; the caller asks design_inverse_can_pack first)
     if (vld == 0) vld = nzs;
-    if (nz <= 64 && !getenv("ALMPC_INV_TILE")) {   // one wave per matrix (grid.y = matrices, as for the tile kernels)
+    if (nz <= 64 && !sw.inv_tile) {   // one wave per matrix (grid.y = matrices, as for the tile kernels)
         const int b = (int)grid.y;
         const dim3 g2((unsigned)(((Out2 ? 2 * b : b) + 3) / 4));
 #define INV_WAVE(NC_) hipLaunchKernelGGL((k_design_inverse_wave<NC_>), g2, dim3(256), 0, st, nz, nzs, b, Hs, cshift, dshift, Out, flag, sHs, sShift, sOut, sFlag, rho_G, sRhoG, rho_mode, rho, rho_out, vM, vOut, sV, vcols, Out2, sOut2, cshift2, vld)
         if (nz <= 16) INV_WAVE(16); else if (nz <= 32) INV_WAVE(32); else if (nz <= 48) INV_WAVE(48); else INV_WAVE(64);
 #undef INV_WAVE
     } else if (nz <= 64) hipLaunchKernelGGL((k_design_inverse_t<2, 8>), grid, dim3(DESIGN_INVERSE_THREADS), lds, st, nz, nzs, Hs, cshift, dshift, Out, flag, sHs, sShift, sOut, sFlag);
-    else if (!getenv("ALMPC_INV_TILE")) {
-        const char* cwv = getenv("ALMPC_INV_CW");   // (experiment: columns per wave)
-        const int cw = cwv ? atoi(cwv) : (grid.y <= 256 ? 16 : 32);   // one matrix per CU: eight waves of 16 columns (51 against 59 us at nz 100)
+    else if (!sw.inv_tile) {
+        const long cw = sw.inv_columns_per_wave.value_or(grid.y <= 256 ? 16 : 32);   // (ALMPC_INV_CW: experiment)   // one matrix per CU: eight waves of 16 columns (51 against 59 us at nz 100)
 #define INV_C32(CW_, H_) hipLaunchKernelGGL((k_design_inverse_c32<CW_, H_>), grid, dim3(64 * (128 / CW_)), 0, st, nz, nzs, Hs, cshift, dshift, Out, flag, sHs, sShift, sOut, sFlag, vM, vOut, sV, vcols, vld, packed_out)
         if (grid.y <= 256) { if (cw == 8) INV_C32(8, true); else if (cw == 16) INV_C32(16, true); else INV_C32(32, true); }
         else { if (cw == 8) INV_C32(8, false); else if (cw == 16) INV_C32(16, false); else INV_C32(32, false); }

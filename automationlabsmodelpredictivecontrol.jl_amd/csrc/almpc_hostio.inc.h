@@ -45,7 +45,6 @@ int io_init_body(almpc_handle* h) {
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamCreateWithFlags(&io.s_out, hipStreamNonBlocking));
     HIP_TRY(h, hipStreamCreateWithFlags(&io.s_in, hipStreamNonBlocking));
-    { const char* up = getenv("ALMPC_X0_UPLOAD"); io.upload = up && up[0] == '1'; }
     const size_t b = (size_t)h->batch;
     for (int s = 0; s < almpc_handle::IO_DEPTH; ++s) {
         HIP_TRY(h, pinned(&io.hX0[s], b * h->n));
@@ -140,7 +139,7 @@ int almpc_update_initialization_async(almpc_handle* h, const double* x0) {
     }
     if (x0 != io.hX0[s]) std::memcpy(io.hX0[s], x0, (size_t)h->batch * h->n * sizeof(double));   // (almpc_x0_staging: already in place)
     if (io.x0_slot < 0) io.dX0_own = h->dX0;   // (the handle's own buffer is kept and freed with the handle)
-    if (io.upload) {
+    if (h->sw.x0_upload) {
         // pinned slot -> device slot on the copy-in stream (under the step that is running); everything enqueued on the compute stream
         // from here on comes after it
         HIP_TRY(h, hipSetDevice(h->device));

@@ -6,6 +6,8 @@
 // ran): the point is that no call touches memory it does not own.  Prints "host logic ok: <launches> launches".
 // With a path argument the fake runtime writes every launch there (stream ordinal, kernel, grid, block, LDS: the launch trace that
 // tests/golden/host_launch_trace.txt pins); the handles below reach every kernel of the step path at least once.
+// A second argument NAME=VALUE is one ALMPC_* switch (csrc/almpc_switches.h) the whole run is made under: its launch trace against the
+// plain one is what tests/golden/host_launch_trace_switches.txt pins per switch.
 #include "../../include/almpc.h"
 
 #include <cmath>
@@ -80,13 +82,15 @@ static int step_and_read(almpc_handle* h, int n, int m, int N, int batch, bool t
 }
 
 int main(int argc, char** argv) {
-    {   // the switches are read at call time: none may come in from the caller's environment
+    {   // every almpc_create below reads the switches: none may come in from the caller's environment
         std::vector<std::string> inherited;
         for (char** e = environ; *e; ++e)
             if (std::strncmp(*e, "ALMPC_", 6) == 0) inherited.emplace_back(*e, std::strchr(*e, '=') - *e);
         for (const std::string& name : inherited) unsetenv(name.c_str());
     }
     if (argc > 1 && fake_hip_trace_to(argv[1])) { std::fprintf(stderr, "cannot write %s\n", argv[1]); return 1; }
+    const char* const eq = argc > 2 ? std::strchr(argv[2], '=') : nullptr;
+    if (argc > 2 && (!eq || setenv(std::string(argv[2], eq - argv[2]).c_str(), eq + 1, 1))) { std::fprintf(stderr, "not NAME=VALUE: %s\n", argv[2]); return 1; }
     almpc_handle* h = nullptr;
     // ---- shared model, input box; then state box + terminal equality + S on the same handle; closed loop on the device
     {
@@ -164,16 +168,16 @@ int main(int argc, char** argv) {
     {
         const int n = 4, m = 2, N = 40, batch = 20;
         const Plant p = chain(n, m);
-        setenv("ALMPC_POLISH_NO_GLDS", "1", 1);   // (read at handle creation)
+        setenv("ALMPC_POLISH_NO_GLDS", "1", 1);   // (a handle's switches are what almpc_create finds)
+        setenv("ALMPC_EAGER_REDO", "1", 1);
         CK(almpc_create(&h, n, m, N, batch, 0, 0));
-        unsetenv("ALMPC_POLISH_NO_GLDS");
         CK(almpc_design_shared(h, p.A.data(), p.B.data(), p.Q.data(), p.R.data(), nullptr, nullptr, p.umin.data(), p.umax.data(), nullptr, nullptr, 0.1, 1e-6));
         std::vector<double> xz((size_t)n * (N + 1), 0.0), uz((size_t)m * N, 0.0);
         CK(almpc_set_reference(h, xz.data(), uz.data(), 0));
-        setenv("ALMPC_EAGER_REDO", "1", 1);
         if (step_and_read(h, n, m, N, batch, false)) return 1;
-        unsetenv("ALMPC_EAGER_REDO");
         almpc_destroy(h); h = nullptr;
+        unsetenv("ALMPC_POLISH_NO_GLDS");
+        unsetenv("ALMPC_EAGER_REDO");
     }
     // ---- per-instance models, nz = 40, no polish: k_admm_inst with the full inverse, then k_rollout<1>
     {
@@ -262,6 +266,34 @@ int main(int argc, char** argv) {
         CKG(almpc_group_get_results_wait(g, t, x.data(), nullptr, nullptr, nullptr, u0.data(), st.data(), nullptr, nullptr));
         CKG(almpc_group_advance_plant(g));
         almpc_group_destroy(g);
+    }
+    // ---- small shared problems, nz = 10: more than two instances per CU (the fake device has 256) take the two-launch path, unless
+    // ALMPC_SHARED_WAVE_MAX_BATCH moves the limit
+    {
+        const int n = 4, m = 2, N = 5, batch = 600;
+        const Plant p = chain(n, m);
+        CK(almpc_create(&h, n, m, N, batch, 0, 0));
+        CK(almpc_design_shared(h, p.A.data(), p.B.data(), p.Q.data(), p.R.data(), nullptr, nullptr, p.umin.data(), p.umax.data(), nullptr, nullptr, 0.1, 1e-6));
+        if (step_and_read(h, n, m, N, batch, false)) return 1;
+        almpc_destroy(h); h = nullptr;
+    }
+    // ---- a switch belongs to the handle, fixed when almpc_create returns: set behind it, ALMPC_NO_SHARED_WAVE does not move the first
+    // handle off k_step_inst_wave; a handle created while it is set takes the two-launch path.  (Without a switch argument only: the
+    // runs under one switch keep the environment still while a handle lives.)
+    if (argc <= 2) {
+        const int n = 4, m = 2, N = 5, batch = 8;
+        const Plant p = chain(n, m);
+        almpc_handle* h2 = nullptr;
+        CK(almpc_create(&h, n, m, N, batch, 0, 0));
+        CK(almpc_design_shared(h, p.A.data(), p.B.data(), p.Q.data(), p.R.data(), nullptr, nullptr, p.umin.data(), p.umax.data(), nullptr, nullptr, 0.1, 1e-6));
+        setenv("ALMPC_NO_SHARED_WAVE", "1", 1);
+        if (step_and_read(h, n, m, N, batch, false)) return 1;
+        if (almpc_create(&h2, n, m, N, batch, 0, 0) != ALMPC_OK) return 1;
+        unsetenv("ALMPC_NO_SHARED_WAVE");
+        almpc_destroy(h); h = h2;
+        CK(almpc_design_shared(h, p.A.data(), p.B.data(), p.Q.data(), p.R.data(), nullptr, nullptr, p.umin.data(), p.umax.data(), nullptr, nullptr, 0.1, 1e-6));
+        if (step_and_read(h, n, m, N, batch, false)) return 1;
+        almpc_destroy(h); h = nullptr;
     }
     fake_hip_trace_close();
     std::printf("host logic ok: %ld launches\n", fake_hip_launch_count());

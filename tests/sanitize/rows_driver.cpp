@@ -61,7 +61,7 @@ static bool all_zero(const std::vector<double>& v) {
 }
 
 int main() {
-    {   // the switches are read at call time: none may come in from the caller's environment
+    {   // every almpc_create below reads the switches: none may come in from the caller's environment
         std::vector<std::string> inherited;
         for (char** e = environ; *e; ++e)
             if (std::strncmp(*e, "ALMPC_", 6) == 0) inherited.emplace_back(*e, std::strchr(*e, '=') - *e);

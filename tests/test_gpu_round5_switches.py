@@ -6,7 +6,8 @@
   * the start of that redo with its inverse built in registers by k_sdual_start (ALMPC_SDUAL_NO_START_BUILD);
   * the redo enqueued gated behind the step BEFORE a synchronous look when the previous look found work (ALMPC_NO_PREDICTED_REDO);
   * the packed-triangle KKT inverse of k_admm_inst (ALMPC_NO_PACKED_MINV), even and odd nz.
-The switches are read with getenv at call time, so one process can run both sides."""
+A handle's switches are what almpc_create finds in the environment ("Diagnostic switches"); every run below creates its
+own handle, so one process can run both sides."""
 import os
 
 import numpy as np

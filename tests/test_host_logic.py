@@ -233,3 +233,27 @@ def test_julia_shim_binds_every_entry_point_of_the_header():
     missing = [n for n in names if n not in bound]
     assert not missing, f"not bound in julia/AlmpcHIP.jl: {missing}"
     assert len(names) >= 45
+
+
+def test_the_environment_is_read_in_one_place_and_the_switch_table_is_documented():
+    """csrc/almpc_switches.h: read_switches() is the only code under csrc/ that calls getenv (a handle's switches are fixed by
+    almpc_create; INTEGRATION.md, "Diagnostic switches"), and the table there lists exactly the names of the header's table."""
+    import re
+    csrc = os.path.join(ROOT, "automationlabsmodelpredictivecontrol.jl_amd", "csrc")
+    hits = []
+    for folder, _, files in os.walk(csrc):
+        for name in files:
+            for i, line in enumerate(open(os.path.join(folder, name), errors="replace"), 1):
+                if "getenv" in line:
+                    hits.append((os.path.relpath(os.path.join(folder, name), csrc), i))
+    header = open(os.path.join(csrc, "almpc_switches.h")).read()
+    reader = header[header.index("inline Switches read_switches()"):]
+    reader = reader[:reader.index("\n}\n")]
+    assert len(hits) == 1 and hits[0][0] == "almpc_switches.h" and reader.count("getenv") == 1, hits
+    names = re.findall(r"^\s*X\((ALMPC_\w+), \w+, (?:ON_IF_1|ON_IF_SET|INTEGER), \"", header, re.M)
+    assert len(names) == len(set(names)) == header.count(" X(ALMPC_") == 40
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    doc = doc[doc.index("## Diagnostic switches"):]
+    doc = doc[:doc.index("\n## ", 5)]
+    listed = re.findall(r"^\| `(ALMPC_\w+)` \|", doc, re.M)
+    assert sorted(listed) == sorted(names)

@@ -58,18 +58,15 @@ def test_host_math_dare_under_asan_ubsan(tmp_path, mo):
     assert np.abs(P - p.P).max() <= 1e-9 * np.abs(p.P).max()
 
 
-@pytest.mark.timeout(900)
-def test_host_launch_logic_of_the_c_abi_under_asan_ubsan(tmp_path):
-    """The HOST half of libalmpc.so -- argument checks, buffer sizing, staging copies, launch-parameter set-up, read-backs: everything in
-    csrc/almpc_api.hip that is not a kernel -- compiled host-only (hipcc --cuda-host-only, one translation unit) under ASan + UBSan and
-    linked against tests/sanitize/fake_hip_runtime.cpp (device memory = calloc'd host memory, so every hipMemcpy / hipMemset of the
-    launch logic is bounds-checked; launches are no-ops).  The driver walks shared, state-row, per-instance, structured, re-linearised,
-    SQP and group handles through design / set_reference / calculate / get_results, synchronously and through tickets.  (Round-4
-    review, item 9: the mid-round segfault inside design_shared is the kind of bug this finds without a GPU lease.)"""
+@pytest.fixture(scope="module")
+def host_logic_exe(tmp_path_factory):
+    """tests/sanitize/host_logic_driver.cpp on the HOST half of libalmpc.so: csrc/almpc_api.hip compiled host-only (hipcc
+    --cuda-host-only, one translation unit) under ASan + UBSan and linked against tests/sanitize/fake_hip_runtime.cpp."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     clang = "/opt/rocm/lib/llvm/bin/clang++"
     if not (os.path.exists(hipcc) and os.path.exists(clang)):
         pytest.skip("no ROCm toolchain here")
+    tmp_path = tmp_path_factory.mktemp("host_logic")
     src = os.path.join(ROOT, "automationlabsmodelpredictivecontrol.jl_amd", "csrc", "almpc_api.hip")
     api_o = str(tmp_path / "api.o")
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-std=c++17", "-fPIC", "--cuda-host-only", "-DALMPC_UNITY", "-Wno-unused-function",
@@ -88,14 +85,79 @@ def test_host_launch_logic_of_the_c_abi_under_asan_ubsan(tmp_path):
     subprocess.check_call([clang, "-std=c++17"] + SAN + ["-c", str(tmp_path / "fatbin.cpp"), "-o", o])
     exe = str(tmp_path / "host_logic_san")
     subprocess.check_call([clang] + SAN + ["-o", exe] + objs + [o, "-lpthread", "-ldl"])
-    trace = tmp_path / "launches.txt"
-    r = _run([exe, str(trace)])
+    return exe
+
+
+def _launch_trace(exe, trace, switch=None):
+    """One run of the driver (under NAME=VALUE if given): the process and its launch lines, ordered stably by the stream's creation
+    ordinal (handles of a group launch from threads of their own)."""
+    r = _run([exe, str(trace)] + ([switch] if switch else []))
+    return r, sorted(trace.read_text().splitlines(), key=lambda line: int(line.split()[0]))
+
+
+@pytest.mark.timeout(900)
+def test_host_launch_logic_of_the_c_abi_under_asan_ubsan(tmp_path, host_logic_exe):
+    """The HOST half of libalmpc.so -- argument checks, buffer sizing, staging copies, launch-parameter set-up, read-backs: everything in
+    csrc/almpc_api.hip that is not a kernel -- under ASan + UBSan against the fake runtime (device memory = calloc'd host memory, so
+    every hipMemcpy / hipMemset of the launch logic is bounds-checked; launches are no-ops).  The driver walks shared, state-row,
+    per-instance, structured, re-linearised, SQP and group handles through design / set_reference / calculate / get_results,
+    synchronously and through tickets.  (Round-4 review, item 9: the mid-round segfault inside design_shared is the kind of bug this
+    finds without a GPU lease.)"""
+    r, lines = _launch_trace(host_logic_exe, tmp_path / "launches.txt")
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     assert "ERROR" not in r.stderr and "runtime error" not in r.stderr
     assert "host logic ok" in r.stdout
     assert int(r.stdout.split("ok:")[1].split()[0]) > 150   # kernel launches were reached on every path
     # the launch sequence (stream, kernel, grid, block, LDS) is pinned: a change of launches on purpose regenerates the golden file.
-    # Handles of a group launch from threads of their own: the lines are ordered stably by the stream's creation ordinal.
-    lines = sorted(trace.read_text().splitlines(), key=lambda line: int(line.split()[0]))
     golden = (Path(ROOT) / "tests" / "golden" / "host_launch_trace.txt").read_text().splitlines()
     assert lines == golden, next(f"line {i + 1}: {a!r} != golden {b!r}" for i, (a, b) in enumerate(zip(lines + [""] * len(golden), golden + [""] * len(lines))) if a != b)
+    # the driver's last block: a switch set behind almpc_create does not reach the handle (ALMPC_NO_SHARED_WAVE=1 set between design and
+    # step: still the one-wave step), a handle created while it is set has it (the two-launch pair)
+    streams = sorted({int(line.split()[0]) for line in lines})
+    kernels = lambda st: [line.split()[1] for line in lines if int(line.split()[0]) == st]
+    live, later = kernels(streams[-2]), kernels(streams[-1])
+    assert any(k.startswith("almpc::k_step_inst_wave") for k in live) and not any(k.startswith(("almpc::k_admm", "almpc::k_polish")) for k in live)
+    assert [k.split("<")[0] for k in later[-3:-1]] == ["almpc::k_admm", "almpc::k_polish"] and not any(k.startswith("almpc::k_step_inst_wave") for k in later)
+
+
+SWITCH_VALUES = {"ALMPC_SHARED_WAVE_MAX_BATCH": "1000000000", "ALMPC_INV_CW": "8"}   # (every other switch: 1)
+# switches that reach no launch decision of the driver: ALMPC_DESIGN_TRACE prints only, ALMPC_X0_UPLOAD moves copies, the other three
+# need a step that leaves instances undecided (no kernel runs here)
+SWITCHES_WITHOUT_TRACE = {"ALMPC_DESIGN_TRACE", "ALMPC_X0_UPLOAD", "ALMPC_NO_EQ_PROJECTION", "ALMPC_NO_PREDICTED_REDO", "ALMPC_SDUAL_NO_SINV_HANDOVER"}
+
+
+@pytest.mark.timeout(900)
+def test_every_switch_steers_the_launches_it_steered_when_read_at_call_time(tmp_path, host_logic_exe):
+    """Every ALMPC_* switch of csrc/almpc_switches.h, one run of the driver each (second argument NAME=VALUE, set before the first
+    almpc_create): the launch trace, the exit status and (ALMPC_STRUCTURED_PRIMAL: the structured design refuses, the driver stops there)
+    the message are those of the last commit whose library read each variable by getenv at the call that used it, recorded with this
+    same driver in tests/golden/host_launch_trace_switches.txt as differences to the plain trace.  35 of the 40 switches change the
+    trace, and must; the five of SWITCHES_WITHOUT_TRACE reach no launch decision on a runtime that runs no kernel and are NOT covered
+    here beyond "nothing else moved" (ALMPC_NO_PREDICTED_REDO and ALMPC_SDUAL_NO_SINV_HANDOVER are held by
+    tests/test_gpu_round5_switches.py on the GPU)."""
+    import difflib
+    import re
+    header = (Path(ROOT) / "automationlabsmodelpredictivecontrol.jl_amd" / "csrc" / "almpc_switches.h").read_text()
+    names = re.findall(r"^\s*X\((ALMPC_\w+),", header, re.M)
+    assert len(names) == 40 and len(set(names)) == 40
+    fixture = (Path(ROOT) / "tests" / "golden" / "host_launch_trace_switches.txt").read_text().splitlines()
+    base_count = int(re.match(r"# base: the first (\d+) lines", [ln for ln in fixture if ln.startswith("# base:")][0]).group(1))
+    base = (Path(ROOT) / "tests" / "golden" / "host_launch_trace.txt").read_text().splitlines()[:base_count]
+    recorded, key = {}, None
+    for ln in fixture:
+        if ln.startswith("== "):
+            key = ln[3:]
+            recorded[key] = []
+        elif not ln.startswith("#"):
+            recorded[key].append(ln)
+    assert sorted(k.split("=")[0] for k in recorded) == sorted(names)
+    for name in names:
+        r, lines = _launch_trace(host_logic_exe, tmp_path / "launches.txt", f"{name}={SWITCH_VALUES.get(name, '1')}")
+        assert "runtime error" not in r.stderr and (r.returncode != 0 or "ERROR" not in r.stderr), (name, r.stderr[-3000:])   # (an early stop leaks its handle)
+        key = f"{name}={SWITCH_VALUES.get(name, '1')} exit {r.returncode}"
+        if r.returncode != 0:   # (the driver's own message: file:line call -> code (text))
+            key += " -> " + r.stderr.splitlines()[0].split(" -> ", 1)[1]
+        assert key in recorded, (key, r.stderr[-3000:])
+        diff = list(difflib.unified_diff(base, lines, n=0, lineterm=""))[2:]
+        assert diff == recorded[key], (name, next((a, b) for a, b in zip(diff + [""] * len(recorded[key]), recorded[key] + [""] * len(diff)) if a != b))
+        assert (len(diff) == 0) == (name in SWITCHES_WITHOUT_TRACE), name

@@ -24,10 +24,11 @@ int main(int argc, char** argv) {
     hipMalloc(&dA, A.size() * 8); hipMalloc(&dO, A.size() * 8); hipMalloc(&dF, b * 4);
     hipMemcpy(dA, A.data(), A.size() * 8, hipMemcpyHostToDevice); hipMemset(dO, 0, A.size() * 8); hipMemset(dF, 0, b * 4);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+    const Switches sw = read_switches();   // (ALMPC_INV_TILE, ALMPC_INV_CW)
     for (int rep = 0; rep < 3; ++rep) {
         hipEventRecord(e0, 0);
         for (int it = 0; it < 20; ++it)
-            launch_design_inverse(dim3(1, b), 520 * 8, 0, nz, nzs, dA, 0.0, nullptr, dO, dF, (long)nz * nzs, 0L, (long)nz * nzs, 1L);
+            launch_design_inverse(sw, dim3(1, b), 520 * 8, 0, nz, nzs, dA, 0.0, nullptr, dO, dF, (long)nz * nzs, 0L, (long)nz * nzs, 1L);
         hipEventRecord(e1, 0); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1);
         printf("nz %d batch %d: %.1f us per launch\n", nz, b, 1e3 * ms / 20);
