@@ -15,7 +15,7 @@ ORACLE   := oracle/_build/libalmpc_oracle.so  # generic name; oracle/c_oracle.py
 TUS      := api tu_step tu_polish_gen tu_instance tu_design_a tu_design_b tu_sdual_a tu_sdual_b tu_sdual_c
 OBJS     := $(patsubst %,$(OBJDIR)/almpc_%.o,$(TUS))
 H_K      := $(CS)/almpc_kernels.hip.h
-H_D      := $(CS)/almpc_design.hip.h $(CS)/almpc_switches.h
+H_D      := $(CS)/almpc_design.hip.h $(CS)/almpc_switches.h $(CS)/almpc_devbuf.h
 H_ALL    := $(wildcard $(CS)/*.h) $(wildcard $(CS)/instances/*.inc) include/almpc.h
 
 all: lib oracle

@@ -15,6 +15,7 @@
 #include "almpc_sdual.hip.h"
 #include "almpc_host_math.h"
 #include "almpc_switches.h"
+#include "almpc_devbuf.h"
 #include "../../include/almpc.h"
 
 // The heavy kernel templates are compiled by their own translation units (almpc_tu_*.hip, one per kernel family, built in parallel);
@@ -48,6 +49,12 @@
 
 using namespace almpc;
 
+// Memory: every device and pinned buffer of a handle is a DevBuf member (csrc/almpc_devbuf.h) and goes when the handle is deleted
+// (destroy_handle); nothing else frees.  The raw pointers below are views that own nothing:
+//   dX0                             the handle's own x0 buffer (x0_own) or a slot of the pinned x0 ring (io.x0_slot says which);
+//   io.dX0[] / io.dU0[] / io.dInts[], redo.dUnsolved   the device's addresses of pinned memory (io.hX0 / hU0 / hInts, redo.hUnsolved).
+// The iterate of an SQP loop lives in the handle's own reference buffers (dXref, dUref); rGuess is filled from another handle's
+// inputs (almpc_set_start_from) but belongs to the handle that starts from it.
 struct almpc_handle {
     int n = 0, m = 0, N = 0, batch = 0, nz = 0, nzs = 0, nrb = 0, ks = 0, ksf = 0, device = 0;
     uint32_t flags = 0;
@@ -58,99 +65,101 @@ struct almpc_handle {
     // host copies of the design (almpc_get_design)
     std::vector<double> H, F, P, d;
     // device: shared design
-    double *dMinvFrag = nullptr, *dVFrag = nullptr, *dHFrag = nullptr, *dFFrag = nullptr, *dG = nullptr;
-    double *dD = nullptr, *dUmin = nullptr, *dUmax = nullptr, *dA = nullptr, *dB = nullptr;
-    double *dXref = nullptr, *dUref = nullptr, *dFS = nullptr, *dV0S = nullptr, *dRho = nullptr;
-    size_t ref_cap[3] = {0, 0, 0};   // doubles in dXref, dUref, dFS (= dV0S) as almpc_set_reference allocated them: re-used while the sizes stay
-    double *wQ = nullptr, *wR = nullptr, *wS = nullptr;   // design weights on the device (almpc_design_batched / _ltv)
+    DevBuf<double> dMinvFrag, dVFrag, dHFrag, dFFrag, dG;
+    DevBuf<double> dD, dUmin, dUmax, dA, dB;
+    DevBuf<double> dXref, dUref, dFS, dV0S, dRho;
+    bool ref_keep = false;   // dXref, dUref, dFS, dV0S are as almpc_set_reference made them: it keeps all four while their sizes stay
+    DevBuf<double> wQ, wR, wS;   // design weights on the device (almpc_design_batched / _ltv)
     int rho_mode = 0;  // 0 scalar rho (OSQP), 1 stiffness profile rho / G_ii
     // blocked rollout of the shared model (rollout_blocked): [Gamma_s | Phi_s] rows per lane, built at design time
-    double* dRollM = nullptr;
+    DevBuf<double> dRollM;
     int roll_s = 0, roll_nb = 0;  // roll_s == 0: shape not covered (n > ROLL_NX or m > ROLL_SMX), the stage-by-stage rollout is used
     long xref_stride = 0, uref_stride = 0, fS_stride = 0;
     std::vector<double> hS;  // S weight, symmetrised (for fS with per-instance references)
     int useS = 0;            // the input-rate term is part of the cost: R[1,1] != 0 and S[1,1] != 0 (src/sub/design_mpc.jl:423-466)
     // device: per-instance state and results
-    double *dX0 = nullptr, *dXs = nullptr, *dZs = nullptr, *dYs = nullptr, *dV0 = nullptr, *dW = nullptr;
-    double *dX = nullptr, *dEx = nullptr, *dU = nullptr, *dEu = nullptr;
-    int32_t *dStatus = nullptr, *dIters = nullptr, *dPiters = nullptr, *dPerm = nullptr;
-    uint32_t* dYflags = nullptr;  // [batch][nrb] signs of the ADMM multipliers (steps run with ALMPC_OPT_NO_WARM_STATE)
+    double* dX0 = nullptr;   // view: x0_own or a slot of the pinned ring
+    DevBuf<double> x0_own, dXs, dZs, dYs, dV0, dW;
+    DevBuf<double> dX, dEx, dU, dEu;
+    DevBuf<int32_t> dStatus, dIters, dPiters, dPerm;
+    DevBuf<uint32_t> dYflags;  // [batch][nrb] signs of the ADMM multipliers (steps run with ALMPC_OPT_NO_WARM_STATE)
     bool state_valid = true;      // xs / ys hold the ADMM state of the last step (a warm start may use them)
     int num_cus = 256;            // persistent-grid size of k_polish<true>
     Switches sw;                  // the ALMPC_* diagnostic switches as almpc_create found them (csrc/almpc_switches.h): fixed for the handle's life
     int fuse_step = 1;            // one kernel per step when the shape allows (almpc_set_step_fusion; starts off with ALMPC_NO_FUSED_STEP=1)
-    double* dSglobal = nullptr;  // polish scratch for working sets beyond 32 rows
-    int32_t* dStartRows = nullptr;   // [batch][65] row list of a guessed working set whose inverse sits in dSglobal (k_guess_iterate_ws)
+    DevBuf<double> dSglobal;  // polish scratch for working sets beyond 32 rows
+    DevBuf<int32_t> dStartRows;   // [batch][65] row list of a guessed working set whose inverse sits in dSglobal (k_guess_iterate_ws)
     // state rows (state box / terminal equality): constraint-space data for k_polish_gen
     int terminal_eq = 0, has_box = 0, mc = 0, R = 0, Rs = 0, np_pairs = 0;
-    double *dGhat = nullptr, *dGnorm = nullptr, *dXmin = nullptr, *dXmax = nullptr;
-    int *dRowTraj = nullptr, *dRowEq = nullptr, *dRowXidx = nullptr, *dRowState = nullptr;
-    double* dOvfSinv = nullptr;    // [batch][32 * 32 + 32] k_polish_gen -> k_polish_gen64: inverse and bounds of a flagged instance
-    double* dVsPlain = nullptr;    // [n][nzs] V = -G F' (shared design with state rows): operand of the s0 table
-    double* dPlain = nullptr;      // small shared designs (nzs <= 64): dense [Minv | H' | F' | V] for the one-wave-per-instance step
-    double* dS0Basis = nullptr;    // [(n + 1)][Rs] PolishGenParams::s0_basis
+    DevBuf<double> dGhat, dGnorm, dXmin, dXmax;
+    DevBuf<int> dRowTraj, dRowEq, dRowXidx, dRowState;
+    DevBuf<double> dOvfSinv;    // [batch][32 * 32 + 32] k_polish_gen -> k_polish_gen64: inverse and bounds of a flagged instance
+    DevBuf<double> dVsPlain;    // [n][nzs] V = -G F' (shared design with state rows): operand of the s0 table
+    DevBuf<double> dPlain;      // small shared designs (nzs <= 64): dense [Minv | H' | F' | V] for the one-wave-per-instance step
+    DevBuf<double> dS0Basis;    // [(n + 1)][Rs] PolishGenParams::s0_basis
     bool s0_basis_ok = false;
-    int32_t* dOverflow = nullptr;  // [2 + batch] k_polish_gen: count, cursor and list of instances to redo with the 64-row build
-    int* dRowMap = nullptr;        // [N*n] state (stage k+2, i) -> state-row index or -1 (k_ghat_inst)
-    double *dGhatE = nullptr, *dWinvE = nullptr;  // shared design with the terminal equality: original rows E of Ghat, Ghat_EE^-1
+    DevBuf<int32_t> dOverflow;  // [2 + batch] k_polish_gen: count, cursor and list of instances to redo with the 64-row build
+    DevBuf<int> dRowMap;        // [N*n] state (stage k+2, i) -> state-row index or -1 (k_ghat_inst)
+    DevBuf<double> dGhatE, dWinvE;  // shared design with the terminal equality: original rows E of Ghat, Ghat_EE^-1
     int eq_proj = 0;               // dGhat is the matrix projected on the terminal equality (k_ghat_project)
     bool ghat_inst = false;        // dGhat / dGnorm hold one constraint-space matrix PER INSTANCE ([batch][R][Rs], [batch][Rs])
     std::vector<double> boxmin, boxmax;  // almpc_set_state_box: the state box of the per-instance / time-varying / SQP designs
-    double *lA = nullptr, *lB = nullptr, *lC = nullptr, *lE = nullptr;  // almpc_design_ltv with state rows: stage models, defects and
+    DevBuf<double> lA, lB, lC, lE;  // almpc_design_ltv with state rows: stage models, defects and
                                                                         // state errors kept for the step's rollouts
     // per-instance models (almpc_design_batched): persistent per-instance operands ...
     bool batched = false;
     bool ltv = false;             // almpc_design_ltv: references and gradient are part of the design
-    double* bQ = nullptr;         // [batch][nz] explicit gradient of an LTV design (unscaled)
-    double *bA = nullptr, *bB = nullptr, *bMinv = nullptr, *bG = nullptr, *bHs = nullptr, *bFs = nullptr, *bVs = nullptr,
-           *bD = nullptr, *bRho = nullptr, *bH = nullptr, *bF = nullptr;
+    DevBuf<double> bQ;         // [batch][nz] explicit gradient of an LTV design (unscaled)
+    DevBuf<double> bA, bB, bMinv, bG, bHs, bFs, bVs, bD, bRho, bH, bF;
     // ... and design temporaries kept for the next re-design (a per-step re-linearisation designs every step)
-    double *bPhi = nullptr, *bGk = nullptr, *bGam = nullptr, *bW = nullptr, *bWP = nullptr, *bP = nullptr;
-    int* bFlag = nullptr;
+    DevBuf<double> bPhi, bGk, bGam, bW, bWP, bP;
+    DevBuf<int> bFlag;
     bool batched_alloc = false;
     bool minv_packed = false;   // bMinv holds packed lower triangles (stride packed_tri_doubles): k_admm_inst<true>
     // SQP outer loop for a black-box Fnn model (almpc_sqp_fnn_*): the network, the stage data of the current linearisation
-    struct Sqp {
+    // a black-box network on the device (the SQP loop's and the re-linearisation pipeline's)
+    struct Net {
+        int H = 0, L = 0, act = 0, net = 0;   // act: activation 0..4, net: NET_* (decode_net)
+        DevBuf<double> W_in, W_h, b_h, W_out;
+    };
+    struct Sqp : Net {
         bool ready = false, started = false;
-        int H = 0, L = 0, act = 0, net = 0, useR = 0, useS = 0;   // act: activation 0..4, net: NET_* (decode_net)
+        int useR = 0, useS = 0;
         long sP = 0;
-        double *W_in = nullptr, *W_h = nullptr, *b_h = nullptr, *W_out = nullptr;
-        double *A = nullptr, *B = nullptr, *c = nullptr, *fval = nullptr, *ebar = nullptr, *qadd = nullptr;
-        double *xref = nullptr, *uref = nullptr, *Q = nullptr, *R = nullptr, *S = nullptr;
-        int* bad = nullptr;
-        double* mer = nullptr;    // [batch][4] step rule 1: step factor, merit of the last accepted point, redo flag
-        double *xback = nullptr, *uback = nullptr, *dxback = nullptr, *vback = nullptr;  // last accepted point and its step
+        DevBuf<double> A, B, c, fval, ebar, qadd;
+        DevBuf<double> xref, uref, Q, R, S;
+        DevBuf<int> bad;
+        DevBuf<double> mer;    // [batch][4] step rule 1: step factor, merit of the last accepted point, redo flag
+        DevBuf<double> xback, uback, dxback, vback;  // last accepted point and its step
         double mu = 0.0;          // merit weight of the defects
         int step_rule = 0;        // 0 fixed step, 1 merit-function safeguard (almpc_sqp_fnn_set_step_rule)
         long since_start = 0;     // iterations since almpc_sqp_fnn_start: the first one gets its guess from ADMM, the others from the iterate
         int structured_qp = 0;       // almpc_sqp_fnn_set_structured: every iteration's QP goes to k_riccati in its stage-wise form
                                      // (no condensed design at all: no Hessian build, no inverse, no m N <= 128 limit)
-        unsigned long long* stats = nullptr;  // [iters][2]
-        int stats_cap = 0;
+        DevBuf<unsigned long long> stats;  // [iters][2]
         // almpc_sqp_fnn_solve: per-instance done | iters | verdict words and the live count ([3 batch + 1]), last residuals [batch],
         // and a pinned ring of live counts the host reads two iterations behind the device
-        int* sv = nullptr;
-        double* kkt = nullptr;
-        int* live_pin = nullptr;
+        DevBuf<int> sv;
+        DevBuf<double> kkt;
+        PinBuf<int> live_pin;
         // almpc_sqp_fnn_set_hessian: 0 Gauss-Newton, 1 exact Lagrangian Hessian (multipliers [batch][N][n], stage blocks [batch][N][(n+m)^2])
         int hessian = 0;
-        double *lam = nullptr, *Wlag = nullptr;
+        DevBuf<double> lam, Wlag;
         // almpc_sqp_fnn_set_row_multipliers: the finishes hand out the state-row multipliers of every iteration's QP ([batch][N][n], zero
         // until the first solved QP); the stopping test and the exact Hessian take them into the adjoint.  Allocated when the handle has state rows.
         int row_mult = 0;
-        double* smu = nullptr;
+        DevBuf<double> smu;
     } sqp;
     // per-step re-linearisation of a black-box Fnn model on the device (almpc_relin_fnn_*, BASELINE configs[3])
-    struct Relin {
+    struct Relin : Net {
         bool ready = false;
-        int H = 0, L = 0, act = 0, net = 0, useR = 0, useS = 0;
-        double *W_in = nullptr, *W_h = nullptr, *b_h = nullptr, *W_out = nullptr;
-        double *ulin = nullptr;   // [batch][m] linearisation input of every instance (the first input reference)
-        double *Q = nullptr, *R = nullptr, *S = nullptr;
-        double *gS = nullptr;     // [nz] unscaled input-rate gradient 2 D'Sbar D u_ref of the shared reference
+        int useR = 0, useS = 0;
+        DevBuf<double> ulin;   // [batch][m] linearisation input of every instance (the first input reference)
+        DevBuf<double> Q, R, S;
+        DevBuf<double> gS;     // [nz] unscaled input-rate gradient 2 D'Sbar D u_ref of the shared reference
         bool have_prev = false;   // a step has been solved since setup: its inputs can seed the next step's working set
-        double *u0 = nullptr, *xnext = nullptr;   // [batch][m] applied inputs, [batch][n] next states (almpc_relin_fnn_advance)
-        double *Ascr = nullptr, *Bscr = nullptr;  // Jacobian outputs of the advance's forward pass (not used)
+        DevBuf<double> u0, xnext;   // [batch][m] applied inputs, [batch][n] next states (almpc_relin_fnn_advance)
+        DevBuf<double> Ascr, Bscr;  // Jacobian outputs of the advance's forward pass (not used)
         float ms_jac = 0, ms_design = 0, ms_step = 0;  // last timed step (almpc_relin_fnn_step with timing)
         hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     } relin;
@@ -171,17 +180,17 @@ struct almpc_handle {
     //  - wait_and_settle: when redo_expected, the gated redo goes out before the wait (predicted), then the count is taken as above;
     //  - drop_lazy_redo (a new design): clears lazy_pending and redo_expected, takes the count.
     struct Redo {
-        int* hUnsolved = nullptr;      // pinned host word: instances left undecided, counted by the finishes
-        int* dUnsolved = nullptr;      // the device's address of it
-        int* dGate = nullptr;          // gate word: number of the last step that left an instance undecided
+        DevBuf<int, Mem::PinnedMapped> hUnsolved;   // pinned host word: instances left undecided, counted by the finishes
+        int* dUnsolved = nullptr;      // view: the device's address of it
+        DevBuf<int> dGate;          // gate word: number of the last step that left an instance undecided
         int unsolved_seen = 0;         // the count at the last look
         int step_serial = 0;           // number of the last enqueued step (1, 2, ...)
         bool lazy_pending = false;     // the last step's redo is deferred and not yet settled
         bool expected = false;         // the last synchronous look found undecided instances (see wait_and_settle)
     } redo;
     int fallback = 2;   // 0 off, 1 asked for (a design it cannot serve is an error), 2 default: on wherever the stage-wise solvers cover the design
-    double *rQ = nullptr, *rR = nullptr, *rP = nullptr, *rKst = nullptr, *rPst = nullptr;   // device copies of Q, R (branch rule applied), shared P; gain scratch
-    double* rGuess = nullptr;   // [batch][N][m] start of the next structured solve (almpc_set_start_from / opts.warm_start), else nullptr
+    DevBuf<double> rQ, rR, rP, rKst, rPst;   // device copies of Q, R (branch rule applied), shared P; gain scratch
+    DevBuf<double> rGuess;   // [batch][N][m] start of the next structured solve (almpc_set_start_from / opts.warm_start), else nullptr
     bool guess_ready = false;   // rGuess was filled for the NEXT almpc_calculate (consumed by it)
     bool r_has_step = false;    // a structured step has run on this design: its inputs can seed a warm start
     hipEvent_t ev_guess = nullptr, ev_guess_done = nullptr;
@@ -192,37 +201,36 @@ struct almpc_handle {
     struct Sd {
         bool ready = false;
         int nt = 0, NT = 0, MC = 0;          // stage-state dimension (n, or n + m with S) and the instantiated (padded) dimensions
-        double* rec = nullptr; size_t rec_cap = 0; long rec_stride = 0, rec_kstride = 0;
-        double* base = nullptr; size_t base_cap = 0; long base_stride = 0; bool has_base = false;
-        double *xmin = nullptr, *xmax = nullptr, *eqt = nullptr;   // state box [n] (null: none), terminal-equality target [n] zeros (null: none)
+        DevBuf<double> rec; long rec_stride = 0, rec_kstride = 0;
+        DevBuf<double> base; long base_stride = 0; bool has_base = false;
+        DevBuf<double> xmin, xmax, eqt;   // state box [n] (null: none), terminal-equality target [n] zeros (null: none)
         bool has_box = false, has_eq = false, useS = false;
         bool per_instance = false;          // records per instance (k_sgains) instead of the host's shared ones
         int gain_N = 0;                     // stages k_sgains computes (1: stage-invariant records)
-        double *dQ = nullptr, *dR = nullptr, *dS = nullptr, *dP = nullptr;   // weights of k_sgains (R with the branch rule applied; dP: a shared terminal weight)
-        int* bad = nullptr;                 // [batch] k_sgains: R + B'PB not positive definite
+        DevBuf<double> dQ, dR, dS, dP;   // weights of k_sgains (R with the branch rule applied; dP: a shared terminal weight)
+        DevBuf<int> bad;                 // [batch] k_sgains: R + B'PB not positive definite
         bool sqp = false;                   // the QP of an SQP iteration: stage models, defects and cost terms of the loop (h->sqp)
-        double *pc = nullptr, *ct = nullptr;   // [batch][N][NT] P_{k+1} c_k, c_k
-        int32_t* ovf = nullptr;
-        int32_t* wsave = nullptr;   // [batch][SDUAL_WSAVE] working set of an instance that ran out of room (start of the next tier)
-        double* sinv_save = nullptr;   // [batch][sdual_sinv_doubles(SDUAL_SINV_SAVE)] its inverse (allocated at the first multi-tier solve)
+        DevBuf<double> pc, ct;   // [batch][N][NT] P_{k+1} c_k, c_k
+        DevBuf<int32_t> ovf;
+        DevBuf<int32_t> wsave;   // [batch][SDUAL_WSAVE] working set of an instance that ran out of room (start of the next tier)
+        DevBuf<double> sinv_save;   // [batch][sdual_sinv_doubles(SDUAL_SINV_SAVE)] its inverse (allocated at the first multi-tier solve)
         int tier_serial = 0;           // number of the last launch_sdual_t call (the tiers' gate value)
-        double* start_inv = nullptr;   // [batch][sdual_sinv_doubles(SDUAL_SINV_SAVE)] inverse of a redo's start (k_sdual_start; allocated at the first such redo)
-        int32_t* start_ws = nullptr;   // [batch][64] working sets the state-row finish of the LAST step gave up with (PolishGenParams::redo_ws)
+        DevBuf<double> start_inv;   // [batch][sdual_sinv_doubles(SDUAL_SINV_SAVE)] inverse of a redo's start (k_sdual_start; allocated at the first such redo)
+        DevBuf<int32_t> start_ws;   // [batch][64] working sets the state-row finish of the LAST step gave up with (PolishGenParams::redo_ws)
         bool start_ws_fresh = false;   // ... written by the last enqueued step (cleared by every step that does not run that finish)
-        double* sinv_glb = nullptr; size_t sinv_cap = 0;   // third tier: Sinv of 128 x 129 per wave of its grid
-        double* ghat = nullptr; size_t ghat_cap = 0; bool ghat_ready = false, ghat_wanted = false;   // shared model: cached sweep responses [TP][TP] (k_sdual: SdualParams::ghat)
+        DevBuf<double> sinv_glb;   // third tier: Sinv of 128 x 129 per wave of its grid
+        DevBuf<double> ghat; bool ghat_ready = false, ghat_wanted = false;   // shared model: cached sweep responses [TP][TP] (k_sdual: SdualParams::ghat)
         std::vector<double> S;               // symmetrised S (base terms of time-varying input references)
         // reachability screen of the state box (k_state_box_screen): tables of the shared model and references, verdicts per instance
-        double *scr_phi = nullptr, *scr_g = nullptr, *scr_rm = nullptr, *scr_rp = nullptr;
-        int32_t* scr_verdict = nullptr;
-        size_t scr_cap = 0;                  // N the table buffers were sized for
+        DevBuf<double> scr_phi, scr_g, scr_rm, scr_rp;
+        DevBuf<int32_t> scr_verdict;
         bool scr_ready = false;              // tables match the current model / references
     } sd;
     // multi-GPU (almpc_comm_*): this handle's rank in an RCCL communicator of one process per GPU
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;
-    long long* dComm4 = nullptr;       // [4] summary words
-    double *dU0 = nullptr, *dU0all = nullptr;  // [batch][m] packed first inputs, [world][batch][m] gathered
+    DevBuf<long long> dComm4;       // [4] summary words
+    DevBuf<double> dU0, dU0all;  // [batch][m] packed first inputs, [world][batch][m] gathered
     // host-facing step path (almpc_update_initialization_async, almpc_get_results_async / _wait, almpc_get_first_input): pinned
     // staging owned by the handle, copies on their own streams, rings of IO_DEPTH slots so that the transfers of one step run
     // under the kernel of the next (csrc/almpc_hostio.inc.h)
@@ -235,22 +243,20 @@ struct almpc_handle {
         // (393 KB over the link at its START, tools/dbg_x0_home.py), the upload costs three HIP calls and a copy-engine latency per step:
         // measured 11.7 k (upload) against 12.8 k (in place) batch-steps/s on the pipelined first-move loop, 8.3 k against 10.4 k serial
         hipStream_t s_in = nullptr;
-        double* dX0dev[IO_DEPTH] = {nullptr, nullptr};
+        DevBuf<double, Mem::DeviceTight> dX0dev[IO_DEPTH];
         hipEvent_t ev_in[IO_DEPTH] = {nullptr, nullptr};
         // x0 ring: pinned host slots the kernels read in place (dX0 = the device's address of the slot); h->dX0 points at the latest
-        double* hX0[IO_DEPTH] = {nullptr, nullptr};
-        double* dX0[IO_DEPTH] = {nullptr, nullptr};
+        PinBuf<double> hX0[IO_DEPTH];
+        double* dX0[IO_DEPTH] = {nullptr, nullptr};           // views: the device's addresses of hX0
         hipEvent_t ev_used[IO_DEPTH] = {nullptr, nullptr};   // the last step that read the slot has finished (recorded on the compute stream)
         bool used_pending[IO_DEPTH] = {false, false};
-        int x0_slot = -1;     // slot h->dX0 points at (-1: the handle's own buffer)
-        double* dX0_own = nullptr;   // the handle's own x0 buffer while h->dX0 points into the ring
+        int x0_slot = -1;     // slot h->dX0 points at (-1: the handle's own buffer, x0_own)
         long x0_count = 0;
         // result ring: ticket t lives in slot t % IO_DEPTH
-        double *hX[IO_DEPTH] = {nullptr, nullptr}, *hEx[IO_DEPTH] = {nullptr, nullptr}, *hU[IO_DEPTH] = {nullptr, nullptr},
-               *hEu[IO_DEPTH] = {nullptr, nullptr}, *hU0[IO_DEPTH] = {nullptr, nullptr};
-        int32_t* hInts[IO_DEPTH] = {nullptr, nullptr};       // pinned [3][batch]: status | iters | polish_iters
-        double* dU0[IO_DEPTH] = {nullptr, nullptr};          // the device's addresses of hU0 / hInts (the pack kernel writes the pinned
-        int32_t* dInts[IO_DEPTH] = {nullptr, nullptr};       // slots directly)
+        PinBuf<double> hX[IO_DEPTH], hEx[IO_DEPTH], hU[IO_DEPTH], hEu[IO_DEPTH], hU0[IO_DEPTH];
+        PinBuf<int32_t> hInts[IO_DEPTH];                     // pinned [3][batch]: status | iters | polish_iters
+        double* dU0[IO_DEPTH] = {nullptr, nullptr};          // views: the device's addresses of hU0 / hInts (the pack kernel writes the
+        int32_t* dInts[IO_DEPTH] = {nullptr, nullptr};       // pinned slots directly)
         hipEvent_t ev_packed[IO_DEPTH] = {nullptr, nullptr}; // compute stream: the results of the slot's step exist (copy-out stream waits)
         hipEvent_t ev_done[IO_DEPTH] = {nullptr, nullptr};   // everything the slot's request asked for has landed in pinned memory
         hipEvent_t ev_big = nullptr;                          // the last read-back of x / e_x / u / e_u has left the result buffers (the next step waits for it)
@@ -282,11 +288,6 @@ int fail(almpc_handle* h, int code, const std::string& msg) {
             return fail(h, ALMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
     } while (0)
 
-template <typename T>
-hipError_t dalloc(T** p, size_t count) {
-    return hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T) + 64);
-}
-
 int pick_ks(int nz, int nrb) {
     const int exact = (nz + 3) / 4;
     // instantiated (NRB, KS) pairs: KS = 4*NRB always; plus the exact-fit specials below
@@ -316,42 +317,25 @@ void io_free(almpc_handle* h);   // almpc_hostio.inc.h
 // through a device-side copy go back to the handle's own device buffer first.
 void io_release_x0(almpc_handle* h) {
     if (h->io.x0_slot >= 0) {
-        h->dX0 = h->io.dX0_own;
+        h->dX0 = h->x0_own;
         h->io.x0_slot = -1;
     }
 }
 
-void free_all(almpc_handle* h) {
+// The end of a handle, in this order: the host-facing side's streams and events, the other events, the communicator, then the handle
+// with every buffer it owns (DevBuf members), the stream last.
+void destroy_handle(almpc_handle* h) {
     io_free(h);
-    void* ptrs[] = {h->dMinvFrag, h->dVFrag, h->dHFrag, h->dFFrag, h->dG, h->dD, h->dUmin, h->dUmax, h->dA, h->dB,
-                    h->dXref, h->dUref, h->dFS, h->dV0S, h->dRho, h->dRollM, h->dX0, h->dXs, h->dZs, h->dYs, h->dV0, h->dW, h->dX, h->dEx,
-                    h->dU, h->dEu, h->dStatus, h->dIters, h->dPiters, h->dPerm, h->dYflags, h->dSglobal, h->dStartRows, h->dGhat, h->dGnorm, h->dXmin,
-                    h->dXmax, h->dRowTraj, h->dRowEq, h->dRowXidx, h->dRowState, h->dRowMap, h->dGhatE, h->dWinvE, h->lA, h->lB, h->lC, h->lE, h->bA, h->bB, h->bMinv, h->bG, h->bHs, h->bFs,
-                    h->bVs, h->bD, h->bRho, h->bH, h->bF, h->bPhi, h->bGk, h->bGam, h->bW, h->bWP, h->bP, h->bFlag, h->bQ, h->dOverflow, h->dOvfSinv, h->dVsPlain, h->dPlain, h->dS0Basis, h->wQ, h->wR, h->wS,
-                    h->sqp.W_in, h->sqp.W_h, h->sqp.b_h, h->sqp.W_out, h->sqp.A, h->sqp.B, h->sqp.c, h->sqp.fval, h->sqp.ebar,
-                    h->sqp.qadd, h->sqp.xref, h->sqp.uref, h->sqp.Q, h->sqp.R, h->sqp.S, h->sqp.bad, h->sqp.stats, h->sqp.mer, h->sqp.xback, h->sqp.uback, h->sqp.dxback, h->sqp.vback,
-                    h->sqp.sv, h->sqp.kkt, h->sqp.lam, h->sqp.Wlag, h->sqp.smu};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (h->sqp.live_pin) (void)hipHostFree(h->sqp.live_pin);
-    for (void* p : {(void*)h->relin.W_in, (void*)h->relin.W_h, (void*)h->relin.b_h, (void*)h->relin.W_out, (void*)h->relin.ulin,
-                    (void*)h->relin.Q, (void*)h->relin.R, (void*)h->relin.S, (void*)h->relin.gS, (void*)h->relin.u0, (void*)h->relin.xnext, (void*)h->relin.Ascr, (void*)h->relin.Bscr})
-        if (p) (void)hipFree(p);
     for (auto& e : h->relin.ev)
         if (e) (void)hipEventDestroy(e);
     if (h->comm && rccl_api().ok) (void)rccl_api().CommDestroy(h->comm);
-    for (void* p : {(void*)h->dComm4, (void*)h->dU0, (void*)h->dU0all, (void*)h->rQ, (void*)h->rR, (void*)h->rP, (void*)h->rKst, (void*)h->rPst, (void*)h->rGuess,
-                    (void*)h->sd.rec, (void*)h->sd.base, (void*)h->sd.xmin, (void*)h->sd.xmax, (void*)h->sd.eqt, (void*)h->sd.ovf, (void*)h->sd.wsave, (void*)h->sd.sinv_glb, (void*)h->sd.ghat, (void*)h->sd.dQ, (void*)h->sd.dR, (void*)h->sd.dS, (void*)h->sd.dP, (void*)h->sd.bad, (void*)h->sd.pc, (void*)h->sd.ct,
-                    (void*)h->sd.sinv_save, (void*)h->sd.start_inv, (void*)h->sd.start_ws, (void*)h->sd.scr_phi, (void*)h->sd.scr_g, (void*)h->sd.scr_rm, (void*)h->sd.scr_rp, (void*)h->sd.scr_verdict})
-        if (p) (void)hipFree(p);
     if (h->ev_guess) (void)hipEventDestroy(h->ev_guess);
     if (h->ev_guess_done) (void)hipEventDestroy(h->ev_guess_done);
-    if (h->redo.hUnsolved) (void)hipHostFree(h->redo.hUnsolved);
-    if (h->redo.dGate) (void)hipFree(h->redo.dGate);
     for (auto& e : h->ev)
         if (e) (void)hipEventDestroy(e);
-    h->ev.clear();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    const hipStream_t stream = h->stream;
+    delete h;
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 // State rows of a design: the state box for stages 2..N+1 (stage 1 is x0 itself, checked per instance) and / or the terminal
@@ -378,27 +362,23 @@ int setup_state_rows(almpc_handle* h, const double* xmin, const double* xmax, bo
     h->R = nz + h->mc;
     h->np_pairs = (h->R + 127) / 128;
     h->Rs = 128 * h->np_pairs;
-    for (void* q : {(void*)h->dGhat, (void*)h->dGnorm, (void*)h->dXmin, (void*)h->dXmax, (void*)h->dRowTraj, (void*)h->dRowEq,
-                    (void*)h->dRowXidx, (void*)h->dRowState, (void*)h->dRowMap})
-        if (q) (void)hipFree(q);
-    h->dGhat = h->dGnorm = h->dXmin = h->dXmax = nullptr;
-    h->dRowTraj = h->dRowEq = h->dRowXidx = h->dRowState = h->dRowMap = nullptr;
+    h->dGhat.reset(); h->dGnorm.reset(); h->dXmin.reset(); h->dXmax.reset();
+    h->dRowTraj.reset(); h->dRowEq.reset(); h->dRowXidx.reset(); h->dRowState.reset(); h->dRowMap.reset();
     h->ghat_inst = false;
-    if (h->dGhatE) { (void)hipFree(h->dGhatE); h->dGhatE = nullptr; }
-    if (h->dWinvE) { (void)hipFree(h->dWinvE); h->dWinvE = nullptr; }
+    h->dGhatE.reset(); h->dWinvE.reset();
     h->eq_proj = 0;
     if (h->mc == 0) return ALMPC_OK;
     if (h->np_pairs > 4) return fail(h, ALMPC_ERR_UNSUPPORTED, "design: state rows need n*N + m*N <= 512");
     if ((size_t)(N + 1) * (n + m) > 32 * 32) return fail(h, ALMPC_ERR_UNSUPPORTED, "design: state rows need (N+1)*(n+m) <= 1024");
     if (per_instance && n > 32) return fail(h, ALMPC_ERR_UNSUPPORTED, "design: state rows with per-instance models need n <= 32");
     const size_t copies = per_instance ? (size_t)h->batch : 1;
-    HIP_TRY(h, dalloc(&h->dGhat, copies * h->R * h->Rs));
-    HIP_TRY(h, dalloc(&h->dGnorm, copies * h->Rs));
+    HIP_TRY(h, h->dGhat.alloc(copies * h->R * h->Rs));
+    HIP_TRY(h, h->dGnorm.alloc(copies * h->Rs));
     if (per_instance) HIP_TRY(h, hipMemset(h->dGhat, 0, copies * h->R * h->Rs * sizeof(double)));  // (the padding columns stay zero)
-    HIP_TRY(h, dalloc(&h->dXmin, (size_t)n)); HIP_TRY(h, dalloc(&h->dXmax, (size_t)n));
-    HIP_TRY(h, dalloc(&h->dRowTraj, (size_t)h->Rs)); HIP_TRY(h, dalloc(&h->dRowEq, (size_t)h->Rs));
-    HIP_TRY(h, dalloc(&h->dRowXidx, (size_t)h->Rs)); HIP_TRY(h, dalloc(&h->dRowState, (size_t)h->Rs));
-    HIP_TRY(h, dalloc(&h->dRowMap, rowmap.size()));
+    HIP_TRY(h, h->dXmin.alloc((size_t)n)); HIP_TRY(h, h->dXmax.alloc((size_t)n));
+    HIP_TRY(h, h->dRowTraj.alloc((size_t)h->Rs)); HIP_TRY(h, h->dRowEq.alloc((size_t)h->Rs));
+    HIP_TRY(h, h->dRowXidx.alloc((size_t)h->Rs)); HIP_TRY(h, h->dRowState.alloc((size_t)h->Rs));
+    HIP_TRY(h, h->dRowMap.alloc(rowmap.size()));
     HIP_TRY(h, hipMemcpy(h->dRowMap, rowmap.data(), rowmap.size() * sizeof(int), hipMemcpyHostToDevice));
     auto up = [&](int* dst, const std::vector<int>& v, int fill) {
         std::vector<int> full((size_t)h->Rs, fill);
@@ -443,17 +423,17 @@ int riccati_weights(almpc_handle* h, const hm::mat& Qm, const hm::mat& Rm, const
     for (int j = 0; j < m; ++j)
         for (int i = 0; i < j; ++i) { const double v = 0.5 * (Rs[(size_t)j * m + i] + Rs[(size_t)i * m + j]); Rs[(size_t)j * m + i] = Rs[(size_t)i * m + j] = v; }
     if (Rm[0] == 0.0) std::fill(Rs.begin(), Rs.end(), 0.0);
-    if (!h->rQ) HIP_TRY(h, dalloc(&h->rQ, (size_t)n * n));
-    if (!h->rR) HIP_TRY(h, dalloc(&h->rR, (size_t)m * m));
+    HIP_TRY(h, h->rQ.once((size_t)n * n));
+    HIP_TRY(h, h->rR.once((size_t)m * m));
     HIP_TRY(h, hipMemcpy(h->rQ, Qs.data(), Qs.size() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->rR, Rs.data(), Rs.size() * sizeof(double), hipMemcpyHostToDevice));
     if (Pshared) {
-        if (!h->rP) HIP_TRY(h, dalloc(&h->rP, (size_t)n * n));
+        HIP_TRY(h, h->rP.once((size_t)n * n));
         HIP_TRY(h, hipMemcpy(h->rP, Pshared, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (!h->rKst) HIP_TRY(h, dalloc(&h->rKst, (size_t)h->batch * h->N * ((size_t)n * m + m)));
-    if (!h->rPst && (size_t)h->batch * h->N * ((size_t)n * n + n) * sizeof(double) <= ((size_t)8 << 30))   // value functions of the last sweep
-        HIP_TRY(h, dalloc(&h->rPst, (size_t)h->batch * h->N * ((size_t)n * n + n)));
+    HIP_TRY(h, h->rKst.once((size_t)h->batch * h->N * ((size_t)n * m + m)));
+    if ((size_t)h->batch * h->N * ((size_t)n * n + n) * sizeof(double) <= ((size_t)8 << 30))   // value functions of the last sweep
+        HIP_TRY(h, h->rPst.once((size_t)h->batch * h->N * ((size_t)n * n + n)));
     return ALMPC_OK;
 }
 
@@ -560,24 +540,20 @@ int sdual_setup_shared(almpc_handle* h, const hm::mat& Am, const hm::mat& Bm, co
         return fail(h, ALMPC_ERR_NUMERIC, "stage-wise solve: R + B'PB is singular (Riccati recursion of the unconstrained problem)");
     const size_t stage = (size_t)sdual_rec_stage(sd.NT, sd.MC);
     const size_t cnt = inv ? stage : stage * N;
-    if (sd.rec_cap < cnt) {
-        if (sd.rec) { (void)hipFree(sd.rec); sd.rec = nullptr; }
-        HIP_TRY(h, dalloc(&sd.rec, cnt));
-        sd.rec_cap = cnt;
-    }
+    HIP_TRY(h, sd.rec.grow(cnt));
     HIP_TRY(h, hipMemcpy(sd.rec, rec.data() + (inv ? stage * (N - 1) : 0), cnt * sizeof(double), hipMemcpyHostToDevice));
     sd.rec_stride = 0;
     sd.rec_kstride = inv ? 0 : (long)stage;
     sd.has_box = xmin != nullptr;
     if (sd.has_box) {
-        if (!sd.xmin) HIP_TRY(h, dalloc(&sd.xmin, (size_t)n));
-        if (!sd.xmax) HIP_TRY(h, dalloc(&sd.xmax, (size_t)n));
+        HIP_TRY(h, sd.xmin.once((size_t)n));
+        HIP_TRY(h, sd.xmax.once((size_t)n));
         HIP_TRY(h, hipMemcpy(sd.xmin, xmin, n * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(sd.xmax, xmax, n * sizeof(double), hipMemcpyHostToDevice));
     }
     sd.has_eq = terminal_eq;
-    if (!sd.ovf) HIP_TRY(h, dalloc(&sd.ovf, (size_t)h->batch + 2));   // (+ the tiers' gate word: SdualParams::ovf_gate)
-    if (!sd.wsave) HIP_TRY(h, dalloc(&sd.wsave, (size_t)h->batch * SDUAL_WSAVE));
+    HIP_TRY(h, sd.ovf.once((size_t)h->batch + 2));   // (+ the tiers' gate word: SdualParams::ovf_gate)
+    HIP_TRY(h, sd.wsave.once((size_t)h->batch * SDUAL_WSAVE));
     HIP_TRY(h, hipMemset(sd.ovf, 0, ((size_t)h->batch + 2) * sizeof(int32_t)));
     sd.S = Sm ? *Sm : hm::mat();
     sd.has_base = false; sd.base_stride = 0;
@@ -604,13 +580,9 @@ hipError_t sdual_build_ghat(almpc_handle* h) {
     sd.ghat_wanted = false;   // (one attempt per design)
     const size_t TP = (size_t)sdual_tp(sd.NT, sd.MC, h->N);
     if (TP * TP * sizeof(double) > ((size_t)256 << 20)) return hipSuccess;
-    if (sd.ghat_cap < TP * TP) {
-        if (sd.ghat) { (void)hipFree(sd.ghat); sd.ghat = nullptr; sd.ghat_cap = 0; }
-        hipError_t e = dalloc(&sd.ghat, TP * TP);
-        if (e != hipSuccess) return e;
-        sd.ghat_cap = TP * TP;
-    }
-    hipError_t e = hipMemsetAsync(sd.ghat, 0, TP * TP * sizeof(double), h->stream);
+    hipError_t e = sd.ghat.grow(TP * TP);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(sd.ghat, 0, TP * TP * sizeof(double), h->stream);
     if (e != hipSuccess) return e;
     SolveMode build;
     build.build_ghat = true;
@@ -642,11 +614,7 @@ int sdual_update_base(almpc_handle* h, const double* uref, size_t cnt) {
                 base[c * TP + (size_t)k * SP + sd.NT + a] -= sv;
             }
     if (!any) return ALMPC_OK;
-    if (sd.base_cap < base.size()) {
-        if (sd.base) { (void)hipFree(sd.base); sd.base = nullptr; }
-        HIP_TRY(h, dalloc(&sd.base, base.size()));
-        sd.base_cap = base.size();
-    }
+    HIP_TRY(h, sd.base.grow(base.size()));
     HIP_TRY(h, hipMemcpy(sd.base, base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice));
     sd.has_base = true;
     sd.base_stride = cnt > 1 ? (long)TP : 0;
@@ -668,37 +636,33 @@ int sdual_setup_batched(almpc_handle* h, const hm::mat& Qm, const hm::mat& Rm, c
     if ((size_t)sgains_lds_doubles(sd.nt, m) * sizeof(double) > 160 * 1024) return fail(h, ALMPC_ERR_UNSUPPORTED, "stage-wise solve: the gain recursion does not fit LDS");
     hm::mat Qs = Qm, Rs = Rm;
     if (Rm[0] == 0.0) std::fill(Rs.begin(), Rs.end(), 0.0);
-    if (!sd.dQ) HIP_TRY(h, dalloc(&sd.dQ, (size_t)n * n));
-    if (!sd.dR) HIP_TRY(h, dalloc(&sd.dR, (size_t)m * m));
+    HIP_TRY(h, sd.dQ.once((size_t)n * n));
+    HIP_TRY(h, sd.dR.once((size_t)m * m));
     HIP_TRY(h, hipMemcpy(sd.dQ, Qs.data(), Qs.size() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(sd.dR, Rs.data(), Rs.size() * sizeof(double), hipMemcpyHostToDevice));
     if (Sm) {
-        if (!sd.dS) HIP_TRY(h, dalloc(&sd.dS, (size_t)m * m));
+        HIP_TRY(h, sd.dS.once((size_t)m * m));
         HIP_TRY(h, hipMemcpy(sd.dS, Sm->data(), Sm->size() * sizeof(double), hipMemcpyHostToDevice));
     }
     const size_t stage = (size_t)sdual_rec_stage(sd.NT, sd.MC);
     sd.gain_N = invariant ? 1 : N;
     const size_t cnt = (size_t)h->batch * sd.gain_N * stage;
-    if (sd.rec_cap < cnt) {
-        if (sd.rec) { (void)hipFree(sd.rec); sd.rec = nullptr; }
-        HIP_TRY(h, dalloc(&sd.rec, cnt));
-        sd.rec_cap = cnt;
-    }
+    HIP_TRY(h, sd.rec.grow(cnt));
     sd.rec_stride = (long)(sd.gain_N * stage);
     sd.rec_kstride = invariant ? 0 : (long)stage;
     sd.per_instance = true; sd.sqp = false;
     sd.has_box = xmin != nullptr;
     if (sd.has_box) {
-        if (!sd.xmin) HIP_TRY(h, dalloc(&sd.xmin, (size_t)n));
-        if (!sd.xmax) HIP_TRY(h, dalloc(&sd.xmax, (size_t)n));
+        HIP_TRY(h, sd.xmin.once((size_t)n));
+        HIP_TRY(h, sd.xmax.once((size_t)n));
         HIP_TRY(h, hipMemcpy(sd.xmin, xmin, n * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(sd.xmax, xmax, n * sizeof(double), hipMemcpyHostToDevice));
     }
     sd.has_eq = terminal_eq;
-    if (!sd.ovf) HIP_TRY(h, dalloc(&sd.ovf, (size_t)h->batch + 2));   // (+ the tiers' gate word: SdualParams::ovf_gate)
+    HIP_TRY(h, sd.ovf.once((size_t)h->batch + 2));   // (+ the tiers' gate word: SdualParams::ovf_gate)
     HIP_TRY(h, hipMemset(sd.ovf, 0, ((size_t)h->batch + 2) * sizeof(int32_t)));
-    if (!sd.wsave) HIP_TRY(h, dalloc(&sd.wsave, (size_t)h->batch * SDUAL_WSAVE));
-    if (!sd.bad) HIP_TRY(h, dalloc(&sd.bad, (size_t)h->batch));
+    HIP_TRY(h, sd.wsave.once((size_t)h->batch * SDUAL_WSAVE));
+    HIP_TRY(h, sd.bad.once((size_t)h->batch));
     HIP_TRY(h, hipMemset(sd.bad, 0, (size_t)h->batch * sizeof(int)));
     sd.S = Sm ? *Sm : hm::mat();
     sd.has_base = false; sd.base_stride = 0;
@@ -758,10 +722,8 @@ hipError_t launch_sdual_t(almpc_handle* h, SdualParams sp, int tier0, int tier1)
     // many rows); tier 3: the same with Sinv in a global scratch, for shapes whose trajectories leave no room for it in LDS.
     // (tier0 = tier1 = 1: ONE launch with room for SD_WCAP2 rows -- the redo of the few instances a condensed step left unsolved)
     if (tier1 > tier0 && sp.wsave && !sp.build_ghat && !h->sw.sdual_no_sinv_handover) {   // tiers hand each other the inverse of their working set
-        if (!h->sd.sinv_save) {
-            const hipError_t e_ = dalloc(&h->sd.sinv_save, (size_t)h->batch * sdual_sinv_doubles(SDUAL_SINV_SAVE));
-            if (e_ != hipSuccess) return e_;
-        }
+        const hipError_t e_ = h->sd.sinv_save.once((size_t)h->batch * sdual_sinv_doubles(SDUAL_SINV_SAVE));
+        if (e_ != hipSuccess) return e_;
         sp.sinv_save = h->sd.sinv_save;
     }
     // the later tiers return at once unless an earlier one of THIS call ran out of room (it stores the call's number in the gate word):
@@ -806,13 +768,8 @@ hipError_t launch_sdual_t(almpc_handle* h, SdualParams sp, int tier0, int tier1)
             else hipLaunchKernelGGL((k_sdual<NT, MC, 2, false, false>), dim3(wgs), dim3(64 * waves), lds, h->stream, sp);
         } else {
             sp.ghat = nullptr;   // (the global-scratch build has no cached-response variant: sweeps)
-            const size_t need = (size_t)wgs * waves * sdual_sinv_doubles(SD_WCAP4);
-            if (h->sd.sinv_cap < need) {
-                if (h->sd.sinv_glb) { (void)hipFree(h->sd.sinv_glb); h->sd.sinv_glb = nullptr; h->sd.sinv_cap = 0; }
-                e = dalloc(&h->sd.sinv_glb, need);
-                if (e != hipSuccess) return e;
-                h->sd.sinv_cap = need;
-            }
+            e = h->sd.sinv_glb.grow((size_t)wgs * waves * sdual_sinv_doubles(SD_WCAP4));
+            if (e != hipSuccess) return e;
             sp.sinv_glb = h->sd.sinv_glb;
             e = ensure_dyn_lds(reinterpret_cast<const void*>(k_sdual<NT, MC, 2, true>), lds);
             if (e != hipSuccess) return e;
@@ -883,13 +840,11 @@ hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int ma
         almpc_handle::Sd& sdw = h->sd;
         const size_t n_ = (size_t)h->n, m_ = (size_t)h->m, N_ = (size_t)h->N;
         hipError_t e;
-        if (sdw.scr_cap < N_) {
-            for (double** q : {&sdw.scr_phi, &sdw.scr_g, &sdw.scr_rm, &sdw.scr_rp}) if (*q) { (void)hipFree(*q); *q = nullptr; }
-            if ((e = dalloc(&sdw.scr_phi, N_ * n_ * n_)) != hipSuccess || (e = dalloc(&sdw.scr_g, N_ * n_ * m_)) != hipSuccess ||
-                (e = dalloc(&sdw.scr_rm, N_ * n_)) != hipSuccess || (e = dalloc(&sdw.scr_rp, N_ * n_)) != hipSuccess) return e;
-            sdw.scr_cap = N_; sdw.scr_ready = false;
-        }
-        if (!sdw.scr_verdict && (e = dalloc(&sdw.scr_verdict, (size_t)h->batch)) != hipSuccess) return e;
+        if (sdw.scr_phi.size() < N_ * n_ * n_ || sdw.scr_g.size() < N_ * n_ * m_ || sdw.scr_rm.size() < N_ * n_ || sdw.scr_rp.size() < N_ * n_)
+            sdw.scr_ready = false;   // (a table is made or replaced below)
+        if ((e = sdw.scr_phi.grow(N_ * n_ * n_)) != hipSuccess || (e = sdw.scr_g.grow(N_ * n_ * m_)) != hipSuccess ||
+            (e = sdw.scr_rm.grow(N_ * n_)) != hipSuccess || (e = sdw.scr_rp.grow(N_ * n_)) != hipSuccess ||
+            (e = sdw.scr_verdict.once((size_t)h->batch)) != hipSuccess) return e;
         ScreenParams cp;
         cp.n = h->n; cp.m = h->m; cp.N = h->N; cp.batch = h->batch;
         cp.A = h->dA; cp.B = h->dB; cp.umin = h->dUmin; cp.umax = h->dUmax; cp.uref = h->dUref;
@@ -928,10 +883,8 @@ hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int ma
     // responses before the solve: k_sdual_start (csrc/almpc_sdual.hip.h)
     if (sp.start_ws && sp.ghat && tier0 >= 1 && !h->sw.sdual_no_start_build) {
         almpc_handle::Sd& sdw = h->sd;
-        if (!sdw.start_inv) {
-            const hipError_t e_ = dalloc(&sdw.start_inv, (size_t)h->batch * sdual_sinv_doubles(SDUAL_SINV_SAVE));
-            if (e_ != hipSuccess) return e_;
-        }
+        const hipError_t ea = sdw.start_inv.once((size_t)h->batch * sdual_sinv_doubles(SDUAL_SINV_SAVE));
+        if (ea != hipSuccess) return ea;
         SdualStartParams tp;
         std::memset(&tp, 0, sizeof(tp));
         tp.batch = h->batch; tp.n = h->n; tp.N = h->N; tp.SP = sd.NT + sd.MC; tp.TP = sdual_tp(sd.NT, sd.MC, h->N);
@@ -973,7 +926,7 @@ int resolve_lazy_redo(almpc_handle* h) {
     if (!r.lazy_pending) return ALMPC_OK;
     r.lazy_pending = false;
     if (!r.hUnsolved) return ALMPC_OK;
-    const int cur = *reinterpret_cast<volatile int*>(r.hUnsolved);
+    const int cur = *reinterpret_cast<volatile int*>(r.hUnsolved.get());
     r.expected = cur != r.unsolved_seen;
     if (cur == r.unsolved_seen) return ALMPC_OK;
     r.unsolved_seen = cur;
@@ -1023,7 +976,7 @@ int wait_and_settle(almpc_handle* h, bool blocking_only = false) {
     if (blocking_only) HIP_TRY(h, hipStreamSynchronize(h->stream));
     else HIP_TRY(h, stream_wait_polling(h));
     if (predicted) {
-        const int cur = *reinterpret_cast<volatile int*>(r.hUnsolved);
+        const int cur = *reinterpret_cast<volatile int*>(r.hUnsolved.get());
         r.expected = cur != r.unsolved_seen;
         r.unsolved_seen = cur;
         return ALMPC_OK;
@@ -1035,7 +988,7 @@ int wait_and_settle(almpc_handle* h, bool blocking_only = false) {
 void drop_lazy_redo(almpc_handle* h) {
     h->redo.lazy_pending = false;
     h->redo.expected = false;
-    if (h->redo.hUnsolved) h->redo.unsolved_seen = *reinterpret_cast<volatile int*>(h->redo.hUnsolved);
+    if (h->redo.hUnsolved) h->redo.unsolved_seen = *reinterpret_cast<volatile int*>(h->redo.hUnsolved.get());
 }
 
 // Lanes of the rollout fused into a finish: g lanes per trajectory row, cpl columns per lane (a power of two); fits: the trajectory
@@ -1058,7 +1011,7 @@ int build_s0_basis(almpc_handle* h) {
     if (h->mc <= 0 || h->batched || h->ltv || h->structured || !h->dVsPlain || !h->dRowTraj || h->sw.no_s0_basis) return ALMPC_OK;
     const RollGeom roll = roll_geom(h);
     if (!roll.fits) return ALMPC_OK;
-    if (!h->dS0Basis) HIP_TRY(h, dalloc(&h->dS0Basis, (size_t)(h->n + 1) * h->Rs));
+    HIP_TRY(h, h->dS0Basis.once((size_t)(h->n + 1) * h->Rs));
     S0BasisParams bp;
     bp.n = h->n; bp.m = h->m; bp.N = h->N; bp.nz = h->nz; bp.nzs = h->nzs; bp.R = h->R; bp.Rs = h->Rs; bp.roll_g = roll.g; bp.roll_cpl = roll.cpl;
     bp.A = h->dA; bp.B = h->dB; bp.Vs = h->dVsPlain; bp.v0S = (h->dV0S && h->fS_stride == 0) ? h->dV0S : nullptr; bp.dvec = h->dD;
@@ -1114,8 +1067,7 @@ int almpc_create(almpc_handle** out, int n, int m, int N, int batch, int device_
     h->ksf = (n + 3) / 4;
     auto bail = [&](int code, const std::string& msg) {
         std::fprintf(stderr, "almpc_create: %s\n", msg.c_str());
-        free_all(h);
-        delete h;
+        destroy_handle(h);
         return code;
     };
 #define TRY(call)                                                                  \
@@ -1132,32 +1084,32 @@ int almpc_create(almpc_handle** out, int n, int m, int N, int batch, int device_
     }
     const size_t fr = (size_t)h->nrb * h->ks * 64, b = (size_t)batch;
     if (structured) {   // no condensed matrices: models, references, inputs / outputs and the gain scratch only
-        TRY(dalloc(&h->dUmin, (size_t)m)); TRY(dalloc(&h->dUmax, (size_t)m));
-        TRY(dalloc(&h->dA, (size_t)n * n)); TRY(dalloc(&h->dB, (size_t)n * m));
-        TRY(dalloc(&h->dX0, b * n));
-        TRY(dalloc(&h->dX, b * n * (N + 1))); TRY(dalloc(&h->dEx, b * n * (N + 1)));
-        TRY(dalloc(&h->dU, b * h->nz)); TRY(dalloc(&h->dEu, b * h->nz));
-        TRY(dalloc(&h->dStatus, b)); TRY(dalloc(&h->dIters, b)); TRY(dalloc(&h->dPiters, b));
+        TRY(h->dUmin.alloc((size_t)m)); TRY(h->dUmax.alloc((size_t)m));
+        TRY(h->dA.alloc((size_t)n * n)); TRY(h->dB.alloc((size_t)n * m));
+        TRY(h->x0_own.alloc(b * n)); h->dX0 = h->x0_own;
+        TRY(h->dX.alloc(b * n * (N + 1))); TRY(h->dEx.alloc(b * n * (N + 1)));
+        TRY(h->dU.alloc(b * h->nz)); TRY(h->dEu.alloc(b * h->nz));
+        TRY(h->dStatus.alloc(b)); TRY(h->dIters.alloc(b)); TRY(h->dPiters.alloc(b));
         TRY(hipMemset(h->dIters, 0, b * sizeof(int32_t)));
         TRY(hipMemset(h->dX0, 0, b * n * sizeof(double)));
         *out = h;
         return ALMPC_OK;
     }
-    TRY(dalloc(&h->dMinvFrag, fr)); TRY(dalloc(&h->dVFrag, (size_t)h->nrb * h->ksf * 64)); TRY(dalloc(&h->dHFrag, fr));
-    TRY(dalloc(&h->dFFrag, (size_t)h->nrb * h->ksf * 64));
-    TRY(dalloc(&h->dG, (size_t)h->nz * h->nzs));
-    TRY(dalloc(&h->dD, (size_t)h->nzs)); TRY(dalloc(&h->dRho, (size_t)h->nzs)); TRY(dalloc(&h->dUmin, (size_t)m)); TRY(dalloc(&h->dUmax, (size_t)m));
-    TRY(dalloc(&h->dA, (size_t)n * n)); TRY(dalloc(&h->dB, (size_t)n * m));
-    TRY(dalloc(&h->dX0, b * n));
-    TRY(dalloc(&h->dXs, b * h->nzs)); TRY(dalloc(&h->dZs, b * h->nzs)); TRY(dalloc(&h->dYs, b * h->nzs));
-    TRY(dalloc(&h->dV0, b * h->nzs)); TRY(dalloc(&h->dW, b * h->nzs));
-    TRY(dalloc(&h->dX, b * n * (N + 1))); TRY(dalloc(&h->dEx, b * n * (N + 1)));
-    TRY(dalloc(&h->dU, b * h->nz)); TRY(dalloc(&h->dEu, b * h->nz));
-    TRY(dalloc(&h->dSglobal, b * POLISH_GLB_PER_INST));
-    TRY(dalloc(&h->dPerm, ((b + 15) / 16) * 16));
+    TRY(h->dMinvFrag.alloc(fr)); TRY(h->dVFrag.alloc((size_t)h->nrb * h->ksf * 64)); TRY(h->dHFrag.alloc(fr));
+    TRY(h->dFFrag.alloc((size_t)h->nrb * h->ksf * 64));
+    TRY(h->dG.alloc((size_t)h->nz * h->nzs));
+    TRY(h->dD.alloc((size_t)h->nzs)); TRY(h->dRho.alloc((size_t)h->nzs)); TRY(h->dUmin.alloc((size_t)m)); TRY(h->dUmax.alloc((size_t)m));
+    TRY(h->dA.alloc((size_t)n * n)); TRY(h->dB.alloc((size_t)n * m));
+    TRY(h->x0_own.alloc(b * n)); h->dX0 = h->x0_own;
+    TRY(h->dXs.alloc(b * h->nzs)); TRY(h->dZs.alloc(b * h->nzs)); TRY(h->dYs.alloc(b * h->nzs));
+    TRY(h->dV0.alloc(b * h->nzs)); TRY(h->dW.alloc(b * h->nzs));
+    TRY(h->dX.alloc(b * n * (N + 1))); TRY(h->dEx.alloc(b * n * (N + 1)));
+    TRY(h->dU.alloc(b * h->nz)); TRY(h->dEu.alloc(b * h->nz));
+    TRY(h->dSglobal.alloc(b * POLISH_GLB_PER_INST));
+    TRY(h->dPerm.alloc(((b + 15) / 16) * 16));
     TRY(hipMemset(h->dPerm, 0xFF, ((b + 15) / 16) * 16 * sizeof(int32_t)));
-    TRY(dalloc(&h->dStatus, b)); TRY(dalloc(&h->dIters, b)); TRY(dalloc(&h->dPiters, b));
-    TRY(dalloc(&h->dYflags, b * h->nrb));
+    TRY(h->dStatus.alloc(b)); TRY(h->dIters.alloc(b)); TRY(h->dPiters.alloc(b));
+    TRY(h->dYflags.alloc(b * h->nrb));
     TRY(hipMemset(h->dXs, 0, b * h->nzs * sizeof(double)));
     TRY(hipMemset(h->dZs, 0, b * h->nzs * sizeof(double)));
     TRY(hipMemset(h->dYs, 0, b * h->nzs * sizeof(double)));
@@ -1171,8 +1123,7 @@ void almpc_destroy(almpc_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    free_all(h);
-    delete h;
+    destroy_handle(h);
 }
 
 int almpc_set_rho_profile(almpc_handle* h, int mode) {
@@ -1226,7 +1177,7 @@ int almpc_set_start_from(almpc_handle* h, almpc_handle* src) {
     if (src->n != h->n || src->m != h->m || src->batch != h->batch || src->N > h->N || src->device != h->device)
         return fail(h, ALMPC_ERR_INVALID, "set_start_from: the source must have the same n, m, batch and device and a horizon <= this handle's");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->rGuess) HIP_TRY(h, dalloc(&h->rGuess, (size_t)h->batch * h->nz));
+    HIP_TRY(h, h->rGuess.once((size_t)h->batch * h->nz));
     if (!h->ev_guess) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_guess, hipEventDisableTiming));
     // the source's last step must be done before its inputs are read on this handle's stream (no host wait)
     HIP_TRY(h, hipEventRecord(h->ev_guess, src->stream));
@@ -1327,8 +1278,8 @@ int almpc_design_shared(almpc_handle* h, const double* A, const double* B, const
         for (int i = 0; i < n; ++i)
             if (h->has_box || (h->terminal_eq && k == N - 1)) rowsel.push_back(k * n + i);
     h->s0_basis_ok = false;
-    if (!rowsel.empty() && !h->dVsPlain) HIP_TRY(h, dalloc(&h->dVsPlain, (size_t)n * h->nzs));
-    if (h->nzs <= 64 && !h->dPlain) HIP_TRY(h, dalloc(&h->dPlain, 2 * (size_t)h->nz * h->nzs + 2 * (size_t)n * h->nzs));
+    if (!rowsel.empty()) HIP_TRY(h, h->dVsPlain.once((size_t)n * h->nzs));
+    if (h->nzs <= 64) HIP_TRY(h, h->dPlain.once(2 * (size_t)h->nz * h->nzs + 2 * (size_t)n * h->nzs));
     int rc = design_shared_device(h->stream, n, m, N, h->nzs, h->nrb, h->ks, h->ksf, Am, Bm, Qm, Rm, Sm, Pm, rho, sigma,
                                   h->dMinvFrag, h->dVFrag, h->dHFrag, h->dFFrag, h->dG, h->dD, h->H, h->F, h->d, h->err,
                                   rowsel, h->Rs, h->dGhat, h->dGnorm, h->rho_mode, h->dRho, rowsel.empty() ? nullptr : h->dVsPlain,
@@ -1354,15 +1305,14 @@ int almpc_design_shared(almpc_handle* h, const double* A, const double* B, const
             std::vector<double> Wrow((size_t)ne * ne);
             for (int a = 0; a < ne; ++a)
                 for (int e = 0; e < ne; ++e) Wrow[(size_t)a * ne + e] = Winv[(size_t)e * ne + a];
-            double* dY = nullptr;
-            HIP_TRY(h, dalloc(&h->dGhatE, GE.size())); HIP_TRY(h, dalloc(&h->dWinvE, Wrow.size())); HIP_TRY(h, dalloc(&dY, Y.size()));
+            DevBuf<double> dY;
+            HIP_TRY(h, h->dGhatE.alloc(GE.size())); HIP_TRY(h, h->dWinvE.alloc(Wrow.size())); HIP_TRY(h, dY.alloc(Y.size()));
             HIP_TRY(h, hipMemcpy(h->dGhatE, GE.data(), GE.size() * sizeof(double), hipMemcpyHostToDevice));
             HIP_TRY(h, hipMemcpy(h->dWinvE, Wrow.data(), Wrow.size() * sizeof(double), hipMemcpyHostToDevice));
             HIP_TRY(h, hipMemcpy(dY, Y.data(), Y.size() * sizeof(double), hipMemcpyHostToDevice));
             hipLaunchKernelGGL(k_ghat_project, dim3(512), dim3(256), 0, h->stream, h->R, Rs, ne, eq0, h->dGhatE, dY, h->dGhat, h->dGnorm);
             HIP_TRY(h, hipGetLastError());
             HIP_TRY(h, hipStreamSynchronize(h->stream));
-            (void)hipFree(dY);
             h->eq_proj = 1;
         }
     }
@@ -1388,8 +1338,7 @@ int almpc_design_shared(almpc_handle* h, const double* A, const double* B, const
                         for (int a = 0; a < m; ++a) M[(size_t)(t * m + a) * 64 + lane] = ApB[j - t][(size_t)a * n + i];
                     for (int c = 0; c < n; ++c) M[(size_t)(ROLL_SMX + c) * 64 + lane] = Apow[j + 1][(size_t)c * n + i];
                 }
-            if (h->dRollM) { (void)hipFree(h->dRollM); h->dRollM = nullptr; }
-            HIP_TRY(h, dalloc(&h->dRollM, M.size()));
+            HIP_TRY(h, h->dRollM.alloc(M.size()));
             HIP_TRY(h, hipMemcpy(h->dRollM, M.data(), M.size() * sizeof(double), hipMemcpyHostToDevice));
             h->roll_s = sblk; h->roll_nb = (N + sblk - 1) / sblk;
         }
@@ -1445,21 +1394,21 @@ int ensure_batched_alloc(almpc_handle* h) {
     const int njf = (n + 15) / 16, ps = 16 * njf, gs = nzs;
     const int kr = ((n * N + HESS_KC - 1) / HESS_KC) * HESS_KC;
     if (!h->batched_alloc) {
-        HIP_TRY(h, dalloc(&h->bA, b * n * n)); HIP_TRY(h, dalloc(&h->bB, b * n * m));
-        HIP_TRY(h, dalloc(&h->bMinv, b * nz * nzs)); HIP_TRY(h, dalloc(&h->bG, b * nz * nzs)); HIP_TRY(h, dalloc(&h->bHs, b * nz * nzs));
-        HIP_TRY(h, dalloc(&h->bFs, b * n * nzs)); HIP_TRY(h, dalloc(&h->bVs, b * n * nzs));
-        HIP_TRY(h, dalloc(&h->bD, b * nzs)); HIP_TRY(h, dalloc(&h->bRho, b * nzs));
-        HIP_TRY(h, dalloc(&h->bH, b * nz * nz)); HIP_TRY(h, dalloc(&h->bF, b * nz * n));
+        HIP_TRY(h, h->bA.alloc(b * n * n)); HIP_TRY(h, h->bB.alloc(b * n * m));
+        HIP_TRY(h, h->bMinv.alloc(b * nz * nzs)); HIP_TRY(h, h->bG.alloc(b * nz * nzs)); HIP_TRY(h, h->bHs.alloc(b * nz * nzs));
+        HIP_TRY(h, h->bFs.alloc(b * n * nzs)); HIP_TRY(h, h->bVs.alloc(b * n * nzs));
+        HIP_TRY(h, h->bD.alloc(b * nzs)); HIP_TRY(h, h->bRho.alloc(b * nzs));
+        HIP_TRY(h, h->bH.alloc(b * nz * nz)); HIP_TRY(h, h->bF.alloc(b * nz * n));
         if (design_instance_lds_doubles(n, m, N) * sizeof(double) > 160 * 1024) {  // dense route only: Gamma panels in HBM
-            HIP_TRY(h, dalloc(&h->bPhi, b * N * n * n)); HIP_TRY(h, dalloc(&h->bGk, b * N * n * m));
-            HIP_TRY(h, dalloc(&h->bGam, b * kr * gs)); HIP_TRY(h, dalloc(&h->bW, b * kr * gs)); HIP_TRY(h, dalloc(&h->bWP, b * kr * ps));
+            HIP_TRY(h, h->bPhi.alloc(b * N * n * n)); HIP_TRY(h, h->bGk.alloc(b * N * n * m));
+            HIP_TRY(h, h->bGam.alloc(b * kr * gs)); HIP_TRY(h, h->bW.alloc(b * kr * gs)); HIP_TRY(h, h->bWP.alloc(b * kr * ps));
             // padding rows / columns of the row-major panels stay zero for the lifetime of the handle
             HIP_TRY(h, hipMemset(h->bGam, 0, b * kr * gs * sizeof(double)));
             HIP_TRY(h, hipMemset(h->bW, 0, b * kr * gs * sizeof(double)));
             HIP_TRY(h, hipMemset(h->bWP, 0, b * kr * ps * sizeof(double)));
         }
-        HIP_TRY(h, dalloc(&h->bP, b * n * n));
-        HIP_TRY(h, dalloc(&h->bFlag, b));
+        HIP_TRY(h, h->bP.alloc(b * n * n));
+        HIP_TRY(h, h->bFlag.alloc(b));
         HIP_TRY(h, hipMemset(h->bHs, 0, b * nz * nzs * sizeof(double)));
         HIP_TRY(h, hipMemset(h->bFs, 0, b * n * nzs * sizeof(double)));
         HIP_TRY(h, hipMemset(h->bVs, 0, b * n * nzs * sizeof(double)));
@@ -1550,6 +1499,16 @@ static const char* net_name(int net) {
 // growing blocks (include/almpc.h)
 static size_t net_wh_doubles(int net, int H, int L) { return net == NET_DENSENET ? densenet_wh_offset(H, L) : (size_t)L * H * H; }
 static size_t net_wout_doubles(int net, int n, int H, int L) { return (size_t)n * H * (net == NET_DENSENET ? L + 1 : 1); }
+// The network of an SQP loop / a re-linearisation pipeline: its shape and fresh device copies of its weights
+static hipError_t upload_net(almpc_handle::Net& q, int n, int m, int H, int L, int act, int net, const double* W_in, const double* W_h,
+                             const double* b_h, const double* W_out) {
+    q.H = H; q.L = L; q.act = act; q.net = net;
+    hipError_t e = q.W_in.upload(W_in, (size_t)H * (n + m));
+    if (e == hipSuccess) e = q.W_h.upload(W_h, net_wh_doubles(net, H, L));
+    if (e == hipSuccess) e = q.b_h.upload(b_h, (size_t)L * H);
+    if (e == hipSuccess) e = q.W_out.upload(W_out, net_wout_doubles(net, n, H, L));
+    return e;
+}
 // The instantiation of a network kernel for the kind net (NET_*, from decode_net): pick(std::integral_constant<int, NET>()) at
 // NET = net, as in  with_net(net, [](auto k) { return k_fnn_rollout<k>; })
 template <class Pick>
@@ -1737,9 +1696,9 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
                 std::copy(Pm.begin(), Pm.end(), Pall.begin() + i * n * n);
             }
         }
-        if (!h->bA) HIP_TRY(h, dalloc(&h->bA, b * n * n));
-        if (!h->bB) HIP_TRY(h, dalloc(&h->bB, b * n * m));
-        if (!h->bP) HIP_TRY(h, dalloc(&h->bP, b * n * n));
+        HIP_TRY(h, h->bA.once(b * n * n));
+        HIP_TRY(h, h->bB.once(b * n * m));
+        HIP_TRY(h, h->bP.once(b * n * n));
         HIP_TRY(h, hipMemcpy(h->bA, A_batch, b * n * n * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(h->bB, B_batch, b * n * m * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(h->bP, Pall.data(), Pall.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -1832,15 +1791,14 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
     { const int rc_ = ensure_batched_alloc(h); if (rc_ != ALMPC_OK) return rc_; }
     hipStream_t st = h->stream;
     tr("state rows + allocation");
-    if (!h->wQ) HIP_TRY(h, dalloc(&h->wQ, (size_t)n * n));
-    if (!h->wR) HIP_TRY(h, dalloc(&h->wR, (size_t)m * m));
-    if (!h->wS) HIP_TRY(h, dalloc(&h->wS, (size_t)m * m));
+    HIP_TRY(h, h->wQ.once((size_t)n * n));
+    HIP_TRY(h, h->wR.once((size_t)m * m));
+    HIP_TRY(h, h->wS.once((size_t)m * m));
     double *dQ = h->wQ, *dR = h->wR, *dS = h->wS;   // (kept with the handle: three hipMalloc + hipFree per design cost 0.15 ms)
-    auto release = [&]() {};
 #define BTRY(call)                                                                                                  \
     do {                                                                                                            \
         hipError_t e_ = (call);                                                                                     \
-        if (e_ != hipSuccess) { release(); return fail(h, ALMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } \
+        if (e_ != hipSuccess) return fail(h, ALMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
     BTRY(hipMemcpyAsync(h->bA, A_batch, b * n * n * sizeof(double), hipMemcpyHostToDevice, st));
     BTRY(hipMemcpyAsync(h->bB, B_batch, b * n * m * sizeof(double), hipMemcpyHostToDevice, st));
@@ -1852,40 +1810,35 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
     tr("weights alloc + copies queued");
     const DesignStrides ds = batched_strides(h, p_inst);
     const unsigned gb = (unsigned)b;
-    double *dAll = nullptr, *dBll = nullptr, *dC = nullptr, *dE = nullptr, *dQa = nullptr;  // LTV staging (freed below)
     if (ltv) {
-        auto upl = [&](double** d, const double* src, size_t cnt) -> hipError_t {
-            hipError_t e = dalloc(d, cnt);
-            if (e == hipSuccess) e = hipMemcpyAsync(*d, src, cnt * sizeof(double), hipMemcpyHostToDevice, st);
-            return e;
-        };
-        hipError_t e = upl(&dAll, ltv->A_all, b * N * n * n);
-        if (e == hipSuccess) e = upl(&dBll, ltv->B_all, b * N * n * m);
-        if (e == hipSuccess && ltv->c_all) e = upl(&dC, ltv->c_all, b * N * n);
-        if (e == hipSuccess) e = upl(&dE, ltv->ebar, b * N * n);
-        if (e == hipSuccess) e = upl(&dQa, ltv->qadd, b * nz);
-        if (e == hipSuccess && !h->bQ) e = dalloc(&h->bQ, b * nz);
-        if (e == hipSuccess) e = hipMemsetAsync(h->bF, 0, b * nz * n * sizeof(double), st);
-        if (e == hipSuccess) {
-            DesignLtvParams lp;
-            lp.n = n; lp.m = m; lp.N = N; lp.nz = nz; lp.useR = useR; lp.useS = useS;
-            lp.A = dAll; lp.B = dBll; lp.c = dC; lp.ebar = dE; lp.P = h->bP; lp.sP = ds.P; lp.Q = dQ; lp.R = dR; lp.S = dS;
-            lp.qadd = dQa; lp.H = h->bH; lp.q = h->bQ;
-            e = launch_design_ltv(h, lp, st);
+        hipError_t e;
+        {
+            DevBuf<double> dAll, dBll, dC, dE, dQa;  // LTV staging (released at the end of this block)
+            e = dAll.upload_async(ltv->A_all, b * N * n * n, st);
+            if (e == hipSuccess) e = dBll.upload_async(ltv->B_all, b * N * n * m, st);
+            if (e == hipSuccess && ltv->c_all) e = dC.upload_async(ltv->c_all, b * N * n, st);
+            if (e == hipSuccess) e = dE.upload_async(ltv->ebar, b * N * n, st);
+            if (e == hipSuccess) e = dQa.upload_async(ltv->qadd, b * nz, st);
+            if (e == hipSuccess) e = h->bQ.once(b * nz);
+            if (e == hipSuccess) e = hipMemsetAsync(h->bF, 0, b * nz * n * sizeof(double), st);
+            if (e == hipSuccess) {
+                DesignLtvParams lp;
+                lp.n = n; lp.m = m; lp.N = N; lp.nz = nz; lp.useR = useR; lp.useS = useS;
+                lp.A = dAll; lp.B = dBll; lp.c = dC; lp.ebar = dE; lp.P = h->bP; lp.sP = ds.P; lp.Q = dQ; lp.R = dR; lp.S = dS;
+                lp.qadd = dQa; lp.H = h->bH; lp.q = h->bQ;
+                e = launch_design_ltv(h, lp, st);
+            }
+            if (e == hipSuccess && h->mc > 0) {   // (needs G_i, d_i: the factor step comes first when there are state rows)
+                launch_batched_factor(h, ds, rho, sigma, st, false);
+                e = launch_ghat_inst(h, dAll, dBll);
+            }
+            if (e == hipSuccess) e = hipStreamSynchronize(st);  // the staging buffers are released right away
+            h->lA.reset(); h->lB.reset(); h->lC.reset(); h->lE.reset();
+            if (e == hipSuccess && h->mc > 0) {   // ... except with state rows: the step rolls the stage models out
+                h->lA = std::move(dAll); h->lB = std::move(dBll); h->lC = std::move(dC); h->lE = std::move(dE);
+            }
         }
-        if (e == hipSuccess && h->mc > 0) {   // (needs G_i, d_i: the factor step comes first when there are state rows)
-            launch_batched_factor(h, ds, rho, sigma, st, false);
-            e = launch_ghat_inst(h, dAll, dBll);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(st);  // the staging buffers are released right away
-        for (double** q : {&h->lA, &h->lB, &h->lC, &h->lE})
-            if (*q) { (void)hipFree(*q); *q = nullptr; }
-        if (e == hipSuccess && h->mc > 0) {   // ... except with state rows: the step rolls the stage models out
-            h->lA = dAll; h->lB = dBll; h->lC = dC; h->lE = dE;
-            dAll = dBll = dC = dE = nullptr;
-        }
-        (void)hipFree(dAll); (void)hipFree(dBll); (void)hipFree(dC); (void)hipFree(dE); (void)hipFree(dQa);
-        if (e != hipSuccess) { release(); return fail(h, ALMPC_ERR_HIP, std::string("design_ltv: ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(h, ALMPC_ERR_HIP, std::string("design_ltv: ") + hipGetErrorString(e));
         if (h->mc == 0) launch_batched_factor(h, ds, rho, sigma, st, false);
         launch_neg_gm_batched(st, gb, nz, nzs, n, h->bG, h->bFs, h->bVs, ds.G, ds.Fs);
         BTRY(hipGetLastError());
@@ -1904,8 +1857,6 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
     BTRY(hipStreamSynchronize(st));
     tr("device done");
 #undef BTRY
-    release();
-    tr("weights freed");
     for (size_t i = 0; i < b; ++i)
         if (flags[i] != 0)
             return fail(h, ALMPC_ERR_NUMERIC, "design_batched: instance " + std::to_string(i) +
@@ -1963,7 +1914,7 @@ int relin_setup_structured(almpc_handle* h, int H, int L, int net, int activatio
                            const double* W_out, const double* xref, const double* uref, const double* Q, const double* R, const double* S,
                            const double* P, const double* umin, const double* umax) {
     const int n = h->n, m = h->m, N = h->N, nz = h->nz;
-    const size_t b = (size_t)h->batch, nin = (size_t)n + m;
+    const size_t b = (size_t)h->batch;
     if (fnn_wave_scratch_doubles(n, m, H, L, net) * sizeof(double) > 160 * 1024)
         return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup: the network's forward-mode Jacobian must fit the 160 KB of LDS");
     for (int i = 0; i < m; ++i)
@@ -1985,25 +1936,17 @@ int relin_setup_structured(almpc_handle* h, int H, int L, int net, int activatio
     if (!sdual_shape_ok(n, m, N, useS))
         return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup (structured): n (+ m with an input-rate weight) <= 48, m <= 16 and (N + 1)(n + m) <= 4096");
     almpc_handle::Relin& q = h->relin;
-    for (void* p_ : {(void*)q.W_in, (void*)q.W_h, (void*)q.b_h, (void*)q.W_out, (void*)q.ulin, (void*)q.Q, (void*)q.R, (void*)q.S, (void*)q.gS})
-        if (p_) (void)hipFree(p_);
-    q.W_in = q.W_h = q.b_h = q.W_out = q.ulin = q.Q = q.R = q.S = q.gS = nullptr;
-    auto up = [&](double** d, const double* src, size_t cnt) -> hipError_t {
-        hipError_t e = dalloc(d, cnt ? cnt : 1);
-        if (e == hipSuccess && src && cnt) e = hipMemcpy(*d, src, cnt * sizeof(double), hipMemcpyHostToDevice);
-        return e;
-    };
+    q.Q.reset(); q.R.reset(); q.S.reset(); q.gS.reset();   // (the network and ulin are replaced by their uploads below)
     std::vector<double> xr((size_t)n * (N + 1), 0.0), ur((size_t)nz, 0.0);
     if (xref) xr.assign(xref, xref + xr.size());
     if (uref) ur.assign(uref, uref + ur.size());
     std::vector<double> ul(b * m);
     for (size_t i = 0; i < b; ++i)
         for (int a = 0; a < m; ++a) ul[i * m + a] = ur[a];  // every instance linearises at the first input reference
-    HIP_TRY(h, up(&q.W_in, W_in, (size_t)H * nin)); HIP_TRY(h, up(&q.W_h, W_h, net_wh_doubles(net, H, L))); HIP_TRY(h, up(&q.b_h, b_h, (size_t)L * H));
-    HIP_TRY(h, up(&q.W_out, W_out, net_wout_doubles(net, n, H, L))); HIP_TRY(h, up(&q.ulin, ul.data(), ul.size()));
-    if (!h->bA) HIP_TRY(h, dalloc(&h->bA, b * n * n));
-    if (!h->bB) HIP_TRY(h, dalloc(&h->bB, b * n * m));
-    if (!h->bP) HIP_TRY(h, dalloc(&h->bP, b * n * n));
+    HIP_TRY(h, upload_net(q, n, m, H, L, activation, net, W_in, W_h, b_h, W_out)); HIP_TRY(h, q.ulin.upload(ul.data(), ul.size()));
+    HIP_TRY(h, h->bA.once(b * n * n));
+    HIP_TRY(h, h->bB.once(b * n * m));
+    HIP_TRY(h, h->bP.once(b * n * n));
     HIP_TRY(h, hipMemset(h->bA, 0, b * n * n * sizeof(double)));
     HIP_TRY(h, hipMemset(h->bB, 0, b * n * m * sizeof(double)));
     HIP_TRY(h, hipMemcpy(h->bP, Pm.data(), Pm.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -2022,9 +1965,9 @@ int relin_setup_structured(almpc_handle* h, int H, int L, int net, int activatio
     h->has_box = h->boxmin.empty() ? 0 : 1;
     for (auto& e : q.ev)
         if (!e) HIP_TRY(h, hipEventCreate(&e));
-    q.H = H; q.L = L; q.act = activation; q.net = net; q.have_prev = false; q.useR = Rm[0] != 0.0; q.useS = useS;
-    if (!q.u0) HIP_TRY(h, dalloc(&q.u0, b * m));
-    if (!q.xnext) HIP_TRY(h, dalloc(&q.xnext, b * n));
+    q.have_prev = false; q.useR = Rm[0] != 0.0; q.useS = useS;
+    HIP_TRY(h, q.u0.once(b * m));
+    HIP_TRY(h, q.xnext.once(b * n));
     h->r_has_step = false;
     h->designed = true;
     const int rc_ref = almpc_set_reference(h, xr.data(), ur.data(), 0);   // (also the input-rate terms of a horizon-varying u_ref: sdual_update_base)
@@ -2269,7 +2212,7 @@ int step_admm_or_guess(Step& s, bool* guess_ws = nullptr) {
     } else if (s.mode.guess == Guess::FromIterate && h->nzs <= 128 && h->nzs > 64 && h->batch <= 2 * h->num_cus && h->dSglobal && h->bG &&
                !h->sw.no_guess_ws) {
         // the guess of an SQP iteration AND the inverse of its working set (33..64 of the inputs on a bound), four waves per instance
-        if (!h->dStartRows) HIP_TRY(h, dalloc(&h->dStartRows, (size_t)h->batch * 65));
+        HIP_TRY(h, h->dStartRows.once((size_t)h->batch * 65));
         GuessWsParams gw;
         gw.G = h->bG; gw.G_stride = (long)h->nz * h->nzs; gw.sinv = h->dSglobal; gw.rows = h->dStartRows;
         hipLaunchKernelGGL(k_guess_iterate_ws, dim3((unsigned)h->batch), dim3(256), 0, st, ip, gw);
@@ -2351,13 +2294,13 @@ int step_state_rows(Step& s) {
     gp.zs = h->dZs; gp.ys = h->dYs; gp.v0 = h->dV0; gp.status = h->dStatus; gp.piters = h->dPiters;
     gp.max_iter = o.polish_max_iter > 0 ? o.polish_max_iter : 20 * h->R + 50;
     gp.roll_g = s.roll.g; gp.roll_cpl = s.roll.cpl; gp.roll = s.rp;
-    if (!h->dOverflow) HIP_TRY(h, dalloc(&h->dOverflow, (size_t)h->batch * 33 + 2));   // list, then [batch][32] working sets
+    HIP_TRY(h, h->dOverflow.once((size_t)h->batch * 33 + 2));   // list, then [batch][32] working sets
     HIP_TRY(h, hipMemsetAsync(h->dOverflow, 0, 2 * sizeof(int32_t), h->stream));
-    if (!h->dOvfSinv) HIP_TRY(h, dalloc(&h->dOvfSinv, (size_t)h->batch * (32 * 32 + 32)));
+    HIP_TRY(h, h->dOvfSinv.once((size_t)h->batch * (32 * 32 + 32)));
     gp.ovf = h->dOverflow; gp.ovf_ws = h->dOverflow + 2 + h->batch; gp.ovf_sinv = h->dOvfSinv;
     if (s.lazy_redo) { gp.unsolved = h->redo.dUnsolved; gp.redo_gate = h->redo.dGate; gp.step_serial = h->redo.step_serial; }
     if (h->fallback && !h->ltv && h->sd.ready && !h->sd.sqp && !h->sw.no_redo_start) {   // a stage-wise redo may follow: it starts from what this finish gives up with
-        if (!h->sd.start_ws) HIP_TRY(h, dalloc(&h->sd.start_ws, (size_t)h->batch * 64));
+        HIP_TRY(h, h->sd.start_ws.once((size_t)h->batch * 64));
         gp.redo_ws = h->sd.start_ws; gp.redo_sp = h->sd.NT + h->sd.MC; gp.redo_nt = h->sd.NT;
         h->sd.start_ws_fresh = true;
     }
@@ -2476,7 +2419,7 @@ int step_structured(almpc_handle* h, const almpc_opts& o) {
     const double* guess = nullptr;
     if (h->guess_ready) { guess = h->rGuess; h->guess_ready = false; }   // almpc_set_start_from: consumed by this step
     else if (o.warm_start && h->r_has_step) {   // receding horizon: the previous step's inputs shifted by one stage (the last stage repeated)
-        if (!h->rGuess) HIP_TRY(h, dalloc(&h->rGuess, (size_t)h->batch * h->nz));
+        HIP_TRY(h, h->rGuess.once((size_t)h->batch * h->nz));
         const long cnt = (long)h->batch * h->nz;
         hipLaunchKernelGGL(k_guess_from_inputs, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, h->batch, h->m, h->N, h->N, 1,
                            (const double*)h->dU, (const double*)h->dUref, h->uref_stride, h->rGuess);
@@ -2515,10 +2458,10 @@ int step_redo(Step& s) {
 hipError_t ensure_unsolved_word(almpc_handle* h) {
     almpc_handle::Redo& r = h->redo;
     if (r.hUnsolved) return hipSuccess;
-    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&r.hUnsolved), sizeof(int), hipHostMallocMapped);
-    if (e != hipSuccess) { r.hUnsolved = nullptr; return e; }
+    hipError_t e = r.hUnsolved.alloc(1);
+    if (e != hipSuccess) return e;
     *r.hUnsolved = 0; r.unsolved_seen = 0;
-    if ((e = dalloc(&r.dGate, 1)) != hipSuccess) return e;
+    if ((e = r.dGate.alloc(1)) != hipSuccess) return e;
     if ((e = hipMemset(r.dGate, 0, sizeof(int))) != hipSuccess) return e;   // (step numbers start at 1)
     return hipHostGetDevicePointer(reinterpret_cast<void**>(&r.dUnsolved), r.hUnsolved, 0);
 }
@@ -2674,7 +2617,7 @@ static int relin_net_setup(almpc_handle* h, bool dense, int H, int L, int activa
     if (h->structured) return relin_setup_structured(h, H, L, net, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, umin, umax);
     if (!(rho > 0.0) || !(sigma >= 0.0)) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: rho must be > 0 and sigma >= 0");
     const int n = h->n, m = h->m, N = h->N, nz = h->nz;
-    const size_t b = (size_t)h->batch, nin = (size_t)n + m;
+    const size_t b = (size_t)h->batch;
     if (fnn_wave_scratch_doubles(n, m, H, L, net) * sizeof(double) > 160 * 1024)
         return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup: the network's forward-mode Jacobian must fit the 160 KB of LDS");
     for (int i = 0; i < m; ++i)
@@ -2694,14 +2637,7 @@ static int relin_net_setup(almpc_handle* h, bool dense, int H, int L, int activa
     const hm::mat Qm = sym(Q, n), Rm = sym(R, m), Sm = sym(S, m), Pm = sym(P, n);
     { const int rc_ = ensure_batched_alloc(h); if (rc_ != ALMPC_OK) return rc_; }
     almpc_handle::Relin& q = h->relin;
-    for (void* p_ : {(void*)q.W_in, (void*)q.W_h, (void*)q.b_h, (void*)q.W_out, (void*)q.ulin, (void*)q.Q, (void*)q.R, (void*)q.S, (void*)q.gS})
-        if (p_) (void)hipFree(p_);
-    q.W_in = q.W_h = q.b_h = q.W_out = q.ulin = q.Q = q.R = q.S = q.gS = nullptr;
-    auto up = [&](double** d, const double* src, size_t cnt) -> hipError_t {
-        hipError_t e = dalloc(d, cnt ? cnt : 1);
-        if (e == hipSuccess && src && cnt) e = hipMemcpy(*d, src, cnt * sizeof(double), hipMemcpyHostToDevice);
-        return e;
-    };
+    q.Q.reset(); q.R.reset(); q.S.reset(); q.gS.reset();   // (the network and ulin are replaced by their uploads below)
     std::vector<double> xr((size_t)n * (N + 1), 0.0), ur((size_t)nz, 0.0);
     if (xref) xr.assign(xref, xref + xr.size());
     if (uref) ur.assign(uref, uref + ur.size());
@@ -2719,26 +2655,23 @@ static int relin_net_setup(almpc_handle* h, bool dense, int H, int L, int activa
     std::vector<double> ul(b * m);
     for (size_t i = 0; i < b; ++i)
         for (int a = 0; a < m; ++a) ul[i * m + a] = ur[a];  // every instance linearises at the first input reference
-    HIP_TRY(h, up(&q.W_in, W_in, (size_t)H * nin)); HIP_TRY(h, up(&q.W_h, W_h, net_wh_doubles(net, H, L))); HIP_TRY(h, up(&q.b_h, b_h, (size_t)L * H));
-    HIP_TRY(h, up(&q.W_out, W_out, net_wout_doubles(net, n, H, L))); HIP_TRY(h, up(&q.ulin, ul.data(), ul.size()));
-    HIP_TRY(h, up(&q.Q, Qm.data(), Qm.size())); HIP_TRY(h, up(&q.R, Rm.data(), Rm.size())); HIP_TRY(h, up(&q.S, Sm.data(), Sm.size()));
-    HIP_TRY(h, up(&q.gS, gS.data(), gS.size()));
+    HIP_TRY(h, upload_net(q, n, m, H, L, activation, net, W_in, W_h, b_h, W_out)); HIP_TRY(h, q.ulin.upload(ul.data(), ul.size()));
+    HIP_TRY(h, q.Q.upload(Qm.data(), Qm.size())); HIP_TRY(h, q.R.upload(Rm.data(), Rm.size())); HIP_TRY(h, q.S.upload(Sm.data(), Sm.size()));
+    HIP_TRY(h, q.gS.upload(gS.data(), gS.size()));
     HIP_TRY(h, hipMemcpy(h->bP, Pm.data(), Pm.size() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->dUmin, umin, m * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->dUmax, umax, m * sizeof(double), hipMemcpyHostToDevice));
     // shared references; the scaled input-rate gradient fS_i = d_i .* gS and v0S_i = -G_i fS_i are per instance (re-made every step)
-    for (double** pp_ : {&h->dXref, &h->dUref, &h->dFS, &h->dV0S})
-        if (*pp_) { (void)hipFree(*pp_); *pp_ = nullptr; }
-    h->ref_cap[0] = h->ref_cap[1] = h->ref_cap[2] = 0;
-    HIP_TRY(h, up(&h->dXref, xr.data(), xr.size())); HIP_TRY(h, up(&h->dUref, ur.data(), ur.size()));
-    HIP_TRY(h, dalloc(&h->dFS, b * nz)); HIP_TRY(h, dalloc(&h->dV0S, b * nz));
+    h->ref_keep = false;
+    HIP_TRY(h, h->dXref.upload(xr.data(), xr.size())); HIP_TRY(h, h->dUref.upload(ur.data(), ur.size()));
+    HIP_TRY(h, h->dFS.alloc(b * nz)); HIP_TRY(h, h->dV0S.alloc(b * nz));
     HIP_TRY(h, hipMemset(h->dFS, 0, b * nz * sizeof(double))); HIP_TRY(h, hipMemset(h->dV0S, 0, b * nz * sizeof(double)));
     h->xref_stride = 0; h->uref_stride = 0; h->fS_stride = nz;
     for (auto& e : q.ev)
         if (!e) HIP_TRY(h, hipEventCreate(&e));
-    q.H = H; q.L = L; q.act = activation; q.net = net; q.have_prev = false;
-    if (!q.u0) HIP_TRY(h, dalloc(&q.u0, b * m));
-    if (!q.xnext) HIP_TRY(h, dalloc(&q.xnext, b * n));
+    q.have_prev = false;
+    HIP_TRY(h, q.u0.once(b * m));
+    HIP_TRY(h, q.xnext.once(b * n));
     h->P = Pm; h->hS = Sm; h->useS = q.useS;
     h->rho = rho; h->sigma = sigma;
     { const int rc_ = setup_state_rows(h, h->boxmin.empty() ? nullptr : h->boxmin.data(), h->boxmax.empty() ? nullptr : h->boxmax.data(), true);
@@ -2878,7 +2811,7 @@ int almpc_relin_fnn_advance(almpc_handle* h) {
     fp.x = h->dX0; fp.u = q.u0; fp.ppi = 1; fp.xs_group = n; fp.us_group = m;
     // (the Jacobians of the forward pass go to a scratch of their own: the model slots keep the last step's linearisations, which a
     // lazily deferred redo of that step still needs)
-    if (!q.Ascr) { HIP_TRY(h, dalloc(&q.Ascr, (size_t)h->batch * n * n)); HIP_TRY(h, dalloc(&q.Bscr, (size_t)h->batch * n * m)); }
+    HIP_TRY(h, q.Ascr.once((size_t)h->batch * n * n)); HIP_TRY(h, q.Bscr.once((size_t)h->batch * n * m));
     fp.A = q.Ascr; fp.B = q.Bscr; fp.f = q.xnext;
     HIP_TRY(h, launch_fnn_jacobian(h->sw, fp, q.net, h->num_cus, st));
     if (h->io.x0_slot >= 0) {   // a pinned x0 slot was read once more by the forward pass: free for the host only after it
@@ -2957,44 +2890,33 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
         std::copy(Pm.begin(), Pm.end(), Pall.begin() + i * n * n);
     }
     if (sq_struct && !h->batched_alloc) {   // the stage-wise QP needs no condensed operand: terminal weights and the flag words only
-        if (!h->bP) HIP_TRY(h, dalloc(&h->bP, b * n * n));
-        if (!h->bFlag) HIP_TRY(h, dalloc(&h->bFlag, b));
+        HIP_TRY(h, h->bP.once(b * n * n));
+        HIP_TRY(h, h->bFlag.once(b));
     } else {
         const int rc_ = ensure_batched_alloc(h);
         if (rc_ != ALMPC_OK) return rc_;
     }
     almpc_handle::Sqp& q = h->sqp;
     const int keep_rule = q.step_rule, keep_structured = q.structured_qp, keep_hessian = q.hessian, keep_rows = q.row_mult;
-    void* old[] = {q.W_in, q.W_h, q.b_h, q.W_out, q.A, q.B, q.c, q.fval, q.ebar, q.qadd, q.xref, q.uref, q.Q, q.R, q.S, q.bad, q.stats, q.mer, q.xback, q.uback, q.dxback, q.vback,
-                   q.sv, q.kkt, q.lam, q.Wlag, q.smu, h->dXref, h->dUref, h->dFS, h->dV0S};
-    for (void* p_ : old)
-        if (p_) (void)hipFree(p_);
-    if (q.live_pin) (void)hipHostFree(q.live_pin);
     q = almpc_handle::Sqp();
     q.step_rule = keep_rule;
     q.structured_qp = keep_structured;
     q.hessian = keep_hessian;
     q.row_mult = keep_rows;
-    h->dXref = h->dUref = h->dFS = h->dV0S = nullptr;
-    h->ref_cap[0] = h->ref_cap[1] = h->ref_cap[2] = 0;
-    auto up = [&](double** d, const double* src, size_t cnt) -> hipError_t {
-        hipError_t e = dalloc(d, cnt ? cnt : 1);
-        if (e == hipSuccess && src && cnt) e = hipMemcpy(*d, src, cnt * sizeof(double), hipMemcpyHostToDevice);
-        return e;
-    };
+    h->dXref.reset(); h->dUref.reset(); h->dFS.reset(); h->dV0S.reset();
+    h->ref_keep = false;
     std::vector<double> xr((size_t)n * (N + 1), 0.0), ur((size_t)nz, 0.0);
     if (xref) xr.assign(xref, xref + xr.size());
     if (uref) ur.assign(uref, uref + ur.size());
-    HIP_TRY(h, up(&q.W_in, W_in, (size_t)H * nin)); HIP_TRY(h, up(&q.W_h, W_h, net_wh_doubles(net, H, L))); HIP_TRY(h, up(&q.b_h, b_h, (size_t)L * H));
-    HIP_TRY(h, up(&q.W_out, W_out, net_wout_doubles(net, n, H, L)));
-    HIP_TRY(h, up(&q.A, nullptr, b * N * n * n)); HIP_TRY(h, up(&q.B, nullptr, b * N * n * m)); HIP_TRY(h, up(&q.c, nullptr, b * N * n));
-    HIP_TRY(h, up(&q.fval, nullptr, b * N * n)); HIP_TRY(h, up(&q.ebar, nullptr, b * N * n)); HIP_TRY(h, up(&q.qadd, nullptr, b * nz));
-    HIP_TRY(h, up(&q.xref, xr.data(), xr.size())); HIP_TRY(h, up(&q.uref, ur.data(), ur.size()));
-    HIP_TRY(h, up(&q.Q, Qm.data(), Qm.size())); HIP_TRY(h, up(&q.R, Rm.data(), Rm.size())); HIP_TRY(h, up(&q.S, Sm.data(), Sm.size()));
-    HIP_TRY(h, dalloc(&q.bad, b));
-    HIP_TRY(h, dalloc(&q.mer, 4 * b));
-    HIP_TRY(h, dalloc(&q.xback, b * (size_t)n * (N + 1))); HIP_TRY(h, dalloc(&q.dxback, b * (size_t)n * (N + 1)));
-    HIP_TRY(h, dalloc(&q.uback, b * nz)); HIP_TRY(h, dalloc(&q.vback, b * nz));
+    HIP_TRY(h, upload_net(q, n, m, H, L, activation, net, W_in, W_h, b_h, W_out));
+    HIP_TRY(h, q.A.alloc(b * N * n * n)); HIP_TRY(h, q.B.alloc(b * N * n * m)); HIP_TRY(h, q.c.alloc(b * N * n));
+    HIP_TRY(h, q.fval.alloc(b * N * n)); HIP_TRY(h, q.ebar.alloc(b * N * n)); HIP_TRY(h, q.qadd.alloc(b * nz));
+    HIP_TRY(h, q.xref.upload(xr.data(), xr.size())); HIP_TRY(h, q.uref.upload(ur.data(), ur.size()));
+    HIP_TRY(h, q.Q.upload(Qm.data(), Qm.size())); HIP_TRY(h, q.R.upload(Rm.data(), Rm.size())); HIP_TRY(h, q.S.upload(Sm.data(), Sm.size()));
+    HIP_TRY(h, q.bad.alloc(b));
+    HIP_TRY(h, q.mer.alloc(4 * b));
+    HIP_TRY(h, q.xback.alloc(b * (size_t)n * (N + 1))); HIP_TRY(h, q.dxback.alloc(b * (size_t)n * (N + 1)));
+    HIP_TRY(h, q.uback.alloc(b * nz)); HIP_TRY(h, q.vback.alloc(b * nz));
     {
         double pm = 0.0;
         for (double v : Pall) pm = std::max(pm, std::fabs(v));
@@ -3003,13 +2925,13 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
                           // set: 0.2 |P| rejects good steps near the solution, 10 |P| rejects every full step of some instances
     }
     HIP_TRY(h, hipMemset(q.bad, 0, b * sizeof(int)));
-    HIP_TRY(h, dalloc(&h->dXref, b * (size_t)n * (N + 1))); HIP_TRY(h, dalloc(&h->dUref, b * nz));
+    HIP_TRY(h, h->dXref.alloc(b * (size_t)n * (N + 1))); HIP_TRY(h, h->dUref.alloc(b * nz));
     HIP_TRY(h, hipMemcpy(h->bP, Pall.data(), Pall.size() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->dUmin, umin, m * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->dUmax, umax, m * sizeof(double), hipMemcpyHostToDevice));
     if (h->batched_alloc) {   // the condensed route (also kept ready when a condensed handle sends its QPs to k_riccati after an earlier design)
-        if (!h->bQ) HIP_TRY(h, dalloc(&h->bQ, b * nz));
-        HIP_TRY(h, dalloc(&h->dFS, b * nz)); HIP_TRY(h, dalloc(&h->dV0S, b * nz));
+        HIP_TRY(h, h->bQ.once(b * nz));
+        HIP_TRY(h, h->dFS.alloc(b * nz)); HIP_TRY(h, h->dV0S.alloc(b * nz));
         // F_i = 0 for an LTV design (the gradient is explicit), so F'_i and V_i stay zero; stage-0 model slots are unused but read
         HIP_TRY(h, hipMemset(h->bF, 0, b * nz * n * sizeof(double)));
         HIP_TRY(h, hipMemset(h->bFs, 0, b * n * nzs * sizeof(double)));
@@ -3017,7 +2939,7 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
         HIP_TRY(h, hipMemset(h->bA, 0, b * n * n * sizeof(double)));
         HIP_TRY(h, hipMemset(h->bB, 0, b * n * m * sizeof(double)));
     }
-    q.H = H; q.L = L; q.act = activation; q.net = net; q.useR = Rm[0] != 0.0; q.useS = q.useR && Sm[0] != 0.0; q.sP = p_inst ? (long)n * n : 0;
+    q.useR = Rm[0] != 0.0; q.useS = q.useR && Sm[0] != 0.0; q.sP = p_inst ? (long)n * n : 0;
     h->P.assign(Pall.begin(), Pall.begin() + (size_t)n * n);
     h->hS = Sm;
     h->useS = q.useS;
@@ -3049,15 +2971,9 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
             if (rc_ == ALMPC_OK) {
                 almpc_handle::Sd& sd = h->sd;
                 const size_t TP = (size_t)sdual_tp(sd.NT, sd.MC, N);
-                if (sd.base_cap < b * TP) {
-                    if (sd.base) { (void)hipFree(sd.base); sd.base = nullptr; }
-                    HIP_TRY(h, dalloc(&sd.base, b * TP));
-                    sd.base_cap = b * TP;
-                }
+                HIP_TRY(h, sd.base.grow(b * TP));
                 sd.has_base = true; sd.base_stride = (long)TP;
-                if (sd.pc) { (void)hipFree(sd.pc); sd.pc = nullptr; }
-                if (sd.ct) { (void)hipFree(sd.ct); sd.ct = nullptr; }
-                HIP_TRY(h, dalloc(&sd.pc, b * N * sd.NT)); HIP_TRY(h, dalloc(&sd.ct, b * N * sd.NT));
+                HIP_TRY(h, sd.pc.alloc(b * N * sd.NT)); HIP_TRY(h, sd.ct.alloc(b * N * sd.NT));
                 sd.sqp = true;
             }
         } else if ((q.structured_qp || h->fallback == 1) && (h->mc > 0 || q.useS))
@@ -3091,7 +3007,7 @@ static int sqp_rows_buffer(almpc_handle* h) {
     almpc_handle::Sqp& q = h->sqp;
     if (!q.row_mult || h->mc == 0 || q.smu) return ALMPC_OK;
     const size_t cnt = (size_t)h->batch * h->N * h->n;
-    HIP_TRY(h, dalloc(&q.smu, cnt));
+    HIP_TRY(h, q.smu.alloc(cnt));
     HIP_TRY(h, hipMemset(q.smu, 0, cnt * sizeof(double)));
     return ALMPC_OK;
 }
@@ -3207,8 +3123,8 @@ int almpc_sqp_fnn_solve(almpc_handle* h, int max_iters, double tol, const almpc_
     const size_t b = (size_t)h->batch;
     hipStream_t st = h->stream;
     HIP_TRY(h, hipStreamSynchronize(st));
-    if (!q.sv) { HIP_TRY(h, dalloc(&q.sv, 3 * b + 1)); HIP_TRY(h, dalloc(&q.kkt, b)); }
-    if (!q.live_pin) HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&q.live_pin), 4 * sizeof(int), hipHostMallocDefault));
+    HIP_TRY(h, q.sv.once(3 * b + 1)); HIP_TRY(h, q.kkt.once(b));
+    HIP_TRY(h, q.live_pin.once(4));
     SqpSolveCtl sv;
     sv.tol = tol; sv.done = q.sv; sv.iters = q.sv + b; sv.verdict = q.sv + 2 * b; sv.live = q.sv + 3 * b; sv.kkt = q.kkt;
     sv.live_pin = q.live_pin;
@@ -3245,11 +3161,8 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
     const int n = h->n, m = h->m, N = h->N, nz = h->nz, nzs = h->nzs;
     const size_t b = (size_t)h->batch;
     hipStream_t st = h->stream;
-    if (q.stats_cap < iters || !q.stats) {
-        if (q.stats) { HIP_TRY(h, hipStreamSynchronize(st)); (void)hipFree(q.stats); q.stats = nullptr; }
-        HIP_TRY(h, dalloc(&q.stats, (size_t)2 * std::max(iters, 1)));
-        q.stats_cap = std::max(iters, 1);
-    }
+    if (q.stats && q.stats.size() < (size_t)2 * iters) HIP_TRY(h, hipStreamSynchronize(st));   // (the buffer is replaced: its last reader first)
+    HIP_TRY(h, q.stats.grow((size_t)2 * std::max(iters, 1)));
     HIP_TRY(h, hipMemsetAsync(q.stats, 0, (size_t)2 * iters * sizeof(unsigned long long), st));
     const DesignStrides ds = batched_strides(h, q.sP != 0);
     const size_t step_lds = sqp_step_lds_doubles(n, m, N) * sizeof(double);
@@ -3305,7 +3218,7 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
     size_t hess_lds = 0, exact_lds = 0;
     if (exact) {
         { const int rc_ = sqp_exact_check(h); if (rc_ != ALMPC_OK) return rc_; }
-        if (!q.lam) { HIP_TRY(h, dalloc(&q.lam, b * N * (size_t)n)); HIP_TRY(h, dalloc(&q.Wlag, b * N * (size_t)(n + m) * (n + m))); }
+        HIP_TRY(h, q.lam.once(b * N * (size_t)n)); HIP_TRY(h, q.Wlag.once(b * N * (size_t)(n + m) * (n + m)));
         if (!sv) {   // the multipliers only: the walk of k_sqp_kkt without the test
             kp.n = n; kp.m = m; kp.N = N; kp.nz = nz; kp.useS = q.useS;
             kp.xref = q.xref; kp.uref = q.uref; kp.Q = q.Q; kp.R = q.R; kp.S = q.S; kp.P = h->bP; kp.sP = q.sP;
@@ -3497,11 +3410,8 @@ int almpc_set_reference(almpc_handle* h, const double* xref, const double* uref,
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (h->structured) {
         h->designed = false;
-        if (h->dXref) { (void)hipFree(h->dXref); h->dXref = nullptr; }
-        if (h->dUref) { (void)hipFree(h->dUref); h->dUref = nullptr; }
-        h->ref_cap[0] = h->ref_cap[1] = h->ref_cap[2] = 0;
-        HIP_TRY(h, dalloc(&h->dXref, cnt * xs));
-        HIP_TRY(h, dalloc(&h->dUref, cnt * us));
+        HIP_TRY(h, h->dXref.alloc(cnt * xs));
+        HIP_TRY(h, h->dUref.alloc(cnt * us));
         HIP_TRY(h, hipMemcpy(h->dXref, xref, cnt * xs * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(h->dUref, uref, cnt * us * sizeof(double), hipMemcpyHostToDevice));
         h->xref_stride = per_instance ? (long)xs : 0;
@@ -3515,18 +3425,15 @@ int almpc_set_reference(almpc_handle* h, const double* xref, const double* uref,
     h->designed = false;                    // the reference buffers are replaced below: designed again on success only
     const size_t fcnt = h->batched ? (size_t)h->batch : cnt;  // per-instance models: fS depends on d_i
     // (a re-design or a new reference of the same shape keeps the four buffers: hipFree + hipMalloc cost ~0.1 ms each)
-    if (!(h->dXref && h->dUref && h->dFS && h->dV0S && h->ref_cap[0] == cnt * xs && h->ref_cap[1] == cnt * us && h->ref_cap[2] == fcnt * us)) {
-        if (h->dXref) { (void)hipFree(h->dXref); h->dXref = nullptr; }
-        if (h->dUref) { (void)hipFree(h->dUref); h->dUref = nullptr; }
-        if (h->dFS) { (void)hipFree(h->dFS); h->dFS = nullptr; }
-        if (h->dV0S) { (void)hipFree(h->dV0S); h->dV0S = nullptr; }
-        h->ref_cap[0] = h->ref_cap[1] = h->ref_cap[2] = 0;
-        HIP_TRY(h, dalloc(&h->dXref, cnt * xs));
-        HIP_TRY(h, dalloc(&h->dUref, cnt * us));
-        HIP_TRY(h, dalloc(&h->dFS, fcnt * us));
-        HIP_TRY(h, dalloc(&h->dV0S, fcnt * us));
-        h->ref_cap[0] = cnt * xs; h->ref_cap[1] = cnt * us; h->ref_cap[2] = fcnt * us;
+    // the exact policy, over the four together: buffers another entry point made, or one size that moved, replace them all
+    if (!(h->ref_keep && h->dXref.size() == cnt * xs && h->dUref.size() == cnt * us && h->dFS.size() == fcnt * us && h->dV0S.size() == fcnt * us)) {
+        h->dXref.reset(); h->dUref.reset(); h->dFS.reset(); h->dV0S.reset();
     }
+    HIP_TRY(h, h->dXref.once(cnt * xs));
+    HIP_TRY(h, h->dUref.once(cnt * us));
+    HIP_TRY(h, h->dFS.once(fcnt * us));
+    HIP_TRY(h, h->dV0S.once(fcnt * us));
+    h->ref_keep = true;
     HIP_TRY(h, hipMemcpy(h->dXref, xref, cnt * xs * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->dUref, uref, cnt * us * sizeof(double), hipMemcpyHostToDevice));
     // fS = d .* (2 D'Sbar D u_ref): the input-rate cost is on u, not e_u (src/sub/design_mpc.jl:423-446)
@@ -3551,8 +3458,8 @@ int almpc_set_reference(almpc_handle* h, const double* xref, const double* uref,
         HIP_TRY(h, hipMemsetAsync(h->dV0S, 0, fcnt * us * sizeof(double), h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     } else if (h->batched) {  // fS_i = d_i .* g and v0S_i = -G_i fS_i on the device, one vector per instance
-        double* dGs = nullptr;
-        HIP_TRY(h, dalloc(&dGs, cnt * us));
+        DevBuf<double> dGs;
+        HIP_TRY(h, dGs.alloc(cnt * us));
         hipError_t e = hipMemcpy(dGs, fS.data(), cnt * us * sizeof(double), hipMemcpyHostToDevice);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_fs_scale, dim3(256), dim3(256), 0, h->stream, h->batch, nz, h->nzs, dGs, per_instance ? (long)us : 0L,
@@ -3562,7 +3469,6 @@ int almpc_set_reference(almpc_handle* h, const double* xref, const double* uref,
             e = hipGetLastError();
             if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         }
-        (void)hipFree(dGs);
         if (e != hipSuccess) return fail(h, ALMPC_ERR_HIP, std::string("set_reference (batched): ") + hipGetErrorString(e));
     } else {
     HIP_TRY(h, hipMemcpy(h->dFS, fS.data(), cnt * us * sizeof(double), hipMemcpyHostToDevice));
@@ -3773,21 +3679,15 @@ static int net_linearize(bool dense, int device_id, int n, int m, int H, int L, 
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || device_id < 0 || device_id >= count) return ALMPC_ERR_NO_DEVICE;
     if (hipSetDevice(device_id) != hipSuccess) return ALMPC_ERR_HIP;
-    std::vector<void*> bufs;
-    auto up = [&](const double* src, size_t cnt) -> double* {
-        double* d = nullptr;
-        if (cnt == 0) cnt = 1;
-        if (hipMalloc(reinterpret_cast<void**>(&d), cnt * sizeof(double)) != hipSuccess) return nullptr;
-        bufs.push_back(d);
-        if (src && hipMemcpy(d, src, cnt * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return d;
-    };
+    using Tight = DevBuf<double, Mem::DeviceTight>;
+    Tight dWin, dWh, dbh, dWout, dx, du, dA, dB, df;
+    auto up = [](Tight& d, const double* src, size_t cnt) -> double* { return d.upload(src, cnt) == hipSuccess ? d.get() : nullptr; };
     FnnParams p;
     p.n = n; p.m = m; p.H = H; p.L = L; p.act = activation; p.batch = batch;
     p.ppi = 1; p.xs_group = n; p.us_group = m;
-    p.W_in = up(W_in, (size_t)H * nin); p.W_h = up(W_h, net_wh_doubles(net, H, L)); p.b_h = up(b_h, (size_t)L * H);
-    p.W_out = up(W_out, net_wout_doubles(net, n, H, L)); p.x = up(x, (size_t)batch * n); p.u = up(u, (size_t)batch * m);
-    p.A = up(nullptr, (size_t)batch * n * n); p.B = up(nullptr, (size_t)batch * n * m); p.f = f ? up(nullptr, (size_t)batch * n) : nullptr;
+    p.W_in = up(dWin, W_in, (size_t)H * nin); p.W_h = up(dWh, W_h, net_wh_doubles(net, H, L)); p.b_h = up(dbh, b_h, (size_t)L * H);
+    p.W_out = up(dWout, W_out, net_wout_doubles(net, n, H, L)); p.x = up(dx, x, (size_t)batch * n); p.u = up(du, u, (size_t)batch * m);
+    p.A = up(dA, nullptr, (size_t)batch * n * n); p.B = up(dB, nullptr, (size_t)batch * n * m); p.f = f ? up(df, nullptr, (size_t)batch * n) : nullptr;
     int rc = ALMPC_OK;
     if (!p.W_in || !p.W_h || !p.b_h || !p.W_out || !p.x || !p.u || !p.A || !p.B || (f && !p.f)) rc = ALMPC_ERR_HIP;
     if (rc == ALMPC_OK) {
@@ -3801,7 +3701,6 @@ static int net_linearize(bool dense, int device_id, int n, int m, int H, int L, 
             (f && hipMemcpy(f, p.f, (size_t)batch * n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
             rc = ALMPC_ERR_HIP;
     }
-    for (void* b : bufs) (void)hipFree(b);
     return rc;
 }
 int almpc_fnn_linearize(int device_id, int n, int m, int H, int L, int activation, const double* W_in, const double* W_h,
@@ -3839,11 +3738,10 @@ int almpc_comm_init(almpc_handle* h, const char* id128, int rank, int world) {
     const ncclResult_t rc = r.CommInitRank(&h->comm, world, id, rank);
     if (rc != ncclSuccess) { h->comm = nullptr; return fail(h, ALMPC_ERR_HIP, std::string("ncclCommInitRank: ") + r.GetErrorString(rc)); }
     h->comm_rank = rank; h->comm_world = world;
-    for (double** pp_ : {&h->dU0, &h->dU0all})
-        if (*pp_) { (void)hipFree(*pp_); *pp_ = nullptr; }
-    if (!h->dComm4) HIP_TRY(h, dalloc(&h->dComm4, 4));
-    HIP_TRY(h, dalloc(&h->dU0, (size_t)h->batch * h->m));
-    HIP_TRY(h, dalloc(&h->dU0all, (size_t)world * h->batch * h->m));
+    h->dU0.reset(); h->dU0all.reset();
+    HIP_TRY(h, h->dComm4.once(4));
+    HIP_TRY(h, h->dU0.alloc((size_t)h->batch * h->m));
+    HIP_TRY(h, h->dU0all.alloc((size_t)world * h->batch * h->m));
     return ALMPC_OK;
 }
 
@@ -3911,7 +3809,7 @@ int almpc_debug_poison_lds(almpc_handle* h) {
     HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_poison_lds), (size_t)(bytes)));
     // one workgroup owns a whole CU's LDS; several waves of workgroups so that every CU is visited
     hipLaunchKernelGGL(k_poison_lds, dim3(1024), dim3(1024), bytes, h->stream, 0x7ff8dead0000beefULL, bytes / 8,
-                       reinterpret_cast<unsigned long long*>(h->dSglobal));
+                       reinterpret_cast<unsigned long long*>(h->dSglobal.get()));
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return ALMPC_OK;
@@ -3920,8 +3818,9 @@ int almpc_debug_poison_lds(almpc_handle* h) {
 #ifdef ALMPC_STAMPS
 // diagnostic build: allocate / fetch the stamp buffer ([waves][16] int64)
 int almpc_dbg_stamps_enable(almpc_handle* h, int waves) {
-    long long* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), (size_t)waves * 16 * sizeof(long long)) != hipSuccess) return -3;
+    DevBuf<long long, Mem::DeviceTight> buf;
+    if (buf.alloc((size_t)waves * 16) != hipSuccess) return -3;
+    long long* d = buf.release();   // (never freed: g_stamps points at it for the life of the process)
     (void)hipMemset(d, 0, (size_t)waves * 16 * sizeof(long long));
     (void)hipMemcpyToSymbol(HIP_SYMBOL(almpc::g_stamps), &d, sizeof(d));
     return 0;

@@ -15,6 +15,7 @@
 #pragma once
 #include "almpc_kernels.hip.h"
 #include "almpc_switches.h"
+#include "almpc_devbuf.h"
 
 #include <string>
 #include <vector>
@@ -1063,31 +1064,26 @@ inline int design_shared_device(hipStream_t stream, int n, int m, int N, int nzs
     symmetrise(Q, n); symmetrise(P, n); symmetrise(R, m); symmetrise(S, m);
     const int njf = (n + 15) / 16, ps = 16 * njf, gs = nzs;
     const int kr = ((n * N + HESS_KC - 1) / HESS_KC) * HESS_KC;
-    std::vector<void*> tmp;
-    auto cleanup = [&]() { for (void* p : tmp) (void)hipFree(p); };
 #define DTRY(call)                                                                           \
     do {                                                                                     \
         hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e_); cleanup(); return -3; } \
+        if (e_ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e_); return -3; } \
     } while (0)
-    auto dnew = [&](double** p, size_t cnt) -> hipError_t {
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(p), cnt * sizeof(double) + 64);
-        if (e == hipSuccess) { tmp.push_back(*p); e = hipMemsetAsync(*p, 0, cnt * sizeof(double), stream); }
+    auto dnew = [&](DevBuf<double>& p, size_t cnt) -> hipError_t {
+        hipError_t e = p.alloc(cnt);
+        if (e == hipSuccess) e = hipMemsetAsync(p, 0, cnt * sizeof(double), stream);
         return e;
     };
-    double *dA, *dB, *dQ, *dR, *dS, *dP, *dPhi, *dGk, *dGam, *dW, *dWP, *dH, *dF, *dHs, *dFs, *dVs, *dMinv;
-    int* dFlag;
-    DTRY(dnew(&dA, (size_t)n * n)); DTRY(dnew(&dB, (size_t)n * m)); DTRY(dnew(&dQ, (size_t)n * n));
-    DTRY(dnew(&dR, (size_t)m * m)); DTRY(dnew(&dS, (size_t)m * m)); DTRY(dnew(&dP, (size_t)n * n));
-    DTRY(dnew(&dPhi, (size_t)N * n * n)); DTRY(dnew(&dGk, (size_t)N * n * m));
-    DTRY(dnew(&dGam, (size_t)kr * gs)); DTRY(dnew(&dW, (size_t)kr * gs)); DTRY(dnew(&dWP, (size_t)kr * ps));
-    DTRY(dnew(&dH, (size_t)nz * nz)); DTRY(dnew(&dF, (size_t)nz * n));
-    DTRY(dnew(&dHs, (size_t)nz * nzs)); DTRY(dnew(&dFs, (size_t)n * nzs)); DTRY(dnew(&dVs, (size_t)n * nzs)); DTRY(dnew(&dMinv, (size_t)nz * nzs));
-    {
-        double* f = nullptr;
-        DTRY(dnew(&f, 8));
-        dFlag = reinterpret_cast<int*>(f);
-    }
+    // design temporaries: all of them live until the stream has been waited for below
+    DevBuf<double> dA, dB, dQ, dR, dS, dP, dPhi, dGk, dGam, dW, dWP, dH, dF, dHs, dFs, dVs, dMinv, dFlagBuf, dCp, dCG, dSelBuf;
+    DTRY(dnew(dA, (size_t)n * n)); DTRY(dnew(dB, (size_t)n * m)); DTRY(dnew(dQ, (size_t)n * n));
+    DTRY(dnew(dR, (size_t)m * m)); DTRY(dnew(dS, (size_t)m * m)); DTRY(dnew(dP, (size_t)n * n));
+    DTRY(dnew(dPhi, (size_t)N * n * n)); DTRY(dnew(dGk, (size_t)N * n * m));
+    DTRY(dnew(dGam, (size_t)kr * gs)); DTRY(dnew(dW, (size_t)kr * gs)); DTRY(dnew(dWP, (size_t)kr * ps));
+    DTRY(dnew(dH, (size_t)nz * nz)); DTRY(dnew(dF, (size_t)nz * n));
+    DTRY(dnew(dHs, (size_t)nz * nzs)); DTRY(dnew(dFs, (size_t)n * nzs)); DTRY(dnew(dVs, (size_t)n * nzs)); DTRY(dnew(dMinv, (size_t)nz * nzs));
+    DTRY(dnew(dFlagBuf, 8));
+    int* const dFlag = reinterpret_cast<int*>(dFlagBuf.get());
     DTRY(hipMemcpyAsync(dA, A.data(), A.size() * sizeof(double), hipMemcpyHostToDevice, stream));
     DTRY(hipMemcpyAsync(dB, B.data(), B.size() * sizeof(double), hipMemcpyHostToDevice, stream));
     DTRY(hipMemcpyAsync(dQ, Q.data(), Q.size() * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -1133,14 +1129,9 @@ inline int design_shared_device(hipStream_t stream, int n, int m, int N, int nzs
     DTRY(hipGetLastError());
     if (!rowsel.empty()) {  // state rows: Ghat = A G A' in constraint space
         const int mc = (int)rowsel.size();
-        double *dCp, *dCG;
-        int* dSel;
-        DTRY(dnew(&dCp, (size_t)mc * nzs)); DTRY(dnew(&dCG, (size_t)mc * nzs));
-        {
-            double* tmpi = nullptr;
-            DTRY(dnew(&tmpi, (size_t)(mc + 1) / 2 + 1));
-            dSel = reinterpret_cast<int*>(tmpi);
-        }
+        DTRY(dnew(dCp, (size_t)mc * nzs)); DTRY(dnew(dCG, (size_t)mc * nzs));
+        DTRY(dnew(dSelBuf, (size_t)(mc + 1) / 2 + 1));
+        int* const dSel = reinterpret_cast<int*>(dSelBuf.get());
         DTRY(hipMemcpyAsync(dSel, rowsel.data(), mc * sizeof(int), hipMemcpyHostToDevice, stream));
         hipLaunchKernelGGL(k_build_cprime, dim3(64), dim3(256), 0, stream, mc, nz, nzs, gs, dSel, dGam, dD, dCp);
         hipLaunchKernelGGL(k_cg, dim3(256), dim3(256), 0, stream, mc, nz, nzs, dCp, dG, dCG);
@@ -1155,7 +1146,6 @@ inline int design_shared_device(hipStream_t stream, int n, int m, int N, int nzs
     DTRY(hipMemcpyAsync(&flag, dFlag, sizeof(int), hipMemcpyDeviceToHost, stream));
     DTRY(hipStreamSynchronize(stream));
 #undef DTRY
-    cleanup();
     if (flag != 0) {
         err = flag == 1 ? "design: condensed Hessian has a non-positive diagonal (R = 0 with an input that does not reach the cost?)"
                         : "design: Cholesky pivot not positive (Hessian not positive definite)";

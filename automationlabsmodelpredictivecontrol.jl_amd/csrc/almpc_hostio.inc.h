@@ -35,11 +35,6 @@ inline __global__ __launch_bounds__(256) void k_pack_step_summary(int batch, int
     }
 }
 
-template <typename T>
-hipError_t pinned(T** p, size_t count) {
-    return hipHostMalloc(reinterpret_cast<void**>(p), count * sizeof(T), hipHostMallocDefault);
-}
-
 int io_init_body(almpc_handle* h) {
     almpc_handle::Io& io = h->io;
     HIP_TRY(h, hipSetDevice(h->device));
@@ -47,14 +42,14 @@ int io_init_body(almpc_handle* h) {
     HIP_TRY(h, hipStreamCreateWithFlags(&io.s_in, hipStreamNonBlocking));
     const size_t b = (size_t)h->batch;
     for (int s = 0; s < almpc_handle::IO_DEPTH; ++s) {
-        HIP_TRY(h, pinned(&io.hX0[s], b * h->n));
-        HIP_TRY(h, pinned(&io.hU0[s], b * h->m));
-        HIP_TRY(h, pinned(&io.hInts[s], 3 * b));
+        HIP_TRY(h, io.hX0[s].alloc(b * h->n));
+        HIP_TRY(h, io.hU0[s].alloc(b * h->m));
+        HIP_TRY(h, io.hInts[s].alloc(3 * b));
         // the device's view of the pinned slots (kernels read x0 from / write the step summary to host memory directly)
         HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&io.dX0[s]), io.hX0[s], 0));
         HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&io.dU0[s]), io.hU0[s], 0));
         HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&io.dInts[s]), io.hInts[s], 0));
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&io.dX0dev[s]), b * h->n * sizeof(double)));
+        HIP_TRY(h, io.dX0dev[s].alloc(b * h->n));
         for (hipEvent_t* e : {&io.ev_used[s], &io.ev_packed[s], &io.ev_done[s], &io.ev_in[s]})
             HIP_TRY(h, hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
@@ -78,21 +73,18 @@ int io_init(almpc_handle* h) {
 
 void io_free(almpc_handle* h) {
     almpc_handle::Io& io = h->io;
-    if (io.dX0_own) h->dX0 = io.dX0_own;
+    io_release_x0(h);
     if (io.s_out) (void)hipStreamSynchronize(io.s_out);
     if (io.s_in) (void)hipStreamSynchronize(io.s_in);
     for (int s = 0; s < almpc_handle::IO_DEPTH; ++s) {
-        if (io.dX0dev[s]) (void)hipFree(io.dX0dev[s]);
         if (io.ev_in[s]) (void)hipEventDestroy(io.ev_in[s]);
-        for (void* p : {(void*)io.hX0[s], (void*)io.hX[s], (void*)io.hEx[s], (void*)io.hU[s], (void*)io.hEu[s], (void*)io.hU0[s], (void*)io.hInts[s]})
-            if (p) (void)hipHostFree(p);
         for (hipEvent_t e : {io.ev_used[s], io.ev_packed[s], io.ev_done[s]})
             if (e) (void)hipEventDestroy(e);
     }
     if (io.ev_big) (void)hipEventDestroy(io.ev_big);
     if (io.s_out) (void)hipStreamDestroy(io.s_out);
     if (io.s_in) (void)hipStreamDestroy(io.s_in);
-    io = almpc_handle::Io();
+    io = almpc_handle::Io();   // (releases the pinned rings and the device slots)
 }
 
 // Wait for an event the way almpc_synchronize waits for the stream: poll first (a blocking wake-up costs milliseconds on this pool)
@@ -138,7 +130,6 @@ int almpc_update_initialization_async(almpc_handle* h, const double* x0) {
         io.used_pending[s] = false;
     }
     if (x0 != io.hX0[s]) std::memcpy(io.hX0[s], x0, (size_t)h->batch * h->n * sizeof(double));   // (almpc_x0_staging: already in place)
-    if (io.x0_slot < 0) io.dX0_own = h->dX0;   // (the handle's own buffer is kept and freed with the handle)
     if (h->sw.x0_upload) {
         // pinned slot -> device slot on the copy-in stream (under the step that is running); everything enqueued on the compute stream
         // from here on comes after it
@@ -174,10 +165,10 @@ int almpc_get_results_async(almpc_handle* h, uint32_t want) {
         HIP_TRY(h, hipStreamWaitEvent(h->stream, io.ev_big, 0));
         io.big_copy_pending = false;
     }
-    if ((want & ALMPC_WANT_X) && !io.hX[s]) HIP_TRY(h, pinned(&io.hX[s], xs));
-    if ((want & ALMPC_WANT_E_X) && !io.hEx[s]) HIP_TRY(h, pinned(&io.hEx[s], xs));
-    if ((want & ALMPC_WANT_U) && !io.hU[s]) HIP_TRY(h, pinned(&io.hU[s], us));
-    if ((want & ALMPC_WANT_E_U) && !io.hEu[s]) HIP_TRY(h, pinned(&io.hEu[s], us));
+    if (want & ALMPC_WANT_X) HIP_TRY(h, io.hX[s].once(xs));
+    if (want & ALMPC_WANT_E_X) HIP_TRY(h, io.hEx[s].once(xs));
+    if (want & ALMPC_WANT_U) HIP_TRY(h, io.hU[s].once(us));
+    if (want & ALMPC_WANT_E_U) HIP_TRY(h, io.hEu[s].once(us));
     const bool small = (want & (ALMPC_WANT_FIRST_INPUT | ALMPC_WANT_STATUS | ALMPC_WANT_ITERS | ALMPC_WANT_POLISH_ITERS)) != 0;
     if (small) {   // straight into the pinned slot: no copy, the next step starts right behind this kernel
         const long cnt = std::max((long)b * h->m, (long)b);

@@ -3,6 +3,9 @@
 // are dummy objects, kernel launches do nothing.  Only what csrc/almpc_api.hip links against.  Test infrastructure, never shipped.
 // fake_hip_trace_to(path): every launch from then on appends one line to `path`: the launching stream's creation ordinal (0: the null
 // stream), the demangled kernel name, grid, block and dynamic LDS bytes.
+// The byte size of every hipMalloc and of every hipHostMalloc that succeeded is kept; fake_hip_dump_allocs(path) writes both lists,
+// sorted (tests/golden/host_alloc_sizes.txt).  fake_hip_fail_alloc_at(k): the k-th hipMalloc / hipHostMalloc from now on returns
+// hipErrorOutOfMemory, once (k = 0: none); returns what was left of the last such count (0: it has fired, or none was set).
 #include <hip/hip_runtime_api.h>
 
 #include <cxxabi.h>
@@ -10,9 +13,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <string>
+#include <vector>
 
 namespace {
 struct Cfg { dim3 grid, block; size_t shmem; hipStream_t stream; };
@@ -25,8 +30,20 @@ struct State {
     std::map<const void*, int> stream_ord;
     std::map<const void*, std::string> kernel_name;
     FILE* trace = nullptr;
+    std::vector<size_t> device_bytes, pinned_bytes;
+    int fail_in = 0;
 };
 State& S() { static State s; return s; }
+
+hipError_t fake_alloc(void** p, size_t n, std::vector<size_t> State::*sizes) {
+    State& g = S(); std::lock_guard<std::mutex> l(g.mu);
+    *p = nullptr;
+    if (g.fail_in > 0 && --g.fail_in == 0) return hipErrorOutOfMemory;
+    *p = std::calloc(n ? n : 1, 1);
+    if (!*p) return hipErrorOutOfMemory;
+    (g.*sizes).push_back(n);
+    return hipSuccess;
+}
 }
 
 extern "C" {
@@ -41,6 +58,23 @@ void fake_hip_trace_close() {
     State& g = S(); std::lock_guard<std::mutex> l(g.mu);
     if (g.trace) std::fclose(g.trace);
     g.trace = nullptr;
+}
+int fake_hip_fail_alloc_at(int k) {
+    State& g = S(); std::lock_guard<std::mutex> l(g.mu);
+    const int left = g.fail_in;
+    g.fail_in = k;
+    return left;
+}
+int fake_hip_dump_allocs(const char* path) {
+    State& g = S(); std::lock_guard<std::mutex> l(g.mu);
+    FILE* f = std::fopen(path, "w");
+    if (!f) return 1;
+    for (auto* v : {&g.device_bytes, &g.pinned_bytes}) {
+        std::sort(v->begin(), v->end());
+        std::fprintf(f, "%s %zu\n", v == &g.device_bytes ? "hipMalloc" : "hipHostMalloc", v->size());
+        for (size_t n : *v) std::fprintf(f, "%zu\n", n);
+    }
+    return std::fclose(f) ? 1 : 0;
 }
 
 hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
@@ -60,9 +94,9 @@ hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_tR0600* p, int) {
 const char* hipGetErrorString(hipError_t) { return "fake HIP runtime"; }
 hipError_t hipGetLastError() { return hipSuccess; }
 
-hipError_t hipMalloc(void** p, size_t n) { *p = std::calloc(n ? n : 1, 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+hipError_t hipMalloc(void** p, size_t n) { return fake_alloc(p, n, &State::device_bytes); }
 hipError_t hipFree(void* p) { std::free(p); return hipSuccess; }
-hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = std::calloc(n ? n : 1, 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+hipError_t hipHostMalloc(void** p, size_t n, unsigned) { return fake_alloc(p, n, &State::pinned_bytes); }
 hipError_t hipHostFree(void* p) { std::free(p); return hipSuccess; }
 hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) { *d = h; return hipSuccess; }
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { std::memmove(d, s, n); return hipSuccess; }

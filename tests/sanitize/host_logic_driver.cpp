@@ -8,6 +8,9 @@
 // tests/golden/host_launch_trace.txt pins); the handles below reach every kernel of the step path at least once.
 // A second argument NAME=VALUE is one ALMPC_* switch (csrc/almpc_switches.h) the whole run is made under: its launch trace against the
 // plain one is what tests/golden/host_launch_trace_switches.txt pins per switch.
+// With a path argument the byte sizes of all device and pinned allocations of the run go to <path>.allocs at the end, sorted
+// (tests/golden/host_alloc_sizes.txt).  With "alloc-failures" as the second argument nothing of the above runs: every entry point that
+// allocates is called with its k-th allocation failing, k = 1, 2, ... until it gets through (alloc_failures below).
 #include "../../include/almpc.h"
 
 #include <cmath>
@@ -20,6 +23,8 @@
 extern "C" long fake_hip_launch_count();
 extern "C" int fake_hip_trace_to(const char* path);
 extern "C" void fake_hip_trace_close();
+extern "C" int fake_hip_fail_alloc_at(int k);
+extern "C" int fake_hip_dump_allocs(const char* path);
 extern char** environ;
 
 #define CK(call)                                                                                             \
@@ -81,6 +86,104 @@ static int step_and_read(almpc_handle* h, int n, int m, int N, int batch, bool t
     return 0;
 }
 
+// `call` on a fresh handle (made by `prep` without failures) with the k-th allocation inside it failing, for k = 1, 2, ... until no
+// allocation is left to fail.  Every call whose allocation failed must return ALMPC_ERR_HIP, and no call fails otherwise.  The
+// redo of undecided instances (almpc_set_structured_fallback) is asked for (`fallback` 1: a stage-wise setup that fails is the
+// call's error; at the default, 2, the design goes on without it) or off (0: its buffers are not made).  Every handle is destroyed:
+// what a failed call leaves behind must be freed exactly once (ASan, LSan).
+template <typename Prep, typename Call>
+static int walk(const char* name, int n, int m, int N, int batch, uint32_t flags, int fallback, Prep prep, Call call) {
+    for (int k = 1; k <= 200; ++k) {
+        almpc_handle* h = nullptr;
+        CK(almpc_create(&h, n, m, N, batch, 0, flags));
+        CK(almpc_set_structured_fallback(h, fallback));
+        CK(prep(h));
+        fake_hip_fail_alloc_at(k);
+        const int rc = call(h);
+        const bool fired = fake_hip_fail_alloc_at(0) == 0;
+        const std::string msg = almpc_last_error(h);
+        almpc_destroy(h);
+        if (rc != (fired ? ALMPC_ERR_HIP : ALMPC_OK)) {
+            std::fprintf(stderr, "%s (fallback %d), allocation %d %s: -> %d (%s)\n", name, fallback, k, fired ? "failing" : "not reached", rc, msg.c_str());
+            return 1;
+        }
+        if (!fired) { std::printf("%s (fallback %d): %d allocations\n", name, fallback, k - 1); return 0; }
+    }
+    std::fprintf(stderr, "%s: still allocating after 200 failures\n", name);
+    return 1;
+}
+
+static int alloc_failures() {
+    const int n = 4, m = 2, N = 12, batch = 7, Hn = 8, L = 2;
+    const Plant p = chain(n, m);
+    const auto nothing = [](almpc_handle*) { return (int)ALMPC_OK; };
+    for (int k = 1;; ++k) {   // almpc_create, condensed and structured
+        almpc_handle *h = nullptr, *hs = nullptr;
+        fake_hip_fail_alloc_at(k);
+        const int rc = almpc_create(&h, n, m, N, batch, 0, 0);
+        const bool fired = fake_hip_fail_alloc_at(0) == 0;
+        fake_hip_fail_alloc_at(k);
+        const int rcs = almpc_create(&hs, n, m, N, batch, 0, ALMPC_FLAG_STRUCTURED);
+        const bool fireds = fake_hip_fail_alloc_at(0) == 0;
+        if ((rc == ALMPC_OK) != (h != nullptr) || (rcs == ALMPC_OK) != (hs != nullptr) || (rc == ALMPC_OK) == fired || (rcs == ALMPC_OK) == fireds || k > 200) {
+            std::fprintf(stderr, "almpc_create, allocation %d failing: -> %d, %d\n", k, rc, rcs);
+            return 1;
+        }
+        almpc_destroy(h); almpc_destroy(hs);
+        if (!fired && !fireds) { std::printf("almpc_create: %d allocations\n", k - 1); break; }
+    }
+    std::vector<double> xr((size_t)n * (N + 1), 0.1), ur((size_t)m * N, 0.05), x0((size_t)batch * n, 0.25), P((size_t)n * n, 0.0);
+    for (int k = 0; k < N; ++k) ur[(size_t)k * m] = 0.01 * k;
+    for (int i = 0; i < n; ++i) P[(size_t)i * n + i] = 150.0;
+    std::vector<double> Ab((size_t)batch * n * n), Bb((size_t)batch * n * m);
+    for (int i = 0; i < batch; ++i) {
+        for (size_t t = 0; t < p.A.size(); ++t) Ab[(size_t)i * n * n + t] = p.A[t];
+        for (size_t t = 0; t < p.B.size(); ++t) Bb[(size_t)i * n * m + t] = p.B[t] * (1.0 + 0.01 * i);
+    }
+    for (const int fb : {1, 0}) {   // the redo of undecided instances asked for, then off
+    const auto box_and_eq = [&](almpc_handle* h) { return almpc_set_terminal_equality(h, 1); };
+    if (walk("almpc_design_shared", n, m, N, batch, 0, fb, box_and_eq, [&](almpc_handle* h) {   // state box + terminal equality: the projection's temporary
+            return almpc_design_shared(h, p.A.data(), p.B.data(), p.Q.data(), p.R.data(), p.S.data(), nullptr, p.umin.data(), p.umax.data(), p.xmin.data(), p.xmax.data(), 0.1, 1e-6);
+        })) return 1;
+    const auto design_batched = [&](almpc_handle* h) {
+        return almpc_design_batched(h, Ab.data(), Bb.data(), p.Q.data(), p.R.data(), p.S.data(), nullptr, 0, p.umin.data(), p.umax.data(), 0.1, 1e-6);
+    };
+    const auto state_box = [&](almpc_handle* h) { return almpc_set_state_box(h, p.xmin.data(), p.xmax.data()); };
+    if (walk("almpc_design_batched", n, m, N, batch, 0, fb, state_box, design_batched)) return 1;
+    {
+        std::vector<double> Aall((size_t)batch * N * n * n), Ball((size_t)batch * N * n * m), call((size_t)batch * N * n, 0.01),
+            xbar((size_t)batch * (N + 1) * n, 0.2), ubar((size_t)batch * N * m, 0.1);
+        for (size_t i = 0; i < (size_t)batch * N; ++i) {
+            for (size_t t = 0; t < p.A.size(); ++t) Aall[i * n * n + t] = p.A[t];
+            for (size_t t = 0; t < p.B.size(); ++t) Ball[i * n * m + t] = p.B[t];
+        }
+        if (walk("almpc_design_ltv", n, m, N, batch, 0, fb, state_box, [&](almpc_handle* h) {   // state rows: the staging buffers are handed to the handle
+                return almpc_design_ltv(h, Aall.data(), Ball.data(), call.data(), xbar.data(), ubar.data(), xr.data(), ur.data(), p.Q.data(), p.R.data(),
+                                        p.S.data(), P.data(), 0, p.umin.data(), p.umax.data(), 0.1, 1e-6);
+            })) return 1;
+    }
+    if (walk("almpc_set_reference", n, m, N, batch, 0, fb, design_batched, [&](almpc_handle* h) {   // per-instance models with S: the gradient's temporary
+            return almpc_set_reference(h, xr.data(), ur.data(), 0);
+        })) return 1;
+    std::vector<double> W_in((size_t)Hn * (n + m), 0.05), W_h((size_t)L * Hn * Hn, 0.02), b_h((size_t)L * Hn, 0.01), W_out((size_t)n * Hn, 0.1);
+    const auto relin = [&](almpc_handle* h) {
+        return almpc_relin_fnn_setup(h, Hn, L, 0, W_in.data(), W_h.data(), b_h.data(), W_out.data(), xr.data(), ur.data(), p.Q.data(), p.R.data(), p.S.data(),
+                                     P.data(), p.umin.data(), p.umax.data(), 0.1, 1e-6);
+    };
+    if (walk("almpc_relin_fnn_setup", n, m, N, batch, 0, fb, state_box, relin)) return 1;
+    if (walk("almpc_relin_fnn_setup (structured)", n, m, N, batch, ALMPC_FLAG_STRUCTURED, fb, nothing, relin)) return 1;
+    if (walk("almpc_sqp_fnn_setup", n, m, N, batch, 0, fb, relin, [&](almpc_handle* h) {   // on a handle that held the re-linearisation pipeline
+            const int rc = almpc_set_state_box(h, p.xmin.data(), p.xmax.data());
+            return rc != ALMPC_OK ? rc : almpc_sqp_fnn_setup(h, Hn, L, 1, W_in.data(), W_h.data(), b_h.data(), W_out.data(), xr.data(), ur.data(), p.Q.data(),
+                                                             p.R.data(), nullptr, P.data(), 0, p.umin.data(), p.umax.data(), 0.1, 1e-6);
+        })) return 1;
+    if (walk("almpc_update_initialization_async", n, m, N, batch, 0, fb, nothing, [&](almpc_handle* h) { return almpc_update_initialization_async(h, x0.data()); }))
+        return 1;
+    }
+    std::printf("alloc failures ok\n");
+    return 0;
+}
+
 int main(int argc, char** argv) {
     {   // every almpc_create below reads the switches: none may come in from the caller's environment
         std::vector<std::string> inherited;
@@ -89,6 +192,7 @@ int main(int argc, char** argv) {
         for (const std::string& name : inherited) unsetenv(name.c_str());
     }
     if (argc > 1 && fake_hip_trace_to(argv[1])) { std::fprintf(stderr, "cannot write %s\n", argv[1]); return 1; }
+    if (argc > 2 && std::strcmp(argv[2], "alloc-failures") == 0) return alloc_failures();
     const char* const eq = argc > 2 ? std::strchr(argv[2], '=') : nullptr;
     if (argc > 2 && (!eq || setenv(std::string(argv[2], eq - argv[2]).c_str(), eq + 1, 1))) { std::fprintf(stderr, "not NAME=VALUE: %s\n", argv[2]); return 1; }
     almpc_handle* h = nullptr;
@@ -296,6 +400,7 @@ int main(int argc, char** argv) {
         almpc_destroy(h); h = nullptr;
     }
     fake_hip_trace_close();
+    if (argc > 1 && fake_hip_dump_allocs((std::string(argv[1]) + ".allocs").c_str())) { std::fprintf(stderr, "cannot write %s.allocs\n", argv[1]); return 1; }
     std::printf("host logic ok: %ld launches\n", fake_hip_launch_count());
     return 0;
 }

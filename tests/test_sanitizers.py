@@ -161,3 +161,35 @@ def test_every_switch_steers_the_launches_it_steered_when_read_at_call_time(tmp_
         diff = list(difflib.unified_diff(base, lines, n=0, lineterm=""))[2:]
         assert diff == recorded[key], (name, next((a, b) for a, b in zip(diff + [""] * len(recorded[key]), recorded[key] + [""] * len(diff)) if a != b))
         assert (len(diff) == 0) == (name in SWITCHES_WITHOUT_TRACE), name
+
+
+@pytest.mark.timeout(900)
+def test_device_and_pinned_allocations_are_the_recorded_ones(tmp_path, host_logic_exe):
+    """The byte size of every hipMalloc and, separately, every hipHostMalloc of the driver's plain run, as sorted lists (group handles
+    design on threads of their own): tests/golden/host_alloc_sizes.txt holds what the last commit that allocated and freed every
+    buffer by hand asked for, recorded with this driver and this fake runtime.  Counts and sizes must both match: no buffer grew,
+    shrank (the 64 bytes of slack behind a device buffer are read by kernels), or is allocated more or fewer times."""
+    r, _ = _launch_trace(host_logic_exe, tmp_path / "launches.txt")
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    got = (tmp_path / "launches.txt.allocs").read_text().splitlines()
+    golden = (Path(ROOT) / "tests" / "golden" / "host_alloc_sizes.txt").read_text().splitlines()
+    assert [ln for ln in got if ln.startswith("hip")] == [ln for ln in golden if ln.startswith("hip")]   # the two counts
+    assert got == golden, next(f"line {i + 1}: {a!r} != golden {b!r}" for i, (a, b) in enumerate(zip(got + [""] * len(golden), golden + [""] * len(got))) if a != b)
+
+
+@pytest.mark.timeout(900)
+def test_a_failed_allocation_is_an_error_and_leaves_nothing_behind(tmp_path, host_logic_exe):
+    """The driver's "alloc-failures" mode: almpc_create, the shared (state box + terminal equality), per-instance and time-varying
+    designs, almpc_set_reference on per-instance models with S, both re-linearisation setups, the SQP setup on a handle that held a
+    re-linearisation pipeline and the first almpc_update_initialization_async, each with its k-th hipMalloc / hipHostMalloc failing
+    for k = 1, 2, ... until the call gets through.  Every call whose allocation failed returns ALMPC_ERR_HIP (almpc_create: an error
+    and no handle) and no other call fails: the driver stops at the first k that does otherwise.  Each entry point is walked with the
+    redo of undecided instances asked for (almpc_set_structured_fallback 1: a stage-wise setup that cannot allocate is the call's
+    error, where the default goes on without the redo) and with it off.  The handle is destroyed afterwards, and the whole run is
+    clean under ASan, UBSan and LSan: nothing leaked, nothing freed twice."""
+    r = _run([host_logic_exe, str(tmp_path / "launches.txt"), "alloc-failures"])
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert "ERROR" not in r.stderr and "runtime error" not in r.stderr
+    assert "alloc failures ok" in r.stdout
+    walked = dict(ln.rsplit(": ", 1) for ln in r.stdout.splitlines() if ln.endswith(" allocations"))
+    assert len(walked) == 1 + 2 * 8 and all(0 < int(v.split()[0]) < 100 for v in walked.values()), walked
