@@ -114,6 +114,16 @@ def load():
     L.almpc_advance_plant.restype = ctypes.c_int
     L.almpc_dare.argtypes = [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]
     L.almpc_dare.restype = ctypes.c_int
+    L.almpc_dare_batched.argtypes = [ctypes.c_int] * 4 + [_dp] * 5 + [_ip]
+    L.almpc_dare_batched.restype = ctypes.c_int
+    L.almpc_set_terminal_weight.argtypes = [_hp, ctypes.c_int]
+    L.almpc_set_terminal_weight.restype = ctypes.c_int
+    L.almpc_relin_fnn_terminal_status.argtypes = [_hp, _ip]
+    L.almpc_relin_fnn_terminal_status.restype = ctypes.c_int
+    L.almpc_get_terminal_weight_instance.argtypes = [_hp, ctypes.c_int, _dp]
+    L.almpc_get_terminal_weight_instance.restype = ctypes.c_int
+    L.almpc_group_set_terminal_weight.argtypes = [_hp, ctypes.c_int]
+    L.almpc_group_set_terminal_weight.restype = ctypes.c_int
     L.almpc_set_structured_fallback.argtypes = [_hp, ctypes.c_int]
     L.almpc_relin_fnn_setup.argtypes = [_hp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_dp] * 12 + [ctypes.c_double, ctypes.c_double]
     L.almpc_relin_fnn_setup.restype = ctypes.c_int
@@ -264,6 +274,39 @@ def dare(A, B, Q, R):
     if rc != ALMPC_OK:
         raise AlmpcError(rc, "almpc_dare")
     return P
+
+
+TERMINAL_WEIGHT_MODES = {"given": 0, "dare_device": 1}  # almpc.h: ALMPC_TERMINAL_*
+
+
+def _terminal_mode(mode):
+    if isinstance(mode, str):
+        if mode not in TERMINAL_WEIGHT_MODES:
+            raise ValueError(f"unknown terminal-weight mode {mode!r}; choose from {sorted(TERMINAL_WEIGHT_MODES)}")
+        return TERMINAL_WEIGHT_MODES[mode]
+    return int(mode)
+
+
+def dare_batched(A, B, Q, R, device=0, P_init=None):
+    """P_i = DARE(A_i, B_i, Q, R) on the GPU (almpc_dare_batched): A (batch, n, n), B (batch, n, m), shared Q, R.  Returns
+    (P (batch, n, n), status (batch,) int32); status 0 = solved, else slot i of P is what P_init held (NaN without P_init)."""
+    L = load()
+    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    if A.ndim != 3 or B.ndim != 3 or A.shape[0] != B.shape[0] or A.shape[1] != A.shape[2] or B.shape[1] != A.shape[1]:
+        raise ValueError(f"expected A (batch, n, n) and B (batch, n, m), got {A.shape} and {B.shape}")
+    b, n, m = B.shape
+    Ac = np.ascontiguousarray(A.transpose(0, 2, 1))  # column-major blocks
+    Bc = np.ascontiguousarray(B.transpose(0, 2, 1))
+    Q, R = _colmajor(Q, (n, n)), _colmajor(R, (m, m))
+    if P_init is None:
+        P = np.full((b, n, n), np.nan)
+    else:
+        P = np.ascontiguousarray(np.asarray(P_init, dtype=np.float64).reshape(b, n, n).transpose(0, 2, 1))
+    st = np.zeros(b, dtype=np.int32)
+    rc = L.almpc_dare_batched(int(device), n, m, b, _ptr(Ac), _ptr(Bc), _ptr(Q), _ptr(R), _ptr(P), st.ctypes.data_as(_ip))
+    if rc != ALMPC_OK:
+        raise AlmpcError(rc, "almpc_dare_batched")
+    return np.ascontiguousarray(P.transpose(0, 2, 1)), st
 
 
 FNN_ACTIVATIONS = {"identity": 0, "relu": 1, "tanh": 2, "sigmoid": 3, "swish": 4}
@@ -634,6 +677,23 @@ class Solver:
         self._check(self.L.almpc_get_design_instance(self.h, int(i), _ptr(H), _ptr(F), _ptr(d)))
         return dict(H=H, F=F, d=d)
 
+    def set_terminal_weight(self, mode):
+        """Before a design: "given" / 0 (default) or "dare_device" / 1 -- design_batched(P=None) and every relin_fnn step take each
+        instance's terminal weight from the DARE of its own model, solved on the device (almpc_set_terminal_weight)."""
+        self._check(self.L.almpc_set_terminal_weight(self.h, _terminal_mode(mode)))
+
+    def relin_terminal_status(self):
+        """(batch,) int32 of the last relin_fnn step with the mode on: 0 = the instance's own DARE solution, 1 = the setup's P."""
+        out = np.zeros(self.batch, dtype=np.int32)
+        self._check(self.L.almpc_relin_fnn_terminal_status(self.h, out.ctypes.data_as(_ip)))
+        return out
+
+    def terminal_weight_instance(self, i):
+        """(n, n) terminal weight instance i was designed with (almpc_get_terminal_weight_instance)."""
+        P = np.empty((self.n, self.n), order="F")
+        self._check(self.L.almpc_get_terminal_weight_instance(self.h, int(i), _ptr(P)))
+        return P
+
     def start_from(self, other: "Solver"):
         """Structured handle: the next calculate starts from `other`'s last inputs (same batch, horizon <= this one's): horizon
         continuation / chaining of solvers (almpc_set_start_from)."""
@@ -828,6 +888,19 @@ class Group:
     def _check(self, rc):
         if rc != ALMPC_OK:
             raise AlmpcError(rc, (self.L.almpc_group_last_error(self.g) or b"").decode())
+
+    def set_terminal_weight(self, mode):
+        """Solver.set_terminal_weight on every handle (almpc_group_set_terminal_weight)."""
+        self._check(self.L.almpc_group_set_terminal_weight(self.g, _terminal_mode(mode)))
+
+    def relin_terminal_status(self):
+        return np.concatenate([h.relin_terminal_status() for h in self.handles])
+
+    def terminal_weight_instance(self, i):
+        for h, (f, c) in zip(self.handles, self.shards):
+            if f <= i < f + c:
+                return h.terminal_weight_instance(i - f)
+        raise IndexError(i)
 
     def _state_rows(self, xmin, xmax, terminal):
         if (xmin is None) != (xmax is None):

@@ -263,6 +263,8 @@ def proceed_controller(system, mpc_controller_type: str, mpc_horizon: int, mpc_s
 def _model_predictive_control_design(system, horizon: int, sample_time: int, references: ReferencesStateInput, **kws_):
     if isinstance(system, ConstrainedBlackBoxControlDiscreteSystem):
         return _design_blackbox(system, horizon, sample_time, references, **kws_)
+    if _kws(kws_).get("mpc_terminal_weight", "reference") != "reference":   # (a linear system is never re-linearised)
+        raise ValueError("mpc_terminal_weight = 'step' needs a black-box model with mpc_linearization = 'step'")
     return _design_linear(system, horizon, sample_time, references, **kws_)
 
 
@@ -275,11 +277,20 @@ def _design_blackbox(system: ConstrainedBlackBoxControlDiscreteSystem, horizon: 
     Extension of this build (BASELINE.json configs[3]), kw mpc_linearization = "step": the dynamics are re-linearised at every
     instance's own current state (and the first input reference) in update_initialization!, each instance gets the
     reference's QP for its own (A_i, B_i) (almpc_design_batched); P stays the design-time terminal weight.  The default
-    "reference" is the reference's behaviour: one linearisation at design time, shared by the batch."""
+    "reference" is the reference's behaviour: one linearisation at design time, shared by the batch.
+
+    With it, kw mpc_terminal_weight = "step": the terminal weight follows the model too -- every step solves DARE(A_i, B_i, Q, R) of
+    the step's own linearisation on the device (almpc_set_terminal_weight); the design-time P serves an instance whose linearisation
+    has no stabilising solution (modeler.solver.relin_terminal_status() says which).  The default "reference" keeps the design-time P."""
     kws = _kws(kws_)
     lin_mode = kws.get("mpc_linearization", "reference")
     if lin_mode not in ("reference", "step"):
         raise ValueError("mpc_linearization must be 'reference' or 'step'")
+    tw_mode = kws.get("mpc_terminal_weight", "reference")
+    if tw_mode not in ("reference", "step"):
+        raise ValueError("mpc_terminal_weight must be 'reference' or 'step'")
+    if tw_mode == "step" and lin_mode != "step":
+        raise ValueError("mpc_terminal_weight = 'step' needs mpc_linearization = 'step'")
     net = _net_kind(system.f)   # Fnn, Icnn, ResNet, PolyNet, DenseNet; the other families raise NotImplementedError with the reason
     dev = int(kws.get("mpc_device", 0))
     x_ref, u_ref = np.asarray(references.x, dtype=np.float64), np.asarray(references.u, dtype=np.float64)
@@ -301,6 +312,7 @@ def _design_blackbox(system: ConstrainedBlackBoxControlDiscreteSystem, horizon: 
         # multiple-shooting form by the stage-wise solvers: the library's default; mpc_structured_fallback = False switches it off
         if not kws.get("mpc_structured_fallback", True):
             mod.solver._check(mod.solver.L.almpc_set_structured_fallback(mod.solver.h, 0))
+        mod.solver.set_terminal_weight("dare_device" if tw_mode == "step" else "given")
         # device-resident pipeline (almpc_relin_fnn_*): Jacobians -> per-instance designs -> step, no host pointers per step
         setup = mod.solver.relin_densenet_setup if net == "densenet" else functools.partial(mod.solver.relin_fnn_setup, net=net)
         setup(f.W_in, f.W_h, f.b_h, f.W_out, references.x, references.u, weights.Q, weights.R, weights.S, np.array(P),

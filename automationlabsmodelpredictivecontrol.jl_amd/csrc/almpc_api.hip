@@ -13,6 +13,7 @@
 #include "almpc_comm.hip.h"
 #include "almpc_riccati.hip.h"
 #include "almpc_sdual.hip.h"
+#include "almpc_dare.hip.h"
 #include "almpc_host_math.h"
 #include "almpc_switches.h"
 #include "almpc_devbuf.h"
@@ -32,6 +33,7 @@
 #include "instances/instance.inc"
 #include "instances/design_a.inc"
 #include "instances/design_b.inc"
+#include "instances/dare.inc"
 #undef ALMPC_KERNEL_INSTANCE
 #endif
 
@@ -196,6 +198,13 @@ struct almpc_handle {
     hipEvent_t ev_guess = nullptr, ev_guess_done = nullptr;
     long rP_stride = 0;   // per-instance terminal weights (batched designs): doubles between instances of bP, else 0 with rP
     bool r_batched_P = false;
+    // almpc_set_terminal_weight: 1 = the terminal weight of a per-instance design is the instance's own DARE solution, computed on the
+    // device (k_dare, csrc/almpc_dare.hip.h).  Its buffers exist only once a design or setup has run with the mode on.
+    int terminal_mode = 0;
+    bool t_step = false;        // the re-linearisation pipeline was set up with the mode on: every step solves its own DAREs into bP
+    long bP_stride = 0;         // doubles between the instances of bP as the last per-instance design left it (0: one shared matrix)
+    DevBuf<double> tP;          // [n][n] the setup's P: terminal weight of an instance whose own DARE has no stabilising solution
+    DevBuf<int32_t> tStat;      // [batch] k_dare's status words of the last design / step
     // stage-wise dual active-set solve (k_sdual, csrc/almpc_sdual.hip.h): input box, state box, terminal equality and S in the
     // multiple-shooting form; stage records of the unconstrained problem (shared: host Riccati at design time)
     struct Sd {
@@ -668,6 +677,81 @@ int sdual_setup_batched(almpc_handle* h, const hm::mat& Qm, const hm::mat& Rm, c
     sd.has_base = false; sd.base_stride = 0;
     sd.ready = true;
     return ALMPC_OK;
+}
+
+// k_dare: P_i = DARE(A_i, B_i, Q, R) of p.batch models, one wave per instance (csrc/almpc_dare.hip.h).  Launch only.
+hipError_t launch_dare(DareParams p, hipStream_t st) {
+    p.lds_per_wave = dare_lds_doubles(p.n, p.m);
+    const int waves = dare_waves(p.n, p.m), d = p.n > p.m ? p.n : p.m;
+    const size_t lds = (size_t)p.lds_per_wave * sizeof(double) * waves;
+    const int wgs = (p.batch + waves - 1) / waves;
+#define DARE_RL(RL_)                                                                              \
+    do {                                                                                          \
+        const hipError_t e_ = ensure_dyn_lds(reinterpret_cast<const void*>(k_dare<RL_>), lds);    \
+        if (e_ != hipSuccess) return e_;                                                          \
+        hipLaunchKernelGGL((k_dare<RL_>), dim3(wgs), dim3(64 * waves), lds, st, p);               \
+    } while (0)
+    if (d <= 16) DARE_RL(16);
+    else if (d <= 32) DARE_RL(32);
+    else DARE_RL(64);
+#undef DARE_RL
+    return hipGetLastError();
+}
+
+// What k_dare cannot be given: a shape beyond its LDS layout, or an R that hm::dare refuses (singular), or R[1,1] == 0 -- the
+// reference's branch rule then drops R from the cost and no DARE is left.  ALMPC_OK, or the error code with *why set.
+int dare_device_check(int n, int m, const hm::mat& Rm, bool branch_rule, const char** why) {
+    if (n > DARE_MAX_N || m > DARE_MAX_M) { *why = "DARE on the device: n <= 48 and m <= 16 (k_dare)"; return ALMPC_ERR_UNSUPPORTED; }
+    if (branch_rule && Rm[0] == 0.0) { *why = "DARE on the device: R[1,1] == 0 drops R from the cost, the equation is singular"; return ALMPC_ERR_NUMERIC; }
+    hm::mat I = hm::eye(m);
+    if (!hm::lu_solve(Rm, I, m, m)) { *why = "DARE on the device: R is singular"; return ALMPC_ERR_NUMERIC; }
+    return ALMPC_OK;
+}
+
+// almpc_set_terminal_weight(ALMPC_TERMINAL_DARE_DEVICE), almpc_design_batched(P = NULL): bP_i = DARE(bA_i, bB_i, Q, R) by k_dare on
+// the handle's stream, behind the uploads of the models and weights (dQ, dR: device).  Waits for it and reports the first instance
+// without a stabilising solution as the host loop does.  Pfirst: host copy of instance 0's weight.
+int design_dare_device(almpc_handle* h, const double* dQ, const double* dR, const hm::mat& Rm, hm::mat& Pfirst) {
+    const int n = h->n, m = h->m;
+    const size_t b = (size_t)h->batch;
+    const char* why = "";
+    { const int rc_ = dare_device_check(n, m, Rm, true, &why); if (rc_ != ALMPC_OK) return fail(h, rc_, std::string("design_batched: ") + why); }
+    HIP_TRY(h, h->tStat.once(b));
+    DareParams dp;
+    dp.n = n; dp.m = m; dp.batch = h->batch;
+    dp.A = h->bA; dp.A_stride = (long)n * n; dp.B = h->bB; dp.B_stride = (long)n * m; dp.Q = dQ; dp.R = dR;
+    dp.P = h->bP; dp.P_stride = (long)n * n; dp.fallback = nullptr; dp.status = h->tStat; dp.lds_per_wave = 0;
+    HIP_TRY(h, launch_dare(dp, h->stream));
+    std::vector<int32_t> stt(b, 0);
+    HIP_TRY(h, hipMemcpyAsync(stt.data(), h->tStat, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < b; ++i)
+        if (stt[i] != 0) return fail(h, ALMPC_ERR_NUMERIC, "design_batched: DARE did not converge for instance " + std::to_string(i));
+    Pfirst.resize((size_t)n * n);
+    HIP_TRY(h, hipMemcpy(Pfirst.data(), h->bP, Pfirst.size() * sizeof(double), hipMemcpyDeviceToHost));
+    return ALMPC_OK;
+}
+
+// The re-linearisation pipeline with the mode on, setup: the checks, the setup's P in a buffer of its own and the status words
+int relin_terminal_setup(almpc_handle* h, const hm::mat& Rm, const hm::mat& Pm) {
+    h->t_step = false;
+    if (h->terminal_mode != ALMPC_TERMINAL_DARE_DEVICE) return ALMPC_OK;
+    const char* why = "";
+    { const int rc_ = dare_device_check(h->n, h->m, Rm, true, &why); if (rc_ != ALMPC_OK) return fail(h, rc_, std::string("relin_fnn_setup: ") + why); }
+    HIP_TRY(h, h->tP.upload(Pm.data(), Pm.size()));
+    HIP_TRY(h, h->tStat.once((size_t)h->batch));
+    HIP_TRY(h, hipMemset(h->tStat, 0, (size_t)h->batch * sizeof(int32_t)));
+    h->t_step = true;
+    return ALMPC_OK;
+}
+// ... and step: bP_i = DARE(bA_i, bB_i, Q, R) of the step's Jacobians, the setup's P where there is none.  Launch only.
+hipError_t launch_relin_dare(almpc_handle* h, const double* dQ, const double* dR) {
+    const int n = h->n, m = h->m;
+    DareParams dp;
+    dp.n = n; dp.m = m; dp.batch = h->batch;
+    dp.A = h->bA; dp.A_stride = (long)n * n; dp.B = h->bB; dp.B_stride = (long)n * m; dp.Q = dQ; dp.R = dR;
+    dp.P = h->bP; dp.P_stride = (long)n * n; dp.fallback = h->tP; dp.status = h->tStat; dp.lds_per_wave = 0;
+    return launch_dare(dp, h->stream);
 }
 
 // k_sgains over the handle's per-instance models (bA, bB; terminal weights bP, shared or per instance): all instances
@@ -1686,9 +1770,11 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
                 for (int i = 0; i < j; ++i) { const double v = 0.5 * (Sm[(size_t)j * m + i] + Sm[(size_t)i * m + j]); Sm[(size_t)j * m + i] = Sm[(size_t)i * m + j] = v; }
         }
         const bool p_inst = P ? (P_per_instance != 0) : true;
+        const bool dev_dare = !P && h->terminal_mode == ALMPC_TERMINAL_DARE_DEVICE;   // (k_dare on the uploaded models, below)
+        h->t_step = false;
         hm::mat Pall;
         if (P) Pall.assign(P, P + (p_inst ? b : 1) * (size_t)n * n);
-        else {
+        else if (!dev_dare) {
             Pall.resize(b * (size_t)n * n);
             for (size_t i = 0; i < b; ++i) {
                 hm::mat Am(A_batch + i * n * n, A_batch + (i + 1) * n * n), Bm(B_batch + i * n * m, B_batch + (i + 1) * n * m), Pm;
@@ -1701,8 +1787,17 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
         HIP_TRY(h, h->bP.once(b * n * n));
         HIP_TRY(h, hipMemcpy(h->bA, A_batch, b * n * n * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(h->bB, B_batch, b * n * m * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(h->bP, Pall.data(), Pall.size() * sizeof(double), hipMemcpyHostToDevice));
+        if (dev_dare) {
+            HIP_TRY(h, h->wQ.once((size_t)n * n));
+            HIP_TRY(h, h->wR.once((size_t)m * m));
+            HIP_TRY(h, hipMemcpy(h->wQ, Qm.data(), Qm.size() * sizeof(double), hipMemcpyHostToDevice));
+            HIP_TRY(h, hipMemcpy(h->wR, Rm.data(), Rm.size() * sizeof(double), hipMemcpyHostToDevice));
+            const int rc_ = design_dare_device(h, h->wQ, h->wR, Rm, Pall);
+            if (rc_ != ALMPC_OK) return rc_;
+        } else
+            HIP_TRY(h, hipMemcpy(h->bP, Pall.data(), Pall.size() * sizeof(double), hipMemcpyHostToDevice));
         h->batched = true; h->ltv = false; h->r_batched_P = true; h->rP_stride = p_inst ? (long)n * n : 0;
+        h->bP_stride = h->rP_stride;
         const double* bxmin = h->boxmin.empty() ? nullptr : h->boxmin.data();
         const double* bxmax = h->boxmax.empty() ? nullptr : h->boxmax.data();
         h->sd.ready = false;
@@ -1762,9 +1857,12 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
     symmetrise(Qm, n); symmetrise(Rm, m); symmetrise(Sm, m);
     // terminal weight: given (shared or per instance), else DARE of every instance's model (src/sub/design_mpc.jl:327)
     const bool p_inst = P ? (P_per_instance != 0) : true;
+    // (almpc_set_terminal_weight: k_dare on the uploaded models instead of the host loop, behind the uploads below; its P_i are symmetric)
+    const bool dev_dare = !P && !ltv && h->terminal_mode == ALMPC_TERMINAL_DARE_DEVICE;
+    h->t_step = false;
     hm::mat Pall;
     if (P) Pall.assign(P, P + (p_inst ? b : 1) * (size_t)n * n);
-    else {
+    else if (!dev_dare) {
         Pall.resize(b * (size_t)n * n);
         for (size_t i = 0; i < b; ++i) {
             hm::mat Am(A_batch + i * n * n, A_batch + (i + 1) * n * n), Bm(B_batch + i * n * m, B_batch + (i + 1) * n * m), Pm;
@@ -1772,12 +1870,12 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
             std::copy(Pm.begin(), Pm.end(), Pall.begin() + i * n * n);
         }
     }
-    for (size_t i = 0; i < (p_inst ? b : 1); ++i) {
+    for (size_t i = 0; i < (dev_dare ? 0 : p_inst ? b : 1); ++i) {
         hm::mat Pm(Pall.begin() + i * n * n, Pall.begin() + (i + 1) * n * n);
         symmetrise(Pm, n);
         std::copy(Pm.begin(), Pm.end(), Pall.begin() + i * n * n);
     }
-    h->P.assign(Pall.begin(), Pall.begin() + (size_t)n * n);
+    if (!dev_dare) h->P.assign(Pall.begin(), Pall.begin() + (size_t)n * n);
     h->hS = Sm;
     h->rho = rho; h->sigma = sigma;
     const int useR = Rm[0] != 0.0, useS = useR && Sm[0] != 0.0;
@@ -1802,12 +1900,18 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
     } while (0)
     BTRY(hipMemcpyAsync(h->bA, A_batch, b * n * n * sizeof(double), hipMemcpyHostToDevice, st));
     BTRY(hipMemcpyAsync(h->bB, B_batch, b * n * m * sizeof(double), hipMemcpyHostToDevice, st));
-    BTRY(hipMemcpyAsync(h->bP, Pall.data(), Pall.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    if (!dev_dare) BTRY(hipMemcpyAsync(h->bP, Pall.data(), Pall.size() * sizeof(double), hipMemcpyHostToDevice, st));
     BTRY(hipMemcpyAsync(dQ, Qm.data(), Qm.size() * sizeof(double), hipMemcpyHostToDevice, st));
     BTRY(hipMemcpyAsync(dR, Rm.data(), Rm.size() * sizeof(double), hipMemcpyHostToDevice, st));
     BTRY(hipMemcpyAsync(dS, Sm.data(), Sm.size() * sizeof(double), hipMemcpyHostToDevice, st));
     BTRY(hipMemsetAsync(h->bFlag, 0, b * sizeof(int), st));
     tr("weights alloc + copies queued");
+    h->bP_stride = p_inst ? (long)n * n : 0;
+    if (dev_dare) {
+        const int rc_ = design_dare_device(h, dQ, dR, Rm, h->P);
+        if (rc_ != ALMPC_OK) return rc_;
+        tr("k_dare");
+    }
     const DesignStrides ds = batched_strides(h, p_inst);
     const unsigned gb = (unsigned)b;
     if (ltv) {
@@ -1950,7 +2054,9 @@ int relin_setup_structured(almpc_handle* h, int H, int L, int net, int activatio
     HIP_TRY(h, hipMemset(h->bA, 0, b * n * n * sizeof(double)));
     HIP_TRY(h, hipMemset(h->bB, 0, b * n * m * sizeof(double)));
     HIP_TRY(h, hipMemcpy(h->bP, Pm.data(), Pm.size() * sizeof(double), hipMemcpyHostToDevice));
-    h->batched = true; h->ltv = false; h->r_batched_P = true; h->rP_stride = 0;
+    { const int rc_ = relin_terminal_setup(h, Rm, Pm); if (rc_ != ALMPC_OK) return rc_; }
+    h->batched = true; h->ltv = false; h->r_batched_P = true; h->rP_stride = h->t_step ? (long)n * n : 0;   // (t_step: one P_i per step, k_dare)
+    h->bP_stride = h->rP_stride;
     h->sd.ready = false;
     {
         const int rc_ = sdual_setup_batched(h, Qm, Rm, useS ? &Sm : nullptr, false, h->boxmin.empty() ? nullptr : h->boxmin.data(),
@@ -2659,6 +2765,8 @@ static int relin_net_setup(almpc_handle* h, bool dense, int H, int L, int activa
     HIP_TRY(h, q.Q.upload(Qm.data(), Qm.size())); HIP_TRY(h, q.R.upload(Rm.data(), Rm.size())); HIP_TRY(h, q.S.upload(Sm.data(), Sm.size()));
     HIP_TRY(h, q.gS.upload(gS.data(), gS.size()));
     HIP_TRY(h, hipMemcpy(h->bP, Pm.data(), Pm.size() * sizeof(double), hipMemcpyHostToDevice));
+    { const int rc_ = relin_terminal_setup(h, Rm, Pm); if (rc_ != ALMPC_OK) return rc_; }
+    h->bP_stride = h->t_step ? (long)n * n : 0;   // (t_step: one P_i per step, k_dare)
     HIP_TRY(h, hipMemcpy(h->dUmin, umin, m * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->dUmax, umax, m * sizeof(double), hipMemcpyHostToDevice));
     // shared references; the scaled input-rate gradient fS_i = d_i .* gS and v0S_i = -G_i fS_i are per instance (re-made every step)
@@ -2680,7 +2788,7 @@ static int relin_net_setup(almpc_handle* h, bool dense, int H, int L, int activa
     h->state_valid = true;
     h->sd.ready = false;
     if (h->fallback) {
-        h->r_batched_P = true; h->rP_stride = 0;
+        h->r_batched_P = true; h->rP_stride = h->bP_stride;
         if (sdual_shape_ok(n, m, N, q.useS != 0)) {
             // (the models change with every step: the records of the instances a step leaves unsolved are computed in that step)
             const int rc_ = sdual_setup_batched(h, Qm, Rm, q.useS ? &Sm : nullptr, false,
@@ -2732,6 +2840,7 @@ int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
         // limit (.../fnn/mpc_modeler_implementation_fnn.jl:23-58) and neither has this route.
         HIP_TRY(h, launch_fnn_jacobian(h->sw, fp, q.net, h->num_cus, st));
         if (timing) HIP_TRY(h, hipEventRecord(q.ev[1], st));
+        if (h->t_step) HIP_TRY(h, launch_relin_dare(h, h->sd.dQ, h->sd.dR));   // every instance's own terminal weight, in front of its records
         HIP_TRY(h, launch_sgains(h, 0));
         if (timing) HIP_TRY(h, hipEventRecord(q.ev[2], st));
         h->designed = true;
@@ -2745,14 +2854,17 @@ int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
         if (timing) HIP_TRY(h, hipEventRecord(q.ev[3], st));
         return ALMPC_OK;
     }
-    const bool fuse_jac = design_fuses_fnn(h, q.H, q.L, q.net);   // the design kernel's workgroups linearise their own instance
+    // (the design kernel's workgroups linearise their own instance -- unless every instance's terminal weight is the DARE solution of
+    // its Jacobians, almpc_set_terminal_weight: P_i has to be there before the design, so the Jacobians get their own launch in front)
+    const bool fuse_jac = design_fuses_fnn(h, q.H, q.L, q.net) && !h->t_step;
     if (!fuse_jac) HIP_TRY(h, launch_fnn_jacobian(h->sw, fp, q.net, h->num_cus, st));
     if (timing) HIP_TRY(h, hipEventRecord(q.ev[1], st));
+    if (h->t_step) HIP_TRY(h, launch_relin_dare(h, q.Q, q.R));
     // 2. the reference's QP for every (A_i, B_i): H_i, F_i, scaling, inverses, V_i; reference-dependent vectors.  A warm step
     // (opts.warm_start = 1 after a solved step) takes its working-set guess from the previous step's inputs shifted by one stage
     // instead of an ADMM phase, and the design then needs one inverse (G_i) instead of two
     const bool warm = opts && opts->warm_start && q.have_prev && (!opts || opts->polish);
-    const DesignStrides ds = batched_strides(h, false);
+    const DesignStrides ds = batched_strides(h, h->t_step);
     {
         const hipError_t e_ = launch_batched_design(h, ds, q.useR, q.useS, q.Q, q.R, q.S, h->rho, h->sigma, warm, fuse_jac ? &fp : nullptr);
         if (e_ != hipSuccess) return fail(h, ALMPC_ERR_HIP, std::string("relin design: ") + hipGetErrorString(e_));
@@ -2960,7 +3072,7 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
     h->xref_stride = (long)n * (N + 1); h->uref_stride = nz; h->fS_stride = nz;
     h->designed = false;  // becomes true with the first iteration's design
     h->batched = true; h->ltv = true;
-    h->r_batched_P = true; h->rP_stride = q.sP;
+    h->r_batched_P = true; h->rP_stride = q.sP; h->bP_stride = q.sP; h->t_step = false;
     h->sd.ready = false;
     if (h->fallback || q.structured_qp) {
         // stage-wise QP of an iteration: k_sgains (stage records, defects' value-function terms, cost terms) + k_sdual; behind it, for
@@ -3396,6 +3508,40 @@ int almpc_get_design_instance(almpc_handle* h, int instance, double* H, double* 
     return ALMPC_OK;
 }
 
+int almpc_set_terminal_weight(almpc_handle* h, int mode) {
+    if (!h) return ALMPC_ERR_INVALID;
+    if (mode != ALMPC_TERMINAL_GIVEN && mode != ALMPC_TERMINAL_DARE_DEVICE) return fail(h, ALMPC_ERR_INVALID, "set_terminal_weight: mode must be 0 or 1");
+    h->terminal_mode = mode;   // (read by the next almpc_design_batched / almpc_relin_fnn_setup)
+    return ALMPC_OK;
+}
+
+int almpc_relin_fnn_terminal_status(almpc_handle* h, int32_t* st) {
+    if (!h || !st) return ALMPC_ERR_INVALID;
+    if (!h->relin.ready || !h->t_step)
+        return fail(h, ALMPC_ERR_NOT_DESIGNED, "relin_fnn_terminal_status needs almpc_set_terminal_weight(ALMPC_TERMINAL_DARE_DEVICE) before almpc_relin_fnn_setup");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(st, h->tStat, (size_t)h->batch * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int i = 0; i < h->batch; ++i) st[i] = st[i] != 0 ? 1 : 0;
+    return ALMPC_OK;
+}
+
+int almpc_get_terminal_weight_instance(almpc_handle* h, int instance, double* P) {
+    if (!h || !P) return ALMPC_ERR_INVALID;
+    if (!h->designed && !h->relin.ready) return fail(h, ALMPC_ERR_NOT_DESIGNED, "get_terminal_weight_instance before a design");
+    if (instance < 0 || instance >= h->batch) return fail(h, ALMPC_ERR_INVALID, "get_terminal_weight_instance: instance out of range");
+    const size_t nn = (size_t)h->n * h->n;
+    if (!h->batched || !h->bP) {   // shared model: one weight
+        if (h->P.size() != nn) return fail(h, ALMPC_ERR_NOT_DESIGNED, "get_terminal_weight_instance before a design");
+        std::memcpy(P, h->P.data(), nn * sizeof(double));
+        return ALMPC_OK;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(P, h->bP + (size_t)instance * (size_t)h->bP_stride, nn * sizeof(double), hipMemcpyDeviceToHost));
+    return ALMPC_OK;
+}
+
 int almpc_set_reference(almpc_handle* h, const double* xref, const double* uref, int per_instance) {
     if (!h) return ALMPC_ERR_INVALID;
     if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, "set_reference before design");
@@ -3662,6 +3808,37 @@ int almpc_dare(int n, int m, const double* A, const double* B, const double* Q, 
     hm::mat Am(A, A + (size_t)n * n), Bm(B, B + (size_t)n * m), Qm(Q, Q + (size_t)n * n), Rm(R, R + (size_t)m * m), Pm;
     if (!hm::dare(Am, Bm, Qm, Rm, n, m, Pm)) return ALMPC_ERR_NUMERIC;
     std::memcpy(P, Pm.data(), (size_t)n * n * sizeof(double));
+    return ALMPC_OK;
+}
+
+int almpc_dare_batched(int device_id, int n, int m, int batch, const double* A_batch, const double* B_batch, const double* Q,
+                       const double* R, double* P_batch, int32_t* status) {
+    if (n < 1 || m < 1 || batch < 1 || !A_batch || !B_batch || !Q || !R || !P_batch || !status) return ALMPC_ERR_INVALID;
+    if (n > DARE_MAX_N || m > DARE_MAX_M) return ALMPC_ERR_UNSUPPORTED;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device_id < 0 || device_id >= count) return ALMPC_ERR_NO_DEVICE;
+    {
+        const char* why = "";
+        const int rc_ = dare_device_check(n, m, hm::mat(R, R + (size_t)m * m), false, &why);
+        if (rc_ != ALMPC_OK) return rc_;
+    }
+    if (hipSetDevice(device_id) != hipSuccess) return ALMPC_ERR_HIP;
+    using Tight = DevBuf<double, Mem::DeviceTight>;
+    const size_t b = (size_t)batch, nn = (size_t)n * n, nm = (size_t)n * m;
+    Tight dA, dB, dQ, dR, dP;
+    DevBuf<int32_t, Mem::DeviceTight> dSt;
+    // (P_batch goes up as well: the slot of an instance without a solution comes back as the caller left it)
+    if (dA.upload(A_batch, b * nn) != hipSuccess || dB.upload(B_batch, b * nm) != hipSuccess || dQ.upload(Q, nn) != hipSuccess ||
+        dR.upload(R, (size_t)m * m) != hipSuccess || dP.upload(P_batch, b * nn) != hipSuccess || dSt.alloc(b) != hipSuccess)
+        return ALMPC_ERR_HIP;
+    DareParams dp;
+    dp.n = n; dp.m = m; dp.batch = batch;
+    dp.A = dA; dp.A_stride = (long)nn; dp.B = dB; dp.B_stride = (long)nm; dp.Q = dQ; dp.R = dR;
+    dp.P = dP; dp.P_stride = (long)nn; dp.fallback = nullptr; dp.status = dSt; dp.lds_per_wave = 0;
+    if (launch_dare(dp, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ALMPC_ERR_HIP;
+    if (hipMemcpy(P_batch, dP, b * nn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(status, dSt, b * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return ALMPC_ERR_HIP;
     return ALMPC_OK;
 }
 

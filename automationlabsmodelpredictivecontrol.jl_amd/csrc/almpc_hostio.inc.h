@@ -371,6 +371,11 @@ int almpc_group_set_structured_fallback(almpc_group* g, int on) {
     for (size_t i = 0; i < g->hs.size(); ++i) { const int rc = almpc_set_structured_fallback(g->hs[i], on); if (rc != ALMPC_OK) return gfail(g, rc, (int)i); }
     return ALMPC_OK;
 }
+int almpc_group_set_terminal_weight(almpc_group* g, int mode) {
+    if (!g) return ALMPC_ERR_INVALID;
+    for (size_t i = 0; i < g->hs.size(); ++i) { const int rc = almpc_set_terminal_weight(g->hs[i], mode); if (rc != ALMPC_OK) return gfail(g, rc, (int)i); }
+    return ALMPC_OK;
+}
 int almpc_group_set_state_box(almpc_group* g, const double* xmin, const double* xmax) {
     if (!g) return ALMPC_ERR_INVALID;
     for (size_t i = 0; i < g->hs.size(); ++i) { const int rc = almpc_set_state_box(g->hs[i], xmin, xmax); if (rc != ALMPC_OK) return gfail(g, rc, (int)i); }

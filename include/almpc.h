@@ -223,7 +223,9 @@ int almpc_design_shared(almpc_handle* h, const double* A, const double* B, const
  * mpc_modeler_implementation_fnn.jl:38-46, and then builds the QP of ..linear.jl:48-100 from (A, B): given (A_i, B_i)
  * the QP of instance i is that QP; BASELINE.json configs[3] re-linearises every step, SURVEY.md section 8b
  * `almpc_design_batched`).  Q, R, S, umin, umax as in almpc_design_shared.  P: NULL -> DARE(A_i, B_i, Q, R) per instance
- * (host, src/sub/design_mpc.jl:327); else one n*n matrix (P_per_instance = 0) or [batch][n*n] (P_per_instance = 1).
+ * (src/sub/design_mpc.jl:327): by default one host solve per instance in a serial loop, 0.5 ms per 12-state instance -- seconds for
+ * thousands of instances; after almpc_set_terminal_weight(h, ALMPC_TERMINAL_DARE_DEVICE) one kernel on the uploaded models (k_dare);
+ * else one n*n matrix (P_per_instance = 0) or [batch][n*n] (P_per_instance = 1).
  * Prediction matrices, condensed Hessian (FP64 MFMA contraction), scaling and both inverses are built on the device for
  * every instance; the step then runs one workgroup per instance with the instance's KKT inverse in LDS.  State rows:
  * almpc_set_state_box / almpc_set_terminal_equality before the design.  Not available with per-instance models:
@@ -395,6 +397,29 @@ int almpc_relin_fnn_timing(almpc_handle* h, float* ms_jacobian, float* ms_design
 int almpc_get_design_instance(almpc_handle* h, int instance, double* H, double* F, double* d);
 
 /*
+ * Where the terminal weight of a design with one model per instance comes from.
+ */
+#define ALMPC_TERMINAL_GIVEN        0   /* default: the caller's P, or the host DARE loop of almpc_design_batched(P = NULL) */
+#define ALMPC_TERMINAL_DARE_DEVICE  1
+/* Call BEFORE the design.  With ALMPC_TERMINAL_DARE_DEVICE:
+ *  - almpc_design_batched(P = NULL), condensed or structured handle: the per-instance DARE runs on the device on the uploaded models
+ *    (k_dare, no host loop).  A failing instance is the same error as on the host path (ALMPC_ERR_NUMERIC, "DARE did not converge for
+ *    instance i", lowest i), so a structured handle keeps its stage-invariant records.
+ *  - almpc_relin_fnn_* (every network kind, condensed and structured): every step solves DARE(A_i, B_i, Q, R) of the step's own
+ *    Jacobians between the Jacobian launch and the design / k_sgains (the Jacobians of an Fnn are then computed by a launch of their
+ *    own in front of the design, as those of the other kinds are: two launches more per Fnn step, one more otherwise).  The setup's P
+ *    is still required: it is the terminal weight of any instance whose own DARE has no stabilising solution in that step (the loop
+ *    goes on as it did before; the instance is reported by almpc_relin_fnn_terminal_status).  R[1,1] == 0 (the reference's branch rule
+ *    drops R) leaves no DARE: the setup and almpc_design_batched(P = NULL) then return ALMPC_ERR_NUMERIC.
+ *  n <= 48 and m <= 16 (k_dare); a design or setup beyond that returns ALMPC_ERR_UNSUPPORTED while the mode is on.
+ *  No effect on almpc_design_shared, almpc_design_ltv, the SQP loop, or any design that is given a P.  Mode 0 and a new design or setup
+ *  restore the default path. */
+int almpc_set_terminal_weight(almpc_handle* h, int mode);
+int almpc_relin_fnn_terminal_status(almpc_handle* h, int32_t* st /* [batch]: 0 own DARE, 1 the setup's P; last step */);
+/* parity hook beside almpc_get_design_instance: the terminal weight instance i was designed with (n*n) */
+int almpc_get_terminal_weight_instance(almpc_handle* h, int instance, double* P);
+
+/*
  * References (replaces _design_reference_mpc, src/main/main_mpc.jl:105-117, and the JuMP.fix of
  * x_reference/u_reference, ...linear.jl:90-100).  per_instance = 0: xref n*(N+1), uref m*N shared
  * by all instances.  per_instance = 1: xref [batch][N+1][n], uref [batch][N][m].
@@ -510,6 +535,7 @@ int almpc_group_set_terminal_equality(almpc_group* g, int on);
 int almpc_group_set_rho_profile(almpc_group* g, int mode);
 int almpc_group_set_structured_fallback(almpc_group* g, int on);
 int almpc_group_set_state_box(almpc_group* g, const double* xmin, const double* xmax);
+int almpc_group_set_terminal_weight(almpc_group* g, int mode);
 /* almpc_design_batched: A_batch [batch][n*n], B_batch [batch][n*m], P NULL | n*n | [batch][n*n] (P_per_instance = 1) */
 int almpc_group_design_batched(almpc_group* g, const double* A_batch, const double* B_batch, const double* Q, const double* R,
                                const double* S, const double* P, int P_per_instance, const double* umin, const double* umax, double rho,
@@ -598,6 +624,15 @@ int almpc_timing_samples(almpc_handle* h, int cap, int* count, float* ms_admm, f
  * (src/sub/design_mpc.jl:312-327 vs .../fnn/mpc_modeler_implementation_fnn.jl:38-46): pass the result as P to the design.
  */
 int almpc_dare(int n, int m, const double* A, const double* B, const double* Q, const double* R, double* P);
+
+/* P_i = DARE(A_i, B_i, Q, R) for a batch of models on device `device_id` (the style of almpc_fnn_linearize: no handle; host pointers,
+ * synchronous): A_batch [batch][n*n], B_batch [batch][n*m], shared Q (n*n) and R (m*m), all column-major; the algorithm of almpc_dare,
+ * one wave per instance (k_dare).
+ * status[i] = 0, or non-zero: no stabilising solution to working precision (P_batch slot i is left untouched).
+ * Returns ALMPC_OK even when some instances fail; ALMPC_ERR_NO_DEVICE without a gfx950 device (no CPU path);
+ * ALMPC_ERR_NUMERIC when R is singular; ALMPC_ERR_UNSUPPORTED beyond n <= 48, m <= 16. */
+int almpc_dare_batched(int device_id, int n, int m, int batch, const double* A_batch, const double* B_batch,
+                       const double* Q, const double* R, double* P_batch, int32_t* status);
 
 /*
  * Network code: the `activation` argument of almpc_fnn_linearize, almpc_relin_fnn_setup, almpc_sqp_fnn_setup and their

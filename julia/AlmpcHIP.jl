@@ -530,6 +530,42 @@ function dare(A::Matrix{Float64}, B::Matrix{Float64}, Q::Matrix{Float64}, R::Mat
     rc == 0 || error("almpc_dare: no convergence ($rc)")
     return P
 end
+"""
+    dare_batched(A_batch, B_batch, Q, R; device = 0) -> (P, status)
+
+P_i = DARE(A_i, B_i, Q, R) on the GPU, one wave per instance (`almpc_dare_batched`): `A_batch` n x n x batch, `B_batch` n x m x batch.
+`status[i] != 0`: no stabilising solution to working precision; slice i of `P` is then NaN.
+"""
+function dare_batched(A_batch::Array{Float64,3}, B_batch::Array{Float64,3}, Q::Matrix{Float64}, R::Matrix{Float64}; device::Integer = 0)
+    n, m, b = size(B_batch, 1), size(B_batch, 2), size(B_batch, 3)
+    size(A_batch) == (n, n, b) || throw(DimensionMismatch("A_batch must be n x n x batch"))
+    P, status = fill(NaN, n, n, b), Vector{Int32}(undef, b)
+    rc = ccall((:almpc_dare_batched, libalmpc), Cint,
+               (Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+               device, n, m, b, A_batch, B_batch, Q, R, P, status)
+    rc == 0 || error("almpc_dare_batched failed ($rc)")
+    return P, status
+end
+"""
+    set_terminal_weight!(mod, mode)
+
+Before a design: `:given` (default) or `:dare_device` -- `design_batched!` without a P and every step of the re-linearisation pipeline
+take each instance's terminal weight from the DARE of its own model, solved on the device (`almpc_set_terminal_weight`).
+"""
+set_terminal_weight!(mod::HipModeler, mode::Symbol) =
+    check(mod.handle, ccall((:almpc_set_terminal_weight, libalmpc), Cint, (Ptr{Cvoid}, Cint), mod.handle, mode === :dare_device ? 1 : 0))
+"after a step of the re-linearisation pipeline with `:dare_device`: 0 = the instance's own DARE solution, 1 = the setup's P"
+function relin_terminal_status(mod::HipModeler)
+    out = Vector{Int32}(undef, mod.batch)
+    check(mod.handle, ccall((:almpc_relin_fnn_terminal_status, libalmpc), Cint, (Ptr{Cvoid}, Ptr{Int32}), mod.handle, out))
+    return out
+end
+"the terminal weight instance `i` was designed with (parity hook beside `design_instance`)"
+function terminal_weight_instance(mod::HipModeler, i::Integer)
+    P = Matrix{Float64}(undef, mod.n, mod.n)
+    check(mod.handle, ccall((:almpc_get_terminal_weight_instance, libalmpc), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), mod.handle, i - 1, P))
+    return P
+end
 "library defaults of the options (OSQP's, plus the documented changes)"
 function default_opts()
     o = Ref(AlmpcOpts())
@@ -666,6 +702,8 @@ function group_set_state_rows!(g::HipGroup; xmin::Union{Nothing,Vector{Float64}}
 end
 group_set_rho_profile!(g::HipGroup, profile::String) =
     gcheck(g.group, ccall((:almpc_group_set_rho_profile, libalmpc), Cint, (Ptr{Cvoid}, Cint), g.group, profile == "stiffness" ? 1 : 0))
+group_set_terminal_weight!(g::HipGroup, mode::Symbol) =
+    gcheck(g.group, ccall((:almpc_group_set_terminal_weight, libalmpc), Cint, (Ptr{Cvoid}, Cint), g.group, mode === :dare_device ? 1 : 0))
 group_set_structured_fallback!(g::HipGroup, on::Bool) =
     gcheck(g.group, ccall((:almpc_group_set_structured_fallback, libalmpc), Cint, (Ptr{Cvoid}, Cint), g.group, on ? 1 : 0))
 
