@@ -124,6 +124,16 @@ def load():
     L.almpc_get_terminal_weight_instance.restype = ctypes.c_int
     L.almpc_group_set_terminal_weight.argtypes = [_hp, ctypes.c_int]
     L.almpc_group_set_terminal_weight.restype = ctypes.c_int
+    L.almpc_c2d.argtypes = [ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double, _dp, _dp]
+    L.almpc_c2d.restype = ctypes.c_int
+    L.almpc_c2d_batched.argtypes = [ctypes.c_int] * 4 + [_dp, _dp, ctypes.c_double, _dp, _dp, _ip]
+    L.almpc_c2d_batched.restype = ctypes.c_int
+    L.almpc_set_model_time.argtypes = [_hp, ctypes.c_int, ctypes.c_double]
+    L.almpc_set_model_time.restype = ctypes.c_int
+    L.almpc_get_model_instance.argtypes = [_hp, ctypes.c_int, _dp, _dp]
+    L.almpc_get_model_instance.restype = ctypes.c_int
+    L.almpc_group_set_model_time.argtypes = [_hp, ctypes.c_int, ctypes.c_double]
+    L.almpc_group_set_model_time.restype = ctypes.c_int
     L.almpc_set_structured_fallback.argtypes = [_hp, ctypes.c_int]
     L.almpc_relin_fnn_setup.argtypes = [_hp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_dp] * 12 + [ctypes.c_double, ctypes.c_double]
     L.almpc_relin_fnn_setup.restype = ctypes.c_int
@@ -307,6 +317,55 @@ def dare_batched(A, B, Q, R, device=0, P_init=None):
     if rc != ALMPC_OK:
         raise AlmpcError(rc, "almpc_dare_batched")
     return np.ascontiguousarray(P.transpose(0, 2, 1)), st
+
+
+MODEL_TIME_MODES = {"discrete": 0, "continuous": 1}  # almpc.h: ALMPC_MODEL_*
+
+
+def _model_time_mode(mode):
+    if isinstance(mode, str):
+        if mode not in MODEL_TIME_MODES:
+            raise ValueError(f"unknown model-time mode {mode!r}; choose from {sorted(MODEL_TIME_MODES)}")
+        return MODEL_TIME_MODES[mode]
+    return int(mode)
+
+
+def c2d(A, B, Ts):
+    """Exact zero-order hold of x' = A x + B u at the sample time Ts (almpc_c2d, host math): returns (A_d, B_d)."""
+    L = load()
+    A = np.asarray(A, dtype=np.float64)
+    n = A.shape[0]
+    B = np.asarray(B, dtype=np.float64).reshape(n, -1)
+    m = B.shape[1]
+    A, B = _colmajor(A, (n, n)), _colmajor(B, (n, m))
+    Ad, Bd = np.empty((n, n), order="F"), np.empty((n, m), order="F")
+    rc = L.almpc_c2d(n, m, _ptr(A), _ptr(B), float(Ts), _ptr(Ad), _ptr(Bd))
+    if rc != ALMPC_OK:
+        raise AlmpcError(rc, "almpc_c2d")
+    return Ad, Bd
+
+
+def c2d_batched(A, B, Ts, device=0, out_init=None):
+    """Zero-order hold of a batch of continuous-time models on the GPU (almpc_c2d_batched): A (batch, n, n), B (batch, n, m), one
+    sample time.  Returns (A_d (batch, n, n), B_d (batch, n, m), status (batch,) int32); status 0 = discretised, else slots i of A_d
+    and B_d are what out_init = (A_init, B_init) held (NaN without out_init)."""
+    L = load()
+    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    if A.ndim != 3 or B.ndim != 3 or A.shape[0] != B.shape[0] or A.shape[1] != A.shape[2] or B.shape[1] != A.shape[1]:
+        raise ValueError(f"expected A (batch, n, n) and B (batch, n, m), got {A.shape} and {B.shape}")
+    b, n, m = B.shape
+    Ac = np.ascontiguousarray(A.transpose(0, 2, 1))  # column-major blocks
+    Bc = np.ascontiguousarray(B.transpose(0, 2, 1))
+    if out_init is None:
+        Ad, Bd = np.full((b, n, n), np.nan), np.full((b, m, n), np.nan)
+    else:
+        Ad = np.ascontiguousarray(np.asarray(out_init[0], dtype=np.float64).reshape(b, n, n).transpose(0, 2, 1))
+        Bd = np.ascontiguousarray(np.asarray(out_init[1], dtype=np.float64).reshape(b, n, m).transpose(0, 2, 1))
+    st = np.zeros(b, dtype=np.int32)
+    rc = L.almpc_c2d_batched(int(device), n, m, b, _ptr(Ac), _ptr(Bc), float(Ts), _ptr(Ad), _ptr(Bd), st.ctypes.data_as(_ip))
+    if rc != ALMPC_OK:
+        raise AlmpcError(rc, "almpc_c2d_batched")
+    return np.ascontiguousarray(Ad.transpose(0, 2, 1)), np.ascontiguousarray(Bd.transpose(0, 2, 1)), st
 
 
 FNN_ACTIVATIONS = {"identity": 0, "relu": 1, "tanh": 2, "sigmoid": 3, "swish": 4}
@@ -694,6 +753,18 @@ class Solver:
         self._check(self.L.almpc_get_terminal_weight_instance(self.h, int(i), _ptr(P)))
         return P
 
+    def set_model_time(self, mode, Ts=0.0):
+        """Before a design: "discrete" / 0 (default) or "continuous" / 1 with the sample time Ts -- the models given to design_shared and
+        design_batched, and the network of the relin_fnn pipeline, are continuous-time and are discretised by zero-order hold at Ts
+        (almpc_set_model_time)."""
+        self._check(self.L.almpc_set_model_time(self.h, _model_time_mode(mode), float(Ts)))
+
+    def model_instance(self, i):
+        """(A (n, n), B (n, m)): the DISCRETE model instance i is designed on (almpc_get_model_instance)."""
+        A, B = np.empty((self.n, self.n), order="F"), np.empty((self.n, self.m), order="F")
+        self._check(self.L.almpc_get_model_instance(self.h, int(i), _ptr(A), _ptr(B)))
+        return A, B
+
     def start_from(self, other: "Solver"):
         """Structured handle: the next calculate starts from `other`'s last inputs (same batch, horizon <= this one's): horizon
         continuation / chaining of solvers (almpc_set_start_from)."""
@@ -892,6 +963,16 @@ class Group:
     def set_terminal_weight(self, mode):
         """Solver.set_terminal_weight on every handle (almpc_group_set_terminal_weight)."""
         self._check(self.L.almpc_group_set_terminal_weight(self.g, _terminal_mode(mode)))
+
+    def set_model_time(self, mode, Ts=0.0):
+        """Solver.set_model_time on every handle (almpc_group_set_model_time)."""
+        self._check(self.L.almpc_group_set_model_time(self.g, _model_time_mode(mode), float(Ts)))
+
+    def model_instance(self, i):
+        for h, (f, c) in zip(self.handles, self.shards):
+            if f <= i < f + c:
+                return h.model_instance(i - f)
+        raise IndexError(i)
 
     def relin_terminal_status(self):
         return np.concatenate([h.relin_terminal_status() for h in self.handles])

@@ -7,6 +7,7 @@ is julia/AlmpcHIP.jl).  Reference (paths relative to /root/r
   proceed_controller                     src/main/main_mpc.jl:22-53
   _design_reference_mpc                  src/main/main_mpc.jl:105-117
   _model_predictive_control_design       src/sub/design_mpc.jl:54-129   (ConstrainedLinearControlDiscreteSystem)
+                                         src/sub/design_mpc.jl:22-41    (ConstrainedLinearControlContinuousSystem: discretise, recurse)
   _create_weights_coefficients           src/sub/design_mpc.jl:264-283
   _IMPLEMENTATION_SOLVER_LIST            src/sub/solver_selection.jl:9-14  (+ new tag "hip")
   update_initialization!                 src/main/computation_mpc.jl:17-29  -> update_initialization
@@ -30,7 +31,8 @@ from . import _capi
 from .sharding import shard_range  # noqa: F401  (re-exported)
 
 __all__ = [
-    "Hyperrectangle", "ConstrainedLinearControlDiscreteSystem", "ConstrainedBlackBoxControlDiscreteSystem", "Fnn", "ResNet", "PolyNet", "Icnn", "DenseNet",
+    "Hyperrectangle", "ConstrainedLinearControlDiscreteSystem", "ConstrainedBlackBoxControlDiscreteSystem",
+    "ConstrainedLinearControlContinuousSystem", "ConstrainedBlackBoxControlContinuousSystem", "proceed_system_discretization", "Fnn", "ResNet", "PolyNet", "Icnn", "DenseNet",
     "proceed_system_linearization", "ReferencesStateInput", "WeightsCoefficient",
     "TerminalIngredient", "ModelPredictiveControlTuning", "ModelPredictiveControlResults",
     "ModelPredictiveControlController", "proceed_controller", "_design_reference_mpc",
@@ -64,7 +66,19 @@ class ConstrainedLinearControlDiscreteSystem:
         self.B = np.asarray(self.B, dtype=np.float64)
         n, m = self.B.shape
         if self.A.shape != (n, n) or self.X.low.shape != (n,) or self.U.low.shape != (m,):
-            raise ValueError("ConstrainedLinearControlDiscreteSystem: inconsistent dimensions")
+            raise ValueError(f"{type(self).__name__}: inconsistent dimensions")
+
+
+@dataclasses.dataclass
+class ConstrainedLinearControlContinuousSystem:
+    """Stand-in for MathematicalSystems.ConstrainedLinearControlContinuousSystem(A, B, X, U): x' = A x + B u.  The same fields and the
+    same validation as the discrete twin; the design discretises it first (src/sub/design_mpc.jl:22-41)."""
+    A: np.ndarray
+    B: np.ndarray
+    X: Hyperrectangle
+    U: Hyperrectangle
+
+    __post_init__ = ConstrainedLinearControlDiscreteSystem.__post_init__
 
 
 @dataclasses.dataclass
@@ -147,10 +161,33 @@ class ConstrainedBlackBoxControlDiscreteSystem:
     U: Hyperrectangle
 
 
-def proceed_system_linearization(system: ConstrainedBlackBoxControlDiscreteSystem, state, input, device: int = 0):
+@dataclasses.dataclass
+class ConstrainedBlackBoxControlContinuousSystem:
+    """Stand-in for MathematicalSystems.ConstrainedBlackBoxControlContinuousSystem(f, statedim, inputdim, X, U): x' = f(x, u) (the
+    Continuous half of the union the reference's black-box design method takes, src/sub/design_mpc.jl:143-147).  Same fields as the
+    discrete twin."""
+    f: Fnn
+    statedim: int
+    inputdim: int
+    X: Hyperrectangle
+    U: Hyperrectangle
+
+
+def proceed_system_discretization(system, sample_time) -> ConstrainedLinearControlDiscreteSystem:
+    """AutomationLabsSystems.proceed_system_discretization (call site: src/sub/design_mpc.jl:35).  The function itself lives outside
+    the reference tree, so its method and its sample time are not there to read: this build's reading is the exact zero-order hold
+    [A_d B_d; 0 I] = exp([A B; 0 0] Ts) at Ts = the controller's sample time (almpc_c2d)."""
+    Ts = float(sample_time)
+    if not (Ts > 0.0 and np.isfinite(Ts)):
+        raise ValueError("a continuous-time system needs a positive sample time (mpc_sample_time)")
+    Ad, Bd = _capi.c2d(system.A, system.B, Ts)
+    return ConstrainedLinearControlDiscreteSystem(np.array(Ad), np.array(Bd), system.X, system.U)
+
+
+def proceed_system_linearization(system, state, input, device: int = 0):
     """AutomationLabsSystems.proceed_system_linearization(system, x, u) (call sites: .../fnn/...:42-46,
-    src/sub/design_mpc.jl:319-326): the linear system (A, B) = Jacobians of f at (x, u), same constraint sets.
-    Computed on the GPU (k_fnn_jacobian)."""
+    src/sub/design_mpc.jl:319-326): the linear system (A, B) = Jacobians of f at (x, u), same constraint sets -- discrete for a
+    discrete black-box system, continuous for a continuous one.  Computed on the GPU (k_fnn_jacobian)."""
     f = system.f
     x, u = np.asarray(state, dtype=np.float64).reshape(1, -1), np.asarray(input, dtype=np.float64).reshape(1, -1)
     net = _net_kind(f)
@@ -158,7 +195,8 @@ def proceed_system_linearization(system: ConstrainedBlackBoxControlDiscreteSyste
         A, B = _capi.densenet_linearize(f.W_in, f.W_h, f.b_h, f.W_out, x, u, act=f.act, device=device)
     else:
         A, B = _capi.fnn_linearize(f.W_in, f.W_h, f.b_h, f.W_out, x, u, act=f.act, device=device, net=net)
-    return ConstrainedLinearControlDiscreteSystem(A[0], B[0], system.X, system.U)
+    lin = ConstrainedLinearControlContinuousSystem if isinstance(system, ConstrainedBlackBoxControlContinuousSystem) else ConstrainedLinearControlDiscreteSystem
+    return lin(A[0], B[0], system.X, system.U)
 
 
 # ---- structs of src/types/types.jl ------------------------------------------------------------------------
@@ -261,10 +299,15 @@ def proceed_controller(system, mpc_controller_type: str, mpc_horizon: int, mpc_s
 
 
 def _model_predictive_control_design(system, horizon: int, sample_time: int, references: ReferencesStateInput, **kws_):
-    if isinstance(system, ConstrainedBlackBoxControlDiscreteSystem):
+    if isinstance(system, (ConstrainedBlackBoxControlDiscreteSystem, ConstrainedBlackBoxControlContinuousSystem)):
         return _design_blackbox(system, horizon, sample_time, references, **kws_)
     if _kws(kws_).get("mpc_terminal_weight", "reference") != "reference":   # (a linear system is never re-linearised)
         raise ValueError("mpc_terminal_weight = 'step' needs a black-box model with mpc_linearization = 'step'")
+    if isinstance(system, ConstrainedLinearControlContinuousSystem):
+        # src/sub/design_mpc.jl:22-41: discretise, then the discrete method (whose controller, on the discrete system, is returned).
+        # Zero-order hold at Ts = mpc_sample_time is this build's reading of proceed_system_discretization (see there).
+        system_d = proceed_system_discretization(system, sample_time)
+        return _model_predictive_control_design(system_d, horizon, sample_time, references, **kws_)
     return _design_linear(system, horizon, sample_time, references, **kws_)
 
 
@@ -281,8 +324,20 @@ def _design_blackbox(system: ConstrainedBlackBoxControlDiscreteSystem, horizon: 
 
     With it, kw mpc_terminal_weight = "step": the terminal weight follows the model too -- every step solves DARE(A_i, B_i, Q, R) of
     the step's own linearisation on the device (almpc_set_terminal_weight); the design-time P serves an instance whose linearisation
-    has no stabilising solution (modeler.solver.relin_terminal_status() says which).  The default "reference" keeps the design-time P."""
+    has no stabilising solution (modeler.solver.relin_terminal_status() says which).  The default "reference" keeps the design-time P.
+
+    A ConstrainedBlackBoxControlContinuousSystem (x' = f(x, u)) is an extension of this build: the reference's method takes the
+    Discrete | Continuous union but has no network modeler for the continuous half.  Here the order is the reference's
+    linearise-then-discretise (.../physical/mpc_modeler_implementation_physical.jl:75-116): the linearisation at the first reference is
+    discretised by zero-order hold at Ts = mpc_sample_time and takes the linear path; P is the DARE of the discretised linearisation at
+    the last reference.  mpc_linearization = "step" runs the device pipeline with almpc_set_model_time: every step's Jacobians are
+    discretised on the device (k_c2d) in front of the design.  mpc_programming_type = "non_linear" raises NotImplementedError (a
+    continuous network inside the NLP needs an integrator)."""
     kws = _kws(kws_)
+    cont = isinstance(system, ConstrainedBlackBoxControlContinuousSystem)
+    if cont and kws.get("mpc_programming_type", "linear") == "non_linear":
+        raise NotImplementedError("mpc_programming_type = 'non_linear' with a continuous-time black-box system: the network inside the "
+                                  "NLP would need an integrator; use a discrete model or mpc_programming_type = 'linear'")
     lin_mode = kws.get("mpc_linearization", "reference")
     if lin_mode not in ("reference", "step"):
         raise ValueError("mpc_linearization must be 'reference' or 'step'")
@@ -296,6 +351,9 @@ def _design_blackbox(system: ConstrainedBlackBoxControlDiscreteSystem, horizon: 
     x_ref, u_ref = np.asarray(references.x, dtype=np.float64), np.asarray(references.u, dtype=np.float64)
     lin_first = proceed_system_linearization(system, x_ref[:, 0], u_ref[:, 0], device=dev)
     lin_last = proceed_system_linearization(system, x_ref[:, -1], u_ref[:, -1], device=dev)
+    if cont:   # (the Jacobians of x' = f(x, u) are continuous-time)
+        lin_first = proceed_system_discretization(lin_first, sample_time)
+        lin_last = proceed_system_discretization(lin_last, sample_time)
     weights = _create_weights_coefficients(lin_first, kws=kws)
     P = _capi.dare(lin_last.A, lin_last.B, weights.Q, weights.R)
     if kws.get("mpc_programming_type", "linear") == "non_linear":
@@ -313,6 +371,7 @@ def _design_blackbox(system: ConstrainedBlackBoxControlDiscreteSystem, horizon: 
         if not kws.get("mpc_structured_fallback", True):
             mod.solver._check(mod.solver.L.almpc_set_structured_fallback(mod.solver.h, 0))
         mod.solver.set_terminal_weight("dare_device" if tw_mode == "step" else "given")
+        mod.solver.set_model_time("continuous" if cont else "discrete", float(sample_time) if cont else 0.0)
         # device-resident pipeline (almpc_relin_fnn_*): Jacobians -> per-instance designs -> step, no host pointers per step
         setup = mod.solver.relin_densenet_setup if net == "densenet" else functools.partial(mod.solver.relin_fnn_setup, net=net)
         setup(f.W_in, f.W_h, f.b_h, f.W_out, references.x, references.u, weights.Q, weights.R, weights.S, np.array(P),

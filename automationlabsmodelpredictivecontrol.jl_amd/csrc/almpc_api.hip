@@ -14,6 +14,7 @@
 #include "almpc_riccati.hip.h"
 #include "almpc_sdual.hip.h"
 #include "almpc_dare.hip.h"
+#include "almpc_c2d.hip.h"
 #include "almpc_host_math.h"
 #include "almpc_switches.h"
 #include "almpc_devbuf.h"
@@ -34,6 +35,7 @@
 #include "instances/design_a.inc"
 #include "instances/design_b.inc"
 #include "instances/dare.inc"
+#include "instances/c2d.inc"
 #undef ALMPC_KERNEL_INSTANCE
 #endif
 
@@ -205,6 +207,13 @@ struct almpc_handle {
     long bP_stride = 0;         // doubles between the instances of bP as the last per-instance design left it (0: one shared matrix)
     DevBuf<double> tP;          // [n][n] the setup's P: terminal weight of an instance whose own DARE has no stabilising solution
     DevBuf<int32_t> tStat;      // [batch] k_dare's status words of the last design / step
+    // almpc_set_model_time: 1 = the models a design is given (almpc_design_shared, almpc_design_batched) and the network of the
+    // re-linearisation pipeline are continuous-time; they are discretised by zero-order hold at model_Ts (hm::c2d on the host for a
+    // shared model, k_c2d in place on the per-instance model slots, csrc/almpc_c2d.hip.h).  cStat exists only once the mode was used.
+    int model_mode = 0;
+    double model_Ts = 0.0;
+    bool c_step = false;        // the re-linearisation pipeline was set up with the mode on: every step discretises its Jacobians
+    DevBuf<int32_t> cStat;      // [batch] k_c2d's status words of the last design / step
     // stage-wise dual active-set solve (k_sdual, csrc/almpc_sdual.hip.h): input box, state box, terminal equality and S in the
     // multiple-shooting form; stage records of the unconstrained problem (shared: host Riccati at design time)
     struct Sd {
@@ -754,6 +763,76 @@ hipError_t launch_relin_dare(almpc_handle* h, const double* dQ, const double* dR
     return launch_dare(dp, h->stream);
 }
 
+// k_c2d: (Ad_i, Bd_i) = zero-order hold of (Ac_i, Bc_i) at p.Ts, one wave per instance (csrc/almpc_c2d.hip.h).  Launch only.
+hipError_t launch_c2d(C2dParams p, hipStream_t st) {
+    p.lds_per_wave = c2d_lds_doubles(p.n, p.m);
+    const int waves = c2d_waves(p.n, p.m);
+    const size_t lds = (size_t)p.lds_per_wave * sizeof(double) * waves;
+    const int wgs = (p.batch + waves - 1) / waves;
+#define C2D_RL(RL_)                                                                              \
+    do {                                                                                         \
+        const hipError_t e_ = ensure_dyn_lds(reinterpret_cast<const void*>(k_c2d<RL_>), lds);    \
+        if (e_ != hipSuccess) return e_;                                                         \
+        hipLaunchKernelGGL((k_c2d<RL_>), dim3(wgs), dim3(64 * waves), lds, st, p);               \
+    } while (0)
+    if (p.n <= 16) C2D_RL(16);
+    else if (p.n <= 32) C2D_RL(32);
+    else C2D_RL(64);
+#undef C2D_RL
+    return hipGetLastError();
+}
+
+bool model_continuous(const almpc_handle* h) { return h->model_mode == ALMPC_MODEL_CONTINUOUS_ZOH; }
+
+// almpc_set_model_time(ALMPC_MODEL_CONTINUOUS_ZOH): the handle's per-instance model slots bA, bB hold continuous-time models; one
+// k_c2d launch on the handle's stream turns them into the discrete ones in place.  Launch only; poison: a failing instance's slots
+// are filled with NaN (re-linearisation step) instead of being left alone.
+hipError_t launch_model_c2d(almpc_handle* h, bool poison) {
+    const int n = h->n, m = h->m;
+    C2dParams cp;
+    cp.n = n; cp.m = m; cp.batch = h->batch;
+    cp.Ac = h->bA; cp.A_stride = (long)n * n; cp.Bc = h->bB; cp.B_stride = (long)n * m; cp.Ts = h->model_Ts;
+    cp.Ad = h->bA; cp.Bd = h->bB; cp.poison = poison ? 1 : 0; cp.status = h->cStat; cp.lds_per_wave = 0;
+    return launch_c2d(cp, h->stream);
+}
+int c2d_shape_check(almpc_handle* h, const char* who) {
+    if (h->n > C2D_MAX_N || h->m > C2D_MAX_M) return fail(h, ALMPC_ERR_UNSUPPORTED, std::string(who) + ": continuous-time models on the device: n <= 64 and m <= 16 (k_c2d)");
+    return ALMPC_OK;
+}
+// ... almpc_design_batched: behind the uploads of the models, in front of everything that reads them.  Waits for it and reports the
+// first instance whose discretisation failed.
+int design_c2d_device(almpc_handle* h) {
+    const size_t b = (size_t)h->batch;
+    HIP_TRY(h, h->cStat.once(b));
+    HIP_TRY(h, launch_model_c2d(h, false));
+    std::vector<int32_t> stt(b, 0);
+    HIP_TRY(h, hipMemcpyAsync(stt.data(), h->cStat, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < b; ++i)
+        if (stt[i] != 0) return fail(h, ALMPC_ERR_NUMERIC, "design_batched: discretisation failed for instance " + std::to_string(i));
+    return ALMPC_OK;
+}
+// ... almpc_relin_*_setup: the shape check and the status words
+int relin_c2d_setup(almpc_handle* h) {
+    h->c_step = false;
+    if (!model_continuous(h)) return ALMPC_OK;
+    { const int rc_ = c2d_shape_check(h, "relin_fnn_setup"); if (rc_ != ALMPC_OK) return rc_; }
+    HIP_TRY(h, h->cStat.once((size_t)h->batch));
+    HIP_TRY(h, hipMemset(h->cStat, 0, (size_t)h->batch * sizeof(int32_t)));
+    h->c_step = true;
+    return ALMPC_OK;
+}
+// P_i = DARE of the zero-order hold of (A_i, B_i) (host loop of almpc_design_batched(P = NULL) with continuous-time models)
+bool host_dare_of(const almpc_handle* h, hm::mat Am, hm::mat Bm, const hm::mat& Qm, const hm::mat& Rm, hm::mat& Pm, const char** what) {
+    *what = "DARE did not converge";
+    if (model_continuous(h)) {
+        hm::mat Ad, Bd;
+        if (hm::c2d(Am, Bm, h->model_Ts, h->n, h->m, Ad, Bd) != 0) { *what = "discretisation failed"; return false; }
+        Am.swap(Ad); Bm.swap(Bd);
+    }
+    return hm::dare(Am, Bm, Qm, Rm, h->n, h->m, Pm);
+}
+
 // k_sgains over the handle's per-instance models (bA, bB; terminal weights bP, shared or per instance): all instances
 // (filter 0) or the ones the condensed step left unsolved (filter 1)
 hipError_t launch_sgains(almpc_handle* h, int filter, SolveMode mode = {}) {
@@ -1278,10 +1357,31 @@ int almpc_set_start_from(almpc_handle* h, almpc_handle* src) {
     return ALMPC_OK;
 }
 
+static int design_shared_discrete(almpc_handle* h, const double* A, const double* B, const double* Q, const double* R,
+                                  const double* S, const double* P, const double* umin, const double* umax,
+                                  const double* xmin, const double* xmax, double rho, double sigma);
+
 int almpc_design_shared(almpc_handle* h, const double* A, const double* B, const double* Q, const double* R,
                         const double* S, const double* P, const double* umin, const double* umax,
                         const double* xmin, const double* xmax, double rho, double sigma) {
     if (!h) return ALMPC_ERR_INVALID;
+    if (A && B && model_continuous(h)) {
+        // almpc_set_model_time: (A, B) is continuous-time; its zero-order hold is the model the handle is designed on and keeps
+        // (src/sub/design_mpc.jl:22-41: discretise, then the discrete method)
+        const int n = h->n, m = h->m;
+        hm::mat Ad, Bd;
+        if (hm::c2d(hm::mat(A, A + (size_t)n * n), hm::mat(B, B + (size_t)n * m), h->model_Ts, n, m, Ad, Bd) != 0) {
+            h->designed = false;
+            return fail(h, ALMPC_ERR_NUMERIC, "design: discretisation of the continuous-time model failed (not finite, or |A| Ts beyond 2^59)");
+        }
+        return design_shared_discrete(h, Ad.data(), Bd.data(), Q, R, S, P, umin, umax, xmin, xmax, rho, sigma);
+    }
+    return design_shared_discrete(h, A, B, Q, R, S, P, umin, umax, xmin, xmax, rho, sigma);
+}
+
+static int design_shared_discrete(almpc_handle* h, const double* A, const double* B, const double* Q, const double* R,
+                                  const double* S, const double* P, const double* umin, const double* umax,
+                                  const double* xmin, const double* xmax, double rho, double sigma) {
     drop_lazy_redo(h);
     if (!A || !B || !Q || !R || !umin || !umax) return fail(h, ALMPC_ERR_INVALID, "design: null matrix pointer");
     if (h->structured) {   // ALMPC_FLAG_STRUCTURED: no condensed matrices at all; rho / sigma are not used
@@ -1771,14 +1871,16 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
         }
         const bool p_inst = P ? (P_per_instance != 0) : true;
         const bool dev_dare = !P && h->terminal_mode == ALMPC_TERMINAL_DARE_DEVICE;   // (k_dare on the uploaded models, below)
-        h->t_step = false;
+        h->t_step = false; h->c_step = false;
+        if (model_continuous(h)) { const int rc_ = c2d_shape_check(h, "design_batched"); if (rc_ != ALMPC_OK) return rc_; }
         hm::mat Pall;
         if (P) Pall.assign(P, P + (p_inst ? b : 1) * (size_t)n * n);
         else if (!dev_dare) {
             Pall.resize(b * (size_t)n * n);
             for (size_t i = 0; i < b; ++i) {
                 hm::mat Am(A_batch + i * n * n, A_batch + (i + 1) * n * n), Bm(B_batch + i * n * m, B_batch + (i + 1) * n * m), Pm;
-                if (!hm::dare(Am, Bm, Qm, Rm, n, m, Pm)) return fail(h, ALMPC_ERR_NUMERIC, "design_batched: DARE did not converge for instance " + std::to_string(i));
+                const char* what = "";
+                if (!host_dare_of(h, Am, Bm, Qm, Rm, Pm, &what)) return fail(h, ALMPC_ERR_NUMERIC, std::string("design_batched: ") + what + " for instance " + std::to_string(i));
                 std::copy(Pm.begin(), Pm.end(), Pall.begin() + i * n * n);
             }
         }
@@ -1787,6 +1889,7 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
         HIP_TRY(h, h->bP.once(b * n * n));
         HIP_TRY(h, hipMemcpy(h->bA, A_batch, b * n * n * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(h->bB, B_batch, b * n * m * sizeof(double), hipMemcpyHostToDevice));
+        if (model_continuous(h)) { const int rc_ = design_c2d_device(h); if (rc_ != ALMPC_OK) return rc_; }   // (in place, in front of every reader)
         if (dev_dare) {
             HIP_TRY(h, h->wQ.once((size_t)n * n));
             HIP_TRY(h, h->wR.once((size_t)m * m));
@@ -1859,14 +1962,17 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
     const bool p_inst = P ? (P_per_instance != 0) : true;
     // (almpc_set_terminal_weight: k_dare on the uploaded models instead of the host loop, behind the uploads below; its P_i are symmetric)
     const bool dev_dare = !P && !ltv && h->terminal_mode == ALMPC_TERMINAL_DARE_DEVICE;
-    h->t_step = false;
+    h->t_step = false; h->c_step = false;
+    const bool cont = !ltv && model_continuous(h);   // (almpc_set_model_time: k_c2d in place on the uploaded models, below)
+    if (cont) { const int rc_ = c2d_shape_check(h, "design_batched"); if (rc_ != ALMPC_OK) return rc_; }
     hm::mat Pall;
     if (P) Pall.assign(P, P + (p_inst ? b : 1) * (size_t)n * n);
     else if (!dev_dare) {
         Pall.resize(b * (size_t)n * n);
         for (size_t i = 0; i < b; ++i) {
             hm::mat Am(A_batch + i * n * n, A_batch + (i + 1) * n * n), Bm(B_batch + i * n * m, B_batch + (i + 1) * n * m), Pm;
-            if (!hm::dare(Am, Bm, Qm, Rm, n, m, Pm)) return fail(h, ALMPC_ERR_NUMERIC, "design_batched: DARE did not converge for instance " + std::to_string(i));
+            const char* what = "";
+            if (!host_dare_of(h, Am, Bm, Qm, Rm, Pm, &what)) return fail(h, ALMPC_ERR_NUMERIC, std::string("design_batched: ") + what + " for instance " + std::to_string(i));
             std::copy(Pm.begin(), Pm.end(), Pall.begin() + i * n * n);
         }
     }
@@ -1907,6 +2013,11 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
     BTRY(hipMemsetAsync(h->bFlag, 0, b * sizeof(int), st));
     tr("weights alloc + copies queued");
     h->bP_stride = p_inst ? (long)n * n : 0;
+    if (cont) {
+        const int rc_ = design_c2d_device(h);
+        if (rc_ != ALMPC_OK) return rc_;
+        tr("k_c2d");
+    }
     if (dev_dare) {
         const int rc_ = design_dare_device(h, dQ, dR, Rm, h->P);
         if (rc_ != ALMPC_OK) return rc_;
@@ -2055,6 +2166,7 @@ int relin_setup_structured(almpc_handle* h, int H, int L, int net, int activatio
     HIP_TRY(h, hipMemset(h->bB, 0, b * n * m * sizeof(double)));
     HIP_TRY(h, hipMemcpy(h->bP, Pm.data(), Pm.size() * sizeof(double), hipMemcpyHostToDevice));
     { const int rc_ = relin_terminal_setup(h, Rm, Pm); if (rc_ != ALMPC_OK) return rc_; }
+    { const int rc_ = relin_c2d_setup(h); if (rc_ != ALMPC_OK) return rc_; }
     h->batched = true; h->ltv = false; h->r_batched_P = true; h->rP_stride = h->t_step ? (long)n * n : 0;   // (t_step: one P_i per step, k_dare)
     h->bP_stride = h->rP_stride;
     h->sd.ready = false;
@@ -2656,6 +2768,7 @@ int almpc_design_ltv(almpc_handle* h, const double* A_all, const double* B_all, 
                      const double* ubar, const double* xref, const double* uref, const double* Q, const double* R, const double* S,
                      const double* P, int P_per_instance, const double* umin, const double* umax, double rho, double sigma) {
     if (!h) return ALMPC_ERR_INVALID;
+    if (model_continuous(h)) return fail(h, ALMPC_ERR_UNSUPPORTED, "design_ltv: continuous-time models (almpc_set_model_time) are not discretised stage by stage; give discrete stage models");
     drop_lazy_redo(h);
     if (!A_all || !B_all || !xbar || !ubar || !Q || !R || !P || !umin || !umax)
         return fail(h, ALMPC_ERR_INVALID, "design_ltv: null pointer (P must be given: there is no single model to take a DARE of)");
@@ -2766,6 +2879,7 @@ static int relin_net_setup(almpc_handle* h, bool dense, int H, int L, int activa
     HIP_TRY(h, q.gS.upload(gS.data(), gS.size()));
     HIP_TRY(h, hipMemcpy(h->bP, Pm.data(), Pm.size() * sizeof(double), hipMemcpyHostToDevice));
     { const int rc_ = relin_terminal_setup(h, Rm, Pm); if (rc_ != ALMPC_OK) return rc_; }
+    { const int rc_ = relin_c2d_setup(h); if (rc_ != ALMPC_OK) return rc_; }
     h->bP_stride = h->t_step ? (long)n * n : 0;   // (t_step: one P_i per step, k_dare)
     HIP_TRY(h, hipMemcpy(h->dUmin, umin, m * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->dUmax, umax, m * sizeof(double), hipMemcpyHostToDevice));
@@ -2840,6 +2954,7 @@ int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
         // limit (.../fnn/mpc_modeler_implementation_fnn.jl:23-58) and neither has this route.
         HIP_TRY(h, launch_fnn_jacobian(h->sw, fp, q.net, h->num_cus, st));
         if (timing) HIP_TRY(h, hipEventRecord(q.ev[1], st));
+        if (h->c_step) HIP_TRY(h, launch_model_c2d(h, true));   // the network is x' = net(x, u): its Jacobians are continuous-time
         if (h->t_step) HIP_TRY(h, launch_relin_dare(h, h->sd.dQ, h->sd.dR));   // every instance's own terminal weight, in front of its records
         HIP_TRY(h, launch_sgains(h, 0));
         if (timing) HIP_TRY(h, hipEventRecord(q.ev[2], st));
@@ -2851,14 +2966,20 @@ int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
         const int rc = almpc_calculate_async(h, &o2);
         if (rc != ALMPC_OK) { h->designed = false; return rc; }
         q.have_prev = true;
+        if (h->c_step) {   // an instance whose discretisation failed leaves with ALMPC_NON_FINITE
+            hipLaunchKernelGGL(k_flag_to_status, dim3((h->batch + 255) / 256), dim3(256), 0, st, h->batch, (const int*)h->cStat.get(), h->dStatus);
+            HIP_TRY(h, hipGetLastError());
+        }
         if (timing) HIP_TRY(h, hipEventRecord(q.ev[3], st));
         return ALMPC_OK;
     }
     // (the design kernel's workgroups linearise their own instance -- unless every instance's terminal weight is the DARE solution of
-    // its Jacobians, almpc_set_terminal_weight: P_i has to be there before the design, so the Jacobians get their own launch in front)
-    const bool fuse_jac = design_fuses_fnn(h, q.H, q.L, q.net) && !h->t_step;
+    // its Jacobians, almpc_set_terminal_weight: P_i has to be there before the design, so the Jacobians get their own launch in front;
+    // the same when the Jacobians are continuous-time and k_c2d stands between them and the design, almpc_set_model_time)
+    const bool fuse_jac = design_fuses_fnn(h, q.H, q.L, q.net) && !h->t_step && !h->c_step;
     if (!fuse_jac) HIP_TRY(h, launch_fnn_jacobian(h->sw, fp, q.net, h->num_cus, st));
     if (timing) HIP_TRY(h, hipEventRecord(q.ev[1], st));
+    if (h->c_step) HIP_TRY(h, launch_model_c2d(h, true));
     if (h->t_step) HIP_TRY(h, launch_relin_dare(h, q.Q, q.R));
     // 2. the reference's QP for every (A_i, B_i): H_i, F_i, scaling, inverses, V_i; reference-dependent vectors.  A warm step
     // (opts.warm_start = 1 after a solved step) takes its working-set guess from the previous step's inputs shifted by one stage
@@ -2895,6 +3016,10 @@ int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
         hipLaunchKernelGGL(k_flag_to_status, dim3((h->batch + 255) / 256), dim3(256), 0, st, h->batch, h->bFlag, h->dStatus);
         HIP_TRY(h, hipGetLastError());
     }
+    if (h->c_step) {   // an instance whose discretisation failed (its model slots hold NaN) leaves with ALMPC_NON_FINITE
+        hipLaunchKernelGGL(k_flag_to_status, dim3((h->batch + 255) / 256), dim3(256), 0, st, h->batch, (const int*)h->cStat.get(), h->dStatus);
+        HIP_TRY(h, hipGetLastError());
+    }
     if (timing) HIP_TRY(h, hipEventRecord(q.ev[3], st));
     return ALMPC_OK;
 }
@@ -2911,6 +3036,8 @@ int almpc_relin_fnn_advance(almpc_handle* h) {
     if (!h) return ALMPC_ERR_INVALID;
     almpc_handle::Relin& q = h->relin;
     if (!q.ready || !q.have_prev) return fail(h, ALMPC_ERR_NOT_DESIGNED, "relin_fnn_advance needs a solved almpc_relin_fnn_step");
+    if (h->c_step)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_advance: the network is continuous-time (almpc_set_model_time); its plant is an integrator, which is the caller's");
     HIP_TRY(h, hipSetDevice(h->device));
     { const int rc_ = enqueue_gated_redo(h); if (rc_ != ALMPC_OK) return rc_; }   // (the network is driven by decided instances' inputs only)
     const int n = h->n, m = h->m;
@@ -2958,6 +3085,8 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
                          const double* R, const double* S, const double* P, int P_per_instance, const double* umin, const double* umax,
                          double rho, double sigma) {
     if (!h) return ALMPC_ERR_INVALID;
+    if (model_continuous(h))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_setup: continuous-time models (almpc_set_model_time) are outside the SQP loop");
     drop_lazy_redo(h);
     if (H < 1 || L < 0 || !W_in || !W_out || (L > 0 && (!W_h || !b_h)) || !Q || !R || !P || !umin || !umax)
         return fail(h, ALMPC_ERR_INVALID, "sqp_fnn_setup: null pointer or bad network shape (P must be given)");
@@ -3515,6 +3644,29 @@ int almpc_set_terminal_weight(almpc_handle* h, int mode) {
     return ALMPC_OK;
 }
 
+int almpc_set_model_time(almpc_handle* h, int mode, double Ts) {
+    if (!h) return ALMPC_ERR_INVALID;
+    if (mode != ALMPC_MODEL_DISCRETE && mode != ALMPC_MODEL_CONTINUOUS_ZOH) return fail(h, ALMPC_ERR_INVALID, "set_model_time: mode must be 0 or 1");
+    if (mode == ALMPC_MODEL_CONTINUOUS_ZOH && !(Ts > 0.0 && std::isfinite(Ts))) return fail(h, ALMPC_ERR_INVALID, "set_model_time: the sample time must be positive and finite");
+    h->model_mode = mode;   // (read by the next design / almpc_relin_*_setup)
+    h->model_Ts = mode == ALMPC_MODEL_CONTINUOUS_ZOH ? Ts : 0.0;
+    return ALMPC_OK;
+}
+
+int almpc_get_model_instance(almpc_handle* h, int instance, double* A, double* B) {
+    if (!h || (!A && !B)) return ALMPC_ERR_INVALID;
+    if (!h->designed && !h->relin.ready) return fail(h, ALMPC_ERR_NOT_DESIGNED, "get_model_instance before a design");
+    if (instance < 0 || instance >= h->batch) return fail(h, ALMPC_ERR_INVALID, "get_model_instance: instance out of range");
+    if (h->ltv) return fail(h, ALMPC_ERR_UNSUPPORTED, "get_model_instance: a time-varying design has no single model per instance");
+    const size_t nn = (size_t)h->n * h->n, nm = (size_t)h->n * h->m;
+    const bool pi = h->batched && h->bA && h->bB;   // one model per instance, else the shared one
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (A) HIP_TRY(h, hipMemcpy(A, pi ? h->bA + (size_t)instance * nn : h->dA.get(), nn * sizeof(double), hipMemcpyDeviceToHost));
+    if (B) HIP_TRY(h, hipMemcpy(B, pi ? h->bB + (size_t)instance * nm : h->dB.get(), nm * sizeof(double), hipMemcpyDeviceToHost));
+    return ALMPC_OK;
+}
+
 int almpc_relin_fnn_terminal_status(almpc_handle* h, int32_t* st) {
     if (!h || !st) return ALMPC_ERR_INVALID;
     if (!h->relin.ready || !h->t_step)
@@ -3808,6 +3960,44 @@ int almpc_dare(int n, int m, const double* A, const double* B, const double* Q, 
     hm::mat Am(A, A + (size_t)n * n), Bm(B, B + (size_t)n * m), Qm(Q, Q + (size_t)n * n), Rm(R, R + (size_t)m * m), Pm;
     if (!hm::dare(Am, Bm, Qm, Rm, n, m, Pm)) return ALMPC_ERR_NUMERIC;
     std::memcpy(P, Pm.data(), (size_t)n * n * sizeof(double));
+    return ALMPC_OK;
+}
+
+int almpc_c2d(int n, int m, const double* Ac, const double* Bc, double Ts, double* Ad, double* Bd) {
+    if (n < 1 || m < 1 || !Ac || !Bc || !Ad || !Bd) return ALMPC_ERR_INVALID;
+    if (!(Ts > 0.0 && std::isfinite(Ts))) return ALMPC_ERR_INVALID;
+    hm::mat Am, Bm;
+    if (hm::c2d(hm::mat(Ac, Ac + (size_t)n * n), hm::mat(Bc, Bc + (size_t)n * m), Ts, n, m, Am, Bm) != 0) return ALMPC_ERR_NUMERIC;
+    std::copy(Am.begin(), Am.end(), Ad);
+    std::copy(Bm.begin(), Bm.end(), Bd);
+    return ALMPC_OK;
+}
+
+int almpc_c2d_batched(int device_id, int n, int m, int batch, const double* Ac_batch, const double* Bc_batch, double Ts,
+                      double* Ad_batch, double* Bd_batch, int32_t* status) {
+    if (n < 1 || m < 1 || batch < 1 || !Ac_batch || !Bc_batch || !Ad_batch || !Bd_batch || !status) return ALMPC_ERR_INVALID;
+    if (!(Ts > 0.0 && std::isfinite(Ts))) return ALMPC_ERR_INVALID;
+    if (n > C2D_MAX_N || m > C2D_MAX_M) return ALMPC_ERR_UNSUPPORTED;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device_id < 0 || device_id >= count) return ALMPC_ERR_NO_DEVICE;
+    if (hipSetDevice(device_id) != hipSuccess) return ALMPC_ERR_HIP;
+    using Tight = DevBuf<double, Mem::DeviceTight>;
+    const size_t b = (size_t)batch, nn = (size_t)n * n, nm = (size_t)n * m;
+    Tight dAc, dBc, dAd, dBd;
+    DevBuf<int32_t, Mem::DeviceTight> dSt;
+    // (Ad_batch, Bd_batch go up as well: the slots of an instance that fails come back as the caller left them)
+    if (dAc.upload(Ac_batch, b * nn) != hipSuccess || dBc.upload(Bc_batch, b * nm) != hipSuccess || dAd.upload(Ad_batch, b * nn) != hipSuccess ||
+        dBd.upload(Bd_batch, b * nm) != hipSuccess || dSt.alloc(b) != hipSuccess)
+        return ALMPC_ERR_HIP;
+    C2dParams cp;
+    cp.n = n; cp.m = m; cp.batch = batch;
+    cp.Ac = dAc; cp.A_stride = (long)nn; cp.Bc = dBc; cp.B_stride = (long)nm; cp.Ts = Ts;
+    cp.Ad = dAd; cp.Bd = dBd; cp.poison = 0; cp.status = dSt; cp.lds_per_wave = 0;
+    if (launch_c2d(cp, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ALMPC_ERR_HIP;
+    if (hipMemcpy(Ad_batch, dAd, b * nn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(Bd_batch, dBd, b * nm * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(status, dSt, b * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return ALMPC_ERR_HIP;
     return ALMPC_OK;
 }
 

@@ -126,6 +126,57 @@ inline bool dare(const mat& A, const mat& B, const mat& Q, const mat& R, int n, 
     return true;
 }
 
+// Exact zero-order hold of x' = Ac x + Bc u at the sample time Ts: [Ad Bd; 0 I] = exp([Ac Bc; 0 0] Ts), without forming the augmented
+// matrix and without a linear solve (a singular Ac is no special case).  Scaling and squaring on the pair (Ad, Bd):
+//   nrm = Ts max_j sum_i |Ac[i,j]|,  s = the halvings that bring nrm to <= 0.5,  h = Ts / 2^s,  X = h Ac,
+//   G = sum_{k=0..K} X^k / (k+1)!  by Horner (K = C2D_TERMS),  Bd = h G Bc,  Ad = I + X G,
+//   s times:  Bd <- Bd + Ad Bd,  Ad <- Ad Ad.
+// Stands in for the discretisation in front of the reference's continuous-time design (src/sub/design_mpc.jl:22-41).  k_c2d
+// (csrc/almpc_c2d.hip.h) is this function on the device, statement by statement.  Returns 0, or 1 with Ad, Bd untouched: nrm not
+// finite, more than C2D_MAX_HALVINGS halvings, or an output entry that is not finite.
+constexpr int C2D_TERMS = 16, C2D_MAX_HALVINGS = 60;
+inline int c2d(const mat& Ac, const mat& Bc, double Ts, int n, int m, mat& Ad, mat& Bd) {
+    double nrm = 0.0;
+    bool notfin = false;
+    for (int j = 0; j < n; ++j) {
+        double cs = 0.0;
+        for (int i = 0; i < n; ++i) cs += std::fabs(Ac[(size_t)j * n + i]);
+        cs *= Ts;
+        notfin = notfin || !(cs <= 1.7976931348623157e308);
+        nrm = std::fmax(nrm, cs);
+    }
+    if (notfin) return 1;
+    int s = 0;
+    double h = Ts;
+    while (nrm > 0.5) {
+        if (++s > C2D_MAX_HALVINGS) return 1;
+        nrm *= 0.5; h *= 0.5;
+    }
+    const size_t nn = (size_t)n * n;
+    mat X(nn), G = eye(n), T;
+    for (size_t i = 0; i < nn; ++i) X[i] = h * Ac[i];
+    for (int k = C2D_TERMS; k >= 1; --k) {
+        const double c = 1.0 / (double)(k + 1);
+        T = mul(X, G, n, n, n);
+        for (int j = 0; j < n; ++j)
+            for (int i = 0; i < n; ++i) G[(size_t)j * n + i] = (i == j ? 1.0 : 0.0) + c * T[(size_t)j * n + i];
+    }
+    mat B1 = mul(G, Bc, n, n, m), A1 = mul(X, G, n, n, n);
+    for (double& v : B1) v *= h;
+    for (int i = 0; i < n; ++i) A1[(size_t)i * n + i] += 1.0;
+    for (int d = 0; d < s; ++d) {
+        mat B2 = mul(A1, B1, n, n, m), A2 = mul(A1, A1, n, n, n);
+        for (size_t i = 0; i < B2.size(); ++i) B2[i] += B1[i];
+        B1.swap(B2); A1.swap(A2);
+    }
+    for (double v : A1)
+        if (!std::isfinite(v)) return 1;
+    for (double v : B1)
+        if (!std::isfinite(v)) return 1;
+    Ad = A1; Bd = B1;
+    return 0;
+}
+
 // Stage records of the UNCONSTRAINED stage-wise problem for k_sdual (csrc/almpc_sdual.hip.h), shared model: backward Riccati
 // recursion of the reference's cost (src/sub/design_mpc.jl:405-468: Q on stages 1..N-1, P on stage N, R on every input, and -- when
 // `S` is given -- the input-rate term (u_k - u_{k+1})'S(u_k - u_{k+1}), k = 0..N-2, which makes the stage state [e_k; v_{k-1}],

@@ -376,6 +376,11 @@ int almpc_group_set_terminal_weight(almpc_group* g, int mode) {
     for (size_t i = 0; i < g->hs.size(); ++i) { const int rc = almpc_set_terminal_weight(g->hs[i], mode); if (rc != ALMPC_OK) return gfail(g, rc, (int)i); }
     return ALMPC_OK;
 }
+int almpc_group_set_model_time(almpc_group* g, int mode, double Ts) {
+    if (!g) return ALMPC_ERR_INVALID;
+    for (size_t i = 0; i < g->hs.size(); ++i) { const int rc = almpc_set_model_time(g->hs[i], mode, Ts); if (rc != ALMPC_OK) return gfail(g, rc, (int)i); }
+    return ALMPC_OK;
+}
 int almpc_group_set_state_box(almpc_group* g, const double* xmin, const double* xmax) {
     if (!g) return ALMPC_ERR_INVALID;
     for (size_t i = 0; i < g->hs.size(); ++i) { const int rc = almpc_set_state_box(g->hs[i], xmin, xmax); if (rc != ALMPC_OK) return gfail(g, rc, (int)i); }

@@ -38,10 +38,9 @@ def splitmix_normal(seed: int, first_instance: int, count: int, dim: int):
     return out[:, :dim]
 
 
-def quadrotor_model(Ts=0.1, mass=0.5, J=(4e-3, 4e-3, 8e-3), g=9.81):
-    """Hover-linearised quadrotor, states [p(3), v(3), (phi,theta,psi), omega(3)], inputs [dT, tau_x, tau_y, tau_z]; exact
-    zero-order hold via expm([[Ac,Bc],[0,0]] Ts) (configs[1])."""
-    import scipy.linalg as sla
+def quadrotor_continuous_model(mass=0.5, J=(4e-3, 4e-3, 8e-3), g=9.81):
+    """Hover-linearised quadrotor in continuous time, x' = Ac x + Bc u: states [p(3), v(3), (phi,theta,psi), omega(3)], inputs
+    [dT, tau_x, tau_y, tau_z]."""
     Ac = np.zeros((12, 12))
     Bc = np.zeros((12, 4))
     Ac[0:3, 3:6] = np.eye(3)
@@ -52,6 +51,13 @@ def quadrotor_model(Ts=0.1, mass=0.5, J=(4e-3, 4e-3, 8e-3), g=9.81):
     Bc[9, 1] = 1.0 / J[0]
     Bc[10, 2] = 1.0 / J[1]
     Bc[11, 3] = 1.0 / J[2]
+    return Ac, Bc
+
+
+def quadrotor_model(Ts=0.1, mass=0.5, J=(4e-3, 4e-3, 8e-3), g=9.81):
+    """quadrotor_continuous_model under an exact zero-order hold via expm([[Ac,Bc],[0,0]] Ts) (configs[1])."""
+    import scipy.linalg as sla
+    Ac, Bc = quadrotor_continuous_model(mass, J, g)
     M = np.zeros((16, 16))
     M[:12, :12] = Ac
     M[:12, 12:] = Bc

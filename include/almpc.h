@@ -420,6 +420,35 @@ int almpc_relin_fnn_terminal_status(almpc_handle* h, int32_t* st /* [batch]: 0 o
 int almpc_get_terminal_weight_instance(almpc_handle* h, int instance, double* P);
 
 /*
+ * Continuous-time models.  The reference accepts them (ConstrainedLinearControlContinuousSystem, src/sub/design_mpc.jl:22-41:
+ * discretise, then the discrete method; the Discrete | Continuous union of the black-box method, :143-147).  Its
+ * proceed_system_discretization lives outside the reference tree; this build's reading is the exact zero-order hold at the sample time,
+ * [A_d B_d; 0 I] = exp([A_c B_c; 0 0] Ts) (almpc_c2d).
+ */
+#define ALMPC_MODEL_DISCRETE        0   /* default: every model is x+ = A x + B u */
+#define ALMPC_MODEL_CONTINUOUS_ZOH  1
+/* Call BEFORE the design.  With ALMPC_MODEL_CONTINUOUS_ZOH and a sample time Ts > 0:
+ *  - almpc_design_shared: (A, B) is x' = A x + B u; it is discretised once on the host, then the design runs as it does today.  The
+ *    handle holds the discrete model (almpc_advance_plant steps it).
+ *  - almpc_design_batched, condensed or structured handle: the uploaded models are discretised in place by one kernel (k_c2d, one wave
+ *    per instance) before anything reads them; with P = NULL the terminal weights are the DAREs of the DISCRETE models (k_dare behind
+ *    k_c2d with ALMPC_TERMINAL_DARE_DEVICE, else hm::c2d + hm::dare per instance on the host).  An instance whose discretisation fails
+ *    (a model that is not finite, |A_i| Ts beyond 2^59) is ALMPC_ERR_NUMERIC, "discretisation failed for instance i", lowest i.
+ *  - almpc_relin_fnn_* (every network kind, condensed and structured): the network is read as x' = net(x, u).  Every step runs
+ *    Jacobians -> k_c2d in place on the model slots -> (k_dare) -> design / k_sgains -> step; the Jacobians of an Fnn get a launch of
+ *    their own (two launches more per Fnn step, one more otherwise).  The setup's P is a weight of the DISCRETE problem, as it is
+ *    with the mode off.  An instance whose discretisation fails in a step leaves that step with ALMPC_NON_FINITE; the others are not
+ *    affected.  almpc_relin_fnn_timing counts k_c2d in the design stage.
+ *  - refused (ALMPC_ERR_UNSUPPORTED): almpc_relin_fnn_advance (the plant of a continuous-time network is an integrator, and that is
+ *    the caller's), almpc_design_ltv, almpc_sqp_*_setup.
+ *  n <= 64 and m <= 16 for the per-instance paths (k_c2d).  One sample time per handle.  Mode 0 and a new design or setup restore the
+ *  default path; with the mode off every launch and allocation is what it was. */
+int almpc_set_model_time(almpc_handle* h, int mode, double Ts);
+/* parity hook: the DISCRETE model instance i is designed on (A n*n, B n*m, column-major; either may be NULL): the shared model, or
+ * slot i of the per-instance models (after a re-linearisation step: that step's linearisation) */
+int almpc_get_model_instance(almpc_handle* h, int instance, double* A, double* B);
+
+/*
  * References (replaces _design_reference_mpc, src/main/main_mpc.jl:105-117, and the JuMP.fix of
  * x_reference/u_reference, ...linear.jl:90-100).  per_instance = 0: xref n*(N+1), uref m*N shared
  * by all instances.  per_instance = 1: xref [batch][N+1][n], uref [batch][N][m].
@@ -536,6 +565,7 @@ int almpc_group_set_rho_profile(almpc_group* g, int mode);
 int almpc_group_set_structured_fallback(almpc_group* g, int on);
 int almpc_group_set_state_box(almpc_group* g, const double* xmin, const double* xmax);
 int almpc_group_set_terminal_weight(almpc_group* g, int mode);
+int almpc_group_set_model_time(almpc_group* g, int mode, double Ts);
 /* almpc_design_batched: A_batch [batch][n*n], B_batch [batch][n*m], P NULL | n*n | [batch][n*n] (P_per_instance = 1) */
 int almpc_group_design_batched(almpc_group* g, const double* A_batch, const double* B_batch, const double* Q, const double* R,
                                const double* S, const double* P, int P_per_instance, const double* umin, const double* umax, double rho,
@@ -633,6 +663,19 @@ int almpc_dare(int n, int m, const double* A, const double* B, const double* Q, 
  * ALMPC_ERR_NUMERIC when R is singular; ALMPC_ERR_UNSUPPORTED beyond n <= 48, m <= 16. */
 int almpc_dare_batched(int device_id, int n, int m, int batch, const double* A_batch, const double* B_batch,
                        const double* Q, const double* R, double* P_batch, int32_t* status);
+
+/* Exact zero-order hold of x' = Ac x + Bc u at the sample time Ts (host math, like almpc_dare): [Ad Bd; 0 I] = exp([Ac Bc; 0 0] Ts) by
+ * scaling and squaring on the pair (Ad, Bd) -- no augmented matrix, no linear solve, so a singular Ac is no special case (the double
+ * integrator gives [[1, 1], [0, 1]] and [0.5, 1] exactly).  Ac n*n, Bc n*m, column-major.  ALMPC_ERR_INVALID: Ts <= 0 or not finite;
+ * ALMPC_ERR_NUMERIC: a model that is not finite, or |Ac|_1 Ts beyond 2^59; Ad, Bd are then untouched. */
+int almpc_c2d(int n, int m, const double* Ac, const double* Bc, double Ts, double* Ad, double* Bd);
+
+/* The same for a batch of models on device `device_id` (the style of almpc_dare_batched: no handle; host pointers, synchronous; the same
+ * layouts): one wave per instance (k_c2d), n <= 64, m <= 16 (beyond: ALMPC_ERR_UNSUPPORTED).
+ * status[i] = 0, or non-zero: the discretisation failed (slots i of Ad_batch and Bd_batch are left untouched).
+ * Returns ALMPC_OK even when some instances fail; ALMPC_ERR_NO_DEVICE without a gfx950 device (no CPU path, nothing is written). */
+int almpc_c2d_batched(int device_id, int n, int m, int batch, const double* Ac_batch, const double* Bc_batch, double Ts,
+                      double* Ad_batch, double* Bd_batch, int32_t* status /* [batch] */);
 
 /*
  * Network code: the `activation` argument of almpc_fnn_linearize, almpc_relin_fnn_setup, almpc_sqp_fnn_setup and their

@@ -566,6 +566,50 @@ function terminal_weight_instance(mod::HipModeler, i::Integer)
     check(mod.handle, ccall((:almpc_get_terminal_weight_instance, libalmpc), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), mod.handle, i - 1, P))
     return P
 end
+"""
+    c2d(Ac, Bc, Ts) -> (Ad, Bd)
+
+Exact zero-order hold of x' = Ac x + Bc u at the sample time `Ts` (`almpc_c2d`, host math): [Ad Bd; 0 I] = exp([Ac Bc; 0 0] Ts).
+"""
+function c2d(Ac::Matrix{Float64}, Bc::Matrix{Float64}, Ts::Real)
+    n, m = size(Bc)
+    size(Ac) == (n, n) || throw(DimensionMismatch("Ac must be n x n"))
+    Ad, Bd = Matrix{Float64}(undef, n, n), Matrix{Float64}(undef, n, m)
+    rc = ccall((:almpc_c2d, libalmpc), Cint, (Cint, Cint, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}),
+               n, m, Ac, Bc, Ts, Ad, Bd)
+    rc == 0 || error("almpc_c2d failed ($rc)")
+    return Ad, Bd
+end
+"""
+    c2d_batched(Ac_batch, Bc_batch, Ts; device = 0) -> (Ad, Bd, status)
+
+The same for a batch of models on the GPU, one wave per instance (`almpc_c2d_batched`): `Ac_batch` n x n x batch, `Bc_batch`
+n x m x batch.  `status[i] != 0`: the discretisation of model i failed; slices i of `Ad` and `Bd` are then NaN.
+"""
+function c2d_batched(Ac_batch::Array{Float64,3}, Bc_batch::Array{Float64,3}, Ts::Real; device::Integer = 0)
+    n, m, b = size(Bc_batch, 1), size(Bc_batch, 2), size(Bc_batch, 3)
+    size(Ac_batch) == (n, n, b) || throw(DimensionMismatch("Ac_batch must be n x n x batch"))
+    Ad, Bd, status = fill(NaN, n, n, b), fill(NaN, n, m, b), Vector{Int32}(undef, b)
+    rc = ccall((:almpc_c2d_batched, libalmpc), Cint,
+               (Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+               device, n, m, b, Ac_batch, Bc_batch, Ts, Ad, Bd, status)
+    rc == 0 || error("almpc_c2d_batched failed ($rc)")
+    return Ad, Bd, status
+end
+"""
+    set_model_time!(mod, mode, Ts = 0.0)
+
+Before a design: `:discrete` (default) or `:continuous` with the sample time `Ts` -- the models given to the designs and the network of
+the re-linearisation pipeline are continuous-time and are discretised by zero-order hold at `Ts` (`almpc_set_model_time`).
+"""
+set_model_time!(mod::HipModeler, mode::Symbol, Ts::Real = 0.0) =
+    check(mod.handle, ccall((:almpc_set_model_time, libalmpc), Cint, (Ptr{Cvoid}, Cint, Cdouble), mod.handle, mode === :continuous ? 1 : 0, Ts))
+"the DISCRETE model instance `i` is designed on (parity hook beside `design_instance`): (A, B)"
+function model_instance(mod::HipModeler, i::Integer)
+    A, B = Matrix{Float64}(undef, mod.n, mod.n), Matrix{Float64}(undef, mod.n, mod.m)
+    check(mod.handle, ccall((:almpc_get_model_instance, libalmpc), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}), mod.handle, i - 1, A, B))
+    return A, B
+end
 "library defaults of the options (OSQP's, plus the documented changes)"
 function default_opts()
     o = Ref(AlmpcOpts())
@@ -704,6 +748,8 @@ group_set_rho_profile!(g::HipGroup, profile::String) =
     gcheck(g.group, ccall((:almpc_group_set_rho_profile, libalmpc), Cint, (Ptr{Cvoid}, Cint), g.group, profile == "stiffness" ? 1 : 0))
 group_set_terminal_weight!(g::HipGroup, mode::Symbol) =
     gcheck(g.group, ccall((:almpc_group_set_terminal_weight, libalmpc), Cint, (Ptr{Cvoid}, Cint), g.group, mode === :dare_device ? 1 : 0))
+group_set_model_time!(g::HipGroup, mode::Symbol, Ts::Real = 0.0) =
+    gcheck(g.group, ccall((:almpc_group_set_model_time, libalmpc), Cint, (Ptr{Cvoid}, Cint, Cdouble), g.group, mode === :continuous ? 1 : 0, Ts))
 group_set_structured_fallback!(g::HipGroup, on::Bool) =
     gcheck(g.group, ccall((:almpc_group_set_structured_fallback, libalmpc), Cint, (Ptr{Cvoid}, Cint), g.group, on ? 1 : 0))
 
