@@ -70,6 +70,13 @@ struct almpc_handle {
     std::vector<double> H, F, P, d;
     // device: shared design
     DevBuf<double> dMinvFrag, dVFrag, dHFrag, dFFrag, dG;
+    // Cold start's affine first ADMM iterate xt1 = W e0 + wS and the prologue's row-constant table.  No allocation of their own: the
+    // shared design hands over two of its temporaries instead of freeing them -- the plain Minv [nz][nzs] and a workspace of at least
+    // n * nzs doubles, laid out [W = -Minv F': n * nzs | wS = -Minv fS: nzs | table: 8 * nzs].  wS and the table belong to a SHARED
+    // reference (almpc_set_reference makes them where the workspace has room for them: cold_ref); per-instance references, which
+    // would need batch * nz doubles of wS, take the full first product and the per-row loads.
+    DevBuf<double> dMinv, dCold;
+    bool cold_ref = false;   // wS and the table in dCold are those of the current (shared) reference
     DevBuf<double> dD, dUmin, dUmax, dA, dB;
     DevBuf<double> dXref, dUref, dFS, dV0S, dRho;
     bool ref_keep = false;   // dXref, dUref, dFS, dV0S are as almpc_set_reference made them: it keeps all four while their sizes stay
@@ -1467,7 +1474,7 @@ static int design_shared_discrete(almpc_handle* h, const double* A, const double
     int rc = design_shared_device(h->stream, n, m, N, h->nzs, h->nrb, h->ks, h->ksf, Am, Bm, Qm, Rm, Sm, Pm, rho, sigma,
                                   h->dMinvFrag, h->dVFrag, h->dHFrag, h->dFFrag, h->dG, h->dD, h->H, h->F, h->d, h->err,
                                   rowsel, h->Rs, h->dGhat, h->dGnorm, h->rho_mode, h->dRho, rowsel.empty() ? nullptr : h->dVsPlain,
-                                  h->nzs <= 64 ? h->dPlain : nullptr);
+                                  h->nzs <= 64 ? h->dPlain : nullptr, &h->dMinv, &h->dCold);
     if (rc != ALMPC_OK) return rc;
     if (h->terminal_eq && h->mc >= n && !h->sw.no_eq_projection) {
         // the n terminal-equality rows (the last n state rows) are in every working set: eliminate them here, once
@@ -2287,6 +2294,11 @@ AdmmParams admm_params(const almpc_handle* h, const almpc_opts& o, bool keep_sta
     ap.dvec = h->dD; ap.rhovec = h->dRho; ap.umin = h->dUmin; ap.umax = h->dUmax;
     ap.uref = h->dUref; ap.uref_stride = h->uref_stride; ap.xref = h->dXref; ap.xref_stride = h->xref_stride;
     ap.fS = h->dFS; ap.fS_stride = h->fS_stride; ap.x0 = h->dX0;
+    if (h->dCold && h->cold_ref && h->uref_stride == 0 && h->fS_stride == 0) {
+        const size_t w = (size_t)h->n * h->nzs;
+        ap.rowc = h->dCold + w + h->nzs;
+        if (!(o.reserved[0] & ALMPC_OPT_FULL_FIRST_PRODUCT)) ap.Wp = h->dCold;
+    }
     ap.xs = h->dXs; ap.zs = h->dZs; ap.ys = h->dYs; ap.v0 = h->dV0; ap.status = h->dStatus; ap.iters = h->dIters;
     ap.piters = h->dPiters;
     ap.perm = h->dPerm;
@@ -2886,7 +2898,7 @@ static int relin_net_setup(almpc_handle* h, bool dense, int H, int L, int activa
     // shared references; the scaled input-rate gradient fS_i = d_i .* gS and v0S_i = -G_i fS_i are per instance (re-made every step)
     h->ref_keep = false;
     HIP_TRY(h, h->dXref.upload(xr.data(), xr.size())); HIP_TRY(h, h->dUref.upload(ur.data(), ur.size()));
-    HIP_TRY(h, h->dFS.alloc(b * nz)); HIP_TRY(h, h->dV0S.alloc(b * nz));
+    HIP_TRY(h, h->dFS.alloc(b * nz)); HIP_TRY(h, h->dV0S.alloc(b * nz)); h->dCold.reset(); h->cold_ref = false;
     HIP_TRY(h, hipMemset(h->dFS, 0, b * nz * sizeof(double))); HIP_TRY(h, hipMemset(h->dV0S, 0, b * nz * sizeof(double)));
     h->xref_stride = 0; h->uref_stride = 0; h->fS_stride = nz;
     for (auto& e : q.ev)
@@ -3144,7 +3156,7 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
     q.structured_qp = keep_structured;
     q.hessian = keep_hessian;
     q.row_mult = keep_rows;
-    h->dXref.reset(); h->dUref.reset(); h->dFS.reset(); h->dV0S.reset();
+    h->dXref.reset(); h->dUref.reset(); h->dFS.reset(); h->dV0S.reset(); h->dCold.reset(); h->cold_ref = false;
     h->ref_keep = false;
     std::vector<double> xr((size_t)n * (N + 1), 0.0), ur((size_t)nz, 0.0);
     if (xref) xr.assign(xref, xref + xr.size());
@@ -3172,7 +3184,7 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
     HIP_TRY(h, hipMemcpy(h->dUmax, umax, m * sizeof(double), hipMemcpyHostToDevice));
     if (h->batched_alloc) {   // the condensed route (also kept ready when a condensed handle sends its QPs to k_riccati after an earlier design)
         HIP_TRY(h, h->bQ.once(b * nz));
-        HIP_TRY(h, h->dFS.alloc(b * nz)); HIP_TRY(h, h->dV0S.alloc(b * nz));
+        HIP_TRY(h, h->dFS.alloc(b * nz)); HIP_TRY(h, h->dV0S.alloc(b * nz)); h->dCold.reset(); h->cold_ref = false;
         // F_i = 0 for an LTV design (the gradient is explicit), so F'_i and V_i stay zero; stage-0 model slots are unused but read
         HIP_TRY(h, hipMemset(h->bF, 0, b * nz * n * sizeof(double)));
         HIP_TRY(h, hipMemset(h->bFs, 0, b * n * nzs * sizeof(double)));
@@ -3727,6 +3739,7 @@ int almpc_set_reference(almpc_handle* h, const double* xref, const double* uref,
     if (!(h->ref_keep && h->dXref.size() == cnt * xs && h->dUref.size() == cnt * us && h->dFS.size() == fcnt * us && h->dV0S.size() == fcnt * us)) {
         h->dXref.reset(); h->dUref.reset(); h->dFS.reset(); h->dV0S.reset();
     }
+    h->cold_ref = false;
     HIP_TRY(h, h->dXref.once(cnt * xs));
     HIP_TRY(h, h->dUref.once(cnt * us));
     HIP_TRY(h, h->dFS.once(fcnt * us));
@@ -3773,8 +3786,17 @@ int almpc_set_reference(almpc_handle* h, const double* xref, const double* uref,
     // v0S = -G fS: constant part of the polish's unconstrained minimiser (k_admm adds the part linear in e0)
     {
         const size_t blocks = (cnt * us + 255) / 256;
+        // shared reference: the same launch makes wS = -Minv fS (constant part of the cold start's first ADMM iterate) and the
+        // prologue's row-constant table, behind W in the workspace the design left
+        NegGmExtra cold;
+        const size_t w = (size_t)n * h->nzs;
+        if (!per_instance && h->dCold && h->dMinv && h->dCold.size() >= w + 9 * (size_t)h->nzs) {
+            cold.G2 = h->dMinv; cold.Out2 = h->dCold + w; cold.tab = h->dCold + w + h->nzs;
+            cold.m = m; cold.dvec = h->dD; cold.rhovec = h->dRho; cold.umin = h->dUmin; cold.umax = h->dUmax; cold.uref = h->dUref;
+            h->cold_ref = true;
+        }
         hipLaunchKernelGGL(k_neg_gm, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, h->stream, nz, h->nzs,
-                           (int)cnt, (int)us, h->dG, h->dFS, h->dV0S, 0L, 0L);
+                           (int)cnt, (int)us, h->dG, h->dFS, h->dV0S, 0L, 0L, cold);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }

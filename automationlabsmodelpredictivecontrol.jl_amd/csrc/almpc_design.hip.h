@@ -911,28 +911,72 @@ inline __global__ __launch_bounds__(256) void k_pack_frags(const double* M, int 
 // ---- Out[:, c] = -G M[:, c] for a few columns (leading dimension ld for M and Out; G dense symmetric, leading dimension nzs).
 // Design-time / set_reference-time helper for the polish's unconstrained minimiser v0 = -G f' = (-G F') e0 + (-G fS):
 // with V = -G F' packed like F', k_admm gets v0 from n columns instead of a second nz x nz product per step.
+//
+// The same launch can carry a second product with the same right-hand sides, Out2 = -G2 M (the cold start's affine first ADMM iterate:
+// W = -Minv F' beside V at design time, wS = -Minv fS beside v0S at set_reference), and -- one column, shared references -- the
+// row-constant table of the ADMM prologue (AdmmParams::rowc): per row the pairs (d, 1/d), (lo, hi), (rho, fS), (v0S, wS) as
+// tab[(pair * nzs + r) * 2 + {0, 1}], pad rows as the prologue sets them.  lo / hi by the prologue's own expression, (umin - uref) * (1 / d),
+// compiled here with the same flags: the finish forms the bounds again for itself and tests ADMM's clipped z against them bit for bit.
+struct NegGmExtra {
+    const double* G2 = nullptr;   // dense symmetric like G, same strides (or null: one product)
+    double* Out2 = nullptr;       // laid out like Out
+    double* tab = nullptr;        // [4][nzs][2] (or null); needs G2 / Out2, ncols == 1 and gridDim.y == 1
+    int m = 0;
+    const double* dvec = nullptr;    // [nzs]
+    const double* rhovec = nullptr;  // [nzs]
+    const double* umin = nullptr;    // [m]
+    const double* umax = nullptr;
+    const double* uref = nullptr;    // [nz]
+};
+
 inline __global__ __launch_bounds__(256) void k_neg_gm(int nz, int nzs, int ncols, int ld, const double* G, const double* M, double* Out,
-                                                long sG, long sM) {
+                                                long sG, long sM, NegGmExtra x = NegGmExtra()) {
     G += blockIdx.y * sG; M += blockIdx.y * sM; Out += blockIdx.y * sM;
+    auto tab_row = [&](int row, double fs, double v0s, double ws) {
+        const bool in = row < nz;
+        const int r = in ? row : 0;
+        const double dv = in ? x.dvec[r] : 1.0;
+        const double ur = x.uref[r];
+        double lo = x.umin[r % x.m] - ur, hi = x.umax[r % x.m] - ur;
+        const double dinv = 1.0 / dv;
+        lo = in ? lo * dinv : 0.0;
+        hi = in ? hi * dinv : 0.0;
+        double* t = x.tab + (size_t)row * 2;
+        t[0] = dv; t[1] = dinv;
+        t[(size_t)nzs * 2] = lo; t[(size_t)nzs * 2 + 1] = hi;
+        t[(size_t)nzs * 4] = x.rhovec[r]; t[(size_t)nzs * 4 + 1] = fs;
+        t[(size_t)nzs * 6] = v0s; t[(size_t)nzs * 6 + 1] = ws;
+    };
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < (long)ncols * nz; t += (long)gridDim.x * blockDim.x) {
         const int c = (int)(t / nz), r = (int)(t % nz);
         const double* mcol = M + (size_t)c * ld;
         // G symmetric: consecutive r, consecutive addresses.  Four partial sums and eight loads in flight: the plain loop was one
         // dependent load-FMA per row of G (27 us for a 100 x 100 product per instance in the SQP loop)
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-        int j = 0;
-        for (; j + 8 <= nz; j += 8) {
-            double g[8], mv[8];
+        auto product = [&](const double* Gp) {
+            double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+            int j = 0;
+            for (; j + 8 <= nz; j += 8) {
+                double g[8], mv[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) { g[u] = G[(size_t)(j + u) * nzs + r]; mv[u] = mcol[j + u]; }
-            a0 += g[0] * mv[0] + g[4] * mv[4];
-            a1 += g[1] * mv[1] + g[5] * mv[5];
-            a2 += g[2] * mv[2] + g[6] * mv[6];
-            a3 += g[3] * mv[3] + g[7] * mv[7];
+                for (int u = 0; u < 8; ++u) { g[u] = Gp[(size_t)(j + u) * nzs + r]; mv[u] = mcol[j + u]; }
+                a0 += g[0] * mv[0] + g[4] * mv[4];
+                a1 += g[1] * mv[1] + g[5] * mv[5];
+                a2 += g[2] * mv[2] + g[6] * mv[6];
+                a3 += g[3] * mv[3] + g[7] * mv[7];
+            }
+            for (; j < nz; ++j) a0 += Gp[(size_t)j * nzs + r] * mcol[j];
+            return -((a0 + a1) + (a2 + a3));
+        };
+        const double o1 = product(G);
+        Out[(size_t)c * ld + r] = o1;
+        if (x.G2) {
+            const double o2 = product(x.G2 + blockIdx.y * sG);
+            x.Out2[blockIdx.y * sM + (size_t)c * ld + r] = o2;
+            if (x.tab) tab_row(r, mcol[r], o1, o2);
         }
-        for (; j < nz; ++j) a0 += G[(size_t)j * nzs + r] * mcol[j];
-        Out[(size_t)c * ld + r] = -((a0 + a1) + (a2 + a3));
     }
+    if (x.tab)
+        for (int row = nz + blockIdx.x * blockDim.x + threadIdx.x; row < nzs; row += gridDim.x * blockDim.x) tab_row(row, 0.0, 0.0, 0.0);
 }
 
 // The same product for ALL columns of one instance at a time (per-instance designs: V_i = -G_i F'_i, n columns): k_neg_gm reads G once
@@ -1049,7 +1093,12 @@ inline int design_shared_device(hipStream_t stream, int n, int m, int N, int nzs
                                 double* dG, double* dD, std::vector<double>& hH, std::vector<double>& hF,
                                 std::vector<double>& hd, std::string& err, const std::vector<int>& rowsel = std::vector<int>(),
                                 int Rs = 0, double* dGhat = nullptr, double* dGnorm = nullptr, int rho_mode = 0,
-                                double* dRho = nullptr, double* dVsOut = nullptr, double* dPlainOut = nullptr) {
+                                double* dRho = nullptr, double* dVsOut = nullptr, double* dPlainOut = nullptr,
+                                DevBuf<double>* keepMinv = nullptr, DevBuf<double>* keepCold = nullptr) {
+    // keepMinv / keepCold (or null, both or neither): two of the design's temporaries go to the caller instead of being freed -- the
+    // plain Minv [nz][nzs] (almpc_set_reference makes wS = -Minv fS from it) and the workspace of k_design_gamma, kr * nzs doubles,
+    // whose head then holds W = -Minv F' as [n][nzs] (zero pad rows), the operand of the cold start's affine first ADMM iterate
+    // (AdmmParams::Wp); almpc_set_reference lays wS and the row-constant table behind it where there is room (kr >= n + 9)
     // dPlainOut (or null): [Minv nz x nzs | H' nz x nzs | F' n x nzs | V n x nzs], the dense column-major operands before they are packed
     // into MFMA fragments -- what the one-wave-per-instance step of small shared problems reads (k_step_inst_wave with stride 0)
     const int nz = m * N;
@@ -1114,7 +1163,12 @@ inline int design_shared_device(hipStream_t stream, int n, int m, int N, int nzs
     hipLaunchKernelGGL(k_design_inverse_chol, dim3(1), dim3(512), inv_lds, stream, nz, nzs, dHs, sigma, (const double*)dRho, dMinv, dFlag, 0L, 0L, 0L, 0L);
     DTRY(hipGetLastError());
     hipLaunchKernelGGL(k_pack_frags, dim3(32), dim3(256), 0, stream, dMinv, nz, nz, nzs, nrb, ks, dMinvFrag);
-    hipLaunchKernelGGL(k_neg_gm, dim3(32), dim3(256), 0, stream, nz, nzs, n, nzs, dG, dFs, dVs, 0L, 0L);
+    NegGmExtra second;
+    if (keepCold) {   // dW (k_design_hessian is done with it) becomes the cold-start workspace: W in its first n * nzs doubles
+        DTRY(hipMemsetAsync(dW, 0, (size_t)n * nzs * sizeof(double), stream));   // (the pad rows of W)
+        second.G2 = dMinv; second.Out2 = dW;
+    }
+    hipLaunchKernelGGL(k_neg_gm, dim3(32), dim3(256), 0, stream, nz, nzs, n, nzs, dG, dFs, dVs, 0L, 0L, second);
     hipLaunchKernelGGL(k_pack_frags, dim3(32), dim3(256), 0, stream, dVs, nz, n, nzs, nrb, ksf, dVFrag);
     if (dVsOut) DTRY(hipMemcpyAsync(dVsOut, dVs, (size_t)n * nzs * sizeof(double), hipMemcpyDeviceToDevice, stream));   // (plain V: the s0 table of the state-row finish)
     if (dPlainOut) {
@@ -1146,6 +1200,7 @@ inline int design_shared_device(hipStream_t stream, int n, int m, int N, int nzs
     DTRY(hipMemcpyAsync(&flag, dFlag, sizeof(int), hipMemcpyDeviceToHost, stream));
     DTRY(hipStreamSynchronize(stream));
 #undef DTRY
+    if (keepCold) { *keepMinv = std::move(dMinv); *keepCold = std::move(dW); }
     if (flag != 0) {
         err = flag == 1 ? "design: condensed Hessian has a non-positive diagonal (R = 0 with an input that does not reach the cost?)"
                         : "design: Cholesky pivot not positive (Hessian not positive definite)";

@@ -121,6 +121,14 @@ struct AdmmParams {
     const double* VFrag;       // [NRB][ksf][64]  -H'^-1 F'  (v0 = V e0 + v0S)
     const double* v0S;         // [1 or batch][nz] -H'^-1 fS
     long v0S_stride;
+    // cold start: x = z = y = 0, so the first right-hand side is -f' and the first iterate -Minv f' = W e0 + wS is affine in e0 like
+    // v0: ksf MFMAs instead of the KS of a full product.  Shared references only: wS = -Minv fS is a column of the table below, and Wp
+    // is given only together with rowc.  Wp == nullptr: the first iterate is a full product like the others.
+    const double* Wp = nullptr;     // [n][nzs] -Minv F', plain column-major with zero pad rows (read as A fragments in place)
+    // shared references (uref_stride == fS_stride == 0) with a table made at set_reference (k_neg_gm's epilogue), or null: per row the pairs
+    // (d, 1/d), (lo, hi), (rho, fS), (v0S, wS) as rowc[(pair * nzs + row) * 2 + {0, 1}]: 16 loads of 16 bytes per lane in place of
+    // 35 of 8 bytes, and no division per step.  lo / hi are made by the prologue's own expression (the finish re-derives them)
+    const double* rowc = nullptr;
     const double* HFrag;       // [NRB][KS][64]   H'   (warm start only)
     const double* FFrag;       // [NRB][KSF][64]  F' = D F
     int ksf;
@@ -176,16 +184,36 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
 
     // ---- every other global load of the prologue is requested up front as well (one exposed latency, not five):
     // F' fragments, the row constants, and x0 / x_ref for e0
-    constexpr int KSF_MAX = 16;  // n <= 64
-    double af[KSF_MAX];
+    // Three n-column products share the B operand e0: f' = F' e0 + fS, v0 = V e0 + v0S (for the finish) and, on a cold start, the
+    // first iterate W e0 + wS.  Their first KSF_FAST fragments (all of them for n <= 16) are requested here, ahead of the inverse's;
+    // larger n fetches the rest KSF_FAST at a time behind the barrier (the arrays stay KSF_FAST long: no 3 x 16 live doubles).
+    constexpr int KSF_FAST = 4;
+    const bool tabled = p.rowc != nullptr;
+    const bool affine = !p.warm && tabled && p.Wp != nullptr;
+    double af[KSF_FAST], aw[KSF_FAST], av[KSF_FAST];
 #pragma unroll
-    for (int ks = 0; ks < KSF_MAX; ++ks)
-        af[ks] = (ks < p.ksf) ? p.FFrag[((size_t)(wv * p.ksf + ks)) * 64 + lane] : 0.0;
+    for (int ks = 0; ks < KSF_FAST; ++ks) {
+        const bool on = ks < p.ksf;
+        const size_t o = ((size_t)(wv * p.ksf + ks)) * 64 + lane;
+        af[ks] = on ? p.FFrag[o] : 0.0;
+        aw[ks] = (on && affine && 4 * ks + q < p.n) ? p.Wp[(size_t)(4 * ks + q) * p.nzs + wv * 16 + col] : 0.0;
+        av[ks] = on ? p.VFrag[o] : 0.0;
+    }
     int row[4];
-    double dv[4], dinv[4], lo[4], hi[4], fs[4], rho[4];
+    double dv[4], dinv[4], lo[4], hi[4], fs[4], rho[4], v0s[4], ws[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) row[i] = wv * 16 + q + 4 * i;
+    if (tabled) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const d2v* t = reinterpret_cast<const d2v*>(p.rowc) + row[i];
+            const d2v c0 = t[0], c1 = t[p.nzs], c2 = t[2 * p.nzs], c3 = t[3 * p.nzs];
+            dv[i] = c0[0]; dinv[i] = c0[1]; lo[i] = c1[0]; hi[i] = c1[1];
+            rho[i] = c2[0]; fs[i] = c2[1]; v0s[i] = c3[0]; ws[i] = c3[1];
+        }
+    } else {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        row[i] = wv * 16 + q + 4 * i;
         const bool in = row[i] < p.nz;
         const int r = in ? row[i] : 0;
         dv[i] = in ? p.dvec[r] : 1.0;
@@ -194,6 +222,9 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
         lo[i] = p.umin[r % p.m] - ur;   // scaled below
         hi[i] = p.umax[r % p.m] - ur;
         fs[i] = in ? p.fS[(size_t)instc * p.fS_stride + r] : 0.0;
+        v0s[i] = in ? p.v0S[(size_t)instc * p.v0S_stride + r] : 0.0;
+        ws[i] = 0.0;   // (no table, no affine first iterate)
+    }
     }
     // ---- e0 = x0 - x_ref[:,1] into LDS as B operand [k][16]
     const int kpf = 4 * p.ksf;
@@ -216,22 +247,50 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
     __syncthreads();
     ALMPC_STAMP(blockIdx.x * NRB + wv, 6);
 
-    // ---- per-row constants and f' = F' e0 + fS
+    // ---- per-row constants, f' = F' e0 + fS, v0 = -H'^-1 f' = V e0 + v0S (V = -H'^-1 F' from the design, v0S = -H'^-1 fS from
+    // set_reference; carried in registers to the flush) and the cold start's first iterate xt1 = -Minv f' = W e0 + wS
+    d4 xt1 = {ws[0], ws[1], ws[2], ws[3]};
+    d4 v04 = {v0s[0], v0s[1], v0s[2], v0s[3]};
     {
         d4 acc = {0.0, 0.0, 0.0, 0.0};
+        for (int ks0 = 0; ks0 < p.ksf; ks0 += KSF_FAST) {
+            if (ks0 > 0) {
 #pragma unroll
-        for (int ks = 0; ks < KSF_MAX; ++ks)
-            if (ks < p.ksf) acc = mfma_f64(af[ks], e0s[(4 * ks + q) * TILE + col], acc);
+                for (int u = 0; u < KSF_FAST; ++u) {
+                    const bool on = ks0 + u < p.ksf;
+                    const size_t o = ((size_t)(wv * p.ksf + ks0 + u)) * 64 + lane;
+                    af[u] = on ? p.FFrag[o] : 0.0;
+                    aw[u] = (on && affine && 4 * (ks0 + u) + q < p.n) ? p.Wp[(size_t)(4 * (ks0 + u) + q) * p.nzs + wv * 16 + col] : 0.0;
+                    av[u] = on ? p.VFrag[o] : 0.0;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < KSF_FAST; ++u)
+                if (ks0 + u < p.ksf) {
+                    const double b = e0s[(4 * (ks0 + u) + q) * TILE + col];
+                    acc = mfma_f64(af[u], b, acc);
+                    v04 = mfma_f64(av[u], b, v04);
+                    if (affine) xt1 = mfma_f64(aw[u], b, xt1);
+                }
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const bool in = row[i] < p.nz;
-            dinv[i] = 1.0 / dv[i];
-            lo[i] = in ? lo[i] * dinv[i] : 0.0;
-            hi[i] = in ? hi[i] * dinv[i] : 0.0;
+            if (!tabled) {
+                dinv[i] = 1.0 / dv[i];
+                lo[i] = in ? lo[i] * dinv[i] : 0.0;
+                hi[i] = in ? hi[i] * dinv[i] : 0.0;
+            }
             fs[i] = in ? acc[i] + fs[i] : 0.0;
         }
     }
 
+    // the affine first iterate waits in the lane's own slots of rhs0 (which it alone reads back), not in registers that would stay
+    // live through the warm-start block and the loop
+    if (affine) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rhs0[row[i] * TILE + col] = xt1[i];
+    }
     ALMPC_STAMP(blockIdx.x * NRB + wv, 7);
     // ---- initial iterate
     // y is carried in scaled form yt = y / rho_i (the update needs no 1/rho then); rho_i is per row
@@ -275,7 +334,7 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         rown[i] = sigma * x[i] - fs[i] + rho[i] * (z[i] - yt[i]);
-        rhs0[row[i] * TILE + col] = rown[i];
+        if (!affine) rhs0[row[i] * TILE + col] = rown[i];   // (the affine first iterate reads no right-hand side)
     }
     // |f/d|_inf per instance (constant part of the dual tolerance)
     {
@@ -296,7 +355,11 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
     double* cur = rhs0;
     double* nxt = rhs1;
     for (int it = 1; it <= p.max_iter; ++it) {
-        const d4 xt4 = tile_matmul<KS>(a, cur, q, col);
+        d4 xt4;
+        if (it == 1 && affine) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) xt4[i] = cur[row[i] * TILE + col];
+        } else xt4 = tile_matmul<KS>(a, cur, q, col);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const double xt = xt4[i];
@@ -338,6 +401,8 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
         __syncthreads();
         if (check) {
             double rp = 0, nx = 0, nzn = 0, rd = 0, nhx = 0, ny = 0, bad = 0;
+            // (four waves' partials per round: all 7 x NRB reads in flight at once were the register peak of the 8-wave kernels)
+#pragma unroll 4
             for (int w2 = 0; w2 < NRB; ++w2) {
                 const double* r = red + w2 * 8 * TILE + col;
                 rp = fmax(rp, r[0 * TILE]); nx = fmax(nx, r[1 * TILE]); nzn = fmax(nzn, r[2 * TILE]);
@@ -358,14 +423,6 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
     }
 
     ALMPC_STAMP(blockIdx.x * NRB + wv, 2);
-    // ---- v0 = -H'^-1 f' for the polish.  f' = F' e0 + fS is affine in e0, so v0 = V e0 + v0S with V = -H'^-1 F' (design)
-    // and v0S = -H'^-1 fS (set_reference): n columns instead of a second nz x nz tile product.  Loads issued before the stores.
-#pragma unroll
-    for (int ks = 0; ks < KSF_MAX; ++ks)
-        af[ks] = (ks < p.ksf) ? p.VFrag[((size_t)(wv * p.ksf + ks)) * 64 + lane] : 0.0;
-    double v0s[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v0s[i] = (row[i] < p.nz) ? p.v0S[(size_t)instc * p.v0S_stride + row[i]] : 0.0;
     if (valid && wv == 0 && q == 0) {
         p.iters[inst] = my_iters;
         p.status[inst] = my_status;
@@ -398,10 +455,6 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
         }
         p.perm[blockIdx.x * TILE + rank] = valid ? inst : -1;
     }
-    d4 v04 = {v0s[0], v0s[1], v0s[2], v0s[3]};
-#pragma unroll
-    for (int ks = 0; ks < KSF_MAX; ++ks)
-        if (ks < p.ksf) v04 = mfma_f64(af[ks], e0s[(4 * ks + q) * TILE + col], v04);
     ALMPC_STAMP(blockIdx.x * NRB + wv, 3);
 
     // ---- results (scaled coordinates) to HBM: transpose each [row][instance] register tile through LDS so that every

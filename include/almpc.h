@@ -88,6 +88,13 @@ typedef struct almpc_opts {
  * are identical.  The next almpc_calculate on the handle must then not ask for warm_start (ALMPC_ERR_INVALID).  Shared-model
  * steps with polish = 1 only; ignored otherwise. */
 #define ALMPC_OPT_NO_WARM_STATE 0x1
+/* A/B control of the cold start's first ADMM iterate.  With x = z = y = 0 the first iterate -Minv f' is affine in e0 = x0 - x_ref[:,1]
+ * and a shared-model step takes it from an n-column product (W e0 + wS, W = -Minv F' from the design, wS = -Minv fS from
+ * almpc_set_reference).  With this bit the first iterate is a full nz x nz product like the others (the same iteration, summed in
+ * another order: results agree to rounding).  The affine form needs wS and exists for SHARED references only: per-instance references
+ * (almpc_set_reference with per_instance = 1), warm starts, per-instance models, and shapes whose design workspace has no room for wS
+ * behind W (fewer than n + 9 rows of n * N rounded up to 32: N = 1 with large n) always take the full product; the bit is ignored there. */
+#define ALMPC_OPT_FULL_FIRST_PRODUCT 0x2
 
 void almpc_default_opts(almpc_opts* opts);
 
