@@ -134,6 +134,16 @@ def load():
     L.almpc_get_model_instance.restype = ctypes.c_int
     L.almpc_group_set_model_time.argtypes = [_hp, ctypes.c_int, ctypes.c_double]
     L.almpc_group_set_model_time.restype = ctypes.c_int
+    L.almpc_sensitivity.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double]
+    L.almpc_get_sensitivity.argtypes = [_hp, _dp, _dp, _dp, _ip]
+    L.almpc_device_sensitivity.argtypes = [_hp] + [ctypes.POINTER(ctypes.c_void_p)] * 4
+    L.almpc_sensitivity_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, _dp, _ip]
+    L.almpc_group_sensitivity.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double]
+    L.almpc_group_get_sensitivity.argtypes = [_hp, _dp, _dp, _dp, _ip]
+    L.almpc_group_sensitivity_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, _dp, _ip]
+    for nm_ in ("almpc_sensitivity", "almpc_get_sensitivity", "almpc_device_sensitivity", "almpc_sensitivity_vjp",
+                "almpc_group_sensitivity", "almpc_group_get_sensitivity", "almpc_group_sensitivity_vjp"):
+        getattr(L, nm_).restype = ctypes.c_int
     L.almpc_set_structured_fallback.argtypes = [_hp, ctypes.c_int]
     L.almpc_relin_fnn_setup.argtypes = [_hp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_dp] * 12 + [ctypes.c_double, ctypes.c_double]
     L.almpc_relin_fnn_setup.restype = ctypes.c_int
@@ -230,6 +240,45 @@ OPT_NO_WARM_STATE = 0x1  # almpc.h: ALMPC_OPT_NO_WARM_STATE (opts.reserved[0])
 OPT_FULL_FIRST_PRODUCT = 0x2  # almpc.h: ALMPC_OPT_FULL_FIRST_PRODUCT (opts.reserved[0]): A/B control of the cold start's affine first iterate
 # almpc.h: ALMPC_WANT_* (almpc_get_results_async)
 WANT = {"x": 0x01, "e_x": 0x02, "u": 0x04, "e_u": 0x08, "status": 0x10, "iters": 0x20, "polish_iters": 0x40, "u0": 0x80}
+# almpc.h: ALMPC_SENS_* (almpc_sensitivity)
+SENS = {"K0": 0x1, "dU": 0x2, "dX": 0x4}
+
+
+def _sens_mask(want):
+    mask = 0
+    for k in ((want,) if isinstance(want, str) else want):
+        if k not in SENS:
+            raise ValueError(f"unknown sensitivity {k!r} (one of {sorted(SENS)})")
+        mask |= SENS[k]
+    if not mask:
+        raise ValueError("sensitivity: nothing asked for")
+    return mask
+
+
+def _sens_read(get, handle, check, want, b, n, m, N):
+    """The Jacobians of the last sensitivity call, Julia-shaped: K0 (batch, m, n), dU (batch, m, N, n), dX (batch, n, N+1, n)
+    -- [b, i, k, c] = d(entry i of stage k) / d x0[c] --, and rows (batch,)."""
+    mask = _sens_mask(want)
+    K0 = np.empty((b, n, m)) if mask & SENS["K0"] else None
+    dU = np.empty((b, n, N, m)) if mask & SENS["dU"] else None
+    dX = np.empty((b, n, N + 1, n)) if mask & SENS["dX"] else None
+    rows = np.empty(b, dtype=np.int32)
+    check(get(handle, _ptr(K0), _ptr(dU), _ptr(dX), rows.ctypes.data_as(_ip)))
+    out = {"rows": rows}
+    if K0 is not None: out["K0"] = K0.transpose(0, 2, 1)
+    if dU is not None: out["dU"] = dU.transpose(0, 3, 2, 1)
+    if dX is not None: out["dX"] = dX.transpose(0, 3, 2, 1)
+    return out
+
+
+def _sens_vjp(call, handle, check, g_u, g_x, act_tol, b, n, m, N):
+    g_u = np.ascontiguousarray(np.asarray(g_u, dtype=np.float64).reshape(b, m, N).transpose(0, 2, 1))
+    if g_x is not None:
+        g_x = np.ascontiguousarray(np.asarray(g_x, dtype=np.float64).reshape(b, n, N + 1).transpose(0, 2, 1))
+    g_x0 = np.empty((b, n))
+    rows = np.empty(b, dtype=np.int32)
+    check(call(handle, _ptr(g_u), _ptr(g_x), float(act_tol), _ptr(g_x0), rows.ctypes.data_as(_ip)))
+    return g_x0, rows
 
 
 def _want_mask(want):
@@ -867,6 +916,24 @@ class Solver:
             if k in bufs: bufs[k] = bufs[k].transpose(0, 2, 1)
         return bufs
 
+    # ---- sensitivities of the last step to x0 (include/almpc.h "Sensitivities"; an extension beyond the reference's surface)
+    def sensitivity(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
+        """almpc_sensitivity + almpc_get_sensitivity: K0 (batch, m, n) = du[:,1]/dx0, dU (batch, m, N, n), dX (batch, n, N+1, n),
+        each [b, i, k, c] = d(entry i of stage k) / d x0[c], and rows (batch,) = rows at a bound (-1: instance not solved, zeros).
+        act_tol <= 0: 1e-9 (in units of the row's Jacobi scale)."""
+        self._check(self.L.almpc_sensitivity(self.h, _sens_mask(want), float(act_tol)))
+        return _sens_read(self.L.almpc_get_sensitivity, self.h, self._check, want, self.batch, self.n, self.m, self.N)
+
+    def device_sensitivity(self):
+        ps = [ctypes.c_void_p() for _ in range(4)]
+        self._check(self.L.almpc_device_sensitivity(self.h, *[ctypes.byref(p) for p in ps]))
+        return dict(zip(("K0", "dU", "dX", "rows"), [p.value for p in ps]))
+
+    def sensitivity_vjp(self, g_u, g_x=None, act_tol=0.0):
+        """dL/dx0 (batch, n) for a loss with gradients g_u (batch, m, N) and g_x (batch, n, N+1) or None on the returned
+        trajectories (almpc_sensitivity_vjp: no Jacobian is formed); also returns rows (batch,)."""
+        return _sens_vjp(self.L.almpc_sensitivity_vjp, self.h, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
+
     def get_first_input(self):
         """u[:, 1] of every instance, (batch, m): what a receding-horizon caller applies (almpc_get_first_input)."""
         u0 = np.empty((self.batch, self.m))
@@ -1203,6 +1270,15 @@ class Group:
 
     def synchronize(self):
         self._check(self.L.almpc_group_synchronize(self.g))
+
+    def sensitivity(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
+        """Solver.sensitivity for the whole batch (almpc_group_sensitivity + almpc_group_get_sensitivity)."""
+        self._check(self.L.almpc_group_sensitivity(self.g, _sens_mask(want), float(act_tol)))
+        return _sens_read(self.L.almpc_group_get_sensitivity, self.g, self._check, want, self.batch, self.n, self.m, self.N)
+
+    def sensitivity_vjp(self, g_u, g_x=None, act_tol=0.0):
+        """Solver.sensitivity_vjp for the whole batch (almpc_group_sensitivity_vjp)."""
+        return _sens_vjp(self.L.almpc_group_sensitivity_vjp, self.g, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
 
     def get_results(self, want=("x", "e_x", "u", "e_u", "status", "iters", "polish_iters")):
         b, n, m, N = self.batch, self.n, self.m, self.N

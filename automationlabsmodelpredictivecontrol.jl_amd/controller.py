@@ -37,7 +37,7 @@ __all__ = [
     "TerminalIngredient", "ModelPredictiveControlTuning", "ModelPredictiveControlResults",
     "ModelPredictiveControlController", "proceed_controller", "_design_reference_mpc",
     "_model_predictive_control_design", "_create_weights_coefficients", "update_initialization", "calculate",
-    "_model_predictive_control_computation", "HipModeler", "shard_range",
+    "_model_predictive_control_computation", "sensitivity", "HipModeler", "shard_range",
 ]
 
 
@@ -571,6 +571,17 @@ def calculate(C: ModelPredictiveControlController) -> None:
         getattr(res, k)[...] = r[k][0] if mod.batch == 1 else r[k]
     if getattr(mod, "sqp", None) is not None:
         mod.sqp["u_prev"] = r["u"].copy()
+
+
+def sensitivity(C: ModelPredictiveControlController, want=("K0",), act_tol: float = 0.0) -> dict:
+    """Derivatives of the last calculate!(C) with respect to the initial state.  An extension of this build: the reference's
+    surface stops at the four result matrices (src/main/computation_mpc.jl:50-53).  Returns {"K0": du[:,1]/dx0 (m, n), "dU":
+    (m, N, n), "dX": (n, N+1, n), "rows": rows at a bound} for what `want` names, with a leading batch axis when the controller
+    has more than one instance; u ~ u* + K0 (x - x0) is the exact local law on the current critical region.  Linear controllers
+    with an input box (modeler.solver.sensitivity / sensitivity_vjp say what else is refused)."""
+    mod: HipModeler = C.tuning.modeler
+    out = mod.solver.sensitivity(want, act_tol)
+    return {k: (v[0] if mod.batch == 1 else v) for k, v in out.items()}
 
 
 def _model_predictive_control_computation(C: ModelPredictiveControlController, X0):

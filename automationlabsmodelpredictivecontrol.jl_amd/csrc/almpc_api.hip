@@ -15,6 +15,7 @@
 #include "almpc_sdual.hip.h"
 #include "almpc_dare.hip.h"
 #include "almpc_c2d.hip.h"
+#include "almpc_sens.hip.h"
 #include "almpc_host_math.h"
 #include "almpc_switches.h"
 #include "almpc_devbuf.h"
@@ -36,6 +37,7 @@
 #include "instances/design_b.inc"
 #include "instances/dare.inc"
 #include "instances/c2d.inc"
+#include "instances/sens.inc"
 #undef ALMPC_KERNEL_INSTANCE
 #endif
 
@@ -221,6 +223,19 @@ struct almpc_handle {
     double model_Ts = 0.0;
     bool c_step = false;        // the re-linearisation pipeline was set up with the mode on: every step discretises its Jacobians
     DevBuf<int32_t> cStat;      // [batch] k_c2d's status words of the last design / step
+    // Solution sensitivities (almpc_sensitivity, almpc_sensitivity_vjp; k_sens, csrc/almpc_sens.hip.h).  Every buffer is made at the
+    // first call that needs it (grow): a handle that never asks allocates and launches what it did.
+    struct Sens {
+        DevBuf<double> K0, dU, dX;      // [batch][n][m], [batch][n][N][m], [batch][n][N+1][n] of the last almpc_sensitivity
+        DevBuf<int32_t> rows;           // [batch] its |W| per instance (-1: not solved)
+        uint32_t have = 0;              // ALMPC_SENS_* bits the buffers hold for the LAST step (0: none)
+        DevBuf<double> V;               // [n][nzs] plain V of a shared design (the handle keeps it in MFMA fragment order only)
+        bool v_ok = false;              // ... unpacked from the current design
+        DevBuf<int32_t> ovf;            // [SENS_OVF_HEAD + batch] instances beyond the first tier's 32 rows
+        DevBuf<double> gu, gx, gx0;     // VJP: uploaded loss gradients, result [batch][n]
+        DevBuf<int32_t> vrows;          // [batch] |W| of the last VJP
+        bool stepped = false;           // a step has run on the current design
+    } sens;
     // stage-wise dual active-set solve (k_sdual, csrc/almpc_sdual.hip.h): input box, state box, terminal equality and S in the
     // multiple-shooting form; stage records of the unconstrained problem (shared: host Riccati at design time)
     struct Sd {
@@ -1156,6 +1171,7 @@ int wait_and_settle(almpc_handle* h, bool blocking_only = false) {
 
 // A new design voids a redo that was deferred for a step of the previous one (its models, references and results are about to go)
 void drop_lazy_redo(almpc_handle* h) {
+    h->sens.stepped = false; h->sens.v_ok = false; h->sens.have = 0;   // (what a sensitivity call looks at goes with the design as well)
     h->redo.lazy_pending = false;
     h->redo.expected = false;
     if (h->redo.hUnsolved) h->redo.unsolved_seen = *reinterpret_cast<volatile int*>(h->redo.hUnsolved.get());
@@ -2741,6 +2757,7 @@ int run_step(almpc_handle* h, const almpc_opts& o, StepMode mode) {
     }
     if (rc != ALMPC_OK) return rc;
     h->state_valid = keep_state;   // (recorded only here: every launch of the step went out)
+    h->sens.stepped = true; h->sens.have = 0;
     if (h->io.x0_slot >= 0) {      // the x0 slot of an asynchronous update is free again once this step has finished
         HIP_TRY(h, hipEventRecord(h->io.ev_used[h->io.x0_slot], h->stream));
         h->io.used_pending[h->io.x0_slot] = true;
@@ -4203,6 +4220,152 @@ int almpc_debug_poison_lds(almpc_handle* h) {
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return ALMPC_OK;
 }
+}  // extern "C"
+
+// ---- solution sensitivities (k_sens) --------------------------------------------------------------------------------------------
+namespace {
+
+// What a sensitivity call can look at: the last step of a condensed design with an input box only.
+int sens_check(almpc_handle* h, const char* who) {
+    if (!h) return ALMPC_ERR_INVALID;
+    const std::string w(who);
+    if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, w + " before design");
+    if (h->structured) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": a structured handle forms no condensed inverse G = H'^-1 (the constraint-space form is not built)");
+    if (h->ltv || h->sqp.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": time-varying and SQP designs solve for a step around a trajectory, not for u(x0)");
+    if (h->relin.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the re-linearisation pipeline's models depend on x0 themselves");
+    if (h->mc > 0) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": designs with state rows (state box, terminal equality) need the constraint-space form, which is not built");
+    if (!h->sens.stepped) return fail(h, ALMPC_ERR_INVALID, w + ": no step has run on this design");
+    return ALMPC_OK;
+}
+
+// Operands every k_sens launch shares; the plain V of a shared design is unpacked once per design.
+int sens_params(almpc_handle* h, double act_tol, SensParams& p) {
+    const int n = h->n, nz = h->nz, nzs = h->nzs;
+    p = SensParams();
+    p.n = n; p.m = h->m; p.N = h->N; p.nz = nz; p.nzs = nzs; p.batch = h->batch;
+    if (h->batched) {
+        p.G = h->bG; p.G_stride = (long)nz * nzs; p.V = h->bVs; p.V_stride = (long)n * nzs; p.d = h->bD; p.d_stride = nzs;
+        p.A = h->bA; p.A_stride = (long)n * n; p.B = h->bB; p.B_stride = (long)n * h->m;
+    } else {
+        if (!h->sens.v_ok) {
+            HIP_TRY(h, h->sens.V.grow((size_t)n * nzs));
+            hipLaunchKernelGGL(k_sens_unpack_v, dim3(32), dim3(256), 0, h->stream, h->dVFrag.get(), nz, n, nzs, h->ksf, h->sens.V.get());
+            HIP_TRY(h, hipGetLastError());
+            h->sens.v_ok = true;
+        }
+        p.G = h->dG; p.V = h->sens.V; p.d = h->dD; p.A = h->dA; p.B = h->dB;
+    }
+    p.umin = h->dUmin; p.umax = h->dUmax; p.u = h->dU; p.status = h->dStatus;
+    p.tau = act_tol > 0.0 ? act_tol : 1e-9;
+    p.ch = sens_ch(n);
+    HIP_TRY(h, h->sens.ovf.grow((size_t)SENS_OVF_HEAD + h->batch));
+    p.ovf = h->sens.ovf;
+    return ALMPC_OK;
+}
+
+// The two tiers, back to back on the handle's stream: no host look in between (the second is gated on the list's count word)
+template <bool VJP>
+int sens_launch(almpc_handle* h, SensParams p) {
+    const int n = h->n, nz = h->nz, nzs = h->nzs;
+    const size_t lds2 = nz > SENS_CAP1 ? (size_t)sens_lds_doubles(n, nzs, nz) * sizeof(double) : 0;   // (nothing is enqueued before a refusal)
+    if (lds2 > 160 * 1024) return fail(h, ALMPC_ERR_UNSUPPORTED, "sensitivity: the second tier's working set does not fit LDS");
+    HIP_TRY(h, hipMemsetAsync(h->sens.ovf, 0, SENS_OVF_HEAD * sizeof(int32_t), h->stream));
+    p.cap = SENS_CAP1; p.lds_per_team = sens_lds_doubles(n, nzs, p.cap);
+    const size_t lds1 = (size_t)SENS_WAVES * p.lds_per_team * sizeof(double);
+    HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens<VJP, false>), lds1));
+    hipLaunchKernelGGL((k_sens<VJP, false>), dim3((unsigned)((h->batch + SENS_WAVES - 1) / SENS_WAVES)), dim3(64 * SENS_WAVES), lds1, h->stream, p);
+    HIP_TRY(h, hipGetLastError());
+    if (nz > SENS_CAP1) {   // (a working set cannot outgrow the first tier otherwise)
+        p.cap = nz; p.lds_per_team = sens_lds_doubles(n, nzs, p.cap);
+        HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens<VJP, true>), lds2));
+        hipLaunchKernelGGL((k_sens<VJP, true>), dim3((unsigned)std::min(h->batch, 4 * h->num_cus)), dim3(SENS_WG), lds2, h->stream, p);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return ALMPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int almpc_sensitivity(almpc_handle* h, uint32_t want, double act_tol) {
+    { const int rc_ = sens_check(h, "sensitivity"); if (rc_ != ALMPC_OK) return rc_; }
+    if (!want || (want & ~(ALMPC_SENS_K0 | ALMPC_SENS_DU | ALMPC_SENS_DX))) return fail(h, ALMPC_ERR_INVALID, "sensitivity: want must be a mask of ALMPC_SENS_*");
+    HIP_TRY(h, hipSetDevice(h->device));
+    { const int rc_ = wait_and_settle(h); if (rc_ != ALMPC_OK) return rc_; }   // (a synchronous look: redone instances take part)
+    const size_t b = (size_t)h->batch, n = (size_t)h->n;
+    h->sens.have = 0;
+    SensParams p;
+    { const int rc_ = sens_params(h, act_tol, p); if (rc_ != ALMPC_OK) return rc_; }
+    HIP_TRY(h, h->sens.rows.grow(b));
+    if (want & ALMPC_SENS_K0) HIP_TRY(h, h->sens.K0.grow(b * n * h->m));
+    if (want & (ALMPC_SENS_DU | ALMPC_SENS_DX)) HIP_TRY(h, h->sens.dU.grow(b * n * h->nz));   // (dX is rolled out from dU)
+    if (want & ALMPC_SENS_DX) HIP_TRY(h, h->sens.dX.grow(b * n * (h->N + 1) * n));
+    p.want = want; p.K0 = h->sens.K0; p.dU = h->sens.dU; p.rows = h->sens.rows;
+    { const int rc_ = sens_launch<false>(h, p); if (rc_ != ALMPC_OK) return rc_; }
+    if (want & ALMPC_SENS_DX) {
+        SensDxParams q;
+        q.n = h->n; q.m = h->m; q.N = h->N; q.nz = h->nz; q.batch = h->batch;
+        q.A = p.A; q.A_stride = p.A_stride; q.B = p.B; q.B_stride = p.B_stride; q.dU = h->sens.dU; q.rows = h->sens.rows; q.dX = h->sens.dX;
+        const size_t lds = (size_t)sens_dx_lds_doubles(h->n, h->m) * sizeof(double);
+        HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens_dx), lds));
+        hipLaunchKernelGGL(k_sens_dx, dim3((unsigned)std::min(h->batch, 16 * h->num_cus)), dim3(256), lds, h->stream, q);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, stream_wait_polling(h));
+    h->sens.have = want | ((want & ALMPC_SENS_DX) ? ALMPC_SENS_DU : 0u);
+    return ALMPC_OK;
+}
+
+int almpc_get_sensitivity(almpc_handle* h, double* K0, double* dU, double* dX, int32_t* rows) {
+    if (!h) return ALMPC_ERR_INVALID;
+    const uint32_t need = (K0 ? ALMPC_SENS_K0 : 0u) | (dU ? ALMPC_SENS_DU : 0u) | (dX ? ALMPC_SENS_DX : 0u);
+    if (!h->sens.have || (need & ~h->sens.have))
+        return fail(h, ALMPC_ERR_INVALID, "get_sensitivity: not computed for the last step (almpc_sensitivity with these ALMPC_SENS_* bits first)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t b = (size_t)h->batch, n = (size_t)h->n;
+    if (K0) HIP_TRY(h, hipMemcpy(K0, h->sens.K0, b * n * h->m * sizeof(double), hipMemcpyDeviceToHost));
+    if (dU) HIP_TRY(h, hipMemcpy(dU, h->sens.dU, b * n * h->nz * sizeof(double), hipMemcpyDeviceToHost));
+    if (dX) HIP_TRY(h, hipMemcpy(dX, h->sens.dX, b * n * (h->N + 1) * n * sizeof(double), hipMemcpyDeviceToHost));
+    if (rows) HIP_TRY(h, hipMemcpy(rows, h->sens.rows, b * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return ALMPC_OK;
+}
+
+int almpc_device_sensitivity(almpc_handle* h, const double** d_K0, const double** d_dU, const double** d_dX, const int32_t** d_rows) {
+    if (!h) return ALMPC_ERR_INVALID;
+    if (!h->sens.have) return fail(h, ALMPC_ERR_INVALID, "device_sensitivity: not computed for the last step");
+    if (d_K0) *d_K0 = (h->sens.have & ALMPC_SENS_K0) ? h->sens.K0.get() : nullptr;
+    if (d_dU) *d_dU = (h->sens.have & ALMPC_SENS_DU) ? h->sens.dU.get() : nullptr;
+    if (d_dX) *d_dX = (h->sens.have & ALMPC_SENS_DX) ? h->sens.dX.get() : nullptr;
+    if (d_rows) *d_rows = h->sens.rows.get();
+    return ALMPC_OK;
+}
+
+int almpc_sensitivity_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows) {
+    { const int rc_ = sens_check(h, "sensitivity_vjp"); if (rc_ != ALMPC_OK) return rc_; }
+    if (!g_u || !g_x0) return fail(h, ALMPC_ERR_INVALID, "sensitivity_vjp: null g_u or g_x0");
+    HIP_TRY(h, hipSetDevice(h->device));
+    { const int rc_ = wait_and_settle(h); if (rc_ != ALMPC_OK) return rc_; }
+    const size_t b = (size_t)h->batch, n = (size_t)h->n, xs = n * (h->N + 1);
+    SensParams p;
+    { const int rc_ = sens_params(h, act_tol, p); if (rc_ != ALMPC_OK) return rc_; }
+    HIP_TRY(h, h->sens.vrows.grow(b)); HIP_TRY(h, h->sens.gx0.grow(b * n)); HIP_TRY(h, h->sens.gu.grow(b * h->nz));
+    HIP_TRY(h, hipMemcpyAsync(h->sens.gu, g_u, b * h->nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (g_x) {
+        HIP_TRY(h, h->sens.gx.grow(b * xs));
+        HIP_TRY(h, hipMemcpyAsync(h->sens.gx, g_x, b * xs * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    p.g_u = h->sens.gu; p.g_x = g_x ? h->sens.gx.get() : nullptr; p.g_x0 = h->sens.gx0; p.rows = h->sens.vrows;
+    { const int rc_ = sens_launch<true>(h, p); if (rc_ != ALMPC_OK) return rc_; }
+    HIP_TRY(h, hipMemcpyAsync(g_x0, h->sens.gx0, b * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (rows) HIP_TRY(h, hipMemcpyAsync(rows, h->sens.vrows, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, stream_wait_polling(h));
+    return ALMPC_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 #ifdef ALMPC_STAMPS
 // diagnostic build: allocate / fetch the stamp buffer ([waves][16] int64)

@@ -609,6 +609,32 @@ int almpc_group_get_results(almpc_group* g, double* x, double* e_x, double* u, d
     return ALMPC_OK;
 }
 
+// Sensitivities of the whole batch (almpc_sensitivity and its getters): every device looks at its own shard's last step at the same
+// time; host arrays are those of the single-handle calls with `batch` = the whole batch, cut along the shards.
+int almpc_group_sensitivity(almpc_group* g, uint32_t want, double act_tol) {
+    if (!g) return ALMPC_ERR_INVALID;
+    return group_fanout(g, [&](int i) { return almpc_sensitivity(g->hs[i], want, act_tol); });
+}
+int almpc_group_get_sensitivity(almpc_group* g, double* K0, double* dU, double* dX, int32_t* rows) {
+    if (!g) return ALMPC_ERR_INVALID;
+    const size_t n = (size_t)g->n, nz = (size_t)g->m * g->N;
+    for (size_t i = 0; i < g->hs.size(); ++i) {
+        const size_t f = (size_t)g->first[i];
+        const int rc = almpc_get_sensitivity(g->hs[i], K0 ? K0 + f * n * g->m : nullptr, dU ? dU + f * n * nz : nullptr,
+                                             dX ? dX + f * n * (g->N + 1) * n : nullptr, rows ? rows + f : nullptr);
+        if (rc != ALMPC_OK) return gfail(g, rc, (int)i);
+    }
+    return ALMPC_OK;
+}
+int almpc_group_sensitivity_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows) {
+    if (!g || !g_u || !g_x0) return ALMPC_ERR_INVALID;
+    const size_t n = (size_t)g->n, nz = (size_t)g->m * g->N;
+    return group_fanout(g, [&](int i) {
+        const size_t f = (size_t)g->first[i];
+        return almpc_sensitivity_vjp(g->hs[i], g_u + f * nz, g_x ? g_x + f * n * (g->N + 1) : nullptr, act_tol, g_x0 + f * n, rows ? rows + f : nullptr);
+    });
+}
+
 // Asynchronous read-back of the whole batch: the request goes to every device (pack kernels / copy streams), the ticket is the group's;
 // almpc_group_get_results_wait gathers into the caller's arrays (layouts of almpc_group_get_results).  The last two tickets are kept.
 int almpc_group_get_results_async(almpc_group* g, uint32_t want) {

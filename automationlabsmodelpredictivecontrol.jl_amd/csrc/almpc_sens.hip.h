@@ -1,0 +1,355 @@
+// almpc_sens.hip.h -- k_sens: sensitivities of the returned solution to the measured state x0, per instance, after a step.
+//
+// Notation of DESIGN.md section 1: scaled QP  min 1/2 w'H'w + f''w,  lo <= w <= hi,  f' = F' e0 + fS,  e0 = x0 - x_ref[:,1],
+// v = d o w,  u = v + u_ref.  W = the rows of the returned u that sit at a bound (rule below).  On the face where those rows are
+// held, with G = H'^-1, V = -G F' and S = G[W,W] (a principal block of an SPD matrix):
+//     dw/dx0 = V - G[:,W] S^-1 V[W,:]          (nz x n; the rows W are zero)
+//     du/dx0 = diag(d) dw/dx0                  (dU; K0 = its first m rows)
+//     dx[:,1]/dx0 = I,  dx[:,k+1]/dx0 = A dx[:,k]/dx0 + B du[:,k]/dx0        (dX: k_sens_dx)
+// and for a loss with gradients g_u [N][m], g_x [N+1][n] the vector-Jacobian product without any Jacobian:
+//     lam_{N+1} = g_x[N+1],  lam_k = A'lam_{k+1} + g_x[k],   p = d o (g_u + [B'lam_2; ...; B'lam_{N+1}])  (zero on the rows W),
+//     g_x0 = lam_1 + V'p - V[W,:]' S^-1 (G[W,:] p).
+// The input-rate weight enters H and the constant fS only, so it changes nothing here.
+//
+// Active-set rule: row j = (stage k, input i) is in W iff  u[i,k] - umin_i <= tau d_j  or  umax_i - u[i,k] <= tau d_j  (d_j the row's
+// Jacobi scale; exact equality would miss a bound by an ulp: u = d ((umin - u_ref) / d) + u_ref).  The test is on the returned u.  At a
+// weakly active row (multiplier zero) the solution map is only directionally differentiable: what comes out is the derivative of the
+// face on which every row at its bound is held.
+//
+// Shape: two tiers, as k_polish_gen / k_polish_gen64.  k_sens<VJP, false>: one wave per instance, SENS_WAVES waves per workgroup that
+// never wait for each other, S up to 32 x 32 in LDS; an instance with more rows is appended to a list (count word + indices).
+// k_sens<VJP, true>: one workgroup of 256 threads per listed instance, S up to nz x nz in LDS; its grid strides over the list, so an
+// empty list returns at once.  Both run the same body on a "team" (64 lanes and wave fences, or 256 threads and barriers):
+//   1  flags of the rows at a bound, in parallel; the row list by one thread, ascending
+//   2  S = G[W,W] into LDS, Cholesky S = L L' in place (a pivot that is not positive and finite: rows = -1, outputs zero)
+//   3  Jacobians: per chunk of `ch` <= 16 columns, Y = S^-1 V[W, chunk] (column-oriented substitutions on all columns at once), then
+//      J = V - G[:,W] Y streamed with thread j on row j (row w of G is column w by symmetry: contiguous), scaled by d, rows W zero
+//      (all nz rows for dU, the first m alone when only K0 is asked for)
+//      VJP: adjoint rollout (lam in LDS), t = G[W,:] p, one solve, two n-column contractions
+// Team LDS (doubles): S cap x (cap | 1), Y cap x ch, p nzs, t cap, lam 2 n; ints: list cap, flags nzs, 4 words.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace almpc {
+
+constexpr int SENS_WAVES = 4;
+constexpr int SENS_CAP1 = 32;       // rows of the first tier
+constexpr int SENS_WG = 256;        // threads of a second-tier workgroup
+constexpr int SENS_OVF_HEAD = 4;    // ints in front of the overflow list: [0] the count (a 16-byte block, zeroed before every call)
+constexpr unsigned SENS_K0 = 1u, SENS_DU = 2u, SENS_DX = 4u;   // ALMPC_SENS_*
+
+struct SensParams {
+    int n, m, N, nz, nzs, batch;
+    const double* G; long G_stride;     // [nz][nzs] symmetric (stride 0: shared)
+    const double* V; long V_stride;     // [n][nzs] plain, V[r, c] at c * nzs + r
+    const double* d; long d_stride;     // [nzs]
+    const double* A; long A_stride;     // n x n column-major (VJP)
+    const double* B; long B_stride;     // n x m
+    const double* umin; const double* umax;   // [m]
+    const double* u;                    // [batch][nz] returned inputs
+    const int32_t* status;              // [batch] almpc_solve_status of the step
+    double tau;
+    int cap, ch;                        // row capacity of this tier (SENS_CAP1 or nz), column chunk (a multiple of 4, <= 16)
+    int lds_per_team;                   // doubles
+    unsigned want;                      // SENS_* (Jacobian mode)
+    double* K0; double* dU;             // [batch][n][m], [batch][n][nz]
+    const double* g_u; const double* g_x;   // [batch][nz], [batch][N+1][n] or null (VJP mode)
+    double* g_x0;                       // [batch][n]
+    int32_t* rows;                      // [batch] |W|, or -1
+    int32_t* ovf;                       // [SENS_OVF_HEAD + batch]
+};
+
+__host__ __device__ inline int sens_ch(int n) { const int c = (n + 3) & ~3; return c < 16 ? c : 16; }
+__host__ __device__ inline int sens_lds_doubles(int n, int nzs, int cap) {
+    const int ints = cap + nzs + 4;
+    return (cap * (cap | 1) + cap * sens_ch(n) + nzs + cap + 2 * n + (ints + 1) / 2 + 1) & ~1;
+}
+
+template <bool WG>
+struct SensTeam {
+    int tid, nt;
+    __device__ __forceinline__ void sync() const {
+        if (WG) __syncthreads();
+        else {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+    }
+};
+
+// X <- S^-1 X for the Cholesky factor L of S (lower triangle of Sl, leading dimension ld): X rows x nc, element (a, c) at a * ldx + c.
+// Column-oriented: row k is divided, then taken out of every row behind (in front) of it -- all columns and rows in parallel.
+template <bool WG>
+__device__ __forceinline__ void sens_solve(const SensTeam<WG>& T, const double* Sl, int ld, int rows, double* X, int ldx, int nc) {
+    for (int k = 0; k < rows; ++k) {
+        const double dk = Sl[k * ld + k];
+        for (int c = T.tid; c < nc; c += T.nt) X[k * ldx + c] /= dk;
+        T.sync();
+        const int cnt = (rows - k - 1) * nc;
+        for (int idx = T.tid; idx < cnt; idx += T.nt) {
+            const int i = k + 1 + idx / nc, c = idx % nc;
+            X[i * ldx + c] -= Sl[i * ld + k] * X[k * ldx + c];
+        }
+        T.sync();
+    }
+    for (int k = rows - 1; k >= 0; --k) {
+        const double dk = Sl[k * ld + k];
+        for (int c = T.tid; c < nc; c += T.nt) X[k * ldx + c] /= dk;
+        T.sync();
+        const int cnt = k * nc;
+        for (int idx = T.tid; idx < cnt; idx += T.nt) {
+            const int i = idx / nc, c = idx % nc;
+            X[i * ldx + c] -= Sl[k * ld + i] * X[k * ldx + c];
+        }
+        T.sync();
+    }
+}
+
+template <bool VJP, bool WG>
+__device__ __forceinline__ void sens_zero(const SensParams& p, const SensTeam<WG>& T, int inst) {
+    const int n = p.n, m = p.m, nz = p.nz;
+    if (VJP) {
+        for (int c = T.tid; c < n; c += T.nt) p.g_x0[(size_t)inst * n + c] = 0.0;
+    } else {
+        if (p.want & SENS_K0)
+            for (int t = T.tid; t < n * m; t += T.nt) p.K0[(size_t)inst * n * m + t] = 0.0;
+        if (p.want & (SENS_DU | SENS_DX))
+            for (int t = T.tid; t < n * nz; t += T.nt) p.dU[(size_t)inst * n * nz + t] = 0.0;
+    }
+}
+
+template <bool VJP, bool WG>
+__device__ __forceinline__ void sens_instance(const SensParams& p, const SensTeam<WG>& T, int inst, double* L) {
+    const int n = p.n, m = p.m, N = p.N, nz = p.nz, nzs = p.nzs, cap = p.cap, ch = p.ch, ld = cap | 1;
+    double* S = L;
+    double* Y = S + cap * ld;
+    double* pv = Y + cap * ch;
+    double* tv = pv + nzs;
+    double* lam = tv + cap;
+    int* wl = reinterpret_cast<int*>(lam + 2 * n);
+    int* act = wl + cap;
+    int* word = act + nzs;   // [0] |W|, [1] the factorisation failed
+    const double* G = p.G + (size_t)inst * p.G_stride;
+    const double* V = p.V + (size_t)inst * p.V_stride;
+    const double* dv = p.d + (size_t)inst * p.d_stride;
+
+    T.sync();   // (the previous instance of this team has read its last LDS operand)
+    // 1: the rows at a bound
+    if (!WG && p.status[inst] != 0) {   // (the second tier only gets solved instances)
+        sens_zero<VJP>(p, T, inst);
+        if (T.tid == 0) p.rows[inst] = -1;
+        return;
+    }
+    for (int j = T.tid; j < nz; j += T.nt) {
+        const double uj = p.u[(size_t)inst * nz + j], tol = p.tau * dv[j];
+        const int i = j % m;
+        act[j] = (uj - p.umin[i] <= tol || p.umax[i] - uj <= tol) ? 1 : 0;
+    }
+    T.sync();
+    if (T.tid == 0) {
+        int r = 0;
+        for (int j = 0; j < nz; ++j)
+            if (act[j]) { if (r < cap) wl[r] = j; ++r; }
+        word[0] = r; word[1] = 0;
+    }
+    T.sync();
+    const int rows = word[0];
+    if (rows > cap) {   // first tier only (the second has cap = nz): hand the instance on
+        if (T.tid == 0) {
+            const int k = atomicAdd(p.ovf, 1);
+            p.ovf[SENS_OVF_HEAD + k] = inst;
+        }
+        return;
+    }
+    // 2: S = G[W,W] = L L'
+    for (int idx = T.tid; idx < rows * rows; idx += T.nt) {
+        const int a = idx / rows, b = idx % rows;
+        S[a * ld + b] = G[(size_t)wl[a] * nzs + wl[b]];
+    }
+    T.sync();
+    for (int k = 0; k < rows; ++k) {
+        if (T.tid == 0) {
+            const double piv = S[k * ld + k];
+            if (!(piv > 0.0 && piv <= 1.7976931348623157e308)) word[1] = 1;
+            S[k * ld + k] = sqrt(piv);
+        }
+        T.sync();
+        if (word[1]) break;   // (the same word for the whole team)
+        const double dk = S[k * ld + k];
+        for (int i = k + 1 + T.tid; i < rows; i += T.nt) S[i * ld + k] /= dk;
+        T.sync();
+        const int rem = rows - k - 1;
+        for (int idx = T.tid; idx < rem * rem; idx += T.nt) {
+            const int i = k + 1 + idx / rem, j = k + 1 + idx % rem;
+            if (j <= i) S[i * ld + j] -= S[i * ld + k] * S[j * ld + k];
+        }
+        T.sync();
+    }
+    if (word[1]) {
+        sens_zero<VJP>(p, T, inst);
+        if (T.tid == 0) p.rows[inst] = -1;
+        return;
+    }
+    if (T.tid == 0) p.rows[inst] = rows;
+
+    if (!VJP) {
+        // 3: per column chunk Y = S^-1 V[W, chunk], then J = V - G[:,W] Y, scaled (K0 alone: only its m rows of J)
+        const int jrows = (p.want & (SENS_DU | SENS_DX)) ? nz : m;
+        for (int c0 = 0; c0 < n; c0 += ch) {
+            const int nc = n - c0 < ch ? n - c0 : ch;
+            for (int idx = T.tid; idx < rows * nc; idx += T.nt) {
+                const int a = idx / nc, c = idx % nc;
+                Y[a * ch + c] = V[(size_t)(c0 + c) * nzs + wl[a]];
+            }
+            T.sync();
+            sens_solve(T, S, ld, rows, Y, ch, nc);
+            for (int j = T.tid; j < jrows; j += T.nt) {
+                const double dj = dv[j];
+                const bool aj = act[j] != 0;
+                for (int q0 = 0; q0 < nc; q0 += 4) {   // (ch is a multiple of 4: columns past nc are read inside Y's row and dropped)
+                    double acc[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) acc[q] = q0 + q < nc ? V[(size_t)(c0 + q0 + q) * nzs + j] : 0.0;
+                    for (int a = 0; a < rows; ++a) {
+                        const double g = G[(size_t)wl[a] * nzs + j];
+                        const double* y = Y + a * ch + q0;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) acc[q] -= g * y[q];
+                    }
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int c = c0 + q0 + q;
+                        if (q0 + q < nc) {
+                            const double val = aj ? 0.0 : dj * acc[q];
+                            if (p.want & (SENS_DU | SENS_DX)) p.dU[((size_t)inst * n + c) * nz + j] = val;
+                            if ((p.want & SENS_K0) && j < m) p.K0[((size_t)inst * n + c) * m + j] = val;
+                        }
+                    }
+                }
+            }
+            T.sync();   // (Y is gathered again)
+        }
+    } else {
+        const double* A = p.A + (size_t)inst * p.A_stride;
+        const double* B = p.B + (size_t)inst * p.B_stride;
+        const double* gu = p.g_u + (size_t)inst * nz;
+        const double* gx = p.g_x ? p.g_x + (size_t)inst * (N + 1) * n : nullptr;
+        double* cur = lam;
+        double* nxt = lam + n;
+        // (0.0 is added where g_x is null, so that a null g_x and a g_x of zeros give the same bits)
+        for (int i = T.tid; i < n; i += T.nt) cur[i] = 0.0 + (gx ? gx[(size_t)N * n + i] : 0.0);
+        T.sync();
+        for (int k = N - 1; k >= 0; --k) {   // cur = lam of state stage k + 1 (0-based): the one input stage k acts on
+            for (int a = T.tid; a < m; a += T.nt) {
+                double s = 0.0;
+                for (int i = 0; i < n; ++i) s += B[i + a * n] * cur[i];
+                const int j = k * m + a;
+                pv[j] = act[j] ? 0.0 : dv[j] * (gu[j] + s);
+            }
+            for (int i = T.tid; i < n; i += T.nt) {
+                double s = 0.0;
+                for (int l = 0; l < n; ++l) s += A[l + i * n] * cur[l];
+                nxt[i] = s + (gx ? gx[(size_t)k * n + i] : 0.0);
+            }
+            T.sync();
+            double* t_ = cur; cur = nxt; nxt = t_;
+        }
+        for (int a = T.tid; a < rows; a += T.nt) {
+            const double* g = G + (size_t)wl[a] * nzs;
+            double s = 0.0;
+            for (int j = 0; j < nz; ++j) s += g[j] * pv[j];
+            tv[a] = s;
+        }
+        T.sync();
+        sens_solve(T, S, ld, rows, tv, 1, 1);
+        for (int c = T.tid; c < n; c += T.nt) {
+            const double* v = V + (size_t)c * nzs;
+            double s1 = 0.0, s2 = 0.0;
+            for (int j = 0; j < nz; ++j) s1 += v[j] * pv[j];
+            for (int a = 0; a < rows; ++a) s2 += v[wl[a]] * tv[a];
+            p.g_x0[(size_t)inst * n + c] = cur[c] + s1 - s2;
+        }
+    }
+}
+
+template <bool VJP, bool WG>
+__global__ __launch_bounds__(256) void k_sens(SensParams p) {
+    extern __shared__ __attribute__((aligned(16))) double sens_smem[];
+    if (WG) {
+        const SensTeam<WG> T{(int)threadIdx.x, (int)blockDim.x};
+        const int count = p.ovf[0];
+        for (int k = blockIdx.x; k < count; k += gridDim.x) sens_instance<VJP, WG>(p, T, p.ovf[SENS_OVF_HEAD + k], sens_smem);
+    } else {
+        const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        const SensTeam<WG> T{(int)(threadIdx.x & 63), 64};
+        double* L = sens_smem + (size_t)wv * p.lds_per_team;
+        const int wpb = (int)(blockDim.x >> 6), nwaves = gridDim.x * wpb;
+        for (int inst = blockIdx.x * wpb + wv; inst < p.batch; inst += nwaves) sens_instance<VJP, WG>(p, T, inst, L);
+    }
+}
+
+// dX from dU: the step's rollout with n right-hand sides.  One workgroup per instance; A, B and two n x n stages in LDS.
+// dX [batch][n][N+1][n]: element (state i, stage k, column c) at ((c (N+1)) + k) n + i.  rows < 0: zeros.
+struct SensDxParams {
+    int n, m, N, nz, batch;
+    const double* A; long A_stride;
+    const double* B; long B_stride;
+    const double* dU;        // [batch][n][nz]
+    const int32_t* rows;     // [batch]
+    double* dX;
+};
+__host__ __device__ inline int sens_dx_lds_doubles(int n, int m) { return 3 * n * n + n * m; }
+
+inline __global__ __launch_bounds__(256) void k_sens_dx(SensDxParams p) {
+    extern __shared__ __attribute__((aligned(16))) double sens_dx_smem[];
+    const int n = p.n, m = p.m, N = p.N, nz = p.nz, tid = threadIdx.x, nt = blockDim.x;
+    double* Al = sens_dx_smem;
+    double* Bl = Al + n * n;
+    double* cur = Bl + n * m;
+    double* nxt = cur + n * n;
+    for (int inst = blockIdx.x; inst < p.batch; inst += gridDim.x) {
+        double* out = p.dX + (size_t)inst * n * (N + 1) * n;
+        __syncthreads();
+        if (p.rows[inst] < 0) {   // (one word for the whole workgroup)
+            for (int t = tid; t < n * (N + 1) * n; t += nt) out[t] = 0.0;
+            continue;
+        }
+        const double* A = p.A + (size_t)inst * p.A_stride;
+        const double* B = p.B + (size_t)inst * p.B_stride;
+        const double* dU = p.dU + (size_t)inst * n * nz;
+        for (int t = tid; t < n * n; t += nt) {
+            Al[t] = A[t];
+            const double e = (t % n == t / n) ? 1.0 : 0.0;
+            cur[t] = e;
+            out[(size_t)(t / n) * (N + 1) * n + t % n] = e;
+        }
+        for (int t = tid; t < n * m; t += nt) Bl[t] = B[t];
+        __syncthreads();
+        for (int k = 0; k < N; ++k) {
+            for (int t = tid; t < n * n; t += nt) {
+                const int i = t % n, c = t / n;
+                double s = 0.0;
+                for (int l = 0; l < n; ++l) s += Al[i + l * n] * cur[l + c * n];
+                const double* du = dU + (size_t)c * nz + (size_t)k * m;
+                for (int a = 0; a < m; ++a) s += Bl[i + a * n] * du[a];
+                nxt[t] = s;
+                out[((size_t)c * (N + 1) + k + 1) * n + i] = s;
+            }
+            __syncthreads();
+            double* t_ = cur; cur = nxt; nxt = t_;
+        }
+    }
+}
+
+// Plain V [n][nzs] (zero pad rows) from the MFMA fragment order a shared design keeps it in (k_pack_frags):
+// frag[(rb * ksf + s) * 64 + l] = V[16 rb + (l & 15)][4 s + (l >> 4)]
+inline __global__ __launch_bounds__(256) void k_sens_unpack_v(const double* frag, int nz, int n, int nzs, int ksf, double* out) {
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n * nzs; t += gridDim.x * blockDim.x) {
+        const int r = t % nzs, c = t / nzs;
+        out[t] = r < nz ? frag[((size_t)(r >> 4) * ksf + (c >> 2)) * 64 + (((c & 3) << 4) | (r & 15))] : 0.0;
+    }
+}
+
+}  // namespace almpc

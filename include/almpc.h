@@ -619,6 +619,10 @@ int almpc_group_update_initialization_staged(almpc_group* g, double* const* slot
 int almpc_group_get_results_async(almpc_group* g, uint32_t want);
 int almpc_group_get_results_wait(almpc_group* g, int ticket, double* x, double* e_x, double* u, double* e_u, double* u0, int32_t* status,
                                  int32_t* iters, int32_t* polish_iters);
+/* almpc_sensitivity / almpc_get_sensitivity / almpc_sensitivity_vjp of the whole batch: arrays as there with `batch` = the whole batch */
+int almpc_group_sensitivity(almpc_group* g, uint32_t want, double act_tol);
+int almpc_group_get_sensitivity(almpc_group* g, double* K0, double* dU, double* dX, int32_t* rows);
+int almpc_group_sensitivity_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows);
 
 /* Design data for parity tests: H nz*nz, F nz*n (both unscaled, column-major), P n*n, d nz. */
 int almpc_get_design(almpc_handle* h, double* H, double* F, double* P, double* d);
@@ -629,6 +633,38 @@ int almpc_get_design(almpc_handle* h, double* H, double* F, double* P, double* d
  */
 int almpc_device_results(almpc_handle* h, const double** d_x, const double** d_e_x,
                          const double** d_u, const double** d_e_u);
+
+/*
+ * Sensitivities of the returned solution to the measured state x0, per instance, after a step (k_sens, DESIGN.md "k_sens"; an
+ * extension: the reference hands out x, e_x, u, e_u only, src/main/computation_mpc.jl:50-53).  W = the rows of the returned u at a
+ * bound: row (stage k, input i) is in W iff u[i,k] - umin_i <= act_tol * d_j or umax_i - u[i,k] <= act_tol * d_j, d_j the row's Jacobi
+ * scale (almpc_get_design); act_tol <= 0 means 1e-9.  The test is on the returned u, not on the finish's internal working set.  With
+ * G = H'^-1, V = -G F', S = G[W,W]:  du/dx0 = diag(d) (V - G[:,W] S^-1 V[W,:]) (rows W are zero), dx[:,1]/dx0 = I,
+ * dx[:,k+1]/dx0 = A dx[:,k]/dx0 + B du[:,k]/dx0.  Where no multiplier of W is zero this is the derivative of the solution map; at a
+ * weakly active row (multiplier zero) the map is only directionally differentiable, and what is returned is the derivative of the face
+ * on which EVERY row at its bound is held.
+ *   almpc_sensitivity          a synchronous look at the LAST step: does what almpc_synchronize does first (the lazy redo included, so
+ *                              redone instances take part), then computes what `want` (a mask of ALMPC_SENS_*) names into device buffers
+ *                              of the handle, which exist from the first such call on (ALMPC_SENS_DX also computes dU).
+ *   almpc_get_sensitivity      copies them out (NULL = not wanted; asking for one that was not computed, or after a newer step:
+ *                              ALMPC_ERR_INVALID); rows [batch] = |W| of every instance.
+ *   almpc_device_sensitivity   the device pointers (NULL for what was not computed); valid until the next almpc_sensitivity.
+ *   almpc_sensitivity_vjp      for a loss L(x, u) with gradients g_u [batch][N][m] and g_x [batch][N+1][n] (NULL: zeros, bit-identical
+ *                              to passing zeros) on the returned trajectories: g_x0 [batch][n] = dL/dx0, without forming a Jacobian
+ *                              (adjoint rollout, one solve with S); host pointers, synchronous like almpc_sensitivity.
+ * An instance whose status is not ALMPC_SOLVED (or whose S is not positive definite to working precision) gets rows = -1 and zeros.
+ * ALMPC_ERR_INVALID before the design's first step.  Served: almpc_design_shared and almpc_design_batched with an input box (shared or
+ * per-instance references, S != 0).  ALMPC_ERR_UNSUPPORTED, with the reason in almpc_last_error: state rows (state box, terminal
+ * equality), ALMPC_FLAG_STRUCTURED handles, almpc_design_ltv, the SQP loop and the re-linearisation pipeline.
+ */
+#define ALMPC_SENS_K0 0x1u   /* [batch][n][m]        du[:,1]/dx0, column-major m x n per instance       */
+#define ALMPC_SENS_DU 0x2u   /* [batch][n][N][m]     Julia Array{Float64,4}(m, N, n, batch)             */
+#define ALMPC_SENS_DX 0x4u   /* [batch][n][N+1][n]                                                      */
+int almpc_sensitivity(almpc_handle* h, uint32_t want, double act_tol);
+int almpc_get_sensitivity(almpc_handle* h, double* K0, double* dU, double* dX, int32_t* rows);      /* NULL = not wanted */
+int almpc_device_sensitivity(almpc_handle* h, const double** d_K0, const double** d_dU, const double** d_dX, const int32_t** d_rows);
+int almpc_sensitivity_vjp(almpc_handle* h, const double* g_u, const double* g_x /* or NULL */, double act_tol,
+                          double* g_x0 /* [batch][n] */, int32_t* rows /* or NULL */);
 
 /*
  * Timing of the last almpc_calculate (needs ALMPC_FLAG_TIMING): milliseconds spent in the ADMM

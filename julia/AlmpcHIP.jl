@@ -19,7 +19,7 @@ export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_s
        group_synchronize!, group_read_results!, group_set_state_rows!, group_set_rho_profile!, group_set_structured_fallback!,
        group_design_batched!, group_design_relin_fnn!, group_relin_step!, group_relin_advance!, group_advance_plant!, group_design_sqp_fnn!,
        group_sqp_start!, group_sqp_iterate!, group_sqp_solve!, group_set_sqp_hessian!, group_set_sqp_row_multipliers!, group_state_multipliers, group_sqp_skipped, group_x0_staging, group_update_initialization_staged!, group_results_async,
-       group_results_wait!
+       group_results_wait!, sensitivity, device_sensitivity, sensitivity_vjp, group_sensitivity, group_sensitivity_vjp
 
 const libalmpc = get(ENV, "ALMPC_LIB", "libalmpc.so")
 
@@ -610,6 +610,56 @@ function model_instance(mod::HipModeler, i::Integer)
     check(mod.handle, ccall((:almpc_get_model_instance, libalmpc), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}), mod.handle, i - 1, A, B))
     return A, B
 end
+# ---- sensitivities of the last step to x0 (include/almpc.h "Sensitivities"; an extension beyond the reference's surface) ----
+const SENS_K0, SENS_DU, SENS_DX = UInt32(1), UInt32(2), UInt32(4)   # ALMPC_SENS_*
+sens_mask(K0::Bool, dU::Bool, dX::Bool) = (K0 ? SENS_K0 : UInt32(0)) | (dU ? SENS_DU : UInt32(0)) | (dX ? SENS_DX : UInt32(0))
+function sens_arrays(n, m, N, batch, K0::Bool, dU::Bool, dX::Bool)
+    (K0 || dU || dX) || error("sensitivity: nothing asked for")
+    return (K0 ? Array{Float64,3}(undef, m, n, batch) : nothing, dU ? Array{Float64,4}(undef, m, N, n, batch) : nothing,
+            dX ? Array{Float64,4}(undef, n, N + 1, n, batch) : nothing, Vector{Int32}(undef, batch))
+end
+function check_sens_sizes(n, m, N, batch, g_u, g_x)
+    length(g_u) == m * N * batch || throw(DimensionMismatch("g_u holds $(length(g_u)) values, the solver reads $(m * N * batch)"))
+    g_x === nothing || length(g_x) == n * (N + 1) * batch ||
+        throw(DimensionMismatch("g_x holds $(length(g_x)) values, the solver reads $(n * (N + 1) * batch)"))
+end
+"""
+    sensitivity(mod; K0 = true, dU = false, dX = false, act_tol = 0.0) -> (K0, dU, dX, rows)
+
+Derivatives of the last step's solution with respect to x0 (`almpc_sensitivity` + `almpc_get_sensitivity`): `K0` m x n x batch
+(the first-move gain), `dU` m x N x n x batch, `dX` n x (N+1) x n x batch (`nothing` for what was not asked for) and `rows`, the
+number of rows at a bound per instance (-1: instance not solved, zeros).
+"""
+function sensitivity(mod::HipModeler; K0::Bool = true, dU::Bool = false, dX::Bool = false, act_tol::Real = 0.0)
+    k, du, dx, rows = sens_arrays(mod.n, mod.m, mod.N, mod.batch, K0, dU, dX)
+    check(mod.handle, ccall((:almpc_sensitivity, libalmpc), Cint, (Ptr{Cvoid}, UInt32, Cdouble), mod.handle, sens_mask(K0, dU, dX), act_tol))
+    pf(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve k du dx check(mod.handle, ccall((:almpc_get_sensitivity, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), mod.handle, pf(k), pf(du), pf(dx), rows))
+    return k, du, dx, rows
+end
+"device pointers of the last `sensitivity` call's buffers (K0, dU, dX, rows; C_NULL for what was not computed)"
+function device_sensitivity(mod::HipModeler)
+    pk, pu, px, pr = Ref{Ptr{Float64}}(C_NULL), Ref{Ptr{Float64}}(C_NULL), Ref{Ptr{Float64}}(C_NULL), Ref{Ptr{Int32}}(C_NULL)
+    check(mod.handle, ccall((:almpc_device_sensitivity, libalmpc), Cint,
+                            (Ptr{Cvoid}, Ref{Ptr{Float64}}, Ref{Ptr{Float64}}, Ref{Ptr{Float64}}, Ref{Ptr{Int32}}), mod.handle, pk, pu, px, pr))
+    return pk[], pu[], px[], pr[]
+end
+"""
+    sensitivity_vjp(mod, g_u, g_x = nothing; act_tol = 0.0) -> (g_x0, rows)
+
+dL/dx0 (n x batch) for a loss with gradients `g_u` (m x N x batch) and `g_x` (n x (N+1) x batch, or nothing) on the returned
+trajectories (`almpc_sensitivity_vjp`: no Jacobian is formed).
+"""
+function sensitivity_vjp(mod::HipModeler, g_u::Array{Float64}, g_x::Union{Nothing,Array{Float64}} = nothing; act_tol::Real = 0.0)
+    check_sens_sizes(mod.n, mod.m, mod.N, mod.batch, g_u, g_x)
+    g_x0, rows = Matrix{Float64}(undef, mod.n, mod.batch), Vector{Int32}(undef, mod.batch)
+    px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
+    GC.@preserve g_x check(mod.handle, ccall((:almpc_sensitivity_vjp, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), mod.handle, g_u, px, act_tol, g_x0, rows))
+    return g_x0, rows
+end
+
 "library defaults of the options (OSQP's, plus the documented changes)"
 function default_opts()
     o = Ref(AlmpcOpts())
@@ -752,6 +802,25 @@ group_set_model_time!(g::HipGroup, mode::Symbol, Ts::Real = 0.0) =
     gcheck(g.group, ccall((:almpc_group_set_model_time, libalmpc), Cint, (Ptr{Cvoid}, Cint, Cdouble), g.group, mode === :continuous ? 1 : 0, Ts))
 group_set_structured_fallback!(g::HipGroup, on::Bool) =
     gcheck(g.group, ccall((:almpc_group_set_structured_fallback, libalmpc), Cint, (Ptr{Cvoid}, Cint), g.group, on ? 1 : 0))
+
+"`sensitivity` for the whole batch (`almpc_group_sensitivity` + `almpc_group_get_sensitivity`)"
+function group_sensitivity(g::HipGroup; K0::Bool = true, dU::Bool = false, dX::Bool = false, act_tol::Real = 0.0)
+    k, du, dx, rows = sens_arrays(g.n, g.m, g.N, g.batch, K0, dU, dX)
+    gcheck(g.group, ccall((:almpc_group_sensitivity, libalmpc), Cint, (Ptr{Cvoid}, UInt32, Cdouble), g.group, sens_mask(K0, dU, dX), act_tol))
+    pf(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve k du dx gcheck(g.group, ccall((:almpc_group_get_sensitivity, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), g.group, pf(k), pf(du), pf(dx), rows))
+    return k, du, dx, rows
+end
+"`sensitivity_vjp` for the whole batch (`almpc_group_sensitivity_vjp`)"
+function group_sensitivity_vjp(g::HipGroup, g_u::Array{Float64}, g_x::Union{Nothing,Array{Float64}} = nothing; act_tol::Real = 0.0)
+    check_sens_sizes(g.n, g.m, g.N, g.batch, g_u, g_x)
+    g_x0, rows = Matrix{Float64}(undef, g.n, g.batch), Vector{Int32}(undef, g.batch)
+    px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
+    GC.@preserve g_x gcheck(g.group, ccall((:almpc_group_sensitivity_vjp, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), g.group, g_u, px, act_tol, g_x0, rows))
+    return g_x0, rows
+end
 
 "`design_batched!` for the whole batch: `A_batch` n x n x batch, `B_batch` n x m x batch, `P` nothing | n x n | n x n x batch"
 function group_design_batched!(g::HipGroup, A_batch::Array{Float64,3}, B_batch::Array{Float64,3}, Q::Matrix{Float64}, R::Matrix{Float64},
