@@ -238,6 +238,7 @@ def load():
 
 OPT_NO_WARM_STATE = 0x1  # almpc.h: ALMPC_OPT_NO_WARM_STATE (opts.reserved[0])
 OPT_FULL_FIRST_PRODUCT = 0x2  # almpc.h: ALMPC_OPT_FULL_FIRST_PRODUCT (opts.reserved[0]): A/B control of the cold start's affine first iterate
+OPT_HBM_HANDOFF = 0x4  # almpc.h: ALMPC_OPT_HBM_HANDOFF (opts.reserved[0]): A/B control of the one-kernel step's LDS hand-off
 # almpc.h: ALMPC_WANT_* (almpc_get_results_async)
 WANT = {"x": 0x01, "e_x": 0x02, "u": 0x04, "e_u": 0x08, "status": 0x10, "iters": 0x20, "polish_iters": 0x40, "u0": 0x80}
 # almpc.h: ALMPC_SENS_* (almpc_sensitivity)

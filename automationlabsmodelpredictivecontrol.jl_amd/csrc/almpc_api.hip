@@ -2574,7 +2574,10 @@ hipError_t launch_step_fused(const AdmmParams& ap, const PolishParams& pp, size_
 int step_fused_shared(Step& s, const PolishLayout& L) {
     almpc_handle* h = s.h;
     const AdmmParams ap = admm_params(h, s.o, s.keep_state);
-    const PolishParams pp = polish_params(s, L);
+    PolishParams pp = polish_params(s, L);
+    // a step that keeps no warm state hands z, v0 and the signs of y to the finish through LDS (records in the finish's idle wave
+    // buffers and second-tier slot) instead of dZs / dV0 / dYflags; ALMPC_OPT_HBM_HANDOFF keeps the global round trip (A/B control)
+    pp.handoff = (!s.keep_state && L.sg_shared_off >= 0 && !(s.o.reserved[0] & ALMPC_OPT_HBM_HANDOFF)) ? 1 : 0;
     HIP_TRY(h, s.t.mark(1));   // (no boundary between the phases to time: admm_ms reads 0)
     HIP_TRY(h, h->ks == 30 ? launch_step_fused<30>(ap, pp, L.l_step, h->stream) : launch_step_fused<32>(ap, pp, L.l_step, h->stream));
     HIP_TRY(h, s.t.mark(2));

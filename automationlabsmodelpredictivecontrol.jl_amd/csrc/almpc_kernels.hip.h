@@ -160,14 +160,30 @@ struct AdmmParams {
     uint32_t* yflags;
 };
 
+__device__ __forceinline__ void lds_barrier();
+
+// A hand-off record (k_step_fused): what the finish needs of one instance, in the LDS the finish will use for it.  Doubles [0, 128): z,
+// [128, 256): v0, both rotated by handoff_rot(rank) rows (the records of a tile are a multiple of 256 bytes apart: unrotated, the 16
+// columns of a wave's scatter would meet in the same banks); then ints: the sign word of every wave's 16 rows of y, the ADMM status
+// and the instance number (-1: pad column).
+constexpr int HANDOFF_STATUS = 8, HANDOFF_INST = 9;
+__device__ __forceinline__ int handoff_rot(int rank) { return 4 * (rank & 7); }
+
+// How the ADMM phase passes z, v0, the signs of y, the status and the processing order to the finish.  NoHandoff (k_admm): through
+// global memory, for a finish in another kernel.  StepHandoff (k_step_fused, below): the tile's own finish follows in the same
+// workgroup, and on a step that keeps no warm state the records go straight into the finish's idle LDS.
+struct NoHandoff {
+    static constexpr bool possible = false;
+};
+
 // One workgroup = NRB waves = one tile of 16 instances.  Wave w owns rows 16w..16w+15 of every
 // instance vector in the MFMA C/D layout: lane (q = l>>4, col = l&15) holds rows 16w + q + 4i,
 // i = 0..3, of instance col -- so the whole ADMM vector update is register-local and only the
 // right-hand side travels through LDS (double-buffered, one barrier per iteration).
 // `after_requests` runs right after the prologue's own global loads have been requested (the fused step kernel asks for G there:
 // loads return in order, so a stream requested first would hold up e0 and the fragments of the first iteration)
-template <int NRB, int KS, typename AfterRequests>
-__device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, AfterRequests after_requests) {
+template <int NRB, int KS, typename AfterRequests, typename Hand>
+__device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, AfterRequests after_requests, const Hand& hand) {
     constexpr int RP = 16 * NRB;  // padded rows
     static_assert(4 * KS <= RP, "K padding must fit the row padding");
     double* rhs0 = smem;                    // [RP][16]
@@ -431,14 +447,72 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
     // ---- polish order: the polish is bound by its slowest instances, so within every tile the instances are ranked by the
     // size of their active-set guess (a proxy for a long active-set chain): perm[tile*16 + rank] = instance (-1: pad column).
     // The polish hands out rank 0 of every tile first, then rank 1, ...  No global counters or atomics are involved.
-    {
+    auto count_guess = [&]() {
         int cntf = 0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) cntf += (row[i] < p.nz && yt[i] != 0.0) ? 1 : 0;
         cntf += __shfl_xor(cntf, 16);
         cntf += __shfl_xor(cntf, 32);
         if (q == 0) red[(wv * 8 + 0) * TILE + col] = (double)cntf;
+    };
+    auto sign_word = [&]() -> uint32_t {  // AdmmParams::yflags: the signs of this wave's 16 rows of y, in every lane of the column
+        uint32_t mk = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t b = (uint32_t)(q + 4 * i);
+            mk |= (yt[i] < 0.0 ? 1u : 0u) << b;
+            mk |= (yt[i] > 0.0 ? 1u : 0u) << (16u + b);
+        }
+        mk |= (uint32_t)__shfl_xor((int)mk, 16);
+        mk |= (uint32_t)__shfl_xor((int)mk, 32);
+        return mk;
+    };
+    if constexpr (Hand::possible) {
+        if (hand.on) {
+            // ---- LDS hand-off: the finish of this tile runs in this workgroup and nothing else reads z, v0 or the signs of y, so they
+            // go from the registers into the finish's own (idle) buffers, one record per instance, filed by rank -- no staging tile,
+            // no global stores, and the finish starts without a load from global memory.  The finish's workgroup-shared constants are
+            // requested here, so that their latency runs under the rank code, and written beside the records.
+            static_assert(RP == 128, "a hand-off record holds 128 rows of z and of v0");
+            constexpr int TPB = 64 * NRB;
+            const double hc0 = hand.load_const((int)threadIdx.x), hc1 = hand.load_const((int)threadIdx.x + TPB);
+            count_guess();
+            lds_barrier();  // everyone is done reading cur/nxt; red holds the per-wave counts
+            // every wave ranks its lane's column itself (the rule of the global path below): lanes 0..15 hold the 16 keys
+            int k0 = valid ? 0 : -1;
+            if (valid)
+                for (int w2 = 0; w2 < NRB; ++w2) k0 += (int)red[(w2 * 8 + 0) * TILE + col];
+            const int key = k0 * 16 + (15 - col);   // larger guess first, ties by column; unique per column
+            int rank = 0;
+#pragma unroll
+            for (int c2 = 0; c2 < TILE; ++c2) rank += (__builtin_amdgcn_readlane(key, c2) > key) ? 1 : 0;
+            if (wv == 0 && q == 0) p.perm[blockIdx.x * TILE + rank] = valid ? inst : -1;   // (for tools; the finish reads the records)
+            const uint32_t mk = sign_word();
+            ALMPC_STAMP(blockIdx.x * NRB + wv, 3);
+            lds_barrier();  // red and the rhs buffers are dead: the finish's buffers lie over them
+            double* rec = hand.record(rank);
+            const int rot = handoff_rot(rank);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int o = (row[i] + rot) & (RP - 1);
+                rec[o] = z[i];
+                rec[RP + o] = v04[i];
+            }
+            int* ri = reinterpret_cast<int*>(rec + 2 * RP);
+            if (q == 0) ri[wv] = (int)mk;
+            if (wv == 0 && q == 0) { ri[HANDOFF_STATUS] = my_status; ri[HANDOFF_INST] = valid ? inst : -1; }
+            hand.store_const((int)threadIdx.x, hc0);
+            hand.store_const((int)threadIdx.x + TPB, hc1);
+            for (int t = (int)threadIdx.x + 2 * TPB; t < hand.SL.total; t += TPB) hand.store_const(t, hand.load_const(t));
+            if (threadIdx.x == 0) {
+                const int nvalid = p.batch - (int)blockIdx.x * TILE;
+                hand.init_queue(nvalid > NRB ? (nvalid < TILE ? nvalid : TILE) - NRB : 0);
+            }
+            ALMPC_STAMP(blockIdx.x * NRB + wv, 4);
+            return;  // (the caller's barrier publishes the records)
+        }
     }
+    count_guess();
     __syncthreads();  // everyone is done reading cur/nxt; red holds the per-wave counts
     if (wv == 0 && q == 0) {  // lanes 0..15 of wave 0: one instance each
         int k0 = valid ? 0 : -1;  // pad columns sort last
@@ -482,15 +556,7 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
         flush(x, p.xs);
         flush(y, p.ys);
     } else {
-        uint32_t mk = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t b = (uint32_t)(q + 4 * i);
-            mk |= (yt[i] < 0.0 ? 1u : 0u) << b;
-            mk |= (yt[i] > 0.0 ? 1u : 0u) << (16u + b);
-        }
-        mk |= (uint32_t)__shfl_xor((int)mk, 16);
-        mk |= (uint32_t)__shfl_xor((int)mk, 32);
+        const uint32_t mk = sign_word();
         if (q == 0 && valid) p.yflags[(size_t)inst * NRB + wv] = mk;
     }
     flush(z, p.zs);
@@ -501,7 +567,7 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
 template <int NRB, int KS>
 __global__ __launch_bounds__(64 * NRB) void k_admm(AdmmParams p) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    admm_body<NRB, KS>(p, smem, []() {});
+    admm_body<NRB, KS>(p, smem, []() {}, NoHandoff{});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -564,6 +630,8 @@ struct PolishParams {
     int* redo_gate = nullptr; // device word (or null): = step_serial when this step leaves an instance with status != 0 -- what a redo launch
     int step_serial = 0;      // that was enqueued behind the step without a host look tests before it does anything (SdualParams::gate)
     int direct = 0;      // k_step_inst_wave: workgroup (= wave) b finishes instance b itself (no perm lookup)
+    int handoff = 0;     // k_step_fused: the ADMM phase has left the shared constants, the queue words and one record per instance (z, v0,
+                         // signs of y, status, instance number) in this workgroup's LDS; zs, v0, yflags, perm are not read
     int fuse_rollout;    // 1: this kernel also produces u, e_u, x, e_x (roll.*), no separate k_rollout launch; 2: u, e_u only;
                          // 3: as 1 with the blocked rollout (shared model: rollM)
     int roll_g, roll_cpl; // rollout lane decomposition: roll_g lanes per state row, roll_cpl columns of [A B] per lane
@@ -898,6 +966,8 @@ __host__ __device__ inline PolishShared polish_shared_layout(int n, int m, int N
 }
 constexpr int POLISH_GLB_PER_INST = 64 * 64;        // doubles of global scratch per instance
 constexpr int POLISH_SG_SHARED_CAP = 48;            // capacity (positions) of the workgroup-shared second-tier slot in LDS
+constexpr int HANDOFF_REC = POLISH_LDS_MIN_PER_WAVE;  // doubles between the hand-off records kept in that slot (k_step_fused)
+static_assert((TILE - 8) * HANDOFF_REC <= POLISH_SG_SHARED_CAP * 64, "the records of ranks 8..15 must fit the second-tier slot");
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 
@@ -925,7 +995,9 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
     double* cd = shc + SL.off_d;    // d and [A B] as the waves read them: workgroup-shared, or the wave's own copy
     double* cab = shc + SL.off_ab;
     if (per_inst) { cd = wave_lds + p.wave_const_off; cab = cd + nzs; }
-    {
+    bool handed = false;   // (wave-uniform)
+    if constexpr (GLDS && GPRE) handed = p.handoff != 0;
+    if (!handed) {
         constexpr int TPB = 64 * NWV;
         const int n = p.roll.n, m = p.m, N = p.roll.N;
         if (!per_inst)
@@ -965,11 +1037,13 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
     }
     if constexpr (GLDS) {
         qcnt = reinterpret_cast<int*>(shc + SL.total + (size_t)POLISH_WAVES_GLDS * p.lds_per_wave);
-        if (threadIdx.x == 0) { qcnt[0] = POLISH_WAVES_GLDS; qcnt[1] = -1; }  // queue counter | owner of the shared second-tier slot
+        // queue counter | owner of the shared second-tier slot | hand-off records still unread in that slot
+        if (!handed && threadIdx.x == 0) { qcnt[0] = POLISH_WAVES_GLDS; qcnt[1] = -1; qcnt[2] = 0; }
         Gp = smem;
     }
-    __syncthreads();
-  auto process = [&](const int inst) {
+    if (!handed) __syncthreads();
+  // rec: the instance's hand-off record of rank `rank` (LDS), or null: its ADMM results are read from global memory
+  auto process = [&](const int inst, const double* rec, const int rank) {
     // the parameters are re-read from the kernarg segment through a pointer the optimiser cannot see through: otherwise
     // every instance-independent load (bounds, scaling, [A B] coefficients, ~40 pointers) is hoisted out of the queue
     // loop and the kernel spills hundreds of registers
@@ -1002,7 +1076,11 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
             wave_fence_lds();
         }
     }
-    const int st_in = GL(p.status)[inst];
+    bool from_rec = false;   // (wave-uniform)
+    if constexpr (GLDS && GPRE) from_rec = rec != nullptr;
+    int st_in;
+    if (from_rec) st_in = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(rec + 256)[HANDOFF_STATUS]);
+    else st_in = GL(p.status)[inst];
     const size_t base = (size_t)inst * nzs;
     // row-distributed vectors: lane l owns the two consecutive rows 2l, 2l+1 (one 16-byte access per vector)
     const int r0 = 2 * lane, r1 = 2 * lane + 1;
@@ -1033,8 +1111,23 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
     if (p.fuse_rollout && lane < p.roll.n) x0r = GL(p.roll.x0)[(size_t)inst * p.roll.n + lane];
     {
         const d2 dv = *reinterpret_cast<const d2*>(cd + rc);
-        const d2 vv = *reinterpret_cast<const d2*>(GL(p.v0) + base + rc);
-        d2 yy;
+        d2 vv, yy, zz;
+        if (from_rec) {
+            // the record sits in this wave's own buffers (first pick) or in the second-tier slot: into registers before either is reused
+            const int o = (rc + handoff_rot(rank)) & 127;
+            zz = *reinterpret_cast<const d2*>(rec + o);
+            vv = *reinterpret_cast<const d2*>(rec + 128 + o);
+            uint32_t wd = (uint32_t)reinterpret_cast<const int*>(rec + 256)[rc >> 4];
+            asm volatile("" : "+v"(zz), "+v"(vv), "+v"(wd));   // (two code paths, not a select of an LDS and a global address)
+            const uint32_t b = (uint32_t)(rc & 15);
+            yy[0] = (double)(int)((wd >> (16u + b)) & 1u) - (double)(int)((wd >> b) & 1u);
+            yy[1] = (double)(int)((wd >> (17u + b)) & 1u) - (double)(int)((wd >> (b + 1u)) & 1u);
+            if (rank >= POLISH_WAVES_GLDS) {   // a record in the second-tier slot has been picked up
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                if (lane == 0) atomicSub(qcnt + 2, 1);
+            }
+        } else {
+        vv = *reinterpret_cast<const d2*>(GL(p.v0) + base + rc);
         if (p.yflags) {  // only the signs of y are needed (the guess below): +-1 / 0 from the flag word of this row pair
             const uint32_t wd = GL(p.yflags)[(size_t)inst * p.yflag_words + (rc >> 4)];
             const uint32_t b = (uint32_t)(rc & 15);
@@ -1043,7 +1136,8 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
         } else {
             yy = *reinterpret_cast<const d2*>(GL(p.ys) + base + rc);
         }
-        const d2 zz = *reinterpret_cast<const d2*>(GL(p.zs) + base + rc);
+        zz = *reinterpret_cast<const d2*>(GL(p.zs) + base + rc);
+        }
         v00 = vv[0]; v01 = vv[1]; y0 = yy[0]; y1 = yy[1]; z0 = zz[0]; z1 = zz[1];
         // bounds exactly as k_admm forms them ((umin - uref) * (1/d)): its z sits ON these values when active
         // (references: LDS copy of a shared one, or global per instance.  Two code paths kept apart by an empty asm: a select of the
@@ -1444,7 +1538,9 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
         if constexpr (GLDS) {
             if (p.sg_shared_off >= 0 && need <= POLISH_SG_SHARED_CAP) {
                 int got = 0;
-                if (lane == 0) got = (atomicCAS(qcnt + 1, -1, wv) == -1) ? 1 : 0;
+                // (not while hand-off records wait in the slot: the wave then takes the global scratch, as when the slot is taken)
+                if (lane == 0)
+                    got = (__hip_atomic_load(qcnt + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0 && atomicCAS(qcnt + 1, -1, wv) == -1) ? 1 : 0;
                 got = __builtin_amdgcn_readfirstlane(got);
                 if (got) { own_slot = true; cap2 = POLISH_SG_SHARED_CAP; Sg = shc + p.sg_shared_off; }
             }
@@ -1843,9 +1939,19 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
         for (int i = wv;;) {
             const int tile = (i >> 4) * (int)gridDim.x + (int)blockIdx.x;
             if (tile >= p.ntiles) break;
-            const int inst = p.perm[tile * 16 + (i & 15)];
+            int inst;
+            const double* rec = nullptr;
+            if (handed) {
+                // this workgroup's own tile: rank i < 8 is wave i's first pick and waits in its own buffers, a later pick in the
+                // second-tier slot; the valid instances have the first ranks
+                if (i >= p.batch - (int)blockIdx.x * TILE) break;
+                rec = i < POLISH_WAVES_GLDS ? wave_lds : shc + p.sg_shared_off + (size_t)(i - POLISH_WAVES_GLDS) * HANDOFF_REC;
+                inst = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(rec + 256)[HANDOFF_INST]);
+            } else {
+                inst = p.perm[tile * 16 + (i & 15)];
+            }
             if (inst >= 0) {
-                process(inst);
+                process(inst, rec, i);
                 ++nproc;
             }
             if (lane_k == 0) i = atomicAdd(qcnt, 1);
@@ -1859,10 +1965,10 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
         // slot s -> (tile s % ntiles, rank s / ntiles): the dispatch order starts with the hardest instance of every tile
         const int slot = blockIdx.x * NWV + wv;
         if (p.direct) {
-            if (slot < p.batch) process(slot);
+            if (slot < p.batch) process(slot, nullptr, 0);
         } else if (slot < p.ntiles * 16) {
             const int inst = p.perm[(slot % p.ntiles) * 16 + slot / p.ntiles];
-            if (inst >= 0) process(inst);
+            if (inst >= 0) process(inst, nullptr, 0);
         }
     }
 }
@@ -1893,6 +1999,38 @@ __global__ __launch_bounds__(64) void k_polish_sgl(PolishParams p_arg) {
 // ------------------------------------------------------------------------------------------------
 constexpr int STEP_KOFF = (int)((sizeof(AdmmParams) + 7) & ~size_t(7));  // PolishParams follows AdmmParams in the kernarg segment
 
+// The ADMM phase's side of the LDS hand-off (admm_body; the layout of a record: handoff_rot).  Ranks 0..7 go into the buffers of the
+// waves 0..7 -- wave w takes rank w first --, ranks 8..15 into the workgroup-shared second-tier slot, which no wave may claim before
+// they have been picked up (the third queue word counts them).  All of this is idle LDS of the finish: nothing is added.
+struct StepHandoff {
+    static constexpr bool possible = true;
+    const PolishParams& pp;
+    double* shc;         // the finish's workgroup-shared constants: the start of the union
+    PolishShared SL;
+    bool on;
+    __device__ __forceinline__ double* record(int rank) const {
+        return rank < POLISH_WAVES_GLDS ? shc + SL.total + (size_t)rank * pp.lds_per_wave
+                                        : shc + pp.sg_shared_off + (size_t)(rank - POLISH_WAVES_GLDS) * HANDOFF_REC;
+    }
+    // entry t of the shared constants as polish_body fills them (shared model; 0 beyond them and where the finish reads global memory)
+    __device__ __forceinline__ double load_const(int t) const {
+        const int n = pp.roll.n, nx = (pp.roll.N + 1) * n;
+        double v = 0.0;
+        if (t < SL.off_umin) v = GL(pp.dvec)[t];
+        else if (t < SL.off_umax) v = GL(pp.umin)[t - SL.off_umin];
+        else if (t < SL.off_uref) v = GL(pp.umax)[t - SL.off_umax];
+        else if (t < SL.off_ab) { if (pp.uref_stride == 0) v = GL(pp.uref)[t - SL.off_uref]; }
+        else if (t < SL.off_xref) { const int u = t - SL.off_ab; v = u < n * n ? GL(pp.roll.A)[u] : GL(pp.roll.B)[u - n * n]; }
+        else if (pp.fuse_rollout && pp.roll.xref_stride == 0 && t < SL.off_xref + nx) v = GL(pp.roll.xref)[t - SL.off_xref];
+        return v;
+    }
+    __device__ __forceinline__ void store_const(int t, double v) const { if (t < SL.total) shc[t] = v; }
+    __device__ __forceinline__ void init_queue(int staged) const {
+        int* qcnt = reinterpret_cast<int*>(shc + SL.total + (size_t)POLISH_WAVES_GLDS * pp.lds_per_wave);
+        qcnt[0] = POLISH_WAVES_GLDS; qcnt[1] = -1; qcnt[2] = staged;
+    }
+};
+
 template <int NRB, int KS>
 __global__ __launch_bounds__(64 * NRB) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_step_fused(AdmmParams ap, PolishParams pp) {
@@ -1909,8 +2047,10 @@ void k_step_fused(AdmmParams ap, PolishParams pp) {
             }
         }
     };
-    admm_body<NRB, KS>(ap, smem + (size_t)pp.nz * gs, request_g);
-    __builtin_amdgcn_s_waitcnt(0);  // this wave's pieces of G have landed
+    double* un = smem + (size_t)pp.nz * gs;   // union(ADMM buffers, finish buffers)
+    const StepHandoff hand{pp, un, polish_shared_layout(pp.roll.n, pp.m, pp.roll.N, pp.nz, pp.nzs, pp.fuse_rollout), pp.handoff != 0};
+    admm_body<NRB, KS>(ap, un, request_g, hand);
+    __builtin_amdgcn_s_waitcnt(0);  // this wave's pieces of G have landed (with the hand-off no store is outstanding: a short wait)
     __syncthreads();                // ... and everybody's; the ADMM results of the tile are visible to the whole workgroup
     polish_body<true, true, STEP_KOFF>(pp, smem);
 }

@@ -95,6 +95,12 @@ typedef struct almpc_opts {
  * (almpc_set_reference with per_instance = 1), warm starts, per-instance models, and shapes whose design workspace has no room for wS
  * behind W (fewer than n + 9 rows of n * N rounded up to 32: N = 1 with large n) always take the full product; the bit is ignored there. */
 #define ALMPC_OPT_FULL_FIRST_PRODUCT 0x2
+/* A/B control of the one-kernel step's hand-off.  A shared-model step that runs as one kernel and keeps no warm state
+ * (ALMPC_OPT_NO_WARM_STATE) passes the ADMM results (z, v0, the signs of y, the status, the processing order) to its finish through
+ * the workgroup's LDS.  With this bit they make the round trip through global memory that every other step makes: the same
+ * arithmetic on the same values, identical results.  Ignored by steps that keep the warm state, by the two-kernel path, by
+ * per-instance models and by shapes without the finish's shared second-tier slot in LDS. */
+#define ALMPC_OPT_HBM_HANDOFF 0x4
 
 void almpc_default_opts(almpc_opts* opts);
 

@@ -48,6 +48,11 @@ Base.@kwdef struct AlmpcOpts         # mirrors `almpc_opts` (72 bytes)
     reserved::NTuple{3,Int32} = (0, 0, 0)
 end
 
+# flag bits of opts.reserved[1] (C: opts.reserved[0]; include/almpc.h: ALMPC_OPT_*), e.g. reserved = (ALMPC_OPT_NO_WARM_STATE, 0, 0)
+const ALMPC_OPT_NO_WARM_STATE = Int32(0x1)       # the step keeps no ADMM state for a warm start of the next one
+const ALMPC_OPT_FULL_FIRST_PRODUCT = Int32(0x2)  # A/B control: the cold start's first ADMM iterate as a full product
+const ALMPC_OPT_HBM_HANDOFF = Int32(0x4)         # A/B control: the one-kernel step hands its ADMM results on through global memory
+
 mutable struct HipModeler            # what sits in tuning.modeler (`modeler::Any`, src/types/types.jl:115)
     handle::Ptr{Cvoid}
     n::Int; m::Int; N::Int; batch::Int

@@ -16,7 +16,12 @@ prof = os.environ.get('ALMPC_RHO_PROFILE', 'scalar'); rho = float(os.environ.get
 s.design_shared(p.A, p.B, p.Q, p.R, p.S, None, p.u_min, p.u_max, rho=rho, rho_profile=prof)
 s.set_reference(p.x_ref, p.u_ref)
 s.update_initialization(X0)
-opts = capi.default_opts(rho=rho) if len(sys.argv) <= 3 else capi.default_opts(rho=rho, max_iter=int(sys.argv[3]), check_every=int(sys.argv[4]) if len(sys.argv) > 4 else 25)
+# ALMPC_NO_WARM_STATE=1: the benchmark's cold-start-every-step options (ALMPC_OPT_NO_WARM_STATE); ALMPC_HBM_HANDOFF=1: with the one-kernel
+# step's hand-off through global memory (ALMPC_OPT_HBM_HANDOFF)
+kw = dict(rho=rho, keep_warm_state=os.environ.get("ALMPC_NO_WARM_STATE") != "1")
+opts = capi.default_opts(**kw) if len(sys.argv) <= 3 else capi.default_opts(max_iter=int(sys.argv[3]), check_every=int(sys.argv[4]) if len(sys.argv) > 4 else 25, **kw)
+if os.environ.get("ALMPC_HBM_HANDOFF") == "1":
+    opts.reserved[0] |= capi.OPT_HBM_HANDOFF
 for _ in range(5):
     s.calculate(opts)
 s.timing_reset(steps)

@@ -10,7 +10,12 @@ p = mo.quadrotor(); B = 4096
 X0 = bench.make_x0(mo, 0, B, None if amp == "mix" else float(amp))
 prof = os.environ.get('ALMPC_RHO_PROFILE', 'scalar'); rho = float(os.environ.get('ALMPC_RHO', '0.1'))
 s = capi.Solver(12, 4, 30, B); s.design_shared(p.A, p.B, p.Q, p.R, p.S, None, p.u_min, p.u_max, rho=rho, rho_profile=prof); s.set_reference(p.x_ref, p.u_ref); s.update_initialization(X0)
-opts = capi.default_opts(rho=rho, max_iter=int(sys.argv[2]) if len(sys.argv) > 2 else 25, check_every=int(sys.argv[2]) if len(sys.argv) > 2 else 25)
+# ALMPC_NO_WARM_STATE=1: the benchmark's cold-start-every-step options (ALMPC_OPT_NO_WARM_STATE); ALMPC_HBM_HANDOFF=1: with the one-kernel
+# step's hand-off through global memory (ALMPC_OPT_HBM_HANDOFF)
+opts = capi.default_opts(rho=rho, max_iter=int(sys.argv[2]) if len(sys.argv) > 2 else 25, check_every=int(sys.argv[2]) if len(sys.argv) > 2 else 25,
+                         keep_warm_state=os.environ.get("ALMPC_NO_WARM_STATE") != "1")
+if os.environ.get("ALMPC_HBM_HANDOFF") == "1":
+    opts.reserved[0] |= capi.OPT_HBM_HANDOFF
 for _ in range(3): s.calculate(opts)
 L = s.L; W = 3 * B
 L.almpc_dbg_stamps_enable(s.h, W)
@@ -59,6 +64,15 @@ print("slowest instances: inst, total, per-phase cycles, polish its, adds counte
 for o in order:
     i = okidx[o]
     print("  ", i, int(tot[o]), d[o].tolist(), int(pit[i]), int(acc[i, 8]), "acc", (acc[i, :6]).tolist())
+
+# the glue between the phases, per tile: the ADMM epilogue (3 -> 4), the last ADMM stamp of the tile -> the first finish stamp of one of
+# its instances, an instance's start (8 -> 9), and the tile from its first ADMM stamp to its last finish stamp
+ta = full[:B // 16 * 8].reshape(B // 16, 8, 16); tf = full[:B].reshape(B // 16, 16, 16)
+if (ta[:, :, 4] > 0).all() and (tf[:, :, 8] > 0).all():
+    glue = tf[:, :, 8].min(axis=1) - ta[:, :, 4].max(axis=1); span = tf[:, :, 14].max(axis=1) - ta[:, :, 0].min(axis=1)
+    print("phase change per tile (cycles): ADMM 3->4 median", int(np.median(ta[:, :, 4] - ta[:, :, 3])), " last ADMM stamp -> first finish stamp median",
+          int(np.median(glue)), "max", int(glue.max()), " finish 8->9 median", int(np.median(tf[:, :, 9] - tf[:, :, 8])),
+          " first ADMM stamp -> last finish stamp: median tile", int(np.median(span)), "slowest tile", int(span.max()))
 
 tl = full[8192:8192 + 2048]
 okw = tl[:, 0] > 0
