@@ -328,6 +328,13 @@ int fail(almpc_handle* h, int code, const std::string& msg) {
             return fail(h, ALMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
     } while (0)
 
+// ... and of the library's own calls: anything but ALMPC_OK is the caller's return value (the message is in h->err already)
+#define ALMPC_TRY(expr)                        \
+    do {                                       \
+        const int rc_try_ = (expr);            \
+        if (rc_try_ != ALMPC_OK) return rc_try_; \
+    } while (0)
+
 int pick_ks(int nz, int nrb) {
     const int exact = (nz + 3) / 4;
     // instantiated (NRB, KS) pairs: KS = 4*NRB always; plus the exact-fit specials below
@@ -457,11 +464,7 @@ hipError_t launch_ghat_inst(almpc_handle* h, const double* A_all, const double* 
 // Device copies of the weights the structured solve uses (R with the reference's branch rule applied: zero if R[1,1] == 0)
 int riccati_weights(almpc_handle* h, const hm::mat& Qm, const hm::mat& Rm, const double* Pshared) {
     const int n = h->n, m = h->m;
-    hm::mat Qs = Qm, Rs = Rm;
-    for (int j = 0; j < n; ++j)
-        for (int i = 0; i < j; ++i) { const double v = 0.5 * (Qs[(size_t)j * n + i] + Qs[(size_t)i * n + j]); Qs[(size_t)j * n + i] = Qs[(size_t)i * n + j] = v; }
-    for (int j = 0; j < m; ++j)
-        for (int i = 0; i < j; ++i) { const double v = 0.5 * (Rs[(size_t)j * m + i] + Rs[(size_t)i * m + j]); Rs[(size_t)j * m + i] = Rs[(size_t)i * m + j] = v; }
+    hm::mat Qs = hm::symmetrised(Qm.data(), n), Rs = hm::symmetrised(Rm.data(), m);
     if (Rm[0] == 0.0) std::fill(Rs.begin(), Rs.end(), 0.0);
     HIP_TRY(h, h->rQ.once((size_t)n * n));
     HIP_TRY(h, h->rR.once((size_t)m * m));
@@ -746,7 +749,7 @@ int design_dare_device(almpc_handle* h, const double* dQ, const double* dR, cons
     const int n = h->n, m = h->m;
     const size_t b = (size_t)h->batch;
     const char* why = "";
-    { const int rc_ = dare_device_check(n, m, Rm, true, &why); if (rc_ != ALMPC_OK) return fail(h, rc_, std::string("design_batched: ") + why); }
+    if (const int bad = dare_device_check(n, m, Rm, true, &why)) return fail(h, bad, std::string("design_batched: ") + why);
     HIP_TRY(h, h->tStat.once(b));
     DareParams dp;
     dp.n = n; dp.m = m; dp.batch = h->batch;
@@ -768,7 +771,7 @@ int relin_terminal_setup(almpc_handle* h, const hm::mat& Rm, const hm::mat& Pm) 
     h->t_step = false;
     if (h->terminal_mode != ALMPC_TERMINAL_DARE_DEVICE) return ALMPC_OK;
     const char* why = "";
-    { const int rc_ = dare_device_check(h->n, h->m, Rm, true, &why); if (rc_ != ALMPC_OK) return fail(h, rc_, std::string("relin_fnn_setup: ") + why); }
+    if (const int bad = dare_device_check(h->n, h->m, Rm, true, &why)) return fail(h, bad, std::string("relin_fnn_setup: ") + why);
     HIP_TRY(h, h->tP.upload(Pm.data(), Pm.size()));
     HIP_TRY(h, h->tStat.once((size_t)h->batch));
     HIP_TRY(h, hipMemset(h->tStat, 0, (size_t)h->batch * sizeof(int32_t)));
@@ -838,7 +841,7 @@ int design_c2d_device(almpc_handle* h) {
 int relin_c2d_setup(almpc_handle* h) {
     h->c_step = false;
     if (!model_continuous(h)) return ALMPC_OK;
-    { const int rc_ = c2d_shape_check(h, "relin_fnn_setup"); if (rc_ != ALMPC_OK) return rc_; }
+    ALMPC_TRY(c2d_shape_check(h, "relin_fnn_setup"));
     HIP_TRY(h, h->cStat.once((size_t)h->batch));
     HIP_TRY(h, hipMemset(h->cStat, 0, (size_t)h->batch * sizeof(int32_t)));
     h->c_step = true;
@@ -986,7 +989,8 @@ hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int ma
     sp.umin = h->dUmin; sp.umax = h->dUmax; sp.uref = h->dUref; sp.uref_stride = h->uref_stride;
     sp.xmin = sd.has_box ? sd.xmin : nullptr; sp.xmax = sd.has_box ? sd.xmax : nullptr;
     sp.xbref = h->dXref; sp.xbref_stride = h->xref_stride;
-    sp.eqt = sd.has_eq ? h->dXref + (size_t)h->N * h->n : nullptr; sp.eqt_stride = h->xref_stride;   // x_N = x_ref_N
+    // x_N = x_ref_N (no references yet: the design-time build of the cached responses, which sets its own below)
+    sp.eqt = sd.has_eq && h->dXref ? h->dXref + (size_t)h->N * h->n : nullptr; sp.eqt_stride = h->xref_stride;
     sp.x0 = h->dX0; sp.x0_stride = h->n; sp.xref = h->dXref; sp.xref_stride = h->xref_stride;
     if (mode.x0_from_results) { sp.x0 = h->dX; sp.x0_stride = (long)h->n * (h->N + 1); }
     if (mode.gated) { sp.gate = h->redo.dGate; sp.gate_val = h->redo.step_serial; }
@@ -1209,6 +1213,113 @@ int build_s0_basis(almpc_handle* h) {
     return ALMPC_OK;
 }
 
+// ---- building blocks of the design and setup entry points (almpc_design_*, almpc_relin_*_setup, almpc_sqp_*_setup) -----------------
+
+// The state box of almpc_set_state_box (both null: none)
+struct StateBox { const double *min = nullptr, *max = nullptr; };
+StateBox state_box(const almpc_handle* h) {
+    StateBox box;
+    if (!h->boxmin.empty()) { box.min = h->boxmin.data(); box.max = h->boxmax.data(); }
+    return box;
+}
+
+// The input box of a design: checked among the arguments (who: the call's name in the message), uploaded behind the first device calls
+int check_input_box(almpc_handle* h, const double* umin, const double* umax, const char* who) {
+    for (int i = 0; i < h->m; ++i)
+        if (!(umin[i] <= umax[i])) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": umin > umax");
+    return ALMPC_OK;
+}
+int upload_input_box(almpc_handle* h, const double* umin, const double* umax) {
+    const int m = h->m;
+    HIP_TRY(h, hipMemcpy(h->dUmin, umin, m * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->dUmax, umax, m * sizeof(double), hipMemcpyHostToDevice));
+    return ALMPC_OK;
+}
+
+// The head of a design or setup call: from here on the handle's previous design is being overwritten (designed again only with the
+// call's last statement), with it -- where the caller says so -- an SQP loop and a re-linearisation pipeline set up on the handle;
+// WAIT_STREAM: and the handle's stream is idle
+enum : unsigned { DROP_SQP = 1u, DROP_RELIN = 2u, WAIT_STREAM = 4u };
+int begin_redesign(almpc_handle* h, unsigned what) {
+    h->designed = false;
+    if (what & DROP_SQP) h->sqp.ready = h->sqp.started = false;
+    if (what & DROP_RELIN) h->relin.ready = false;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (what & WAIT_STREAM) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return ALMPC_OK;
+}
+
+// Terminal weights of a per-instance design, into Pall: the caller's (one matrix, or one per instance), else -- unless k_dare makes
+// them behind the uploads (dev_dare: Pall stays empty) -- the DARE solution of every instance's model (src/sub/design_mpc.jl:327)
+int terminal_weights(almpc_handle* h, const double* A_batch, const double* B_batch, const hm::mat& Qm, const hm::mat& Rm, const double* P,
+                     int P_per_instance, bool dev_dare, const char* who, hm::mat& Pall) {
+    const size_t n = (size_t)h->n, m = (size_t)h->m, b = (size_t)h->batch;
+    if (P) Pall.assign(P, P + (P_per_instance ? b : 1) * n * n);
+    else if (!dev_dare) {
+        Pall.resize(b * n * n);
+        for (size_t i = 0; i < b; ++i) {
+            hm::mat Am(A_batch + i * n * n, A_batch + (i + 1) * n * n), Bm(B_batch + i * n * m, B_batch + (i + 1) * n * m), Pm;
+            const char* what = "";
+            if (!host_dare_of(h, Am, Bm, Qm, Rm, Pm, &what)) return fail(h, ALMPC_ERR_NUMERIC, std::string(who) + ": " + what + " for instance " + std::to_string(i));
+            std::copy(Pm.begin(), Pm.end(), Pall.begin() + i * n * n);
+        }
+    }
+    return ALMPC_OK;
+}
+
+// k_sdual's set-up from a shared model with its terminal weight (stage records by the host, at design time) or -- null -- for the
+// handle's per-instance model slots (records by k_sgains; one_stage: the terminal weight is the instance's own DARE solution)
+struct SharedModel { const hm::mat &A, &B, &P; };
+int setup_sdual(almpc_handle* h, const SharedModel* shared, bool one_stage, const hm::mat& Qm, const hm::mat& Rm, const hm::mat* Sm, StateBox box) {
+    if (!shared) return sdual_setup_batched(h, Qm, Rm, Sm, one_stage, box.min, box.max, h->terminal_eq != 0);
+    hm::mat Rb = Rm;   // the reference's branch rule (src/sub/design_mpc.jl:423-466): R enters only with a non-zero [1,1] element
+    if (Rm[0] == 0.0) std::fill(Rb.begin(), Rb.end(), 0.0);
+    return sdual_setup_shared(h, shared->A, shared->B, Qm, Rb, Sm, shared->P, box.min, box.max, h->terminal_eq != 0);
+}
+
+bool primal_redo_covers(const almpc_handle* h, bool rows, bool useS) { return riccati_shape_ok(h) && !rows && !useS; }
+
+// The redo of the instances a condensed step leaves without a certificate, and the stage-wise QP of an SQP iteration: the stage-wise
+// dual active set (k_sdual: also state rows and the input-rate weight, Sm non-null) and behind it -- input box only, no S -- the primal
+// Riccati active set.  must: a solver that cannot be set up is the call's error (refusal: the text for a shape outside k_sdual), else
+// the design goes on without it.  h->sd.ready says afterwards whether k_sdual is set up; what follows from that is the caller's.
+int setup_redo_solvers(almpc_handle* h, const SharedModel* shared, bool one_stage, const hm::mat& Qm, const hm::mat& Rm, const hm::mat* Sm,
+                       StateBox box, bool must, const char* refusal) {
+    const bool useS = Sm != nullptr, rows = box.min || h->terminal_eq;
+    h->sd.ready = false;
+    if (sdual_shape_ok(h->n, h->m, h->N, useS)) {
+        const int rc = setup_sdual(h, shared, one_stage, Qm, Rm, Sm, box);
+        if (rc != ALMPC_OK && must) return rc;
+    } else if (must && (rows || useS))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, refusal);
+    if (primal_redo_covers(h, rows, useS)) ALMPC_TRY(riccati_weights(h, Qm, Rm, shared ? shared->P.data() : nullptr));
+    return ALMPC_OK;
+}
+
+// The solvers of a design on an ALMPC_FLAG_STRUCTURED handle, which has no others: k_sdual (input box, state box, terminal equality,
+// input-rate weight) and the primal k_riccati (input box only) -- the solver of shapes k_sdual does not cover and the safety net for
+// instances the dual method leaves without a certificate (a saturated open-loop unstable plant: Ghat_WW numerically singular)
+int setup_structured_solvers(almpc_handle* h, const SharedModel* shared, bool one_stage, const hm::mat& Qm, const hm::mat& Rm, const hm::mat* Sm,
+                             StateBox box) {
+    const bool useS = Sm != nullptr;
+    h->sd.ready = false;
+    if (sdual_shape_ok(h->n, h->m, h->N, useS) && !h->sw.structured_primal)
+        ALMPC_TRY(setup_sdual(h, shared, one_stage, Qm, Rm, Sm, box));
+    else if (box.min || h->terminal_eq || useS)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "structured solve: state rows / input-rate weight need the stage-wise dual solve (n + m <= 48, (N + 1)(n + m) <= 4096)");
+    if (riccati_shape_ok(h)) ALMPC_TRY(riccati_weights(h, Qm, Rm, shared ? shared->P.data() : nullptr));
+    else if (!h->sd.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, "structured solve: shape outside both stage-wise solvers");
+    return ALMPC_OK;
+}
+
+// The tail of a design: default references (zeros, shared).  A design whose references cannot be set is not left "designed".
+int set_zero_reference(almpc_handle* h) {
+    std::vector<double> xr((size_t)h->n * (h->N + 1), 0.0), ur((size_t)h->nz, 0.0);
+    const int rc = almpc_set_reference(h, xr.data(), ur.data(), 0);
+    if (rc != ALMPC_OK) h->designed = false;
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1380,106 +1491,117 @@ int almpc_set_start_from(almpc_handle* h, almpc_handle* src) {
     return ALMPC_OK;
 }
 
-static int design_shared_discrete(almpc_handle* h, const double* A, const double* B, const double* Q, const double* R,
-                                  const double* S, const double* P, const double* umin, const double* umax,
-                                  const double* xmin, const double* xmax, double rho, double sigma);
-
-int almpc_design_shared(almpc_handle* h, const double* A, const double* B, const double* Q, const double* R,
-                        const double* S, const double* P, const double* umin, const double* umax,
-                        const double* xmin, const double* xmax, double rho, double sigma) {
-    if (!h) return ALMPC_ERR_INVALID;
-    if (A && B && model_continuous(h)) {
-        // almpc_set_model_time: (A, B) is continuous-time; its zero-order hold is the model the handle is designed on and keeps
-        // (src/sub/design_mpc.jl:22-41: discretise, then the discrete method)
-        const int n = h->n, m = h->m;
-        hm::mat Ad, Bd;
-        if (hm::c2d(hm::mat(A, A + (size_t)n * n), hm::mat(B, B + (size_t)n * m), h->model_Ts, n, m, Ad, Bd) != 0) {
-            h->designed = false;
-            return fail(h, ALMPC_ERR_NUMERIC, "design: discretisation of the continuous-time model failed (not finite, or |A| Ts beyond 2^59)");
-        }
-        return design_shared_discrete(h, Ad.data(), Bd.data(), Q, R, S, P, umin, umax, xmin, xmax, rho, sigma);
-    }
-    return design_shared_discrete(h, A, B, Q, R, S, P, umin, umax, xmin, xmax, rho, sigma);
+// ALMPC_FLAG_STRUCTURED: no condensed matrices at all; rho / sigma are not used
+static int design_shared_structured(almpc_handle* h, const double* A, const double* B, const double* Q, const double* R, const double* S,
+                                    const double* P, const double* umin, const double* umax, const double* xmin, const double* xmax) {
+    const int n = h->n, m = h->m;
+    if ((xmin == nullptr) != (xmax == nullptr)) return fail(h, ALMPC_ERR_INVALID, "design: give both xmin and xmax or neither");
+    ALMPC_TRY(check_input_box(h, umin, umax, "design"));
+    if (xmin)
+        for (int i = 0; i < n; ++i)
+            if (!(xmin[i] <= xmax[i])) return fail(h, ALMPC_ERR_INVALID, "design: xmin > xmax");
+    h->r_has_step = false; h->guess_ready = false;
+    ALMPC_TRY(begin_redesign(h, DROP_SQP));   // (an SQP loop set up on this handle is gone with its per-instance reference buffers)
+    hm::mat Am(A, A + (size_t)n * n), Bm(B, B + (size_t)n * m), Qm(Q, Q + (size_t)n * n), Rm(R, R + (size_t)m * m), Pm;
+    if (P) Pm.assign(P, P + (size_t)n * n);
+    else if (!hm::dare(Am, Bm, Qm, Rm, n, m, Pm)) return fail(h, ALMPC_ERR_NUMERIC, "design: DARE did not converge");
+    h->P = Pm; h->H.clear(); h->F.clear(); h->d.clear();
+    // the reference's branch rules (src/sub/design_mpc.jl:423-466): R and S enter only with a non-zero [1,1] element, S only with R
+    const bool useS = R[0] != 0.0 && S && S[0] != 0.0;
+    hm::mat Sm;
+    if (useS) Sm.assign(S, S + (size_t)m * m);
+    const SharedModel model{Am, Bm, Pm};
+    ALMPC_TRY(setup_structured_solvers(h, &model, false, Qm, Rm, useS ? &Sm : nullptr, StateBox{xmin, xmax}));
+    ALMPC_TRY(upload_input_box(h, umin, umax));
+    HIP_TRY(h, hipMemcpy(h->dA, A, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->dB, B, (size_t)n * m * sizeof(double), hipMemcpyHostToDevice));
+    h->batched = false; h->ltv = false; h->r_batched_P = false; h->rP_stride = 0;
+    h->hS.assign((size_t)m * m, 0.0); h->useS = useS ? 1 : 0;
+    if (useS) h->hS = Sm;
+    h->has_box = xmin ? 1 : 0;
+    h->designed = true;
+    return set_zero_reference(h);
 }
 
-static int design_shared_discrete(almpc_handle* h, const double* A, const double* B, const double* Q, const double* R,
-                                  const double* S, const double* P, const double* umin, const double* umax,
-                                  const double* xmin, const double* xmax, double rho, double sigma) {
-    drop_lazy_redo(h);
-    if (!A || !B || !Q || !R || !umin || !umax) return fail(h, ALMPC_ERR_INVALID, "design: null matrix pointer");
-    if (h->structured) {   // ALMPC_FLAG_STRUCTURED: no condensed matrices at all; rho / sigma are not used
-        const int n = h->n, m = h->m, N = h->N;
-        if ((xmin == nullptr) != (xmax == nullptr)) return fail(h, ALMPC_ERR_INVALID, "design: give both xmin and xmax or neither");
-        for (int i = 0; i < m; ++i)
-            if (!(umin[i] <= umax[i])) return fail(h, ALMPC_ERR_INVALID, "design: umin > umax");
-        if (xmin)
-            for (int i = 0; i < n; ++i)
-                if (!(xmin[i] <= xmax[i])) return fail(h, ALMPC_ERR_INVALID, "design: xmin > xmax");
-        h->designed = false;
-        h->r_has_step = false; h->guess_ready = false;
-        h->sqp.ready = h->sqp.started = false;   // (an SQP loop set up on this handle is gone with its per-instance reference buffers)
-        HIP_TRY(h, hipSetDevice(h->device));
-        hm::mat Am(A, A + (size_t)n * n), Bm(B, B + (size_t)n * m), Qm(Q, Q + (size_t)n * n), Rm(R, R + (size_t)m * m), Pm;
-        if (P) Pm.assign(P, P + (size_t)n * n);
-        else if (!hm::dare(Am, Bm, Qm, Rm, n, m, Pm)) return fail(h, ALMPC_ERR_NUMERIC, "design: DARE did not converge");
-        h->P = Pm; h->H.clear(); h->F.clear(); h->d.clear();
-        // the reference's branch rules (src/sub/design_mpc.jl:423-466): R and S enter only with a non-zero [1,1] element, S only with R
-        const bool useS = R[0] != 0.0 && S && S[0] != 0.0;
-        hm::mat Rb = Rm, Sm;
-        if (Rm[0] == 0.0) std::fill(Rb.begin(), Rb.end(), 0.0);
-        if (useS) Sm.assign(S, S + (size_t)m * m);
-        h->sd.ready = false;
-        if (sdual_shape_ok(n, m, N, useS) && !h->sw.structured_primal) {
-            // the stage-wise dual active set (k_sdual): input box, state box, terminal equality, input-rate weight
-            const int rc_ = sdual_setup_shared(h, Am, Bm, Qm, Rb, useS ? &Sm : nullptr, Pm, xmin, xmax, h->terminal_eq != 0);
-            if (rc_ != ALMPC_OK) return rc_;
-        } else if (xmin || h->terminal_eq || useS)
-            return fail(h, ALMPC_ERR_UNSUPPORTED, "structured solve: state rows / input-rate weight need the stage-wise dual solve (n + m <= 48, (N + 1)(n + m) <= 4096)");
-        // the primal Riccati active set (k_riccati, input box only): the solver of shapes k_sdual does not cover and the safety net for
-        // instances the dual method leaves without a certificate (a saturated open-loop unstable plant: Ghat_WW numerically singular)
-        if (riccati_shape_ok(h)) { const int rc_ = riccati_weights(h, Qm, Rm, Pm.data()); if (rc_ != ALMPC_OK) return rc_; }
-        else if (!h->sd.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, "structured solve: shape outside both stage-wise solvers");
-        HIP_TRY(h, hipMemcpy(h->dUmin, umin, m * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(h->dUmax, umax, m * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(h->dA, A, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(h->dB, B, (size_t)n * m * sizeof(double), hipMemcpyHostToDevice));
-        h->batched = false; h->ltv = false; h->r_batched_P = false; h->rP_stride = 0;
-        h->hS.assign((size_t)m * m, 0.0); h->useS = useS ? 1 : 0;
-        if (useS) h->hS = Sm;
-        h->has_box = xmin ? 1 : 0;
-        h->designed = true;
-        std::vector<double> xr((size_t)n * (N + 1), 0.0), ur((size_t)h->nz, 0.0);
-        const int rc_ref = almpc_set_reference(h, xr.data(), ur.data(), 0);
-        if (rc_ref != ALMPC_OK) h->designed = false;
-        return rc_ref;
-    }
+// The n terminal-equality rows (the last n state rows) of a shared design are in every working set: eliminated here, once
+static int project_terminal_equality(almpc_handle* h) {
+    const int n = h->n;
+    if (!(h->terminal_eq && h->mc >= n && !h->sw.no_eq_projection)) return ALMPC_OK;
+    const int ne = n, eq0 = h->R - n, Rs = h->Rs;
+    std::vector<double> GE((size_t)ne * Rs), GEE((size_t)ne * ne), Y;
+    HIP_TRY(h, hipMemcpy(GE.data(), h->dGhat + (size_t)eq0 * Rs, GE.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int a = 0; a < ne; ++a)
+        for (int b = 0; b < ne; ++b) GEE[(size_t)b * ne + a] = GE[(size_t)a * Rs + eq0 + b];
+    hm::mat Winv = hm::eye(ne);
+    bool ok = hm::lu_solve(GEE, Winv, ne, ne);
+    for (double v : Winv) ok = ok && std::isfinite(v);
+    if (!ok) return ALMPC_OK;   // (a singular Ghat_EE -- terminal state not reachable in N steps -- keeps the row-by-row path, which reports it)
+    Y.assign((size_t)ne * Rs, 0.0);   // Y = Winv GhatE, row-major [ne][Rs]
+    for (int a = 0; a < ne; ++a)
+        for (int e = 0; e < ne; ++e) {
+            const double wv = Winv[(size_t)e * ne + a];   // Winv(a, e)
+            for (int b = 0; b < Rs; ++b) Y[(size_t)a * Rs + b] += wv * GE[(size_t)e * Rs + b];
+        }
+    std::vector<double> Wrow((size_t)ne * ne);
+    for (int a = 0; a < ne; ++a)
+        for (int e = 0; e < ne; ++e) Wrow[(size_t)a * ne + e] = Winv[(size_t)e * ne + a];
+    DevBuf<double> dY;
+    HIP_TRY(h, h->dGhatE.alloc(GE.size())); HIP_TRY(h, h->dWinvE.alloc(Wrow.size())); HIP_TRY(h, dY.alloc(Y.size()));
+    HIP_TRY(h, hipMemcpy(h->dGhatE, GE.data(), GE.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->dWinvE, Wrow.data(), Wrow.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(dY, Y.data(), Y.size() * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_ghat_project, dim3(512), dim3(256), 0, h->stream, h->R, Rs, ne, eq0, h->dGhatE, dY, h->dGhat, h->dGnorm);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->eq_proj = 1;
+    return ALMPC_OK;
+}
+
+// Blocked rollout of a shared model: s stages per block with one lane per (stage, state row); lane (j, i) holds row i of
+// [A^j B, ..., A B, B (stages t = 0..j), 0 ... | A^(j+1)]  (design-time host math, n x n products)
+static int build_rollout_table(almpc_handle* h, const hm::mat& Am, const hm::mat& Bm) {
+    const int n = h->n, m = h->m, N = h->N;
+    int sblk = std::min(N, std::min(64 / n, ROLL_SMX / m));
+    h->roll_s = 0;
+    if (!(sblk >= 1 && n <= ROLL_NX && !h->sw.rollout_stagewise)) return ALMPC_OK;
+    std::vector<double> M((size_t)(ROLL_SMX + ROLL_NX) * 64, 0.0);
+    std::vector<hm::mat> Apow(sblk + 1), ApB(sblk);  // A^j, A^j B
+    Apow[0] = hm::eye(n);
+    for (int j = 1; j <= sblk; ++j) Apow[j] = hm::mul(Am, Apow[j - 1], n, n, n);
+    for (int j = 0; j < sblk; ++j) ApB[j] = hm::mul(Apow[j], Bm, n, n, m);
+    for (int j = 0; j < sblk; ++j)
+        for (int i = 0; i < n; ++i) {
+            const int lane = j * n + i;
+            for (int t = 0; t <= j; ++t)
+                for (int a = 0; a < m; ++a) M[(size_t)(t * m + a) * 64 + lane] = ApB[j - t][(size_t)a * n + i];
+            for (int c = 0; c < n; ++c) M[(size_t)(ROLL_SMX + c) * 64 + lane] = Apow[j + 1][(size_t)c * n + i];
+        }
+    HIP_TRY(h, h->dRollM.alloc(M.size()));
+    HIP_TRY(h, hipMemcpy(h->dRollM, M.data(), M.size() * sizeof(double), hipMemcpyHostToDevice));
+    h->roll_s = sblk; h->roll_nb = (N + sblk - 1) / sblk;
+    return ALMPC_OK;
+}
+
+static int design_shared_condensed(almpc_handle* h, const double* A, const double* B, const double* Q, const double* R, const double* S,
+                                   const double* P, const double* umin, const double* umax, const double* xmin, const double* xmax,
+                                   double rho, double sigma) {
     if ((xmin == nullptr) != (xmax == nullptr)) return fail(h, ALMPC_ERR_INVALID, "design: give both xmin and xmax or neither");
     if (!(rho > 0.0) || !(sigma >= 0.0)) return fail(h, ALMPC_ERR_INVALID, "design: rho must be > 0 and sigma >= 0");
-    // from here on the handle's previous design is being overwritten: it counts as designed again only after the last step below
-    h->designed = false;
-    h->sqp.ready = h->sqp.started = false;
-    h->relin.ready = false;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int n = h->n, m = h->m, N = h->N, nz = h->nz;
-    for (int i = 0; i < m; ++i)
-        if (!(umin[i] <= umax[i])) return fail(h, ALMPC_ERR_INVALID, "design: umin > umax");
+    ALMPC_TRY(begin_redesign(h, DROP_SQP | DROP_RELIN));
+    const int n = h->n, m = h->m, N = h->N;
+    ALMPC_TRY(check_input_box(h, umin, umax, "design"));
     hm::mat Am(A, A + (size_t)n * n), Bm(B, B + (size_t)n * m), Qm(Q, Q + (size_t)n * n), Rm(R, R + (size_t)m * m);
-    hm::mat Sm = S ? hm::mat(S, S + (size_t)m * m) : hm::mat((size_t)m * m, 0.0);
     hm::mat Pm;
     if (P) Pm.assign(P, P + (size_t)n * n);
     else if (!hm::dare(Am, Bm, Qm, Rm, n, m, Pm)) return fail(h, ALMPC_ERR_NUMERIC, "design: DARE did not converge");
     h->P = Pm;
-    for (int j = 0; j < m; ++j)  // S enters the cost as a quadratic form: only its symmetric part counts
-        for (int i = 0; i < j; ++i) {
-            const double v = 0.5 * (Sm[(size_t)j * m + i] + Sm[(size_t)i * m + j]);
-            Sm[(size_t)j * m + i] = Sm[(size_t)i * m + j] = v;
-        }
+    const hm::mat Sm = hm::symmetrised(S, m);   // S enters the cost as a quadratic form: only its symmetric part counts
     h->hS = Sm;
     h->useS = (Rm[0] != 0.0 && Sm[0] != 0.0) ? 1 : 0;  // the reference drops the S term together with R (src/sub/design_mpc.jl:423-466)
     h->rho = rho; h->sigma = sigma;
 
     // ---- state rows (state box, terminal equality): row tables and the shared constraint-space matrix
-    { const int rc_ = setup_state_rows(h, xmin, xmax, false); if (rc_ != ALMPC_OK) return rc_; }
+    ALMPC_TRY(setup_state_rows(h, xmin, xmax, false));
     std::vector<int> rowsel;   // rows of Gamma the state rows are, in row order
     for (int k = 0; k < N; ++k)
         for (int i = 0; i < n; ++i)
@@ -1487,99 +1609,49 @@ static int design_shared_discrete(almpc_handle* h, const double* A, const double
     h->s0_basis_ok = false;
     if (!rowsel.empty()) HIP_TRY(h, h->dVsPlain.once((size_t)n * h->nzs));
     if (h->nzs <= 64) HIP_TRY(h, h->dPlain.once(2 * (size_t)h->nz * h->nzs + 2 * (size_t)n * h->nzs));
-    int rc = design_shared_device(h->stream, n, m, N, h->nzs, h->nrb, h->ks, h->ksf, Am, Bm, Qm, Rm, Sm, Pm, rho, sigma,
-                                  h->dMinvFrag, h->dVFrag, h->dHFrag, h->dFFrag, h->dG, h->dD, h->H, h->F, h->d, h->err,
-                                  rowsel, h->Rs, h->dGhat, h->dGnorm, h->rho_mode, h->dRho, rowsel.empty() ? nullptr : h->dVsPlain,
-                                  h->nzs <= 64 ? h->dPlain : nullptr, &h->dMinv, &h->dCold);
-    if (rc != ALMPC_OK) return rc;
-    if (h->terminal_eq && h->mc >= n && !h->sw.no_eq_projection) {
-        // the n terminal-equality rows (the last n state rows) are in every working set: eliminate them here, once
-        const int ne = n, eq0 = h->R - n, Rs = h->Rs;
-        std::vector<double> GE((size_t)ne * Rs), GEE((size_t)ne * ne), Y;
-        HIP_TRY(h, hipMemcpy(GE.data(), h->dGhat + (size_t)eq0 * Rs, GE.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int a = 0; a < ne; ++a)
-            for (int b = 0; b < ne; ++b) GEE[(size_t)b * ne + a] = GE[(size_t)a * Rs + eq0 + b];
-        hm::mat Winv = hm::eye(ne);
-        bool ok = hm::lu_solve(GEE, Winv, ne, ne);
-        for (double v : Winv) ok = ok && std::isfinite(v);
-        if (ok) {   // (a singular Ghat_EE -- terminal state not reachable in N steps -- keeps the row-by-row path, which reports it)
-            Y.assign((size_t)ne * Rs, 0.0);   // Y = Winv GhatE, row-major [ne][Rs]
-            for (int a = 0; a < ne; ++a)
-                for (int e = 0; e < ne; ++e) {
-                    const double wv = Winv[(size_t)e * ne + a];   // Winv(a, e)
-                    for (int b = 0; b < Rs; ++b) Y[(size_t)a * Rs + b] += wv * GE[(size_t)e * Rs + b];
-                }
-            std::vector<double> Wrow((size_t)ne * ne);
-            for (int a = 0; a < ne; ++a)
-                for (int e = 0; e < ne; ++e) Wrow[(size_t)a * ne + e] = Winv[(size_t)e * ne + a];
-            DevBuf<double> dY;
-            HIP_TRY(h, h->dGhatE.alloc(GE.size())); HIP_TRY(h, h->dWinvE.alloc(Wrow.size())); HIP_TRY(h, dY.alloc(Y.size()));
-            HIP_TRY(h, hipMemcpy(h->dGhatE, GE.data(), GE.size() * sizeof(double), hipMemcpyHostToDevice));
-            HIP_TRY(h, hipMemcpy(h->dWinvE, Wrow.data(), Wrow.size() * sizeof(double), hipMemcpyHostToDevice));
-            HIP_TRY(h, hipMemcpy(dY, Y.data(), Y.size() * sizeof(double), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(k_ghat_project, dim3(512), dim3(256), 0, h->stream, h->R, Rs, ne, eq0, h->dGhatE, dY, h->dGhat, h->dGnorm);
-            HIP_TRY(h, hipGetLastError());
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            h->eq_proj = 1;
-        }
-    }
-    HIP_TRY(h, hipMemcpy(h->dUmin, umin, m * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->dUmax, umax, m * sizeof(double), hipMemcpyHostToDevice));
+    ALMPC_TRY(design_shared_device(h->stream, n, m, N, h->nzs, h->nrb, h->ks, h->ksf, Am, Bm, Qm, Rm, Sm, Pm, rho, sigma,
+                                   h->dMinvFrag, h->dVFrag, h->dHFrag, h->dFFrag, h->dG, h->dD, h->H, h->F, h->d, h->err,
+                                   rowsel, h->Rs, h->dGhat, h->dGnorm, h->rho_mode, h->dRho, rowsel.empty() ? nullptr : h->dVsPlain,
+                                   h->nzs <= 64 ? h->dPlain : nullptr, &h->dMinv, &h->dCold));
+    ALMPC_TRY(project_terminal_equality(h));
+    ALMPC_TRY(upload_input_box(h, umin, umax));
     HIP_TRY(h, hipMemcpy(h->dA, A, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->dB, B, (size_t)n * m * sizeof(double), hipMemcpyHostToDevice));
-    {
-        // blocked rollout: s stages per block with one lane per (stage, state row); lane (j, i) holds row i of
-        // [A^j B, ..., A B, B (stages t = 0..j), 0 ... | A^(j+1)]  (design-time host math, n x n products)
-        int sblk = std::min(N, std::min(64 / n, ROLL_SMX / m));
-        h->roll_s = 0;
-        if (sblk >= 1 && n <= ROLL_NX && !h->sw.rollout_stagewise) {
-            std::vector<double> M((size_t)(ROLL_SMX + ROLL_NX) * 64, 0.0);
-            std::vector<hm::mat> Apow(sblk + 1), ApB(sblk);  // A^j, A^j B
-            Apow[0] = hm::eye(n);
-            for (int j = 1; j <= sblk; ++j) Apow[j] = hm::mul(Am, Apow[j - 1], n, n, n);
-            for (int j = 0; j < sblk; ++j) ApB[j] = hm::mul(Apow[j], Bm, n, n, m);
-            for (int j = 0; j < sblk; ++j)
-                for (int i = 0; i < n; ++i) {
-                    const int lane = j * n + i;
-                    for (int t = 0; t <= j; ++t)
-                        for (int a = 0; a < m; ++a) M[(size_t)(t * m + a) * 64 + lane] = ApB[j - t][(size_t)a * n + i];
-                    for (int c = 0; c < n; ++c) M[(size_t)(ROLL_SMX + c) * 64 + lane] = Apow[j + 1][(size_t)c * n + i];
-                }
-            HIP_TRY(h, h->dRollM.alloc(M.size()));
-            HIP_TRY(h, hipMemcpy(h->dRollM, M.data(), M.size() * sizeof(double), hipMemcpyHostToDevice));
-            h->roll_s = sblk; h->roll_nb = (N + sblk - 1) / sblk;
-        }
-    }
-    // redo of the instances a step leaves without a certificate (default on): the stage-wise dual active set (k_sdual: also state rows
-    // and S), and behind it -- input box only, S = 0 -- the primal Riccati active set
+    ALMPC_TRY(build_rollout_table(h, Am, Bm));
+    // redo of the instances a step leaves without a certificate (default on)
     h->sd.ready = false;
     if (h->fallback) {
         const bool useS = h->useS != 0;
-        if (sdual_shape_ok(n, m, N, useS)) {
-            hm::mat Rb = Rm;
-            if (Rm[0] == 0.0) std::fill(Rb.begin(), Rb.end(), 0.0);
-            const int rc_ = sdual_setup_shared(h, Am, Bm, Qm, Rb, useS ? &Sm : nullptr, Pm, xmin, xmax, h->terminal_eq != 0);
-            if (rc_ != ALMPC_OK && h->fallback == 1) return rc_;
-        } else if (h->fallback == 1 && (h->mc > 0 || useS))
-            return fail(h, ALMPC_ERR_UNSUPPORTED, "structured fallback: state rows / input-rate weight need n + m <= 48 and (N + 1)(n + m) <= 4096");
-        if (riccati_shape_ok(h) && h->mc == 0 && !useS) {
-            const int rc_ = riccati_weights(h, Qm, Rm, Pm.data());
-            if (rc_ != ALMPC_OK) return rc_;
-            h->r_batched_P = false; h->rP_stride = 0;
-        }
+        const SharedModel model{Am, Bm, Pm};
+        ALMPC_TRY(setup_redo_solvers(h, &model, false, Qm, Rm, useS ? &Sm : nullptr, StateBox{xmin, xmax}, h->fallback == 1,
+                                     "structured fallback: state rows / input-rate weight need n + m <= 48 and (N + 1)(n + m) <= 4096"));
+        if (primal_redo_covers(h, h->mc > 0, useS)) { h->r_batched_P = false; h->rP_stride = 0; }   // (k_riccati: the shared P)
     }
-    h->designed = true;
-    h->batched = false;
-    h->ltv = false;
-    // default references: zeros, shared
-    std::vector<double> xr((size_t)n * (N + 1), 0.0), ur((size_t)nz, 0.0);
-    const int rc_ref = almpc_set_reference(h, xr.data(), ur.data(), 0);
-    if (rc_ref != ALMPC_OK) h->designed = false;
-    return rc_ref;
+    h->designed = true; h->batched = false; h->ltv = false;
+    return set_zero_reference(h);
 }
 
-// Per-instance models: every instance gets its own condensed QP from (A_i, B_i).  The design kernels of
-// almpc_design.hip.h run with blockIdx.y = instance; the per-step path is k_admm_inst + k_polish<false> with strides.
+int almpc_design_shared(almpc_handle* h, const double* A, const double* B, const double* Q, const double* R,
+                        const double* S, const double* P, const double* umin, const double* umax,
+                        const double* xmin, const double* xmax, double rho, double sigma) {
+    if (!h) return ALMPC_ERR_INVALID;
+    hm::mat Ad, Bd;
+    if (A && B && model_continuous(h)) {
+        // almpc_set_model_time: (A, B) is continuous-time; its zero-order hold is the model the handle is designed on and keeps
+        // (src/sub/design_mpc.jl:22-41: discretise, then the discrete method)
+        const int n = h->n, m = h->m;
+        if (hm::c2d(hm::mat(A, A + (size_t)n * n), hm::mat(B, B + (size_t)n * m), h->model_Ts, n, m, Ad, Bd) != 0) {
+            h->designed = false;
+            return fail(h, ALMPC_ERR_NUMERIC, "design: discretisation of the continuous-time model failed (not finite, or |A| Ts beyond 2^59)");
+        }
+        A = Ad.data(); B = Bd.data();
+    }
+    drop_lazy_redo(h);
+    if (!A || !B || !Q || !R || !umin || !umax) return fail(h, ALMPC_ERR_INVALID, "design: null matrix pointer");
+    return h->structured ? design_shared_structured(h, A, B, Q, R, S, P, umin, umax, xmin, xmax)
+                         : design_shared_condensed(h, A, B, Q, R, S, P, umin, umax, xmin, xmax, rho, sigma);
+}
+
 }  // extern "C"
 
 namespace {
@@ -1873,266 +1945,236 @@ hipError_t launch_batched_design(almpc_handle* h, const DesignStrides& ds, int u
     return hipGetLastError();
 }
 
-int design_batched_common(almpc_handle* h, const double* A_batch, const double* B_batch, const double* Q, const double* R,
-                          const double* S, const double* P, int P_per_instance, const double* umin, const double* umax,
-                          double rho, double sigma, const LtvInputs* ltv) {
-    if (!h) return ALMPC_ERR_INVALID;
-    drop_lazy_redo(h);
-    if (h->structured) {   // one model per instance, structured solve: models and terminal weights on the device, nothing condensed
-        if (ltv) return fail(h, ALMPC_ERR_UNSUPPORTED, "structured solve: time-varying designs go through almpc_sqp_fnn_* (stage models on the device)");
-        if (!A_batch || !B_batch || !Q || !R || !umin || !umax) return fail(h, ALMPC_ERR_INVALID, "design_batched: null matrix pointer");
-        const int n = h->n, m = h->m, N = h->N;
-        const size_t b = (size_t)h->batch;
-        const bool useS = R[0] != 0.0 && S && S[0] != 0.0;
-        h->designed = false;
-        HIP_TRY(h, hipSetDevice(h->device));
-        hm::mat Qm(Q, Q + (size_t)n * n), Rm(R, R + (size_t)m * m), Sm;
-        if (useS) {
-            Sm.assign(S, S + (size_t)m * m);
-            for (int j = 0; j < m; ++j)
-                for (int i = 0; i < j; ++i) { const double v = 0.5 * (Sm[(size_t)j * m + i] + Sm[(size_t)i * m + j]); Sm[(size_t)j * m + i] = Sm[(size_t)i * m + j] = v; }
-        }
-        const bool p_inst = P ? (P_per_instance != 0) : true;
-        const bool dev_dare = !P && h->terminal_mode == ALMPC_TERMINAL_DARE_DEVICE;   // (k_dare on the uploaded models, below)
-        h->t_step = false; h->c_step = false;
-        if (model_continuous(h)) { const int rc_ = c2d_shape_check(h, "design_batched"); if (rc_ != ALMPC_OK) return rc_; }
-        hm::mat Pall;
-        if (P) Pall.assign(P, P + (p_inst ? b : 1) * (size_t)n * n);
-        else if (!dev_dare) {
-            Pall.resize(b * (size_t)n * n);
-            for (size_t i = 0; i < b; ++i) {
-                hm::mat Am(A_batch + i * n * n, A_batch + (i + 1) * n * n), Bm(B_batch + i * n * m, B_batch + (i + 1) * n * m), Pm;
-                const char* what = "";
-                if (!host_dare_of(h, Am, Bm, Qm, Rm, Pm, &what)) return fail(h, ALMPC_ERR_NUMERIC, std::string("design_batched: ") + what + " for instance " + std::to_string(i));
-                std::copy(Pm.begin(), Pm.end(), Pall.begin() + i * n * n);
-            }
-        }
-        HIP_TRY(h, h->bA.once(b * n * n));
-        HIP_TRY(h, h->bB.once(b * n * m));
-        HIP_TRY(h, h->bP.once(b * n * n));
-        HIP_TRY(h, hipMemcpy(h->bA, A_batch, b * n * n * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(h->bB, B_batch, b * n * m * sizeof(double), hipMemcpyHostToDevice));
-        if (model_continuous(h)) { const int rc_ = design_c2d_device(h); if (rc_ != ALMPC_OK) return rc_; }   // (in place, in front of every reader)
-        if (dev_dare) {
-            HIP_TRY(h, h->wQ.once((size_t)n * n));
-            HIP_TRY(h, h->wR.once((size_t)m * m));
-            HIP_TRY(h, hipMemcpy(h->wQ, Qm.data(), Qm.size() * sizeof(double), hipMemcpyHostToDevice));
-            HIP_TRY(h, hipMemcpy(h->wR, Rm.data(), Rm.size() * sizeof(double), hipMemcpyHostToDevice));
-            const int rc_ = design_dare_device(h, h->wQ, h->wR, Rm, Pall);
-            if (rc_ != ALMPC_OK) return rc_;
-        } else
-            HIP_TRY(h, hipMemcpy(h->bP, Pall.data(), Pall.size() * sizeof(double), hipMemcpyHostToDevice));
-        h->batched = true; h->ltv = false; h->r_batched_P = true; h->rP_stride = p_inst ? (long)n * n : 0;
-        h->bP_stride = h->rP_stride;
-        const double* bxmin = h->boxmin.empty() ? nullptr : h->boxmin.data();
-        const double* bxmax = h->boxmax.empty() ? nullptr : h->boxmax.data();
-        h->sd.ready = false;
-        if (sdual_shape_ok(n, m, N, useS) && !h->sw.structured_primal) {
-            const int rc_ = sdual_setup_batched(h, Qm, Rm, useS ? &Sm : nullptr, P == nullptr && !useS, bxmin, bxmax, h->terminal_eq != 0);
-            if (rc_ != ALMPC_OK) return rc_;
-            HIP_TRY(h, launch_sgains(h, 0));
-            std::vector<int> bad(b, 0);
-            HIP_TRY(h, hipMemcpyAsync(bad.data(), h->sd.bad, b * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            for (size_t i = 0; i < b; ++i)
-                if (bad[i]) return fail(h, ALMPC_ERR_NUMERIC, "design_batched: R + B'PB is not positive definite for instance " + std::to_string(i));
-        } else if (bxmin || h->terminal_eq || useS)
-            return fail(h, ALMPC_ERR_UNSUPPORTED, "structured solve: state rows / input-rate weight need the stage-wise dual solve (n + m <= 48, (N + 1)(n + m) <= 4096)");
-        if (riccati_shape_ok(h)) { const int rc_ = riccati_weights(h, Qm, Rm, nullptr); if (rc_ != ALMPC_OK) return rc_; }
-        else if (!h->sd.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, "structured solve: shape outside both stage-wise solvers");
-        HIP_TRY(h, hipMemcpy(h->dUmin, umin, m * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(h->dUmax, umax, m * sizeof(double), hipMemcpyHostToDevice));
-        h->P.assign(Pall.begin(), Pall.begin() + (size_t)n * n); h->H.clear(); h->F.clear(); h->d.clear();
-        h->hS.assign((size_t)m * m, 0.0); h->useS = useS ? 1 : 0;
-        if (useS) h->hS = Sm;
-        h->has_box = bxmin ? 1 : 0;
-        h->designed = true;
-        std::vector<double> xr((size_t)n * (N + 1), 0.0), ur((size_t)h->nz, 0.0);
-        const int rc_ref = almpc_set_reference(h, xr.data(), ur.data(), 0);
-        if (rc_ref != ALMPC_OK) h->designed = false;
-        return rc_ref;
+// almpc_design_batched on an ALMPC_FLAG_STRUCTURED handle: one model per instance, structured solve -- models and terminal weights on
+// the device, nothing condensed; rho / sigma are not used
+int design_batched_structured(almpc_handle* h, const double* A_batch, const double* B_batch, const double* Q, const double* R,
+                              const double* S, const double* P, int P_per_instance, const double* umin, const double* umax) {
+    if (!A_batch || !B_batch || !Q || !R || !umin || !umax) return fail(h, ALMPC_ERR_INVALID, "design_batched: null matrix pointer");
+    const int n = h->n, m = h->m;
+    const size_t b = (size_t)h->batch;
+    const bool useS = R[0] != 0.0 && S && S[0] != 0.0;
+    ALMPC_TRY(begin_redesign(h, 0));
+    hm::mat Qm(Q, Q + (size_t)n * n), Rm(R, R + (size_t)m * m), Sm;
+    if (useS) Sm = hm::symmetrised(S, m);
+    const bool p_inst = P ? (P_per_instance != 0) : true;
+    const bool dev_dare = !P && h->terminal_mode == ALMPC_TERMINAL_DARE_DEVICE;   // (k_dare on the uploaded models, below)
+    h->t_step = false; h->c_step = false;
+    if (model_continuous(h)) ALMPC_TRY(c2d_shape_check(h, "design_batched"));
+    hm::mat Pall;
+    ALMPC_TRY(terminal_weights(h, A_batch, B_batch, Qm, Rm, P, p_inst, dev_dare, "design_batched", Pall));
+    HIP_TRY(h, h->bA.once(b * n * n));
+    HIP_TRY(h, h->bB.once(b * n * m));
+    HIP_TRY(h, h->bP.once(b * n * n));
+    HIP_TRY(h, hipMemcpy(h->bA, A_batch, b * n * n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->bB, B_batch, b * n * m * sizeof(double), hipMemcpyHostToDevice));
+    if (model_continuous(h)) ALMPC_TRY(design_c2d_device(h));   // (in place, in front of every reader)
+    if (dev_dare) {
+        HIP_TRY(h, h->wQ.once((size_t)n * n));
+        HIP_TRY(h, h->wR.once((size_t)m * m));
+        HIP_TRY(h, hipMemcpy(h->wQ, Qm.data(), Qm.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->wR, Rm.data(), Rm.size() * sizeof(double), hipMemcpyHostToDevice));
+        ALMPC_TRY(design_dare_device(h, h->wQ, h->wR, Rm, Pall));
+    } else
+        HIP_TRY(h, hipMemcpy(h->bP, Pall.data(), Pall.size() * sizeof(double), hipMemcpyHostToDevice));
+    h->batched = true; h->ltv = false; h->r_batched_P = true; h->rP_stride = p_inst ? (long)n * n : 0;
+    h->bP_stride = h->rP_stride;
+    const StateBox box = state_box(h);
+    // (one stage of records per instance when the terminal weight is the instance's own DARE solution)
+    ALMPC_TRY(setup_structured_solvers(h, nullptr, P == nullptr && !useS, Qm, Rm, useS ? &Sm : nullptr, box));
+    if (h->sd.ready) {
+        HIP_TRY(h, launch_sgains(h, 0));
+        std::vector<int> bad(b, 0);
+        HIP_TRY(h, hipMemcpyAsync(bad.data(), h->sd.bad, b * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (size_t i = 0; i < b; ++i)
+            if (bad[i]) return fail(h, ALMPC_ERR_NUMERIC, "design_batched: R + B'PB is not positive definite for instance " + std::to_string(i));
     }
+    ALMPC_TRY(upload_input_box(h, umin, umax));   // (no umin <= umax check on this route)
+    h->P.assign(Pall.begin(), Pall.begin() + (size_t)n * n); h->H.clear(); h->F.clear(); h->d.clear();
+    h->hS.assign((size_t)m * m, 0.0); h->useS = useS ? 1 : 0;
+    if (useS) h->hS = Sm;
+    h->has_box = box.min ? 1 : 0;
+    h->designed = true;
+    return set_zero_reference(h);
+}
+
+// ALMPC_DESIGN_TRACE=1: host-side time between the marks of a per-instance design on stderr (where the call spends its wall clock)
+struct DesignTrace {
+    bool on = false;
+    std::chrono::steady_clock::time_point mark = std::chrono::steady_clock::now();
+    void operator()(const char* what) {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[almpc design] %-28s %8.1f us\n", what, std::chrono::duration<double, std::micro>(now - mark).count());
+        mark = now;
+    }
+};
+
+// What the front of a condensed per-instance design leaves its caller: the weights, symmetrised; one terminal weight per instance?
+struct BatchedDesign { hm::mat Qm, Rm, Sm; bool p_inst = true; int useR = 0, useS = 0; DesignStrides ds; DesignTrace tr; };
+
+// The front of the condensed per-instance designs (almpc_design_batched, almpc_design_ltv): argument checks, weights, terminal weights,
+// state rows, the per-instance operands, then models and weights on the device -- continuous-time models discretised in place (k_c2d).
+// (What a time-varying design cannot have -- P null, continuous-time models -- its entry point has refused already.)
+int batched_design_front(almpc_handle* h, const double* A_batch, const double* B_batch, const double* Q, const double* R, const double* S,
+                         const double* P, int P_per_instance, const double* umin, const double* umax, double rho, double sigma, BatchedDesign& d) {
     if (!A_batch || !B_batch || !Q || !R || !umin || !umax) return fail(h, ALMPC_ERR_INVALID, "design_batched: null matrix pointer");
     if (!(rho > 0.0) || !(sigma >= 0.0)) return fail(h, ALMPC_ERR_INVALID, "design_batched: rho must be > 0 and sigma >= 0");
-    h->designed = false;  // the previous design is overwritten below; set again by the last statement on success
-    h->sqp.ready = h->sqp.started = false;
-    h->relin.ready = false;
-    // ALMPC_DESIGN_TRACE=1: host-side time between the marks below on stderr (where a design call spends its wall clock)
-    const bool trace_ = h->sw.design_trace;
-    auto t_mark_ = std::chrono::steady_clock::now();
-    auto tr = [&](const char* what) {
-        if (!trace_) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[almpc design] %-28s %8.1f us\n", what, std::chrono::duration<double, std::micro>(now - t_mark_).count());
-        t_mark_ = now;
-    };
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int n = h->n, m = h->m, N = h->N, nz = h->nz, nzs = h->nzs;
+    DesignTrace& tr = d.tr;
+    tr.on = h->sw.design_trace;
+    ALMPC_TRY(begin_redesign(h, DROP_SQP | DROP_RELIN));
+    const int n = h->n, m = h->m;
     const size_t b = (size_t)h->batch;
-    for (int i = 0; i < m; ++i)
-        if (!(umin[i] <= umax[i])) return fail(h, ALMPC_ERR_INVALID, "design_batched: umin > umax");
-    hm::mat Qm(Q, Q + (size_t)n * n), Rm(R, R + (size_t)m * m);
-    hm::mat Sm = S ? hm::mat(S, S + (size_t)m * m) : hm::mat((size_t)m * m, 0.0);
-    auto symmetrise = [](hm::mat& M, int k) {
-        for (int j = 0; j < k; ++j)
-            for (int i = 0; i < j; ++i) {
-                const double v = 0.5 * (M[(size_t)j * k + i] + M[(size_t)i * k + j]);
-                M[(size_t)j * k + i] = M[(size_t)i * k + j] = v;
-            }
-    };
-    symmetrise(Qm, n); symmetrise(Rm, m); symmetrise(Sm, m);
-    // terminal weight: given (shared or per instance), else DARE of every instance's model (src/sub/design_mpc.jl:327)
-    const bool p_inst = P ? (P_per_instance != 0) : true;
+    ALMPC_TRY(check_input_box(h, umin, umax, "design_batched"));
+    d.Qm = hm::symmetrised(Q, n); d.Rm = hm::symmetrised(R, m); d.Sm = hm::symmetrised(S, m);
+    const hm::mat &Qm = d.Qm, &Rm = d.Rm, &Sm = d.Sm;
+    const bool p_inst = d.p_inst = P ? (P_per_instance != 0) : true;
     // (almpc_set_terminal_weight: k_dare on the uploaded models instead of the host loop, behind the uploads below; its P_i are symmetric)
-    const bool dev_dare = !P && !ltv && h->terminal_mode == ALMPC_TERMINAL_DARE_DEVICE;
+    const bool dev_dare = !P && h->terminal_mode == ALMPC_TERMINAL_DARE_DEVICE;
     h->t_step = false; h->c_step = false;
-    const bool cont = !ltv && model_continuous(h);   // (almpc_set_model_time: k_c2d in place on the uploaded models, below)
-    if (cont) { const int rc_ = c2d_shape_check(h, "design_batched"); if (rc_ != ALMPC_OK) return rc_; }
+    const bool cont = model_continuous(h);   // (almpc_set_model_time: k_c2d in place on the uploaded models, below)
+    if (cont) ALMPC_TRY(c2d_shape_check(h, "design_batched"));
     hm::mat Pall;
-    if (P) Pall.assign(P, P + (p_inst ? b : 1) * (size_t)n * n);
-    else if (!dev_dare) {
-        Pall.resize(b * (size_t)n * n);
-        for (size_t i = 0; i < b; ++i) {
-            hm::mat Am(A_batch + i * n * n, A_batch + (i + 1) * n * n), Bm(B_batch + i * n * m, B_batch + (i + 1) * n * m), Pm;
-            const char* what = "";
-            if (!host_dare_of(h, Am, Bm, Qm, Rm, Pm, &what)) return fail(h, ALMPC_ERR_NUMERIC, std::string("design_batched: ") + what + " for instance " + std::to_string(i));
-            std::copy(Pm.begin(), Pm.end(), Pall.begin() + i * n * n);
-        }
-    }
+    ALMPC_TRY(terminal_weights(h, A_batch, B_batch, Qm, Rm, P, p_inst, dev_dare, "design_batched", Pall));
     for (size_t i = 0; i < (dev_dare ? 0 : p_inst ? b : 1); ++i) {
-        hm::mat Pm(Pall.begin() + i * n * n, Pall.begin() + (i + 1) * n * n);
-        symmetrise(Pm, n);
+        const hm::mat Pm = hm::symmetrised(Pall.data() + i * n * n, n);
         std::copy(Pm.begin(), Pm.end(), Pall.begin() + i * n * n);
     }
     if (!dev_dare) h->P.assign(Pall.begin(), Pall.begin() + (size_t)n * n);
     h->hS = Sm;
     h->rho = rho; h->sigma = sigma;
-    const int useR = Rm[0] != 0.0, useS = useR && Sm[0] != 0.0;
-    h->useS = useS;
+    d.useR = Rm[0] != 0.0; d.useS = d.useR && Sm[0] != 0.0;
+    h->useS = d.useS;
     tr("host preparation");
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     tr("stream idle");
     // state rows (almpc_set_state_box, almpc_set_terminal_equality): one constraint-space matrix per instance
-    { const int rc_ = setup_state_rows(h, h->boxmin.empty() ? nullptr : h->boxmin.data(), h->boxmax.empty() ? nullptr : h->boxmax.data(), true);
-      if (rc_ != ALMPC_OK) return rc_; }
-    { const int rc_ = ensure_batched_alloc(h); if (rc_ != ALMPC_OK) return rc_; }
+    ALMPC_TRY(setup_state_rows(h, state_box(h).min, state_box(h).max, true));
+    ALMPC_TRY(ensure_batched_alloc(h));
     hipStream_t st = h->stream;
     tr("state rows + allocation");
     HIP_TRY(h, h->wQ.once((size_t)n * n));
     HIP_TRY(h, h->wR.once((size_t)m * m));
     HIP_TRY(h, h->wS.once((size_t)m * m));
     double *dQ = h->wQ, *dR = h->wR, *dS = h->wS;   // (kept with the handle: three hipMalloc + hipFree per design cost 0.15 ms)
-#define BTRY(call)                                                                                                  \
-    do {                                                                                                            \
-        hipError_t e_ = (call);                                                                                     \
-        if (e_ != hipSuccess) return fail(h, ALMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-    BTRY(hipMemcpyAsync(h->bA, A_batch, b * n * n * sizeof(double), hipMemcpyHostToDevice, st));
-    BTRY(hipMemcpyAsync(h->bB, B_batch, b * n * m * sizeof(double), hipMemcpyHostToDevice, st));
-    if (!dev_dare) BTRY(hipMemcpyAsync(h->bP, Pall.data(), Pall.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    BTRY(hipMemcpyAsync(dQ, Qm.data(), Qm.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    BTRY(hipMemcpyAsync(dR, Rm.data(), Rm.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    BTRY(hipMemcpyAsync(dS, Sm.data(), Sm.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    BTRY(hipMemsetAsync(h->bFlag, 0, b * sizeof(int), st));
+    HIP_TRY(h, hipMemcpyAsync(h->bA, A_batch, b * n * n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(h->bB, B_batch, b * n * m * sizeof(double), hipMemcpyHostToDevice, st));
+    if (!dev_dare) HIP_TRY(h, hipMemcpyAsync(h->bP, Pall.data(), Pall.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(dQ, Qm.data(), Qm.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(dR, Rm.data(), Rm.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(dS, Sm.data(), Sm.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemsetAsync(h->bFlag, 0, b * sizeof(int), st));
     tr("weights alloc + copies queued");
     h->bP_stride = p_inst ? (long)n * n : 0;
     if (cont) {
-        const int rc_ = design_c2d_device(h);
-        if (rc_ != ALMPC_OK) return rc_;
+        ALMPC_TRY(design_c2d_device(h));
         tr("k_c2d");
     }
     if (dev_dare) {
-        const int rc_ = design_dare_device(h, dQ, dR, Rm, h->P);
-        if (rc_ != ALMPC_OK) return rc_;
+        ALMPC_TRY(design_dare_device(h, dQ, dR, Rm, h->P));
         tr("k_dare");
     }
-    const DesignStrides ds = batched_strides(h, p_inst);
-    const unsigned gb = (unsigned)b;
-    if (ltv) {
-        hipError_t e;
-        {
-            DevBuf<double> dAll, dBll, dC, dE, dQa;  // LTV staging (released at the end of this block)
-            e = dAll.upload_async(ltv->A_all, b * N * n * n, st);
-            if (e == hipSuccess) e = dBll.upload_async(ltv->B_all, b * N * n * m, st);
-            if (e == hipSuccess && ltv->c_all) e = dC.upload_async(ltv->c_all, b * N * n, st);
-            if (e == hipSuccess) e = dE.upload_async(ltv->ebar, b * N * n, st);
-            if (e == hipSuccess) e = dQa.upload_async(ltv->qadd, b * nz, st);
-            if (e == hipSuccess) e = h->bQ.once(b * nz);
-            if (e == hipSuccess) e = hipMemsetAsync(h->bF, 0, b * nz * n * sizeof(double), st);
-            if (e == hipSuccess) {
-                DesignLtvParams lp;
-                lp.n = n; lp.m = m; lp.N = N; lp.nz = nz; lp.useR = useR; lp.useS = useS;
-                lp.A = dAll; lp.B = dBll; lp.c = dC; lp.ebar = dE; lp.P = h->bP; lp.sP = ds.P; lp.Q = dQ; lp.R = dR; lp.S = dS;
-                lp.qadd = dQa; lp.H = h->bH; lp.q = h->bQ;
-                e = launch_design_ltv(h, lp, st);
-            }
-            if (e == hipSuccess && h->mc > 0) {   // (needs G_i, d_i: the factor step comes first when there are state rows)
-                launch_batched_factor(h, ds, rho, sigma, st, false);
-                e = launch_ghat_inst(h, dAll, dBll);
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(st);  // the staging buffers are released right away
-            h->lA.reset(); h->lB.reset(); h->lC.reset(); h->lE.reset();
-            if (e == hipSuccess && h->mc > 0) {   // ... except with state rows: the step rolls the stage models out
-                h->lA = std::move(dAll); h->lB = std::move(dBll); h->lC = std::move(dC); h->lE = std::move(dE);
-            }
-        }
-        if (e != hipSuccess) return fail(h, ALMPC_ERR_HIP, std::string("design_ltv: ") + hipGetErrorString(e));
-        if (h->mc == 0) launch_batched_factor(h, ds, rho, sigma, st, false);
-        launch_neg_gm_batched(st, gb, nz, nzs, n, h->bG, h->bFs, h->bVs, ds.G, ds.Fs);
-        BTRY(hipGetLastError());
-    } else {
-        BTRY(launch_batched_design(h, ds, useR, useS, dQ, dR, dS, rho, sigma, false));
-        if (h->mc > 0) BTRY(launch_ghat_inst(h, nullptr, nullptr));
-    }
-    tr("kernels queued");
+    d.ds = batched_strides(h, p_inst);
+    return ALMPC_OK;
+}
+
+// ... and behind their kernels: the flags and the host copies of instance 0 (almpc_get_design; every instance:
+// almpc_get_design_instance) read back, a flagged instance reported, the input box uploaded
+int batched_design_readback(almpc_handle* h, BatchedDesign& d, const double* umin, const double* umax) {
+    const int n = h->n, nz = h->nz, nzs = h->nzs;
+    const size_t b = (size_t)h->batch;
+    hipStream_t st = h->stream;
+    d.tr("kernels queued");
     std::vector<int> flags(b, 0);
-    BTRY(hipMemcpyAsync(flags.data(), h->bFlag, b * sizeof(int), hipMemcpyDeviceToHost, st));
-    // host copies of instance 0 for almpc_get_design (every instance: almpc_get_design_instance)
+    HIP_TRY(h, hipMemcpyAsync(flags.data(), h->bFlag, b * sizeof(int), hipMemcpyDeviceToHost, st));
     h->H.assign((size_t)nz * nz, 0.0); h->F.assign((size_t)nz * n, 0.0); h->d.assign((size_t)nzs, 0.0);
-    BTRY(hipMemcpyAsync(h->H.data(), h->bH, h->H.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    BTRY(hipMemcpyAsync(h->F.data(), h->bF, h->F.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    BTRY(hipMemcpyAsync(h->d.data(), h->bD, h->d.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    BTRY(hipStreamSynchronize(st));
-    tr("device done");
-#undef BTRY
+    HIP_TRY(h, hipMemcpyAsync(h->H.data(), h->bH, h->H.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(h->F.data(), h->bF, h->F.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(h->d.data(), h->bD, h->d.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    d.tr("device done");
     for (size_t i = 0; i < b; ++i)
         if (flags[i] != 0)
             return fail(h, ALMPC_ERR_NUMERIC, "design_batched: instance " + std::to_string(i) +
                         (flags[i] == 1 ? ": condensed Hessian has a non-positive diagonal" : ": Cholesky pivot not positive"));
-    HIP_TRY(h, hipMemcpy(h->dUmin, umin, m * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->dUmax, umax, m * sizeof(double), hipMemcpyHostToDevice));
+    return upload_input_box(h, umin, umax);
+}
+
+// almpc_design_batched on a condensed handle: every instance gets its own condensed QP from (A_i, B_i).  The design kernels of
+// almpc_design.hip.h run with blockIdx.y = instance; the per-step path is k_admm_inst + k_polish<false> with strides.
+int design_batched_condensed(almpc_handle* h, const double* A_batch, const double* B_batch, const double* Q, const double* R, const double* S,
+                             const double* P, int P_per_instance, const double* umin, const double* umax, double rho, double sigma) {
+    BatchedDesign d;
+    ALMPC_TRY(batched_design_front(h, A_batch, B_batch, Q, R, S, P, P_per_instance, umin, umax, rho, sigma, d));
+    const DesignStrides& ds = d.ds;
+    const int n = h->n, useR = d.useR, useS = d.useS;
+    double *dQ = h->wQ, *dR = h->wR, *dS = h->wS;
+    HIP_TRY(h, launch_batched_design(h, ds, useR, useS, dQ, dR, dS, rho, sigma, false));
+    if (h->mc > 0) HIP_TRY(h, launch_ghat_inst(h, nullptr, nullptr));
+    ALMPC_TRY(batched_design_readback(h, d, umin, umax));
     h->sd.ready = false;
-    if (h->fallback && !ltv) {
-        h->r_batched_P = true; h->rP_stride = p_inst ? (long)n * n : 0;
-        if (sdual_shape_ok(n, m, N, useS != 0)) {
-            // (one stage of records per instance when the terminal weight is the instance's own DARE solution)
-            const int rc_ = sdual_setup_batched(h, Qm, Rm, useS ? &Sm : nullptr, P == nullptr && !useS,
-                                                h->boxmin.empty() ? nullptr : h->boxmin.data(), h->boxmax.empty() ? nullptr : h->boxmax.data(), h->terminal_eq != 0);
-            if (rc_ != ALMPC_OK && h->fallback == 1) return rc_;
-            // (the stage records are computed when a step leaves instances to redo, for those instances only: nothing here)
-        } else if (h->fallback == 1 && (h->mc > 0 || useS))
-            return fail(h, ALMPC_ERR_UNSUPPORTED, "structured fallback: state rows / input-rate weight need n + m <= 48 and (N + 1)(n + m) <= 4096");
-        if (riccati_shape_ok(h) && h->mc == 0 && !useS) {
-            const int rc_ = riccati_weights(h, Qm, Rm, nullptr);
-            if (rc_ != ALMPC_OK) return rc_;
+    if (h->fallback) {
+        h->r_batched_P = true; h->rP_stride = d.p_inst ? (long)n * n : 0;
+        // (one stage of records per instance when the terminal weight is the instance's own DARE solution; the stage records are
+        // computed when a step leaves instances to redo, for those instances only: nothing here)
+        ALMPC_TRY(setup_redo_solvers(h, nullptr, P == nullptr && !useS, d.Qm, d.Rm, useS ? &d.Sm : nullptr, state_box(h), h->fallback == 1,
+                                     "structured fallback: state rows / input-rate weight need n + m <= 48 and (N + 1)(n + m) <= 4096"));
+    }
+    h->designed = true; h->batched = true; h->ltv = false;
+    const int rc = set_zero_reference(h);
+    d.tr("flags + set_reference");
+    return rc;
+}
+
+// almpc_design_ltv (a condensed handle): the per-instance design from stage models.  The QP variable is v = u - ubar, so ubar takes
+// the place of the input reference (bounds umin - ubar <= v, u = v + ubar); the gradient is the explicit vector q_i (F'_i = V_i = 0:
+// the step kernels add nothing for e0).  No redo by the stage-wise solvers.
+int design_ltv_condensed(almpc_handle* h, const double* A_batch, const double* B_batch, const double* Q, const double* R, const double* S,
+                         const double* P, int P_per_instance, const double* umin, const double* umax, double rho, double sigma,
+                         const LtvInputs& ltv) {
+    BatchedDesign d;
+    ALMPC_TRY(batched_design_front(h, A_batch, B_batch, Q, R, S, P, P_per_instance, umin, umax, rho, sigma, d));
+    const DesignStrides& ds = d.ds;
+    const int n = h->n, m = h->m, N = h->N, nz = h->nz, nzs = h->nzs;
+    const size_t b = (size_t)h->batch;
+    hipStream_t st = h->stream;
+    double *dQ = h->wQ, *dR = h->wR, *dS = h->wS;
+    hipError_t e;
+    {
+        DevBuf<double> dAll, dBll, dC, dE, dQa;  // LTV staging (released at the end of this block)
+        e = dAll.upload_async(ltv.A_all, b * N * n * n, st);
+        if (e == hipSuccess) e = dBll.upload_async(ltv.B_all, b * N * n * m, st);
+        if (e == hipSuccess && ltv.c_all) e = dC.upload_async(ltv.c_all, b * N * n, st);
+        if (e == hipSuccess) e = dE.upload_async(ltv.ebar, b * N * n, st);
+        if (e == hipSuccess) e = dQa.upload_async(ltv.qadd, b * nz, st);
+        if (e == hipSuccess) e = h->bQ.once(b * nz);
+        if (e == hipSuccess) e = hipMemsetAsync(h->bF, 0, b * nz * n * sizeof(double), st);
+        if (e == hipSuccess) {
+            DesignLtvParams lp;
+            lp.n = n; lp.m = m; lp.N = N; lp.nz = nz; lp.useR = d.useR; lp.useS = d.useS;
+            lp.A = dAll; lp.B = dBll; lp.c = dC; lp.ebar = dE; lp.P = h->bP; lp.sP = ds.P; lp.Q = dQ; lp.R = dR; lp.S = dS;
+            lp.qadd = dQa; lp.H = h->bH; lp.q = h->bQ;
+            e = launch_design_ltv(h, lp, st);
+        }
+        if (e == hipSuccess && h->mc > 0) {   // (needs G_i, d_i: the factor step comes first when there are state rows)
+            launch_batched_factor(h, ds, rho, sigma, st, false);
+            e = launch_ghat_inst(h, dAll, dBll);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(st);  // the staging buffers are released right away
+        h->lA.reset(); h->lB.reset(); h->lC.reset(); h->lE.reset();
+        if (e == hipSuccess && h->mc > 0) {   // ... except with state rows: the step rolls the stage models out
+            h->lA = std::move(dAll); h->lB = std::move(dBll); h->lC = std::move(dC); h->lE = std::move(dE);
         }
     }
-    h->designed = true;
-    h->batched = true;
-    h->ltv = false;
-    if (!ltv) {
-        std::vector<double> xr((size_t)n * (N + 1), 0.0), ur((size_t)nz, 0.0);
-        const int rc = almpc_set_reference(h, xr.data(), ur.data(), 0);
-        if (rc != ALMPC_OK) h->designed = false;
-        tr("flags + set_reference");
-        return rc;
-    }
-    // LTV: the QP variable is v = u - ubar, so ubar takes the place of the input reference (bounds umin - ubar <= v, u = v + ubar);
-    // the gradient is the explicit vector q_i (F'_i = V_i = 0: the step kernels add nothing for e0)
-    {
-        const int rc = almpc_set_reference(h, ltv->xbar, ltv->ubar, 1);
-        if (rc != ALMPC_OK) { h->designed = false; return rc; }
-    }
+    if (e != hipSuccess) return fail(h, ALMPC_ERR_HIP, std::string("design_ltv: ") + hipGetErrorString(e));
+    if (h->mc == 0) launch_batched_factor(h, ds, rho, sigma, st, false);
+    launch_neg_gm_batched(st, (unsigned)b, nz, nzs, n, h->bG, h->bFs, h->bVs, ds.G, ds.Fs);
+    HIP_TRY(h, hipGetLastError());
+    ALMPC_TRY(batched_design_readback(h, d, umin, umax));
+    h->sd.ready = false;
+    h->designed = true; h->batched = true; h->ltv = false;
+    const int rc = almpc_set_reference(h, ltv.xbar, ltv.ubar, 1);
+    if (rc != ALMPC_OK) { h->designed = false; return rc; }
     h->designed = false;  // until the explicit gradient below is in place
     hipLaunchKernelGGL(k_fs_scale, dim3(256), dim3(256), 0, h->stream, h->batch, nz, nzs, h->bQ, (long)nz, h->bD, h->dFS);
     hipLaunchKernelGGL(k_neg_gm, dim3(1, (unsigned)h->batch), dim3(256), 0, h->stream, nz, nzs, 1, nz, h->bG, h->dFS, h->dV0S,
@@ -2141,79 +2183,6 @@ int design_batched_common(almpc_handle* h, const double* A_batch, const double* 
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->ltv = true;
     h->designed = true;
-    return ALMPC_OK;
-}
-}  // namespace
-
-namespace {
-// almpc_relin_fnn_setup on an ALMPC_FLAG_STRUCTURED handle: network, references and weights on the device, the per-instance model and
-// terminal-weight slots, and the stage-wise solver's per-instance set-up (records per stage: the terminal weight is the caller's P).
-int relin_setup_structured(almpc_handle* h, int H, int L, int net, int activation, const double* W_in, const double* W_h, const double* b_h,
-                           const double* W_out, const double* xref, const double* uref, const double* Q, const double* R, const double* S,
-                           const double* P, const double* umin, const double* umax) {
-    const int n = h->n, m = h->m, N = h->N, nz = h->nz;
-    const size_t b = (size_t)h->batch;
-    if (fnn_wave_scratch_doubles(n, m, H, L, net) * sizeof(double) > 160 * 1024)
-        return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup: the network's forward-mode Jacobian must fit the 160 KB of LDS");
-    for (int i = 0; i < m; ++i)
-        if (!(umin[i] <= umax[i])) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: umin > umax");
-    h->designed = false;
-    h->sqp.ready = h->sqp.started = false;
-    h->relin.ready = false;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    auto sym = [](const double* M, int k) {
-        hm::mat o((size_t)k * k, 0.0);
-        if (M)
-            for (int j = 0; j < k; ++j)
-                for (int i = 0; i < k; ++i) o[(size_t)j * k + i] = 0.5 * (M[(size_t)j * k + i] + M[(size_t)i * k + j]);
-        return o;
-    };
-    const hm::mat Qm = sym(Q, n), Rm = sym(R, m), Sm = sym(S, m), Pm = sym(P, n);
-    const bool useS = Rm[0] != 0.0 && S && Sm[0] != 0.0;
-    if (!sdual_shape_ok(n, m, N, useS))
-        return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup (structured): n (+ m with an input-rate weight) <= 48, m <= 16 and (N + 1)(n + m) <= 4096");
-    almpc_handle::Relin& q = h->relin;
-    q.Q.reset(); q.R.reset(); q.S.reset(); q.gS.reset();   // (the network and ulin are replaced by their uploads below)
-    std::vector<double> xr((size_t)n * (N + 1), 0.0), ur((size_t)nz, 0.0);
-    if (xref) xr.assign(xref, xref + xr.size());
-    if (uref) ur.assign(uref, uref + ur.size());
-    std::vector<double> ul(b * m);
-    for (size_t i = 0; i < b; ++i)
-        for (int a = 0; a < m; ++a) ul[i * m + a] = ur[a];  // every instance linearises at the first input reference
-    HIP_TRY(h, upload_net(q, n, m, H, L, activation, net, W_in, W_h, b_h, W_out)); HIP_TRY(h, q.ulin.upload(ul.data(), ul.size()));
-    HIP_TRY(h, h->bA.once(b * n * n));
-    HIP_TRY(h, h->bB.once(b * n * m));
-    HIP_TRY(h, h->bP.once(b * n * n));
-    HIP_TRY(h, hipMemset(h->bA, 0, b * n * n * sizeof(double)));
-    HIP_TRY(h, hipMemset(h->bB, 0, b * n * m * sizeof(double)));
-    HIP_TRY(h, hipMemcpy(h->bP, Pm.data(), Pm.size() * sizeof(double), hipMemcpyHostToDevice));
-    { const int rc_ = relin_terminal_setup(h, Rm, Pm); if (rc_ != ALMPC_OK) return rc_; }
-    { const int rc_ = relin_c2d_setup(h); if (rc_ != ALMPC_OK) return rc_; }
-    h->batched = true; h->ltv = false; h->r_batched_P = true; h->rP_stride = h->t_step ? (long)n * n : 0;   // (t_step: one P_i per step, k_dare)
-    h->bP_stride = h->rP_stride;
-    h->sd.ready = false;
-    {
-        const int rc_ = sdual_setup_batched(h, Qm, Rm, useS ? &Sm : nullptr, false, h->boxmin.empty() ? nullptr : h->boxmin.data(),
-                                            h->boxmax.empty() ? nullptr : h->boxmax.data(), h->terminal_eq != 0);
-        if (rc_ != ALMPC_OK) return rc_;
-    }
-    if (riccati_shape_ok(h)) { const int rc_ = riccati_weights(h, Qm, Rm, nullptr); if (rc_ != ALMPC_OK) return rc_; }
-    HIP_TRY(h, hipMemcpy(h->dUmin, umin, m * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->dUmax, umax, m * sizeof(double), hipMemcpyHostToDevice));
-    h->P = Pm; h->H.clear(); h->F.clear(); h->d.clear();
-    h->hS = Sm; h->useS = useS ? 1 : 0;
-    h->has_box = h->boxmin.empty() ? 0 : 1;
-    for (auto& e : q.ev)
-        if (!e) HIP_TRY(h, hipEventCreate(&e));
-    q.have_prev = false; q.useR = Rm[0] != 0.0; q.useS = useS;
-    HIP_TRY(h, q.u0.once(b * m));
-    HIP_TRY(h, q.xnext.once(b * n));
-    h->r_has_step = false;
-    h->designed = true;
-    const int rc_ref = almpc_set_reference(h, xr.data(), ur.data(), 0);   // (also the input-rate terms of a horizon-varying u_ref: sdual_update_base)
-    if (rc_ref != ALMPC_OK) { h->designed = false; return rc_ref; }
-    q.ready = true;
     return ALMPC_OK;
 }
 
@@ -2790,7 +2759,10 @@ extern "C" {
 int almpc_design_batched(almpc_handle* h, const double* A_batch, const double* B_batch, const double* Q, const double* R,
                          const double* S, const double* P, int P_per_instance, const double* umin, const double* umax,
                          double rho, double sigma) {
-    return design_batched_common(h, A_batch, B_batch, Q, R, S, P, P_per_instance, umin, umax, rho, sigma, nullptr);
+    if (!h) return ALMPC_ERR_INVALID;
+    drop_lazy_redo(h);
+    return h->structured ? design_batched_structured(h, A_batch, B_batch, Q, R, S, P, P_per_instance, umin, umax)
+                         : design_batched_condensed(h, A_batch, B_batch, Q, R, S, P, P_per_instance, umin, umax, rho, sigma);
 }
 
 // Time-varying models: see include/almpc.h.  The host prepares ebar = xbar - x_ref (stages 1..N), the input part of the
@@ -2837,7 +2809,8 @@ int almpc_design_ltv(almpc_handle* h, const double* A_all, const double* B_all, 
                 }
     }
     LtvInputs in{A_all, B_all, c_all, ebar.data(), qadd.data(), ubar, xbar};
-    return design_batched_common(h, A0.data(), B0.data(), Q, R, S, P, P_per_instance, umin, umax, rho, sigma, &in);
+    if (h->structured) return fail(h, ALMPC_ERR_UNSUPPORTED, "structured solve: time-varying designs go through almpc_sqp_fnn_* (stage models on the device)");
+    return design_ltv_condensed(h, A0.data(), B0.data(), Q, R, S, P, P_per_instance, umin, umax, rho, sigma, in);
 }
 
 int almpc_get_gradient_instance(almpc_handle* h, int instance, double* q) {
@@ -2849,50 +2822,104 @@ int almpc_get_gradient_instance(almpc_handle* h, int instance, double* q) {
     return ALMPC_OK;
 }
 
+// The network arguments of a setup call that are there and have a shape
+static bool net_args_ok(int H, int L, const double* W_in, const double* W_h, const double* b_h, const double* W_out) {
+    return H >= 1 && L >= 0 && W_in && W_out && (L == 0 || (W_h && b_h));
+}
+// ... and its kind and activation (setup_net); who: "relin" or "sqp", the call's name in the message
+static int decode_setup_net(almpc_handle* h, bool dense, const char* who, int* activation, int* net) {
+    if (setup_net(dense, *activation, net, activation)) return ALMPC_OK;
+    return fail(h, ALMPC_ERR_UNSUPPORTED, std::string(who) + (dense ? "_densenet_setup: activation must be 0..4"
+                                                                    : "_fnn_setup: activation must be ALMPC_NET_CODE(kind 0..2, activation 0..4)"));
+}
+// The network of a pipeline or loop as the kernels take it: shape, weights and the batch; points and outputs are the caller's
+static FnnParams fnn_params(const almpc_handle* h, const almpc_handle::Net& q) {
+    FnnParams fp;
+    fp.n = h->n; fp.m = h->m; fp.H = q.H; fp.L = q.L; fp.act = q.act; fp.batch = h->batch;
+    fp.W_in = q.W_in; fp.W_h = q.W_h; fp.b_h = q.b_h; fp.W_out = q.W_out;
+    return fp;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // Per-step re-linearisation of a black-box Fnn model, resident on the device (BASELINE configs[3]; include/almpc.h).
-// (dense: almpc_relin_densenet_setup, activation a bare code; else almpc_relin_fnn_setup, activation an ALMPC_NET_CODE)
-static int relin_net_setup(almpc_handle* h, bool dense, int H, int L, int activation, const double* W_in, const double* W_h,
-                           const double* b_h, const double* W_out, const double* xref, const double* uref, const double* Q,
-                           const double* R, const double* S, const double* P, const double* umin, const double* umax, double rho,
-                           double sigma) {
-    if (!h) return ALMPC_ERR_INVALID;
-    drop_lazy_redo(h);
-    if (H < 1 || L < 0 || !W_in || !W_out || (L > 0 && (!W_h || !b_h)) || !Q || !R || !P || !umin || !umax)
-        return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: null pointer or bad network shape (P must be given: the terminal weight "
-                                          "comes from the linearisation at the last reference, src/sub/design_mpc.jl:312-327)");
-    int net = NET_FNN;
-    if (!setup_net(dense, activation, &net, &activation))
-        return fail(h, ALMPC_ERR_UNSUPPORTED, dense ? "relin_densenet_setup: activation must be 0..4"
-                                                    : "relin_fnn_setup: activation must be ALMPC_NET_CODE(kind 0..2, activation 0..4)");
-    if (h->structured) return relin_setup_structured(h, H, L, net, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, umin, umax);
-    if (!(rho > 0.0) || !(sigma >= 0.0)) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: rho must be > 0 and sigma >= 0");
-    const int n = h->n, m = h->m, N = h->N, nz = h->nz;
+
+// Host side of a setup: the weights, symmetrised, and the references
+struct RelinSetup { hm::mat Qm, Rm, Sm, Pm; std::vector<double> xr, ur; };
+
+// The front of almpc_relin_*_setup on either kind of handle: the checks that are left, the previous design gone, then the network and
+// every instance's linearisation input on the device, the timing events, the buffers of almpc_relin_fnn_advance
+static int relin_setup_common(almpc_handle* h, int H, int L, int net, int activation, const double* W_in, const double* W_h, const double* b_h,
+                              const double* W_out, const double* xref, const double* uref, const double* Q, const double* R, const double* S,
+                              const double* P, const double* umin, const double* umax, RelinSetup& s) {
+    const int n = h->n, m = h->m, N = h->N;
     const size_t b = (size_t)h->batch;
     if (fnn_wave_scratch_doubles(n, m, H, L, net) * sizeof(double) > 160 * 1024)
         return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup: the network's forward-mode Jacobian must fit the 160 KB of LDS");
-    for (int i = 0; i < m; ++i)
-        if (!(umin[i] <= umax[i])) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: umin > umax");
-    h->designed = false;
-    h->sqp.ready = h->sqp.started = false;
-    h->relin.ready = false;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    auto sym = [](const double* M, int k) {
-        hm::mat o((size_t)k * k, 0.0);
-        if (M)
-            for (int j = 0; j < k; ++j)
-                for (int i = 0; i < k; ++i) o[(size_t)j * k + i] = 0.5 * (M[(size_t)j * k + i] + M[(size_t)i * k + j]);
-        return o;
-    };
-    const hm::mat Qm = sym(Q, n), Rm = sym(R, m), Sm = sym(S, m), Pm = sym(P, n);
-    { const int rc_ = ensure_batched_alloc(h); if (rc_ != ALMPC_OK) return rc_; }
+    ALMPC_TRY(check_input_box(h, umin, umax, "relin_fnn_setup"));
+    ALMPC_TRY(begin_redesign(h, DROP_SQP | DROP_RELIN | WAIT_STREAM));
+    s.Qm = hm::symmetrised(Q, n); s.Rm = hm::symmetrised(R, m); s.Sm = hm::symmetrised(S, m); s.Pm = hm::symmetrised(P, n);
     almpc_handle::Relin& q = h->relin;
+    q.useR = s.Rm[0] != 0.0; q.useS = q.useR && s.Sm[0] != 0.0;
+    if (h->structured && !sdual_shape_ok(n, m, N, q.useS != 0))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup (structured): n (+ m with an input-rate weight) <= 48, m <= 16 and (N + 1)(n + m) <= 4096");
     q.Q.reset(); q.R.reset(); q.S.reset(); q.gS.reset();   // (the network and ulin are replaced by their uploads below)
-    std::vector<double> xr((size_t)n * (N + 1), 0.0), ur((size_t)nz, 0.0);
-    if (xref) xr.assign(xref, xref + xr.size());
-    if (uref) ur.assign(uref, uref + ur.size());
-    q.useR = Rm[0] != 0.0; q.useS = q.useR && Sm[0] != 0.0;
+    s.xr.assign((size_t)n * (N + 1), 0.0); s.ur.assign((size_t)h->nz, 0.0);
+    if (xref) s.xr.assign(xref, xref + s.xr.size());
+    if (uref) s.ur.assign(uref, uref + s.ur.size());
+    std::vector<double> ul(b * m);
+    for (size_t i = 0; i < b; ++i)
+        for (int a = 0; a < m; ++a) ul[i * m + a] = s.ur[a];  // every instance linearises at the first input reference
+    HIP_TRY(h, upload_net(q, n, m, H, L, activation, net, W_in, W_h, b_h, W_out)); HIP_TRY(h, q.ulin.upload(ul.data(), ul.size()));
+    for (auto& e : q.ev)
+        if (!e) HIP_TRY(h, hipEventCreate(&e));
+    q.have_prev = false;
+    HIP_TRY(h, q.u0.once(b * m));
+    HIP_TRY(h, q.xnext.once(b * n));
+    return ALMPC_OK;
+}
+
+// ... on an ALMPC_FLAG_STRUCTURED handle: the per-instance model and terminal-weight slots, and the stage-wise solver's per-instance
+// set-up (records per stage: the terminal weight is the caller's P)
+static int relin_setup_structured(almpc_handle* h, const RelinSetup& s, const double* umin, const double* umax) {
+    const int n = h->n, m = h->m;
+    const size_t b = (size_t)h->batch;
+    const hm::mat &Qm = s.Qm, &Rm = s.Rm, &Sm = s.Sm, &Pm = s.Pm;
+    almpc_handle::Relin& q = h->relin;
+    HIP_TRY(h, h->bA.once(b * n * n));
+    HIP_TRY(h, h->bB.once(b * n * m));
+    HIP_TRY(h, h->bP.once(b * n * n));
+    HIP_TRY(h, hipMemset(h->bA, 0, b * n * n * sizeof(double)));
+    HIP_TRY(h, hipMemset(h->bB, 0, b * n * m * sizeof(double)));
+    HIP_TRY(h, hipMemcpy(h->bP, Pm.data(), Pm.size() * sizeof(double), hipMemcpyHostToDevice));
+    ALMPC_TRY(relin_terminal_setup(h, Rm, Pm));
+    ALMPC_TRY(relin_c2d_setup(h));
+    h->batched = true; h->ltv = false; h->r_batched_P = true; h->rP_stride = h->t_step ? (long)n * n : 0;   // (t_step: one P_i per step, k_dare)
+    h->bP_stride = h->rP_stride;
+    const StateBox box = state_box(h);
+    h->sd.ready = false;   // (k_sdual whatever ALMPC_STRUCTURED_PRIMAL says: the step's k_sgains has no other reader)
+    ALMPC_TRY(sdual_setup_batched(h, Qm, Rm, q.useS ? &Sm : nullptr, false, box.min, box.max, h->terminal_eq != 0));
+    if (riccati_shape_ok(h)) ALMPC_TRY(riccati_weights(h, Qm, Rm, nullptr));
+    ALMPC_TRY(upload_input_box(h, umin, umax));
+    h->P = Pm; h->H.clear(); h->F.clear(); h->d.clear();
+    h->hS = Sm; h->useS = q.useS;
+    h->has_box = box.min ? 1 : 0;
+    h->r_has_step = false;
+    h->designed = true;
+    const int rc_ref = almpc_set_reference(h, s.xr.data(), s.ur.data(), 0);   // (also the input-rate terms of a horizon-varying u_ref: sdual_update_base)
+    if (rc_ref != ALMPC_OK) { h->designed = false; return rc_ref; }
+    q.ready = true;
+    return ALMPC_OK;
+}
+
+// ... on a condensed handle: weights and references on the device (shared; the scaled input-rate gradient fS_i = d_i .* gS and
+// v0S_i = -G_i fS_i are per instance, re-made every step), the per-instance operands and state rows, the redo's solvers
+static int relin_setup_condensed(almpc_handle* h, const RelinSetup& s, const double* umin, const double* umax, double rho, double sigma) {
+    const int n = h->n, m = h->m, N = h->N, nz = h->nz;
+    const size_t b = (size_t)h->batch;
+    const hm::mat &Qm = s.Qm, &Rm = s.Rm, &Sm = s.Sm, &Pm = s.Pm;
+    const std::vector<double>&xr = s.xr, &ur = s.ur;
+    almpc_handle::Relin& q = h->relin;
+    ALMPC_TRY(ensure_batched_alloc(h));
     // unscaled input-rate gradient of the shared reference: 2 D'Sbar D u_ref (the rate cost is on u itself, src/sub/design_mpc.jl:423-446)
     std::vector<double> gS((size_t)nz, 0.0);
     if (q.useS)
@@ -2903,55 +2930,54 @@ static int relin_net_setup(almpc_handle* h, bool dense, int H, int L, int activa
                 gS[i * m + a] += 2.0 * sd;
                 gS[(i + 1) * m + a] -= 2.0 * sd;
             }
-    std::vector<double> ul(b * m);
-    for (size_t i = 0; i < b; ++i)
-        for (int a = 0; a < m; ++a) ul[i * m + a] = ur[a];  // every instance linearises at the first input reference
-    HIP_TRY(h, upload_net(q, n, m, H, L, activation, net, W_in, W_h, b_h, W_out)); HIP_TRY(h, q.ulin.upload(ul.data(), ul.size()));
     HIP_TRY(h, q.Q.upload(Qm.data(), Qm.size())); HIP_TRY(h, q.R.upload(Rm.data(), Rm.size())); HIP_TRY(h, q.S.upload(Sm.data(), Sm.size()));
     HIP_TRY(h, q.gS.upload(gS.data(), gS.size()));
     HIP_TRY(h, hipMemcpy(h->bP, Pm.data(), Pm.size() * sizeof(double), hipMemcpyHostToDevice));
-    { const int rc_ = relin_terminal_setup(h, Rm, Pm); if (rc_ != ALMPC_OK) return rc_; }
-    { const int rc_ = relin_c2d_setup(h); if (rc_ != ALMPC_OK) return rc_; }
+    ALMPC_TRY(relin_terminal_setup(h, Rm, Pm));
+    ALMPC_TRY(relin_c2d_setup(h));
     h->bP_stride = h->t_step ? (long)n * n : 0;   // (t_step: one P_i per step, k_dare)
-    HIP_TRY(h, hipMemcpy(h->dUmin, umin, m * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->dUmax, umax, m * sizeof(double), hipMemcpyHostToDevice));
-    // shared references; the scaled input-rate gradient fS_i = d_i .* gS and v0S_i = -G_i fS_i are per instance (re-made every step)
+    ALMPC_TRY(upload_input_box(h, umin, umax));
     h->ref_keep = false;
     HIP_TRY(h, h->dXref.upload(xr.data(), xr.size())); HIP_TRY(h, h->dUref.upload(ur.data(), ur.size()));
     HIP_TRY(h, h->dFS.alloc(b * nz)); HIP_TRY(h, h->dV0S.alloc(b * nz)); h->dCold.reset(); h->cold_ref = false;
     HIP_TRY(h, hipMemset(h->dFS, 0, b * nz * sizeof(double))); HIP_TRY(h, hipMemset(h->dV0S, 0, b * nz * sizeof(double)));
     h->xref_stride = 0; h->uref_stride = 0; h->fS_stride = nz;
-    for (auto& e : q.ev)
-        if (!e) HIP_TRY(h, hipEventCreate(&e));
-    q.have_prev = false;
-    HIP_TRY(h, q.u0.once(b * m));
-    HIP_TRY(h, q.xnext.once(b * n));
     h->P = Pm; h->hS = Sm; h->useS = q.useS;
     h->rho = rho; h->sigma = sigma;
-    { const int rc_ = setup_state_rows(h, h->boxmin.empty() ? nullptr : h->boxmin.data(), h->boxmax.empty() ? nullptr : h->boxmax.data(), true);
-      if (rc_ != ALMPC_OK) return rc_; }
+    const StateBox box = state_box(h);
+    ALMPC_TRY(setup_state_rows(h, box.min, box.max, true));
     h->batched = true; h->ltv = false;
     h->state_valid = true;
     h->sd.ready = false;
     if (h->fallback) {
         h->r_batched_P = true; h->rP_stride = h->bP_stride;
-        if (sdual_shape_ok(n, m, N, q.useS != 0)) {
-            // (the models change with every step: the records of the instances a step leaves unsolved are computed in that step)
-            const int rc_ = sdual_setup_batched(h, Qm, Rm, q.useS ? &Sm : nullptr, false,
-                                                h->boxmin.empty() ? nullptr : h->boxmin.data(), h->boxmax.empty() ? nullptr : h->boxmax.data(), h->terminal_eq != 0);
-            if (rc_ != ALMPC_OK && h->fallback == 1) return rc_;
-            // the references were uploaded above, not through almpc_set_reference (which this pipeline refuses): the input-rate terms
-            // of a horizon-varying u_ref (+-S (u_ref[k-1] - u_ref[k])) have to reach the stage-wise redo from here
-            if (rc_ == ALMPC_OK) { const int rb_ = sdual_update_base(h, ur.data(), 1); if (rb_ != ALMPC_OK) return rb_; }
-        } else if (h->fallback == 1 && (h->mc > 0 || q.useS))
-            return fail(h, ALMPC_ERR_UNSUPPORTED, "structured fallback: state rows / input-rate weight need n + m <= 48 and (N + 1)(n + m) <= 4096");
-        if (riccati_shape_ok(h) && h->mc == 0 && !q.useS) {
-            const int rc_ = riccati_weights(h, Qm, Rm, nullptr);
-            if (rc_ != ALMPC_OK) return rc_;
-        }
+        // (the models change with every step: the records of the instances a step leaves unsolved are computed in that step)
+        ALMPC_TRY(setup_redo_solvers(h, nullptr, false, Qm, Rm, q.useS ? &Sm : nullptr, box, h->fallback == 1,
+                                     "structured fallback: state rows / input-rate weight need n + m <= 48 and (N + 1)(n + m) <= 4096"));
+        // the references were uploaded above, not through almpc_set_reference (which this pipeline refuses): the input-rate terms
+        // of a horizon-varying u_ref (+-S (u_ref[k-1] - u_ref[k])) have to reach the stage-wise redo from here
+        if (h->sd.ready) ALMPC_TRY(sdual_update_base(h, ur.data(), 1));
     }
     q.ready = true;
     return ALMPC_OK;
+}
+
+// (dense: almpc_relin_densenet_setup, activation a bare code; else almpc_relin_fnn_setup, activation an ALMPC_NET_CODE)
+static int relin_net_setup(almpc_handle* h, bool dense, int H, int L, int activation, const double* W_in, const double* W_h,
+                           const double* b_h, const double* W_out, const double* xref, const double* uref, const double* Q,
+                           const double* R, const double* S, const double* P, const double* umin, const double* umax, double rho,
+                           double sigma) {
+    if (!h) return ALMPC_ERR_INVALID;
+    drop_lazy_redo(h);
+    if (!net_args_ok(H, L, W_in, W_h, b_h, W_out) || !Q || !R || !P || !umin || !umax)
+        return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: null pointer or bad network shape (P must be given: the terminal weight "
+                                          "comes from the linearisation at the last reference, src/sub/design_mpc.jl:312-327)");
+    int net = NET_FNN;
+    ALMPC_TRY(decode_setup_net(h, dense, "relin", &activation, &net));
+    if (!h->structured && (!(rho > 0.0) || !(sigma >= 0.0))) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_setup: rho must be > 0 and sigma >= 0");
+    RelinSetup s;
+    ALMPC_TRY(relin_setup_common(h, H, L, net, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, umin, umax, s));
+    return h->structured ? relin_setup_structured(h, s, umin, umax) : relin_setup_condensed(h, s, umin, umax, rho, sigma);
 }
 int almpc_relin_fnn_setup(almpc_handle* h, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
                           const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
@@ -2974,9 +3000,7 @@ int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
     const bool timing = (h->flags & ALMPC_FLAG_TIMING) != 0;
     if (timing) HIP_TRY(h, hipEventRecord(q.ev[0], st));
     // 1. Jacobians at (x0_i, u_ref[:,1]) straight into the handle's per-instance model slots
-    FnnParams fp;
-    fp.n = n; fp.m = m; fp.H = q.H; fp.L = q.L; fp.act = q.act; fp.batch = h->batch;
-    fp.W_in = q.W_in; fp.W_h = q.W_h; fp.b_h = q.b_h; fp.W_out = q.W_out;
+    FnnParams fp = fnn_params(h, q);
     fp.x = h->dX0; fp.u = q.ulin; fp.ppi = 1; fp.xs_group = n; fp.us_group = m;
     fp.A = h->bA; fp.B = h->bB; fp.f = nullptr;
     if (h->structured) {
@@ -3071,14 +3095,12 @@ int almpc_relin_fnn_advance(almpc_handle* h) {
     if (h->c_step)
         return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_advance: the network is continuous-time (almpc_set_model_time); its plant is an integrator, which is the caller's");
     HIP_TRY(h, hipSetDevice(h->device));
-    { const int rc_ = enqueue_gated_redo(h); if (rc_ != ALMPC_OK) return rc_; }   // (the network is driven by decided instances' inputs only)
+    ALMPC_TRY(enqueue_gated_redo(h));   // (the network is driven by decided instances' inputs only)
     const int n = h->n, m = h->m;
     hipStream_t st = h->stream;
     const size_t cnt = (size_t)h->batch * m;
     hipLaunchKernelGGL(k_pack_first_input, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, h->batch, m, h->N, h->dU, q.u0);
-    FnnParams fp;
-    fp.n = n; fp.m = m; fp.H = q.H; fp.L = q.L; fp.act = q.act; fp.batch = h->batch;
-    fp.W_in = q.W_in; fp.W_h = q.W_h; fp.b_h = q.b_h; fp.W_out = q.W_out;
+    FnnParams fp = fnn_params(h, q);
     fp.x = h->dX0; fp.u = q.u0; fp.ppi = 1; fp.xs_group = n; fp.us_group = m;
     // (the Jacobians of the forward pass go to a scratch of their own: the model slots keep the last step's linearisations, which a
     // lazily deferred redo of that step still needs)
@@ -3120,12 +3142,10 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
     if (model_continuous(h))
         return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_setup: continuous-time models (almpc_set_model_time) are outside the SQP loop");
     drop_lazy_redo(h);
-    if (H < 1 || L < 0 || !W_in || !W_out || (L > 0 && (!W_h || !b_h)) || !Q || !R || !P || !umin || !umax)
+    if (!net_args_ok(H, L, W_in, W_h, b_h, W_out) || !Q || !R || !P || !umin || !umax)
         return fail(h, ALMPC_ERR_INVALID, "sqp_fnn_setup: null pointer or bad network shape (P must be given)");
     int net = NET_FNN;
-    if (!setup_net(dense, activation, &net, &activation))
-        return fail(h, ALMPC_ERR_UNSUPPORTED, dense ? "sqp_densenet_setup: activation must be 0..4"
-                                                    : "sqp_fnn_setup: activation must be ALMPC_NET_CODE(kind 0..2, activation 0..4)");
+    ALMPC_TRY(decode_setup_net(h, dense, "sqp", &activation, &net));
     if (!(rho > 0.0) || !(sigma >= 0.0)) return fail(h, ALMPC_ERR_INVALID, "sqp_fnn_setup: rho must be > 0 and sigma >= 0");
     const int n = h->n, m = h->m, N = h->N, nz = h->nz, nzs = h->nzs;
     const size_t b = (size_t)h->batch, nin = (size_t)n + m;
@@ -3141,34 +3161,21 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
         return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_setup: nz <= 128, or nz^2 + 3 n nz doubles must fit the 160 KB of LDS");
     if ((net == NET_DENSENET ? fnn_wave_scratch_doubles(n, m, H, L, net) : 2 * (size_t)H + 2 * (size_t)H * nin + nin) * sizeof(double) > 160 * 1024)
         return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_setup: the network's forward-mode Jacobian must fit the 160 KB of LDS");
-    for (int i = 0; i < m; ++i)
-        if (!(umin[i] <= umax[i])) return fail(h, ALMPC_ERR_INVALID, "sqp_fnn_setup: umin > umax");
-    h->designed = false;  // any earlier design of the handle is replaced (its reference buffers are released below)
-    h->sqp.ready = h->sqp.started = false;
-    h->relin.ready = false;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    auto sym = [](const double* M, int k) {
-        hm::mat o((size_t)k * k, 0.0);
-        if (M)
-            for (int j = 0; j < k; ++j)
-                for (int i = 0; i < k; ++i) o[(size_t)j * k + i] = 0.5 * (M[(size_t)j * k + i] + M[(size_t)i * k + j]);
-        return o;
-    };
-    const hm::mat Qm = sym(Q, n), Rm = sym(R, m), Sm = sym(S, m);
+    ALMPC_TRY(check_input_box(h, umin, umax, "sqp_fnn_setup"));
+    // (any earlier design of the handle is replaced: its reference buffers are released below)
+    ALMPC_TRY(begin_redesign(h, DROP_SQP | DROP_RELIN | WAIT_STREAM));
+    const hm::mat Qm = hm::symmetrised(Q, n), Rm = hm::symmetrised(R, m), Sm = hm::symmetrised(S, m);
     const bool p_inst = P_per_instance != 0;
     hm::mat Pall((p_inst ? b : 1) * (size_t)n * n);
     for (size_t i = 0; i < (p_inst ? b : 1); ++i) {
-        const hm::mat Pm = sym(P + i * n * n, n);
+        const hm::mat Pm = hm::symmetrised(P + i * n * n, n);
         std::copy(Pm.begin(), Pm.end(), Pall.begin() + i * n * n);
     }
     if (sq_struct && !h->batched_alloc) {   // the stage-wise QP needs no condensed operand: terminal weights and the flag words only
         HIP_TRY(h, h->bP.once(b * n * n));
         HIP_TRY(h, h->bFlag.once(b));
-    } else {
-        const int rc_ = ensure_batched_alloc(h);
-        if (rc_ != ALMPC_OK) return rc_;
-    }
+    } else
+        ALMPC_TRY(ensure_batched_alloc(h));
     almpc_handle::Sqp& q = h->sqp;
     const int keep_rule = q.step_rule, keep_structured = q.structured_qp, keep_hessian = q.hessian, keep_rows = q.row_mult;
     q = almpc_handle::Sqp();
@@ -3200,8 +3207,7 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
     HIP_TRY(h, hipMemset(q.bad, 0, b * sizeof(int)));
     HIP_TRY(h, h->dXref.alloc(b * (size_t)n * (N + 1))); HIP_TRY(h, h->dUref.alloc(b * nz));
     HIP_TRY(h, hipMemcpy(h->bP, Pall.data(), Pall.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->dUmin, umin, m * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->dUmax, umax, m * sizeof(double), hipMemcpyHostToDevice));
+    ALMPC_TRY(upload_input_box(h, umin, umax));
     if (h->batched_alloc) {   // the condensed route (also kept ready when a condensed handle sends its QPs to k_riccati after an earlier design)
         HIP_TRY(h, h->bQ.once(b * nz));
         HIP_TRY(h, h->dFS.alloc(b * nz)); HIP_TRY(h, h->dV0S.alloc(b * nz)); h->dCold.reset(); h->cold_ref = false;
@@ -3219,17 +3225,13 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
     h->rho = rho; h->sigma = sigma;
     // state rows (almpc_set_state_box: the box of .../fnn/mpc_modeler_implementation_fnn.jl:146-153; terminal equality): one
     // constraint-space matrix per instance, rebuilt with every iteration's linearisation
-    const double* bxmin = h->boxmin.empty() ? nullptr : h->boxmin.data();
-    const double* bxmax = h->boxmax.empty() ? nullptr : h->boxmax.data();
+    const StateBox box = state_box(h);
     if (q.structured_qp) {   // no constraint-space matrix: the state rows are coordinates of the stage-wise trajectory (k_sdual)
-        const int rc_ = setup_state_rows(h, nullptr, nullptr, true);
-        if (rc_ != ALMPC_OK) return rc_;
-        h->has_box = bxmin ? 1 : 0;
-        h->mc = bxmin ? N * n : (h->terminal_eq ? n : 0);
-    } else {
-        const int rc_ = setup_state_rows(h, bxmin, bxmax, true);
-        if (rc_ != ALMPC_OK) return rc_;
-    }
+        ALMPC_TRY(setup_state_rows(h, nullptr, nullptr, true));
+        h->has_box = box.min ? 1 : 0;
+        h->mc = box.min ? N * n : (h->terminal_eq ? n : 0);
+    } else
+        ALMPC_TRY(setup_state_rows(h, box.min, box.max, true));
     h->xref_stride = (long)n * (N + 1); h->uref_stride = nz; h->fS_stride = nz;
     h->designed = false;  // becomes true with the first iteration's design
     h->batched = true; h->ltv = true;
@@ -3238,23 +3240,16 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
     if (h->fallback || q.structured_qp) {
         // stage-wise QP of an iteration: k_sgains (stage records, defects' value-function terms, cost terms) + k_sdual; behind it, for
         // an input box without S, the primal Riccati active set
-        if (sdual_shape_ok(n, m, N, q.useS != 0)) {
-            const int rc_ = sdual_setup_batched(h, Qm, Rm, q.useS ? &Sm : nullptr, false, bxmin, bxmax, h->terminal_eq != 0);
-            if (rc_ != ALMPC_OK && (h->fallback == 1 || q.structured_qp)) return rc_;
-            if (rc_ == ALMPC_OK) {
-                almpc_handle::Sd& sd = h->sd;
-                const size_t TP = (size_t)sdual_tp(sd.NT, sd.MC, N);
-                HIP_TRY(h, sd.base.grow(b * TP));
-                sd.has_base = true; sd.base_stride = (long)TP;
-                HIP_TRY(h, sd.pc.alloc(b * N * sd.NT)); HIP_TRY(h, sd.ct.alloc(b * N * sd.NT));
-                sd.sqp = true;
-            }
-        } else if ((q.structured_qp || h->fallback == 1) && (h->mc > 0 || q.useS))
-            return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_setup: state rows / input-rate weight in the stage-wise QP need n + m <= 48 and (N + 1)(n + m) <= 4096");
-        if (riccati_shape_ok(h) && h->mc == 0 && !q.useS) {
-            const int rc_ = riccati_weights(h, Qm, Rm, nullptr);
-            if (rc_ != ALMPC_OK) return rc_;
-        } else if (!h->sd.ready && q.structured_qp)
+        ALMPC_TRY(setup_redo_solvers(h, nullptr, false, Qm, Rm, q.useS ? &Sm : nullptr, box, h->fallback == 1 || q.structured_qp,
+                                     "sqp_fnn_setup: state rows / input-rate weight in the stage-wise QP need n + m <= 48 and (N + 1)(n + m) <= 4096"));
+        if (h->sd.ready) {
+            almpc_handle::Sd& sd = h->sd;
+            const size_t TP = (size_t)sdual_tp(sd.NT, sd.MC, N);
+            HIP_TRY(h, sd.base.grow(b * TP));
+            sd.has_base = true; sd.base_stride = (long)TP;
+            HIP_TRY(h, sd.pc.alloc(b * N * sd.NT)); HIP_TRY(h, sd.ct.alloc(b * N * sd.NT));
+            sd.sqp = true;
+        } else if (q.structured_qp && !primal_redo_covers(h, h->mc > 0, q.useS != 0))
             return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_setup: the shape is outside both stage-wise QP solvers");
     }
     q.ready = true; q.started = false;
@@ -3319,7 +3314,7 @@ int almpc_sqp_fnn_start(almpc_handle* h, const double* x0, const double* u_guess
     hipLaunchKernelGGL(roll, dim3((unsigned)b), dim3(256), l, st, rp);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemsetAsync(q.bad, 0, b * sizeof(int), st));
-    { const int rc_ = sqp_rows_buffer(h); if (rc_ != ALMPC_OK) return rc_; }
+    ALMPC_TRY(sqp_rows_buffer(h));
     if (q.smu) HIP_TRY(h, hipMemsetAsync(q.smu, 0, b * N * (size_t)n * sizeof(double), st));   // (no QP solved yet)
     {
         std::vector<double> d0(4 * b, 0.0);
@@ -3440,9 +3435,8 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
     const DesignStrides ds = batched_strides(h, q.sP != 0);
     const size_t step_lds = sqp_step_lds_doubles(n, m, N) * sizeof(double);
     if (step_lds > 64 * 1024) HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sqp_step), (size_t)(step_lds)));
-    FnnParams fp;
-    fp.n = n; fp.m = m; fp.H = q.H; fp.L = q.L; fp.act = q.act; fp.batch = (int)(b * N);
-    fp.W_in = q.W_in; fp.W_h = q.W_h; fp.b_h = q.b_h; fp.W_out = q.W_out;
+    FnnParams fp = fnn_params(h, q);
+    fp.batch = (int)(b * N);   // (every stage of every instance is a point)
     fp.x = h->dXref; fp.u = h->dUref; fp.ppi = N; fp.xs_group = (long)n * (N + 1); fp.us_group = nz;
     fp.A = q.A; fp.B = q.B; fp.f = q.fval;
     SqpParams sp;
@@ -3477,7 +3471,7 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
         if (q.structured_qp)
             return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp row multipliers: the condensed QP route only (the stage-wise route of "
                                                   "almpc_sqp_fnn_set_structured / ALMPC_FLAG_STRUCTURED does not hand them out)");
-        { const int rc_ = sqp_rows_buffer(h); if (rc_ != ALMPC_OK) return rc_; }
+        ALMPC_TRY(sqp_rows_buffer(h));
         rows.mu = q.smu; rows.done = sv ? sv->done : nullptr; rows.mer = q.step_rule ? q.mer : nullptr;
     }
     bool all_done = false;
@@ -3490,7 +3484,7 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
     SqpExactParams xp;
     size_t hess_lds = 0, exact_lds = 0;
     if (exact) {
-        { const int rc_ = sqp_exact_check(h); if (rc_ != ALMPC_OK) return rc_; }
+        ALMPC_TRY(sqp_exact_check(h));
         HIP_TRY(h, q.lam.once(b * N * (size_t)n)); HIP_TRY(h, q.Wlag.once(b * N * (size_t)(n + m) * (n + m)));
         if (!sv) {   // the multipliers only: the walk of k_sqp_kkt without the test
             kp.n = n; kp.m = m; kp.N = N; kp.nz = nz; kp.useS = q.useS;
@@ -3746,7 +3740,7 @@ int almpc_set_reference(almpc_handle* h, const double* xref, const double* uref,
         HIP_TRY(h, hipMemcpy(h->dUref, uref, cnt * us * sizeof(double), hipMemcpyHostToDevice));
         h->xref_stride = per_instance ? (long)xs : 0;
         h->uref_stride = per_instance ? (long)us : 0;
-        { const int rc_ = sdual_update_base(h, uref, cnt); if (rc_ != ALMPC_OK) return rc_; }
+        ALMPC_TRY(sdual_update_base(h, uref, cnt));
         h->designed = true;
         return ALMPC_OK;
     }
@@ -3824,8 +3818,8 @@ int almpc_set_reference(almpc_handle* h, const double* xref, const double* uref,
     h->xref_stride = per_instance ? (long)xs : 0;
     h->uref_stride = per_instance ? (long)us : 0;
     h->fS_stride = (per_instance || h->batched) ? (long)us : 0;
-    { const int rc_ = sdual_update_base(h, uref, cnt); if (rc_ != ALMPC_OK) return rc_; }
-    { const int rc_ = build_s0_basis(h); if (rc_ != ALMPC_OK) return rc_; }   // (v0S has changed)
+    ALMPC_TRY(sdual_update_base(h, uref, cnt));
+    ALMPC_TRY(build_s0_basis(h));   // (v0S has changed)
     h->designed = true;
     return ALMPC_OK;
 }
@@ -3868,7 +3862,7 @@ int almpc_get_results(almpc_handle* h, double* x, double* e_x, double* u, double
     if (!h) return ALMPC_ERR_INVALID;
     if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, "get_results before design");
     HIP_TRY(h, hipSetDevice(h->device));
-    { const int rc_ = wait_and_settle(h, true); if (rc_ != ALMPC_OK) return rc_; }
+    ALMPC_TRY(wait_and_settle(h, true));
     const size_t b = (size_t)h->batch, xs = (size_t)h->n * (h->N + 1), us = (size_t)h->nz;
     if (x) HIP_TRY(h, hipMemcpy(x, h->dX, b * xs * sizeof(double), hipMemcpyDeviceToHost));
     if (e_x) HIP_TRY(h, hipMemcpy(e_x, h->dEx, b * xs * sizeof(double), hipMemcpyDeviceToHost));
@@ -4051,8 +4045,7 @@ int almpc_dare_batched(int device_id, int n, int m, int batch, const double* A_b
     if (hipGetDeviceCount(&count) != hipSuccess || device_id < 0 || device_id >= count) return ALMPC_ERR_NO_DEVICE;
     {
         const char* why = "";
-        const int rc_ = dare_device_check(n, m, hm::mat(R, R + (size_t)m * m), false, &why);
-        if (rc_ != ALMPC_OK) return rc_;
+        ALMPC_TRY(dare_device_check(n, m, hm::mat(R, R + (size_t)m * m), false, &why));
     }
     if (hipSetDevice(device_id) != hipSuccess) return ALMPC_ERR_HIP;
     using Tight = DevBuf<double, Mem::DeviceTight>;
@@ -4196,7 +4189,7 @@ int almpc_advance_plant(almpc_handle* h) {
     if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, "advance_plant before design");
     if (h->batched) return fail(h, ALMPC_ERR_UNSUPPORTED, "advance_plant: per-instance models have no shared plant (advance the states on the caller's side)");
     HIP_TRY(h, hipSetDevice(h->device));
-    { const int rc_ = enqueue_gated_redo(h); if (rc_ != ALMPC_OK) return rc_; }   // the plant must not be driven by an undecided instance's iterate
+    ALMPC_TRY(enqueue_gated_redo(h));   // the plant must not be driven by an undecided instance's iterate
     const int per_block = 256 / h->n;
     const double* x0_in = h->dX0;
     const int x0_slot = h->io.x0_slot;
@@ -4292,20 +4285,20 @@ int sens_launch(almpc_handle* h, SensParams p) {
 extern "C" {
 
 int almpc_sensitivity(almpc_handle* h, uint32_t want, double act_tol) {
-    { const int rc_ = sens_check(h, "sensitivity"); if (rc_ != ALMPC_OK) return rc_; }
+    ALMPC_TRY(sens_check(h, "sensitivity"));
     if (!want || (want & ~(ALMPC_SENS_K0 | ALMPC_SENS_DU | ALMPC_SENS_DX))) return fail(h, ALMPC_ERR_INVALID, "sensitivity: want must be a mask of ALMPC_SENS_*");
     HIP_TRY(h, hipSetDevice(h->device));
-    { const int rc_ = wait_and_settle(h); if (rc_ != ALMPC_OK) return rc_; }   // (a synchronous look: redone instances take part)
+    ALMPC_TRY(wait_and_settle(h));   // (a synchronous look: redone instances take part)
     const size_t b = (size_t)h->batch, n = (size_t)h->n;
     h->sens.have = 0;
     SensParams p;
-    { const int rc_ = sens_params(h, act_tol, p); if (rc_ != ALMPC_OK) return rc_; }
+    ALMPC_TRY(sens_params(h, act_tol, p));
     HIP_TRY(h, h->sens.rows.grow(b));
     if (want & ALMPC_SENS_K0) HIP_TRY(h, h->sens.K0.grow(b * n * h->m));
     if (want & (ALMPC_SENS_DU | ALMPC_SENS_DX)) HIP_TRY(h, h->sens.dU.grow(b * n * h->nz));   // (dX is rolled out from dU)
     if (want & ALMPC_SENS_DX) HIP_TRY(h, h->sens.dX.grow(b * n * (h->N + 1) * n));
     p.want = want; p.K0 = h->sens.K0; p.dU = h->sens.dU; p.rows = h->sens.rows;
-    { const int rc_ = sens_launch<false>(h, p); if (rc_ != ALMPC_OK) return rc_; }
+    ALMPC_TRY(sens_launch<false>(h, p));
     if (want & ALMPC_SENS_DX) {
         SensDxParams q;
         q.n = h->n; q.m = h->m; q.N = h->N; q.nz = h->nz; q.batch = h->batch;
@@ -4345,13 +4338,13 @@ int almpc_device_sensitivity(almpc_handle* h, const double** d_K0, const double*
 }
 
 int almpc_sensitivity_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows) {
-    { const int rc_ = sens_check(h, "sensitivity_vjp"); if (rc_ != ALMPC_OK) return rc_; }
+    ALMPC_TRY(sens_check(h, "sensitivity_vjp"));
     if (!g_u || !g_x0) return fail(h, ALMPC_ERR_INVALID, "sensitivity_vjp: null g_u or g_x0");
     HIP_TRY(h, hipSetDevice(h->device));
-    { const int rc_ = wait_and_settle(h); if (rc_ != ALMPC_OK) return rc_; }
+    ALMPC_TRY(wait_and_settle(h));
     const size_t b = (size_t)h->batch, n = (size_t)h->n, xs = n * (h->N + 1);
     SensParams p;
-    { const int rc_ = sens_params(h, act_tol, p); if (rc_ != ALMPC_OK) return rc_; }
+    ALMPC_TRY(sens_params(h, act_tol, p));
     HIP_TRY(h, h->sens.vrows.grow(b)); HIP_TRY(h, h->sens.gx0.grow(b * n)); HIP_TRY(h, h->sens.gu.grow(b * h->nz));
     HIP_TRY(h, hipMemcpyAsync(h->sens.gu, g_u, b * h->nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (g_x) {
@@ -4359,7 +4352,7 @@ int almpc_sensitivity_vjp(almpc_handle* h, const double* g_u, const double* g_x,
         HIP_TRY(h, hipMemcpyAsync(h->sens.gx, g_x, b * xs * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
     p.g_u = h->sens.gu; p.g_x = g_x ? h->sens.gx.get() : nullptr; p.g_x0 = h->sens.gx0; p.rows = h->sens.vrows;
-    { const int rc_ = sens_launch<true>(h, p); if (rc_ != ALMPC_OK) return rc_; }
+    ALMPC_TRY(sens_launch<true>(h, p));
     HIP_TRY(h, hipMemcpyAsync(g_x0, h->sens.gx0, b * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (rows) HIP_TRY(h, hipMemcpyAsync(rows, h->sens.vrows, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, stream_wait_polling(h));

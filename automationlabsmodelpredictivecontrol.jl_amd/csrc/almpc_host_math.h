@@ -66,6 +66,18 @@ inline bool lu_solve(mat A, mat& B, int n, int c) {
     return true;
 }
 
+// The symmetric part of the k x k matrix M (null: zeros): the diagonal as it is, 0.5 (M_ij + M_ji) off it.  A weight enters the cost
+// as a quadratic form, so only this part counts.
+inline mat symmetrised(const double* M, int k) {
+    mat o((size_t)k * k, 0.0);
+    if (!M) return o;
+    for (int j = 0; j < k; ++j) {
+        o[(size_t)j * k + j] = M[(size_t)j * k + j];
+        for (int i = 0; i < j; ++i) o[(size_t)j * k + i] = o[(size_t)i * k + j] = 0.5 * (M[(size_t)j * k + i] + M[(size_t)i * k + j]);
+    }
+    return o;
+}
+
 inline double amax(const mat& A) {  // max-abs norm (no squares: a diverging iterate must not overflow the test that rejects it)
     double s = 0.0;
     for (double v : A) s = std::fmax(s, std::fabs(v));

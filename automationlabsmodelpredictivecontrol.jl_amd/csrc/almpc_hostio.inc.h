@@ -106,7 +106,7 @@ extern "C" {
 // there and passes the same pointer on: no staging copy.
 int almpc_x0_staging(almpc_handle* h, double** x0_slot) {
     if (!h || !x0_slot) return h ? fail(h, ALMPC_ERR_INVALID, "x0_staging: null pointer") : ALMPC_ERR_INVALID;
-    { const int rc = io_init(h); if (rc != ALMPC_OK) return rc; }
+    ALMPC_TRY(io_init(h));
     almpc_handle::Io& io = h->io;
     const int s = (int)(io.x0_count % almpc_handle::IO_DEPTH);
     if (io.used_pending[s]) {   // the slot is written by the caller from here on: the last step that read it must have finished
@@ -120,7 +120,7 @@ int almpc_x0_staging(almpc_handle* h, double** x0_slot) {
 
 int almpc_update_initialization_async(almpc_handle* h, const double* x0) {
     if (!h || !x0) return h ? fail(h, ALMPC_ERR_INVALID, "update_initialization_async: null x0") : ALMPC_ERR_INVALID;
-    { const int rc = io_init(h); if (rc != ALMPC_OK) return rc; }
+    ALMPC_TRY(io_init(h));
     almpc_handle::Io& io = h->io;
     const int s = (int)(io.x0_count % almpc_handle::IO_DEPTH);
     // the slot is free once the last step that read it has finished (normally long ago: IO_DEPTH - 1 steps may be in flight)
@@ -150,12 +150,12 @@ int almpc_get_results_async(almpc_handle* h, uint32_t want) {
     if (!h) return ALMPC_ERR_INVALID;
     if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, "get_results_async before design");
     if (want == 0 || (want & ~(uint32_t)ALMPC_WANT_ALL)) return fail(h, ALMPC_ERR_INVALID, "get_results_async: want must be a non-empty mask of ALMPC_WANT_*");
-    { const int rc = io_init(h); if (rc != ALMPC_OK) return rc; }
+    ALMPC_TRY(io_init(h));
     almpc_handle::Io& io = h->io;
     HIP_TRY(h, hipSetDevice(h->device));
     // "solution or verdict" on the ticket path too: what the step's finish left undecided is redone on the stream before the results
     // are packed (gated launches: nothing runs unless the step left something)
-    { const int rc = enqueue_gated_redo(h); if (rc != ALMPC_OK) return rc; }
+    ALMPC_TRY(enqueue_gated_redo(h));
     const long t = io.next_ticket;
     const int s = (int)(t % almpc_handle::IO_DEPTH);
     const size_t b = (size_t)h->batch, xs = b * h->n * (h->N + 1), us = b * h->nz;
@@ -256,8 +256,7 @@ int almpc_get_first_input(almpc_handle* h, double* u0) {
     if (!h || !u0) return h ? fail(h, ALMPC_ERR_INVALID, "get_first_input: null u0") : ALMPC_ERR_INVALID;
     if (h->redo.lazy_pending) {   // (synchronous getter: settle a lazily deferred redo before the first inputs are packed)
         HIP_TRY(h, hipSetDevice(h->device));
-        const int rc_ = wait_and_settle(h, true);
-        if (rc_ != ALMPC_OK) return rc_;
+        ALMPC_TRY(wait_and_settle(h, true));
     }
     const int t = almpc_get_results_async(h, ALMPC_WANT_FIRST_INPUT);
     if (t < 0) return t;

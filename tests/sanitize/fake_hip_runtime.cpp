@@ -6,6 +6,9 @@
 // The byte size of every hipMalloc and of every hipHostMalloc that succeeded is kept; fake_hip_dump_allocs(path) writes both lists,
 // sorted (tests/golden/host_alloc_sizes.txt).  fake_hip_fail_alloc_at(k): the k-th hipMalloc / hipHostMalloc from now on returns
 // hipErrorOutOfMemory, once (k = 0: none); returns what was left of the last such count (0: it has fired, or none was set).
+// fake_hip_record_uploads(1) (off by default): every host-to-device hipMemcpy(Async) is kept as (bytes, 64-bit FNV-1a of the payload) and
+// every hipMemset(Async) as (bytes, value); fake_hip_print_uploads(f) writes what was kept since the last call, sorted (f null:
+// writes nothing), and forgets it.
 #include <hip/hip_runtime_api.h>
 
 #include <cxxabi.h>
@@ -17,6 +20,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -32,6 +36,8 @@ struct State {
     FILE* trace = nullptr;
     std::vector<size_t> device_bytes, pinned_bytes;
     int fail_in = 0;
+    bool record_uploads = false;
+    std::vector<std::pair<size_t, unsigned long long>> copies, sets;
 };
 State& S() { static State s; return s; }
 
@@ -42,6 +48,23 @@ hipError_t fake_alloc(void** p, size_t n, std::vector<size_t> State::*sizes) {
     *p = std::calloc(n ? n : 1, 1);
     if (!*p) return hipErrorOutOfMemory;
     (g.*sizes).push_back(n);
+    return hipSuccess;
+}
+
+hipError_t fake_copy(void* d, const void* s, size_t n, hipMemcpyKind kind) {
+    std::memmove(d, s, n);
+    State& g = S(); std::lock_guard<std::mutex> l(g.mu);
+    if (g.record_uploads && kind == hipMemcpyHostToDevice) {
+        unsigned long long hash = 14695981039346656037ull;
+        for (size_t i = 0; i < n; ++i) hash = (hash ^ static_cast<const unsigned char*>(s)[i]) * 1099511628211ull;
+        g.copies.emplace_back(n, hash);
+    }
+    return hipSuccess;
+}
+hipError_t fake_set(void* d, int v, size_t n) {
+    std::memset(d, v, n);
+    State& g = S(); std::lock_guard<std::mutex> l(g.mu);
+    if (g.record_uploads) g.sets.emplace_back(n, (unsigned long long)(unsigned char)v);
     return hipSuccess;
 }
 }
@@ -77,6 +100,16 @@ int fake_hip_dump_allocs(const char* path) {
     return std::fclose(f) ? 1 : 0;
 }
 
+void fake_hip_record_uploads(int on) { State& g = S(); std::lock_guard<std::mutex> l(g.mu); g.record_uploads = on != 0; }
+void fake_hip_print_uploads(FILE* f) {
+    State& g = S(); std::lock_guard<std::mutex> l(g.mu);
+    std::sort(g.copies.begin(), g.copies.end());
+    std::sort(g.sets.begin(), g.sets.end());
+    for (const auto& c : g.copies) if (f) std::fprintf(f, "  upload %zu %016llx\n", c.first, c.second);
+    for (const auto& c : g.sets) if (f) std::fprintf(f, "  memset %zu %llu\n", c.first, c.second);
+    g.copies.clear(); g.sets.clear();
+}
+
 hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
 hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
@@ -99,10 +132,10 @@ hipError_t hipFree(void* p) { std::free(p); return hipSuccess; }
 hipError_t hipHostMalloc(void** p, size_t n, unsigned) { return fake_alloc(p, n, &State::pinned_bytes); }
 hipError_t hipHostFree(void* p) { std::free(p); return hipSuccess; }
 hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) { *d = h; return hipSuccess; }
-hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { std::memmove(d, s, n); return hipSuccess; }
-hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { std::memmove(d, s, n); return hipSuccess; }
-hipError_t hipMemset(void* d, int v, size_t n) { std::memset(d, v, n); return hipSuccess; }
-hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { std::memset(d, v, n); return hipSuccess; }
+hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind k) { return fake_copy(d, s, n, k); }
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t) { return fake_copy(d, s, n, k); }
+hipError_t hipMemset(void* d, int v, size_t n) { return fake_set(d, v, n); }
+hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { return fake_set(d, v, n); }
 
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
     *s = reinterpret_cast<hipStream_t>(std::malloc(8));

@@ -11,8 +11,12 @@
 // With a path argument the byte sizes of all device and pinned allocations of the run go to <path>.allocs at the end, sorted
 // (tests/golden/host_alloc_sizes.txt).  With "alloc-failures" as the second argument nothing of the above runs: every entry point that
 // allocates is called with its k-th allocation failing, k = 1, 2, ... until it gets through (alloc_failures below).
+// With "setups" as the second argument the design and setup entry points are walked on the routes the plain run does not reach
+// (setups below): every call's return line and, sorted, what it uploaded and set on the device go to stdout; with the launch trace and
+// the allocation sizes they are what tests/golden/host_setups.txt pins.
 #include "../../include/almpc.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -25,6 +29,8 @@ extern "C" int fake_hip_trace_to(const char* path);
 extern "C" void fake_hip_trace_close();
 extern "C" int fake_hip_fail_alloc_at(int k);
 extern "C" int fake_hip_dump_allocs(const char* path);
+extern "C" void fake_hip_record_uploads(int on);
+extern "C" void fake_hip_print_uploads(FILE* f);
 extern char** environ;
 
 #define CK(call)                                                                                             \
@@ -145,11 +151,15 @@ static int alloc_failures() {
     if (walk("almpc_design_shared", n, m, N, batch, 0, fb, box_and_eq, [&](almpc_handle* h) {   // state box + terminal equality: the projection's temporary
             return almpc_design_shared(h, p.A.data(), p.B.data(), p.Q.data(), p.R.data(), p.S.data(), nullptr, p.umin.data(), p.umax.data(), p.xmin.data(), p.xmax.data(), 0.1, 1e-6);
         })) return 1;
+    if (walk("almpc_design_shared (structured)", n, m, N, batch, ALMPC_FLAG_STRUCTURED, fb, box_and_eq, [&](almpc_handle* h) {
+            return almpc_design_shared(h, p.A.data(), p.B.data(), p.Q.data(), p.R.data(), p.S.data(), nullptr, p.umin.data(), p.umax.data(), p.xmin.data(), p.xmax.data(), 0.1, 1e-6);
+        })) return 1;
     const auto design_batched = [&](almpc_handle* h) {
         return almpc_design_batched(h, Ab.data(), Bb.data(), p.Q.data(), p.R.data(), p.S.data(), nullptr, 0, p.umin.data(), p.umax.data(), 0.1, 1e-6);
     };
     const auto state_box = [&](almpc_handle* h) { return almpc_set_state_box(h, p.xmin.data(), p.xmax.data()); };
     if (walk("almpc_design_batched", n, m, N, batch, 0, fb, state_box, design_batched)) return 1;
+    if (walk("almpc_design_batched (structured)", n, m, N, batch, ALMPC_FLAG_STRUCTURED, fb, state_box, design_batched)) return 1;
     {
         std::vector<double> Aall((size_t)batch * N * n * n), Ball((size_t)batch * N * n * m), call((size_t)batch * N * n, 0.01),
             xbar((size_t)batch * (N + 1) * n, 0.2), ubar((size_t)batch * N * m, 0.1);
@@ -184,6 +194,243 @@ static int alloc_failures() {
     return 0;
 }
 
+// One line per call, `what -> code (almpc_last_error)`, and behind a setup call what it copied to and set on the device, sorted (a step's
+// own copies are dropped).  Whatever a path returns is its pin: nothing here stops at an error code.
+static int show(almpc_handle* h, const char* what, int rc, bool uploads = true) {
+    std::printf("%s -> %d (%s)\n", what, rc, rc != ALMPC_OK && h ? almpc_last_error(h) : "");
+    fake_hip_print_uploads(uploads ? stdout : nullptr);
+    return rc;
+}
+
+static int setups() {
+    const int n = 4, m = 2, N = 12, batch = 13, Hn = 8, L = 2;
+    const Plant p = chain(n, m);
+    fake_hip_record_uploads(1);
+    std::vector<double> xr((size_t)n * (N + 1), 0.1), ur((size_t)m * N, 0.05), x0((size_t)batch * n, 0.25);
+    for (int k = 0; k < N; ++k) ur[(size_t)k * m] = 0.01 * k;
+    std::vector<double> Ab((size_t)batch * n * n), Bb((size_t)batch * n * m), P((size_t)n * n, 0.0), Pb((size_t)batch * n * n, 0.0);
+    for (int i = 0; i < batch; ++i) {
+        for (size_t t = 0; t < p.A.size(); ++t) Ab[(size_t)i * n * n + t] = p.A[t];
+        for (size_t t = 0; t < p.B.size(); ++t) Bb[(size_t)i * n * m + t] = p.B[t] * (1.0 + 0.01 * i);
+        for (int j = 0; j < n; ++j) Pb[(size_t)i * n * n + (size_t)j * n + j] = 150.0 + i;
+        Pb[(size_t)i * n * n + 1] = 3.0;   // (not symmetric: what a path does with that is part of its pin)
+    }
+    for (int j = 0; j < n; ++j) P[(size_t)j * n + j] = 150.0;
+    P[1] = 3.0;
+    Plant ps = p;   // weights that are not symmetric
+    ps.Q[1] = 2.0; ps.R[1] = 0.02; ps.S[1] = 0.5;
+    Plant pd = p;   // ... for the designs that take their terminal weight from a DARE, which wants Q and R symmetric: S only
+    pd.S[1] = 0.5;
+    std::vector<double> W_in((size_t)Hn * (n + m), 0.05), W_h((size_t)L * Hn * Hn, 0.02), b_h((size_t)L * Hn, 0.01), W_out((size_t)n * Hn, 0.1);
+    std::vector<double> Wd_h((size_t)Hn * Hn * L * (L + 1) / 2, 0.02), Wd_out((size_t)n * Hn * (L + 1), 0.1);   // DenseNet: growing blocks
+    for (size_t t = 0; t < W_in.size(); ++t) W_in[t] += 0.001 * t;
+    std::vector<double> Aall((size_t)batch * N * n * n), Ball((size_t)batch * N * n * m), call((size_t)batch * N * n, 0.01),
+        xbar((size_t)batch * (N + 1) * n, 0.2), ubar((size_t)batch * N * m, 0.1);
+    for (size_t i = 0; i < (size_t)batch * N; ++i) {
+        for (size_t t = 0; t < p.A.size(); ++t) Aall[i * n * n + t] = p.A[t];
+        for (size_t t = 0; t < p.B.size(); ++t) Ball[i * n * m + t] = p.B[t];
+    }
+    almpc_opts cold, warm;
+    almpc_default_opts(&cold);
+    almpc_default_opts(&warm);
+    warm.warm_start = 1;
+    almpc_handle* h = nullptr;
+    const auto open = [&](const char* title, uint32_t flags, bool box) {
+        std::printf("---- %s\n", title);
+        if (almpc_create(&h, n, m, N, batch, 0, flags) != ALMPC_OK) return 1;
+        return box ? show(h, "set_state_box", almpc_set_state_box(h, p.xmin.data(), p.xmax.data())) : 0;
+    };
+    const auto close = [&] { almpc_destroy(h); h = nullptr; };
+    const auto step = [&] {
+        show(h, "  update_initialization", almpc_update_initialization(h, x0.data()), false);
+        show(h, "  calculate", almpc_calculate(h, &cold), false);
+    };
+    const auto relin_steps = [&] {
+        show(h, "  update_initialization", almpc_update_initialization(h, x0.data()), false);
+        show(h, "  relin_fnn_step cold", almpc_relin_fnn_step(h, &cold), false);
+        show(h, "  relin_fnn_step warm", almpc_relin_fnn_step(h, &warm), false);
+    };
+    const auto sqp_iterate = [&] {
+        show(h, "  sqp_fnn_start", almpc_sqp_fnn_start(h, x0.data(), nullptr), false);
+        double si = 0.0, di = 0.0;
+        show(h, "  sqp_fnn_iterate", almpc_sqp_fnn_iterate(h, 1, 1.0, nullptr, &si, &di), false);
+    };
+    const auto batched = [&](const Plant& w_, const double* S, const double* Pw, int per) {
+        const Plant& w = &w_ == &ps && !Pw ? pd : w_;
+        return almpc_design_batched(h, Ab.data(), Bb.data(), w.Q.data(), w.R.data(), S, Pw, per, w.umin.data(), w.umax.data(), 0.1, 1e-6);
+    };
+    const auto shared = [&](const Plant& w_, const double* S, const double* Pw, const double* xmin, const double* xmax) {
+        const Plant& w = &w_ == &ps && !Pw ? pd : w_;
+        return almpc_design_shared(h, w.A.data(), w.B.data(), w.Q.data(), w.R.data(), S, Pw, w.umin.data(), w.umax.data(), xmin, xmax, 0.1, 1e-6);
+    };
+    const auto relin = [&](const Plant& w, int act) {
+        return almpc_relin_fnn_setup(h, Hn, L, act, W_in.data(), W_h.data(), b_h.data(), W_out.data(), xr.data(), ur.data(), w.Q.data(), w.R.data(), w.S.data(),
+                                     P.data(), w.umin.data(), w.umax.data(), 0.1, 1e-6);
+    };
+    const auto sqp = [&](const Plant& w, const double* S, int act) {
+        return almpc_sqp_fnn_setup(h, Hn, L, act, W_in.data(), W_h.data(), b_h.data(), W_out.data(), xr.data(), ur.data(), w.Q.data(), w.R.data(), S, Pb.data(), 1,
+                                   w.umin.data(), w.umax.data(), 0.1, 1e-6);
+    };
+    const auto ltv = [&](const Plant& w) {
+        return almpc_design_ltv(h, Aall.data(), Ball.data(), call.data(), xbar.data(), ubar.data(), xr.data(), ur.data(), w.Q.data(), w.R.data(), w.S.data(), P.data(), 0,
+                                w.umin.data(), w.umax.data(), 0.1, 1e-6);
+    };
+    // ---- the condensed designs the plain run walks, here for what they upload
+    if (open("condensed: design_shared, input box; then state box + terminal equality + S", 0, false)) return 1;
+    show(h, "design_shared", shared(ps, nullptr, nullptr, nullptr, nullptr)); step();
+    show(h, "set_terminal_equality", almpc_set_terminal_equality(h, 1));
+    show(h, "design_shared (box, eq, S, P)", shared(ps, ps.S.data(), P.data(), p.xmin.data(), p.xmax.data())); step();
+    close();
+    for (const bool box : {false, true}) {
+        if (open(box ? "condensed: design_batched, state box + S" : "condensed: design_batched, input box", 0, box)) return 1;
+        show(h, "design_batched P null", batched(ps, box ? ps.S.data() : nullptr, nullptr, 0)); step();
+        show(h, "design_batched P shared", batched(ps, box ? ps.S.data() : nullptr, P.data(), 0)); step();
+        show(h, "design_batched P per instance", batched(ps, box ? ps.S.data() : nullptr, Pb.data(), 1)); step();
+        close();
+    }
+    for (const bool box : {false, true}) {
+        if (open(box ? "condensed: relin_fnn_setup, state box" : "condensed: relin_fnn_setup", 0, box)) return 1;
+        show(h, "relin_fnn_setup", relin(ps, 1)); relin_steps();
+        show(h, "sqp_fnn_setup behind it", sqp(ps, ps.S.data(), 1)); sqp_iterate();
+        close();
+    }
+    // ---- structured handle, almpc_design_batched
+    for (const bool box : {false, true})
+        for (int pk = 0; pk < 3; ++pk) {
+            if (open(box ? "structured: design_batched, state box + S" : "structured: design_batched, input box", ALMPC_FLAG_STRUCTURED, box)) return 1;
+            show(h, pk == 0 ? "design_batched P null" : (pk == 1 ? "design_batched P shared" : "design_batched P per instance"),
+                 batched(ps, box ? ps.S.data() : nullptr, pk == 0 ? nullptr : (pk == 1 ? P.data() : Pb.data()), pk == 2));
+            step();
+            close();
+        }
+    // ---- structured handle, almpc_design_shared (state box + S), almpc_relin_fnn_setup
+    if (open("structured: design_shared, state box + S", ALMPC_FLAG_STRUCTURED, false)) return 1;
+    show(h, "design_shared", shared(ps, ps.S.data(), nullptr, p.xmin.data(), p.xmax.data())); step();
+    close();
+    for (const bool box : {false, true}) {
+        if (open(box ? "structured: relin_fnn_setup, state box" : "structured: relin_fnn_setup", ALMPC_FLAG_STRUCTURED, box)) return 1;
+        show(h, "relin_fnn_setup", relin(ps, ALMPC_NET_CODE(1, 2))); relin_steps();
+        close();
+    }
+    // ---- SQP on the structured routes, P per instance
+    if (open("condensed: sqp_fnn_set_structured(1), state box", 0, true)) return 1;
+    show(h, "sqp_fnn_set_structured", almpc_sqp_fnn_set_structured(h, 1));
+    show(h, "sqp_fnn_setup", sqp(ps, ps.S.data(), 1)); sqp_iterate();
+    close();
+    if (open("structured: sqp_fnn_setup", ALMPC_FLAG_STRUCTURED, false)) return 1;
+    show(h, "sqp_fnn_setup", sqp(ps, nullptr, 1)); sqp_iterate();
+    close();
+    // ---- almpc_design_ltv
+    if (open("condensed: design_ltv, state box", 0, true)) return 1;
+    show(h, "design_ltv", ltv(ps)); step();
+    close();
+    if (open("condensed: design_ltv, input box", 0, false)) return 1;
+    show(h, "design_ltv", ltv(ps)); step();
+    close();
+    // ---- DenseNet
+    if (open("condensed: DenseNet", 0, false)) return 1;
+    show(h, "relin_densenet_setup", almpc_relin_densenet_setup(h, Hn, L, 1, W_in.data(), Wd_h.data(), b_h.data(), Wd_out.data(), xr.data(), ur.data(), ps.Q.data(),
+                                                               ps.R.data(), ps.S.data(), P.data(), p.umin.data(), p.umax.data(), 0.1, 1e-6));
+    relin_steps();
+    show(h, "sqp_densenet_setup", almpc_sqp_densenet_setup(h, Hn, L, 1, W_in.data(), Wd_h.data(), b_h.data(), Wd_out.data(), xr.data(), ur.data(), ps.Q.data(),
+                                                           ps.R.data(), nullptr, Pb.data(), 1, p.umin.data(), p.umax.data(), 0.1, 1e-6));
+    sqp_iterate();
+    close();
+    // ---- terminal weights and discretisation on the device
+    for (const uint32_t flags : {0u, (uint32_t)ALMPC_FLAG_STRUCTURED}) {
+        if (open(flags ? "structured: set_terminal_weight(DARE_DEVICE)" : "condensed: set_terminal_weight(DARE_DEVICE)", flags, false)) return 1;
+        show(h, "set_terminal_weight", almpc_set_terminal_weight(h, ALMPC_TERMINAL_DARE_DEVICE));
+        show(h, "design_batched P null", batched(ps, nullptr, nullptr, 0)); step();
+        show(h, "relin_fnn_setup", relin(ps, 1)); relin_steps();
+        close();
+        if (open(flags ? "structured: set_model_time(1, 0.1)" : "condensed: set_model_time(1, 0.1)", flags, false)) return 1;
+        show(h, "set_model_time", almpc_set_model_time(h, ALMPC_MODEL_CONTINUOUS_ZOH, 0.1));
+        show(h, "design_shared", shared(ps, nullptr, nullptr, nullptr, nullptr)); step();
+        show(h, "design_batched P null", batched(ps, nullptr, nullptr, 0)); step();
+        show(h, "relin_fnn_setup", relin(ps, 1)); relin_steps();
+        show(h, "sqp_fnn_setup", sqp(ps, nullptr, 1));
+        show(h, "design_ltv", ltv(ps));
+        close();
+    }
+    // ---- refusals: every entry point with one thing wrong at a time
+    for (const uint32_t flags : {0u, (uint32_t)ALMPC_FLAG_STRUCTURED}) {
+        if (open(flags ? "structured: refusals" : "condensed: refusals", flags, false)) return 1;
+        Plant bad = p;
+        bad.umin[1] = 2.0;   // umin > umax
+        Plant xb = p;
+        xb.xmin[2] = 4.0;    // xmin > xmax
+        const int Hbig = 3000;   // 2 H (1 + n + m) doubles of Jacobian scratch: beyond 160 KB
+        std::vector<double> Wb_in((size_t)Hbig * (n + m), 0.01), Wb_out((size_t)n * Hbig, 0.01);
+        show(h, "design_shared, Q null", almpc_design_shared(h, p.A.data(), p.B.data(), nullptr, p.R.data(), nullptr, nullptr, p.umin.data(), p.umax.data(), nullptr, nullptr, 0.1, 1e-6));
+        show(h, "design_shared, umin > umax", shared(bad, nullptr, nullptr, nullptr, nullptr));
+        show(h, "design_shared, xmin without xmax", shared(p, nullptr, nullptr, p.xmin.data(), nullptr));
+        show(h, "design_shared, xmin > xmax", shared(p, nullptr, nullptr, xb.xmin.data(), xb.xmax.data()));
+        show(h, "design_shared, rho 0", almpc_design_shared(h, p.A.data(), p.B.data(), p.Q.data(), p.R.data(), nullptr, nullptr, p.umin.data(), p.umax.data(), nullptr, nullptr, 0.0, 1e-6));
+        show(h, "design_batched, A null", almpc_design_batched(h, nullptr, Bb.data(), p.Q.data(), p.R.data(), nullptr, nullptr, 0, p.umin.data(), p.umax.data(), 0.1, 1e-6));
+        show(h, "design_batched, umin > umax", batched(bad, nullptr, nullptr, 0));
+        show(h, "design_batched, rho 0", almpc_design_batched(h, Ab.data(), Bb.data(), p.Q.data(), p.R.data(), nullptr, nullptr, 0, p.umin.data(), p.umax.data(), 0.0, 1e-6));
+        show(h, "set_state_box, xmin without xmax", almpc_set_state_box(h, p.xmin.data(), nullptr));
+        show(h, "set_state_box, xmin > xmax", almpc_set_state_box(h, xb.xmin.data(), xb.xmax.data()));
+        show(h, "design_ltv", ltv(p));   // (a structured handle: time-varying designs are refused)
+        show(h, "design_ltv, P null", almpc_design_ltv(h, Aall.data(), Ball.data(), call.data(), xbar.data(), ubar.data(), xr.data(), ur.data(), p.Q.data(), p.R.data(), nullptr,
+                                                       nullptr, 0, p.umin.data(), p.umax.data(), 0.1, 1e-6));
+        show(h, "design_ltv, umin > umax", ltv(bad));
+        show(h, "design_ltv, rho 0", almpc_design_ltv(h, Aall.data(), Ball.data(), call.data(), xbar.data(), ubar.data(), xr.data(), ur.data(), p.Q.data(), p.R.data(), nullptr,
+                                                      P.data(), 0, p.umin.data(), p.umax.data(), 0.0, 1e-6));
+        for (const bool dense : {false, true}) {
+            const auto rs = [&](int Hh, int Ll, int act, const double* Wi, const double* Wo, const double* Pw, const Plant& w, double rho) {
+                return (dense ? almpc_relin_densenet_setup : almpc_relin_fnn_setup)(h, Hh, Ll, act, Wi, dense ? Wd_h.data() : W_h.data(), b_h.data(), Wo, xr.data(), ur.data(),
+                                                                                    w.Q.data(), w.R.data(), w.S.data(), Pw, w.umin.data(), w.umax.data(), rho, 1e-6);
+            };
+            const auto ss = [&](int Hh, int Ll, int act, const double* Wi, const double* Wo, const double* Pw, const Plant& w, double rho) {
+                return (dense ? almpc_sqp_densenet_setup : almpc_sqp_fnn_setup)(h, Hh, Ll, act, Wi, dense ? Wd_h.data() : W_h.data(), b_h.data(), Wo, xr.data(), ur.data(),
+                                                                                w.Q.data(), w.R.data(), w.S.data(), Pw, 0, w.umin.data(), w.umax.data(), rho, 1e-6);
+            };
+            const double* Wo = dense ? Wd_out.data() : W_out.data();
+            std::printf("-- %s\n", dense ? "DenseNet" : "Fnn");
+            show(h, "relin setup, P null", rs(Hn, L, 1, W_in.data(), Wo, nullptr, p, 0.1));
+            show(h, "relin setup, umin > umax", rs(Hn, L, 1, W_in.data(), Wo, P.data(), bad, 0.1));
+            show(h, "relin setup, rho 0", rs(Hn, L, 1, W_in.data(), Wo, P.data(), p, 0.0));
+            show(h, "relin setup, activation 9", rs(Hn, L, 9, W_in.data(), Wo, P.data(), p, 0.1));
+            show(h, "relin setup, network beyond 160 KB", rs(Hbig, 0, 1, Wb_in.data(), Wb_out.data(), P.data(), p, 0.1));
+            show(h, "sqp setup, P null", ss(Hn, L, 1, W_in.data(), Wo, nullptr, p, 0.1));
+            show(h, "sqp setup, umin > umax", ss(Hn, L, 1, W_in.data(), Wo, P.data(), bad, 0.1));
+            show(h, "sqp setup, rho 0", ss(Hn, L, 1, W_in.data(), Wo, P.data(), p, 0.0));
+            show(h, "sqp setup, activation 9", ss(Hn, L, 9, W_in.data(), Wo, P.data(), p, 0.1));
+            show(h, "sqp setup, network beyond 160 KB", ss(Hbig, 0, 1, Wb_in.data(), Wb_out.data(), P.data(), p, 0.1));
+        }
+        close();
+    }
+    {   // shapes: what almpc_create lets through decides which refusals of the setups can be reached at all
+        std::printf("---- refusals by shape\n");
+        std::printf("create n = 65 -> %d\n", almpc_create(&h, 65, 1, 4, 2, 0, 0));
+        std::printf("create structured n = 40 (outside both stage-wise solvers) -> %d\n", almpc_create(&h, 40, 2, 4, 2, 0, ALMPC_FLAG_STRUCTURED));
+        // n + m = 50 with an input-rate weight: outside the stage-wise dual solve, n = 40 outside the primal one
+        const int n2 = 40, m2 = 10, N2 = 8, b2 = 3;
+        const Plant w = chain(n2, m2);
+        std::vector<double> A2((size_t)b2 * n2 * n2), B2((size_t)b2 * n2 * m2);
+        for (int i = 0; i < b2; ++i) {
+            std::copy(w.A.begin(), w.A.end(), A2.begin() + (size_t)i * n2 * n2);
+            std::copy(w.B.begin(), w.B.end(), B2.begin() + (size_t)i * n2 * m2);
+        }
+        if (almpc_create(&h, n2, m2, N2, b2, 0, 0) != ALMPC_OK) return 1;
+        show(h, "set_structured_fallback 1", almpc_set_structured_fallback(h, 1));
+        show(h, "design_shared, S + state box, fallback 1", almpc_design_shared(h, w.A.data(), w.B.data(), w.Q.data(), w.R.data(), w.S.data(), nullptr, w.umin.data(),
+                                                                               w.umax.data(), w.xmin.data(), w.xmax.data(), 0.1, 1e-6));
+        show(h, "design_shared, S, fallback 1", almpc_design_shared(h, w.A.data(), w.B.data(), w.Q.data(), w.R.data(), w.S.data(), nullptr, w.umin.data(), w.umax.data(),
+                                                                   nullptr, nullptr, 0.1, 1e-6));
+        show(h, "design_batched, S, fallback 1", almpc_design_batched(h, A2.data(), B2.data(), w.Q.data(), w.R.data(), w.S.data(), nullptr, 0, w.umin.data(), w.umax.data(), 0.1, 1e-6));
+        close();
+        if (almpc_create(&h, n2, m2, N2, b2, 0, 0) != ALMPC_OK) return 1;   // (the default: the redo wherever the solvers cover the design)
+        show(h, "design_shared, S + state box", almpc_design_shared(h, w.A.data(), w.B.data(), w.Q.data(), w.R.data(), w.S.data(), nullptr, w.umin.data(), w.umax.data(),
+                                                                   w.xmin.data(), w.xmax.data(), 0.1, 1e-6));
+        close();
+    }
+    fake_hip_record_uploads(0);
+    std::printf("setups ok\n");
+    return 0;
+}
+
 int main(int argc, char** argv) {
     {   // every almpc_create below reads the switches: none may come in from the caller's environment
         std::vector<std::string> inherited;
@@ -193,6 +440,11 @@ int main(int argc, char** argv) {
     }
     if (argc > 1 && fake_hip_trace_to(argv[1])) { std::fprintf(stderr, "cannot write %s\n", argv[1]); return 1; }
     if (argc > 2 && std::strcmp(argv[2], "alloc-failures") == 0) return alloc_failures();
+    if (argc > 2 && std::strcmp(argv[2], "setups") == 0) {
+        if (setups()) return 1;
+        fake_hip_trace_close();
+        return fake_hip_dump_allocs((std::string(argv[1]) + ".allocs").c_str());
+    }
     const char* const eq = argc > 2 ? std::strchr(argv[2], '=') : nullptr;
     if (argc > 2 && (!eq || setenv(std::string(argv[2], eq - argv[2]).c_str(), eq + 1, 1))) { std::fprintf(stderr, "not NAME=VALUE: %s\n", argv[2]); return 1; }
     almpc_handle* h = nullptr;

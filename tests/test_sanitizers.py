@@ -180,7 +180,7 @@ def test_device_and_pinned_allocations_are_the_recorded_ones(tmp_path, host_logi
 @pytest.mark.timeout(900)
 def test_a_failed_allocation_is_an_error_and_leaves_nothing_behind(tmp_path, host_logic_exe):
     """The driver's "alloc-failures" mode: almpc_create, the shared (state box + terminal equality), per-instance and time-varying
-    designs, almpc_set_reference on per-instance models with S, both re-linearisation setups, the SQP setup on a handle that held a
+    designs, the shared and per-instance designs of a structured handle, almpc_set_reference on per-instance models with S, both re-linearisation setups, the SQP setup on a handle that held a
     re-linearisation pipeline and the first almpc_update_initialization_async, each with its k-th hipMalloc / hipHostMalloc failing
     for k = 1, 2, ... until the call gets through.  Every call whose allocation failed returns ALMPC_ERR_HIP (almpc_create: an error
     and no handle) and no other call fails: the driver stops at the first k that does otherwise.  Each entry point is walked with the
@@ -192,4 +192,29 @@ def test_a_failed_allocation_is_an_error_and_leaves_nothing_behind(tmp_path, hos
     assert "ERROR" not in r.stderr and "runtime error" not in r.stderr
     assert "alloc failures ok" in r.stdout
     walked = dict(ln.rsplit(": ", 1) for ln in r.stdout.splitlines() if ln.endswith(" allocations"))
-    assert len(walked) == 1 + 2 * 8 and all(0 < int(v.split()[0]) < 100 for v in walked.values()), walked
+    assert len(walked) == 1 + 2 * 10 and all(0 < int(v.split()[0]) < 100 for v in walked.values()), walked
+
+
+def _setups_record(exe, tmp_path):
+    """One run of the driver's "setups" mode as the text tests/golden/host_setups.txt holds: the return line of every call with what
+    it uploaded and set on the device (sorted per call), the launch trace, the sorted allocation sizes."""
+    r, lines = _launch_trace(exe, tmp_path / "setups.txt", "setups")
+    allocs = (tmp_path / "setups.txt.allocs").read_text().splitlines() if r.returncode == 0 else []
+    return r, ["== calls"] + r.stdout.splitlines() + ["== launches"] + lines + ["== allocations"] + allocs
+
+
+@pytest.mark.timeout(900)
+def test_design_and_setup_entry_points_do_what_they_were_recorded_doing(tmp_path, host_logic_exe):
+    """The driver's "setups" mode: the design and setup entry points on the routes the plain run does not reach -- almpc_design_batched
+    and almpc_relin_fnn_setup on a structured handle, the SQP setup on both structured routes, almpc_design_ltv, the DenseNet setups,
+    terminal weights and discretisation on the device, per-instance P, weights that are not symmetric -- each followed by a step, and
+    every entry point with one argument wrong at a time.  Return code and error text of every call, every byte it uploads (size and
+    FNV-1a digest, sorted per call: uploads may change places) or sets, every launch and every allocation size are those of the commit
+    before the entry points were taken apart into shared building blocks, recorded with this driver in tests/golden/host_setups.txt.
+    The fake runtime runs no kernel, so read-backs are zeros; whatever a path returned then, an error included, is its pin."""
+    r, got = _setups_record(host_logic_exe, tmp_path)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert "ERROR" not in r.stderr and "runtime error" not in r.stderr
+    assert "setups ok" in r.stdout
+    golden = (Path(ROOT) / "tests" / "golden" / "host_setups.txt").read_text().splitlines()
+    assert got == golden, next(f"line {i + 1}: {a!r} != golden {b!r}" for i, (a, b) in enumerate(zip(got + [""] * len(golden), golden + [""] * len(got))) if a != b)
