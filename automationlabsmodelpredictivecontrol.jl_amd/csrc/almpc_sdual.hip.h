@@ -666,6 +666,10 @@ __global__ __launch_bounds__(64 * SDUAL_WAVES, 2) void k_sdual(SdualParams p) {
 
         int it = 0, status = 1;
         bool bad = false, overflow = false;
+        // the table of cached responses this attempt uses: a solve that ends WITHOUT a verdict on it (the confirmation from scratch fails
+        // after three refinements: the direction of a nearly dependent row, a difference of columns, has lost its digits -- seen on an
+        // instance at the edge of feasibility, (n, m, N) = (7, 3, 10) with a state box) is done again from its start with sweeps
+        const double* gh_tab = p.ghat;
         // ---- stage 1 of the reference is x0 itself: outside the state box -> infeasible
         bool x0_out = false;
         if (has_box && lane < n) {
@@ -689,6 +693,15 @@ __global__ __launch_bounds__(64 * SDUAL_WAVES, 2) void k_sdual(SdualParams p) {
         int ns = 0, si = 0, st_kend = N, refined = 0;
         int pr = 0, sd = 0;
         double bp = 0.0, lam_p = 0.0, gpp = 0.0;
+        auto restart_with_sweeps = [&]() {   // the state of a solve that has not begun (the change count goes on)
+            gh_tab = nullptr;
+            nW = 0; kmaxW = -1; inW = 0ull;
+#pragma unroll
+            for (int sl = 0; sl < PPL; ++sl) { Wrow[sl] = 0; Wside[sl] = 0; lam[sl] = 0.0; cpos[sl] = 0.0; rpos[sl] = 0.0; }
+            status = 1; refined = 0; ns = 0; si = 0; st_kend = N; pr = 0; sd = 0; bp = 0.0; lam_p = 0.0; gpp = 0.0;
+            s = sA; w = sB;
+            mode = M_FULL; after = A_INIT;
+        };
         // end of a start (the rows of the start list are in the working set, with their inverse): multipliers from s0, rows whose
         // multiplier has the wrong sign leave, then the full solve.  Reached from the last M_START pass, or directly when a smaller tier
         // handed over its working set WITH its inverse (M_STARTED: no sweep).
@@ -782,9 +795,9 @@ __global__ __launch_bounds__(64 * SDUAL_WAVES, 2) void k_sdual(SdualParams p) {
                     sinv_mul(cbuf, rpos);
                 }
                 const int tsrc = mode == M_START ? (slist[si] >> 2) : pr;
-                if (p.ghat) {   // cached responses (shared model): no sweep
+                if (gh_tab) {   // cached responses (shared model): no sweep
                     use_sweep = false;
-                    const double* gp = p.ghat + (size_t)tsrc * TP;
+                    const double* gp = gh_tab + (size_t)tsrc * TP;
                     if (mode != M_DIR) {
                         for (int t0 = 0; t0 < TP; t0 += 512) {   // (the column's loads in flight together: one at a time is an L2 round trip each)
                             double v[8];
@@ -817,7 +830,7 @@ __global__ __launch_bounds__(64 * SDUAL_WAVES, 2) void k_sdual(SdualParams p) {
                                 double a_[LU][CPL], r_[LU];
 #pragma unroll
                                 for (int u = 0; u < LU; ++u) {
-                                    const double* gl = p.ghat + (size_t)__builtin_amdgcn_readfirstlane(slist[l + u]) * TP;
+                                    const double* gl = gh_tab + (size_t)__builtin_amdgcn_readfirstlane(slist[l + u]) * TP;
                                     r_[u] = ubuf[l + u];
 #pragma unroll
                                     for (int j = 0; j < CPL; ++j) a_[u][j] = gl[tc[j]];
@@ -828,7 +841,7 @@ __global__ __launch_bounds__(64 * SDUAL_WAVES, 2) void k_sdual(SdualParams p) {
                                     for (int j = 0; j < CPL; ++j) acc[j] = fma(-r_[u], a_[u][j], acc[j]);
                             }
                             for (; l < nW; ++l) {
-                                const double* gl = p.ghat + (size_t)__builtin_amdgcn_readfirstlane(slist[l]) * TP;
+                                const double* gl = gh_tab + (size_t)__builtin_amdgcn_readfirstlane(slist[l]) * TP;
                                 const double r0 = ubuf[l];
                                 double a_[CPL];
 #pragma unroll
@@ -997,7 +1010,10 @@ __global__ __launch_bounds__(64 * SDUAL_WAVES, 2) void k_sdual(SdualParams p) {
                     if (nan2) { bad = true; break; }
                     resn = wave_max(resn);
                     if (resn <= 1e-8 && vmax <= 1e-8) { status = 0; break; }
-                    if (refined >= 3) break;
+                    if (refined >= 3) {
+                        if (gh_tab && it < p.max_iter) { restart_with_sweeps(); continue; }
+                        break;
+                    }
                     ++refined;
                     if (nW > 0) {
                         double dl[PPL];
