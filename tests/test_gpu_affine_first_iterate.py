@@ -236,7 +236,7 @@ def test_per_instance_references_and_stale_constants(capi, mo, n, m, N):
 
 
 # ---------------------------------------------------------------------------- the row-constant table of shared references
-@pytest.mark.parametrize("n,m,N", [(12, 4, 30), (4, 4, 31), (6, 3, 30)])   # fused step (twice) and the k_admm + k_polish pair (6 waves)
+@pytest.mark.parametrize("n,m,N", [(12, 4, 30), (4, 4, 31), (6, 3, 30)])   # fused step, and the k_admm + k_polish pair of 8 waves (nz 124: past the fused step) and of 6
 def test_row_constant_table_gives_the_bounds_of_the_per_instance_loads(capi, mo, n, m, N):
     """Shared references read d, 1/d, lo, hi, rho, fS, v0S, wS from a table made at set_reference; per-instance references load and
     derive them in the step as before.  The finish forms lo / hi itself and tests ADMM's clipped z against them, so the table must
