@@ -898,13 +898,16 @@ inline __global__ __launch_bounds__(256) void k_design_rho(int nz, int nzs, int 
 
 // ---- dense (column-major, ld) -> MFMA A-fragment layout ---------------------------------------------
 // frag[(rb*ks + s)*64 + l] = M[rb*16 + (l&15)][4 s + (l>>4)]  (zero outside rows x cols)
+// paired (the KKT inverse of k_admm, see minv_frags_paired): fragments 2 j and 2 j + 1 of a row block interleaved per lane,
+// [nrb][ks / 2][64][2], so that one 16-byte load fetches a lane's element of both.  The same doubles in the same buffer.
 inline __global__ __launch_bounds__(256) void k_pack_frags(const double* M, int rows, int cols, int ld, int nrb, int ks,
-                                                    double* frag) {
+                                                    double* frag, int paired = 0) {
     const int total = nrb * ks * 64;
     for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
         const int l = t & 63, s = (t >> 6) % ks, rb = (t >> 6) / ks;
         const int r = rb * 16 + (l & 15), c = 4 * s + (l >> 4);
-        frag[t] = (r < rows && c < cols) ? M[(size_t)c * ld + r] : 0.0;
+        const size_t o = paired ? (((size_t)(rb * (ks / 2) + s / 2) * 64 + l) * 2 + (s & 1)) : (size_t)t;
+        frag[o] = (r < rows && c < cols) ? M[(size_t)c * ld + r] : 0.0;
     }
 }
 
@@ -1162,7 +1165,7 @@ inline int design_shared_device(hipStream_t stream, int n, int m, int N, int nzs
     hipLaunchKernelGGL(k_design_rho, dim3(1), dim3(256), 0, stream, nz, nzs, rho_mode, rho, dG, dRho, 0L, 0L);
     hipLaunchKernelGGL(k_design_inverse_chol, dim3(1), dim3(512), inv_lds, stream, nz, nzs, dHs, sigma, (const double*)dRho, dMinv, dFlag, 0L, 0L, 0L, 0L);
     DTRY(hipGetLastError());
-    hipLaunchKernelGGL(k_pack_frags, dim3(32), dim3(256), 0, stream, dMinv, nz, nz, nzs, nrb, ks, dMinvFrag);
+    hipLaunchKernelGGL(k_pack_frags, dim3(32), dim3(256), 0, stream, dMinv, nz, nz, nzs, nrb, ks, dMinvFrag, minv_frags_paired(ks) ? 1 : 0);
     NegGmExtra second;
     if (keepCold) {   // dW (k_design_hessian is done with it) becomes the cold-start workspace: W in its first n * nzs doubles
         DTRY(hipMemsetAsync(dW, 0, (size_t)n * nzs * sizeof(double), stream));   // (the pad rows of W)

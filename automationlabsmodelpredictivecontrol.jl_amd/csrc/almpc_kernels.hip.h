@@ -88,6 +88,16 @@ typedef double d2v __attribute__((ext_vector_type(2)));
 
 constexpr int TILE = 16;  // instances per workgroup tile = MFMA N dimension
 
+// Layout of AdmmParams::MinvFrag, one rule for the design's packer (k_pack_frags) and the reader (admm_body): an even number of
+// fragments per row block is stored pair by pair, an odd one (k_admm<1,3>) fragment by fragment.
+__host__ __device__ constexpr bool minv_frags_paired(int ks) {
+#ifdef ALMPC_EXP_MINV_UNPAIRED
+    return false;
+#else
+    return ks % 2 == 0;
+#endif
+}
+
 __device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
@@ -117,7 +127,7 @@ __device__ __forceinline__ double qmax(double v) {  // max over the 4 lanes that
 
 struct AdmmParams {
     int nz, n, m, batch, nzs;  // nzs: row stride of per-instance vectors (= 16*NRB)
-    const double* MinvFrag;    // [NRB][KS][64]   (H' + (sigma+rho) I)^-1
+    const double* MinvFrag;    // [NRB][KS][64]   (H' + (sigma+rho) I)^-1; even KS: pair-packed [NRB][KS/2][64][2] (minv_frags_paired)
     const double* VFrag;       // [NRB][ksf][64]  -H'^-1 F'  (v0 = V e0 + v0S)
     const double* v0S;         // [1 or batch][nz] -H'^-1 fS
     long v0S_stride;
@@ -161,6 +171,7 @@ struct AdmmParams {
 };
 
 __device__ __forceinline__ void lds_barrier();
+__device__ __forceinline__ void wave_fence_lds();
 
 // A hand-off record (k_step_fused): what the finish needs of one instance, in the LDS the finish will use for it.  Doubles [0, 128): z,
 // [128, 256): v0, both rotated by handoff_rot(rank) rows (the records of a tile are a multiple of 256 bytes apart: unrotated, the 16
@@ -219,7 +230,9 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
     double dv[4], dinv[4], lo[4], hi[4], fs[4], rho[4], v0s[4], ws[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) row[i] = wv * 16 + q + 4 * i;
+    [[maybe_unused]] d2v tpair = {0.0, 0.0};
     if (tabled) {
+#ifdef ALMPC_EXP_TABLE_GLOBAL   // the earlier form: every lane fetches its sixteen pairs itself, each load a 16-fold broadcast
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const d2v* t = reinterpret_cast<const d2v*>(p.rowc) + row[i];
@@ -227,6 +240,11 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
             dv[i] = c0[0]; dinv[i] = c0[1]; lo[i] = c1[0]; hi[i] = c1[1];
             rho[i] = c2[0]; fs[i] = c2[1]; v0s[i] = c3[0]; ws[i] = c3[1];
         }
+#else
+        // a wave's 16 rows x 4 pairs are 64 distinct pairs: ONE 16-byte load per lane (pair lane >> 4 of row 16 wv + (lane & 15)), handed
+        // round through LDS behind the barrier below -- not sixteen loads per lane that each fetch 64 bytes for a whole wave
+        tpair = reinterpret_cast<const d2v*>(p.rowc)[(size_t)q * p.nzs + wv * 16 + col];
+#endif
     } else {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -256,12 +274,35 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
     // in order, and these 30 fragments (115 KB per workgroup) are not needed before the first iteration, while everything
     // above is needed by the prologue, which now runs under this stream instead of behind it.
     double a[KS];
+    if constexpr (minv_frags_paired(KS)) {   // two fragments per 16-byte load: half the requests of the prologue's longest stream
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) a[ks] = p.MinvFrag[((size_t)(wv * KS + ks)) * 64 + lane];
+        for (int ks = 0; ks < KS; ks += 2) {
+            const d2v v = reinterpret_cast<const d2v*>(p.MinvFrag)[((size_t)(wv * (KS / 2) + ks / 2)) * 64 + lane];
+            a[ks] = v[0]; a[ks + 1] = v[1];
+        }
+    } else {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) a[ks] = p.MinvFrag[((size_t)(wv * KS + ks)) * 64 + lane];
+    }
     after_requests();
     ALMPC_STAMP(blockIdx.x * NRB + wv, 5);
     __syncthreads();
     ALMPC_STAMP(blockIdx.x * NRB + wv, 6);
+#ifndef ALMPC_EXP_TABLE_GLOBAL
+    if (tabled) {
+        // the wave's table pairs through its own 256-double block of rhs0 (rows 16 wv .. 16 wv + 15: nobody else touches it before the
+        // first iteration's barrier, and the affine iterate is parked there only below), read back as broadcasts: pair pp of row q + 4 i
+        d2v* stage = reinterpret_cast<d2v*>(rhs0 + wv * 16 * TILE);
+        stage[lane] = tpair;   // lane = 16 * pair + row
+        wave_fence_lds();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const d2v c0 = stage[q + 4 * i], c1 = stage[16 + q + 4 * i], c2 = stage[32 + q + 4 * i], c3 = stage[48 + q + 4 * i];
+            dv[i] = c0[0]; dinv[i] = c0[1]; lo[i] = c1[0]; hi[i] = c1[1];
+            rho[i] = c2[0]; fs[i] = c2[1]; v0s[i] = c3[0]; ws[i] = c3[1];
+        }
+    }
+#endif
 
     // ---- per-row constants, f' = F' e0 + fS, v0 = -H'^-1 f' = V e0 + v0S (V = -H'^-1 F' from the design, v0S = -H'^-1 fS from
     // set_reference; carried in registers to the flush) and the cold start's first iterate xt1 = -Minv f' = W e0 + wS
@@ -360,10 +401,19 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
         mf = qmax(mf);
         if (q == 0) red[(wv * 8 + 7) * TILE + col] = mf;
     }
-    __syncthreads();
+    // Slot 7 of red is written here and nowhere else, and nf is used in the convergence test only: the partials are read at the first
+    // check, behind that check's own barrier.  The barrier here publishes rhs0 for the first product; the affine first iterate reads
+    // only the lane's own slots, so that path has none before its first iteration.
     double nf = 0.0;
-    for (int w2 = 0; w2 < NRB; ++w2) nf = fmax(nf, red[(w2 * 8 + 7) * TILE + col]);
+    bool have_nf = false;   // (wave-uniform)
+#ifdef ALMPC_EXP_NF_BARRIERS   // the earlier form: read at once, between two barriers
     __syncthreads();
+    for (int w2 = 0; w2 < NRB; ++w2) nf = fmax(nf, red[(w2 * 8 + 7) * TILE + col]);
+    have_nf = true;
+    __syncthreads();
+#else
+    if (!affine) __syncthreads();
+#endif
 
     ALMPC_STAMP(blockIdx.x * NRB + wv, 1);
     bool active = true;
@@ -424,6 +474,10 @@ __device__ __forceinline__ void admm_body(const AdmmParams& p, double* smem, Aft
                 rp = fmax(rp, r[0 * TILE]); nx = fmax(nx, r[1 * TILE]); nzn = fmax(nzn, r[2 * TILE]);
                 rd = fmax(rd, r[3 * TILE]); nhx = fmax(nhx, r[4 * TILE]); ny = fmax(ny, r[5 * TILE]);
                 bad = fmax(bad, r[6 * TILE]);
+            }
+            if (!have_nf) {   // first check: every wave wrote its slot 7 before the barrier above
+                for (int w2 = 0; w2 < NRB; ++w2) nf = fmax(nf, red[(w2 * 8 + 7) * TILE + col]);
+                have_nf = true;
             }
             if (active) {
                 const bool conv = (rp <= p.eps_abs + p.eps_rel * fmax(nx, nzn)) &&
@@ -1263,6 +1317,22 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
     // update.  One 16-byte load per row and lane; row indices come from the LDS copy of wrow (zero beyond k: row 0
     // is a valid address and its weight is zero).  Split in a load half and an FMA half so that the first chunk's L2
     // round trip can be started before the LDS work that produces the weights.
+    // Round 3: CH row indices in CH / 4 wave-uniform 16-byte reads of the LDS copy, addresses on the vector unit.  v_readlane ->
+    // s_mul -> address costs ~30 cycles per row one after the other (tools/microbench/dep_latency.hip: a VALU write to a scalar
+    // register is slow to reach its reader), 1.0 k of the 4.1 k cycles of a one-row change at 30 rows; the LDS copy is ONE ~80-cycle
+    // round trip per chunk.  (What round 2 measured as slower was one dependent ds_read per row.)
+    auto idx_load = [&](int l0, int (&rows)[CH]) {
+        typedef int i4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+        for (int t = 0; t < CH; t += 4) {
+            const i4 r4 = *reinterpret_cast<const i4*>(wrow_s + l0 + t);
+            rows[t] = r4[0]; rows[t + 1] = r4[1]; rows[t + 2] = r4[2]; rows[t + 3] = r4[3];
+        }
+    };
+    auto g_req = [&](const int (&rows)[CH], d2 (&g)[CH]) {
+#pragma unroll
+        for (int t = 0; t < CH; ++t) g[t] = *reinterpret_cast<const d2*>(Gp + (rows[t] * gs + rc));
+    };
     auto g_load = [&](int l0, d2 (&g)[CH]) {
         // row indices straight from the position-distributed register (v_readlane -> scalar address part): the LDS copy wrow_s cost a
         // dependent LDS round trip per chunk before the rows of G could even be requested
@@ -1270,20 +1340,27 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
 #pragma unroll
         for (int t = 0; t < CH; ++t) g[t] = *reinterpret_cast<const d2*>(Gp + (__builtin_amdgcn_readlane(wrow, l0 + t) * gs + rc));
 #else
-        // Round 3: CH row indices in CH / 4 wave-uniform 16-byte reads of the LDS copy, addresses on the vector unit.  v_readlane ->
-        // s_mul -> address costs ~30 cycles per row one after the other (tools/microbench/dep_latency.hip: a VALU write to a scalar
-        // register is slow to reach its reader), 1.0 k of the 4.1 k cycles of a one-row change at 30 rows; the LDS copy is ONE ~80-cycle
-        // round trip per chunk.  (What round 2 measured as slower was one dependent ds_read per row.)
-        typedef int i4 __attribute__((ext_vector_type(4)));
         int rows[CH];
-#pragma unroll
-        for (int t = 0; t < CH; t += 4) {
-            const i4 r4 = *reinterpret_cast<const i4*>(wrow_s + l0 + t);
-            rows[t] = r4[0]; rows[t + 1] = r4[1]; rows[t + 2] = r4[2]; rows[t + 3] = r4[3];
-        }
-#pragma unroll
-        for (int t = 0; t < CH; ++t) g[t] = *reinterpret_cast<const d2*>(Gp + (rows[t] * gs + rc));
+        idx_load(l0, rows);
+        g_req(rows, g);
 #endif
+    };
+    // Index look-ahead: that round trip is paid once per sweep, not once per chunk.  The indices of chunk l0 + CH depend on nothing
+    // chunk l0 computes, so they are requested together with the rows of chunk l0 and wait in CH registers.  wrow_s is zero beyond k
+    // and 64 ints long; the chunk after the last one is read too (and not used), at offset 0 where it would lie beyond the array
+    // (memory mode at k > 64 - CH).  Only where G is in LDS (CH = 8): with G in global memory the rows are an L2 round trip that
+    // dwarfs the one for the indices, and k_polish<false> has no 16 registers to spare (it spilled 260 bytes per lane with them).
+#if defined(ALMPC_EXP_ROWS_READLANE) || defined(ALMPC_EXP_NO_INDEX_LOOKAHEAD)
+    constexpr bool IDX_AHEAD = false;
+#else
+    constexpr bool IDX_AHEAD = CH == 8;
+#endif
+    // rows of chunk l0 into g: with the look-ahead from the indices in nx, which then take those of the next chunk
+    auto g_next = [&](int l0, [[maybe_unused]] int (&nx)[CH], d2 (&g)[CH]) {
+        if constexpr (IDX_AHEAD) {
+            g_req(nx, g);
+            idx_load(l0 + CH < 64 ? l0 + CH : 0, nx);
+        } else g_load(l0, g);
     };
     auto g_fma = [&](int l0, const double* ab, const d2 (&g)[CH], double& q0, double& q1) {
         double av[CH];
@@ -1294,9 +1371,11 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
     };
     auto g_rows_times = [&](const double* ab, double& q0, double& q1) {
         q0 = 0.0; q1 = 0.0;
+        [[maybe_unused]] int nx[CH];
+        if constexpr (IDX_AHEAD) idx_load(0, nx);
         for (int l0 = 0; l0 < k; l0 += CH) {
             d2 g[CH];
-            g_load(l0, g);
+            g_next(l0, nx, g);
             g_fma(l0, ab, g, q0, q1);
         }
     };
@@ -1328,6 +1407,8 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
         const d2 gj = *reinterpret_cast<const d2*>(Gp + (j * gs + rc));  // row j = column j
         d2 g[CH];
         g_load(0, g);  // rows of positions 0..CH-1: in flight while Sinv c is formed
+        [[maybe_unused]] int nx[CH];
+        if constexpr (IDX_AHEAD) idx_load(CH, nx);  // and the indices of the second chunk (wrow_s does not change before the sweep)
         // c = G[W, j] = G[j, W] (symmetric) gathered straight from row j, beside the load of the row itself
         const double cv = Gp[j * gs + wrow];  // wrow is always a valid row index
         const double gjj = Gp[j * gs + j];
@@ -1341,7 +1422,7 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
         double q0 = 0.0, q1 = 0.0;
         g_fma(0, pbufb, g, q0, q1);
         for (int l0 = CH; l0 < k; l0 += CH) {
-            g_load(l0, g);
+            g_next(l0, nx, g);
             g_fma(l0, pbufb, g, q0, q1);
         }
         // (measured and dropped, round 3: two chunks in flight -- the loads of chunk c + 1 ahead of the FMAs of chunk c: mixed batch -1 %)
