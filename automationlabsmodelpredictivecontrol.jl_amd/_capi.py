@@ -141,8 +141,13 @@ def load():
     L.almpc_group_sensitivity.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double]
     L.almpc_group_get_sensitivity.argtypes = [_hp, _dp, _dp, _dp, _ip]
     L.almpc_group_sensitivity_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, _dp, _ip]
+    L.almpc_sensitivity_rows.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double]
+    L.almpc_sensitivity_rows_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.c_double, _dp, _ip]
+    L.almpc_group_sensitivity_rows.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double]
+    L.almpc_group_sensitivity_rows_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.c_double, _dp, _ip]
     for nm_ in ("almpc_sensitivity", "almpc_get_sensitivity", "almpc_device_sensitivity", "almpc_sensitivity_vjp",
-                "almpc_group_sensitivity", "almpc_group_get_sensitivity", "almpc_group_sensitivity_vjp"):
+                "almpc_group_sensitivity", "almpc_group_get_sensitivity", "almpc_group_sensitivity_vjp",
+                "almpc_sensitivity_rows", "almpc_sensitivity_rows_vjp", "almpc_group_sensitivity_rows", "almpc_group_sensitivity_rows_vjp"):
         getattr(L, nm_).restype = ctypes.c_int
     L.almpc_set_structured_fallback.argtypes = [_hp, ctypes.c_int]
     L.almpc_relin_fnn_setup.argtypes = [_hp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_dp] * 12 + [ctypes.c_double, ctypes.c_double]
@@ -273,12 +278,14 @@ def _sens_read(get, handle, check, want, b, n, m, N):
 
 
 def _sens_vjp(call, handle, check, g_u, g_x, act_tol, b, n, m, N):
+    """act_tol: the tolerance of almpc_sensitivity_vjp, or the pair (act_tol_u, act_tol_x) of the rows form."""
     g_u = np.ascontiguousarray(np.asarray(g_u, dtype=np.float64).reshape(b, m, N).transpose(0, 2, 1))
     if g_x is not None:
         g_x = np.ascontiguousarray(np.asarray(g_x, dtype=np.float64).reshape(b, n, N + 1).transpose(0, 2, 1))
     g_x0 = np.empty((b, n))
     rows = np.empty(b, dtype=np.int32)
-    check(call(handle, _ptr(g_u), _ptr(g_x), float(act_tol), _ptr(g_x0), rows.ctypes.data_as(_ip)))
+    tols = tuple(float(t) for t in act_tol) if isinstance(act_tol, tuple) else (float(act_tol),)
+    check(call(handle, _ptr(g_u), _ptr(g_x), *tols, _ptr(g_x0), rows.ctypes.data_as(_ip)))
     return g_x0, rows
 
 
@@ -935,6 +942,18 @@ class Solver:
         trajectories (almpc_sensitivity_vjp: no Jacobian is formed); also returns rows (batch,)."""
         return _sens_vjp(self.L.almpc_sensitivity_vjp, self.h, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
 
+    def sensitivity_rows(self, want=("K0", "dU", "dX"), act_tol_u=0.0, act_tol_x=0.0) -> dict:
+        """sensitivity for shared designs with a state box and / or the terminal equality as well (almpc_sensitivity_rows +
+        almpc_get_sensitivity): rows counts input, state-box and terminal-equality rows at a bound; act_tol_x is the state rows'
+        threshold (0: 1e-7, relative to max(1, |bound|)).  Without state rows it is sensitivity(want, act_tol_u), bit for bit."""
+        self._check(self.L.almpc_sensitivity_rows(self.h, _sens_mask(want), float(act_tol_u), float(act_tol_x)))
+        return _sens_read(self.L.almpc_get_sensitivity, self.h, self._check, want, self.batch, self.n, self.m, self.N)
+
+    def sensitivity_rows_vjp(self, g_u, g_x=None, act_tol_u=0.0, act_tol_x=0.0):
+        """sensitivity_vjp in the rows form (almpc_sensitivity_rows_vjp): (g_x0 (batch, n), rows (batch,))."""
+        return _sens_vjp(self.L.almpc_sensitivity_rows_vjp, self.h, self._check, g_u, g_x, (act_tol_u, act_tol_x), self.batch, self.n,
+                         self.m, self.N)
+
     def get_first_input(self):
         """u[:, 1] of every instance, (batch, m): what a receding-horizon caller applies (almpc_get_first_input)."""
         u0 = np.empty((self.batch, self.m))
@@ -1280,6 +1299,16 @@ class Group:
     def sensitivity_vjp(self, g_u, g_x=None, act_tol=0.0):
         """Solver.sensitivity_vjp for the whole batch (almpc_group_sensitivity_vjp)."""
         return _sens_vjp(self.L.almpc_group_sensitivity_vjp, self.g, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
+
+    def sensitivity_rows(self, want=("K0", "dU", "dX"), act_tol_u=0.0, act_tol_x=0.0) -> dict:
+        """Solver.sensitivity_rows for the whole batch (almpc_group_sensitivity_rows + almpc_group_get_sensitivity)."""
+        self._check(self.L.almpc_group_sensitivity_rows(self.g, _sens_mask(want), float(act_tol_u), float(act_tol_x)))
+        return _sens_read(self.L.almpc_group_get_sensitivity, self.g, self._check, want, self.batch, self.n, self.m, self.N)
+
+    def sensitivity_rows_vjp(self, g_u, g_x=None, act_tol_u=0.0, act_tol_x=0.0):
+        """Solver.sensitivity_rows_vjp for the whole batch (almpc_group_sensitivity_rows_vjp)."""
+        return _sens_vjp(self.L.almpc_group_sensitivity_rows_vjp, self.g, self._check, g_u, g_x, (act_tol_u, act_tol_x), self.batch, self.n,
+                         self.m, self.N)
 
     def get_results(self, want=("x", "e_x", "u", "e_u", "status", "iters", "polish_iters")):
         b, n, m, N = self.batch, self.n, self.m, self.N

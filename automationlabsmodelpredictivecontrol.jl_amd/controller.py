@@ -268,6 +268,7 @@ class HipModeler:
         self.relinearize = None  # dict for mpc_linearization='step' (black-box models), see _design_blackbox
         self.sqp = None          # dict for mpc_programming_type='non_linear', see _design_blackbox_nonlinear
         self.allow_unsolved = False  # kw mpc_allow_unsolved: calculate! returns the iterate of an instance without a certificate instead of raising
+        self.state_rows = False      # a linear design with a state box or the terminal equality: sensitivity(C) takes the rows form
 
 
 def _design_reference_mpc(state_reference, input_reference, horizon: int) -> ReferencesStateInput:
@@ -510,6 +511,7 @@ def _design_linear(system: ConstrainedLinearControlDiscreteSystem, horizon: int,
     opts = _capi.default_opts(**sopt)
     modeler_ = HipModeler(solver, opts, batch)
     modeler_.allow_unsolved = bool(kws.get("mpc_allow_unsolved", False))
+    modeler_.state_rows = state_box or terminal == "equality"   # (sensitivity(C) then takes the rows form)
     tuning = ModelPredictiveControlTuning(modeler_, references, horizon, weights,
                                           TerminalIngredient(terminal, np.array(P)), float(sample_time), int(max_time))
     shape = (lambda *s: s) if batch == 1 else (lambda *s: (batch, *s))
@@ -573,14 +575,19 @@ def calculate(C: ModelPredictiveControlController) -> None:
         mod.sqp["u_prev"] = r["u"].copy()
 
 
-def sensitivity(C: ModelPredictiveControlController, want=("K0",), act_tol: float = 0.0) -> dict:
+def sensitivity(C: ModelPredictiveControlController, want=("K0",), act_tol: float = 0.0, act_tol_x: float = 0.0) -> dict:
     """Derivatives of the last calculate!(C) with respect to the initial state.  An extension of this build: the reference's
     surface stops at the four result matrices (src/main/computation_mpc.jl:50-53).  Returns {"K0": du[:,1]/dx0 (m, n), "dU":
     (m, N, n), "dX": (n, N+1, n), "rows": rows at a bound} for what `want` names, with a leading batch axis when the controller
     has more than one instance; u ~ u* + K0 (x - x0) is the exact local law on the current critical region.  Linear controllers
-    with an input box (modeler.solver.sensitivity / sensitivity_vjp say what else is refused)."""
+    with an input box; with mpc_state_constraint or mpc_terminal_ingredient = "equality" the rows form is taken (rows then counts
+    state rows too, act_tol_x is their threshold: Solver.sensitivity_rows).  modeler.solver.sensitivity / sensitivity_rows say what
+    is refused."""
     mod: HipModeler = C.tuning.modeler
-    out = mod.solver.sensitivity(want, act_tol)
+    if mod.state_rows:
+        out = mod.solver.sensitivity_rows(want, act_tol, act_tol_x)
+    else:
+        out = mod.solver.sensitivity(want, act_tol)
     return {k: (v[0] if mod.batch == 1 else v) for k, v in out.items()}
 
 

@@ -231,6 +231,9 @@ struct almpc_handle {
         uint32_t have = 0;              // ALMPC_SENS_* bits the buffers hold for the LAST step (0: none)
         DevBuf<double> V;               // [n][nzs] plain V of a shared design (the handle keeps it in MFMA fragment order only)
         bool v_ok = false;              // ... unpacked from the current design
+        DevBuf<double> T1;              // [n][Rs] row values of the unconstrained minimiser (rows form: k_sens_rows_table)
+        bool t1_ok = false;             // ... built from the current design
+        DevBuf<double> HF;              // [nz][nz] H, [n][nz] F unscaled: what the table kernel refines V against
         DevBuf<int32_t> ovf;            // [SENS_OVF_HEAD + batch] instances beyond the first tier's 32 rows
         DevBuf<double> gu, gx, gx0;     // VJP: uploaded loss gradients, result [batch][n]
         DevBuf<int32_t> vrows;          // [batch] |W| of the last VJP
@@ -1175,7 +1178,7 @@ int wait_and_settle(almpc_handle* h, bool blocking_only = false) {
 
 // A new design voids a redo that was deferred for a step of the previous one (its models, references and results are about to go)
 void drop_lazy_redo(almpc_handle* h) {
-    h->sens.stepped = false; h->sens.v_ok = false; h->sens.have = 0;   // (what a sensitivity call looks at goes with the design as well)
+    h->sens.stepped = false; h->sens.v_ok = false; h->sens.t1_ok = false; h->sens.have = 0;   // (what a sensitivity call looks at goes with the design as well)
     h->redo.lazy_pending = false;
     h->redo.expected = false;
     if (h->redo.hUnsolved) h->redo.unsolved_seen = *reinterpret_cast<volatile int*>(h->redo.hUnsolved.get());
@@ -4221,24 +4224,31 @@ int almpc_debug_poison_lds(almpc_handle* h) {
 // ---- solution sensitivities (k_sens) --------------------------------------------------------------------------------------------
 namespace {
 
-// What a sensitivity call can look at: the last step of a condensed design with an input box only.
-int sens_check(almpc_handle* h, const char* who) {
+// What a sensitivity call can look at: the last step of a condensed design with an input box only; the rows form
+// (almpc_sensitivity_rows, rows_form) also that of a shared design with state rows.
+int sens_check(almpc_handle* h, const char* who, bool rows_form = false) {
     if (!h) return ALMPC_ERR_INVALID;
     const std::string w(who);
     if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, w + " before design");
     if (h->structured) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": a structured handle forms no condensed inverse G = H'^-1 (the constraint-space form is not built)");
     if (h->ltv || h->sqp.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": time-varying and SQP designs solve for a step around a trajectory, not for u(x0)");
     if (h->relin.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the re-linearisation pipeline's models depend on x0 themselves");
-    if (h->mc > 0) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": designs with state rows (state box, terminal equality) need the constraint-space form, which is not built");
+    if (h->mc > 0 && !rows_form)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": designs with state rows (state box, terminal equality) need the constraint-space form (almpc_sensitivity_rows)");
+    if (h->mc > 0 && (h->batched || h->ghat_inst))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": per-instance models with state rows keep one constraint-space matrix per instance, for which the rows form is not built");
     if (!h->sens.stepped) return fail(h, ALMPC_ERR_INVALID, w + ": no step has run on this design");
     return ALMPC_OK;
 }
 
 // Operands every k_sens launch shares; the plain V of a shared design is unpacked once per design.
-int sens_params(almpc_handle* h, double act_tol, SensParams& p) {
+// rows (a shared design with state rows, sens_check passed in the rows form): the operands are Ghat and the table T1, made at the
+// first such call on a design
+int sens_params(almpc_handle* h, double act_tol, SensParams& p, bool rows = false, double act_tol_x = 0.0) {
     const int n = h->n, nz = h->nz, nzs = h->nzs;
     p = SensParams();
     p.n = n; p.m = h->m; p.N = h->N; p.nz = nz; p.nzs = nzs; p.batch = h->batch;
+    p.cap2 = nz;
     if (h->batched) {
         p.G = h->bG; p.G_stride = (long)nz * nzs; p.V = h->bVs; p.V_stride = (long)n * nzs; p.d = h->bD; p.d_stride = nzs;
         p.A = h->bA; p.A_stride = (long)n * n; p.B = h->bB; p.B_stride = (long)n * h->m;
@@ -4251,6 +4261,30 @@ int sens_params(almpc_handle* h, double act_tol, SensParams& p) {
         }
         p.G = h->dG; p.V = h->sens.V; p.d = h->dD; p.A = h->dA; p.B = h->dB;
     }
+    if (rows) {
+        const int ne = h->eq_proj ? n : 0, eq0 = h->R - n;
+        if (!h->sens.t1_ok) {
+            HIP_TRY(h, h->sens.T1.grow((size_t)n * h->Rs));
+            SensRowsTableParams tp;
+            tp.n = n; tp.m = h->m; tp.N = h->N; tp.nz = nz; tp.nzs = nzs; tp.R = h->R; tp.Rs = h->Rs; tp.eq_proj = h->eq_proj; tp.eq0 = eq0; tp.ne = ne;
+            tp.A = h->dA; tp.B = h->dB; tp.V = h->sens.V; tp.d = h->dD; tp.row_xidx = h->dRowXidx;
+            // the design's H and F for the table's refinement of V (the stream is idle: wait_and_settle has run)
+            if (h->H.size() != (size_t)nz * nz || h->F.size() != (size_t)nz * n) return fail(h, ALMPC_ERR_INVALID, "sensitivity_rows: the design's H and F are not kept");
+            HIP_TRY(h, h->sens.HF.grow((size_t)nz * nz + (size_t)nz * n));
+            HIP_TRY(h, hipMemcpy(h->sens.HF, h->H.data(), (size_t)nz * nz * sizeof(double), hipMemcpyHostToDevice));
+            HIP_TRY(h, hipMemcpy(h->sens.HF + (size_t)nz * nz, h->F.data(), (size_t)nz * n * sizeof(double), hipMemcpyHostToDevice));
+            tp.H = h->sens.HF; tp.F = h->sens.HF + (size_t)nz * nz; tp.G = h->dG;
+            tp.GhatE = h->eq_proj ? h->dGhatE.get() : nullptr; tp.WinvE = h->eq_proj ? h->dWinvE.get() : nullptr; tp.out = h->sens.T1;
+            // (dynamic LDS far below the 64 KB that need no opt-in: (N + 1) n <= 1024 and nz <= 512 by the design's limits on state rows)
+            hipLaunchKernelGGL(k_sens_rows_table, dim3((unsigned)n), dim3(256), (size_t)sens_rows_table_lds_doubles(n, h->N, nz) * sizeof(double), h->stream, tp);
+            HIP_TRY(h, hipGetLastError());
+            h->sens.t1_ok = true;
+        }
+        p.G = h->dGhat; p.V = h->sens.T1;
+        p.R = h->R; p.Rs = h->Rs; p.cap2 = nz - ne; p.eq_proj = h->eq_proj; p.eq0 = eq0; p.ne = ne;
+        p.x = h->dX; p.xmin = h->dXmin; p.xmax = h->dXmax; p.row_xidx = h->dRowXidx; p.row_eq = h->dRowEq;
+        p.tau_x = act_tol_x > 0.0 ? act_tol_x : 1e-7;
+    }
     p.umin = h->dUmin; p.umax = h->dUmax; p.u = h->dU; p.status = h->dStatus;
     p.tau = act_tol > 0.0 ? act_tol : 1e-9;
     p.ch = sens_ch(n);
@@ -4260,45 +4294,54 @@ int sens_params(almpc_handle* h, double act_tol, SensParams& p) {
 }
 
 // The two tiers, back to back on the handle's stream: no host look in between (the second is gated on the list's count word)
-template <bool VJP>
+// (ROWS: p.cap2 rows at most in an independent working set, one flag per row of A)
+template <bool VJP, bool ROWS>
 int sens_launch(almpc_handle* h, SensParams p) {
-    const int n = h->n, nz = h->nz, nzs = h->nzs;
-    const size_t lds2 = nz > SENS_CAP1 ? (size_t)sens_lds_doubles(n, nzs, nz) * sizeof(double) : 0;   // (nothing is enqueued before a refusal)
+    const int n = h->n, nzs = h->nzs, cap2 = p.cap2, nfl = ROWS ? h->Rs : nzs;
+    const size_t lds2 = cap2 > SENS_CAP1 ? (size_t)sens_lds_doubles(n, nzs, cap2, nfl) * sizeof(double) : 0;
     if (lds2 > 160 * 1024) return fail(h, ALMPC_ERR_UNSUPPORTED, "sensitivity: the second tier's working set does not fit LDS");
     HIP_TRY(h, hipMemsetAsync(h->sens.ovf, 0, SENS_OVF_HEAD * sizeof(int32_t), h->stream));
-    p.cap = SENS_CAP1; p.lds_per_team = sens_lds_doubles(n, nzs, p.cap);
+    p.cap = SENS_CAP1; p.lds_per_team = sens_lds_doubles(n, nzs, p.cap, nfl);
     const size_t lds1 = (size_t)SENS_WAVES * p.lds_per_team * sizeof(double);
-    HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens<VJP, false>), lds1));
-    hipLaunchKernelGGL((k_sens<VJP, false>), dim3((unsigned)((h->batch + SENS_WAVES - 1) / SENS_WAVES)), dim3(64 * SENS_WAVES), lds1, h->stream, p);
+    HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens<VJP, false, ROWS>), lds1));
+    hipLaunchKernelGGL((k_sens<VJP, false, ROWS>), dim3((unsigned)((h->batch + SENS_WAVES - 1) / SENS_WAVES)), dim3(64 * SENS_WAVES), lds1, h->stream, p);
     HIP_TRY(h, hipGetLastError());
-    if (nz > SENS_CAP1) {   // (a working set cannot outgrow the first tier otherwise)
-        p.cap = nz; p.lds_per_team = sens_lds_doubles(n, nzs, p.cap);
-        HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens<VJP, true>), lds2));
-        hipLaunchKernelGGL((k_sens<VJP, true>), dim3((unsigned)std::min(h->batch, 4 * h->num_cus)), dim3(SENS_WG), lds2, h->stream, p);
+    if (cap2 > SENS_CAP1) {   // (a working set cannot outgrow the first tier otherwise)
+        p.cap = cap2; p.lds_per_team = sens_lds_doubles(n, nzs, p.cap, nfl);
+        HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens<VJP, true, ROWS>), lds2));
+        hipLaunchKernelGGL((k_sens<VJP, true, ROWS>), dim3((unsigned)std::min(h->batch, 4 * h->num_cus)), dim3(SENS_WG), lds2, h->stream, p);
         HIP_TRY(h, hipGetLastError());
     }
     return ALMPC_OK;
 }
 
-}  // namespace
+// The LDS-fit test of the second tier on its own, in front of everything a call enqueues (the design-time tables included)
+int sens_fits(almpc_handle* h, bool rows) {
+    const int cap2 = h->nz - ((rows && h->eq_proj) ? h->n : 0);
+    if (cap2 > SENS_CAP1 && (size_t)sens_lds_doubles(h->n, h->nzs, cap2, rows ? h->Rs : h->nzs) * sizeof(double) > 160 * 1024)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "sensitivity: the second tier's working set does not fit LDS");
+    return ALMPC_OK;
+}
 
-extern "C" {
-
-int almpc_sensitivity(almpc_handle* h, uint32_t want, double act_tol) {
-    ALMPC_TRY(sens_check(h, "sensitivity"));
-    if (!want || (want & ~(ALMPC_SENS_K0 | ALMPC_SENS_DU | ALMPC_SENS_DX))) return fail(h, ALMPC_ERR_INVALID, "sensitivity: want must be a mask of ALMPC_SENS_*");
+// almpc_sensitivity (rows_form false) and almpc_sensitivity_rows: a design without state rows takes the same path through both
+int sens_jacobians(almpc_handle* h, const char* who, bool rows_form, uint32_t want, double act_tol, double act_tol_x) {
+    ALMPC_TRY(sens_check(h, who, rows_form));
+    if (!want || (want & ~(ALMPC_SENS_K0 | ALMPC_SENS_DU | ALMPC_SENS_DX))) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": want must be a mask of ALMPC_SENS_*");
+    const bool rows = rows_form && h->mc > 0;
+    if (rows) ALMPC_TRY(sens_fits(h, true));
     HIP_TRY(h, hipSetDevice(h->device));
     ALMPC_TRY(wait_and_settle(h));   // (a synchronous look: redone instances take part)
     const size_t b = (size_t)h->batch, n = (size_t)h->n;
     h->sens.have = 0;
     SensParams p;
-    ALMPC_TRY(sens_params(h, act_tol, p));
+    ALMPC_TRY(sens_params(h, act_tol, p, rows, act_tol_x));
     HIP_TRY(h, h->sens.rows.grow(b));
     if (want & ALMPC_SENS_K0) HIP_TRY(h, h->sens.K0.grow(b * n * h->m));
     if (want & (ALMPC_SENS_DU | ALMPC_SENS_DX)) HIP_TRY(h, h->sens.dU.grow(b * n * h->nz));   // (dX is rolled out from dU)
     if (want & ALMPC_SENS_DX) HIP_TRY(h, h->sens.dX.grow(b * n * (h->N + 1) * n));
     p.want = want; p.K0 = h->sens.K0; p.dU = h->sens.dU; p.rows = h->sens.rows;
-    ALMPC_TRY(sens_launch<false>(h, p));
+    if (rows) ALMPC_TRY((sens_launch<false, true>(h, p)));
+    else ALMPC_TRY((sens_launch<false, false>(h, p)));
     if (want & ALMPC_SENS_DX) {
         SensDxParams q;
         q.n = h->n; q.m = h->m; q.N = h->N; q.nz = h->nz; q.batch = h->batch;
@@ -4311,6 +4354,44 @@ int almpc_sensitivity(almpc_handle* h, uint32_t want, double act_tol) {
     HIP_TRY(h, stream_wait_polling(h));
     h->sens.have = want | ((want & ALMPC_SENS_DX) ? ALMPC_SENS_DU : 0u);
     return ALMPC_OK;
+}
+
+int sens_vjp(almpc_handle* h, const char* who, bool rows_form, const double* g_u, const double* g_x, double act_tol, double act_tol_x,
+             double* g_x0, int32_t* rows_out) {
+    ALMPC_TRY(sens_check(h, who, rows_form));
+    if (!g_u || !g_x0) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": null g_u or g_x0");
+    const bool rows = rows_form && h->mc > 0;
+    if (rows) ALMPC_TRY(sens_fits(h, true));
+    HIP_TRY(h, hipSetDevice(h->device));
+    ALMPC_TRY(wait_and_settle(h));
+    const size_t b = (size_t)h->batch, n = (size_t)h->n, xs = n * (h->N + 1);
+    SensParams p;
+    ALMPC_TRY(sens_params(h, act_tol, p, rows, act_tol_x));
+    HIP_TRY(h, h->sens.vrows.grow(b)); HIP_TRY(h, h->sens.gx0.grow(b * n)); HIP_TRY(h, h->sens.gu.grow(b * h->nz));
+    HIP_TRY(h, hipMemcpyAsync(h->sens.gu, g_u, b * h->nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (g_x) {
+        HIP_TRY(h, h->sens.gx.grow(b * xs));
+        HIP_TRY(h, hipMemcpyAsync(h->sens.gx, g_x, b * xs * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    p.g_u = h->sens.gu; p.g_x = g_x ? h->sens.gx.get() : nullptr; p.g_x0 = h->sens.gx0; p.rows = h->sens.vrows;
+    if (rows) ALMPC_TRY((sens_launch<true, true>(h, p)));
+    else ALMPC_TRY((sens_launch<true, false>(h, p)));
+    HIP_TRY(h, hipMemcpyAsync(g_x0, h->sens.gx0, b * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (rows_out) HIP_TRY(h, hipMemcpyAsync(rows_out, h->sens.vrows, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, stream_wait_polling(h));
+    return ALMPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int almpc_sensitivity(almpc_handle* h, uint32_t want, double act_tol) {
+    return sens_jacobians(h, "sensitivity", false, want, act_tol, 0.0);
+}
+
+int almpc_sensitivity_rows(almpc_handle* h, uint32_t want, double act_tol_u, double act_tol_x) {
+    return sens_jacobians(h, "sensitivity_rows", true, want, act_tol_u, act_tol_x);
 }
 
 int almpc_get_sensitivity(almpc_handle* h, double* K0, double* dU, double* dX, int32_t* rows) {
@@ -4338,25 +4419,12 @@ int almpc_device_sensitivity(almpc_handle* h, const double** d_K0, const double*
 }
 
 int almpc_sensitivity_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows) {
-    ALMPC_TRY(sens_check(h, "sensitivity_vjp"));
-    if (!g_u || !g_x0) return fail(h, ALMPC_ERR_INVALID, "sensitivity_vjp: null g_u or g_x0");
-    HIP_TRY(h, hipSetDevice(h->device));
-    ALMPC_TRY(wait_and_settle(h));
-    const size_t b = (size_t)h->batch, n = (size_t)h->n, xs = n * (h->N + 1);
-    SensParams p;
-    ALMPC_TRY(sens_params(h, act_tol, p));
-    HIP_TRY(h, h->sens.vrows.grow(b)); HIP_TRY(h, h->sens.gx0.grow(b * n)); HIP_TRY(h, h->sens.gu.grow(b * h->nz));
-    HIP_TRY(h, hipMemcpyAsync(h->sens.gu, g_u, b * h->nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (g_x) {
-        HIP_TRY(h, h->sens.gx.grow(b * xs));
-        HIP_TRY(h, hipMemcpyAsync(h->sens.gx, g_x, b * xs * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    }
-    p.g_u = h->sens.gu; p.g_x = g_x ? h->sens.gx.get() : nullptr; p.g_x0 = h->sens.gx0; p.rows = h->sens.vrows;
-    ALMPC_TRY(sens_launch<true>(h, p));
-    HIP_TRY(h, hipMemcpyAsync(g_x0, h->sens.gx0, b * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (rows) HIP_TRY(h, hipMemcpyAsync(rows, h->sens.vrows, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, stream_wait_polling(h));
-    return ALMPC_OK;
+    return sens_vjp(h, "sensitivity_vjp", false, g_u, g_x, act_tol, 0.0, g_x0, rows);
+}
+
+int almpc_sensitivity_rows_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol_u, double act_tol_x, double* g_x0,
+                               int32_t* rows) {
+    return sens_vjp(h, "sensitivity_rows_vjp", true, g_u, g_x, act_tol_u, act_tol_x, g_x0, rows);
 }
 
 }  // extern "C"

@@ -633,6 +633,21 @@ int almpc_group_sensitivity_vjp(almpc_group* g, const double* g_u, const double*
         return almpc_sensitivity_vjp(g->hs[i], g_u + f * nz, g_x ? g_x + f * n * (g->N + 1) : nullptr, act_tol, g_x0 + f * n, rows ? rows + f : nullptr);
     });
 }
+// ... and the rows forms (almpc_sensitivity_rows, almpc_sensitivity_rows_vjp); almpc_group_get_sensitivity serves both
+int almpc_group_sensitivity_rows(almpc_group* g, uint32_t want, double act_tol_u, double act_tol_x) {
+    if (!g) return ALMPC_ERR_INVALID;
+    return group_fanout(g, [&](int i) { return almpc_sensitivity_rows(g->hs[i], want, act_tol_u, act_tol_x); });
+}
+int almpc_group_sensitivity_rows_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol_u, double act_tol_x, double* g_x0,
+                                     int32_t* rows) {
+    if (!g || !g_u || !g_x0) return ALMPC_ERR_INVALID;
+    const size_t n = (size_t)g->n, nz = (size_t)g->m * g->N;
+    return group_fanout(g, [&](int i) {
+        const size_t f = (size_t)g->first[i];
+        return almpc_sensitivity_rows_vjp(g->hs[i], g_u + f * nz, g_x ? g_x + f * n * (g->N + 1) : nullptr, act_tol_u, act_tol_x, g_x0 + f * n,
+                                          rows ? rows + f : nullptr);
+    });
+}
 
 // Asynchronous read-back of the whole batch: the request goes to every device (pack kernels / copy streams), the ticket is the group's;
 // almpc_group_get_results_wait gathers into the caller's arrays (layouts of almpc_group_get_results).  The last two tickets are kept.

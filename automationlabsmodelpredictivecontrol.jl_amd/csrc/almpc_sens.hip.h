@@ -16,9 +16,9 @@
 // weakly active row (multiplier zero) the solution map is only directionally differentiable: what comes out is the derivative of the
 // face on which every row at its bound is held.
 //
-// Shape: two tiers, as k_polish_gen / k_polish_gen64.  k_sens<VJP, false>: one wave per instance, SENS_WAVES waves per workgroup that
-// never wait for each other, S up to 32 x 32 in LDS; an instance with more rows is appended to a list (count word + indices).
-// k_sens<VJP, true>: one workgroup of 256 threads per listed instance, S up to nz x nz in LDS; its grid strides over the list, so an
+// Shape: two tiers, as k_polish_gen / k_polish_gen64.  k_sens<VJP, false, ROWS>: one wave per instance, SENS_WAVES waves per workgroup
+// that never wait for each other, S up to 32 x 32 in LDS; an instance with more rows is appended to a list (count word + indices).
+// k_sens<VJP, true, ROWS>: one workgroup of 256 threads per listed instance, S up to nz x nz in LDS; its grid strides over the list, so an
 // empty list returns at once.  Both run the same body on a "team" (64 lanes and wave fences, or 256 threads and barriers):
 //   1  flags of the rows at a bound, in parallel; the row list by one thread, ascending
 //   2  S = G[W,W] into LDS, Cholesky S = L L' in place (a pivot that is not positive and finite: rows = -1, outputs zero)
@@ -26,7 +26,21 @@
 //      J = V - G[:,W] Y streamed with thread j on row j (row w of G is column w by symmetry: contiguous), scaled by d, rows W zero
 //      (all nz rows for dU, the first m alone when only K0 is asked for)
 //      VJP: adjoint rollout (lam in LDS), t = G[W,:] p, one solve, two n-column contractions
-// Team LDS (doubles): S cap x (cap | 1), Y cap x ch, p nzs, t cap, lam 2 n; ints: list cap, flags nzs, 4 words.
+// Team LDS (doubles): S cap x (cap | 1), Y cap x ch, p nzs, t cap, lam 2 n; ints: list cap, flags nzs (Rs in the rows form), 4 words.
+//
+// Rows form (k_sens<.., .., true>; almpc_sensitivity_rows): shared designs with state rows (state box, terminal equality).  The rows
+// are those of A = [I; C'] (R = nz + mc rows, padded to Rs); a state row's bound moves with x0, its value being
+// (Phi e0 + Gamma D w)_r.  With Ghat = A G A' (the handle's dGhat, [R][Rs]; its first nz rows are G A') and the row values of the
+// unconstrained minimiser  T1 = A V + [0; Phi_rows]  (R x n, kept as [n][Rs]: k_sens_rows_table), on the face where W is held
+//     S = Ghat[W,W],   dw/dx0 = T1[0:nz] - Ghat[0:nz, W] S^-1 T1[W],
+//     g_x0 = lam_1 + T1[0:nz]' p - T1[W]' S^-1 (Ghat[W, 0:nz] p)
+// -- the body above with row r of Ghat (stride Rs) in place of G's and T1 in place of V; with an input box alone it is the same
+// formula.  W: input rows by the rule above; a state-box row (stage k >= 2, state i) iff  x[i,k] - xmin_i <= tau_x max(1, |xmin_i|)
+// or  xmax_i - x[i,k] <= tau_x max(1, |xmax_i|)  on the returned x (a bound that is not finite or at least 1e300 in size -- the
+// handle's "no box" filler -- is never active); every terminal-equality row, always.  Where the handle's Ghat is the one projected on
+// the terminal equality E (eq_proj) the same formula holds in projected quantities: the list is W' = W \ E, Ghat as stored, T1
+// projected by the table kernel; `rows` still reports |W|.  A working set of more than nz rows (nz - n projected) cannot be
+// independent: rows = -1 and zeros, as for a failed Cholesky.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -58,11 +72,20 @@ struct SensParams {
     double* g_x0;                       // [batch][n]
     int32_t* rows;                      // [batch] |W|, or -1
     int32_t* ovf;                       // [SENS_OVF_HEAD + batch]
+    // rows form: G is Ghat [R][Rs], V is T1 [n][Rs]
+    int R, Rs;                          // rows of A, padded
+    int cap2;                           // most rows an independent working set can hold (nz, or nz - ne projected)
+    int eq_proj, eq0, ne;               // Ghat and T1 are projected on the rows eq0 .. eq0 + ne - 1
+    const double* x;                    // [batch][N+1][n] returned states
+    const double* xmin; const double* xmax;          // [n]
+    const int* row_xidx; const int* row_eq;          // [Rs] a state row's place in x, whether it is an equality row
+    double tau_x;
 };
 
 __host__ __device__ inline int sens_ch(int n) { const int c = (n + 3) & ~3; return c < 16 ? c : 16; }
-__host__ __device__ inline int sens_lds_doubles(int n, int nzs, int cap) {
-    const int ints = cap + nzs + 4;
+// (nfl: rows that carry a flag -- nzs, or Rs in the rows form)
+__host__ __device__ inline int sens_lds_doubles(int n, int nzs, int cap, int nfl) {
+    const int ints = cap + nfl + 4;
     return (cap * (cap | 1) + cap * sens_ch(n) + nzs + cap + 2 * n + (ints + 1) / 2 + 1) & ~1;
 }
 
@@ -120,9 +143,10 @@ __device__ __forceinline__ void sens_zero(const SensParams& p, const SensTeam<WG
     }
 }
 
-template <bool VJP, bool WG>
+template <bool VJP, bool WG, bool ROWS>
 __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTeam<WG>& T, int inst, double* L) {
     const int n = p.n, m = p.m, N = p.N, nz = p.nz, nzs = p.nzs, cap = p.cap, ch = p.ch, ld = cap | 1;
+    const int gs = ROWS ? p.Rs : nzs;   // stride of a row of G (Ghat) and of a column of V (T1); the rows that carry a flag
     double* S = L;
     double* Y = S + cap * ld;
     double* pv = Y + cap * ch;
@@ -130,7 +154,7 @@ __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTea
     double* lam = tv + cap;
     int* wl = reinterpret_cast<int*>(lam + 2 * n);
     int* act = wl + cap;
-    int* word = act + nzs;   // [0] |W|, [1] the factorisation failed
+    int* word = act + gs;   // [0] rows in the list, [1] the factorisation failed
     const double* G = p.G + (size_t)inst * p.G_stride;
     const double* V = p.V + (size_t)inst * p.V_stride;
     const double* dv = p.d + (size_t)inst * p.d_stride;
@@ -147,16 +171,39 @@ __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTea
         const int i = j % m;
         act[j] = (uj - p.umin[i] <= tol || p.umax[i] - uj <= tol) ? 1 : 0;
     }
+    if (ROWS) {
+        const double* xs = p.x + (size_t)inst * (N + 1) * n;
+        for (int r = nz + T.tid; r < p.R; r += T.nt) {
+            int f = 1;   // (an equality row)
+            if (!p.row_eq[r]) {
+                const int xi = p.row_xidx[r];
+                const double xv = xs[xi], lo = p.xmin[xi % n], hi = p.xmax[xi % n];
+                // (fabs(b) < 1e300 is false for an infinite bound, for NaN and for the "no box" filler)
+                f = ((fabs(lo) < 1e300 && xv - lo <= p.tau_x * fmax(1.0, fabs(lo))) ||
+                     (fabs(hi) < 1e300 && hi - xv <= p.tau_x * fmax(1.0, fabs(hi)))) ? 1 : 0;
+            }
+            act[r] = f;
+        }
+    }
     T.sync();
+    const int held = (ROWS && p.eq_proj) ? p.ne : 0;   // rows of W that the projection took out of the problem
     if (T.tid == 0) {
         int r = 0;
-        for (int j = 0; j < nz; ++j)
+        const int nrows = ROWS ? p.R : nz;
+        for (int j = 0; j < nrows; ++j) {
+            if (ROWS && held && j >= p.eq0 && j < p.eq0 + p.ne) continue;
             if (act[j]) { if (r < cap) wl[r] = j; ++r; }
+        }
         word[0] = r; word[1] = 0;
     }
     T.sync();
     const int rows = word[0];
-    if (rows > cap) {   // first tier only (the second has cap = nz): hand the instance on
+    if (ROWS && rows > p.cap2) {   // more rows than free directions: not independent
+        sens_zero<VJP>(p, T, inst);
+        if (T.tid == 0) p.rows[inst] = -1;
+        return;
+    }
+    if (rows > cap) {   // first tier only (the second has cap = nz, cap2 in the rows form): hand the instance on
         if (T.tid == 0) {
             const int k = atomicAdd(p.ovf, 1);
             p.ovf[SENS_OVF_HEAD + k] = inst;
@@ -166,7 +213,7 @@ __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTea
     // 2: S = G[W,W] = L L'
     for (int idx = T.tid; idx < rows * rows; idx += T.nt) {
         const int a = idx / rows, b = idx % rows;
-        S[a * ld + b] = G[(size_t)wl[a] * nzs + wl[b]];
+        S[a * ld + b] = G[(size_t)wl[a] * gs + wl[b]];
     }
     T.sync();
     for (int k = 0; k < rows; ++k) {
@@ -192,7 +239,7 @@ __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTea
         if (T.tid == 0) p.rows[inst] = -1;
         return;
     }
-    if (T.tid == 0) p.rows[inst] = rows;
+    if (T.tid == 0) p.rows[inst] = rows + held;
 
     if (!VJP) {
         // 3: per column chunk Y = S^-1 V[W, chunk], then J = V - G[:,W] Y, scaled (K0 alone: only its m rows of J)
@@ -201,7 +248,7 @@ __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTea
             const int nc = n - c0 < ch ? n - c0 : ch;
             for (int idx = T.tid; idx < rows * nc; idx += T.nt) {
                 const int a = idx / nc, c = idx % nc;
-                Y[a * ch + c] = V[(size_t)(c0 + c) * nzs + wl[a]];
+                Y[a * ch + c] = V[(size_t)(c0 + c) * gs + wl[a]];
             }
             T.sync();
             sens_solve(T, S, ld, rows, Y, ch, nc);
@@ -211,9 +258,9 @@ __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTea
                 for (int q0 = 0; q0 < nc; q0 += 4) {   // (ch is a multiple of 4: columns past nc are read inside Y's row and dropped)
                     double acc[4];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) acc[q] = q0 + q < nc ? V[(size_t)(c0 + q0 + q) * nzs + j] : 0.0;
+                    for (int q = 0; q < 4; ++q) acc[q] = q0 + q < nc ? V[(size_t)(c0 + q0 + q) * gs + j] : 0.0;
                     for (int a = 0; a < rows; ++a) {
-                        const double g = G[(size_t)wl[a] * nzs + j];
+                        const double g = G[(size_t)wl[a] * gs + j];
                         const double* y = Y + a * ch + q0;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) acc[q] -= g * y[q];
@@ -257,7 +304,7 @@ __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTea
             double* t_ = cur; cur = nxt; nxt = t_;
         }
         for (int a = T.tid; a < rows; a += T.nt) {
-            const double* g = G + (size_t)wl[a] * nzs;
+            const double* g = G + (size_t)wl[a] * gs;
             double s = 0.0;
             for (int j = 0; j < nz; ++j) s += g[j] * pv[j];
             tv[a] = s;
@@ -265,7 +312,7 @@ __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTea
         T.sync();
         sens_solve(T, S, ld, rows, tv, 1, 1);
         for (int c = T.tid; c < n; c += T.nt) {
-            const double* v = V + (size_t)c * nzs;
+            const double* v = V + (size_t)c * gs;
             double s1 = 0.0, s2 = 0.0;
             for (int j = 0; j < nz; ++j) s1 += v[j] * pv[j];
             for (int a = 0; a < rows; ++a) s2 += v[wl[a]] * tv[a];
@@ -274,19 +321,19 @@ __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTea
     }
 }
 
-template <bool VJP, bool WG>
+template <bool VJP, bool WG, bool ROWS>
 __global__ __launch_bounds__(256) void k_sens(SensParams p) {
     extern __shared__ __attribute__((aligned(16))) double sens_smem[];
     if (WG) {
         const SensTeam<WG> T{(int)threadIdx.x, (int)blockDim.x};
         const int count = p.ovf[0];
-        for (int k = blockIdx.x; k < count; k += gridDim.x) sens_instance<VJP, WG>(p, T, p.ovf[SENS_OVF_HEAD + k], sens_smem);
+        for (int k = blockIdx.x; k < count; k += gridDim.x) sens_instance<VJP, WG, ROWS>(p, T, p.ovf[SENS_OVF_HEAD + k], sens_smem);
     } else {
         const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
         const SensTeam<WG> T{(int)(threadIdx.x & 63), 64};
         double* L = sens_smem + (size_t)wv * p.lds_per_team;
         const int wpb = (int)(blockDim.x >> 6), nwaves = gridDim.x * wpb;
-        for (int inst = blockIdx.x * wpb + wv; inst < p.batch; inst += nwaves) sens_instance<VJP, WG>(p, T, inst, L);
+        for (int inst = blockIdx.x * wpb + wv; inst < p.batch; inst += nwaves) sens_instance<VJP, WG, ROWS>(p, T, inst, L);
     }
 }
 
@@ -349,6 +396,75 @@ inline __global__ __launch_bounds__(256) void k_sens_unpack_v(const double* frag
     for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n * nzs; t += gridDim.x * blockDim.x) {
         const int r = t % nzs, c = t / nzs;
         out[t] = r < nz ? frag[((size_t)(r >> 4) * ksf + (c >> 2)) * 64 + (((c & 3) << 4) | (r & 15))] : 0.0;
+    }
+}
+
+// Design-time table of the rows form: T1 = A V + [0; Phi_rows] as [n][Rs] (zero pad rows).  Workgroup c rolls (e0 = unit_c,
+// v = d o V[:, c]) out through the shared A, B and reads the state rows where row_xidx says; the first nz entries are V[:, c].
+// eq_proj: T1 - Ghat[:, E] Ghat_EE^-1 T1[E] from the rows the projection took out of Ghat (GhatE [ne][Rs]) and WinvE = Ghat_EE^-1
+// ([ne][ne]); the rows E themselves exactly zero.
+// The handle's V = -G F' is a product with the rounded inverse and carries cond(H') times the FP64 unit into every entry (1e-9 on the
+// quadrotor: a VJP, whose terms cancel, then misses a few 1e-9 of its size).  The column is therefore refined once against the
+// design's own H, F (unscaled, column-major, as almpc_get_design hands them out):  v <- v - G (D H D v + D F[:, c]),  which leaves
+// what a factor-based solve gives (3.6e-11 against 4.1e-9 in the numpy restatement of this step, tests/sens_rows_ref.py).
+// LDS: the trajectory [(N+1)][n], ne doubles, and the column with its residual, 2 nz.
+struct SensRowsTableParams {
+    int n, m, N, nz, nzs, R, Rs, eq_proj, eq0, ne;
+    const double* A; const double* B; const double* V; const double* d;   // V [n][nzs] plain
+    const double* H; const double* F; const double* G;                    // H [nz][nz], F [n][nz] unscaled; G [nz][nzs] = H'^-1
+    const int* row_xidx;
+    const double* GhatE; const double* WinvE;
+    double* out;
+};
+__host__ __device__ inline int sens_rows_table_lds_doubles(int n, int N, int nz) { return (N + 1) * n + n + 2 * nz; }
+
+inline __global__ __launch_bounds__(256) void k_sens_rows_table(SensRowsTableParams p) {
+    extern __shared__ __attribute__((aligned(16))) double sens_tab_smem[];
+    const int n = p.n, m = p.m, N = p.N, nz = p.nz, c = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    double* X = sens_tab_smem;
+    double* le = X + (N + 1) * n;
+    double* v = le + n;
+    double* res = v + nz;
+    double* o = p.out + (size_t)c * p.Rs;
+    for (int j = tid; j < nz; j += nt) v[j] = p.V[(size_t)c * p.nzs + j];
+    for (int i = tid; i < n; i += nt) X[i] = i == c ? 1.0 : 0.0;
+    __syncthreads();
+    for (int i = tid; i < nz; i += nt) {   // residual of H' v = -F'[:, c] (H is symmetric: column i is row i)
+        double s = 0.0;
+        for (int j = 0; j < nz; ++j) s += p.H[(size_t)i * nz + j] * (p.d[j] * v[j]);
+        res[i] = p.d[i] * (s + p.F[(size_t)c * nz + i]);
+    }
+    __syncthreads();
+    for (int i = tid; i < nz; i += nt) {
+        double s = 0.0;
+        for (int j = 0; j < nz; ++j) s += p.G[(size_t)i * p.nzs + j] * res[j];
+        v[i] -= s;   // (every thread its own entries: nobody reads v in this loop)
+    }
+    __syncthreads();
+    for (int k = 0; k < N; ++k) {
+        for (int i = tid; i < n; i += nt) {
+            double s = 0.0;
+            for (int l = 0; l < n; ++l) s += p.A[i + l * n] * X[k * n + l];
+            for (int a = 0; a < m; ++a) s += p.B[i + a * n] * (p.d[k * m + a] * v[k * m + a]);
+            X[(k + 1) * n + i] = s;
+        }
+        __syncthreads();
+    }
+    if (p.eq_proj) {
+        for (int a = tid; a < p.ne; a += nt) {
+            double s = 0.0;
+            for (int e = 0; e < p.ne; ++e) s += p.WinvE[a * p.ne + e] * X[p.row_xidx[p.eq0 + e]];
+            le[a] = s;
+        }
+        __syncthreads();
+    }
+    for (int r = tid; r < p.Rs; r += nt) {
+        double t = r < nz ? v[r] : (r < p.R ? X[p.row_xidx[r]] : 0.0);
+        if (p.eq_proj && r < p.R) {
+            for (int a = 0; a < p.ne; ++a) t -= p.GhatE[(size_t)a * p.Rs + r] * le[a];
+            if (r >= p.eq0 && r < p.eq0 + p.ne) t = 0.0;
+        }
+        o[r] = t;
     }
 }
 

@@ -629,6 +629,9 @@ int almpc_group_get_results_wait(almpc_group* g, int ticket, double* x, double* 
 int almpc_group_sensitivity(almpc_group* g, uint32_t want, double act_tol);
 int almpc_group_get_sensitivity(almpc_group* g, double* K0, double* dU, double* dX, int32_t* rows);
 int almpc_group_sensitivity_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows);
+int almpc_group_sensitivity_rows(almpc_group* g, uint32_t want, double act_tol_u, double act_tol_x);
+int almpc_group_sensitivity_rows_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol_u, double act_tol_x,
+                                     double* g_x0, int32_t* rows);
 
 /* Design data for parity tests: H nz*nz, F nz*n (both unscaled, column-major), P n*n, d nz. */
 int almpc_get_design(almpc_handle* h, double* H, double* F, double* P, double* d);
@@ -661,7 +664,21 @@ int almpc_device_results(almpc_handle* h, const double** d_x, const double** d_e
  * An instance whose status is not ALMPC_SOLVED (or whose S is not positive definite to working precision) gets rows = -1 and zeros.
  * ALMPC_ERR_INVALID before the design's first step.  Served: almpc_design_shared and almpc_design_batched with an input box (shared or
  * per-instance references, S != 0).  ALMPC_ERR_UNSUPPORTED, with the reason in almpc_last_error: state rows (state box, terminal
- * equality), ALMPC_FLAG_STRUCTURED handles, almpc_design_ltv, the SQP loop and the re-linearisation pipeline.
+ * equality; see the rows form below), ALMPC_FLAG_STRUCTURED handles, almpc_design_ltv, the SQP loop and the re-linearisation pipeline.
+ *
+ * Rows form: almpc_sensitivity_rows / almpc_sensitivity_rows_vjp also serve almpc_design_shared with a state box and / or the terminal
+ * equality (shared or per-instance references, S != 0, instances redone by the stage-wise fallback).  W then ranges over the rows of
+ * A = [I; C']: input rows by the rule above with act_tol_u; a state-box row (stage k >= 2, state i) is in W iff
+ *     x[i,k] - xmin_i <= act_tol_x * max(1, |xmin_i|)   or   xmax_i - x[i,k] <= act_tol_x * max(1, |xmax_i|)
+ * on the returned x (act_tol_x <= 0 means 1e-7: a factor 100 above the 1e-9 the returned state rows keep to their bounds; a bound that
+ * is not finite or at least 1e300 in size is never active); every terminal-equality row is in W.  A state row's bound moves with x0,
+ * so with Ghat = A G A' and T1 = A V + [0; Phi_rows]:  S = Ghat[W,W],  du/dx0 = diag(d) (T1[0:nz] - Ghat[0:nz,W] S^-1 T1[W]) (input
+ * rows of W are zero), dX by the same rollout -- with an input box alone the formula above.  As there, at a weakly active row what
+ * comes out is the derivative of the face on which every flagged row is held.  rows [batch] = |W| over input, state and equality
+ * rows; -1 and zeros for an instance that is not ALMPC_SOLVED or whose S is not positive definite (a working set of more than nz
+ * rows among them).  Results go to the same buffers: almpc_get_sensitivity and almpc_device_sensitivity serve them.  On a design
+ * without state rows the rows form takes the path of almpc_sensitivity / almpc_sensitivity_vjp with act_tol = act_tol_u: the same
+ * bits.  Still ALMPC_ERR_UNSUPPORTED: per-instance models (almpc_design_batched) with state rows, and what is refused above.
  */
 #define ALMPC_SENS_K0 0x1u   /* [batch][n][m]        du[:,1]/dx0, column-major m x n per instance       */
 #define ALMPC_SENS_DU 0x2u   /* [batch][n][N][m]     Julia Array{Float64,4}(m, N, n, batch)             */
@@ -671,6 +688,9 @@ int almpc_get_sensitivity(almpc_handle* h, double* K0, double* dU, double* dX, i
 int almpc_device_sensitivity(almpc_handle* h, const double** d_K0, const double** d_dU, const double** d_dX, const int32_t** d_rows);
 int almpc_sensitivity_vjp(almpc_handle* h, const double* g_u, const double* g_x /* or NULL */, double act_tol,
                           double* g_x0 /* [batch][n] */, int32_t* rows /* or NULL */);
+int almpc_sensitivity_rows(almpc_handle* h, uint32_t want, double act_tol_u, double act_tol_x);
+int almpc_sensitivity_rows_vjp(almpc_handle* h, const double* g_u, const double* g_x /* or NULL */, double act_tol_u, double act_tol_x,
+                               double* g_x0 /* [batch][n] */, int32_t* rows /* or NULL */);
 
 /*
  * Timing of the last almpc_calculate (needs ALMPC_FLAG_TIMING): milliseconds spent in the ADMM

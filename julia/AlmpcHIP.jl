@@ -19,7 +19,8 @@ export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_s
        group_synchronize!, group_read_results!, group_set_state_rows!, group_set_rho_profile!, group_set_structured_fallback!,
        group_design_batched!, group_design_relin_fnn!, group_relin_step!, group_relin_advance!, group_advance_plant!, group_design_sqp_fnn!,
        group_sqp_start!, group_sqp_iterate!, group_sqp_solve!, group_set_sqp_hessian!, group_set_sqp_row_multipliers!, group_state_multipliers, group_sqp_skipped, group_x0_staging, group_update_initialization_staged!, group_results_async,
-       group_results_wait!, sensitivity, device_sensitivity, sensitivity_vjp, group_sensitivity, group_sensitivity_vjp
+       group_results_wait!, sensitivity, device_sensitivity, sensitivity_vjp, group_sensitivity, group_sensitivity_vjp,
+       sensitivity_rows, sensitivity_rows_vjp, group_sensitivity_rows, group_sensitivity_rows_vjp
 
 const libalmpc = get(ENV, "ALMPC_LIB", "libalmpc.so")
 
@@ -664,6 +665,32 @@ function sensitivity_vjp(mod::HipModeler, g_u::Array{Float64}, g_x::Union{Nothin
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), mod.handle, g_u, px, act_tol, g_x0, rows))
     return g_x0, rows
 end
+"""
+    sensitivity_rows(mod; K0 = true, dU = false, dX = false, act_tol_u = 0.0, act_tol_x = 0.0) -> (K0, dU, dX, rows)
+
+`sensitivity` for designs with `mpc_state_constraint` and / or `mpc_terminal_ingredient = "equality"` as well
+(`almpc_sensitivity_rows` + `almpc_get_sensitivity`): `rows` counts input, state-box and terminal-equality rows at a bound;
+`act_tol_x` is the state rows' threshold (0: 1e-7 of max(1, |bound|)).  Without state rows it is `sensitivity` with `act_tol_u`.
+"""
+function sensitivity_rows(mod::HipModeler; K0::Bool = true, dU::Bool = false, dX::Bool = false, act_tol_u::Real = 0.0, act_tol_x::Real = 0.0)
+    k, du, dx, rows = sens_arrays(mod.n, mod.m, mod.N, mod.batch, K0, dU, dX)
+    check(mod.handle, ccall((:almpc_sensitivity_rows, libalmpc), Cint, (Ptr{Cvoid}, UInt32, Cdouble, Cdouble), mod.handle,
+                            sens_mask(K0, dU, dX), act_tol_u, act_tol_x))
+    pf(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve k du dx check(mod.handle, ccall((:almpc_get_sensitivity, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), mod.handle, pf(k), pf(du), pf(dx), rows))
+    return k, du, dx, rows
+end
+"`sensitivity_vjp` in the rows form (`almpc_sensitivity_rows_vjp`)"
+function sensitivity_rows_vjp(mod::HipModeler, g_u::Array{Float64}, g_x::Union{Nothing,Array{Float64}} = nothing;
+                              act_tol_u::Real = 0.0, act_tol_x::Real = 0.0)
+    check_sens_sizes(mod.n, mod.m, mod.N, mod.batch, g_u, g_x)
+    g_x0, rows = Matrix{Float64}(undef, mod.n, mod.batch), Vector{Int32}(undef, mod.batch)
+    px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
+    GC.@preserve g_x check(mod.handle, ccall((:almpc_sensitivity_rows_vjp, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Ptr{Float64}, Ptr{Int32}), mod.handle, g_u, px, act_tol_u, act_tol_x, g_x0, rows))
+    return g_x0, rows
+end
 
 "library defaults of the options (OSQP's, plus the documented changes)"
 function default_opts()
@@ -824,6 +851,26 @@ function group_sensitivity_vjp(g::HipGroup, g_u::Array{Float64}, g_x::Union{Noth
     px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
     GC.@preserve g_x gcheck(g.group, ccall((:almpc_group_sensitivity_vjp, libalmpc), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), g.group, g_u, px, act_tol, g_x0, rows))
+    return g_x0, rows
+end
+"`sensitivity_rows` for the whole batch (`almpc_group_sensitivity_rows` + `almpc_group_get_sensitivity`)"
+function group_sensitivity_rows(g::HipGroup; K0::Bool = true, dU::Bool = false, dX::Bool = false, act_tol_u::Real = 0.0, act_tol_x::Real = 0.0)
+    k, du, dx, rows = sens_arrays(g.n, g.m, g.N, g.batch, K0, dU, dX)
+    gcheck(g.group, ccall((:almpc_group_sensitivity_rows, libalmpc), Cint, (Ptr{Cvoid}, UInt32, Cdouble, Cdouble), g.group,
+                          sens_mask(K0, dU, dX), act_tol_u, act_tol_x))
+    pf(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve k du dx gcheck(g.group, ccall((:almpc_group_get_sensitivity, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), g.group, pf(k), pf(du), pf(dx), rows))
+    return k, du, dx, rows
+end
+"`sensitivity_rows_vjp` for the whole batch (`almpc_group_sensitivity_rows_vjp`)"
+function group_sensitivity_rows_vjp(g::HipGroup, g_u::Array{Float64}, g_x::Union{Nothing,Array{Float64}} = nothing;
+                                    act_tol_u::Real = 0.0, act_tol_x::Real = 0.0)
+    check_sens_sizes(g.n, g.m, g.N, g.batch, g_u, g_x)
+    g_x0, rows = Matrix{Float64}(undef, g.n, g.batch), Vector{Int32}(undef, g.batch)
+    px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
+    GC.@preserve g_x gcheck(g.group, ccall((:almpc_group_sensitivity_rows_vjp, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Ptr{Float64}, Ptr{Int32}), g.group, g_u, px, act_tol_u, act_tol_x, g_x0, rows))
     return g_x0, rows
 end
 

@@ -6,6 +6,8 @@ DESIGN.md section 4 ("Sensitivities"):
                 read-back), and the same through Solver.sensitivity, which also copies the arrays to the host
     VJP         almpc_sensitivity_vjp with and without g_x: host pointers, so the call includes the upload of the loss gradients and
                 the read-back of g_x0
+    rows form   the same batch with a tight state box (+-3 (1, 1, 1, .5, .5, .5, .1, ..., .1), x0 clipped to 0.99 of it) and the terminal
+                equality, the library's default step: almpc_sensitivity_rows (K0; K0 + dU + dX) and almpc_sensitivity_rows_vjp
 medians over `reps` repetitions after a warm-up, with minimum and maximum.  There is no threshold: nothing exists to compare against.
 Run it under `rocprofv3 --kernel-trace --stats -- python tools/time_sensitivity.py` for the kernels' own times.
     python tools/time_sensitivity.py [reps=20] [batch=4096]"""
@@ -65,4 +67,29 @@ rng = np.random.default_rng(1)
 g_u, g_x = rng.normal(size=(batch, p.m, p.N)), rng.normal(size=(batch, p.n, p.N + 1))
 print(f"| `almpc_sensitivity_vjp`, g_u only | | {clock(lambda: s.sensitivity_vjp(g_u))} |")
 print(f"| `almpc_sensitivity_vjp`, g_u and g_x | | {clock(lambda: s.sensitivity_vjp(g_u, g_x))} |")
+s.close()
+
+# the state-row leg
+XBOX = 3.0 * np.array([1, 1, 1, .5, .5, .5, .1, .1, .1, .1, .1, .1])
+s = capi.Solver(p.n, p.m, p.N, batch)
+s.design_shared(p.A, p.B, p.Q, p.R, p.S, None, p.u_min, p.u_max, xmin=-XBOX, xmax=XBOX, terminal="equality")
+s.set_reference(p.x_ref, p.u_ref)
+s.update_initialization(np.clip(X0, -0.99 * XBOX, 0.99 * XBOX))
+t_step = clock(lambda: s.calculate())
+st = s.get_results(want=("status",))["status"]
+rows = s.sensitivity_rows(("K0",))["rows"]
+ok = rows[rows >= 0]
+print()
+print(f"state box and terminal equality: {int((st != 0).sum())} of {batch} not solved (infeasible); rows min {ok.min()} / median {int(np.median(ok))} / "
+      f"max {ok.max()}, {int((ok - p.n > 32).sum())} instances beyond the first tier (the {p.n} equality rows are projected out)")
+print()
+print("| call | us per call of the whole batch: median (min, max) | with the read-back to host arrays |")
+print("|---|---|---|")
+print(f"| `almpc_calculate` (state rows, default options; for scale) | {t_step} | |")
+for want in (("K0",), ("K0", "dU", "dX")):
+    mask = capi._sens_mask(want)
+    bare = clock(lambda: s._check(s.L.almpc_sensitivity_rows(s.h, mask, 0.0, 0.0)))
+    full = clock(lambda: s.sensitivity_rows(want))
+    print(f"| `almpc_sensitivity_rows`, {' + '.join(want)} | {bare} | {full} |", flush=True)
+print(f"| `almpc_sensitivity_rows_vjp`, g_u and g_x | | {clock(lambda: s.sensitivity_rows_vjp(g_u, g_x))} |")
 s.close()
