@@ -39,6 +39,11 @@ _hp = ctypes.c_void_p
 _lib = None
 
 
+class almpc_param_grads(ctypes.Structure):
+    """almpc.h: almpc_param_grads (almpc_sensitivity_params_vjp): host pointers, NULL = not wanted."""
+    _fields_ = [(k, _dp) for k in ("x0", "f", "u_ref", "u_min", "u_max", "Q", "P", "A", "R", "S", "B")] + [("rows", _ip)]
+
+
 def load():
     """Load libalmpc.so and declare the prototypes of include/almpc.h.  Raises OSError if the
     library has not been built (`make lib` or `python -c 'import __graft_entry__ as g; g.build()'`)."""
@@ -145,7 +150,10 @@ def load():
     L.almpc_sensitivity_rows_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.c_double, _dp, _ip]
     L.almpc_group_sensitivity_rows.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double]
     L.almpc_group_sensitivity_rows_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.c_double, _dp, _ip]
+    L.almpc_sensitivity_params_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.POINTER(almpc_param_grads)]
+    L.almpc_group_sensitivity_params_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.POINTER(almpc_param_grads)]
     for nm_ in ("almpc_sensitivity", "almpc_get_sensitivity", "almpc_device_sensitivity", "almpc_sensitivity_vjp",
+                "almpc_sensitivity_params_vjp", "almpc_group_sensitivity_params_vjp",
                 "almpc_group_sensitivity", "almpc_group_get_sensitivity", "almpc_group_sensitivity_vjp",
                 "almpc_sensitivity_rows", "almpc_sensitivity_rows_vjp", "almpc_group_sensitivity_rows", "almpc_group_sensitivity_rows_vjp"):
         getattr(L, nm_).restype = ctypes.c_int
@@ -287,6 +295,34 @@ def _sens_vjp(call, handle, check, g_u, g_x, act_tol, b, n, m, N):
     tols = tuple(float(t) for t in act_tol) if isinstance(act_tol, tuple) else (float(act_tol),)
     check(call(handle, _ptr(g_u), _ptr(g_x), *tols, _ptr(g_x0), rows.ctypes.data_as(_ip)))
     return g_x0, rows
+
+
+PARAM_GROUPS = ("x0", "f", "u_ref", "u_min", "u_max", "Q", "P", "A", "R", "S", "B")   # almpc.h: the fields of almpc_param_grads
+
+
+def _sens_params_vjp(call, handle, check, g_u, g_x, want, act_tol, b, n, m, N):
+    """almpc_sensitivity_params_vjp: {group: array} for the groups `want` names, Julia-shaped with the batch axis first -- x0 (b, n),
+    f and u_ref (b, m, N), u_min / u_max (b, m), Q / P / A (b, n, n), R / S (b, m, m), B (b, n, m) --, and rows (b,)."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    for k in want:
+        if k not in PARAM_GROUPS:
+            raise ValueError(f"unknown parameter group {k!r} (one of {PARAM_GROUPS})")
+    g_u = np.ascontiguousarray(np.asarray(g_u, dtype=np.float64).reshape(b, m, N).transpose(0, 2, 1))
+    if g_x is not None:
+        g_x = np.ascontiguousarray(np.asarray(g_x, dtype=np.float64).reshape(b, n, N + 1).transpose(0, 2, 1))
+    # the C layouts: stage-major trajectories, column-major matrices
+    shapes = {"x0": (b, n), "f": (b, N, m), "u_ref": (b, N, m), "u_min": (b, m), "u_max": (b, m), "Q": (b, n, n), "P": (b, n, n),
+              "A": (b, n, n), "R": (b, m, m), "S": (b, m, m), "B": (b, m, n)}
+    # (one block for all of them: several fresh arrays of this size cost the read-back ten times what the copies take)
+    sizes = [int(np.prod(shapes[k])) for k in want]
+    block, offs = np.empty(sum(sizes)), np.cumsum([0] + sizes)
+    raw = {k: block[offs[i]:offs[i + 1]].reshape(shapes[k]) for i, k in enumerate(want)}
+    rows = np.empty(b, dtype=np.int32)
+    out = almpc_param_grads(**{k: _ptr(v) for k, v in raw.items()}, rows=rows.ctypes.data_as(_ip))
+    check(call(handle, _ptr(g_u), _ptr(g_x), float(act_tol), ctypes.byref(out)))
+    res = {k: (v if v.ndim == 2 else v.transpose(0, 2, 1)) for k, v in raw.items()}
+    res["rows"] = rows
+    return res
 
 
 def _want_mask(want):
@@ -942,6 +978,13 @@ class Solver:
         trajectories (almpc_sensitivity_vjp: no Jacobian is formed); also returns rows (batch,)."""
         return _sens_vjp(self.L.almpc_sensitivity_vjp, self.h, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
 
+    def sensitivity_params_vjp(self, g_u, g_x=None, want=PARAM_GROUPS, act_tol=0.0) -> dict:
+        """Gradients of the loss of sensitivity_vjp in the problem data, per instance (almpc_sensitivity_params_vjp): x0, the QP's
+        linear term f, u_ref, the input box, the weights Q, P, R, S and the model A, B -- what `want` names -- and rows.  For a shared
+        design the caller sums over the batch."""
+        return _sens_params_vjp(self.L.almpc_sensitivity_params_vjp, self.h, self._check, g_u, g_x, want, act_tol, self.batch, self.n,
+                                self.m, self.N)
+
     def sensitivity_rows(self, want=("K0", "dU", "dX"), act_tol_u=0.0, act_tol_x=0.0) -> dict:
         """sensitivity for shared designs with a state box and / or the terminal equality as well (almpc_sensitivity_rows +
         almpc_get_sensitivity): rows counts input, state-box and terminal-equality rows at a bound; act_tol_x is the state rows'
@@ -1299,6 +1342,11 @@ class Group:
     def sensitivity_vjp(self, g_u, g_x=None, act_tol=0.0):
         """Solver.sensitivity_vjp for the whole batch (almpc_group_sensitivity_vjp)."""
         return _sens_vjp(self.L.almpc_group_sensitivity_vjp, self.g, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
+
+    def sensitivity_params_vjp(self, g_u, g_x=None, want=PARAM_GROUPS, act_tol=0.0) -> dict:
+        """Solver.sensitivity_params_vjp for the whole batch (almpc_group_sensitivity_params_vjp)."""
+        return _sens_params_vjp(self.L.almpc_group_sensitivity_params_vjp, self.g, self._check, g_u, g_x, want, act_tol, self.batch,
+                                self.n, self.m, self.N)
 
     def sensitivity_rows(self, want=("K0", "dU", "dX"), act_tol_u=0.0, act_tol_x=0.0) -> dict:
         """Solver.sensitivity_rows for the whole batch (almpc_group_sensitivity_rows + almpc_group_get_sensitivity)."""

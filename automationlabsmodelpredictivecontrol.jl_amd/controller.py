@@ -37,7 +37,7 @@ __all__ = [
     "TerminalIngredient", "ModelPredictiveControlTuning", "ModelPredictiveControlResults",
     "ModelPredictiveControlController", "proceed_controller", "_design_reference_mpc",
     "_model_predictive_control_design", "_create_weights_coefficients", "update_initialization", "calculate",
-    "_model_predictive_control_computation", "sensitivity", "HipModeler", "shard_range",
+    "_model_predictive_control_computation", "sensitivity", "sensitivity_params", "HipModeler", "shard_range",
 ]
 
 
@@ -588,6 +588,17 @@ def sensitivity(C: ModelPredictiveControlController, want=("K0",), act_tol: floa
         out = mod.solver.sensitivity_rows(want, act_tol, act_tol_x)
     else:
         out = mod.solver.sensitivity(want, act_tol)
+    return {k: (v[0] if mod.batch == 1 else v) for k, v in out.items()}
+
+
+def sensitivity_params(C: ModelPredictiveControlController, g_u, g_x=None, want=_capi.PARAM_GROUPS, act_tol: float = 0.0) -> dict:
+    """Gradients of a loss on the last calculate!(C) in the problem data (beside `sensitivity`, an extension of this build): for loss
+    gradients g_u (m, N) and g_x (n, N+1) on the returned trajectories (a leading batch axis when the controller has more than one
+    instance) the gradients in x0, the QP's linear term f, u_ref, the input box (u_min, u_max), the weights Q, P, R, S and the model
+    A, B -- what `want` names -- per instance, and rows.  Linear controllers with an input box (Solver.sensitivity_params_vjp says
+    what is refused); the terminal weight counts as data also where the design computed it."""
+    mod: HipModeler = C.tuning.modeler
+    out = mod.solver.sensitivity_params_vjp(g_u, g_x, want, act_tol)
     return {k: (v[0] if mod.batch == 1 else v) for k, v in out.items()}
 
 

@@ -238,6 +238,15 @@ struct almpc_handle {
         DevBuf<double> gu, gx, gx0;     // VJP: uploaded loss gradients, result [batch][n]
         DevBuf<int32_t> vrows;          // [batch] |W| of the last VJP
         bool stepped = false;           // a step has run on the current design
+        // parameter gradients (almpc_sensitivity_params_vjp): the design's Q and whether it kept R, host side (every condensed design
+        // leaves them); the rest is made at the first such call
+        std::vector<double> Q;
+        int useR = 0;
+        DevBuf<double> W;               // [Q n*n | S m*m | P n*n] device copies of the weights (P: a shared design's; else the handle's bP)
+        bool w_ok = false;              // ... of the current design
+        DevBuf<double> pz;              // [batch][nz] z | [batch][nz] nu | [batch][m] dL/dumin | [batch][m] dL/dumax (k_sens_pz)
+        DevBuf<double> pout;            // k_sens_params' outputs: u_ref, Q, P, A, R, S, B, each [batch][its size]
+        DevBuf<double> traj;            // [workgroups][3][(N+1) n] zeta, mu, al of the instance a workgroup is at
     } sens;
     // stage-wise dual active-set solve (k_sdual, csrc/almpc_sdual.hip.h): input box, state box, terminal equality and S in the
     // multiple-shooting form; stage records of the unconstrained problem (shared: host Riccati at design time)
@@ -1178,7 +1187,7 @@ int wait_and_settle(almpc_handle* h, bool blocking_only = false) {
 
 // A new design voids a redo that was deferred for a step of the previous one (its models, references and results are about to go)
 void drop_lazy_redo(almpc_handle* h) {
-    h->sens.stepped = false; h->sens.v_ok = false; h->sens.t1_ok = false; h->sens.have = 0;   // (what a sensitivity call looks at goes with the design as well)
+    h->sens.stepped = false; h->sens.v_ok = false; h->sens.t1_ok = false; h->sens.w_ok = false; h->sens.have = 0;   // (what a sensitivity call looks at goes with the design as well)
     h->redo.lazy_pending = false;
     h->redo.expected = false;
     if (h->redo.hUnsolved) h->redo.unsolved_seen = *reinterpret_cast<volatile int*>(h->redo.hUnsolved.get());
@@ -1601,6 +1610,7 @@ static int design_shared_condensed(almpc_handle* h, const double* A, const doubl
     const hm::mat Sm = hm::symmetrised(S, m);   // S enters the cost as a quadratic form: only its symmetric part counts
     h->hS = Sm;
     h->useS = (Rm[0] != 0.0 && Sm[0] != 0.0) ? 1 : 0;  // the reference drops the S term together with R (src/sub/design_mpc.jl:423-466)
+    h->sens.Q = Qm; h->sens.useR = Rm[0] != 0.0;
     h->rho = rho; h->sigma = sigma;
 
     // ---- state rows (state box, terminal equality): row tables and the shared constraint-space matrix
@@ -2048,6 +2058,7 @@ int batched_design_front(almpc_handle* h, const double* A_batch, const double* B
     h->rho = rho; h->sigma = sigma;
     d.useR = Rm[0] != 0.0; d.useS = d.useR && Sm[0] != 0.0;
     h->useS = d.useS;
+    h->sens.Q = Qm; h->sens.useR = d.useR;
     tr("host preparation");
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     tr("stream idle");
@@ -4382,6 +4393,101 @@ int sens_vjp(almpc_handle* h, const char* who, bool rows_form, const double* g_u
     return ALMPC_OK;
 }
 
+// almpc_sensitivity_params_vjp: k_sens_pz (the VJP with z, nu and the bound gradients), then k_sens_params where a group behind the
+// stage recursions is wanted; only the wanted groups are computed and copied.
+int sens_params_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, const almpc_param_grads* out) {
+    const char* who = "sensitivity_params_vjp";
+    ALMPC_TRY(sens_check(h, who));
+    if (!g_u || !out) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": null g_u or out");
+    const bool want2 = out->u_ref || out->Q || out->P || out->A || out->R || out->S || out->B;   // (a group of k_sens_params)
+    if (!want2 && !out->x0 && !out->f && !out->u_min && !out->u_max && !out->rows)
+        return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": every pointer of out is null");
+    const int ni = h->n, mi = h->m, nz = h->nz, nzs = h->nzs;
+    if (h->sens.Q.size() != (size_t)ni * ni || h->hS.size() != (size_t)mi * mi || (!h->batched && h->P.size() != (size_t)ni * ni))
+        return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": the design's weights are not kept");
+    // the dynamic LDS of all three kernels, in front of everything the call enqueues
+    const size_t lds1 = (size_t)SENS_WAVES * sens_pz_lds_doubles(ni, nzs, SENS_CAP1) * sizeof(double);
+    const size_t lds2 = nz > SENS_CAP1 ? (size_t)sens_pz_lds_doubles(ni, nzs, nz) * sizeof(double) : 0;
+    const size_t lds3 = (size_t)sens_grad_lds_doubles(ni) * sizeof(double);
+    if (lds1 > 160 * 1024 || lds2 > 160 * 1024 || lds3 > 160 * 1024)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, std::string(who) + ": the working set does not fit LDS");
+    HIP_TRY(h, hipSetDevice(h->device));
+    ALMPC_TRY(wait_and_settle(h));
+    const size_t b = (size_t)h->batch, n = (size_t)ni, m = (size_t)mi, xs = n * (h->N + 1);
+    SensParams p;
+    ALMPC_TRY(sens_params(h, act_tol, p));
+    HIP_TRY(h, h->sens.vrows.grow(b)); HIP_TRY(h, h->sens.gx0.grow(b * n)); HIP_TRY(h, h->sens.gu.grow(b * nz));
+    HIP_TRY(h, h->sens.pz.grow(b * (2 * (size_t)nz + 2 * m)));
+    HIP_TRY(h, hipMemcpyAsync(h->sens.gu, g_u, b * nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (g_x) {
+        HIP_TRY(h, h->sens.gx.grow(b * xs));
+        HIP_TRY(h, hipMemcpyAsync(h->sens.gx, g_x, b * xs * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    p.g_u = h->sens.gu; p.g_x = g_x ? h->sens.gx.get() : nullptr; p.g_x0 = h->sens.gx0; p.rows = h->sens.vrows;
+    p.z = h->sens.pz; p.nu = p.z + b * nz; p.gmin = p.nu + b * nz; p.gmax = p.gmin + b * m;
+    // the two tiers, as sens_launch
+    HIP_TRY(h, hipMemsetAsync(h->sens.ovf, 0, SENS_OVF_HEAD * sizeof(int32_t), h->stream));
+    p.cap = SENS_CAP1; p.lds_per_team = sens_pz_lds_doubles(ni, nzs, p.cap);
+    HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens_pz<false>), lds1));
+    hipLaunchKernelGGL((k_sens_pz<false>), dim3((unsigned)((h->batch + SENS_WAVES - 1) / SENS_WAVES)), dim3(64 * SENS_WAVES), lds1, h->stream, p);
+    HIP_TRY(h, hipGetLastError());
+    if (nz > SENS_CAP1) {
+        p.cap = nz; p.lds_per_team = sens_pz_lds_doubles(ni, nzs, p.cap);
+        HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens_pz<true>), lds2));
+        hipLaunchKernelGGL((k_sens_pz<true>), dim3((unsigned)std::min(h->batch, 4 * h->num_cus)), dim3(SENS_WG), lds2, h->stream, p);
+        HIP_TRY(h, hipGetLastError());
+    }
+    const size_t off_ur = 0, off_Q = off_ur + b * nz, off_P = off_Q + b * n * n, off_A = off_P + b * n * n, off_R = off_A + b * n * n,
+                 off_S = off_R + b * m * m, off_B = off_S + b * m * m, out_total = off_B + b * n * m;
+    if (want2) {
+        if (!h->sens.w_ok) {   // (once per design, in stream order in front of k_sens_params)
+            HIP_TRY(h, h->sens.W.grow(2 * n * n + m * m));
+            HIP_TRY(h, hipMemcpyAsync(h->sens.W, h->sens.Q.data(), n * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(h->sens.W + n * n, h->hS.data(), m * m * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            if (!h->batched) HIP_TRY(h, hipMemcpyAsync(h->sens.W + n * n + m * m, h->P.data(), n * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            h->sens.w_ok = true;
+        }
+        const int grid = std::min(h->batch, 8 * h->num_cus);
+        HIP_TRY(h, h->sens.pout.grow(out_total));
+        HIP_TRY(h, h->sens.traj.grow((size_t)grid * 3 * xs));
+        SensGradParams q = SensGradParams();
+        q.n = ni; q.m = mi; q.N = h->N; q.nz = nz; q.batch = h->batch; q.useR = h->sens.useR; q.useS = h->useS;
+        q.A = p.A; q.A_stride = p.A_stride; q.B = p.B; q.B_stride = p.B_stride;
+        q.Q = h->sens.W; q.S = h->sens.W + n * n;
+        if (h->batched) { q.P = h->bP; q.P_stride = h->bP_stride; }
+        else { q.P = h->sens.W + n * n + m * m; q.P_stride = 0; }
+        q.ex = h->dEx; q.ev = h->dEu; q.u = h->dU; q.g_u = p.g_u; q.g_x = p.g_x; q.z = p.z; q.nu = p.nu; q.rows = p.rows;
+        q.traj = h->sens.traj;
+        double* o = h->sens.pout;
+        q.gur = out->u_ref ? o + off_ur : nullptr; q.gQ = out->Q ? o + off_Q : nullptr; q.gP = out->P ? o + off_P : nullptr;
+        q.gA = out->A ? o + off_A : nullptr; q.gR = out->R ? o + off_R : nullptr; q.gS = out->S ? o + off_S : nullptr;
+        q.gB = out->B ? o + off_B : nullptr;
+        HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens_params), lds3));
+        hipLaunchKernelGGL(k_sens_params, dim3((unsigned)grid), dim3(256), lds3, h->stream, q);
+        HIP_TRY(h, hipGetLastError());
+    }
+    const auto back = [&](double* dst, const double* src, size_t count) {
+        return dst ? hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+    };
+    HIP_TRY(h, back(out->x0, h->sens.gx0, b * n));
+    HIP_TRY(h, back(out->f, p.z, b * nz));
+    HIP_TRY(h, back(out->u_min, p.gmin, b * m));
+    HIP_TRY(h, back(out->u_max, p.gmax, b * m));
+    if (want2) {
+        const double* o = h->sens.pout;
+        HIP_TRY(h, back(out->u_ref, o + off_ur, b * nz));
+        HIP_TRY(h, back(out->Q, o + off_Q, b * n * n));
+        HIP_TRY(h, back(out->P, o + off_P, b * n * n));
+        HIP_TRY(h, back(out->A, o + off_A, b * n * n));
+        HIP_TRY(h, back(out->R, o + off_R, b * m * m));
+        HIP_TRY(h, back(out->S, o + off_S, b * m * m));
+        HIP_TRY(h, back(out->B, o + off_B, b * n * m));
+    }
+    if (out->rows) HIP_TRY(h, hipMemcpyAsync(out->rows, h->sens.vrows, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, stream_wait_polling(h));
+    return ALMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4425,6 +4531,10 @@ int almpc_sensitivity_vjp(almpc_handle* h, const double* g_u, const double* g_x,
 int almpc_sensitivity_rows_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol_u, double act_tol_x, double* g_x0,
                                int32_t* rows) {
     return sens_vjp(h, "sensitivity_rows_vjp", true, g_u, g_x, act_tol_u, act_tol_x, g_x0, rows);
+}
+
+int almpc_sensitivity_params_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, const almpc_param_grads* out) {
+    return sens_params_vjp(h, g_u, g_x, act_tol, out);
 }
 
 }  // extern "C"

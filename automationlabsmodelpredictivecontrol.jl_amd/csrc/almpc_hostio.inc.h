@@ -648,6 +648,20 @@ int almpc_group_sensitivity_rows_vjp(almpc_group* g, const double* g_u, const do
                                           rows ? rows + f : nullptr);
     });
 }
+// ... and the parameter gradients (almpc_sensitivity_params_vjp): every output is per instance, so the shards' slices are disjoint
+int almpc_group_sensitivity_params_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, const almpc_param_grads* out) {
+    if (!g || !g_u || !out) return ALMPC_ERR_INVALID;
+    const size_t n = (size_t)g->n, m = (size_t)g->m, nz = m * g->N;
+    return group_fanout(g, [&](int i) {
+        const size_t f = (size_t)g->first[i];
+        const auto at = [f](double* ptr, size_t per) { return ptr ? ptr + f * per : nullptr; };
+        almpc_param_grads o;
+        o.x0 = at(out->x0, n); o.f = at(out->f, nz); o.u_ref = at(out->u_ref, nz); o.u_min = at(out->u_min, m); o.u_max = at(out->u_max, m);
+        o.Q = at(out->Q, n * n); o.P = at(out->P, n * n); o.A = at(out->A, n * n); o.R = at(out->R, m * m); o.S = at(out->S, m * m);
+        o.B = at(out->B, n * m); o.rows = out->rows ? out->rows + f : nullptr;
+        return almpc_sensitivity_params_vjp(g->hs[i], g_u + f * nz, g_x ? g_x + f * n * (g->N + 1) : nullptr, act_tol, &o);
+    });
+}
 
 // Asynchronous read-back of the whole batch: the request goes to every device (pack kernels / copy streams), the ticket is the group's;
 // almpc_group_get_results_wait gathers into the caller's arrays (layouts of almpc_group_get_results).  The last two tickets are kept.

@@ -41,6 +41,28 @@
 // the terminal equality E (eq_proj) the same formula holds in projected quantities: the list is W' = W \ E, Ghat as stored, T1
 // projected by the table kernel; `rows` still reports |W|.  A working set of more than nz rows (nz - n projected) cannot be
 // independent: rows = -1 and zeros, as for a failed Cholesky.
+//
+// Parameter gradients (almpc_sensitivity_params_vjp: k_sens_pz, then k_sens_params): the same loss, differentiated in the problem data
+// on the face where W is held.  Stages 1-based, v = e_u, e_x[:,1] = e0, sym(a, b) = a b' + b a', Qbar_1 = 0, Qbar_k = Q (k = 2..N),
+// Qbar_{N+1} = P.  With q_k = g_u[:,k] + B'lam_{k+1} (all rows, unscaled):
+//     z_W = 0,  z_F = -H_FF^-1 q_F;   nu_j = q_j + (H z)_j on the rows of W, 0 elsewhere (the gradient in the bound the row sits at)
+// On the device, from the VJP's factor:  p = d o q (p_W = 0),  t = S^-1 G[W,:] p,  z = -d o (G p - G[:,W] t) (rows W written as zeros),
+// nu_j = q_j + t_a / d_j for j = W[a] -- k_sens_pz = the VJP body plus the product G p (thread j on row j of G, read as column j).
+//     zeta_1 = 0,  zeta_{k+1} = A zeta_k + B z_k                                     (the step's rollout from (0, z))
+//     mu_{N+1} = g_x[N+1] + 2 P zeta_{N+1},   mu_k = A'mu_{k+1} + g_x[k] + 2 Qbar_k zeta_k
+//     al_{N+1} = 2 P e_x[:,N+1],              al_k = A'al_{k+1} + 2 Qbar_k e_x[:,k]
+//     dL/dx0 = mu_1 = lam_1 + F'z (handed out by the VJP's own expression: the bits of almpc_sensitivity_vjp),   dL/df = z
+//     dL/dQ = sum_{k=2..N} sym(zeta_k, e_x[:,k]),  dL/dP = sym(zeta_{N+1}, e_x[:,N+1]),  dL/dR = sum_{k=1..N} sym(z_k, v_k)
+//     dL/dS = sum_{k=1..N-1} sym(z_k - z_{k+1}, u_k - u_{k+1})                        (the rate cost is on u, not on e_u)
+//     dL/dA = sum_{k=1..N} mu_{k+1} e_x[:,k]' + al_{k+1} zeta_k',   dL/dB = sum_{k=1..N} mu_{k+1} v_k' + al_{k+1} z_k'
+//     dL/du_ref[:,k] = g_u[:,k] - nu_k + 2 S (z_k - z_{k+1}) - 2 S (z_{k-1} - z_k)    (S terms only where S is in the design; the
+//                                                                                     differences z_0 - z_1, z_N - z_{N+1} are absent)
+//     dL/dumin_i = sum_k nu_(k,i) over the rows at the lower bound, dL/dumax_i over those at the upper (at both: lower)
+// Conventions: a symmetric matrix gradient G_Q is the symmetric matrix with dL = sum_ij (G_Q)_ij dQ_ij for symmetric dQ.  P is data,
+// also where the design computed it as a DARE: its dependence on A, B, Q, R is not followed.  Where the design dropped R or S (the
+// reference's [1,1] rule, src/sub/design_mpc.jl:423-456) that gradient is zero.  x_ref needs no output:
+// dL/dx_ref[:,1] = g_x[1] - dL/dx0 and dL/dx_ref[:,k] = g_x[k] for k >= 2.  Weakly active rows: as above, the derivative of the face on
+// which every flagged row is held.  Every sum runs in ascending stage order in one thread: the same bits wherever the instance sits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -80,6 +102,8 @@ struct SensParams {
     const double* xmin; const double* xmax;          // [n]
     const int* row_xidx; const int* row_eq;          // [Rs] a state row's place in x, whether it is an equality row
     double tau_x;
+    // parameter gradients (k_sens_pz): z = dL/df and nu [batch][nz], the bound gradients [batch][m]
+    double* z; double* nu; double* gmin; double* gmax;
 };
 
 __host__ __device__ inline int sens_ch(int n) { const int c = (n + 3) & ~3; return c < 16 ? c : 16; }
@@ -88,6 +112,9 @@ __host__ __device__ inline int sens_lds_doubles(int n, int nzs, int cap, int nfl
     const int ints = cap + nfl + 4;
     return (cap * (cap | 1) + cap * sens_ch(n) + nzs + cap + 2 * n + (ints + 1) / 2 + 1) & ~1;
 }
+
+// k_sens_pz keeps q on the rows of W (then nu) behind the VJP's team LDS
+__host__ __device__ inline int sens_pz_lds_doubles(int n, int nzs, int cap) { return sens_lds_doubles(n, nzs, cap, nzs) + ((nzs + 1) & ~1); }
 
 template <bool WG>
 struct SensTeam {
@@ -143,8 +170,16 @@ __device__ __forceinline__ void sens_zero(const SensParams& p, const SensTeam<WG
     }
 }
 
-template <bool VJP, bool WG, bool ROWS>
+template <bool WG>
+__device__ __forceinline__ void sens_zero_pz(const SensParams& p, const SensTeam<WG>& T, int inst) {
+    for (int j = T.tid; j < p.nz; j += T.nt) { p.z[(size_t)inst * p.nz + j] = 0.0; p.nu[(size_t)inst * p.nz + j] = 0.0; }
+    for (int i = T.tid; i < p.m; i += T.nt) { p.gmin[(size_t)inst * p.m + i] = 0.0; p.gmax[(size_t)inst * p.m + i] = 0.0; }
+}
+
+// (PAR: the VJP with z, nu and the bound gradients behind it -- k_sens_pz; no rows form)
+template <bool VJP, bool WG, bool ROWS, bool PAR = false>
 __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTeam<WG>& T, int inst, double* L) {
+    static_assert(!PAR || (VJP && !ROWS), "the parameter gradients extend the VJP of the input-box form");
     const int n = p.n, m = p.m, N = p.N, nz = p.nz, nzs = p.nzs, cap = p.cap, ch = p.ch, ld = cap | 1;
     const int gs = ROWS ? p.Rs : nzs;   // stride of a row of G (Ghat) and of a column of V (T1); the rows that carry a flag
     double* S = L;
@@ -163,6 +198,7 @@ __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTea
     // 1: the rows at a bound
     if (!WG && p.status[inst] != 0) {   // (the second tier only gets solved instances)
         sens_zero<VJP>(p, T, inst);
+        if (PAR) sens_zero_pz(p, T, inst);
         if (T.tid == 0) p.rows[inst] = -1;
         return;
     }
@@ -200,6 +236,7 @@ __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTea
     const int rows = word[0];
     if (ROWS && rows > p.cap2) {   // more rows than free directions: not independent
         sens_zero<VJP>(p, T, inst);
+        if (PAR) sens_zero_pz(p, T, inst);
         if (T.tid == 0) p.rows[inst] = -1;
         return;
     }
@@ -236,6 +273,7 @@ __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTea
     }
     if (word[1]) {
         sens_zero<VJP>(p, T, inst);
+        if (PAR) sens_zero_pz(p, T, inst);
         if (T.tid == 0) p.rows[inst] = -1;
         return;
     }
@@ -285,6 +323,7 @@ __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTea
         const double* gx = p.g_x ? p.g_x + (size_t)inst * (N + 1) * n : nullptr;
         double* cur = lam;
         double* nxt = lam + n;
+        double* qv = L + sens_lds_doubles(n, nzs, cap, nzs);   // (PAR) q on the rows of W, zero elsewhere
         // (0.0 is added where g_x is null, so that a null g_x and a g_x of zeros give the same bits)
         for (int i = T.tid; i < n; i += T.nt) cur[i] = 0.0 + (gx ? gx[(size_t)N * n + i] : 0.0);
         T.sync();
@@ -294,6 +333,7 @@ __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTea
                 for (int i = 0; i < n; ++i) s += B[i + a * n] * cur[i];
                 const int j = k * m + a;
                 pv[j] = act[j] ? 0.0 : dv[j] * (gu[j] + s);
+                if (PAR) qv[j] = act[j] ? gu[j] + s : 0.0;
             }
             for (int i = T.tid; i < n; i += T.nt) {
                 double s = 0.0;
@@ -318,6 +358,27 @@ __device__ __forceinline__ void sens_instance(const SensParams& p, const SensTea
             for (int a = 0; a < rows; ++a) s2 += v[wl[a]] * tv[a];
             p.g_x0[(size_t)inst * n + c] = cur[c] + s1 - s2;
         }
+        if (PAR) {
+            for (int a = T.tid; a < rows; a += T.nt) qv[wl[a]] += tv[a] / dv[wl[a]];   // nu
+            T.sync();
+            for (int j = T.tid; j < nz; j += T.nt) {   // row j of G p - G[:,W] t, read as column j: contiguous across the team
+                double s = 0.0;
+                for (int i = 0; i < nz; ++i) s += G[(size_t)i * gs + j] * pv[i];
+                for (int a = 0; a < rows; ++a) s -= G[(size_t)wl[a] * gs + j] * tv[a];
+                p.z[(size_t)inst * nz + j] = act[j] ? 0.0 : -dv[j] * s;
+                p.nu[(size_t)inst * nz + j] = qv[j];
+            }
+            for (int i = T.tid; i < m; i += T.nt) {   // ascending stages; a row at both bounds counts as lower
+                double lo = 0.0, hi = 0.0;
+                for (int k = 0; k < N; ++k) {
+                    const int j = k * m + i;
+                    if (!act[j]) continue;
+                    if (p.u[(size_t)inst * nz + j] - p.umin[i] <= p.tau * dv[j]) lo += qv[j];
+                    else hi += qv[j];
+                }
+                p.gmin[(size_t)inst * m + i] = lo; p.gmax[(size_t)inst * m + i] = hi;
+            }
+        }
     }
 }
 
@@ -334,6 +395,161 @@ __global__ __launch_bounds__(256) void k_sens(SensParams p) {
         double* L = sens_smem + (size_t)wv * p.lds_per_team;
         const int wpb = (int)(blockDim.x >> 6), nwaves = gridDim.x * wpb;
         for (int inst = blockIdx.x * wpb + wv; inst < p.batch; inst += nwaves) sens_instance<VJP, WG, ROWS>(p, T, inst, L);
+    }
+}
+
+// The VJP with z, nu and the bound gradients behind it (almpc_sensitivity_params_vjp): k_sens's grid, both tiers
+template <bool WG>
+__global__ __launch_bounds__(256) void k_sens_pz(SensParams p) {
+    extern __shared__ __attribute__((aligned(16))) double sens_pz_smem[];
+    if (WG) {
+        const SensTeam<WG> T{(int)threadIdx.x, (int)blockDim.x};
+        const int count = p.ovf[0];
+        for (int k = blockIdx.x; k < count; k += gridDim.x) sens_instance<true, WG, false, true>(p, T, p.ovf[SENS_OVF_HEAD + k], sens_pz_smem);
+    } else {
+        const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        const SensTeam<WG> T{(int)(threadIdx.x & 63), 64};
+        double* L = sens_pz_smem + (size_t)wv * p.lds_per_team;
+        const int wpb = (int)(blockDim.x >> 6), nwaves = gridDim.x * wpb;
+        for (int inst = blockIdx.x * wpb + wv; inst < p.batch; inst += nwaves) sens_instance<true, WG, false, true>(p, T, inst, L);
+    }
+}
+
+// Stage recursions and outer-product sums of the parameter gradients, behind k_sens_pz on the same stream.  One workgroup per
+// instance (grid-stride); stage vectors in LDS (6 n doubles), the trajectories zeta, mu, al in the workgroup's slice of a scratch
+// buffer ([grid][3][(N+1) n]: written and read by this workgroup alone, a barrier in between).  Then every output entry is one
+// thread's sum over the stages, ascending, in one register.  Q, P, S are read as M + M' (twice their symmetric part).
+// Outputs column-major per instance: Q, P, A n x n, B n x m, R, S m x m; u_ref [N][m].  rows < 0: zeros.
+struct SensGradParams {
+    int n, m, N, nz, batch, useR, useS;
+    const double* A; long A_stride;
+    const double* B; long B_stride;
+    const double* Q; const double* S;           // [n][n], [m][m]: the design's weights
+    const double* P; long P_stride;
+    const double* ex; const double* ev; const double* u;   // the step's e_x [batch][N+1][n], e_u and u [batch][nz]
+    const double* g_u; const double* g_x;       // as k_sens (g_x may be null)
+    const double* z; const double* nu;          // [batch][nz] from k_sens_pz
+    const int32_t* rows;
+    double* traj;
+    double *gur, *gQ, *gP, *gA, *gR, *gS, *gB;  // null where not wanted
+};
+__host__ __device__ inline int sens_grad_lds_doubles(int n) { return 6 * n; }
+
+inline __global__ __launch_bounds__(256) void k_sens_params(SensGradParams p) {
+    extern __shared__ __attribute__((aligned(16))) double sens_grad_smem[];
+    const int n = p.n, m = p.m, N = p.N, nz = p.nz, tid = threadIdx.x, nt = blockDim.x, xs = (N + 1) * n;
+    double* zc = sens_grad_smem;
+    double* zn = zc + n;
+    double* cur = zn + n;       // [mu | al]
+    double* nxt = cur + 2 * n;
+    double* Zt = p.traj + (size_t)blockIdx.x * 3 * xs;
+    double* Mt = Zt + xs;
+    double* At = Mt + xs;
+    const int oP = n * n, oA = 2 * n * n, oB = 3 * n * n, oR = oB + n * m, oS = oR + m * m, oU = oS + m * m, total = oU + nz;
+    for (int inst = blockIdx.x; inst < p.batch; inst += gridDim.x) {
+        const bool ok = p.rows[inst] >= 0;   // (one word for the whole workgroup)
+        const double* A = p.A + (size_t)inst * p.A_stride;
+        const double* B = p.B + (size_t)inst * p.B_stride;
+        const double* P = p.P + (size_t)inst * p.P_stride;
+        const double* ex = p.ex + (size_t)inst * xs;
+        const double* ev = p.ev + (size_t)inst * nz;
+        const double* u = p.u + (size_t)inst * nz;
+        const double* z = p.z + (size_t)inst * nz;
+        const double* gx = p.g_x ? p.g_x + (size_t)inst * xs : nullptr;
+        __syncthreads();   // (the previous instance's sums have read the trajectories and the stage vectors)
+        if (ok) {
+            for (int i = tid; i < n; i += nt) { zc[i] = 0.0; Zt[i] = 0.0; }
+            __syncthreads();
+            for (int k = 0; k < N; ++k) {
+                for (int i = tid; i < n; i += nt) {
+                    double s = 0.0;
+                    for (int l = 0; l < n; ++l) s += A[i + l * n] * zc[l];
+                    for (int a = 0; a < m; ++a) s += B[i + a * n] * z[k * m + a];
+                    zn[i] = s; Zt[(k + 1) * n + i] = s;
+                }
+                __syncthreads();
+                double* t_ = zc; zc = zn; zn = t_;
+            }
+            for (int t = tid; t < 2 * n; t += nt) {   // mu_{N+1}, al_{N+1}
+                const int i = t % n, al = t / n;
+                const double* src = al ? ex + (size_t)N * n : zc;
+                double s = 0.0;
+                for (int l = 0; l < n; ++l) s += (P[i + l * n] + P[l + i * n]) * src[l];
+                if (!al) s += gx ? gx[(size_t)N * n + i] : 0.0;
+                cur[t] = s; (al ? At : Mt)[N * n + i] = s;
+            }
+            __syncthreads();
+            for (int k = N - 1; k >= 1; --k) {   // (stage 1 of mu is dL/dx0, which the VJP body hands out; al_1 is not used)
+                for (int t = tid; t < 2 * n; t += nt) {
+                    const int i = t % n, al = t / n;
+                    const double* c = cur + al * n;
+                    const double* src = al ? ex + (size_t)k * n : Zt + (size_t)k * n;
+                    double s = 0.0, w = 0.0;
+                    for (int l = 0; l < n; ++l) s += A[l + i * n] * c[l];
+                    for (int l = 0; l < n; ++l) w += (p.Q[i + l * n] + p.Q[l + i * n]) * src[l];
+                    if (!al) s += gx ? gx[(size_t)k * n + i] : 0.0;
+                    s += w;
+                    nxt[t] = s; (al ? At : Mt)[k * n + i] = s;
+                }
+                __syncthreads();
+                double* t_ = cur; cur = nxt; nxt = t_;
+            }
+        }
+        for (int e = tid; e < total; e += nt) {
+            double s = 0.0;
+            if (e < oP) {
+                if (!p.gQ) continue;
+                const int i = e % n, j = e / n;
+                if (ok) for (int k = 1; k < N; ++k) s += Zt[k * n + i] * ex[k * n + j] + ex[k * n + i] * Zt[k * n + j];
+                p.gQ[(size_t)inst * n * n + e] = s;
+            } else if (e < oA) {
+                if (!p.gP) continue;
+                const int i = (e - oP) % n, j = (e - oP) / n;
+                if (ok) s = Zt[N * n + i] * ex[N * n + j] + ex[N * n + i] * Zt[N * n + j];
+                p.gP[(size_t)inst * n * n + (e - oP)] = s;
+            } else if (e < oB) {
+                if (!p.gA) continue;
+                const int i = (e - oA) % n, j = (e - oA) / n;
+                if (ok) for (int k = 0; k < N; ++k) s += Mt[(k + 1) * n + i] * ex[k * n + j] + At[(k + 1) * n + i] * Zt[k * n + j];
+                p.gA[(size_t)inst * n * n + (e - oA)] = s;
+            } else if (e < oR) {
+                if (!p.gB) continue;
+                const int i = (e - oB) % n, a = (e - oB) / n;
+                if (ok) for (int k = 0; k < N; ++k) s += Mt[(k + 1) * n + i] * ev[k * m + a] + At[(k + 1) * n + i] * z[k * m + a];
+                p.gB[(size_t)inst * n * m + (e - oB)] = s;
+            } else if (e < oS) {
+                if (!p.gR) continue;
+                const int a = (e - oR) % m, b = (e - oR) / m;
+                if (ok && p.useR) for (int k = 0; k < N; ++k) s += z[k * m + a] * ev[k * m + b] + ev[k * m + a] * z[k * m + b];
+                p.gR[(size_t)inst * m * m + (e - oR)] = s;
+            } else if (e < oU) {
+                if (!p.gS) continue;
+                const int a = (e - oS) % m, b = (e - oS) / m;
+                if (ok && p.useS)
+                    for (int k = 0; k + 1 < N; ++k) {
+                        const double dza = z[k * m + a] - z[(k + 1) * m + a], dzb = z[k * m + b] - z[(k + 1) * m + b];
+                        const double dua = u[k * m + a] - u[(k + 1) * m + a], dub = u[k * m + b] - u[(k + 1) * m + b];
+                        s += dza * dub + dua * dzb;
+                    }
+                p.gS[(size_t)inst * m * m + (e - oS)] = s;
+            } else {
+                if (!p.gur) continue;
+                const int j = e - oU, k = j / m, a = j % m;
+                if (ok) {
+                    s = p.g_u[(size_t)inst * nz + j] - p.nu[(size_t)inst * nz + j];
+                    if (p.useS) {
+                        double w = 0.0;
+                        for (int b = 0; b < m; ++b) {
+                            const double sab = p.S[a + b * m] + p.S[b + a * m];
+                            if (k + 1 < N) w += sab * (z[k * m + b] - z[(k + 1) * m + b]);
+                            if (k > 0) w -= sab * (z[(k - 1) * m + b] - z[k * m + b]);
+                        }
+                        s += w;
+                    }
+                }
+                p.gur[(size_t)inst * nz + j] = s;
+            }
+        }
     }
 }
 

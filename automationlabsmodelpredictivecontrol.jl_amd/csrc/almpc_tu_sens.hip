@@ -1,4 +1,5 @@
-// almpc_tu_sens.hip -- one translation unit of libalmpc.so: k_sens (solution sensitivities after a step, two tiers).
+// almpc_tu_sens.hip -- one translation unit of libalmpc.so: k_sens and k_sens_pz (solution sensitivities and parameter gradients
+// after a step, two tiers each).
 // Device code only; the launch logic is in almpc_api.hip, which declares these instantiations `extern template` (see there).
 #include "almpc_sens.hip.h"
 #define ALMPC_KERNEL_INSTANCE(...) template __global__ __VA_ARGS__;

@@ -693,6 +693,50 @@ int almpc_sensitivity_rows_vjp(almpc_handle* h, const double* g_u, const double*
                                double* g_x0 /* [batch][n] */, int32_t* rows /* or NULL */);
 
 /*
+ * Parameter gradients of the returned solution: for the loss of almpc_sensitivity_vjp (g_u [batch][N][m], g_x [batch][N+1][n] or NULL),
+ * its gradient in the problem data, per instance, on the face where the rows W (same rule, same act_tol) are held -- the backward
+ * pass of a step for a caller who learns or tunes the controller (k_sens_pz, k_sens_params; DESIGN.md "k_sens_params").  Stages
+ * 1-based, v = e_u, sym(a, b) = a b' + b a', Qbar_1 = 0, Qbar_k = Q (k = 2..N), Qbar_{N+1} = P:
+ *     lam_{N+1} = g_x[N+1],  lam_k = A'lam_{k+1} + g_x[k],   q_k = g_u[:,k] + B'lam_{k+1}
+ *     z_W = 0,  z_F = -H_FF^-1 q_F;   nu_j = q_j + (H z)_j on the rows of W, 0 elsewhere
+ *     zeta_1 = 0,  zeta_{k+1} = A zeta_k + B z_k
+ *     mu_{N+1} = g_x[N+1] + 2 P zeta_{N+1},  mu_k = A'mu_{k+1} + g_x[k] + 2 Qbar_k zeta_k
+ *     al_{N+1} = 2 P e_x[:,N+1],             al_k = A'al_{k+1} + 2 Qbar_k e_x[:,k]
+ *     x0    = mu_1 (= lam_1 + F'z: the bits of almpc_sensitivity_vjp's g_x0)      f = z  (the gradient in the QP's linear term)
+ *     Q     = sum_{k=2..N} sym(zeta_k, e_x[:,k])        P = sym(zeta_{N+1}, e_x[:,N+1])        R = sum_{k=1..N} sym(z_k, v_k)
+ *     S     = sum_{k=1..N-1} sym(z_k - z_{k+1}, u_k - u_{k+1})                    (the rate cost is on u, not on e_u)
+ *     A     = sum_{k=1..N} mu_{k+1} e_x[:,k]' + al_{k+1} zeta_k'                  B = sum_{k=1..N} mu_{k+1} v_k' + al_{k+1} z_k'
+ *     u_ref[:,k] = g_u[:,k] - nu_k + 2 S (z_k - z_{k+1}) - 2 S (z_{k-1} - z_k)    (S terms only where S is in the design)
+ *     u_min_i = sum_k nu_(k,i) over the rows at the lower bound, u_max_i over those at the upper (a row at both counts as lower)
+ * Conventions: the gradient of a symmetric matrix (Q, P, R, S) is the symmetric matrix G with dL = sum_ij G_ij dM_ij for symmetric dM.
+ * P is data, also where the design computed it as a DARE: its dependence on A, B, Q, R is not followed.  Where the design dropped R
+ * or S (R[1,1] == 0; S[1,1] == 0: src/sub/design_mpc.jl:423-456) that gradient is zero.  x_ref needs no output:
+ * dL/dx_ref[:,1] = g_x[1] - x0, dL/dx_ref[:,k] = g_x[k] for k >= 2.  At a weakly active row: the derivative of the face on which every
+ * flagged row is held, as above.  Outputs are per instance also where the design is shared (the caller sums over the batch), and for
+ * almpc_design_batched, whose Q, R, S and box are shared by the instances.
+ * The call is synchronous and settles first like almpc_sensitivity_vjp; only the groups whose pointer is not NULL are computed and
+ * copied (without u_ref, Q, P, A, R, S, B the second kernel is not launched).  Refusals are almpc_sensitivity_vjp's: ALMPC_ERR_UNSUPPORTED
+ * for state rows, ALMPC_FLAG_STRUCTURED handles, almpc_design_ltv, the SQP loop and the re-linearisation pipeline; ALMPC_ERR_INVALID
+ * before the design's first step, for a NULL g_u or out, and for an out whose pointers are all NULL.  An instance that is not
+ * ALMPC_SOLVED (or whose S is not positive definite) gets rows = -1 and zeros in every output.
+ */
+typedef struct almpc_param_grads {      /* host pointers, NULL = not wanted; per instance, batch slowest */
+    double *x0;              /* [batch][n]                         */
+    double *f;               /* [batch][N][m]                      */
+    double *u_ref;           /* [batch][N][m]                      */
+    double *u_min, *u_max;   /* [batch][m]                         */
+    double *Q, *P, *A;       /* [batch][n*n] column-major          */
+    double *R, *S;           /* [batch][m*m]                       */
+    double *B;               /* [batch][n*m] column-major n x m    */
+    int32_t *rows;           /* [batch] |W|, or -1                 */
+} almpc_param_grads;
+int almpc_sensitivity_params_vjp(almpc_handle* h, const double* g_u, const double* g_x /* or NULL */, double act_tol,
+                                 const almpc_param_grads* out);
+/* ... of the whole batch of a group: every array with `batch` = the whole batch, cut along the shards */
+int almpc_group_sensitivity_params_vjp(almpc_group* g, const double* g_u, const double* g_x /* or NULL */, double act_tol,
+                                       const almpc_param_grads* out);
+
+/*
  * Timing of the last almpc_calculate (needs ALMPC_FLAG_TIMING): milliseconds spent in the ADMM
  * kernel, the polish kernel(s), the rollout kernel, and the whole enqueue->done span, measured
  * with HIP events on the handle's stream.

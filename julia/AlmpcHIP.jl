@@ -20,7 +20,8 @@ export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_s
        group_design_batched!, group_design_relin_fnn!, group_relin_step!, group_relin_advance!, group_advance_plant!, group_design_sqp_fnn!,
        group_sqp_start!, group_sqp_iterate!, group_sqp_solve!, group_set_sqp_hessian!, group_set_sqp_row_multipliers!, group_state_multipliers, group_sqp_skipped, group_x0_staging, group_update_initialization_staged!, group_results_async,
        group_results_wait!, sensitivity, device_sensitivity, sensitivity_vjp, group_sensitivity, group_sensitivity_vjp,
-       sensitivity_rows, sensitivity_rows_vjp, group_sensitivity_rows, group_sensitivity_rows_vjp
+       sensitivity_rows, sensitivity_rows_vjp, group_sensitivity_rows, group_sensitivity_rows_vjp, sensitivity_params_vjp,
+       group_sensitivity_params_vjp
 
 const libalmpc = get(ENV, "ALMPC_LIB", "libalmpc.so")
 
@@ -692,6 +693,40 @@ function sensitivity_rows_vjp(mod::HipModeler, g_u::Array{Float64}, g_x::Union{N
     return g_x0, rows
 end
 
+# almpc_param_grads (include/almpc.h): host pointers, C_NULL = not wanted
+struct ParamGrads
+    x0::Ptr{Float64}; f::Ptr{Float64}; u_ref::Ptr{Float64}; u_min::Ptr{Float64}; u_max::Ptr{Float64}
+    Q::Ptr{Float64}; P::Ptr{Float64}; A::Ptr{Float64}; R::Ptr{Float64}; S::Ptr{Float64}; B::Ptr{Float64}
+    rows::Ptr{Int32}
+end
+const PARAM_GROUPS = (:x0, :f, :u_ref, :u_min, :u_max, :Q, :P, :A, :R, :S, :B)
+# the arrays of the wanted groups (batch last) and the struct that points at them; keep the arrays alive around the call
+function param_grad_arrays(n, m, N, batch, want)
+    all(k -> k in PARAM_GROUPS, want) || error("sensitivity_params_vjp: want must be a subset of $(PARAM_GROUPS)")
+    dims = Dict(:x0 => (n, batch), :f => (m, N, batch), :u_ref => (m, N, batch), :u_min => (m, batch), :u_max => (m, batch),
+                :Q => (n, n, batch), :P => (n, n, batch), :A => (n, n, batch), :R => (m, m, batch), :S => (m, m, batch), :B => (n, m, batch))
+    out = Dict{Symbol,Any}(k => Array{Float64}(undef, dims[k]...) for k in want)
+    out[:rows] = Vector{Int32}(undef, batch)
+    pf(k) = haskey(out, k) ? pointer(out[k]) : Ptr{Float64}(C_NULL)
+    return out, ParamGrads(pf(:x0), pf(:f), pf(:u_ref), pf(:u_min), pf(:u_max), pf(:Q), pf(:P), pf(:A), pf(:R), pf(:S), pf(:B), pointer(out[:rows]))
+end
+"""
+    sensitivity_params_vjp(mod, g_u, g_x = nothing; want = PARAM_GROUPS, act_tol = 0.0) -> Dict
+
+Gradients of the loss of `sensitivity_vjp` in the problem data, per instance (`almpc_sensitivity_params_vjp`): `:x0` n x batch, `:f` and
+`:u_ref` m x N x batch, `:u_min`, `:u_max` m x batch, `:Q`, `:P`, `:A` n x n x batch, `:R`, `:S` m x m x batch, `:B` n x m x batch, and
+`:rows`.  For a shared design the caller sums over the batch.
+"""
+function sensitivity_params_vjp(mod::HipModeler, g_u::Array{Float64}, g_x::Union{Nothing,Array{Float64}} = nothing;
+                                want = PARAM_GROUPS, act_tol::Real = 0.0)
+    check_sens_sizes(mod.n, mod.m, mod.N, mod.batch, g_u, g_x)
+    out, pg = param_grad_arrays(mod.n, mod.m, mod.N, mod.batch, want)
+    px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
+    GC.@preserve g_x out check(mod.handle, ccall((:almpc_sensitivity_params_vjp, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ref{ParamGrads}), mod.handle, g_u, px, act_tol, Ref(pg)))
+    return out
+end
+
 "library defaults of the options (OSQP's, plus the documented changes)"
 function default_opts()
     o = Ref(AlmpcOpts())
@@ -852,6 +887,16 @@ function group_sensitivity_vjp(g::HipGroup, g_u::Array{Float64}, g_x::Union{Noth
     GC.@preserve g_x gcheck(g.group, ccall((:almpc_group_sensitivity_vjp, libalmpc), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), g.group, g_u, px, act_tol, g_x0, rows))
     return g_x0, rows
+end
+"`sensitivity_params_vjp` for the whole batch (`almpc_group_sensitivity_params_vjp`)"
+function group_sensitivity_params_vjp(g::HipGroup, g_u::Array{Float64}, g_x::Union{Nothing,Array{Float64}} = nothing;
+                                      want = PARAM_GROUPS, act_tol::Real = 0.0)
+    check_sens_sizes(g.n, g.m, g.N, g.batch, g_u, g_x)
+    out, pg = param_grad_arrays(g.n, g.m, g.N, g.batch, want)
+    px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
+    GC.@preserve g_x out gcheck(g.group, ccall((:almpc_group_sensitivity_params_vjp, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ref{ParamGrads}), g.group, g_u, px, act_tol, Ref(pg)))
+    return out
 end
 "`sensitivity_rows` for the whole batch (`almpc_group_sensitivity_rows` + `almpc_group_get_sensitivity`)"
 function group_sensitivity_rows(g::HipGroup; K0::Bool = true, dU::Bool = false, dX::Bool = false, act_tol_u::Real = 0.0, act_tol_x::Real = 0.0)

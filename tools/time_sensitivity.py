@@ -6,6 +6,9 @@ DESIGN.md section 4 ("Sensitivities"):
                 read-back), and the same through Solver.sensitivity, which also copies the arrays to the host
     VJP         almpc_sensitivity_vjp with and without g_x: host pointers, so the call includes the upload of the loss gradients and
                 the read-back of g_x0
+    params      almpc_sensitivity_params_vjp beside it (Solver.sensitivity_params_vjp: the same upload, the read-back of the wanted
+                groups): the groups of the first kernel alone, every group, and every group through the C call into host arrays
+                that stay
     rows form   the same batch with a tight state box (+-3 (1, 1, 1, .5, .5, .5, .1, ..., .1), x0 clipped to 0.99 of it) and the terminal
                 equality, the library's default step: almpc_sensitivity_rows (K0; K0 + dU + dX) and almpc_sensitivity_rows_vjp
 medians over `reps` repetitions after a warm-up, with minimum and maximum.  There is no threshold: nothing exists to compare against.
@@ -67,6 +70,20 @@ rng = np.random.default_rng(1)
 g_u, g_x = rng.normal(size=(batch, p.m, p.N)), rng.normal(size=(batch, p.n, p.N + 1))
 print(f"| `almpc_sensitivity_vjp`, g_u only | | {clock(lambda: s.sensitivity_vjp(g_u))} |")
 print(f"| `almpc_sensitivity_vjp`, g_u and g_x | | {clock(lambda: s.sensitivity_vjp(g_u, g_x))} |")
+# the parameter gradients: the same upload, k_sens_pz in place of k_sens<VJP>, k_sens_params behind it where a group needs it
+print(f"| `almpc_sensitivity_params_vjp`, x0, f, u_min, u_max (no second kernel) | | "
+      f"{clock(lambda: s.sensitivity_params_vjp(g_u, g_x, want=('x0', 'f', 'u_min', 'u_max')))} |")
+print(f"| `almpc_sensitivity_params_vjp`, every group (fresh host arrays per call) | | {clock(lambda: s.sensitivity_params_vjp(g_u, g_x))} |")
+# ... and the C call alone into host arrays that stay (what a training loop does): the wrapper's fresh arrays are first touched by the
+# read-back, which can cost more than the call
+gu_c, gx_c = np.ascontiguousarray(g_u.transpose(0, 2, 1)), np.ascontiguousarray(g_x.transpose(0, 2, 1))
+per = {"x0": p.n, "f": p.nz, "u_ref": p.nz, "u_min": p.m, "u_max": p.m, "Q": p.n * p.n, "P": p.n * p.n, "A": p.n * p.n, "R": p.m * p.m,
+       "S": p.m * p.m, "B": p.n * p.m}
+kept = {k: np.zeros((batch, v)) for k, v in per.items()}
+kept_rows = np.zeros(batch, dtype=np.int32)
+out = capi.almpc_param_grads(**{k: capi._ptr(v) for k, v in kept.items()}, rows=kept_rows.ctypes.data_as(capi._ip))
+t_kept = clock(lambda: s._check(s.L.almpc_sensitivity_params_vjp(s.h, capi._ptr(gu_c), capi._ptr(gx_c), 0.0, out)))
+print(f"| `almpc_sensitivity_params_vjp`, every group, host arrays kept by the caller | | {t_kept} |", flush=True)
 s.close()
 
 # the state-row leg
