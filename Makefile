@@ -36,7 +36,7 @@ $(OBJDIR)/almpc_tu_design_b.o:   $(H_K) $(H_D) $(CS)/almpc_riccati.hip.h $(CS)/a
 $(OBJDIR)/almpc_tu_sdual_a.o:    $(H_K) $(CS)/almpc_riccati.hip.h $(CS)/almpc_sdual.hip.h $(CS)/instances/sdual_a.inc
 $(OBJDIR)/almpc_tu_sdual_b.o:    $(H_K) $(CS)/almpc_riccati.hip.h $(CS)/almpc_sdual.hip.h $(CS)/instances/sdual_b.inc
 $(OBJDIR)/almpc_tu_sdual_c.o:    $(H_K) $(CS)/almpc_riccati.hip.h $(CS)/almpc_sdual.hip.h $(CS)/instances/sdual_c.inc
-$(OBJDIR)/almpc_tu_dare.o:       $(CS)/almpc_dare.hip.h $(CS)/instances/dare.inc
+$(OBJDIR)/almpc_tu_dare.o:       $(CS)/almpc_dare.hip.h $(CS)/almpc_dare_vjp.hip.h $(CS)/instances/dare.inc
 $(OBJDIR)/almpc_tu_c2d.o:        $(CS)/almpc_c2d.hip.h $(CS)/instances/c2d.inc
 $(OBJDIR)/almpc_tu_sens.o:       $(CS)/almpc_sens.hip.h $(CS)/instances/sens.inc
 

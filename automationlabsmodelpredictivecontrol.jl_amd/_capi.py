@@ -121,6 +121,10 @@ def load():
     L.almpc_dare.restype = ctypes.c_int
     L.almpc_dare_batched.argtypes = [ctypes.c_int] * 4 + [_dp] * 5 + [_ip]
     L.almpc_dare_batched.restype = ctypes.c_int
+    L.almpc_dare_vjp.argtypes = [ctypes.c_int, ctypes.c_int] + [_dp] * 10
+    L.almpc_dare_vjp.restype = ctypes.c_int
+    L.almpc_dare_vjp_batched.argtypes = [ctypes.c_int] * 4 + [_dp] * 10 + [_ip]
+    L.almpc_dare_vjp_batched.restype = ctypes.c_int
     L.almpc_set_terminal_weight.argtypes = [_hp, ctypes.c_int]
     L.almpc_set_terminal_weight.restype = ctypes.c_int
     L.almpc_relin_fnn_terminal_status.argtypes = [_hp, _ip]
@@ -152,8 +156,11 @@ def load():
     L.almpc_group_sensitivity_rows_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.c_double, _dp, _ip]
     L.almpc_sensitivity_params_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.POINTER(almpc_param_grads)]
     L.almpc_group_sensitivity_params_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.POINTER(almpc_param_grads)]
+    L.almpc_sensitivity_params_vjp_dare.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.POINTER(almpc_param_grads), _ip]
+    L.almpc_group_sensitivity_params_vjp_dare.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.POINTER(almpc_param_grads), _ip]
     for nm_ in ("almpc_sensitivity", "almpc_get_sensitivity", "almpc_device_sensitivity", "almpc_sensitivity_vjp",
                 "almpc_sensitivity_params_vjp", "almpc_group_sensitivity_params_vjp",
+                "almpc_sensitivity_params_vjp_dare", "almpc_group_sensitivity_params_vjp_dare",
                 "almpc_group_sensitivity", "almpc_group_get_sensitivity", "almpc_group_sensitivity_vjp",
                 "almpc_sensitivity_rows", "almpc_sensitivity_rows_vjp", "almpc_group_sensitivity_rows", "almpc_group_sensitivity_rows_vjp"):
         getattr(L, nm_).restype = ctypes.c_int
@@ -300,9 +307,13 @@ def _sens_vjp(call, handle, check, g_u, g_x, act_tol, b, n, m, N):
 PARAM_GROUPS = ("x0", "f", "u_ref", "u_min", "u_max", "Q", "P", "A", "R", "S", "B")   # almpc.h: the fields of almpc_param_grads
 
 
-def _sens_params_vjp(call, handle, check, g_u, g_x, want, act_tol, b, n, m, N):
+TERMINAL_GRADIENTS = ("data", "dare")   # almpc_sensitivity_params_vjp, almpc_sensitivity_params_vjp_dare
+
+
+def _sens_params_vjp(call, handle, check, g_u, g_x, want, act_tol, b, n, m, N, dare=False):
     """almpc_sensitivity_params_vjp: {group: array} for the groups `want` names, Julia-shaped with the batch axis first -- x0 (b, n),
-    f and u_ref (b, m, N), u_min / u_max (b, m), Q / P / A (b, n, n), R / S (b, m, m), B (b, n, m) --, and rows (b,)."""
+    f and u_ref (b, m, N), u_min / u_max (b, m), Q / P / A (b, n, n), R / S (b, m, m), B (b, n, m) --, and rows (b,).  dare: `call` is
+    the _dare form, which also fills dare_status (b,)."""
     want = (want,) if isinstance(want, str) else tuple(want)
     for k in want:
         if k not in PARAM_GROUPS:
@@ -319,10 +330,19 @@ def _sens_params_vjp(call, handle, check, g_u, g_x, want, act_tol, b, n, m, N):
     raw = {k: block[offs[i]:offs[i + 1]].reshape(shapes[k]) for i, k in enumerate(want)}
     rows = np.empty(b, dtype=np.int32)
     out = almpc_param_grads(**{k: _ptr(v) for k, v in raw.items()}, rows=rows.ctypes.data_as(_ip))
-    check(call(handle, _ptr(g_u), _ptr(g_x), float(act_tol), ctypes.byref(out)))
+    dare_status = np.zeros(b, dtype=np.int32) if dare else None
+    check(call(handle, _ptr(g_u), _ptr(g_x), float(act_tol), ctypes.byref(out), *((dare_status.ctypes.data_as(_ip),) if dare else ())))
     res = {k: (v if v.ndim == 2 else v.transpose(0, 2, 1)) for k, v in raw.items()}
     res["rows"] = rows
+    if dare:
+        res["dare_status"] = dare_status
     return res
+
+
+def _terminal_gradient(terminal):
+    if terminal not in TERMINAL_GRADIENTS:
+        raise ValueError(f"unknown terminal {terminal!r}; choose from {TERMINAL_GRADIENTS}")
+    return terminal == "dare"
 
 
 def _want_mask(want):
@@ -378,6 +398,48 @@ def dare(A, B, Q, R):
     if rc != ALMPC_OK:
         raise AlmpcError(rc, "almpc_dare")
     return P
+
+
+def dare_vjp(A, B, Q, R, P, g_P, want=("A", "B", "Q", "R")) -> dict:
+    """The adjoint of dare (almpc_dare_vjp, host code): for P = DARE(A, B, Q, R) and a symmetric g_P = dL/dP, what the loss gains through
+    P in A (n, n), B (n, m), Q (n, n), R (m, m) -- the ones `want` names.  AlmpcError -6 when P is not the stabilising solution of this
+    model; its text carries the status (1 singular R + B'PB, 2 closed loop not stable, 3 P does not solve the equation)."""
+    L = load()
+    A, B = np.asfortranarray(A, dtype=np.float64), np.asfortranarray(B, dtype=np.float64)
+    n, m = B.shape
+    Q, R, P, g_P = _colmajor(Q, (n, n)), _colmajor(R, (m, m)), _colmajor(P, (n, n)), _colmajor(g_P, (n, n))
+    shapes = {"A": (n, n), "B": (n, m), "Q": (n, n), "R": (m, m)}
+    out = {k: np.empty(shapes[k], order="F") for k in want}
+    rc = L.almpc_dare_vjp(n, m, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P), _ptr(g_P), *(_ptr(out.get(k)) for k in ("A", "B", "Q", "R")))
+    if rc != ALMPC_OK:
+        raise AlmpcError(rc, "almpc_dare_vjp" if rc != -6 else L.almpc_last_error(None).decode())
+    return out
+
+
+def dare_vjp_batched(A, B, Q, R, P, g_P, device=0, want=("A", "B", "Q", "R"), init=None):
+    """dare_vjp for a batch on the GPU (almpc_dare_vjp_batched): A, P, g_P (batch, n, n), B (batch, n, m), shared Q, R.  Returns
+    ({group: array (batch, ...)} for the groups `want` names, status (batch,) int32); status 0 = followed, else the slots i are what
+    init[group] held (NaN without init)."""
+    L = load()
+    A, B, P, g_P = (np.asarray(a, dtype=np.float64) for a in (A, B, P, g_P))
+    if A.ndim != 3 or B.ndim != 3 or A.shape[0] != B.shape[0] or A.shape[1] != A.shape[2] or B.shape[1] != A.shape[1]:
+        raise ValueError(f"expected A (batch, n, n) and B (batch, n, m), got {A.shape} and {B.shape}")
+    b, n, m = B.shape
+    if P.shape != (b, n, n) or g_P.shape != (b, n, n):
+        raise ValueError(f"expected P and g_P {(b, n, n)}, got {P.shape} and {g_P.shape}")
+    cm = lambda a: np.ascontiguousarray(a.transpose(0, 2, 1))  # column-major blocks
+    Q, R = _colmajor(Q, (n, n)), _colmajor(R, (m, m))
+    shapes = {"A": (b, n, n), "B": (b, n, m), "Q": (b, n, n), "R": (b, m, m)}
+    out = {}
+    for k in want:
+        out[k] = np.full(shapes[k], np.nan).transpose(0, 2, 1).copy() if init is None or k not in init else \
+            cm(np.asarray(init[k], dtype=np.float64).reshape(shapes[k]))
+    st = np.zeros(b, dtype=np.int32)
+    rc = L.almpc_dare_vjp_batched(int(device), n, m, b, _ptr(cm(A)), _ptr(cm(B)), _ptr(Q), _ptr(R), _ptr(cm(P)), _ptr(cm(g_P)),
+                                  *(_ptr(out.get(k)) for k in ("A", "B", "Q", "R")), st.ctypes.data_as(_ip))
+    if rc != ALMPC_OK:
+        raise AlmpcError(rc, "almpc_dare_vjp_batched")
+    return {k: np.ascontiguousarray(v.transpose(0, 2, 1)) for k, v in out.items()}, st
 
 
 TERMINAL_WEIGHT_MODES = {"given": 0, "dare_device": 1}  # almpc.h: ALMPC_TERMINAL_*
@@ -978,12 +1040,15 @@ class Solver:
         trajectories (almpc_sensitivity_vjp: no Jacobian is formed); also returns rows (batch,)."""
         return _sens_vjp(self.L.almpc_sensitivity_vjp, self.h, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
 
-    def sensitivity_params_vjp(self, g_u, g_x=None, want=PARAM_GROUPS, act_tol=0.0) -> dict:
+    def sensitivity_params_vjp(self, g_u, g_x=None, want=PARAM_GROUPS, act_tol=0.0, terminal="data") -> dict:
         """Gradients of the loss of sensitivity_vjp in the problem data, per instance (almpc_sensitivity_params_vjp): x0, the QP's
         linear term f, u_ref, the input box, the weights Q, P, R, S and the model A, B -- what `want` names -- and rows.  For a shared
-        design the caller sums over the batch."""
-        return _sens_params_vjp(self.L.almpc_sensitivity_params_vjp, self.h, self._check, g_u, g_x, want, act_tol, self.batch, self.n,
-                                self.m, self.N)
+        design the caller sums over the batch.  terminal="data": P is data; "dare" (almpc_sensitivity_params_vjp_dare): P_i =
+        DARE(A_i, B_i, Q, R) is followed into Q, R, A, B, and the dict also carries dare_status (batch,): 0 followed, else the
+        instance keeps its P-as-data values (its P is not the stabilising DARE solution of the design's model)."""
+        dare = _terminal_gradient(terminal)
+        call = self.L.almpc_sensitivity_params_vjp_dare if dare else self.L.almpc_sensitivity_params_vjp
+        return _sens_params_vjp(call, self.h, self._check, g_u, g_x, want, act_tol, self.batch, self.n, self.m, self.N, dare)
 
     def sensitivity_rows(self, want=("K0", "dU", "dX"), act_tol_u=0.0, act_tol_x=0.0) -> dict:
         """sensitivity for shared designs with a state box and / or the terminal equality as well (almpc_sensitivity_rows +
@@ -1343,10 +1408,11 @@ class Group:
         """Solver.sensitivity_vjp for the whole batch (almpc_group_sensitivity_vjp)."""
         return _sens_vjp(self.L.almpc_group_sensitivity_vjp, self.g, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
 
-    def sensitivity_params_vjp(self, g_u, g_x=None, want=PARAM_GROUPS, act_tol=0.0) -> dict:
-        """Solver.sensitivity_params_vjp for the whole batch (almpc_group_sensitivity_params_vjp)."""
-        return _sens_params_vjp(self.L.almpc_group_sensitivity_params_vjp, self.g, self._check, g_u, g_x, want, act_tol, self.batch,
-                                self.n, self.m, self.N)
+    def sensitivity_params_vjp(self, g_u, g_x=None, want=PARAM_GROUPS, act_tol=0.0, terminal="data") -> dict:
+        """Solver.sensitivity_params_vjp for the whole batch (almpc_group_sensitivity_params_vjp, almpc_group_sensitivity_params_vjp_dare)."""
+        dare = _terminal_gradient(terminal)
+        call = self.L.almpc_group_sensitivity_params_vjp_dare if dare else self.L.almpc_group_sensitivity_params_vjp
+        return _sens_params_vjp(call, self.g, self._check, g_u, g_x, want, act_tol, self.batch, self.n, self.m, self.N, dare)
 
     def sensitivity_rows(self, want=("K0", "dU", "dX"), act_tol_u=0.0, act_tol_x=0.0) -> dict:
         """Solver.sensitivity_rows for the whole batch (almpc_group_sensitivity_rows + almpc_group_get_sensitivity)."""

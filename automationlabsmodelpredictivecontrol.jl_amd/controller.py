@@ -591,14 +591,18 @@ def sensitivity(C: ModelPredictiveControlController, want=("K0",), act_tol: floa
     return {k: (v[0] if mod.batch == 1 else v) for k, v in out.items()}
 
 
-def sensitivity_params(C: ModelPredictiveControlController, g_u, g_x=None, want=_capi.PARAM_GROUPS, act_tol: float = 0.0) -> dict:
+def sensitivity_params(C: ModelPredictiveControlController, g_u, g_x=None, want=_capi.PARAM_GROUPS, act_tol: float = 0.0,
+                       terminal: str = "data") -> dict:
     """Gradients of a loss on the last calculate!(C) in the problem data (beside `sensitivity`, an extension of this build): for loss
     gradients g_u (m, N) and g_x (n, N+1) on the returned trajectories (a leading batch axis when the controller has more than one
     instance) the gradients in x0, the QP's linear term f, u_ref, the input box (u_min, u_max), the weights Q, P, R, S and the model
     A, B -- what `want` names -- per instance, and rows.  Linear controllers with an input box (Solver.sensitivity_params_vjp says
-    what is refused); the terminal weight counts as data also where the design computed it."""
+    what is refused).  terminal="data": the terminal weight counts as data also where the design computed it.  terminal="dare": the
+    gradient of the reference's own problem, whose P is always are(Discrete, A, B, Q, R) (src/sub/design_mpc.jl:318-327) -- Q, R, A, B
+    also gain what the loss gains through P, and the dict carries dare_status (0: followed; else that instance's P is not the
+    stabilising DARE solution of its model and it keeps the "data" values)."""
     mod: HipModeler = C.tuning.modeler
-    out = mod.solver.sensitivity_params_vjp(g_u, g_x, want, act_tol)
+    out = mod.solver.sensitivity_params_vjp(g_u, g_x, want, act_tol, terminal)
     return {k: (v[0] if mod.batch == 1 else v) for k, v in out.items()}
 
 

@@ -14,6 +14,7 @@
 #include "almpc_riccati.hip.h"
 #include "almpc_sdual.hip.h"
 #include "almpc_dare.hip.h"
+#include "almpc_dare_vjp.hip.h"
 #include "almpc_c2d.hip.h"
 #include "almpc_sens.hip.h"
 #include "almpc_host_math.h"
@@ -240,13 +241,14 @@ struct almpc_handle {
         bool stepped = false;           // a step has run on the current design
         // parameter gradients (almpc_sensitivity_params_vjp): the design's Q and whether it kept R, host side (every condensed design
         // leaves them); the rest is made at the first such call
-        std::vector<double> Q;
+        std::vector<double> Q, R;       // (R: what the design's DARE was taken with, for almpc_sensitivity_params_vjp_dare)
         int useR = 0;
-        DevBuf<double> W;               // [Q n*n | S m*m | P n*n] device copies of the weights (P: a shared design's; else the handle's bP)
+        DevBuf<double> W;               // [Q n*n | S m*m | P n*n | R m*m] device copies of the weights (P: a shared design's; else the handle's bP)
         bool w_ok = false;              // ... of the current design
         DevBuf<double> pz;              // [batch][nz] z | [batch][nz] nu | [batch][m] dL/dumin | [batch][m] dL/dumax (k_sens_pz)
         DevBuf<double> pout;            // k_sens_params' outputs: u_ref, Q, P, A, R, S, B, each [batch][its size]
         DevBuf<double> traj;            // [workgroups][3][(N+1) n] zeta, mu, al of the instance a workgroup is at
+        DevBuf<int32_t> dstat;          // [batch] k_dare_vjp's status words (almpc_sensitivity_params_vjp_dare)
     } sens;
     // stage-wise dual active-set solve (k_sdual, csrc/almpc_sdual.hip.h): input box, state box, terminal equality and S in the
     // multiple-shooting form; stage records of the unconstrained problem (shared: host Riccati at design time)
@@ -741,6 +743,25 @@ hipError_t launch_dare(DareParams p, hipStream_t st) {
     else if (d <= 32) DARE_RL(32);
     else DARE_RL(64);
 #undef DARE_RL
+    return hipGetLastError();
+}
+
+// k_dare_vjp: the adjoint of P_i = DARE(A_i, B_i, Q, R), one wave per instance (csrc/almpc_dare_vjp.hip.h).  Launch only.
+hipError_t launch_dare_vjp(DareVjpParams p, hipStream_t st) {
+    p.lds_per_wave = dare_lds_doubles(p.n, p.m);
+    const int waves = dare_waves(p.n, p.m), d = p.n > p.m ? p.n : p.m;
+    const size_t lds = (size_t)waves * p.lds_per_wave * sizeof(double);
+    const unsigned wgs = (unsigned)((p.batch + waves - 1) / waves);
+#define DARE_VJP_RL(RL_)                                                                              \
+    do {                                                                                              \
+        const hipError_t e_ = ensure_dyn_lds(reinterpret_cast<const void*>(k_dare_vjp<RL_>), lds);    \
+        if (e_ != hipSuccess) return e_;                                                              \
+        hipLaunchKernelGGL((k_dare_vjp<RL_>), dim3(wgs), dim3(64 * waves), lds, st, p);               \
+    } while (0)
+    if (d <= 16) DARE_VJP_RL(16);
+    else if (d <= 32) DARE_VJP_RL(32);
+    else DARE_VJP_RL(64);
+#undef DARE_VJP_RL
     return hipGetLastError();
 }
 
@@ -1351,7 +1372,15 @@ void almpc_default_opts(almpc_opts* o) {
     o->warm_start = 0;
 }
 
-const char* almpc_last_error(const almpc_handle* h) { return h ? h->err.c_str() : "null handle"; }
+// (without a handle: the text of the calling thread's last failed almpc_dare_vjp, handed out once)
+static thread_local std::string g_nohandle_err, g_nohandle_err_out;
+const char* almpc_last_error(const almpc_handle* h) {
+    if (h) return h->err.c_str();
+    if (g_nohandle_err.empty()) return "null handle";
+    g_nohandle_err_out.swap(g_nohandle_err);
+    g_nohandle_err.clear();
+    return g_nohandle_err_out.c_str();
+}
 
 int almpc_create(almpc_handle** out, int n, int m, int N, int batch, int device_id, uint32_t flags) {
     if (!out) return ALMPC_ERR_INVALID;
@@ -1610,7 +1639,7 @@ static int design_shared_condensed(almpc_handle* h, const double* A, const doubl
     const hm::mat Sm = hm::symmetrised(S, m);   // S enters the cost as a quadratic form: only its symmetric part counts
     h->hS = Sm;
     h->useS = (Rm[0] != 0.0 && Sm[0] != 0.0) ? 1 : 0;  // the reference drops the S term together with R (src/sub/design_mpc.jl:423-466)
-    h->sens.Q = Qm; h->sens.useR = Rm[0] != 0.0;
+    h->sens.Q = Qm; h->sens.R = Rm; h->sens.useR = Rm[0] != 0.0;
     h->rho = rho; h->sigma = sigma;
 
     // ---- state rows (state box, terminal equality): row tables and the shared constraint-space matrix
@@ -2058,7 +2087,7 @@ int batched_design_front(almpc_handle* h, const double* A_batch, const double* B
     h->rho = rho; h->sigma = sigma;
     d.useR = Rm[0] != 0.0; d.useS = d.useR && Sm[0] != 0.0;
     h->useS = d.useS;
-    h->sens.Q = Qm; h->sens.useR = d.useR;
+    h->sens.Q = Qm; h->sens.R = Rm; h->sens.useR = d.useR;
     tr("host preparation");
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     tr("stream idle");
@@ -4013,6 +4042,26 @@ int almpc_dare(int n, int m, const double* A, const double* B, const double* Q, 
     return ALMPC_OK;
 }
 
+int almpc_dare_vjp(int n, int m, const double* A, const double* B, const double* Q, const double* R, const double* P, const double* g_P,
+                   double* g_A, double* g_B, double* g_Q, double* g_R) {
+    if (n < 1 || m < 1 || !A || !B || !Q || !R || !P || !g_P) return ALMPC_ERR_INVALID;
+    const size_t nn = (size_t)n * n, nm = (size_t)n * m, mm = (size_t)m * m;
+    hm::mat gA, gB, gQ, gR;
+    const int st = hm::dare_vjp(hm::mat(A, A + nn), hm::mat(B, B + nm), hm::mat(Q, Q + nn), hm::mat(R, R + mm), hm::mat(P, P + nn),
+                                hm::mat(g_P, g_P + nn), n, m, g_A ? &gA : nullptr, g_B ? &gB : nullptr, g_Q ? &gQ : nullptr, g_R ? &gR : nullptr);
+    if (st != 0) {
+        static const char* const why[] = {"", "R + B'PB is singular", "the closed loop A - B K is not stable: P is not the stabilising solution",
+                                          "P does not solve the equation for this model"};
+        g_nohandle_err = "dare_vjp: status " + std::to_string(st) + " (" + why[st] + ")";
+        return ALMPC_ERR_NUMERIC;
+    }
+    if (g_A) std::copy(gA.begin(), gA.end(), g_A);
+    if (g_B) std::copy(gB.begin(), gB.end(), g_B);
+    if (g_Q) std::copy(gQ.begin(), gQ.end(), g_Q);
+    if (g_R) std::copy(gR.begin(), gR.end(), g_R);
+    return ALMPC_OK;
+}
+
 int almpc_c2d(int n, int m, const double* Ac, const double* Bc, double Ts, double* Ad, double* Bd) {
     if (n < 1 || m < 1 || !Ac || !Bc || !Ad || !Bd) return ALMPC_ERR_INVALID;
     if (!(Ts > 0.0 && std::isfinite(Ts))) return ALMPC_ERR_INVALID;
@@ -4077,6 +4126,46 @@ int almpc_dare_batched(int device_id, int n, int m, int batch, const double* A_b
     if (launch_dare(dp, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ALMPC_ERR_HIP;
     if (hipMemcpy(P_batch, dP, b * nn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(status, dSt, b * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return ALMPC_ERR_HIP;
+    return ALMPC_OK;
+}
+
+int almpc_dare_vjp_batched(int device_id, int n, int m, int batch, const double* A_batch, const double* B_batch, const double* Q,
+                           const double* R, const double* P_batch, const double* gP_batch, double* gA_batch, double* gB_batch,
+                           double* gQ_batch, double* gR_batch, int32_t* status) {
+    if (n < 1 || m < 1 || batch < 1 || !A_batch || !B_batch || !Q || !R || !P_batch || !gP_batch || !status) return ALMPC_ERR_INVALID;
+    if (n > DARE_MAX_N || m > DARE_MAX_M) return ALMPC_ERR_UNSUPPORTED;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device_id < 0 || device_id >= count) return ALMPC_ERR_NO_DEVICE;
+    {
+        const char* why = "";
+        ALMPC_TRY(dare_device_check(n, m, hm::mat(R, R + (size_t)m * m), false, &why));
+    }
+    if (hipSetDevice(device_id) != hipSuccess) return ALMPC_ERR_HIP;
+    using Tight = DevBuf<double, Mem::DeviceTight>;
+    const size_t b = (size_t)batch, nn = (size_t)n * n, nm = (size_t)n * m, mm = (size_t)m * m;
+    Tight dA, dB, dQ, dR, dP, dgP, dgA, dgB, dgQ, dgR;
+    DevBuf<int32_t, Mem::DeviceTight> dSt;
+    // (the outputs go up as well: the slots of an instance that is refused come back as the caller left them)
+    const auto up = [](Tight& dst, const double* src, size_t cnt) { return src ? dst.upload(src, cnt) : hipSuccess; };
+    if (up(dA, A_batch, b * nn) != hipSuccess || up(dB, B_batch, b * nm) != hipSuccess || up(dQ, Q, nn) != hipSuccess ||
+        up(dR, R, mm) != hipSuccess || up(dP, P_batch, b * nn) != hipSuccess || up(dgP, gP_batch, b * nn) != hipSuccess ||
+        up(dgA, gA_batch, b * nn) != hipSuccess || up(dgB, gB_batch, b * nm) != hipSuccess || up(dgQ, gQ_batch, b * nn) != hipSuccess ||
+        up(dgR, gR_batch, b * mm) != hipSuccess || dSt.alloc(b) != hipSuccess)
+        return ALMPC_ERR_HIP;
+    DareVjpParams vp;
+    vp.n = n; vp.m = m; vp.batch = batch;
+    vp.A = dA; vp.A_stride = (long)nn; vp.B = dB; vp.B_stride = (long)nm; vp.P = dP; vp.P_stride = (long)nn; vp.gP = dgP; vp.gP_stride = (long)nn;
+    vp.Q = dQ; vp.R = dR;
+    vp.gA = gA_batch ? dgA.get() : nullptr; vp.gA_stride = (long)nn; vp.gB = gB_batch ? dgB.get() : nullptr; vp.gB_stride = (long)nm;
+    vp.gQ = gQ_batch ? dgQ.get() : nullptr; vp.gQ_stride = (long)nn; vp.gR = gR_batch ? dgR.get() : nullptr; vp.gR_stride = (long)mm;
+    vp.accumulate = 0; vp.rows = nullptr; vp.status = dSt; vp.lds_per_wave = 0;
+    if (launch_dare_vjp(vp, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ALMPC_ERR_HIP;
+    const auto down = [](double* dst, const Tight& src, size_t cnt) {
+        return dst ? hipMemcpy(dst, src, cnt * sizeof(double), hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    if (down(gA_batch, dgA, b * nn) != hipSuccess || down(gB_batch, dgB, b * nm) != hipSuccess || down(gQ_batch, dgQ, b * nn) != hipSuccess ||
+        down(gR_batch, dgR, b * mm) != hipSuccess || hipMemcpy(status, dSt, b * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
         return ALMPC_ERR_HIP;
     return ALMPC_OK;
 }
@@ -4395,10 +4484,19 @@ int sens_vjp(almpc_handle* h, const char* who, bool rows_form, const double* g_u
 
 // almpc_sensitivity_params_vjp: k_sens_pz (the VJP with z, nu and the bound gradients), then k_sens_params where a group behind the
 // stage recursions is wanted; only the wanted groups are computed and copied.
-int sens_params_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, const almpc_param_grads* out) {
-    const char* who = "sensitivity_params_vjp";
+// follow_dare (almpc_sensitivity_params_vjp_dare): k_sens_params also computes dL/dP, and one launch of k_dare_vjp adds what the loss
+// gains through P_i = DARE(A_i, B_i, Q, R) to the Q, R, A, B groups in sens.pout, in front of the copies back.
+int sens_params_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, const almpc_param_grads* out,
+                    bool follow_dare = false, int32_t* dare_status = nullptr) {
+    const char* who = follow_dare ? "sensitivity_params_vjp_dare" : "sensitivity_params_vjp";
     ALMPC_TRY(sens_check(h, who));
     if (!g_u || !out) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": null g_u or out");
+    if (follow_dare) {
+        if (!h->sens.useR) return fail(h, ALMPC_ERR_UNSUPPORTED, std::string(who) + ": the design dropped R (R[1,1] == 0): there is no DARE to follow");
+        if (h->n > DARE_MAX_N || h->m > DARE_MAX_M) return fail(h, ALMPC_ERR_UNSUPPORTED, std::string(who) + ": n <= 48 and m <= 16 (k_dare_vjp)");
+        if (h->sens.R.size() != (size_t)h->m * h->m) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": the design's weights are not kept");
+    }
+    const bool chain = follow_dare && (out->Q || out->R || out->A || out->B);   // (a group the DARE reaches)
     const bool want2 = out->u_ref || out->Q || out->P || out->A || out->R || out->S || out->B;   // (a group of k_sens_params)
     if (!want2 && !out->x0 && !out->f && !out->u_min && !out->u_max && !out->rows)
         return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": every pointer of out is null");
@@ -4441,7 +4539,9 @@ int sens_params_vjp(almpc_handle* h, const double* g_u, const double* g_x, doubl
                  off_S = off_R + b * m * m, off_B = off_S + b * m * m, out_total = off_B + b * n * m;
     if (want2) {
         if (!h->sens.w_ok) {   // (once per design, in stream order in front of k_sens_params)
-            HIP_TRY(h, h->sens.W.grow(2 * n * n + m * m));
+            HIP_TRY(h, h->sens.W.grow(2 * n * n + 2 * m * m));
+            if (h->sens.R.size() == m * m)
+                HIP_TRY(h, hipMemcpyAsync(h->sens.W + 2 * n * n + m * m, h->sens.R.data(), m * m * sizeof(double), hipMemcpyHostToDevice, h->stream));
             HIP_TRY(h, hipMemcpyAsync(h->sens.W, h->sens.Q.data(), n * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
             HIP_TRY(h, hipMemcpyAsync(h->sens.W + n * n, h->hS.data(), m * m * sizeof(double), hipMemcpyHostToDevice, h->stream));
             if (!h->batched) HIP_TRY(h, hipMemcpyAsync(h->sens.W + n * n + m * m, h->P.data(), n * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -4459,12 +4559,38 @@ int sens_params_vjp(almpc_handle* h, const double* g_u, const double* g_x, doubl
         q.ex = h->dEx; q.ev = h->dEu; q.u = h->dU; q.g_u = p.g_u; q.g_x = p.g_x; q.z = p.z; q.nu = p.nu; q.rows = p.rows;
         q.traj = h->sens.traj;
         double* o = h->sens.pout;
-        q.gur = out->u_ref ? o + off_ur : nullptr; q.gQ = out->Q ? o + off_Q : nullptr; q.gP = out->P ? o + off_P : nullptr;
+        q.gur = out->u_ref ? o + off_ur : nullptr; q.gQ = out->Q ? o + off_Q : nullptr; q.gP = (out->P || chain) ? o + off_P : nullptr;
         q.gA = out->A ? o + off_A : nullptr; q.gR = out->R ? o + off_R : nullptr; q.gS = out->S ? o + off_S : nullptr;
         q.gB = out->B ? o + off_B : nullptr;
         HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens_params), lds3));
         hipLaunchKernelGGL(k_sens_params, dim3((unsigned)grid), dim3(256), lds3, h->stream, q);
         HIP_TRY(h, hipGetLastError());
+        if (chain) {
+            HIP_TRY(h, h->sens.dstat.grow(b));
+            HIP_TRY(h, hipMemsetAsync(h->sens.dstat, 0, b * sizeof(int32_t), h->stream));   // (an instance with rows < 0 is skipped: 0)
+            DareVjpParams vp;
+            vp.n = ni; vp.m = mi; vp.batch = h->batch;
+            vp.A = q.A; vp.A_stride = q.A_stride; vp.B = q.B; vp.B_stride = q.B_stride; vp.P = q.P; vp.P_stride = q.P_stride;
+            vp.gP = o + off_P; vp.gP_stride = (long)(n * n);
+            vp.Q = h->sens.W; vp.R = h->sens.W + 2 * n * n + m * m;
+            vp.gA = q.gA; vp.gA_stride = (long)(n * n); vp.gB = q.gB; vp.gB_stride = (long)(n * m);
+            vp.gQ = q.gQ; vp.gQ_stride = (long)(n * n); vp.gR = q.gR; vp.gR_stride = (long)(m * m);
+            vp.accumulate = 1; vp.rows = p.rows; vp.status = h->sens.dstat; vp.lds_per_wave = 0;
+            HIP_TRY(h, launch_dare_vjp(vp, h->stream));
+        }
+    }
+    if (follow_dare) {   // the status words first: without dare_status a refused instance fails the call, and nothing is copied out
+        std::vector<int32_t> stt(b, 0);
+        if (chain) {
+            HIP_TRY(h, hipMemcpyAsync(stt.data(), h->sens.dstat, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, stream_wait_polling(h));
+        }
+        if (dare_status) std::copy(stt.begin(), stt.end(), dare_status);
+        else
+            for (size_t i = 0; i < b; ++i)
+                if (stt[i] != 0)
+                    return fail(h, ALMPC_ERR_NUMERIC, std::string(who) + ": the terminal weight of instance " + std::to_string(i) +
+                                " is not the stabilising DARE solution of its model (k_dare_vjp status " + std::to_string(stt[i]) + ")");
     }
     const auto back = [&](double* dst, const double* src, size_t count) {
         return dst ? hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToHost, h->stream) : hipSuccess;
@@ -4535,6 +4661,11 @@ int almpc_sensitivity_rows_vjp(almpc_handle* h, const double* g_u, const double*
 
 int almpc_sensitivity_params_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, const almpc_param_grads* out) {
     return sens_params_vjp(h, g_u, g_x, act_tol, out);
+}
+
+int almpc_sensitivity_params_vjp_dare(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, const almpc_param_grads* out,
+                                      int32_t* dare_status) {
+    return sens_params_vjp(h, g_u, g_x, act_tol, out, true, dare_status);
 }
 
 }  // extern "C"

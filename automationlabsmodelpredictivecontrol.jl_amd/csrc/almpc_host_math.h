@@ -138,6 +138,68 @@ inline bool dare(const mat& A, const mat& B, const mat& Q, const mat& R, int n, 
     return true;
 }
 
+// The adjoint of P = dare(A, B, Q, R): for a symmetric gP = dL/dP, what the loss gains in A, B, Q, R through P.  With Sm = R + B'PB,
+// K = Sm^-1 B'PA, Acl = A - B K and X the solution of the discrete Lyapunov equation X = Acl X Acl' + gP:
+//   gQ = X,  gR = K X K',  gA = 2 P Acl X,  gB = -2 P Acl X K'          (gQ, gR symmetric)
+// X by doubling: X_0 = gP, A_0 = Acl; D = A_j X_j A_j', X_{j+1} = sym(X_j + D), A_{j+1} = A_j A_j, until max|D| <= 1e-13 max(1, max|X_{j+1}|),
+// 64 doublings at most.  k_dare_vjp (csrc/almpc_dare_vjp.hip.h) is this function on the device, statement by statement.  Returns 0, or
+// with every output untouched: 1 Sm is singular; 2 an entry of X is not finite or the doubling does not stop (the closed loop is not
+// stable: P is not the stabilising solution); 3 the residual of the equation exceeds dare's acceptance bound (P is no solution).
+// Outputs that are null are skipped.
+inline int dare_vjp(const mat& A, const mat& B, const mat& Q, const mat& R, const mat& P, const mat& gP, int n, int m, mat* gA, mat* gB,
+                    mat* gQ, mat* gR) {
+    const mat At = transpose(A, n, n), Bt = transpose(B, n, m);
+    const mat PA = mul(P, A, n, n, n), PB = mul(P, B, n, n, m);
+    mat S = mul(Bt, PB, m, n, m);
+    for (size_t i = 0; i < S.size(); ++i) S[i] += R[i];
+    mat K = mul(Bt, PA, m, n, n);  // B'PA, m x n
+    if (!lu_solve(S, K, m, n)) return 1;
+    {
+        mat res = mul(At, PA, n, n, n);
+        const mat corr = mul(mul(At, PB, n, n, m), K, n, m, n);
+        for (size_t i = 0; i < res.size(); ++i) res[i] += Q[i] - P[i] - corr[i];
+        if (!(amax(res) <= 1e-7 * std::fmax(1.0, std::fmax(amax(P), amax(Q))))) return 3;
+    }
+    mat Aj = A;
+    {
+        const mat BK = mul(B, K, n, m, n);
+        for (size_t i = 0; i < Aj.size(); ++i) Aj[i] -= BK[i];
+    }
+    const mat PAcl = mul(P, Aj, n, n, n);
+    mat X = gP;
+    bool converged = false;
+    for (int it = 0; it < 64 && !converged; ++it) {
+        const mat D = mul(mul(Aj, X, n, n, n), transpose(Aj, n, n), n, n, n);
+        mat A2 = mul(Aj, Aj, n, n, n);
+        for (size_t i = 0; i < X.size(); ++i) X[i] += D[i];
+        for (int j = 0; j < n; ++j)
+            for (int i = 0; i < j; ++i) X[(size_t)j * n + i] = X[(size_t)i * n + j] = 0.5 * (X[(size_t)j * n + i] + X[(size_t)i * n + j]);
+        for (double v : X)
+            if (!std::isfinite(v)) return 2;
+        converged = amax(D) <= 1e-13 * std::fmax(1.0, amax(X));
+        Aj.swap(A2);
+    }
+    if (!converged) return 2;
+    const mat Kt = transpose(K, m, n);  // n x m
+    const mat PAX = mul(PAcl, X, n, n, n);
+    if (gQ) *gQ = X;
+    if (gA) {
+        *gA = PAX;
+        for (double& v : *gA) v *= 2.0;
+    }
+    if (gB) {
+        *gB = mul(PAX, Kt, n, n, m);
+        for (double& v : *gB) v *= -2.0;
+    }
+    if (gR) {
+        mat G = mul(mul(K, X, m, n, n), Kt, m, n, m);
+        for (int j = 0; j < m; ++j)
+            for (int i = 0; i < j; ++i) G[(size_t)j * m + i] = G[(size_t)i * m + j] = 0.5 * (G[(size_t)j * m + i] + G[(size_t)i * m + j]);
+        *gR = G;
+    }
+    return 0;
+}
+
 // Exact zero-order hold of x' = Ac x + Bc u at the sample time Ts: [Ad Bd; 0 I] = exp([Ac Bc; 0 0] Ts), without forming the augmented
 // matrix and without a linear solve (a singular Ac is no special case).  Scaling and squaring on the pair (Ad, Bd):
 //   nrm = Ts max_j sum_i |Ac[i,j]|,  s = the halvings that bring nrm to <= 0.5,  h = Ts / 2^s,  X = h Ac,

@@ -649,7 +649,9 @@ int almpc_group_sensitivity_rows_vjp(almpc_group* g, const double* g_u, const do
     });
 }
 // ... and the parameter gradients (almpc_sensitivity_params_vjp): every output is per instance, so the shards' slices are disjoint
-int almpc_group_sensitivity_params_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, const almpc_param_grads* out) {
+// (follow_dare: almpc_sensitivity_params_vjp_dare on every shard, dare_status cut the same way)
+static int group_sens_params_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, const almpc_param_grads* out,
+                                 bool follow_dare, int32_t* dare_status) {
     if (!g || !g_u || !out) return ALMPC_ERR_INVALID;
     const size_t n = (size_t)g->n, m = (size_t)g->m, nz = m * g->N;
     return group_fanout(g, [&](int i) {
@@ -659,8 +661,17 @@ int almpc_group_sensitivity_params_vjp(almpc_group* g, const double* g_u, const 
         o.x0 = at(out->x0, n); o.f = at(out->f, nz); o.u_ref = at(out->u_ref, nz); o.u_min = at(out->u_min, m); o.u_max = at(out->u_max, m);
         o.Q = at(out->Q, n * n); o.P = at(out->P, n * n); o.A = at(out->A, n * n); o.R = at(out->R, m * m); o.S = at(out->S, m * m);
         o.B = at(out->B, n * m); o.rows = out->rows ? out->rows + f : nullptr;
-        return almpc_sensitivity_params_vjp(g->hs[i], g_u + f * nz, g_x ? g_x + f * n * (g->N + 1) : nullptr, act_tol, &o);
+        const double* gx = g_x ? g_x + f * n * (g->N + 1) : nullptr;
+        if (follow_dare) return almpc_sensitivity_params_vjp_dare(g->hs[i], g_u + f * nz, gx, act_tol, &o, dare_status ? dare_status + f : nullptr);
+        return almpc_sensitivity_params_vjp(g->hs[i], g_u + f * nz, gx, act_tol, &o);
     });
+}
+int almpc_group_sensitivity_params_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, const almpc_param_grads* out) {
+    return group_sens_params_vjp(g, g_u, g_x, act_tol, out, false, nullptr);
+}
+int almpc_group_sensitivity_params_vjp_dare(almpc_group* g, const double* g_u, const double* g_x, double act_tol, const almpc_param_grads* out,
+                                            int32_t* dare_status) {
+    return group_sens_params_vjp(g, g_u, g_x, act_tol, out, true, dare_status);
 }
 
 // Asynchronous read-back of the whole batch: the request goes to every device (pack kernels / copy streams), the ticket is the group's;

@@ -59,7 +59,8 @@
 //                                                                                     differences z_0 - z_1, z_N - z_{N+1} are absent)
 //     dL/dumin_i = sum_k nu_(k,i) over the rows at the lower bound, dL/dumax_i over those at the upper (at both: lower)
 // Conventions: a symmetric matrix gradient G_Q is the symmetric matrix with dL = sum_ij (G_Q)_ij dQ_ij for symmetric dQ.  P is data,
-// also where the design computed it as a DARE: its dependence on A, B, Q, R is not followed.  Where the design dropped R or S (the
+// also where the design computed it as a DARE: its dependence on A, B, Q, R is followed behind these kernels, by k_dare_vjp
+// (csrc/almpc_dare_vjp.hip.h, almpc_sensitivity_params_vjp_dare), from the P group they write.  Where the design dropped R or S (the
 // reference's [1,1] rule, src/sub/design_mpc.jl:423-456) that gradient is zero.  x_ref needs no output:
 // dL/dx_ref[:,1] = g_x[1] - dL/dx0 and dL/dx_ref[:,k] = g_x[k] for k >= 2.  Weakly active rows: as above, the derivative of the face on
 // which every flagged row is held.  Every sum runs in ascending stage order in one thread: the same bits wherever the instance sits.

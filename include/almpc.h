@@ -709,7 +709,8 @@ int almpc_sensitivity_rows_vjp(almpc_handle* h, const double* g_u, const double*
  *     u_ref[:,k] = g_u[:,k] - nu_k + 2 S (z_k - z_{k+1}) - 2 S (z_{k-1} - z_k)    (S terms only where S is in the design)
  *     u_min_i = sum_k nu_(k,i) over the rows at the lower bound, u_max_i over those at the upper (a row at both counts as lower)
  * Conventions: the gradient of a symmetric matrix (Q, P, R, S) is the symmetric matrix G with dL = sum_ij G_ij dM_ij for symmetric dM.
- * P is data, also where the design computed it as a DARE: its dependence on A, B, Q, R is not followed.  Where the design dropped R
+ * P is data in this call, also where the design computed it as a DARE; almpc_sensitivity_params_vjp_dare (below) follows its dependence
+ * on A, B, Q, R.  Where the design dropped R
  * or S (R[1,1] == 0; S[1,1] == 0: src/sub/design_mpc.jl:423-456) that gradient is zero.  x_ref needs no output:
  * dL/dx_ref[:,1] = g_x[1] - x0, dL/dx_ref[:,k] = g_x[k] for k >= 2.  At a weakly active row: the derivative of the face on which every
  * flagged row is held, as above.  Outputs are per instance also where the design is shared (the caller sums over the batch), and for
@@ -735,6 +736,26 @@ int almpc_sensitivity_params_vjp(almpc_handle* h, const double* g_u, const doubl
 /* ... of the whole batch of a group: every array with `batch` = the whole batch, cut along the shards */
 int almpc_group_sensitivity_params_vjp(almpc_group* g, const double* g_u, const double* g_x /* or NULL */, double act_tol,
                                        const almpc_param_grads* out);
+
+/*
+ * The same with the terminal weight followed: P_i = DARE(A_i, B_i, Q, R) is a function of the model and the weights (the reference has
+ * no other P: src/sub/design_mpc.jl:318-327), so Q, R, A, B also gain what the loss gains through P.  With the P group gP of the call
+ * above (computed internally when out->P is NULL) one launch of k_dare_vjp (almpc_dare_vjp_batched below, DESIGN.md "k_dare_vjp") adds
+ *     Q += X,   R += K X K',   A += 2 P Acl X,   B += -2 P Acl X K'        X = Acl X Acl' + gP,  Acl = A - B K,  K = (R + B'PB)^-1 B'PA
+ * per instance, from the design's own A_i, B_i, P_i, Q, R.  out->P is still the gradient in P as data; x0, f, u_ref, u_min, u_max, S,
+ * P and rows are bit for bit those of almpc_sensitivity_params_vjp, and so are its refusals and the -1 and zeros of an unsolved
+ * instance (dare_status 0).  No flag records where P came from: the kernel tests it.  dare_status[i] = 0: followed; 1: R + B'PB is
+ * singular; 2: the closed loop A - B K is not stable (P solves the equation but is not the stabilising solution); 3: P does not solve
+ * the equation of the design's model (a P the caller gave that is no DARE solution).  An instance with a non-zero status keeps the
+ * P-as-data values in Q, R, A, B bit for bit and the call returns ALMPC_OK; with dare_status == NULL such an instance makes the call
+ * ALMPC_ERR_NUMERIC (almpc_last_error names the lowest one) and nothing is copied out.  ALMPC_ERR_UNSUPPORTED: a design that dropped
+ * R (R[1,1] == 0: no DARE), n > 48 or m > 16.  Not followed anywhere else: the re-linearisation pipeline, almpc_design_ltv and the
+ * SQP loop, and designs with state rows are refused as above.
+ */
+int almpc_sensitivity_params_vjp_dare(almpc_handle* h, const double* g_u, const double* g_x /* or NULL */, double act_tol,
+                                      const almpc_param_grads* out, int32_t* dare_status /* [batch] or NULL */);
+int almpc_group_sensitivity_params_vjp_dare(almpc_group* g, const double* g_u, const double* g_x /* or NULL */, double act_tol,
+                                            const almpc_param_grads* out, int32_t* dare_status /* [batch] or NULL */);
 
 /*
  * Timing of the last almpc_calculate (needs ALMPC_FLAG_TIMING): milliseconds spent in the ADMM
@@ -776,6 +797,29 @@ int almpc_dare(int n, int m, const double* A, const double* B, const double* Q, 
  * ALMPC_ERR_NUMERIC when R is singular; ALMPC_ERR_UNSUPPORTED beyond n <= 48, m <= 16. */
 int almpc_dare_batched(int device_id, int n, int m, int batch, const double* A_batch, const double* B_batch,
                        const double* Q, const double* R, double* P_batch, int32_t* status);
+
+/*
+ * The adjoint of almpc_dare (host math): for P = DARE(A, B, Q, R) and a symmetric g_P = dL/dP (n*n), what the loss gains through P in
+ * the four arguments.  Sm = R + B'PB, K = Sm^-1 B'PA, Acl = A - B K, X = Acl X Acl' + g_P (discrete Lyapunov equation, by doubling):
+ *     g_Q = X,   g_R = K X K',   g_A = 2 P Acl X,   g_B = -2 P Acl X K'
+ * g_Q and g_R are symmetric (the convention of almpc_param_grads).  Outputs may be NULL.  ALMPC_ERR_NUMERIC, nothing written, with
+ * the status in almpc_last_error(NULL) (the calling thread's last such failure, handed out once): 1 R + B'PB is singular; 2 the closed
+ * loop is not stable to working precision (64 doublings), P is not the stabilising solution; 3 the residual of the equation exceeds
+ * almpc_dare's acceptance bound 1e-7 max(1, max|P|, max|Q|), P is no solution for this model.
+ */
+int almpc_dare_vjp(int n, int m, const double* A, const double* B, const double* Q, const double* R,
+                   const double* P, const double* g_P, double* g_A, double* g_B, double* g_Q, double* g_R);
+
+/* The same for a batch on device `device_id` (the style of almpc_dare_batched: no handle; host pointers, synchronous; the same layouts):
+ * P_batch, gP_batch, gA_batch, gQ_batch [batch][n*n], gB_batch [batch][n*m], gR_batch [batch][m*m]; the outputs may be NULL; one wave per
+ * instance (k_dare_vjp).  status[i] = 0, or 1 / 2 / 3 as above (the output slots i are left untouched).  What the handle calls cannot
+ * serve: a black-box design takes P from the linearisation at the LAST reference and its dynamics from the FIRST, so its caller chains
+ * out->P of almpc_sensitivity_params_vjp through this call on the last-reference Jacobians.
+ * Returns ALMPC_OK even when some instances fail; ALMPC_ERR_NO_DEVICE without a gfx950 device (no CPU path);
+ * ALMPC_ERR_NUMERIC when R is singular; ALMPC_ERR_UNSUPPORTED beyond n <= 48, m <= 16. */
+int almpc_dare_vjp_batched(int device_id, int n, int m, int batch, const double* A_batch, const double* B_batch,
+                           const double* Q, const double* R, const double* P_batch, const double* gP_batch,
+                           double* gA_batch, double* gB_batch, double* gQ_batch, double* gR_batch, int32_t* status);
 
 /* Exact zero-order hold of x' = Ac x + Bc u at the sample time Ts (host math, like almpc_dare): [Ad Bd; 0 I] = exp([Ac Bc; 0 0] Ts) by
  * scaling and squaring on the pair (Ad, Bd) -- no augmented matrix, no linear solve, so a singular Ac is no special case (the double

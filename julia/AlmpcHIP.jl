@@ -21,7 +21,7 @@ export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_s
        group_sqp_start!, group_sqp_iterate!, group_sqp_solve!, group_set_sqp_hessian!, group_set_sqp_row_multipliers!, group_state_multipliers, group_sqp_skipped, group_x0_staging, group_update_initialization_staged!, group_results_async,
        group_results_wait!, sensitivity, device_sensitivity, sensitivity_vjp, group_sensitivity, group_sensitivity_vjp,
        sensitivity_rows, sensitivity_rows_vjp, group_sensitivity_rows, group_sensitivity_rows_vjp, sensitivity_params_vjp,
-       group_sensitivity_params_vjp
+       group_sensitivity_params_vjp, dare_vjp, dare_vjp_batched
 
 const libalmpc = get(ENV, "ALMPC_LIB", "libalmpc.so")
 
@@ -554,6 +554,37 @@ function dare_batched(A_batch::Array{Float64,3}, B_batch::Array{Float64,3}, Q::M
     return P, status
 end
 """
+    dare_vjp(A, B, Q, R, P, g_P) -> (g_A, g_B, g_Q, g_R)
+
+The adjoint of `dare` (`almpc_dare_vjp`, host): for P = DARE(A, B, Q, R) and a symmetric g_P = dL/dP, what the loss gains through P in
+A, B, Q, R.  An error when P is not the stabilising solution of this model.
+"""
+function dare_vjp(A::Matrix{Float64}, B::Matrix{Float64}, Q::Matrix{Float64}, R::Matrix{Float64}, P::Matrix{Float64}, g_P::Matrix{Float64})
+    n, m = size(B)
+    g_A, g_B, g_Q, g_R = Matrix{Float64}(undef, n, n), Matrix{Float64}(undef, n, m), Matrix{Float64}(undef, n, n), Matrix{Float64}(undef, m, m)
+    rc = ccall((:almpc_dare_vjp, libalmpc), Cint, (Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+               Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), n, m, A, B, Q, R, P, g_P, g_A, g_B, g_Q, g_R)
+    rc == 0 || error("almpc_dare_vjp: " * unsafe_string(ccall((:almpc_last_error, libalmpc), Cstring, (Ptr{Cvoid},), C_NULL)) * " ($rc)")
+    return g_A, g_B, g_Q, g_R
+end
+"""
+    dare_vjp_batched(A_batch, B_batch, Q, R, P_batch, gP_batch; device = 0) -> (g_A, g_B, g_Q, g_R, status)
+
+`dare_vjp` on the GPU, one wave per instance (`almpc_dare_vjp_batched`): batch last.  `status[i] != 0` (1 singular R + B'PB, 2 closed loop
+not stable, 3 P does not solve the equation): the slices i are then NaN.
+"""
+function dare_vjp_batched(A_batch::Array{Float64,3}, B_batch::Array{Float64,3}, Q::Matrix{Float64}, R::Matrix{Float64},
+                          P_batch::Array{Float64,3}, gP_batch::Array{Float64,3}; device::Integer = 0)
+    n, m, b = size(B_batch, 1), size(B_batch, 2), size(B_batch, 3)
+    size(A_batch) == size(P_batch) == size(gP_batch) == (n, n, b) || throw(DimensionMismatch("A_batch, P_batch, gP_batch must be n x n x batch"))
+    g_A, g_B, g_Q, g_R, status = fill(NaN, n, n, b), fill(NaN, n, m, b), fill(NaN, n, n, b), fill(NaN, m, m, b), Vector{Int32}(undef, b)
+    rc = ccall((:almpc_dare_vjp_batched, libalmpc), Cint,
+               (Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), device, n, m, b, A_batch, B_batch, Q, R, P_batch, gP_batch, g_A, g_B, g_Q, g_R, status)
+    rc == 0 || error("almpc_dare_vjp_batched failed ($rc)")
+    return g_A, g_B, g_Q, g_R, status
+end
+"""
     set_terminal_weight!(mod, mode)
 
 Before a design: `:given` (default) or `:dare_device` -- `design_batched!` without a P and every step of the re-linearisation pipeline
@@ -711,17 +742,26 @@ function param_grad_arrays(n, m, N, batch, want)
     return out, ParamGrads(pf(:x0), pf(:f), pf(:u_ref), pf(:u_min), pf(:u_max), pf(:Q), pf(:P), pf(:A), pf(:R), pf(:S), pf(:B), pointer(out[:rows]))
 end
 """
-    sensitivity_params_vjp(mod, g_u, g_x = nothing; want = PARAM_GROUPS, act_tol = 0.0) -> Dict
+    sensitivity_params_vjp(mod, g_u, g_x = nothing; want = PARAM_GROUPS, act_tol = 0.0, terminal = :data) -> Dict
 
 Gradients of the loss of `sensitivity_vjp` in the problem data, per instance (`almpc_sensitivity_params_vjp`): `:x0` n x batch, `:f` and
 `:u_ref` m x N x batch, `:u_min`, `:u_max` m x batch, `:Q`, `:P`, `:A` n x n x batch, `:R`, `:S` m x m x batch, `:B` n x m x batch, and
-`:rows`.  For a shared design the caller sums over the batch.
+`:rows`.  For a shared design the caller sums over the batch.  `terminal = :dare` (`almpc_sensitivity_params_vjp_dare`): the terminal
+weight P = are(Discrete, A, B, Q, R) of the reference's own problem is followed into `:Q`, `:R`, `:A`, `:B`, and the Dict carries
+`:dare_status` (0: followed; else that instance keeps its `:data` values).
 """
 function sensitivity_params_vjp(mod::HipModeler, g_u::Array{Float64}, g_x::Union{Nothing,Array{Float64}} = nothing;
-                                want = PARAM_GROUPS, act_tol::Real = 0.0)
+                                want = PARAM_GROUPS, act_tol::Real = 0.0, terminal::Symbol = :data)
+    terminal in (:data, :dare) || error("sensitivity_params_vjp: terminal must be :data or :dare")
     check_sens_sizes(mod.n, mod.m, mod.N, mod.batch, g_u, g_x)
     out, pg = param_grad_arrays(mod.n, mod.m, mod.N, mod.batch, want)
     px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
+    if terminal === :dare
+        st = out[:dare_status] = Vector{Int32}(undef, mod.batch)
+        GC.@preserve g_x out check(mod.handle, ccall((:almpc_sensitivity_params_vjp_dare, libalmpc), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ref{ParamGrads}, Ptr{Int32}), mod.handle, g_u, px, act_tol, Ref(pg), st))
+        return out
+    end
     GC.@preserve g_x out check(mod.handle, ccall((:almpc_sensitivity_params_vjp, libalmpc), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ref{ParamGrads}), mod.handle, g_u, px, act_tol, Ref(pg)))
     return out
@@ -888,12 +928,19 @@ function group_sensitivity_vjp(g::HipGroup, g_u::Array{Float64}, g_x::Union{Noth
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), g.group, g_u, px, act_tol, g_x0, rows))
     return g_x0, rows
 end
-"`sensitivity_params_vjp` for the whole batch (`almpc_group_sensitivity_params_vjp`)"
+"`sensitivity_params_vjp` for the whole batch (`almpc_group_sensitivity_params_vjp`, `almpc_group_sensitivity_params_vjp_dare`)"
 function group_sensitivity_params_vjp(g::HipGroup, g_u::Array{Float64}, g_x::Union{Nothing,Array{Float64}} = nothing;
-                                      want = PARAM_GROUPS, act_tol::Real = 0.0)
+                                      want = PARAM_GROUPS, act_tol::Real = 0.0, terminal::Symbol = :data)
+    terminal in (:data, :dare) || error("group_sensitivity_params_vjp: terminal must be :data or :dare")
     check_sens_sizes(g.n, g.m, g.N, g.batch, g_u, g_x)
     out, pg = param_grad_arrays(g.n, g.m, g.N, g.batch, want)
     px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
+    if terminal === :dare
+        st = out[:dare_status] = Vector{Int32}(undef, g.batch)
+        GC.@preserve g_x out gcheck(g.group, ccall((:almpc_group_sensitivity_params_vjp_dare, libalmpc), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ref{ParamGrads}, Ptr{Int32}), g.group, g_u, px, act_tol, Ref(pg), st))
+        return out
+    end
     GC.@preserve g_x out gcheck(g.group, ccall((:almpc_group_sensitivity_params_vjp, libalmpc), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ref{ParamGrads}), g.group, g_u, px, act_tol, Ref(pg)))
     return out
