@@ -494,20 +494,51 @@ int riccati_weights(almpc_handle* h, const hm::mat& Qm, const hm::mat& Rm, const
     return ALMPC_OK;
 }
 
+// LDS a workgroup can have on gfx950, in bytes (the stage-wise layer below sizes its launches by it)
+constexpr int LDS_BUDGET = 160 * 1024;
+
 bool riccati_shape_ok(const almpc_handle* h) {
-    return h->n <= 32 && h->m <= 16 && (long)h->m * h->N <= 1024 && riccati_lds_doubles(h->n, h->m, h->N) * sizeof(double) <= 160 * 1024;
+    return h->n <= 32 && h->m <= 16 && (long)h->m * h->N <= 1024 && riccati_lds_doubles(h->n, h->m, h->N) * sizeof(double) <= LDS_BUDGET;
 }
 
-// What a launch of the stage-wise solvers is for, beyond the plain solve (by value: a nested launch does not inherit it)
-struct SolveMode {
-    bool x0_from_results = false;   // a deferred redo: x0 = stage 1 of the step's own x (the caller may have handed over the next x0 since)
-    bool gated = false;             // enqueued behind the step: returns at once unless the step left an instance undecided (almpc_handle::Redo)
-    bool predicted = false;         // a gated redo that is EXPECTED to have work (tier policy of a plain redo)
-    bool build_ghat = false;        // k_sdual's build of the cached responses (sdual_build_ghat): never gated
+// Which instances a launch of the stage-wise solvers takes (the kernels compare the int: SdualParams::filter)
+// ALL: the whole batch; UNSOLVED: the instances whose status is not 0 (the redo behind a condensed step); SQP_FLAGGED, SQP_ALL: the QP
+// of the current SQP iteration, for the instances the condensed path flagged or left unsolved / for every instance
+enum SolveFilter : int { FILTER_ALL = 0, FILTER_UNSOLVED = 1, FILTER_SQP_FLAGGED = 2, FILTER_SQP_ALL = 3 };
+
+// One call of launch_riccati / launch_sgains / launch_sdual: the plain solve of the whole batch unless a field says otherwise.
+// By value: a nested launch does not inherit it.
+struct SolveCall {
+    SolveFilter filter = FILTER_ALL;
+    const double* guess = nullptr;   // inputs [batch][N][m] whose bounds seed the working set
+    int max_iter = 0;                // cap of the working-set changes (0: the solver's own)
+    bool x0_from_results = false;    // a deferred redo: x0 = stage 1 of the step's own x (the caller may have handed over the next x0 since)
+    bool gated = false;              // enqueued behind the step: returns at once unless the step left an instance undecided (almpc_handle::Redo)
+    bool predicted = false;          // a gated redo that is EXPECTED to have work (tier policy of a plain redo)
+    // k_sdual only
+    bool single_launch = false;      // one launch with room for 64 or 128 rows in place of the tiers (few instances: a redo)
+    int first_tier = 0;              // 1: starts that are known to hold many rows skip the 32-row tier
+    RowMultOut rows = {};            // the SQP loop's row multipliers
 };
 
-// k_riccati over the batch (filter = 0) or over the instances whose status is not 0 (filter = 1, start = the step's own result)
-hipError_t launch_riccati(almpc_handle* h, int filter, const double* guess, int max_iter, SolveMode mode = {}) {
+// Per-wave slices of LDS: as many waves per workgroup as fit the budget, at most `most`, at least one ...
+int waves_in_lds(size_t per_wave, int most) {
+    while (most > 1 && per_wave * most > LDS_BUDGET) --most;
+    return most;
+}
+// ... and the workgroups that cover the batch with them, capped (a wave walks the instances beyond the cap)
+int capped_grid(int batch, int waves, int cap) { return std::min((batch + waves - 1) / waves, cap); }
+// A kernel on such slices: its limit of dynamic LDS raised to `lds` where need be, then the launch (a macro: the launch names the kernel)
+#define LAUNCH_WAVES(KERNEL, wgs, waves, lds, st, p)                                          \
+    [&]() -> hipError_t {                                                                     \
+        const hipError_t e_ = ensure_dyn_lds(reinterpret_cast<const void*>(KERNEL), lds);     \
+        if (e_ != hipSuccess) return e_;                                                      \
+        hipLaunchKernelGGL(KERNEL, dim3(wgs), dim3(64 * (waves)), lds, st, p);                \
+        return hipGetLastError();                                                             \
+    }()
+
+// k_riccati over the instances of call.filter, start = call.guess
+hipError_t launch_riccati(almpc_handle* h, SolveCall call) {
     RiccatiParams rp;
     rp.n = h->n; rp.m = h->m; rp.N = h->N; rp.batch = h->batch;
     const bool pi = h->batched && !h->structured ? true : h->batched;
@@ -518,17 +549,16 @@ hipError_t launch_riccati(almpc_handle* h, int filter, const double* guess, int 
     if (!rp.Q || !rp.R || !rp.P || !h->rKst) return hipErrorInvalidValue;   // no riccati_weights() for this design: nothing to launch with
     rp.umin = h->dUmin; rp.umax = h->dUmax;
     rp.uref = h->dUref; rp.uref_stride = h->uref_stride; rp.xref = h->dXref; rp.xref_stride = h->xref_stride;
-    rp.x0 = h->dX0; rp.x0_stride = h->n; rp.uguess = guess; rp.filter = filter; rp.Kst = h->rKst; rp.Pst = h->rPst;
-    if (mode.x0_from_results) { rp.x0 = h->dX; rp.x0_stride = (long)h->n * (h->N + 1); }
-    if (mode.gated) { rp.gate = h->redo.dGate; rp.gate_val = h->redo.step_serial; }
+    rp.x0 = h->dX0; rp.x0_stride = h->n; rp.uguess = call.guess; rp.filter = call.filter; rp.Kst = h->rKst; rp.Pst = h->rPst;
+    if (call.x0_from_results) { rp.x0 = h->dX; rp.x0_stride = (long)h->n * (h->N + 1); }
+    if (call.gated) { rp.gate = h->redo.dGate; rp.gate_val = h->redo.step_serial; }
     rp.x = h->dX; rp.ex = h->dEx; rp.u = h->dU; rp.eu = h->dEu; rp.status = h->dStatus; rp.piters = h->dPiters;
-    rp.max_iter = max_iter > 0 ? max_iter : 20 * h->N * h->m + 50;
+    rp.max_iter = call.max_iter > 0 ? call.max_iter : 20 * h->N * h->m + 50;
     rp.tol = 1e-9;
     rp.lds_per_wave = riccati_lds_doubles(h->n, h->m, h->N);
     rp.A_kstride = 0; rp.B_kstride = 0; rp.c = nullptr; rp.c_stride = 0; rp.ebar = nullptr; rp.ebar_stride = 0;
     rp.qu = nullptr; rp.qu_stride = 0; rp.qu_scale = 1.0; rp.flag = nullptr; rp.v_only = 0;
-    if (h->sqp.ready && filter >= 2) {   // the QP of the current SQP iteration: stage models, defects, state errors, input gradient
-                                         // (2: instances the condensed path flagged or left unsolved; 3: every instance)
+    if (h->sqp.ready && call.filter >= FILTER_SQP_FLAGGED) {   // the QP of the current SQP iteration: stage models, defects, state errors, input gradient
         const almpc_handle::Sqp& q = h->sqp;
         const long n = h->n, m = h->m, N = h->N;
         rp.A = q.A; rp.A_stride = N * n * n; rp.A_kstride = n * n;
@@ -539,25 +569,16 @@ hipError_t launch_riccati(almpc_handle* h, int filter, const double* guess, int 
         rp.x0 = nullptr; rp.flag = h->bFlag; rp.v_only = 1;
     }
     const size_t per = (size_t)rp.lds_per_wave * sizeof(double);
-    int waves = RICCATI_WAVES;   // per-wave slices of LDS: as many waves per workgroup as fit
-    while (waves > 1 && per * waves > 160 * 1024) --waves;
+    const int waves = waves_in_lds(per, RICCATI_WAVES);
     const size_t lds = per * waves;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    int wgs = (h->batch + waves - 1) / waves;
-    const int cap = h->num_cus * 2;
-    if (wgs > cap) wgs = cap;
-#define RICCATI_LAUNCH(NC_, MC_)                                                                               \
-    do {                                                                                                       \
-        const hipError_t e_ = ensure_dyn_lds(reinterpret_cast<const void*>(k_riccati_t<NC_, MC_>), lds);       \
-        if (e_ != hipSuccess) return e_;                                                                       \
-        hipLaunchKernelGGL((k_riccati_t<NC_, MC_>), dim3(wgs), dim3(64 * waves), lds, h->stream, rp);          \
-    } while (0)
+    if (lds > LDS_BUDGET) return hipErrorInvalidValue;
+    const int wgs = capped_grid(h->batch, waves, h->num_cus * 2);
+#define RICCATI_LAUNCH(NC_, MC_) return LAUNCH_WAVES((k_riccati_t<NC_, MC_>), wgs, waves, lds, h->stream, rp)
     if (h->n == 12 && h->m == 4 && !h->sw.riccati_generic) RICCATI_LAUNCH(12, 4);
     else if (h->n == 4 && h->m == 2 && !h->sw.riccati_generic) RICCATI_LAUNCH(4, 2);
     else if (h->n == 2 && h->m == 1 && !h->sw.riccati_generic) RICCATI_LAUNCH(2, 1);
     else RICCATI_LAUNCH(0, 0);
 #undef RICCATI_LAUNCH
-    return hipGetLastError();
 }
 
 // ---- stage-wise dual active-set solve (k_sdual) ----------------------------------------------------------------------------
@@ -573,34 +594,25 @@ bool sdual_shape_ok(int n, int m, int N, bool useS) {
     int NT = 0, MC = 0;
     if (!sdual_pick_shape(useS ? n + m : n, m, &NT, &MC)) return false;
     if ((N + 64 / (NT + MC)) / (64 / (NT + MC)) > 64) return false;   // (one bit per coordinate and lane in the working-set mask)
-    return (size_t)sdual_lds_doubles(NT, MC, N, SD_WCAP2) * sizeof(double) <= 160 * 1024;
+    return (size_t)sdual_lds_doubles(NT, MC, N, SD_WCAP2) * sizeof(double) <= LDS_BUDGET;
 }
 
-// Stage records of a SHARED model on the device (host Riccati, design time), state box / terminal equality / S of the design.
-// Rm: the reference's branch rule applied (zeros when R[1,1] == 0); Sm null: no input-rate term.
-hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int max_iter, bool single_launch = false, int first_tier = 0,
-                        SolveMode mode = {}, RowMultOut rmult = {});
 hipError_t sdual_build_ghat(almpc_handle* h);
 
-int sdual_setup_shared(almpc_handle* h, const hm::mat& Am, const hm::mat& Bm, const hm::mat& Qm, const hm::mat& Rm, const hm::mat* Sm,
-                       const hm::mat& Pm, const double* xmin, const double* xmax, bool terminal_eq) {
-    const int n = h->n, m = h->m, N = h->N;
+// Front of the two set-ups below: whether there is an input-rate term, the size of the stage state and the instantiated shape for it
+int sdual_setup_shape(almpc_handle* h, bool useS) {
     almpc_handle::Sd& sd = h->sd;
     sd.ready = false;
-    sd.useS = Sm != nullptr;
-    sd.nt = sd.useS ? n + m : n;
-    if (!sdual_pick_shape(sd.nt, m, &sd.NT, &sd.MC) || !sdual_shape_ok(n, m, N, sd.useS))
+    sd.useS = useS;
+    sd.nt = useS ? h->n + h->m : h->n;
+    if (!sdual_pick_shape(sd.nt, h->m, &sd.NT, &sd.MC) || !sdual_shape_ok(h->n, h->m, h->N, useS))
         return fail(h, ALMPC_ERR_UNSUPPORTED, "stage-wise solve: n (+ m with an input-rate weight) <= 48, m <= 16 and (N + 1)(n + m) <= 4096");
-    hm::mat rec;
-    bool inv = false;
-    if (!hm::stage_records(Am, Bm, Qm, Rm, Sm, Pm, n, m, N, sd.NT, sd.MC, rec, inv))
-        return fail(h, ALMPC_ERR_NUMERIC, "stage-wise solve: R + B'PB is singular (Riccati recursion of the unconstrained problem)");
-    const size_t stage = (size_t)sdual_rec_stage(sd.NT, sd.MC);
-    const size_t cnt = inv ? stage : stage * N;
-    HIP_TRY(h, sd.rec.grow(cnt));
-    HIP_TRY(h, hipMemcpy(sd.rec, rec.data() + (inv ? stage * (N - 1) : 0), cnt * sizeof(double), hipMemcpyHostToDevice));
-    sd.rec_stride = 0;
-    sd.rec_kstride = inv ? 0 : (long)stage;
+    return ALMPC_OK;
+}
+// ... and their back: state box, terminal equality, the tiers' overflow words and saved working sets, S, no reference terms yet
+int sdual_setup_rows(almpc_handle* h, const hm::mat* Sm, const double* xmin, const double* xmax, bool terminal_eq) {
+    const int n = h->n;
+    almpc_handle::Sd& sd = h->sd;
     sd.has_box = xmin != nullptr;
     if (sd.has_box) {
         HIP_TRY(h, sd.xmin.once((size_t)n));
@@ -614,6 +626,27 @@ int sdual_setup_shared(almpc_handle* h, const hm::mat& Am, const hm::mat& Bm, co
     HIP_TRY(h, hipMemset(sd.ovf, 0, ((size_t)h->batch + 2) * sizeof(int32_t)));
     sd.S = Sm ? *Sm : hm::mat();
     sd.has_base = false; sd.base_stride = 0;
+    return ALMPC_OK;
+}
+
+// Stage records of a SHARED model on the device (host Riccati, design time), state box / terminal equality / S of the design.
+// Rm: the reference's branch rule applied (zeros when R[1,1] == 0); Sm null: no input-rate term.
+int sdual_setup_shared(almpc_handle* h, const hm::mat& Am, const hm::mat& Bm, const hm::mat& Qm, const hm::mat& Rm, const hm::mat* Sm,
+                       const hm::mat& Pm, const double* xmin, const double* xmax, bool terminal_eq) {
+    const int n = h->n, m = h->m, N = h->N;
+    almpc_handle::Sd& sd = h->sd;
+    ALMPC_TRY(sdual_setup_shape(h, Sm != nullptr));
+    hm::mat rec;
+    bool inv = false;
+    if (!hm::stage_records(Am, Bm, Qm, Rm, Sm, Pm, n, m, N, sd.NT, sd.MC, rec, inv))
+        return fail(h, ALMPC_ERR_NUMERIC, "stage-wise solve: R + B'PB is singular (Riccati recursion of the unconstrained problem)");
+    const size_t stage = (size_t)sdual_rec_stage(sd.NT, sd.MC);
+    const size_t cnt = inv ? stage : stage * N;
+    HIP_TRY(h, sd.rec.grow(cnt));
+    HIP_TRY(h, hipMemcpy(sd.rec, rec.data() + (inv ? stage * (N - 1) : 0), cnt * sizeof(double), hipMemcpyHostToDevice));
+    sd.rec_stride = 0;
+    sd.rec_kstride = inv ? 0 : (long)stage;
+    ALMPC_TRY(sdual_setup_rows(h, Sm, xmin, xmax, terminal_eq));
     sd.per_instance = false; sd.gain_N = 0; sd.sqp = false;
     sd.scr_ready = false;
     sd.ready = true;
@@ -627,26 +660,6 @@ int sdual_setup_shared(almpc_handle* h, const hm::mat& Am, const hm::mat& Bm, co
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
     return ALMPC_OK;
-}
-
-// Cached responses of a shared model: every coordinate that can be a row, one sweep each, once (k_sdual's build mode on
-// min(TP, 2048) waves), TP x TP doubles.  Memory cap 256 MB per handle (TP <= 5792: e.g. the quadrotor with S up to N = 361); above it
-// the table is not built and a working-set change costs two sweeps again (SdualParams::ghat == null).  Enqueued on the handle's stream.
-hipError_t sdual_build_ghat(almpc_handle* h) {
-    almpc_handle::Sd& sd = h->sd;
-    sd.ghat_wanted = false;   // (one attempt per design)
-    const size_t TP = (size_t)sdual_tp(sd.NT, sd.MC, h->N);
-    if (TP * TP * sizeof(double) > ((size_t)256 << 20)) return hipSuccess;
-    hipError_t e = sd.ghat.grow(TP * TP);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(sd.ghat, 0, TP * TP * sizeof(double), h->stream);
-    if (e != hipSuccess) return e;
-    SolveMode build;
-    build.build_ghat = true;
-    e = launch_sdual(h, 0, nullptr, 0, false, 0, build);
-    if (e != hipSuccess) return e;
-    sd.ghat_ready = true;
-    return hipSuccess;
 }
 
 // Linear cost terms of the stage-wise problem that depend on the references: only the input-rate term does (it is on u = v + u_ref,
@@ -685,12 +698,8 @@ int sdual_setup_batched(almpc_handle* h, const hm::mat& Qm, const hm::mat& Rm, c
                         const double* xmin, const double* xmax, bool terminal_eq) {
     const int n = h->n, m = h->m, N = h->N;
     almpc_handle::Sd& sd = h->sd;
-    sd.ready = false;
-    sd.useS = Sm != nullptr;
-    sd.nt = sd.useS ? n + m : n;
-    if (!sdual_pick_shape(sd.nt, m, &sd.NT, &sd.MC) || !sdual_shape_ok(n, m, N, sd.useS))
-        return fail(h, ALMPC_ERR_UNSUPPORTED, "stage-wise solve: n (+ m with an input-rate weight) <= 48, m <= 16 and (N + 1)(n + m) <= 4096");
-    if ((size_t)sgains_lds_doubles(sd.nt, m) * sizeof(double) > 160 * 1024) return fail(h, ALMPC_ERR_UNSUPPORTED, "stage-wise solve: the gain recursion does not fit LDS");
+    ALMPC_TRY(sdual_setup_shape(h, Sm != nullptr));
+    if ((size_t)sgains_lds_doubles(sd.nt, m) * sizeof(double) > LDS_BUDGET) return fail(h, ALMPC_ERR_UNSUPPORTED, "stage-wise solve: the gain recursion does not fit LDS");
     hm::mat Qs = Qm, Rs = Rm;
     if (Rm[0] == 0.0) std::fill(Rs.begin(), Rs.end(), 0.0);
     HIP_TRY(h, sd.dQ.once((size_t)n * n));
@@ -707,22 +716,10 @@ int sdual_setup_batched(almpc_handle* h, const hm::mat& Qm, const hm::mat& Rm, c
     HIP_TRY(h, sd.rec.grow(cnt));
     sd.rec_stride = (long)(sd.gain_N * stage);
     sd.rec_kstride = invariant ? 0 : (long)stage;
-    sd.per_instance = true; sd.sqp = false;
-    sd.has_box = xmin != nullptr;
-    if (sd.has_box) {
-        HIP_TRY(h, sd.xmin.once((size_t)n));
-        HIP_TRY(h, sd.xmax.once((size_t)n));
-        HIP_TRY(h, hipMemcpy(sd.xmin, xmin, n * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(sd.xmax, xmax, n * sizeof(double), hipMemcpyHostToDevice));
-    }
-    sd.has_eq = terminal_eq;
-    HIP_TRY(h, sd.ovf.once((size_t)h->batch + 2));   // (+ the tiers' gate word: SdualParams::ovf_gate)
-    HIP_TRY(h, hipMemset(sd.ovf, 0, ((size_t)h->batch + 2) * sizeof(int32_t)));
-    HIP_TRY(h, sd.wsave.once((size_t)h->batch * SDUAL_WSAVE));
+    sd.per_instance = true; sd.sqp = false;   // (scr_ready and the table flags keep what a shared design left: per_instance is asked before them)
+    ALMPC_TRY(sdual_setup_rows(h, Sm, xmin, xmax, terminal_eq));
     HIP_TRY(h, sd.bad.once((size_t)h->batch));
     HIP_TRY(h, hipMemset(sd.bad, 0, (size_t)h->batch * sizeof(int)));
-    sd.S = Sm ? *Sm : hm::mat();
-    sd.has_base = false; sd.base_stride = 0;
     sd.ready = true;
     return ALMPC_OK;
 }
@@ -733,17 +730,11 @@ hipError_t launch_dare(DareParams p, hipStream_t st) {
     const int waves = dare_waves(p.n, p.m), d = p.n > p.m ? p.n : p.m;
     const size_t lds = (size_t)p.lds_per_wave * sizeof(double) * waves;
     const int wgs = (p.batch + waves - 1) / waves;
-#define DARE_RL(RL_)                                                                              \
-    do {                                                                                          \
-        const hipError_t e_ = ensure_dyn_lds(reinterpret_cast<const void*>(k_dare<RL_>), lds);    \
-        if (e_ != hipSuccess) return e_;                                                          \
-        hipLaunchKernelGGL((k_dare<RL_>), dim3(wgs), dim3(64 * waves), lds, st, p);               \
-    } while (0)
+#define DARE_RL(RL_) return LAUNCH_WAVES((k_dare<RL_>), wgs, waves, lds, st, p)
     if (d <= 16) DARE_RL(16);
     else if (d <= 32) DARE_RL(32);
     else DARE_RL(64);
 #undef DARE_RL
-    return hipGetLastError();
 }
 
 // k_dare_vjp: the adjoint of P_i = DARE(A_i, B_i, Q, R), one wave per instance (csrc/almpc_dare_vjp.hip.h).  Launch only.
@@ -752,17 +743,11 @@ hipError_t launch_dare_vjp(DareVjpParams p, hipStream_t st) {
     const int waves = dare_waves(p.n, p.m), d = p.n > p.m ? p.n : p.m;
     const size_t lds = (size_t)waves * p.lds_per_wave * sizeof(double);
     const unsigned wgs = (unsigned)((p.batch + waves - 1) / waves);
-#define DARE_VJP_RL(RL_)                                                                              \
-    do {                                                                                              \
-        const hipError_t e_ = ensure_dyn_lds(reinterpret_cast<const void*>(k_dare_vjp<RL_>), lds);    \
-        if (e_ != hipSuccess) return e_;                                                              \
-        hipLaunchKernelGGL((k_dare_vjp<RL_>), dim3(wgs), dim3(64 * waves), lds, st, p);               \
-    } while (0)
+#define DARE_VJP_RL(RL_) return LAUNCH_WAVES((k_dare_vjp<RL_>), wgs, waves, lds, st, p)
     if (d <= 16) DARE_VJP_RL(16);
     else if (d <= 32) DARE_VJP_RL(32);
     else DARE_VJP_RL(64);
 #undef DARE_VJP_RL
-    return hipGetLastError();
 }
 
 // What k_dare cannot be given: a shape beyond its LDS layout, or an R that hm::dare refuses (singular), or R[1,1] == 0 -- the
@@ -827,17 +812,11 @@ hipError_t launch_c2d(C2dParams p, hipStream_t st) {
     const int waves = c2d_waves(p.n, p.m);
     const size_t lds = (size_t)p.lds_per_wave * sizeof(double) * waves;
     const int wgs = (p.batch + waves - 1) / waves;
-#define C2D_RL(RL_)                                                                              \
-    do {                                                                                         \
-        const hipError_t e_ = ensure_dyn_lds(reinterpret_cast<const void*>(k_c2d<RL_>), lds);    \
-        if (e_ != hipSuccess) return e_;                                                         \
-        hipLaunchKernelGGL((k_c2d<RL_>), dim3(wgs), dim3(64 * waves), lds, st, p);               \
-    } while (0)
+#define C2D_RL(RL_) return LAUNCH_WAVES((k_c2d<RL_>), wgs, waves, lds, st, p)
     if (p.n <= 16) C2D_RL(16);
     else if (p.n <= 32) C2D_RL(32);
     else C2D_RL(64);
 #undef C2D_RL
-    return hipGetLastError();
 }
 
 bool model_continuous(const almpc_handle* h) { return h->model_mode == ALMPC_MODEL_CONTINUOUS_ZOH; }
@@ -891,9 +870,8 @@ bool host_dare_of(const almpc_handle* h, hm::mat Am, hm::mat Bm, const hm::mat& 
     return hm::dare(Am, Bm, Qm, Rm, h->n, h->m, Pm);
 }
 
-// k_sgains over the handle's per-instance models (bA, bB; terminal weights bP, shared or per instance): all instances
-// (filter 0) or the ones the condensed step left unsolved (filter 1)
-hipError_t launch_sgains(almpc_handle* h, int filter, SolveMode mode = {}) {
+// k_sgains over the handle's per-instance models (bA, bB; terminal weights bP, shared or per instance): the instances of call.filter
+hipError_t launch_sgains(almpc_handle* h, SolveCall call = {}) {
     const almpc_handle::Sd& sd = h->sd;
     SgainsParams gp;
     std::memset(&gp, 0, sizeof(gp));
@@ -903,12 +881,10 @@ hipError_t launch_sgains(almpc_handle* h, int filter, SolveMode mode = {}) {
     gp.B = h->bB; gp.B_stride = n * m; gp.B_kstride = 0;
     gp.P = h->bP; gp.P_stride = h->rP_stride;   // (one matrix with stride 0, or one per instance)
     gp.Q = sd.dQ; gp.R = sd.dR; gp.S = sd.useS ? sd.dS : nullptr;
-    gp.c = nullptr; gp.c_stride = 0;
-    gp.filter = filter; gp.status = h->dStatus; gp.flag = nullptr;
+    gp.filter = call.filter; gp.status = h->dStatus;
     gp.rec = sd.rec; gp.rec_stride = sd.rec_stride;
-    gp.pc = nullptr; gp.ct = nullptr; gp.pc_stride = 0;
     gp.bad = sd.bad;
-    if (mode.gated) { gp.gate = h->redo.dGate; gp.gate_val = h->redo.step_serial; }
+    if (call.gated) { gp.gate = h->redo.dGate; gp.gate_val = h->redo.step_serial; }
     if (sd.sqp) {   // the QP of the current SQP iteration: stage models, defects, state errors and input gradient of the loop
         const almpc_handle::Sqp& q = h->sqp;
         const long N = h->N;
@@ -924,111 +900,122 @@ hipError_t launch_sgains(almpc_handle* h, int filter, SolveMode mode = {}) {
     if (!gp.A || !gp.B || !gp.P || !gp.rec) return hipErrorInvalidValue;
     gp.lds_per_wave = sgains_lds_doubles(sd.nt, h->m);
     const size_t per = (size_t)gp.lds_per_wave * sizeof(double);
-    int waves = SGAINS_WAVES;
-    while (waves > 1 && per * waves > 160 * 1024) --waves;
+    const int waves = waves_in_lds(per, SGAINS_WAVES);
     const size_t lds = per * waves;
-    int wgs = (h->batch + waves - 1) / waves;
-    const int cap = h->num_cus * 2;
-    if (wgs > cap) wgs = cap;
-    const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_sgains), lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sgains, dim3(wgs), dim3(64 * waves), lds, h->stream, gp);
-    return hipGetLastError();
+    const int wgs = capped_grid(h->batch, waves, h->num_cus * 2);
+    return LAUNCH_WAVES((k_sgains), wgs, waves, lds, h->stream, gp);
 }
 
+// Sinv of SD_WCAP4 rows fits LDS beside the trajectories (else: the global-scratch build)
+bool sdual_fits128(int NT, int MC, int N) { return (size_t)sdual_lds_doubles(NT, MC, N, SD_WCAP4, true) * sizeof(double) <= LDS_BUDGET; }
+
+struct SdualTiers { int first, last; };
+
 template <int NT, int MC>
-hipError_t launch_sdual_t(almpc_handle* h, SdualParams sp, int tier0, int tier1) {
+hipError_t launch_sdual_t(almpc_handle* h, SdualParams sp, SdualTiers tiers) {
     // tier 0: every (filtered) instance with room for SD_WCAP1 rows (several waves per workgroup); tier 1: the instances that outgrew it,
     // SD_WCAP2 rows; tier 2: SD_WCAP4 rows, two working-set positions per lane (mostly infeasible instances whose verdict needs that
     // many rows); tier 3: the same with Sinv in a global scratch, for shapes whose trajectories leave no room for it in LDS.
-    // (tier0 = tier1 = 1: ONE launch with room for SD_WCAP2 rows -- the redo of the few instances a condensed step left unsolved)
-    if (tier1 > tier0 && sp.wsave && !sp.build_ghat && !h->sw.sdual_no_sinv_handover) {   // tiers hand each other the inverse of their working set
+    // (first = last = 1: ONE launch with room for SD_WCAP2 rows -- the redo of the few instances a condensed step left unsolved)
+    if (tiers.last > tiers.first && sp.wsave && !h->sw.sdual_no_sinv_handover) {   // tiers hand each other the inverse of their working set
         const hipError_t e_ = h->sd.sinv_save.once((size_t)h->batch * sdual_sinv_doubles(SDUAL_SINV_SAVE));
         if (e_ != hipSuccess) return e_;
         sp.sinv_save = h->sd.sinv_save;
     }
     // the later tiers return at once unless an earlier one of THIS call ran out of room (it stores the call's number in the gate word):
     // their scan for flagged instances alone is 16 dependent loads per wave, 9 us of an idle launch on 4096 instances
-    if (sp.ovf && !sp.build_ghat) { sp.ovf_gate = sp.ovf + sp.batch; sp.ovf_gate_val = ++h->sd.tier_serial; }
-    for (int tier = tier0; tier <= tier1; ++tier) {
+    if (sp.ovf) { sp.ovf_gate = sp.ovf + sp.batch; sp.ovf_gate_val = ++h->sd.tier_serial; }
+    const bool fits128 = sdual_fits128(NT, MC, sp.N);
+    for (int tier = tiers.first; tier <= tiers.last; ++tier) {
         sp.wcap = tier == 0 ? SD_WCAP1 : (tier == 1 ? SD_WCAP2 : SD_WCAP4);
-        sp.only_ovf = tier > tier0;
-        bool glb = tier == 3;
-        const bool fits128 = (size_t)sdual_lds_doubles(NT, MC, sp.N, SD_WCAP4, true) * sizeof(double) <= 160 * 1024;
+        sp.only_ovf = tier > tiers.first;
+        const bool glb = tier == 3;
         if (tier == 2 && !fits128) continue;   // (Sinv of 128 rows does not fit beside the trajectories: the global-scratch build)
         if (tier == 3 && fits128) continue;
         sp.lds_per_wave = sdual_lds_doubles(NT, MC, sp.N, sp.wcap, !glb);
         const size_t per = (size_t)sp.lds_per_wave * sizeof(double);
-        int waves = SDUAL_WAVES;
-        while (waves > 1 && per * waves > 160 * 1024) --waves;
-        if (per * waves > 160 * 1024) return hipErrorInvalidValue;
-        if (tier >= 1) waves = 1;   // few instances: spread them over the compute units
+        const int waves = waves_in_lds(per, tier >= 1 ? 1 : SDUAL_WAVES);   // (the later tiers' few instances: spread over the compute units)
         const size_t lds = per * waves;
-        int per_cu = (int)((160 * 1024) / lds);
-        if (per_cu < 1) per_cu = 1;
-        if (per_cu * waves > 8) per_cu = 8 / waves > 0 ? 8 / waves : 1;
-        int wgs = (sp.batch + waves - 1) / waves;
-        int cap = h->num_cus * per_cu;
-        if (glb) cap = h->num_cus;
-        if (wgs > cap) wgs = cap;
-        hipError_t e;
+        if (lds > LDS_BUDGET) return hipErrorInvalidValue;
+        const int per_cu = std::max(1, std::min((int)(LDS_BUDGET / lds), 8 / waves));   // (at most 8 waves on a compute unit)
+        const int wgs = capped_grid(sp.batch, waves, glb ? h->num_cus : h->num_cus * per_cu);
         const size_t lds_gh = lds + (size_t)(NT + MC) * (sdual_rec_row(NT, MC) + 2) * sizeof(double);   // (+ the workgroup's copy of a stage-invariant record, rows padded)
         // cached responses: the build whose sweeps fetch their records stage by stage and whose column stream runs four times deeper (see k_sdual)
-        const bool gh = sp.ghat != nullptr && lds_gh <= 160 * 1024 && !h->sw.sdual_no_gh;
-        if (tier < 2) {
-            const void* kf = gh ? reinterpret_cast<const void*>(k_sdual<NT, MC, 1, false, true>) : reinterpret_cast<const void*>(k_sdual<NT, MC, 1, false, false>);
-            e = ensure_dyn_lds(kf, gh ? lds_gh : lds);
-            if (e != hipSuccess) return e;
-            if (gh) hipLaunchKernelGGL((k_sdual<NT, MC, 1, false, true>), dim3(wgs), dim3(64 * waves), lds_gh, h->stream, sp);
-            else hipLaunchKernelGGL((k_sdual<NT, MC, 1, false, false>), dim3(wgs), dim3(64 * waves), lds, h->stream, sp);
-        } else if (!glb) {
-            const void* kf = gh ? reinterpret_cast<const void*>(k_sdual<NT, MC, 2, false, true>) : reinterpret_cast<const void*>(k_sdual<NT, MC, 2, false, false>);
-            e = ensure_dyn_lds(kf, gh ? lds_gh : lds);
-            if (e != hipSuccess) return e;
-            if (gh) hipLaunchKernelGGL((k_sdual<NT, MC, 2, false, true>), dim3(wgs), dim3(64 * waves), lds_gh, h->stream, sp);
-            else hipLaunchKernelGGL((k_sdual<NT, MC, 2, false, false>), dim3(wgs), dim3(64 * waves), lds, h->stream, sp);
-        } else {
+        const bool gh = sp.ghat != nullptr && lds_gh <= LDS_BUDGET && !h->sw.sdual_no_gh;
+        hipError_t e;
+        if (tier < 2)
+            e = gh ? LAUNCH_WAVES((k_sdual<NT, MC, 1, false, true>), wgs, waves, lds_gh, h->stream, sp) : LAUNCH_WAVES((k_sdual<NT, MC, 1, false, false>), wgs, waves, lds, h->stream, sp);
+        else if (!glb)
+            e = gh ? LAUNCH_WAVES((k_sdual<NT, MC, 2, false, true>), wgs, waves, lds_gh, h->stream, sp) : LAUNCH_WAVES((k_sdual<NT, MC, 2, false, false>), wgs, waves, lds, h->stream, sp);
+        else {
             sp.ghat = nullptr;   // (the global-scratch build has no cached-response variant: sweeps)
-            e = h->sd.sinv_glb.grow((size_t)wgs * waves * sdual_sinv_doubles(SD_WCAP4));
-            if (e != hipSuccess) return e;
+            if ((e = h->sd.sinv_glb.grow((size_t)wgs * waves * sdual_sinv_doubles(SD_WCAP4))) != hipSuccess) return e;
             sp.sinv_glb = h->sd.sinv_glb;
-            e = ensure_dyn_lds(reinterpret_cast<const void*>(k_sdual<NT, MC, 2, true>), lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_sdual<NT, MC, 2, true>), dim3(wgs), dim3(64 * waves), lds, h->stream, sp);
+            e = LAUNCH_WAVES((k_sdual<NT, MC, 2, true>), wgs, waves, lds, h->stream, sp);
         }
-        e = hipGetLastError();
         if (e != hipSuccess) return e;
         sp.filter = 0;   // the later tiers select by the overflow flag alone (the first one has rewritten the statuses)
     }
     return hipSuccess;
 }
 
-// k_sdual over the batch (filter 0), over the instances whose status is not 0 (filter 1: redo after the condensed path), start from
-// `guess` (inputs [batch][N][m]) when given
-hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int max_iter, bool single_launch, int first_tier, SolveMode mode,
-                        RowMultOut rmult) {
-    if (!h->sd.ready) return hipErrorInvalidValue;
-    if (h->sd.ghat_wanted && !h->sd.ghat_ready && !mode.build_ghat && !h->sd.per_instance && !h->sd.sqp) {   // first use on a condensed handle
-        const hipError_t eb = sdual_build_ghat(h);
-        if (eb != hipSuccess) return eb;
-    }
+hipError_t launch_sdual_shape(almpc_handle* h, const SdualParams& sp, SdualTiers tiers) {
+#define SD_CASE(NT_, MC_) if (h->sd.NT == NT_ && h->sd.MC == MC_) return launch_sdual_t<NT_, MC_>(h, sp, tiers)
+    SD_CASE(2, 2); SD_CASE(4, 2); SD_CASE(6, 2); SD_CASE(8, 4); SD_CASE(12, 4); SD_CASE(16, 4); SD_CASE(16, 8); SD_CASE(32, 16); SD_CASE(48, 16);
+#undef SD_CASE
+    return hipErrorInvalidValue;
+}
+
+// SdualParams of the handle's design, zero but for what the design fixes: shape, stage records, state box, the solver's own cap
+SdualParams sdual_design_params(const almpc_handle* h) {
     const almpc_handle::Sd& sd = h->sd;
     SdualParams sp;
     std::memset(&sp, 0, sizeof(sp));
-    sp.n = h->n; sp.nt = sd.nt; sp.m = h->m; sp.N = h->N; sp.batch = h->batch;
+    sp.n = h->n; sp.nt = sd.nt; sp.m = h->m; sp.N = h->N;
     sp.rec = sd.rec; sp.rec_stride = sd.rec_stride; sp.rec_kstride = sd.rec_kstride;
-    sp.base = sd.has_base ? sd.base : nullptr; sp.base_stride = sd.base_stride;
-    sp.pc = nullptr; sp.ct = nullptr; sp.pc_stride = 0;
-    sp.umin = h->dUmin; sp.umax = h->dUmax; sp.uref = h->dUref; sp.uref_stride = h->uref_stride;
     sp.xmin = sd.has_box ? sd.xmin : nullptr; sp.xmax = sd.has_box ? sd.xmax : nullptr;
+    sp.rows_state = (sd.has_box || sd.has_eq) ? 1 : 0;
+    sp.max_iter = 20 * (h->N * h->m + (sp.rows_state ? h->N * h->n : 0)) + 50;
+    sp.tol = 1e-9;
+    return sp;
+}
+
+// Cached responses of a shared model: every coordinate that can be a row, one sweep each, once (k_sdual's build mode on
+// min(TP, 2048) waves), TP x TP doubles.  Memory cap 256 MB per handle (TP <= 5792: e.g. the quadrotor with S up to N = 361); above it
+// the table is not built and a working-set change costs two sweeps again (SdualParams::ghat == null).  Enqueued on the handle's stream.
+// A launcher of its own with no SolveCall: the build is never gated, never screened and never started from a working set.
+hipError_t sdual_build_ghat(almpc_handle* h) {
+    almpc_handle::Sd& sd = h->sd;
+    sd.ghat_wanted = false;   // (one attempt per design)
+    const size_t TP = (size_t)sdual_tp(sd.NT, sd.MC, h->N);
+    if (TP * TP * sizeof(double) > ((size_t)256 << 20)) return hipSuccess;
+    hipError_t e;
+    if ((e = sd.ghat.grow(TP * TP)) != hipSuccess || (e = hipMemsetAsync(sd.ghat, 0, TP * TP * sizeof(double), h->stream)) != hipSuccess) return e;
+    SdualParams sp = sdual_design_params(h);   // + what else the build reads: the waves walk the coordinates, no instance data
+    sp.batch = TP < 2048 ? (int)TP : 2048;
+    sp.umin = sd.rec; sp.umax = sd.rec; sp.uref = sd.rec;   // (read into the bound tables, not used: the handle's own arrays may not exist yet)
+    sp.eqt = sd.has_eq ? sd.rec : nullptr;   // (has_eq decides which coordinates can be rows; the target values are not used)
+    sp.x0_stride = h->n; sp.base_stride = sd.base_stride;   // (not read without x0 and base: as every launch before had them)
+    sp.build_ghat = 1; sp.ghat_out = sd.ghat;
+    e = launch_sdual_shape(h, sp, {0, 0});   // (one launch, SD_WCAP1 rows of LDS: the build holds no working set)
+    sd.ghat_ready = e == hipSuccess;
+    return e;
+}
+
+// SdualParams of a solve: the handle's problem, the call's selection and start, and over them the QP of the current SQP iteration
+SdualParams sdual_solve_params(const almpc_handle* h, const SolveCall& call) {
+    const almpc_handle::Sd& sd = h->sd;
+    SdualParams sp = sdual_design_params(h);
+    sp.batch = h->batch;
+    sp.base = sd.has_base ? sd.base : nullptr; sp.base_stride = sd.base_stride;
+    sp.umin = h->dUmin; sp.umax = h->dUmax; sp.uref = h->dUref; sp.uref_stride = h->uref_stride;
     sp.xbref = h->dXref; sp.xbref_stride = h->xref_stride;
-    // x_N = x_ref_N (no references yet: the design-time build of the cached responses, which sets its own below)
-    sp.eqt = sd.has_eq && h->dXref ? h->dXref + (size_t)h->N * h->n : nullptr; sp.eqt_stride = h->xref_stride;
+    sp.eqt = sd.has_eq && h->dXref ? h->dXref + (size_t)h->N * h->n : nullptr; sp.eqt_stride = h->xref_stride;   // x_N = x_ref_N
     sp.x0 = h->dX0; sp.x0_stride = h->n; sp.xref = h->dXref; sp.xref_stride = h->xref_stride;
-    if (mode.x0_from_results) { sp.x0 = h->dX; sp.x0_stride = (long)h->n * (h->N + 1); }
-    if (mode.gated) { sp.gate = h->redo.dGate; sp.gate_val = h->redo.step_serial; }
-    sp.uguess = guess; sp.filter = filter; sp.flag = nullptr; sp.v_only = 0;
-    if (filter == 1 && sd.start_ws && sd.start_ws_fresh && !sd.sqp) sp.start_ws = sd.start_ws;   // (the redo behind a state-row finish)
+    if (call.x0_from_results) { sp.x0 = h->dX; sp.x0_stride = (long)h->n * (h->N + 1); }
+    if (call.gated) { sp.gate = h->redo.dGate; sp.gate_val = h->redo.step_serial; }
+    sp.uguess = call.guess; sp.filter = call.filter;
+    if (call.filter == FILTER_UNSOLVED && sd.start_ws && sd.start_ws_fresh && !sd.sqp) sp.start_ws = sd.start_ws;   // (the redo behind a state-row finish)
     sp.x = h->dX; sp.ex = h->dEx; sp.u = h->dU; sp.eu = h->dEu; sp.status = h->dStatus; sp.piters = h->dPiters;
     if (sd.sqp) {   // dx_0 = 0, variable v = u - ubar (the handle's per-instance references ARE the iterate xbar, ubar), cost terms per instance
         const almpc_handle::Sqp& q = h->sqp;
@@ -1037,96 +1024,95 @@ hipError_t launch_sdual(almpc_handle* h, int filter, const double* guess, int ma
         sp.eqt = sd.has_eq ? q.xref + (size_t)h->N * h->n : nullptr; sp.eqt_stride = 0;
         sp.x0 = nullptr; sp.xref = nullptr; sp.xref_stride = 0;
         sp.flag = h->bFlag; sp.v_only = 1;
-        sp.rows = rmult;
+        sp.rows = call.rows;
     }
-    sp.ovf = sd.ovf; sp.only_ovf = 0; sp.wsave = sd.wsave;
+    sp.ovf = sd.ovf; sp.wsave = sd.wsave;
     sp.gbad = sd.per_instance ? sd.bad : nullptr;
     sp.ghat = (sd.ghat_ready && !sd.per_instance && !sd.sqp && sd.rec_stride == 0) ? sd.ghat : nullptr;
-    if (mode.build_ghat) {   // design time: the waves walk the coordinates (no instance data is read)
-        const int TP = sdual_tp(sd.NT, sd.MC, h->N);
-        sp.build_ghat = 1; sp.ghat_out = sd.ghat; sp.ghat = nullptr;
-        sp.batch = TP < 2048 ? TP : 2048;
-        sp.uref_stride = 0; sp.xbref = nullptr; sp.xbref_stride = 0; sp.x0 = nullptr; sp.xref = nullptr; sp.xref_stride = 0;
-        sp.eqt = sd.has_eq ? sd.rec : nullptr; sp.eqt_stride = 0;   // (has_eq decides which coordinates can be rows; the target values are not used)
-        sp.umin = sd.rec; sp.umax = sd.rec; sp.uref = sd.rec;       // (read into the bound tables, not used: the handle's own arrays may not exist yet)
-        sp.x = sp.ex = sp.u = sp.eu = nullptr; sp.status = nullptr; sp.piters = nullptr;
-        sp.base = nullptr; sp.pc = nullptr; sp.ct = nullptr; sp.uguess = nullptr; sp.filter = 0; sp.flag = nullptr;
-        sp.ovf = nullptr; sp.wsave = nullptr; sp.gbad = nullptr;
-        single_launch = false; first_tier = 0;
+    if (call.max_iter > 0) sp.max_iter = call.max_iter;
+    return sp;
+}
+
+// State box of a shared model with shared references, every instance solved from scratch: the reachability screen in front of the
+// solve (one table kernel per design / reference change, one small launch per solve) -- instances it certifies infeasible never reach
+// a sweep.  The verdicts [batch], or null: no screen for this call (or *err).
+const int32_t* launch_sdual_screen(almpc_handle* h, const SolveCall& call, const double* x0, long x0_stride, hipError_t* err) {
+    almpc_handle::Sd& sd = h->sd;
+    if (!sd.has_box || sd.per_instance || sd.sqp || call.filter != FILTER_ALL || call.first_tier != 0 || !x0 || h->uref_stride != 0 ||
+        h->xref_stride != 0 || !h->dA || !h->dB || h->sw.sdual_no_screen) return nullptr;
+    const size_t n = (size_t)h->n, m = (size_t)h->m, N = (size_t)h->N;
+    hipError_t& e = *err;
+    if (sd.scr_phi.size() < N * n * n || sd.scr_g.size() < N * n * m || sd.scr_rm.size() < N * n || sd.scr_rp.size() < N * n)
+        sd.scr_ready = false;   // (a table is made or replaced below)
+    if ((e = sd.scr_phi.grow(N * n * n)) != hipSuccess || (e = sd.scr_g.grow(N * n * m)) != hipSuccess ||
+        (e = sd.scr_rm.grow(N * n)) != hipSuccess || (e = sd.scr_rp.grow(N * n)) != hipSuccess ||
+        (e = sd.scr_verdict.once((size_t)h->batch)) != hipSuccess) return nullptr;
+    ScreenParams cp;
+    cp.n = h->n; cp.m = h->m; cp.N = h->N; cp.batch = h->batch;
+    cp.A = h->dA; cp.B = h->dB; cp.umin = h->dUmin; cp.umax = h->dUmax; cp.uref = h->dUref;
+    cp.xmin = sd.xmin; cp.xmax = sd.xmax; cp.xref = h->dXref; cp.x0 = x0; cp.x0_stride = x0_stride;
+    cp.phi = sd.scr_phi; cp.gtab = sd.scr_g; cp.rm = sd.scr_rm; cp.rp = sd.scr_rp; cp.verdict = sd.scr_verdict;
+    if (!sd.scr_ready) {
+        hipLaunchKernelGGL(k_screen_tables, dim3(1), dim3(256), 0, h->stream, cp);
+        if ((e = hipGetLastError()) != hipSuccess) return nullptr;
+        sd.scr_ready = true;
     }
-    sp.rows_state = (sd.has_box || sd.has_eq) ? 1 : 0;
-    // state box of a shared model with shared references, every instance solved from scratch: the reachability screen first (one
-    // table kernel per design / reference change, one small launch per solve) -- instances it certifies infeasible never reach a sweep
-    if (sd.has_box && !mode.build_ghat && !sd.per_instance && !sd.sqp && filter == 0 && first_tier == 0 && sp.x0 && h->uref_stride == 0 &&
-        h->xref_stride == 0 && h->dA && h->dB && !h->sw.sdual_no_screen) {
-        almpc_handle::Sd& sdw = h->sd;
-        const size_t n_ = (size_t)h->n, m_ = (size_t)h->m, N_ = (size_t)h->N;
-        hipError_t e;
-        if (sdw.scr_phi.size() < N_ * n_ * n_ || sdw.scr_g.size() < N_ * n_ * m_ || sdw.scr_rm.size() < N_ * n_ || sdw.scr_rp.size() < N_ * n_)
-            sdw.scr_ready = false;   // (a table is made or replaced below)
-        if ((e = sdw.scr_phi.grow(N_ * n_ * n_)) != hipSuccess || (e = sdw.scr_g.grow(N_ * n_ * m_)) != hipSuccess ||
-            (e = sdw.scr_rm.grow(N_ * n_)) != hipSuccess || (e = sdw.scr_rp.grow(N_ * n_)) != hipSuccess ||
-            (e = sdw.scr_verdict.once((size_t)h->batch)) != hipSuccess) return e;
-        ScreenParams cp;
-        cp.n = h->n; cp.m = h->m; cp.N = h->N; cp.batch = h->batch;
-        cp.A = h->dA; cp.B = h->dB; cp.umin = h->dUmin; cp.umax = h->dUmax; cp.uref = h->dUref;
-        cp.xmin = sd.xmin; cp.xmax = sd.xmax; cp.xref = h->dXref; cp.x0 = sp.x0; cp.x0_stride = sp.x0_stride;
-        cp.phi = sdw.scr_phi; cp.gtab = sdw.scr_g; cp.rm = sdw.scr_rm; cp.rp = sdw.scr_rp; cp.verdict = sdw.scr_verdict;
-        if (!sdw.scr_ready) {
-            hipLaunchKernelGGL(k_screen_tables, dim3(1), dim3(256), 0, h->stream, cp);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            sdw.scr_ready = true;
-        }
-        if ((e = hipMemsetAsync(sdw.scr_verdict, 0, (size_t)h->batch * sizeof(int32_t), h->stream)) != hipSuccess) return e;
-        const dim3 sg((unsigned)((h->batch + 63) / 64), (unsigned)h->N);
+    if ((e = hipMemsetAsync(sd.scr_verdict, 0, (size_t)h->batch * sizeof(int32_t), h->stream)) != hipSuccess) return nullptr;
+    const dim3 sg((unsigned)((h->batch + 63) / 64), (unsigned)h->N);
 #define SCR_CASE(NT_) if (h->n <= NT_) hipLaunchKernelGGL((k_state_box_screen<NT_>), sg, dim3(64), 0, h->stream, cp)
-        SCR_CASE(4); else SCR_CASE(8); else SCR_CASE(12); else SCR_CASE(16); else SCR_CASE(32); else SCR_CASE(48); else return hipErrorInvalidValue;
+    SCR_CASE(4); else SCR_CASE(8); else SCR_CASE(12); else SCR_CASE(16); else SCR_CASE(32); else SCR_CASE(48); else e = hipErrorInvalidValue;
 #undef SCR_CASE
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        sp.screen = sdw.scr_verdict;
-    }
-    const int rows = h->N * h->m + ((sd.has_box || sd.has_eq) ? h->N * h->n : 0);
-    sp.max_iter = max_iter > 0 ? max_iter : 20 * rows + 50;
-    sp.tol = 1e-9;
-    // single launch (the redo behind a condensed step: few instances, occupancy does not matter): the 128-row build when its Sinv fits
-    // LDS beside the trajectories, else the 64-row one.  first_tier 1: starts that are known to hold many rows
-    int tier0 = first_tier, tier1 = 3;
-    if (mode.build_ghat) tier1 = 0;
-    if (single_launch) {
-        int NT_ = sd.NT, MC_ = sd.MC;
-        const bool fits128 = (size_t)sdual_lds_doubles(NT_, MC_, h->N, SD_WCAP4, true) * sizeof(double) <= 160 * 1024;
-        // (round 5: the 64-row build first -- one working-set position per lane: its Sinv products, borderings and column streams are
-        // cheaper per change than the 128-row build's -- and the 128-row build only for what outgrows it, which costs little since the
-        // tiers hand over their inverse; ALMPC_SDUAL_REDO_128=1: the one 128-row launch of round 4)
-        tier0 = (fits128 && (h->sw.sdual_redo_128 || (mode.gated && !mode.predicted))) ? 2 : 1;   // (a gated redo that is not expected to have work: one launch)
-        tier1 = fits128 ? 2 : 1;
-    }
-    // the redo's start (the finish's working set + the terminal-equality rows) with its inverse, built in registers from the cached
-    // responses before the solve: k_sdual_start (csrc/almpc_sdual.hip.h)
-    if (sp.start_ws && sp.ghat && tier0 >= 1 && !h->sw.sdual_no_start_build) {
-        almpc_handle::Sd& sdw = h->sd;
-        const hipError_t ea = sdw.start_inv.once((size_t)h->batch * sdual_sinv_doubles(SDUAL_SINV_SAVE));
-        if (ea != hipSuccess) return ea;
-        SdualStartParams tp;
-        std::memset(&tp, 0, sizeof(tp));
-        tp.batch = h->batch; tp.n = h->n; tp.N = h->N; tp.SP = sd.NT + sd.MC; tp.TP = sdual_tp(sd.NT, sd.MC, h->N);
-        // (the list is built for the LARGEST tier of this call: the first tier installs it if it leaves room to work, else hands it on)
-        tp.wcap = (tier0 == 1 && tier1 < 2) ? SD_WCAP2 : SD_WCAP4; tp.has_eq = sd.has_eq ? 1 : 0;
-        tp.status = h->dStatus; tp.gate = sp.gate; tp.gate_val = sp.gate_val;
-        tp.ghat = sp.ghat; tp.start_ws = sdw.start_ws; tp.start_inv = sdw.start_inv;
-        // (one workgroup per instance at a time; a workgroup looks at up to 64 SDUAL_START_WAVES instances)
-        int wgs = h->batch < h->num_cus * 4 ? h->batch : h->num_cus * 4;
-        const int wmin = (h->batch + 64 * SDUAL_START_WAVES - 1) / (64 * SDUAL_START_WAVES);
-        if (wgs < wmin) wgs = wmin;
-        hipLaunchKernelGGL(k_sdual_start, dim3(wgs), dim3(64 * SDUAL_START_WAVES), 0, h->stream, tp);
-        const hipError_t e_ = hipGetLastError();
-        if (e_ != hipSuccess) return e_;
-        sp.start_inv = sdw.start_inv;
-    }
-#define SD_CASE(NT_, MC_) if (sd.NT == NT_ && sd.MC == MC_) return launch_sdual_t<NT_, MC_>(h, sp, tier0, tier1)
-    SD_CASE(2, 2); SD_CASE(4, 2); SD_CASE(6, 2); SD_CASE(8, 4); SD_CASE(12, 4); SD_CASE(16, 4); SD_CASE(16, 8); SD_CASE(32, 16); SD_CASE(48, 16);
-#undef SD_CASE
-    return hipErrorInvalidValue;
+    if (e == hipSuccess) e = hipGetLastError();
+    return e == hipSuccess ? sd.scr_verdict.get() : nullptr;
+}
+
+// Which tiers of launch_sdual_t a solve runs.  The tiers from call.first_tier on (1: starts that are known to hold many rows), or
+// for call.single_launch (the redo behind a condensed step: few instances, occupancy does not matter): the 128-row build when its
+// Sinv fits LDS beside the trajectories, else the 64-row one.
+SdualTiers sdual_tiers(const SolveCall& call, bool fits128, const Switches& sw) {
+    if (!call.single_launch) return {call.first_tier, 3};
+    // (round 5: the 64-row build first -- one working-set position per lane: its Sinv products, borderings and column streams are
+    // cheaper per change than the 128-row build's -- and the 128-row build only for what outgrows it, which costs little since the
+    // tiers hand over their inverse; ALMPC_SDUAL_REDO_128=1: the one 128-row launch of round 4)
+    const bool one_launch = sw.sdual_redo_128 || (call.gated && !call.predicted);   // (a gated redo that is not expected to have work: one launch)
+    return {fits128 && one_launch ? 2 : 1, fits128 ? 2 : 1};
+}
+
+// The redo's start (the finish's working set + the terminal-equality rows) with its inverse, built in registers from the cached
+// responses before the solve: k_sdual_start (csrc/almpc_sdual.hip.h).  Sets sp.start_inv when it ran.
+hipError_t launch_sdual_start(almpc_handle* h, SdualParams& sp, SdualTiers tiers) {
+    almpc_handle::Sd& sd = h->sd;
+    if (!sp.start_ws || !sp.ghat || tiers.first < 1 || h->sw.sdual_no_start_build) return hipSuccess;
+    const hipError_t ea = sd.start_inv.once((size_t)h->batch * sdual_sinv_doubles(SDUAL_SINV_SAVE));
+    if (ea != hipSuccess) return ea;
+    SdualStartParams tp;
+    std::memset(&tp, 0, sizeof(tp));
+    tp.batch = h->batch; tp.n = h->n; tp.N = h->N; tp.SP = sd.NT + sd.MC; tp.TP = sdual_tp(sd.NT, sd.MC, h->N);
+    // (the list is built for the LARGEST tier of this call: the first tier installs it if it leaves room to work, else hands it on)
+    tp.wcap = (tiers.first == 1 && tiers.last < 2) ? SD_WCAP2 : SD_WCAP4; tp.has_eq = sd.has_eq ? 1 : 0;
+    tp.status = h->dStatus; tp.gate = sp.gate; tp.gate_val = sp.gate_val;
+    tp.ghat = sp.ghat; tp.start_ws = sd.start_ws; tp.start_inv = sd.start_inv;
+    // (one workgroup per instance at a time; a workgroup looks at up to 64 SDUAL_START_WAVES instances)
+    const int wmin = (h->batch + 64 * SDUAL_START_WAVES - 1) / (64 * SDUAL_START_WAVES);
+    const int wgs = std::max(std::min(h->batch, h->num_cus * 4), wmin);
+    hipLaunchKernelGGL(k_sdual_start, dim3(wgs), dim3(64 * SDUAL_START_WAVES), 0, h->stream, tp);
+    sp.start_inv = sd.start_inv;
+    return hipGetLastError();
+}
+
+// k_sdual over the instances of call.filter, start = call.guess: the cached responses at the first use on a condensed handle, the
+// reachability screen, the redo's start, then the tiers of the handle's (NT, MC)
+hipError_t launch_sdual(almpc_handle* h, SolveCall call) {
+    almpc_handle::Sd& sd = h->sd;
+    if (!sd.ready) return hipErrorInvalidValue;
+    hipError_t e = hipSuccess;
+    if (sd.ghat_wanted && !sd.ghat_ready && !sd.per_instance && !sd.sqp && (e = sdual_build_ghat(h)) != hipSuccess) return e;
+    SdualParams sp = sdual_solve_params(h, call);
+    sp.screen = launch_sdual_screen(h, call, sp.x0, sp.x0_stride, &e);
+    if (e != hipSuccess) return e;
+    const SdualTiers tiers = sdual_tiers(call, sdual_fits128(sd.NT, sd.MC, h->N), h->sw);
+    if ((e = launch_sdual_start(h, sp, tiers)) != hipSuccess) return e;
+    return launch_sdual_shape(h, sp, tiers);
 }
 
 // Wait for the handle's stream: poll for a while before the blocking wait, whose wake-up (interrupt + scheduler) costs 0.1 - 15 ms on
@@ -1141,6 +1127,25 @@ hipError_t stream_wait_polling(almpc_handle* h) {
     return hipStreamSynchronize(h->stream);
 }
 
+// The primal Riccati active set can redo this design: an input box alone, no input-rate weight, riccati_weights() done
+bool primal_redo_ready(const almpc_handle* h) { return h->mc == 0 && !h->useS && h->rKst; }
+
+// The redo of the instances a condensed step left undecided, from the step's own result: k_sdual (behind k_sgains for per-instance
+// models, whose last step's models are still in the model slots) and / or k_riccati, as the caller says and the design allows.
+//   caller               dual   primal           why
+//   resolve_lazy_redo    yes    yes, behind it   the primal method takes what the dual one left without a certificate
+//   enqueue_gated_redo   else   if ready         ONE of the two: an empty gated launch still costs 3 - 4 us of stream time
+//   step_redo (eager)    yes    yes, behind it   as the lazy look; ALMPC_DBG_NO_SDUAL_FB / ALMPC_DBG_NO_PRIMAL_NET take one out
+int launch_redo(almpc_handle* h, SolveCall call, bool dual, bool primal) {
+    call.filter = FILTER_UNSOLVED; call.guess = h->dU; call.single_launch = true;
+    if (dual && h->sd.ready) {
+        if (h->sd.per_instance) HIP_TRY(h, launch_sgains(h, call));
+        HIP_TRY(h, launch_sdual(h, call));
+    }
+    if (primal && primal_redo_ready(h)) HIP_TRY(h, launch_riccati(h, call));
+    return ALMPC_OK;
+}
+
 // Lazy redo (see almpc_handle::Redo): called where the host is about to look at results and the stream is idle.  If the finish of
 // a step since the last look left instances unsolved, the stage-wise solvers redo them now (from the step's own result).
 int resolve_lazy_redo(almpc_handle* h) {
@@ -1152,13 +1157,8 @@ int resolve_lazy_redo(almpc_handle* h) {
     r.expected = cur != r.unsolved_seen;
     if (cur == r.unsolved_seen) return ALMPC_OK;
     r.unsolved_seen = cur;
-    SolveMode mode;
-    mode.x0_from_results = true;
-    if (h->sd.ready) {
-        if (h->sd.per_instance) HIP_TRY(h, launch_sgains(h, 1, mode));   // (the last step's models are still in the model slots)
-        HIP_TRY(h, launch_sdual(h, 1, h->dU, 0, true, 0, mode));
-    }
-    if (h->mc == 0 && !h->useS && h->rKst) HIP_TRY(h, launch_riccati(h, 1, h->dU, 0, mode));
+    SolveCall deferred; deferred.x0_from_results = true;
+    ALMPC_TRY(launch_redo(h, deferred, true, true));
     HIP_TRY(h, stream_wait_polling(h));   // (a redo is 0.1 - 0.4 ms of kernels: the blocking wait's wake-up alone was seen to double that)
     return ALMPC_OK;
 }
@@ -1167,17 +1167,12 @@ int resolve_lazy_redo(almpc_handle* h) {
 // results are about to be consumed without a synchronous call; does nothing unless a lazily deferred redo is pending.
 int enqueue_gated_redo(almpc_handle* h, bool predicted = false) {
     if (!h->redo.lazy_pending || !h->redo.dGate || h->sw.no_gated_redo) return ALMPC_OK;
-    SolveMode mode;
-    mode.x0_from_results = true; mode.gated = true; mode.predicted = predicted;
-    // As few launches as possible: an empty gated launch still costs 3 - 4 us of stream time on a 60 us step.  An input box alone
-    // (no state rows, no S): the primal Riccati active set by itself -- it is the solver that needs no certificate from another one
-    // (slower per instance than the dual method, but what it gets here is rare) --, ONE launch.  Otherwise the dual method's
-    // 128-row build in one launch (+ the stage records of per-instance models).
-    if (h->mc == 0 && !h->useS && h->rKst) HIP_TRY(h, launch_riccati(h, 1, h->dU, 0, mode));
-    else if (h->sd.ready) {
-        if (h->sd.per_instance) HIP_TRY(h, launch_sgains(h, 1, mode));
-        HIP_TRY(h, launch_sdual(h, 1, h->dU, 0, true, 0, mode));
-    }
+    SolveCall gated; gated.x0_from_results = true; gated.gated = true; gated.predicted = predicted;
+    // As few launches as possible.  An input box alone (no state rows, no S): the primal Riccati active set by itself -- it is the
+    // solver that needs no certificate from another one (slower per instance than the dual method, but what it gets here is rare) --,
+    // ONE launch.  Otherwise the dual method's 128-row build in one launch (+ the stage records of per-instance models).
+    const bool primal = primal_redo_ready(h);
+    ALMPC_TRY(launch_redo(h, gated, !primal, primal));
     h->redo.lazy_pending = false;   // (this step is settled on the stream; a later synchronous look has nothing left to do for it)
     return ALMPC_OK;
 }
@@ -2024,7 +2019,7 @@ int design_batched_structured(almpc_handle* h, const double* A_batch, const doub
     // (one stage of records per instance when the terminal weight is the instance's own DARE solution)
     ALMPC_TRY(setup_structured_solvers(h, nullptr, P == nullptr && !useS, Qm, Rm, useS ? &Sm : nullptr, box));
     if (h->sd.ready) {
-        HIP_TRY(h, launch_sgains(h, 0));
+        HIP_TRY(h, launch_sgains(h));   // (every instance)
         std::vector<int> bad(b, 0);
         HIP_TRY(h, hipMemcpyAsync(bad.data(), h->sd.bad, b * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2687,12 +2682,15 @@ int step_structured(almpc_handle* h, const almpc_opts& o) {
         HIP_TRY(h, hipGetLastError());
         guess = h->rGuess;
     }
+    SolveCall solve, net;
+    solve.guess = guess; solve.max_iter = o.polish_max_iter;
+    net.filter = FILTER_UNSOLVED; net.guess = h->dU;
     if (h->sd.ready) {
-        HIP_TRY(h, launch_sdual(h, 0, guess, o.polish_max_iter));
+        HIP_TRY(h, launch_sdual(h, solve));
         // safety net (input box only, S = 0): what the dual method left without a certificate goes to the primal Riccati active set
-        if (!h->sd.has_box && !h->sd.has_eq && !h->sd.useS && h->rKst) HIP_TRY(h, launch_riccati(h, 1, h->dU, 0));
+        if (!h->sd.has_box && !h->sd.has_eq && !h->sd.useS && h->rKst) HIP_TRY(h, launch_riccati(h, net));
     } else
-        HIP_TRY(h, launch_riccati(h, 0, guess, o.polish_max_iter));
+        HIP_TRY(h, launch_riccati(h, solve));
     h->r_has_step = true;
     return ALMPC_OK;
 }
@@ -2707,12 +2705,7 @@ int step_redo(Step& s) {
         return ALMPC_OK;
     }
     if (!h->fallback || h->ltv || !s.o.polish) return ALMPC_OK;
-    if (h->sd.ready && !h->sw.dbg_no_sdual_fb) {
-        if (h->sd.per_instance) HIP_TRY(h, launch_sgains(h, 1));   // (stage records of the unsolved instances only, from the models of this step)
-        HIP_TRY(h, launch_sdual(h, 1, h->dU, 0, true));
-    }
-    if (h->mc == 0 && !h->useS && h->rKst && !h->sw.dbg_no_primal_net) HIP_TRY(h, launch_riccati(h, 1, h->dU, 0));
-    return ALMPC_OK;
+    return launch_redo(h, SolveCall(), !h->sw.dbg_no_sdual_fb, !h->sw.dbg_no_primal_net);   // (right behind the step: its x0 is still the handle's)
 }
 
 // The pinned count and the gate word of the redo (almpc_handle::Redo): at the first step that defers its redo
@@ -3055,7 +3048,7 @@ int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
         if (timing) HIP_TRY(h, hipEventRecord(q.ev[1], st));
         if (h->c_step) HIP_TRY(h, launch_model_c2d(h, true));   // the network is x' = net(x, u): its Jacobians are continuous-time
         if (h->t_step) HIP_TRY(h, launch_relin_dare(h, h->sd.dQ, h->sd.dR));   // every instance's own terminal weight, in front of its records
-        HIP_TRY(h, launch_sgains(h, 0));
+        HIP_TRY(h, launch_sgains(h));   // (every instance)
         if (timing) HIP_TRY(h, hipEventRecord(q.ev[2], st));
         h->designed = true;
         almpc_opts o2;
@@ -3576,11 +3569,15 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
             // input box without S: the primal Riccati active set (an iterate of this loop has about half of its inputs on a bound: rows a
             // primal method holds at no cost, while the dual one pays a sweep per row of its start -- measured 0.56 against 3.1 ms per
             // iteration at the configs[4] shape); with state rows / S: k_sgains + k_sdual
-            if (h->mc == 0 && !q.useS && h->rKst)
-                HIP_TRY(h, launch_riccati(h, 3, h->dUref, opts ? opts->polish_max_iter : 0));
-            else if (h->sd.ready) {
-                HIP_TRY(h, launch_sgains(h, 0));
-                HIP_TRY(h, launch_sdual(h, 0, h->dUref, opts ? opts->polish_max_iter : 0, false, h->nz > 48 ? 1 : 0));
+            SolveCall qp;
+            qp.guess = h->dUref; qp.max_iter = opts ? opts->polish_max_iter : 0;
+            if (h->mc == 0 && !q.useS && h->rKst) {
+                qp.filter = FILTER_SQP_ALL;
+                HIP_TRY(h, launch_riccati(h, qp));
+            } else if (h->sd.ready) {
+                qp.first_tier = h->nz > 48 ? 1 : 0;
+                HIP_TRY(h, launch_sgains(h));
+                HIP_TRY(h, launch_sdual(h, qp));
             } else
                 return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_iterate: no stage-wise QP solver for this design");
             q.since_start += 1;
@@ -3615,8 +3612,10 @@ static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_o
             // (an iterate holds half of its inputs on bounds; a saturated unstable linearisation is where the dual method has no
             // certificate) --, ONE idle launch per iteration instead of three; with state rows / S: k_sgains + k_sdual
             const bool primal_only = h->mc == 0 && !q.useS && h->rKst && !h->sw.sqp_redo_dual_first;
-            if (h->sd.ready && !primal_only) { HIP_TRY(h, launch_sgains(h, 2)); HIP_TRY(h, launch_sdual(h, 2, nullptr, 0, true, 0, {}, rows)); }
-            if (h->mc == 0 && !q.useS && h->rKst) HIP_TRY(h, launch_riccati(h, 2, nullptr, 0));
+            SolveCall flagged;
+            flagged.filter = FILTER_SQP_FLAGGED; flagged.single_launch = true; flagged.rows = rows;   // (the last two: k_sdual's)
+            if (h->sd.ready && !primal_only) { HIP_TRY(h, launch_sgains(h, flagged)); HIP_TRY(h, launch_sdual(h, flagged)); }
+            if (h->mc == 0 && !q.useS && h->rKst) HIP_TRY(h, launch_riccati(h, flagged));
         }
         q.since_start += 1;
         sp.stats = q.stats + 2 * it;
