@@ -158,7 +158,13 @@ def load():
     L.almpc_group_sensitivity_params_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.POINTER(almpc_param_grads)]
     L.almpc_sensitivity_params_vjp_dare.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.POINTER(almpc_param_grads), _ip]
     L.almpc_group_sensitivity_params_vjp_dare.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.POINTER(almpc_param_grads), _ip]
+    L.almpc_sensitivity_stagewise.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double]
+    L.almpc_sensitivity_stagewise_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, _dp, _ip]
+    L.almpc_group_sensitivity_stagewise.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double]
+    L.almpc_group_sensitivity_stagewise_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, _dp, _ip]
     for nm_ in ("almpc_sensitivity", "almpc_get_sensitivity", "almpc_device_sensitivity", "almpc_sensitivity_vjp",
+                "almpc_sensitivity_stagewise", "almpc_sensitivity_stagewise_vjp",
+                "almpc_group_sensitivity_stagewise", "almpc_group_sensitivity_stagewise_vjp",
                 "almpc_sensitivity_params_vjp", "almpc_group_sensitivity_params_vjp",
                 "almpc_sensitivity_params_vjp_dare", "almpc_group_sensitivity_params_vjp_dare",
                 "almpc_group_sensitivity", "almpc_group_get_sensitivity", "almpc_group_sensitivity_vjp",
@@ -1040,6 +1046,16 @@ class Solver:
         trajectories (almpc_sensitivity_vjp: no Jacobian is formed); also returns rows (batch,)."""
         return _sens_vjp(self.L.almpc_sensitivity_vjp, self.h, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
 
+    def sensitivity_stagewise(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
+        """sensitivity on a structured handle (almpc_sensitivity_stagewise + almpc_get_sensitivity): the Riccati recursion on the face
+        where the inputs at a bound are held; input box only, S = 0.  act_tol is relative to the width of the input box (0: 1e-7)."""
+        self._check(self.L.almpc_sensitivity_stagewise(self.h, _sens_mask(want), float(act_tol)))
+        return _sens_read(self.L.almpc_get_sensitivity, self.h, self._check, want, self.batch, self.n, self.m, self.N)
+
+    def sensitivity_stagewise_vjp(self, g_u, g_x=None, act_tol=0.0):
+        """sensitivity_vjp on a structured handle (almpc_sensitivity_stagewise_vjp): (g_x0 (batch, n), rows (batch,))."""
+        return _sens_vjp(self.L.almpc_sensitivity_stagewise_vjp, self.h, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
+
     def sensitivity_params_vjp(self, g_u, g_x=None, want=PARAM_GROUPS, act_tol=0.0, terminal="data") -> dict:
         """Gradients of the loss of sensitivity_vjp in the problem data, per instance (almpc_sensitivity_params_vjp): x0, the QP's
         linear term f, u_ref, the input box, the weights Q, P, R, S and the model A, B -- what `want` names -- and rows.  For a shared
@@ -1407,6 +1423,16 @@ class Group:
     def sensitivity_vjp(self, g_u, g_x=None, act_tol=0.0):
         """Solver.sensitivity_vjp for the whole batch (almpc_group_sensitivity_vjp)."""
         return _sens_vjp(self.L.almpc_group_sensitivity_vjp, self.g, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
+
+    def sensitivity_stagewise(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
+        """Solver.sensitivity_stagewise for the whole batch (almpc_group_sensitivity_stagewise + almpc_group_get_sensitivity)."""
+        self._check(self.L.almpc_group_sensitivity_stagewise(self.g, _sens_mask(want), float(act_tol)))
+        return _sens_read(self.L.almpc_group_get_sensitivity, self.g, self._check, want, self.batch, self.n, self.m, self.N)
+
+    def sensitivity_stagewise_vjp(self, g_u, g_x=None, act_tol=0.0):
+        """Solver.sensitivity_stagewise_vjp for the whole batch (almpc_group_sensitivity_stagewise_vjp)."""
+        return _sens_vjp(self.L.almpc_group_sensitivity_stagewise_vjp, self.g, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m,
+                         self.N)
 
     def sensitivity_params_vjp(self, g_u, g_x=None, want=PARAM_GROUPS, act_tol=0.0, terminal="data") -> dict:
         """Solver.sensitivity_params_vjp for the whole batch (almpc_group_sensitivity_params_vjp, almpc_group_sensitivity_params_vjp_dare)."""

@@ -685,4 +685,325 @@ inline __global__ __launch_bounds__(256) void k_sens_rows_table(SensRowsTablePar
     }
 }
 
+// ---- k_sens_face: the same sensitivities on a structured handle (almpc_sensitivity_stagewise, almpc_sensitivity_stagewise_vjp) --------
+//
+// A structured handle forms no G = H'^-1, and none is needed: on the face where the rows W of the returned u are held the problem is
+// an LQ problem whose clamped inputs are taken out stage by stage, and its derivative in x0 is a Riccati recursion with a masked B --
+// O(N (n^3 + n^2 m)) per instance, whatever m N and the spectral radius of A.  Input box only, S = 0.  Stages 0-based: x_0 = x0,
+// Qbar_k = Q (1 <= k <= N-1), Qbar_0 = 0, P on stage N; W_k the inputs of stage k at a bound, f the free ones:
+//     P+ = P at k = N;  for k = N-1 .. 0:
+//       Lam = R_ff + B_f' P+ B_f                 (R as the design uses it: zero when R[1,1] == 0)
+//       K_k[f,:] = Lam^-1 B_f' P+ A,   K_k[W_k,:] = 0,   Acl_k = A - B K_k
+//       P+ <- Qbar_k + Acl_k' P+ Acl_k + K_k' R K_k            (symmetrised)
+//     Jacobians:  dx_0 = I,  du_k = -K_k dx_k,  dx_{k+1} = A dx_k + B du_k          (K0 = -K_0)
+//     VJP:        lam_N = g_x[N],  lam_k = g_x[k] - K_k' g_u[k] + Acl_k' lam_{k+1},   g_x0 = lam_0
+// The VJP rides the backward sweep (no stored gains, no Jacobian); K0 alone is the backward sweep; dU and dX need the gains of every
+// stage, which go to a per-instance scratch [N][m n] in global memory and come back one stage ahead in the forward pass.
+//
+// Active-set rule, on the returned u (there is no Jacobi scale here): row (k, i) is in W iff  u[i,k] - umin_i <= tau w_i  or
+// umax_i - u[i,k] <= tau w_i,  w_i = umax_i - umin_i.  Weakly active rows: the derivative of the face on which every flagged row is
+// held, as in k_sens.
+//
+// One wave per instance, up to SENS_FACE_WAVES waves per workgroup that never wait for each other; every matrix of a stage in the
+// wave's slice of LDS, column-major: A, Q, P+, T (= P+ Acl, then the new P before it is symmetrised; dx+ in the forward pass), Acl |
+// B, P+ B, K (B'P+A solved in place), R K | R, Lam (Cholesky in place; a clamped input is an identity row and column, so the factor
+// is that of the free block) | lam, lam+ | the stage masks.  A pivot that is not positive and finite: rows = -1 and zeros, as an
+// unsolved instance.  <NC, MC>: dimensions known at compile time (0, 0: from the parameters), as k_riccati_t.
+constexpr int SENS_FACE_WAVES = 4;
+
+struct SensFaceParams {
+    int n, m, N, batch;
+    const double* A; long A_stride;     // n x n column-major (stride 0: shared)
+    const double* B; long B_stride;     // n x m
+    const double* Q; const double* R;   // n x n, m x m, symmetric, shared (R: zeros where the design dropped it)
+    const double* P; long P_stride;     // n x n terminal weight
+    const double* umin; const double* umax;   // [m]
+    const double* u;                    // [batch][N][m] returned inputs
+    const int32_t* status;              // [batch]
+    double tau;
+    unsigned want;                      // SENS_* (Jacobian mode)
+    double* Kst;                        // [batch][N][m n] gains (only with SENS_DU / SENS_DX)
+    double* K0; double* dU; double* dX; // layouts of SensParams / SensDxParams
+    const double* g_u; const double* g_x;   // [batch][N][m], [batch][N+1][n] or null (VJP mode)
+    double* g_x0;                       // [batch][n]
+    int32_t* rows;                      // [batch] |W|, or -1
+    int lds_per_wave;                   // doubles
+};
+
+__host__ __device__ inline int sens_face_lds_doubles(int n, int m, int N) {
+    return (5 * n * n + 4 * n * m + 2 * m * m + 2 * n + (N + 1) / 2 + 1) & ~1;
+}
+
+// out (r x c) = op(X) (r x k) Y (k x c), column-major; TX: X is stored k x r and used transposed
+template <bool TX>
+__device__ __forceinline__ void sens_face_mul(double* out, const double* X, const double* Y, int r, int k, int c, int lane) {
+    for (int t = lane; t < r * c; t += 64) {
+        const int i = t % r, j = t / r;
+        double acc = 0.0;
+        for (int l = 0; l < k; ++l) acc += (TX ? X[l + i * k] : X[i + l * r]) * Y[l + j * k];
+        out[t] = acc;
+    }
+}
+
+template <bool VJP, int NC, int MC>
+__global__ __launch_bounds__(64 * SENS_FACE_WAVES) void k_sens_face(SensFaceParams p) {
+    extern __shared__ __attribute__((aligned(16))) double sens_face_smem[];
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int n = NC ? NC : p.n, m = MC ? MC : p.m, N = p.N, nn = n * n, nm = n * m, mm = m * m, nz = N * m;
+    const SensTeam<false> T{lane, 64};
+    double* L = sens_face_smem + (size_t)wv * p.lds_per_wave;
+    double* As = L;            double* Qs = As + nn;    double* Pn = Qs + nn;   double* Tm = Pn + nn;   double* Ac = Tm + nn;
+    double* Bs = Ac + nn;      double* PB = Bs + nm;    double* Ks = PB + nm;   double* RK = Ks + nm;
+    double* Rs = RK + nm;      double* Lam = Rs + mm;
+    double* lam = Lam + mm;    double* lamn = lam + n;
+    uint32_t* wset = reinterpret_cast<uint32_t*>(lamn + n);   // [N] bit a: input a of the stage is held
+    const bool jac = !VJP && (p.want & (SENS_DU | SENS_DX)) != 0;
+
+    const int wpb = (int)(blockDim.x >> 6), nwaves = gridDim.x * wpb;
+    for (int inst = blockIdx.x * wpb + wv; inst < p.batch; inst += nwaves) {
+        T.sync();   // (the previous instance of this wave has read its last LDS operand)
+        bool ok = p.status[inst] == 0;
+        int rows = 0;
+        if (ok) {
+            const double* Ag = p.A + (size_t)inst * p.A_stride;
+            const double* Bg = p.B + (size_t)inst * p.B_stride;
+            const double* Pg = p.P + (size_t)inst * p.P_stride;
+            for (int t = lane; t < nn; t += 64) { As[t] = Ag[t]; Qs[t] = p.Q[t]; Pn[t] = 0.5 * (Pg[t] + Pg[(t % n) * n + t / n]); }
+            for (int t = lane; t < nm; t += 64) Bs[t] = Bg[t];
+            for (int t = lane; t < mm; t += 64) Rs[t] = p.R[t];
+            for (int k = lane; k < N; k += 64) wset[k] = 0u;
+            T.sync();
+            // the rows at a bound
+            for (int t = lane; t < nz; t += 64) {
+                const int k = t / m, a = t - k * m;
+                const double uj = p.u[(size_t)inst * nz + t], lo = p.umin[a], hi = p.umax[a], tol = p.tau * (hi - lo);
+                if (uj - lo <= tol || hi - uj <= tol) { atomicOr(&wset[k], 1u << a); ++rows; }
+            }
+            for (int o = 32; o > 0; o >>= 1) rows += __shfl_xor(rows, o);
+            if (VJP) {   // (0.0 is added where g_x is null, so that a null g_x and a g_x of zeros give the same bits)
+                const double* gx = p.g_x ? p.g_x + (size_t)inst * (N + 1) * n : nullptr;
+                for (int i = lane; i < n; i += 64) lam[i] = 0.0 + (gx ? gx[(size_t)N * n + i] : 0.0);
+            }
+            T.sync();
+        }
+        // ---- backward sweep
+        for (int k = N - 1; ok && k >= 0; --k) {
+            const uint32_t wk = wset[k];
+            sens_face_mul<false>(PB, Pn, Bs, n, n, m, lane);   // P+ B
+            T.sync();
+            sens_face_mul<true>(Ks, PB, As, m, n, n, lane);    // B' P+ A = (P+ B)' A   (P+ is symmetric)
+            sens_face_mul<true>(Lam, Bs, PB, m, n, m, lane);   // B' P+ B
+            T.sync();
+            for (int t = lane; t < mm; t += 64) {              // Lam = R + B'P+B, identity on the held inputs
+                const int i = t % m, j = t / m;
+                const bool hi_ = (wk >> i) & 1u, hj = (wk >> j) & 1u;
+                Lam[t] = (hi_ || hj) ? (i == j ? 1.0 : 0.0) : Lam[t] + Rs[t];
+            }
+            for (int t = lane; t < nm; t += 64)                // the rows of the held inputs vanish
+                if ((wk >> (t % m)) & 1u) Ks[t] = 0.0;
+            T.sync();
+            if constexpr (MC > 0 && MC <= 4) {
+                // m <= 4: every lane factors Lam in its own registers (ten entries, no fence between the pivots; the diagonal is
+                // kept as its reciprocal), then takes a column of B'P+A through both substitutions
+                double l[MC][MC];
+#pragma unroll
+                for (int i = 0; i < MC; ++i)
+#pragma unroll
+                    for (int j = 0; j <= i; ++j) l[i][j] = Lam[i + j * MC];
+#pragma unroll
+                for (int c = 0; c < MC; ++c) {
+                    const double piv = l[c][c];
+                    if (!(piv > 0.0 && piv <= 1.7976931348623157e308)) ok = false;
+                    const double inv = 1.0 / sqrt(piv);
+                    l[c][c] = inv;
+#pragma unroll
+                    for (int i = c + 1; i < MC; ++i) l[i][c] *= inv;
+#pragma unroll
+                    for (int j = c + 1; j < MC; ++j)
+#pragma unroll
+                        for (int i = j; i < MC; ++i) l[i][j] -= l[i][c] * l[j][c];
+                }
+                if (!ok) break;   // (every lane factored the same matrix)
+                for (int c = lane; c < n; c += 64) {
+                    double x[MC];
+#pragma unroll
+                    for (int i = 0; i < MC; ++i) x[i] = Ks[i + c * MC];
+#pragma unroll
+                    for (int i = 0; i < MC; ++i) {
+#pragma unroll
+                        for (int j = 0; j < i; ++j) x[i] -= l[i][j] * x[j];
+                        x[i] *= l[i][i];
+                    }
+#pragma unroll
+                    for (int i = MC - 1; i >= 0; --i) {
+#pragma unroll
+                        for (int j = i + 1; j < MC; ++j) x[i] -= l[j][i] * x[j];
+                        x[i] *= l[i][i];
+                    }
+#pragma unroll
+                    for (int i = 0; i < MC; ++i) Ks[i + c * MC] = x[i];
+                }
+            } else {
+            // Lam = C C' in place (lower triangle)
+            for (int c = 0; c < m; ++c) {
+                const double piv = Lam[c + c * m];             // (every lane reads the same word)
+                if (!(piv > 0.0 && piv <= 1.7976931348623157e308)) { ok = false; break; }
+                const double dk = sqrt(piv);
+                T.sync();
+                for (int i = c + lane; i < m; i += 64) Lam[i + c * m] = i == c ? dk : Lam[i + c * m] / dk;
+                T.sync();
+                const int rem = m - c - 1;
+                for (int idx = lane; idx < rem * rem; idx += 64) {
+                    const int i = c + 1 + idx / rem, j = c + 1 + idx % rem;
+                    if (j <= i) Lam[i + j * m] -= Lam[i + c * m] * Lam[j + c * m];
+                }
+                T.sync();
+            }
+            if (!ok) break;
+            // K = Lam^-1 (B'P+A): a lane takes a column through both substitutions
+            for (int c = lane; c < n; c += 64) {
+                double* x = Ks + c * m;
+                for (int i = 0; i < m; ++i) {
+                    double s = x[i];
+                    for (int j = 0; j < i; ++j) s -= Lam[i + j * m] * x[j];
+                    x[i] = s / Lam[i + i * m];
+                }
+                for (int i = m - 1; i >= 0; --i) {
+                    double s = x[i];
+                    for (int j = i + 1; j < m; ++j) s -= Lam[j + i * m] * x[j];
+                    x[i] = s / Lam[i + i * m];
+                }
+            }
+            }
+            T.sync();
+            if (jac) {
+                double* Kg = p.Kst + ((size_t)inst * N + k) * nm;
+                for (int t = lane; t < nm; t += 64) Kg[t] = Ks[t];
+            }
+            if (!VJP && k == 0 && (p.want & SENS_K0))
+                for (int t = lane; t < nm; t += 64) p.K0[(size_t)inst * nm + t] = 0.0 - Ks[t];
+            if (!VJP && k == 0) break;                         // (P_0 has no reader)
+            for (int t = lane; t < nn; t += 64) {              // Acl = A - B K
+                const int i = t % n, j = t / n;
+                double s = As[t];
+                for (int a = 0; a < m; ++a) s -= Bs[i + a * n] * Ks[a + j * m];
+                Ac[t] = s;
+            }
+            if (k > 0) sens_face_mul<false>(RK, Rs, Ks, m, m, n, lane);   // R K
+            T.sync();
+            double ln = 0.0;
+            if (VJP && lane < n) {                             // lam_k = g_x[k] - K' g_u[k] + Acl' lam_{k+1}
+                const double* gu = p.g_u + (size_t)inst * nz + (size_t)k * m;
+                ln = p.g_x ? p.g_x[((size_t)inst * (N + 1) + k) * n + lane] : 0.0;
+                for (int a = 0; a < m; ++a) ln -= Ks[a + lane * m] * gu[a];
+                for (int l = 0; l < n; ++l) ln += Ac[l + lane * n] * lam[l];
+            }
+            if (k > 0) {
+                sens_face_mul<false>(Tm, Pn, Ac, n, n, n, lane);   // P+ Acl
+                T.sync();
+                double pnew[16];   // n n <= 1024: at most 16 entries per lane
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                    const int t = lane + 64 * c;
+                    double s = 0.0;
+                    if (t < nn) {
+                        const int i = t % n, j = t / n;
+                        s = Qs[t];
+                        for (int l = 0; l < n; ++l) s += Ac[l + i * n] * Tm[l + j * n];
+                        for (int a = 0; a < m; ++a) s += Ks[a + i * m] * RK[a + j * m];
+                    }
+                    pnew[c] = s;
+                }
+                T.sync();
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                    const int t = lane + 64 * c;
+                    if (t < nn) Tm[t] = pnew[c];               // (Tm is free now: the new P before it is symmetrised)
+                }
+                T.sync();
+                for (int t = lane; t < nn; t += 64) Pn[t] = 0.5 * (Tm[t] + Tm[(t % n) * n + t / n]);
+            }
+            if (VJP && lane < n) lamn[lane] = ln;
+            T.sync();
+            if (VJP) { double* sw = lam; lam = lamn; lamn = sw; }
+        }
+        if (!ok) {   // unsolved, or a pivot that is not positive and finite
+            if (VJP) {
+                for (int c = lane; c < n; c += 64) p.g_x0[(size_t)inst * n + c] = 0.0;
+            } else {
+                if (p.want & SENS_K0)
+                    for (int t = lane; t < nm; t += 64) p.K0[(size_t)inst * nm + t] = 0.0;
+                if (jac)
+                    for (int t = lane; t < n * nz; t += 64) p.dU[(size_t)inst * n * nz + t] = 0.0;
+                if (p.want & SENS_DX)
+                    for (int t = lane; t < (N + 1) * nn; t += 64) p.dX[(size_t)inst * (N + 1) * nn + t] = 0.0;
+            }
+            if (lane == 0) p.rows[inst] = -1;
+            continue;
+        }
+        if (lane == 0) p.rows[inst] = rows;
+        if (VJP) {
+            for (int c = lane; c < n; c += 64) p.g_x0[(size_t)inst * n + c] = lam[c];
+            continue;
+        }
+        if (!jac) continue;
+        // ---- forward pass: dx in Pn, dx+ in Tm, du in PB.  The gains were stored by other lanes of this wave: made visible at device
+        // scope, read back past the L1 and one stage ahead
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        __builtin_amdgcn_wave_barrier();
+        const double* Kg = p.Kst + (size_t)inst * N * nm;
+        double* dUo = p.dU + (size_t)inst * n * nz;
+        double* dXo = p.dX + (size_t)inst * (N + 1) * nn;
+        const bool wdx = (p.want & SENS_DX) != 0;
+        double kreg[8];   // n m <= 512: at most 8 entries per lane
+        auto kload = [&](int k) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const int t = lane + 64 * c;
+                kreg[c] = t < nm ? __hip_atomic_load(Kg + (size_t)k * nm + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+            }
+        };
+        kload(0);
+        double* dx = Pn;
+        double* dxn = Tm;
+        for (int t = lane; t < nn; t += 64) {
+            const int i = t % n, c = t / n;
+            const double v = i == c ? 1.0 : 0.0;
+            dx[t] = v;
+            if (wdx) dXo[(size_t)c * (N + 1) * n + i] = v;
+        }
+        T.sync();
+        for (int k = 0; k < N; ++k) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const int t = lane + 64 * c;
+                if (t < nm) Ks[t] = kreg[c];
+            }
+            if (k + 1 < N) kload(k + 1);
+            T.sync();
+            for (int t = lane; t < nm; t += 64) {              // du = -K dx  (dx_0 = I: the bits of K0)
+                const int a = t % m, c = t / m;
+                double s = 0.0;
+                if (k == 0) s -= Ks[t];
+                else for (int j = 0; j < n; ++j) s -= Ks[a + j * m] * dx[j + c * n];
+                PB[t] = s;
+                dUo[(size_t)c * nz + (size_t)k * m + a] = s;
+            }
+            T.sync();
+            if (k + 1 < N || wdx) {
+                for (int t = lane; t < nn; t += 64) {          // dx+ = A dx + B du
+                    const int i = t % n, c = t / n;
+                    double s = 0.0;
+                    for (int j = 0; j < n; ++j) s += As[i + j * n] * dx[j + c * n];
+                    for (int a = 0; a < m; ++a) s += Bs[i + a * n] * PB[a + c * m];
+                    dxn[t] = s;
+                    if (wdx) dXo[((size_t)c * (N + 1) + k + 1) * n + i] = s;
+                }
+                T.sync();
+                double* sw = dx; dx = dxn; dxn = sw;
+            }
+        }
+    }
+}
+
 }  // namespace almpc

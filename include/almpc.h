@@ -693,6 +693,39 @@ int almpc_sensitivity_rows_vjp(almpc_handle* h, const double* g_u, const double*
                                double* g_x0 /* [batch][n] */, int32_t* rows /* or NULL */);
 
 /*
+ * The same on ALMPC_FLAG_STRUCTURED handles (k_sens_face, DESIGN.md "k_sens_face"), which form no G = H'^-1 and need none: on the face
+ * where the rows W are held the problem is an LQ problem whose clamped inputs are taken out stage by stage, and its derivative is a
+ * Riccati recursion with a masked B -- O(N (n^3 + n^2 m)) per instance, whatever m N and the spectral radius of A.  Input box only,
+ * S = 0.  Stages 0-based: x_0 = x0, Qbar_k = Q (1 <= k <= N-1), Qbar_0 = 0, P on stage N; W_k the inputs of stage k in W, f the free:
+ *     P+ = P at k = N;  for k = N-1 .. 0:
+ *       Lam = R_ff + B_f' P+ B_f                 (R as the design uses it: zero when R[1,1] == 0)
+ *       K_k[f,:] = Lam^-1 B_f' P+ A,   K_k[W_k,:] = 0,   Acl_k = A - B K_k
+ *       P+ <- Qbar_k + Acl_k' P+ Acl_k + K_k' R K_k            (symmetrised)
+ *     Jacobians:  dx_0 = I,  du_k = -K_k dx_k,  dx_{k+1} = A dx_k + B du_k          (K0 = -K_0)
+ *     VJP:        lam_N = g_x[N],  lam_k = g_x[k] - K_k' g_u[k] + Acl_k' lam_{k+1},   g_x0 = lam_0
+ * W, on the returned u (a structured handle has no Jacobi scale): row (stage k, input i) is in W iff
+ *     u[i,k] - umin_i <= act_tol * w_i   or   umax_i - u[i,k] <= act_tol * w_i,     w_i = umax_i - umin_i;
+ * act_tol <= 0 means 1e-7: k_riccati writes a working-set row out as the bound itself, but k_sdual's confirmation accepts a
+ * working-set row up to 1e-8 of its width away from its bound (csrc/almpc_sdual.hip.h:1012, `resn <= 1e-8`), and the default is ten
+ * times that.  At a weakly active row: the derivative of the face on which every flagged row is held, as above.
+ *   almpc_sensitivity_stagewise      almpc_sensitivity: synchronous, settles first, results in the same buffers of the handle, so
+ *                                    almpc_get_sensitivity and almpc_device_sensitivity serve them; layouts and rows as there.  A call
+ *                                    for ALMPC_SENS_K0 alone is one backward sweep and allocates no gain scratch.
+ *   almpc_sensitivity_stagewise_vjp  almpc_sensitivity_vjp: the adjoint rides the backward sweep, no gain is stored, no Jacobian formed;
+ *                                    g_x = NULL is bit-identical to zeros.
+ * An instance that is not ALMPC_SOLVED, or one of whose Lam has a pivot that is not positive and finite, gets rows = -1 and zeros.
+ * Served: almpc_design_shared and almpc_design_batched on a structured handle (A_i, B_i, P_i per instance).  ALMPC_ERR_UNSUPPORTED,
+ * with the reason in almpc_last_error: a handle that is not structured (almpc_sensitivity serves it), S != 0 in the design, a state box
+ * or the terminal equality, the SQP loop and the re-linearisation pipeline, a shape outside k_riccati (n <= 32, m <= 16, m N <= 1024).
+ * ALMPC_ERR_INVALID: before the design's first step, a `want` that is no mask of ALMPC_SENS_*, a NULL g_u or g_x0.
+ */
+int almpc_sensitivity_stagewise(almpc_handle* h, uint32_t want, double act_tol);            /* ALMPC_SENS_K0 | _DU | _DX */
+int almpc_sensitivity_stagewise_vjp(almpc_handle* h, const double* g_u, const double* g_x /* or NULL */, double act_tol,
+                                    double* g_x0 /* [batch][n] */, int32_t* rows /* or NULL */);
+int almpc_group_sensitivity_stagewise(almpc_group* g, uint32_t want, double act_tol);
+int almpc_group_sensitivity_stagewise_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows);
+
+/*
  * Parameter gradients of the returned solution: for the loss of almpc_sensitivity_vjp (g_u [batch][N][m], g_x [batch][N+1][n] or NULL),
  * its gradient in the problem data, per instance, on the face where the rows W (same rule, same act_tol) are held -- the backward
  * pass of a step for a caller who learns or tunes the controller (k_sens_pz, k_sens_params; DESIGN.md "k_sens_params").  Stages

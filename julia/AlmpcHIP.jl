@@ -21,7 +21,8 @@ export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_s
        group_sqp_start!, group_sqp_iterate!, group_sqp_solve!, group_set_sqp_hessian!, group_set_sqp_row_multipliers!, group_state_multipliers, group_sqp_skipped, group_x0_staging, group_update_initialization_staged!, group_results_async,
        group_results_wait!, sensitivity, device_sensitivity, sensitivity_vjp, group_sensitivity, group_sensitivity_vjp,
        sensitivity_rows, sensitivity_rows_vjp, group_sensitivity_rows, group_sensitivity_rows_vjp, sensitivity_params_vjp,
-       group_sensitivity_params_vjp, dare_vjp, dare_vjp_batched
+       group_sensitivity_params_vjp, dare_vjp, dare_vjp_batched, sensitivity_stagewise, sensitivity_stagewise_vjp,
+       group_sensitivity_stagewise, group_sensitivity_stagewise_vjp
 
 const libalmpc = get(ENV, "ALMPC_LIB", "libalmpc.so")
 
@@ -723,6 +724,30 @@ function sensitivity_rows_vjp(mod::HipModeler, g_u::Array{Float64}, g_x::Union{N
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Ptr{Float64}, Ptr{Int32}), mod.handle, g_u, px, act_tol_u, act_tol_x, g_x0, rows))
     return g_x0, rows
 end
+"""
+    sensitivity_stagewise(mod; K0 = true, dU = false, dX = false, act_tol = 0.0) -> (K0, dU, dX, rows)
+
+`sensitivity` on a structured modeler (`almpc_sensitivity_stagewise` + `almpc_get_sensitivity`): the Riccati recursion on the face where
+the inputs at a bound are held, for any m N; input box only, S = 0.  `act_tol` is relative to the width of the input box (0: 1e-7).
+"""
+function sensitivity_stagewise(mod::HipModeler; K0::Bool = true, dU::Bool = false, dX::Bool = false, act_tol::Real = 0.0)
+    k, du, dx, rows = sens_arrays(mod.n, mod.m, mod.N, mod.batch, K0, dU, dX)
+    check(mod.handle, ccall((:almpc_sensitivity_stagewise, libalmpc), Cint, (Ptr{Cvoid}, UInt32, Cdouble), mod.handle,
+                            sens_mask(K0, dU, dX), act_tol))
+    pf(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve k du dx check(mod.handle, ccall((:almpc_get_sensitivity, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), mod.handle, pf(k), pf(du), pf(dx), rows))
+    return k, du, dx, rows
+end
+"`sensitivity_vjp` on a structured modeler (`almpc_sensitivity_stagewise_vjp`)"
+function sensitivity_stagewise_vjp(mod::HipModeler, g_u::Array{Float64}, g_x::Union{Nothing,Array{Float64}} = nothing; act_tol::Real = 0.0)
+    check_sens_sizes(mod.n, mod.m, mod.N, mod.batch, g_u, g_x)
+    g_x0, rows = Matrix{Float64}(undef, mod.n, mod.batch), Vector{Int32}(undef, mod.batch)
+    px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
+    GC.@preserve g_x check(mod.handle, ccall((:almpc_sensitivity_stagewise_vjp, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), mod.handle, g_u, px, act_tol, g_x0, rows))
+    return g_x0, rows
+end
 
 # almpc_param_grads (include/almpc.h): host pointers, C_NULL = not wanted
 struct ParamGrads
@@ -925,6 +950,25 @@ function group_sensitivity_vjp(g::HipGroup, g_u::Array{Float64}, g_x::Union{Noth
     g_x0, rows = Matrix{Float64}(undef, g.n, g.batch), Vector{Int32}(undef, g.batch)
     px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
     GC.@preserve g_x gcheck(g.group, ccall((:almpc_group_sensitivity_vjp, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), g.group, g_u, px, act_tol, g_x0, rows))
+    return g_x0, rows
+end
+"`sensitivity_stagewise` for the whole batch (`almpc_group_sensitivity_stagewise` + `almpc_group_get_sensitivity`)"
+function group_sensitivity_stagewise(g::HipGroup; K0::Bool = true, dU::Bool = false, dX::Bool = false, act_tol::Real = 0.0)
+    k, du, dx, rows = sens_arrays(g.n, g.m, g.N, g.batch, K0, dU, dX)
+    gcheck(g.group, ccall((:almpc_group_sensitivity_stagewise, libalmpc), Cint, (Ptr{Cvoid}, UInt32, Cdouble), g.group,
+                          sens_mask(K0, dU, dX), act_tol))
+    pf(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve k du dx gcheck(g.group, ccall((:almpc_group_get_sensitivity, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), g.group, pf(k), pf(du), pf(dx), rows))
+    return k, du, dx, rows
+end
+"`sensitivity_stagewise_vjp` for the whole batch (`almpc_group_sensitivity_stagewise_vjp`)"
+function group_sensitivity_stagewise_vjp(g::HipGroup, g_u::Array{Float64}, g_x::Union{Nothing,Array{Float64}} = nothing; act_tol::Real = 0.0)
+    check_sens_sizes(g.n, g.m, g.N, g.batch, g_u, g_x)
+    g_x0, rows = Matrix{Float64}(undef, g.n, g.batch), Vector{Int32}(undef, g.batch)
+    px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
+    GC.@preserve g_x gcheck(g.group, ccall((:almpc_group_sensitivity_stagewise_vjp, libalmpc), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), g.group, g_u, px, act_tol, g_x0, rows))
     return g_x0, rows
 end
