@@ -1096,6 +1096,17 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
         Gp = smem;
     }
     if (!handed) __syncthreads();
+    // Lane geometry that depends on the lane number and the shape alone: the input index r0 % m of the lane's row pair (an integer
+    // division by the runtime m) is formed once per kernel and carried into the instances in one register; r1's index follows from
+    // it.  Not in k_polish<false> (CH == 16), which has no register to spare; -DALMPC_EXP_LANE_GEOMETRY_PER_INSTANCE: every instance
+    // divides again, as before.
+#ifdef ALMPC_EXP_LANE_GEOMETRY_PER_INSTANCE
+    constexpr bool GEO_ONCE = false;
+#else
+    constexpr bool GEO_ONCE = CH == 8;
+#endif
+    [[maybe_unused]] int geo_m0 = 0;
+    if constexpr (GEO_ONCE) geo_m0 = (2 * lane_k) % p.m;
   // rec: the instance's hand-off record of rank `rank` (LDS), or null: its ADMM results are read from global memory
   auto process = [&](const int inst, const double* rec, const int rank) {
     // the parameters are re-read from the kernarg segment through a pointer the optimiser cannot see through: otherwise
@@ -1142,11 +1153,24 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
     const bool inrow = r0 < nzs;            // nzs is even: the pair (r0, r1) is inside the padded vector or not at all
     const int rc = inrow ? r0 : 0;          // clamped pair index for loads (lanes beyond the vector read pair 0)
     const bool skip = (st_in == 2);  // non-finite instance: nothing to polish, the ADMM iterate is handed on as is
+    int im0;                                // input index of row r0 (r0 % m), and of row r1 = r0 + 1
+    if constexpr (GEO_ONCE) im0 = geo_m0; else im0 = r0 % p.m;
+    const int im1 = (im0 + 1 == p.m) ? 0 : im0 + 1;
 
     double* rowbuf = wave_lds;         // [128] one row-distributed vector, for gathers by row index
     double* pbufa = rowbuf + 128;      // [64]  one position-distributed vector, for broadcasts by position
     double* pbufb = pbufa + 64;        // [64]  a second one
-    int* wrow_s = reinterpret_cast<int*>(pbufb + 64);  // [64] row index of each position (copy of wrow)
+    // [64] the row of each position as the sweeps address it: its element offset row * gs into G (gs is fixed for the whole kernel, a
+    // row enters once and is read by every later sweep: the multiply is paid by the writer).  -DALMPC_EXP_ROW_NUMBERS: the earlier
+    // form, a copy of wrow that every reader multiplies by gs.
+    int* wrow_s = reinterpret_cast<int*>(pbufb + 64);
+#ifdef ALMPC_EXP_ROW_NUMBERS
+    auto woff = [&](int row) { return row; };
+    auto wadr = [&](int e) { return e * gs; };
+#else
+    auto woff = [&](int row) { return row * gs; };
+    auto wadr = [&](int e) { return e; };
+#endif
     // second tier (working sets beyond 32 rows): Sinv in memory, leading dimension 64, capacity cap2.  Its home is the wave's own
     // LDS (SGL), the workgroup-shared LDS slot if this wave gets it (G-in-LDS builds; chosen when the tier is entered), or the
     // instance's global scratch.  In the G-in-LDS builds the pointer is a generic one (flat accesses): the tier is rare there.
@@ -1207,11 +1231,11 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
         }
         if (in0) {
             const double di = 1.0 / dv[0], ur = urp0;
-            lo0 = (shc[SL.off_umin + r0 % p.m] - ur) * di; hi0 = (shc[SL.off_umax + r0 % p.m] - ur) * di; w0 = fmin(fmax(z0, lo0), hi0);
+            lo0 = (shc[SL.off_umin + im0] - ur) * di; hi0 = (shc[SL.off_umax + im0] - ur) * di; w0 = fmin(fmax(z0, lo0), hi0);
         } else { v00 = 0.0; y0 = 0.0; z0 = 0.0; }
         if (in1) {
             const double di = 1.0 / dv[1], ur = urp1;
-            lo1 = (shc[SL.off_umin + r1 % p.m] - ur) * di; hi1 = (shc[SL.off_umax + r1 % p.m] - ur) * di; w1 = fmin(fmax(z1, lo1), hi1);
+            lo1 = (shc[SL.off_umin + im1] - ur) * di; hi1 = (shc[SL.off_umax + im1] - ur) * di; w1 = fmin(fmax(z1, lo1), hi1);
         } else { v01 = 0.0; y1 = 0.0; z1 = 0.0; }
     }
     int wrow = 0, wsd = 0;   // position-distributed: row index, side (+1 upper / -1 lower)
@@ -1315,8 +1339,8 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
     };
     // (q0, q1) = sum_{l<k} G[W_l, rows] * a_l, a given in LDS buffer ab (zero beyond k): the only O(nz k) part of an
     // update.  One 16-byte load per row and lane; row indices come from the LDS copy of wrow (zero beyond k: row 0
-    // is a valid address and its weight is zero).  Split in a load half and an FMA half so that the first chunk's L2
-    // round trip can be started before the LDS work that produces the weights.
+    // is a valid address and its weight is zero; wrow_s holds them as element offsets row * gs).  Split in a load half
+    // and an FMA half so that the first chunk's L2 round trip can be started before the LDS work that produces the weights.
     // Round 3: CH row indices in CH / 4 wave-uniform 16-byte reads of the LDS copy, addresses on the vector unit.  v_readlane ->
     // s_mul -> address costs ~30 cycles per row one after the other (tools/microbench/dep_latency.hip: a VALU write to a scalar
     // register is slow to reach its reader), 1.0 k of the 4.1 k cycles of a one-row change at 30 rows; the LDS copy is ONE ~80-cycle
@@ -1331,7 +1355,7 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
     };
     auto g_req = [&](const int (&rows)[CH], d2 (&g)[CH]) {
 #pragma unroll
-        for (int t = 0; t < CH; ++t) g[t] = *reinterpret_cast<const d2*>(Gp + (rows[t] * gs + rc));
+        for (int t = 0; t < CH; ++t) g[t] = *reinterpret_cast<const d2*>(Gp + (wadr(rows[t]) + rc));   // rows[]: entries of wrow_s
     };
     auto g_load = [&](int l0, d2 (&g)[CH]) {
         // row indices straight from the position-distributed register (v_readlane -> scalar address part): the LDS copy wrow_s cost a
@@ -1458,7 +1482,7 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
             if (pos < cap2) S[pos * M::WL + k] = bv;
         }
         if (pos == k) { wrow = j; wsd = sd; wbnd = bval; lam = mu; }
-        if (lane == 0) wrow_s[k] = j;
+        if (lane == 0) wrow_s[k] = woff(j);   // (j is wave-uniform: a scalar multiply, once per add)
         if (r0 == j) { act0 = true; bnd0 = bval; }
         if (r1 == j) { act1 = true; bnd1 = bval; }
         k += 1;
@@ -1502,7 +1526,7 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
                 const int lrow = __builtin_amdgcn_readlane(wrow, last), lsd = __builtin_amdgcn_readlane(wsd, last);
                 const double lbv = readlane_d(wbnd, last), llam = readlane_d(lam, last);
                 if (pos == rp) { wrow = lrow; wsd = lsd; wbnd = lbv; lam = llam; }
-                if (lane == 0) wrow_s[rp] = lrow;
+                if (lane == 0) wrow_s[rp] = woff(lrow);
             }
             // position `last` returns to the zero padding
 #pragma unroll
@@ -1529,7 +1553,7 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
                 const int lrow = __builtin_amdgcn_readlane(wrow, last), lsd = __builtin_amdgcn_readlane(wsd, last);
                 const double lbv = readlane_d(wbnd, last), llam = readlane_d(lam, last);
                 if (pos == rp) { wrow = lrow; wsd = lsd; wbnd = lbv; lam = llam; }
-                if (lane == 0) wrow_s[rp] = lrow;
+                if (lane == 0) wrow_s[rp] = woff(lrow);
             }
             {   // position `last` returns to the identity padding
                 const double iv = (pos == last) ? 1.0 : 0.0;
@@ -1697,7 +1721,7 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
                     put_rows(s0 > 0 ? hi0 : lo0, s1 > 0 ? hi1 : lo1);
                     wbnd = lane < k0 ? rowbuf[wrow] : 0.0;
                     lam = 0.0;
-                    wrow_s[lane] = wrow;
+                    wrow_s[lane] = woff(wrow);
                     const double* src = GL(p.sglobal) + (size_t)inst * POLISH_GLB_PER_INST;
                     if (Sg != src) {
                         for (int c = 0; c < 64; c += 8) {
@@ -1731,12 +1755,12 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
         // cheaper than one down-date per row; the primal active-set loop below starts from a feasible point and a
         // working set either way, so its finite termination does not depend on this shortcut).
         for (int pass = 0; pass < 2; ++pass) {
-        if (lane < 32) wrow_s[lane] = (lane < k) ? wrow : 0;
+        if (lane < 32) wrow_s[lane] = (lane < k) ? woff(wrow) : 0;
         // K = G[W,W] into the leading k x k block of the (zero padded) register Sinv
         {
             double gv[16];
 #pragma unroll
-            for (int t = 0; t < 16; ++t) gv[t] = Gp[wrow_s[16 * hhf + t] * gs + wrow];
+            for (int t = 0; t < 16; ++t) gv[t] = Gp[wadr(wrow_s[16 * hhf + t]) + wrow];
 #pragma unroll
             for (int t = 0; t < 16; ++t) Sr[t] = (16 * hhf + t < k && pos < k) ? gv[t] : 0.0;
         }
@@ -1892,7 +1916,7 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
                 roll_load<ROLL_SMX, ROLL_NX>(GL(p.rollM), lane, cu, cx);
             }
             // blocked rollout: e_u goes to LDS in stage order (= row order), zero padded to whole blocks
-            const int m0 = r0 % m, m1 = (m0 + 1 == m) ? 0 : m0 + 1;
+            const int m0 = im0, m1 = im1;
             double e0 = 0.0, e1 = 0.0;
             if (in0) {
                 const double uu = fmin(fmax(wout[0] * dvp[0] + ur0, shc[SL.off_umin + m0]), shc[SL.off_umax + m0]);
@@ -1942,7 +1966,7 @@ __device__ __forceinline__ void polish_body(const PolishParams& p_arg, double* s
             ALMPC_STAMP(inst, 14);
             return;
         }
-        const int m0 = r0 % m, m1 = (m0 + 1 == m) ? 0 : m0 + 1, k0s = r0 / m, k1s = (m0 + 1 == m) ? k0s + 1 : k0s;
+        const int m0 = im0, m1 = im1, k0s = r0 / m, k1s = (m0 + 1 == m) ? k0s + 1 : k0s;
         if (in0) {
             const double uu = fmin(fmax(wout[0] * dvp[0] + ur0, shc[SL.off_umin + m0]), shc[SL.off_umax + m0]);
             GL(rp.u)[(size_t)inst * nz + r0] = uu;
