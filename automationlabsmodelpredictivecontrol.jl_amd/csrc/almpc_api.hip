@@ -163,6 +163,10 @@ struct almpc_handle {
         // until the first solved QP); the stopping test and the exact Hessian take them into the adjoint.  Allocated when the handle has state rows.
         int row_mult = 0;
         DevBuf<double> smu;
+        void reset_keeping_switches() {   // a new setup: everything goes but what the set_* calls chose
+            Sqp fresh; fresh.step_rule = step_rule; fresh.structured_qp = structured_qp; fresh.hessian = hessian; fresh.row_mult = row_mult;
+            *this = std::move(fresh);
+        }
     } sqp;
     // per-step re-linearisation of a black-box Fnn model on the device (almpc_relin_fnn_*, BASELINE configs[3])
     struct Relin : Net {
@@ -2876,6 +2880,11 @@ static FnnParams fnn_params(const almpc_handle* h, const almpc_handle::Net& q) {
     fp.W_in = q.W_in; fp.W_h = q.W_h; fp.b_h = q.b_h; fp.W_out = q.W_out;
     return fp;
 }
+// ... at its points (ppi per group, the strides between groups), with where the Jacobians and the outputs (null: none) go
+static FnnParams fnn_points(FnnParams fp, const double* x, const double* u, int ppi, long xs_group, long us_group, double* A, double* B, double* f) {
+    fp.x = x; fp.u = u; fp.ppi = ppi; fp.xs_group = xs_group; fp.us_group = us_group; fp.A = A; fp.B = B; fp.f = f;
+    return fp;
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Per-step re-linearisation of a black-box Fnn model, resident on the device (BASELINE configs[3]; include/almpc.h).
@@ -3027,90 +3036,80 @@ int almpc_relin_densenet_setup(almpc_handle* h, int H, int L, int activation, co
     return relin_net_setup(h, true, H, L, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, umin, umax, rho, sigma);
 }
 
+// Structured handle (m N beyond the condensed limit, round 5): Jacobians -> the stage records of every instance's own
+// unconstrained problem (k_sgains) -> the stage-wise dual active set (k_sdual), warm-started from the previous step's inputs
+// shifted by one stage when opts->warm_start is set.  No Hessian is formed: the reference's Fnn-LP delegation has no horizon
+// limit (.../fnn/mpc_modeler_implementation_fnn.jl:23-58) and neither has this route.
+static int relin_step_structured(almpc_handle* h, almpc_opts o2) {
+    almpc_handle::Relin& q = h->relin;
+    HIP_TRY(h, launch_sgains(h));   // (every instance)
+    if (h->flags & ALMPC_FLAG_TIMING) HIP_TRY(h, hipEventRecord(q.ev[2], h->stream));
+    h->designed = true;
+    if (!q.have_prev) o2.warm_start = 0;   // (a warm start needs a solved step behind it)
+    const int rc = almpc_calculate_async(h, &o2);
+    if (rc != ALMPC_OK) h->designed = false;
+    return rc;
+}
+
+// Condensed handle (fused: the network's points when the design kernel linearises; design_flags: the flag words the finish left to the caller)
+static int relin_step_condensed(almpc_handle* h, almpc_opts o2, const FnnParams* fused, const int** design_flags) {
+    almpc_handle::Relin& q = h->relin;
+    const int nz = h->nz, nzs = h->nzs;
+    hipStream_t st = h->stream;
+    // 2. the reference's QP for every (A_i, B_i): H_i, F_i, scaling, inverses, V_i; reference-dependent vectors.  A warm step
+    // (opts.warm_start = 1 after a solved step) takes its working-set guess from the previous step's inputs shifted by one stage
+    // instead of an ADMM phase, and the design then needs one inverse (G_i) instead of two
+    const bool warm = o2.warm_start && q.have_prev && o2.polish;
+    const DesignStrides ds = batched_strides(h, h->t_step);
+    const hipError_t e_ = launch_batched_design(h, ds, q.useR, q.useS, q.Q, q.R, q.S, h->rho, h->sigma, warm, fused);
+    if (e_ != hipSuccess) return fail(h, ALMPC_ERR_HIP, std::string("relin design: ") + hipGetErrorString(e_));
+    if (h->mc > 0) HIP_TRY(h, launch_ghat_inst(h, nullptr, nullptr));
+    if (q.useS) {
+        hipLaunchKernelGGL(k_fs_scale, dim3(256), dim3(256), 0, st, h->batch, nz, nzs, q.gS, 0L, h->bD, h->dFS);
+        hipLaunchKernelGGL(k_neg_gm, dim3(1, (unsigned)h->batch), dim3(256), 0, st, nz, nzs, 1, nz, h->bG, h->dFS, h->dV0S, (long)nz * nzs, (long)nz);
+        HIP_TRY(h, hipGetLastError());
+    }
+    if (h->flags & ALMPC_FLAG_TIMING) HIP_TRY(h, hipEventRecord(q.ev[2], st));
+    // 3. the step itself
+    h->designed = true;
+    o2.warm_start = 0;   // (the per-instance ADMM's own warm start is not what a warm step of this pipeline means)
+    // an instance whose design was flagged gets ALMPC_NON_FINITE: by the finish itself when it is polish_body (input box only), else by
+    // a launch of its own behind the step
+    StepMode mode;
+    mode.guess = warm ? Guess::ShiftInputs : Guess::Admm; mode.fold_flag = h->mc == 0 && o2.polish != 0;
+    const int rc = calculate_checked(h, &o2, mode);
+    if (rc != ALMPC_OK) h->designed = false;   // (no step ran on this step's designs: the handle is not left "designed")
+    if (!mode.fold_flag) *design_flags = h->bFlag;
+    return rc;
+}
+
 int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
     if (!h) return ALMPC_ERR_INVALID;
     almpc_handle::Relin& q = h->relin;
     if (!q.ready) return fail(h, ALMPC_ERR_NOT_DESIGNED, "relin_fnn_step before relin_fnn_setup");
     HIP_TRY(h, hipSetDevice(h->device));
-    const int n = h->n, m = h->m, nz = h->nz, nzs = h->nzs;
     hipStream_t st = h->stream;
     const bool timing = (h->flags & ALMPC_FLAG_TIMING) != 0;
     if (timing) HIP_TRY(h, hipEventRecord(q.ev[0], st));
     // 1. Jacobians at (x0_i, u_ref[:,1]) straight into the handle's per-instance model slots
-    FnnParams fp = fnn_params(h, q);
-    fp.x = h->dX0; fp.u = q.ulin; fp.ppi = 1; fp.xs_group = n; fp.us_group = m;
-    fp.A = h->bA; fp.B = h->bB; fp.f = nullptr;
-    if (h->structured) {
-        // Structured handle (m N beyond the condensed limit, round 5): Jacobians -> the stage records of every instance's own
-        // unconstrained problem (k_sgains) -> the stage-wise dual active set (k_sdual), warm-started from the previous step's inputs
-        // shifted by one stage when opts->warm_start is set.  No Hessian is formed: the reference's Fnn-LP delegation has no horizon
-        // limit (.../fnn/mpc_modeler_implementation_fnn.jl:23-58) and neither has this route.
-        HIP_TRY(h, launch_fnn_jacobian(h->sw, fp, q.net, h->num_cus, st));
-        if (timing) HIP_TRY(h, hipEventRecord(q.ev[1], st));
-        if (h->c_step) HIP_TRY(h, launch_model_c2d(h, true));   // the network is x' = net(x, u): its Jacobians are continuous-time
-        if (h->t_step) HIP_TRY(h, launch_relin_dare(h, h->sd.dQ, h->sd.dR));   // every instance's own terminal weight, in front of its records
-        HIP_TRY(h, launch_sgains(h));   // (every instance)
-        if (timing) HIP_TRY(h, hipEventRecord(q.ev[2], st));
-        h->designed = true;
-        almpc_opts o2;
-        almpc_default_opts(&o2);
-        if (opts) o2 = *opts;
-        if (!q.have_prev) o2.warm_start = 0;
-        const int rc = almpc_calculate_async(h, &o2);
-        if (rc != ALMPC_OK) { h->designed = false; return rc; }
-        q.have_prev = true;
-        if (h->c_step) {   // an instance whose discretisation failed leaves with ALMPC_NON_FINITE
-            hipLaunchKernelGGL(k_flag_to_status, dim3((h->batch + 255) / 256), dim3(256), 0, st, h->batch, (const int*)h->cStat.get(), h->dStatus);
-            HIP_TRY(h, hipGetLastError());
-        }
-        if (timing) HIP_TRY(h, hipEventRecord(q.ev[3], st));
-        return ALMPC_OK;
-    }
-    // (the design kernel's workgroups linearise their own instance -- unless every instance's terminal weight is the DARE solution of
-    // its Jacobians, almpc_set_terminal_weight: P_i has to be there before the design, so the Jacobians get their own launch in front;
+    const FnnParams fp = fnn_points(fnn_params(h, q), h->dX0, q.ulin, 1, h->n, h->m, h->bA, h->bB, nullptr);
+    // (the condensed design kernel's workgroups linearise their own instance -- unless every instance's terminal weight is the DARE solution
+    // of its Jacobians, almpc_set_terminal_weight: P_i has to be there before the design, so the Jacobians get their own launch in front;
     // the same when the Jacobians are continuous-time and k_c2d stands between them and the design, almpc_set_model_time)
-    const bool fuse_jac = design_fuses_fnn(h, q.H, q.L, q.net) && !h->t_step && !h->c_step;
+    const bool fuse_jac = !h->structured && design_fuses_fnn(h, q.H, q.L, q.net) && !h->t_step && !h->c_step;
     if (!fuse_jac) HIP_TRY(h, launch_fnn_jacobian(h->sw, fp, q.net, h->num_cus, st));
     if (timing) HIP_TRY(h, hipEventRecord(q.ev[1], st));
-    if (h->c_step) HIP_TRY(h, launch_model_c2d(h, true));
-    if (h->t_step) HIP_TRY(h, launch_relin_dare(h, q.Q, q.R));
-    // 2. the reference's QP for every (A_i, B_i): H_i, F_i, scaling, inverses, V_i; reference-dependent vectors.  A warm step
-    // (opts.warm_start = 1 after a solved step) takes its working-set guess from the previous step's inputs shifted by one stage
-    // instead of an ADMM phase, and the design then needs one inverse (G_i) instead of two
-    const bool warm = opts && opts->warm_start && q.have_prev && (!opts || opts->polish);
-    const DesignStrides ds = batched_strides(h, h->t_step);
-    {
-        const hipError_t e_ = launch_batched_design(h, ds, q.useR, q.useS, q.Q, q.R, q.S, h->rho, h->sigma, warm, fuse_jac ? &fp : nullptr);
-        if (e_ != hipSuccess) return fail(h, ALMPC_ERR_HIP, std::string("relin design: ") + hipGetErrorString(e_));
-    }
-    if (h->mc > 0) HIP_TRY(h, launch_ghat_inst(h, nullptr, nullptr));
-    if (q.useS) {
-        hipLaunchKernelGGL(k_fs_scale, dim3(256), dim3(256), 0, st, h->batch, nz, nzs, q.gS, 0L, h->bD, h->dFS);
-        hipLaunchKernelGGL(k_neg_gm, dim3(1, (unsigned)h->batch), dim3(256), 0, st, nz, nzs, 1, nz, h->bG, h->dFS, h->dV0S,
-                           (long)nz * nzs, (long)nz);
-        HIP_TRY(h, hipGetLastError());
-    }
-    if (timing) HIP_TRY(h, hipEventRecord(q.ev[2], st));
-    // 3. the step itself
-    h->designed = true;
-    almpc_opts o2;
-    almpc_default_opts(&o2);
+    if (h->c_step) HIP_TRY(h, launch_model_c2d(h, true));   // the network is x' = net(x, u): its Jacobians are continuous-time
+    if (h->t_step) HIP_TRY(h, launch_relin_dare(h, h->structured ? h->sd.dQ : q.Q, h->structured ? h->sd.dR : q.R));   // every instance's own P_i, from the route's Q and R
+    almpc_opts o2; almpc_default_opts(&o2);   // the options of the step inside: the caller's; each route sets the solver's own warm start by its rule
     if (opts) o2 = *opts;
-    o2.warm_start = 0;   // (the per-instance ADMM's own warm start is not what a warm step of this pipeline means)
-    // an instance whose design was flagged gets ALMPC_NON_FINITE: by the finish itself when it is polish_body (input box only), else by
-    // a launch of its own behind the step
-    StepMode mode;
-    mode.guess = warm ? Guess::ShiftInputs : Guess::Admm;
-    mode.fold_flag = h->mc == 0 && o2.polish != 0;
-    const int rc = calculate_checked(h, &o2, mode);
-    if (rc != ALMPC_OK) { h->designed = false; return rc; }   // (no step ran on this step's designs: the handle is not left "designed")
+    const int* design_flags = nullptr;
+    ALMPC_TRY(h->structured ? relin_step_structured(h, o2) : relin_step_condensed(h, o2, fuse_jac ? &fp : nullptr, &design_flags));
+    // solved; the instances of design_flags and those whose discretisation failed (their model slots hold NaN) leave with ALMPC_NON_FINITE
     q.have_prev = true;
-    if (!mode.fold_flag) {
-        hipLaunchKernelGGL(k_flag_to_status, dim3((h->batch + 255) / 256), dim3(256), 0, st, h->batch, h->bFlag, h->dStatus);
-        HIP_TRY(h, hipGetLastError());
-    }
-    if (h->c_step) {   // an instance whose discretisation failed (its model slots hold NaN) leaves with ALMPC_NON_FINITE
-        hipLaunchKernelGGL(k_flag_to_status, dim3((h->batch + 255) / 256), dim3(256), 0, st, h->batch, (const int*)h->cStat.get(), h->dStatus);
+    for (const int* flags : {design_flags, h->c_step ? (const int*)h->cStat.get() : nullptr}) {
+        if (!flags) continue;
+        hipLaunchKernelGGL(k_flag_to_status, dim3((h->batch + 255) / 256), dim3(256), 0, st, h->batch, flags, h->dStatus);
         HIP_TRY(h, hipGetLastError());
     }
     if (timing) HIP_TRY(h, hipEventRecord(q.ev[3], st));
@@ -3118,8 +3117,7 @@ int almpc_relin_fnn_step_async(almpc_handle* h, const almpc_opts* opts) {
 }
 
 int almpc_relin_fnn_step(almpc_handle* h, const almpc_opts* opts) {
-    const int rc = almpc_relin_fnn_step_async(h, opts);
-    if (rc != ALMPC_OK) return rc;
+    ALMPC_TRY(almpc_relin_fnn_step_async(h, opts));
     return almpc_synchronize(h);
 }
 
@@ -3137,12 +3135,10 @@ int almpc_relin_fnn_advance(almpc_handle* h) {
     hipStream_t st = h->stream;
     const size_t cnt = (size_t)h->batch * m;
     hipLaunchKernelGGL(k_pack_first_input, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, h->batch, m, h->N, h->dU, q.u0);
-    FnnParams fp = fnn_params(h, q);
-    fp.x = h->dX0; fp.u = q.u0; fp.ppi = 1; fp.xs_group = n; fp.us_group = m;
     // (the Jacobians of the forward pass go to a scratch of their own: the model slots keep the last step's linearisations, which a
     // lazily deferred redo of that step still needs)
     HIP_TRY(h, q.Ascr.once((size_t)h->batch * n * n)); HIP_TRY(h, q.Bscr.once((size_t)h->batch * n * m));
-    fp.A = q.Ascr; fp.B = q.Bscr; fp.f = q.xnext;
+    const FnnParams fp = fnn_points(fnn_params(h, q), h->dX0, q.u0, 1, n, m, q.Ascr, q.Bscr, q.xnext);
     HIP_TRY(h, launch_fnn_jacobian(h->sw, fp, q.net, h->num_cus, st));
     if (h->io.x0_slot >= 0) {   // a pinned x0 slot was read once more by the forward pass: free for the host only after it
         HIP_TRY(h, hipEventRecord(h->io.ev_used[h->io.x0_slot], st));
@@ -3214,12 +3210,7 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
     } else
         ALMPC_TRY(ensure_batched_alloc(h));
     almpc_handle::Sqp& q = h->sqp;
-    const int keep_rule = q.step_rule, keep_structured = q.structured_qp, keep_hessian = q.hessian, keep_rows = q.row_mult;
-    q = almpc_handle::Sqp();
-    q.step_rule = keep_rule;
-    q.structured_qp = keep_structured;
-    q.hessian = keep_hessian;
-    q.row_mult = keep_rows;
+    q.reset_keeping_switches();
     h->dXref.reset(); h->dUref.reset(); h->dFS.reset(); h->dV0S.reset(); h->dCold.reset(); h->cold_ref = false;
     h->ref_keep = false;
     std::vector<double> xr((size_t)n * (N + 1), 0.0), ur((size_t)nz, 0.0);
@@ -3296,15 +3287,13 @@ int almpc_sqp_fnn_setup(almpc_handle* h, int H, int L, int activation, const dou
                         const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
                         const double* S, const double* P, int P_per_instance, const double* umin, const double* umax, double rho,
                         double sigma) {
-    return sqp_net_setup(h, false, H, L, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, P_per_instance, umin, umax, rho,
-                         sigma);
+    return sqp_net_setup(h, false, H, L, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, P_per_instance, umin, umax, rho, sigma);
 }
 int almpc_sqp_densenet_setup(almpc_handle* h, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
                              const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
                              const double* S, const double* P, int P_per_instance, const double* umin, const double* umax, double rho,
                              double sigma) {
-    return sqp_net_setup(h, true, H, L, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, P_per_instance, umin, umax, rho,
-                         sigma);
+    return sqp_net_setup(h, true, H, L, activation, W_in, W_h, b_h, W_out, xref, uref, Q, R, S, P, P_per_instance, umin, umax, rho, sigma);
 }
 
 // The row multipliers' buffer, once the switch is on and the handle has state rows (zero: no QP solved yet)
@@ -3328,20 +3317,18 @@ int almpc_sqp_fnn_start(almpc_handle* h, const double* x0, const double* u_guess
     HIP_TRY(h, hipStreamSynchronize(st));
     io_release_x0(h);
     HIP_TRY(h, hipMemcpy(h->dX0, x0, b * n * sizeof(double), hipMemcpyHostToDevice));
-    if (u_guess) {
-        std::vector<double> ug(u_guess, u_guess + b * nz), lo(m), hi(m);
-        HIP_TRY(h, hipMemcpy(lo.data(), h->dUmin, m * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(h, hipMemcpy(hi.data(), h->dUmax, m * sizeof(double), hipMemcpyDeviceToHost));
-        for (size_t t = 0; t < ug.size(); ++t) ug[t] = std::min(std::max(ug[t], lo[t % m]), hi[t % m]);
-        HIP_TRY(h, hipMemcpy(h->dUref, ug.data(), ug.size() * sizeof(double), hipMemcpyHostToDevice));
-    } else {  // the input reference, clipped to the box
-        std::vector<double> ur(nz), lo(m), hi(m), ug(b * nz);
+    // the start: the caller's guess or the input reference, clipped to the box
+    std::vector<double> ug(b * nz), lo(m), hi(m);
+    if (u_guess) ug.assign(u_guess, u_guess + b * nz);
+    else {
+        std::vector<double> ur(nz);
         HIP_TRY(h, hipMemcpy(ur.data(), q.uref, nz * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(h, hipMemcpy(lo.data(), h->dUmin, m * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(h, hipMemcpy(hi.data(), h->dUmax, m * sizeof(double), hipMemcpyDeviceToHost));
-        for (size_t t = 0; t < ug.size(); ++t) ug[t] = std::min(std::max(ur[t % nz], lo[t % m]), hi[t % m]);
-        HIP_TRY(h, hipMemcpy(h->dUref, ug.data(), ug.size() * sizeof(double), hipMemcpyHostToDevice));
+        for (size_t t = 0; t < ug.size(); ++t) ug[t] = ur[t % nz];
     }
+    HIP_TRY(h, hipMemcpy(lo.data(), h->dUmin, m * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(hi.data(), h->dUmax, m * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t t = 0; t < ug.size(); ++t) ug[t] = std::min(std::max(ug[t], lo[t % m]), hi[t % m]);
+    HIP_TRY(h, hipMemcpy(h->dUref, ug.data(), ug.size() * sizeof(double), hipMemcpyHostToDevice));
     FnnRolloutParams rp;
     rp.n = n; rp.m = m; rp.H = q.H; rp.L = q.L; rp.act = q.act; rp.N = N;
     rp.W_in = q.W_in; rp.W_h = q.W_h; rp.b_h = q.b_h; rp.W_out = q.W_out; rp.x0 = h->dX0; rp.ubar = h->dUref; rp.xbar = h->dXref;
@@ -3353,14 +3340,11 @@ int almpc_sqp_fnn_start(almpc_handle* h, const double* x0, const double* u_guess
     HIP_TRY(h, hipMemsetAsync(q.bad, 0, b * sizeof(int), st));
     ALMPC_TRY(sqp_rows_buffer(h));
     if (q.smu) HIP_TRY(h, hipMemsetAsync(q.smu, 0, b * N * (size_t)n * sizeof(double), st));   // (no QP solved yet)
-    {
-        std::vector<double> d0(4 * b, 0.0);
-        for (size_t i = 0; i < b; ++i) { d0[4 * i] = 1.0; d0[4 * i + 1] = std::numeric_limits<double>::infinity(); }
-        HIP_TRY(h, hipMemcpyAsync(q.mer, d0.data(), d0.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-    }
-    q.started = true;
-    q.since_start = 0;
+    std::vector<double> d0(4 * b, 0.0);
+    for (size_t i = 0; i < b; ++i) { d0[4 * i] = 1.0; d0[4 * i + 1] = std::numeric_limits<double>::infinity(); }
+    HIP_TRY(h, hipMemcpyAsync(q.mer, d0.data(), d0.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    q.started = true; q.since_start = 0;
     return ALMPC_OK;
 }
 
@@ -3372,9 +3356,6 @@ struct SqpSolveCtl {
     int* live_pin;                        // pinned [4]
     hipEvent_t ev[4];
 };
-
-static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_opts* opts, double* step_inf, double* defect_inf,
-                    const SqpSolveCtl* sv);
 
 // what the exact-Hessian mode covers: the condensed route, smooth activations, nz <= 128, the per-wave LDS scratch of k_fnn_lag_hessian
 // within 64 KB for four waves; state rows only with their multipliers handed out (almpc_sqp_fnn_set_row_multipliers) and the stage-wise
@@ -3393,6 +3374,213 @@ static int sqp_exact_check(almpc_handle* h) {
                                                   " network's per-wave scratch (its activation sites' Jacobians) must fit 16 KB of LDS");
     if (sqp_exact_lds_doubles(h->n, h->m, h->nz) * sizeof(double) > 64 * 1024)
         return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp exact Hessian: the network / stage scratch must fit 64 KB of LDS");
+    return ALMPC_OK;
+}
+
+// k_sqp_prepare's and k_sqp_step's
+static SqpParams sqp_step_params(const almpc_handle* h, double step_scale, const SqpSolveCtl* sv) {
+    const almpc_handle::Sqp& q = h->sqp;
+    SqpParams sp;
+    sp.n = h->n; sp.m = h->m; sp.N = h->N; sp.nz = h->nz; sp.batch = h->batch; sp.useR = q.useR; sp.useS = q.useS;
+    sp.xref = q.xref; sp.uref = q.uref; sp.R = q.R; sp.S = q.S; sp.umin = h->dUmin; sp.umax = h->dUmax;
+    sp.xbar = h->dXref; sp.ubar = h->dUref; sp.fval = q.fval; sp.A = q.A; sp.B = q.B; sp.c = q.c; sp.ebar = q.ebar; sp.qadd = q.qadd;
+    sp.v = h->dEu; sp.flag = h->bFlag; sp.status = h->dStatus; sp.bad = q.bad; sp.stats = q.stats; sp.step_scale = step_scale;
+    sp.x = h->dX; sp.ex = h->dEx; sp.u = h->dU; sp.eu = h->dEu; sp.adaptive = q.step_rule; sp.mu = q.mu; sp.Q = q.Q; sp.P = h->bP; sp.sP = q.sP; sp.mer = q.mer;
+    sp.xback = q.xback; sp.uback = q.uback; sp.dxback = q.dxback; sp.vback = q.vback;
+    if (sv) { sp.done = sv->done; sp.verdict = sv->verdict; }
+    return sp;
+}
+// What the iterations of one call launch with, made once by sqp_plan: the route decisions, the LDS sizes and every kernel's parameters
+struct SqpCall {
+    const almpc_opts* opts; const SqpSolveCtl* sv;
+    bool exact = false, ltv_scales = false, prep_in_design = false; size_t step_lds = 0, hess_lds = 0, exact_lds = 0;
+    RowMultOut rows; DesignStrides ds; FnnParams fp; SqpParams sp; SqpKktParams kp; DesignLtvParams lp; FnnHessParams hp; SqpExactParams xp;
+};
+static int sqp_plan(almpc_handle* h, double step_scale, SqpCall& c) {
+    almpc_handle::Sqp& q = h->sqp;
+    const SqpSolveCtl* sv = c.sv;
+    const int n = h->n, m = h->m, N = h->N, nz = h->nz;
+    const size_t b = (size_t)h->batch;
+    c.ds = batched_strides(h, q.sP != 0);
+    c.step_lds = sqp_step_lds_doubles(n, m, N) * sizeof(double);
+    if (c.step_lds > 64 * 1024) HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sqp_step), (size_t)(c.step_lds)));
+    c.fp = fnn_points(fnn_params(h, q), h->dXref, h->dUref, N, (long)n * (N + 1), nz, q.A, q.B, q.fval);
+    c.fp.batch = (int)(b * N);   // (every stage of every instance is a point)
+    c.sp = sqp_step_params(h, step_scale, sv);
+    if (sv && c.step_lds > 64 * 1024) HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sqp_kkt), (size_t)(c.step_lds)));
+    // state rows with almpc_sqp_fnn_set_row_multipliers: whichever finish decides an instance's QP hands its row multipliers out, and the
+    // adjoint walk of k_sqp_kkt (the stopping test, the multipliers of the exact Hessian) takes them in
+    if (q.row_mult && h->mc > 0) {
+        if (q.structured_qp)
+            return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp row multipliers: the condensed QP route only (the stage-wise route of "
+                                                  "almpc_sqp_fnn_set_structured / ALMPC_FLAG_STRUCTURED does not hand them out)");
+        ALMPC_TRY(sqp_rows_buffer(h));
+        c.rows.mu = q.smu; c.rows.done = sv ? sv->done : nullptr; c.rows.mer = q.step_rule ? q.mer : nullptr;
+    }
+    DesignLtvParams& lp = c.lp;
+    lp.n = n; lp.m = m; lp.N = N; lp.nz = nz; lp.useR = q.useR; lp.useS = q.useS;
+    lp.A = q.A; lp.B = q.B; lp.c = q.c; lp.ebar = q.ebar; lp.P = h->bP; lp.sP = q.sP; lp.Q = q.Q; lp.R = q.R; lp.S = q.S;
+    lp.qadd = q.qadd; lp.H = h->bH; lp.q = h->bQ;
+    c.exact = q.hessian == 1;
+    if (c.exact) {
+        ALMPC_TRY(sqp_exact_check(h));
+        HIP_TRY(h, q.lam.once(b * N * (size_t)n)); HIP_TRY(h, q.Wlag.once(b * N * (size_t)(n + m) * (n + m)));
+        if (!sv && c.step_lds > 64 * 1024) HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sqp_kkt), (size_t)(c.step_lds)));
+        FnnHessParams& hp = c.hp; SqpExactParams& xp = c.xp;
+        hp.n = n; hp.m = m; hp.H = q.H; hp.L = q.L; hp.act = q.act; hp.N = N; hp.batch = h->batch;
+        hp.W_in = q.W_in; hp.W_h = q.W_h; hp.b_h = q.b_h; hp.W_out = q.W_out; hp.xbar = h->dXref; hp.ubar = h->dUref; hp.lam = q.lam;
+        hp.done = sv ? sv->done : nullptr; hp.W = q.Wlag;
+        xp.n = n; xp.m = m; xp.N = N; xp.nz = nz; xp.A = q.A; xp.B = q.B; xp.c = q.c; xp.W = q.Wlag; xp.ubar = h->dUref;
+        xp.umin = h->dUmin; xp.umax = h->dUmax; xp.done = sv ? sv->done : nullptr; xp.H = h->bH; xp.q = h->bQ;
+        c.hess_lds = 4 * fnn_hess_wave_doubles(n, m, q.H, q.L, q.net) * sizeof(double); c.exact_lds = sqp_exact_lds_doubles(n, m, nz) * sizeof(double);
+    }
+    if (sv || c.exact) {   // k_sqp_kkt: the stopping test of almpc_sqp_fnn_solve, or (sv null) the multipliers only: its adjoint walk without the test
+        SqpKktParams& kp = c.kp;
+        kp.n = n; kp.m = m; kp.N = N; kp.nz = nz; kp.useS = q.useS;
+        kp.xref = q.xref; kp.uref = q.uref; kp.Q = q.Q; kp.R = q.R; kp.S = q.S; kp.P = h->bP; kp.sP = q.sP;
+        kp.umin = h->dUmin; kp.umax = h->dUmax; kp.xbar = h->dXref; kp.ubar = h->dUref; kp.fval = q.fval; kp.A = q.A; kp.B = q.B;
+        kp.tol = sv ? sv->tol : 0.0; kp.it = 0;
+        kp.done = sv ? sv->done : nullptr; kp.iters = sv ? sv->iters : nullptr; kp.kkt = sv ? sv->kkt : nullptr; kp.live = sv ? sv->live : nullptr;
+        if (c.exact) kp.lam = q.lam;
+        if (c.rows.mu) { kp.mu = q.smu; kp.term_eq = h->terminal_eq ? 1 : 0; }
+        if (c.rows.mu && h->has_box) { kp.xmin = h->dXmin; kp.xmax = h->dXmax; }
+    }
+    // register-tile design kernel: scaling, scaled gradient and the flag reset ride along as its tail (three launches less per iteration)
+    // (not in exact mode: k_sqp_exact_qp changes H and q after the design, the factor then scales them)
+    c.ltv_scales = !c.exact && ltv_reg_path(h) && nz <= 128 && !q.structured_qp && !h->sw.dbg_split_scale;
+    if (c.ltv_scales) { lp.sc_d = h->bD; lp.sc_Hs = h->bHs; lp.sc_fS = h->dFS; lp.sc_flag = h->bFlag; lp.nzs = h->nzs; }
+    // ... and k_sqp_prepare as its head (its outputs are that kernel's inputs): a fourth launch less
+    c.prep_in_design = c.ltv_scales && !h->sw.dbg_split_prepare;
+    if (c.prep_in_design) { lp.prep_on = 1; lp.prep = c.sp; }
+    return ALMPC_OK;
+}
+
+// Jacobians and network outputs at the iterate (into q.A, q.B, q.fval); the stopping test at the top of iteration `it`, its live count into
+// the pinned ring; unless `last`: the exact mode's multipliers (from the test, or the walk alone) and Hessians, the stage data, the flag reset
+static int sqp_linearise(almpc_handle* h, const SqpCall& c, int it, bool last) {
+    const almpc_handle::Sqp& q = h->sqp;
+    const size_t b = (size_t)h->batch;
+    hipStream_t st = h->stream;
+    HIP_TRY(h, launch_fnn_jacobian(h->sw, c.fp, q.net, h->num_cus, st));
+    if (c.sv || (c.exact && !last)) {
+        SqpKktParams kp = c.kp; kp.it = c.sv ? it : 0;
+        hipLaunchKernelGGL(k_sqp_kkt, dim3((unsigned)b), dim3(256), c.step_lds, st, kp);
+    }
+    if (c.sv) {
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(c.sv->live_pin + (it & 3), c.sv->live, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipEventRecord(c.sv->ev[it & 3], st));
+    }
+    if (last) return ALMPC_OK;
+    if (c.exact) {
+        void (*hk)(FnnHessParams) = with_net(q.net, [](auto k) { return k_fnn_lag_hessian<k>; });
+        hipLaunchKernelGGL(hk, dim3((unsigned)((b * h->N + 3) / 4)), dim3(256), c.hess_lds, st, c.hp);
+        HIP_TRY(h, hipGetLastError());
+    }
+    if (!c.prep_in_design) hipLaunchKernelGGL(k_sqp_prepare, dim3((unsigned)b), dim3(256), 0, st, c.sp);
+    if (!c.ltv_scales) HIP_TRY(h, hipMemsetAsync(h->bFlag, 0, b * sizeof(int), st));
+    return ALMPC_OK;
+}
+
+// The QP in its stage-wise form for every instance; start: v = 0 (working set = the iterate's inputs on a bound)
+static int sqp_qp_stagewise(almpc_handle* h, const SqpCall& c) {
+    const almpc_handle::Sqp& q = h->sqp;
+    h->designed = true;
+    // input box without S: the primal Riccati active set (an iterate of this loop has about half of its inputs on a bound: rows a
+    // primal method holds at no cost, while the dual one pays a sweep per row of its start -- measured 0.56 against 3.1 ms per
+    // iteration at the configs[4] shape); with state rows / S: k_sgains + k_sdual
+    SolveCall qp;
+    qp.guess = h->dUref; qp.max_iter = c.opts ? c.opts->polish_max_iter : 0;
+    if (h->mc == 0 && !q.useS && h->rKst) {
+        qp.filter = FILTER_SQP_ALL;
+        HIP_TRY(h, launch_riccati(h, qp));
+    } else if (h->sd.ready) {
+        qp.first_tier = h->nz > 48 ? 1 : 0;
+        HIP_TRY(h, launch_sgains(h));
+        HIP_TRY(h, launch_sdual(h, qp));
+    } else
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_iterate: no stage-wise QP solver for this design");
+    return ALMPC_OK;
+}
+
+// The condensed QP: design, exact H and q, factor, constraint-space matrix, scaled gradient, v0, step; behind it the redo of the flagged
+static int sqp_qp_condensed(almpc_handle* h, const SqpCall& c) {
+    const almpc_handle::Sqp& q = h->sqp;
+    const int nz = h->nz, nzs = h->nzs;
+    const size_t b = (size_t)h->batch;
+    hipStream_t st = h->stream;
+    HIP_TRY(h, launch_design_ltv(h, c.lp, st));
+    if (c.exact) {   // H, q of the exact QP (an instance whose result is not positive definite is flagged by the factor and, with the
+                     // structured fallback on, takes the Gauss-Newton QP in its stage-wise form)
+        hipLaunchKernelGGL(k_sqp_exact_qp, dim3((unsigned)b), dim3(256), c.exact_lds, st, c.xp);
+        HIP_TRY(h, hipGetLastError());
+    }
+    StepMode mode;
+    mode.guess = (!h->sw.sqp_admm_always && q.since_start > 0) ? Guess::FromIterate : Guess::Admm; mode.rows = c.rows;
+    // (with the scaling in the design kernel's tail fS_i exists before the inverse: v0S_i = -G_i fS_i comes out of the inverse's launch)
+    const bool v0_in_inverse = c.ltv_scales && design_inverse_makes_v(h->sw, nz);
+    launch_batched_factor(h, c.ds, h->rho, h->sigma, st, mode.guess != Guess::Admm, c.ltv_scales, false, v0_in_inverse ? h->dFS : nullptr, h->dV0S);
+    if (h->mc > 0) HIP_TRY(h, launch_ghat_inst(h, q.A, q.B));
+    if (!c.ltv_scales) hipLaunchKernelGGL(k_fs_scale, dim3(256), dim3(256), 0, st, h->batch, nz, nzs, h->bQ, (long)nz, h->bD, h->dFS);
+    if (!v0_in_inverse) hipLaunchKernelGGL(k_neg_gm, dim3(1, (unsigned)b), dim3(256), 0, st, nz, nzs, 1, nz, h->bG, h->dFS, h->dV0S, (long)nz * nzs, (long)nz);
+    HIP_TRY(h, hipGetLastError());
+    h->designed = true;
+    ALMPC_TRY(calculate_checked(h, c.opts, mode));
+    // structured fallback: an instance whose condensed Hessian came out indefinite to working precision (open-loop unstable
+    // linearisation over the horizon) or whose QP was left unsolved gets this iteration's QP solved in its stage-wise form
+    if (!h->fallback) return ALMPC_OK;
+    // input box without S: the primal Riccati active set alone -- the solver this loop's stage-wise QP route uses for such problems
+    // (an iterate holds half of its inputs on bounds; a saturated unstable linearisation is where the dual method has no
+    // certificate) --, ONE idle launch per iteration instead of three; with state rows / S: k_sgains + k_sdual
+    const bool primal_only = h->mc == 0 && !q.useS && h->rKst && !h->sw.sqp_redo_dual_first;
+    SolveCall flagged;
+    flagged.filter = FILTER_SQP_FLAGGED; flagged.single_launch = true; flagged.rows = c.rows;   // (the last two: k_sdual's)
+    if (h->sd.ready && !primal_only) { HIP_TRY(h, launch_sgains(h, flagged)); HIP_TRY(h, launch_sdual(h, flagged)); }
+    if (h->mc == 0 && !q.useS && h->rKst) HIP_TRY(h, launch_riccati(h, flagged));
+    return ALMPC_OK;
+}
+
+static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_opts* opts, double* step_inf, double* defect_inf,
+                    const SqpSolveCtl* sv) {
+    almpc_handle::Sqp& q = h->sqp;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    if (q.stats && q.stats.size() < (size_t)2 * iters) HIP_TRY(h, hipStreamSynchronize(st));   // (the buffer is replaced: its last reader first)
+    HIP_TRY(h, q.stats.grow((size_t)2 * std::max(iters, 1)));
+    HIP_TRY(h, hipMemsetAsync(q.stats, 0, (size_t)2 * iters * sizeof(unsigned long long), st));
+    SqpCall c; c.opts = opts; c.sv = sv;
+    ALMPC_TRY(sqp_plan(h, step_scale, c));
+    bool all_done = false;
+    for (int it = 0; it < iters; ++it) {
+        if (sv && it >= 2) {   // every live instance had converged at the top of iteration it - 2: the rest is frozen work
+            HIP_TRY(h, hipEventSynchronize(sv->ev[(it - 2) & 3]));
+            if (sv->live_pin[(it - 2) & 3] == 0) { all_done = true; break; }
+        }
+        ALMPC_TRY(sqp_linearise(h, c, it, false));
+        ALMPC_TRY(q.structured_qp ? sqp_qp_stagewise(h, c) : sqp_qp_condensed(h, c));
+        q.since_start += 1;   // the update behind either QP route; its step and defect norms go to the iteration's slot of the histories
+        c.sp.stats = q.stats + 2 * it;
+        hipLaunchKernelGGL(k_sqp_step, dim3((unsigned)h->batch), dim3(256), c.step_lds, st, c.sp);
+        HIP_TRY(h, hipGetLastError());
+    }
+    if (sv && !all_done) ALMPC_TRY(sqp_linearise(h, c, iters, true));   // the last test, at the final iterate
+    if (sv) return almpc_synchronize(h);   // (per-instance verdicts instead of ALMPC_ERR_NUMERIC; no histories)
+    // the histories of almpc_sqp_fnn_iterate and its verdict: ALMPC_ERR_NUMERIC names the first instance that skipped an iteration
+    const size_t b = (size_t)h->batch;
+    std::vector<unsigned long long> stats((size_t)2 * iters);
+    std::vector<int> bad(b);
+    HIP_TRY(h, hipMemcpyAsync(stats.data(), q.stats, stats.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(bad.data(), q.bad, b * sizeof(int), hipMemcpyDeviceToHost, st));
+    ALMPC_TRY(almpc_synchronize(h));
+    for (int it = 0; it < iters; ++it) {
+        if (step_inf) std::memcpy(&step_inf[it], &stats[2 * it], 8);
+        if (defect_inf) std::memcpy(&defect_inf[it], &stats[2 * it + 1], 8);
+    }
+    for (size_t i = 0; i < b; ++i)
+        if (bad[i])
+            return fail(h, ALMPC_ERR_NUMERIC, "sqp_fnn_iterate: instance " + std::to_string(i) +
+                        ": an iteration was skipped (condensed Hessian not positive definite to working precision, a non-finite QP "
+                        "solution, or -- with state rows -- an infeasible QP); its iterate is the last good one, the other instances are unaffected");
     return ALMPC_OK;
 }
 
@@ -3456,194 +3644,6 @@ int almpc_sqp_fnn_solve(almpc_handle* h, int max_iters, double tol, const almpc_
         if (iters) iters[i] = w[b + i];
         if (kkt) kkt[i] = r[i];
     }
-    return ALMPC_OK;
-}
-
-static int sqp_loop(almpc_handle* h, int iters, double step_scale, const almpc_opts* opts, double* step_inf, double* defect_inf,
-                    const SqpSolveCtl* sv) {
-    almpc_handle::Sqp& q = h->sqp;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int n = h->n, m = h->m, N = h->N, nz = h->nz, nzs = h->nzs;
-    const size_t b = (size_t)h->batch;
-    hipStream_t st = h->stream;
-    if (q.stats && q.stats.size() < (size_t)2 * iters) HIP_TRY(h, hipStreamSynchronize(st));   // (the buffer is replaced: its last reader first)
-    HIP_TRY(h, q.stats.grow((size_t)2 * std::max(iters, 1)));
-    HIP_TRY(h, hipMemsetAsync(q.stats, 0, (size_t)2 * iters * sizeof(unsigned long long), st));
-    const DesignStrides ds = batched_strides(h, q.sP != 0);
-    const size_t step_lds = sqp_step_lds_doubles(n, m, N) * sizeof(double);
-    if (step_lds > 64 * 1024) HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sqp_step), (size_t)(step_lds)));
-    FnnParams fp = fnn_params(h, q);
-    fp.batch = (int)(b * N);   // (every stage of every instance is a point)
-    fp.x = h->dXref; fp.u = h->dUref; fp.ppi = N; fp.xs_group = (long)n * (N + 1); fp.us_group = nz;
-    fp.A = q.A; fp.B = q.B; fp.f = q.fval;
-    SqpParams sp;
-    sp.n = n; sp.m = m; sp.N = N; sp.nz = nz; sp.batch = h->batch; sp.useR = q.useR; sp.useS = q.useS;
-    sp.xref = q.xref; sp.uref = q.uref; sp.R = q.R; sp.S = q.S; sp.umin = h->dUmin; sp.umax = h->dUmax;
-    sp.xbar = h->dXref; sp.ubar = h->dUref; sp.fval = q.fval; sp.A = q.A; sp.B = q.B; sp.c = q.c; sp.ebar = q.ebar; sp.qadd = q.qadd;
-    sp.v = h->dEu; sp.flag = h->bFlag; sp.status = h->dStatus; sp.bad = q.bad; sp.stats = q.stats; sp.step_scale = step_scale;
-    sp.x = h->dX; sp.ex = h->dEx; sp.u = h->dU; sp.eu = h->dEu; sp.adaptive = q.step_rule; sp.mu = q.mu; sp.Q = q.Q; sp.P = h->bP; sp.sP = q.sP; sp.mer = q.mer;
-    sp.xback = q.xback; sp.uback = q.uback; sp.dxback = q.dxback; sp.vback = q.vback;
-    SqpKktParams kp;
-    if (sv) {
-        sp.done = sv->done; sp.verdict = sv->verdict;
-        kp.n = n; kp.m = m; kp.N = N; kp.nz = nz; kp.useS = q.useS;
-        kp.xref = q.xref; kp.uref = q.uref; kp.Q = q.Q; kp.R = q.R; kp.S = q.S; kp.P = h->bP; kp.sP = q.sP;
-        kp.umin = h->dUmin; kp.umax = h->dUmax; kp.xbar = h->dXref; kp.ubar = h->dUref; kp.fval = q.fval; kp.A = q.A; kp.B = q.B;
-        kp.tol = sv->tol; kp.it = 0; kp.done = sv->done; kp.iters = sv->iters; kp.kkt = sv->kkt; kp.live = sv->live;
-        if (step_lds > 64 * 1024) HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sqp_kkt), (size_t)(step_lds)));
-    }
-    // the stopping test at the top of iteration `it` (the Jacobians and network outputs at the iterate are in q.A, q.B, q.fval)
-    auto kkt_test = [&](int it) -> hipError_t {
-        kp.it = it;
-        hipLaunchKernelGGL(k_sqp_kkt, dim3((unsigned)b), dim3(256), step_lds, st, kp);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(sv->live_pin + (it & 3), sv->live, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipEventRecord(sv->ev[it & 3], st);
-        return e;
-    };
-    // state rows with almpc_sqp_fnn_set_row_multipliers: whichever finish decides an instance's QP hands its row multipliers out, and the
-    // adjoint walk of k_sqp_kkt (the stopping test, the multipliers of the exact Hessian) takes them in
-    RowMultOut rows;
-    if (q.row_mult && h->mc > 0) {
-        if (q.structured_qp)
-            return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp row multipliers: the condensed QP route only (the stage-wise route of "
-                                                  "almpc_sqp_fnn_set_structured / ALMPC_FLAG_STRUCTURED does not hand them out)");
-        ALMPC_TRY(sqp_rows_buffer(h));
-        rows.mu = q.smu; rows.done = sv ? sv->done : nullptr; rows.mer = q.step_rule ? q.mer : nullptr;
-    }
-    bool all_done = false;
-    DesignLtvParams lp;
-    lp.n = n; lp.m = m; lp.N = N; lp.nz = nz; lp.useR = q.useR; lp.useS = q.useS;
-    lp.A = q.A; lp.B = q.B; lp.c = q.c; lp.ebar = q.ebar; lp.P = h->bP; lp.sP = q.sP; lp.Q = q.Q; lp.R = q.R; lp.S = q.S;
-    lp.qadd = q.qadd; lp.H = h->bH; lp.q = h->bQ;
-    const bool exact = q.hessian == 1;
-    FnnHessParams hp;
-    SqpExactParams xp;
-    size_t hess_lds = 0, exact_lds = 0;
-    if (exact) {
-        ALMPC_TRY(sqp_exact_check(h));
-        HIP_TRY(h, q.lam.once(b * N * (size_t)n)); HIP_TRY(h, q.Wlag.once(b * N * (size_t)(n + m) * (n + m)));
-        if (!sv) {   // the multipliers only: the walk of k_sqp_kkt without the test
-            kp.n = n; kp.m = m; kp.N = N; kp.nz = nz; kp.useS = q.useS;
-            kp.xref = q.xref; kp.uref = q.uref; kp.Q = q.Q; kp.R = q.R; kp.S = q.S; kp.P = h->bP; kp.sP = q.sP;
-            kp.umin = h->dUmin; kp.umax = h->dUmax; kp.xbar = h->dXref; kp.ubar = h->dUref; kp.fval = q.fval; kp.A = q.A; kp.B = q.B;
-            kp.tol = 0.0; kp.it = 0; kp.done = nullptr; kp.iters = nullptr; kp.kkt = nullptr; kp.live = nullptr;
-            if (step_lds > 64 * 1024) HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sqp_kkt), (size_t)(step_lds)));
-        }
-        kp.lam = q.lam;
-        hp.n = n; hp.m = m; hp.H = q.H; hp.L = q.L; hp.act = q.act; hp.N = N; hp.batch = h->batch;
-        hp.W_in = q.W_in; hp.W_h = q.W_h; hp.b_h = q.b_h; hp.W_out = q.W_out; hp.xbar = h->dXref; hp.ubar = h->dUref; hp.lam = q.lam;
-        hp.done = sv ? sv->done : nullptr; hp.W = q.Wlag;
-        xp.n = n; xp.m = m; xp.N = N; xp.nz = nz; xp.A = q.A; xp.B = q.B; xp.c = q.c; xp.W = q.Wlag; xp.ubar = h->dUref;
-        xp.umin = h->dUmin; xp.umax = h->dUmax; xp.done = sv ? sv->done : nullptr; xp.H = h->bH; xp.q = h->bQ;
-        hess_lds = 4 * fnn_hess_wave_doubles(n, m, q.H, q.L, q.net) * sizeof(double);
-        exact_lds = sqp_exact_lds_doubles(n, m, nz) * sizeof(double);
-    }
-    if (rows.mu) {
-        kp.mu = q.smu; kp.term_eq = h->terminal_eq ? 1 : 0;
-        if (h->has_box) { kp.xmin = h->dXmin; kp.xmax = h->dXmax; }
-    }
-    // register-tile design kernel: scaling, scaled gradient and the flag reset ride along as its tail (three launches less per iteration)
-    // (not in exact mode: k_sqp_exact_qp changes H and q after the design, the factor then scales them)
-    const bool ltv_scales = !exact && ltv_reg_path(h) && nz <= 128 && !q.structured_qp && !h->sw.dbg_split_scale;
-    if (ltv_scales) { lp.sc_d = h->bD; lp.sc_Hs = h->bHs; lp.sc_fS = h->dFS; lp.sc_flag = h->bFlag; lp.nzs = nzs; }
-    // ... and k_sqp_prepare as its head (its outputs are that kernel's inputs): a fourth launch less
-    const bool prep_in_design = ltv_scales && !h->sw.dbg_split_prepare;
-    if (prep_in_design) { lp.prep_on = 1; lp.prep = sp; }
-    for (int it = 0; it < iters; ++it) {
-        if (sv && it >= 2) {   // every live instance had converged at the top of iteration it - 2: the rest is frozen work
-            HIP_TRY(h, hipEventSynchronize(sv->ev[(it - 2) & 3]));
-            if (sv->live_pin[(it - 2) & 3] == 0) { all_done = true; break; }
-        }
-        HIP_TRY(h, launch_fnn_jacobian(h->sw, fp, q.net, h->num_cus, st));
-        if (sv) HIP_TRY(h, kkt_test(it));
-        if (exact) {   // multipliers (from the test above, or the walk alone), then the stage Lagrangian Hessians at the iterate
-            if (!sv) hipLaunchKernelGGL(k_sqp_kkt, dim3((unsigned)b), dim3(256), step_lds, st, kp);
-            void (*hk)(FnnHessParams) = with_net(q.net, [](auto k) { return k_fnn_lag_hessian<k>; });
-            hipLaunchKernelGGL(hk, dim3((unsigned)((b * N + 3) / 4)), dim3(256), hess_lds, st, hp);
-            HIP_TRY(h, hipGetLastError());
-        }
-        if (!prep_in_design) hipLaunchKernelGGL(k_sqp_prepare, dim3((unsigned)b), dim3(256), 0, st, sp);
-        if (!ltv_scales) HIP_TRY(h, hipMemsetAsync(h->bFlag, 0, b * sizeof(int), st));
-        if (q.structured_qp) {   // the QP in its stage-wise form for every instance; start: v = 0 (working set = the iterate's inputs on a bound)
-            h->designed = true;
-            // input box without S: the primal Riccati active set (an iterate of this loop has about half of its inputs on a bound: rows a
-            // primal method holds at no cost, while the dual one pays a sweep per row of its start -- measured 0.56 against 3.1 ms per
-            // iteration at the configs[4] shape); with state rows / S: k_sgains + k_sdual
-            SolveCall qp;
-            qp.guess = h->dUref; qp.max_iter = opts ? opts->polish_max_iter : 0;
-            if (h->mc == 0 && !q.useS && h->rKst) {
-                qp.filter = FILTER_SQP_ALL;
-                HIP_TRY(h, launch_riccati(h, qp));
-            } else if (h->sd.ready) {
-                qp.first_tier = h->nz > 48 ? 1 : 0;
-                HIP_TRY(h, launch_sgains(h));
-                HIP_TRY(h, launch_sdual(h, qp));
-            } else
-                return fail(h, ALMPC_ERR_UNSUPPORTED, "sqp_fnn_iterate: no stage-wise QP solver for this design");
-            q.since_start += 1;
-            sp.stats = q.stats + 2 * it;
-            hipLaunchKernelGGL(k_sqp_step, dim3((unsigned)b), dim3(256), step_lds, st, sp);
-            HIP_TRY(h, hipGetLastError());
-            continue;
-        }
-        HIP_TRY(h, launch_design_ltv(h, lp, st));
-        if (exact) {   // H, q of the exact QP (an instance whose result is not positive definite is flagged by the factor and, with the
-                       // structured fallback on, takes the Gauss-Newton QP in its stage-wise form)
-            hipLaunchKernelGGL(k_sqp_exact_qp, dim3((unsigned)b), dim3(256), exact_lds, st, xp);
-            HIP_TRY(h, hipGetLastError());
-        }
-        StepMode mode;
-        mode.guess = (!h->sw.sqp_admm_always && q.since_start > 0) ? Guess::FromIterate : Guess::Admm;
-        mode.rows = rows;
-        // (with the scaling in the design kernel's tail fS_i exists before the inverse: v0S_i = -G_i fS_i comes out of the inverse's launch)
-        const bool v0_in_inverse = ltv_scales && design_inverse_makes_v(h->sw, nz);
-        launch_batched_factor(h, ds, h->rho, h->sigma, st, mode.guess != Guess::Admm, ltv_scales, false, v0_in_inverse ? h->dFS : nullptr, h->dV0S);
-        if (h->mc > 0) HIP_TRY(h, launch_ghat_inst(h, q.A, q.B));
-        if (!ltv_scales) hipLaunchKernelGGL(k_fs_scale, dim3(256), dim3(256), 0, st, h->batch, nz, nzs, h->bQ, (long)nz, h->bD, h->dFS);
-        if (!v0_in_inverse) hipLaunchKernelGGL(k_neg_gm, dim3(1, (unsigned)b), dim3(256), 0, st, nz, nzs, 1, nz, h->bG, h->dFS, h->dV0S, (long)nz * nzs, (long)nz);
-        HIP_TRY(h, hipGetLastError());
-        h->designed = true;
-        const int rc = calculate_checked(h, opts, mode);
-        if (rc != ALMPC_OK) return rc;
-        // structured fallback: an instance whose condensed Hessian came out indefinite to working precision (open-loop unstable
-        // linearisation over the horizon) or whose QP was left unsolved gets this iteration's QP solved in its stage-wise form
-        if (h->fallback) {
-            // input box without S: the primal Riccati active set alone -- the solver this loop's stage-wise QP route uses for such problems
-            // (an iterate holds half of its inputs on bounds; a saturated unstable linearisation is where the dual method has no
-            // certificate) --, ONE idle launch per iteration instead of three; with state rows / S: k_sgains + k_sdual
-            const bool primal_only = h->mc == 0 && !q.useS && h->rKst && !h->sw.sqp_redo_dual_first;
-            SolveCall flagged;
-            flagged.filter = FILTER_SQP_FLAGGED; flagged.single_launch = true; flagged.rows = rows;   // (the last two: k_sdual's)
-            if (h->sd.ready && !primal_only) { HIP_TRY(h, launch_sgains(h, flagged)); HIP_TRY(h, launch_sdual(h, flagged)); }
-            if (h->mc == 0 && !q.useS && h->rKst) HIP_TRY(h, launch_riccati(h, flagged));
-        }
-        q.since_start += 1;
-        sp.stats = q.stats + 2 * it;
-        hipLaunchKernelGGL(k_sqp_step, dim3((unsigned)b), dim3(256), step_lds, st, sp);
-        HIP_TRY(h, hipGetLastError());
-    }
-    if (sv && !all_done) {   // the last test, at the final iterate
-        HIP_TRY(h, launch_fnn_jacobian(h->sw, fp, q.net, h->num_cus, st));
-        HIP_TRY(h, kkt_test(iters));
-    }
-    if (sv) return almpc_synchronize(h);   // (per-instance verdicts instead of ALMPC_ERR_NUMERIC; no histories)
-    std::vector<unsigned long long> stats((size_t)2 * iters);
-    std::vector<int> bad(b);
-    HIP_TRY(h, hipMemcpyAsync(stats.data(), q.stats, stats.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(bad.data(), q.bad, b * sizeof(int), hipMemcpyDeviceToHost, st));
-    { const int rc = almpc_synchronize(h); if (rc != ALMPC_OK) return rc; }
-    for (int it = 0; it < iters; ++it) {
-        double a, c2;
-        std::memcpy(&a, &stats[2 * it], 8); std::memcpy(&c2, &stats[2 * it + 1], 8);
-        if (step_inf) step_inf[it] = a;
-        if (defect_inf) defect_inf[it] = c2;
-    }
-    for (size_t i = 0; i < b; ++i)
-        if (bad[i])
-            return fail(h, ALMPC_ERR_NUMERIC, "sqp_fnn_iterate: instance " + std::to_string(i) +
-                        ": an iteration was skipped (condensed Hessian not positive definite to working precision, a non-finite QP "
-                        "solution, or -- with state rows -- an infeasible QP); its iterate is the last good one, the other instances are unaffected");
     return ALMPC_OK;
 }
 

@@ -9,6 +9,9 @@
 // fake_hip_record_uploads(1) (off by default): every host-to-device hipMemcpy(Async) is kept as (bytes, 64-bit FNV-1a of the payload) and
 // every hipMemset(Async) as (bytes, value); fake_hip_print_uploads(f) writes what was kept since the last call, sorted (f null:
 // writes nothing), and forgets it.
+// fake_hip_trace_calls(1) (off by default): the trace also gets one line, in call order and with the stream's ordinal in front, for
+// every hipMemsetAsync (bytes, value), hipMemcpyAsync (kind, bytes), hipEventRecord, hipStreamSynchronize and hipEventSynchronize (the
+// stream the event was last recorded on): between the launches of a loop their order is part of what the host does.
 #include <hip/hip_runtime_api.h>
 
 #include <cxxabi.h>
@@ -37,9 +40,26 @@ struct State {
     std::vector<size_t> device_bytes, pinned_bytes;
     int fail_in = 0;
     bool record_uploads = false;
+    bool trace_calls = false;
+    std::map<const void*, int> event_ord;   // the ordinal of the stream an event was last recorded on
     std::vector<std::pair<size_t, unsigned long long>> copies, sets;
 };
 State& S() { static State s; return s; }
+
+int ord_of(State& g, hipStream_t st) {
+    const auto o = g.stream_ord.find(st);
+    return st && o != g.stream_ord.end() ? o->second : 0;
+}
+// one line of the ordered trace for a call that is no launch (fake_hip_trace_calls)
+void trace_call(int ord, const char* what, const char* detail = "") {
+    State& g = S(); std::lock_guard<std::mutex> l(g.mu);
+    if (g.trace && g.trace_calls) std::fprintf(g.trace, "%d %s%s\n", ord, what, detail);
+}
+void trace_call(hipStream_t st, const char* what, const char* detail = "") {
+    int ord;
+    { State& g = S(); std::lock_guard<std::mutex> l(g.mu); ord = ord_of(g, st); }
+    trace_call(ord, what, detail);
+}
 
 hipError_t fake_alloc(void** p, size_t n, std::vector<size_t> State::*sizes) {
     State& g = S(); std::lock_guard<std::mutex> l(g.mu);
@@ -100,6 +120,7 @@ int fake_hip_dump_allocs(const char* path) {
     return std::fclose(f) ? 1 : 0;
 }
 
+void fake_hip_trace_calls(int on) { State& g = S(); std::lock_guard<std::mutex> l(g.mu); g.trace_calls = on != 0; }
 void fake_hip_record_uploads(int on) { State& g = S(); std::lock_guard<std::mutex> l(g.mu); g.record_uploads = on != 0; }
 void fake_hip_print_uploads(FILE* f) {
     State& g = S(); std::lock_guard<std::mutex> l(g.mu);
@@ -133,9 +154,19 @@ hipError_t hipHostMalloc(void** p, size_t n, unsigned) { return fake_alloc(p, n,
 hipError_t hipHostFree(void* p) { std::free(p); return hipSuccess; }
 hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) { *d = h; return hipSuccess; }
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind k) { return fake_copy(d, s, n, k); }
-hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t) { return fake_copy(d, s, n, k); }
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t st) {
+    char detail[64];
+    std::snprintf(detail, sizeof detail, " kind %d bytes %zu", (int)k, n);
+    trace_call(st, "hipMemcpyAsync", detail);
+    return fake_copy(d, s, n, k);
+}
 hipError_t hipMemset(void* d, int v, size_t n) { return fake_set(d, v, n); }
-hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { return fake_set(d, v, n); }
+hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st) {
+    char detail[64];
+    std::snprintf(detail, sizeof detail, " bytes %zu value %d", n, v);
+    trace_call(st, "hipMemsetAsync", detail);
+    return fake_set(d, v, n);
+}
 
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
     *s = reinterpret_cast<hipStream_t>(std::malloc(8));
@@ -149,14 +180,27 @@ hipError_t hipStreamDestroy(hipStream_t s) {
     return hipSuccess;
 }
 hipError_t hipStreamQuery(hipStream_t) { return hipSuccess; }
-hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t st) { trace_call(st, "hipStreamSynchronize"); return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
 hipError_t hipEventCreate(hipEvent_t* e) { *e = reinterpret_cast<hipEvent_t>(std::malloc(8)); return hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
-hipError_t hipEventDestroy(hipEvent_t e) { std::free(e); return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t e) {
+    { State& g = S(); std::lock_guard<std::mutex> l(g.mu); g.event_ord.erase(e); }
+    std::free(e);
+    return hipSuccess;
+}
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t st) {
+    { State& g = S(); std::lock_guard<std::mutex> l(g.mu); g.event_ord[e] = ord_of(g, st); }
+    trace_call(st, "hipEventRecord");
+    return hipSuccess;
+}
 hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
-hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
+hipError_t hipEventSynchronize(hipEvent_t e) {
+    int ord = 0;
+    { State& g = S(); std::lock_guard<std::mutex> l(g.mu); const auto o = g.event_ord.find(e); if (o != g.event_ord.end()) ord = o->second; }
+    trace_call(ord, "hipEventSynchronize");
+    return hipSuccess;
+}
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.01f; return hipSuccess; }
 
 hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
@@ -165,8 +209,7 @@ hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void**, size_t 
     ++g.launches;
     if (g.trace) {
         const auto k = g.kernel_name.find(f);
-        const auto o = g.stream_ord.find(st);
-        std::fprintf(g.trace, "%d %s grid %u %u %u block %u %u %u lds %zu\n", st && o != g.stream_ord.end() ? o->second : 0,
+        std::fprintf(g.trace, "%d %s grid %u %u %u block %u %u %u lds %zu\n", ord_of(g, st),
                      k != g.kernel_name.end() ? k->second.c_str() : "?", grid.x, grid.y, grid.z, block.x, block.y, block.z, sh);
     }
     return hipSuccess;

@@ -14,6 +14,9 @@
 // With "setups" as the second argument the design and setup entry points are walked on the routes the plain run does not reach
 // (setups below): every call's return line and, sorted, what it uploaded and set on the device go to stdout; with the launch trace and
 // the allocation sizes they are what tests/golden/host_setups.txt pins.
+// With "loops" as the second argument (and, if given, one switch NAME=VALUE as the third) the SQP loop and the re-linearised step are
+// walked (loops below) with the fake runtime's ordered call trace on: return lines, trace and allocation sizes are what
+// tests/golden/host_loops.txt pins.
 #include "../../include/almpc.h"
 
 #include <algorithm>
@@ -30,6 +33,7 @@ extern "C" void fake_hip_trace_close();
 extern "C" int fake_hip_fail_alloc_at(int k);
 extern "C" int fake_hip_dump_allocs(const char* path);
 extern "C" void fake_hip_record_uploads(int on);
+extern "C" void fake_hip_trace_calls(int on);
 extern "C" void fake_hip_print_uploads(FILE* f);
 extern char** environ;
 
@@ -431,6 +435,204 @@ static int setups() {
     return 0;
 }
 
+// The SQP loop (start, iterate, solve on every QP route, both Hessian modes, row multipliers, every refusal) and the re-linearised
+// step (cold, warm, timing, advance; terminal weights and discretisation on the device) with the ordered call trace on.
+static int loops() {
+    const int n = 4, m = 2, N = 12, batch = 5, Hn = 8, L = 2, TANH = 2;
+    const Plant p = chain(n, m);
+    fake_hip_record_uploads(1);
+    fake_hip_trace_calls(1);
+    std::vector<double> xr((size_t)n * (N + 1), 0.1), ur((size_t)m * N, 0.05), x0((size_t)batch * n, 0.25), P((size_t)n * n, 0.0);
+    for (int k = 0; k < N; ++k) ur[(size_t)k * m] = 0.01 * k;
+    for (int j = 0; j < n; ++j) P[(size_t)j * n + j] = 150.0;
+    std::vector<double> W_in((size_t)Hn * (n + m), 0.05), W_h((size_t)L * Hn * Hn, 0.02), b_h((size_t)L * Hn, 0.01), W_out((size_t)n * Hn, 0.1);
+    std::vector<double> Wd_h((size_t)Hn * Hn * L * (L + 1) / 2, 0.02), Wd_out((size_t)n * Hn * (L + 1), 0.1);   // DenseNet: growing blocks
+    for (size_t t = 0; t < W_in.size(); ++t) W_in[t] += 0.001 * t;
+    std::vector<double> ug((size_t)batch * m * N);   // a start that leaves the input box on both sides
+    for (size_t t = 0; t < ug.size(); ++t) ug[t] = 0.4 * (double)(t % 9) - 1.6;
+    std::vector<double> si(8), di(8), kkt(batch), mu((size_t)batch * N * n);
+    std::vector<int32_t> st(batch), its(batch), sk(batch);
+    almpc_opts cold, warm;
+    almpc_default_opts(&cold);
+    almpc_default_opts(&warm);
+    warm.warm_start = 1;
+    almpc_handle* h = nullptr;
+    const auto open = [&](const char* title, uint32_t flags, bool box, int horizon = 0) {
+        std::printf("---- %s\n", title);
+        if (almpc_create(&h, n, m, horizon ? horizon : N, batch, 0, flags) != ALMPC_OK) return 1;
+        return box ? show(h, "set_state_box", almpc_set_state_box(h, p.xmin.data(), p.xmax.data())) : 0;
+    };
+    const auto close = [&] { almpc_destroy(h); h = nullptr; };
+    const auto sqp = [&](const Plant& w, const double* S, int act, bool dense = false) {
+        return show(h, dense ? "sqp_densenet_setup" : "sqp_fnn_setup",
+                    (dense ? almpc_sqp_densenet_setup : almpc_sqp_fnn_setup)(h, Hn, L, act, W_in.data(), dense ? Wd_h.data() : W_h.data(), b_h.data(),
+                                                                             dense ? Wd_out.data() : W_out.data(), xr.data(), ur.data(), w.Q.data(), w.R.data(), S,
+                                                                             P.data(), 0, w.umin.data(), w.umax.data(), 0.1, 1e-6));
+    };
+    const auto start = [&](const double* guess) { return show(h, guess ? "  sqp_fnn_start (guess outside the box)" : "  sqp_fnn_start", almpc_sqp_fnn_start(h, x0.data(), guess)); };
+    const auto iterate = [&](int k, double scale = 1.0) {
+        std::printf("  iterate %d %g:", k, scale);
+        return show(h, "", almpc_sqp_fnn_iterate(h, k, scale, nullptr, si.data(), di.data()));
+    };
+    const auto solve = [&](int k, double tol = 1e-6) {
+        std::printf("  solve %d %g:", k, tol);
+        return show(h, "", almpc_sqp_fnn_solve(h, k, tol, nullptr, st.data(), its.data(), kkt.data()));
+    };
+    const auto hessian = [&](int mode) { return show(h, mode ? "  set_hessian exact" : "  set_hessian gauss-newton", almpc_sqp_fnn_set_hessian(h, mode)); };
+    const auto rows_on = [&] { return show(h, "  set_row_multipliers 1", almpc_sqp_fnn_set_row_multipliers(h, 1)); };
+    // ---- 1. condensed, input box only
+    if (open("sqp 1: condensed, input box", 0, false)) return 1;
+    sqp(p, nullptr, TANH); start(nullptr);
+    iterate(3); iterate(2, 0.5);
+    show(h, "  set_step_rule 1", almpc_sqp_fnn_set_step_rule(h, 1));
+    solve(4);
+    hessian(1); start(ug.data());
+    iterate(2); solve(3);
+    close();
+    // ---- 2. condensed, state box, the default fallback
+    if (open("sqp 2: condensed, state box", 0, true)) return 1;
+    sqp(p, nullptr, TANH); start(nullptr);
+    iterate(2); rows_on(); iterate(2); solve(3);
+    hessian(1); solve(3);
+    show(h, "  state_multipliers", almpc_sqp_fnn_state_multipliers(h, mu.data()));
+    show(h, "  skipped", almpc_sqp_fnn_skipped(h, sk.data()));
+    close();
+    // ---- 3. condensed, input box with S: the flagged redo is k_sgains + k_sdual
+    if (open("sqp 3: condensed, input box, S", 0, false)) return 1;
+    sqp(p, p.S.data(), TANH); start(nullptr);
+    iterate(2);
+    close();
+    // ---- 4. no redo
+    if (open("sqp 4: condensed, input box, fallback off", 0, false)) return 1;
+    show(h, "set_structured_fallback 0", almpc_set_structured_fallback(h, 0));
+    sqp(p, nullptr, TANH); start(nullptr);
+    iterate(2); solve(2);
+    close();
+    // ---- 5. every QP stage-wise on a condensed handle, state box
+    if (open("sqp 5: sqp_fnn_set_structured(1), state box", 0, true)) return 1;
+    show(h, "sqp_fnn_set_structured", almpc_sqp_fnn_set_structured(h, 1));
+    sqp(p, nullptr, TANH); start(nullptr);
+    iterate(2); solve(3);
+    rows_on(); iterate(1);
+    close();
+    // ---- 6. structured handle, input box: k_riccati
+    if (open("sqp 6: structured, input box", ALMPC_FLAG_STRUCTURED, false)) return 1;
+    sqp(p, nullptr, TANH); start(nullptr);
+    iterate(2); solve(3);
+    close();
+    // ---- 7. DenseNet
+    if (open("sqp 7: DenseNet", 0, false)) return 1;
+    sqp(p, nullptr, TANH, true); start(nullptr);
+    iterate(2); hessian(1); solve(2);
+    close();
+    // ---- 8. nz = 140 on a condensed handle: almpc_create lets m N <= 128 through, so nz > 128 never reaches this loop.  Its branches
+    // without the scaling in the design kernel's tail (k_sqp_prepare, flag memset, k_fs_scale, k_neg_gm by launches of their own) are
+    // walked by the exact-Hessian cases above and by the whole mode under ALMPC_DBG_SPLIT_SCALE=1 and ALMPC_LTV_LDS=1
+    std::printf("---- sqp 8: condensed, nz 140\ncreate n 4, m 2, N 70 -> %d\n", almpc_create(&h, n, m, 70, batch, 0, 0));
+    // ... and the plain run's nz = 80 (N = 40): from the second iteration on the guess builds the inverse of its working set
+    // (k_guess_iterate_ws), with an input box and with state rows
+    for (const bool box : {false, true}) {
+        const int N80 = 40;
+        std::vector<double> xr80((size_t)n * (N80 + 1), 0.1), ur80((size_t)m * N80, 0.05);
+        if (open(box ? "sqp 8: condensed, state box, nz 80" : "sqp 8: condensed, input box, nz 80", 0, box, N80)) return 1;
+        show(h, "sqp_fnn_setup", almpc_sqp_fnn_setup(h, Hn, L, TANH, W_in.data(), W_h.data(), b_h.data(), W_out.data(), xr80.data(), ur80.data(), p.Q.data(), p.R.data(),
+                                                     nullptr, P.data(), 0, p.umin.data(), p.umax.data(), 0.1, 1e-6));
+        start(nullptr);
+        iterate(2);
+        close();
+    }
+    // ---- 9. refusals, one at a time
+    if (open("sqp 9: refusals", 0, false)) return 1;
+    show(h, "start before setup", almpc_sqp_fnn_start(h, x0.data(), nullptr));
+    show(h, "iterate before setup", almpc_sqp_fnn_iterate(h, 1, 1.0, nullptr, nullptr, nullptr));
+    show(h, "solve before setup", almpc_sqp_fnn_solve(h, 1, 1e-6, nullptr, nullptr, nullptr, nullptr));
+    show(h, "state_multipliers before setup", almpc_sqp_fnn_state_multipliers(h, mu.data()));
+    show(h, "skipped before setup", almpc_sqp_fnn_skipped(h, sk.data()));
+    show(h, "set_hessian 2", almpc_sqp_fnn_set_hessian(h, 2));
+    show(h, "set_step_rule 2", almpc_sqp_fnn_set_step_rule(h, 2));
+    sqp(p, nullptr, TANH);
+    show(h, "iterate before start", almpc_sqp_fnn_iterate(h, 1, 1.0, nullptr, nullptr, nullptr));
+    show(h, "solve before start", almpc_sqp_fnn_solve(h, 1, 1e-6, nullptr, nullptr, nullptr, nullptr));
+    show(h, "start, x0 null", almpc_sqp_fnn_start(h, nullptr, nullptr));
+    start(nullptr);
+    show(h, "iterate, iters 0", almpc_sqp_fnn_iterate(h, 0, 1.0, nullptr, nullptr, nullptr));
+    show(h, "iterate, step_scale 0", almpc_sqp_fnn_iterate(h, 1, 0.0, nullptr, nullptr, nullptr));
+    show(h, "iterate, step_scale 1.5", almpc_sqp_fnn_iterate(h, 1, 1.5, nullptr, nullptr, nullptr));
+    show(h, "solve, max_iters 0", almpc_sqp_fnn_solve(h, 0, 1e-6, nullptr, nullptr, nullptr, nullptr));
+    show(h, "solve, tol 0", almpc_sqp_fnn_solve(h, 1, 0.0, nullptr, nullptr, nullptr, nullptr));
+    {
+        Plant r0 = p;
+        r0.R[0] = 0.0;
+        sqp(r0, nullptr, TANH); start(nullptr);
+        show(h, "solve, R[0,0] = 0", almpc_sqp_fnn_solve(h, 1, 1e-6, nullptr, nullptr, nullptr, nullptr));
+        iterate(1);
+    }
+    sqp(p, nullptr, 1);   // relu
+    show(h, "set_hessian exact, relu", almpc_sqp_fnn_set_hessian(h, 1));
+    close();
+    if (open("sqp 9: exact asked for before a relu setup", 0, false)) return 1;
+    hessian(1);
+    sqp(p, nullptr, 1); start(nullptr);
+    iterate(1); solve(1);
+    close();
+    if (open("sqp 9: exact with state rows", 0, true)) return 1;
+    sqp(p, nullptr, TANH);
+    show(h, "set_hessian exact, no row multipliers", almpc_sqp_fnn_set_hessian(h, 1));
+    close();
+    if (open("sqp 9: exact with state rows and their multipliers, fallback off", 0, true)) return 1;
+    show(h, "set_structured_fallback 0", almpc_set_structured_fallback(h, 0));
+    sqp(p, nullptr, TANH); rows_on();
+    show(h, "set_hessian exact, no fallback", almpc_sqp_fnn_set_hessian(h, 1));
+    close();
+    if (open("sqp 9: exact on the stage-wise route", ALMPC_FLAG_STRUCTURED, false)) return 1;
+    sqp(p, nullptr, TANH);
+    show(h, "set_hessian exact, structured", almpc_sqp_fnn_set_hessian(h, 1));
+    close();
+    // ---- 10 - 14. the re-linearised step: as set up, with every instance's own terminal weight, with a continuous-time network
+    const auto relin_walk = [&] {
+        show(h, "relin_fnn_setup", almpc_relin_fnn_setup(h, Hn, L, TANH, W_in.data(), W_h.data(), b_h.data(), W_out.data(), xr.data(), ur.data(), p.Q.data(), p.R.data(),
+                                                         p.S.data(), P.data(), p.umin.data(), p.umax.data(), 0.1, 1e-6));
+        float a = 0, b = 0, c = 0;
+        show(h, "  update_initialization", almpc_update_initialization(h, x0.data()));
+        show(h, "  relin_fnn_step cold", almpc_relin_fnn_step(h, &cold));
+        show(h, "  update_initialization", almpc_update_initialization(h, x0.data()));
+        show(h, "  relin_fnn_step warm", almpc_relin_fnn_step(h, &warm));
+        show(h, "  relin_fnn_timing", almpc_relin_fnn_timing(h, &a, &b, &c));
+        show(h, "  relin_fnn_advance", almpc_relin_fnn_advance(h));
+        show(h, "  update_initialization", almpc_update_initialization(h, x0.data()));
+        show(h, "  relin_fnn_step warm", almpc_relin_fnn_step(h, &warm));
+    };
+    for (int variant = 0; variant < 3; ++variant)
+        for (int kind = 0; kind < 3; ++kind) {
+            const char* const titles[3][3] = {{"relin 10: condensed, timing", "relin 11: condensed, state box", "relin 12: structured, timing"},
+                                              {"relin 13: condensed, timing, DARE on the device", "relin 13: condensed, state box, DARE on the device", "relin 13: structured, timing, DARE on the device"},
+                                              {"relin 14: condensed, timing, continuous time", "relin 14: condensed, state box, continuous time", "relin 14: structured, timing, continuous time"}};
+            if (open(titles[variant][kind], kind == 2 ? ALMPC_FLAG_STRUCTURED | ALMPC_FLAG_TIMING : (kind == 0 ? ALMPC_FLAG_TIMING : 0u), kind == 1)) return 1;
+            if (variant == 1) show(h, "set_terminal_weight", almpc_set_terminal_weight(h, ALMPC_TERMINAL_DARE_DEVICE));
+            if (variant == 2) show(h, "set_model_time", almpc_set_model_time(h, ALMPC_MODEL_CONTINUOUS_ZOH, 0.1));
+            relin_walk();
+            close();
+        }
+    // ---- 15. the `warm` predicate without a polish; calls out of order
+    if (open("relin 15: no polish, calls out of order", 0, false)) return 1;
+    show(h, "relin_fnn_step before setup", almpc_relin_fnn_step(h, &cold));
+    show(h, "relin_fnn_advance before setup", almpc_relin_fnn_advance(h));
+    show(h, "relin_fnn_setup", almpc_relin_fnn_setup(h, Hn, L, TANH, W_in.data(), W_h.data(), b_h.data(), W_out.data(), xr.data(), ur.data(), p.Q.data(), p.R.data(),
+                                                     p.S.data(), P.data(), p.umin.data(), p.umax.data(), 0.1, 1e-6));
+    show(h, "relin_fnn_advance before a step", almpc_relin_fnn_advance(h));
+    show(h, "  update_initialization", almpc_update_initialization(h, x0.data()));
+    show(h, "  relin_fnn_step cold", almpc_relin_fnn_step(h, &cold));
+    almpc_opts rough = warm;
+    rough.polish = 0;
+    show(h, "  update_initialization", almpc_update_initialization(h, x0.data()));
+    show(h, "  relin_fnn_step warm_start 1, polish 0", almpc_relin_fnn_step(h, &rough));
+    show(h, "  relin_fnn_step, opts null", almpc_relin_fnn_step(h, nullptr));
+    close();
+    fake_hip_record_uploads(0);
+    std::printf("loops ok\n");
+    return 0;
+}
+
 int main(int argc, char** argv) {
     {   // every almpc_create below reads the switches: none may come in from the caller's environment
         std::vector<std::string> inherited;
@@ -442,6 +644,13 @@ int main(int argc, char** argv) {
     if (argc > 2 && std::strcmp(argv[2], "alloc-failures") == 0) return alloc_failures();
     if (argc > 2 && std::strcmp(argv[2], "setups") == 0) {
         if (setups()) return 1;
+        fake_hip_trace_close();
+        return fake_hip_dump_allocs((std::string(argv[1]) + ".allocs").c_str());
+    }
+    if (argc > 2 && std::strcmp(argv[2], "loops") == 0) {
+        const char* const sw = argc > 3 ? std::strchr(argv[3], '=') : nullptr;
+        if (argc > 3 && (!sw || setenv(std::string(argv[3], sw - argv[3]).c_str(), sw + 1, 1))) { std::fprintf(stderr, "not NAME=VALUE: %s\n", argv[3]); return 1; }
+        if (loops()) return 1;
         fake_hip_trace_close();
         return fake_hip_dump_allocs((std::string(argv[1]) + ".allocs").c_str());
     }

@@ -218,3 +218,64 @@ def test_design_and_setup_entry_points_do_what_they_were_recorded_doing(tmp_path
     assert "setups ok" in r.stdout
     golden = (Path(ROOT) / "tests" / "golden" / "host_setups.txt").read_text().splitlines()
     assert got == golden, next(f"line {i + 1}: {a!r} != golden {b!r}" for i, (a, b) in enumerate(zip(got + [""] * len(golden), golden + [""] * len(got))) if a != b)
+
+
+LOOP_SWITCHES = ("ALMPC_DBG_SPLIT_SCALE", "ALMPC_DBG_SPLIT_PREPARE", "ALMPC_DBG_SPLIT_JACOBIAN", "ALMPC_SQP_ADMM_ALWAYS", "ALMPC_SQP_REDO_DUAL_FIRST",
+                 "ALMPC_NO_GUESS_WS", "ALMPC_LTV_LDS")
+
+
+def _loops_record(exe, tmp_path, switch=None):
+    """One run of the driver's "loops" mode (under NAME=1 if given) as the text tests/golden/host_loops.txt holds: the return line of
+    every call with what it uploaded and set by synchronous calls (sorted per call), the ordered trace of launches, asynchronous
+    memsets and copies, event records and synchronisations, the sorted allocation sizes."""
+    trace = tmp_path / "loops.txt"
+    r = _run([exe, str(trace), "loops"] + ([switch + "=1"] if switch else []))
+    lines = sorted(trace.read_text().splitlines(), key=lambda line: int(line.split()[0]))
+    allocs = (tmp_path / "loops.txt.allocs").read_text().splitlines() if r.returncode == 0 else []
+    return r, ["== calls"] + r.stdout.splitlines() + ["== trace"] + lines + ["== allocations"] + allocs
+
+
+@pytest.mark.timeout(900)
+def test_sqp_loop_and_relinearised_step_do_what_they_were_recorded_doing(tmp_path, host_logic_exe):
+    """The driver's "loops" mode: almpc_sqp_fnn_start / _iterate / _solve on every QP route (condensed with an input box, with state
+    rows, with S, without the redo; stage-wise on a condensed and on a structured handle; DenseNet), in both Hessian modes, with row
+    multipliers, with a start guess outside the box, a second and third iteration, every refusal of the loop's entry points; and
+    almpc_relin_fnn_step cold and warm, _timing, _advance on a condensed, a state-row and a structured handle, each again with
+    every instance's own terminal weight (k_dare) and with a continuous-time network (k_c2d).  Return code and error text of every
+    call, every byte it uploads, and IN CALL ORDER every launch (kernel, grid, block, LDS), hipMemsetAsync (bytes, value),
+    hipMemcpyAsync (kind, bytes), hipEventRecord, hipStreamSynchronize and hipEventSynchronize, and every allocation size, are those of
+    the commit before this section of csrc/almpc_api.hip was taken apart into one job per function, recorded with this driver in
+    tests/golden/host_loops.txt; tests/golden/host_loops_switches.txt holds the same under each of LOOP_SWITCHES as the difference to
+    the plain record.  A stand-alone program: nothing is loaded into Python.
+    What this pin does not see:
+    - no kernel runs on the fake runtime, so the live count of almpc_sqp_fnn_solve never reaches 0: solve always runs max_iters
+      iterations and the last test.  The early exit is held by tests/test_gpu_sqp_solve.py on the GPU;
+    - kernel arguments: which buffer goes into which field of a parameter struct is held by the GPU suite and by
+      tools/dump_sqp_relin_cases.py --compare against the parent's build;
+    - a condensed handle with nz > 128 does not exist (almpc_create: m N <= 128): the loop's branches without the scaling in the design
+      kernel's tail are walked by the exact-Hessian cases and under ALMPC_DBG_SPLIT_SCALE and ALMPC_LTV_LDS;
+    - four refusals no shape of the driver reaches: almpc_sqp_fnn_solve's "m <= 64", "sqp_fnn_iterate: no stage-wise QP solver for this
+      design" (a setup that leaves neither stage-wise solver ready is refused before), and the two LDS-scratch refusals of the exact
+      Hessian mode (the per-wave scratch of k_fnn_lag_hessian, the stage scratch of k_sqp_exact_qp)."""
+    import difflib
+    strip = lambda text: [ln for ln in text.splitlines() if not ln.startswith("# ")]
+    first_diff = lambda got, want: next(f"line {i + 1}: {a!r} != golden {b!r}" for i, (a, b) in enumerate(zip(got + [""] * len(want), want + [""] * len(got))) if a != b)
+    r, plain = _loops_record(host_logic_exe, tmp_path)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert "ERROR" not in r.stderr and "runtime error" not in r.stderr
+    assert "loops ok" in r.stdout
+    golden = strip((Path(ROOT) / "tests" / "golden" / "host_loops.txt").read_text())
+    assert plain == golden, first_diff(plain, golden)
+    recorded, key = {}, None
+    for ln in strip((Path(ROOT) / "tests" / "golden" / "host_loops_switches.txt").read_text()):
+        if ln.startswith("== ALMPC_"):
+            key = ln[3:]
+            recorded[key] = []
+        else:
+            recorded[key].append(ln)
+    assert sorted(recorded) == sorted(LOOP_SWITCHES)
+    for name in LOOP_SWITCHES:
+        r, got = _loops_record(host_logic_exe, tmp_path, name)
+        assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (name, r.stderr[-3000:])
+        diff = list(difflib.unified_diff(golden, got, n=0, lineterm=""))[2:]
+        assert diff and diff == recorded[name], (name, first_diff(diff, recorded[name]))
