@@ -64,6 +64,10 @@ def load():
     L.almpc_design_shared.argtypes = [_hp] + [_dp] * 10 + [ctypes.c_double, ctypes.c_double]
     L.almpc_design_batched.argtypes = [_hp] + [_dp] * 6 + [ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_double]
     L.almpc_design_batched.restype = ctypes.c_int
+    L.almpc_design_batched_weighted.argtypes = [_hp] + [_dp] * 6 + [ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_double]
+    L.almpc_design_batched_weighted.restype = ctypes.c_int
+    L.almpc_get_weights_instance.argtypes = [_hp, ctypes.c_int, _dp, _dp, _dp]
+    L.almpc_get_weights_instance.restype = ctypes.c_int
     L.almpc_get_design_instance.argtypes = [_hp, ctypes.c_int, _dp, _dp, _dp]
     L.almpc_design_ltv.argtypes = [_hp] + [_dp] * 11 + [ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_double]
     L.almpc_design_ltv.restype = ctypes.c_int
@@ -220,6 +224,8 @@ def load():
         getattr(L, nm_).argtypes = [_hp, ctypes.c_int]
     L.almpc_group_set_state_box.argtypes = [_hp, _dp, _dp]
     L.almpc_group_design_batched.argtypes = [_hp] + [_dp] * 6 + [ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_double]
+    L.almpc_group_design_batched_weighted.argtypes = L.almpc_group_design_batched.argtypes
+    L.almpc_group_design_batched_weighted.restype = ctypes.c_int
     L.almpc_group_relin_fnn_setup.argtypes = [_hp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_dp] * 12 + [ctypes.c_double, ctypes.c_double]
     L.almpc_group_relin_fnn_step.argtypes = [_hp, ctypes.POINTER(almpc_opts)]
     L.almpc_group_relin_fnn_step_async.argtypes = [_hp, ctypes.POINTER(almpc_opts)]
@@ -269,6 +275,25 @@ OPT_HBM_HANDOFF = 0x4  # almpc.h: ALMPC_OPT_HBM_HANDOFF (opts.reserved[0]): A/B 
 WANT = {"x": 0x01, "e_x": 0x02, "u": 0x04, "e_u": 0x08, "status": 0x10, "iters": 0x20, "polish_iters": 0x40, "u0": 0x80}
 # almpc.h: ALMPC_SENS_* (almpc_sensitivity)
 SENS = {"K0": 0x1, "dU": 0x2, "dX": 0x4}
+
+
+def _weighted_design_args(n, m, b, A_batch, B_batch, Q_batch, R_batch, S_batch, P, umin, umax):
+    """((A, B, Q, R, S, P, umin, umax) as the C call takes them: every block column-major, S / P None where not given; P_per_instance)."""
+    def blocks(M, r, c):
+        return np.ascontiguousarray(np.asarray(M, dtype=np.float64).reshape(b, r, c).transpose(0, 2, 1))
+    A, B = blocks(A_batch, n, n), blocks(B_batch, n, m)
+    Q, R = blocks(Q_batch, n, n), blocks(R_batch, m, m)
+    S = None if S_batch is None else blocks(S_batch, m, m)
+    p_inst = 0
+    if P is not None:
+        P = np.asarray(P, dtype=np.float64)
+        if P.ndim == 3:
+            P = blocks(P, n, n); p_inst = 1
+        else:
+            P = _colmajor(P, (n, n))
+    umin = np.ascontiguousarray(umin, dtype=np.float64).reshape(m)
+    umax = np.ascontiguousarray(umax, dtype=np.float64).reshape(m)
+    return (A, B, Q, R, S, P, umin, umax), p_inst
 
 
 def _sens_mask(want):
@@ -704,6 +729,23 @@ class Solver:
         umax = np.ascontiguousarray(umax, dtype=np.float64).reshape(m)
         self._check(self.L.almpc_design_batched(self.h, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(S), _ptr(P), p_inst, _ptr(umin),
                                                 _ptr(umax), float(rho), float(sigma)))
+
+    def design_batched_weighted(self, A_batch, B_batch, Q_batch, R_batch, S_batch=None, P=None, umin=None, umax=None, rho=0.1, sigma=1e-6,
+                                rho_profile="scalar", xmin=None, xmax=None, terminal="none"):
+        """design_batched with one weight set per instance (almpc_design_batched_weighted): Q_batch (batch, n, n), R_batch and
+        S_batch (batch, m, m), S_batch None for S = 0 everywhere.  The other arguments are design_batched's."""
+        self._state_rows(xmin, xmax, terminal)
+        self._check(self.L.almpc_set_rho_profile(self.h, {"scalar": 0, "stiffness": 1}[rho_profile]))
+        args, p_inst = _weighted_design_args(self.n, self.m, self.batch, A_batch, B_batch, Q_batch, R_batch, S_batch, P, umin, umax)
+        self._check(self.L.almpc_design_batched_weighted(self.h, *[_ptr(a) for a in args[:6]], p_inst, _ptr(args[6]), _ptr(args[7]),
+                                                         float(rho), float(sigma)))
+
+    def get_weights_instance(self, i):
+        """dict(Q (n, n), R (m, m), S (m, m)): the weights instance i is designed on, as the design kernels read them
+        (almpc_get_weights_instance)."""
+        Q, R, S = np.empty((self.n, self.n), order="F"), np.empty((self.m, self.m), order="F"), np.empty((self.m, self.m), order="F")
+        self._check(self.L.almpc_get_weights_instance(self.h, int(i), _ptr(Q), _ptr(R), _ptr(S)))
+        return dict(Q=Q, R=R, S=S)
 
     def design_ltv(self, A_all, B_all, c_all, xbar, ubar, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, rho=0.1, sigma=1e-6,
                    rho_profile="scalar", xmin=None, xmax=None, terminal="none"):
@@ -1224,6 +1266,15 @@ class Group:
         umax = np.ascontiguousarray(umax, dtype=np.float64).reshape(m)
         self._check(self.L.almpc_group_design_batched(self.g, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(S), _ptr(P), p_inst, _ptr(umin),
                                                       _ptr(umax), float(rho), float(sigma)))
+
+    def design_batched_weighted(self, A_batch, B_batch, Q_batch, R_batch, S_batch=None, P=None, umin=None, umax=None, rho=0.1, sigma=1e-6,
+                                rho_profile="scalar", xmin=None, xmax=None, terminal="none"):
+        """almpc_group_design_batched_weighted: arguments of Solver.design_batched_weighted for the whole batch."""
+        self._state_rows(xmin, xmax, terminal)
+        self._check(self.L.almpc_group_set_rho_profile(self.g, {"scalar": 0, "stiffness": 1}[rho_profile]))
+        args, p_inst = _weighted_design_args(self.n, self.m, self.batch, A_batch, B_batch, Q_batch, R_batch, S_batch, P, umin, umax)
+        self._check(self.L.almpc_group_design_batched_weighted(self.g, *[_ptr(a) for a in args[:6]], p_inst, _ptr(args[6]), _ptr(args[7]),
+                                                               float(rho), float(sigma)))
 
     def _fnn_args(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, act, p_batched, net="fnn"):
         n, m, N = self.n, self.m, self.N

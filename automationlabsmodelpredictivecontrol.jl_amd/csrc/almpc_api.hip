@@ -84,6 +84,13 @@ struct almpc_handle {
     DevBuf<double> dXref, dUref, dFS, dV0S, dRho;
     bool ref_keep = false;   // dXref, dUref, dFS, dV0S are as almpc_set_reference made them: it keeps all four while their sizes stay
     DevBuf<double> wQ, wR, wS;   // design weights on the device (almpc_design_batched / _ltv)
+    // almpc_design_batched_weighted: one (Q_i, R_i, S_i) per instance, [batch][n*n] and [batch][m*m] twice, symmetrised as the design
+    // takes them.  Made by that call only (wiS: when it is given an S_batch); every other design leaves `weighted` off (drop_lazy_redo)
+    DevBuf<double> wiQ, wiR, wiS;
+    bool weighted = false, wiS_given = false;   // (wiS_given: wiS holds this design's S_i)
+    // ... staged through pinned host buffers of the same sizes (the symmetrised sets: no page faults and no staging copy per design);
+    // hSi is also what almpc_set_reference forms fS from while the input-rate term is part of the cost
+    PinBuf<double> hQi, hRi, hSi;
     int rho_mode = 0;  // 0 scalar rho (OSQP), 1 stiffness profile rho / G_ii
     // blocked rollout of the shared model (rollout_blocked): [Gamma_s | Phi_s] rows per lane, built at design time
     DevBuf<double> dRollM;
@@ -768,7 +775,9 @@ int dare_device_check(int n, int m, const hm::mat& Rm, bool branch_rule, const c
 // almpc_set_terminal_weight(ALMPC_TERMINAL_DARE_DEVICE), almpc_design_batched(P = NULL): bP_i = DARE(bA_i, bB_i, Q, R) by k_dare on
 // the handle's stream, behind the uploads of the models and weights (dQ, dR: device).  Waits for it and reports the first instance
 // without a stabilising solution as the host loop does.  Pfirst: host copy of instance 0's weight.
-int design_dare_device(almpc_handle* h, const double* dQ, const double* dR, const hm::mat& Rm, hm::mat& Pfirst) {
+// sQ, sR: strides of dQ, dR (0: shared; almpc_design_batched_weighted: one pair per instance -- Rm is then instance 0's, and a singular
+// R_i of another instance is k_dare's own status 1, reported like an instance without a stabilising solution)
+int design_dare_device(almpc_handle* h, const double* dQ, const double* dR, const hm::mat& Rm, hm::mat& Pfirst, long sQ = 0, long sR = 0) {
     const int n = h->n, m = h->m;
     const size_t b = (size_t)h->batch;
     const char* why = "";
@@ -777,6 +786,7 @@ int design_dare_device(almpc_handle* h, const double* dQ, const double* dR, cons
     DareParams dp;
     dp.n = n; dp.m = m; dp.batch = h->batch;
     dp.A = h->bA; dp.A_stride = (long)n * n; dp.B = h->bB; dp.B_stride = (long)n * m; dp.Q = dQ; dp.R = dR;
+    dp.Q_stride = sQ; dp.R_stride = sR;
     dp.P = h->bP; dp.P_stride = (long)n * n; dp.fallback = nullptr; dp.status = h->tStat; dp.lds_per_wave = 0;
     HIP_TRY(h, launch_dare(dp, h->stream));
     std::vector<int32_t> stt(b, 0);
@@ -1211,6 +1221,7 @@ void drop_lazy_redo(almpc_handle* h) {
     h->sens.stepped = false; h->sens.v_ok = false; h->sens.t1_ok = false; h->sens.w_ok = false; h->sens.have = 0;   // (what a sensitivity call looks at goes with the design as well)
     h->redo.lazy_pending = false;
     h->redo.expected = false;
+    h->weighted = false;   // (almpc_design_batched_weighted sets it again behind this call)
     if (h->redo.hUnsolved) h->redo.unsolved_seen = *reinterpret_cast<volatile int*>(h->redo.hUnsolved.get());
 }
 
@@ -1284,8 +1295,9 @@ int begin_redesign(almpc_handle* h, unsigned what) {
 
 // Terminal weights of a per-instance design, into Pall: the caller's (one matrix, or one per instance), else -- unless k_dare makes
 // them behind the uploads (dev_dare: Pall stays empty) -- the DARE solution of every instance's model (src/sub/design_mpc.jl:327)
+// Qi, Ri (almpc_design_batched_weighted): [batch] weights, instance i's DARE from its own pair instead of (Qm, Rm)
 int terminal_weights(almpc_handle* h, const double* A_batch, const double* B_batch, const hm::mat& Qm, const hm::mat& Rm, const double* P,
-                     int P_per_instance, bool dev_dare, const char* who, hm::mat& Pall) {
+                     int P_per_instance, bool dev_dare, const char* who, hm::mat& Pall, const double* Qi = nullptr, const double* Ri = nullptr) {
     const size_t n = (size_t)h->n, m = (size_t)h->m, b = (size_t)h->batch;
     if (P) Pall.assign(P, P + (P_per_instance ? b : 1) * n * n);
     else if (!dev_dare) {
@@ -1293,7 +1305,9 @@ int terminal_weights(almpc_handle* h, const double* A_batch, const double* B_bat
         for (size_t i = 0; i < b; ++i) {
             hm::mat Am(A_batch + i * n * n, A_batch + (i + 1) * n * n), Bm(B_batch + i * n * m, B_batch + (i + 1) * n * m), Pm;
             const char* what = "";
-            if (!host_dare_of(h, Am, Bm, Qm, Rm, Pm, &what)) return fail(h, ALMPC_ERR_NUMERIC, std::string(who) + ": " + what + " for instance " + std::to_string(i));
+            const bool ok = Qi ? host_dare_of(h, Am, Bm, hm::mat(Qi + i * n * n, Qi + (i + 1) * n * n), hm::mat(Ri + i * m * m, Ri + (i + 1) * m * m), Pm, &what)
+                               : host_dare_of(h, Am, Bm, Qm, Rm, Pm, &what);
+            if (!ok) return fail(h, ALMPC_ERR_NUMERIC, std::string(who) + ": " + what + " for instance " + std::to_string(i));
             std::copy(Pm.begin(), Pm.end(), Pall.begin() + i * n * n);
         }
     }
@@ -1923,8 +1937,8 @@ bool design_fuses_fnn(const almpc_handle* h, int H, int L, int net) {
     return lds <= 160 * 1024 && !h->sw.dbg_split_jacobian;
 }
 
-// The per-instance design from DEVICE-resident operands (bA, bB, bP; weights dQ, dR, dS): prediction matrices, H_i and F_i,
-// scaling, both inverses, V_i.  Launches only (handle's stream); the caller checks bFlag.
+// The per-instance design from DEVICE-resident operands (bA, bB, bP; weights dQ, dR, dS, shared or -- ds.Q, ds.R, ds.S -- one set per
+// instance): prediction matrices, H_i and F_i, scaling, both inverses, V_i.  Launches only (handle's stream); the caller checks bFlag.
 // fuse_fnn: the models are linearisations of this network at fuse_fnn->x / u (re-linearisation pipeline): done by the design kernel's
 // own workgroups when *fused comes back true -- else the caller launches the Jacobians first
 hipError_t launch_batched_design(almpc_handle* h, const DesignStrides& ds, int useR, int useS, const double* dQ, const double* dR,
@@ -1951,7 +1965,7 @@ hipError_t launch_batched_design(almpc_handle* h, const DesignStrides& ds, int u
         dp.flag = h->bFlag; dp.sFlag = 1;
         dp.n = n; dp.m = m; dp.N = N; dp.nz = nz; dp.useR = useR; dp.useS = useS;
         dp.A = h->bA; dp.B = h->bB; dp.P = h->bP; dp.sA = ds.A; dp.sB = ds.B; dp.sP = ds.P;
-        dp.Q = dQ; dp.R = dR; dp.S = dS; dp.H = h->bH; dp.F = h->bF; dp.sH = ds.H; dp.sF = ds.F;
+        dp.Q = dQ; dp.R = dR; dp.S = dS; dp.sQ = ds.Q; dp.sR = ds.R; dp.sS = ds.S; dp.H = h->bH; dp.F = h->bF; dp.sH = ds.H; dp.sF = ds.F;
         if (nz <= 128 && design_instance_lds_doubles(n, m, N) >= 128 && !h->sw.dbg_split_scale) {   // the scaling rides along (k_design_scale's body, one launch less)
             dp.d = h->bD; dp.Hs = h->bHs; dp.Fs = h->bFs; dp.sd = ds.d; dp.sHs = ds.Hs; dp.sFs = ds.Fs; dp.nzs = nzs;
         }
@@ -2053,13 +2067,23 @@ struct DesignTrace {
 };
 
 // What the front of a condensed per-instance design leaves its caller: the weights, symmetrised; one terminal weight per instance?
-struct BatchedDesign { hm::mat Qm, Rm, Sm; bool p_inst = true; int useR = 0, useS = 0; DesignStrides ds; DesignTrace tr; };
+// (dQ, dR, dS: the weights the design kernels read, the handle's shared set or -- ds.Q, ds.R, ds.S -- its per-instance buffers)
+struct BatchedDesign {
+    hm::mat Qm, Rm, Sm; bool p_inst = true; int useR = 0, useS = 0; DesignStrides ds; DesignTrace tr;
+    const double *dQ = nullptr, *dR = nullptr, *dS = nullptr;
+};
+
+// almpc_design_batched_weighted: every instance's weights, [batch] matrices each, symmetrised one by one as almpc_design_batched
+// symmetrises its single set (S null: no S_batch), in the handle's pinned buffers.  The front's Q, R, S are then instance 0's: the
+// branch is the whole batch's.
+struct InstanceWeights { const double* Q; const double* R; const double* S; };
 
 // The front of the condensed per-instance designs (almpc_design_batched, almpc_design_ltv): argument checks, weights, terminal weights,
 // state rows, the per-instance operands, then models and weights on the device -- continuous-time models discretised in place (k_c2d).
 // (What a time-varying design cannot have -- P null, continuous-time models -- its entry point has refused already.)
 int batched_design_front(almpc_handle* h, const double* A_batch, const double* B_batch, const double* Q, const double* R, const double* S,
-                         const double* P, int P_per_instance, const double* umin, const double* umax, double rho, double sigma, BatchedDesign& d) {
+                         const double* P, int P_per_instance, const double* umin, const double* umax, double rho, double sigma, BatchedDesign& d,
+                         const InstanceWeights* wi = nullptr) {
     if (!A_batch || !B_batch || !Q || !R || !umin || !umax) return fail(h, ALMPC_ERR_INVALID, "design_batched: null matrix pointer");
     if (!(rho > 0.0) || !(sigma >= 0.0)) return fail(h, ALMPC_ERR_INVALID, "design_batched: rho must be > 0 and sigma >= 0");
     DesignTrace& tr = d.tr;
@@ -2077,7 +2101,7 @@ int batched_design_front(almpc_handle* h, const double* A_batch, const double* B
     const bool cont = model_continuous(h);   // (almpc_set_model_time: k_c2d in place on the uploaded models, below)
     if (cont) ALMPC_TRY(c2d_shape_check(h, "design_batched"));
     hm::mat Pall;
-    ALMPC_TRY(terminal_weights(h, A_batch, B_batch, Qm, Rm, P, p_inst, dev_dare, "design_batched", Pall));
+    ALMPC_TRY(terminal_weights(h, A_batch, B_batch, Qm, Rm, P, p_inst, dev_dare, "design_batched", Pall, wi ? wi->Q : nullptr, wi ? wi->R : nullptr));
     for (size_t i = 0; i < (dev_dare ? 0 : p_inst ? b : 1); ++i) {
         const hm::mat Pm = hm::symmetrised(Pall.data() + i * n * n, n);
         std::copy(Pm.begin(), Pm.end(), Pall.begin() + i * n * n);
@@ -2096,16 +2120,26 @@ int batched_design_front(almpc_handle* h, const double* A_batch, const double* B
     ALMPC_TRY(ensure_batched_alloc(h));
     hipStream_t st = h->stream;
     tr("state rows + allocation");
-    HIP_TRY(h, h->wQ.once((size_t)n * n));
-    HIP_TRY(h, h->wR.once((size_t)m * m));
-    HIP_TRY(h, h->wS.once((size_t)m * m));
-    double *dQ = h->wQ, *dR = h->wR, *dS = h->wS;   // (kept with the handle: three hipMalloc + hipFree per design cost 0.15 ms)
+    if (!wi) {
+        HIP_TRY(h, h->wQ.once((size_t)n * n));
+        HIP_TRY(h, h->wR.once((size_t)m * m));
+        HIP_TRY(h, h->wS.once((size_t)m * m));
+    } else {   // one set per instance: buffers of their own, made here and nowhere else
+        HIP_TRY(h, h->wiQ.grow(b * n * n));
+        HIP_TRY(h, h->wiR.grow(b * m * m));
+        if (wi->S) HIP_TRY(h, h->wiS.grow(b * m * m));
+    }
+    const bool s_given = !wi || wi->S;
+    double *dQ = wi ? h->wiQ.get() : h->wQ.get(), *dR = wi ? h->wiR.get() : h->wR.get();   // (kept with the handle: three hipMalloc + hipFree per design cost 0.15 ms)
+    double* dS = !wi ? h->wS.get() : s_given ? h->wiS.get() : nullptr;
+    const double *Qup = wi ? wi->Q : Qm.data(), *Rup = wi ? wi->R : Rm.data(), *Sup = wi ? wi->S : Sm.data();
+    const size_t qn = wi ? b * n * n : Qm.size(), rn = wi ? b * m * m : Rm.size(), sn = wi ? b * m * m : Sm.size();
     HIP_TRY(h, hipMemcpyAsync(h->bA, A_batch, b * n * n * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(h, hipMemcpyAsync(h->bB, B_batch, b * n * m * sizeof(double), hipMemcpyHostToDevice, st));
     if (!dev_dare) HIP_TRY(h, hipMemcpyAsync(h->bP, Pall.data(), Pall.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dQ, Qm.data(), Qm.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dR, Rm.data(), Rm.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dS, Sm.data(), Sm.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(dQ, Qup, qn * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(dR, Rup, rn * sizeof(double), hipMemcpyHostToDevice, st));
+    if (s_given) HIP_TRY(h, hipMemcpyAsync(dS, Sup, sn * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(h, hipMemsetAsync(h->bFlag, 0, b * sizeof(int), st));
     tr("weights alloc + copies queued");
     h->bP_stride = p_inst ? (long)n * n : 0;
@@ -2114,10 +2148,12 @@ int batched_design_front(almpc_handle* h, const double* A_batch, const double* B
         tr("k_c2d");
     }
     if (dev_dare) {
-        ALMPC_TRY(design_dare_device(h, dQ, dR, Rm, h->P));
+        ALMPC_TRY(design_dare_device(h, dQ, dR, Rm, h->P, wi ? (long)n * n : 0, wi ? (long)m * m : 0));
         tr("k_dare");
     }
     d.ds = batched_strides(h, p_inst);
+    if (wi) { d.ds.Q = (long)n * n; d.ds.R = (long)m * m; d.ds.S = s_given ? (long)m * m : 0; }
+    d.dQ = dQ; d.dR = dR; d.dS = dS;
     return ALMPC_OK;
 }
 
@@ -2146,17 +2182,19 @@ int batched_design_readback(almpc_handle* h, BatchedDesign& d, const double* umi
 // almpc_design_batched on a condensed handle: every instance gets its own condensed QP from (A_i, B_i).  The design kernels of
 // almpc_design.hip.h run with blockIdx.y = instance; the per-step path is k_admm_inst + k_polish<false> with strides.
 int design_batched_condensed(almpc_handle* h, const double* A_batch, const double* B_batch, const double* Q, const double* R, const double* S,
-                             const double* P, int P_per_instance, const double* umin, const double* umax, double rho, double sigma) {
+                             const double* P, int P_per_instance, const double* umin, const double* umax, double rho, double sigma,
+                             const InstanceWeights* wi = nullptr) {
     BatchedDesign d;
-    ALMPC_TRY(batched_design_front(h, A_batch, B_batch, Q, R, S, P, P_per_instance, umin, umax, rho, sigma, d));
+    ALMPC_TRY(batched_design_front(h, A_batch, B_batch, Q, R, S, P, P_per_instance, umin, umax, rho, sigma, d, wi));
     const DesignStrides& ds = d.ds;
     const int n = h->n, useR = d.useR, useS = d.useS;
-    double *dQ = h->wQ, *dR = h->wR, *dS = h->wS;
-    HIP_TRY(h, launch_batched_design(h, ds, useR, useS, dQ, dR, dS, rho, sigma, false));
+    HIP_TRY(h, launch_batched_design(h, ds, useR, useS, d.dQ, d.dR, d.dS, rho, sigma, false));
     if (h->mc > 0) HIP_TRY(h, launch_ghat_inst(h, nullptr, nullptr));
     ALMPC_TRY(batched_design_readback(h, d, umin, umax));
     h->sd.ready = false;
-    if (h->fallback) {
+    // (per-instance weights: the stage-wise solvers take shared weights, so no redo covers this design -- run_step, step_redo)
+    h->weighted = wi != nullptr; h->wiS_given = wi && wi->S;
+    if (h->fallback && !wi) {
         h->r_batched_P = true; h->rP_stride = d.p_inst ? (long)n * n : 0;
         // (one stage of records per instance when the terminal weight is the instance's own DARE solution; the stage records are
         // computed when a step leaves instances to redo, for those instances only: nothing here)
@@ -2709,7 +2747,7 @@ int step_redo(Step& s) {
         h->redo.lazy_pending = true;   // (resolve_lazy_redo at the next host sync point)
         return ALMPC_OK;
     }
-    if (!h->fallback || h->ltv || !s.o.polish) return ALMPC_OK;
+    if (!h->fallback || h->ltv || h->weighted || !s.o.polish) return ALMPC_OK;
     return launch_redo(h, SolveCall(), !h->sw.dbg_no_sdual_fb, !h->sw.dbg_no_primal_net);   // (right behind the step: its x0 is still the handle's)
 }
 
@@ -2737,7 +2775,7 @@ int run_step(almpc_handle* h, const almpc_opts& o, StepMode mode) {
     // polish_gen_body with state rows --: shared model, per-instance models, re-linearisation pipeline.  Infeasible instances keep
     // their verdict and are not counted; what is counted is rare -- a handful of edge-of-feasibility instances in 4096 -- and a
     // stage-wise solve of one of them takes about a millisecond, which an eager redo would put behind every step)
-    const bool lazy_redo = h->fallback == 2 && !h->structured && !h->ltv && o.polish != 0 &&
+    const bool lazy_redo = h->fallback == 2 && !h->structured && !h->ltv && !h->weighted && o.polish != 0 &&
                            (h->sd.ready || (h->mc == 0 && h->rKst)) && !h->sw.eager_redo;
     HIP_TRY(h, hipSetDevice(h->device));
     if (h->io.big_copy_pending) {   // an asynchronous read-back straight from the result buffers: this step overwrites them
@@ -2804,6 +2842,74 @@ int almpc_design_batched(almpc_handle* h, const double* A_batch, const double* B
     drop_lazy_redo(h);
     return h->structured ? design_batched_structured(h, A_batch, B_batch, Q, R, S, P, P_per_instance, umin, umax)
                          : design_batched_condensed(h, A_batch, B_batch, Q, R, S, P, P_per_instance, umin, umax, rho, sigma);
+}
+
+// One weight set per instance: see include/almpc.h.  The checks that are this call's own, every set symmetrised, then the condensed
+// per-instance design with strides on its weights.
+int almpc_design_batched_weighted(almpc_handle* h, const double* A_batch, const double* B_batch, const double* Q_batch, const double* R_batch,
+                                  const double* S_batch, const double* P, int P_per_instance, const double* umin, const double* umax,
+                                  double rho, double sigma) {
+    if (!h) return ALMPC_ERR_INVALID;
+    if (!A_batch || !B_batch || !Q_batch || !R_batch || !umin || !umax) return fail(h, ALMPC_ERR_INVALID, "design_batched_weighted: null matrix pointer");
+    if (h->structured)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "design_batched_weighted: an ALMPC_FLAG_STRUCTURED handle's solvers (k_sgains, k_riccati, k_sdual) take shared weights");
+    if (h->fallback == 1)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "design_batched_weighted: almpc_set_structured_fallback(h, 1) asks for a stage-wise redo, whose solvers take shared weights");
+    const int n = h->n, m = h->m;
+    const size_t b = (size_t)h->batch, nn = (size_t)n * n, mm = (size_t)m * m;
+    // the branch rule (src/sub/design_mpc.jl:423-456) is one choice per launch: every instance has to take instance 0's
+    for (size_t i = 1; i < b; ++i) {
+        if ((R_batch[i * mm] != 0.0) != (R_batch[0] != 0.0))
+            return fail(h, ALMPC_ERR_INVALID, "design_batched_weighted: R[1,1] == 0 for some instances and not for others (the branch is one for the batch): instance " + std::to_string(i));
+        if (S_batch && (S_batch[i * mm] != 0.0) != (S_batch[0] != 0.0))
+            return fail(h, ALMPC_ERR_INVALID, "design_batched_weighted: S[1,1] == 0 for some instances and not for others (the branch is one for the batch): instance " + std::to_string(i));
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (nothing of an earlier design still reads the staging buffers)
+    HIP_TRY(h, h->hQi.grow(b * nn));
+    HIP_TRY(h, h->hRi.grow(b * mm));
+    if (S_batch) HIP_TRY(h, h->hSi.grow(b * mm));
+    const InstanceWeights wi{h->hQi, h->hRi, S_batch ? h->hSi.get() : nullptr};
+    // (hm::symmetrised's arithmetic, written into place: no vector per matrix)
+    const auto sym_into = [](const double* M, int k, double* o) {
+        for (int j = 0; j < k; ++j) {
+            o[(size_t)j * k + j] = M[(size_t)j * k + j];
+            for (int i = 0; i < j; ++i) o[(size_t)j * k + i] = o[(size_t)i * k + j] = 0.5 * (M[(size_t)j * k + i] + M[(size_t)i * k + j]);
+        }
+    };
+    for (size_t i = 0; i < b; ++i) {
+        sym_into(Q_batch + i * nn, n, h->hQi + i * nn);
+        sym_into(R_batch + i * mm, m, h->hRi + i * mm);
+        if (S_batch) sym_into(S_batch + i * mm, m, h->hSi + i * mm);
+    }
+    drop_lazy_redo(h);
+    return design_batched_condensed(h, A_batch, B_batch, Q_batch, R_batch, S_batch, P, P_per_instance, umin, umax, rho, sigma, &wi);
+}
+
+// parity hook: the weights instance i is designed on, as the design kernels read them (symmetrised); the shared set for every i
+// unless the design is almpc_design_batched_weighted's
+int almpc_get_weights_instance(almpc_handle* h, int instance, double* Q, double* R, double* S) {
+    if (!h) return ALMPC_ERR_INVALID;
+    if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, "get_weights_instance before design");
+    if (instance < 0 || instance >= h->batch) return fail(h, ALMPC_ERR_INVALID, "get_weights_instance: instance out of range");
+    const size_t nn = (size_t)h->n * h->n, mm = (size_t)h->m * h->m, i = (size_t)instance;
+    if (!h->weighted) {
+        if (h->sens.Q.size() != nn || h->sens.R.size() != mm || h->hS.size() != mm)
+            return fail(h, ALMPC_ERR_UNSUPPORTED, "get_weights_instance: this design keeps no host copy of its weights (condensed almpc_design_shared / _batched do)");
+        if (Q) std::copy(h->sens.Q.begin(), h->sens.Q.end(), Q);
+        if (R) std::copy(h->sens.R.begin(), h->sens.R.end(), R);
+        if (S) std::copy(h->hS.begin(), h->hS.end(), S);
+        return ALMPC_OK;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (Q) HIP_TRY(h, hipMemcpy(Q, h->wiQ + i * nn, nn * sizeof(double), hipMemcpyDeviceToHost));
+    if (R) HIP_TRY(h, hipMemcpy(R, h->wiR + i * mm, mm * sizeof(double), hipMemcpyDeviceToHost));
+    if (S) {
+        if (!h->wiS_given) std::fill(S, S + mm, 0.0);   // (no S_batch: S = 0 everywhere)
+        else HIP_TRY(h, hipMemcpy(S, h->wiS + i * mm, mm * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return ALMPC_OK;
 }
 
 // Time-varying models: see include/almpc.h.  The host prepares ebar = xbar - x_ref (stages 1..N), the input part of the
@@ -3805,15 +3911,19 @@ int almpc_set_reference(almpc_handle* h, const double* xref, const double* uref,
     HIP_TRY(h, hipMemcpy(h->dXref, xref, cnt * xs * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->dUref, uref, cnt * us * sizeof(double), hipMemcpyHostToDevice));
     // fS = d .* (2 D'Sbar D u_ref): the input-rate cost is on u, not e_u (src/sub/design_mpc.jl:423-446)
-    std::vector<double> fS(cnt * us, 0.0);
+    // (per-instance weights with an input-rate term: one vector per instance, from S_i, whatever the reference's form)
+    const bool s_inst = h->weighted && h->useS && h->wiS_given;
+    const size_t gcnt = s_inst ? (size_t)h->batch : cnt;
+    std::vector<double> fS(gcnt * us, 0.0);
     if (h->useS) {  // S counts only together with R (the reference's branch rule, src/sub/design_mpc.jl:423-466), as in the design kernels
-        for (size_t c = 0; c < cnt; ++c) {
-            const double* ur = uref + c * us;
+        for (size_t c = 0; c < gcnt; ++c) {
+            const double* ur = uref + (per_instance ? c : 0) * us;
+            const double* Sw = s_inst ? h->hSi + c * m * m : h->hS.data();
             double* f = fS.data() + c * us;
             for (int i = 0; i + 1 < N; ++i)
                 for (int a = 0; a < m; ++a) {
                     double sd = 0.0;  // (S (u_i - u_{i+1}))_a
-                    for (int b2 = 0; b2 < m; ++b2) sd += h->hS[(size_t)b2 * m + a] * (ur[i * m + b2] - ur[(i + 1) * m + b2]);
+                    for (int b2 = 0; b2 < m; ++b2) sd += Sw[(size_t)b2 * m + a] * (ur[i * m + b2] - ur[(i + 1) * m + b2]);
                     f[i * m + a] += 2.0 * sd;
                     f[(i + 1) * m + a] -= 2.0 * sd;
                 }
@@ -3827,10 +3937,10 @@ int almpc_set_reference(almpc_handle* h, const double* xref, const double* uref,
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     } else if (h->batched) {  // fS_i = d_i .* g and v0S_i = -G_i fS_i on the device, one vector per instance
         DevBuf<double> dGs;
-        HIP_TRY(h, dGs.alloc(cnt * us));
-        hipError_t e = hipMemcpy(dGs, fS.data(), cnt * us * sizeof(double), hipMemcpyHostToDevice);
+        HIP_TRY(h, dGs.alloc(gcnt * us));
+        hipError_t e = hipMemcpy(dGs, fS.data(), gcnt * us * sizeof(double), hipMemcpyHostToDevice);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_fs_scale, dim3(256), dim3(256), 0, h->stream, h->batch, nz, h->nzs, dGs, per_instance ? (long)us : 0L,
+            hipLaunchKernelGGL(k_fs_scale, dim3(256), dim3(256), 0, h->stream, h->batch, nz, h->nzs, dGs, (per_instance || s_inst) ? (long)us : 0L,
                                h->bD, h->dFS);
             hipLaunchKernelGGL(k_neg_gm, dim3(1, (unsigned)h->batch), dim3(256), 0, h->stream, nz, h->nzs, 1, (int)us, h->bG, h->dFS,
                                h->dV0S, (long)nz * h->nzs, (long)us);
@@ -4538,7 +4648,7 @@ int sens_params_vjp(almpc_handle* h, const double* g_u, const double* g_x, doubl
     const size_t off_ur = 0, off_Q = off_ur + b * nz, off_P = off_Q + b * n * n, off_A = off_P + b * n * n, off_R = off_A + b * n * n,
                  off_S = off_R + b * m * m, off_B = off_S + b * m * m, out_total = off_B + b * n * m;
     if (want2) {
-        if (!h->sens.w_ok) {   // (once per design, in stream order in front of k_sens_params)
+        if (!h->sens.w_ok && !h->weighted) {   // (once per design, in stream order in front of k_sens_params; per-instance weights are on the device already)
             HIP_TRY(h, h->sens.W.grow(2 * n * n + 2 * m * m));
             if (h->sens.R.size() == m * m)
                 HIP_TRY(h, hipMemcpyAsync(h->sens.W + 2 * n * n + m * m, h->sens.R.data(), m * m * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -4554,6 +4664,7 @@ int sens_params_vjp(almpc_handle* h, const double* g_u, const double* g_x, doubl
         q.n = ni; q.m = mi; q.N = h->N; q.nz = nz; q.batch = h->batch; q.useR = h->sens.useR; q.useS = h->useS;
         q.A = p.A; q.A_stride = p.A_stride; q.B = p.B; q.B_stride = p.B_stride;
         q.Q = h->sens.W; q.S = h->sens.W + n * n;
+        if (h->weighted) { q.Q = h->wiQ; q.Q_stride = (long)(n * n); q.S = h->useS ? h->wiS.get() : nullptr; q.S_stride = h->useS ? (long)(m * m) : 0; }
         if (h->batched) { q.P = h->bP; q.P_stride = h->bP_stride; }
         else { q.P = h->sens.W + n * n + m * m; q.P_stride = 0; }
         q.ex = h->dEx; q.ev = h->dEu; q.u = h->dU; q.g_u = p.g_u; q.g_x = p.g_x; q.z = p.z; q.nu = p.nu; q.rows = p.rows;
@@ -4573,6 +4684,7 @@ int sens_params_vjp(almpc_handle* h, const double* g_u, const double* g_x, doubl
             vp.A = q.A; vp.A_stride = q.A_stride; vp.B = q.B; vp.B_stride = q.B_stride; vp.P = q.P; vp.P_stride = q.P_stride;
             vp.gP = o + off_P; vp.gP_stride = (long)(n * n);
             vp.Q = h->sens.W; vp.R = h->sens.W + 2 * n * n + m * m;
+            if (h->weighted) { vp.Q = h->wiQ; vp.Q_stride = (long)(n * n); vp.R = h->wiR; vp.R_stride = (long)(m * m); }
             vp.gA = q.gA; vp.gA_stride = (long)(n * n); vp.gB = q.gB; vp.gB_stride = (long)(n * m);
             vp.gQ = q.gQ; vp.gQ_stride = (long)(n * n); vp.gR = q.gR; vp.gR_stride = (long)(m * m);
             vp.accumulate = 1; vp.rows = p.rows; vp.status = h->sens.dstat; vp.lds_per_wave = 0;

@@ -26,7 +26,8 @@ struct DareParams {
     int n, m, batch;
     const double* A; long A_stride;    // n x n column-major per instance
     const double* B; long B_stride;    // n x m
-    const double* Q; const double* R;  // shared, n x n and m x m
+    const double* Q; const double* R;  // n x n and m x m: shared (strides 0), or one pair per instance
+    long Q_stride = 0, R_stride = 0;
     double* P; long P_stride;          // n x n per instance: written only for an instance that is accepted ...
     const double* fallback;            // ... or, when non-null, with this shared n x n matrix for one that is not
     int32_t* status;                   // [batch] 0 accepted; 1 singular pivot, 2 no fixed point / not finite, 3 residual too large
@@ -163,15 +164,17 @@ __global__ __launch_bounds__(64 * DARE_WAVES) void k_dare(DareParams p) {
     for (int inst = blockIdx.x * wpb + wv; inst < p.batch; inst += nwaves) {
         const double* Ag = p.A + (size_t)inst * p.A_stride;
         const double* Bg = p.B + (size_t)inst * p.B_stride;
+        const double* Qg = p.Q + (size_t)inst * p.Q_stride;
+        const double* Rg = p.R + (size_t)inst * p.R_stride;
         int st = 0;
         dare_fence();
         // G0 = B R^-1 B': R X = B' by the same solve, then B X.  Ak = A, Hk = Q.
         if (row < n) {
-            for (int j = cg; j < n; j += CG) { Ak[row + j * ld] = Ag[row + j * n]; Hk[row + j * ld] = p.Q[row + j * n]; }
+            for (int j = cg; j < n; j += CG) { Ak[row + j * ld] = Ag[row + j * n]; Hk[row + j * ld] = Qg[row + j * n]; }
             for (int a = cg; a < m; a += CG) W[row + a * ld] = Bg[row + a * n];          // B (n x m) in W for now
         }
         if (row < m) {
-            for (int b = cg; b < m; b += CG) Sm[row + b * ld] = p.R[row + b * m];
+            for (int b = cg; b < m; b += CG) Sm[row + b * ld] = Rg[row + b * m];
             for (int j = cg; j < n; j += CG) XA[row + j * ld] = Bg[j + row * n];         // B' (m x n)
         }
         dare_fence();
@@ -229,7 +232,7 @@ __global__ __launch_bounds__(64 * DARE_WAVES) void k_dare(DareParams p) {
                 for (int j = cg; j < n; j += CG) {
                     Ak[row + j * ld] = Ag[row + j * n];
                     pmax = fmax(pmax, fabs(Hk[row + j * ld]));
-                    qmax = fmax(qmax, fabs(p.Q[row + j * n]));
+                    qmax = fmax(qmax, fabs(Qg[row + j * n]));
                 }
                 for (int a = cg; a < m; a += CG) Gk[row + a * ld] = Bg[row + a * n];     // B in Gk
             }
@@ -242,7 +245,7 @@ __global__ __launch_bounds__(64 * DARE_WAVES) void k_dare(DareParams p) {
                 for (int b = cg; b < m; b += CG) {
                     double acc = 0.0;
                     for (int l = 0; l < n; ++l) acc += Gk[l + row * ld] * W[l + b * ld];
-                    Sm[row + b * ld] = acc + p.R[row + b * m];
+                    Sm[row + b * ld] = acc + Rg[row + b * m];
                 }
             dare_fence();
             dare_mul<RL, true, false>(Gk, Ak, W, nullptr, n, n, m, ld, lane);            // A'PB over B (B was last read before the fence)
@@ -256,7 +259,7 @@ __global__ __launch_bounds__(64 * DARE_WAVES) void k_dare(DareParams p) {
                     double acc = 0.0, corr = 0.0;
                     for (int l = 0; l < n; ++l) acc += Ak[l + row * ld] * XG[l + j * ld];
                     for (int a = 0; a < m; ++a) corr += Gk[row + a * ld] * XA[a + j * ld];
-                    const double res = acc + (p.Q[row + j * n] - Hk[row + j * ld] - corr);
+                    const double res = acc + (Qg[row + j * n] - Hk[row + j * ld] - corr);
                     rmax = fmax(rmax, fabs(res));
                     notfin = notfin || !(fabs(res) <= 1.7976931348623157e308);
                 }

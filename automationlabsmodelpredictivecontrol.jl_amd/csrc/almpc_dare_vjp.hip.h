@@ -31,7 +31,8 @@ struct DareVjpParams {
     const double* B; long B_stride;    // n x m
     const double* P; long P_stride;    // n x n: a solution of the instance's DARE (tested)
     const double* gP; long gP_stride;  // n x n symmetric dL/dP
-    const double* Q; const double* R;  // shared, n x n and m x m
+    const double* Q; const double* R;  // n x n and m x m: shared (strides 0), or one pair per instance
+    long Q_stride = 0, R_stride = 0;
     double* gA; long gA_stride;        // outputs, each may be null
     double* gB; long gB_stride;
     double* gQ; long gQ_stride;
@@ -62,6 +63,8 @@ __global__ __launch_bounds__(64 * DARE_WAVES) void k_dare_vjp(DareVjpParams p) {
         const double* Bg = p.B + (size_t)inst * p.B_stride;
         const double* Pg = p.P + (size_t)inst * p.P_stride;
         const double* Gg = p.gP + (size_t)inst * p.gP_stride;
+        const double* Qg = p.Q + (size_t)inst * p.Q_stride;
+        const double* Rg = p.R + (size_t)inst * p.R_stride;
         int st = 0;
         dare_fence();
         // ---- 1. the residual of the equation, as k_dare's last block: S0 = A, S1 = P, S2 = B
@@ -72,7 +75,7 @@ __global__ __launch_bounds__(64 * DARE_WAVES) void k_dare_vjp(DareVjpParams p) {
                 const double pv = Pg[row + j * n];
                 S1[row + j * ld] = pv;
                 pmax = fmax(pmax, fabs(pv));
-                qmax = fmax(qmax, fabs(p.Q[row + j * n]));
+                qmax = fmax(qmax, fabs(Qg[row + j * n]));
             }
             for (int a = cg; a < m; a += CG) S2[row + a * ld] = Bg[row + a * n];
         }
@@ -85,7 +88,7 @@ __global__ __launch_bounds__(64 * DARE_WAVES) void k_dare_vjp(DareVjpParams p) {
             for (int b = cg; b < m; b += CG) {
                 double acc = 0.0;
                 for (int l = 0; l < n; ++l) acc += S2[l + row * ld] * S4[l + b * ld];
-                Sm[row + b * ld] = acc + p.R[row + b * m];
+                Sm[row + b * ld] = acc + Rg[row + b * m];
             }
         dare_fence();
         dare_mul<RL, true, false>(S2, S0, S4, nullptr, n, n, m, ld, lane);           // A'PB over B (B was last read before the fence)
@@ -98,7 +101,7 @@ __global__ __launch_bounds__(64 * DARE_WAVES) void k_dare_vjp(DareVjpParams p) {
                     double acc = 0.0, corr = 0.0;
                     for (int l = 0; l < n; ++l) acc += S0[l + row * ld] * S3[l + j * ld];
                     for (int a = 0; a < m; ++a) corr += S2[row + a * ld] * S5[a + j * ld];
-                    const double res = acc + (p.Q[row + j * n] - S1[row + j * ld] - corr);
+                    const double res = acc + (Qg[row + j * n] - S1[row + j * ld] - corr);
                     rmax = fmax(rmax, fabs(res));
                     notfin = notfin || !(fabs(res) <= 1.7976931348623157e308);
                 }

@@ -28,6 +28,7 @@ struct DesignStrides {
     long A = 0, B = 0, P = 0, Phi = 0, Gk = 0, Gam = 0, WP = 0, H = 0, F = 0, d = 0, Hs = 0, Fs = 0, G = 0, Minv = 0, rho = 0,
          flag = 0;
     int h_symmetric = 0;   // H is symmetric by construction (k_design_instance): k_design_scale skips its transposed, uncoalesced read
+    long Q = 0, R = 0, S = 0;   // the weights: shared (0), or one set per instance (almpc_design_batched_weighted)
 };
 
 // ---- K1/K2 -------------------------------------------------------------------------------------
@@ -72,7 +73,7 @@ inline __global__ __launch_bounds__(256) void k_design_gamma(int n, int m, int N
                                                       const double* Phi, const double* Gk, double* Gam, double* W,
                                                       double* WP, int gs, int ps, DesignStrides st) {
     const int k = blockIdx.x;
-    P += blockIdx.y * st.P; Phi += blockIdx.y * st.Phi; Gk += blockIdx.y * st.Gk;
+    Q += blockIdx.y * st.Q; P += blockIdx.y * st.P; Phi += blockIdx.y * st.Phi; Gk += blockIdx.y * st.Gk;
     Gam += blockIdx.y * st.Gam; W += blockIdx.y * st.Gam; WP += blockIdx.y * st.WP;
     const double* Qk = (k == N - 1) ? P : Q;  // stage N+1 carries only P (src/sub/design_mpc.jl:448-456)
     const int nz = m * N;
@@ -118,6 +119,7 @@ inline __global__ __launch_bounds__(768) void k_design_hessian(HessParams p) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     p.Gam += blockIdx.y * p.st.Gam; p.W += blockIdx.y * p.st.Gam; p.WP += blockIdx.y * p.st.WP;
     p.H += blockIdx.y * p.st.H; p.F += blockIdx.y * p.st.F;
+    p.R += blockIdx.y * p.st.R; p.S += blockIdx.y * p.st.S;   // (read under useR / useS only)
     const int ws = p.gs + 16, pps = p.ps + 16;  // padded LDS strides: the 4 k-groups of a B read hit different banks
     double* GI = smem;                       // [KC][16]
     double* Wc = GI + HESS_KC * 16;          // [KC][ws]

@@ -398,6 +398,27 @@ int almpc_group_design_batched(almpc_group* g, const double* A_batch, const doub
     });
 }
 
+// ... and one weight set per instance as well: Q_batch [batch][n*n], R_batch, S_batch (or NULL) [batch][m*m] cut along the shards.  The
+// branch rule holds for the whole batch, not shard by shard: tested here, with the batch's instance numbers
+int almpc_group_design_batched_weighted(almpc_group* g, const double* A_batch, const double* B_batch, const double* Q_batch, const double* R_batch,
+                                        const double* S_batch, const double* P, int P_per_instance, const double* umin, const double* umax,
+                                        double rho, double sigma) {
+    if (!g) return ALMPC_ERR_INVALID;
+    if (!A_batch || !B_batch || !Q_batch || !R_batch) { g->err = "design_batched_weighted: null matrix pointer"; return ALMPC_ERR_INVALID; }
+    const size_t nn = (size_t)g->n * g->n, nm = (size_t)g->n * g->m, mm = (size_t)g->m * g->m;
+    for (size_t i = 1; i < (size_t)g->batch; ++i)
+        if ((R_batch[i * mm] != 0.0) != (R_batch[0] != 0.0) || (S_batch && (S_batch[i * mm] != 0.0) != (S_batch[0] != 0.0))) {
+            g->err = "design_batched_weighted: R[1,1] == 0 or S[1,1] == 0 for some instances and not for others (the branch is one for the batch): instance " + std::to_string(i);
+            return ALMPC_ERR_INVALID;
+        }
+    return group_fanout(g, [&](int i) {
+        const size_t f = (size_t)g->first[i];
+        return almpc_design_batched_weighted(g->hs[i], A_batch + f * nn, B_batch + f * nm, Q_batch + f * nn, R_batch + f * mm,
+                                             S_batch ? S_batch + f * mm : nullptr, (P && P_per_instance) ? P + f * nn : P, P_per_instance,
+                                             umin, umax, rho, sigma);
+    });
+}
+
 // the re-linearisation pipeline of a black-box Fnn model (BASELINE configs[3]) on every device: shared network and references
 int almpc_group_relin_fnn_setup(almpc_group* g, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
                                 const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,

@@ -796,7 +796,8 @@ inline __global__ __launch_bounds__(256) void k_guess_shift(AdmmInstParams p, co
 struct DesignInstParams {
     int n, m, N, nz, useR, useS;
     const double* A; const double* B; const double* P; long sA, sB, sP;   // per instance
-    const double* Q; const double* R; const double* S;                     // shared
+    const double* Q; const double* R; const double* S;                     // shared (sQ = sR = sS = 0), or one set per instance
+    long sQ = 0, sR = 0, sS = 0;                                           // (almpc_design_batched_weighted)
     double* H; double* F; long sH, sF;                                     // column-major nz x nz, nz x n
     int* flag = nullptr; long sFlag = 0;                                   // design flag of the instance: cleared here when given (instead of
                                                                            // by a memset launch in front of every re-design)
@@ -822,6 +823,9 @@ __global__ __launch_bounds__(256) void k_design_instance_t(DesignInstParams p) {
     const double* A = p.A + blockIdx.x * p.sA;
     const double* B = p.B + blockIdx.x * p.sB;
     const double* P = p.P + blockIdx.x * p.sP;
+    const double* Q = p.Q + blockIdx.x * p.sQ;
+    const double* R = p.R + blockIdx.x * p.sR;   // (read under useR / useS only: null + 0 otherwise)
+    const double* S = p.S + blockIdx.x * p.sS;
     double* H = p.H + blockIdx.x * p.sH;
     double* F = p.F + blockIdx.x * p.sF;
     double* As = smem;             // [n][n] column-major: As[j*n+i] = A_ij
@@ -846,7 +850,7 @@ __global__ __launch_bounds__(256) void k_design_instance_t(DesignInstParams p) {
         __syncthreads();   // (A_i, B_i are in the handle's model slots now: read back below, by the step's rollout and by the redo)
     }
     if (p.flag && threadIdx.x == 0) p.flag[blockIdx.x * p.sFlag] = 0;
-    for (int t = threadIdx.x; t < nn; t += T) { As[t] = A[t]; Qs[t] = p.Q[t]; Ps[t] = P[t]; Phi[t] = (t % n == t / n) ? 1.0 : 0.0; }
+    for (int t = threadIdx.x; t < nn; t += T) { As[t] = A[t]; Qs[t] = Q[t]; Ps[t] = P[t]; Phi[t] = (t % n == t / n) ? 1.0 : 0.0; }
     for (int t = threadIdx.x; t < nm; t += T) Bs[t] = B[t];
     __syncthreads();
     for (int k = 1; k <= N; ++k) {  // Phi[k] = A Phi[k-1]
@@ -924,10 +928,10 @@ __global__ __launch_bounds__(256) void k_design_instance_t(DesignInstParams p) {
             for (int l = 0; l < n; ++l) sp += g[l] * pg[l];
             double v = 2.0 * (C + sp);
             const int j = i - d;
-            if (p.useR && d == 0) v += 2.0 * p.R[(size_t)qq * m + pp];
+            if (p.useR && d == 0) v += 2.0 * R[(size_t)qq * m + pp];
             if (p.useS) {  // delta_u[:,i] = u[:,i] - u[:,i+1], i = 1..N-1 (src/sub/design_mpc.jl:429-431)
-                if (d == 0) v += 2.0 * ((i <= N - 2 ? 1 : 0) + (i >= 1 ? 1 : 0)) * p.S[(size_t)qq * m + pp];
-                else if (d == 1) v -= 2.0 * p.S[(size_t)qq * m + pp];
+                if (d == 0) v += 2.0 * ((i <= N - 2 ? 1 : 0) + (i >= 1 ? 1 : 0)) * S[(size_t)qq * m + pp];
+                else if (d == 1) v -= 2.0 * S[(size_t)qq * m + pp];
             }
             const int row = i * m + pp, col = j * m + qq;
             H[(size_t)col * nz + row] = v;

@@ -425,7 +425,8 @@ struct SensGradParams {
     int n, m, N, nz, batch, useR, useS;
     const double* A; long A_stride;
     const double* B; long B_stride;
-    const double* Q; const double* S;           // [n][n], [m][m]: the design's weights
+    const double* Q; const double* S;           // [n][n], [m][m]: the design's weights, shared (strides 0) or one pair per instance
+    long Q_stride = 0, S_stride = 0;
     const double* P; long P_stride;
     const double* ex; const double* ev; const double* u;   // the step's e_x [batch][N+1][n], e_u and u [batch][nz]
     const double* g_u; const double* g_x;       // as k_sens (g_x may be null)
@@ -452,6 +453,8 @@ inline __global__ __launch_bounds__(256) void k_sens_params(SensGradParams p) {
         const double* A = p.A + (size_t)inst * p.A_stride;
         const double* B = p.B + (size_t)inst * p.B_stride;
         const double* P = p.P + (size_t)inst * p.P_stride;
+        const double* Q = p.Q + (size_t)inst * p.Q_stride;
+        const double* S = p.S + (size_t)inst * p.S_stride;
         const double* ex = p.ex + (size_t)inst * xs;
         const double* ev = p.ev + (size_t)inst * nz;
         const double* u = p.u + (size_t)inst * nz;
@@ -487,7 +490,7 @@ inline __global__ __launch_bounds__(256) void k_sens_params(SensGradParams p) {
                     const double* src = al ? ex + (size_t)k * n : Zt + (size_t)k * n;
                     double s = 0.0, w = 0.0;
                     for (int l = 0; l < n; ++l) s += A[l + i * n] * c[l];
-                    for (int l = 0; l < n; ++l) w += (p.Q[i + l * n] + p.Q[l + i * n]) * src[l];
+                    for (int l = 0; l < n; ++l) w += (Q[i + l * n] + Q[l + i * n]) * src[l];
                     if (!al) s += gx ? gx[(size_t)k * n + i] : 0.0;
                     s += w;
                     nxt[t] = s; (al ? At : Mt)[k * n + i] = s;
@@ -541,7 +544,7 @@ inline __global__ __launch_bounds__(256) void k_sens_params(SensGradParams p) {
                     if (p.useS) {
                         double w = 0.0;
                         for (int b = 0; b < m; ++b) {
-                            const double sab = p.S[a + b * m] + p.S[b + a * m];
+                            const double sab = S[a + b * m] + S[b + a * m];
                             if (k + 1 < N) w += sab * (z[k * m + b] - z[(k + 1) * m + b]);
                             if (k > 0) w -= sab * (z[(k - 1) * m + b] - z[k * m + b]);
                         }

@@ -250,6 +250,36 @@ int almpc_design_batched(almpc_handle* h, const double* A_batch, const double* B
                          const double* umin, const double* umax, double rho, double sigma);
 
 /*
+ * The same with one weight set PER INSTANCE (a condensed handle): Q_batch [batch][n*n], R_batch [batch][m*m], S_batch [batch][m*m] or
+ * NULL (S = 0 everywhere), each block column-major.  One plant with thousands of candidate tunings in one batch; and the design
+ * that can take back the per-instance g_Q, g_R, g_S of almpc_sensitivity_params_vjp(_dare).  Everything else is almpc_design_batched:
+ * layouts, P (NULL -> DARE(A_i, B_i, Q_i, R_i), host loop or k_dare after almpc_set_terminal_weight), almpc_set_model_time,
+ * almpc_set_state_box / almpc_set_terminal_equality, almpc_set_rho_profile; every Q_i, R_i, S_i is symmetrised where almpc_design_batched
+ * symmetrises its Q, R, S, so a batch of equal sets gives the bits of almpc_design_batched.  The step, almpc_sensitivity(_vjp) and
+ * almpc_sensitivity_params_vjp(_dare) run on the design as they do on almpc_design_batched's; almpc_set_reference forms the
+ * input-rate part of the gradient from each instance's S_i.
+ * Branch rule: R[1,1] == 0 and S[1,1] == 0 (src/sub/design_mpc.jl:423-456) are one choice per design, so every instance must take the
+ * same branch: a batch in which R_i[1,1] (or S_i[1,1]) is zero for some instances and not for others is ALMPC_ERR_INVALID, the lowest
+ * instance that differs from instance 0 named in almpc_last_error.
+ * The weights live in device buffers of the handle that only this call allocates.  A later almpc_design_batched or almpc_design_shared
+ * puts the handle back on shared weights.
+ * Not built (ALMPC_ERR_UNSUPPORTED, or as said):
+ *  - ALMPC_FLAG_STRUCTURED handles: their solvers and screens (k_sgains, k_riccati, k_sdual, k_sens_face) take shared weights;
+ *  - the stage-wise redo of a condensed handle, which runs the same kernels: after almpc_set_structured_fallback(h, 1) this call is
+ *    refused; under the default ("auto") the redo counts as not covering the design, no redo launch follows a step, and an instance
+ *    the finish leaves with ALMPC_MAX_ITER keeps that status;
+ *  - per-instance input boxes: umin, umax are shared (the step kernels read the box);
+ *  - the re-linearisation pipeline, almpc_design_ltv and the SQP loop keep shared weights: there is no weighted form of them.
+ */
+int almpc_design_batched_weighted(almpc_handle* h, const double* A_batch, const double* B_batch, const double* Q_batch /* [batch][n*n] */,
+                                  const double* R_batch /* [batch][m*m] */, const double* S_batch /* [batch][m*m] or NULL */, const double* P,
+                                  int P_per_instance, const double* umin, const double* umax, double rho, double sigma);
+/* parity hook: the weights instance i is designed on, as the design kernels read them (symmetrised; S zeros where the design has none);
+ * Q n*n, R m*m, S m*m column-major, any may be NULL.  On a design with shared weights (condensed almpc_design_shared / _batched) every
+ * instance gets that set. */
+int almpc_get_weights_instance(almpc_handle* h, int instance, double* Q, double* R, double* S);
+
+/*
  * Design with TIME-VARYING models per instance: the QP of one SQP / multiple-shooting iteration around the trajectory
  * (xbar, ubar) of every instance (BASELINE.json configs[4]: SQP outer loop around the condensed-QP kernel; the reference has no
  * such path -- its NLP methods were removed, CHANGELOG.md:5 -- so only the QP itself has a reference meaning: with
@@ -583,6 +613,11 @@ int almpc_group_set_model_time(almpc_group* g, int mode, double Ts);
 int almpc_group_design_batched(almpc_group* g, const double* A_batch, const double* B_batch, const double* Q, const double* R,
                                const double* S, const double* P, int P_per_instance, const double* umin, const double* umax, double rho,
                                double sigma);
+/* almpc_design_batched_weighted: Q_batch [batch][n*n], R_batch, S_batch (or NULL) [batch][m*m] cut along the shards as well; the branch
+ * rule holds for the whole batch */
+int almpc_group_design_batched_weighted(almpc_group* g, const double* A_batch, const double* B_batch, const double* Q_batch,
+                                        const double* R_batch, const double* S_batch, const double* P, int P_per_instance,
+                                        const double* umin, const double* umax, double rho, double sigma);
 /* almpc_relin_fnn_* (BASELINE configs[3]): the same network and references on every device; step_async + almpc_group_synchronize */
 int almpc_group_relin_fnn_setup(almpc_group* g, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
                                 const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,
@@ -747,7 +782,8 @@ int almpc_group_sensitivity_stagewise_vjp(almpc_group* g, const double* g_u, con
  * or S (R[1,1] == 0; S[1,1] == 0: src/sub/design_mpc.jl:423-456) that gradient is zero.  x_ref needs no output:
  * dL/dx_ref[:,1] = g_x[1] - x0, dL/dx_ref[:,k] = g_x[k] for k >= 2.  At a weakly active row: the derivative of the face on which every
  * flagged row is held, as above.  Outputs are per instance also where the design is shared (the caller sums over the batch), and for
- * almpc_design_batched, whose Q, R, S and box are shared by the instances.
+ * almpc_design_batched, whose Q, R, S and box are shared by the instances; almpc_design_batched_weighted is the design that takes
+ * g_Q, g_R, g_S back instance by instance (each instance's own Q_i, S_i, R_i enter its adjoint).
  * The call is synchronous and settles first like almpc_sensitivity_vjp; only the groups whose pointer is not NULL are computed and
  * copied (without u_ref, Q, P, A, R, S, B the second kernel is not launched).  Refusals are almpc_sensitivity_vjp's: ALMPC_ERR_UNSUPPORTED
  * for state rows, ALMPC_FLAG_STRUCTURED handles, almpc_design_ltv, the SQP loop and the re-linearisation pipeline; ALMPC_ERR_INVALID

@@ -17,7 +17,7 @@ export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_s
        update_initialization_async!, x0_staging, results_async, results_wait!, host_results, first_input, first_input!, ALLOW_UNSOLVED,
        HipGroup, group_design_hip, group_handle, group_shard, group_update_initialization!, group_calculate!, group_calculate_async!,
        group_synchronize!, group_read_results!, group_set_state_rows!, group_set_rho_profile!, group_set_structured_fallback!,
-       group_design_batched!, group_design_relin_fnn!, group_relin_step!, group_relin_advance!, group_advance_plant!, group_design_sqp_fnn!,
+       group_design_batched!, design_batched_weighted!, weights_instance, group_design_batched_weighted!, group_design_relin_fnn!, group_relin_step!, group_relin_advance!, group_advance_plant!, group_design_sqp_fnn!,
        group_sqp_start!, group_sqp_iterate!, group_sqp_solve!, group_set_sqp_hessian!, group_set_sqp_row_multipliers!, group_state_multipliers, group_sqp_skipped, group_x0_staging, group_update_initialization_staged!, group_results_async,
        group_results_wait!, sensitivity, device_sensitivity, sensitivity_vjp, group_sensitivity, group_sensitivity_vjp,
        sensitivity_rows, sensitivity_rows_vjp, group_sensitivity_rows, group_sensitivity_rows_vjp, sensitivity_params_vjp,
@@ -163,6 +163,36 @@ function design_batched!(mod::HipModeler, A_batch::Array{Float64,3}, B_batch::Ar
     check(mod.handle, ccall((:almpc_set_reference, libalmpc), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint),
                             mod.handle, x_ref, u_ref, 0))
     return mod
+end
+
+"""
+    design_batched_weighted!(mod, A_batch, B_batch, Q_batch, R_batch, S_batch, P, umin, umax; x_ref, u_ref)
+
+`design_batched!` with one weight set per instance (`almpc_design_batched_weighted`): `Q_batch` n x n x batch, `R_batch` and `S_batch`
+m x m x batch, `S_batch` = nothing for S = 0 everywhere.  Every instance must take the same R[1,1] == 0 / S[1,1] == 0 branch.
+"""
+function design_batched_weighted!(mod::HipModeler, A_batch::Array{Float64,3}, B_batch::Array{Float64,3}, Q_batch::Array{Float64,3},
+                                  R_batch::Array{Float64,3}, S_batch::Union{Nothing,Array{Float64,3}}, P, umin::Vector{Float64},
+                                  umax::Vector{Float64}; x_ref::Matrix{Float64}, u_ref::Matrix{Float64})
+    all(size(M, 3) == mod.batch for M in (A_batch, B_batch, Q_batch, R_batch)) || throw(DimensionMismatch("one model and one weight set per instance"))
+    S_batch === nothing || size(S_batch, 3) == mod.batch || throw(DimensionMismatch("one S per instance"))
+    pptr = P === nothing ? Ptr{Float64}(C_NULL) : pointer(P)
+    sptr = S_batch === nothing ? Ptr{Float64}(C_NULL) : pointer(S_batch)
+    pinst = (P !== nothing && ndims(P) == 3) ? 1 : 0
+    GC.@preserve P S_batch check(mod.handle, ccall((:almpc_design_batched_weighted, libalmpc), Cint,
+                   (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint,
+                    Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
+                   mod.handle, A_batch, B_batch, Q_batch, R_batch, sptr, pptr, pinst, umin, umax, mod.opts.rho, mod.opts.sigma))
+    check(mod.handle, ccall((:almpc_set_reference, libalmpc), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint),
+                            mod.handle, x_ref, u_ref, 0))
+    return mod
+end
+"the weights instance `i` is designed on, as the design kernels read them (parity hook): (Q, R, S)"
+function weights_instance(mod::HipModeler, i::Integer)
+    Q, R, S = Matrix{Float64}(undef, mod.n, mod.n), Matrix{Float64}(undef, mod.m, mod.m), Matrix{Float64}(undef, mod.m, mod.m)
+    check(mod.handle, ccall((:almpc_get_weights_instance, libalmpc), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                            mod.handle, i - 1, Q, R, S))
+    return Q, R, S
 end
 
 """
@@ -1020,6 +1050,23 @@ function group_design_batched!(g::HipGroup, A_batch::Array{Float64,3}, B_batch::
                    (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint,
                     Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
                    g.group, A_batch, B_batch, Q, R, S, pptr, pinst, umin, umax, g.opts.rho, g.opts.sigma))
+    gcheck(g.group, ccall((:almpc_group_set_reference, libalmpc), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint), g.group, x_ref, u_ref, 0))
+    return g
+end
+
+"`design_batched_weighted!` for the whole batch: `Q_batch` n x n x batch, `R_batch` / `S_batch` m x m x batch (`S_batch` may be nothing)"
+function group_design_batched_weighted!(g::HipGroup, A_batch::Array{Float64,3}, B_batch::Array{Float64,3}, Q_batch::Array{Float64,3},
+                                        R_batch::Array{Float64,3}, S_batch::Union{Nothing,Array{Float64,3}}, P, umin::Vector{Float64},
+                                        umax::Vector{Float64}; x_ref::Matrix{Float64}, u_ref::Matrix{Float64})
+    all(size(M, 3) == g.batch for M in (A_batch, B_batch, Q_batch, R_batch)) || throw(DimensionMismatch("one model and one weight set per instance"))
+    S_batch === nothing || size(S_batch, 3) == g.batch || throw(DimensionMismatch("one S per instance"))
+    pptr = P === nothing ? Ptr{Float64}(C_NULL) : pointer(P)
+    sptr = S_batch === nothing ? Ptr{Float64}(C_NULL) : pointer(S_batch)
+    pinst = (P !== nothing && ndims(P) == 3) ? 1 : 0
+    GC.@preserve P S_batch gcheck(g.group, ccall((:almpc_group_design_batched_weighted, libalmpc), Cint,
+                   (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint,
+                    Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
+                   g.group, A_batch, B_batch, Q_batch, R_batch, sptr, pptr, pinst, umin, umax, g.opts.rho, g.opts.sigma))
     gcheck(g.group, ccall((:almpc_group_set_reference, libalmpc), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint), g.group, x_ref, u_ref, 0))
     return g
 end
