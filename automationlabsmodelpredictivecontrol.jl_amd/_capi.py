@@ -166,8 +166,14 @@ def load():
     L.almpc_sensitivity_stagewise_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, _dp, _ip]
     L.almpc_group_sensitivity_stagewise.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double]
     L.almpc_group_sensitivity_stagewise_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, _dp, _ip]
+    L.almpc_sensitivity_stagewise_rate.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double]
+    L.almpc_sensitivity_stagewise_rate_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, _dp, _ip]
+    L.almpc_group_sensitivity_stagewise_rate.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double]
+    L.almpc_group_sensitivity_stagewise_rate_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, _dp, _ip]
     for nm_ in ("almpc_sensitivity", "almpc_get_sensitivity", "almpc_device_sensitivity", "almpc_sensitivity_vjp",
                 "almpc_sensitivity_stagewise", "almpc_sensitivity_stagewise_vjp",
+                "almpc_sensitivity_stagewise_rate", "almpc_sensitivity_stagewise_rate_vjp",
+                "almpc_group_sensitivity_stagewise_rate", "almpc_group_sensitivity_stagewise_rate_vjp",
                 "almpc_group_sensitivity_stagewise", "almpc_group_sensitivity_stagewise_vjp",
                 "almpc_sensitivity_params_vjp", "almpc_group_sensitivity_params_vjp",
                 "almpc_sensitivity_params_vjp_dare", "almpc_group_sensitivity_params_vjp_dare",
@@ -1098,6 +1104,18 @@ class Solver:
         """sensitivity_vjp on a structured handle (almpc_sensitivity_stagewise_vjp): (g_x0 (batch, n), rows (batch,))."""
         return _sens_vjp(self.L.almpc_sensitivity_stagewise_vjp, self.h, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
 
+    def sensitivity_stagewise_rate(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
+        """sensitivity_stagewise for every structured input-box design, with or without an input-rate weight S
+        (almpc_sensitivity_stagewise_rate + almpc_get_sensitivity): with S the recursion runs in the stage state [dx_k; du_(k-1)]
+        (k_sens_face_rate), without it the call is sensitivity_stagewise to the byte."""
+        self._check(self.L.almpc_sensitivity_stagewise_rate(self.h, _sens_mask(want), float(act_tol)))
+        return _sens_read(self.L.almpc_get_sensitivity, self.h, self._check, want, self.batch, self.n, self.m, self.N)
+
+    def sensitivity_stagewise_rate_vjp(self, g_u, g_x=None, act_tol=0.0):
+        """sensitivity_stagewise_vjp for designs with or without S (almpc_sensitivity_stagewise_rate_vjp): (g_x0 (batch, n), rows (batch,))."""
+        return _sens_vjp(self.L.almpc_sensitivity_stagewise_rate_vjp, self.h, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m,
+                         self.N)
+
     def sensitivity_params_vjp(self, g_u, g_x=None, want=PARAM_GROUPS, act_tol=0.0, terminal="data") -> dict:
         """Gradients of the loss of sensitivity_vjp in the problem data, per instance (almpc_sensitivity_params_vjp): x0, the QP's
         linear term f, u_ref, the input box, the weights Q, P, R, S and the model A, B -- what `want` names -- and rows.  For a shared
@@ -1484,6 +1502,16 @@ class Group:
         """Solver.sensitivity_stagewise_vjp for the whole batch (almpc_group_sensitivity_stagewise_vjp)."""
         return _sens_vjp(self.L.almpc_group_sensitivity_stagewise_vjp, self.g, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m,
                          self.N)
+
+    def sensitivity_stagewise_rate(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
+        """Solver.sensitivity_stagewise_rate for the whole batch (almpc_group_sensitivity_stagewise_rate + almpc_group_get_sensitivity)."""
+        self._check(self.L.almpc_group_sensitivity_stagewise_rate(self.g, _sens_mask(want), float(act_tol)))
+        return _sens_read(self.L.almpc_group_get_sensitivity, self.g, self._check, want, self.batch, self.n, self.m, self.N)
+
+    def sensitivity_stagewise_rate_vjp(self, g_u, g_x=None, act_tol=0.0):
+        """Solver.sensitivity_stagewise_rate_vjp for the whole batch (almpc_group_sensitivity_stagewise_rate_vjp)."""
+        return _sens_vjp(self.L.almpc_group_sensitivity_stagewise_rate_vjp, self.g, self._check, g_u, g_x, act_tol, self.batch, self.n,
+                         self.m, self.N)
 
     def sensitivity_params_vjp(self, g_u, g_x=None, want=PARAM_GROUPS, act_tol=0.0, terminal="data") -> dict:
         """Solver.sensitivity_params_vjp for the whole batch (almpc_group_sensitivity_params_vjp, almpc_group_sensitivity_params_vjp_dare)."""

@@ -260,7 +260,10 @@ struct almpc_handle {
         DevBuf<double> pout;            // k_sens_params' outputs: u_ref, Q, P, A, R, S, B, each [batch][its size]
         DevBuf<double> traj;            // [workgroups][3][(N+1) n] zeta, mu, al of the instance a workgroup is at
         DevBuf<int32_t> dstat;          // [batch] k_dare_vjp's status words (almpc_sensitivity_params_vjp_dare)
-        DevBuf<double> Kst;             // [batch][N][m n] stage gains of k_sens_face (almpc_sensitivity_stagewise with dU or dX)
+        DevBuf<double> Kst;             // [batch][N][m n] stage gains of k_sens_face (almpc_sensitivity_stagewise with dU or dX);
+                                        // [batch][N][m (n + m)] those of k_sens_face_rate
+        DevBuf<double> S;               // [m*m] the design's input-rate weight for k_sens_face_rate (h->hS; shared on every structured design)
+        bool s_ok = false;              // ... of the current design
     } sens;
     // stage-wise dual active-set solve (k_sdual, csrc/almpc_sdual.hip.h): input box, state box, terminal equality and S in the
     // multiple-shooting form; stage records of the unconstrained problem (shared: host Riccati at design time)
@@ -1218,7 +1221,7 @@ int wait_and_settle(almpc_handle* h, bool blocking_only = false) {
 
 // A new design voids a redo that was deferred for a step of the previous one (its models, references and results are about to go)
 void drop_lazy_redo(almpc_handle* h) {
-    h->sens.stepped = false; h->sens.v_ok = false; h->sens.t1_ok = false; h->sens.w_ok = false; h->sens.have = 0;   // (what a sensitivity call looks at goes with the design as well)
+    h->sens.stepped = false; h->sens.v_ok = false; h->sens.t1_ok = false; h->sens.w_ok = false; h->sens.s_ok = false; h->sens.have = 0;   // (what a sensitivity call looks at goes with the design as well)
     h->redo.lazy_pending = false;
     h->redo.expected = false;
     h->weighted = false;   // (almpc_design_batched_weighted sets it again behind this call)
@@ -4815,6 +4818,102 @@ int sens_face_vjp(almpc_handle* h, const double* g_u, const double* g_x, double 
     return ALMPC_OK;
 }
 
+// ---- ... and with the input-rate weight S (k_sens_face_rate): the recursion in the stage state [dx_k; du_(k-1)] ----
+
+// What almpc_sensitivity_stagewise_rate can look at: the last step of a structured design with an input box only, with or without S
+int sens_face_rate_check(almpc_handle* h, const char* who) {
+    if (!h) return ALMPC_ERR_INVALID;
+    const std::string w(who);
+    if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, w + " before design");
+    if (!h->structured) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the handle is a condensed one, whose sensitivities come from G = H'^-1 (almpc_sensitivity)");
+    if (h->ltv || h->sqp.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": time-varying and SQP designs solve for a step around a trajectory, not for u(x0)");
+    if (h->relin.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the re-linearisation pipeline's models depend on x0 themselves");
+    if (h->has_box || h->terminal_eq || (h->sd.ready && (h->sd.has_box || h->sd.has_eq)))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": state rows (state box, terminal equality) are not held on the face of the stage-wise recursion");
+    if (!h->rQ || !h->rR || !(h->r_batched_P ? h->bP.get() : h->rP.get()))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the shape is outside the primal stage-wise solver, whose weights the recursion reads (n <= 32, m <= 16, m N <= 1024)");
+    if (h->useS && (h->weighted || h->hS.size() != (size_t)h->m * h->m))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the design's shared input-rate weight is not kept");
+    const int lds = h->useS ? sens_face_rate_lds_doubles(h->n, h->m, h->N) : sens_face_lds_doubles(h->n, h->m, h->N);
+    if ((size_t)lds * sizeof(double) > (size_t)LDS_BUDGET)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": a stage of the recursion does not fit LDS");
+    if (!h->sens.stepped) return fail(h, ALMPC_ERR_INVALID, w + ": no step has run on this design");
+    return ALMPC_OK;
+}
+
+// Operands of a k_sens_face_rate launch: those of k_sens_face and S, which goes to the device once per design
+int sens_face_rate_params(almpc_handle* h, double act_tol, SensFaceRateParams& q) {
+    const size_t mm = (size_t)h->m * h->m;
+    if (!h->sens.s_ok) {   // (in stream order in front of the kernel)
+        HIP_TRY(h, h->sens.S.grow(mm));
+        HIP_TRY(h, hipMemcpyAsync(h->sens.S, h->hS.data(), mm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        h->sens.s_ok = true;
+    }
+    q = SensFaceRateParams();
+    q.f = sens_face_params(h, act_tol);
+    q.f.lds_per_wave = sens_face_rate_lds_doubles(h->n, h->m, h->N);
+    q.S = h->sens.S;
+    return ALMPC_OK;
+}
+
+template <bool VJP>
+int sens_face_rate_launch(almpc_handle* h, const SensFaceRateParams& q) {
+    const size_t per_wave = (size_t)q.f.lds_per_wave * sizeof(double);
+    const int waves = waves_in_lds(per_wave, SENS_FACE_RATE_WAVES), wgs = capped_grid(h->batch, waves, 16 * h->num_cus);
+    if (h->n == 12 && h->m == 4) HIP_TRY(h, LAUNCH_WAVES((k_sens_face_rate<VJP, 12, 4>), wgs, waves, waves * per_wave, h->stream, q));
+    else HIP_TRY(h, LAUNCH_WAVES((k_sens_face_rate<VJP, 0, 0>), wgs, waves, waves * per_wave, h->stream, q));
+    return ALMPC_OK;
+}
+
+int sens_face_rate_jacobians(almpc_handle* h, uint32_t want, double act_tol) {
+    const char* who = "sensitivity_stagewise_rate";
+    ALMPC_TRY(sens_face_rate_check(h, who));
+    if (!want || (want & ~(ALMPC_SENS_K0 | ALMPC_SENS_DU | ALMPC_SENS_DX))) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": want must be a mask of ALMPC_SENS_*");
+    if (!h->useS) return sens_face_jacobians(h, want, act_tol);   // (no rate term: k_sens_face, to the byte)
+    HIP_TRY(h, hipSetDevice(h->device));
+    ALMPC_TRY(wait_and_settle(h));
+    const size_t b = (size_t)h->batch, n = (size_t)h->n;
+    h->sens.have = 0;
+    SensFaceRateParams q;
+    ALMPC_TRY(sens_face_rate_params(h, act_tol, q));
+    HIP_TRY(h, h->sens.rows.grow(b));
+    if (want & ALMPC_SENS_K0) HIP_TRY(h, h->sens.K0.grow(b * n * h->m));
+    if (want & (ALMPC_SENS_DU | ALMPC_SENS_DX)) {   // (the forward pass writes dU on its way to dX)
+        HIP_TRY(h, h->sens.dU.grow(b * n * h->nz));
+        HIP_TRY(h, h->sens.Kst.grow(b * h->nz * (n + h->m)));
+    }
+    if (want & ALMPC_SENS_DX) HIP_TRY(h, h->sens.dX.grow(b * n * (h->N + 1) * n));
+    q.f.want = want; q.f.K0 = h->sens.K0; q.f.dU = h->sens.dU; q.f.dX = h->sens.dX; q.f.Kst = h->sens.Kst; q.f.rows = h->sens.rows;
+    ALMPC_TRY(sens_face_rate_launch<false>(h, q));
+    HIP_TRY(h, stream_wait_polling(h));
+    h->sens.have = want | ((want & ALMPC_SENS_DX) ? ALMPC_SENS_DU : 0u);
+    return ALMPC_OK;
+}
+
+int sens_face_rate_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows_out) {
+    const char* who = "sensitivity_stagewise_rate_vjp";
+    ALMPC_TRY(sens_face_rate_check(h, who));
+    if (!g_u || !g_x0) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": null g_u or g_x0");
+    if (!h->useS) return sens_face_vjp(h, g_u, g_x, act_tol, g_x0, rows_out);
+    HIP_TRY(h, hipSetDevice(h->device));
+    ALMPC_TRY(wait_and_settle(h));
+    const size_t b = (size_t)h->batch, n = (size_t)h->n, xs = n * (h->N + 1);
+    SensFaceRateParams q;
+    ALMPC_TRY(sens_face_rate_params(h, act_tol, q));
+    HIP_TRY(h, h->sens.vrows.grow(b)); HIP_TRY(h, h->sens.gx0.grow(b * n)); HIP_TRY(h, h->sens.gu.grow(b * h->nz));
+    HIP_TRY(h, hipMemcpyAsync(h->sens.gu, g_u, b * h->nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (g_x) {
+        HIP_TRY(h, h->sens.gx.grow(b * xs));
+        HIP_TRY(h, hipMemcpyAsync(h->sens.gx, g_x, b * xs * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    q.f.g_u = h->sens.gu; q.f.g_x = g_x ? h->sens.gx.get() : nullptr; q.f.g_x0 = h->sens.gx0; q.f.rows = h->sens.vrows;
+    ALMPC_TRY(sens_face_rate_launch<true>(h, q));
+    HIP_TRY(h, hipMemcpyAsync(g_x0, h->sens.gx0, b * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (rows_out) HIP_TRY(h, hipMemcpyAsync(rows_out, h->sens.vrows, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, stream_wait_polling(h));
+    return ALMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4873,6 +4972,12 @@ int almpc_sensitivity_stagewise(almpc_handle* h, uint32_t want, double act_tol) 
 
 int almpc_sensitivity_stagewise_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows) {
     return sens_face_vjp(h, g_u, g_x, act_tol, g_x0, rows);
+}
+
+int almpc_sensitivity_stagewise_rate(almpc_handle* h, uint32_t want, double act_tol) { return sens_face_rate_jacobians(h, want, act_tol); }
+
+int almpc_sensitivity_stagewise_rate_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows) {
+    return sens_face_rate_vjp(h, g_u, g_x, act_tol, g_x0, rows);
 }
 
 }  // extern "C"

@@ -683,6 +683,20 @@ int almpc_group_sensitivity_stagewise_vjp(almpc_group* g, const double* g_u, con
                                                rows ? rows + f : nullptr);
     });
 }
+// ... and those of structured designs with or without S (almpc_sensitivity_stagewise_rate, almpc_sensitivity_stagewise_rate_vjp)
+int almpc_group_sensitivity_stagewise_rate(almpc_group* g, uint32_t want, double act_tol) {
+    if (!g) return ALMPC_ERR_INVALID;
+    return group_fanout(g, [&](int i) { return almpc_sensitivity_stagewise_rate(g->hs[i], want, act_tol); });
+}
+int almpc_group_sensitivity_stagewise_rate_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows) {
+    if (!g || !g_u || !g_x0) return ALMPC_ERR_INVALID;
+    const size_t n = (size_t)g->n, nz = (size_t)g->m * g->N;
+    return group_fanout(g, [&](int i) {
+        const size_t f = (size_t)g->first[i];
+        return almpc_sensitivity_stagewise_rate_vjp(g->hs[i], g_u + f * nz, g_x ? g_x + f * n * (g->N + 1) : nullptr, act_tol, g_x0 + f * n,
+                                                    rows ? rows + f : nullptr);
+    });
+}
 // ... and the parameter gradients (almpc_sensitivity_params_vjp): every output is per instance, so the shards' slices are disjoint
 // (follow_dare: almpc_sensitivity_params_vjp_dare on every shard, dare_status cut the same way)
 static int group_sens_params_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, const almpc_param_grads* out,

@@ -1009,4 +1009,371 @@ __global__ __launch_bounds__(64 * SENS_FACE_WAVES) void k_sens_face(SensFacePara
     }
 }
 
+// ---- k_sens_face_rate: k_sens_face for a design with the input-rate weight S (almpc_sensitivity_stagewise_rate, .._rate_vjp) --------
+//
+// The cost carries sum_k (u_k - u_{k+1})' S (u_k - u_{k+1}), k = 0 .. N-2, so a stage sees the input before it: the face problem is
+// an LQ problem in the stage state z_k = [dx_k; du_{k-1}], nt = n + m.  R as the design uses it, S symmetrised; S_k = S for k >= 1
+// and S_0 = 0 (nothing ties u_0 to an input applied before the horizon):
+//     At = [A 0; 0 0] (nt x nt)    Bt = [B; I] (nt x m)    Nt_k = [0; -S_k] (nt x m)    Rt_k = R + S_k
+//     Qt_k = blkdiag(Qbar_k, S_k),  Qbar_k = Q (1 <= k <= N-1)
+//     Pi+ = blkdiag(sym(P), 0) at k = N;  for k = N-1 .. 0:
+//       Lam = (Rt_k + Bt' Pi+ Bt)_ff
+//       K_k[f,:] = Lam^-1 (Bt' Pi+ At + Nt_k')_f,   K_k[W_k,:] = 0   (m x nt),   Acl_k = At - Bt K_k
+//       Pi+ <- Qt_k + K_k' Rt_k K_k - Nt_k K_k - K_k' Nt_k' + Acl_k' Pi+ Acl_k            (symmetrised; k >= 1 only: Pi_0 has no reader)
+//     Jacobians:  dz_0 = [I_n; 0],  du_k = -K_k dz_k,  dz_{k+1} = [A dx_k + B du_k; du_k]          (K0 = -K_0[:, :n])
+//     VJP:        lam_N = [g_x[N]; 0],  lam_k = [g_x[k]; 0] - K_k' g_u[k] + Acl_k' lam_{k+1},   g_x0 = lam_0[:n]
+// The blocks of At, Bt and Nt are used where they are cheap: Pi+ Bt = Pi+[:, :n] B + Pi+[:, n:],  Bt' Pi+ At = [(Pi+ Bt)[:n]' A, 0],
+// the w columns of B'Pi+At + Nt' are -S_k, the lower rows of Acl are -K, and dz is carried as dx (n x n) and the du before (m x n).
+// Pi+ Acl and Acl' (Pi+ Acl) are full nt x nt products (the closed loop has no zero block), computed by 2 x 2 blocks of the result in
+// a lane's registers: the one-entry-per-lane product of k_sens_face read every operand word from LDS once per product and made K0
+// of 4096 quadrotors at N = 50 cost 3.5 times k_sens_face on the S = 0 design; blocked it costs 1.8 times.
+//
+// Everything else is k_sens_face: the active-set rule, one wave per instance on its slice of LDS, SensTeam<false> fences, rows = -1
+// and zeros for an unsolved instance or a pivot that is not positive and finite, gains through a scratch [N][m nt] for dU and dX.
+// LDS, column-major: A, Q (n x n) | Pi+, T (= Pi+ Acl, then the symmetrised new Pi), Acl (nt x nt) | B (n x m) | Pi+ Bt, K, Rt K, S K
+// (nt x m or m x nt) | R, S, Lam (m x m) | lam, lam+ (nt) | the stage masks.  The new Pi is written over the old one, which has no
+// reader once Pi+ Acl is formed, and symmetrised into T; then the two change places -- no per-lane copy of a matrix, whatever nt.
+// The look-ahead gain of the forward pass is the only per-lane array: m nt <= 768 entries, 12 a lane.
+constexpr int SENS_FACE_RATE_WAVES = 4;
+constexpr int SENS_FACE_RATE_MAX_M = 16, SENS_FACE_RATE_MAX_NT = 48;   // (the shapes the structured solve with S serves: n <= 32, m <= 16, n + m <= 48)
+
+struct SensFaceRateParams {
+    SensFaceParams f;                   // as k_sens_face; Kst is [batch][N][m nt], lds_per_wave that of sens_face_rate_lds_doubles
+    const double* S;                    // m x m, shared
+};
+
+__host__ __device__ inline int sens_face_rate_lds_doubles(int n, int m, int N) {
+    const int nt = n + m;
+    return (2 * n * n + 3 * nt * nt + n * m + 4 * nt * m + 3 * m * m + 2 * nt + (N + 1) / 2 + 1) & ~1;
+}
+
+// out (r x c) = X (r x k) Y (k x c), column-major, a 2 x 2 block of the result in a lane's registers: every operand word read from LDS
+// feeds two products, half the reads of sens_face_mul; each entry is summed in the same order.  An odd edge takes its last row or
+// column twice and stores it once.
+__device__ __forceinline__ void sens_face_mul22(double* out, const double* X, const double* Y, int r, int k, int c, int lane) {
+    const int rb = (r + 1) >> 1, cb = (c + 1) >> 1;
+    for (int t = lane; t < rb * cb; t += 64) {
+        const int i = 2 * (t % rb), j = 2 * (t / rb);
+        const bool i1 = i + 1 < r, j1 = j + 1 < c;
+        const int ii = i1 ? i + 1 : i, jj = j1 ? j + 1 : j;
+        double a00 = 0.0, a10 = 0.0, a01 = 0.0, a11 = 0.0;
+        for (int l = 0; l < k; ++l) {
+            const double x0 = X[i + l * r], x1 = X[ii + l * r], y0 = Y[l + j * k], y1 = Y[l + jj * k];
+            a00 += x0 * y0; a10 += x1 * y0; a01 += x0 * y1; a11 += x1 * y1;
+        }
+        out[i + j * r] = a00;
+        if (i1) out[ii + j * r] = a10;
+        if (j1) out[i + jj * r] = a01;
+        if (i1 && j1) out[ii + jj * r] = a11;
+    }
+}
+
+template <bool VJP, int NC, int MC>
+__global__ __launch_bounds__(64 * SENS_FACE_RATE_WAVES) void k_sens_face_rate(SensFaceRateParams q) {
+    extern __shared__ __attribute__((aligned(16))) double sens_face_rate_smem[];
+    static_assert((NC == 0) == (MC == 0), "both dimensions at compile time, or neither");
+    static_assert(MC <= SENS_FACE_RATE_MAX_M && NC + MC <= SENS_FACE_RATE_MAX_NT, "a build beyond the served shapes");
+    constexpr int KREG = NC ? (MC * (NC + MC) + 63) / 64 : (SENS_FACE_RATE_MAX_M * SENS_FACE_RATE_MAX_NT + 63) / 64;
+    static_assert(64 * KREG >= (NC ? MC * (NC + MC) : SENS_FACE_RATE_MAX_M * SENS_FACE_RATE_MAX_NT), "the look-ahead gain does not fit its registers");
+    const SensFaceParams& p = q.f;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int n = NC ? NC : p.n, m = MC ? MC : p.m, N = p.N, nt = n + m, nn = n * n, nm = n * m, mm = m * m, nz = N * m, tt = nt * nt, tm = nt * m;
+    const SensTeam<false> T{lane, 64};
+    double* L = sens_face_rate_smem + (size_t)wv * p.lds_per_wave;
+    double* As = L;            double* Qs = As + nn;
+    double* Pn = Qs + nn;      double* Tm = Pn + tt;    double* Ac = Tm + tt;
+    double* Bs = Ac + tt;
+    double* PB = Bs + nm;      double* Ks = PB + tm;    double* RK = Ks + tm;   double* SK = RK + tm;
+    double* Rs = SK + tm;      double* Ss = Rs + mm;    double* Lam = Ss + mm;
+    double* lam = Lam + mm;    double* lamn = lam + nt;
+    uint32_t* wset = reinterpret_cast<uint32_t*>(lamn + nt);   // [N] bit a: input a of the stage is held (m <= 16 bits)
+    const bool jac = !VJP && (p.want & (SENS_DU | SENS_DX)) != 0;
+
+    const int wpb = (int)(blockDim.x >> 6), nwaves = gridDim.x * wpb;
+    for (int inst = blockIdx.x * wpb + wv; inst < p.batch; inst += nwaves) {
+        T.sync();   // (the previous instance of this wave has read its last LDS operand)
+        bool ok = p.status[inst] == 0;
+        int rows = 0;
+        if (ok) {
+            const double* Ag = p.A + (size_t)inst * p.A_stride;
+            const double* Bg = p.B + (size_t)inst * p.B_stride;
+            const double* Pg = p.P + (size_t)inst * p.P_stride;
+            for (int t = lane; t < nn; t += 64) { As[t] = Ag[t]; Qs[t] = p.Q[t]; }
+            for (int t = lane; t < tt; t += 64) {              // Pi+ = blkdiag(sym(P), 0)
+                const int i = t % nt, j = t / nt;
+                Pn[t] = (i < n && j < n) ? 0.5 * (Pg[i + j * n] + Pg[j + i * n]) : 0.0;
+            }
+            for (int t = lane; t < nm; t += 64) Bs[t] = Bg[t];
+            for (int t = lane; t < mm; t += 64) { Rs[t] = p.R[t]; Ss[t] = 0.5 * (q.S[t] + q.S[(t % m) * m + t / m]); }
+            for (int k = lane; k < N; k += 64) wset[k] = 0u;
+            T.sync();
+            // the rows at a bound
+            for (int t = lane; t < nz; t += 64) {
+                const int k = t / m, a = t - k * m;
+                const double uj = p.u[(size_t)inst * nz + t], lo = p.umin[a], hi = p.umax[a], tol = p.tau * (hi - lo);
+                if (uj - lo <= tol || hi - uj <= tol) { atomicOr(&wset[k], 1u << a); ++rows; }
+            }
+            for (int o = 32; o > 0; o >>= 1) rows += __shfl_xor(rows, o);
+            if (VJP) {   // (0.0 is added where g_x is null, so that a null g_x and a g_x of zeros give the same bits)
+                const double* gx = p.g_x ? p.g_x + (size_t)inst * (N + 1) * n : nullptr;
+                for (int i = lane; i < nt; i += 64) lam[i] = i < n ? 0.0 + (gx ? gx[(size_t)N * n + i] : 0.0) : 0.0;
+            }
+            T.sync();
+        }
+        // ---- backward sweep
+        for (int k = N - 1; ok && k >= 0; --k) {
+            const uint32_t wk = wset[k];
+            const bool rate = k > 0;                           // S_0 = 0: stage 0 has no S term in Rt, Nt or Qt
+            for (int t = lane; t < tm; t += 64) {              // Pi+ Bt = Pi+[:, :n] B + Pi+[:, n:]
+                const int i = t % nt, a = t / nt;
+                double acc = Pn[i + (n + a) * nt];
+                for (int l = 0; l < n; ++l) acc += Pn[i + l * nt] * Bs[l + a * n];
+                PB[t] = acc;
+            }
+            T.sync();
+            for (int t = lane; t < tm; t += 64) {              // Bt' Pi+ At + Nt' = [(Pi+ Bt)[:n]' A, -S_k]
+                const int a = t % m, j = t / m;
+                double acc = 0.0;
+                if (j < n) for (int l = 0; l < n; ++l) acc += PB[l + a * nt] * As[l + j * n];
+                else if (rate) acc = 0.0 - Ss[a + (j - n) * m];
+                Ks[t] = ((wk >> a) & 1u) ? 0.0 : acc;          // the rows of the held inputs vanish
+            }
+            for (int t = lane; t < mm; t += 64) {              // Lam = Rt + Bt' Pi+ Bt = R + S_k + B' (Pi+ Bt)[:n] + (Pi+ Bt)[n:], identity on the held inputs
+                const int i = t % m, j = t / m;
+                double acc = PB[n + i + j * nt];
+                for (int l = 0; l < n; ++l) acc += Bs[l + i * n] * PB[l + j * nt];
+                acc += Rs[t];
+                if (rate) acc += Ss[t];
+                const bool hi_ = (wk >> i) & 1u, hj = (wk >> j) & 1u;
+                Lam[t] = (hi_ || hj) ? (i == j ? 1.0 : 0.0) : acc;
+            }
+            T.sync();
+            if constexpr (MC > 0 && MC <= 4) {
+                // m <= 4: every lane factors Lam in its own registers (the diagonal kept as its reciprocal), then takes a column of
+                // the right-hand side through both substitutions
+                double l[MC][MC];
+#pragma unroll
+                for (int i = 0; i < MC; ++i)
+#pragma unroll
+                    for (int j = 0; j <= i; ++j) l[i][j] = Lam[i + j * MC];
+#pragma unroll
+                for (int c = 0; c < MC; ++c) {
+                    const double piv = l[c][c];
+                    if (!(piv > 0.0 && piv <= 1.7976931348623157e308)) ok = false;
+                    const double inv = 1.0 / sqrt(piv);
+                    l[c][c] = inv;
+#pragma unroll
+                    for (int i = c + 1; i < MC; ++i) l[i][c] *= inv;
+#pragma unroll
+                    for (int j = c + 1; j < MC; ++j)
+#pragma unroll
+                        for (int i = j; i < MC; ++i) l[i][j] -= l[i][c] * l[j][c];
+                }
+                if (!ok) break;   // (every lane factored the same matrix)
+                for (int c = lane; c < nt; c += 64) {
+                    double x[MC];
+#pragma unroll
+                    for (int i = 0; i < MC; ++i) x[i] = Ks[i + c * MC];
+#pragma unroll
+                    for (int i = 0; i < MC; ++i) {
+#pragma unroll
+                        for (int j = 0; j < i; ++j) x[i] -= l[i][j] * x[j];
+                        x[i] *= l[i][i];
+                    }
+#pragma unroll
+                    for (int i = MC - 1; i >= 0; --i) {
+#pragma unroll
+                        for (int j = i + 1; j < MC; ++j) x[i] -= l[j][i] * x[j];
+                        x[i] *= l[i][i];
+                    }
+#pragma unroll
+                    for (int i = 0; i < MC; ++i) Ks[i + c * MC] = x[i];
+                }
+            } else {
+                // Lam = C C' in place (lower triangle)
+                for (int c = 0; c < m; ++c) {
+                    const double piv = Lam[c + c * m];         // (every lane reads the same word)
+                    if (!(piv > 0.0 && piv <= 1.7976931348623157e308)) { ok = false; break; }
+                    const double dk = sqrt(piv);
+                    T.sync();
+                    for (int i = c + lane; i < m; i += 64) Lam[i + c * m] = i == c ? dk : Lam[i + c * m] / dk;
+                    T.sync();
+                    const int rem = m - c - 1;
+                    for (int idx = lane; idx < rem * rem; idx += 64) {
+                        const int i = c + 1 + idx / rem, j = c + 1 + idx % rem;
+                        if (j <= i) Lam[i + j * m] -= Lam[i + c * m] * Lam[j + c * m];
+                    }
+                    T.sync();
+                }
+                if (!ok) break;
+                // K = Lam^-1 (Bt'Pi+At + Nt'): a lane takes a column through both substitutions
+                for (int c = lane; c < nt; c += 64) {
+                    double* x = Ks + c * m;
+                    for (int i = 0; i < m; ++i) {
+                        double s = x[i];
+                        for (int j = 0; j < i; ++j) s -= Lam[i + j * m] * x[j];
+                        x[i] = s / Lam[i + i * m];
+                    }
+                    for (int i = m - 1; i >= 0; --i) {
+                        double s = x[i];
+                        for (int j = i + 1; j < m; ++j) s -= Lam[j + i * m] * x[j];
+                        x[i] = s / Lam[i + i * m];
+                    }
+                }
+            }
+            T.sync();
+            if (jac) {
+                double* Kg = p.Kst + ((size_t)inst * N + k) * tm;
+                for (int t = lane; t < tm; t += 64) Kg[t] = Ks[t];
+            }
+            if (!VJP && k == 0 && (p.want & SENS_K0))
+                for (int t = lane; t < nm; t += 64) p.K0[(size_t)inst * nm + t] = 0.0 - Ks[t];   // (the x columns come first)
+            if (!VJP && k == 0) break;                         // (Pi_0 has no reader)
+            for (int t = lane; t < tt; t += 64) {              // Acl = At - Bt K = [A - B K_x, -B K_w; -K]
+                const int i = t % nt, j = t / nt;
+                double s;
+                if (i < n) {
+                    s = j < n ? As[i + j * n] : 0.0;
+                    for (int a = 0; a < m; ++a) s -= Bs[i + a * n] * Ks[a + j * m];
+                } else s = 0.0 - Ks[(i - n) + j * m];
+                Ac[t] = s;
+            }
+            if (k > 0)
+                for (int t = lane; t < tm; t += 64) {          // Rt K and S K
+                    const int a = t % m, j = t / m;
+                    double r = 0.0, s = 0.0;
+                    for (int b = 0; b < m; ++b) {
+                        const double kb = Ks[b + j * m];
+                        r += Rs[a + b * m] * kb;
+                        s += Ss[a + b * m] * kb;
+                    }
+                    RK[t] = r + s;
+                    SK[t] = s;
+                }
+            T.sync();
+            double ln = 0.0;
+            if (VJP && lane < nt) {                            // lam_k = [g_x[k]; 0] - K' g_u[k] + Acl' lam_{k+1}
+                const double* gu = p.g_u + (size_t)inst * nz + (size_t)k * m;
+                ln = (p.g_x && lane < n) ? p.g_x[((size_t)inst * (N + 1) + k) * n + lane] : 0.0;
+                for (int a = 0; a < m; ++a) ln -= Ks[a + lane * m] * gu[a];
+                for (int l = 0; l < nt; ++l) ln += Ac[l + lane * nt] * lam[l];
+            }
+            if (k > 0) {
+                sens_face_mul22(Tm, Pn, Ac, nt, nt, nt, lane);        // Pi+ Acl
+                T.sync();
+                // the new Pi over the old one, which has no reader left: Acl' (Pi+ Acl) by 2 x 2 blocks, then the terms of the stage
+                const int hb = (nt + 1) >> 1;
+                for (int t = lane; t < hb * hb; t += 64) {
+                    const int i0 = 2 * (t % hb), j0 = 2 * (t / hb);
+                    const int i1 = i0 + 1 < nt ? i0 + 1 : i0, j1 = j0 + 1 < nt ? j0 + 1 : j0;
+                    double acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+                    for (int l = 0; l < nt; ++l) {
+                        const double a0 = Ac[l + i0 * nt], a1 = Ac[l + i1 * nt], b0 = Tm[l + j0 * nt], b1 = Tm[l + j1 * nt];
+                        acc[0][0] += a0 * b0; acc[1][0] += a1 * b0; acc[0][1] += a0 * b1; acc[1][1] += a1 * b1;
+                    }
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int i = i0 + (e & 1), j = j0 + (e >> 1);
+                        if (i >= nt || j >= nt) continue;
+                        double s = (i < n && j < n) ? Qs[i + j * n] : ((i >= n && j >= n) ? Ss[(i - n) + (j - n) * m] : 0.0);
+                        s += acc[e & 1][e >> 1];
+                        for (int a = 0; a < m; ++a) s += Ks[a + i * m] * RK[a + j * m];
+                        if (i >= n) s += SK[(i - n) + j * m];  // - Nt K = [0; S K]
+                        if (j >= n) s += SK[(j - n) + i * m];  // - K' Nt'
+                        Pn[i + j * nt] = s;
+                    }
+                }
+                T.sync();
+                for (int t = lane; t < tt; t += 64) Tm[t] = 0.5 * (Pn[t] + Pn[(t % nt) * nt + t / nt]);
+                double* sw = Pn; Pn = Tm; Tm = sw;
+            }
+            if (VJP && lane < nt) lamn[lane] = ln;
+            T.sync();
+            if (VJP) { double* sw = lam; lam = lamn; lamn = sw; }
+        }
+        if (!ok) {   // unsolved, or a pivot that is not positive and finite
+            if (VJP) {
+                for (int c = lane; c < n; c += 64) p.g_x0[(size_t)inst * n + c] = 0.0;
+            } else {
+                if (p.want & SENS_K0)
+                    for (int t = lane; t < nm; t += 64) p.K0[(size_t)inst * nm + t] = 0.0;
+                if (jac)
+                    for (int t = lane; t < n * nz; t += 64) p.dU[(size_t)inst * n * nz + t] = 0.0;
+                if (p.want & SENS_DX)
+                    for (int t = lane; t < (N + 1) * nn; t += 64) p.dX[(size_t)inst * (N + 1) * nn + t] = 0.0;
+            }
+            if (lane == 0) p.rows[inst] = -1;
+            continue;
+        }
+        if (lane == 0) p.rows[inst] = rows;
+        if (VJP) {
+            for (int c = lane; c < n; c += 64) p.g_x0[(size_t)inst * n + c] = lam[c];
+            continue;
+        }
+        if (!jac) continue;
+        // ---- forward pass: dx in Pn, dx+ in Tm (n x n each), du in PB and the du before in RK (m x n each).  The gains were stored by
+        // other lanes of this wave: made visible at device scope, read back past the L1 and one stage ahead
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        __builtin_amdgcn_wave_barrier();
+        const double* Kg = p.Kst + (size_t)inst * N * tm;
+        double* dUo = p.dU + (size_t)inst * n * nz;
+        double* dXo = p.dX + (size_t)inst * (N + 1) * nn;
+        const bool wdx = (p.want & SENS_DX) != 0;
+        double kreg[KREG];
+        auto kload = [&](int k) {
+#pragma unroll
+            for (int c = 0; c < KREG; ++c) {
+                const int t = lane + 64 * c;
+                kreg[c] = t < tm ? __hip_atomic_load(Kg + (size_t)k * tm + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+            }
+        };
+        kload(0);
+        double* dx = Pn;
+        double* dxn = Tm;
+        double* du = PB;
+        double* dup = RK;
+        for (int t = lane; t < nn; t += 64) {
+            const int i = t % n, c = t / n;
+            const double v = i == c ? 1.0 : 0.0;
+            dx[t] = v;
+            if (wdx) dXo[(size_t)c * (N + 1) * n + i] = v;
+        }
+        T.sync();
+        for (int k = 0; k < N; ++k) {
+#pragma unroll
+            for (int c = 0; c < KREG; ++c) {
+                const int t = lane + 64 * c;
+                if (t < tm) Ks[t] = kreg[c];
+            }
+            if (k + 1 < N) kload(k + 1);
+            T.sync();
+            for (int t = lane; t < nm; t += 64) {              // du = -K dz = -K_x dx - K_w du-  (dz_0 = [I; 0]: the bits of K0)
+                const int a = t % m, c = t / m;
+                double s = 0.0;
+                if (k == 0) s -= Ks[t];
+                else {
+                    for (int j = 0; j < n; ++j) s -= Ks[a + j * m] * dx[j + c * n];
+                    for (int b = 0; b < m; ++b) s -= Ks[a + (n + b) * m] * dup[b + c * m];
+                }
+                du[t] = s;
+                dUo[(size_t)c * nz + (size_t)k * m + a] = s;
+            }
+            T.sync();
+            if (k + 1 < N || wdx) {
+                for (int t = lane; t < nn; t += 64) {          // dx+ = A dx + B du
+                    const int i = t % n, c = t / n;
+                    double s = 0.0;
+                    for (int j = 0; j < n; ++j) s += As[i + j * n] * dx[j + c * n];
+                    for (int a = 0; a < m; ++a) s += Bs[i + a * n] * du[a + c * m];
+                    dxn[t] = s;
+                    if (wdx) dXo[((size_t)c * (N + 1) + k + 1) * n + i] = s;
+                }
+                T.sync();
+                double* sw = dx; dx = dxn; dxn = sw;
+            }
+            { double* sw = du; du = dup; dup = sw; }
+        }
+    }
+}
+
 }  // namespace almpc

@@ -761,6 +761,37 @@ int almpc_group_sensitivity_stagewise(almpc_group* g, uint32_t want, double act_
 int almpc_group_sensitivity_stagewise_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows);
 
 /*
+ * The same with the input-rate weight S (k_sens_face_rate, DESIGN.md "k_sens_face_rate"): every structured input-box design, with or
+ * without S.  The cost carries sum_k (u_k - u_{k+1})' S (u_k - u_{k+1}), k = 0 .. N-2, so a stage sees the input before it and the
+ * recursion runs in the stage state z_k = [dx_k; du_{k-1}], nt = n + m.  R as the design uses it; S_k = S (symmetrised) for k >= 1 and
+ * S_0 = 0, because nothing ties u_0 to an input applied before the horizon:
+ *     At = [A 0; 0 0] (nt x nt)    Bt = [B; I] (nt x m)    Nt_k = [0; -S_k] (nt x m)    Rt_k = R + S_k
+ *     Qt_k = blkdiag(Qbar_k, S_k),  Qbar_k = Q (1 <= k <= N-1),  Qbar_0 = 0
+ *     Pi+ = blkdiag(sym(P), 0) at k = N;  for k = N-1 .. 0:
+ *       Lam = (Rt_k + Bt' Pi+ Bt)_ff
+ *       K_k[f,:] = Lam^-1 (Bt' Pi+ At + Nt_k')_f,   K_k[W_k,:] = 0   (m x nt),   Acl_k = At - Bt K_k
+ *       Pi+ <- Qt_k + K_k' Rt_k K_k - Nt_k K_k - K_k' Nt_k' + Acl_k' Pi+ Acl_k            (symmetrised)
+ *     Jacobians:  dz_0 = [I_n; 0],  du_k = -K_k dz_k,  dz_{k+1} = At dz_k + Bt du_k = [A dx_k + B du_k; du_k]      (K0 = -K_0[:, :n])
+ *     VJP:        lam_N = [g_x[N]; 0],  lam_k = [g_x[k]; 0] - K_k' g_u[k] + Acl_k' lam_{k+1},   g_x0 = lam_0[:n]
+ * Everything else is the pair above: synchronous, settles first, results in the handle's buffers (almpc_get_sensitivity and
+ * almpc_device_sensitivity serve them), the same layouts, the same rule for W with act_tol <= 0 meaning 1e-7, g_x = NULL bit-identical
+ * to zeros, rows = -1 and zeros for an instance that is not ALMPC_SOLVED or has a pivot that is not positive and finite, no gain
+ * scratch for ALMPC_SENS_K0 alone (with dU or dX the scratch is [batch][N][m nt]).
+ * On a design without the rate term (S == NULL, S[1,1] == 0 or R[1,1] == 0) the calls take the path of almpc_sensitivity_stagewise /
+ * almpc_sensitivity_stagewise_vjp and k_sens_face: the same bits.  Those two calls themselves go on refusing a design with S.
+ * Served: almpc_design_shared and almpc_design_batched on a structured handle (S is shared by the batch on both), in the shapes the
+ * structured solve serves with S: n <= 32, m <= 16, n + m <= 48, (N + 1)(n + m) <= 4096, m N <= 1024.  ALMPC_ERR_UNSUPPORTED, with the
+ * reason in almpc_last_error: a handle that is not structured, a state box or the terminal equality, time-varying and SQP designs and
+ * the re-linearisation pipeline, a design without the primal solver's weights, a stage that does not fit LDS.  ALMPC_ERR_INVALID:
+ * before the design's first step, a `want` that is no mask of ALMPC_SENS_*, a NULL g_u or g_x0.
+ */
+int almpc_sensitivity_stagewise_rate(almpc_handle* h, uint32_t want, double act_tol);       /* ALMPC_SENS_K0 | _DU | _DX */
+int almpc_sensitivity_stagewise_rate_vjp(almpc_handle* h, const double* g_u, const double* g_x /* or NULL */, double act_tol,
+                                         double* g_x0 /* [batch][n] */, int32_t* rows /* or NULL */);
+int almpc_group_sensitivity_stagewise_rate(almpc_group* g, uint32_t want, double act_tol);
+int almpc_group_sensitivity_stagewise_rate_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows);
+
+/*
  * Parameter gradients of the returned solution: for the loss of almpc_sensitivity_vjp (g_u [batch][N][m], g_x [batch][N+1][n] or NULL),
  * its gradient in the problem data, per instance, on the face where the rows W (same rule, same act_tol) are held -- the backward
  * pass of a step for a caller who learns or tunes the controller (k_sens_pz, k_sens_params; DESIGN.md "k_sens_params").  Stages

@@ -22,7 +22,8 @@ export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_s
        group_results_wait!, sensitivity, device_sensitivity, sensitivity_vjp, group_sensitivity, group_sensitivity_vjp,
        sensitivity_rows, sensitivity_rows_vjp, group_sensitivity_rows, group_sensitivity_rows_vjp, sensitivity_params_vjp,
        group_sensitivity_params_vjp, dare_vjp, dare_vjp_batched, sensitivity_stagewise, sensitivity_stagewise_vjp,
-       group_sensitivity_stagewise, group_sensitivity_stagewise_vjp
+       group_sensitivity_stagewise, group_sensitivity_stagewise_vjp, sensitivity_stagewise_rate, sensitivity_stagewise_rate_vjp,
+       group_sensitivity_stagewise_rate, group_sensitivity_stagewise_rate_vjp
 
 const libalmpc = get(ENV, "ALMPC_LIB", "libalmpc.so")
 
@@ -778,6 +779,36 @@ function sensitivity_stagewise_vjp(mod::HipModeler, g_u::Array{Float64}, g_x::Un
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), mod.handle, g_u, px, act_tol, g_x0, rows))
     return g_x0, rows
 end
+"""
+    sensitivity_stagewise_rate(mod; K0 = true, dU = false, dX = false, act_tol = 0.0) -> (K0, dU, dX, rows)
+
+`sensitivity_stagewise` for every structured input-box design, with or without the input-rate weight S
+(`almpc_sensitivity_stagewise_rate` + `almpc_get_sensitivity`): with S the Riccati recursion on the face runs in the stage state
+`[dx_k; du_(k-1)]`; without it the call returns the bits of `sensitivity_stagewise`.
+"""
+function sensitivity_stagewise_rate(mod::HipModeler; K0::Bool = true, dU::Bool = false, dX::Bool = false, act_tol::Real = 0.0)
+    k, du, dx, rows = sens_arrays(mod.n, mod.m, mod.N, mod.batch, K0, dU, dX)
+    check(mod.handle, ccall((:almpc_sensitivity_stagewise_rate, libalmpc), Cint, (Ptr{Cvoid}, UInt32, Cdouble), mod.handle,
+                            sens_mask(K0, dU, dX), act_tol))
+    pf(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve k du dx check(mod.handle, ccall((:almpc_get_sensitivity, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), mod.handle, pf(k), pf(du), pf(dx), rows))
+    return k, du, dx, rows
+end
+"""
+    sensitivity_stagewise_rate_vjp(mod, g_u, g_x = nothing; act_tol = 0.0) -> (g_x0, rows)
+
+`sensitivity_stagewise_vjp` for designs with or without S (`almpc_sensitivity_stagewise_rate_vjp`): the adjoint rides the backward
+sweep of the recursion in `[dx_k; du_(k-1)]`.
+"""
+function sensitivity_stagewise_rate_vjp(mod::HipModeler, g_u::Array{Float64}, g_x::Union{Nothing,Array{Float64}} = nothing; act_tol::Real = 0.0)
+    check_sens_sizes(mod.n, mod.m, mod.N, mod.batch, g_u, g_x)
+    g_x0, rows = Matrix{Float64}(undef, mod.n, mod.batch), Vector{Int32}(undef, mod.batch)
+    px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
+    GC.@preserve g_x check(mod.handle, ccall((:almpc_sensitivity_stagewise_rate_vjp, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), mod.handle, g_u, px, act_tol, g_x0, rows))
+    return g_x0, rows
+end
 
 # almpc_param_grads (include/almpc.h): host pointers, C_NULL = not wanted
 struct ParamGrads
@@ -999,6 +1030,25 @@ function group_sensitivity_stagewise_vjp(g::HipGroup, g_u::Array{Float64}, g_x::
     g_x0, rows = Matrix{Float64}(undef, g.n, g.batch), Vector{Int32}(undef, g.batch)
     px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
     GC.@preserve g_x gcheck(g.group, ccall((:almpc_group_sensitivity_stagewise_vjp, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), g.group, g_u, px, act_tol, g_x0, rows))
+    return g_x0, rows
+end
+"`sensitivity_stagewise_rate` for the whole batch (`almpc_group_sensitivity_stagewise_rate` + `almpc_group_get_sensitivity`)"
+function group_sensitivity_stagewise_rate(g::HipGroup; K0::Bool = true, dU::Bool = false, dX::Bool = false, act_tol::Real = 0.0)
+    k, du, dx, rows = sens_arrays(g.n, g.m, g.N, g.batch, K0, dU, dX)
+    gcheck(g.group, ccall((:almpc_group_sensitivity_stagewise_rate, libalmpc), Cint, (Ptr{Cvoid}, UInt32, Cdouble), g.group,
+                          sens_mask(K0, dU, dX), act_tol))
+    pf(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve k du dx gcheck(g.group, ccall((:almpc_group_get_sensitivity, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), g.group, pf(k), pf(du), pf(dx), rows))
+    return k, du, dx, rows
+end
+"`sensitivity_stagewise_rate_vjp` for the whole batch (`almpc_group_sensitivity_stagewise_rate_vjp`)"
+function group_sensitivity_stagewise_rate_vjp(g::HipGroup, g_u::Array{Float64}, g_x::Union{Nothing,Array{Float64}} = nothing; act_tol::Real = 0.0)
+    check_sens_sizes(g.n, g.m, g.N, g.batch, g_u, g_x)
+    g_x0, rows = Matrix{Float64}(undef, g.n, g.batch), Vector{Int32}(undef, g.batch)
+    px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
+    GC.@preserve g_x gcheck(g.group, ccall((:almpc_group_sensitivity_stagewise_rate_vjp, libalmpc), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), g.group, g_u, px, act_tol, g_x0, rows))
     return g_x0, rows
 end
