@@ -4729,30 +4729,38 @@ int sens_params_vjp(almpc_handle* h, const double* g_u, const double* g_x, doubl
     return ALMPC_OK;
 }
 
-// ---- the same on a structured handle (k_sens_face): the Riccati recursion on the face, no condensed operand ----
+// ---- the same on a structured handle (k_sens_face, k_sens_face_rate): the Riccati recursion on the face, no condensed operand ----
+// One path for almpc_sensitivity_stagewise[_vjp] (rate false: designs with S = 0) and almpc_sensitivity_stagewise_rate[_vjp] (rate
+// true: with or without S).  k_sens_face_rate runs where the call takes S and the design has it (rate && h->useS); a rate call on a
+// design without S launches k_sens_face on the operands of the plain call: the same bytes.
 
-// What almpc_sensitivity_stagewise can look at: the last step of a structured design with an input box only and S = 0
-int sens_face_check(almpc_handle* h, const char* who) {
+// What these calls can look at: the last step of a structured design with an input box only
+int sens_face_check(almpc_handle* h, const char* who, bool rate) {
     if (!h) return ALMPC_ERR_INVALID;
     const std::string w(who);
     if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, w + " before design");
     if (!h->structured) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the handle is a condensed one, whose sensitivities come from G = H'^-1 (almpc_sensitivity)");
     if (h->ltv || h->sqp.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": time-varying and SQP designs solve for a step around a trajectory, not for u(x0)");
     if (h->relin.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the re-linearisation pipeline's models depend on x0 themselves");
-    if (h->useS) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": with an input-rate weight S the stage state is [e_k; v_(k-1)], for which the recursion is not built");
+    if (!rate && h->useS) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": with an input-rate weight S the stage state is [e_k; v_(k-1)], for which the recursion is not built");
     if (h->has_box || h->terminal_eq || (h->sd.ready && (h->sd.has_box || h->sd.has_eq)))
         return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": state rows (state box, terminal equality) are not held on the face of the stage-wise recursion");
     if (!h->rQ || !h->rR || !(h->r_batched_P ? h->bP.get() : h->rP.get()))
         return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the shape is outside the primal stage-wise solver, whose weights the recursion reads (n <= 32, m <= 16, m N <= 1024)");
-    if ((size_t)sens_face_lds_doubles(h->n, h->m, h->N) * sizeof(double) > (size_t)LDS_BUDGET)
+    if (rate && h->useS && (h->weighted || h->hS.size() != (size_t)h->m * h->m))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the design's shared input-rate weight is not kept");
+    const int lds = h->useS ? sens_face_rate_lds_doubles(h->n, h->m, h->N) : sens_face_lds_doubles(h->n, h->m, h->N);   // (useS: a rate call)
+    if ((size_t)lds * sizeof(double) > (size_t)LDS_BUDGET)
         return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": a stage of the recursion does not fit LDS");
     if (!h->sens.stepped) return fail(h, ALMPC_ERR_INVALID, w + ": no step has run on this design");
     return ALMPC_OK;
 }
 
-// Operands of a k_sens_face launch: the models, weights and results k_riccati is launched with (launch_riccati)
-SensFaceParams sens_face_params(almpc_handle* h, double act_tol) {
-    SensFaceParams p = SensFaceParams();
+// Operands of a launch: the models, weights and results k_riccati is launched with (launch_riccati) in q.f; with_S (k_sens_face_rate)
+// also S, which goes to the device once per design, and that kernel's slice of LDS
+int sens_face_params(almpc_handle* h, double act_tol, bool with_S, SensFaceRateParams& q) {
+    q = SensFaceRateParams();
+    SensFaceParams& p = q.f;
     p.n = h->n; p.m = h->m; p.N = h->N; p.batch = h->batch;
     p.A = h->batched ? h->bA : h->dA; p.A_stride = h->batched ? (long)h->n * h->n : 0;
     p.B = h->batched ? h->bB : h->dB; p.B_stride = h->batched ? (long)h->n * h->m : 0;
@@ -4760,146 +4768,66 @@ SensFaceParams sens_face_params(almpc_handle* h, double act_tol) {
     p.P = h->r_batched_P ? h->bP : h->rP; p.P_stride = h->r_batched_P ? h->rP_stride : 0;
     p.umin = h->dUmin; p.umax = h->dUmax; p.u = h->dU; p.status = h->dStatus;
     p.tau = act_tol > 0.0 ? act_tol : 1e-7;   // (ten times what k_sdual's confirmation leaves a working-set row away from its bound)
-    p.lds_per_wave = sens_face_lds_doubles(h->n, h->m, h->N);
-    return p;
-}
-
-template <bool VJP>
-int sens_face_launch(almpc_handle* h, const SensFaceParams& p) {
-    const size_t per_wave = (size_t)p.lds_per_wave * sizeof(double);
-    const int waves = waves_in_lds(per_wave, SENS_FACE_WAVES), wgs = capped_grid(h->batch, waves, 16 * h->num_cus);
-    if (h->n == 12 && h->m == 4) HIP_TRY(h, LAUNCH_WAVES((k_sens_face<VJP, 12, 4>), wgs, waves, waves * per_wave, h->stream, p));
-    else HIP_TRY(h, LAUNCH_WAVES((k_sens_face<VJP, 0, 0>), wgs, waves, waves * per_wave, h->stream, p));
-    return ALMPC_OK;
-}
-
-int sens_face_jacobians(almpc_handle* h, uint32_t want, double act_tol) {
-    const char* who = "sensitivity_stagewise";
-    ALMPC_TRY(sens_face_check(h, who));
-    if (!want || (want & ~(ALMPC_SENS_K0 | ALMPC_SENS_DU | ALMPC_SENS_DX))) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": want must be a mask of ALMPC_SENS_*");
-    HIP_TRY(h, hipSetDevice(h->device));
-    ALMPC_TRY(wait_and_settle(h));
-    const size_t b = (size_t)h->batch, n = (size_t)h->n;
-    h->sens.have = 0;
-    SensFaceParams p = sens_face_params(h, act_tol);
-    HIP_TRY(h, h->sens.rows.grow(b));
-    if (want & ALMPC_SENS_K0) HIP_TRY(h, h->sens.K0.grow(b * n * h->m));
-    if (want & (ALMPC_SENS_DU | ALMPC_SENS_DX)) {   // (the forward pass writes dU on its way to dX)
-        HIP_TRY(h, h->sens.dU.grow(b * n * h->nz));
-        HIP_TRY(h, h->sens.Kst.grow(b * h->nz * n));
-    }
-    if (want & ALMPC_SENS_DX) HIP_TRY(h, h->sens.dX.grow(b * n * (h->N + 1) * n));
-    p.want = want; p.K0 = h->sens.K0; p.dU = h->sens.dU; p.dX = h->sens.dX; p.Kst = h->sens.Kst; p.rows = h->sens.rows;
-    ALMPC_TRY(sens_face_launch<false>(h, p));
-    HIP_TRY(h, stream_wait_polling(h));
-    h->sens.have = want | ((want & ALMPC_SENS_DX) ? ALMPC_SENS_DU : 0u);
-    return ALMPC_OK;
-}
-
-int sens_face_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows_out) {
-    const char* who = "sensitivity_stagewise_vjp";
-    ALMPC_TRY(sens_face_check(h, who));
-    if (!g_u || !g_x0) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": null g_u or g_x0");
-    HIP_TRY(h, hipSetDevice(h->device));
-    ALMPC_TRY(wait_and_settle(h));
-    const size_t b = (size_t)h->batch, n = (size_t)h->n, xs = n * (h->N + 1);
-    SensFaceParams p = sens_face_params(h, act_tol);
-    HIP_TRY(h, h->sens.vrows.grow(b)); HIP_TRY(h, h->sens.gx0.grow(b * n)); HIP_TRY(h, h->sens.gu.grow(b * h->nz));
-    HIP_TRY(h, hipMemcpyAsync(h->sens.gu, g_u, b * h->nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (g_x) {
-        HIP_TRY(h, h->sens.gx.grow(b * xs));
-        HIP_TRY(h, hipMemcpyAsync(h->sens.gx, g_x, b * xs * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    }
-    p.g_u = h->sens.gu; p.g_x = g_x ? h->sens.gx.get() : nullptr; p.g_x0 = h->sens.gx0; p.rows = h->sens.vrows;
-    ALMPC_TRY(sens_face_launch<true>(h, p));
-    HIP_TRY(h, hipMemcpyAsync(g_x0, h->sens.gx0, b * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (rows_out) HIP_TRY(h, hipMemcpyAsync(rows_out, h->sens.vrows, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, stream_wait_polling(h));
-    return ALMPC_OK;
-}
-
-// ---- ... and with the input-rate weight S (k_sens_face_rate): the recursion in the stage state [dx_k; du_(k-1)] ----
-
-// What almpc_sensitivity_stagewise_rate can look at: the last step of a structured design with an input box only, with or without S
-int sens_face_rate_check(almpc_handle* h, const char* who) {
-    if (!h) return ALMPC_ERR_INVALID;
-    const std::string w(who);
-    if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, w + " before design");
-    if (!h->structured) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the handle is a condensed one, whose sensitivities come from G = H'^-1 (almpc_sensitivity)");
-    if (h->ltv || h->sqp.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": time-varying and SQP designs solve for a step around a trajectory, not for u(x0)");
-    if (h->relin.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the re-linearisation pipeline's models depend on x0 themselves");
-    if (h->has_box || h->terminal_eq || (h->sd.ready && (h->sd.has_box || h->sd.has_eq)))
-        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": state rows (state box, terminal equality) are not held on the face of the stage-wise recursion");
-    if (!h->rQ || !h->rR || !(h->r_batched_P ? h->bP.get() : h->rP.get()))
-        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the shape is outside the primal stage-wise solver, whose weights the recursion reads (n <= 32, m <= 16, m N <= 1024)");
-    if (h->useS && (h->weighted || h->hS.size() != (size_t)h->m * h->m))
-        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the design's shared input-rate weight is not kept");
-    const int lds = h->useS ? sens_face_rate_lds_doubles(h->n, h->m, h->N) : sens_face_lds_doubles(h->n, h->m, h->N);
-    if ((size_t)lds * sizeof(double) > (size_t)LDS_BUDGET)
-        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": a stage of the recursion does not fit LDS");
-    if (!h->sens.stepped) return fail(h, ALMPC_ERR_INVALID, w + ": no step has run on this design");
-    return ALMPC_OK;
-}
-
-// Operands of a k_sens_face_rate launch: those of k_sens_face and S, which goes to the device once per design
-int sens_face_rate_params(almpc_handle* h, double act_tol, SensFaceRateParams& q) {
+    p.lds_per_wave = with_S ? sens_face_rate_lds_doubles(h->n, h->m, h->N) : sens_face_lds_doubles(h->n, h->m, h->N);
+    if (!with_S) return ALMPC_OK;
     const size_t mm = (size_t)h->m * h->m;
     if (!h->sens.s_ok) {   // (in stream order in front of the kernel)
         HIP_TRY(h, h->sens.S.grow(mm));
         HIP_TRY(h, hipMemcpyAsync(h->sens.S, h->hS.data(), mm * sizeof(double), hipMemcpyHostToDevice, h->stream));
         h->sens.s_ok = true;
     }
-    q = SensFaceRateParams();
-    q.f = sens_face_params(h, act_tol);
-    q.f.lds_per_wave = sens_face_rate_lds_doubles(h->n, h->m, h->N);
     q.S = h->sens.S;
     return ALMPC_OK;
 }
 
+// (q.S is set exactly where sens_face_params was asked for k_sens_face_rate's operands)
 template <bool VJP>
-int sens_face_rate_launch(almpc_handle* h, const SensFaceRateParams& q) {
+int sens_face_launch(almpc_handle* h, const SensFaceRateParams& q) {
+    const bool with_S = q.S != nullptr;
     const size_t per_wave = (size_t)q.f.lds_per_wave * sizeof(double);
-    const int waves = waves_in_lds(per_wave, SENS_FACE_RATE_WAVES), wgs = capped_grid(h->batch, waves, 16 * h->num_cus);
-    if (h->n == 12 && h->m == 4) HIP_TRY(h, LAUNCH_WAVES((k_sens_face_rate<VJP, 12, 4>), wgs, waves, waves * per_wave, h->stream, q));
-    else HIP_TRY(h, LAUNCH_WAVES((k_sens_face_rate<VJP, 0, 0>), wgs, waves, waves * per_wave, h->stream, q));
+    const int waves = waves_in_lds(per_wave, with_S ? SENS_FACE_RATE_WAVES : SENS_FACE_WAVES), wgs = capped_grid(h->batch, waves, 16 * h->num_cus);
+    const bool quad = h->n == 12 && h->m == 4;
+    if (with_S && quad) HIP_TRY(h, LAUNCH_WAVES((k_sens_face_rate<VJP, 12, 4>), wgs, waves, waves * per_wave, h->stream, q));
+    else if (with_S) HIP_TRY(h, LAUNCH_WAVES((k_sens_face_rate<VJP, 0, 0>), wgs, waves, waves * per_wave, h->stream, q));
+    else if (quad) HIP_TRY(h, LAUNCH_WAVES((k_sens_face<VJP, 12, 4>), wgs, waves, waves * per_wave, h->stream, q.f));
+    else HIP_TRY(h, LAUNCH_WAVES((k_sens_face<VJP, 0, 0>), wgs, waves, waves * per_wave, h->stream, q.f));
     return ALMPC_OK;
 }
 
-int sens_face_rate_jacobians(almpc_handle* h, uint32_t want, double act_tol) {
-    const char* who = "sensitivity_stagewise_rate";
-    ALMPC_TRY(sens_face_rate_check(h, who));
+int sens_face_jacobians(almpc_handle* h, const char* who, uint32_t want, double act_tol, bool rate) {
+    ALMPC_TRY(sens_face_check(h, who, rate));
     if (!want || (want & ~(ALMPC_SENS_K0 | ALMPC_SENS_DU | ALMPC_SENS_DX))) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": want must be a mask of ALMPC_SENS_*");
-    if (!h->useS) return sens_face_jacobians(h, want, act_tol);   // (no rate term: k_sens_face, to the byte)
+    const bool with_S = rate && h->useS;
     HIP_TRY(h, hipSetDevice(h->device));
     ALMPC_TRY(wait_and_settle(h));
     const size_t b = (size_t)h->batch, n = (size_t)h->n;
     h->sens.have = 0;
     SensFaceRateParams q;
-    ALMPC_TRY(sens_face_rate_params(h, act_tol, q));
+    ALMPC_TRY(sens_face_params(h, act_tol, with_S, q));
     HIP_TRY(h, h->sens.rows.grow(b));
     if (want & ALMPC_SENS_K0) HIP_TRY(h, h->sens.K0.grow(b * n * h->m));
     if (want & (ALMPC_SENS_DU | ALMPC_SENS_DX)) {   // (the forward pass writes dU on its way to dX)
         HIP_TRY(h, h->sens.dU.grow(b * n * h->nz));
-        HIP_TRY(h, h->sens.Kst.grow(b * h->nz * (n + h->m)));
+        HIP_TRY(h, h->sens.Kst.grow(b * h->nz * (n + (with_S ? h->m : 0))));
     }
     if (want & ALMPC_SENS_DX) HIP_TRY(h, h->sens.dX.grow(b * n * (h->N + 1) * n));
     q.f.want = want; q.f.K0 = h->sens.K0; q.f.dU = h->sens.dU; q.f.dX = h->sens.dX; q.f.Kst = h->sens.Kst; q.f.rows = h->sens.rows;
-    ALMPC_TRY(sens_face_rate_launch<false>(h, q));
+    ALMPC_TRY(sens_face_launch<false>(h, q));
     HIP_TRY(h, stream_wait_polling(h));
     h->sens.have = want | ((want & ALMPC_SENS_DX) ? ALMPC_SENS_DU : 0u);
     return ALMPC_OK;
 }
 
-int sens_face_rate_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows_out) {
-    const char* who = "sensitivity_stagewise_rate_vjp";
-    ALMPC_TRY(sens_face_rate_check(h, who));
+int sens_face_vjp(almpc_handle* h, const char* who, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows_out,
+                  bool rate) {
+    ALMPC_TRY(sens_face_check(h, who, rate));
     if (!g_u || !g_x0) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": null g_u or g_x0");
-    if (!h->useS) return sens_face_vjp(h, g_u, g_x, act_tol, g_x0, rows_out);
+    const bool with_S = rate && h->useS;
     HIP_TRY(h, hipSetDevice(h->device));
     ALMPC_TRY(wait_and_settle(h));
     const size_t b = (size_t)h->batch, n = (size_t)h->n, xs = n * (h->N + 1);
     SensFaceRateParams q;
-    ALMPC_TRY(sens_face_rate_params(h, act_tol, q));
+    ALMPC_TRY(sens_face_params(h, act_tol, with_S, q));
     HIP_TRY(h, h->sens.vrows.grow(b)); HIP_TRY(h, h->sens.gx0.grow(b * n)); HIP_TRY(h, h->sens.gu.grow(b * h->nz));
     HIP_TRY(h, hipMemcpyAsync(h->sens.gu, g_u, b * h->nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (g_x) {
@@ -4907,7 +4835,7 @@ int sens_face_rate_vjp(almpc_handle* h, const double* g_u, const double* g_x, do
         HIP_TRY(h, hipMemcpyAsync(h->sens.gx, g_x, b * xs * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
     q.f.g_u = h->sens.gu; q.f.g_x = g_x ? h->sens.gx.get() : nullptr; q.f.g_x0 = h->sens.gx0; q.f.rows = h->sens.vrows;
-    ALMPC_TRY(sens_face_rate_launch<true>(h, q));
+    ALMPC_TRY(sens_face_launch<true>(h, q));
     HIP_TRY(h, hipMemcpyAsync(g_x0, h->sens.gx0, b * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (rows_out) HIP_TRY(h, hipMemcpyAsync(rows_out, h->sens.vrows, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, stream_wait_polling(h));
@@ -4968,16 +4896,20 @@ int almpc_sensitivity_params_vjp_dare(almpc_handle* h, const double* g_u, const 
     return sens_params_vjp(h, g_u, g_x, act_tol, out, true, dare_status);
 }
 
-int almpc_sensitivity_stagewise(almpc_handle* h, uint32_t want, double act_tol) { return sens_face_jacobians(h, want, act_tol); }
-
-int almpc_sensitivity_stagewise_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows) {
-    return sens_face_vjp(h, g_u, g_x, act_tol, g_x0, rows);
+int almpc_sensitivity_stagewise(almpc_handle* h, uint32_t want, double act_tol) {
+    return sens_face_jacobians(h, "sensitivity_stagewise", want, act_tol, false);
 }
 
-int almpc_sensitivity_stagewise_rate(almpc_handle* h, uint32_t want, double act_tol) { return sens_face_rate_jacobians(h, want, act_tol); }
+int almpc_sensitivity_stagewise_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows) {
+    return sens_face_vjp(h, "sensitivity_stagewise_vjp", g_u, g_x, act_tol, g_x0, rows, false);
+}
+
+int almpc_sensitivity_stagewise_rate(almpc_handle* h, uint32_t want, double act_tol) {
+    return sens_face_jacobians(h, "sensitivity_stagewise_rate", want, act_tol, true);
+}
 
 int almpc_sensitivity_stagewise_rate_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows) {
-    return sens_face_rate_vjp(h, g_u, g_x, act_tol, g_x0, rows);
+    return sens_face_vjp(h, "sensitivity_stagewise_rate_vjp", g_u, g_x, act_tol, g_x0, rows, true);
 }
 
 }  // extern "C"

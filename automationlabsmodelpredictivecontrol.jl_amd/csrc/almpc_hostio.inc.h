@@ -303,6 +303,24 @@ int group_fanout(almpc_group* g, F&& call) {
     return ALMPC_OK;
 }
 
+// The group form of every sensitivity call: every device looks at its own shard's last step at the same time; host arrays are those
+// of the single-handle calls with `batch` = the whole batch, cut along the shards.  `call` is the per-handle entry point with its
+// tolerances bound: call(h, want) for the Jacobians, call(h, g_u, g_x, g_x0, rows) on the shard's slices for a VJP.
+template <class Call>
+int group_sens_jacobians(almpc_group* g, uint32_t want, Call&& call) {
+    if (!g) return ALMPC_ERR_INVALID;
+    return group_fanout(g, [&](int i) { return call(g->hs[i], want); });
+}
+template <class Call>
+int group_sens_vjp(almpc_group* g, const double* g_u, const double* g_x, double* g_x0, int32_t* rows, Call&& call) {
+    if (!g || !g_u || !g_x0) return ALMPC_ERR_INVALID;
+    const size_t n = (size_t)g->n, nz = (size_t)g->m * g->N;
+    return group_fanout(g, [&](int i) {
+        const size_t f = (size_t)g->first[i];
+        return call(g->hs[i], g_u + f * nz, g_x ? g_x + f * n * (g->N + 1) : nullptr, g_x0 + f * n, rows ? rows + f : nullptr);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -629,11 +647,9 @@ int almpc_group_get_results(almpc_group* g, double* x, double* e_x, double* u, d
     return ALMPC_OK;
 }
 
-// Sensitivities of the whole batch (almpc_sensitivity and its getters): every device looks at its own shard's last step at the same
-// time; host arrays are those of the single-handle calls with `batch` = the whole batch, cut along the shards.
+// Sensitivities of the whole batch (group_sens_jacobians, group_sens_vjp above): almpc_sensitivity and its getters ...
 int almpc_group_sensitivity(almpc_group* g, uint32_t want, double act_tol) {
-    if (!g) return ALMPC_ERR_INVALID;
-    return group_fanout(g, [&](int i) { return almpc_sensitivity(g->hs[i], want, act_tol); });
+    return group_sens_jacobians(g, want, [=](almpc_handle* h, uint32_t w) { return almpc_sensitivity(h, w, act_tol); });
 }
 int almpc_group_get_sensitivity(almpc_group* g, double* K0, double* dU, double* dX, int32_t* rows) {
     if (!g) return ALMPC_ERR_INVALID;
@@ -647,54 +663,36 @@ int almpc_group_get_sensitivity(almpc_group* g, double* K0, double* dU, double* 
     return ALMPC_OK;
 }
 int almpc_group_sensitivity_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows) {
-    if (!g || !g_u || !g_x0) return ALMPC_ERR_INVALID;
-    const size_t n = (size_t)g->n, nz = (size_t)g->m * g->N;
-    return group_fanout(g, [&](int i) {
-        const size_t f = (size_t)g->first[i];
-        return almpc_sensitivity_vjp(g->hs[i], g_u + f * nz, g_x ? g_x + f * n * (g->N + 1) : nullptr, act_tol, g_x0 + f * n, rows ? rows + f : nullptr);
+    return group_sens_vjp(g, g_u, g_x, g_x0, rows, [=](almpc_handle* h, const double* gu, const double* gx, double* gx0, int32_t* r) {
+        return almpc_sensitivity_vjp(h, gu, gx, act_tol, gx0, r);
     });
 }
-// ... and the rows forms (almpc_sensitivity_rows, almpc_sensitivity_rows_vjp); almpc_group_get_sensitivity serves both
+// ... and the rows forms (almpc_sensitivity_rows, almpc_sensitivity_rows_vjp); almpc_group_get_sensitivity serves every form
 int almpc_group_sensitivity_rows(almpc_group* g, uint32_t want, double act_tol_u, double act_tol_x) {
-    if (!g) return ALMPC_ERR_INVALID;
-    return group_fanout(g, [&](int i) { return almpc_sensitivity_rows(g->hs[i], want, act_tol_u, act_tol_x); });
+    return group_sens_jacobians(g, want, [=](almpc_handle* h, uint32_t w) { return almpc_sensitivity_rows(h, w, act_tol_u, act_tol_x); });
 }
 int almpc_group_sensitivity_rows_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol_u, double act_tol_x, double* g_x0,
                                      int32_t* rows) {
-    if (!g || !g_u || !g_x0) return ALMPC_ERR_INVALID;
-    const size_t n = (size_t)g->n, nz = (size_t)g->m * g->N;
-    return group_fanout(g, [&](int i) {
-        const size_t f = (size_t)g->first[i];
-        return almpc_sensitivity_rows_vjp(g->hs[i], g_u + f * nz, g_x ? g_x + f * n * (g->N + 1) : nullptr, act_tol_u, act_tol_x, g_x0 + f * n,
-                                          rows ? rows + f : nullptr);
+    return group_sens_vjp(g, g_u, g_x, g_x0, rows, [=](almpc_handle* h, const double* gu, const double* gx, double* gx0, int32_t* r) {
+        return almpc_sensitivity_rows_vjp(h, gu, gx, act_tol_u, act_tol_x, gx0, r);
     });
 }
-// ... and the forms of structured handles (almpc_sensitivity_stagewise, almpc_sensitivity_stagewise_vjp); almpc_group_get_sensitivity again
+// ... and the forms of structured handles (almpc_sensitivity_stagewise, almpc_sensitivity_stagewise_vjp)
 int almpc_group_sensitivity_stagewise(almpc_group* g, uint32_t want, double act_tol) {
-    if (!g) return ALMPC_ERR_INVALID;
-    return group_fanout(g, [&](int i) { return almpc_sensitivity_stagewise(g->hs[i], want, act_tol); });
+    return group_sens_jacobians(g, want, [=](almpc_handle* h, uint32_t w) { return almpc_sensitivity_stagewise(h, w, act_tol); });
 }
 int almpc_group_sensitivity_stagewise_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows) {
-    if (!g || !g_u || !g_x0) return ALMPC_ERR_INVALID;
-    const size_t n = (size_t)g->n, nz = (size_t)g->m * g->N;
-    return group_fanout(g, [&](int i) {
-        const size_t f = (size_t)g->first[i];
-        return almpc_sensitivity_stagewise_vjp(g->hs[i], g_u + f * nz, g_x ? g_x + f * n * (g->N + 1) : nullptr, act_tol, g_x0 + f * n,
-                                               rows ? rows + f : nullptr);
+    return group_sens_vjp(g, g_u, g_x, g_x0, rows, [=](almpc_handle* h, const double* gu, const double* gx, double* gx0, int32_t* r) {
+        return almpc_sensitivity_stagewise_vjp(h, gu, gx, act_tol, gx0, r);
     });
 }
 // ... and those of structured designs with or without S (almpc_sensitivity_stagewise_rate, almpc_sensitivity_stagewise_rate_vjp)
 int almpc_group_sensitivity_stagewise_rate(almpc_group* g, uint32_t want, double act_tol) {
-    if (!g) return ALMPC_ERR_INVALID;
-    return group_fanout(g, [&](int i) { return almpc_sensitivity_stagewise_rate(g->hs[i], want, act_tol); });
+    return group_sens_jacobians(g, want, [=](almpc_handle* h, uint32_t w) { return almpc_sensitivity_stagewise_rate(h, w, act_tol); });
 }
 int almpc_group_sensitivity_stagewise_rate_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows) {
-    if (!g || !g_u || !g_x0) return ALMPC_ERR_INVALID;
-    const size_t n = (size_t)g->n, nz = (size_t)g->m * g->N;
-    return group_fanout(g, [&](int i) {
-        const size_t f = (size_t)g->first[i];
-        return almpc_sensitivity_stagewise_rate_vjp(g->hs[i], g_u + f * nz, g_x ? g_x + f * n * (g->N + 1) : nullptr, act_tol, g_x0 + f * n,
-                                                    rows ? rows + f : nullptr);
+    return group_sens_vjp(g, g_u, g_x, g_x0, rows, [=](almpc_handle* h, const double* gu, const double* gx, double* gx0, int32_t* r) {
+        return almpc_sensitivity_stagewise_rate_vjp(h, gu, gx, act_tol, gx0, r);
     });
 }
 // ... and the parameter gradients (almpc_sensitivity_params_vjp): every output is per instance, so the shards' slices are disjoint

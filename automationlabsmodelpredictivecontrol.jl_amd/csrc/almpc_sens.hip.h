@@ -688,30 +688,57 @@ inline __global__ __launch_bounds__(256) void k_sens_rows_table(SensRowsTablePar
     }
 }
 
-// ---- k_sens_face: the same sensitivities on a structured handle (almpc_sensitivity_stagewise, almpc_sensitivity_stagewise_vjp) --------
+// ---- k_sens_face, k_sens_face_rate: the same sensitivities on a structured handle --------
+// (almpc_sensitivity_stagewise, almpc_sensitivity_stagewise_vjp; with the input-rate weight S almpc_sensitivity_stagewise_rate, .._rate_vjp)
 //
 // A structured handle forms no G = H'^-1, and none is needed: on the face where the rows W of the returned u are held the problem is
 // an LQ problem whose clamped inputs are taken out stage by stage, and its derivative in x0 is a Riccati recursion with a masked B --
-// O(N (n^3 + n^2 m)) per instance, whatever m N and the spectral radius of A.  Input box only, S = 0.  Stages 0-based: x_0 = x0,
-// Qbar_k = Q (1 <= k <= N-1), Qbar_0 = 0, P on stage N; W_k the inputs of stage k at a bound, f the free ones:
-//     P+ = P at k = N;  for k = N-1 .. 0:
-//       Lam = R_ff + B_f' P+ B_f                 (R as the design uses it: zero when R[1,1] == 0)
-//       K_k[f,:] = Lam^-1 B_f' P+ A,   K_k[W_k,:] = 0,   Acl_k = A - B K_k
-//       P+ <- Qbar_k + Acl_k' P+ Acl_k + K_k' R K_k            (symmetrised)
-//     Jacobians:  dx_0 = I,  du_k = -K_k dx_k,  dx_{k+1} = A dx_k + B du_k          (K0 = -K_0)
-//     VJP:        lam_N = g_x[N],  lam_k = g_x[k] - K_k' g_u[k] + Acl_k' lam_{k+1},   g_x0 = lam_0
+// O(N (n^3 + n^2 m)) per instance, whatever m N and the spectral radius of A.  Input box only.  Both kernels are the same sweep over a
+// stage state of width w (w = n without S, w = nt = n + m with it), put together from the pieces below (sens_face_*); what a stage
+// computes between them -- P+ B, the right-hand side and Lam, Acl, the Riccati update -- is each kernel's own.  Stages 0-based, W_k the
+// inputs of stage k at a bound, f the free ones:
+//     backward, k = N-1 .. 0:  Lam (m x m, identity on W_k) and the right-hand side (m x w, rows W_k zero) from P+   [the kernel]
+//                              K_k = Lam^-1 rhs                                                                    [sens_face_gain_solve]
+//                              Acl_k, and P+ <- the Riccati update (k >= 1 only: P_0 has no reader)                  [the kernel]
+//     Jacobians:  dz_0 = [I_n; 0],  du_k = -K_k dz_k,  dx_{k+1} = A dx_k + B du_k          (K0 = -K_0[:, :n])        [sens_face_forward_rate; k_sens_face: in its body]
+//     VJP:        lam_N = [g_x[N]; 0],  lam_k = [g_x[k]; 0] - K_k' g_u[k] + Acl_k' lam_{k+1},   g_x0 = lam_0[:n]     [sens_face_costate]
 // The VJP rides the backward sweep (no stored gains, no Jacobian); K0 alone is the backward sweep; dU and dX need the gains of every
-// stage, which go to a per-instance scratch [N][m n] in global memory and come back one stage ahead in the forward pass.
+// stage, which go to a per-instance scratch Kst [N][m w] in global memory (stage k at k m w, column-major m x w, the x columns first)
+// and come back one stage ahead in the forward pass.
 //
-// Active-set rule, on the returned u (there is no Jacobi scale here): row (k, i) is in W iff  u[i,k] - umin_i <= tau w_i  or
-// umax_i - u[i,k] <= tau w_i,  w_i = umax_i - umin_i.  Weakly active rows: the derivative of the face on which every flagged row is
-// held, as in k_sens.
+// Conventions, stated once for both kernels:
+//   Active-set rule, on the returned u (there is no Jacobi scale here): row (k, i) is in W iff  u[i,k] - umin_i <= tau w_i  or
+//     umax_i - u[i,k] <= tau w_i,  w_i = umax_i - umin_i.  Weakly active rows: the derivative of the face on which every flagged row
+//     is held, as in k_sens.  A clamped input is an identity row and column of Lam, so the factor is that of the free block.
+//   Team: one wave per instance, up to SENS_FACE_WAVES (SENS_FACE_RATE_WAVES) waves per workgroup that never wait for each other;
+//     every matrix of a stage in the wave's slice of LDS, column-major.  Every hand-over through LDS is a SensTeam<false> fence
+//     (release, wave barrier, acquire); a piece says in its comment which fences it holds and which it leaves to its caller.
+//   Failure: an unsolved instance (status != 0), or a pivot of Lam that is not positive and finite, gives rows = -1 and zeros in every
+//     output that was asked for (sens_face_unsolved).
+//   <NC, MC>: dimensions known at compile time (0, 0: from the parameters), as k_riccati_t.
 //
-// One wave per instance, up to SENS_FACE_WAVES waves per workgroup that never wait for each other; every matrix of a stage in the
-// wave's slice of LDS, column-major: A, Q, P+, T (= P+ Acl, then the new P before it is symmetrised; dx+ in the forward pass), Acl |
-// B, P+ B, K (B'P+A solved in place), R K | R, Lam (Cholesky in place; a clamped input is an identity row and column, so the factor
-// is that of the free block) | lam, lam+ | the stage masks.  A pivot that is not positive and finite: rows = -1 and zeros, as an
-// unsolved instance.  <NC, MC>: dimensions known at compile time (0, 0: from the parameters), as k_riccati_t.
+// k_sens_face (S = 0; w = n):
+//     P+ = sym(P) at k = N;  Lam = R_ff + B_f' P+ B_f  (R as the design uses it: zero when R[1,1] == 0),  rhs = B_f' P+ A,
+//     Acl_k = A - B K_k,   P+ <- Qbar_k + Acl_k' P+ Acl_k + K_k' R K_k  (symmetrised),  Qbar_k = Q (1 <= k <= N-1)
+//   every product one entry per lane (sens_face_mul), which fixes its order of summation.  LDS: A, Q, P+, T (= P+ Acl, then the new P
+//   before it is symmetrised; dx+ in the forward pass), Acl | B, P+ B, K (solved in place), R K | R, Lam | lam, lam+ | the stage masks.
+//
+// k_sens_face_rate (S in the design; w = nt):
+//   The cost carries sum_k (u_k - u_{k+1})' S (u_k - u_{k+1}), k = 0 .. N-2, so a stage sees the input before it: the face problem is
+//   an LQ problem in the stage state z_k = [dx_k; du_{k-1}].  R as the design uses it, S symmetrised; S_k = S for k >= 1 and S_0 = 0
+//   (nothing ties u_0 to an input applied before the horizon):
+//     At = [A 0; 0 0] (nt x nt)    Bt = [B; I] (nt x m)    Nt_k = [0; -S_k] (nt x m)    Rt_k = R + S_k    Qt_k = blkdiag(Qbar_k, S_k)
+//     Pi+ = blkdiag(sym(P), 0) at k = N;  Lam = (Rt_k + Bt' Pi+ Bt)_ff,  rhs = (Bt' Pi+ At + Nt_k')_f,  Acl_k = At - Bt K_k,
+//     Pi+ <- Qt_k + K_k' Rt_k K_k - Nt_k K_k - K_k' Nt_k' + Acl_k' Pi+ Acl_k            (symmetrised)
+//   The blocks of At, Bt and Nt are used where they are cheap: Pi+ Bt = Pi+[:, :n] B + Pi+[:, n:],  Bt' Pi+ At = [(Pi+ Bt)[:n]' A, 0],
+//   the w columns of B'Pi+At + Nt' are -S_k, the lower rows of Acl are -K, and dz is carried as dx (n x n) and the du before (m x n).
+//   Pi+ Acl and Acl' (Pi+ Acl) are full nt x nt products (the closed loop has no zero block), computed by 2 x 2 blocks of the result
+//   in a lane's registers (sens_face_mul22): the one-entry-per-lane product of k_sens_face read every operand word from LDS once per
+//   product and made K0 of 4096 quadrotors at N = 50 cost 3.5 times k_sens_face on the S = 0 design; blocked it costs 1.8 times.
+//   LDS: A, Q (n x n) | Pi+, T (= Pi+ Acl, then the symmetrised new Pi), Acl (nt x nt) | B (n x m) | Pi+ Bt, K, Rt K, S K (nt x m or
+//   m x nt) | R, S, Lam (m x m) | lam, lam+ (nt) | the stage masks.  The new Pi is written over the old one, which has no reader once
+//   Pi+ Acl is formed, and symmetrised into T; then the two change places -- no per-lane copy of a matrix, whatever nt.  The look-ahead
+//   gain of the forward pass is the only per-lane array: m nt <= 768 entries, 12 a lane.
 constexpr int SENS_FACE_WAVES = 4;
 
 struct SensFaceParams {
@@ -748,6 +775,223 @@ __device__ __forceinline__ void sens_face_mul(double* out, const double* X, cons
     }
 }
 
+// ---- the pieces both kernels are put together from.  n, m, N are the kernel's own (compile-time in a <NC, MC> build); w is the width
+// of its stage state; every pointer is into the calling wave's slice of LDS unless it says global.
+
+// A, Q, B and R of the instance into LDS.  No fence: the one inside sens_face_active_set, which follows, hands them over.  Behind this
+// call and in front of that fence each kernel writes what is its own, in loops of its own: P+ (sym(P), or blkdiag(sym(P), 0)) and,
+// with the rate weight, sym(S).  These stores are independent copies into disjoint arrays, so their order among themselves changes
+// no bit; both kernels use the same one (stage_in, P+, S).
+__device__ __forceinline__ void sens_face_stage_in(const SensFaceParams& p, int inst, double* As, double* Qs, double* Bs, double* Rs,
+                                                   int n, int m, int lane) {
+    const double* Ag = p.A + (size_t)inst * p.A_stride;
+    const double* Bg = p.B + (size_t)inst * p.B_stride;
+    for (int t = lane; t < n * n; t += 64) { As[t] = Ag[t]; Qs[t] = p.Q[t]; }
+    for (int t = lane; t < n * m; t += 64) Bs[t] = Bg[t];
+    for (int t = lane; t < m * m; t += 64) Rs[t] = p.R[t];
+}
+
+// The rows at a bound: wset[k] bit a = input a of stage k is held (m <= 16 bits of a word).  Returns |W|, the same in every lane.  One
+// fence, between the zeroing of the masks and the flags; the masks themselves are handed over by the caller's next fence.
+__device__ __forceinline__ int sens_face_active_set(const SensTeam<false>& T, const SensFaceParams& p, int inst, uint32_t* wset,
+                                                    int m, int N, int lane) {
+    const int nz = N * m;
+    int rows = 0;
+    for (int k = lane; k < N; k += 64) wset[k] = 0u;
+    T.sync();
+    for (int t = lane; t < nz; t += 64) {
+        const int k = t / m, a = t - k * m;
+        const double uj = p.u[(size_t)inst * nz + t], lo = p.umin[a], hi = p.umax[a], tol = p.tau * (hi - lo);
+        if (uj - lo <= tol || hi - uj <= tol) { atomicOr(&wset[k], 1u << a); ++rows; }
+    }
+    for (int o = 32; o > 0; o >>= 1) rows += __shfl_xor(rows, o);
+    return rows;
+}
+
+// K = Lam^-1 K in place: Lam (m x m, SPD on the free inputs, identity on the held ones) is factored, then a lane takes a column of K
+// (m x cols) through both substitutions.  False on a pivot that is not positive and finite (every lane sees the same one): the caller
+// leaves its sweep for sens_face_unsolved.  0 < MC <= 4: every lane factors Lam in its own registers (ten entries, no fence between
+// the pivots; the diagonal is kept as its reciprocal).  Otherwise the Cholesky factor replaces the lower triangle of Lam in LDS, three
+// fences a pivot.  The caller fences in front (Lam and K written) and behind (K read).
+template <int MC>
+__device__ __forceinline__ bool sens_face_gain_solve(const SensTeam<false>& T, double* Lam, double* Ks, int m, int cols, int lane) {
+    if constexpr (MC > 0 && MC <= 4) {
+        bool ok = true;
+        double l[MC][MC];
+#pragma unroll
+        for (int i = 0; i < MC; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) l[i][j] = Lam[i + j * MC];
+#pragma unroll
+        for (int c = 0; c < MC; ++c) {
+            const double piv = l[c][c];
+            if (!(piv > 0.0 && piv <= 1.7976931348623157e308)) ok = false;
+            const double inv = 1.0 / sqrt(piv);
+            l[c][c] = inv;
+#pragma unroll
+            for (int i = c + 1; i < MC; ++i) l[i][c] *= inv;
+#pragma unroll
+            for (int j = c + 1; j < MC; ++j)
+#pragma unroll
+                for (int i = j; i < MC; ++i) l[i][j] -= l[i][c] * l[j][c];
+        }
+        if (!ok) return false;
+        for (int c = lane; c < cols; c += 64) {
+            double x[MC];
+#pragma unroll
+            for (int i = 0; i < MC; ++i) x[i] = Ks[i + c * MC];
+#pragma unroll
+            for (int i = 0; i < MC; ++i) {
+#pragma unroll
+                for (int j = 0; j < i; ++j) x[i] -= l[i][j] * x[j];
+                x[i] *= l[i][i];
+            }
+#pragma unroll
+            for (int i = MC - 1; i >= 0; --i) {
+#pragma unroll
+                for (int j = i + 1; j < MC; ++j) x[i] -= l[j][i] * x[j];
+                x[i] *= l[i][i];
+            }
+#pragma unroll
+            for (int i = 0; i < MC; ++i) Ks[i + c * MC] = x[i];
+        }
+    } else {
+        for (int c = 0; c < m; ++c) {
+            const double piv = Lam[c + c * m];                 // (every lane reads the same word)
+            if (!(piv > 0.0 && piv <= 1.7976931348623157e308)) return false;
+            const double dk = sqrt(piv);
+            T.sync();
+            for (int i = c + lane; i < m; i += 64) Lam[i + c * m] = i == c ? dk : Lam[i + c * m] / dk;
+            T.sync();
+            const int rem = m - c - 1;
+            for (int idx = lane; idx < rem * rem; idx += 64) {
+                const int i = c + 1 + idx / rem, j = c + 1 + idx % rem;
+                if (j <= i) Lam[i + j * m] -= Lam[i + c * m] * Lam[j + c * m];
+            }
+            T.sync();
+        }
+        for (int c = lane; c < cols; c += 64) {
+            double* x = Ks + c * m;
+            for (int i = 0; i < m; ++i) {
+                double s = x[i];
+                for (int j = 0; j < i; ++j) s -= Lam[i + j * m] * x[j];
+                x[i] = s / Lam[i + i * m];
+            }
+            for (int i = m - 1; i >= 0; --i) {
+                double s = x[i];
+                for (int j = i + 1; j < m; ++j) s -= Lam[j + i * m] * x[j];
+                x[i] = s / Lam[i + i * m];
+            }
+        }
+    }
+    return true;
+}
+
+// The costate of the VJP, lam_k = [g_x[k]; 0] - K_k' g_u[k] + Acl_k' lam_{k+1}: n of its w rows have a g_x.
+// sens_face_costate_end writes lam_N = [g_x[N]; 0] (0.0 is added where g_x is null, so that a null g_x and a g_x of zeros give the same
+// bits); sens_face_costate returns row `lane` of lam_k (0 beyond w), which the caller stores behind its own fence.
+__device__ __forceinline__ void sens_face_costate_end(const SensFaceParams& p, int inst, double* lam, int n, int w, int N, int lane) {
+    const double* gx = p.g_x ? p.g_x + (size_t)inst * (N + 1) * n : nullptr;
+    for (int i = lane; i < w; i += 64) lam[i] = i < n ? 0.0 + (gx ? gx[(size_t)N * n + i] : 0.0) : 0.0;
+}
+__device__ __forceinline__ double sens_face_costate(const SensFaceParams& p, int inst, int k, const double* Ks, const double* Ac,
+                                                    const double* lam, int n, int w, int m, int N, int lane) {
+    double ln = 0.0;
+    if (lane < w) {
+        const double* gu = p.g_u + (size_t)inst * (N * m) + (size_t)k * m;
+        ln = (p.g_x && lane < n) ? p.g_x[((size_t)inst * (N + 1) + k) * n + lane] : 0.0;
+        for (int a = 0; a < m; ++a) ln -= Ks[a + lane * m] * gu[a];
+        for (int l = 0; l < w; ++l) ln += Ac[l + lane * w] * lam[l];
+    }
+    return ln;
+}
+
+// An unsolved instance, or a pivot that is not positive and finite: zeros in what was asked for, rows = -1
+template <bool VJP>
+__device__ __forceinline__ void sens_face_unsolved(const SensFaceParams& p, int inst, int n, int m, int N, int lane) {
+    const int nn = n * n, nm = n * m, nz = N * m;
+    if (VJP) {
+        for (int c = lane; c < n; c += 64) p.g_x0[(size_t)inst * n + c] = 0.0;
+    } else {
+        if (p.want & SENS_K0)
+            for (int t = lane; t < nm; t += 64) p.K0[(size_t)inst * nm + t] = 0.0;
+        if (p.want & (SENS_DU | SENS_DX))
+            for (int t = lane; t < n * nz; t += 64) p.dU[(size_t)inst * n * nz + t] = 0.0;
+        if (p.want & SENS_DX)
+            for (int t = lane; t < (N + 1) * nn; t += 64) p.dX[(size_t)inst * (N + 1) * nn + t] = 0.0;
+    }
+    if (lane == 0) p.rows[inst] = -1;
+}
+
+// The forward pass behind a backward sweep in the stage state [dx; du-] that stored its gains in p.Kst: dU, and dX where it is asked
+// for.  dx and dxn are n x n, du and dup (the du of the stage before) m x n; Ks takes the stage's gain, m x (n + m).  The gains were
+// stored by other lanes of this wave: made visible at device scope, read back past the L1 and one stage ahead, in look-ahead
+// registers whose number follows from KM_MAX, the caller's compile-time bound on m (n + m) -- a caller cannot truncate the gain.
+// dz_0 = [I; 0] gives du_0 the bits of K0.  (k_sens_face keeps its own forward pass in its body: see there.)
+template <int KM_MAX>
+__device__ __forceinline__ void sens_face_forward_rate(const SensTeam<false>& T, const SensFaceParams& p, int inst, const double* As,
+                                                       const double* Bs, double* Ks, double* dx, double* dxn, double* du, double* dup,
+                                                       int n, int m, int N, int lane) {
+    constexpr int KREG = (KM_MAX + 63) / 64;
+    const int nn = n * n, nm = n * m, nz = N * m, km = (n + m) * m;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __builtin_amdgcn_wave_barrier();
+    const double* Kg = p.Kst + (size_t)inst * N * km;
+    double* dUo = p.dU + (size_t)inst * n * nz;
+    double* dXo = p.dX + (size_t)inst * (N + 1) * nn;
+    const bool wdx = (p.want & SENS_DX) != 0;
+    double kreg[KREG];
+    auto kload = [&](int k) {
+#pragma unroll
+        for (int c = 0; c < KREG; ++c) {
+            const int t = lane + 64 * c;
+            kreg[c] = t < km ? __hip_atomic_load(Kg + (size_t)k * km + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+        }
+    };
+    kload(0);
+    for (int t = lane; t < nn; t += 64) {
+        const int i = t % n, c = t / n;
+        const double v = i == c ? 1.0 : 0.0;
+        dx[t] = v;
+        if (wdx) dXo[(size_t)c * (N + 1) * n + i] = v;
+    }
+    T.sync();
+    for (int k = 0; k < N; ++k) {
+#pragma unroll
+        for (int c = 0; c < KREG; ++c) {
+            const int t = lane + 64 * c;
+            if (t < km) Ks[t] = kreg[c];
+        }
+        if (k + 1 < N) kload(k + 1);
+        T.sync();
+        for (int t = lane; t < nm; t += 64) {                  // du = -K dz = -K_x dx - K_w du-
+            const int a = t % m, c = t / m;
+            double s = 0.0;
+            if (k == 0) s -= Ks[t];
+            else {
+                for (int j = 0; j < n; ++j) s -= Ks[a + j * m] * dx[j + c * n];
+                for (int b = 0; b < m; ++b) s -= Ks[a + (n + b) * m] * dup[b + c * m];
+            }
+            du[t] = s;
+            dUo[(size_t)c * nz + (size_t)k * m + a] = s;
+        }
+        T.sync();
+        if (k + 1 < N || wdx) {
+            for (int t = lane; t < nn; t += 64) {              // dx+ = A dx + B du
+                const int i = t % n, c = t / n;
+                double s = 0.0;
+                for (int j = 0; j < n; ++j) s += As[i + j * n] * dx[j + c * n];
+                for (int a = 0; a < m; ++a) s += Bs[i + a * n] * du[a + c * m];
+                dxn[t] = s;
+                if (wdx) dXo[((size_t)c * (N + 1) + k + 1) * n + i] = s;
+            }
+            T.sync();
+            double* sw = dx; dx = dxn; dxn = sw;
+        }
+        { double* sw = du; du = dup; dup = sw; }
+    }
+}
+
 template <bool VJP, int NC, int MC>
 __global__ __launch_bounds__(64 * SENS_FACE_WAVES) void k_sens_face(SensFaceParams p) {
     extern __shared__ __attribute__((aligned(16))) double sens_face_smem[];
@@ -759,7 +1003,7 @@ __global__ __launch_bounds__(64 * SENS_FACE_WAVES) void k_sens_face(SensFacePara
     double* Bs = Ac + nn;      double* PB = Bs + nm;    double* Ks = PB + nm;   double* RK = Ks + nm;
     double* Rs = RK + nm;      double* Lam = Rs + mm;
     double* lam = Lam + mm;    double* lamn = lam + n;
-    uint32_t* wset = reinterpret_cast<uint32_t*>(lamn + n);   // [N] bit a: input a of the stage is held
+    uint32_t* wset = reinterpret_cast<uint32_t*>(lamn + n);   // [N] the stage masks
     const bool jac = !VJP && (p.want & (SENS_DU | SENS_DX)) != 0;
 
     const int wpb = (int)(blockDim.x >> 6), nwaves = gridDim.x * wpb;
@@ -768,25 +1012,11 @@ __global__ __launch_bounds__(64 * SENS_FACE_WAVES) void k_sens_face(SensFacePara
         bool ok = p.status[inst] == 0;
         int rows = 0;
         if (ok) {
-            const double* Ag = p.A + (size_t)inst * p.A_stride;
-            const double* Bg = p.B + (size_t)inst * p.B_stride;
             const double* Pg = p.P + (size_t)inst * p.P_stride;
-            for (int t = lane; t < nn; t += 64) { As[t] = Ag[t]; Qs[t] = p.Q[t]; Pn[t] = 0.5 * (Pg[t] + Pg[(t % n) * n + t / n]); }
-            for (int t = lane; t < nm; t += 64) Bs[t] = Bg[t];
-            for (int t = lane; t < mm; t += 64) Rs[t] = p.R[t];
-            for (int k = lane; k < N; k += 64) wset[k] = 0u;
-            T.sync();
-            // the rows at a bound
-            for (int t = lane; t < nz; t += 64) {
-                const int k = t / m, a = t - k * m;
-                const double uj = p.u[(size_t)inst * nz + t], lo = p.umin[a], hi = p.umax[a], tol = p.tau * (hi - lo);
-                if (uj - lo <= tol || hi - uj <= tol) { atomicOr(&wset[k], 1u << a); ++rows; }
-            }
-            for (int o = 32; o > 0; o >>= 1) rows += __shfl_xor(rows, o);
-            if (VJP) {   // (0.0 is added where g_x is null, so that a null g_x and a g_x of zeros give the same bits)
-                const double* gx = p.g_x ? p.g_x + (size_t)inst * (N + 1) * n : nullptr;
-                for (int i = lane; i < n; i += 64) lam[i] = 0.0 + (gx ? gx[(size_t)N * n + i] : 0.0);
-            }
+            sens_face_stage_in(p, inst, As, Qs, Bs, Rs, n, m, lane);
+            for (int t = lane; t < nn; t += 64) Pn[t] = 0.5 * (Pg[t] + Pg[(t % n) * n + t / n]);   // P+ = sym(P)
+            rows = sens_face_active_set(T, p, inst, wset, m, N, lane);
+            if (VJP) sens_face_costate_end(p, inst, lam, n, n, N, lane);
             T.sync();
         }
         // ---- backward sweep
@@ -805,79 +1035,7 @@ __global__ __launch_bounds__(64 * SENS_FACE_WAVES) void k_sens_face(SensFacePara
             for (int t = lane; t < nm; t += 64)                // the rows of the held inputs vanish
                 if ((wk >> (t % m)) & 1u) Ks[t] = 0.0;
             T.sync();
-            if constexpr (MC > 0 && MC <= 4) {
-                // m <= 4: every lane factors Lam in its own registers (ten entries, no fence between the pivots; the diagonal is
-                // kept as its reciprocal), then takes a column of B'P+A through both substitutions
-                double l[MC][MC];
-#pragma unroll
-                for (int i = 0; i < MC; ++i)
-#pragma unroll
-                    for (int j = 0; j <= i; ++j) l[i][j] = Lam[i + j * MC];
-#pragma unroll
-                for (int c = 0; c < MC; ++c) {
-                    const double piv = l[c][c];
-                    if (!(piv > 0.0 && piv <= 1.7976931348623157e308)) ok = false;
-                    const double inv = 1.0 / sqrt(piv);
-                    l[c][c] = inv;
-#pragma unroll
-                    for (int i = c + 1; i < MC; ++i) l[i][c] *= inv;
-#pragma unroll
-                    for (int j = c + 1; j < MC; ++j)
-#pragma unroll
-                        for (int i = j; i < MC; ++i) l[i][j] -= l[i][c] * l[j][c];
-                }
-                if (!ok) break;   // (every lane factored the same matrix)
-                for (int c = lane; c < n; c += 64) {
-                    double x[MC];
-#pragma unroll
-                    for (int i = 0; i < MC; ++i) x[i] = Ks[i + c * MC];
-#pragma unroll
-                    for (int i = 0; i < MC; ++i) {
-#pragma unroll
-                        for (int j = 0; j < i; ++j) x[i] -= l[i][j] * x[j];
-                        x[i] *= l[i][i];
-                    }
-#pragma unroll
-                    for (int i = MC - 1; i >= 0; --i) {
-#pragma unroll
-                        for (int j = i + 1; j < MC; ++j) x[i] -= l[j][i] * x[j];
-                        x[i] *= l[i][i];
-                    }
-#pragma unroll
-                    for (int i = 0; i < MC; ++i) Ks[i + c * MC] = x[i];
-                }
-            } else {
-            // Lam = C C' in place (lower triangle)
-            for (int c = 0; c < m; ++c) {
-                const double piv = Lam[c + c * m];             // (every lane reads the same word)
-                if (!(piv > 0.0 && piv <= 1.7976931348623157e308)) { ok = false; break; }
-                const double dk = sqrt(piv);
-                T.sync();
-                for (int i = c + lane; i < m; i += 64) Lam[i + c * m] = i == c ? dk : Lam[i + c * m] / dk;
-                T.sync();
-                const int rem = m - c - 1;
-                for (int idx = lane; idx < rem * rem; idx += 64) {
-                    const int i = c + 1 + idx / rem, j = c + 1 + idx % rem;
-                    if (j <= i) Lam[i + j * m] -= Lam[i + c * m] * Lam[j + c * m];
-                }
-                T.sync();
-            }
-            if (!ok) break;
-            // K = Lam^-1 (B'P+A): a lane takes a column through both substitutions
-            for (int c = lane; c < n; c += 64) {
-                double* x = Ks + c * m;
-                for (int i = 0; i < m; ++i) {
-                    double s = x[i];
-                    for (int j = 0; j < i; ++j) s -= Lam[i + j * m] * x[j];
-                    x[i] = s / Lam[i + i * m];
-                }
-                for (int i = m - 1; i >= 0; --i) {
-                    double s = x[i];
-                    for (int j = i + 1; j < m; ++j) s -= Lam[j + i * m] * x[j];
-                    x[i] = s / Lam[i + i * m];
-                }
-            }
-            }
+            if (!sens_face_gain_solve<MC>(T, Lam, Ks, m, n, lane)) { ok = false; break; }   // K = Lam^-1 (B'P+A)
             T.sync();
             if (jac) {
                 double* Kg = p.Kst + ((size_t)inst * N + k) * nm;
@@ -895,12 +1053,7 @@ __global__ __launch_bounds__(64 * SENS_FACE_WAVES) void k_sens_face(SensFacePara
             if (k > 0) sens_face_mul<false>(RK, Rs, Ks, m, m, n, lane);   // R K
             T.sync();
             double ln = 0.0;
-            if (VJP && lane < n) {                             // lam_k = g_x[k] - K' g_u[k] + Acl' lam_{k+1}
-                const double* gu = p.g_u + (size_t)inst * nz + (size_t)k * m;
-                ln = p.g_x ? p.g_x[((size_t)inst * (N + 1) + k) * n + lane] : 0.0;
-                for (int a = 0; a < m; ++a) ln -= Ks[a + lane * m] * gu[a];
-                for (int l = 0; l < n; ++l) ln += Ac[l + lane * n] * lam[l];
-            }
+            if (VJP) ln = sens_face_costate(p, inst, k, Ks, Ac, lam, n, n, m, N, lane);
             if (k > 0) {
                 sens_face_mul<false>(Tm, Pn, Ac, n, n, n, lane);   // P+ Acl
                 T.sync();
@@ -930,20 +1083,7 @@ __global__ __launch_bounds__(64 * SENS_FACE_WAVES) void k_sens_face(SensFacePara
             T.sync();
             if (VJP) { double* sw = lam; lam = lamn; lamn = sw; }
         }
-        if (!ok) {   // unsolved, or a pivot that is not positive and finite
-            if (VJP) {
-                for (int c = lane; c < n; c += 64) p.g_x0[(size_t)inst * n + c] = 0.0;
-            } else {
-                if (p.want & SENS_K0)
-                    for (int t = lane; t < nm; t += 64) p.K0[(size_t)inst * nm + t] = 0.0;
-                if (jac)
-                    for (int t = lane; t < n * nz; t += 64) p.dU[(size_t)inst * n * nz + t] = 0.0;
-                if (p.want & SENS_DX)
-                    for (int t = lane; t < (N + 1) * nn; t += 64) p.dX[(size_t)inst * (N + 1) * nn + t] = 0.0;
-            }
-            if (lane == 0) p.rows[inst] = -1;
-            continue;
-        }
+        if (!ok) { sens_face_unsolved<VJP>(p, inst, n, m, N, lane); continue; }
         if (lane == 0) p.rows[inst] = rows;
         if (VJP) {
             for (int c = lane; c < n; c += 64) p.g_x0[(size_t)inst * n + c] = lam[c];
@@ -951,7 +1091,9 @@ __global__ __launch_bounds__(64 * SENS_FACE_WAVES) void k_sens_face(SensFacePara
         }
         if (!jac) continue;
         // ---- forward pass: dx in Pn, dx+ in Tm, du in PB.  The gains were stored by other lanes of this wave: made visible at device
-        // scope, read back past the L1 and one stage ahead
+        // scope, read back past the L1 and one stage ahead.  The same scaffold as sens_face_forward_rate without the du- term, kept in the
+        // body: taken out as a function it costs the <.., 12, 4> build its schedule (229 VGPRs for 235, K0 of 4096 quadrotors 0.5 to 0.8 %
+        // slower: DESIGN.md section 4)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         __builtin_amdgcn_wave_barrier();
         const double* Kg = p.Kst + (size_t)inst * N * nm;
@@ -1009,31 +1151,7 @@ __global__ __launch_bounds__(64 * SENS_FACE_WAVES) void k_sens_face(SensFacePara
     }
 }
 
-// ---- k_sens_face_rate: k_sens_face for a design with the input-rate weight S (almpc_sensitivity_stagewise_rate, .._rate_vjp) --------
-//
-// The cost carries sum_k (u_k - u_{k+1})' S (u_k - u_{k+1}), k = 0 .. N-2, so a stage sees the input before it: the face problem is
-// an LQ problem in the stage state z_k = [dx_k; du_{k-1}], nt = n + m.  R as the design uses it, S symmetrised; S_k = S for k >= 1
-// and S_0 = 0 (nothing ties u_0 to an input applied before the horizon):
-//     At = [A 0; 0 0] (nt x nt)    Bt = [B; I] (nt x m)    Nt_k = [0; -S_k] (nt x m)    Rt_k = R + S_k
-//     Qt_k = blkdiag(Qbar_k, S_k),  Qbar_k = Q (1 <= k <= N-1)
-//     Pi+ = blkdiag(sym(P), 0) at k = N;  for k = N-1 .. 0:
-//       Lam = (Rt_k + Bt' Pi+ Bt)_ff
-//       K_k[f,:] = Lam^-1 (Bt' Pi+ At + Nt_k')_f,   K_k[W_k,:] = 0   (m x nt),   Acl_k = At - Bt K_k
-//       Pi+ <- Qt_k + K_k' Rt_k K_k - Nt_k K_k - K_k' Nt_k' + Acl_k' Pi+ Acl_k            (symmetrised; k >= 1 only: Pi_0 has no reader)
-//     Jacobians:  dz_0 = [I_n; 0],  du_k = -K_k dz_k,  dz_{k+1} = [A dx_k + B du_k; du_k]          (K0 = -K_0[:, :n])
-//     VJP:        lam_N = [g_x[N]; 0],  lam_k = [g_x[k]; 0] - K_k' g_u[k] + Acl_k' lam_{k+1},   g_x0 = lam_0[:n]
-// The blocks of At, Bt and Nt are used where they are cheap: Pi+ Bt = Pi+[:, :n] B + Pi+[:, n:],  Bt' Pi+ At = [(Pi+ Bt)[:n]' A, 0],
-// the w columns of B'Pi+At + Nt' are -S_k, the lower rows of Acl are -K, and dz is carried as dx (n x n) and the du before (m x n).
-// Pi+ Acl and Acl' (Pi+ Acl) are full nt x nt products (the closed loop has no zero block), computed by 2 x 2 blocks of the result in
-// a lane's registers: the one-entry-per-lane product of k_sens_face read every operand word from LDS once per product and made K0
-// of 4096 quadrotors at N = 50 cost 3.5 times k_sens_face on the S = 0 design; blocked it costs 1.8 times.
-//
-// Everything else is k_sens_face: the active-set rule, one wave per instance on its slice of LDS, SensTeam<false> fences, rows = -1
-// and zeros for an unsolved instance or a pivot that is not positive and finite, gains through a scratch [N][m nt] for dU and dX.
-// LDS, column-major: A, Q (n x n) | Pi+, T (= Pi+ Acl, then the symmetrised new Pi), Acl (nt x nt) | B (n x m) | Pi+ Bt, K, Rt K, S K
-// (nt x m or m x nt) | R, S, Lam (m x m) | lam, lam+ (nt) | the stage masks.  The new Pi is written over the old one, which has no
-// reader once Pi+ Acl is formed, and symmetrised into T; then the two change places -- no per-lane copy of a matrix, whatever nt.
-// The look-ahead gain of the forward pass is the only per-lane array: m nt <= 768 entries, 12 a lane.
+// ---- k_sens_face_rate (the description is in front of k_sens_face)
 constexpr int SENS_FACE_RATE_WAVES = 4;
 constexpr int SENS_FACE_RATE_MAX_M = 16, SENS_FACE_RATE_MAX_NT = 48;   // (the shapes the structured solve with S serves: n <= 32, m <= 16, n + m <= 48)
 
@@ -1073,11 +1191,10 @@ __global__ __launch_bounds__(64 * SENS_FACE_RATE_WAVES) void k_sens_face_rate(Se
     extern __shared__ __attribute__((aligned(16))) double sens_face_rate_smem[];
     static_assert((NC == 0) == (MC == 0), "both dimensions at compile time, or neither");
     static_assert(MC <= SENS_FACE_RATE_MAX_M && NC + MC <= SENS_FACE_RATE_MAX_NT, "a build beyond the served shapes");
-    constexpr int KREG = NC ? (MC * (NC + MC) + 63) / 64 : (SENS_FACE_RATE_MAX_M * SENS_FACE_RATE_MAX_NT + 63) / 64;
-    static_assert(64 * KREG >= (NC ? MC * (NC + MC) : SENS_FACE_RATE_MAX_M * SENS_FACE_RATE_MAX_NT), "the look-ahead gain does not fit its registers");
+    constexpr int KM_MAX = NC ? MC * (NC + MC) : SENS_FACE_RATE_MAX_M * SENS_FACE_RATE_MAX_NT;   // m nt at most: sizes the look-ahead gain
     const SensFaceParams& p = q.f;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int n = NC ? NC : p.n, m = MC ? MC : p.m, N = p.N, nt = n + m, nn = n * n, nm = n * m, mm = m * m, nz = N * m, tt = nt * nt, tm = nt * m;
+    const int n = NC ? NC : p.n, m = MC ? MC : p.m, N = p.N, nt = n + m, nn = n * n, nm = n * m, mm = m * m, tt = nt * nt, tm = nt * m;
     const SensTeam<false> T{lane, 64};
     double* L = sens_face_rate_smem + (size_t)wv * p.lds_per_wave;
     double* As = L;            double* Qs = As + nn;
@@ -1095,29 +1212,15 @@ __global__ __launch_bounds__(64 * SENS_FACE_RATE_WAVES) void k_sens_face_rate(Se
         bool ok = p.status[inst] == 0;
         int rows = 0;
         if (ok) {
-            const double* Ag = p.A + (size_t)inst * p.A_stride;
-            const double* Bg = p.B + (size_t)inst * p.B_stride;
             const double* Pg = p.P + (size_t)inst * p.P_stride;
-            for (int t = lane; t < nn; t += 64) { As[t] = Ag[t]; Qs[t] = p.Q[t]; }
+            sens_face_stage_in(p, inst, As, Qs, Bs, Rs, n, m, lane);
             for (int t = lane; t < tt; t += 64) {              // Pi+ = blkdiag(sym(P), 0)
                 const int i = t % nt, j = t / nt;
                 Pn[t] = (i < n && j < n) ? 0.5 * (Pg[i + j * n] + Pg[j + i * n]) : 0.0;
             }
-            for (int t = lane; t < nm; t += 64) Bs[t] = Bg[t];
-            for (int t = lane; t < mm; t += 64) { Rs[t] = p.R[t]; Ss[t] = 0.5 * (q.S[t] + q.S[(t % m) * m + t / m]); }
-            for (int k = lane; k < N; k += 64) wset[k] = 0u;
-            T.sync();
-            // the rows at a bound
-            for (int t = lane; t < nz; t += 64) {
-                const int k = t / m, a = t - k * m;
-                const double uj = p.u[(size_t)inst * nz + t], lo = p.umin[a], hi = p.umax[a], tol = p.tau * (hi - lo);
-                if (uj - lo <= tol || hi - uj <= tol) { atomicOr(&wset[k], 1u << a); ++rows; }
-            }
-            for (int o = 32; o > 0; o >>= 1) rows += __shfl_xor(rows, o);
-            if (VJP) {   // (0.0 is added where g_x is null, so that a null g_x and a g_x of zeros give the same bits)
-                const double* gx = p.g_x ? p.g_x + (size_t)inst * (N + 1) * n : nullptr;
-                for (int i = lane; i < nt; i += 64) lam[i] = i < n ? 0.0 + (gx ? gx[(size_t)N * n + i] : 0.0) : 0.0;
-            }
+            for (int t = lane; t < mm; t += 64) Ss[t] = 0.5 * (q.S[t] + q.S[(t % m) * m + t / m]);
+            rows = sens_face_active_set(T, p, inst, wset, m, N, lane);
+            if (VJP) sens_face_costate_end(p, inst, lam, n, nt, N, lane);
             T.sync();
         }
         // ---- backward sweep
@@ -1148,79 +1251,7 @@ __global__ __launch_bounds__(64 * SENS_FACE_RATE_WAVES) void k_sens_face_rate(Se
                 Lam[t] = (hi_ || hj) ? (i == j ? 1.0 : 0.0) : acc;
             }
             T.sync();
-            if constexpr (MC > 0 && MC <= 4) {
-                // m <= 4: every lane factors Lam in its own registers (the diagonal kept as its reciprocal), then takes a column of
-                // the right-hand side through both substitutions
-                double l[MC][MC];
-#pragma unroll
-                for (int i = 0; i < MC; ++i)
-#pragma unroll
-                    for (int j = 0; j <= i; ++j) l[i][j] = Lam[i + j * MC];
-#pragma unroll
-                for (int c = 0; c < MC; ++c) {
-                    const double piv = l[c][c];
-                    if (!(piv > 0.0 && piv <= 1.7976931348623157e308)) ok = false;
-                    const double inv = 1.0 / sqrt(piv);
-                    l[c][c] = inv;
-#pragma unroll
-                    for (int i = c + 1; i < MC; ++i) l[i][c] *= inv;
-#pragma unroll
-                    for (int j = c + 1; j < MC; ++j)
-#pragma unroll
-                        for (int i = j; i < MC; ++i) l[i][j] -= l[i][c] * l[j][c];
-                }
-                if (!ok) break;   // (every lane factored the same matrix)
-                for (int c = lane; c < nt; c += 64) {
-                    double x[MC];
-#pragma unroll
-                    for (int i = 0; i < MC; ++i) x[i] = Ks[i + c * MC];
-#pragma unroll
-                    for (int i = 0; i < MC; ++i) {
-#pragma unroll
-                        for (int j = 0; j < i; ++j) x[i] -= l[i][j] * x[j];
-                        x[i] *= l[i][i];
-                    }
-#pragma unroll
-                    for (int i = MC - 1; i >= 0; --i) {
-#pragma unroll
-                        for (int j = i + 1; j < MC; ++j) x[i] -= l[j][i] * x[j];
-                        x[i] *= l[i][i];
-                    }
-#pragma unroll
-                    for (int i = 0; i < MC; ++i) Ks[i + c * MC] = x[i];
-                }
-            } else {
-                // Lam = C C' in place (lower triangle)
-                for (int c = 0; c < m; ++c) {
-                    const double piv = Lam[c + c * m];         // (every lane reads the same word)
-                    if (!(piv > 0.0 && piv <= 1.7976931348623157e308)) { ok = false; break; }
-                    const double dk = sqrt(piv);
-                    T.sync();
-                    for (int i = c + lane; i < m; i += 64) Lam[i + c * m] = i == c ? dk : Lam[i + c * m] / dk;
-                    T.sync();
-                    const int rem = m - c - 1;
-                    for (int idx = lane; idx < rem * rem; idx += 64) {
-                        const int i = c + 1 + idx / rem, j = c + 1 + idx % rem;
-                        if (j <= i) Lam[i + j * m] -= Lam[i + c * m] * Lam[j + c * m];
-                    }
-                    T.sync();
-                }
-                if (!ok) break;
-                // K = Lam^-1 (Bt'Pi+At + Nt'): a lane takes a column through both substitutions
-                for (int c = lane; c < nt; c += 64) {
-                    double* x = Ks + c * m;
-                    for (int i = 0; i < m; ++i) {
-                        double s = x[i];
-                        for (int j = 0; j < i; ++j) s -= Lam[i + j * m] * x[j];
-                        x[i] = s / Lam[i + i * m];
-                    }
-                    for (int i = m - 1; i >= 0; --i) {
-                        double s = x[i];
-                        for (int j = i + 1; j < m; ++j) s -= Lam[j + i * m] * x[j];
-                        x[i] = s / Lam[i + i * m];
-                    }
-                }
-            }
+            if (!sens_face_gain_solve<MC>(T, Lam, Ks, m, nt, lane)) { ok = false; break; }   // K = Lam^-1 (Bt'Pi+At + Nt')
             T.sync();
             if (jac) {
                 double* Kg = p.Kst + ((size_t)inst * N + k) * tm;
@@ -1252,12 +1283,7 @@ __global__ __launch_bounds__(64 * SENS_FACE_RATE_WAVES) void k_sens_face_rate(Se
                 }
             T.sync();
             double ln = 0.0;
-            if (VJP && lane < nt) {                            // lam_k = [g_x[k]; 0] - K' g_u[k] + Acl' lam_{k+1}
-                const double* gu = p.g_u + (size_t)inst * nz + (size_t)k * m;
-                ln = (p.g_x && lane < n) ? p.g_x[((size_t)inst * (N + 1) + k) * n + lane] : 0.0;
-                for (int a = 0; a < m; ++a) ln -= Ks[a + lane * m] * gu[a];
-                for (int l = 0; l < nt; ++l) ln += Ac[l + lane * nt] * lam[l];
-            }
+            if (VJP) ln = sens_face_costate(p, inst, k, Ks, Ac, lam, n, nt, m, N, lane);
             if (k > 0) {
                 sens_face_mul22(Tm, Pn, Ac, nt, nt, nt, lane);        // Pi+ Acl
                 T.sync();
@@ -1291,88 +1317,13 @@ __global__ __launch_bounds__(64 * SENS_FACE_RATE_WAVES) void k_sens_face_rate(Se
             T.sync();
             if (VJP) { double* sw = lam; lam = lamn; lamn = sw; }
         }
-        if (!ok) {   // unsolved, or a pivot that is not positive and finite
-            if (VJP) {
-                for (int c = lane; c < n; c += 64) p.g_x0[(size_t)inst * n + c] = 0.0;
-            } else {
-                if (p.want & SENS_K0)
-                    for (int t = lane; t < nm; t += 64) p.K0[(size_t)inst * nm + t] = 0.0;
-                if (jac)
-                    for (int t = lane; t < n * nz; t += 64) p.dU[(size_t)inst * n * nz + t] = 0.0;
-                if (p.want & SENS_DX)
-                    for (int t = lane; t < (N + 1) * nn; t += 64) p.dX[(size_t)inst * (N + 1) * nn + t] = 0.0;
-            }
-            if (lane == 0) p.rows[inst] = -1;
-            continue;
-        }
+        if (!ok) { sens_face_unsolved<VJP>(p, inst, n, m, N, lane); continue; }
         if (lane == 0) p.rows[inst] = rows;
         if (VJP) {
             for (int c = lane; c < n; c += 64) p.g_x0[(size_t)inst * n + c] = lam[c];
             continue;
         }
-        if (!jac) continue;
-        // ---- forward pass: dx in Pn, dx+ in Tm (n x n each), du in PB and the du before in RK (m x n each).  The gains were stored by
-        // other lanes of this wave: made visible at device scope, read back past the L1 and one stage ahead
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __builtin_amdgcn_wave_barrier();
-        const double* Kg = p.Kst + (size_t)inst * N * tm;
-        double* dUo = p.dU + (size_t)inst * n * nz;
-        double* dXo = p.dX + (size_t)inst * (N + 1) * nn;
-        const bool wdx = (p.want & SENS_DX) != 0;
-        double kreg[KREG];
-        auto kload = [&](int k) {
-#pragma unroll
-            for (int c = 0; c < KREG; ++c) {
-                const int t = lane + 64 * c;
-                kreg[c] = t < tm ? __hip_atomic_load(Kg + (size_t)k * tm + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-            }
-        };
-        kload(0);
-        double* dx = Pn;
-        double* dxn = Tm;
-        double* du = PB;
-        double* dup = RK;
-        for (int t = lane; t < nn; t += 64) {
-            const int i = t % n, c = t / n;
-            const double v = i == c ? 1.0 : 0.0;
-            dx[t] = v;
-            if (wdx) dXo[(size_t)c * (N + 1) * n + i] = v;
-        }
-        T.sync();
-        for (int k = 0; k < N; ++k) {
-#pragma unroll
-            for (int c = 0; c < KREG; ++c) {
-                const int t = lane + 64 * c;
-                if (t < tm) Ks[t] = kreg[c];
-            }
-            if (k + 1 < N) kload(k + 1);
-            T.sync();
-            for (int t = lane; t < nm; t += 64) {              // du = -K dz = -K_x dx - K_w du-  (dz_0 = [I; 0]: the bits of K0)
-                const int a = t % m, c = t / m;
-                double s = 0.0;
-                if (k == 0) s -= Ks[t];
-                else {
-                    for (int j = 0; j < n; ++j) s -= Ks[a + j * m] * dx[j + c * n];
-                    for (int b = 0; b < m; ++b) s -= Ks[a + (n + b) * m] * dup[b + c * m];
-                }
-                du[t] = s;
-                dUo[(size_t)c * nz + (size_t)k * m + a] = s;
-            }
-            T.sync();
-            if (k + 1 < N || wdx) {
-                for (int t = lane; t < nn; t += 64) {          // dx+ = A dx + B du
-                    const int i = t % n, c = t / n;
-                    double s = 0.0;
-                    for (int j = 0; j < n; ++j) s += As[i + j * n] * dx[j + c * n];
-                    for (int a = 0; a < m; ++a) s += Bs[i + a * n] * du[a + c * m];
-                    dxn[t] = s;
-                    if (wdx) dXo[((size_t)c * (N + 1) + k + 1) * n + i] = s;
-                }
-                T.sync();
-                double* sw = dx; dx = dxn; dxn = sw;
-            }
-            { double* sw = du; du = dup; dup = sw; }
-        }
+        if (jac) sens_face_forward_rate<KM_MAX>(T, p, inst, As, Bs, Ks, Pn, Tm, PB, RK, n, m, N, lane);   // (dx, dx+ are n x n in Pi+, T)
     }
 }
 

@@ -13,41 +13,15 @@ import numpy as np
 import pytest
 
 import sens_face_cases as fc
+import sens_face_gpu as fg
 import sens_face_ref as fr
 import sens_ref as sr
+from sens_face_gpu import ERR_INVALID, ERR_UNSUPPORTED, K_SENS_RTOL, flat
 
 pytestmark = pytest.mark.gpu
 
-ERR_INVALID, ERR_UNSUPPORTED = -1, -4
-K_SENS_RTOL = 1e-8   # k_sens's tolerance (tests/test_gpu_sensitivity.py)
-
-
-def design(s, name):
-    ps, X0, shared = fc.case(name)
-    if shared:
-        p = ps
-        s.design_shared(p.A, p.B, p.Q, p.R, p.S, p.P, p.u_min, p.u_max)
-    else:
-        p = ps[0]
-        s.design_batched(np.stack([q.A for q in ps]), np.stack([q.B for q in ps]), p.Q, p.R, None, np.stack([q.P for q in ps]), p.u_min, p.u_max)
-    s.set_reference(p.x_ref, p.u_ref)
-    return p
-
-
-def solve(capi, name, opts=None, make=None, structured=True):
-    ps, X0, shared = fc.case(name)
-    p = ps if shared else ps[0]
-    s = make() if make else capi.Solver(p.n, p.m, p.N, X0.shape[0], structured=structured)
-    design(s, name)
-    s.update_initialization(X0)
-    s.calculate(opts)
-    return s
-
-
-def flat(dU):
-    """J (nz, n) stage-major from a Julia-shaped dU (m, N, n)"""
-    m, N, n = dU.shape
-    return dU.transpose(1, 0, 2).reshape(N * m, n)
+solve = functools.partial(fg.solve, cases=fc, batched_S=False)
+_refused = functools.partial(fg.refused, jac="sensitivity_stagewise", vjp="sensitivity_stagewise_vjp")
 
 
 @functools.lru_cache(maxsize=None)
@@ -166,7 +140,12 @@ def test_first_move_gain_against_differences_of_the_device_solution(capi, name, 
 def test_unsolved_instances_get_minus_one_and_zeros(capi, monkeypatch):
     """k_sdual hands what its cap leaves undecided to k_riccati, which has its own: on such a handle no polish_max_iter produces an
     unsolved instance.  Under ALMPC_STRUCTURED_PRIMAL k_riccati is the only solver and the cap is its own: at 8 working-set changes
-    it leaves part of the quadrotor batch unsolved."""
+    it leaves part of the quadrotor batch unsolved.
+
+    The zeros and rows = -1 are written by sens_face_unsolved (csrc/almpc_sens.hip.h), the one epilogue of k_sens_face and
+    k_sens_face_rate, so this test is also the test of the rate kernel's failure path.  It has no twin on a design with S: under
+    ALMPC_STRUCTURED_PRIMAL the design of a structured handle refuses an input-rate weight ("state rows / input-rate weight need
+    the stage-wise dual solve": setup_structured_solvers, csrc/almpc_api.hip), so these means leave no unsolved instance there."""
     name = "quad-30"
     monkeypatch.setenv("ALMPC_STRUCTURED_PRIMAL", "1")
     full = solve(capi, name)
@@ -192,14 +171,6 @@ def test_unsolved_instances_get_minus_one_and_zeros(capi, monkeypatch):
         for k in ("K0", "dU", "dX", "g_x0", "rows", "vrows"):
             assert np.ascontiguousarray(a[k][i]).tobytes() == np.ascontiguousarray(b[k][i]).tobytes(), (i, k)
     print(f"{bad.size} unsolved of {b['status'].size}")
-
-
-def _refused(capi, s, code=ERR_UNSUPPORTED):
-    for call in (lambda: s.sensitivity_stagewise(("K0",)), lambda: s.sensitivity_stagewise_vjp(np.zeros((s.batch, s.m, s.N)))):
-        with pytest.raises(capi.AlmpcError) as e:
-            call()
-        assert e.value.code == code, e.value
-        assert (s.L.almpc_last_error(s.h) or b"").decode().strip()
 
 
 def test_refusals(capi, mo):

@@ -14,46 +14,16 @@ import numpy as np
 import pytest
 
 import sens_face_cases as fc0
+import sens_face_gpu as fg
 import sens_face_rate_cases as fc
 import sens_face_rate_ref as fr
 import sens_ref as sr
+from sens_face_gpu import ERR_INVALID, ERR_UNSUPPORTED, K_SENS_RTOL, flat, same
 
 pytestmark = pytest.mark.gpu
 
-ERR_INVALID, ERR_UNSUPPORTED = -1, -4
-K_SENS_RTOL = 1e-8   # k_sens's tolerance (tests/test_gpu_sensitivity.py)
-
-
-def design(s, name, cases=fc):
-    ps, X0, shared = cases.case(name)
-    if shared:
-        p = ps
-        s.design_shared(p.A, p.B, p.Q, p.R, p.S, p.P, p.u_min, p.u_max)
-    else:
-        p = ps[0]
-        s.design_batched(np.stack([q.A for q in ps]), np.stack([q.B for q in ps]), p.Q, p.R, p.S, np.stack([q.P for q in ps]), p.u_min, p.u_max)
-    s.set_reference(p.x_ref, p.u_ref)
-    return p
-
-
-def solve(capi, name, opts=None, make=None, structured=True, cases=fc):
-    ps, X0, shared = cases.case(name)
-    p = ps if shared else ps[0]
-    s = make() if make else capi.Solver(p.n, p.m, p.N, X0.shape[0], structured=structured)
-    design(s, name, cases)
-    s.update_initialization(X0)
-    s.calculate(opts)
-    return s
-
-
-def flat(dU):
-    """J (nz, n) stage-major from a Julia-shaped dU (m, N, n)"""
-    m, N, n = dU.shape
-    return dU.transpose(1, 0, 2).reshape(N * m, n)
-
-
-def same(a, b):
-    return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+solve = functools.partial(fg.solve, cases=fc, batched_S=True)   # (cases=fc0 at a call: a case of the S = 0 table)
+_refused = functools.partial(fg.refused, jac="sensitivity_stagewise_rate", vjp="sensitivity_stagewise_rate_vjp")
 
 
 @functools.lru_cache(maxsize=None)
@@ -228,14 +198,6 @@ def test_a_call_disturbs_nothing_and_a_group_equals_one_handle(capi):
     assert sens["rows"].max() > 0
     for k in ("K0", "dU", "dX", "g_x0", "rows", "vrows"):
         assert same(sens[k], gs[k]), k
-
-
-def _refused(capi, s, code=ERR_UNSUPPORTED):
-    for call in (lambda: s.sensitivity_stagewise_rate(("K0",)), lambda: s.sensitivity_stagewise_rate_vjp(np.zeros((s.batch, s.m, s.N)))):
-        with pytest.raises(capi.AlmpcError) as e:
-            call()
-        assert e.value.code == code, e.value
-        assert (s.L.almpc_last_error(s.h) or b"").decode().strip()
 
 
 def test_refusals(capi, mo):
