@@ -180,6 +180,14 @@ def load():
                 "almpc_group_sensitivity", "almpc_group_get_sensitivity", "almpc_group_sensitivity_vjp",
                 "almpc_sensitivity_rows", "almpc_sensitivity_rows_vjp", "almpc_group_sensitivity_rows", "almpc_group_sensitivity_rows_vjp"):
         getattr(L, nm_).restype = ctypes.c_int
+    L.almpc_certificate.argtypes = [_hp, ctypes.c_uint32]
+    L.almpc_get_certificate.argtypes = [_hp, _dp, _dp, _dp, _dp]
+    L.almpc_device_certificate.argtypes = [_hp] + [ctypes.POINTER(ctypes.c_void_p)] * 4
+    L.almpc_group_certificate.argtypes = [_hp, ctypes.c_uint32]
+    L.almpc_group_get_certificate.argtypes = [_hp, _dp, _dp, _dp, _dp]
+    for nm_ in ("almpc_certificate", "almpc_get_certificate", "almpc_device_certificate", "almpc_group_certificate",
+                "almpc_group_get_certificate"):
+        getattr(L, nm_).restype = ctypes.c_int
     L.almpc_set_structured_fallback.argtypes = [_hp, ctypes.c_int]
     L.almpc_relin_fnn_setup.argtypes = [_hp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_dp] * 12 + [ctypes.c_double, ctypes.c_double]
     L.almpc_relin_fnn_setup.restype = ctypes.c_int
@@ -281,6 +289,8 @@ OPT_HBM_HANDOFF = 0x4  # almpc.h: ALMPC_OPT_HBM_HANDOFF (opts.reserved[0]): A/B 
 WANT = {"x": 0x01, "e_x": 0x02, "u": 0x04, "e_u": 0x08, "status": 0x10, "iters": 0x20, "polish_iters": 0x40, "u0": 0x80}
 # almpc.h: ALMPC_SENS_* (almpc_sensitivity)
 SENS = {"K0": 0x1, "dU": 0x2, "dX": 0x4}
+# almpc.h: ALMPC_CERT_* (almpc_certificate)
+CERT = {"cost": 0x1, "res": 0x2, "grad": 0x4, "costate": 0x8}
 
 
 def _weighted_design_args(n, m, b, A_batch, B_batch, Q_batch, R_batch, S_batch, P, umin, umax):
@@ -327,6 +337,47 @@ def _sens_read(get, handle, check, want, b, n, m, N):
     if dU is not None: out["dU"] = dU.transpose(0, 3, 2, 1)
     if dX is not None: out["dX"] = dX.transpose(0, 3, 2, 1)
     return out
+
+
+def _cert_mask(want):
+    mask = 0
+    for k in ((want,) if isinstance(want, str) else want):
+        if k not in CERT:
+            raise ValueError(f"unknown certificate quantity {k!r} (one of {sorted(CERT)})")
+        mask |= CERT[k]
+    if not mask:
+        raise ValueError("certificate: nothing asked for")
+    return mask
+
+
+def _cert_read(get, handle, check, want, b, n, m, N):
+    """What the last certificate call computed, shaped as get_results shapes u and x: cost (batch,), res (batch,),
+    grad (batch, m, N), costate (batch, n, N+1)."""
+    mask = _cert_mask(want)
+    cost = np.empty(b) if mask & CERT["cost"] else None
+    res = np.empty(b) if mask & CERT["res"] else None
+    grad = np.empty((b, N, m)) if mask & CERT["grad"] else None
+    costate = np.empty((b, N + 1, n)) if mask & CERT["costate"] else None
+    check(get(handle, _ptr(cost), _ptr(res), _ptr(grad), _ptr(costate)))
+    out = {}
+    if cost is not None: out["cost"] = cost
+    if res is not None: out["res"] = res
+    if grad is not None: out["grad"] = grad.transpose(0, 2, 1)
+    if costate is not None: out["costate"] = costate.transpose(0, 2, 1)
+    return out
+
+
+def multipliers(grad, u, umin, umax, act_tol=1e-9):
+    """Multipliers of the input box from a certificate's grad and the step's u, both (batch, m, N): mu = -grad at the inputs that sit
+    at a bound, zero elsewhere, in the OSQP sign convention (positive at umax, negative at umin).  An input is at a bound when it is
+    within act_tol * (umax - umin) of it.  Host side: the device applies no activity tolerance."""
+    grad = np.asarray(grad, dtype=np.float64)
+    u = np.asarray(u, dtype=np.float64)
+    lo = np.asarray(umin, dtype=np.float64).reshape(1, -1, 1)
+    hi = np.asarray(umax, dtype=np.float64).reshape(1, -1, 1)
+    tol = float(act_tol) * (hi - lo)
+    active = (u - lo <= tol) | (hi - u <= tol)
+    return np.where(active, -grad, 0.0)
 
 
 def _sens_vjp(call, handle, check, g_u, g_x, act_tol, b, n, m, N):
@@ -1089,6 +1140,19 @@ class Solver:
         self._check(self.L.almpc_device_sensitivity(self.h, *[ctypes.byref(p) for p in ps]))
         return dict(zip(("K0", "dU", "dX", "rows"), [p.value for p in ps]))
 
+    # ---- certificate of the last step (include/almpc.h "Certificate of the last step")
+    def certificate(self, want=("cost", "res", "grad", "costate")) -> dict:
+        """almpc_certificate + almpc_get_certificate: cost (batch,) the objective value, res (batch,) the KKT residual of the returned
+        inputs, grad (batch, m, N) the gradient of the objective in the inputs, costate (batch, n, N+1) (costate[:, :, 0] = dJ/dx0).
+        From the returned trajectories alone: every instance is certified whatever its status."""
+        self._check(self.L.almpc_certificate(self.h, _cert_mask(want)))
+        return _cert_read(self.L.almpc_get_certificate, self.h, self._check, want, self.batch, self.n, self.m, self.N)
+
+    def device_certificate(self):
+        ps = [ctypes.c_void_p() for _ in range(4)]
+        self._check(self.L.almpc_device_certificate(self.h, *[ctypes.byref(p) for p in ps]))
+        return dict(zip(("cost", "res", "grad", "costate"), [p.value for p in ps]))
+
     def sensitivity_vjp(self, g_u, g_x=None, act_tol=0.0):
         """dL/dx0 (batch, n) for a loss with gradients g_u (batch, m, N) and g_x (batch, n, N+1) or None on the returned
         trajectories (almpc_sensitivity_vjp: no Jacobian is formed); also returns rows (batch,)."""
@@ -1488,6 +1552,11 @@ class Group:
         """Solver.sensitivity for the whole batch (almpc_group_sensitivity + almpc_group_get_sensitivity)."""
         self._check(self.L.almpc_group_sensitivity(self.g, _sens_mask(want), float(act_tol)))
         return _sens_read(self.L.almpc_group_get_sensitivity, self.g, self._check, want, self.batch, self.n, self.m, self.N)
+
+    def certificate(self, want=("cost", "res", "grad", "costate")) -> dict:
+        """Solver.certificate for the whole batch (almpc_group_certificate + almpc_group_get_certificate)."""
+        self._check(self.L.almpc_group_certificate(self.g, _cert_mask(want)))
+        return _cert_read(self.L.almpc_group_get_certificate, self.g, self._check, want, self.batch, self.n, self.m, self.N)
 
     def sensitivity_vjp(self, g_u, g_x=None, act_tol=0.0):
         """Solver.sensitivity_vjp for the whole batch (almpc_group_sensitivity_vjp)."""

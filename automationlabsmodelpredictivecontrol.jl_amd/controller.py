@@ -37,7 +37,7 @@ __all__ = [
     "TerminalIngredient", "ModelPredictiveControlTuning", "ModelPredictiveControlResults",
     "ModelPredictiveControlController", "proceed_controller", "_design_reference_mpc",
     "_model_predictive_control_design", "_create_weights_coefficients", "update_initialization", "calculate",
-    "_model_predictive_control_computation", "sensitivity", "sensitivity_params", "HipModeler", "shard_range",
+    "_model_predictive_control_computation", "sensitivity", "sensitivity_params", "certificate", "HipModeler", "shard_range",
 ]
 
 
@@ -588,6 +588,18 @@ def sensitivity(C: ModelPredictiveControlController, want=("K0",), act_tol: floa
         out = mod.solver.sensitivity_rows(want, act_tol, act_tol_x)
     else:
         out = mod.solver.sensitivity(want, act_tol)
+    return {k: (v[0] if mod.batch == 1 else v) for k, v in out.items()}
+
+
+def certificate(C: ModelPredictiveControlController, want=("cost", "res", "grad", "costate")) -> dict:
+    """Certificate of the last calculate!(C) (beside `sensitivity`, an extension of this build): {"cost": the objective value JuMP
+    would report, "res": the KKT residual of the returned inputs (0 at an optimum, whatever the solver's own status says), "grad":
+    the gradient of the objective in the inputs (m, N), "costate": (n, N+1), whose first column is d cost / d x0} for what `want`
+    names, with a leading batch axis when the controller has more than one instance.  The multipliers of the input box are
+    _capi.multipliers(grad, u, umin, umax).  Linear controllers; with mpc_state_constraint or the terminal equality only "cost"
+    is served (Solver.certificate says what is refused)."""
+    mod: HipModeler = C.tuning.modeler
+    out = mod.solver.certificate(want)
     return {k: (v[0] if mod.batch == 1 else v) for k, v in out.items()}
 
 

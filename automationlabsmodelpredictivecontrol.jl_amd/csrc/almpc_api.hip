@@ -17,6 +17,7 @@
 #include "almpc_dare_vjp.hip.h"
 #include "almpc_c2d.hip.h"
 #include "almpc_sens.hip.h"
+#include "almpc_cert.hip.h"
 #include "almpc_host_math.h"
 #include "almpc_switches.h"
 #include "almpc_devbuf.h"
@@ -39,6 +40,7 @@
 #include "instances/dare.inc"
 #include "instances/c2d.inc"
 #include "instances/sens.inc"
+#include "instances/cert.inc"
 #undef ALMPC_KERNEL_INSTANCE
 #endif
 
@@ -265,6 +267,15 @@ struct almpc_handle {
         DevBuf<double> S;               // [m*m] the design's input-rate weight for k_sens_face_rate (h->hS; shared on every structured design)
         bool s_ok = false;              // ... of the current design
     } sens;
+    // Certificate of the last step (almpc_certificate; k_cert, csrc/almpc_cert.hip.h): cost, KKT residual, input gradient, costates.
+    // As with sens, every buffer is made at the first call that needs it.
+    struct Cert {
+        DevBuf<double> cost, res, grad, costate;   // [batch], [batch], [batch][N][m], [batch][N+1][n] of the last almpc_certificate
+        uint32_t have = 0;                         // ALMPC_CERT_* bits the buffers hold for the LAST step (0: none)
+        DevBuf<double> W;                          // [Q n*n | R m*m | S m*m | P n*n] shared weights of a condensed design, from the host copies
+        bool w_ok = false;                         // ... of the current design
+        int useR = 0;                              // R[1,1] != 0 as the last riccati_weights() took it: a structured design's branch (the condensed ones keep sens.useR)
+    } cert;
     // stage-wise dual active-set solve (k_sdual, csrc/almpc_sdual.hip.h): input box, state box, terminal equality and S in the
     // multiple-shooting form; stage records of the unconstrained problem (shared: host Riccati at design time)
     struct Sd {
@@ -495,6 +506,7 @@ int riccati_weights(almpc_handle* h, const hm::mat& Qm, const hm::mat& Rm, const
     const int n = h->n, m = h->m;
     hm::mat Qs = hm::symmetrised(Qm.data(), n), Rs = hm::symmetrised(Rm.data(), m);
     if (Rm[0] == 0.0) std::fill(Rs.begin(), Rs.end(), 0.0);
+    h->cert.useR = Rm[0] != 0.0;
     HIP_TRY(h, h->rQ.once((size_t)n * n));
     HIP_TRY(h, h->rR.once((size_t)m * m));
     HIP_TRY(h, hipMemcpy(h->rQ, Qs.data(), Qs.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -1222,6 +1234,7 @@ int wait_and_settle(almpc_handle* h, bool blocking_only = false) {
 // A new design voids a redo that was deferred for a step of the previous one (its models, references and results are about to go)
 void drop_lazy_redo(almpc_handle* h) {
     h->sens.stepped = false; h->sens.v_ok = false; h->sens.t1_ok = false; h->sens.w_ok = false; h->sens.s_ok = false; h->sens.have = 0;   // (what a sensitivity call looks at goes with the design as well)
+    h->cert.have = 0; h->cert.w_ok = false;
     h->redo.lazy_pending = false;
     h->redo.expected = false;
     h->weighted = false;   // (almpc_design_batched_weighted sets it again behind this call)
@@ -2812,6 +2825,7 @@ int run_step(almpc_handle* h, const almpc_opts& o, StepMode mode) {
     if (rc != ALMPC_OK) return rc;
     h->state_valid = keep_state;   // (recorded only here: every launch of the step went out)
     h->sens.stepped = true; h->sens.have = 0;
+    h->cert.have = 0;
     if (h->io.x0_slot >= 0) {      // the x0 slot of an asynchronous update is free again once this step has finished
         HIP_TRY(h, hipEventRecord(h->io.ev_used[h->io.x0_slot], h->stream));
         h->io.used_pending[h->io.x0_slot] = true;
@@ -4842,9 +4856,132 @@ int sens_face_vjp(almpc_handle* h, const char* who, const double* g_u, const dou
     return ALMPC_OK;
 }
 
+// ---- certificate of the last step (k_cert): cost, KKT residual, input gradient, costates from the returned trajectories ----
+
+constexpr uint32_t CERT_ALL = ALMPC_CERT_COST | ALMPC_CERT_RES | ALMPC_CERT_GRAD | ALMPC_CERT_COSTATE;
+
+// What the call can look at: the last step of a time-invariant design.  With state rows the trajectory alone determines the cost only.
+int cert_check(almpc_handle* h, uint32_t want) {
+    if (!h) return ALMPC_ERR_INVALID;
+    if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, "certificate before design");
+    if (!want || (want & ~CERT_ALL)) return fail(h, ALMPC_ERR_INVALID, "certificate: want must be a mask of ALMPC_CERT_*");
+    if (h->ltv || h->sqp.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the QP of a time-varying or SQP design has a defect term and a trajectory of its own");
+    if (h->relin.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the re-linearisation pipeline's QP has a defect term and a trajectory of its own");
+    const bool state_rows = h->has_box || h->terminal_eq || h->mc > 0 || (h->sd.ready && (h->sd.has_box || h->sd.has_eq));
+    if (state_rows && (want & ~ALMPC_CERT_COST))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: with state rows (state box, terminal equality) their multipliers enter the costates, and the trajectory does not determine them: ALMPC_CERT_COST alone is served");
+    if (h->n > CERT_MAX_N || h->m > CERT_MAX_M || (size_t)cert_lds_doubles(h->n, h->m) * sizeof(double) > (size_t)LDS_BUDGET)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: needs n <= 64, m <= 16 and the operands of an instance in 160 KB of LDS");
+    if (h->structured) {
+        // (a guard: almpc_create gives a structured handle only to the primal stage-wise solver's shapes, and every design of one
+        // leaves that solver's weights on the device -- riccati_weights)
+        if (!h->rQ || !h->rR || !(h->r_batched_P ? h->bP.get() : h->rP.get()))
+            return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the shape is outside the primal stage-wise solver, whose weights the kernel reads (n <= 32, m <= 16, m N <= 1024)");
+        if (h->hS.size() != (size_t)h->m * h->m) return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the design's input-rate weight is not kept");
+    } else if (h->weighted) {
+        if (!h->wiQ || !h->wiR || (h->useS && !(h->wiS_given && h->wiS))) return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the design's per-instance weights are not kept");
+    } else if (h->sens.Q.size() != (size_t)h->n * h->n || h->sens.R.size() != (size_t)h->m * h->m || h->hS.size() != (size_t)h->m * h->m ||
+               (!h->batched && h->P.size() != (size_t)h->n * h->n)) {
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the design's weights are not kept");
+    }
+    if (!h->sens.stepped) return fail(h, ALMPC_ERR_INVALID, "certificate: no step has run on this design");
+    return ALMPC_OK;
+}
+
+// Operands of the launch.  Models and per-instance weights are on the device already; the shared weights of a design go there once
+// per design, from the host copies the designs keep (in stream order in front of the kernel).
+int cert_params(almpc_handle* h, CertParams& p) {
+    p = CertParams();
+    const size_t n = (size_t)h->n, m = (size_t)h->m, nn = n * n, mm = m * m;
+    p.n = h->n; p.m = h->m; p.N = h->N; p.batch = h->batch;
+    p.A = h->batched ? h->bA : h->dA; p.A_stride = h->batched ? (long)nn : 0;
+    p.B = h->batched ? h->bB : h->dB; p.B_stride = h->batched ? (long)(n * m) : 0;
+    p.useS = h->useS;
+    if (h->structured) {
+        p.useR = h->cert.useR;
+        p.Q = h->rQ; p.R = h->rR;
+        p.P = h->r_batched_P ? h->bP : h->rP; p.P_stride = h->r_batched_P ? h->rP_stride : 0;
+    } else {
+        p.useR = h->sens.useR;
+        if (h->weighted) { p.Q = h->wiQ; p.Q_stride = (long)nn; p.R = h->wiR; p.R_stride = (long)mm; p.S = h->wiS; p.S_stride = (long)mm; }
+        if (h->batched) { p.P = h->bP; p.P_stride = h->bP_stride; }
+    }
+    const bool up_qr = !h->structured && !h->weighted, up_s = p.useS && !h->weighted, up_p = !h->structured && !h->batched;
+    if ((up_qr || up_s || up_p) && !h->cert.w_ok) {
+        HIP_TRY(h, h->cert.W.grow(2 * nn + 2 * mm));
+        if (up_qr) {
+            HIP_TRY(h, hipMemcpyAsync(h->cert.W, h->sens.Q.data(), nn * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(h->cert.W + nn, h->sens.R.data(), mm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        }
+        if (up_s) HIP_TRY(h, hipMemcpyAsync(h->cert.W + nn + mm, h->hS.data(), mm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        if (up_p) HIP_TRY(h, hipMemcpyAsync(h->cert.W + nn + 2 * mm, h->P.data(), nn * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        h->cert.w_ok = true;
+    }
+    if (up_qr) { p.Q = h->cert.W; p.R = h->cert.W + nn; }
+    if (up_s) p.S = h->cert.W + nn + mm;
+    if (up_p) p.P = h->cert.W + nn + 2 * mm;
+    p.umin = h->dUmin; p.umax = h->dUmax;
+    p.ex = h->dEx; p.eu = h->dEu; p.u = h->dU;
+    p.lds_per_wave = cert_lds_doubles(h->n, h->m);
+    return ALMPC_OK;
+}
+
+int cert_launch(almpc_handle* h, const CertParams& p) {
+    const size_t per_wave = (size_t)p.lds_per_wave * sizeof(double);
+    const int waves = waves_in_lds(per_wave, CERT_WAVES), wgs = capped_grid(h->batch, waves, 16 * h->num_cus);
+    if (h->n <= 16) HIP_TRY(h, LAUNCH_WAVES((k_cert<16>), wgs, waves, waves * per_wave, h->stream, p));
+    else if (h->n <= 32) HIP_TRY(h, LAUNCH_WAVES((k_cert<32>), wgs, waves, waves * per_wave, h->stream, p));
+    else HIP_TRY(h, LAUNCH_WAVES((k_cert<64>), wgs, waves, waves * per_wave, h->stream, p));
+    return ALMPC_OK;
+}
+
+int certificate(almpc_handle* h, uint32_t want) {
+    ALMPC_TRY(cert_check(h, want));
+    HIP_TRY(h, hipSetDevice(h->device));
+    ALMPC_TRY(wait_and_settle(h));   // (a synchronous look: the certificate is of the results a caller would read, redone instances included)
+    const size_t b = (size_t)h->batch;
+    h->cert.have = 0;
+    CertParams p;
+    ALMPC_TRY(cert_params(h, p));
+    if (want & ALMPC_CERT_COST) { HIP_TRY(h, h->cert.cost.grow(b)); p.cost = h->cert.cost; }
+    if (want & ALMPC_CERT_RES) { HIP_TRY(h, h->cert.res.grow(b)); p.res = h->cert.res; }
+    if (want & ALMPC_CERT_GRAD) { HIP_TRY(h, h->cert.grad.grow(b * h->nz)); p.grad = h->cert.grad; }
+    if (want & ALMPC_CERT_COSTATE) { HIP_TRY(h, h->cert.costate.grow(b * (size_t)h->n * (h->N + 1))); p.costate = h->cert.costate; }
+    ALMPC_TRY(cert_launch(h, p));
+    HIP_TRY(h, stream_wait_polling(h));
+    h->cert.have = want;
+    return ALMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int almpc_certificate(almpc_handle* h, uint32_t want) { return certificate(h, want); }
+
+int almpc_get_certificate(almpc_handle* h, double* cost, double* res, double* grad, double* costate) {
+    if (!h) return ALMPC_ERR_INVALID;
+    const uint32_t need = (cost ? ALMPC_CERT_COST : 0u) | (res ? ALMPC_CERT_RES : 0u) | (grad ? ALMPC_CERT_GRAD : 0u) | (costate ? ALMPC_CERT_COSTATE : 0u);
+    if (!h->cert.have || (need & ~h->cert.have))
+        return fail(h, ALMPC_ERR_INVALID, "get_certificate: not computed for the last step (almpc_certificate with these ALMPC_CERT_* bits first)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t b = (size_t)h->batch;
+    if (cost) HIP_TRY(h, hipMemcpy(cost, h->cert.cost, b * sizeof(double), hipMemcpyDeviceToHost));
+    if (res) HIP_TRY(h, hipMemcpy(res, h->cert.res, b * sizeof(double), hipMemcpyDeviceToHost));
+    if (grad) HIP_TRY(h, hipMemcpy(grad, h->cert.grad, b * h->nz * sizeof(double), hipMemcpyDeviceToHost));
+    if (costate) HIP_TRY(h, hipMemcpy(costate, h->cert.costate, b * (size_t)h->n * (h->N + 1) * sizeof(double), hipMemcpyDeviceToHost));
+    return ALMPC_OK;
+}
+
+int almpc_device_certificate(almpc_handle* h, const double** d_cost, const double** d_res, const double** d_grad, const double** d_costate) {
+    if (!h) return ALMPC_ERR_INVALID;
+    if (!h->cert.have) return fail(h, ALMPC_ERR_INVALID, "device_certificate: not computed for the last step");
+    if (d_cost) *d_cost = (h->cert.have & ALMPC_CERT_COST) ? h->cert.cost.get() : nullptr;
+    if (d_res) *d_res = (h->cert.have & ALMPC_CERT_RES) ? h->cert.res.get() : nullptr;
+    if (d_grad) *d_grad = (h->cert.have & ALMPC_CERT_GRAD) ? h->cert.grad.get() : nullptr;
+    if (d_costate) *d_costate = (h->cert.have & ALMPC_CERT_COSTATE) ? h->cert.costate.get() : nullptr;
+    return ALMPC_OK;
+}
 
 int almpc_sensitivity(almpc_handle* h, uint32_t want, double act_tol) {
     return sens_jacobians(h, "sensitivity", false, want, act_tol, 0.0);

@@ -720,6 +720,22 @@ int almpc_group_sensitivity_params_vjp_dare(almpc_group* g, const double* g_u, c
                                             int32_t* dare_status) {
     return group_sens_params_vjp(g, g_u, g_x, act_tol, out, true, dare_status);
 }
+// ... and the certificate of the last step (almpc_certificate, almpc_get_certificate): every output is per instance, cut along the shards
+int almpc_group_certificate(almpc_group* g, uint32_t want) {
+    if (!g) return ALMPC_ERR_INVALID;
+    return group_fanout(g, [&](int i) { return almpc_certificate(g->hs[i], want); });
+}
+int almpc_group_get_certificate(almpc_group* g, double* cost, double* res, double* grad, double* costate) {
+    if (!g) return ALMPC_ERR_INVALID;
+    const size_t n = (size_t)g->n, nz = (size_t)g->m * g->N;
+    for (size_t i = 0; i < g->hs.size(); ++i) {
+        const size_t f = (size_t)g->first[i];
+        const int rc = almpc_get_certificate(g->hs[i], cost ? cost + f : nullptr, res ? res + f : nullptr, grad ? grad + f * nz : nullptr,
+                                             costate ? costate + f * n * (g->N + 1) : nullptr);
+        if (rc != ALMPC_OK) return gfail(g, rc, (int)i);
+    }
+    return ALMPC_OK;
+}
 
 // Asynchronous read-back of the whole batch: the request goes to every device (pack kernels / copy streams), the ticket is the group's;
 // almpc_group_get_results_wait gathers into the caller's arrays (layouts of almpc_group_get_results).  The last two tickets are kept.

@@ -792,6 +792,48 @@ int almpc_group_sensitivity_stagewise_rate(almpc_group* g, uint32_t want, double
 int almpc_group_sensitivity_stagewise_rate_vjp(almpc_group* g, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows);
 
 /*
+ * Certificate of the last step (k_cert, DESIGN.md "k_cert"): the objective value, the costates, the gradient of the objective in the
+ * inputs and a KKT residual, from the returned trajectories and the design data alone -- no solver internals, so the same kernel and
+ * the same numbers serve condensed, per-instance, weighted and structured handles, and an instance is certified whatever its status
+ * (an ALMPC_MAX_ITER instance gets the residual of the inputs it returned).  Per instance, stages 0-based, e_k = e_x[:,k],
+ * v_k = e_u[:,k], u_k = u[:,k]; Q, R, S, P symmetrised; useR = R[1,1] != 0 and useS = useR && S[1,1] != 0 as the design took them
+ * (src/sub/design_mpc.jl:436-465):
+ *     cost    J     = e_N'P e_N + sum_{k<N} (e_k'Q e_k + [useR] v_k'R v_k) + [useS] sum_{i<N-1} (u_i - u_{i+1})'S (u_i - u_{i+1})
+ *                     (the reference's objective: the constant e_0'Q e_0 included)
+ *     costate lam_N = 2 P e_N,  lam_k = 2 Q e_k + A'lam_{k+1};   lam_0 = dJ/dx0 at fixed inputs, = dJ* / dx0 at an optimum
+ *     grad    g_k   = B'lam_{k+1} + [useR] 2 R v_k + [useS]([k < N-1] 2 S (u_k - u_{k+1}) - [k > 0] 2 S (u_{k-1} - u_k))
+ *                     (stacked: H v + f of the condensed QP; no H is formed)
+ *     res           = max_{k,j} |u_k - clip(u_k - g_k, umin, umax)|       (0 at an optimum; the oracle's kkt_residual in unscaled u coordinates)
+ * res is as large as |g| at an input inside the box: it measures how far the GRADIENT is from the normal cone of the box, not how far u
+ * is from the optimum.  With stiff weights the two differ by many orders (quadrotor, Q = 100 I, N = 30: inputs within 5e-12 of the exact
+ * optimum have res up to 1e-2, entries of H being up to 1e9), so judge res against the size of g (res <= 1e-9 max(1, |g|_inf), say).
+ * The multipliers of the input box are -g at the inputs that sit at a bound (positive at umax); that mask is the caller's.
+ *   almpc_certificate         synchronous, settles first (a lazily redone instance is certified on its redone result); `want` is a mask
+ *                             of ALMPC_CERT_*; the results stay in buffers of the handle until the next step or design.
+ *   almpc_get_certificate     copies out what the last almpc_certificate computed (NULL: not wanted; a pointer whose bit was not
+ *                             asked for is ALMPC_ERR_INVALID).  Layouts: cost, res [batch]; grad [batch][N][m]; costate [batch][N+1][n].
+ *   almpc_device_certificate  the device addresses of the same buffers (NULL for a bit that was not computed).
+ * Served: almpc_design_shared, almpc_design_batched and almpc_design_batched_weighted on condensed handles, almpc_design_shared and
+ * almpc_design_batched on ALMPC_FLAG_STRUCTURED handles; n <= 64, m <= 16 (a structured handle exists only for n <= 32, m <= 16,
+ * m N <= 1024 -- almpc_create --, and the kernel reads the weights its designs leave for the primal stage-wise solver).
+ * ALMPC_ERR_NOT_DESIGNED before a design;
+ * ALMPC_ERR_INVALID before the design's first step, for want = 0 or unknown bits, and from the getters after a new step or design;
+ * ALMPC_ERR_UNSUPPORTED, with the reason in almpc_last_error: almpc_design_ltv, the SQP loop and the re-linearisation pipeline (their QP
+ * has a defect term and a trajectory of its own), and on designs with a state box or the terminal equality every bit but
+ * ALMPC_CERT_COST (the state-row multipliers enter the costates, and the trajectory alone does not determine them).
+ */
+#define ALMPC_CERT_COST 1u
+#define ALMPC_CERT_RES 2u
+#define ALMPC_CERT_GRAD 4u
+#define ALMPC_CERT_COSTATE 8u
+int almpc_certificate(almpc_handle* h, uint32_t want);
+int almpc_get_certificate(almpc_handle* h, double* cost /*[batch]*/, double* res /*[batch]*/, double* grad /*[batch][N][m]*/,
+                          double* costate /*[batch][N+1][n]*/);   /* NULL = not wanted */
+int almpc_device_certificate(almpc_handle* h, const double** d_cost, const double** d_res, const double** d_grad, const double** d_costate);
+int almpc_group_certificate(almpc_group* g, uint32_t want);
+int almpc_group_get_certificate(almpc_group* g, double* cost, double* res, double* grad, double* costate);
+
+/*
  * Parameter gradients of the returned solution: for the loss of almpc_sensitivity_vjp (g_u [batch][N][m], g_x [batch][N+1][n] or NULL),
  * its gradient in the problem data, per instance, on the face where the rows W (same rule, same act_tol) are held -- the backward
  * pass of a step for a caller who learns or tunes the controller (k_sens_pz, k_sens_params; DESIGN.md "k_sens_params").  Stages

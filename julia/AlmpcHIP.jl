@@ -23,7 +23,8 @@ export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_s
        sensitivity_rows, sensitivity_rows_vjp, group_sensitivity_rows, group_sensitivity_rows_vjp, sensitivity_params_vjp,
        group_sensitivity_params_vjp, dare_vjp, dare_vjp_batched, sensitivity_stagewise, sensitivity_stagewise_vjp,
        group_sensitivity_stagewise, group_sensitivity_stagewise_vjp, sensitivity_stagewise_rate, sensitivity_stagewise_rate_vjp,
-       group_sensitivity_stagewise_rate, group_sensitivity_stagewise_rate_vjp
+       group_sensitivity_stagewise_rate, group_sensitivity_stagewise_rate_vjp, certificate, certificate!, device_certificate,
+       group_certificate, group_certificate!
 
 const libalmpc = get(ENV, "ALMPC_LIB", "libalmpc.so")
 
@@ -810,6 +811,46 @@ function sensitivity_stagewise_rate_vjp(mod::HipModeler, g_u::Array{Float64}, g_
     return g_x0, rows
 end
 
+# ---- certificate of the last step (include/almpc.h "Certificate of the last step"): ALMPC_CERT_* bits
+cert_mask(cost, res, grad, costate) =
+    UInt32((cost === nothing ? 0 : 1) | (res === nothing ? 0 : 2) | (grad === nothing ? 0 : 4) | (costate === nothing ? 0 : 8))
+function check_cert_sizes(n, m, N, batch, cost, res, grad, costate)
+    for (name, a, len) in (("cost", cost, batch), ("res", res, batch), ("grad", grad, m * N * batch), ("costate", costate, n * (N + 1) * batch))
+        a === nothing || length(a) == len || throw(DimensionMismatch("$name holds $(length(a)) values, the solver writes $len"))
+    end
+    cert_mask(cost, res, grad, costate) != 0 || error("certificate: nothing asked for")
+end
+"""
+    certificate!(mod, cost, res, grad, costate)
+
+The certificate of the last `calculate!` into the caller's arrays (`almpc_certificate` + `almpc_get_certificate`); `nothing` = not
+wanted.  `cost` (batch): the objective value JuMP would report; `res` (batch): the KKT residual of the returned inputs, whatever the
+solver's own status says; `grad` (m x N x batch): the gradient of the objective in the inputs (its negative at an input that sits at a
+bound is that bound's multiplier, positive at `u_max`); `costate` (n x (N+1) x batch), whose first column is d cost / d x0.
+"""
+function certificate!(mod::HipModeler, cost::Union{Nothing,Array{Float64}}, res::Union{Nothing,Array{Float64}},
+                      grad::Union{Nothing,Array{Float64}}, costate::Union{Nothing,Array{Float64}})
+    check_cert_sizes(mod.n, mod.m, mod.N, mod.batch, cost, res, grad, costate)
+    check(mod.handle, ccall((:almpc_certificate, libalmpc), Cint, (Ptr{Cvoid}, UInt32), mod.handle, cert_mask(cost, res, grad, costate)))
+    pf(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve cost res grad costate check(mod.handle, ccall((:almpc_get_certificate, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), mod.handle, pf(cost), pf(res), pf(grad), pf(costate)))
+    return cost, res, grad, costate
+end
+"`certificate!` into fresh arrays: `certificate(mod; cost = true, res = true, grad = false, costate = false) -> (cost, res, grad, costate)`"
+function certificate(mod::HipModeler; cost::Bool = true, res::Bool = true, grad::Bool = false, costate::Bool = false)
+    return certificate!(mod, cost ? Vector{Float64}(undef, mod.batch) : nothing, res ? Vector{Float64}(undef, mod.batch) : nothing,
+                        grad ? Array{Float64,3}(undef, mod.m, mod.N, mod.batch) : nothing,
+                        costate ? Array{Float64,3}(undef, mod.n, mod.N + 1, mod.batch) : nothing)
+end
+"device pointers of the last certificate (`almpc_device_certificate`): `C_NULL` for what was not computed"
+function device_certificate(mod::HipModeler)
+    pc, pr, pg, pl = Ref{Ptr{Float64}}(C_NULL), Ref{Ptr{Float64}}(C_NULL), Ref{Ptr{Float64}}(C_NULL), Ref{Ptr{Float64}}(C_NULL)
+    check(mod.handle, ccall((:almpc_device_certificate, libalmpc), Cint,
+                            (Ptr{Cvoid}, Ref{Ptr{Float64}}, Ref{Ptr{Float64}}, Ref{Ptr{Float64}}, Ref{Ptr{Float64}}), mod.handle, pc, pr, pg, pl))
+    return pc[], pr[], pg[], pl[]
+end
+
 # almpc_param_grads (include/almpc.h): host pointers, C_NULL = not wanted
 struct ParamGrads
     x0::Ptr{Float64}; f::Ptr{Float64}; u_ref::Ptr{Float64}; u_min::Ptr{Float64}; u_max::Ptr{Float64}
@@ -1051,6 +1092,22 @@ function group_sensitivity_stagewise_rate_vjp(g::HipGroup, g_u::Array{Float64}, 
     GC.@preserve g_x gcheck(g.group, ccall((:almpc_group_sensitivity_stagewise_rate_vjp, libalmpc), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), g.group, g_u, px, act_tol, g_x0, rows))
     return g_x0, rows
+end
+"`certificate!` for the whole batch (`almpc_group_certificate` + `almpc_group_get_certificate`)"
+function group_certificate!(g::HipGroup, cost::Union{Nothing,Array{Float64}}, res::Union{Nothing,Array{Float64}},
+                            grad::Union{Nothing,Array{Float64}}, costate::Union{Nothing,Array{Float64}})
+    check_cert_sizes(g.n, g.m, g.N, g.batch, cost, res, grad, costate)
+    gcheck(g.group, ccall((:almpc_group_certificate, libalmpc), Cint, (Ptr{Cvoid}, UInt32), g.group, cert_mask(cost, res, grad, costate)))
+    pf(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve cost res grad costate gcheck(g.group, ccall((:almpc_group_get_certificate, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), g.group, pf(cost), pf(res), pf(grad), pf(costate)))
+    return cost, res, grad, costate
+end
+"`certificate` for the whole batch"
+function group_certificate(g::HipGroup; cost::Bool = true, res::Bool = true, grad::Bool = false, costate::Bool = false)
+    return group_certificate!(g, cost ? Vector{Float64}(undef, g.batch) : nothing, res ? Vector{Float64}(undef, g.batch) : nothing,
+                              grad ? Array{Float64,3}(undef, g.m, g.N, g.batch) : nothing,
+                              costate ? Array{Float64,3}(undef, g.n, g.N + 1, g.batch) : nothing)
 end
 "`sensitivity_params_vjp` for the whole batch (`almpc_group_sensitivity_params_vjp`, `almpc_group_sensitivity_params_vjp_dare`)"
 function group_sensitivity_params_vjp(g::HipGroup, g_u::Array{Float64}, g_x::Union{Nothing,Array{Float64}} = nothing;
