@@ -322,6 +322,11 @@ int almpc_get_gradient_instance(almpc_handle* h, int instance, double* q);
  *            An instance whose condensed Hessian is not positive definite to working precision (open-loop unstable
  *            linearisation over a long horizon) or whose QP solution is non-finite keeps its last good iterate; the call then
  *            returns ALMPC_ERR_NUMERIC after finishing all other instances; almpc_sqp_fnn_skipped tells which.
+ *            Shapes: setup checks the loop's own kernels (n <= 64, their LDS); the step behind every QP is the per-instance one of
+ *            almpc_design_batched / almpc_design_ltv, whose finish rolls the stages out with n + m <= 8 g lanes, g the largest power
+ *            of two with g n <= 64, and (N + 1)(n + m) <= 1024 -- n <= 16 in effect.  Beyond that the first iterate (as
+ *            almpc_calculate on those designs) returns ALMPC_ERR_UNSUPPORTED; the stage-wise route (almpc_sqp_fnn_set_structured) has
+ *            its own limits.
  */
 int almpc_sqp_fnn_setup(almpc_handle* h, int H, int L, int activation, const double* W_in, const double* W_h, const double* b_h,
                         const double* W_out, const double* xref, const double* uref, const double* Q, const double* R,

@@ -56,6 +56,26 @@ def stage_hessian(model, x, u, lam):
     return 0.5 * (Wz + Wz.T)
 
 
+def evaluate_points(model, X, U, dtype=np.longdouble):
+    """net_ref.evaluate_points for a DenseNet: (A (p, n, n), B (p, n, m), f (p, n)) at X (p, n), U (p, m), every operation in `dtype`."""
+    import net_ref
+    if type(model) is not DenseNetModel:
+        return net_ref.evaluate_points(model, X, U, dtype)
+    c = lambda w: np.asarray(w, dtype=dtype)
+    Z = np.concatenate([c(X), c(U)], axis=1)
+    W_in, W_out = c(model.W_in), c(model.W_out)
+    y = Z @ W_in.T
+    J = np.broadcast_to(W_in, (Z.shape[0],) + W_in.shape).copy()
+    for W, b in zip(model.W_h, model.b_h):
+        W, b = c(W), c(b)
+        v, d = net_ref.act_any(model.act, y @ W.T + b)
+        J = np.concatenate([np.einsum("ij,pjc->pic", W, J) * d[:, :, None], J], axis=1)
+        y = np.concatenate([v, y], axis=1)
+    Jo = np.einsum("ij,pjc->pic", W_out, J)
+    n = W_out.shape[0]
+    return Jo[:, :, :n], Jo[:, :, n:], y @ W_out.T
+
+
 def synthetic_densenet(n=4, m=2, H=16, L=2, seed=0x5EED0004, act="relu"):
     """Weights ~ U(-1, 1) / sqrt(fan_in) (biases 0.1 U(-1, 1)), W_out rescaled so that A at the origin has spectral radius 0.95, as
     net_ref.synthetic_net does."""

@@ -114,6 +114,48 @@ def stage_hessian(model, x, u, lam):
     return 0.5 * (Wz + Wz.T)
 
 
+def act_any(act, a):
+    """value and derivative of the activation in the array's own precision (FnnModel._act for any float type)"""
+    one = a.dtype.type(1)
+    if act == "relu":
+        return np.maximum(a, 0), (a > 0).astype(a.dtype)
+    if act == "tanh":
+        t = np.tanh(a)
+        return t, one - t * t
+    if act in ("sigmoid", "swish"):
+        s = one / (one + np.exp(-a))
+        return (s, s * (one - s)) if act == "sigmoid" else (a * s, s * (one + a * (one - s)))
+    if act == "identity":
+        return a, np.ones_like(a)
+    raise ValueError(act)
+
+
+def evaluate_points(model, X, U, dtype=np.longdouble):
+    """(A (p, n, n), B (p, n, m), f (p, n)) of an Fnn, ResNet or PolyNet at the points X (p, n), U (p, m), every operation in `dtype`:
+    numpy long double (the yardstick of the float64 restatement) or float64 (the restatement itself, over all points at once)."""
+    c = lambda w: np.asarray(w, dtype=dtype)
+    Z = np.concatenate([c(X), c(U)], axis=1)
+    W_in, W_out = c(model.W_in), c(model.W_out)
+    y = Z @ W_in.T
+    J = np.broadcast_to(W_in, (Z.shape[0],) + W_in.shape).copy()
+    for W, b in zip(model.W_h, model.b_h):
+        W, b = c(W), c(b)
+        v, d = act_any(model.act, y @ W.T + b)
+        WJ = np.einsum("ij,pjc->pic", W, J) * d[:, :, None]
+        if type(model) is ResNetModel:
+            J, y = J + WJ, y + v
+        elif type(model) is PolyNetModel:
+            v2, d2 = act_any(model.act, v @ W.T + b)
+            J, y = J + WJ + np.einsum("ij,pjc->pic", W, WJ) * d2[:, :, None], y + v + v2
+        elif type(model) is mo.FnnModel:
+            J, y = WJ, v
+        else:
+            raise TypeError(type(model))
+    Jo = np.einsum("ij,pjc->pic", W_out, J)
+    n = W_out.shape[0]
+    return Jo[:, :, :n], Jo[:, :, n:], y @ W_out.T
+
+
 def as_kind(f, kind):
     """The same weights as a model of another kind (no rescaling)."""
     return MODELS[kind](f.W_in.copy(), [w.copy() for w in f.W_h], [b.copy() for b in f.b_h], f.W_out.copy(), f.act)
