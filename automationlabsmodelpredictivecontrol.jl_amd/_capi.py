@@ -188,6 +188,15 @@ def load():
     for nm_ in ("almpc_certificate", "almpc_get_certificate", "almpc_device_certificate", "almpc_group_certificate",
                 "almpc_group_get_certificate"):
         getattr(L, nm_).restype = ctypes.c_int
+    L.almpc_set_keep_stage_models.argtypes = [_hp, ctypes.c_int]
+    L.almpc_certificate_ltv.argtypes = [_hp, ctypes.c_uint32]
+    L.almpc_get_certificate_ltv.argtypes = [_hp] + [_dp] * 6
+    L.almpc_device_certificate_ltv.argtypes = [_hp] + [ctypes.POINTER(ctypes.c_void_p)] * 6
+    L.almpc_relin_fnn_certificate.argtypes = [_hp, ctypes.c_uint32]
+    L.almpc_group_relin_fnn_certificate.argtypes = [_hp, ctypes.c_uint32]
+    for nm_ in ("almpc_set_keep_stage_models", "almpc_certificate_ltv", "almpc_get_certificate_ltv", "almpc_device_certificate_ltv",
+                "almpc_relin_fnn_certificate", "almpc_group_relin_fnn_certificate"):
+        getattr(L, nm_).restype = ctypes.c_int
     L.almpc_set_structured_fallback.argtypes = [_hp, ctypes.c_int]
     L.almpc_relin_fnn_setup.argtypes = [_hp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_dp] * 12 + [ctypes.c_double, ctypes.c_double]
     L.almpc_relin_fnn_setup.restype = ctypes.c_int
@@ -291,6 +300,8 @@ WANT = {"x": 0x01, "e_x": 0x02, "u": 0x04, "e_u": 0x08, "status": 0x10, "iters":
 SENS = {"K0": 0x1, "dU": 0x2, "dX": 0x4}
 # almpc.h: ALMPC_CERT_* (almpc_certificate)
 CERT = {"cost": 0x1, "res": 0x2, "grad": 0x4, "costate": 0x8}
+# ... and ALMPC_CERT_STATES (almpc_certificate_ltv: x and e_x come together)
+CERT_LTV = dict(CERT, x=0x10, e_x=0x10)
 
 
 def _weighted_design_args(n, m, b, A_batch, B_batch, Q_batch, R_batch, S_batch, P, umin, umax):
@@ -339,12 +350,12 @@ def _sens_read(get, handle, check, want, b, n, m, N):
     return out
 
 
-def _cert_mask(want):
+def _cert_mask(want, table=CERT):
     mask = 0
     for k in ((want,) if isinstance(want, str) else want):
-        if k not in CERT:
-            raise ValueError(f"unknown certificate quantity {k!r} (one of {sorted(CERT)})")
-        mask |= CERT[k]
+        if k not in table:
+            raise ValueError(f"unknown certificate quantity {k!r} (one of {sorted(table)})")
+        mask |= table[k]
     if not mask:
         raise ValueError("certificate: nothing asked for")
     return mask
@@ -804,12 +815,20 @@ class Solver:
         self._check(self.L.almpc_get_weights_instance(self.h, int(i), _ptr(Q), _ptr(R), _ptr(S)))
         return dict(Q=Q, R=R, S=S)
 
+    def set_keep_stage_models(self, on=True):
+        """almpc_set_keep_stage_models: the next design_ltv keeps its stage models on the device for certificate_ltv
+        (batch N n (n + m + 1) doubles of device memory)."""
+        self._check(self.L.almpc_set_keep_stage_models(self.h, 1 if on else 0))
+
     def design_ltv(self, A_all, B_all, c_all, xbar, ubar, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, rho=0.1, sigma=1e-6,
-                   rho_profile="scalar", xmin=None, xmax=None, terminal="none"):
+                   rho_profile="scalar", xmin=None, xmax=None, terminal="none", keep_stage_models=None):
         """Time-varying models: A_all (batch, N, n, n), B_all (batch, N, n, m), c_all (batch, N, n) or None, xbar (batch, n, N+1),
         ubar (batch, m, N), x_ref (n, N+1) / u_ref (m, N) or None, P (n, n) or (batch, n, n).  The QP variable is v = u - ubar.
-        xmin / xmax: state box on xbar + dx (stages 1..N+1); terminal = "equality": xbar + dx = x_ref at stage N+1."""
+        xmin / xmax: state box on xbar + dx (stages 1..N+1); terminal = "equality": xbar + dx = x_ref at stage N+1.
+        keep_stage_models: None leaves the handle's switch as it is; True / False sets it first (set_keep_stage_models)."""
         n, m, N, b = self.n, self.m, self.N, self.batch
+        if keep_stage_models is not None:
+            self.set_keep_stage_models(keep_stage_models)
         self._state_rows(xmin, xmax, terminal)
         self._check(self.L.almpc_set_rho_profile(self.h, {"scalar": 0, "stiffness": 1}[rho_profile]))
         A = np.ascontiguousarray(np.asarray(A_all, dtype=np.float64).reshape(b, N, n, n).transpose(0, 1, 3, 2))
@@ -914,6 +933,12 @@ class Solver:
     def relin_fnn_advance(self):
         """x0 <- fnn(x0, u[:,1]) on the device (closed loop of the black-box model)."""
         self._check(self.L.almpc_relin_fnn_advance(self.h))
+
+    def relin_fnn_certificate(self, want=("cost", "res", "grad", "costate")) -> dict:
+        """almpc_relin_fnn_certificate + almpc_get_certificate: `certificate` of the last relin_fnn_step, with that step's own models,
+        terminal weights and weights."""
+        self._check(self.L.almpc_relin_fnn_certificate(self.h, _cert_mask(want)))
+        return _cert_read(self.L.almpc_get_certificate, self.h, self._check, want, self.batch, self.n, self.m, self.N)
 
     def relin_fnn_timing(self):
         a, d, s = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
@@ -1152,6 +1177,25 @@ class Solver:
         ps = [ctypes.c_void_p() for _ in range(4)]
         self._check(self.L.almpc_device_certificate(self.h, *[ctypes.byref(p) for p in ps]))
         return dict(zip(("cost", "res", "grad", "costate"), [p.value for p in ps]))
+
+    # ---- ... of a step of a time-varying design (include/almpc.h "Certificate of a step of a time-varying design")
+    def certificate_ltv(self, want=("cost", "res", "grad", "costate", "x", "e_x")) -> dict:
+        """almpc_certificate_ltv + almpc_get_certificate_ltv after design_ltv(keep_stage_models=True) and a step: cost (batch,), res (batch,),
+        grad (batch, m, N), costate (batch, n, N+1) (costate[:, :, k+1] = dJ/dc_k), x (batch, n, N+1) the predicted states xbar + dx and
+        e_x = x - x_ref, for what `want` names ("x" and "e_x" come together)."""
+        mask = _cert_mask(want, CERT_LTV)
+        self._check(self.L.almpc_certificate_ltv(self.h, mask))
+        b, n, m, N = self.batch, self.n, self.m, self.N
+        names = (want,) if isinstance(want, str) else tuple(want)
+        shapes = dict(cost=(b,), res=(b,), grad=(b, N, m), costate=(b, N + 1, n), x=(b, N + 1, n), e_x=(b, N + 1, n))
+        bufs = {k: (np.empty(shapes[k]) if k in names else None) for k in shapes}
+        self._check(self.L.almpc_get_certificate_ltv(self.h, *[_ptr(bufs[k]) for k in ("cost", "res", "grad", "costate", "x", "e_x")]))
+        return {k: (v if v.ndim == 1 else v.transpose(0, 2, 1)) for k, v in bufs.items() if v is not None}
+
+    def device_certificate_ltv(self):
+        ps = [ctypes.c_void_p() for _ in range(6)]
+        self._check(self.L.almpc_device_certificate_ltv(self.h, *[ctypes.byref(p) for p in ps]))
+        return dict(zip(("cost", "res", "grad", "costate", "x", "e_x"), [p.value for p in ps]))
 
     def sensitivity_vjp(self, g_u, g_x=None, act_tol=0.0):
         """dL/dx0 (batch, n) for a loss with gradients g_u (batch, m, N) and g_x (batch, n, N+1) or None on the returned
@@ -1556,6 +1600,11 @@ class Group:
     def certificate(self, want=("cost", "res", "grad", "costate")) -> dict:
         """Solver.certificate for the whole batch (almpc_group_certificate + almpc_group_get_certificate)."""
         self._check(self.L.almpc_group_certificate(self.g, _cert_mask(want)))
+        return _cert_read(self.L.almpc_group_get_certificate, self.g, self._check, want, self.batch, self.n, self.m, self.N)
+
+    def relin_fnn_certificate(self, want=("cost", "res", "grad", "costate")) -> dict:
+        """Solver.relin_fnn_certificate for the whole batch (almpc_group_relin_fnn_certificate + almpc_group_get_certificate)."""
+        self._check(self.L.almpc_group_relin_fnn_certificate(self.g, _cert_mask(want)))
         return _cert_read(self.L.almpc_group_get_certificate, self.g, self._check, want, self.batch, self.n, self.m, self.N)
 
     def sensitivity_vjp(self, g_u, g_x=None, act_tol=0.0):

@@ -18,6 +18,7 @@
 #include "almpc_c2d.hip.h"
 #include "almpc_sens.hip.h"
 #include "almpc_cert.hip.h"
+#include "almpc_cert_ltv.hip.h"
 #include "almpc_host_math.h"
 #include "almpc_switches.h"
 #include "almpc_devbuf.h"
@@ -41,6 +42,7 @@
 #include "instances/c2d.inc"
 #include "instances/sens.inc"
 #include "instances/cert.inc"
+#include "instances/cert_ltv.inc"
 #undef ALMPC_KERNEL_INSTANCE
 #endif
 
@@ -183,6 +185,7 @@ struct almpc_handle {
         int useR = 0, useS = 0;
         DevBuf<double> ulin;   // [batch][m] linearisation input of every instance (the first input reference)
         DevBuf<double> Q, R, S;
+        std::vector<double> hQ, hR;   // the setup's Q and R, symmetrised, on the host (almpc_relin_fnn_certificate; S: h->hS)
         DevBuf<double> gS;     // [nz] unscaled input-rate gradient 2 D'Sbar D u_ref of the shared reference
         bool have_prev = false;   // a step has been solved since setup: its inputs can seed the next step's working set
         DevBuf<double> u0, xnext;   // [batch][m] applied inputs, [batch][n] next states (almpc_relin_fnn_advance)
@@ -275,6 +278,13 @@ struct almpc_handle {
         DevBuf<double> W;                          // [Q n*n | R m*m | S m*m | P n*n] shared weights of a condensed design, from the host copies
         bool w_ok = false;                         // ... of the current design
         int useR = 0;                              // R[1,1] != 0 as the last riccati_weights() took it: a structured design's branch (the condensed ones keep sens.useR)
+        // almpc_certificate_ltv (k_cert_ltv, csrc/almpc_cert_ltv.hip.h): the predicted states beside the four above, and what a design
+        // with almpc_set_keep_stage_models on leaves for it: the stage models in lA, lB, lC and the shared references here
+        DevBuf<double> x, ex;                      // [batch][N+1][n] of the last almpc_certificate_ltv
+        uint32_t have_ltv = 0;                     // ALMPC_CERT_* | ALMPC_CERT_STATES bits the buffers hold for the LAST step (0: none)
+        int keep = 0;                              // almpc_set_keep_stage_models: read by the next almpc_design_ltv
+        bool kept = false, kept_c = false;         // the current design is almpc_design_ltv's and left its stage models (and defects)
+        DevBuf<double> xref, uref;                 // [N+1][n], [N][m] the design's shared references (zeros for NULL)
     } cert;
     // stage-wise dual active-set solve (k_sdual, csrc/almpc_sdual.hip.h): input box, state box, terminal equality and S in the
     // multiple-shooting form; stage records of the unconstrained problem (shared: host Riccati at design time)
@@ -1234,7 +1244,7 @@ int wait_and_settle(almpc_handle* h, bool blocking_only = false) {
 // A new design voids a redo that was deferred for a step of the previous one (its models, references and results are about to go)
 void drop_lazy_redo(almpc_handle* h) {
     h->sens.stepped = false; h->sens.v_ok = false; h->sens.t1_ok = false; h->sens.w_ok = false; h->sens.s_ok = false; h->sens.have = 0;   // (what a sensitivity call looks at goes with the design as well)
-    h->cert.have = 0; h->cert.w_ok = false;
+    h->cert.have = 0; h->cert.w_ok = false; h->cert.have_ltv = 0; h->cert.kept = false;
     h->redo.lazy_pending = false;
     h->redo.expected = false;
     h->weighted = false;   // (almpc_design_batched_weighted sets it again behind this call)
@@ -1736,6 +1746,8 @@ struct LtvInputs {
     const double* qadd;    // [batch][nz]    input part of the gradient
     const double* ubar;    // [batch][nz]    linearisation inputs (become the per-instance input reference)
     const double* xbar;    // [batch][(N+1)*n]
+    const double* xref;    // [(N+1)*n] or null   the shared references as the caller gave them (kept for almpc_certificate_ltv)
+    const double* uref;    // [nz] or null
 };
 
 // Persistent per-instance operands of the batched / LTV / SQP designs (allocated once per handle).
@@ -2261,6 +2273,8 @@ int design_ltv_condensed(almpc_handle* h, const double* A_batch, const double* B
         h->lA.reset(); h->lB.reset(); h->lC.reset(); h->lE.reset();
         if (e == hipSuccess && h->mc > 0) {   // ... except with state rows: the step rolls the stage models out
             h->lA = std::move(dAll); h->lB = std::move(dBll); h->lC = std::move(dC); h->lE = std::move(dE);
+        } else if (e == hipSuccess && h->cert.keep) {   // ... or for almpc_certificate_ltv (almpc_set_keep_stage_models)
+            h->lA = std::move(dAll); h->lB = std::move(dBll); h->lC = std::move(dC);
         }
     }
     if (e != hipSuccess) return fail(h, ALMPC_ERR_HIP, std::string("design_ltv: ") + hipGetErrorString(e));
@@ -2278,6 +2292,14 @@ int design_ltv_condensed(almpc_handle* h, const double* A_batch, const double* B
                        (long)nz * nzs, (long)nz);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->cert.keep) {   // the shared references beside the kept stage models (xbar, ubar are the reference buffers already)
+        std::vector<double> xr((size_t)n * (N + 1), 0.0), ur((size_t)nz, 0.0);
+        if (ltv.xref) xr.assign(ltv.xref, ltv.xref + xr.size());
+        if (ltv.uref) ur.assign(ltv.uref, ltv.uref + ur.size());
+        HIP_TRY(h, h->cert.xref.upload(xr.data(), xr.size()));
+        HIP_TRY(h, h->cert.uref.upload(ur.data(), ur.size()));
+        h->cert.kept = true; h->cert.kept_c = ltv.c_all != nullptr;
+    }
     h->ltv = true;
     h->designed = true;
     return ALMPC_OK;
@@ -2825,7 +2847,7 @@ int run_step(almpc_handle* h, const almpc_opts& o, StepMode mode) {
     if (rc != ALMPC_OK) return rc;
     h->state_valid = keep_state;   // (recorded only here: every launch of the step went out)
     h->sens.stepped = true; h->sens.have = 0;
-    h->cert.have = 0;
+    h->cert.have = 0; h->cert.have_ltv = 0;
     if (h->io.x0_slot >= 0) {      // the x0 slot of an asynchronous update is free again once this step has finished
         HIP_TRY(h, hipEventRecord(h->io.ev_used[h->io.x0_slot], h->stream));
         h->io.used_pending[h->io.x0_slot] = true;
@@ -2972,7 +2994,7 @@ int almpc_design_ltv(almpc_handle* h, const double* A_all, const double* B_all, 
                     qa[(k + 1) * m + a] -= 2.0 * sd;
                 }
     }
-    LtvInputs in{A_all, B_all, c_all, ebar.data(), qadd.data(), ubar, xbar};
+    LtvInputs in{A_all, B_all, c_all, ebar.data(), qadd.data(), ubar, xbar, xref, uref};
     if (h->structured) return fail(h, ALMPC_ERR_UNSUPPORTED, "structured solve: time-varying designs go through almpc_sqp_fnn_* (stage models on the device)");
     return design_ltv_condensed(h, A0.data(), B0.data(), Q, R, S, P, P_per_instance, umin, umax, rho, sigma, in);
 }
@@ -3029,6 +3051,7 @@ static int relin_setup_common(almpc_handle* h, int H, int L, int net, int activa
     s.Qm = hm::symmetrised(Q, n); s.Rm = hm::symmetrised(R, m); s.Sm = hm::symmetrised(S, m); s.Pm = hm::symmetrised(P, n);
     almpc_handle::Relin& q = h->relin;
     q.useR = s.Rm[0] != 0.0; q.useS = q.useR && s.Sm[0] != 0.0;
+    q.hQ = s.Qm; q.hR = s.Rm;   // (almpc_relin_fnn_certificate uploads them at its first call)
     if (h->structured && !sdual_shape_ok(n, m, N, q.useS != 0))
         return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup (structured): n (+ m with an input-rate weight) <= 48, m <= 16 and (N + 1)(n + m) <= 4096");
     q.Q.reset(); q.R.reset(); q.S.reset(); q.gS.reset();   // (the network and ulin are replaced by their uploads below)
@@ -4953,11 +4976,150 @@ int certificate(almpc_handle* h, uint32_t want) {
     return ALMPC_OK;
 }
 
+// ---- ... of a step of a time-varying design (k_cert_ltv): the same four and the predicted states, from u, e_u and the kept stage models ----
+
+constexpr uint32_t CERT_LTV_ALL = CERT_ALL | ALMPC_CERT_STATES;
+
+int cert_ltv_check(almpc_handle* h, uint32_t want) {
+    if (!h) return ALMPC_ERR_INVALID;
+    if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, "certificate_ltv before design");
+    if (!want || (want & ~CERT_LTV_ALL)) return fail(h, ALMPC_ERR_INVALID, "certificate_ltv: want must be a mask of ALMPC_CERT_* and ALMPC_CERT_STATES");
+    if (!h->ltv || h->sqp.ready || h->relin.ready)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate_ltv: the design is not almpc_design_ltv's (time-invariant designs: almpc_certificate; the re-linearisation "
+                                              "pipeline: almpc_relin_fnn_certificate; the SQP loop has no certificate)");
+    if (!h->cert.kept || !h->lA || !h->lB || (h->cert.kept_c && !h->lC) || !h->cert.xref || !h->cert.uref)
+        return fail(h, ALMPC_ERR_INVALID, "certificate_ltv: the design released its stage models (almpc_set_keep_stage_models(h, 1) before almpc_design_ltv)");
+    const bool state_rows = h->has_box || h->terminal_eq || h->mc > 0;
+    if (state_rows && (want & ~(ALMPC_CERT_COST | ALMPC_CERT_STATES)))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate_ltv: with state rows (state box, terminal equality) their multipliers enter the costates, and the trajectory does not determine them: ALMPC_CERT_COST and ALMPC_CERT_STATES alone are served");
+    if (h->n > CERT_LTV_MAX_N || h->m > CERT_LTV_MAX_M || (long)(h->N + 1) * (h->n + h->m) > CERT_LTV_MAX_STATES)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate_ltv: needs n <= 16, m <= 16 and (N + 1)(n + m) <= 1024, the shapes a step of an LTV design runs at");
+    if (!h->sens.stepped) return fail(h, ALMPC_ERR_INVALID, "certificate_ltv: no step has run on this design");
+    return ALMPC_OK;
+}
+
+int certificate_ltv(almpc_handle* h, uint32_t want) {
+    ALMPC_TRY(cert_ltv_check(h, want));
+    HIP_TRY(h, hipSetDevice(h->device));
+    ALMPC_TRY(wait_and_settle(h));
+    const size_t b = (size_t)h->batch, xs = (size_t)h->n * (h->N + 1);
+    h->cert.have_ltv = 0; h->cert.have = 0;   // (the four buffers are shared with almpc_certificate)
+    CertLtvParams p = CertLtvParams();
+    p.n = h->n; p.m = h->m; p.N = h->N; p.batch = h->batch;
+    p.useR = h->sens.useR; p.useS = h->useS;
+    p.A = h->lA; p.B = h->lB; p.c = h->cert.kept_c ? h->lC.get() : nullptr;
+    p.Q = h->wQ; p.R = h->wR; p.S = h->wS;   // (the design's weights, symmetrised: batched_design_front)
+    p.P = h->bP; p.P_stride = h->bP_stride;
+    p.umin = h->dUmin; p.umax = h->dUmax;
+    p.xbar = h->dXref; p.xref = h->cert.xref; p.uref = h->cert.uref;   // (dXref: the design's almpc_set_reference(xbar, ubar, 1))
+    p.eu = h->dEu; p.u = h->dU;
+    if (want & ALMPC_CERT_COST) { HIP_TRY(h, h->cert.cost.grow(b)); p.cost = h->cert.cost; }
+    if (want & ALMPC_CERT_RES) { HIP_TRY(h, h->cert.res.grow(b)); p.res = h->cert.res; }
+    if (want & ALMPC_CERT_GRAD) { HIP_TRY(h, h->cert.grad.grow(b * h->nz)); p.grad = h->cert.grad; }
+    if (want & ALMPC_CERT_COSTATE) { HIP_TRY(h, h->cert.costate.grow(b * xs)); p.costate = h->cert.costate; }
+    if (want & ALMPC_CERT_STATES) { HIP_TRY(h, h->cert.x.grow(b * xs)); HIP_TRY(h, h->cert.ex.grow(b * xs)); p.x = h->cert.x; p.ex = h->cert.ex; }
+    p.lds_per_wave = cert_ltv_lds_doubles(h->n, h->N);
+    const size_t per_wave = (size_t)p.lds_per_wave * sizeof(double);
+    const int waves = waves_in_lds(per_wave, CERT_LTV_WAVES), wgs = capped_grid(h->batch, waves, CERT_LTV_WGS_PER_CU * h->num_cus);
+    if (p.c) HIP_TRY(h, LAUNCH_WAVES((k_cert_ltv<true>), wgs, waves, waves * per_wave, h->stream, p));
+    else HIP_TRY(h, LAUNCH_WAVES((k_cert_ltv<false>), wgs, waves, waves * per_wave, h->stream, p));
+    HIP_TRY(h, stream_wait_polling(h));
+    h->cert.have_ltv = want;
+    return ALMPC_OK;
+}
+
+// ---- ... of a step of the re-linearisation pipeline: a per-instance time-invariant design, so k_cert on the step's own (A_i, B_i, P_i) ----
+
+int relin_certificate(almpc_handle* h, uint32_t want) {
+    if (!h) return ALMPC_ERR_INVALID;
+    almpc_handle::Relin& q = h->relin;
+    if (!q.ready && !h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, "relin_fnn_certificate before relin_fnn_setup");
+    if (!want || (want & ~CERT_ALL)) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_certificate: want must be a mask of ALMPC_CERT_*");
+    if (!q.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_certificate: the design is not the re-linearisation pipeline's (almpc_certificate, almpc_certificate_ltv)");
+    const bool state_rows = h->has_box || h->terminal_eq || h->mc > 0 || (h->sd.ready && (h->sd.has_box || h->sd.has_eq));
+    if (state_rows && (want & ~ALMPC_CERT_COST))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_certificate: with state rows (state box, terminal equality) their multipliers enter the costates, and the trajectory does not determine them: ALMPC_CERT_COST alone is served");
+    if (h->n > CERT_MAX_N || h->m > CERT_MAX_M || (size_t)cert_lds_doubles(h->n, h->m) * sizeof(double) > (size_t)LDS_BUDGET)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_certificate: needs n <= 64, m <= 16 and the operands of an instance in 160 KB of LDS");
+    const size_t n = (size_t)h->n, m = (size_t)h->m, nn = n * n, mm = m * m, b = (size_t)h->batch;
+    if (q.hQ.size() != nn || q.hR.size() != mm || h->hS.size() != mm || !h->bA || !h->bB || !h->bP)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_certificate: the pipeline's weights and models are not kept");
+    if (!q.have_prev || !h->designed || !h->sens.stepped) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_certificate: no step has run since relin_fnn_setup");
+    HIP_TRY(h, hipSetDevice(h->device));
+    ALMPC_TRY(wait_and_settle(h));
+    h->cert.have = 0; h->cert.have_ltv = 0;
+    CertParams p = CertParams();
+    p.n = h->n; p.m = h->m; p.N = h->N; p.batch = h->batch;
+    p.useR = q.useR; p.useS = q.useS;
+    p.A = h->bA; p.A_stride = (long)nn; p.B = h->bB; p.B_stride = (long)(n * m);   // the Jacobians of the last step (k_c2d's result with almpc_set_model_time)
+    p.P = h->bP; p.P_stride = h->bP_stride;                                        // one for the batch, or the last step's P_i (almpc_set_terminal_weight)
+    if (!h->cert.w_ok) {   // the shared weights, once per setup, in stream order in front of the kernel
+        HIP_TRY(h, h->cert.W.grow(2 * nn + 2 * mm));
+        HIP_TRY(h, hipMemcpyAsync(h->cert.W, q.hQ.data(), nn * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->cert.W + nn, q.hR.data(), mm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->cert.W + nn + mm, h->hS.data(), mm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        h->cert.w_ok = true;
+    }
+    p.Q = h->cert.W; p.R = h->cert.W + nn; p.S = h->cert.W + nn + mm;
+    p.umin = h->dUmin; p.umax = h->dUmax;
+    p.ex = h->dEx; p.eu = h->dEu; p.u = h->dU;
+    p.lds_per_wave = cert_lds_doubles(h->n, h->m);
+    if (want & ALMPC_CERT_COST) { HIP_TRY(h, h->cert.cost.grow(b)); p.cost = h->cert.cost; }
+    if (want & ALMPC_CERT_RES) { HIP_TRY(h, h->cert.res.grow(b)); p.res = h->cert.res; }
+    if (want & ALMPC_CERT_GRAD) { HIP_TRY(h, h->cert.grad.grow(b * h->nz)); p.grad = h->cert.grad; }
+    if (want & ALMPC_CERT_COSTATE) { HIP_TRY(h, h->cert.costate.grow(b * n * (h->N + 1))); p.costate = h->cert.costate; }
+    ALMPC_TRY(cert_launch(h, p));
+    HIP_TRY(h, stream_wait_polling(h));
+    h->cert.have = want;
+    return ALMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int almpc_certificate(almpc_handle* h, uint32_t want) { return certificate(h, want); }
+
+int almpc_set_keep_stage_models(almpc_handle* h, int on) {
+    if (!h) return ALMPC_ERR_INVALID;
+    h->cert.keep = on != 0;
+    return ALMPC_OK;
+}
+
+int almpc_certificate_ltv(almpc_handle* h, uint32_t want) { return certificate_ltv(h, want); }
+
+int almpc_get_certificate_ltv(almpc_handle* h, double* cost, double* res, double* grad, double* costate, double* x, double* e_x) {
+    if (!h) return ALMPC_ERR_INVALID;
+    const uint32_t need = (cost ? ALMPC_CERT_COST : 0u) | (res ? ALMPC_CERT_RES : 0u) | (grad ? ALMPC_CERT_GRAD : 0u) |
+                          (costate ? ALMPC_CERT_COSTATE : 0u) | ((x || e_x) ? ALMPC_CERT_STATES : 0u);
+    if (!h->cert.have_ltv || (need & ~h->cert.have_ltv))
+        return fail(h, ALMPC_ERR_INVALID, "get_certificate_ltv: not computed for the last step (almpc_certificate_ltv with these ALMPC_CERT_* bits first)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t b = (size_t)h->batch, xs = (size_t)h->n * (h->N + 1);
+    if (cost) HIP_TRY(h, hipMemcpy(cost, h->cert.cost, b * sizeof(double), hipMemcpyDeviceToHost));
+    if (res) HIP_TRY(h, hipMemcpy(res, h->cert.res, b * sizeof(double), hipMemcpyDeviceToHost));
+    if (grad) HIP_TRY(h, hipMemcpy(grad, h->cert.grad, b * h->nz * sizeof(double), hipMemcpyDeviceToHost));
+    if (costate) HIP_TRY(h, hipMemcpy(costate, h->cert.costate, b * xs * sizeof(double), hipMemcpyDeviceToHost));
+    if (x) HIP_TRY(h, hipMemcpy(x, h->cert.x, b * xs * sizeof(double), hipMemcpyDeviceToHost));
+    if (e_x) HIP_TRY(h, hipMemcpy(e_x, h->cert.ex, b * xs * sizeof(double), hipMemcpyDeviceToHost));
+    return ALMPC_OK;
+}
+
+int almpc_device_certificate_ltv(almpc_handle* h, const double** d_cost, const double** d_res, const double** d_grad, const double** d_costate,
+                                 const double** d_x, const double** d_ex) {
+    if (!h) return ALMPC_ERR_INVALID;
+    const uint32_t have = h->cert.have_ltv;
+    if (!have) return fail(h, ALMPC_ERR_INVALID, "device_certificate_ltv: not computed for the last step");
+    if (d_cost) *d_cost = (have & ALMPC_CERT_COST) ? h->cert.cost.get() : nullptr;
+    if (d_res) *d_res = (have & ALMPC_CERT_RES) ? h->cert.res.get() : nullptr;
+    if (d_grad) *d_grad = (have & ALMPC_CERT_GRAD) ? h->cert.grad.get() : nullptr;
+    if (d_costate) *d_costate = (have & ALMPC_CERT_COSTATE) ? h->cert.costate.get() : nullptr;
+    if (d_x) *d_x = (have & ALMPC_CERT_STATES) ? h->cert.x.get() : nullptr;
+    if (d_ex) *d_ex = (have & ALMPC_CERT_STATES) ? h->cert.ex.get() : nullptr;
+    return ALMPC_OK;
+}
+
+int almpc_relin_fnn_certificate(almpc_handle* h, uint32_t want) { return relin_certificate(h, want); }
 
 int almpc_get_certificate(almpc_handle* h, double* cost, double* res, double* grad, double* costate) {
     if (!h) return ALMPC_ERR_INVALID;

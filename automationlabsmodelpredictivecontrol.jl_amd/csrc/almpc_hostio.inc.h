@@ -725,6 +725,11 @@ int almpc_group_certificate(almpc_group* g, uint32_t want) {
     if (!g) return ALMPC_ERR_INVALID;
     return group_fanout(g, [&](int i) { return almpc_certificate(g->hs[i], want); });
 }
+// (the re-linearisation pipeline's certificate fills the same buffers: almpc_group_get_certificate reads them)
+int almpc_group_relin_fnn_certificate(almpc_group* g, uint32_t want) {
+    if (!g) return ALMPC_ERR_INVALID;
+    return group_fanout(g, [&](int i) { return almpc_relin_fnn_certificate(g->hs[i], want); });
+}
 int almpc_group_get_certificate(almpc_group* g, double* cost, double* res, double* grad, double* costate) {
     if (!g) return ALMPC_ERR_INVALID;
     const size_t n = (size_t)g->n, nz = (size_t)g->m * g->N;

@@ -290,7 +290,8 @@ int almpc_get_weights_instance(almpc_handle* h, int instance, double* Q, double*
  *   almpc_design_shared;  P: terminal weight, n*n (P_per_instance = 0) or [batch][n*n] (required).
  * Linearised dynamics dx_{k+1} = A_k dx_k + B_k v_k + c_k, dx_0 = 0, cost of src/sub/design_mpc.jl:405-468 in (xbar + dx, ubar + v),
  * bounds umin <= ubar + v <= umax.  almpc_calculate then solves for v; almpc_get_results returns u = ubar + v and e_u = v
- * (x / e_x are not defined for an LTV design: roll the nonlinear model out on the caller's side).  almpc_set_reference is
+ * (x / e_x of almpc_get_results are not defined for an LTV design: the predicted states xbar + dx, the cost, the costates and a KKT
+ * residual of the step come from almpc_certificate_ltv below, "Certificate of a step of a time-varying design").  almpc_set_reference is
  * not used with this design.  Needs nz^2 + 3 n nz + 4 n^2 + ... doubles <= 160 KB of LDS (nz <= ~120 for n = 12).
  */
 int almpc_design_ltv(almpc_handle* h, const double* A_all, const double* B_all, const double* c_all, const double* xbar,
@@ -837,6 +838,54 @@ int almpc_get_certificate(almpc_handle* h, double* cost /*[batch]*/, double* res
 int almpc_device_certificate(almpc_handle* h, const double** d_cost, const double** d_res, const double** d_grad, const double** d_costate);
 int almpc_group_certificate(almpc_group* g, uint32_t want);
 int almpc_group_get_certificate(almpc_group* g, double* cost, double* res, double* grad, double* costate);
+
+/*
+ * Certificate of a step of a time-varying design (k_cert_ltv, DESIGN.md "k_cert_ltv"): what an SQP / multiple-shooting caller of
+ * almpc_design_ltv needs to close its outer loop on the device -- the predicted states to take the step with, the cost for a merit
+ * function, the costates (the multipliers of the linearised dynamics: an exact Lagrangian Hessian W_k = d2(lam_{k+1}'f)/dz2 is built from
+ * them) and a method-independent KKT residual as a stopping test.  From the returned u and e_u = v and the design data alone.  Per
+ * instance, stages 0-based, v_k = e_u[:,k], u_k = u[:,k], w_k = u_k - uref_k, d_i = u_i - u_{i+1}; Q, R, S, P symmetrised; useR, useS as
+ * the design took them:
+ *     forward   dx_0 = 0,  dx_{k+1} = A_k dx_k + B_k v_k + c_k          (c = 0 if the design got NULL)
+ *               x_k = xbar_k + dx_k,  e_k = x_k - xref_k
+ *     cost      J = e_N'P e_N + sum_{k<N} (e_k'Q e_k + [useR] w_k'R w_k) + [useS] sum_{i<N-1} d_i'S d_i
+ *     backward  lam_N = 2 P e_N,  lam_k = 2 Q e_k + A_k'lam_{k+1}
+ *               g_k = B_k'lam_{k+1} + [useR] 2 R w_k + [useS]([k < N-1] 2 S d_k - [k > 0] 2 S d_{k-1})
+ *     res       max_{k,j} |u_k - clip(u_k - g_k, umin, umax)|
+ * With H, q of the design's QP min 1/2 v'Hv + q'v (almpc_get_design_instance, almpc_get_gradient_instance): stacked g = H v + q;
+ * J(v) - J(0) = 1/2 v'Hv + q'v; lam_{k+1} = dJ/dc_k at fixed v.  res is to be judged against max(1, |g|_inf), as almpc_certificate's.
+ *   almpc_set_keep_stage_models  on != 0: the NEXT almpc_design_ltv moves its copies of A_all, B_all, c_all into the handle instead of
+ *                             releasing them behind the design kernels, and uploads the shared xref / uref (xbar, ubar are on the device
+ *                             already).  Costs batch N n (n + m + 1) doubles of device memory until the next almpc_design_ltv or
+ *                             almpc_destroy.  Default 0: the design is exactly what it was.
+ *   almpc_certificate_ltv     synchronous, settles first; `want` is a mask of ALMPC_CERT_* and ALMPC_CERT_STATES; the results stay in
+ *                             buffers of the handle (cost, res, grad, costate: those of almpc_certificate) until the next step or design.
+ *   almpc_get_certificate_ltv copies out what the last almpc_certificate_ltv computed (NULL: not wanted; a pointer whose bit was not
+ *                             asked for is ALMPC_ERR_INVALID; x and e_x both belong to ALMPC_CERT_STATES).
+ *   almpc_device_certificate_ltv  the device addresses of the same buffers (NULL for a bit that was not computed).
+ * Shapes: those a step of an LTV design runs at -- n <= 16, m <= 16, (N + 1)(n + m) <= 1024 (else ALMPC_ERR_UNSUPPORTED).
+ * ALMPC_ERR_NOT_DESIGNED before a design; ALMPC_ERR_INVALID before the design's first step, for want = 0 or unknown bits, from the
+ * getters after a new step or design, and after an almpc_design_ltv made with the keep switch off (the message names the switch);
+ * ALMPC_ERR_UNSUPPORTED on a design that is not almpc_design_ltv's (the message names almpc_certificate; the SQP loop stays without a
+ * certificate: its Jacobians belong to the iterate before the update), and with a state box or the terminal equality for every bit but
+ * ALMPC_CERT_COST and ALMPC_CERT_STATES.  almpc_certificate keeps refusing these designs.
+ *
+ * The re-linearisation pipeline is a per-instance time-invariant design (e_x[:,k+1] = A_i e_x[:,k] + B_i e_u[:,k]), so k_cert serves it:
+ *   almpc_relin_fnn_certificate  almpc_certificate's four quantities for the last almpc_relin_fnn_step, with the models (A_i, B_i), the
+ *                             terminal weights (one per step after almpc_set_terminal_weight) and the weights that step used; condensed
+ *                             and structured handles; with state rows ALMPC_CERT_COST alone.  Fills almpc_certificate's buffers: read
+ *                             them with almpc_get_certificate, almpc_device_certificate, almpc_group_get_certificate.  Error codes as
+ *                             almpc_certificate's; ALMPC_ERR_UNSUPPORTED on a design that is not the pipeline's.
+ */
+#define ALMPC_CERT_STATES 16u
+int almpc_set_keep_stage_models(almpc_handle* h, int on);
+int almpc_certificate_ltv(almpc_handle* h, uint32_t want);            /* ALMPC_CERT_* | ALMPC_CERT_STATES */
+int almpc_get_certificate_ltv(almpc_handle* h, double* cost, double* res, double* grad, double* costate,
+                              double* x /*[batch][N+1][n]*/, double* e_x /*[batch][N+1][n]*/);
+int almpc_device_certificate_ltv(almpc_handle* h, const double** d_cost, const double** d_res, const double** d_grad,
+                                 const double** d_costate, const double** d_x, const double** d_ex);
+int almpc_relin_fnn_certificate(almpc_handle* h, uint32_t want);      /* k_cert on the step's own (A_i, B_i, P_i) */
+int almpc_group_relin_fnn_certificate(almpc_group* g, uint32_t want);
 
 /*
  * Parameter gradients of the returned solution: for the loss of almpc_sensitivity_vjp (g_u [batch][N][m], g_x [batch][N+1][n] or NULL),

@@ -24,7 +24,8 @@ export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_s
        group_sensitivity_params_vjp, dare_vjp, dare_vjp_batched, sensitivity_stagewise, sensitivity_stagewise_vjp,
        group_sensitivity_stagewise, group_sensitivity_stagewise_vjp, sensitivity_stagewise_rate, sensitivity_stagewise_rate_vjp,
        group_sensitivity_stagewise_rate, group_sensitivity_stagewise_rate_vjp, certificate, certificate!, device_certificate,
-       group_certificate, group_certificate!
+       group_certificate, group_certificate!, set_keep_stage_models, certificate_ltv, certificate_ltv!, device_certificate_ltv,
+       relin_fnn_certificate, relin_fnn_certificate!, group_relin_fnn_certificate, group_relin_fnn_certificate!
 
 const libalmpc = get(ENV, "ALMPC_LIB", "libalmpc.so")
 
@@ -851,6 +852,72 @@ function device_certificate(mod::HipModeler)
     return pc[], pr[], pg[], pl[]
 end
 
+# ---- ... of a step of a time-varying design (include/almpc.h "Certificate of a step of a time-varying design"): ALMPC_CERT_STATES = 16
+"`almpc_set_keep_stage_models`: the next `almpc_design_ltv` keeps its stage models on the device for `certificate_ltv` (batch N n (n + m + 1) doubles)"
+set_keep_stage_models(mod::HipModeler, on::Bool = true) =
+    check(mod.handle, ccall((:almpc_set_keep_stage_models, libalmpc), Cint, (Ptr{Cvoid}, Cint), mod.handle, on ? 1 : 0))
+"""
+    certificate_ltv!(mod, cost, res, grad, costate, x, e_x)
+
+The certificate of the last step of an `almpc_design_ltv` design made with `set_keep_stage_models` (`almpc_certificate_ltv` +
+`almpc_get_certificate_ltv`) into the caller's arrays; `nothing` = not wanted.  `cost`, `res` (batch), `grad` (m x N x batch) and
+`costate` (n x (N+1) x batch; `costate[:, k+1]` is d cost / d c_k) as `certificate!`'s; `x`, `e_x` (n x (N+1) x batch): the predicted
+states xbar + dx of the linearised dynamics and x - x_ref.
+"""
+function certificate_ltv!(mod::HipModeler, cost::Union{Nothing,Array{Float64}}, res::Union{Nothing,Array{Float64}},
+                          grad::Union{Nothing,Array{Float64}}, costate::Union{Nothing,Array{Float64}},
+                          x::Union{Nothing,Array{Float64}}, e_x::Union{Nothing,Array{Float64}})
+    traj = mod.n * (mod.N + 1) * mod.batch
+    for (name, a, len) in (("cost", cost, mod.batch), ("res", res, mod.batch), ("grad", grad, mod.m * mod.N * mod.batch), ("costate", costate, traj),
+                           ("x", x, traj), ("e_x", e_x, traj))
+        a === nothing || length(a) == len || throw(DimensionMismatch("$name holds $(length(a)) values, the solver writes $len"))
+    end
+    want = cert_mask(cost, res, grad, costate) | UInt32((x === nothing && e_x === nothing) ? 0 : 16)
+    want != 0 || error("certificate_ltv: nothing asked for")
+    check(mod.handle, ccall((:almpc_certificate_ltv, libalmpc), Cint, (Ptr{Cvoid}, UInt32), mod.handle, want))
+    pf(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve cost res grad costate x e_x check(mod.handle, ccall((:almpc_get_certificate_ltv, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        mod.handle, pf(cost), pf(res), pf(grad), pf(costate), pf(x), pf(e_x)))
+    return cost, res, grad, costate, x, e_x
+end
+"`certificate_ltv!` into fresh arrays: `certificate_ltv(mod; cost, res, grad, costate, states) -> (cost, res, grad, costate, x, e_x)`"
+function certificate_ltv(mod::HipModeler; cost::Bool = true, res::Bool = true, grad::Bool = false, costate::Bool = false, states::Bool = true)
+    traj() = Array{Float64,3}(undef, mod.n, mod.N + 1, mod.batch)
+    return certificate_ltv!(mod, cost ? Vector{Float64}(undef, mod.batch) : nothing, res ? Vector{Float64}(undef, mod.batch) : nothing,
+                            grad ? Array{Float64,3}(undef, mod.m, mod.N, mod.batch) : nothing, costate ? traj() : nothing,
+                            states ? traj() : nothing, states ? traj() : nothing)
+end
+"device pointers of the last `certificate_ltv` (`almpc_device_certificate_ltv`): `C_NULL` for what was not computed"
+function device_certificate_ltv(mod::HipModeler)
+    ps = ntuple(_ -> Ref{Ptr{Float64}}(C_NULL), 6)
+    check(mod.handle, ccall((:almpc_device_certificate_ltv, libalmpc), Cint,
+                            (Ptr{Cvoid}, Ref{Ptr{Float64}}, Ref{Ptr{Float64}}, Ref{Ptr{Float64}}, Ref{Ptr{Float64}}, Ref{Ptr{Float64}}, Ref{Ptr{Float64}}),
+                            mod.handle, ps[1], ps[2], ps[3], ps[4], ps[5], ps[6]))
+    return map(p -> p[], ps)
+end
+"""
+    relin_fnn_certificate!(mod, cost, res, grad, costate)
+
+`certificate!` for the last step of the re-linearisation pipeline (`almpc_relin_fnn_certificate` + `almpc_get_certificate`): with that
+step's own models, terminal weights and weights.
+"""
+function relin_fnn_certificate!(mod::HipModeler, cost::Union{Nothing,Array{Float64}}, res::Union{Nothing,Array{Float64}},
+                                grad::Union{Nothing,Array{Float64}}, costate::Union{Nothing,Array{Float64}})
+    check_cert_sizes(mod.n, mod.m, mod.N, mod.batch, cost, res, grad, costate)
+    check(mod.handle, ccall((:almpc_relin_fnn_certificate, libalmpc), Cint, (Ptr{Cvoid}, UInt32), mod.handle, cert_mask(cost, res, grad, costate)))
+    pf(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve cost res grad costate check(mod.handle, ccall((:almpc_get_certificate, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), mod.handle, pf(cost), pf(res), pf(grad), pf(costate)))
+    return cost, res, grad, costate
+end
+"`relin_fnn_certificate!` into fresh arrays"
+function relin_fnn_certificate(mod::HipModeler; cost::Bool = true, res::Bool = true, grad::Bool = false, costate::Bool = false)
+    return relin_fnn_certificate!(mod, cost ? Vector{Float64}(undef, mod.batch) : nothing, res ? Vector{Float64}(undef, mod.batch) : nothing,
+                                  grad ? Array{Float64,3}(undef, mod.m, mod.N, mod.batch) : nothing,
+                                  costate ? Array{Float64,3}(undef, mod.n, mod.N + 1, mod.batch) : nothing)
+end
+
 # almpc_param_grads (include/almpc.h): host pointers, C_NULL = not wanted
 struct ParamGrads
     x0::Ptr{Float64}; f::Ptr{Float64}; u_ref::Ptr{Float64}; u_min::Ptr{Float64}; u_max::Ptr{Float64}
@@ -1108,6 +1175,22 @@ function group_certificate(g::HipGroup; cost::Bool = true, res::Bool = true, gra
     return group_certificate!(g, cost ? Vector{Float64}(undef, g.batch) : nothing, res ? Vector{Float64}(undef, g.batch) : nothing,
                               grad ? Array{Float64,3}(undef, g.m, g.N, g.batch) : nothing,
                               costate ? Array{Float64,3}(undef, g.n, g.N + 1, g.batch) : nothing)
+end
+"`relin_fnn_certificate!` for the whole batch (`almpc_group_relin_fnn_certificate` + `almpc_group_get_certificate`)"
+function group_relin_fnn_certificate!(g::HipGroup, cost::Union{Nothing,Array{Float64}}, res::Union{Nothing,Array{Float64}},
+                                      grad::Union{Nothing,Array{Float64}}, costate::Union{Nothing,Array{Float64}})
+    check_cert_sizes(g.n, g.m, g.N, g.batch, cost, res, grad, costate)
+    gcheck(g.group, ccall((:almpc_group_relin_fnn_certificate, libalmpc), Cint, (Ptr{Cvoid}, UInt32), g.group, cert_mask(cost, res, grad, costate)))
+    pf(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve cost res grad costate gcheck(g.group, ccall((:almpc_group_get_certificate, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), g.group, pf(cost), pf(res), pf(grad), pf(costate)))
+    return cost, res, grad, costate
+end
+"`relin_fnn_certificate` for the whole batch"
+function group_relin_fnn_certificate(g::HipGroup; cost::Bool = true, res::Bool = true, grad::Bool = false, costate::Bool = false)
+    return group_relin_fnn_certificate!(g, cost ? Vector{Float64}(undef, g.batch) : nothing, res ? Vector{Float64}(undef, g.batch) : nothing,
+                                        grad ? Array{Float64,3}(undef, g.m, g.N, g.batch) : nothing,
+                                        costate ? Array{Float64,3}(undef, g.n, g.N + 1, g.batch) : nothing)
 end
 "`sensitivity_params_vjp` for the whole batch (`almpc_group_sensitivity_params_vjp`, `almpc_group_sensitivity_params_vjp_dare`)"
 function group_sensitivity_params_vjp(g::HipGroup, g_u::Array{Float64}, g_x::Union{Nothing,Array{Float64}} = nothing;
