@@ -100,8 +100,19 @@ struct almpc_handle {
     DevBuf<double> dRollM;
     int roll_s = 0, roll_nb = 0;  // roll_s == 0: shape not covered (n > ROLL_NX or m > ROLL_SMX), the stage-by-stage rollout is used
     long xref_stride = 0, uref_stride = 0, fS_stride = 0;
-    std::vector<double> hS;  // S weight, symmetrised (for fS with per-instance references)
-    int useS = 0;            // the input-rate term is part of the cost: R[1,1] != 0 and S[1,1] != 0 (src/sub/design_mpc.jl:423-466)
+    // The cost weights a design keeps for its readers (almpc_set_reference's fS, almpc_get_weights_instance, the parameter gradients,
+    // k_sens_face_rate, the certificates): the only host copy -- with the shared P above -- and the only device copy made from it;
+    // the solvers' own buffers (rQ.., wQ.., wiQ.., sd.dQ.., sqp.Q.., relin.Q..) hold what their kernels take.  keep_weights() fills it
+    // in every design and setup path, kept_on_device() is the only writer of W (DESIGN.md "Where a design's weights live").
+    // Q, R: as the path takes them (almpc_design_shared's as given, else symmetrised; a weighted design's: instance 0's), empty where
+    // it keeps none (structured designs, the SQP setup); S: symmetrised (a structured design's as given, zeros where its branch drops
+    // it); useR: R[1,1] != 0, useS: and S[1,1] != 0 -- the input-rate term is part of the cost (src/sub/design_mpc.jl:423-466)
+    struct Kept {
+        std::vector<double> Q, R, S;
+        int useR = 0, useS = 0;
+        DevBuf<double> W;         // [Q n*n | R m*m | S m*m | P n*n]
+        uint32_t on_device = 0;   // KEPT_* parts of W that hold the current design's matrices (none after a design: drop_lazy_redo)
+    } kept;
     // device: per-instance state and results
     double* dX0 = nullptr;   // view: x0_own or a slot of the pinned ring
     DevBuf<double> x0_own, dXs, dZs, dYs, dV0, dW;
@@ -185,7 +196,6 @@ struct almpc_handle {
         int useR = 0, useS = 0;
         DevBuf<double> ulin;   // [batch][m] linearisation input of every instance (the first input reference)
         DevBuf<double> Q, R, S;
-        std::vector<double> hQ, hR;   // the setup's Q and R, symmetrised, on the host (almpc_relin_fnn_certificate; S: h->hS)
         DevBuf<double> gS;     // [nz] unscaled input-rate gradient 2 D'Sbar D u_ref of the shared reference
         bool have_prev = false;   // a step has been solved since setup: its inputs can seed the next step's working set
         DevBuf<double> u0, xnext;   // [batch][m] applied inputs, [batch][n] next states (almpc_relin_fnn_advance)
@@ -255,34 +265,23 @@ struct almpc_handle {
         DevBuf<double> gu, gx, gx0;     // VJP: uploaded loss gradients, result [batch][n]
         DevBuf<int32_t> vrows;          // [batch] |W| of the last VJP
         bool stepped = false;           // a step has run on the current design
-        // parameter gradients (almpc_sensitivity_params_vjp): the design's Q and whether it kept R, host side (every condensed design
-        // leaves them); the rest is made at the first such call
-        std::vector<double> Q, R;       // (R: what the design's DARE was taken with, for almpc_sensitivity_params_vjp_dare)
-        int useR = 0;
-        DevBuf<double> W;               // [Q n*n | S m*m | P n*n | R m*m] device copies of the weights (P: a shared design's; else the handle's bP)
-        bool w_ok = false;              // ... of the current design
-        DevBuf<double> pz;              // [batch][nz] z | [batch][nz] nu | [batch][m] dL/dumin | [batch][m] dL/dumax (k_sens_pz)
+        // parameter gradients (almpc_sensitivity_params_vjp), made at the first such call; the weights are the handle's kept ones
+        DevBuf<double> pz;             // [batch][nz] z | [batch][nz] nu | [batch][m] dL/dumin | [batch][m] dL/dumax (k_sens_pz)
         DevBuf<double> pout;            // k_sens_params' outputs: u_ref, Q, P, A, R, S, B, each [batch][its size]
         DevBuf<double> traj;            // [workgroups][3][(N+1) n] zeta, mu, al of the instance a workgroup is at
         DevBuf<int32_t> dstat;          // [batch] k_dare_vjp's status words (almpc_sensitivity_params_vjp_dare)
         DevBuf<double> Kst;             // [batch][N][m n] stage gains of k_sens_face (almpc_sensitivity_stagewise with dU or dX);
-                                        // [batch][N][m (n + m)] those of k_sens_face_rate
-        DevBuf<double> S;               // [m*m] the design's input-rate weight for k_sens_face_rate (h->hS; shared on every structured design)
-        bool s_ok = false;              // ... of the current design
+                                        // [batch][N][m (n + m)] those of k_sens_face_rate (its S: the kept one, shared on every structured design)
     } sens;
-    // Certificate of the last step (almpc_certificate; k_cert, csrc/almpc_cert.hip.h): cost, KKT residual, input gradient, costates.
-    // As with sens, every buffer is made at the first call that needs it.
+    // Certificate of the last step (almpc_certificate, almpc_relin_fnn_certificate: k_cert, csrc/almpc_cert.hip.h; almpc_certificate_ltv:
+    // k_cert_ltv, csrc/almpc_cert_ltv.hip.h).  As with sens, every buffer is made at the first call that needs it.
     struct Cert {
-        DevBuf<double> cost, res, grad, costate;   // [batch], [batch], [batch][N][m], [batch][N+1][n] of the last almpc_certificate
-        uint32_t have = 0;                         // ALMPC_CERT_* bits the buffers hold for the LAST step (0: none)
-        DevBuf<double> W;                          // [Q n*n | R m*m | S m*m | P n*n] shared weights of a condensed design, from the host copies
-        bool w_ok = false;                         // ... of the current design
-        int useR = 0;                              // R[1,1] != 0 as the last riccati_weights() took it: a structured design's branch (the condensed ones keep sens.useR)
-        // almpc_certificate_ltv (k_cert_ltv, csrc/almpc_cert_ltv.hip.h): the predicted states beside the four above, and what a design
-        // with almpc_set_keep_stage_models on leaves for it: the stage models in lA, lB, lC and the shared references here
+        DevBuf<double> cost, res, grad, costate;   // [batch], [batch], [batch][N][m], [batch][N+1][n] of the last certificate call
         DevBuf<double> x, ex;                      // [batch][N+1][n] of the last almpc_certificate_ltv
-        uint32_t have_ltv = 0;                     // ALMPC_CERT_* | ALMPC_CERT_STATES bits the buffers hold for the LAST step (0: none)
-        int keep = 0;                              // almpc_set_keep_stage_models: read by the next almpc_design_ltv
+        uint32_t have = 0;                         // ALMPC_CERT_* (| ALMPC_CERT_STATES) bits the buffers hold for the LAST step (0: none)
+        bool ltv_form = false;                     // ... filled by almpc_certificate_ltv: the getters of the other form are refused
+        // what a design with almpc_set_keep_stage_models on leaves for almpc_certificate_ltv: lA, lB, lC and the shared references here
+        int keep = 0;                             // almpc_set_keep_stage_models: read by the next almpc_design_ltv
         bool kept = false, kept_c = false;         // the current design is almpc_design_ltv's and left its stage models (and defects)
         DevBuf<double> xref, uref;                 // [N+1][n], [N][m] the design's shared references (zeros for NULL)
     } cert;
@@ -511,12 +510,42 @@ hipError_t launch_ghat_inst(almpc_handle* h, const double* A_all, const double* 
     return hipGetLastError();
 }
 
+// The weights a design or setup path takes, into the handle's record (Q, R null: none kept); what is on the device is the last design's
+void keep_weights(almpc_handle* h, const hm::mat* Q, const hm::mat* R, const hm::mat& S, bool useR, bool useS) {
+    almpc_handle::Kept& k = h->kept;
+    k.Q = Q ? *Q : hm::mat(); k.R = R ? *R : hm::mat(); k.S = S;
+    k.useR = useR; k.useS = useS; k.on_device = 0;
+}
+
+// The parts of that record (and the shared P) a reader needs, on the device: each goes there once per design, in stream order in
+// front of the reading kernel.  d: the needed pointers, null for the rest.  (That a needed matrix is kept is the caller's check.)
+enum : uint32_t { KEPT_Q = 1u, KEPT_R = 2u, KEPT_S = 4u, KEPT_P = 8u };
+struct KeptDev { const double *Q, *R, *S, *P; };
+int kept_on_device(almpc_handle* h, uint32_t need, KeptDev& d) {
+    almpc_handle::Kept& k = h->kept;
+    const size_t nn = (size_t)h->n * h->n, mm = (size_t)h->m * h->m;
+    const std::vector<double>* src[4] = {&k.Q, &k.R, &k.S, &h->P};
+    const size_t len[4] = {nn, mm, mm, nn}, off[4] = {0, nn, nn + mm, nn + 2 * mm};
+    if (need) HIP_TRY(h, k.W.grow(2 * nn + 2 * mm));
+    const double* at[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < 4; ++i) {
+        if (!(need >> i & 1u)) continue;
+        if (!(k.on_device >> i & 1u)) {
+            if (src[i]->size() != len[i]) return fail(h, ALMPC_ERR_INVALID, "the design's weights are not kept");
+            HIP_TRY(h, hipMemcpyAsync(k.W + off[i], src[i]->data(), len[i] * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        }
+        at[i] = k.W + off[i];
+    }
+    k.on_device |= need;
+    d = KeptDev{at[0], at[1], at[2], at[3]};
+    return ALMPC_OK;
+}
+
 // Device copies of the weights the structured solve uses (R with the reference's branch rule applied: zero if R[1,1] == 0)
 int riccati_weights(almpc_handle* h, const hm::mat& Qm, const hm::mat& Rm, const double* Pshared) {
     const int n = h->n, m = h->m;
     hm::mat Qs = hm::symmetrised(Qm.data(), n), Rs = hm::symmetrised(Rm.data(), m);
     if (Rm[0] == 0.0) std::fill(Rs.begin(), Rs.end(), 0.0);
-    h->cert.useR = Rm[0] != 0.0;
     HIP_TRY(h, h->rQ.once((size_t)n * n));
     HIP_TRY(h, h->rR.once((size_t)m * m));
     HIP_TRY(h, hipMemcpy(h->rQ, Qs.data(), Qs.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -1168,7 +1197,7 @@ hipError_t stream_wait_polling(almpc_handle* h) {
 }
 
 // The primal Riccati active set can redo this design: an input box alone, no input-rate weight, riccati_weights() done
-bool primal_redo_ready(const almpc_handle* h) { return h->mc == 0 && !h->useS && h->rKst; }
+bool primal_redo_ready(const almpc_handle* h) { return h->mc == 0 && !h->kept.useS && h->rKst; }
 
 // The redo of the instances a condensed step left undecided, from the step's own result: k_sdual (behind k_sgains for per-instance
 // models, whose last step's models are still in the model slots) and / or k_riccati, as the caller says and the design allows.
@@ -1243,8 +1272,9 @@ int wait_and_settle(almpc_handle* h, bool blocking_only = false) {
 
 // A new design voids a redo that was deferred for a step of the previous one (its models, references and results are about to go)
 void drop_lazy_redo(almpc_handle* h) {
-    h->sens.stepped = false; h->sens.v_ok = false; h->sens.t1_ok = false; h->sens.w_ok = false; h->sens.s_ok = false; h->sens.have = 0;   // (what a sensitivity call looks at goes with the design as well)
-    h->cert.have = 0; h->cert.w_ok = false; h->cert.have_ltv = 0; h->cert.kept = false;
+    h->sens.stepped = false; h->sens.v_ok = false; h->sens.t1_ok = false; h->sens.have = 0;   // (what a sensitivity call looks at goes with the design as well)
+    h->cert.have = 0; h->cert.kept = false;
+    h->kept.on_device = 0;
     h->redo.lazy_pending = false;
     h->redo.expected = false;
     h->weighted = false;   // (almpc_design_batched_weighted sets it again behind this call)
@@ -1582,7 +1612,7 @@ static int design_shared_structured(almpc_handle* h, const double* A, const doub
         for (int i = 0; i < n; ++i)
             if (!(xmin[i] <= xmax[i])) return fail(h, ALMPC_ERR_INVALID, "design: xmin > xmax");
     h->r_has_step = false; h->guess_ready = false;
-    ALMPC_TRY(begin_redesign(h, DROP_SQP));   // (an SQP loop set up on this handle is gone with its per-instance reference buffers)
+    ALMPC_TRY(begin_redesign(h, DROP_SQP | DROP_RELIN));   // (an SQP loop or pipeline set up on this handle is gone with its references)
     hm::mat Am(A, A + (size_t)n * n), Bm(B, B + (size_t)n * m), Qm(Q, Q + (size_t)n * n), Rm(R, R + (size_t)m * m), Pm;
     if (P) Pm.assign(P, P + (size_t)n * n);
     else if (!hm::dare(Am, Bm, Qm, Rm, n, m, Pm)) return fail(h, ALMPC_ERR_NUMERIC, "design: DARE did not converge");
@@ -1597,8 +1627,7 @@ static int design_shared_structured(almpc_handle* h, const double* A, const doub
     HIP_TRY(h, hipMemcpy(h->dA, A, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->dB, B, (size_t)n * m * sizeof(double), hipMemcpyHostToDevice));
     h->batched = false; h->ltv = false; h->r_batched_P = false; h->rP_stride = 0;
-    h->hS.assign((size_t)m * m, 0.0); h->useS = useS ? 1 : 0;
-    if (useS) h->hS = Sm;
+    keep_weights(h, nullptr, nullptr, useS ? Sm : hm::mat((size_t)m * m, 0.0), R[0] != 0.0, useS);
     h->has_box = xmin ? 1 : 0;
     h->designed = true;
     return set_zero_reference(h);
@@ -1677,9 +1706,7 @@ static int design_shared_condensed(almpc_handle* h, const double* A, const doubl
     else if (!hm::dare(Am, Bm, Qm, Rm, n, m, Pm)) return fail(h, ALMPC_ERR_NUMERIC, "design: DARE did not converge");
     h->P = Pm;
     const hm::mat Sm = hm::symmetrised(S, m);   // S enters the cost as a quadratic form: only its symmetric part counts
-    h->hS = Sm;
-    h->useS = (Rm[0] != 0.0 && Sm[0] != 0.0) ? 1 : 0;  // the reference drops the S term together with R (src/sub/design_mpc.jl:423-466)
-    h->sens.Q = Qm; h->sens.R = Rm; h->sens.useR = Rm[0] != 0.0;
+    keep_weights(h, &Qm, &Rm, Sm, Rm[0] != 0.0, Rm[0] != 0.0 && Sm[0] != 0.0);  // the reference drops the S term together with R (src/sub/design_mpc.jl:423-466)
     h->rho = rho; h->sigma = sigma;
 
     // ---- state rows (state box, terminal equality): row tables and the shared constraint-space matrix
@@ -1703,7 +1730,7 @@ static int design_shared_condensed(almpc_handle* h, const double* A, const doubl
     // redo of the instances a step leaves without a certificate (default on)
     h->sd.ready = false;
     if (h->fallback) {
-        const bool useS = h->useS != 0;
+        const bool useS = h->kept.useS != 0;
         const SharedModel model{Am, Bm, Pm};
         ALMPC_TRY(setup_redo_solvers(h, &model, false, Qm, Rm, useS ? &Sm : nullptr, StateBox{xmin, xmax}, h->fallback == 1,
                                      "structured fallback: state rows / input-rate weight need n + m <= 48 and (N + 1)(n + m) <= 4096"));
@@ -2075,8 +2102,7 @@ int design_batched_structured(almpc_handle* h, const double* A_batch, const doub
     }
     ALMPC_TRY(upload_input_box(h, umin, umax));   // (no umin <= umax check on this route)
     h->P.assign(Pall.begin(), Pall.begin() + (size_t)n * n); h->H.clear(); h->F.clear(); h->d.clear();
-    h->hS.assign((size_t)m * m, 0.0); h->useS = useS ? 1 : 0;
-    if (useS) h->hS = Sm;
+    keep_weights(h, nullptr, nullptr, useS ? Sm : hm::mat((size_t)m * m, 0.0), R[0] != 0.0, useS);
     h->has_box = box.min ? 1 : 0;
     h->designed = true;
     return set_zero_reference(h);
@@ -2135,11 +2161,9 @@ int batched_design_front(almpc_handle* h, const double* A_batch, const double* B
         std::copy(Pm.begin(), Pm.end(), Pall.begin() + i * n * n);
     }
     if (!dev_dare) h->P.assign(Pall.begin(), Pall.begin() + (size_t)n * n);
-    h->hS = Sm;
     h->rho = rho; h->sigma = sigma;
     d.useR = Rm[0] != 0.0; d.useS = d.useR && Sm[0] != 0.0;
-    h->useS = d.useS;
-    h->sens.Q = Qm; h->sens.R = Rm; h->sens.useR = d.useR;
+    keep_weights(h, &Qm, &Rm, Sm, d.useR, d.useS);
     tr("host preparation");
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     tr("stream idle");
@@ -2847,7 +2871,7 @@ int run_step(almpc_handle* h, const almpc_opts& o, StepMode mode) {
     if (rc != ALMPC_OK) return rc;
     h->state_valid = keep_state;   // (recorded only here: every launch of the step went out)
     h->sens.stepped = true; h->sens.have = 0;
-    h->cert.have = 0; h->cert.have_ltv = 0;
+    h->cert.have = 0;
     if (h->io.x0_slot >= 0) {      // the x0 slot of an asynchronous update is free again once this step has finished
         HIP_TRY(h, hipEventRecord(h->io.ev_used[h->io.x0_slot], h->stream));
         h->io.used_pending[h->io.x0_slot] = true;
@@ -2933,11 +2957,12 @@ int almpc_get_weights_instance(almpc_handle* h, int instance, double* Q, double*
     if (instance < 0 || instance >= h->batch) return fail(h, ALMPC_ERR_INVALID, "get_weights_instance: instance out of range");
     const size_t nn = (size_t)h->n * h->n, mm = (size_t)h->m * h->m, i = (size_t)instance;
     if (!h->weighted) {
-        if (h->sens.Q.size() != nn || h->sens.R.size() != mm || h->hS.size() != mm)
+        const almpc_handle::Kept& k = h->kept;
+        if (k.Q.size() != nn || k.R.size() != mm || k.S.size() != mm || h->relin.ready)   // (the pipeline's Q and R are kept for its certificate)
             return fail(h, ALMPC_ERR_UNSUPPORTED, "get_weights_instance: this design keeps no host copy of its weights (condensed almpc_design_shared / _batched do)");
-        if (Q) std::copy(h->sens.Q.begin(), h->sens.Q.end(), Q);
-        if (R) std::copy(h->sens.R.begin(), h->sens.R.end(), R);
-        if (S) std::copy(h->hS.begin(), h->hS.end(), S);
+        if (Q) std::copy(k.Q.begin(), k.Q.end(), Q);
+        if (R) std::copy(k.R.begin(), k.R.end(), R);
+        if (S) std::copy(k.S.begin(), k.S.end(), S);
         return ALMPC_OK;
     }
     HIP_TRY(h, hipSetDevice(h->device));
@@ -3051,7 +3076,7 @@ static int relin_setup_common(almpc_handle* h, int H, int L, int net, int activa
     s.Qm = hm::symmetrised(Q, n); s.Rm = hm::symmetrised(R, m); s.Sm = hm::symmetrised(S, m); s.Pm = hm::symmetrised(P, n);
     almpc_handle::Relin& q = h->relin;
     q.useR = s.Rm[0] != 0.0; q.useS = q.useR && s.Sm[0] != 0.0;
-    q.hQ = s.Qm; q.hR = s.Rm;   // (almpc_relin_fnn_certificate uploads them at its first call)
+    keep_weights(h, &s.Qm, &s.Rm, s.Sm, q.useR != 0, q.useS != 0);
     if (h->structured && !sdual_shape_ok(n, m, N, q.useS != 0))
         return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_setup (structured): n (+ m with an input-rate weight) <= 48, m <= 16 and (N + 1)(n + m) <= 4096");
     q.Q.reset(); q.R.reset(); q.S.reset(); q.gS.reset();   // (the network and ulin are replaced by their uploads below)
@@ -3093,7 +3118,6 @@ static int relin_setup_structured(almpc_handle* h, const RelinSetup& s, const do
     if (riccati_shape_ok(h)) ALMPC_TRY(riccati_weights(h, Qm, Rm, nullptr));
     ALMPC_TRY(upload_input_box(h, umin, umax));
     h->P = Pm; h->H.clear(); h->F.clear(); h->d.clear();
-    h->hS = Sm; h->useS = q.useS;
     h->has_box = box.min ? 1 : 0;
     h->r_has_step = false;
     h->designed = true;
@@ -3134,7 +3158,7 @@ static int relin_setup_condensed(almpc_handle* h, const RelinSetup& s, const dou
     HIP_TRY(h, h->dFS.alloc(b * nz)); HIP_TRY(h, h->dV0S.alloc(b * nz)); h->dCold.reset(); h->cold_ref = false;
     HIP_TRY(h, hipMemset(h->dFS, 0, b * nz * sizeof(double))); HIP_TRY(h, hipMemset(h->dV0S, 0, b * nz * sizeof(double)));
     h->xref_stride = 0; h->uref_stride = 0; h->fS_stride = nz;
-    h->P = Pm; h->hS = Sm; h->useS = q.useS;
+    h->P = Pm;
     h->rho = rho; h->sigma = sigma;
     const StateBox box = state_box(h);
     ALMPC_TRY(setup_state_rows(h, box.min, box.max, true));
@@ -3394,8 +3418,7 @@ static int sqp_net_setup(almpc_handle* h, bool dense, int H, int L, int activati
     }
     q.useR = Rm[0] != 0.0; q.useS = q.useR && Sm[0] != 0.0; q.sP = p_inst ? (long)n * n : 0;
     h->P.assign(Pall.begin(), Pall.begin() + (size_t)n * n);
-    h->hS = Sm;
-    h->useS = q.useS;
+    keep_weights(h, nullptr, nullptr, Sm, q.useR != 0, q.useS != 0);
     h->rho = rho; h->sigma = sigma;
     // state rows (almpc_set_state_box: the box of .../fnn/mpc_modeler_implementation_fnn.jl:146-153; terminal equality): one
     // constraint-space matrix per instance, rebuilt with every iteration's linearisation
@@ -3952,13 +3975,13 @@ int almpc_set_reference(almpc_handle* h, const double* xref, const double* uref,
     HIP_TRY(h, hipMemcpy(h->dUref, uref, cnt * us * sizeof(double), hipMemcpyHostToDevice));
     // fS = d .* (2 D'Sbar D u_ref): the input-rate cost is on u, not e_u (src/sub/design_mpc.jl:423-446)
     // (per-instance weights with an input-rate term: one vector per instance, from S_i, whatever the reference's form)
-    const bool s_inst = h->weighted && h->useS && h->wiS_given;
+    const bool s_inst = h->weighted && h->kept.useS && h->wiS_given;
     const size_t gcnt = s_inst ? (size_t)h->batch : cnt;
     std::vector<double> fS(gcnt * us, 0.0);
-    if (h->useS) {  // S counts only together with R (the reference's branch rule, src/sub/design_mpc.jl:423-466), as in the design kernels
+    if (h->kept.useS) {  // S counts only together with R (the reference's branch rule, src/sub/design_mpc.jl:423-466), as in the design kernels
         for (size_t c = 0; c < gcnt; ++c) {
             const double* ur = uref + (per_instance ? c : 0) * us;
-            const double* Sw = s_inst ? h->hSi + c * m * m : h->hS.data();
+            const double* Sw = s_inst ? h->hSi + c * m * m : h->kept.S.data();
             double* f = fS.data() + c * us;
             for (int i = 0; i + 1 < N; ++i)
                 for (int a = 0; a < m; ++a) {
@@ -3971,7 +3994,7 @@ int almpc_set_reference(almpc_handle* h, const double* xref, const double* uref,
                 for (int r = 0; r < nz; ++r) f[r] *= h->d[r];
         }
     }
-    if (h->batched && !h->useS) {   // no input-rate weight: fS_i = 0 and v0S_i = -G_i fS_i = 0 (no pass over the 0.5 GB of G_i)
+    if (h->batched && !h->kept.useS) {   // no input-rate weight: fS_i = 0 and v0S_i = -G_i fS_i = 0 (no pass over the 0.5 GB of G_i)
         HIP_TRY(h, hipMemsetAsync(h->dFS, 0, fcnt * us * sizeof(double), h->stream));
         HIP_TRY(h, hipMemsetAsync(h->dV0S, 0, fcnt * us * sizeof(double), h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -4606,6 +4629,21 @@ int sens_jacobians(almpc_handle* h, const char* who, bool rows_form, uint32_t wa
     return ALMPC_OK;
 }
 
+// What every VJP is staged with: the loss gradients uploaded (g_x may be null), the result and its |W| words grown, and the four
+// pointers of the kernel's parameters (SensParams, SensFaceParams) set
+template <class Params>
+int sens_vjp_stage(almpc_handle* h, const double* g_u, const double* g_x, Params& p) {
+    const size_t b = (size_t)h->batch, n = (size_t)h->n, xs = n * (h->N + 1);
+    HIP_TRY(h, h->sens.vrows.grow(b)); HIP_TRY(h, h->sens.gx0.grow(b * n)); HIP_TRY(h, h->sens.gu.grow(b * h->nz));
+    HIP_TRY(h, hipMemcpyAsync(h->sens.gu, g_u, b * h->nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (g_x) {
+        HIP_TRY(h, h->sens.gx.grow(b * xs));
+        HIP_TRY(h, hipMemcpyAsync(h->sens.gx, g_x, b * xs * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    p.g_u = h->sens.gu; p.g_x = g_x ? h->sens.gx.get() : nullptr; p.g_x0 = h->sens.gx0; p.rows = h->sens.vrows;
+    return ALMPC_OK;
+}
+
 int sens_vjp(almpc_handle* h, const char* who, bool rows_form, const double* g_u, const double* g_x, double act_tol, double act_tol_x,
              double* g_x0, int32_t* rows_out) {
     ALMPC_TRY(sens_check(h, who, rows_form));
@@ -4614,16 +4652,10 @@ int sens_vjp(almpc_handle* h, const char* who, bool rows_form, const double* g_u
     if (rows) ALMPC_TRY(sens_fits(h, true));
     HIP_TRY(h, hipSetDevice(h->device));
     ALMPC_TRY(wait_and_settle(h));
-    const size_t b = (size_t)h->batch, n = (size_t)h->n, xs = n * (h->N + 1);
+    const size_t b = (size_t)h->batch, n = (size_t)h->n;
     SensParams p;
     ALMPC_TRY(sens_params(h, act_tol, p, rows, act_tol_x));
-    HIP_TRY(h, h->sens.vrows.grow(b)); HIP_TRY(h, h->sens.gx0.grow(b * n)); HIP_TRY(h, h->sens.gu.grow(b * h->nz));
-    HIP_TRY(h, hipMemcpyAsync(h->sens.gu, g_u, b * h->nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (g_x) {
-        HIP_TRY(h, h->sens.gx.grow(b * xs));
-        HIP_TRY(h, hipMemcpyAsync(h->sens.gx, g_x, b * xs * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    }
-    p.g_u = h->sens.gu; p.g_x = g_x ? h->sens.gx.get() : nullptr; p.g_x0 = h->sens.gx0; p.rows = h->sens.vrows;
+    ALMPC_TRY(sens_vjp_stage(h, g_u, g_x, p));
     if (rows) ALMPC_TRY((sens_launch<true, true>(h, p)));
     else ALMPC_TRY((sens_launch<true, false>(h, p)));
     HIP_TRY(h, hipMemcpyAsync(g_x0, h->sens.gx0, b * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -4632,118 +4664,120 @@ int sens_vjp(almpc_handle* h, const char* who, bool rows_form, const double* g_u
     return ALMPC_OK;
 }
 
-// almpc_sensitivity_params_vjp: k_sens_pz (the VJP with z, nu and the bound gradients), then k_sens_params where a group behind the
-// stage recursions is wanted; only the wanted groups are computed and copied.
+// ---- almpc_sensitivity_params_vjp: k_sens_pz (the VJP with z, nu and the bound gradients), then k_sens_params where a group behind
+// the stage recursions is wanted; only the wanted groups are computed and copied.
 // follow_dare (almpc_sensitivity_params_vjp_dare): k_sens_params also computes dL/dP, and one launch of k_dare_vjp adds what the loss
 // gains through P_i = DARE(A_i, B_i, Q, R) to the Q, R, A, B groups in sens.pout, in front of the copies back.
-int sens_params_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, const almpc_param_grads* out,
-                    bool follow_dare = false, int32_t* dare_status = nullptr) {
-    const char* who = follow_dare ? "sensitivity_params_vjp_dare" : "sensitivity_params_vjp";
+
+// What the call can look at and be asked for, and the dynamic LDS of all three kernels, in front of everything it enqueues
+int sens_params_vjp_check(almpc_handle* h, const char* who, bool follow_dare, const double* g_u, const almpc_param_grads* out) {
     ALMPC_TRY(sens_check(h, who));
-    if (!g_u || !out) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": null g_u or out");
+    const std::string w(who);
+    if (!g_u || !out) return fail(h, ALMPC_ERR_INVALID, w + ": null g_u or out");
+    const size_t n = (size_t)h->n, m = (size_t)h->m;
     if (follow_dare) {
-        if (!h->sens.useR) return fail(h, ALMPC_ERR_UNSUPPORTED, std::string(who) + ": the design dropped R (R[1,1] == 0): there is no DARE to follow");
-        if (h->n > DARE_MAX_N || h->m > DARE_MAX_M) return fail(h, ALMPC_ERR_UNSUPPORTED, std::string(who) + ": n <= 48 and m <= 16 (k_dare_vjp)");
-        if (h->sens.R.size() != (size_t)h->m * h->m) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": the design's weights are not kept");
+        if (!h->kept.useR) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the design dropped R (R[1,1] == 0): there is no DARE to follow");
+        if (h->n > DARE_MAX_N || h->m > DARE_MAX_M) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": n <= 48 and m <= 16 (k_dare_vjp)");
+        if (h->kept.R.size() != m * m) return fail(h, ALMPC_ERR_INVALID, w + ": the design's weights are not kept");
     }
-    const bool chain = follow_dare && (out->Q || out->R || out->A || out->B);   // (a group the DARE reaches)
-    const bool want2 = out->u_ref || out->Q || out->P || out->A || out->R || out->S || out->B;   // (a group of k_sens_params)
-    if (!want2 && !out->x0 && !out->f && !out->u_min && !out->u_max && !out->rows)
-        return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": every pointer of out is null");
-    const int ni = h->n, mi = h->m, nz = h->nz, nzs = h->nzs;
-    if (h->sens.Q.size() != (size_t)ni * ni || h->hS.size() != (size_t)mi * mi || (!h->batched && h->P.size() != (size_t)ni * ni))
-        return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": the design's weights are not kept");
-    // the dynamic LDS of all three kernels, in front of everything the call enqueues
-    const size_t lds1 = (size_t)SENS_WAVES * sens_pz_lds_doubles(ni, nzs, SENS_CAP1) * sizeof(double);
-    const size_t lds2 = nz > SENS_CAP1 ? (size_t)sens_pz_lds_doubles(ni, nzs, nz) * sizeof(double) : 0;
-    const size_t lds3 = (size_t)sens_grad_lds_doubles(ni) * sizeof(double);
-    if (lds1 > 160 * 1024 || lds2 > 160 * 1024 || lds3 > 160 * 1024)
-        return fail(h, ALMPC_ERR_UNSUPPORTED, std::string(who) + ": the working set does not fit LDS");
-    HIP_TRY(h, hipSetDevice(h->device));
-    ALMPC_TRY(wait_and_settle(h));
-    const size_t b = (size_t)h->batch, n = (size_t)ni, m = (size_t)mi, xs = n * (h->N + 1);
-    SensParams p;
-    ALMPC_TRY(sens_params(h, act_tol, p));
-    HIP_TRY(h, h->sens.vrows.grow(b)); HIP_TRY(h, h->sens.gx0.grow(b * n)); HIP_TRY(h, h->sens.gu.grow(b * nz));
-    HIP_TRY(h, h->sens.pz.grow(b * (2 * (size_t)nz + 2 * m)));
-    HIP_TRY(h, hipMemcpyAsync(h->sens.gu, g_u, b * nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (g_x) {
-        HIP_TRY(h, h->sens.gx.grow(b * xs));
-        HIP_TRY(h, hipMemcpyAsync(h->sens.gx, g_x, b * xs * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    }
-    p.g_u = h->sens.gu; p.g_x = g_x ? h->sens.gx.get() : nullptr; p.g_x0 = h->sens.gx0; p.rows = h->sens.vrows;
-    p.z = h->sens.pz; p.nu = p.z + b * nz; p.gmin = p.nu + b * nz; p.gmax = p.gmin + b * m;
-    // the two tiers, as sens_launch
+    if (!out->u_ref && !out->Q && !out->P && !out->A && !out->R && !out->S && !out->B && !out->x0 && !out->f && !out->u_min && !out->u_max && !out->rows)
+        return fail(h, ALMPC_ERR_INVALID, w + ": every pointer of out is null");
+    if (h->kept.Q.size() != n * n || h->kept.S.size() != m * m || (!h->batched && h->P.size() != n * n))
+        return fail(h, ALMPC_ERR_INVALID, w + ": the design's weights are not kept");
+    const size_t lds1 = (size_t)SENS_WAVES * sens_pz_lds_doubles(h->n, h->nzs, SENS_CAP1) * sizeof(double);
+    const size_t lds2 = h->nz > SENS_CAP1 ? (size_t)sens_pz_lds_doubles(h->n, h->nzs, h->nz) * sizeof(double) : 0;
+    const size_t lds3 = (size_t)sens_grad_lds_doubles(h->n) * sizeof(double);
+    if (lds1 > 160 * 1024 || lds2 > 160 * 1024 || lds3 > 160 * 1024) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the working set does not fit LDS");
+    return ALMPC_OK;
+}
+
+// k_sens_pz's two tiers, as sens_launch
+int sens_pz_launch(almpc_handle* h, SensParams p) {
+    const int n = h->n, nz = h->nz, nzs = h->nzs;
     HIP_TRY(h, hipMemsetAsync(h->sens.ovf, 0, SENS_OVF_HEAD * sizeof(int32_t), h->stream));
-    p.cap = SENS_CAP1; p.lds_per_team = sens_pz_lds_doubles(ni, nzs, p.cap);
+    p.cap = SENS_CAP1; p.lds_per_team = sens_pz_lds_doubles(n, nzs, p.cap);
+    const size_t lds1 = (size_t)SENS_WAVES * p.lds_per_team * sizeof(double);
     HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens_pz<false>), lds1));
     hipLaunchKernelGGL((k_sens_pz<false>), dim3((unsigned)((h->batch + SENS_WAVES - 1) / SENS_WAVES)), dim3(64 * SENS_WAVES), lds1, h->stream, p);
     HIP_TRY(h, hipGetLastError());
     if (nz > SENS_CAP1) {
-        p.cap = nz; p.lds_per_team = sens_pz_lds_doubles(ni, nzs, p.cap);
-        HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens_pz<true>), lds2));
-        hipLaunchKernelGGL((k_sens_pz<true>), dim3((unsigned)std::min(h->batch, 4 * h->num_cus)), dim3(SENS_WG), lds2, h->stream, p);
+        p.cap = nz; p.lds_per_team = sens_pz_lds_doubles(n, nzs, p.cap);
+        HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens_pz<true>), p.lds_per_team * sizeof(double)));
+        hipLaunchKernelGGL((k_sens_pz<true>), dim3((unsigned)std::min(h->batch, 4 * h->num_cus)), dim3(SENS_WG), p.lds_per_team * sizeof(double), h->stream, p);
         HIP_TRY(h, hipGetLastError());
     }
-    const size_t off_ur = 0, off_Q = off_ur + b * nz, off_P = off_Q + b * n * n, off_A = off_P + b * n * n, off_R = off_A + b * n * n,
-                 off_S = off_R + b * m * m, off_B = off_S + b * m * m, out_total = off_B + b * n * m;
-    if (want2) {
-        if (!h->sens.w_ok && !h->weighted) {   // (once per design, in stream order in front of k_sens_params; per-instance weights are on the device already)
-            HIP_TRY(h, h->sens.W.grow(2 * n * n + 2 * m * m));
-            if (h->sens.R.size() == m * m)
-                HIP_TRY(h, hipMemcpyAsync(h->sens.W + 2 * n * n + m * m, h->sens.R.data(), m * m * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(h->sens.W, h->sens.Q.data(), n * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(h->sens.W + n * n, h->hS.data(), m * m * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            if (!h->batched) HIP_TRY(h, hipMemcpyAsync(h->sens.W + n * n + m * m, h->P.data(), n * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            h->sens.w_ok = true;
-        }
-        const int grid = std::min(h->batch, 8 * h->num_cus);
-        HIP_TRY(h, h->sens.pout.grow(out_total));
-        HIP_TRY(h, h->sens.traj.grow((size_t)grid * 3 * xs));
-        SensGradParams q = SensGradParams();
-        q.n = ni; q.m = mi; q.N = h->N; q.nz = nz; q.batch = h->batch; q.useR = h->sens.useR; q.useS = h->useS;
-        q.A = p.A; q.A_stride = p.A_stride; q.B = p.B; q.B_stride = p.B_stride;
-        q.Q = h->sens.W; q.S = h->sens.W + n * n;
-        if (h->weighted) { q.Q = h->wiQ; q.Q_stride = (long)(n * n); q.S = h->useS ? h->wiS.get() : nullptr; q.S_stride = h->useS ? (long)(m * m) : 0; }
-        if (h->batched) { q.P = h->bP; q.P_stride = h->bP_stride; }
-        else { q.P = h->sens.W + n * n + m * m; q.P_stride = 0; }
-        q.ex = h->dEx; q.ev = h->dEu; q.u = h->dU; q.g_u = p.g_u; q.g_x = p.g_x; q.z = p.z; q.nu = p.nu; q.rows = p.rows;
-        q.traj = h->sens.traj;
-        double* o = h->sens.pout;
-        q.gur = out->u_ref ? o + off_ur : nullptr; q.gQ = out->Q ? o + off_Q : nullptr; q.gP = (out->P || chain) ? o + off_P : nullptr;
-        q.gA = out->A ? o + off_A : nullptr; q.gR = out->R ? o + off_R : nullptr; q.gS = out->S ? o + off_S : nullptr;
-        q.gB = out->B ? o + off_B : nullptr;
-        HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens_params), lds3));
-        hipLaunchKernelGGL(k_sens_params, dim3((unsigned)grid), dim3(256), lds3, h->stream, q);
-        HIP_TRY(h, hipGetLastError());
-        if (chain) {
-            HIP_TRY(h, h->sens.dstat.grow(b));
-            HIP_TRY(h, hipMemsetAsync(h->sens.dstat, 0, b * sizeof(int32_t), h->stream));   // (an instance with rows < 0 is skipped: 0)
-            DareVjpParams vp;
-            vp.n = ni; vp.m = mi; vp.batch = h->batch;
-            vp.A = q.A; vp.A_stride = q.A_stride; vp.B = q.B; vp.B_stride = q.B_stride; vp.P = q.P; vp.P_stride = q.P_stride;
-            vp.gP = o + off_P; vp.gP_stride = (long)(n * n);
-            vp.Q = h->sens.W; vp.R = h->sens.W + 2 * n * n + m * m;
-            if (h->weighted) { vp.Q = h->wiQ; vp.Q_stride = (long)(n * n); vp.R = h->wiR; vp.R_stride = (long)(m * m); }
-            vp.gA = q.gA; vp.gA_stride = (long)(n * n); vp.gB = q.gB; vp.gB_stride = (long)(n * m);
-            vp.gQ = q.gQ; vp.gQ_stride = (long)(n * n); vp.gR = q.gR; vp.gR_stride = (long)(m * m);
-            vp.accumulate = 1; vp.rows = p.rows; vp.status = h->sens.dstat; vp.lds_per_wave = 0;
-            HIP_TRY(h, launch_dare_vjp(vp, h->stream));
-        }
+    return ALMPC_OK;
+}
+
+// k_sens_params' outputs in sens.pout: u_ref, Q, P, A, R, S, B, each [batch][its size]
+struct ParamGradLayout {
+    size_t ur, Q, P, A, R, S, B, total;
+    ParamGradLayout(size_t b, size_t n, size_t m, size_t nz)
+        : ur(0), Q(ur + b * nz), P(Q + b * n * n), A(P + b * n * n), R(A + b * n * n), S(R + b * m * m), B(S + b * m * m), total(B + b * n * m) {}
+};
+
+// k_sens_params behind k_sens_pz's z, nu and rows: the wanted groups (with_gP: dL/dP whether or not it is wanted, for the DARE chain).
+// The shared weights are the handle's kept ones; per-instance weights are on the device already.
+int sens_params_launch(almpc_handle* h, const SensParams& p, const almpc_param_grads* out, bool with_gP, const ParamGradLayout& L, SensGradParams& q) {
+    const size_t n = (size_t)h->n, m = (size_t)h->m, xs = n * (h->N + 1);
+    KeptDev w;
+    ALMPC_TRY(kept_on_device(h, h->weighted ? 0u : KEPT_Q | KEPT_S | (h->kept.R.size() == m * m ? KEPT_R : 0u) | (h->batched ? 0u : KEPT_P), w));
+    const int grid = std::min(h->batch, 8 * h->num_cus);
+    HIP_TRY(h, h->sens.pout.grow(L.total));
+    HIP_TRY(h, h->sens.traj.grow((size_t)grid * 3 * xs));
+    q = SensGradParams();
+    q.n = h->n; q.m = h->m; q.N = h->N; q.nz = h->nz; q.batch = h->batch; q.useR = h->kept.useR; q.useS = h->kept.useS;
+    q.A = p.A; q.A_stride = p.A_stride; q.B = p.B; q.B_stride = p.B_stride; q.Q = w.Q; q.S = w.S;
+    if (h->weighted) { q.Q = h->wiQ; q.Q_stride = (long)(n * n); q.S = h->kept.useS ? h->wiS.get() : nullptr; q.S_stride = h->kept.useS ? (long)(m * m) : 0; }
+    if (h->batched) { q.P = h->bP; q.P_stride = h->bP_stride; }
+    else { q.P = w.P; q.P_stride = 0; }
+    q.ex = h->dEx; q.ev = h->dEu; q.u = h->dU; q.g_u = p.g_u; q.g_x = p.g_x; q.z = p.z; q.nu = p.nu; q.rows = p.rows; q.traj = h->sens.traj;
+    double* o = h->sens.pout;
+    q.gur = out->u_ref ? o + L.ur : nullptr; q.gQ = out->Q ? o + L.Q : nullptr; q.gP = (out->P || with_gP) ? o + L.P : nullptr;
+    q.gA = out->A ? o + L.A : nullptr; q.gR = out->R ? o + L.R : nullptr; q.gS = out->S ? o + L.S : nullptr; q.gB = out->B ? o + L.B : nullptr;
+    const size_t lds = (size_t)sens_grad_lds_doubles(h->n) * sizeof(double);
+    HIP_TRY(h, ensure_dyn_lds(reinterpret_cast<const void*>(k_sens_params), lds));
+    hipLaunchKernelGGL(k_sens_params, dim3((unsigned)grid), dim3(256), lds, h->stream, q);
+    HIP_TRY(h, hipGetLastError());
+    return ALMPC_OK;
+}
+
+// The DARE chain behind it (launch: a group the DARE reaches is wanted, and q is k_sens_params' launch): k_dare_vjp on dL/dP (at gP_at of sens.pout),
+// added to the Q, R, A, B groups of q.  Then its status words, in front of the copies back: without dare_status a refused instance
+// fails the call, and nothing is copied out.
+int sens_dare_chain(almpc_handle* h, const char* who, bool launch, const SensGradParams& q, size_t gP_at, int32_t* dare_status) {
+    const size_t b = (size_t)h->batch, n = (size_t)h->n, m = (size_t)h->m;
+    std::vector<int32_t> stt(b, 0);
+    if (launch) {
+        HIP_TRY(h, h->sens.dstat.grow(b));
+        HIP_TRY(h, hipMemsetAsync(h->sens.dstat, 0, b * sizeof(int32_t), h->stream));   // (an instance with rows < 0 is skipped: 0)
+        KeptDev w;
+        ALMPC_TRY(kept_on_device(h, h->weighted ? 0u : KEPT_Q | KEPT_R, w));
+        DareVjpParams vp;
+        vp.n = h->n; vp.m = h->m; vp.batch = h->batch;
+        vp.A = q.A; vp.A_stride = q.A_stride; vp.B = q.B; vp.B_stride = q.B_stride; vp.P = q.P; vp.P_stride = q.P_stride;
+        vp.gP = h->sens.pout + gP_at; vp.gP_stride = (long)(n * n);
+        vp.Q = w.Q; vp.R = w.R;
+        if (h->weighted) { vp.Q = h->wiQ; vp.Q_stride = (long)(n * n); vp.R = h->wiR; vp.R_stride = (long)(m * m); }
+        vp.gA = q.gA; vp.gA_stride = (long)(n * n); vp.gB = q.gB; vp.gB_stride = (long)(n * m);
+        vp.gQ = q.gQ; vp.gQ_stride = (long)(n * n); vp.gR = q.gR; vp.gR_stride = (long)(m * m);
+        vp.accumulate = 1; vp.rows = q.rows; vp.status = h->sens.dstat; vp.lds_per_wave = 0;
+        HIP_TRY(h, launch_dare_vjp(vp, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(stt.data(), h->sens.dstat, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, stream_wait_polling(h));
     }
-    if (follow_dare) {   // the status words first: without dare_status a refused instance fails the call, and nothing is copied out
-        std::vector<int32_t> stt(b, 0);
-        if (chain) {
-            HIP_TRY(h, hipMemcpyAsync(stt.data(), h->sens.dstat, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, stream_wait_polling(h));
-        }
-        if (dare_status) std::copy(stt.begin(), stt.end(), dare_status);
-        else
-            for (size_t i = 0; i < b; ++i)
-                if (stt[i] != 0)
-                    return fail(h, ALMPC_ERR_NUMERIC, std::string(who) + ": the terminal weight of instance " + std::to_string(i) +
-                                " is not the stabilising DARE solution of its model (k_dare_vjp status " + std::to_string(stt[i]) + ")");
-    }
+    if (dare_status) std::copy(stt.begin(), stt.end(), dare_status);
+    else
+        for (size_t i = 0; i < b; ++i)
+            if (stt[i] != 0)
+                return fail(h, ALMPC_ERR_NUMERIC, std::string(who) + ": the terminal weight of instance " + std::to_string(i) +
+                            " is not the stabilising DARE solution of its model (k_dare_vjp status " + std::to_string(stt[i]) + ")");
+    return ALMPC_OK;
+}
+
+// The wanted groups back to the host (pout: k_sens_params ran), and the wait
+int sens_params_back(almpc_handle* h, const almpc_param_grads* out, const SensParams& p, const double* pout, const ParamGradLayout& L) {
+    const size_t b = (size_t)h->batch, n = (size_t)h->n, m = (size_t)h->m, nz = (size_t)h->nz;
     const auto back = [&](double* dst, const double* src, size_t count) {
         return dst ? hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToHost, h->stream) : hipSuccess;
     };
@@ -4751,24 +4785,45 @@ int sens_params_vjp(almpc_handle* h, const double* g_u, const double* g_x, doubl
     HIP_TRY(h, back(out->f, p.z, b * nz));
     HIP_TRY(h, back(out->u_min, p.gmin, b * m));
     HIP_TRY(h, back(out->u_max, p.gmax, b * m));
-    if (want2) {
-        const double* o = h->sens.pout;
-        HIP_TRY(h, back(out->u_ref, o + off_ur, b * nz));
-        HIP_TRY(h, back(out->Q, o + off_Q, b * n * n));
-        HIP_TRY(h, back(out->P, o + off_P, b * n * n));
-        HIP_TRY(h, back(out->A, o + off_A, b * n * n));
-        HIP_TRY(h, back(out->R, o + off_R, b * m * m));
-        HIP_TRY(h, back(out->S, o + off_S, b * m * m));
-        HIP_TRY(h, back(out->B, o + off_B, b * n * m));
+    if (pout) {
+        HIP_TRY(h, back(out->u_ref, pout + L.ur, b * nz));
+        HIP_TRY(h, back(out->Q, pout + L.Q, b * n * n));
+        HIP_TRY(h, back(out->P, pout + L.P, b * n * n));
+        HIP_TRY(h, back(out->A, pout + L.A, b * n * n));
+        HIP_TRY(h, back(out->R, pout + L.R, b * m * m));
+        HIP_TRY(h, back(out->S, pout + L.S, b * m * m));
+        HIP_TRY(h, back(out->B, pout + L.B, b * n * m));
     }
     if (out->rows) HIP_TRY(h, hipMemcpyAsync(out->rows, h->sens.vrows, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, stream_wait_polling(h));
     return ALMPC_OK;
 }
 
+int sens_params_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, const almpc_param_grads* out,
+                    bool follow_dare = false, int32_t* dare_status = nullptr) {
+    const char* who = follow_dare ? "sensitivity_params_vjp_dare" : "sensitivity_params_vjp";
+    ALMPC_TRY(sens_params_vjp_check(h, who, follow_dare, g_u, out));
+    const bool chain = follow_dare && (out->Q || out->R || out->A || out->B);   // (a group the DARE reaches)
+    const bool want2 = out->u_ref || out->Q || out->P || out->A || out->R || out->S || out->B;   // (a group of k_sens_params)
+    HIP_TRY(h, hipSetDevice(h->device));
+    ALMPC_TRY(wait_and_settle(h));
+    const size_t b = (size_t)h->batch, m = (size_t)h->m, nz = (size_t)h->nz;
+    SensParams p;
+    ALMPC_TRY(sens_params(h, act_tol, p));
+    ALMPC_TRY(sens_vjp_stage(h, g_u, g_x, p));
+    HIP_TRY(h, h->sens.pz.grow(b * (2 * nz + 2 * m)));
+    p.z = h->sens.pz; p.nu = p.z + b * nz; p.gmin = p.nu + b * nz; p.gmax = p.gmin + b * m;
+    ALMPC_TRY(sens_pz_launch(h, p));
+    const ParamGradLayout L(b, (size_t)h->n, m, nz);
+    SensGradParams q;
+    if (want2) ALMPC_TRY(sens_params_launch(h, p, out, chain, L, q));
+    if (follow_dare) ALMPC_TRY(sens_dare_chain(h, who, chain, q, L.P, dare_status));
+    return sens_params_back(h, out, p, want2 ? h->sens.pout.get() : nullptr, L);
+}
+
 // ---- the same on a structured handle (k_sens_face, k_sens_face_rate): the Riccati recursion on the face, no condensed operand ----
 // One path for almpc_sensitivity_stagewise[_vjp] (rate false: designs with S = 0) and almpc_sensitivity_stagewise_rate[_vjp] (rate
-// true: with or without S).  k_sens_face_rate runs where the call takes S and the design has it (rate && h->useS); a rate call on a
+// true: with or without S).  k_sens_face_rate runs where the call takes S and the design has it (rate && h->kept.useS); a rate call on a
 // design without S launches k_sens_face on the operands of the plain call: the same bytes.
 
 // What these calls can look at: the last step of a structured design with an input box only
@@ -4779,14 +4834,14 @@ int sens_face_check(almpc_handle* h, const char* who, bool rate) {
     if (!h->structured) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the handle is a condensed one, whose sensitivities come from G = H'^-1 (almpc_sensitivity)");
     if (h->ltv || h->sqp.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": time-varying and SQP designs solve for a step around a trajectory, not for u(x0)");
     if (h->relin.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the re-linearisation pipeline's models depend on x0 themselves");
-    if (!rate && h->useS) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": with an input-rate weight S the stage state is [e_k; v_(k-1)], for which the recursion is not built");
+    if (!rate && h->kept.useS) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": with an input-rate weight S the stage state is [e_k; v_(k-1)], for which the recursion is not built");
     if (h->has_box || h->terminal_eq || (h->sd.ready && (h->sd.has_box || h->sd.has_eq)))
         return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": state rows (state box, terminal equality) are not held on the face of the stage-wise recursion");
     if (!h->rQ || !h->rR || !(h->r_batched_P ? h->bP.get() : h->rP.get()))
         return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the shape is outside the primal stage-wise solver, whose weights the recursion reads (n <= 32, m <= 16, m N <= 1024)");
-    if (rate && h->useS && (h->weighted || h->hS.size() != (size_t)h->m * h->m))
+    if (rate && h->kept.useS && (h->weighted || h->kept.S.size() != (size_t)h->m * h->m))
         return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the design's shared input-rate weight is not kept");
-    const int lds = h->useS ? sens_face_rate_lds_doubles(h->n, h->m, h->N) : sens_face_lds_doubles(h->n, h->m, h->N);   // (useS: a rate call)
+    const int lds = h->kept.useS ? sens_face_rate_lds_doubles(h->n, h->m, h->N) : sens_face_lds_doubles(h->n, h->m, h->N);   // (useS: a rate call)
     if ((size_t)lds * sizeof(double) > (size_t)LDS_BUDGET)
         return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": a stage of the recursion does not fit LDS");
     if (!h->sens.stepped) return fail(h, ALMPC_ERR_INVALID, w + ": no step has run on this design");
@@ -4807,13 +4862,9 @@ int sens_face_params(almpc_handle* h, double act_tol, bool with_S, SensFaceRateP
     p.tau = act_tol > 0.0 ? act_tol : 1e-7;   // (ten times what k_sdual's confirmation leaves a working-set row away from its bound)
     p.lds_per_wave = with_S ? sens_face_rate_lds_doubles(h->n, h->m, h->N) : sens_face_lds_doubles(h->n, h->m, h->N);
     if (!with_S) return ALMPC_OK;
-    const size_t mm = (size_t)h->m * h->m;
-    if (!h->sens.s_ok) {   // (in stream order in front of the kernel)
-        HIP_TRY(h, h->sens.S.grow(mm));
-        HIP_TRY(h, hipMemcpyAsync(h->sens.S, h->hS.data(), mm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        h->sens.s_ok = true;
-    }
-    q.S = h->sens.S;
+    KeptDev w;
+    ALMPC_TRY(kept_on_device(h, KEPT_S, w));
+    q.S = w.S;
     return ALMPC_OK;
 }
 
@@ -4834,7 +4885,7 @@ int sens_face_launch(almpc_handle* h, const SensFaceRateParams& q) {
 int sens_face_jacobians(almpc_handle* h, const char* who, uint32_t want, double act_tol, bool rate) {
     ALMPC_TRY(sens_face_check(h, who, rate));
     if (!want || (want & ~(ALMPC_SENS_K0 | ALMPC_SENS_DU | ALMPC_SENS_DX))) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": want must be a mask of ALMPC_SENS_*");
-    const bool with_S = rate && h->useS;
+    const bool with_S = rate && h->kept.useS;
     HIP_TRY(h, hipSetDevice(h->device));
     ALMPC_TRY(wait_and_settle(h));
     const size_t b = (size_t)h->batch, n = (size_t)h->n;
@@ -4859,19 +4910,13 @@ int sens_face_vjp(almpc_handle* h, const char* who, const double* g_u, const dou
                   bool rate) {
     ALMPC_TRY(sens_face_check(h, who, rate));
     if (!g_u || !g_x0) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": null g_u or g_x0");
-    const bool with_S = rate && h->useS;
+    const bool with_S = rate && h->kept.useS;
     HIP_TRY(h, hipSetDevice(h->device));
     ALMPC_TRY(wait_and_settle(h));
-    const size_t b = (size_t)h->batch, n = (size_t)h->n, xs = n * (h->N + 1);
+    const size_t b = (size_t)h->batch, n = (size_t)h->n;
     SensFaceRateParams q;
     ALMPC_TRY(sens_face_params(h, act_tol, with_S, q));
-    HIP_TRY(h, h->sens.vrows.grow(b)); HIP_TRY(h, h->sens.gx0.grow(b * n)); HIP_TRY(h, h->sens.gu.grow(b * h->nz));
-    HIP_TRY(h, hipMemcpyAsync(h->sens.gu, g_u, b * h->nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (g_x) {
-        HIP_TRY(h, h->sens.gx.grow(b * xs));
-        HIP_TRY(h, hipMemcpyAsync(h->sens.gx, g_x, b * xs * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    }
-    q.f.g_u = h->sens.gu; q.f.g_x = g_x ? h->sens.gx.get() : nullptr; q.f.g_x0 = h->sens.gx0; q.f.rows = h->sens.vrows;
+    ALMPC_TRY(sens_vjp_stage(h, g_u, g_x, q.f));
     ALMPC_TRY(sens_face_launch<true>(h, q));
     HIP_TRY(h, hipMemcpyAsync(g_x0, h->sens.gx0, b * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (rows_out) HIP_TRY(h, hipMemcpyAsync(rows_out, h->sens.vrows, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -4879,74 +4924,108 @@ int sens_face_vjp(almpc_handle* h, const char* who, const double* g_u, const dou
     return ALMPC_OK;
 }
 
-// ---- certificate of the last step (k_cert): cost, KKT residual, input gradient, costates from the returned trajectories ----
-
+// ---- certificate of the last step: cost, KKT residual, input gradient, costates from the returned trajectories and the design ----
+// Three forms on one host path: Plain (almpc_certificate: a time-invariant design, k_cert), Ltv (almpc_certificate_ltv: k_cert_ltv on
+// almpc_design_ltv's kept stage models, also the predicted states), Relin (almpc_relin_fnn_certificate: the pipeline's step is a
+// per-instance time-invariant design, so k_cert on the step's own A_i, B_i, P_i and the setup's weights)
+enum class CertForm { Plain, Ltv, Relin };
 constexpr uint32_t CERT_ALL = ALMPC_CERT_COST | ALMPC_CERT_RES | ALMPC_CERT_GRAD | ALMPC_CERT_COSTATE;
+constexpr uint32_t CERT_LTV_ALL = CERT_ALL | ALMPC_CERT_STATES;
 
-// What the call can look at: the last step of a time-invariant design.  With state rows the trajectory alone determines the cost only.
-int cert_check(almpc_handle* h, uint32_t want) {
+// What a form can look at: the last step of a design of its kind.  With state rows the trajectory alone determines the cost (and
+// the states) only.
+int cert_check(almpc_handle* h, CertForm form, uint32_t want) {
     if (!h) return ALMPC_ERR_INVALID;
-    if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, "certificate before design");
-    if (!want || (want & ~CERT_ALL)) return fail(h, ALMPC_ERR_INVALID, "certificate: want must be a mask of ALMPC_CERT_*");
-    if (h->ltv || h->sqp.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the QP of a time-varying or SQP design has a defect term and a trajectory of its own");
-    if (h->relin.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the re-linearisation pipeline's QP has a defect term and a trajectory of its own");
-    const bool state_rows = h->has_box || h->terminal_eq || h->mc > 0 || (h->sd.ready && (h->sd.has_box || h->sd.has_eq));
-    if (state_rows && (want & ~ALMPC_CERT_COST))
-        return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: with state rows (state box, terminal equality) their multipliers enter the costates, and the trajectory does not determine them: ALMPC_CERT_COST alone is served");
-    if (h->n > CERT_MAX_N || h->m > CERT_MAX_M || (size_t)cert_lds_doubles(h->n, h->m) * sizeof(double) > (size_t)LDS_BUDGET)
-        return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: needs n <= 64, m <= 16 and the operands of an instance in 160 KB of LDS");
-    if (h->structured) {
+    const bool ltv = form == CertForm::Ltv, relin = form == CertForm::Relin;
+    const std::string w(ltv ? "certificate_ltv" : relin ? "relin_fnn_certificate" : "certificate");
+    if (relin ? !h->relin.ready && !h->designed : !h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, w + (relin ? " before relin_fnn_setup" : " before design"));
+    if (!want || (want & ~(ltv ? CERT_LTV_ALL : CERT_ALL)))
+        return fail(h, ALMPC_ERR_INVALID, w + ": want must be a mask of ALMPC_CERT_*" + (ltv ? " and ALMPC_CERT_STATES" : ""));
+    // the design's kind (Ltv: and that it left its stage models)
+    if (ltv) {
+        if (!h->ltv || h->sqp.ready || h->relin.ready)
+            return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate_ltv: the design is not almpc_design_ltv's (time-invariant designs: almpc_certificate; the re-linearisation "
+                                                  "pipeline: almpc_relin_fnn_certificate; the SQP loop has no certificate)");
+        if (!h->cert.kept || !h->lA || !h->lB || (h->cert.kept_c && !h->lC) || !h->cert.xref || !h->cert.uref)
+            return fail(h, ALMPC_ERR_INVALID, "certificate_ltv: the design released its stage models (almpc_set_keep_stage_models(h, 1) before almpc_design_ltv)");
+    } else if (relin) {
+        if (!h->relin.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_certificate: the design is not the re-linearisation pipeline's (almpc_certificate, almpc_certificate_ltv)");
+    } else {
+        if (h->ltv || h->sqp.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the QP of a time-varying or SQP design has a defect term and a trajectory of its own");
+        if (h->relin.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the re-linearisation pipeline's QP has a defect term and a trajectory of its own");
+    }
+    const bool state_rows = h->has_box || h->terminal_eq || h->mc > 0 || (!ltv && h->sd.ready && (h->sd.has_box || h->sd.has_eq));
+    if (state_rows && (want & ~(ALMPC_CERT_COST | (ltv ? ALMPC_CERT_STATES : 0u))))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": with state rows (state box, terminal equality) their multipliers enter the costates, and the trajectory does not determine them: " +
+                                              (ltv ? "ALMPC_CERT_COST and ALMPC_CERT_STATES alone are served" : "ALMPC_CERT_COST alone is served"));
+    if (ltv) {
+        if (h->n > CERT_LTV_MAX_N || h->m > CERT_LTV_MAX_M || (long)(h->N + 1) * (h->n + h->m) > CERT_LTV_MAX_STATES)
+            return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate_ltv: needs n <= 16, m <= 16 and (N + 1)(n + m) <= 1024, the shapes a step of an LTV design runs at");
+    } else if (h->n > CERT_MAX_N || h->m > CERT_MAX_M || (size_t)cert_lds_doubles(h->n, h->m) * sizeof(double) > (size_t)LDS_BUDGET)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": needs n <= 64, m <= 16 and the operands of an instance in 160 KB of LDS");
+    // the weights the form's kernel reads are there (Ltv: batched_design_front left them on the device -- wQ, wR, wS)
+    const almpc_handle::Kept& k = h->kept;
+    const size_t nn = (size_t)h->n * h->n, mm = (size_t)h->m * h->m;
+    if (relin) {
+        if (k.Q.size() != nn || k.R.size() != mm || k.S.size() != mm || !h->bA || !h->bB || !h->bP)
+            return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_certificate: the pipeline's weights and models are not kept");
+    } else if (ltv) {
+    } else if (h->structured) {
         // (a guard: almpc_create gives a structured handle only to the primal stage-wise solver's shapes, and every design of one
         // leaves that solver's weights on the device -- riccati_weights)
         if (!h->rQ || !h->rR || !(h->r_batched_P ? h->bP.get() : h->rP.get()))
             return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the shape is outside the primal stage-wise solver, whose weights the kernel reads (n <= 32, m <= 16, m N <= 1024)");
-        if (h->hS.size() != (size_t)h->m * h->m) return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the design's input-rate weight is not kept");
+        if (k.S.size() != mm) return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the design's input-rate weight is not kept");
     } else if (h->weighted) {
-        if (!h->wiQ || !h->wiR || (h->useS && !(h->wiS_given && h->wiS))) return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the design's per-instance weights are not kept");
-    } else if (h->sens.Q.size() != (size_t)h->n * h->n || h->sens.R.size() != (size_t)h->m * h->m || h->hS.size() != (size_t)h->m * h->m ||
-               (!h->batched && h->P.size() != (size_t)h->n * h->n)) {
+        if (!h->wiQ || !h->wiR || (k.useS && !(h->wiS_given && h->wiS))) return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the design's per-instance weights are not kept");
+    } else if (k.Q.size() != nn || k.R.size() != mm || k.S.size() != mm || (!h->batched && h->P.size() != nn)) {
         return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate: the design's weights are not kept");
     }
-    if (!h->sens.stepped) return fail(h, ALMPC_ERR_INVALID, "certificate: no step has run on this design");
+    if (relin ? !h->relin.have_prev || !h->designed || !h->sens.stepped : !h->sens.stepped)
+        return fail(h, ALMPC_ERR_INVALID, w + (relin ? ": no step has run since relin_fnn_setup" : ": no step has run on this design"));
     return ALMPC_OK;
 }
 
-// Operands of the launch.  Models and per-instance weights are on the device already; the shared weights of a design go there once
-// per design, from the host copies the designs keep (in stream order in front of the kernel).
-int cert_params(almpc_handle* h, CertParams& p) {
+// The wanted outputs of the four both kernels have, grown, into the parameters of either (the LTV form adds x and ex itself)
+template <class Params>
+int cert_outputs(almpc_handle* h, uint32_t want, Params& p) {
+    const size_t b = (size_t)h->batch;
+    almpc_handle::Cert& c = h->cert;
+    if (want & ALMPC_CERT_COST) { HIP_TRY(h, c.cost.grow(b)); p.cost = c.cost; }
+    if (want & ALMPC_CERT_RES) { HIP_TRY(h, c.res.grow(b)); p.res = c.res; }
+    if (want & ALMPC_CERT_GRAD) { HIP_TRY(h, c.grad.grow(b * h->nz)); p.grad = c.grad; }
+    if (want & ALMPC_CERT_COSTATE) { HIP_TRY(h, c.costate.grow(b * (size_t)h->n * (h->N + 1))); p.costate = c.costate; }
+    return ALMPC_OK;
+}
+
+// k_cert's operands.  Models and per-instance weights are on the device already; shared weights are the handle's kept ones (a
+// structured design: the primal stage-wise solver's).  relin: the step's own Jacobians (k_c2d's result with almpc_set_model_time)
+// and P -- one for the batch, or the last step's P_i (almpc_set_terminal_weight) -- in the per-instance slots, the setup's Q, R, S.
+int cert_params(almpc_handle* h, bool relin, uint32_t want, CertParams& p) {
     p = CertParams();
     const size_t n = (size_t)h->n, m = (size_t)h->m, nn = n * n, mm = m * m;
+    const bool riccati = h->structured && !relin;
     p.n = h->n; p.m = h->m; p.N = h->N; p.batch = h->batch;
+    p.useR = h->kept.useR; p.useS = h->kept.useS;
     p.A = h->batched ? h->bA : h->dA; p.A_stride = h->batched ? (long)nn : 0;
     p.B = h->batched ? h->bB : h->dB; p.B_stride = h->batched ? (long)(n * m) : 0;
-    p.useS = h->useS;
-    if (h->structured) {
-        p.useR = h->cert.useR;
+    if (riccati) {
         p.Q = h->rQ; p.R = h->rR;
         p.P = h->r_batched_P ? h->bP : h->rP; p.P_stride = h->r_batched_P ? h->rP_stride : 0;
     } else {
-        p.useR = h->sens.useR;
         if (h->weighted) { p.Q = h->wiQ; p.Q_stride = (long)nn; p.R = h->wiR; p.R_stride = (long)mm; p.S = h->wiS; p.S_stride = (long)mm; }
         if (h->batched) { p.P = h->bP; p.P_stride = h->bP_stride; }
     }
-    const bool up_qr = !h->structured && !h->weighted, up_s = p.useS && !h->weighted, up_p = !h->structured && !h->batched;
-    if ((up_qr || up_s || up_p) && !h->cert.w_ok) {
-        HIP_TRY(h, h->cert.W.grow(2 * nn + 2 * mm));
-        if (up_qr) {
-            HIP_TRY(h, hipMemcpyAsync(h->cert.W, h->sens.Q.data(), nn * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(h->cert.W + nn, h->sens.R.data(), mm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        }
-        if (up_s) HIP_TRY(h, hipMemcpyAsync(h->cert.W + nn + mm, h->hS.data(), mm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        if (up_p) HIP_TRY(h, hipMemcpyAsync(h->cert.W + nn + 2 * mm, h->P.data(), nn * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        h->cert.w_ok = true;
-    }
-    if (up_qr) { p.Q = h->cert.W; p.R = h->cert.W + nn; }
-    if (up_s) p.S = h->cert.W + nn + mm;
-    if (up_p) p.P = h->cert.W + nn + 2 * mm;
+    KeptDev w;
+    ALMPC_TRY(kept_on_device(h, (!riccati && !h->weighted ? KEPT_Q | KEPT_R : 0u) | ((p.useS || relin) && !h->weighted ? KEPT_S : 0u) |
+                                    (!riccati && !h->batched ? KEPT_P : 0u), w));
+    if (w.Q) { p.Q = w.Q; p.R = w.R; }
+    if (w.S) p.S = w.S;
+    if (w.P) p.P = w.P;
     p.umin = h->dUmin; p.umax = h->dUmax;
     p.ex = h->dEx; p.eu = h->dEu; p.u = h->dU;
     p.lds_per_wave = cert_lds_doubles(h->n, h->m);
-    return ALMPC_OK;
+    return cert_outputs(h, want, p);
 }
 
 int cert_launch(almpc_handle* h, const CertParams& p) {
@@ -4958,142 +5037,54 @@ int cert_launch(almpc_handle* h, const CertParams& p) {
     return ALMPC_OK;
 }
 
-int certificate(almpc_handle* h, uint32_t want) {
-    ALMPC_TRY(cert_check(h, want));
-    HIP_TRY(h, hipSetDevice(h->device));
-    ALMPC_TRY(wait_and_settle(h));   // (a synchronous look: the certificate is of the results a caller would read, redone instances included)
-    const size_t b = (size_t)h->batch;
-    h->cert.have = 0;
-    CertParams p;
-    ALMPC_TRY(cert_params(h, p));
-    if (want & ALMPC_CERT_COST) { HIP_TRY(h, h->cert.cost.grow(b)); p.cost = h->cert.cost; }
-    if (want & ALMPC_CERT_RES) { HIP_TRY(h, h->cert.res.grow(b)); p.res = h->cert.res; }
-    if (want & ALMPC_CERT_GRAD) { HIP_TRY(h, h->cert.grad.grow(b * h->nz)); p.grad = h->cert.grad; }
-    if (want & ALMPC_CERT_COSTATE) { HIP_TRY(h, h->cert.costate.grow(b * (size_t)h->n * (h->N + 1))); p.costate = h->cert.costate; }
-    ALMPC_TRY(cert_launch(h, p));
-    HIP_TRY(h, stream_wait_polling(h));
-    h->cert.have = want;
-    return ALMPC_OK;
-}
-
-// ---- ... of a step of a time-varying design (k_cert_ltv): the same four and the predicted states, from u, e_u and the kept stage models ----
-
-constexpr uint32_t CERT_LTV_ALL = CERT_ALL | ALMPC_CERT_STATES;
-
-int cert_ltv_check(almpc_handle* h, uint32_t want) {
-    if (!h) return ALMPC_ERR_INVALID;
-    if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, "certificate_ltv before design");
-    if (!want || (want & ~CERT_LTV_ALL)) return fail(h, ALMPC_ERR_INVALID, "certificate_ltv: want must be a mask of ALMPC_CERT_* and ALMPC_CERT_STATES");
-    if (!h->ltv || h->sqp.ready || h->relin.ready)
-        return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate_ltv: the design is not almpc_design_ltv's (time-invariant designs: almpc_certificate; the re-linearisation "
-                                              "pipeline: almpc_relin_fnn_certificate; the SQP loop has no certificate)");
-    if (!h->cert.kept || !h->lA || !h->lB || (h->cert.kept_c && !h->lC) || !h->cert.xref || !h->cert.uref)
-        return fail(h, ALMPC_ERR_INVALID, "certificate_ltv: the design released its stage models (almpc_set_keep_stage_models(h, 1) before almpc_design_ltv)");
-    const bool state_rows = h->has_box || h->terminal_eq || h->mc > 0;
-    if (state_rows && (want & ~(ALMPC_CERT_COST | ALMPC_CERT_STATES)))
-        return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate_ltv: with state rows (state box, terminal equality) their multipliers enter the costates, and the trajectory does not determine them: ALMPC_CERT_COST and ALMPC_CERT_STATES alone are served");
-    if (h->n > CERT_LTV_MAX_N || h->m > CERT_LTV_MAX_M || (long)(h->N + 1) * (h->n + h->m) > CERT_LTV_MAX_STATES)
-        return fail(h, ALMPC_ERR_UNSUPPORTED, "certificate_ltv: needs n <= 16, m <= 16 and (N + 1)(n + m) <= 1024, the shapes a step of an LTV design runs at");
-    if (!h->sens.stepped) return fail(h, ALMPC_ERR_INVALID, "certificate_ltv: no step has run on this design");
-    return ALMPC_OK;
-}
-
-int certificate_ltv(almpc_handle* h, uint32_t want) {
-    ALMPC_TRY(cert_ltv_check(h, want));
-    HIP_TRY(h, hipSetDevice(h->device));
-    ALMPC_TRY(wait_and_settle(h));
-    const size_t b = (size_t)h->batch, xs = (size_t)h->n * (h->N + 1);
-    h->cert.have_ltv = 0; h->cert.have = 0;   // (the four buffers are shared with almpc_certificate)
+// k_cert_ltv from u, e_u and what the design kept: the stage models, its references and its weights on the device
+int cert_ltv_launch(almpc_handle* h, uint32_t want) {
     CertLtvParams p = CertLtvParams();
     p.n = h->n; p.m = h->m; p.N = h->N; p.batch = h->batch;
-    p.useR = h->sens.useR; p.useS = h->useS;
+    p.useR = h->kept.useR; p.useS = h->kept.useS;
     p.A = h->lA; p.B = h->lB; p.c = h->cert.kept_c ? h->lC.get() : nullptr;
     p.Q = h->wQ; p.R = h->wR; p.S = h->wS;   // (the design's weights, symmetrised: batched_design_front)
     p.P = h->bP; p.P_stride = h->bP_stride;
     p.umin = h->dUmin; p.umax = h->dUmax;
     p.xbar = h->dXref; p.xref = h->cert.xref; p.uref = h->cert.uref;   // (dXref: the design's almpc_set_reference(xbar, ubar, 1))
     p.eu = h->dEu; p.u = h->dU;
-    if (want & ALMPC_CERT_COST) { HIP_TRY(h, h->cert.cost.grow(b)); p.cost = h->cert.cost; }
-    if (want & ALMPC_CERT_RES) { HIP_TRY(h, h->cert.res.grow(b)); p.res = h->cert.res; }
-    if (want & ALMPC_CERT_GRAD) { HIP_TRY(h, h->cert.grad.grow(b * h->nz)); p.grad = h->cert.grad; }
-    if (want & ALMPC_CERT_COSTATE) { HIP_TRY(h, h->cert.costate.grow(b * xs)); p.costate = h->cert.costate; }
-    if (want & ALMPC_CERT_STATES) { HIP_TRY(h, h->cert.x.grow(b * xs)); HIP_TRY(h, h->cert.ex.grow(b * xs)); p.x = h->cert.x; p.ex = h->cert.ex; }
+    ALMPC_TRY(cert_outputs(h, want, p));
+    const size_t xs = (size_t)h->batch * h->n * (h->N + 1);
+    if (want & ALMPC_CERT_STATES) { HIP_TRY(h, h->cert.x.grow(xs)); HIP_TRY(h, h->cert.ex.grow(xs)); p.x = h->cert.x; p.ex = h->cert.ex; }
     p.lds_per_wave = cert_ltv_lds_doubles(h->n, h->N);
     const size_t per_wave = (size_t)p.lds_per_wave * sizeof(double);
     const int waves = waves_in_lds(per_wave, CERT_LTV_WAVES), wgs = capped_grid(h->batch, waves, CERT_LTV_WGS_PER_CU * h->num_cus);
     if (p.c) HIP_TRY(h, LAUNCH_WAVES((k_cert_ltv<true>), wgs, waves, waves * per_wave, h->stream, p));
     else HIP_TRY(h, LAUNCH_WAVES((k_cert_ltv<false>), wgs, waves, waves * per_wave, h->stream, p));
-    HIP_TRY(h, stream_wait_polling(h));
-    h->cert.have_ltv = want;
     return ALMPC_OK;
 }
 
-// ---- ... of a step of the re-linearisation pipeline: a per-instance time-invariant design, so k_cert on the step's own (A_i, B_i, P_i) ----
-
-int relin_certificate(almpc_handle* h, uint32_t want) {
-    if (!h) return ALMPC_ERR_INVALID;
-    almpc_handle::Relin& q = h->relin;
-    if (!q.ready && !h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, "relin_fnn_certificate before relin_fnn_setup");
-    if (!want || (want & ~CERT_ALL)) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_certificate: want must be a mask of ALMPC_CERT_*");
-    if (!q.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_certificate: the design is not the re-linearisation pipeline's (almpc_certificate, almpc_certificate_ltv)");
-    const bool state_rows = h->has_box || h->terminal_eq || h->mc > 0 || (h->sd.ready && (h->sd.has_box || h->sd.has_eq));
-    if (state_rows && (want & ~ALMPC_CERT_COST))
-        return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_certificate: with state rows (state box, terminal equality) their multipliers enter the costates, and the trajectory does not determine them: ALMPC_CERT_COST alone is served");
-    if (h->n > CERT_MAX_N || h->m > CERT_MAX_M || (size_t)cert_lds_doubles(h->n, h->m) * sizeof(double) > (size_t)LDS_BUDGET)
-        return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_certificate: needs n <= 64, m <= 16 and the operands of an instance in 160 KB of LDS");
-    const size_t n = (size_t)h->n, m = (size_t)h->m, nn = n * n, mm = m * m, b = (size_t)h->batch;
-    if (q.hQ.size() != nn || q.hR.size() != mm || h->hS.size() != mm || !h->bA || !h->bB || !h->bP)
-        return fail(h, ALMPC_ERR_UNSUPPORTED, "relin_fnn_certificate: the pipeline's weights and models are not kept");
-    if (!q.have_prev || !h->designed || !h->sens.stepped) return fail(h, ALMPC_ERR_INVALID, "relin_fnn_certificate: no step has run since relin_fnn_setup");
+int certificate(almpc_handle* h, CertForm form, uint32_t want) {
+    ALMPC_TRY(cert_check(h, form, want));
     HIP_TRY(h, hipSetDevice(h->device));
-    ALMPC_TRY(wait_and_settle(h));
-    h->cert.have = 0; h->cert.have_ltv = 0;
-    CertParams p = CertParams();
-    p.n = h->n; p.m = h->m; p.N = h->N; p.batch = h->batch;
-    p.useR = q.useR; p.useS = q.useS;
-    p.A = h->bA; p.A_stride = (long)nn; p.B = h->bB; p.B_stride = (long)(n * m);   // the Jacobians of the last step (k_c2d's result with almpc_set_model_time)
-    p.P = h->bP; p.P_stride = h->bP_stride;                                        // one for the batch, or the last step's P_i (almpc_set_terminal_weight)
-    if (!h->cert.w_ok) {   // the shared weights, once per setup, in stream order in front of the kernel
-        HIP_TRY(h, h->cert.W.grow(2 * nn + 2 * mm));
-        HIP_TRY(h, hipMemcpyAsync(h->cert.W, q.hQ.data(), nn * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->cert.W + nn, q.hR.data(), mm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->cert.W + nn + mm, h->hS.data(), mm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        h->cert.w_ok = true;
+    ALMPC_TRY(wait_and_settle(h));   // (a synchronous look: the certificate is of the results a caller would read, redone instances included)
+    h->cert.have = 0;
+    if (form == CertForm::Ltv) ALMPC_TRY(cert_ltv_launch(h, want));
+    else {
+        CertParams p;
+        ALMPC_TRY(cert_params(h, form == CertForm::Relin, want, p));
+        ALMPC_TRY(cert_launch(h, p));
     }
-    p.Q = h->cert.W; p.R = h->cert.W + nn; p.S = h->cert.W + nn + mm;
-    p.umin = h->dUmin; p.umax = h->dUmax;
-    p.ex = h->dEx; p.eu = h->dEu; p.u = h->dU;
-    p.lds_per_wave = cert_lds_doubles(h->n, h->m);
-    if (want & ALMPC_CERT_COST) { HIP_TRY(h, h->cert.cost.grow(b)); p.cost = h->cert.cost; }
-    if (want & ALMPC_CERT_RES) { HIP_TRY(h, h->cert.res.grow(b)); p.res = h->cert.res; }
-    if (want & ALMPC_CERT_GRAD) { HIP_TRY(h, h->cert.grad.grow(b * h->nz)); p.grad = h->cert.grad; }
-    if (want & ALMPC_CERT_COSTATE) { HIP_TRY(h, h->cert.costate.grow(b * n * (h->N + 1))); p.costate = h->cert.costate; }
-    ALMPC_TRY(cert_launch(h, p));
     HIP_TRY(h, stream_wait_polling(h));
-    h->cert.have = want;
+    h->cert.have = want; h->cert.ltv_form = form == CertForm::Ltv;
     return ALMPC_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int almpc_certificate(almpc_handle* h, uint32_t want) { return certificate(h, want); }
-
-int almpc_set_keep_stage_models(almpc_handle* h, int on) {
+// The getters and the device views of either pair: the last certificate call's buffers, where it was of this form (ltv: the _ltv
+// pair, with x and e_x / d_x and d_ex)
+int get_certificate(almpc_handle* h, bool ltv, double* cost, double* res, double* grad, double* costate, double* x, double* e_x) {
     if (!h) return ALMPC_ERR_INVALID;
-    h->cert.keep = on != 0;
-    return ALMPC_OK;
-}
-
-int almpc_certificate_ltv(almpc_handle* h, uint32_t want) { return certificate_ltv(h, want); }
-
-int almpc_get_certificate_ltv(almpc_handle* h, double* cost, double* res, double* grad, double* costate, double* x, double* e_x) {
-    if (!h) return ALMPC_ERR_INVALID;
+    const std::string w(ltv ? "certificate_ltv" : "certificate");
+    const uint32_t have = h->cert.ltv_form == ltv ? h->cert.have : 0u;
     const uint32_t need = (cost ? ALMPC_CERT_COST : 0u) | (res ? ALMPC_CERT_RES : 0u) | (grad ? ALMPC_CERT_GRAD : 0u) |
                           (costate ? ALMPC_CERT_COSTATE : 0u) | ((x || e_x) ? ALMPC_CERT_STATES : 0u);
-    if (!h->cert.have_ltv || (need & ~h->cert.have_ltv))
-        return fail(h, ALMPC_ERR_INVALID, "get_certificate_ltv: not computed for the last step (almpc_certificate_ltv with these ALMPC_CERT_* bits first)");
+    if (!have || (need & ~have))
+        return fail(h, ALMPC_ERR_INVALID, "get_" + w + ": not computed for the last step (almpc_" + w + " with these ALMPC_CERT_* bits first)");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t b = (size_t)h->batch, xs = (size_t)h->n * (h->N + 1);
     if (cost) HIP_TRY(h, hipMemcpy(cost, h->cert.cost, b * sizeof(double), hipMemcpyDeviceToHost));
@@ -5105,11 +5096,11 @@ int almpc_get_certificate_ltv(almpc_handle* h, double* cost, double* res, double
     return ALMPC_OK;
 }
 
-int almpc_device_certificate_ltv(almpc_handle* h, const double** d_cost, const double** d_res, const double** d_grad, const double** d_costate,
-                                 const double** d_x, const double** d_ex) {
+int device_certificate(almpc_handle* h, bool ltv, const double** d_cost, const double** d_res, const double** d_grad, const double** d_costate,
+                       const double** d_x, const double** d_ex) {
     if (!h) return ALMPC_ERR_INVALID;
-    const uint32_t have = h->cert.have_ltv;
-    if (!have) return fail(h, ALMPC_ERR_INVALID, "device_certificate_ltv: not computed for the last step");
+    const uint32_t have = h->cert.ltv_form == ltv ? h->cert.have : 0u;
+    if (!have) return fail(h, ALMPC_ERR_INVALID, std::string(ltv ? "device_certificate_ltv" : "device_certificate") + ": not computed for the last step");
     if (d_cost) *d_cost = (have & ALMPC_CERT_COST) ? h->cert.cost.get() : nullptr;
     if (d_res) *d_res = (have & ALMPC_CERT_RES) ? h->cert.res.get() : nullptr;
     if (d_grad) *d_grad = (have & ALMPC_CERT_GRAD) ? h->cert.grad.get() : nullptr;
@@ -5119,30 +5110,37 @@ int almpc_device_certificate_ltv(almpc_handle* h, const double** d_cost, const d
     return ALMPC_OK;
 }
 
-int almpc_relin_fnn_certificate(almpc_handle* h, uint32_t want) { return relin_certificate(h, want); }
+}  // namespace
 
-int almpc_get_certificate(almpc_handle* h, double* cost, double* res, double* grad, double* costate) {
+extern "C" {
+
+int almpc_certificate(almpc_handle* h, uint32_t want) { return certificate(h, CertForm::Plain, want); }
+
+int almpc_set_keep_stage_models(almpc_handle* h, int on) {
     if (!h) return ALMPC_ERR_INVALID;
-    const uint32_t need = (cost ? ALMPC_CERT_COST : 0u) | (res ? ALMPC_CERT_RES : 0u) | (grad ? ALMPC_CERT_GRAD : 0u) | (costate ? ALMPC_CERT_COSTATE : 0u);
-    if (!h->cert.have || (need & ~h->cert.have))
-        return fail(h, ALMPC_ERR_INVALID, "get_certificate: not computed for the last step (almpc_certificate with these ALMPC_CERT_* bits first)");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t b = (size_t)h->batch;
-    if (cost) HIP_TRY(h, hipMemcpy(cost, h->cert.cost, b * sizeof(double), hipMemcpyDeviceToHost));
-    if (res) HIP_TRY(h, hipMemcpy(res, h->cert.res, b * sizeof(double), hipMemcpyDeviceToHost));
-    if (grad) HIP_TRY(h, hipMemcpy(grad, h->cert.grad, b * h->nz * sizeof(double), hipMemcpyDeviceToHost));
-    if (costate) HIP_TRY(h, hipMemcpy(costate, h->cert.costate, b * (size_t)h->n * (h->N + 1) * sizeof(double), hipMemcpyDeviceToHost));
+    h->cert.keep = on != 0;
     return ALMPC_OK;
 }
 
+int almpc_certificate_ltv(almpc_handle* h, uint32_t want) { return certificate(h, CertForm::Ltv, want); }
+
+int almpc_relin_fnn_certificate(almpc_handle* h, uint32_t want) { return certificate(h, CertForm::Relin, want); }
+
+int almpc_get_certificate(almpc_handle* h, double* cost, double* res, double* grad, double* costate) {
+    return get_certificate(h, false, cost, res, grad, costate, nullptr, nullptr);
+}
+
+int almpc_get_certificate_ltv(almpc_handle* h, double* cost, double* res, double* grad, double* costate, double* x, double* e_x) {
+    return get_certificate(h, true, cost, res, grad, costate, x, e_x);
+}
+
 int almpc_device_certificate(almpc_handle* h, const double** d_cost, const double** d_res, const double** d_grad, const double** d_costate) {
-    if (!h) return ALMPC_ERR_INVALID;
-    if (!h->cert.have) return fail(h, ALMPC_ERR_INVALID, "device_certificate: not computed for the last step");
-    if (d_cost) *d_cost = (h->cert.have & ALMPC_CERT_COST) ? h->cert.cost.get() : nullptr;
-    if (d_res) *d_res = (h->cert.have & ALMPC_CERT_RES) ? h->cert.res.get() : nullptr;
-    if (d_grad) *d_grad = (h->cert.have & ALMPC_CERT_GRAD) ? h->cert.grad.get() : nullptr;
-    if (d_costate) *d_costate = (h->cert.have & ALMPC_CERT_COSTATE) ? h->cert.costate.get() : nullptr;
-    return ALMPC_OK;
+    return device_certificate(h, false, d_cost, d_res, d_grad, d_costate, nullptr, nullptr);
+}
+
+int almpc_device_certificate_ltv(almpc_handle* h, const double** d_cost, const double** d_res, const double** d_grad, const double** d_costate,
+                                 const double** d_x, const double** d_ex) {
+    return device_certificate(h, true, d_cost, d_res, d_grad, d_costate, d_x, d_ex);
 }
 
 int almpc_sensitivity(almpc_handle* h, uint32_t want, double act_tol) {

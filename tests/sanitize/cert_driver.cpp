@@ -3,7 +3,8 @@
 // UndefinedBehaviorSanitizer and linked against tests/sanitize/fake_hip_runtime.cpp, as host_logic_driver.cpp is (device memory =
 // calloc'd host memory, launches = no-ops, so every buffer the calls size, upload and read back is bounds-checked).  Walks the entry
 // points on condensed (shared, per-instance, weighted) and structured (shared, per-instance) handles with and without S and with R
-// dropped, every `want` mask, null outputs, every refusal, and a group of three.  Prints "cert host logic ok: <launches> launches".
+// dropped, every `want` mask, null outputs, every refusal, a group of three, and the certificate interleaved with the other readers of
+// the handle's kept weights on handles that are redesigned (also with m > n).  Prints "cert host logic ok: <launches> launches".
 #include "../../include/almpc.h"
 
 #include <cstdio>
@@ -105,6 +106,80 @@ static int walk_handle(const char* name, almpc_handle* h, int n, int m, int N, i
     CK(almpc_certificate(h, ALMPC_CERT_COST | ALMPC_CERT_RES));   // (the shared weights are on the device already)
     CK(almpc_get_certificate(h, cost.data(), nullptr, nullptr, nullptr));
     std::printf("%s ok\n", name);
+    return 0;
+}
+
+// The handle's one record of its weights and its one device copy, between readers and between designs: the certificate, every group of
+// the parameter gradients (with and without the DARE followed) and the certificate again on a condensed handle, redesigned with other
+// weights (the readers in the other order), with R dropped, per instance, weighted and per instance again; the certificate between the
+// two structured-handle sensitivity calls, redesigned with another S.  m > n as well: the offsets in the device copy are not symmetric.
+struct Grads {
+    std::vector<double> g_u, g_x, x0, f, u_ref, u_min, u_max, Q, P, A, R, S, B;
+    std::vector<int32_t> rows, dare;
+    almpc_param_grads out;
+    Grads(int n, int m, int N, int b)
+        : g_u((size_t)b * N * m, 0.5), g_x((size_t)b * (N + 1) * n, -0.25), x0((size_t)b * n), f((size_t)b * N * m), u_ref((size_t)b * N * m),
+          u_min((size_t)b * m), u_max((size_t)b * m), Q((size_t)b * n * n), P((size_t)b * n * n), A((size_t)b * n * n), R((size_t)b * m * m),
+          S((size_t)b * m * m), B((size_t)b * n * m), rows(b), dare(b) {
+        std::memset(&out, 0, sizeof out);
+        out.x0 = x0.data(); out.f = f.data(); out.u_ref = u_ref.data(); out.u_min = u_min.data(); out.u_max = u_max.data();
+        out.Q = Q.data(); out.P = P.data(); out.A = A.data(); out.R = R.data(); out.S = S.data(); out.B = B.data(); out.rows = rows.data();
+    }
+};
+
+static int readers(almpc_handle* h, Grads& g, int n, int batch, bool params_first, bool follow_dare) {
+    if (step(h, n, batch)) return 1;
+    if (!params_first) CK(almpc_certificate(h, 15));
+    CK(almpc_sensitivity_params_vjp(h, g.g_u.data(), g.g_x.data(), 0.0, &g.out));
+    if (follow_dare) CK(almpc_sensitivity_params_vjp_dare(h, g.g_u.data(), nullptr, 0.0, &g.out, g.dare.data()));
+    CK(almpc_certificate(h, 15));
+    CK(almpc_get_certificate(h, g.x0.data(), g.u_min.data(), g.f.data(), nullptr));
+    return 0;
+}
+
+static int interleaved(int n, int m, int N, int batch) {
+    almpc_handle* h = nullptr;
+    const Plant p = chain(n, m);
+    Plant q = p;   // other weights: Q2 = 3 Q + a symmetric off-diagonal term, R2 = R / 4, S2 = 2 S, another P
+    for (double& v : q.Q) v *= 3.0;
+    q.Q[1] = q.Q[(size_t)n] = 7.0;
+    for (double& v : q.R) v *= 0.25;
+    for (double& v : q.S) v *= 2.0;
+    for (double& v : q.P) v *= 1.5;
+    std::vector<double> R0 = q.R;
+    R0[0] = 0.0;
+    const std::vector<double> Ab = tiled(p.A, batch), Bb = tiled(p.B, batch), Pb = tiled(p.P, batch);
+    const std::vector<double> Qb = tiled(q.Q, batch), Rb = tiled(q.R, batch), Sb = tiled(q.S, batch);
+    Grads g(n, m, N, batch);
+    CK(almpc_create(&h, n, m, N, batch, 0, 0));
+    CK(almpc_design_shared(h, p.A.data(), p.B.data(), p.Q.data(), p.R.data(), p.S.data(), nullptr, p.umin.data(), p.umax.data(), nullptr, nullptr, 0.1, 1e-6));
+    if (readers(h, g, n, batch, false, true)) return 1;
+    CK(almpc_design_shared(h, q.A.data(), q.B.data(), q.Q.data(), q.R.data(), q.S.data(), q.P.data(), q.umin.data(), q.umax.data(), nullptr, nullptr, 0.1, 1e-6));
+    if (readers(h, g, n, batch, true, true)) return 1;
+    CK(almpc_design_shared(h, q.A.data(), q.B.data(), q.Q.data(), R0.data(), q.S.data(), q.P.data(), q.umin.data(), q.umax.data(), nullptr, nullptr, 0.1, 1e-6));
+    if (readers(h, g, n, batch, false, false)) return 1;
+    REFUSED(almpc_sensitivity_params_vjp_dare(h, g.g_u.data(), nullptr, 0.0, &g.out, g.dare.data()), ALMPC_ERR_UNSUPPORTED);
+    CK(almpc_design_batched(h, Ab.data(), Bb.data(), p.Q.data(), p.R.data(), p.S.data(), Pb.data(), 1, p.umin.data(), p.umax.data(), 0.1, 1e-6));
+    if (readers(h, g, n, batch, false, true)) return 1;
+    CK(almpc_design_batched_weighted(h, Ab.data(), Bb.data(), Qb.data(), Rb.data(), Sb.data(), Pb.data(), 1, p.umin.data(), p.umax.data(), 0.1, 1e-6));
+    if (readers(h, g, n, batch, true, true)) return 1;
+    CK(almpc_design_batched(h, Ab.data(), Bb.data(), p.Q.data(), p.R.data(), p.S.data(), nullptr, 0, p.umin.data(), p.umax.data(), 0.1, 1e-6));
+    if (readers(h, g, n, batch, false, true)) return 1;
+    almpc_destroy(h); h = nullptr;
+    CK(almpc_create(&h, n, m, N, batch, 0, ALMPC_FLAG_STRUCTURED));
+    for (int pass = 0; pass < 2; ++pass) {   // S, then 2 S and the calls in the reverse order
+        const Plant& w = pass ? q : p;
+        CK(almpc_design_shared(h, w.A.data(), w.B.data(), w.Q.data(), w.R.data(), w.S.data(), w.P.data(), w.umin.data(), w.umax.data(), nullptr, nullptr, 0.1, 1e-6));
+        if (step(h, n, batch)) return 1;
+        if (pass) CK(almpc_sensitivity_stagewise_rate_vjp(h, g.g_u.data(), g.g_x.data(), 0.0, g.x0.data(), g.rows.data()));
+        else CK(almpc_sensitivity_stagewise_rate(h, ALMPC_SENS_K0, 0.0));
+        CK(almpc_certificate(h, 15));
+        if (pass) CK(almpc_sensitivity_stagewise_rate(h, ALMPC_SENS_K0 | ALMPC_SENS_DU | ALMPC_SENS_DX, 0.0));
+        else CK(almpc_sensitivity_stagewise_rate_vjp(h, g.g_u.data(), nullptr, 0.0, g.x0.data(), nullptr));
+        CK(almpc_certificate(h, 15));
+    }
+    almpc_destroy(h); h = nullptr;
+    std::printf("interleaved %d-%d-%d ok\n", n, m, N);
     return 0;
 }
 
@@ -275,6 +350,8 @@ int main() {
         CKG(almpc_group_get_certificate(g, nullptr, res.data(), nullptr, nullptr));
         almpc_group_destroy(g);
     }
+    // ---- readers interleaved and handles redesigned; (2, 3, 4): m > n
+    if (interleaved(n, m, N, batch) || interleaved(2, 3, 4, 5)) return 1;
     std::printf("cert host logic ok: %ld launches\n", fake_hip_launch_count());
     return 0;
 }

@@ -265,6 +265,62 @@ int main() {
         CK(almpc_relin_fnn_certificate(h, ALMPC_CERT_COST));
         almpc_destroy(h); h = nullptr;
     }
+    // ---- the pipeline, a plain design and the pipeline again on one handle (also m > n: the offsets in the one device copy of the
+    // weights are not symmetric); then a time-varying design and a plain one: the getters of the form that did not fill the buffers
+    for (int variant = 0; variant < 4; ++variant) {   // condensed | structured, x (5, 2, 9) | (2, 3, 4)
+        const bool wide = variant & 2;
+        const int n2 = wide ? 2 : n, m2 = wide ? 3 : m, N2 = wide ? 4 : N, b2 = wide ? 5 : batch;
+        const Plant w = chain(n2, m2);
+        Plant v = w;
+        for (double& q : v.Q) q *= 3.0;
+        for (double& q : v.S) q *= 0.5;
+        std::vector<double> W2_in((size_t)Hn * (n2 + m2), 0.05), W2_out((size_t)n2 * Hn, 0.1), xr2((size_t)n2 * (N2 + 1), 0.0), ur2((size_t)m2 * N2, 0.0);
+        std::vector<double> x2((size_t)b2 * n2, 0.1), lam2((size_t)b2 * (N2 + 1) * n2), grad2((size_t)b2 * N2 * m2);
+        CK(almpc_create(&h, n2, m2, N2, b2, 0, (variant & 1) ? ALMPC_FLAG_STRUCTURED : 0));
+        for (int pass = 0; pass < 2; ++pass) {
+            const Plant& u = pass ? v : w;
+            CK(almpc_relin_fnn_setup(h, Hn, L, 2, W2_in.data(), W_h.data(), b_h.data(), W2_out.data(), xr2.data(), ur2.data(), u.Q.data(), u.R.data(), u.S.data(),
+                                     u.P.data(), u.umin.data(), u.umax.data(), 0.1, 1e-6));
+            CK(almpc_update_initialization(h, x2.data()));
+            CK(almpc_relin_fnn_step(h, nullptr));
+            CK(almpc_relin_fnn_certificate(h, 15));
+            CK(almpc_get_certificate(h, cost.data(), res.data(), grad2.data(), lam2.data()));
+            REFUSED(almpc_get_certificate_ltv(h, cost.data(), nullptr, nullptr, nullptr, nullptr, nullptr), ALMPC_ERR_INVALID);
+            CK(almpc_relin_fnn_step(h, nullptr));   // (a step's redesign: the weights go to the device again)
+            CK(almpc_relin_fnn_certificate(h, 15));
+            if (pass) break;
+            CK(almpc_design_shared(h, w.A.data(), w.B.data(), v.Q.data(), w.R.data(), v.S.data(), w.P.data(), w.umin.data(), w.umax.data(), nullptr, nullptr, 0.1, 1e-6));
+            CK(almpc_update_initialization(h, x2.data()));
+            CK(almpc_calculate(h, nullptr));
+            REFUSED(almpc_relin_fnn_certificate(h, 15), ALMPC_ERR_UNSUPPORTED);
+            CK(almpc_certificate(h, 15));
+            CK(almpc_get_certificate(h, cost.data(), res.data(), grad2.data(), lam2.data()));
+        }
+        almpc_destroy(h); h = nullptr;
+    }
+    {
+        std::vector<double> x((size_t)batch * (N + 1) * n), xs((size_t)batch * n, 0.25);
+        const double* d[6];
+        CK(almpc_create(&h, n, m, N, batch, 0, 0));
+        CK(almpc_set_keep_stage_models(h, 1));
+        CK(design(h, p, a, 0));
+        CK(almpc_calculate(h, nullptr));
+        CK(almpc_certificate_ltv(h, 31));
+        CK(almpc_get_certificate_ltv(h, cost.data(), res.data(), grad.data(), lam.data(), x.data(), nullptr));
+        REFUSED(almpc_get_certificate(h, cost.data(), nullptr, nullptr, nullptr), ALMPC_ERR_INVALID);
+        REFUSED(almpc_device_certificate(h, &d[0], &d[1], &d[2], &d[3]), ALMPC_ERR_INVALID);
+        CK(almpc_design_shared(h, p.A.data(), p.B.data(), p.Q.data(), p.R.data(), p.S.data(), nullptr, p.umin.data(), p.umax.data(), nullptr, nullptr, 0.1, 1e-6));
+        CK(almpc_update_initialization(h, xs.data()));
+        CK(almpc_calculate(h, nullptr));
+        CK(almpc_certificate(h, 15));
+        CK(almpc_get_certificate(h, cost.data(), res.data(), grad.data(), lam.data()));
+        REFUSED(almpc_get_certificate_ltv(h, cost.data(), nullptr, nullptr, nullptr, nullptr, nullptr), ALMPC_ERR_INVALID);
+        REFUSED(almpc_device_certificate_ltv(h, &d[0], &d[1], &d[2], &d[3], &d[4], &d[5]), ALMPC_ERR_INVALID);
+        CK(almpc_calculate(h, nullptr));   // a new step voids both
+        REFUSED(almpc_get_certificate(h, cost.data(), nullptr, nullptr, nullptr), ALMPC_ERR_INVALID);
+        REFUSED(almpc_get_certificate_ltv(h, cost.data(), nullptr, nullptr, nullptr, nullptr, nullptr), ALMPC_ERR_INVALID);
+        almpc_destroy(h); h = nullptr;
+    }
     // ---- a group of three handles, uneven shards: condensed, structured
     for (int variant = 0; variant < 2; ++variant) {
         almpc_group* g = nullptr;
