@@ -1,5 +1,8 @@
 """ctypes binding of libalmpc.so (include/almpc.h).  The HIP library is the only compute path: if it is
-missing or fails to load this module raises -- there is no CPU fallback."""
+missing or fails to load this module raises -- there is no CPU fallback.
+
+A new entry point is bound by one line of the prototype table below (_HANDLE_CALLS; its name in _GROUP_FORMS too if the header
+has an almpc_group_ form of the same signature) and one method: on _Target if both forms exist, else on Solver or Group."""
 from __future__ import annotations
 
 import ctypes
@@ -44,6 +47,92 @@ class almpc_param_grads(ctypes.Structure):
     _fields_ = [(k, _dp) for k in ("x0", "f", "u_ref", "u_min", "u_max", "Q", "P", "A", "R", "S", "B")] + [("rows", _ip)]
 
 
+# ---- the prototypes of include/almpc.h (tests/test_capi_marshalling.py holds this table against the header)
+_i, _d, _u32 = ctypes.c_int, ctypes.c_double, ctypes.c_uint32
+_cip = ctypes.POINTER(ctypes.c_int)
+_op = ctypes.POINTER(almpc_opts)
+_gp = ctypes.POINTER(almpc_param_grads)
+_vpp = ctypes.POINTER(ctypes.c_void_p)
+_NET = [_i, _i, _i] + [_dp] * 4                      # H, L, activation, W_in, W_h, b_h, W_out
+_BOX = [_dp, _dp, _d, _d]                            # umin, umax, rho, sigma
+_BATCHED = [_dp] * 6 + [_i] + _BOX                   # A, B, Q, R, S, P, P_per_instance, ...
+_SQP_SETUP = _NET + [_dp] * 6 + [_i] + _BOX          # ..., x_ref, u_ref, Q, R, S, P, P_per_instance, ...
+_RELIN_SETUP = _NET + [_dp] * 6 + _BOX
+_VJP = [_dp, _dp, _d, _dp, _ip]                      # g_u, g_x, act_tol, g_x0, rows
+_RESULTS = [_dp] * 4 + [_ip] * 3                     # x, e_x, u, e_u, status, iters, polish_iters
+_RESULTS_U0 = [_dp] * 5 + [_ip] * 3                  # ... with u0 after e_u
+_LINEARIZE = [_i] * 6 + [_dp] * 4 + [_i] + [_dp] * 5
+
+# almpc_<name>(handle, ...): the arguments after the handle
+_HANDLE_CALLS = {
+    "last_error": [], "set_terminal_equality": [_i], "set_rho_profile": [_i], "set_step_fusion": [_i], "set_structured_fallback": [_i],
+    "set_start_from": [_hp], "set_state_box": [_dp, _dp], "set_terminal_weight": [_i], "set_model_time": [_i, _d],
+    "set_keep_stage_models": [_i],
+    "design_shared": [_dp] * 10 + [_d, _d], "design_batched": _BATCHED, "design_batched_weighted": _BATCHED,
+    "design_ltv": [_dp] * 11 + [_i] + _BOX,
+    "get_weights_instance": [_i, _dp, _dp, _dp], "get_design_instance": [_i, _dp, _dp, _dp], "get_gradient_instance": [_i, _dp],
+    "get_terminal_weight_instance": [_i, _dp], "get_model_instance": [_i, _dp, _dp], "get_design": [_dp] * 4,
+    "sqp_fnn_setup": _SQP_SETUP, "sqp_densenet_setup": _SQP_SETUP, "sqp_fnn_start": [_dp, _dp],
+    "sqp_fnn_iterate": [_i, _d, _op, _dp, _dp], "sqp_fnn_solve": [_i, _d, _op, _ip, _ip, _dp], "sqp_fnn_skipped": [_ip],
+    "sqp_fnn_set_step_rule": [_i], "sqp_fnn_set_hessian": [_i], "sqp_fnn_set_row_multipliers": [_i], "sqp_fnn_set_structured": [_i],
+    "sqp_fnn_state_multipliers": [_dp],
+    "relin_fnn_setup": _RELIN_SETUP, "relin_densenet_setup": _RELIN_SETUP, "relin_fnn_step": [_op], "relin_fnn_step_async": [_op],
+    "relin_fnn_advance": [], "relin_fnn_timing": [_fp] * 3, "relin_fnn_terminal_status": [_ip], "relin_fnn_certificate": [_u32],
+    "set_reference": [_dp, _dp, _i], "update_initialization": [_dp], "update_initialization_device": [ctypes.c_void_p],
+    "update_initialization_async": [_dp], "x0_staging": [ctypes.POINTER(_dp)],
+    "calculate": [_op], "calculate_async": [_op], "synchronize": [], "advance_plant": [],
+    "get_results": _RESULTS, "get_results_async": [_u32], "get_results_wait": [_i] + _RESULTS_U0, "host_results": [_i] + [_vpp] * 8,
+    "get_first_input": [_dp], "device_results": [_vpp] * 4,
+    "sensitivity": [_u32, _d], "get_sensitivity": [_dp, _dp, _dp, _ip], "device_sensitivity": [_vpp] * 4, "sensitivity_vjp": _VJP,
+    "sensitivity_rows": [_u32, _d, _d], "sensitivity_rows_vjp": [_dp, _dp, _d, _d, _dp, _ip],
+    "sensitivity_stagewise": [_u32, _d], "sensitivity_stagewise_vjp": _VJP,
+    "sensitivity_stagewise_rate": [_u32, _d], "sensitivity_stagewise_rate_vjp": _VJP,
+    "sensitivity_params_vjp": [_dp, _dp, _d, _gp], "sensitivity_params_vjp_dare": [_dp, _dp, _d, _gp, _ip],
+    "certificate": [_u32], "get_certificate": [_dp] * 4, "device_certificate": [_vpp] * 4,
+    "certificate_ltv": [_u32], "get_certificate_ltv": [_dp] * 6, "device_certificate_ltv": [_vpp] * 6,
+    "get_timing": [_fp] * 4, "timing_reset": [_i], "timing_set_stride": [_i], "timing_summary": [_cip] + [_dp] * 4,
+    "timing_samples": [_i, _cip] + [_fp] * 4,
+    "comm_init": [ctypes.c_char_p, _i, _i], "comm_summary": [ctypes.POINTER(ctypes.c_int64)],
+    "comm_allgather_first_input": [_dp, ctypes.POINTER(_dp)], "debug_poison_lds": [],
+}
+# almpc_group_<name>(group, ...) with the arguments of almpc_<name>(handle, ...)
+_GROUP_FORMS = (
+    "last_error", "set_terminal_equality", "set_rho_profile", "set_structured_fallback", "set_state_box", "set_terminal_weight",
+    "set_model_time", "design_shared", "design_batched", "design_batched_weighted",
+    "sqp_fnn_setup", "sqp_densenet_setup", "sqp_fnn_start", "sqp_fnn_iterate", "sqp_fnn_solve", "sqp_fnn_skipped", "sqp_fnn_set_step_rule",
+    "sqp_fnn_set_hessian", "sqp_fnn_set_row_multipliers", "sqp_fnn_set_structured", "sqp_fnn_state_multipliers",
+    "relin_fnn_setup", "relin_densenet_setup", "relin_fnn_step", "relin_fnn_step_async", "relin_fnn_advance", "relin_fnn_certificate",
+    "set_reference", "update_initialization", "calculate", "calculate_async", "synchronize", "advance_plant",
+    "get_results_async", "get_results_wait",
+    "sensitivity", "get_sensitivity", "sensitivity_vjp", "sensitivity_rows", "sensitivity_rows_vjp", "sensitivity_stagewise",
+    "sensitivity_stagewise_vjp", "sensitivity_stagewise_rate", "sensitivity_stagewise_rate_vjp", "sensitivity_params_vjp",
+    "sensitivity_params_vjp_dare", "certificate", "get_certificate",
+)
+# everything else, by its full name
+_OTHER_CALLS = {
+    "almpc_default_opts": [_op], "almpc_create": [ctypes.POINTER(_hp), _i, _i, _i, _i, _i, _u32], "almpc_destroy": [_hp],
+    "almpc_group_create": [ctypes.POINTER(_hp), _i, _i, _i, _i, _i, _cip, _u32], "almpc_group_destroy": [_hp],
+    "almpc_group_size": [_hp], "almpc_group_handle": [_hp, _i], "almpc_group_shard": [_hp, _i, _cip, _cip],
+    "almpc_group_get_results": [_hp] + _RESULTS_U0, "almpc_group_x0_staging": [_hp, ctypes.POINTER(_dp)],
+    "almpc_group_update_initialization_staged": [_hp, ctypes.POINTER(_dp)],
+    "almpc_dare": [_i, _i] + [_dp] * 5, "almpc_dare_batched": [_i] * 4 + [_dp] * 5 + [_ip],
+    "almpc_dare_vjp": [_i, _i] + [_dp] * 10, "almpc_dare_vjp_batched": [_i] * 4 + [_dp] * 10 + [_ip],
+    "almpc_c2d": [_i, _i, _dp, _dp, _d, _dp, _dp], "almpc_c2d_batched": [_i] * 4 + [_dp, _dp, _d, _dp, _dp, _ip],
+    "almpc_fnn_linearize": _LINEARIZE, "almpc_densenet_linearize": _LINEARIZE, "almpc_comm_unique_id": [ctypes.c_char_p],
+}
+# the return type is int unless named here
+_RESTYPES = {"almpc_default_opts": None, "almpc_destroy": None, "almpc_group_destroy": None, "almpc_last_error": ctypes.c_char_p,
+             "almpc_group_last_error": ctypes.c_char_p, "almpc_group_handle": _hp}
+
+
+def prototypes():
+    """{symbol: argument types} of every function of include/almpc.h this module binds."""
+    table = {"almpc_" + k: [_hp] + v for k, v in _HANDLE_CALLS.items()}
+    table.update({"almpc_group_" + k: [_hp] + _HANDLE_CALLS[k] for k in _GROUP_FORMS})
+    table.update(_OTHER_CALLS)
+    return table
+
+
 def load():
     """Load libalmpc.so and declare the prototypes of include/almpc.h.  Raises OSError if the
     library has not been built (`make lib` or `python -c 'import __graft_entry__ as g; g.build()'`)."""
@@ -53,240 +142,10 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise OSError(f"{LIB_PATH} not found: build the HIP library first (make lib). There is no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    L.almpc_default_opts.argtypes = [ctypes.POINTER(almpc_opts)]
-    L.almpc_default_opts.restype = None
-    L.almpc_create.argtypes = [ctypes.POINTER(_hp), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                               ctypes.c_int, ctypes.c_uint32]
-    L.almpc_destroy.argtypes = [_hp]
-    L.almpc_destroy.restype = None
-    L.almpc_last_error.argtypes = [_hp]
-    L.almpc_last_error.restype = ctypes.c_char_p
-    L.almpc_design_shared.argtypes = [_hp] + [_dp] * 10 + [ctypes.c_double, ctypes.c_double]
-    L.almpc_design_batched.argtypes = [_hp] + [_dp] * 6 + [ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_double]
-    L.almpc_design_batched.restype = ctypes.c_int
-    L.almpc_design_batched_weighted.argtypes = [_hp] + [_dp] * 6 + [ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_double]
-    L.almpc_design_batched_weighted.restype = ctypes.c_int
-    L.almpc_get_weights_instance.argtypes = [_hp, ctypes.c_int, _dp, _dp, _dp]
-    L.almpc_get_weights_instance.restype = ctypes.c_int
-    L.almpc_get_design_instance.argtypes = [_hp, ctypes.c_int, _dp, _dp, _dp]
-    L.almpc_design_ltv.argtypes = [_hp] + [_dp] * 11 + [ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_double]
-    L.almpc_design_ltv.restype = ctypes.c_int
-    L.almpc_get_gradient_instance.argtypes = [_hp, ctypes.c_int, _dp]
-    L.almpc_get_gradient_instance.restype = ctypes.c_int
-    L.almpc_sqp_fnn_setup.argtypes = [_hp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_dp] * 10 + [ctypes.c_int, _dp, _dp,
-                                                                                                     ctypes.c_double, ctypes.c_double]
-    L.almpc_sqp_fnn_setup.restype = ctypes.c_int
-    L.almpc_sqp_densenet_setup.argtypes = L.almpc_sqp_fnn_setup.argtypes
-    L.almpc_sqp_densenet_setup.restype = ctypes.c_int
-    L.almpc_sqp_fnn_start.argtypes = [_hp, _dp, _dp]
-    L.almpc_sqp_fnn_start.restype = ctypes.c_int
-    L.almpc_sqp_fnn_iterate.argtypes = [_hp, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, _dp, _dp]
-    L.almpc_sqp_fnn_iterate.restype = ctypes.c_int
-    L.almpc_sqp_fnn_skipped.argtypes = [_hp, _ip]
-    L.almpc_sqp_fnn_set_step_rule.argtypes = [_hp, ctypes.c_int]
-    L.almpc_sqp_fnn_set_step_rule.restype = ctypes.c_int
-    L.almpc_sqp_fnn_skipped.restype = ctypes.c_int
-    L.almpc_sqp_fnn_solve.argtypes = [_hp, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, _ip, _ip, _dp]
-    L.almpc_sqp_fnn_solve.restype = ctypes.c_int
-    L.almpc_sqp_fnn_set_hessian.argtypes = [_hp, ctypes.c_int]
-    L.almpc_sqp_fnn_set_hessian.restype = ctypes.c_int
-    L.almpc_sqp_fnn_set_row_multipliers.argtypes = [_hp, ctypes.c_int]
-    L.almpc_sqp_fnn_set_row_multipliers.restype = ctypes.c_int
-    L.almpc_sqp_fnn_state_multipliers.argtypes = [_hp, _dp]
-    L.almpc_sqp_fnn_state_multipliers.restype = ctypes.c_int
-    L.almpc_get_design_instance.restype = ctypes.c_int
-    L.almpc_set_reference.argtypes = [_hp, _dp, _dp, ctypes.c_int]
-    L.almpc_set_terminal_equality.argtypes = [_hp, ctypes.c_int]
-    L.almpc_set_state_box.argtypes = [_hp, _dp, _dp]
-    L.almpc_set_state_box.restype = ctypes.c_int
-    L.almpc_sqp_fnn_set_structured.argtypes = [_hp, ctypes.c_int]
-    L.almpc_sqp_fnn_set_structured.restype = ctypes.c_int
-    L.almpc_set_rho_profile.argtypes = [_hp, ctypes.c_int]
-    L.almpc_set_rho_profile.restype = ctypes.c_int
-    L.almpc_set_step_fusion.argtypes = [_hp, ctypes.c_int]
-    L.almpc_set_step_fusion.restype = ctypes.c_int
-    L.almpc_set_terminal_equality.restype = ctypes.c_int
-    L.almpc_update_initialization.argtypes = [_hp, _dp]
-    L.almpc_update_initialization_device.argtypes = [_hp, ctypes.c_void_p]
-    L.almpc_calculate.argtypes = [_hp, ctypes.POINTER(almpc_opts)]
-    L.almpc_calculate_async.argtypes = [_hp, ctypes.POINTER(almpc_opts)]
-    L.almpc_synchronize.argtypes = [_hp]
-    L.almpc_get_results.argtypes = [_hp, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
-    L.almpc_get_design.argtypes = [_hp, _dp, _dp, _dp, _dp]
-    L.almpc_device_results.argtypes = [_hp] + [ctypes.POINTER(ctypes.c_void_p)] * 4
-    L.almpc_get_timing.argtypes = [_hp, _fp, _fp, _fp, _fp]
-    L.almpc_timing_reset.argtypes = [_hp, ctypes.c_int]
-    L.almpc_timing_set_stride.argtypes = [_hp, ctypes.c_int]
-    L.almpc_timing_set_stride.restype = ctypes.c_int
-    L.almpc_debug_poison_lds.argtypes = [_hp]
-    L.almpc_advance_plant.argtypes = [_hp]
-    L.almpc_advance_plant.restype = ctypes.c_int
-    L.almpc_dare.argtypes = [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]
-    L.almpc_dare.restype = ctypes.c_int
-    L.almpc_dare_batched.argtypes = [ctypes.c_int] * 4 + [_dp] * 5 + [_ip]
-    L.almpc_dare_batched.restype = ctypes.c_int
-    L.almpc_dare_vjp.argtypes = [ctypes.c_int, ctypes.c_int] + [_dp] * 10
-    L.almpc_dare_vjp.restype = ctypes.c_int
-    L.almpc_dare_vjp_batched.argtypes = [ctypes.c_int] * 4 + [_dp] * 10 + [_ip]
-    L.almpc_dare_vjp_batched.restype = ctypes.c_int
-    L.almpc_set_terminal_weight.argtypes = [_hp, ctypes.c_int]
-    L.almpc_set_terminal_weight.restype = ctypes.c_int
-    L.almpc_relin_fnn_terminal_status.argtypes = [_hp, _ip]
-    L.almpc_relin_fnn_terminal_status.restype = ctypes.c_int
-    L.almpc_get_terminal_weight_instance.argtypes = [_hp, ctypes.c_int, _dp]
-    L.almpc_get_terminal_weight_instance.restype = ctypes.c_int
-    L.almpc_group_set_terminal_weight.argtypes = [_hp, ctypes.c_int]
-    L.almpc_group_set_terminal_weight.restype = ctypes.c_int
-    L.almpc_c2d.argtypes = [ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double, _dp, _dp]
-    L.almpc_c2d.restype = ctypes.c_int
-    L.almpc_c2d_batched.argtypes = [ctypes.c_int] * 4 + [_dp, _dp, ctypes.c_double, _dp, _dp, _ip]
-    L.almpc_c2d_batched.restype = ctypes.c_int
-    L.almpc_set_model_time.argtypes = [_hp, ctypes.c_int, ctypes.c_double]
-    L.almpc_set_model_time.restype = ctypes.c_int
-    L.almpc_get_model_instance.argtypes = [_hp, ctypes.c_int, _dp, _dp]
-    L.almpc_get_model_instance.restype = ctypes.c_int
-    L.almpc_group_set_model_time.argtypes = [_hp, ctypes.c_int, ctypes.c_double]
-    L.almpc_group_set_model_time.restype = ctypes.c_int
-    L.almpc_sensitivity.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double]
-    L.almpc_get_sensitivity.argtypes = [_hp, _dp, _dp, _dp, _ip]
-    L.almpc_device_sensitivity.argtypes = [_hp] + [ctypes.POINTER(ctypes.c_void_p)] * 4
-    L.almpc_sensitivity_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, _dp, _ip]
-    L.almpc_group_sensitivity.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double]
-    L.almpc_group_get_sensitivity.argtypes = [_hp, _dp, _dp, _dp, _ip]
-    L.almpc_group_sensitivity_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, _dp, _ip]
-    L.almpc_sensitivity_rows.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double]
-    L.almpc_sensitivity_rows_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.c_double, _dp, _ip]
-    L.almpc_group_sensitivity_rows.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double]
-    L.almpc_group_sensitivity_rows_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.c_double, _dp, _ip]
-    L.almpc_sensitivity_params_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.POINTER(almpc_param_grads)]
-    L.almpc_group_sensitivity_params_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.POINTER(almpc_param_grads)]
-    L.almpc_sensitivity_params_vjp_dare.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.POINTER(almpc_param_grads), _ip]
-    L.almpc_group_sensitivity_params_vjp_dare.argtypes = [_hp, _dp, _dp, ctypes.c_double, ctypes.POINTER(almpc_param_grads), _ip]
-    L.almpc_sensitivity_stagewise.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double]
-    L.almpc_sensitivity_stagewise_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, _dp, _ip]
-    L.almpc_group_sensitivity_stagewise.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double]
-    L.almpc_group_sensitivity_stagewise_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, _dp, _ip]
-    L.almpc_sensitivity_stagewise_rate.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double]
-    L.almpc_sensitivity_stagewise_rate_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, _dp, _ip]
-    L.almpc_group_sensitivity_stagewise_rate.argtypes = [_hp, ctypes.c_uint32, ctypes.c_double]
-    L.almpc_group_sensitivity_stagewise_rate_vjp.argtypes = [_hp, _dp, _dp, ctypes.c_double, _dp, _ip]
-    for nm_ in ("almpc_sensitivity", "almpc_get_sensitivity", "almpc_device_sensitivity", "almpc_sensitivity_vjp",
-                "almpc_sensitivity_stagewise", "almpc_sensitivity_stagewise_vjp",
-                "almpc_sensitivity_stagewise_rate", "almpc_sensitivity_stagewise_rate_vjp",
-                "almpc_group_sensitivity_stagewise_rate", "almpc_group_sensitivity_stagewise_rate_vjp",
-                "almpc_group_sensitivity_stagewise", "almpc_group_sensitivity_stagewise_vjp",
-                "almpc_sensitivity_params_vjp", "almpc_group_sensitivity_params_vjp",
-                "almpc_sensitivity_params_vjp_dare", "almpc_group_sensitivity_params_vjp_dare",
-                "almpc_group_sensitivity", "almpc_group_get_sensitivity", "almpc_group_sensitivity_vjp",
-                "almpc_sensitivity_rows", "almpc_sensitivity_rows_vjp", "almpc_group_sensitivity_rows", "almpc_group_sensitivity_rows_vjp"):
-        getattr(L, nm_).restype = ctypes.c_int
-    L.almpc_certificate.argtypes = [_hp, ctypes.c_uint32]
-    L.almpc_get_certificate.argtypes = [_hp, _dp, _dp, _dp, _dp]
-    L.almpc_device_certificate.argtypes = [_hp] + [ctypes.POINTER(ctypes.c_void_p)] * 4
-    L.almpc_group_certificate.argtypes = [_hp, ctypes.c_uint32]
-    L.almpc_group_get_certificate.argtypes = [_hp, _dp, _dp, _dp, _dp]
-    for nm_ in ("almpc_certificate", "almpc_get_certificate", "almpc_device_certificate", "almpc_group_certificate",
-                "almpc_group_get_certificate"):
-        getattr(L, nm_).restype = ctypes.c_int
-    L.almpc_set_keep_stage_models.argtypes = [_hp, ctypes.c_int]
-    L.almpc_certificate_ltv.argtypes = [_hp, ctypes.c_uint32]
-    L.almpc_get_certificate_ltv.argtypes = [_hp] + [_dp] * 6
-    L.almpc_device_certificate_ltv.argtypes = [_hp] + [ctypes.POINTER(ctypes.c_void_p)] * 6
-    L.almpc_relin_fnn_certificate.argtypes = [_hp, ctypes.c_uint32]
-    L.almpc_group_relin_fnn_certificate.argtypes = [_hp, ctypes.c_uint32]
-    for nm_ in ("almpc_set_keep_stage_models", "almpc_certificate_ltv", "almpc_get_certificate_ltv", "almpc_device_certificate_ltv",
-                "almpc_relin_fnn_certificate", "almpc_group_relin_fnn_certificate"):
-        getattr(L, nm_).restype = ctypes.c_int
-    L.almpc_set_structured_fallback.argtypes = [_hp, ctypes.c_int]
-    L.almpc_relin_fnn_setup.argtypes = [_hp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_dp] * 12 + [ctypes.c_double, ctypes.c_double]
-    L.almpc_relin_fnn_setup.restype = ctypes.c_int
-    L.almpc_relin_densenet_setup.argtypes = L.almpc_relin_fnn_setup.argtypes
-    L.almpc_relin_densenet_setup.restype = ctypes.c_int
-    L.almpc_relin_fnn_step.argtypes = [_hp, ctypes.POINTER(almpc_opts)]
-    L.almpc_relin_fnn_step_async.argtypes = [_hp, ctypes.POINTER(almpc_opts)]
-    L.almpc_relin_fnn_timing.argtypes = [_hp, _fp, _fp, _fp]
-    L.almpc_relin_fnn_advance.argtypes = [_hp]
-    L.almpc_comm_unique_id.argtypes = [ctypes.c_char_p]
-    L.almpc_comm_init.argtypes = [_hp, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]
-    L.almpc_comm_summary.argtypes = [_hp, ctypes.POINTER(ctypes.c_int64)]
-    L.almpc_comm_allgather_first_input.argtypes = [_hp, _dp, ctypes.POINTER(_dp)]
-    L.almpc_fnn_linearize.argtypes = [ctypes.c_int] * 6 + [_dp] * 4 + [ctypes.c_int] + [_dp] * 5
-    L.almpc_fnn_linearize.restype = ctypes.c_int
-    L.almpc_densenet_linearize.argtypes = L.almpc_fnn_linearize.argtypes
-    L.almpc_densenet_linearize.restype = ctypes.c_int
-    L.almpc_debug_poison_lds.restype = ctypes.c_int
-    L.almpc_timing_summary.argtypes = [_hp, ctypes.POINTER(ctypes.c_int)] + [_dp] * 4
-    # host-facing step path (pinned staging, copy streams) and one-process multi-GPU groups
-    L.almpc_update_initialization_async.argtypes = [_hp, _dp]
-    L.almpc_x0_staging.argtypes = [_hp, ctypes.POINTER(_dp)]
-    L.almpc_get_results_async.argtypes = [_hp, ctypes.c_uint32]
-    L.almpc_get_results_wait.argtypes = [_hp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
-    L.almpc_host_results.argtypes = [_hp, ctypes.c_int] + [ctypes.POINTER(ctypes.c_void_p)] * 8
-    L.almpc_get_first_input.argtypes = [_hp, _dp]
-    L.almpc_group_create.argtypes = [ctypes.POINTER(_hp), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                     ctypes.POINTER(ctypes.c_int), ctypes.c_uint32]
-    L.almpc_group_destroy.argtypes = [_hp]
-    L.almpc_group_destroy.restype = None
-    L.almpc_group_last_error.argtypes = [_hp]
-    L.almpc_group_last_error.restype = ctypes.c_char_p
-    L.almpc_group_size.argtypes = [_hp]
-    L.almpc_group_handle.argtypes = [_hp, ctypes.c_int]
-    L.almpc_group_handle.restype = _hp
-    L.almpc_group_shard.argtypes = [_hp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-    L.almpc_group_design_shared.argtypes = [_hp] + [_dp] * 10 + [ctypes.c_double, ctypes.c_double]
-    L.almpc_group_set_reference.argtypes = [_hp, _dp, _dp, ctypes.c_int]
-    L.almpc_group_update_initialization.argtypes = [_hp, _dp]
-    L.almpc_group_calculate.argtypes = [_hp, ctypes.POINTER(almpc_opts)]
-    L.almpc_group_calculate_async.argtypes = [_hp, ctypes.POINTER(almpc_opts)]
-    L.almpc_group_synchronize.argtypes = [_hp]
-    L.almpc_group_get_results.argtypes = [_hp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
-    # group forms of everything a handle can do
-    for nm_ in ("almpc_group_set_terminal_equality", "almpc_group_set_rho_profile", "almpc_group_set_structured_fallback",
-                "almpc_group_sqp_fnn_set_structured", "almpc_group_sqp_fnn_set_step_rule", "almpc_group_sqp_fnn_set_hessian",
-                "almpc_group_sqp_fnn_set_row_multipliers"):
-        getattr(L, nm_).argtypes = [_hp, ctypes.c_int]
-    L.almpc_group_set_state_box.argtypes = [_hp, _dp, _dp]
-    L.almpc_group_design_batched.argtypes = [_hp] + [_dp] * 6 + [ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_double]
-    L.almpc_group_design_batched_weighted.argtypes = L.almpc_group_design_batched.argtypes
-    L.almpc_group_design_batched_weighted.restype = ctypes.c_int
-    L.almpc_group_relin_fnn_setup.argtypes = [_hp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_dp] * 12 + [ctypes.c_double, ctypes.c_double]
-    L.almpc_group_relin_fnn_step.argtypes = [_hp, ctypes.POINTER(almpc_opts)]
-    L.almpc_group_relin_fnn_step_async.argtypes = [_hp, ctypes.POINTER(almpc_opts)]
-    L.almpc_group_relin_fnn_advance.argtypes = [_hp]
-    L.almpc_group_advance_plant.argtypes = [_hp]
-    L.almpc_group_sqp_fnn_setup.argtypes = [_hp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_dp] * 10 + [ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_double]
-    L.almpc_group_relin_densenet_setup.argtypes = L.almpc_group_relin_fnn_setup.argtypes
-    L.almpc_group_sqp_densenet_setup.argtypes = L.almpc_group_sqp_fnn_setup.argtypes
-    L.almpc_group_sqp_fnn_start.argtypes = [_hp, _dp, _dp]
-    L.almpc_group_sqp_fnn_iterate.argtypes = [_hp, ctypes.c_int, ctypes.c_double, ctypes.POINTER(almpc_opts), _dp, _dp]
-    L.almpc_group_sqp_fnn_skipped.argtypes = [_hp, _ip]
-    L.almpc_group_sqp_fnn_state_multipliers.argtypes = [_hp, _dp]
-    L.almpc_group_sqp_fnn_solve.argtypes = [_hp, ctypes.c_int, ctypes.c_double, ctypes.POINTER(almpc_opts), _ip, _ip, _dp]
-    L.almpc_group_x0_staging.argtypes = [_hp, ctypes.POINTER(_dp)]
-    L.almpc_group_update_initialization_staged.argtypes = [_hp, ctypes.POINTER(_dp)]
-    L.almpc_group_get_results_async.argtypes = [_hp, ctypes.c_uint32]
-    L.almpc_group_get_results_wait.argtypes = [_hp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
-    for nm_ in ("almpc_group_set_terminal_equality", "almpc_group_set_rho_profile", "almpc_group_set_structured_fallback", "almpc_group_set_state_box",
-                "almpc_group_design_batched", "almpc_group_relin_fnn_setup", "almpc_group_relin_fnn_step", "almpc_group_relin_fnn_step_async",
-                "almpc_group_relin_fnn_advance", "almpc_group_advance_plant", "almpc_group_sqp_fnn_set_structured", "almpc_group_sqp_fnn_set_step_rule",
-                "almpc_group_sqp_fnn_setup", "almpc_group_relin_densenet_setup", "almpc_group_sqp_densenet_setup", "almpc_group_sqp_fnn_start", "almpc_group_sqp_fnn_iterate", "almpc_group_sqp_fnn_skipped", "almpc_group_sqp_fnn_solve", "almpc_group_sqp_fnn_set_hessian",
-                "almpc_group_sqp_fnn_set_row_multipliers", "almpc_group_sqp_fnn_state_multipliers",
-                "almpc_group_x0_staging", "almpc_group_update_initialization_staged", "almpc_group_get_results_async", "almpc_group_get_results_wait"):
-        getattr(L, nm_).restype = ctypes.c_int
-    L.almpc_set_start_from.argtypes = [_hp, _hp]
-    L.almpc_set_start_from.restype = ctypes.c_int
-    L.almpc_timing_samples.argtypes = [_hp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _fp, _fp, _fp, _fp]
-    L.almpc_timing_samples.restype = ctypes.c_int
-    for name in ("almpc_x0_staging", "almpc_update_initialization_async", "almpc_get_results_async", "almpc_get_results_wait", "almpc_host_results",
-                 "almpc_get_first_input", "almpc_group_create", "almpc_group_size", "almpc_group_shard", "almpc_group_design_shared",
-                 "almpc_group_set_reference", "almpc_group_update_initialization", "almpc_group_calculate",
-                 "almpc_group_calculate_async", "almpc_group_synchronize", "almpc_group_get_results"):
-        getattr(L, name).restype = ctypes.c_int
-    for name in ("almpc_create", "almpc_design_shared", "almpc_set_reference", "almpc_update_initialization",
-                 "almpc_update_initialization_device", "almpc_calculate", "almpc_calculate_async", "almpc_synchronize",
-                 "almpc_get_results", "almpc_get_design", "almpc_device_results", "almpc_get_timing", "almpc_timing_reset",
-                 "almpc_timing_summary"):
-        getattr(L, name).restype = ctypes.c_int
+    for name, argtypes in prototypes().items():
+        getattr(L, name).argtypes = argtypes
+    for name, restype in _RESTYPES.items():
+        getattr(L, name).restype = restype
     _lib = L
     return L
 
@@ -304,23 +163,40 @@ CERT = {"cost": 0x1, "res": 0x2, "grad": 0x4, "costate": 0x8}
 CERT_LTV = dict(CERT, x=0x10, e_x=0x10)
 
 
-def _weighted_design_args(n, m, b, A_batch, B_batch, Q_batch, R_batch, S_batch, P, umin, umax):
-    """((A, B, Q, R, S, P, umin, umax) as the C call takes them: every block column-major, S / P None where not given; P_per_instance)."""
-    def blocks(M, r, c):
-        return np.ascontiguousarray(np.asarray(M, dtype=np.float64).reshape(b, r, c).transpose(0, 2, 1))
-    A, B = blocks(A_batch, n, n), blocks(B_batch, n, m)
-    Q, R = blocks(Q_batch, n, n), blocks(R_batch, m, m)
-    S = None if S_batch is None else blocks(S_batch, m, m)
-    p_inst = 0
-    if P is not None:
-        P = np.asarray(P, dtype=np.float64)
-        if P.ndim == 3:
-            P = blocks(P, n, n); p_inst = 1
-        else:
-            P = _colmajor(P, (n, n))
-    umin = np.ascontiguousarray(umin, dtype=np.float64).reshape(m)
-    umax = np.ascontiguousarray(umax, dtype=np.float64).reshape(m)
-    return (A, B, Q, R, S, P, umin, umax), p_inst
+# ---- host arrays as the C calls take them, each conversion written once
+def _vec(v, k):
+    """a vector of length k"""
+    return np.ascontiguousarray(v, dtype=np.float64).reshape(k)
+
+
+def _blocks(M, b, r, c):
+    """(b, r, c) -> one column-major r x c block per instance"""
+    return np.ascontiguousarray(np.asarray(M, dtype=np.float64).reshape(b, r, c).transpose(0, 2, 1))
+
+
+def _traj(T, rows, stages):
+    """a shared trajectory (rows, stages) -> stage-major"""
+    return np.ascontiguousarray(np.asarray(T, dtype=np.float64).reshape(rows, stages).T)
+
+
+_traj_batch = _blocks   # one trajectory (rows, stages) per instance -> stage-major: the same move
+
+
+def _terminal_weight(P, b, n):
+    """P (n, n) shared or (b, n, n) per instance -> (array, P_per_instance)"""
+    P = np.asarray(P, dtype=np.float64)
+    if P.ndim == 3:
+        return _blocks(P, b, n, n), 1
+    return _colmajor(P, (n, n)), 0
+
+
+def _rho_code(rho_profile):
+    """almpc_set_rho_profile: "scalar" (OSQP: rho for every row) | "stiffness" (rho_i = rho / (H'^-1)_ii)"""
+    return {"scalar": 0, "stiffness": 1}[rho_profile]
+
+
+def _optional(conv, a, *args):
+    return None if a is None else conv(a, *args)
 
 
 def _sens_mask(want):
@@ -393,9 +269,7 @@ def multipliers(grad, u, umin, umax, act_tol=1e-9):
 
 def _sens_vjp(call, handle, check, g_u, g_x, act_tol, b, n, m, N):
     """act_tol: the tolerance of almpc_sensitivity_vjp, or the pair (act_tol_u, act_tol_x) of the rows form."""
-    g_u = np.ascontiguousarray(np.asarray(g_u, dtype=np.float64).reshape(b, m, N).transpose(0, 2, 1))
-    if g_x is not None:
-        g_x = np.ascontiguousarray(np.asarray(g_x, dtype=np.float64).reshape(b, n, N + 1).transpose(0, 2, 1))
+    g_u, g_x = _traj_batch(g_u, b, m, N), _optional(_traj_batch, g_x, b, n, N + 1)
     g_x0 = np.empty((b, n))
     rows = np.empty(b, dtype=np.int32)
     tols = tuple(float(t) for t in act_tol) if isinstance(act_tol, tuple) else (float(act_tol),)
@@ -417,9 +291,7 @@ def _sens_params_vjp(call, handle, check, g_u, g_x, want, act_tol, b, n, m, N, d
     for k in want:
         if k not in PARAM_GROUPS:
             raise ValueError(f"unknown parameter group {k!r} (one of {PARAM_GROUPS})")
-    g_u = np.ascontiguousarray(np.asarray(g_u, dtype=np.float64).reshape(b, m, N).transpose(0, 2, 1))
-    if g_x is not None:
-        g_x = np.ascontiguousarray(np.asarray(g_x, dtype=np.float64).reshape(b, n, N + 1).transpose(0, 2, 1))
+    g_u, g_x = _traj_batch(g_u, b, m, N), _optional(_traj_batch, g_x, b, n, N + 1)
     # the C layouts: stage-major trajectories, column-major matrices
     shapes = {"x0": (b, n), "f": (b, N, m), "u_ref": (b, N, m), "u_min": (b, m), "u_max": (b, m), "Q": (b, n, n), "P": (b, n, n),
               "A": (b, n, n), "R": (b, m, m), "S": (b, m, m), "B": (b, m, n)}
@@ -449,6 +321,29 @@ def _want_mask(want):
         return sum(WANT[k] for k in set(want))
     except KeyError as e:
         raise ValueError(f"unknown result {e.args[0]!r}; choose from {sorted(WANT)}") from None
+
+
+def _result_table(b, n, m, N):
+    """{name: (shape of the C buffer, dtype, ctypes pointer type)} in the order of the C calls' arguments; the trajectories (three
+    axes) are stage-major there and go back Julia-shaped, as (batch, n, N+1) and (batch, m, N) views"""
+    shapes = {"x": (b, N + 1, n), "e_x": (b, N + 1, n), "u": (b, N, m), "e_u": (b, N, m), "u0": (b, m),
+              "status": (b,), "iters": (b,), "polish_iters": (b,)}
+    f8, i4 = np.dtype(np.float64), np.dtype(np.int32)   # (dtype objects: np.empty takes them as they are)
+    return {k: (s, i4, _ip) if len(s) == 1 else (s, f8, _dp) for k, s in shapes.items()}
+
+
+def _result_bufs(table, want):
+    """fresh buffers for the names of `table` that `want` holds: ({name: its Julia-shaped view}, the pointer list of the C call with
+    NULL = not wanted)"""
+    bufs, args = {}, []
+    for k, (shape, dtype, ptype) in table.items():
+        if k in want:
+            a = np.empty(shape, dtype)
+            args.append(a.ctypes.data_as(ptype))
+            bufs[k] = a.transpose(0, 2, 1) if len(shape) == 3 else a
+        else:
+            args.append(None)
+    return bufs, args
 
 
 def comm_unique_id() -> bytes:
@@ -526,13 +421,13 @@ def dare_vjp_batched(A, B, Q, R, P, g_P, device=0, want=("A", "B", "Q", "R"), in
     b, n, m = B.shape
     if P.shape != (b, n, n) or g_P.shape != (b, n, n):
         raise ValueError(f"expected P and g_P {(b, n, n)}, got {P.shape} and {g_P.shape}")
-    cm = lambda a: np.ascontiguousarray(a.transpose(0, 2, 1))  # column-major blocks
+    cm = lambda a: _blocks(a, *a.shape)
     Q, R = _colmajor(Q, (n, n)), _colmajor(R, (m, m))
     shapes = {"A": (b, n, n), "B": (b, n, m), "Q": (b, n, n), "R": (b, m, m)}
     out = {}
     for k in want:
         out[k] = np.full(shapes[k], np.nan).transpose(0, 2, 1).copy() if init is None or k not in init else \
-            cm(np.asarray(init[k], dtype=np.float64).reshape(shapes[k]))
+            _blocks(init[k], *shapes[k])
     st = np.zeros(b, dtype=np.int32)
     rc = L.almpc_dare_vjp_batched(int(device), n, m, b, _ptr(cm(A)), _ptr(cm(B)), _ptr(Q), _ptr(R), _ptr(cm(P)), _ptr(cm(g_P)),
                                   *(_ptr(out.get(k)) for k in ("A", "B", "Q", "R")), st.ctypes.data_as(_ip))
@@ -560,13 +455,12 @@ def dare_batched(A, B, Q, R, device=0, P_init=None):
     if A.ndim != 3 or B.ndim != 3 or A.shape[0] != B.shape[0] or A.shape[1] != A.shape[2] or B.shape[1] != A.shape[1]:
         raise ValueError(f"expected A (batch, n, n) and B (batch, n, m), got {A.shape} and {B.shape}")
     b, n, m = B.shape
-    Ac = np.ascontiguousarray(A.transpose(0, 2, 1))  # column-major blocks
-    Bc = np.ascontiguousarray(B.transpose(0, 2, 1))
+    Ac, Bc = _blocks(A, b, n, n), _blocks(B, b, n, m)
     Q, R = _colmajor(Q, (n, n)), _colmajor(R, (m, m))
     if P_init is None:
         P = np.full((b, n, n), np.nan)
     else:
-        P = np.ascontiguousarray(np.asarray(P_init, dtype=np.float64).reshape(b, n, n).transpose(0, 2, 1))
+        P = _blocks(P_init, b, n, n)
     st = np.zeros(b, dtype=np.int32)
     rc = L.almpc_dare_batched(int(device), n, m, b, _ptr(Ac), _ptr(Bc), _ptr(Q), _ptr(R), _ptr(P), st.ctypes.data_as(_ip))
     if rc != ALMPC_OK:
@@ -609,13 +503,11 @@ def c2d_batched(A, B, Ts, device=0, out_init=None):
     if A.ndim != 3 or B.ndim != 3 or A.shape[0] != B.shape[0] or A.shape[1] != A.shape[2] or B.shape[1] != A.shape[1]:
         raise ValueError(f"expected A (batch, n, n) and B (batch, n, m), got {A.shape} and {B.shape}")
     b, n, m = B.shape
-    Ac = np.ascontiguousarray(A.transpose(0, 2, 1))  # column-major blocks
-    Bc = np.ascontiguousarray(B.transpose(0, 2, 1))
+    Ac, Bc = _blocks(A, b, n, n), _blocks(B, b, n, m)
     if out_init is None:
         Ad, Bd = np.full((b, n, n), np.nan), np.full((b, m, n), np.nan)
     else:
-        Ad = np.ascontiguousarray(np.asarray(out_init[0], dtype=np.float64).reshape(b, n, n).transpose(0, 2, 1))
-        Bd = np.ascontiguousarray(np.asarray(out_init[1], dtype=np.float64).reshape(b, n, m).transpose(0, 2, 1))
+        Ad, Bd = _blocks(out_init[0], b, n, n), _blocks(out_init[1], b, n, m)
     st = np.zeros(b, dtype=np.int32)
     rc = L.almpc_c2d_batched(int(device), n, m, b, _ptr(Ac), _ptr(Bc), float(Ts), _ptr(Ad), _ptr(Bd), st.ctypes.data_as(_ip))
     if rc != ALMPC_OK:
@@ -671,79 +563,82 @@ def _densenet_act(act):
     return FNN_ACTIVATIONS[act]
 
 
+def _fnn_buffers(W_in, W_h, b_h, W_out, act, net):
+    """The buffers of a network in the Fnn weight layout (include/almpc.h): W_in (H, n+m), W_h[l] (H, H) one after another, b_h[l] (H,),
+    W_out (n, H), all column-major (one-element dummies for L = 0).  -> H, L, code, W_in, W_h, b_h, W_out"""
+    W_in, W_out = np.asfortranarray(W_in, dtype=np.float64), np.asfortranarray(W_out, dtype=np.float64)
+    nl = len(W_h)
+    Wh = np.ascontiguousarray(np.stack([np.asfortranarray(W, dtype=np.float64).T for W in W_h])) if nl else np.zeros((1, 1, 1))
+    bh = np.ascontiguousarray(np.stack([np.asarray(v, dtype=np.float64) for v in b_h])) if nl else np.zeros((1, 1))
+    return W_in.shape[0], nl, net_code(net, act), W_in, Wh, bh, W_out
+
+
+def _densenet_buffers(W_in, W_h, b_h, W_out, act, n, m):
+    """_fnn_buffers for a DenseNet: the layout of _pack_densenet and a bare activation code"""
+    H, nl, W_in, Wh, bh, W_out = _pack_densenet(W_in, W_h, b_h, W_out, n, m)
+    return H, nl, _densenet_act(act), W_in, Wh, bh, W_out
+
+
+def _linearize(call, name, device, n, m, net, x, u, want_f):
+    H, nl, code, *W = net
+    batch = x.shape[0]
+    A = np.empty((batch, n, n)); B = np.empty((batch, m, n)); f = np.empty((batch, n)) if want_f else None
+    rc = call(int(device), n, m, H, nl, code, *[_ptr(w) for w in W], batch, _ptr(x), _ptr(u), _ptr(A), _ptr(B), _ptr(f))
+    if rc != ALMPC_OK:
+        raise AlmpcError(rc, name)
+    A, B = A.transpose(0, 2, 1), B.transpose(0, 2, 1)  # column-major buffers -> (batch, row, col)
+    return (A, B, f) if want_f else (A, B)
+
+
 def fnn_linearize(W_in, W_h, b_h, W_out, x, u, act="relu", device=0, want_f=False, net="fnn"):
     """Batched Jacobians of a network model on the GPU: x (batch, n), u (batch, m) -> A (batch, n, n), B (batch, n, m).
     net: "fnn", "resnet" or "polynet" (NET_KINDS), all in the Fnn weight layout."""
-    L = load()
-    W_in, W_out = np.asfortranarray(W_in, dtype=np.float64), np.asfortranarray(W_out, dtype=np.float64)
-    H, nin = W_in.shape
-    n = W_out.shape[0]
-    m = nin - n
-    nl = len(W_h)
-    Wh = np.ascontiguousarray(np.stack([np.asfortranarray(W, dtype=np.float64).T for W in W_h])) if nl else np.zeros((1, 1, 1))
-    bh = np.ascontiguousarray(np.stack([np.asarray(b, dtype=np.float64) for b in b_h])) if nl else np.zeros((1, 1))
+    net = _fnn_buffers(W_in, W_h, b_h, W_out, act, net)
     x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
     u = np.ascontiguousarray(np.atleast_2d(u), dtype=np.float64)
-    batch = x.shape[0]
-    A = np.empty((batch, n, n)); B = np.empty((batch, m, n)); f = np.empty((batch, n)) if want_f else None
-    rc = L.almpc_fnn_linearize(int(device), n, m, H, nl, net_code(net, act), _ptr(W_in), _ptr(Wh), _ptr(bh), _ptr(W_out),
-                               batch, _ptr(x), _ptr(u), _ptr(A), _ptr(B), _ptr(f))
-    if rc != ALMPC_OK:
-        raise AlmpcError(rc, "almpc_fnn_linearize")
-    A, B = A.transpose(0, 2, 1), B.transpose(0, 2, 1)  # column-major buffers -> (batch, row, col)
-    return (A, B, f) if want_f else (A, B)
+    n = net[6].shape[0]   # (W_out is n x H, W_in H x (n + m))
+    return _linearize(load().almpc_fnn_linearize, "almpc_fnn_linearize", device, n, net[3].shape[1] - n, net, x, u, want_f)
 
 
 def densenet_linearize(W_in, W_h, b_h, W_out, x, u, act="relu", device=0, want_f=False):
     """fnn_linearize for a DenseNet (almpc_densenet_linearize): W_h a list of (H, (l+1) H) blocks, W_out (n, (L+1) H)."""
     x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
     u = np.ascontiguousarray(np.atleast_2d(u), dtype=np.float64)
-    H, nl, W_in, Wh, bh, W_out = _pack_densenet(W_in, W_h, b_h, W_out, x.shape[1], u.shape[1])
-    n, m = x.shape[1], u.shape[1]
-    batch = x.shape[0]
-    if u.shape[0] != batch:
+    if u.shape[0] != x.shape[0]:
         raise ValueError("x and u must hold the same number of points")
-    code = _densenet_act(act)
-    L = load()
-    A = np.empty((batch, n, n)); B = np.empty((batch, m, n)); f = np.empty((batch, n)) if want_f else None
-    rc = L.almpc_densenet_linearize(int(device), n, m, H, nl, code, _ptr(W_in), _ptr(Wh), _ptr(bh), _ptr(W_out),
-                                    batch, _ptr(x), _ptr(u), _ptr(A), _ptr(B), _ptr(f))
-    if rc != ALMPC_OK:
-        raise AlmpcError(rc, "almpc_densenet_linearize")
-    A, B = A.transpose(0, 2, 1), B.transpose(0, 2, 1)
-    return (A, B, f) if want_f else (A, B)
+    net = _densenet_buffers(W_in, W_h, b_h, W_out, act, x.shape[1], u.shape[1])
+    return _linearize(load().almpc_densenet_linearize, "almpc_densenet_linearize", device, x.shape[1], u.shape[1], net, x, u, want_f)
 
 
-class Solver:
-    """Thin object wrapper of an almpc_handle: one device, one batch shard."""
+class _Form:
+    """The C functions of one form of the API -- almpc_<name> for a handle, almpc_group_<name> for a group --, looked up once."""
 
-    def __init__(self, n, m, N, batch, device=0, timing=False, structured=False, structured_fallback=None):
-        """structured: ALMPC_FLAG_STRUCTURED (the stage-wise solve of the multiple-shooting form is the handle's solver: no m*N <= 128
-        limit).  structured_fallback: the redo of the instances a condensed step leaves without a certificate by the stage-wise
-        solvers -- None: the library default (on wherever they cover the design), True: required, False: off."""
-        self.L = load()
+    def __init__(self, L, prefix):
+        for name in _GROUP_FORMS + ("get_results",):
+            setattr(self, name, getattr(L, prefix + name))
+
+
+class _Target:
+    """What a handle and a group can both do, written once: self._t is the almpc_handle* or the almpc_group*, self._f the C
+    functions of that form.  Host arrays cover the target's whole batch."""
+
+    _PREFIX = None          # of the C functions: "almpc_" or "almpc_group_"
+    _NO_U0 = None           # almpc_get_results has no u0 argument, almpc_group_get_results has
+
+    def _bind(self, L, n, m, N, batch):
+        self.L = L
         self.n, self.m, self.N, self.batch = int(n), int(m), int(N), int(batch)
         self.nz = self.m * self.N
-        h = _hp()
-        rc = self.L.almpc_create(ctypes.byref(h), self.n, self.m, self.N, self.batch, int(device),
-                                 (FLAG_TIMING if timing else 0) | (FLAG_STRUCTURED if structured else 0))
-        if rc != ALMPC_OK:
-            raise AlmpcError(rc, "almpc_create failed (is a gfx950 GPU visible? there is no CPU fallback)")
-        self.h = h
-        if structured_fallback is not None:
-            self._check(self.L.almpc_set_structured_fallback(self.h, 1 if structured_fallback else 0))
+        self._f = _Form(L, self._PREFIX)
+        self._results = _result_table(self.batch, self.n, self.m, self.N)
+        self._get_results = {k: v for k, v in self._results.items() if k != "u0"} if self._NO_U0 else self._results
+        self._t = None
 
     def _check(self, rc):
         if rc != ALMPC_OK:
-            raise AlmpcError(rc, (self.L.almpc_last_error(self.h) or b"").decode())
+            raise AlmpcError(rc, (self._f.last_error(self._t) or b"").decode())
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.almpc_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
+    # ---- designs
     def design_shared(self, A, B, Q, R, S=None, P=None, umin=None, umax=None, xmin=None, xmax=None, rho=0.1, sigma=1e-6,
                       terminal="none", rho_profile="scalar"):
         """xmin/xmax: state box (the reference's kw mpc_state_constraint); terminal: "none" | "equality";
@@ -751,63 +646,309 @@ class Solver:
         n, m = self.n, self.m
         if terminal not in ("none", "equality"):
             raise ValueError("terminal must be 'none' or 'equality'")
-        self._check(self.L.almpc_set_terminal_equality(self.h, 1 if terminal == "equality" else 0))
-        self._check(self.L.almpc_set_rho_profile(self.h, {"scalar": 0, "stiffness": 1}[rho_profile]))
+        self._check(self._f.set_terminal_equality(self._t, 1 if terminal == "equality" else 0))
+        self._check(self._f.set_rho_profile(self._t, _rho_code(rho_profile)))
         A, B, Q, R = _colmajor(A, (n, n)), _colmajor(B, (n, m)), _colmajor(Q, (n, n)), _colmajor(R, (m, m))
-        S = None if S is None else _colmajor(S, (m, m))
-        P = None if P is None else _colmajor(P, (n, n))
-        umin = np.ascontiguousarray(umin, dtype=np.float64).reshape(m)
-        umax = np.ascontiguousarray(umax, dtype=np.float64).reshape(m)
-        xmin = None if xmin is None else np.ascontiguousarray(xmin, dtype=np.float64).reshape(n)
-        xmax = None if xmax is None else np.ascontiguousarray(xmax, dtype=np.float64).reshape(n)
-        self._check(self.L.almpc_design_shared(self.h, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(S), _ptr(P), _ptr(umin),
-                                               _ptr(umax), _ptr(xmin), _ptr(xmax), float(rho), float(sigma)))
+        S, P = _optional(_colmajor, S, (m, m)), _optional(_colmajor, P, (n, n))
+        umin, umax = _vec(umin, m), _vec(umax, m)
+        xmin, xmax = _optional(_vec, xmin, n), _optional(_vec, xmax, n)
+        self._check(self._f.design_shared(self._t, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(S), _ptr(P), _ptr(umin), _ptr(umax),
+                                          _ptr(xmin), _ptr(xmax), float(rho), float(sigma)))
 
     def _state_rows(self, xmin, xmax, terminal):
         """State box / terminal equality of the designs without xmin / xmax arguments (almpc_set_state_box, almpc_set_terminal_equality)."""
         if (xmin is None) != (xmax is None):
             raise ValueError("give both xmin and xmax or neither")
-        self._check(self.L.almpc_set_terminal_equality(self.h, 1 if terminal == "equality" else 0))
-        if xmin is None:
-            self._check(self.L.almpc_set_state_box(self.h, None, None))
-        else:
-            lo = np.ascontiguousarray(xmin, dtype=np.float64).reshape(self.n)
-            hi = np.ascontiguousarray(xmax, dtype=np.float64).reshape(self.n)
-            self._check(self.L.almpc_set_state_box(self.h, _ptr(lo), _ptr(hi)))
+        self._check(self._f.set_terminal_equality(self._t, 1 if terminal == "equality" else 0))
+        lo, hi = _optional(_vec, xmin, self.n), _optional(_vec, xmax, self.n)
+        self._check(self._f.set_state_box(self._t, _ptr(lo), _ptr(hi)))
+
+    def _design_batched(self, design, weight, A_batch, B_batch, Q, R, S, P, umin, umax, rho, sigma, rho_profile, xmin, xmax, terminal):
+        """weight(W, k): the conversion of a k x k weight, shared or one per instance"""
+        n, m, b = self.n, self.m, self.batch
+        self._state_rows(xmin, xmax, terminal)
+        self._check(self._f.set_rho_profile(self._t, _rho_code(rho_profile)))
+        A, B = _blocks(A_batch, b, n, n), _blocks(B_batch, b, n, m)
+        Q, R, S = weight(Q, n), weight(R, m), _optional(weight, S, m)
+        P, p_inst = (None, 0) if P is None else _terminal_weight(P, b, n)
+        umin, umax = _vec(umin, m), _vec(umax, m)
+        self._check(design(self._t, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(S), _ptr(P), p_inst, _ptr(umin), _ptr(umax), float(rho),
+                           float(sigma)))
 
     def design_batched(self, A_batch, B_batch, Q, R, S=None, P=None, umin=None, umax=None, rho=0.1, sigma=1e-6,
                        rho_profile="scalar", xmin=None, xmax=None, terminal="none"):
         """One model per instance: A_batch (batch, n, n), B_batch (batch, n, m).  P: None (DARE per instance), (n, n) shared
         or (batch, n, n).  xmin / xmax: state box (stages 1..N+1); terminal = "equality": e_x[:, N+1] = 0."""
-        n, m, b = self.n, self.m, self.batch
-        self._state_rows(xmin, xmax, terminal)
-        self._check(self.L.almpc_set_rho_profile(self.h, {"scalar": 0, "stiffness": 1}[rho_profile]))
-        A = np.ascontiguousarray(np.asarray(A_batch, dtype=np.float64).reshape(b, n, n).transpose(0, 2, 1))  # column-major blocks
-        B = np.ascontiguousarray(np.asarray(B_batch, dtype=np.float64).reshape(b, n, m).transpose(0, 2, 1))
-        Q, R = _colmajor(Q, (n, n)), _colmajor(R, (m, m))
-        S = None if S is None else _colmajor(S, (m, m))
-        p_inst = 0
-        if P is not None:
-            P = np.asarray(P, dtype=np.float64)
-            if P.ndim == 3:
-                P = np.ascontiguousarray(P.reshape(b, n, n).transpose(0, 2, 1)); p_inst = 1
-            else:
-                P = _colmajor(P, (n, n))
-        umin = np.ascontiguousarray(umin, dtype=np.float64).reshape(m)
-        umax = np.ascontiguousarray(umax, dtype=np.float64).reshape(m)
-        self._check(self.L.almpc_design_batched(self.h, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(S), _ptr(P), p_inst, _ptr(umin),
-                                                _ptr(umax), float(rho), float(sigma)))
+        self._design_batched(self._f.design_batched, lambda W, k: _colmajor(W, (k, k)), A_batch, B_batch, Q, R, S, P, umin, umax, rho,
+                             sigma, rho_profile, xmin, xmax, terminal)
 
     def design_batched_weighted(self, A_batch, B_batch, Q_batch, R_batch, S_batch=None, P=None, umin=None, umax=None, rho=0.1, sigma=1e-6,
                                 rho_profile="scalar", xmin=None, xmax=None, terminal="none"):
         """design_batched with one weight set per instance (almpc_design_batched_weighted): Q_batch (batch, n, n), R_batch and
         S_batch (batch, m, m), S_batch None for S = 0 everywhere.  The other arguments are design_batched's."""
-        self._state_rows(xmin, xmax, terminal)
-        self._check(self.L.almpc_set_rho_profile(self.h, {"scalar": 0, "stiffness": 1}[rho_profile]))
-        args, p_inst = _weighted_design_args(self.n, self.m, self.batch, A_batch, B_batch, Q_batch, R_batch, S_batch, P, umin, umax)
-        self._check(self.L.almpc_design_batched_weighted(self.h, *[_ptr(a) for a in args[:6]], p_inst, _ptr(args[6]), _ptr(args[7]),
-                                                         float(rho), float(sigma)))
+        self._design_batched(self._f.design_batched_weighted, lambda W, k: _blocks(W, self.batch, k, k), A_batch, B_batch, Q_batch,
+                             R_batch, S_batch, P, umin, umax, rho, sigma, rho_profile, xmin, xmax, terminal)
 
+    def set_terminal_weight(self, mode):
+        """Before a design: "given" / 0 (default) or "dare_device" / 1 -- design_batched(P=None) and every relin_fnn step take each
+        instance's terminal weight from the DARE of its own model, solved on the device (almpc_set_terminal_weight)."""
+        self._check(self._f.set_terminal_weight(self._t, _terminal_mode(mode)))
+
+    def set_model_time(self, mode, Ts=0.0):
+        """Before a design: "discrete" / 0 (default) or "continuous" / 1 with the sample time Ts -- the models given to design_shared and
+        design_batched, and the network of the relin_fnn pipeline, are continuous-time and are discretised by zero-order hold at Ts
+        (almpc_set_model_time)."""
+        self._check(self._f.set_model_time(self._t, _model_time_mode(mode), float(Ts)))
+
+    # ---- network models: the SQP loop (almpc_sqp_fnn_*) and the per-step re-linearisation (almpc_relin_fnn_*)
+    def _net_setup(self, setup, net, x_ref, u_ref, Q, R, S, P, umin, umax, rho, sigma, rho_profile, xmin, xmax, terminal, qp_solver=None):
+        """net: (H, L, code, W_in, W_h, b_h, W_out).  qp_solver None: a relin setup (shared P, no P_per_instance argument)."""
+        n, m, N = self.n, self.m, self.N
+        self._state_rows(xmin, xmax, terminal)
+        if qp_solver is not None:
+            self._check(self._f.sqp_fnn_set_structured(self._t, 1 if qp_solver == "structured" else 0))
+        self._check(self._f.set_rho_profile(self._t, _rho_code(rho_profile)))
+        xr, ur = _optional(_traj, x_ref, n, N + 1), _optional(_traj, u_ref, m, N)
+        Q, R, S = _colmajor(Q, (n, n)), _colmajor(R, (m, m)), _optional(_colmajor, S, (m, m))
+        if qp_solver is None:
+            P, p_inst = _colmajor(P, (n, n)), ()
+        else:
+            P, p_inst = _terminal_weight(P, self.batch, n)
+            p_inst = (p_inst,)
+        umin, umax = _vec(umin, m), _vec(umax, m)
+        self._check(setup(self._t, *net[:3], *[_ptr(w) for w in net[3:]], _ptr(xr), _ptr(ur), _ptr(Q), _ptr(R), _ptr(S), _ptr(P), *p_inst,
+                          _ptr(umin), _ptr(umax), float(rho), float(sigma)))
+
+    def sqp_fnn_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu", rho=0.1,
+                      sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", qp_solver="condensed", net="fnn"):
+        """SQP outer loop for a network model (almpc_sqp_fnn_*): network (and net) as in fnn_linearize, x_ref (n, N+1) / u_ref (m, N) or None,
+        P (n, n) or (batch, n, n).  qp_solver: "condensed" (default) or "structured" (every QP through k_riccati, no condensed design).  xmin / xmax: the state box of the reference's NLP branch
+        (.../fnn/mpc_modeler_implementation_fnn.jl:146-153) as rows of every iteration's QP; terminal = "equality"."""
+        self._net_setup(self._f.sqp_fnn_setup, _fnn_buffers(W_in, W_h, b_h, W_out, act, net), x_ref, u_ref, Q, R, S, P, umin, umax, rho,
+                        sigma, rho_profile, xmin, xmax, terminal, qp_solver)
+
+    def sqp_densenet_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu",
+                           rho=0.1, sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", qp_solver="condensed"):
+        """sqp_fnn_setup for a DenseNet (almpc_sqp_densenet_setup; network as in densenet_linearize); then the sqp_fnn_* calls."""
+        self._net_setup(self._f.sqp_densenet_setup, _densenet_buffers(W_in, W_h, b_h, W_out, act, self.n, self.m), x_ref, u_ref, Q, R, S,
+                        P, umin, umax, rho, sigma, rho_profile, xmin, xmax, terminal, qp_solver)
+
+    def relin_fnn_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu", rho=0.1,
+                        sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", net="fnn"):
+        """Device-resident per-step re-linearisation of a network model (almpc_relin_fnn_*, BASELINE configs[3]): network (and net)
+        as in fnn_linearize, shared x_ref (n, N+1) / u_ref (m, N) or None, shared P (n, n); xmin / xmax / terminal as in design_batched."""
+        self._net_setup(self._f.relin_fnn_setup, _fnn_buffers(W_in, W_h, b_h, W_out, act, net), x_ref, u_ref, Q, R, S, P, umin, umax, rho,
+                        sigma, rho_profile, xmin, xmax, terminal)
+
+    def relin_densenet_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu",
+                             rho=0.1, sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none"):
+        """relin_fnn_setup for a DenseNet (almpc_relin_densenet_setup; network as in densenet_linearize); then the relin_fnn_* calls."""
+        self._net_setup(self._f.relin_densenet_setup, _densenet_buffers(W_in, W_h, b_h, W_out, act, self.n, self.m), x_ref, u_ref, Q, R,
+                        S, P, umin, umax, rho, sigma, rho_profile, xmin, xmax, terminal)
+
+    def relin_fnn_step(self, opts: almpc_opts | None = None, sync=True):
+        fn = self._f.relin_fnn_step if sync else self._f.relin_fnn_step_async
+        self._check(fn(self._t, ctypes.byref(opts) if opts is not None else None))
+
+    def relin_fnn_advance(self):
+        """x0 <- fnn(x0, u[:,1]) on the device (closed loop of the black-box model)."""
+        self._check(self._f.relin_fnn_advance(self._t))
+
+    def relin_fnn_certificate(self, want=("cost", "res", "grad", "costate")) -> dict:
+        """almpc_relin_fnn_certificate + almpc_get_certificate: `certificate` of the last relin_fnn_step, with that step's own models,
+        terminal weights and weights."""
+        return self._certificate(self._f.relin_fnn_certificate, want)
+
+    def sqp_fnn_start(self, x0, u_guess=None):
+        """x0 (batch, n); u_guess (batch, m, N) or None."""
+        x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).reshape(self.batch, self.n))
+        ug = _optional(_traj_batch, u_guess, self.batch, self.m, self.N)
+        self._check(self._f.sqp_fnn_start(self._t, _ptr(x0), _ptr(ug)))
+
+    def sqp_fnn_iterate(self, iters, step_scale=1.0, opts=None, step_rule="fixed"):
+        """-> (step_inf[iters], defect_inf[iters]); raises AlmpcError(ALMPC_ERR_NUMERIC) when an instance had to skip an iteration
+        (the histories are still filled: see .sqp_last).  step_rule: "fixed" | "merit" (l1 merit-function safeguard)."""
+        self._check(self._f.sqp_fnn_set_step_rule(self._t, {"fixed": 0, "merit": 1}[step_rule]))
+        st, de = np.zeros(int(iters)), np.zeros(int(iters))
+        self.sqp_last = (st, de)
+        self._check(self._f.sqp_fnn_iterate(self._t, int(iters), float(step_scale), ctypes.byref(opts) if opts is not None else None,
+                                            _ptr(st), _ptr(de)))
+        return st, de
+
+    def sqp_fnn_solve(self, max_iters, tol, opts=None, step_rule="merit"):
+        """Solve to a tolerance (almpc_sqp_fnn_solve): at most max_iters iterations, each instance frozen once its iterate passes the
+        first-order test (zero defects, projected adjoint-gradient residual <= tol).  -> dict(status (batch,) int32: 0 converged,
+        1 iteration limit, 2 skipped, 3 infeasible QP; iters (batch,) int32; kkt (batch,) residual of the last test).
+        The step rule is a setting of the handle and stays in force: a later sqp_fnn_iterate sets its own (default "fixed")."""
+        self._check(self._f.sqp_fnn_set_step_rule(self._t, {"fixed": 0, "merit": 1}[step_rule]))
+        st, it, kk = np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch)
+        self._check(self._f.sqp_fnn_solve(self._t, int(max_iters), float(tol), ctypes.byref(opts) if opts is not None else None,
+                                          st.ctypes.data_as(_ip), it.ctypes.data_as(_ip), _ptr(kk)))
+        return dict(status=st, iters=it, kkt=kk)
+
+    def sqp_fnn_set_hessian(self, mode):
+        """Hessian of the loop's QPs: "gauss_newton" (default) or "exact" (almpc_sqp_fnn_set_hessian); stays in force."""
+        self._check(self._f.sqp_fnn_set_hessian(self._t, SQP_HESSIANS[mode]))
+
+    def sqp_fnn_set_row_multipliers(self, on):
+        """State rows (state box, terminal equality) in the loop's stopping test and exact Hessian: the finishes hand the row multipliers
+        of every iteration's QP out (almpc_sqp_fnn_set_row_multipliers; default off, stays in force)."""
+        self._check(self._f.sqp_fnn_set_row_multipliers(self._t, 1 if on else 0))
+
+    def sqp_fnn_state_multipliers(self):
+        """-> (batch, n, N): multiplier of the row of x_{k+1}[i] at [:, i, k] in each instance's last solved QP (> 0 upper bound, < 0 lower
+        bound, free on a terminal-equality row, 0 outside the working set); zeros with the switch off or without state rows."""
+        mu = np.zeros((self.batch, self.N, self.n))
+        self._check(self._f.sqp_fnn_state_multipliers(self._t, _ptr(mu)))
+        return np.ascontiguousarray(mu.transpose(0, 2, 1))
+
+    def sqp_fnn_skipped(self):
+        out = np.zeros(self.batch, dtype=np.int32)
+        self._check(self._f.sqp_fnn_skipped(self._t, out.ctypes.data_as(_ip)))
+        return out
+
+    # ---- the step
+    def set_reference(self, x_ref, u_ref, per_instance=False):
+        """x_ref (n, N+1) / u_ref (m, N), or with per_instance (batch, n, N+1) / (batch, m, N)."""
+        n, m, N = self.n, self.m, self.N
+        if per_instance:
+            xr, ur = _traj_batch(x_ref, self.batch, n, N + 1), _traj_batch(u_ref, self.batch, m, N)
+        else:
+            xr, ur = _traj(x_ref, n, N + 1), _traj(u_ref, m, N)
+        self._check(self._f.set_reference(self._t, _ptr(xr), _ptr(ur), 1 if per_instance else 0))
+
+    def update_initialization(self, x0):
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(self.batch, self.n)
+        self._check(self._f.update_initialization(self._t, _ptr(x0)))
+
+    def calculate(self, opts: almpc_opts | None = None, sync=True):
+        fn = self._f.calculate if sync else self._f.calculate_async
+        self._check(fn(self._t, None if opts is None else ctypes.byref(opts)))
+
+    def synchronize(self):
+        self._check(self._f.synchronize(self._t))
+
+    def advance_plant(self):
+        self._check(self._f.advance_plant(self._t))
+
+    def get_results(self, want=("x", "e_x", "u", "e_u", "status", "iters", "polish_iters")):
+        """The last step's results, Julia-shaped: x, e_x (batch, n, N+1), u, e_u (batch, m, N), status, iters, polish_iters (batch,)."""
+        bufs, args = _result_bufs(self._get_results, want)
+        self._check(self._f.get_results(self._t, *args))
+        return bufs
+
+    def get_results_async(self, want=("u0", "status")) -> int:
+        """Ask for results of the last enqueued step (names of WANT; "u0" = u[:, 1] of every instance); returns a ticket."""
+        t = self._f.get_results_async(self._t, _want_mask(want))
+        if t < 0:
+            self._check(t)
+        return t
+
+    def get_results_wait(self, ticket, want=("u0", "status")):
+        """Results of a ticket in fresh arrays (almpc_get_results_wait).  Shapes as get_results; u0 (batch, m)."""
+        _want_mask(want)
+        bufs, args = _result_bufs(self._results, want)
+        self._check(self._f.get_results_wait(self._t, int(ticket), *args))
+        return bufs
+
+    # ---- sensitivities of the last step to x0 (include/almpc.h "Sensitivities"; an extension beyond the reference's surface)
+    def _sensitivity(self, call, want, *tols):
+        self._check(call(self._t, _sens_mask(want), *[float(t) for t in tols]))
+        return _sens_read(self._f.get_sensitivity, self._t, self._check, want, self.batch, self.n, self.m, self.N)
+
+    def _vjp(self, call, g_u, g_x, act_tol):
+        return _sens_vjp(call, self._t, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
+
+    def sensitivity(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
+        """almpc_sensitivity + almpc_get_sensitivity: K0 (batch, m, n) = du[:,1]/dx0, dU (batch, m, N, n), dX (batch, n, N+1, n),
+        each [b, i, k, c] = d(entry i of stage k) / d x0[c], and rows (batch,) = rows at a bound (-1: instance not solved, zeros).
+        act_tol <= 0: 1e-9 (in units of the row's Jacobi scale)."""
+        return self._sensitivity(self._f.sensitivity, want, act_tol)
+
+    def sensitivity_vjp(self, g_u, g_x=None, act_tol=0.0):
+        """dL/dx0 (batch, n) for a loss with gradients g_u (batch, m, N) and g_x (batch, n, N+1) or None on the returned
+        trajectories (almpc_sensitivity_vjp: no Jacobian is formed); also returns rows (batch,)."""
+        return self._vjp(self._f.sensitivity_vjp, g_u, g_x, act_tol)
+
+    def sensitivity_stagewise(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
+        """sensitivity on a structured handle (almpc_sensitivity_stagewise + almpc_get_sensitivity): the Riccati recursion on the face
+        where the inputs at a bound are held; input box only, S = 0.  act_tol is relative to the width of the input box (0: 1e-7)."""
+        return self._sensitivity(self._f.sensitivity_stagewise, want, act_tol)
+
+    def sensitivity_stagewise_vjp(self, g_u, g_x=None, act_tol=0.0):
+        """sensitivity_vjp on a structured handle (almpc_sensitivity_stagewise_vjp): (g_x0 (batch, n), rows (batch,))."""
+        return self._vjp(self._f.sensitivity_stagewise_vjp, g_u, g_x, act_tol)
+
+    def sensitivity_stagewise_rate(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
+        """sensitivity_stagewise for every structured input-box design, with or without an input-rate weight S
+        (almpc_sensitivity_stagewise_rate + almpc_get_sensitivity): with S the recursion runs in the stage state [dx_k; du_(k-1)]
+        (k_sens_face_rate), without it the call is sensitivity_stagewise to the byte."""
+        return self._sensitivity(self._f.sensitivity_stagewise_rate, want, act_tol)
+
+    def sensitivity_stagewise_rate_vjp(self, g_u, g_x=None, act_tol=0.0):
+        """sensitivity_stagewise_vjp for designs with or without S (almpc_sensitivity_stagewise_rate_vjp): (g_x0 (batch, n), rows (batch,))."""
+        return self._vjp(self._f.sensitivity_stagewise_rate_vjp, g_u, g_x, act_tol)
+
+    def sensitivity_rows(self, want=("K0", "dU", "dX"), act_tol_u=0.0, act_tol_x=0.0) -> dict:
+        """sensitivity for shared designs with a state box and / or the terminal equality as well (almpc_sensitivity_rows +
+        almpc_get_sensitivity): rows counts input, state-box and terminal-equality rows at a bound; act_tol_x is the state rows'
+        threshold (0: 1e-7, relative to max(1, |bound|)).  Without state rows it is sensitivity(want, act_tol_u), bit for bit."""
+        return self._sensitivity(self._f.sensitivity_rows, want, act_tol_u, act_tol_x)
+
+    def sensitivity_rows_vjp(self, g_u, g_x=None, act_tol_u=0.0, act_tol_x=0.0):
+        """sensitivity_vjp in the rows form (almpc_sensitivity_rows_vjp): (g_x0 (batch, n), rows (batch,))."""
+        return self._vjp(self._f.sensitivity_rows_vjp, g_u, g_x, (act_tol_u, act_tol_x))
+
+    def sensitivity_params_vjp(self, g_u, g_x=None, want=PARAM_GROUPS, act_tol=0.0, terminal="data") -> dict:
+        """Gradients of the loss of sensitivity_vjp in the problem data, per instance (almpc_sensitivity_params_vjp): x0, the QP's
+        linear term f, u_ref, the input box, the weights Q, P, R, S and the model A, B -- what `want` names -- and rows.  For a shared
+        design the caller sums over the batch.  terminal="data": P is data; "dare" (almpc_sensitivity_params_vjp_dare): P_i =
+        DARE(A_i, B_i, Q, R) is followed into Q, R, A, B, and the dict also carries dare_status (batch,): 0 followed, else the
+        instance keeps its P-as-data values (its P is not the stabilising DARE solution of the design's model)."""
+        dare = _terminal_gradient(terminal)
+        call = self._f.sensitivity_params_vjp_dare if dare else self._f.sensitivity_params_vjp
+        return _sens_params_vjp(call, self._t, self._check, g_u, g_x, want, act_tol, self.batch, self.n, self.m, self.N, dare)
+
+    # ---- certificate of the last step (include/almpc.h "Certificate of the last step")
+    def _certificate(self, call, want):
+        self._check(call(self._t, _cert_mask(want)))
+        return _cert_read(self._f.get_certificate, self._t, self._check, want, self.batch, self.n, self.m, self.N)
+
+    def certificate(self, want=("cost", "res", "grad", "costate")) -> dict:
+        """almpc_certificate + almpc_get_certificate: cost (batch,) the objective value, res (batch,) the KKT residual of the returned
+        inputs, grad (batch, m, N) the gradient of the objective in the inputs, costate (batch, n, N+1) (costate[:, :, 0] = dJ/dx0).
+        From the returned trajectories alone: every instance is certified whatever its status."""
+        return self._certificate(self._f.certificate, want)
+
+
+class Solver(_Target):
+    """Thin object wrapper of an almpc_handle: one device, one batch shard."""
+
+    _PREFIX = "almpc_"
+    _NO_U0 = True
+
+    def __init__(self, n, m, N, batch, device=0, timing=False, structured=False, structured_fallback=None):
+        """structured: ALMPC_FLAG_STRUCTURED (the stage-wise solve of the multiple-shooting form is the handle's solver: no m*N <= 128
+        limit).  structured_fallback: the redo of the instances a condensed step leaves without a certificate by the stage-wise
+        solvers -- None: the library default (on wherever they cover the design), True: required, False: off."""
+        self._bind(load(), n, m, N, batch)
+        h = _hp()
+        rc = self.L.almpc_create(ctypes.byref(h), self.n, self.m, self.N, self.batch, int(device),
+                                 (FLAG_TIMING if timing else 0) | (FLAG_STRUCTURED if structured else 0))
+        if rc != ALMPC_OK:
+            raise AlmpcError(rc, "almpc_create failed (is a gfx950 GPU visible? there is no CPU fallback)")
+        self.h = self._t = h
+        if structured_fallback is not None:
+            self._check(self.L.almpc_set_structured_fallback(self.h, 1 if structured_fallback else 0))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.almpc_destroy(self.h)
+            self.h = self._t = None
+
+    __del__ = close
+
+    # ---- what a design leaves on the handle
     def get_weights_instance(self, i):
         """dict(Q (n, n), R (m, m), S (m, m)): the weights instance i is designed on, as the design kernels read them
         (almpc_get_weights_instance)."""
@@ -815,6 +956,42 @@ class Solver:
         self._check(self.L.almpc_get_weights_instance(self.h, int(i), _ptr(Q), _ptr(R), _ptr(S)))
         return dict(Q=Q, R=R, S=S)
 
+    def get_gradient_instance(self, i):
+        q = np.empty(self.nz)
+        self._check(self.L.almpc_get_gradient_instance(self.h, int(i), _ptr(q)))
+        return q
+
+    def get_design_instance(self, i):
+        n, nz = self.n, self.nz
+        H = np.empty((nz, nz), order="F"); F = np.empty((nz, n), order="F"); d = np.empty(nz)
+        self._check(self.L.almpc_get_design_instance(self.h, int(i), _ptr(H), _ptr(F), _ptr(d)))
+        return dict(H=H, F=F, d=d)
+
+    def get_design(self):
+        n, nz = self.n, self.nz
+        H = np.empty((nz, nz), order="F"); F = np.empty((nz, n), order="F"); P = np.empty((n, n), order="F"); d = np.empty(nz)
+        self._check(self.L.almpc_get_design(self.h, _ptr(H), _ptr(F), _ptr(P), _ptr(d)))
+        return dict(H=H, F=F, P=P, d=d)
+
+    def terminal_weight_instance(self, i):
+        """(n, n) terminal weight instance i was designed with (almpc_get_terminal_weight_instance)."""
+        P = np.empty((self.n, self.n), order="F")
+        self._check(self.L.almpc_get_terminal_weight_instance(self.h, int(i), _ptr(P)))
+        return P
+
+    def model_instance(self, i):
+        """(A (n, n), B (n, m)): the DISCRETE model instance i is designed on (almpc_get_model_instance)."""
+        A, B = np.empty((self.n, self.n), order="F"), np.empty((self.n, self.m), order="F")
+        self._check(self.L.almpc_get_model_instance(self.h, int(i), _ptr(A), _ptr(B)))
+        return A, B
+
+    def relin_terminal_status(self):
+        """(batch,) int32 of the last relin_fnn step with the mode on: 0 = the instance's own DARE solution, 1 = the setup's P."""
+        out = np.zeros(self.batch, dtype=np.int32)
+        self._check(self.L.almpc_relin_fnn_terminal_status(self.h, out.ctypes.data_as(_ip)))
+        return out
+
+    # ---- time-varying designs and their certificate (include/almpc.h "Certificate of a step of a time-varying design")
     def set_keep_stage_models(self, on=True):
         """almpc_set_keep_stage_models: the next design_ltv keeps its stage models on the device for certificate_ltv
         (batch N n (n + m + 1) doubles of device memory)."""
@@ -830,115 +1007,29 @@ class Solver:
         if keep_stage_models is not None:
             self.set_keep_stage_models(keep_stage_models)
         self._state_rows(xmin, xmax, terminal)
-        self._check(self.L.almpc_set_rho_profile(self.h, {"scalar": 0, "stiffness": 1}[rho_profile]))
-        A = np.ascontiguousarray(np.asarray(A_all, dtype=np.float64).reshape(b, N, n, n).transpose(0, 1, 3, 2))
-        B = np.ascontiguousarray(np.asarray(B_all, dtype=np.float64).reshape(b, N, n, m).transpose(0, 1, 3, 2))
+        self._check(self.L.almpc_set_rho_profile(self.h, _rho_code(rho_profile)))
+        A, B = _blocks(A_all, b * N, n, n), _blocks(B_all, b * N, n, m)
         c = None if c_all is None else np.ascontiguousarray(np.asarray(c_all, dtype=np.float64).reshape(b, N, n))
-        xb = np.ascontiguousarray(np.asarray(xbar, dtype=np.float64).reshape(b, n, N + 1).transpose(0, 2, 1))
-        ub = np.ascontiguousarray(np.asarray(ubar, dtype=np.float64).reshape(b, m, N).transpose(0, 2, 1))
-        xr = None if x_ref is None else np.ascontiguousarray(np.asarray(x_ref, dtype=np.float64).reshape(n, N + 1).T)
-        ur = None if u_ref is None else np.ascontiguousarray(np.asarray(u_ref, dtype=np.float64).reshape(m, N).T)
-        Q, R = _colmajor(Q, (n, n)), _colmajor(R, (m, m))
-        S = None if S is None else _colmajor(S, (m, m))
-        P = np.asarray(P, dtype=np.float64)
-        p_inst = 0
-        if P.ndim == 3:
-            P = np.ascontiguousarray(P.reshape(b, n, n).transpose(0, 2, 1)); p_inst = 1
-        else:
-            P = _colmajor(P, (n, n))
-        umin = np.ascontiguousarray(umin, dtype=np.float64).reshape(m)
-        umax = np.ascontiguousarray(umax, dtype=np.float64).reshape(m)
+        xb, ub = _traj_batch(xbar, b, n, N + 1), _traj_batch(ubar, b, m, N)
+        xr, ur = _optional(_traj, x_ref, n, N + 1), _optional(_traj, u_ref, m, N)
+        Q, R, S = _colmajor(Q, (n, n)), _colmajor(R, (m, m)), _optional(_colmajor, S, (m, m))
+        P, p_inst = _terminal_weight(P, b, n)
+        umin, umax = _vec(umin, m), _vec(umax, m)
         self._check(self.L.almpc_design_ltv(self.h, _ptr(A), _ptr(B), _ptr(c), _ptr(xb), _ptr(ub), _ptr(xr), _ptr(ur), _ptr(Q), _ptr(R),
                                             _ptr(S), _ptr(P), p_inst, _ptr(umin), _ptr(umax), float(rho), float(sigma)))
 
-    def sqp_fnn_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu", rho=0.1,
-                      sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", qp_solver="condensed", net="fnn"):
-        """SQP outer loop for a network model (almpc_sqp_fnn_*): network (and net) as in fnn_linearize, x_ref (n, N+1) / u_ref (m, N) or None,
-        P (n, n) or (batch, n, n).  qp_solver: "condensed" (default) or "structured" (every QP through k_riccati, no condensed design).  xmin / xmax: the state box of the reference's NLP branch
-        (.../fnn/mpc_modeler_implementation_fnn.jl:146-153) as rows of every iteration's QP; terminal = "equality"."""
-        W_in, W_out = np.asfortranarray(W_in, dtype=np.float64), np.asfortranarray(W_out, dtype=np.float64)
-        H = W_in.shape[0]
-        nl = len(W_h)
-        Wh = np.ascontiguousarray(np.stack([np.asfortranarray(W, dtype=np.float64).T for W in W_h])) if nl else np.zeros((1, 1, 1))
-        bh = np.ascontiguousarray(np.stack([np.asarray(v, dtype=np.float64) for v in b_h])) if nl else np.zeros((1, 1))
-        self._sqp_setup(self.L.almpc_sqp_fnn_setup, H, nl, net_code(net, act), W_in, Wh, bh, W_out, x_ref, u_ref, Q, R, S, P, umin, umax,
-                        rho, sigma, rho_profile, xmin, xmax, terminal, qp_solver)
-
-    def sqp_densenet_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu",
-                           rho=0.1, sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", qp_solver="condensed"):
-        """sqp_fnn_setup for a DenseNet (almpc_sqp_densenet_setup; network as in densenet_linearize); then the sqp_fnn_* calls."""
-        H, nl, W_in, Wh, bh, W_out = _pack_densenet(W_in, W_h, b_h, W_out, self.n, self.m)
-        self._sqp_setup(self.L.almpc_sqp_densenet_setup, H, nl, _densenet_act(act), W_in, Wh, bh, W_out, x_ref, u_ref, Q, R, S, P, umin,
-                        umax, rho, sigma, rho_profile, xmin, xmax, terminal, qp_solver)
-
-    def _sqp_setup(self, setup, H, nl, code, W_in, Wh, bh, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, rho, sigma, rho_profile, xmin,
-                   xmax, terminal, qp_solver):
-        n, m, N, b = self.n, self.m, self.N, self.batch
-        self._state_rows(xmin, xmax, terminal)
-        self._check(self.L.almpc_sqp_fnn_set_structured(self.h, 1 if qp_solver == "structured" else 0))
-        self._check(self.L.almpc_set_rho_profile(self.h, {"scalar": 0, "stiffness": 1}[rho_profile]))
-        xr = None if x_ref is None else np.ascontiguousarray(np.asarray(x_ref, dtype=np.float64).reshape(n, N + 1).T)
-        ur = None if u_ref is None else np.ascontiguousarray(np.asarray(u_ref, dtype=np.float64).reshape(m, N).T)
-        Q, R = _colmajor(Q, (n, n)), _colmajor(R, (m, m))
-        S = None if S is None else _colmajor(S, (m, m))
-        P = np.asarray(P, dtype=np.float64)
-        p_inst = 0
-        if P.ndim == 3:
-            P = np.ascontiguousarray(P.reshape(b, n, n).transpose(0, 2, 1)); p_inst = 1
-        else:
-            P = _colmajor(P, (n, n))
-        umin = np.ascontiguousarray(umin, dtype=np.float64).reshape(m)
-        umax = np.ascontiguousarray(umax, dtype=np.float64).reshape(m)
-        self._check(setup(self.h, H, nl, code, _ptr(W_in), _ptr(Wh), _ptr(bh), _ptr(W_out), _ptr(xr), _ptr(ur), _ptr(Q), _ptr(R), _ptr(S),
-                          _ptr(P), p_inst, _ptr(umin), _ptr(umax), float(rho), float(sigma)))
-
-    def relin_fnn_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu", rho=0.1,
-                        sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", net="fnn"):
-        """Device-resident per-step re-linearisation of a network model (almpc_relin_fnn_*, BASELINE configs[3]): network (and net)
-        as in fnn_linearize, shared x_ref (n, N+1) / u_ref (m, N) or None, shared P (n, n); xmin / xmax / terminal as in design_batched."""
-        W_in, W_out = np.asfortranarray(W_in, dtype=np.float64), np.asfortranarray(W_out, dtype=np.float64)
-        H = W_in.shape[0]
-        nl = len(W_h)
-        Wh = np.ascontiguousarray(np.stack([np.asfortranarray(W, dtype=np.float64).T for W in W_h])) if nl else np.zeros((1, 1, 1))
-        bh = np.ascontiguousarray(np.stack([np.asarray(v, dtype=np.float64) for v in b_h])) if nl else np.zeros((1, 1))
-        self._relin_setup(self.L.almpc_relin_fnn_setup, H, nl, net_code(net, act), W_in, Wh, bh, W_out, x_ref, u_ref, Q, R, S, P, umin,
-                          umax, rho, sigma, rho_profile, xmin, xmax, terminal)
-
-    def relin_densenet_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu",
-                             rho=0.1, sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none"):
-        """relin_fnn_setup for a DenseNet (almpc_relin_densenet_setup; network as in densenet_linearize); then the relin_fnn_* calls."""
-        H, nl, W_in, Wh, bh, W_out = _pack_densenet(W_in, W_h, b_h, W_out, self.n, self.m)
-        self._relin_setup(self.L.almpc_relin_densenet_setup, H, nl, _densenet_act(act), W_in, Wh, bh, W_out, x_ref, u_ref, Q, R, S, P,
-                          umin, umax, rho, sigma, rho_profile, xmin, xmax, terminal)
-
-    def _relin_setup(self, setup, H, nl, code, W_in, Wh, bh, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, rho, sigma, rho_profile, xmin,
-                     xmax, terminal):
-        n, m, N = self.n, self.m, self.N
-        self._state_rows(xmin, xmax, terminal)
-        self._check(self.L.almpc_set_rho_profile(self.h, {"scalar": 0, "stiffness": 1}[rho_profile]))
-        xr = None if x_ref is None else np.ascontiguousarray(np.asarray(x_ref, dtype=np.float64).reshape(n, N + 1).T)
-        ur = None if u_ref is None else np.ascontiguousarray(np.asarray(u_ref, dtype=np.float64).reshape(m, N).T)
-        Q, R = _colmajor(Q, (n, n)), _colmajor(R, (m, m))
-        S = None if S is None else _colmajor(S, (m, m))
-        P = _colmajor(P, (n, n))
-        umin = np.ascontiguousarray(umin, dtype=np.float64).reshape(m)
-        umax = np.ascontiguousarray(umax, dtype=np.float64).reshape(m)
-        self._check(setup(self.h, H, nl, code, _ptr(W_in), _ptr(Wh), _ptr(bh), _ptr(W_out), _ptr(xr), _ptr(ur), _ptr(Q), _ptr(R), _ptr(S),
-                          _ptr(P), _ptr(umin), _ptr(umax), float(rho), float(sigma)))
-
-    def relin_fnn_step(self, opts: almpc_opts | None = None, sync=True):
-        fn = self.L.almpc_relin_fnn_step if sync else self.L.almpc_relin_fnn_step_async
-        self._check(fn(self.h, ctypes.byref(opts) if opts is not None else None))
-
-    def relin_fnn_advance(self):
-        """x0 <- fnn(x0, u[:,1]) on the device (closed loop of the black-box model)."""
-        self._check(self.L.almpc_relin_fnn_advance(self.h))
-
-    def relin_fnn_certificate(self, want=("cost", "res", "grad", "costate")) -> dict:
-        """almpc_relin_fnn_certificate + almpc_get_certificate: `certificate` of the last relin_fnn_step, with that step's own models,
-        terminal weights and weights."""
-        self._check(self.L.almpc_relin_fnn_certificate(self.h, _cert_mask(want)))
-        return _cert_read(self.L.almpc_get_certificate, self.h, self._check, want, self.batch, self.n, self.m, self.N)
+    def certificate_ltv(self, want=("cost", "res", "grad", "costate", "x", "e_x")) -> dict:
+        """almpc_certificate_ltv + almpc_get_certificate_ltv after design_ltv(keep_stage_models=True) and a step: cost (batch,), res (batch,),
+        grad (batch, m, N), costate (batch, n, N+1) (costate[:, :, k+1] = dJ/dc_k), x (batch, n, N+1) the predicted states xbar + dx and
+        e_x = x - x_ref, for what `want` names ("x" and "e_x" come together)."""
+        mask = _cert_mask(want, CERT_LTV)
+        self._check(self.L.almpc_certificate_ltv(self.h, mask))
+        b, n, m, N = self.batch, self.n, self.m, self.N
+        names = (want,) if isinstance(want, str) else tuple(want)
+        sizes = dict(cost=(b,), res=(b,), grad=(b, N, m), costate=(b, N + 1, n), x=(b, N + 1, n), e_x=(b, N + 1, n))
+        bufs = {k: (np.empty(sizes[k]) if k in names else None) for k in sizes}
+        self._check(self.L.almpc_get_certificate_ltv(self.h, *[_ptr(bufs[k]) for k in ("cost", "res", "grad", "costate", "x", "e_x")]))
+        return {k: (v if v.ndim == 1 else v.transpose(0, 2, 1)) for k, v in bufs.items() if v is not None}
 
     def relin_fnn_timing(self):
         a, d, s = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
@@ -963,94 +1054,6 @@ class Solver:
         self._check(self.L.almpc_comm_allgather_first_input(self.h, _ptr(out), None))
         return out
 
-    def sqp_fnn_start(self, x0, u_guess=None):
-        """x0 (batch, n); u_guess (batch, m, N) or None."""
-        x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).reshape(self.batch, self.n))
-        ug = None if u_guess is None else np.ascontiguousarray(np.asarray(u_guess, dtype=np.float64).reshape(self.batch, self.m, self.N).transpose(0, 2, 1))
-        self._check(self.L.almpc_sqp_fnn_start(self.h, _ptr(x0), _ptr(ug)))
-
-    def sqp_fnn_iterate(self, iters, step_scale=1.0, opts=None, step_rule="fixed"):
-        """-> (step_inf[iters], defect_inf[iters]); raises AlmpcError(ALMPC_ERR_NUMERIC) when an instance had to skip an iteration
-        (the histories are still filled: see .sqp_last).  step_rule: "fixed" | "merit" (l1 merit-function safeguard)."""
-        self._check(self.L.almpc_sqp_fnn_set_step_rule(self.h, {"fixed": 0, "merit": 1}[step_rule]))
-        st, de = np.zeros(int(iters)), np.zeros(int(iters))
-        self.sqp_last = (st, de)
-        self._check(self.L.almpc_sqp_fnn_iterate(self.h, int(iters), float(step_scale), ctypes.byref(opts) if opts is not None else None,
-                                                 _ptr(st), _ptr(de)))
-        return st, de
-
-    def sqp_fnn_solve(self, max_iters, tol, opts=None, step_rule="merit"):
-        """Solve to a tolerance (almpc_sqp_fnn_solve): at most max_iters iterations, each instance frozen once its iterate passes the
-        first-order test (zero defects, projected adjoint-gradient residual <= tol).  -> dict(status (batch,) int32: 0 converged,
-        1 iteration limit, 2 skipped, 3 infeasible QP; iters (batch,) int32; kkt (batch,) residual of the last test).
-        The step rule is a setting of the handle and stays in force: a later sqp_fnn_iterate sets its own (default "fixed")."""
-        self._check(self.L.almpc_sqp_fnn_set_step_rule(self.h, {"fixed": 0, "merit": 1}[step_rule]))
-        st, it, kk = np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch)
-        self._check(self.L.almpc_sqp_fnn_solve(self.h, int(max_iters), float(tol), ctypes.byref(opts) if opts is not None else None,
-                                               st.ctypes.data_as(_ip), it.ctypes.data_as(_ip), _ptr(kk)))
-        return dict(status=st, iters=it, kkt=kk)
-
-    def sqp_fnn_set_hessian(self, mode):
-        """Hessian of the loop's QPs: "gauss_newton" (default) or "exact" (almpc_sqp_fnn_set_hessian); stays in force."""
-        self._check(self.L.almpc_sqp_fnn_set_hessian(self.h, SQP_HESSIANS[mode]))
-
-    def sqp_fnn_set_row_multipliers(self, on):
-        """State rows (state box, terminal equality) in the loop's stopping test and exact Hessian: the finishes hand the row multipliers
-        of every iteration's QP out (almpc_sqp_fnn_set_row_multipliers; default off, stays in force)."""
-        self._check(self.L.almpc_sqp_fnn_set_row_multipliers(self.h, 1 if on else 0))
-
-    def sqp_fnn_state_multipliers(self):
-        """-> (batch, n, N): multiplier of the row of x_{k+1}[i] at [:, i, k] in each instance's last solved QP (> 0 upper bound, < 0 lower
-        bound, free on a terminal-equality row, 0 outside the working set); zeros with the switch off or without state rows."""
-        mu = np.zeros((self.batch, self.N, self.n))
-        self._check(self.L.almpc_sqp_fnn_state_multipliers(self.h, _ptr(mu)))
-        return np.ascontiguousarray(mu.transpose(0, 2, 1))
-
-    def sqp_fnn_skipped(self):
-        out = np.zeros(self.batch, dtype=np.int32)
-        self._check(self.L.almpc_sqp_fnn_skipped(self.h, out.ctypes.data_as(_ip)))
-        return out
-
-    def get_gradient_instance(self, i):
-        q = np.empty(self.nz)
-        self._check(self.L.almpc_get_gradient_instance(self.h, int(i), _ptr(q)))
-        return q
-
-    def get_design_instance(self, i):
-        n, nz = self.n, self.nz
-        H = np.empty((nz, nz), order="F"); F = np.empty((nz, n), order="F"); d = np.empty(nz)
-        self._check(self.L.almpc_get_design_instance(self.h, int(i), _ptr(H), _ptr(F), _ptr(d)))
-        return dict(H=H, F=F, d=d)
-
-    def set_terminal_weight(self, mode):
-        """Before a design: "given" / 0 (default) or "dare_device" / 1 -- design_batched(P=None) and every relin_fnn step take each
-        instance's terminal weight from the DARE of its own model, solved on the device (almpc_set_terminal_weight)."""
-        self._check(self.L.almpc_set_terminal_weight(self.h, _terminal_mode(mode)))
-
-    def relin_terminal_status(self):
-        """(batch,) int32 of the last relin_fnn step with the mode on: 0 = the instance's own DARE solution, 1 = the setup's P."""
-        out = np.zeros(self.batch, dtype=np.int32)
-        self._check(self.L.almpc_relin_fnn_terminal_status(self.h, out.ctypes.data_as(_ip)))
-        return out
-
-    def terminal_weight_instance(self, i):
-        """(n, n) terminal weight instance i was designed with (almpc_get_terminal_weight_instance)."""
-        P = np.empty((self.n, self.n), order="F")
-        self._check(self.L.almpc_get_terminal_weight_instance(self.h, int(i), _ptr(P)))
-        return P
-
-    def set_model_time(self, mode, Ts=0.0):
-        """Before a design: "discrete" / 0 (default) or "continuous" / 1 with the sample time Ts -- the models given to design_shared and
-        design_batched, and the network of the relin_fnn pipeline, are continuous-time and are discretised by zero-order hold at Ts
-        (almpc_set_model_time)."""
-        self._check(self.L.almpc_set_model_time(self.h, _model_time_mode(mode), float(Ts)))
-
-    def model_instance(self, i):
-        """(A (n, n), B (n, m)): the DISCRETE model instance i is designed on (almpc_get_model_instance)."""
-        A, B = np.empty((self.n, self.n), order="F"), np.empty((self.n, self.m), order="F")
-        self._check(self.L.almpc_get_model_instance(self.h, int(i), _ptr(A), _ptr(B)))
-        return A, B
-
     def start_from(self, other: "Solver"):
         """Structured handle: the next calculate starts from `other`'s last inputs (same batch, horizon <= this one's): horizon
         continuation / chaining of solvers (almpc_set_start_from)."""
@@ -1060,48 +1063,8 @@ class Solver:
         """One kernel per step (default) or the two-kernel path whose stage times can be told apart."""
         self._check(self.L.almpc_set_step_fusion(self.h, 1 if on else 0))
 
-    def set_reference(self, x_ref, u_ref, per_instance=False):
-        """x_ref (n, N+1) / u_ref (m, N), or with per_instance (batch, n, N+1) / (batch, m, N)."""
-        n, m, N = self.n, self.m, self.N
-        x_ref, u_ref = np.asarray(x_ref, dtype=np.float64), np.asarray(u_ref, dtype=np.float64)
-        if per_instance:
-            xr = np.ascontiguousarray(x_ref.reshape(self.batch, n, N + 1).transpose(0, 2, 1))
-            ur = np.ascontiguousarray(u_ref.reshape(self.batch, m, N).transpose(0, 2, 1))
-        else:
-            xr = np.ascontiguousarray(x_ref.reshape(n, N + 1).T)
-            ur = np.ascontiguousarray(u_ref.reshape(m, N).T)
-        self._check(self.L.almpc_set_reference(self.h, _ptr(xr), _ptr(ur), 1 if per_instance else 0))
-
-    def update_initialization(self, x0):
-        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(self.batch, self.n)
-        self._check(self.L.almpc_update_initialization(self.h, _ptr(x0)))
-
     def update_initialization_device(self, dev_ptr: int):
         self._check(self.L.almpc_update_initialization_device(self.h, ctypes.c_void_p(dev_ptr)))
-
-    def calculate(self, opts: almpc_opts | None = None, sync=True):
-        fn = self.L.almpc_calculate if sync else self.L.almpc_calculate_async
-        self._check(fn(self.h, None if opts is None else ctypes.byref(opts)))
-
-    def synchronize(self):
-        self._check(self.L.almpc_synchronize(self.h))
-
-    def get_results(self, want=("x", "e_x", "u", "e_u", "status", "iters", "polish_iters")):
-        b, n, m, N = self.batch, self.n, self.m, self.N
-        bufs = {}
-        if "x" in want: bufs["x"] = np.empty((b, N + 1, n))
-        if "e_x" in want: bufs["e_x"] = np.empty((b, N + 1, n))
-        if "u" in want: bufs["u"] = np.empty((b, N, m))
-        if "e_u" in want: bufs["e_u"] = np.empty((b, N, m))
-        for k in ("status", "iters", "polish_iters"):
-            if k in want: bufs[k] = np.empty(b, dtype=np.int32)
-        ip = lambda k: bufs[k].ctypes.data_as(_ip) if k in bufs else None
-        self._check(self.L.almpc_get_results(self.h, _ptr(bufs.get("x")), _ptr(bufs.get("e_x")), _ptr(bufs.get("u")),
-                                             _ptr(bufs.get("e_u")), ip("status"), ip("iters"), ip("polish_iters")))
-        # Julia-shaped views: (batch, n, N+1) and (batch, m, N)
-        for k in ("x", "e_x", "u", "e_u"):
-            if k in bufs: bufs[k] = bufs[k].transpose(0, 2, 1)
-        return bufs
 
     # ---- host-facing step path: pinned staging, transfers on copy streams (include/almpc.h "Host-facing step path")
     def update_initialization_async(self, x0):
@@ -1116,135 +1079,27 @@ class Solver:
         self._check(self.L.almpc_x0_staging(self.h, ctypes.byref(ptr)))
         return np.ctypeslib.as_array(ptr, shape=(self.batch, self.n))
 
-    def get_results_async(self, want=("u0", "status")) -> int:
-        """Ask for results of the last enqueued step (names of WANT; "u0" = u[:, 1] of every instance); returns a ticket."""
-        t = self.L.almpc_get_results_async(self.h, _want_mask(want))
-        if t < 0:
-            self._check(t)
-        return t
+    _results_copy = _Target.get_results_wait
 
     def get_results_wait(self, ticket, want=("u0", "status"), copy=True):
         """Results of a ticket.  copy=True: fresh arrays (almpc_get_results_wait); copy=False: views of the handle's pinned slot
         (almpc_host_results: zero-copy, valid until two more requests).  Shapes as get_results; u0 (batch, m)."""
-        b, n, m, N = self.batch, self.n, self.m, self.N
-        shapes = {"x": (b, N + 1, n), "e_x": (b, N + 1, n), "u": (b, N, m), "e_u": (b, N, m), "u0": (b, m),
-                  "status": (b,), "iters": (b,), "polish_iters": (b,)}
-        order = ("x", "e_x", "u", "e_u", "u0", "status", "iters", "polish_iters")
+        if copy:
+            return self._results_copy(ticket, want)
         want = set(want)
         _want_mask(want)
-        if copy:
-            bufs = {k: np.empty(shapes[k], dtype=np.int32 if k in ("status", "iters", "polish_iters") else np.float64) for k in want}
-            args = [(bufs[k].ctypes.data_as(_ip if bufs[k].dtype == np.int32 else _dp) if k in bufs else None) for k in order]
-            self._check(self.L.almpc_get_results_wait(self.h, int(ticket), *args))
-        else:
-            self._check(self.L.almpc_get_results_wait(self.h, int(ticket), *([None] * 8)))
-            ps = [ctypes.c_void_p() for _ in order]
-            self._check(self.L.almpc_host_results(self.h, int(ticket), *[ctypes.byref(q) for q in ps]))
-            bufs = {}
-            for k, q in zip(order, ps):
-                if k in want:
-                    if not q.value:
-                        raise AlmpcError(-1, f"result {k!r} was not part of the request of ticket {ticket}")
-                    ct = ctypes.c_int32 if k in ("status", "iters", "polish_iters") else ctypes.c_double
-                    cnt = int(np.prod(shapes[k]))
-                    bufs[k] = np.ctypeslib.as_array(ctypes.cast(q.value, ctypes.POINTER(ct)), shape=(cnt,)).reshape(shapes[k])
-        for k in ("x", "e_x", "u", "e_u"):
-            if k in bufs: bufs[k] = bufs[k].transpose(0, 2, 1)
+        self._check(self.L.almpc_get_results_wait(self.h, int(ticket), *([None] * 8)))
+        ps = [ctypes.c_void_p() for _ in self._results]
+        self._check(self.L.almpc_host_results(self.h, int(ticket), *[ctypes.byref(q) for q in ps]))
+        bufs = {}
+        for k, q in zip(self._results, ps):
+            if k in want:
+                if not q.value:
+                    raise AlmpcError(-1, f"result {k!r} was not part of the request of ticket {ticket}")
+                shape, dtype, ptype = self._results[k]
+                a = np.ctypeslib.as_array(ctypes.cast(q.value, ptype), shape=(int(np.prod(shape)),)).reshape(shape)
+                bufs[k] = a.transpose(0, 2, 1) if len(shape) == 3 else a
         return bufs
-
-    # ---- sensitivities of the last step to x0 (include/almpc.h "Sensitivities"; an extension beyond the reference's surface)
-    def sensitivity(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
-        """almpc_sensitivity + almpc_get_sensitivity: K0 (batch, m, n) = du[:,1]/dx0, dU (batch, m, N, n), dX (batch, n, N+1, n),
-        each [b, i, k, c] = d(entry i of stage k) / d x0[c], and rows (batch,) = rows at a bound (-1: instance not solved, zeros).
-        act_tol <= 0: 1e-9 (in units of the row's Jacobi scale)."""
-        self._check(self.L.almpc_sensitivity(self.h, _sens_mask(want), float(act_tol)))
-        return _sens_read(self.L.almpc_get_sensitivity, self.h, self._check, want, self.batch, self.n, self.m, self.N)
-
-    def device_sensitivity(self):
-        ps = [ctypes.c_void_p() for _ in range(4)]
-        self._check(self.L.almpc_device_sensitivity(self.h, *[ctypes.byref(p) for p in ps]))
-        return dict(zip(("K0", "dU", "dX", "rows"), [p.value for p in ps]))
-
-    # ---- certificate of the last step (include/almpc.h "Certificate of the last step")
-    def certificate(self, want=("cost", "res", "grad", "costate")) -> dict:
-        """almpc_certificate + almpc_get_certificate: cost (batch,) the objective value, res (batch,) the KKT residual of the returned
-        inputs, grad (batch, m, N) the gradient of the objective in the inputs, costate (batch, n, N+1) (costate[:, :, 0] = dJ/dx0).
-        From the returned trajectories alone: every instance is certified whatever its status."""
-        self._check(self.L.almpc_certificate(self.h, _cert_mask(want)))
-        return _cert_read(self.L.almpc_get_certificate, self.h, self._check, want, self.batch, self.n, self.m, self.N)
-
-    def device_certificate(self):
-        ps = [ctypes.c_void_p() for _ in range(4)]
-        self._check(self.L.almpc_device_certificate(self.h, *[ctypes.byref(p) for p in ps]))
-        return dict(zip(("cost", "res", "grad", "costate"), [p.value for p in ps]))
-
-    # ---- ... of a step of a time-varying design (include/almpc.h "Certificate of a step of a time-varying design")
-    def certificate_ltv(self, want=("cost", "res", "grad", "costate", "x", "e_x")) -> dict:
-        """almpc_certificate_ltv + almpc_get_certificate_ltv after design_ltv(keep_stage_models=True) and a step: cost (batch,), res (batch,),
-        grad (batch, m, N), costate (batch, n, N+1) (costate[:, :, k+1] = dJ/dc_k), x (batch, n, N+1) the predicted states xbar + dx and
-        e_x = x - x_ref, for what `want` names ("x" and "e_x" come together)."""
-        mask = _cert_mask(want, CERT_LTV)
-        self._check(self.L.almpc_certificate_ltv(self.h, mask))
-        b, n, m, N = self.batch, self.n, self.m, self.N
-        names = (want,) if isinstance(want, str) else tuple(want)
-        shapes = dict(cost=(b,), res=(b,), grad=(b, N, m), costate=(b, N + 1, n), x=(b, N + 1, n), e_x=(b, N + 1, n))
-        bufs = {k: (np.empty(shapes[k]) if k in names else None) for k in shapes}
-        self._check(self.L.almpc_get_certificate_ltv(self.h, *[_ptr(bufs[k]) for k in ("cost", "res", "grad", "costate", "x", "e_x")]))
-        return {k: (v if v.ndim == 1 else v.transpose(0, 2, 1)) for k, v in bufs.items() if v is not None}
-
-    def device_certificate_ltv(self):
-        ps = [ctypes.c_void_p() for _ in range(6)]
-        self._check(self.L.almpc_device_certificate_ltv(self.h, *[ctypes.byref(p) for p in ps]))
-        return dict(zip(("cost", "res", "grad", "costate", "x", "e_x"), [p.value for p in ps]))
-
-    def sensitivity_vjp(self, g_u, g_x=None, act_tol=0.0):
-        """dL/dx0 (batch, n) for a loss with gradients g_u (batch, m, N) and g_x (batch, n, N+1) or None on the returned
-        trajectories (almpc_sensitivity_vjp: no Jacobian is formed); also returns rows (batch,)."""
-        return _sens_vjp(self.L.almpc_sensitivity_vjp, self.h, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
-
-    def sensitivity_stagewise(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
-        """sensitivity on a structured handle (almpc_sensitivity_stagewise + almpc_get_sensitivity): the Riccati recursion on the face
-        where the inputs at a bound are held; input box only, S = 0.  act_tol is relative to the width of the input box (0: 1e-7)."""
-        self._check(self.L.almpc_sensitivity_stagewise(self.h, _sens_mask(want), float(act_tol)))
-        return _sens_read(self.L.almpc_get_sensitivity, self.h, self._check, want, self.batch, self.n, self.m, self.N)
-
-    def sensitivity_stagewise_vjp(self, g_u, g_x=None, act_tol=0.0):
-        """sensitivity_vjp on a structured handle (almpc_sensitivity_stagewise_vjp): (g_x0 (batch, n), rows (batch,))."""
-        return _sens_vjp(self.L.almpc_sensitivity_stagewise_vjp, self.h, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
-
-    def sensitivity_stagewise_rate(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
-        """sensitivity_stagewise for every structured input-box design, with or without an input-rate weight S
-        (almpc_sensitivity_stagewise_rate + almpc_get_sensitivity): with S the recursion runs in the stage state [dx_k; du_(k-1)]
-        (k_sens_face_rate), without it the call is sensitivity_stagewise to the byte."""
-        self._check(self.L.almpc_sensitivity_stagewise_rate(self.h, _sens_mask(want), float(act_tol)))
-        return _sens_read(self.L.almpc_get_sensitivity, self.h, self._check, want, self.batch, self.n, self.m, self.N)
-
-    def sensitivity_stagewise_rate_vjp(self, g_u, g_x=None, act_tol=0.0):
-        """sensitivity_stagewise_vjp for designs with or without S (almpc_sensitivity_stagewise_rate_vjp): (g_x0 (batch, n), rows (batch,))."""
-        return _sens_vjp(self.L.almpc_sensitivity_stagewise_rate_vjp, self.h, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m,
-                         self.N)
-
-    def sensitivity_params_vjp(self, g_u, g_x=None, want=PARAM_GROUPS, act_tol=0.0, terminal="data") -> dict:
-        """Gradients of the loss of sensitivity_vjp in the problem data, per instance (almpc_sensitivity_params_vjp): x0, the QP's
-        linear term f, u_ref, the input box, the weights Q, P, R, S and the model A, B -- what `want` names -- and rows.  For a shared
-        design the caller sums over the batch.  terminal="data": P is data; "dare" (almpc_sensitivity_params_vjp_dare): P_i =
-        DARE(A_i, B_i, Q, R) is followed into Q, R, A, B, and the dict also carries dare_status (batch,): 0 followed, else the
-        instance keeps its P-as-data values (its P is not the stabilising DARE solution of the design's model)."""
-        dare = _terminal_gradient(terminal)
-        call = self.L.almpc_sensitivity_params_vjp_dare if dare else self.L.almpc_sensitivity_params_vjp
-        return _sens_params_vjp(call, self.h, self._check, g_u, g_x, want, act_tol, self.batch, self.n, self.m, self.N, dare)
-
-    def sensitivity_rows(self, want=("K0", "dU", "dX"), act_tol_u=0.0, act_tol_x=0.0) -> dict:
-        """sensitivity for shared designs with a state box and / or the terminal equality as well (almpc_sensitivity_rows +
-        almpc_get_sensitivity): rows counts input, state-box and terminal-equality rows at a bound; act_tol_x is the state rows'
-        threshold (0: 1e-7, relative to max(1, |bound|)).  Without state rows it is sensitivity(want, act_tol_u), bit for bit."""
-        self._check(self.L.almpc_sensitivity_rows(self.h, _sens_mask(want), float(act_tol_u), float(act_tol_x)))
-        return _sens_read(self.L.almpc_get_sensitivity, self.h, self._check, want, self.batch, self.n, self.m, self.N)
-
-    def sensitivity_rows_vjp(self, g_u, g_x=None, act_tol_u=0.0, act_tol_x=0.0):
-        """sensitivity_vjp in the rows form (almpc_sensitivity_rows_vjp): (g_x0 (batch, n), rows (batch,))."""
-        return _sens_vjp(self.L.almpc_sensitivity_rows_vjp, self.h, self._check, g_u, g_x, (act_tol_u, act_tol_x), self.batch, self.n,
-                         self.m, self.N)
 
     def get_first_input(self):
         """u[:, 1] of every instance, (batch, m): what a receding-horizon caller applies (almpc_get_first_input)."""
@@ -1252,24 +1107,29 @@ class Solver:
         self._check(self.L.almpc_get_first_input(self.h, _ptr(u0)))
         return u0
 
-    def get_design(self):
-        n, nz = self.n, self.nz
-        H = np.empty((nz, nz), order="F"); F = np.empty((nz, n), order="F"); P = np.empty((n, n), order="F"); d = np.empty(nz)
-        self._check(self.L.almpc_get_design(self.h, _ptr(H), _ptr(F), _ptr(P), _ptr(d)))
-        return dict(H=H, F=F, P=P, d=d)
+    # ---- device pointers of the last results (valid until the next call that computes them)
+    def _device_views(self, call, names):
+        ps = [ctypes.c_void_p() for _ in names]
+        self._check(call(self.h, *[ctypes.byref(p) for p in ps]))
+        return dict(zip(names, [p.value for p in ps]))
 
     def device_results(self):
-        ps = [ctypes.c_void_p() for _ in range(4)]
-        self._check(self.L.almpc_device_results(self.h, *[ctypes.byref(p) for p in ps]))
-        return dict(zip(("x", "e_x", "u", "e_u"), [p.value for p in ps]))
+        return self._device_views(self.L.almpc_device_results, ("x", "e_x", "u", "e_u"))
 
+    def device_sensitivity(self):
+        return self._device_views(self.L.almpc_device_sensitivity, ("K0", "dU", "dX", "rows"))
+
+    def device_certificate(self):
+        return self._device_views(self.L.almpc_device_certificate, ("cost", "res", "grad", "costate"))
+
+    def device_certificate_ltv(self):
+        return self._device_views(self.L.almpc_device_certificate_ltv, ("cost", "res", "grad", "costate", "x", "e_x"))
+
+    # ---- timing (ALMPC_FLAG_TIMING) and test hooks
     def get_timing(self):
         v = [ctypes.c_float() for _ in range(4)]
         self._check(self.L.almpc_get_timing(self.h, *[ctypes.byref(x) for x in v]))
         return dict(zip(("admm_ms", "polish_ms", "rollout_ms", "total_ms"), [x.value for x in v]))
-
-    def advance_plant(self):
-        self._check(self.L.almpc_advance_plant(self.h))
 
     def debug_poison_lds(self):
         self._check(self.L.almpc_debug_poison_lds(self.h))
@@ -1301,31 +1161,31 @@ class _HandleView(Solver):
     """A Solver over a handle owned by a Group (no create / destroy of its own)."""
 
     def __init__(self, L, h, n, m, N, batch):
-        self.L, self.h = L, h
-        self.n, self.m, self.N, self.batch = n, m, N, batch
-        self.nz = m * N
+        self._bind(L, n, m, N, batch)
+        self.h = self._t = h
 
     def close(self):
-        self.h = None
+        self.h = self._t = None
 
     __del__ = close
 
 
-class Group:
+class Group(_Target):
     """One process, several GPUs (almpc_group_*): one handle per entry of `devices` on its contiguous shard of the batch; every call
     fans out over the handles, nothing on the step path synchronises across devices.  Host arrays cover the whole batch."""
 
+    _PREFIX = "almpc_group_"
+    _NO_U0 = False
+
     def __init__(self, n, m, N, batch, devices, timing=False, structured=False, structured_fallback=None):
-        self.L = load()
-        self.n, self.m, self.N, self.batch = int(n), int(m), int(N), int(batch)
-        self.nz = self.m * self.N
+        self._bind(load(), n, m, N, batch)
         devs = (ctypes.c_int * len(devices))(*[int(d) for d in devices])
         g = _hp()
         rc = self.L.almpc_group_create(ctypes.byref(g), self.n, self.m, self.N, self.batch, len(devices), devs,
                                        (FLAG_TIMING if timing else 0) | (FLAG_STRUCTURED if structured else 0))
         if rc != ALMPC_OK:
             raise AlmpcError(rc, "almpc_group_create failed (are the devices visible? there is no CPU fallback)")
-        self.g = g
+        self.g = self._t = g
         self.shards = []
         for i in range(len(devices)):
             f, c = ctypes.c_int(), ctypes.c_int()
@@ -1336,179 +1196,45 @@ class Group:
         if structured_fallback is not None:
             self._check(self.L.almpc_group_set_structured_fallback(self.g, 1 if structured_fallback else 0))
 
-    def _check(self, rc):
-        if rc != ALMPC_OK:
-            raise AlmpcError(rc, (self.L.almpc_group_last_error(self.g) or b"").decode())
+    def close(self):
+        if getattr(self, "g", None):
+            for hv in self.handles:
+                hv.close()
+            self.L.almpc_group_destroy(self.g)
+            self.g = self._t = None
 
-    def set_terminal_weight(self, mode):
-        """Solver.set_terminal_weight on every handle (almpc_group_set_terminal_weight)."""
-        self._check(self.L.almpc_group_set_terminal_weight(self.g, _terminal_mode(mode)))
+    __del__ = close
 
-    def set_model_time(self, mode, Ts=0.0):
-        """Solver.set_model_time on every handle (almpc_group_set_model_time)."""
-        self._check(self.L.almpc_group_set_model_time(self.g, _model_time_mode(mode), float(Ts)))
-
-    def model_instance(self, i):
+    # ---- what only the handles have: by shard
+    def _shard_of(self, i):
+        """(the handle that holds instance i, its index there)"""
         for h, (f, c) in zip(self.handles, self.shards):
             if f <= i < f + c:
-                return h.model_instance(i - f)
+                return h, i - f
         raise IndexError(i)
+
+    def model_instance(self, i):
+        h, k = self._shard_of(i)
+        return h.model_instance(k)
+
+    def terminal_weight_instance(self, i):
+        h, k = self._shard_of(i)
+        return h.terminal_weight_instance(k)
 
     def relin_terminal_status(self):
         return np.concatenate([h.relin_terminal_status() for h in self.handles])
 
-    def terminal_weight_instance(self, i):
-        for h, (f, c) in zip(self.handles, self.shards):
-            if f <= i < f + c:
-                return h.terminal_weight_instance(i - f)
-        raise IndexError(i)
-
-    def _state_rows(self, xmin, xmax, terminal):
-        if (xmin is None) != (xmax is None):
-            raise ValueError("give both xmin and xmax or neither")
-        self._check(self.L.almpc_group_set_terminal_equality(self.g, 1 if terminal == "equality" else 0))
-        lo = None if xmin is None else np.ascontiguousarray(xmin, dtype=np.float64).reshape(self.n)
-        hi = None if xmax is None else np.ascontiguousarray(xmax, dtype=np.float64).reshape(self.n)
-        self._check(self.L.almpc_group_set_state_box(self.g, _ptr(lo), _ptr(hi)))
-
-    def design_batched(self, A_batch, B_batch, Q, R, S=None, P=None, umin=None, umax=None, rho=0.1, sigma=1e-6, rho_profile="scalar",
-                       xmin=None, xmax=None, terminal="none"):
-        """almpc_group_design_batched: arguments of Solver.design_batched for the whole batch."""
-        n, m, b = self.n, self.m, self.batch
-        self._state_rows(xmin, xmax, terminal)
-        self._check(self.L.almpc_group_set_rho_profile(self.g, {"scalar": 0, "stiffness": 1}[rho_profile]))
-        A = np.ascontiguousarray(np.asarray(A_batch, dtype=np.float64).reshape(b, n, n).transpose(0, 2, 1))
-        B = np.ascontiguousarray(np.asarray(B_batch, dtype=np.float64).reshape(b, n, m).transpose(0, 2, 1))
-        Q, R = _colmajor(Q, (n, n)), _colmajor(R, (m, m))
-        S = None if S is None else _colmajor(S, (m, m))
-        p_inst = 0
-        if P is not None:
-            P = np.asarray(P, dtype=np.float64)
-            if P.ndim == 3:
-                P = np.ascontiguousarray(P.reshape(b, n, n).transpose(0, 2, 1)); p_inst = 1
-            else:
-                P = _colmajor(P, (n, n))
-        umin = np.ascontiguousarray(umin, dtype=np.float64).reshape(m)
-        umax = np.ascontiguousarray(umax, dtype=np.float64).reshape(m)
-        self._check(self.L.almpc_group_design_batched(self.g, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(S), _ptr(P), p_inst, _ptr(umin),
-                                                      _ptr(umax), float(rho), float(sigma)))
-
-    def design_batched_weighted(self, A_batch, B_batch, Q_batch, R_batch, S_batch=None, P=None, umin=None, umax=None, rho=0.1, sigma=1e-6,
-                                rho_profile="scalar", xmin=None, xmax=None, terminal="none"):
-        """almpc_group_design_batched_weighted: arguments of Solver.design_batched_weighted for the whole batch."""
-        self._state_rows(xmin, xmax, terminal)
-        self._check(self.L.almpc_group_set_rho_profile(self.g, {"scalar": 0, "stiffness": 1}[rho_profile]))
-        args, p_inst = _weighted_design_args(self.n, self.m, self.batch, A_batch, B_batch, Q_batch, R_batch, S_batch, P, umin, umax)
-        self._check(self.L.almpc_group_design_batched_weighted(self.g, *[_ptr(a) for a in args[:6]], p_inst, _ptr(args[6]), _ptr(args[7]),
-                                                               float(rho), float(sigma)))
-
-    def _fnn_args(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, act, p_batched, net="fnn"):
-        n, m, N = self.n, self.m, self.N
-        W_in = np.asarray(W_in, dtype=np.float64)
-        H = W_in.shape[0]
-        if net == "densenet":   # (the DenseNet layout and a bare activation: the *_densenet_setup calls)
-            H, nl, W_in, Wh, bh, W_out = _pack_densenet(W_in, W_h, b_h, W_out, n, m)
-        else:
-            W_h = [np.asarray(w, dtype=np.float64) for w in W_h]
-            nl = len(W_h)
-            Wh = np.ascontiguousarray(np.stack([w.T for w in W_h])) if nl else None
-            bh = np.ascontiguousarray(np.stack([np.asarray(v, dtype=np.float64) for v in b_h])) if nl else None
-        xr = np.ascontiguousarray(np.asarray(x_ref, dtype=np.float64).reshape(n, N + 1).T)
-        ur = np.ascontiguousarray(np.asarray(u_ref, dtype=np.float64).reshape(m, N).T)
-        P = np.asarray(P, dtype=np.float64)
-        p_inst = 0
-        if p_batched and P.ndim == 3:
-            P = np.ascontiguousarray(P.reshape(self.batch, n, n).transpose(0, 2, 1)); p_inst = 1
-        else:
-            P = _colmajor(P, (n, n))
-        arrs = [_colmajor(W_in, (H, n + m)), Wh, bh, _colmajor(W_out, (n, H * (nl + 1 if net == "densenet" else 1))), xr, ur, _colmajor(Q, (n, n)), _colmajor(R, (m, m)),
-                None if S is None else _colmajor(S, (m, m)), P,
-                np.ascontiguousarray(umin, dtype=np.float64).reshape(m), np.ascontiguousarray(umax, dtype=np.float64).reshape(m)]
-        return H, nl, _densenet_act(act) if net == "densenet" else net_code(net, act), arrs, p_inst
-
-    def relin_fnn_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu", rho=0.1,
-                        sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", net="fnn"):
-        self._state_rows(xmin, xmax, terminal)
-        self._check(self.L.almpc_group_set_rho_profile(self.g, {"scalar": 0, "stiffness": 1}[rho_profile]))
-        H, nl, a, arrs, _ = self._fnn_args(W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, act, False, net)
-        self._keep = arrs
-        self._check(self.L.almpc_group_relin_fnn_setup(self.g, H, nl, a, *[_ptr(v) for v in arrs], float(rho), float(sigma)))
-
-    def relin_densenet_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu",
-                             rho=0.1, sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none"):
-        """almpc_group_relin_densenet_setup: Solver.relin_densenet_setup on every device."""
-        self._state_rows(xmin, xmax, terminal)
-        self._check(self.L.almpc_group_set_rho_profile(self.g, {"scalar": 0, "stiffness": 1}[rho_profile]))
-        H, nl, a, arrs, _ = self._fnn_args(W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, act, False, "densenet")
-        self._keep = arrs
-        self._check(self.L.almpc_group_relin_densenet_setup(self.g, H, nl, a, *[_ptr(v) for v in arrs], float(rho), float(sigma)))
-
-    def relin_fnn_step(self, opts: almpc_opts | None = None, sync=True):
-        fn = self.L.almpc_group_relin_fnn_step if sync else self.L.almpc_group_relin_fnn_step_async
-        self._check(fn(self.g, None if opts is None else ctypes.byref(opts)))
-
-    def relin_fnn_advance(self):
-        self._check(self.L.almpc_group_relin_fnn_advance(self.g))
-
-    def advance_plant(self):
-        self._check(self.L.almpc_group_advance_plant(self.g))
-
-    def sqp_fnn_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu", rho=0.1,
-                      sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", qp_solver="condensed", net="fnn"):
-        self._state_rows(xmin, xmax, terminal)
-        self._check(self.L.almpc_group_set_rho_profile(self.g, {"scalar": 0, "stiffness": 1}[rho_profile]))
-        self._check(self.L.almpc_group_sqp_fnn_set_structured(self.g, 1 if qp_solver == "structured" else 0))
-        H, nl, a, arrs, p_inst = self._fnn_args(W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, act, True, net)
-        self._keep = arrs
-        ptrs = [_ptr(v) for v in arrs]
-        self._check(self.L.almpc_group_sqp_fnn_setup(self.g, H, nl, a, *ptrs[:10], p_inst, ptrs[10], ptrs[11], float(rho), float(sigma)))
-
-    def sqp_densenet_setup(self, W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None, act="relu",
-                           rho=0.1, sigma=1e-6, rho_profile="scalar", xmin=None, xmax=None, terminal="none", qp_solver="condensed"):
-        """almpc_group_sqp_densenet_setup: Solver.sqp_densenet_setup on every device."""
-        self._state_rows(xmin, xmax, terminal)
-        self._check(self.L.almpc_group_set_rho_profile(self.g, {"scalar": 0, "stiffness": 1}[rho_profile]))
-        self._check(self.L.almpc_group_sqp_fnn_set_structured(self.g, 1 if qp_solver == "structured" else 0))
-        H, nl, a, arrs, p_inst = self._fnn_args(W_in, W_h, b_h, W_out, x_ref, u_ref, Q, R, S, P, umin, umax, act, True, "densenet")
-        self._keep = arrs
-        ptrs = [_ptr(v) for v in arrs]
-        self._check(self.L.almpc_group_sqp_densenet_setup(self.g, H, nl, a, *ptrs[:10], p_inst, ptrs[10], ptrs[11], float(rho),
-                                                          float(sigma)))
-
-    def sqp_fnn_start(self, x0, u_guess=None):
+    # ---- the step path of a group
+    def update_initialization(self, x0, resident=False):
+        """x0 (batch, n) to the handles' shards.  Default: almpc_group_update_initialization (pinned slots read in place by the next
+        step, no device copy -- the per-step path).  resident=True: a device copy per handle (almpc_update_initialization), for states
+        that many steps will read (the pinned slot costs every step its transfer over the link)."""
         x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(self.batch, self.n)
-        ug = None if u_guess is None else np.ascontiguousarray(np.asarray(u_guess, dtype=np.float64).reshape(self.batch, self.m, self.N).transpose(0, 2, 1))
-        self._check(self.L.almpc_group_sqp_fnn_start(self.g, _ptr(x0), _ptr(ug)))
-
-    def sqp_fnn_iterate(self, iters, step_scale=1.0, opts=None, step_rule="fixed"):
-        self._check(self.L.almpc_group_sqp_fnn_set_step_rule(self.g, {"fixed": 0, "merit": 1}[step_rule]))
-        st, de = np.zeros(int(iters)), np.zeros(int(iters))
-        self._check(self.L.almpc_group_sqp_fnn_iterate(self.g, int(iters), float(step_scale), None if opts is None else ctypes.byref(opts),
-                                                       _ptr(st), _ptr(de)))
-        return st, de
-
-    def sqp_fnn_solve(self, max_iters, tol, opts=None, step_rule="merit"):
-        self._check(self.L.almpc_group_sqp_fnn_set_step_rule(self.g, {"fixed": 0, "merit": 1}[step_rule]))
-        st, it, kk = np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch)
-        self._check(self.L.almpc_group_sqp_fnn_solve(self.g, int(max_iters), float(tol), None if opts is None else ctypes.byref(opts),
-                                                     st.ctypes.data_as(_ip), it.ctypes.data_as(_ip), _ptr(kk)))
-        return dict(status=st, iters=it, kkt=kk)
-
-    def sqp_fnn_set_hessian(self, mode):
-        self._check(self.L.almpc_group_sqp_fnn_set_hessian(self.g, SQP_HESSIANS[mode]))
-
-    def sqp_fnn_set_row_multipliers(self, on):
-        self._check(self.L.almpc_group_sqp_fnn_set_row_multipliers(self.g, 1 if on else 0))
-
-    def sqp_fnn_state_multipliers(self):
-        mu = np.zeros((self.batch, self.N, self.n))
-        self._check(self.L.almpc_group_sqp_fnn_state_multipliers(self.g, _ptr(mu)))
-        return np.ascontiguousarray(mu.transpose(0, 2, 1))
-
-    def sqp_fnn_skipped(self):
-        sk = np.zeros(self.batch, dtype=np.int32)
-        self._check(self.L.almpc_group_sqp_fnn_skipped(self.g, sk.ctypes.data_as(_ip)))
-        return sk
+        if resident:
+            for hv, (f, c) in zip(self.handles, self.shards):
+                hv.update_initialization(x0[f:f + c])
+            return
+        self._check(self._f.update_initialization(self._t, _ptr(x0)))
 
     def x0_staging(self):
         """The handles' pinned x0 slots as numpy views ((count_i, n) each): write the shards' states there, then update_initialization_staged()."""
@@ -1520,142 +1246,7 @@ class Group:
     def update_initialization_staged(self):
         self._check(self.L.almpc_group_update_initialization_staged(self.g, self._slots))
 
-    def get_results_async(self, want=("u0", "status")) -> int:
-        t = self.L.almpc_group_get_results_async(self.g, _want_mask(want))
-        if t < 0:
-            self._check(t)
-        return t
-
-    def get_results_wait(self, ticket, want=("u0", "status")):
-        b, n, m, N = self.batch, self.n, self.m, self.N
-        shapes = {"x": (b, N + 1, n), "e_x": (b, N + 1, n), "u": (b, N, m), "e_u": (b, N, m), "u0": (b, m),
-                  "status": (b,), "iters": (b,), "polish_iters": (b,)}
-        order = ("x", "e_x", "u", "e_u", "u0", "status", "iters", "polish_iters")
-        bufs = {k: np.empty(shapes[k], dtype=np.int32 if k in ("status", "iters", "polish_iters") else np.float64) for k in set(want)}
-        args = [(bufs[k].ctypes.data_as(_ip if bufs[k].dtype == np.int32 else _dp) if k in bufs else None) for k in order]
-        self._check(self.L.almpc_group_get_results_wait(self.g, int(ticket), *args))
-        for k in ("x", "e_x", "u", "e_u"):
-            if k in bufs: bufs[k] = bufs[k].transpose(0, 2, 1)
-        return bufs
-
-    def close(self):
-        if getattr(self, "g", None):
-            for hv in self.handles:
-                hv.close()
-            self.L.almpc_group_destroy(self.g)
-            self.g = None
-
-    __del__ = close
-
-    def design_shared(self, A, B, Q, R, S=None, P=None, umin=None, umax=None, xmin=None, xmax=None, rho=0.1, sigma=1e-6,
-                      terminal="none", rho_profile="scalar"):
-        n, m = self.n, self.m
-        for hv in self.handles:   # per-handle options go through the handles (almpc_group_handle)
-            hv._check(self.L.almpc_set_terminal_equality(hv.h, 1 if terminal == "equality" else 0))
-            hv._check(self.L.almpc_set_rho_profile(hv.h, {"scalar": 0, "stiffness": 1}[rho_profile]))
-        A, B, Q, R = _colmajor(A, (n, n)), _colmajor(B, (n, m)), _colmajor(Q, (n, n)), _colmajor(R, (m, m))
-        S = None if S is None else _colmajor(S, (m, m))
-        P = None if P is None else _colmajor(P, (n, n))
-        umin = np.ascontiguousarray(umin, dtype=np.float64).reshape(m)
-        umax = np.ascontiguousarray(umax, dtype=np.float64).reshape(m)
-        xmin = None if xmin is None else np.ascontiguousarray(xmin, dtype=np.float64).reshape(n)
-        xmax = None if xmax is None else np.ascontiguousarray(xmax, dtype=np.float64).reshape(n)
-        self._check(self.L.almpc_group_design_shared(self.g, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(S), _ptr(P), _ptr(umin),
-                                                     _ptr(umax), _ptr(xmin), _ptr(xmax), float(rho), float(sigma)))
-
-    def set_reference(self, x_ref, u_ref, per_instance=False):
-        n, m, N = self.n, self.m, self.N
-        x_ref, u_ref = np.asarray(x_ref, dtype=np.float64), np.asarray(u_ref, dtype=np.float64)
-        if per_instance:
-            xr = np.ascontiguousarray(x_ref.reshape(self.batch, n, N + 1).transpose(0, 2, 1))
-            ur = np.ascontiguousarray(u_ref.reshape(self.batch, m, N).transpose(0, 2, 1))
-        else:
-            xr = np.ascontiguousarray(x_ref.reshape(n, N + 1).T)
-            ur = np.ascontiguousarray(u_ref.reshape(m, N).T)
-        self._check(self.L.almpc_group_set_reference(self.g, _ptr(xr), _ptr(ur), 1 if per_instance else 0))
-
-    def update_initialization(self, x0, resident=False):
-        """x0 (batch, n) to the handles' shards.  Default: almpc_group_update_initialization (pinned slots read in place by the next
-        step, no device copy -- the per-step path).  resident=True: a device copy per handle (almpc_update_initialization), for states
-        that many steps will read (the pinned slot costs every step its transfer over the link)."""
-        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(self.batch, self.n)
-        if resident:
-            for hv, (f, c) in zip(self.handles, self.shards):
-                hv.update_initialization(x0[f:f + c])
-            return
-        self._check(self.L.almpc_group_update_initialization(self.g, _ptr(x0)))
-
-    def calculate(self, opts: almpc_opts | None = None, sync=True):
-        fn = self.L.almpc_group_calculate if sync else self.L.almpc_group_calculate_async
-        self._check(fn(self.g, None if opts is None else ctypes.byref(opts)))
-
-    def synchronize(self):
-        self._check(self.L.almpc_group_synchronize(self.g))
-
-    def sensitivity(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
-        """Solver.sensitivity for the whole batch (almpc_group_sensitivity + almpc_group_get_sensitivity)."""
-        self._check(self.L.almpc_group_sensitivity(self.g, _sens_mask(want), float(act_tol)))
-        return _sens_read(self.L.almpc_group_get_sensitivity, self.g, self._check, want, self.batch, self.n, self.m, self.N)
-
-    def certificate(self, want=("cost", "res", "grad", "costate")) -> dict:
-        """Solver.certificate for the whole batch (almpc_group_certificate + almpc_group_get_certificate)."""
-        self._check(self.L.almpc_group_certificate(self.g, _cert_mask(want)))
-        return _cert_read(self.L.almpc_group_get_certificate, self.g, self._check, want, self.batch, self.n, self.m, self.N)
-
-    def relin_fnn_certificate(self, want=("cost", "res", "grad", "costate")) -> dict:
-        """Solver.relin_fnn_certificate for the whole batch (almpc_group_relin_fnn_certificate + almpc_group_get_certificate)."""
-        self._check(self.L.almpc_group_relin_fnn_certificate(self.g, _cert_mask(want)))
-        return _cert_read(self.L.almpc_group_get_certificate, self.g, self._check, want, self.batch, self.n, self.m, self.N)
-
-    def sensitivity_vjp(self, g_u, g_x=None, act_tol=0.0):
-        """Solver.sensitivity_vjp for the whole batch (almpc_group_sensitivity_vjp)."""
-        return _sens_vjp(self.L.almpc_group_sensitivity_vjp, self.g, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m, self.N)
-
-    def sensitivity_stagewise(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
-        """Solver.sensitivity_stagewise for the whole batch (almpc_group_sensitivity_stagewise + almpc_group_get_sensitivity)."""
-        self._check(self.L.almpc_group_sensitivity_stagewise(self.g, _sens_mask(want), float(act_tol)))
-        return _sens_read(self.L.almpc_group_get_sensitivity, self.g, self._check, want, self.batch, self.n, self.m, self.N)
-
-    def sensitivity_stagewise_vjp(self, g_u, g_x=None, act_tol=0.0):
-        """Solver.sensitivity_stagewise_vjp for the whole batch (almpc_group_sensitivity_stagewise_vjp)."""
-        return _sens_vjp(self.L.almpc_group_sensitivity_stagewise_vjp, self.g, self._check, g_u, g_x, act_tol, self.batch, self.n, self.m,
-                         self.N)
-
-    def sensitivity_stagewise_rate(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
-        """Solver.sensitivity_stagewise_rate for the whole batch (almpc_group_sensitivity_stagewise_rate + almpc_group_get_sensitivity)."""
-        self._check(self.L.almpc_group_sensitivity_stagewise_rate(self.g, _sens_mask(want), float(act_tol)))
-        return _sens_read(self.L.almpc_group_get_sensitivity, self.g, self._check, want, self.batch, self.n, self.m, self.N)
-
-    def sensitivity_stagewise_rate_vjp(self, g_u, g_x=None, act_tol=0.0):
-        """Solver.sensitivity_stagewise_rate_vjp for the whole batch (almpc_group_sensitivity_stagewise_rate_vjp)."""
-        return _sens_vjp(self.L.almpc_group_sensitivity_stagewise_rate_vjp, self.g, self._check, g_u, g_x, act_tol, self.batch, self.n,
-                         self.m, self.N)
-
-    def sensitivity_params_vjp(self, g_u, g_x=None, want=PARAM_GROUPS, act_tol=0.0, terminal="data") -> dict:
-        """Solver.sensitivity_params_vjp for the whole batch (almpc_group_sensitivity_params_vjp, almpc_group_sensitivity_params_vjp_dare)."""
-        dare = _terminal_gradient(terminal)
-        call = self.L.almpc_group_sensitivity_params_vjp_dare if dare else self.L.almpc_group_sensitivity_params_vjp
-        return _sens_params_vjp(call, self.g, self._check, g_u, g_x, want, act_tol, self.batch, self.n, self.m, self.N, dare)
-
-    def sensitivity_rows(self, want=("K0", "dU", "dX"), act_tol_u=0.0, act_tol_x=0.0) -> dict:
-        """Solver.sensitivity_rows for the whole batch (almpc_group_sensitivity_rows + almpc_group_get_sensitivity)."""
-        self._check(self.L.almpc_group_sensitivity_rows(self.g, _sens_mask(want), float(act_tol_u), float(act_tol_x)))
-        return _sens_read(self.L.almpc_group_get_sensitivity, self.g, self._check, want, self.batch, self.n, self.m, self.N)
-
-    def sensitivity_rows_vjp(self, g_u, g_x=None, act_tol_u=0.0, act_tol_x=0.0):
-        """Solver.sensitivity_rows_vjp for the whole batch (almpc_group_sensitivity_rows_vjp)."""
-        return _sens_vjp(self.L.almpc_group_sensitivity_rows_vjp, self.g, self._check, g_u, g_x, (act_tol_u, act_tol_x), self.batch, self.n,
-                         self.m, self.N)
-
     def get_results(self, want=("x", "e_x", "u", "e_u", "status", "iters", "polish_iters")):
-        b, n, m, N = self.batch, self.n, self.m, self.N
-        shapes = {"x": (b, N + 1, n), "e_x": (b, N + 1, n), "u": (b, N, m), "e_u": (b, N, m), "u0": (b, m),
-                  "status": (b,), "iters": (b,), "polish_iters": (b,)}
-        order = ("x", "e_x", "u", "e_u", "u0", "status", "iters", "polish_iters")
+        """_Target.get_results with "u0" (batch, m) among the names; a name that is none of WANT is refused."""
         _want_mask(want)
-        bufs = {k: np.empty(shapes[k], dtype=np.int32 if k in ("status", "iters", "polish_iters") else np.float64) for k in set(want)}
-        args = [(bufs[k].ctypes.data_as(_ip if bufs[k].dtype == np.int32 else _dp) if k in bufs else None) for k in order]
-        self._check(self.L.almpc_group_get_results(self.g, *args))
-        for k in ("x", "e_x", "u", "e_u"):
-            if k in bufs: bufs[k] = bufs[k].transpose(0, 2, 1)
-        return bufs
+        return _Target.get_results(self, want)

@@ -142,12 +142,10 @@ def test_header_declares_the_entry_points_and_the_bindings_have_them(pkg):
         assert re.search(r"\bint %s\(" % s, header), s
     assert re.search(r"#define ALMPC_CERT_STATES 16u\b", header)
     capi = pkg._capi
-    with open(capi.__file__) as f:
-        src = f.read()
     with open(os.path.join(ROOT, "julia", "AlmpcHIP.jl")) as f:
         shim = f.read()
     for s in SYMBOLS:
-        assert "L.%s.argtypes" % s in src, s
+        assert s in capi.prototypes(), s
         assert "(:%s, libalmpc)" % s in shim, s
     assert capi.CERT_LTV == {"cost": 1, "res": 2, "grad": 4, "costate": 8, "x": 16, "e_x": 16}
     for cls, names in ((capi.Solver, ("set_keep_stage_models", "certificate_ltv", "device_certificate_ltv", "relin_fnn_certificate")),

@@ -118,3 +118,22 @@ def test_group_of_structured_handles_tickets_and_staged_x0(capi, mo):
     assert np.array_equal(got["status"], ref["status"]) and np.array_equal(got["u"], ref["u"])
     assert np.array_equal(got["u0"], ref["u"][:, :, 0])
     assert set(np.unique(ref["status"])) <= {0, 3} and (ref["status"] == 0).sum() >= 100
+
+
+def test_group_relin_without_hidden_layers_or_references(capi):
+    """A network without hidden layers (L = 0: no W_h, b_h) and no references (x_ref = u_ref = None: zeros), the two arguments a
+    group used to hand to C differently from a handle: the group's step is the handle's, bit for bit."""
+    n, m, N, batch, H = 4, 2, 5, 7, 8
+    rng = np.random.default_rng(0x5EED0009)
+    W_in, W_out = 0.3 * rng.standard_normal((H, n + m)), 0.3 * rng.standard_normal((n, H))
+    X0 = 0.5 * rng.standard_normal((batch, n))
+    Q, R = 100.0 * np.eye(n), 0.1 * np.eye(m)
+    got = []
+    for s in (capi.Solver(n, m, N, batch), capi.Group(n, m, N, batch, devices=[0, 0])):
+        s.relin_fnn_setup(W_in, [], [], W_out, None, None, Q, R, None, Q, -np.ones(m), np.ones(m), act="tanh")
+        s.update_initialization(X0)
+        s.relin_fnn_step()
+        got.append(s.get_results(want=("status", "u", "x")))
+        s.close()
+    for k in ("status", "u", "x"):
+        assert np.array_equal(got[0][k], got[1][k]), k

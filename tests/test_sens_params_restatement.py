@@ -164,8 +164,7 @@ def test_header_and_bindings_carry_the_parameter_gradients(pkg):
     capi = pkg._capi
     for cls in (capi.Solver, capi.Group):
         assert callable(getattr(cls, "sensitivity_params_vjp"))
-    src = open(os.path.join(os.path.dirname(capi.__file__), "_capi.py")).read()
-    assert not [n for n in NAMES if ("L." + n + ".argtypes") not in src]
+    assert not [n for n in NAMES if n not in capi.prototypes()]
     body = re.search(r"typedef struct almpc_param_grads \{(.*?)\} almpc_param_grads;", header, re.S).group(1)
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     fields = [f.strip().lstrip("*") for decl in body.split(";") if decl.strip() for f in decl.strip().split(None, 1)[1].split(",")]

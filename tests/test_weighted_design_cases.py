@@ -151,11 +151,10 @@ def test_g_form_equals_the_direct_form_with_each_instances_own_weights(mo, case)
 def test_header_capi_and_shim_carry_the_new_symbols(pkg):
     hdr = _read(ROOT, "include", "almpc.h")
     shim = _read(ROOT, "julia", "AlmpcHIP.jl")
-    capi_src = _read(ROOT, "automationlabsmodelpredictivecontrol.jl_amd", "_capi.py")
     for s in SYMBOLS:
         assert re.search(r"^int %s\(" % s, hdr, re.M), s
         assert "(:%s, libalmpc)" % s in shim, s
-        assert "L.%s.argtypes" % s in capi_src and "L.%s.restype" % s in capi_src, s
+        assert s in pkg._capi.prototypes() and s not in pkg._capi._RESTYPES, s   # (declared, and returning int)
     assert "const double* Q_batch /* [batch][n*n] */" in hdr and "const double* S_batch /* [batch][m*m] or NULL */" in hdr
     for cls, names in ((pkg._capi.Solver, ("design_batched_weighted", "get_weights_instance")), (pkg._capi.Group, ("design_batched_weighted",))):
         for nm in names:
