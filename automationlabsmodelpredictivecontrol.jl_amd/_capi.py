@@ -87,6 +87,7 @@ _HANDLE_CALLS = {
     "sensitivity_rows": [_u32, _d, _d], "sensitivity_rows_vjp": [_dp, _dp, _d, _d, _dp, _ip],
     "sensitivity_stagewise": [_u32, _d], "sensitivity_stagewise_vjp": _VJP,
     "sensitivity_stagewise_rate": [_u32, _d], "sensitivity_stagewise_rate_vjp": _VJP,
+    "sensitivity_ltv": [_u32, _d], "sensitivity_ltv_vjp": _VJP,
     "sensitivity_params_vjp": [_dp, _dp, _d, _gp], "sensitivity_params_vjp_dare": [_dp, _dp, _d, _gp, _ip],
     "certificate": [_u32], "get_certificate": [_dp] * 4, "device_certificate": [_vpp] * 4,
     "certificate_ltv": [_u32], "get_certificate_ltv": [_dp] * 6, "device_certificate_ltv": [_vpp] * 6,
@@ -1030,6 +1031,18 @@ class Solver(_Target):
         bufs = {k: (np.empty(sizes[k]) if k in names else None) for k in sizes}
         self._check(self.L.almpc_get_certificate_ltv(self.h, *[_ptr(bufs[k]) for k in ("cost", "res", "grad", "costate", "x", "e_x")]))
         return {k: (v if v.ndim == 1 else v.transpose(0, 2, 1)) for k, v in bufs.items() if v is not None}
+
+    def sensitivity_ltv(self, want=("K0", "dU", "dX"), act_tol=0.0) -> dict:
+        """Sensitivities of the last step of a design_ltv(keep_stage_models=True) design in its initial deviation (almpc_sensitivity_ltv +
+        almpc_get_sensitivity, k_sens_ltv): the face recursion with the stage models A_k, B_k; shapes as sensitivity_stagewise.  K0 is
+        the gain of a real-time iteration: apply clip(u_0 + K0 (x_meas - xbar_0)).  act_tol is relative to the width of the input box
+        (0: 1e-7)."""
+        return self._sensitivity(self.L.almpc_sensitivity_ltv, want, act_tol)
+
+    def sensitivity_ltv_vjp(self, g_u, g_x=None, act_tol=0.0):
+        """sensitivity_vjp of the same step (almpc_sensitivity_ltv_vjp): g_x is a loss gradient on the predicted states xbar + dx of
+        certificate_ltv; (g_x0 (batch, n), rows (batch,))."""
+        return self._vjp(self.L.almpc_sensitivity_ltv_vjp, g_u, g_x, act_tol)
 
     def relin_fnn_timing(self):
         a, d, s = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()

@@ -17,6 +17,7 @@
 #include "almpc_dare_vjp.hip.h"
 #include "almpc_c2d.hip.h"
 #include "almpc_sens.hip.h"
+#include "almpc_sens_ltv.hip.h"
 #include "almpc_cert.hip.h"
 #include "almpc_cert_ltv.hip.h"
 #include "almpc_host_math.h"
@@ -41,6 +42,7 @@
 #include "instances/dare.inc"
 #include "instances/c2d.inc"
 #include "instances/sens.inc"
+#include "instances/sens_ltv.inc"
 #include "instances/cert.inc"
 #include "instances/cert_ltv.inc"
 #undef ALMPC_KERNEL_INSTANCE
@@ -271,7 +273,8 @@ struct almpc_handle {
         DevBuf<double> traj;            // [workgroups][3][(N+1) n] zeta, mu, al of the instance a workgroup is at
         DevBuf<int32_t> dstat;          // [batch] k_dare_vjp's status words (almpc_sensitivity_params_vjp_dare)
         DevBuf<double> Kst;             // [batch][N][m n] stage gains of k_sens_face (almpc_sensitivity_stagewise with dU or dX);
-                                        // [batch][N][m (n + m)] those of k_sens_face_rate (its S: the kept one, shared on every structured design)
+                                        // [batch][N][m (n + m)] those of k_sens_face_rate (its S: the kept one, shared on every structured design);
+                                        // k_sens_ltv's (almpc_sensitivity_ltv), of either width
     } sens;
     // Certificate of the last step (almpc_certificate, almpc_relin_fnn_certificate: k_cert, csrc/almpc_cert.hip.h; almpc_certificate_ltv:
     // k_cert_ltv, csrc/almpc_cert_ltv.hip.h).  As with sens, every buffer is made at the first call that needs it.
@@ -4504,7 +4507,7 @@ int sens_check(almpc_handle* h, const char* who, bool rows_form = false) {
     const std::string w(who);
     if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, w + " before design");
     if (h->structured) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": a structured handle forms no condensed inverse G = H'^-1 (the constraint-space form is not built)");
-    if (h->ltv || h->sqp.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": time-varying and SQP designs solve for a step around a trajectory, not for u(x0)");
+    if (h->ltv || h->sqp.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": time-varying and SQP designs solve for a step around a trajectory, not for u(x0) (an almpc_design_ltv design, in its initial deviation: almpc_sensitivity_ltv)");
     if (h->relin.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the re-linearisation pipeline's models depend on x0 themselves");
     if (h->mc > 0 && !rows_form)
         return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": designs with state rows (state box, terminal equality) need the constraint-space form (almpc_sensitivity_rows)");
@@ -4831,8 +4834,9 @@ int sens_face_check(almpc_handle* h, const char* who, bool rate) {
     if (!h) return ALMPC_ERR_INVALID;
     const std::string w(who);
     if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, w + " before design");
+    // (in front of the handle's kind: almpc_design_ltv exists on condensed handles only, and its refusal names the call that serves it)
+    if (h->ltv || h->sqp.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": time-varying and SQP designs solve for a step around a trajectory, not for u(x0) (an almpc_design_ltv design, in its initial deviation: almpc_sensitivity_ltv)");
     if (!h->structured) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the handle is a condensed one, whose sensitivities come from G = H'^-1 (almpc_sensitivity)");
-    if (h->ltv || h->sqp.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": time-varying and SQP designs solve for a step around a trajectory, not for u(x0)");
     if (h->relin.ready) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the re-linearisation pipeline's models depend on x0 themselves");
     if (!rate && h->kept.useS) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": with an input-rate weight S the stage state is [e_k; v_(k-1)], for which the recursion is not built");
     if (h->has_box || h->terminal_eq || (h->sd.ready && (h->sd.has_box || h->sd.has_eq)))
@@ -4918,6 +4922,97 @@ int sens_face_vjp(almpc_handle* h, const char* who, const double* g_u, const dou
     ALMPC_TRY(sens_face_params(h, act_tol, with_S, q));
     ALMPC_TRY(sens_vjp_stage(h, g_u, g_x, q.f));
     ALMPC_TRY(sens_face_launch<true>(h, q));
+    HIP_TRY(h, hipMemcpyAsync(g_x0, h->sens.gx0, b * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (rows_out) HIP_TRY(h, hipMemcpyAsync(rows_out, h->sens.vrows, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, stream_wait_polling(h));
+    return ALMPC_OK;
+}
+
+// ---- the same for a step of a time-varying design (k_sens_ltv): the face recursion with the kept stage models, in the initial deviation ----
+// almpc_sensitivity_ltv, almpc_sensitivity_ltv_vjp.  RATE is the design's branch (kept.useS); the weights are the design's own device
+// copies (wQ, wR, wS: batched_design_front), the terminal weights its bP.
+
+// What these calls can look at: the last step of an almpc_design_ltv design that kept its stage models, with an input box only
+int sens_ltv_check(almpc_handle* h, const char* who) {
+    if (!h) return ALMPC_ERR_INVALID;
+    const std::string w(who);
+    if (!h->designed) return fail(h, ALMPC_ERR_NOT_DESIGNED, w + " before design");
+    if (!h->ltv || h->sqp.ready || h->relin.ready)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the design is not almpc_design_ltv's (condensed time-invariant designs: almpc_sensitivity, almpc_sensitivity_rows; "
+                                                  "structured handles: almpc_sensitivity_stagewise_rate; the re-linearisation pipeline's models depend on x0 themselves; "
+                                                  "the SQP loop's Jacobians belong to the iterate before the update)");
+    if (h->has_box || h->terminal_eq || h->mc > 0)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": state rows (state box, terminal equality) are not held on the face of the stage-wise recursion");
+    if (!h->cert.kept || !h->lA || !h->lB)
+        return fail(h, ALMPC_ERR_INVALID, w + ": the design released its stage models (almpc_set_keep_stage_models(h, 1) before almpc_design_ltv)");
+    if (h->n > SENS_LTV_MAX_N || h->m > SENS_LTV_MAX_M || (long)(h->N + 1) * (h->n + h->m) > SENS_LTV_MAX_STATES)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": needs n <= 16, m <= 16 and (N + 1)(n + m) <= 1024, the shapes a step of an LTV design runs at");
+    if (!h->wQ || !h->wR || !h->wS || !h->bP) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the design's weights are not kept");
+    if (!h->sens.stepped) return fail(h, ALMPC_ERR_INVALID, w + ": no step has run on this design");
+    return ALMPC_OK;
+}
+
+void sens_ltv_params(almpc_handle* h, double act_tol, SensLtvParams& q) {
+    q = SensLtvParams();
+    SensFaceParams& p = q.f;
+    const long n = h->n, m = h->m, N = h->N;
+    p.n = h->n; p.m = h->m; p.N = h->N; p.batch = h->batch;
+    p.A = h->lA; p.A_stride = N * n * n;
+    p.B = h->lB; p.B_stride = N * n * m;
+    p.Q = h->wQ; p.R = h->wR; q.S = h->wS; q.useR = h->kept.useR;
+    p.P = h->bP; p.P_stride = h->bP_stride;
+    p.umin = h->dUmin; p.umax = h->dUmax; p.u = h->dU; p.status = h->dStatus;
+    p.tau = act_tol > 0.0 ? act_tol : 1e-7;   // (k_sens_face's rule and default)
+    p.lds_per_wave = sens_ltv_lds_doubles(h->n, h->m, h->N, h->kept.useS != 0);
+}
+
+template <bool VJP>
+int sens_ltv_launch(almpc_handle* h, const SensLtvParams& q) {
+    const size_t per_wave = (size_t)q.f.lds_per_wave * sizeof(double);
+    const int waves = waves_in_lds(per_wave, SENS_LTV_WAVES), wgs = capped_grid(h->batch, waves, 16 * h->num_cus);
+    const bool quad = h->n == 12 && h->m == 4, rate = h->kept.useS != 0;
+    if (rate && quad) HIP_TRY(h, LAUNCH_WAVES((k_sens_ltv<VJP, true, 12, 4>), wgs, waves, waves * per_wave, h->stream, q));
+    else if (rate) HIP_TRY(h, LAUNCH_WAVES((k_sens_ltv<VJP, true, 0, 0>), wgs, waves, waves * per_wave, h->stream, q));
+    else if (quad) HIP_TRY(h, LAUNCH_WAVES((k_sens_ltv<VJP, false, 12, 4>), wgs, waves, waves * per_wave, h->stream, q));
+    else HIP_TRY(h, LAUNCH_WAVES((k_sens_ltv<VJP, false, 0, 0>), wgs, waves, waves * per_wave, h->stream, q));
+    return ALMPC_OK;
+}
+
+int sens_ltv_jacobians(almpc_handle* h, uint32_t want, double act_tol) {
+    const char* who = "sensitivity_ltv";
+    ALMPC_TRY(sens_ltv_check(h, who));
+    if (!want || (want & ~(ALMPC_SENS_K0 | ALMPC_SENS_DU | ALMPC_SENS_DX))) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": want must be a mask of ALMPC_SENS_*");
+    HIP_TRY(h, hipSetDevice(h->device));
+    ALMPC_TRY(wait_and_settle(h));
+    const size_t b = (size_t)h->batch, n = (size_t)h->n;
+    h->sens.have = 0;
+    SensLtvParams q;
+    sens_ltv_params(h, act_tol, q);
+    HIP_TRY(h, h->sens.rows.grow(b));
+    if (want & ALMPC_SENS_K0) HIP_TRY(h, h->sens.K0.grow(b * n * h->m));
+    if (want & (ALMPC_SENS_DU | ALMPC_SENS_DX)) {   // (the forward pass writes dU on its way to dX; K0 alone allocates no gain scratch)
+        HIP_TRY(h, h->sens.dU.grow(b * n * h->nz));
+        HIP_TRY(h, h->sens.Kst.grow(b * h->nz * (n + (h->kept.useS ? h->m : 0))));
+    }
+    if (want & ALMPC_SENS_DX) HIP_TRY(h, h->sens.dX.grow(b * n * (h->N + 1) * n));
+    q.f.want = want; q.f.K0 = h->sens.K0; q.f.dU = h->sens.dU; q.f.dX = h->sens.dX; q.f.Kst = h->sens.Kst; q.f.rows = h->sens.rows;
+    ALMPC_TRY(sens_ltv_launch<false>(h, q));
+    HIP_TRY(h, stream_wait_polling(h));
+    h->sens.have = want | ((want & ALMPC_SENS_DX) ? ALMPC_SENS_DU : 0u);
+    return ALMPC_OK;
+}
+
+int sens_ltv_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows_out) {
+    const char* who = "sensitivity_ltv_vjp";
+    ALMPC_TRY(sens_ltv_check(h, who));
+    if (!g_u || !g_x0) return fail(h, ALMPC_ERR_INVALID, std::string(who) + ": null g_u or g_x0");
+    HIP_TRY(h, hipSetDevice(h->device));
+    ALMPC_TRY(wait_and_settle(h));
+    const size_t b = (size_t)h->batch, n = (size_t)h->n;
+    SensLtvParams q;
+    sens_ltv_params(h, act_tol, q);
+    ALMPC_TRY(sens_vjp_stage(h, g_u, g_x, q.f));
+    ALMPC_TRY(sens_ltv_launch<true>(h, q));
     HIP_TRY(h, hipMemcpyAsync(g_x0, h->sens.gx0, b * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (rows_out) HIP_TRY(h, hipMemcpyAsync(rows_out, h->sens.vrows, b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, stream_wait_polling(h));
@@ -5207,6 +5302,12 @@ int almpc_sensitivity_stagewise_rate(almpc_handle* h, uint32_t want, double act_
 
 int almpc_sensitivity_stagewise_rate_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows) {
     return sens_face_vjp(h, "sensitivity_stagewise_rate_vjp", g_u, g_x, act_tol, g_x0, rows, true);
+}
+
+int almpc_sensitivity_ltv(almpc_handle* h, uint32_t want, double act_tol) { return sens_ltv_jacobians(h, want, act_tol); }
+
+int almpc_sensitivity_ltv_vjp(almpc_handle* h, const double* g_u, const double* g_x, double act_tol, double* g_x0, int32_t* rows) {
+    return sens_ltv_vjp(h, g_u, g_x, act_tol, g_x0, rows);
 }
 
 }  // extern "C"

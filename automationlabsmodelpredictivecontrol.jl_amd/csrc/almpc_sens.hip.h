@@ -739,6 +739,8 @@ inline __global__ __launch_bounds__(256) void k_sens_rows_table(SensRowsTablePar
 //   m x nt) | R, S, Lam (m x m) | lam, lam+ (nt) | the stage masks.  The new Pi is written over the old one, which has no reader once
 //   Pi+ Acl is formed, and symmetrised into T; then the two change places -- no per-lane copy of a matrix, whatever nt.  The look-ahead
 //   gain of the forward pass is the only per-lane array: m nt <= 768 entries, 12 a lane.
+// k_sens_ltv (almpc_sens_ltv.hip.h) mirrors the stage bodies of both kernels entry for entry, with a model per stage: a change of the
+// arithmetic here belongs there as well.
 constexpr int SENS_FACE_WAVES = 4;
 
 struct SensFaceParams {

@@ -888,6 +888,49 @@ int almpc_relin_fnn_certificate(almpc_handle* h, uint32_t want);      /* k_cert 
 int almpc_group_relin_fnn_certificate(almpc_group* g, uint32_t want);
 
 /*
+ * Sensitivities of a step of a time-varying design in its initial deviation (k_sens_ltv, DESIGN.md "k_sens_ltv"): what a real-time-
+ * iteration caller of almpc_design_ltv needs when the measured state arrives after the QP was prepared around xbar_0 -- the control
+ * to apply is clip(u_0 + K0 (x_meas - xbar_0)) -- and what a learning loop around an LTV step backpropagates through.  Let p perturb
+ * the initial deviation: the design's QP with dx_0 = p in place of dx_0 = 0, everything else as almpc_design_ltv states it.  All
+ * derivatives are taken at p = 0, on the face W of the returned u.  The linearisation trajectory, the defects c_k and the references
+ * do not enter (the face problem is linear in p); the derivative of the linearisation itself belongs to the caller's outer loop.
+ * Stages 0-based, A_k, B_k the design's stage models, R, S, useR, useS as the design took them (R = 0 without useR), P symmetrised
+ * (per instance where the design got one per instance), W_k the inputs of stage k in W, f the free ones.
+ * Without the rate term (useS == 0), the recursion of almpc_sensitivity_stagewise with one model per stage:
+ *     P+ = sym(P) at k = N;  for k = N-1 .. 0:
+ *       Lam = R_ff + B_k,f' P+ B_k,f
+ *       K_k[f,:] = Lam^-1 B_k,f' P+ A_k,   K_k[W_k,:] = 0,   Acl_k = A_k - B_k K_k
+ *       P+ <- Qbar_k + Acl_k' P+ Acl_k + K_k' R K_k      (symmetrised; Qbar_k = Q for 1 <= k <= N-1; P_0 has no reader)
+ *     Jacobians:  dx_0 = I,  du_k = -K_k dx_k,  dx_{k+1} = A_k dx_k + B_k du_k          (K0 = -K_0)
+ *     VJP:        lam_N = g_x[N],  lam_k = g_x[k] - K_k' g_u[k] + Acl_k' lam_{k+1},   g_x0 = lam_0
+ * With it (useS != 0): the recursion of almpc_sensitivity_stagewise_rate above, unchanged, in the stage state [dx_k; du_{k-1}] with
+ * At_k = [A_k 0; 0 0], Bt_k = [B_k; I] and S_0 = 0.
+ * dX is the derivative of the predicted states x_k = xbar_k + dx_k of ALMPC_CERT_STATES, g_x a loss gradient on those states.
+ * W, on the returned u: row (stage k, input i) is in W iff
+ *     u[i,k] - umin_i <= act_tol * w_i   or   umax_i - u[i,k] <= act_tol * w_i,     w_i = umax_i - umin_i;
+ * act_tol <= 0 means 1e-7.  At a weakly active row: the derivative of the face on which every flagged row is held.
+ *   almpc_sensitivity_ltv      synchronous, settles first; results in the handle's sensitivity buffers in the layouts of
+ *                              almpc_sensitivity, so almpc_get_sensitivity and almpc_device_sensitivity serve them until the next step
+ *                              or design.  ALMPC_SENS_K0 alone is one backward sweep and allocates no gain scratch; with dU or dX
+ *                              the gains of every stage go to a scratch [batch][N][m w], w = n or n + m.
+ *   almpc_sensitivity_ltv_vjp  the adjoint rides the backward sweep, no gain is stored, no Jacobian formed; g_x = NULL is bit-identical
+ *                              to zeros.
+ * An instance that is not ALMPC_SOLVED, or one of whose Lam has a pivot that is not positive and finite, gets rows = -1 and zeros in
+ * every output asked for.  Gradients in c_k, in the stage models or in the weights are not formed.  There is no group form, because
+ * almpc_design_ltv has none.
+ * Shapes: those a step of an LTV design runs at -- n <= 16, m <= 16, (N + 1)(n + m) <= 1024 (else ALMPC_ERR_UNSUPPORTED).
+ * ALMPC_ERR_NOT_DESIGNED before a design; ALMPC_ERR_INVALID before the design's first step, for a `want` that is no mask of
+ * ALMPC_SENS_*, for a NULL g_u or g_x0, and after an almpc_design_ltv made with the keep switch off (the message names
+ * almpc_set_keep_stage_models); ALMPC_ERR_UNSUPPORTED, with the reason in almpc_last_error, on a design that is not almpc_design_ltv's
+ * (the message names the call that serves it; the SQP loop stays refused: its Jacobians belong to the iterate before the update) and
+ * with a state box or the terminal equality.  almpc_sensitivity and its rows and stage-wise forms keep refusing these designs, with a
+ * message that names almpc_sensitivity_ltv.
+ */
+int almpc_sensitivity_ltv(almpc_handle* h, uint32_t want, double act_tol);          /* ALMPC_SENS_K0 | _DU | _DX */
+int almpc_sensitivity_ltv_vjp(almpc_handle* h, const double* g_u, const double* g_x /* or NULL */, double act_tol,
+                              double* g_x0 /* [batch][n] */, int32_t* rows /* or NULL */);
+
+/*
  * Parameter gradients of the returned solution: for the loss of almpc_sensitivity_vjp (g_u [batch][N][m], g_x [batch][N+1][n] or NULL),
  * its gradient in the problem data, per instance, on the face where the rows W (same rule, same act_tol) are held -- the backward
  * pass of a step for a caller who learns or tunes the controller (k_sens_pz, k_sens_params; DESIGN.md "k_sens_params").  Stages

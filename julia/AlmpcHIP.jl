@@ -25,7 +25,8 @@ export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_s
        group_sensitivity_stagewise, group_sensitivity_stagewise_vjp, sensitivity_stagewise_rate, sensitivity_stagewise_rate_vjp,
        group_sensitivity_stagewise_rate, group_sensitivity_stagewise_rate_vjp, certificate, certificate!, device_certificate,
        group_certificate, group_certificate!, set_keep_stage_models, certificate_ltv, certificate_ltv!, device_certificate_ltv,
-       relin_fnn_certificate, relin_fnn_certificate!, group_relin_fnn_certificate, group_relin_fnn_certificate!
+       relin_fnn_certificate, relin_fnn_certificate!, group_relin_fnn_certificate, group_relin_fnn_certificate!,
+       sensitivity_ltv, sensitivity_ltv_vjp
 
 const libalmpc = get(ENV, "ALMPC_LIB", "libalmpc.so")
 
@@ -808,6 +809,37 @@ function sensitivity_stagewise_rate_vjp(mod::HipModeler, g_u::Array{Float64}, g_
     g_x0, rows = Matrix{Float64}(undef, mod.n, mod.batch), Vector{Int32}(undef, mod.batch)
     px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
     GC.@preserve g_x check(mod.handle, ccall((:almpc_sensitivity_stagewise_rate_vjp, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), mod.handle, g_u, px, act_tol, g_x0, rows))
+    return g_x0, rows
+end
+"""
+    sensitivity_ltv(mod; K0 = true, dU = false, dX = false, act_tol = 0.0) -> (K0, dU, dX, rows)
+
+The sensitivities of the last step of a `design_ltv!` design made with `set_keep_stage_models` in its initial deviation
+(`almpc_sensitivity_ltv` + `almpc_get_sensitivity`): the Riccati recursion on the face with the stage models `A_k, B_k`, with or without
+the input-rate weight S.  `K0` is the gain of a real-time iteration: apply `clamp.(u_0 + K0 * (x_meas - xbar_0), u_min, u_max)`.
+`act_tol` is relative to the width of the input box (0: 1e-7).
+"""
+function sensitivity_ltv(mod::HipModeler; K0::Bool = true, dU::Bool = false, dX::Bool = false, act_tol::Real = 0.0)
+    k, du, dx, rows = sens_arrays(mod.n, mod.m, mod.N, mod.batch, K0, dU, dX)
+    check(mod.handle, ccall((:almpc_sensitivity_ltv, libalmpc), Cint, (Ptr{Cvoid}, UInt32, Cdouble), mod.handle,
+                            sens_mask(K0, dU, dX), act_tol))
+    pf(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve k du dx check(mod.handle, ccall((:almpc_get_sensitivity, libalmpc), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), mod.handle, pf(k), pf(du), pf(dx), rows))
+    return k, du, dx, rows
+end
+"""
+    sensitivity_ltv_vjp(mod, g_u, g_x = nothing; act_tol = 0.0) -> (g_x0, rows)
+
+`sensitivity_vjp` of the same step (`almpc_sensitivity_ltv_vjp`): `g_x` is a loss gradient on the predicted states `xbar + dx` of
+`certificate_ltv`; the adjoint rides the backward sweep, no Jacobian is formed.
+"""
+function sensitivity_ltv_vjp(mod::HipModeler, g_u::Array{Float64}, g_x::Union{Nothing,Array{Float64}} = nothing; act_tol::Real = 0.0)
+    check_sens_sizes(mod.n, mod.m, mod.N, mod.batch, g_u, g_x)
+    g_x0, rows = Matrix{Float64}(undef, mod.n, mod.batch), Vector{Int32}(undef, mod.batch)
+    px = g_x === nothing ? Ptr{Float64}(C_NULL) : pointer(g_x)
+    GC.@preserve g_x check(mod.handle, ccall((:almpc_sensitivity_ltv_vjp, libalmpc), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Int32}), mod.handle, g_u, px, act_tol, g_x0, rows))
     return g_x0, rows
 end
