@@ -12,7 +12,7 @@ OBJDIR   := build/obj
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-cuda-compat
 ORACLE   := oracle/_build/libalmpc_oracle.so  # generic name; oracle/c_oracle.py builds a per-CPU copy itself
 
-TUS      := api tu_step tu_polish_gen tu_instance tu_design_a tu_design_b tu_sdual_a tu_sdual_b tu_sdual_c tu_dare tu_c2d tu_sens tu_sens_ltv tu_cert tu_cert_ltv
+TUS      := api tu_step tu_polish_gen tu_instance tu_design_a tu_design_b tu_sdual_a tu_sdual_b tu_sdual_c tu_dare tu_c2d tu_sens tu_sens_ltv tu_cert tu_cert_ltv tu_ltv_stage
 OBJS     := $(patsubst %,$(OBJDIR)/almpc_%.o,$(TUS))
 H_K      := $(CS)/almpc_kernels.hip.h
 H_D      := $(CS)/almpc_design.hip.h $(CS)/almpc_switches.h $(CS)/almpc_devbuf.h
@@ -42,6 +42,7 @@ $(OBJDIR)/almpc_tu_sens.o:       $(CS)/almpc_sens.hip.h $(CS)/instances/sens.inc
 $(OBJDIR)/almpc_tu_sens_ltv.o:   $(CS)/almpc_sens.hip.h $(CS)/almpc_sens_ltv.hip.h $(CS)/instances/sens_ltv.inc
 $(OBJDIR)/almpc_tu_cert.o:       $(CS)/almpc_cert.hip.h $(CS)/instances/cert.inc
 $(OBJDIR)/almpc_tu_cert_ltv.o:   $(CS)/almpc_cert.hip.h $(CS)/almpc_cert_ltv.hip.h $(CS)/instances/cert_ltv.inc
+$(OBJDIR)/almpc_tu_ltv_stage.o:  $(CS)/almpc_ltv_stage.hip.h
 
 $(OBJDIR)/almpc_%.o: $(CS)/almpc_%.hip
 	@mkdir -p $(dir $@)

@@ -70,6 +70,8 @@ _HANDLE_CALLS = {
     "set_keep_stage_models": [_i],
     "design_shared": [_dp] * 10 + [_d, _d], "design_batched": _BATCHED, "design_batched_weighted": _BATCHED,
     "design_ltv": [_dp] * 11 + [_i] + _BOX,
+    "design_ltv_stagewise": [_dp] * 11 + [_i, _dp, _dp, _i], "ltv_stagewise_update": [_dp] * 5 + [_i],
+    "get_ltv_stagewise_prepared": [_dp] * 3,
     "get_weights_instance": [_i, _dp, _dp, _dp], "get_design_instance": [_i, _dp, _dp, _dp], "get_gradient_instance": [_i, _dp],
     "get_terminal_weight_instance": [_i, _dp], "get_model_instance": [_i, _dp, _dp], "get_design": [_dp] * 4,
     "sqp_fnn_setup": _SQP_SETUP, "sqp_densenet_setup": _SQP_SETUP, "sqp_fnn_start": [_dp, _dp],
@@ -1018,6 +1020,62 @@ class Solver(_Target):
         umin, umax = _vec(umin, m), _vec(umax, m)
         self._check(self.L.almpc_design_ltv(self.h, _ptr(A), _ptr(B), _ptr(c), _ptr(xb), _ptr(ub), _ptr(xr), _ptr(ur), _ptr(Q), _ptr(R),
                                             _ptr(S), _ptr(P), p_inst, _ptr(umin), _ptr(umax), float(rho), float(sigma)))
+
+    def _ltv_stage_data(self, A_all, B_all, c_all, xbar, ubar, on_device):
+        """The five trajectory arrays of design_ltv_stagewise / ltv_stagewise_update as the C call takes them, and what keeps them alive.
+        Host form: numpy arrays in design_ltv's shapes.  Device form: integer device addresses (c_all: None or an address) of float64
+        memory in the C layout -- A_all [batch][N][n*n] and B_all [batch][N][n*m] column-major blocks, c_all [batch][N][n],
+        xbar [batch][N+1][n], ubar [batch][N][m]."""
+        n, m, N, b = self.n, self.m, self.N, self.batch
+        if on_device:
+            for name, a in (("A_all", A_all), ("B_all", B_all), ("xbar", xbar), ("ubar", ubar)):
+                if not isinstance(a, (int, np.integer)) or int(a) == 0:
+                    raise TypeError(f"on_device=True: {name} must be a non-zero integer device address")
+            if c_all is not None and not isinstance(c_all, (int, np.integer)):
+                raise TypeError("on_device=True: c_all must be None or an integer device address")
+            dev = lambda a: None if a is None else ctypes.cast(ctypes.c_void_p(int(a)), _dp)
+            return [dev(A_all), dev(B_all), dev(c_all), dev(xbar), dev(ubar)], None
+        A, B = _blocks(A_all, b * N, n, n), _blocks(B_all, b * N, n, m)
+        c = None if c_all is None else np.ascontiguousarray(np.asarray(c_all, dtype=np.float64).reshape(b, N, n))
+        xb, ub = _traj_batch(xbar, b, n, N + 1), _traj_batch(ubar, b, m, N)
+        keep = (A, B, c, xb, ub)
+        return [_ptr(a) for a in keep], keep
+
+    def design_ltv_stagewise(self, A_all, B_all, c_all, xbar, ubar, x_ref, u_ref, Q, R, S=None, P=None, umin=None, umax=None,
+                             xmin=None, xmax=None, terminal="none", on_device=False):
+        """design_ltv's problem on the stage-wise solvers of a structured handle (almpc_design_ltv_stagewise): no m N <= 128 limit, no
+        rho / sigma.  Arrays as design_ltv takes them, or with on_device=True the five trajectory arrays as integer device addresses
+        (see _ltv_stage_data for the layout; e.g. torch tensors' data_ptr()).  Weights, references, P and bounds are host arrays in
+        both forms.  get_results() then has every output: u = ubar + v, e_u = v, x = xbar + dx, e_x = dx.  No group form."""
+        n, m, b = self.n, self.m, self.batch
+        self._state_rows(xmin, xmax, terminal)
+        data, keep = self._ltv_stage_data(A_all, B_all, c_all, xbar, ubar, on_device)
+        xr, ur = _optional(_traj, x_ref, n, self.N + 1), _optional(_traj, u_ref, m, self.N)
+        Q, R, S = _colmajor(Q, (n, n)), _colmajor(R, (m, m)), _optional(_colmajor, S, (m, m))
+        P, p_inst = _terminal_weight(P, b, n)
+        umin, umax = _vec(umin, m), _vec(umax, m)
+        self._check(self.L.almpc_design_ltv_stagewise(self.h, *data, _ptr(xr), _ptr(ur), _ptr(Q), _ptr(R), _ptr(S), _ptr(P), p_inst,
+                                                      _ptr(umin), _ptr(umax), 1 if on_device else 0))
+        del keep
+
+    def ltv_stagewise_update(self, A_all, B_all, c_all, xbar, ubar, on_device=False):
+        """New trajectory data into the design of design_ltv_stagewise (almpc_ltv_stagewise_update): the per-iteration call of a
+        caller's outer loop.  With on_device=True nothing is waited for: the arrays must be complete before the call and may be
+        overwritten after synchronize().  c_all is None exactly when the design's was."""
+        data, keep = self._ltv_stage_data(A_all, B_all, c_all, xbar, ubar, on_device)
+        self._check(self.L.almpc_ltv_stagewise_update(self.h, *data, 1 if on_device else 0))
+        del keep
+
+    def ltv_stagewise_prepared(self, eq_target=False) -> dict:
+        """What k_ltv_stage_prepare left for the current data (almpc_get_ltv_stagewise_prepared): ebar (batch, N, n), qadd (batch, N, m)
+        and, when asked for (designs with the terminal equality), eq_target (n,)."""
+        b, n, m, N = self.batch, self.n, self.m, self.N
+        out = dict(ebar=np.empty((b, N, n)), qadd=np.empty((b, N, m)))
+        eq = np.empty(n) if eq_target else None
+        self._check(self.L.almpc_get_ltv_stagewise_prepared(self.h, _ptr(out["ebar"]), _ptr(out["qadd"]), _ptr(eq)))
+        if eq is not None:
+            out["eq_target"] = eq
+        return out
 
     def certificate_ltv(self, want=("cost", "res", "grad", "costate", "x", "e_x")) -> dict:
         """almpc_certificate_ltv + almpc_get_certificate_ltv after design_ltv(keep_stage_models=True) and a step: cost (batch,), res (batch,),

@@ -20,6 +20,7 @@
 #include "almpc_sens_ltv.hip.h"
 #include "almpc_cert.hip.h"
 #include "almpc_cert_ltv.hip.h"
+#include "almpc_ltv_stage.hip.h"
 #include "almpc_host_math.h"
 #include "almpc_switches.h"
 #include "almpc_devbuf.h"
@@ -288,6 +289,16 @@ struct almpc_handle {
         bool kept = false, kept_c = false;         // the current design is almpc_design_ltv's and left its stage models (and defects)
         DevBuf<double> xref, uref;                 // [N+1][n], [N][m] the design's shared references (zeros for NULL)
     } cert;
+    // almpc_design_ltv_stagewise (a structured handle): a caller's time-varying design on the stage-wise solvers.  The stage models
+    // live in lA, lB, lC (always kept: the solvers read them, and so can almpc_certificate_ltv / almpc_sensitivity_ltv), the shared
+    // references in cert.xref / cert.uref, the iterate (xbar, ubar) in dXref / dUref, the weights in wQ, wR, wS, bP.  Every buffer is
+    // made by the design call; almpc_ltv_stagewise_update copies into them and launches k_ltv_stage_prepare, nothing else.
+    struct Lsw {
+        bool ready = false, has_c = false;
+        long sP = 0;                         // doubles between the instances' terminal weights in bP (0: one shared matrix)
+        DevBuf<double> ebar, qadd, eqt;      // k_ltv_stage_prepare: [batch][N][n], [batch][N][m], [n] (with the terminal equality)
+        DevBuf<double> xst, ust;             // host form: xbar, ubar staged in front of the kernel
+    } lsw;
     // stage-wise dual active-set solve (k_sdual, csrc/almpc_sdual.hip.h): input box, state box, terminal equality and S in the
     // multiple-shooting form; stage records of the unconstrained problem (shared: host Riccati at design time)
     struct Sd {
@@ -636,6 +647,15 @@ hipError_t launch_riccati(almpc_handle* h, SolveCall call) {
         rp.qu = q.qadd; rp.qu_stride = N * m; rp.qu_scale = 0.5;
         rp.P = h->bP; rp.P_stride = q.sP;
         rp.x0 = nullptr; rp.flag = h->bFlag; rp.v_only = 1;
+    } else if (h->lsw.ready) {   // almpc_design_ltv_stagewise: the caller's stage models, k_ltv_stage_prepare's vectors; dx_0 = 0 (x0 = xbar_0)
+        const almpc_handle::Lsw& l = h->lsw;
+        const long n = h->n, m = h->m, N = h->N;
+        rp.A = h->lA; rp.A_stride = N * n * n; rp.A_kstride = n * n;
+        rp.B = h->lB; rp.B_stride = N * n * m; rp.B_kstride = n * m;
+        rp.c = l.has_c ? h->lC.get() : nullptr; rp.c_stride = N * n; rp.ebar = l.ebar; rp.ebar_stride = N * n;
+        rp.qu = l.qadd; rp.qu_stride = N * m; rp.qu_scale = 0.5;
+        rp.P = h->bP; rp.P_stride = l.sP;
+        rp.x0 = h->dXref; rp.x0_stride = n * (N + 1);
     }
     const size_t per = (size_t)rp.lds_per_wave * sizeof(double);
     const int waves = waves_in_lds(per, RICCATI_WAVES);
@@ -968,6 +988,15 @@ hipError_t launch_sgains(almpc_handle* h, SolveCall call = {}) {
         gp.ebar = q.ebar; gp.ebar_stride = N * n; gp.qadd = q.qadd; gp.qadd_stride = N * m; gp.qscale = 0.5;
         gp.base = sd.base; gp.base_stride = sd.base_stride;
         gp.flag = h->bFlag;
+    } else if (h->lsw.ready) {   // almpc_design_ltv_stagewise: the caller's stage models and defects, k_ltv_stage_prepare's cost terms
+        const almpc_handle::Lsw& l = h->lsw;
+        const long N = h->N;
+        gp.A = h->lA; gp.A_stride = N * n * n; gp.A_kstride = n * n;
+        gp.B = h->lB; gp.B_stride = N * n * m; gp.B_kstride = n * m;
+        gp.P = h->bP; gp.P_stride = l.sP;
+        if (l.has_c) { gp.c = h->lC; gp.c_stride = N * n; gp.pc = sd.pc; gp.ct = sd.ct; gp.pc_stride = N * sd.NT; }
+        gp.ebar = l.ebar; gp.ebar_stride = N * n; gp.qadd = l.qadd; gp.qadd_stride = N * m; gp.qscale = 0.5;
+        gp.base = sd.base; gp.base_stride = sd.base_stride;
     }
     if (!gp.A || !gp.B || !gp.P || !gp.rec) return hipErrorInvalidValue;
     gp.lds_per_wave = sgains_lds_doubles(sd.nt, h->m);
@@ -1097,6 +1126,12 @@ SdualParams sdual_solve_params(const almpc_handle* h, const SolveCall& call) {
         sp.x0 = nullptr; sp.xref = nullptr; sp.xref_stride = 0;
         sp.flag = h->bFlag; sp.v_only = 1;
         sp.rows = call.rows;
+    } else if (h->lsw.ready) {   // almpc_design_ltv_stagewise: dx_0 = 0, v = u - ubar, the references ARE the caller's trajectory; all outputs
+        const almpc_handle::Lsw& l = h->lsw;
+        sp.base = sd.base; sp.base_stride = sd.base_stride;
+        if (l.has_c) { sp.pc = sd.pc; sp.ct = sd.ct; sp.pc_stride = (long)h->N * sd.NT; }
+        sp.eqt = sd.has_eq ? l.eqt.get() : nullptr; sp.eqt_stride = 0;
+        sp.x0 = nullptr;
     }
     sp.ovf = sd.ovf; sp.wsave = sd.wsave;
     sp.gbad = sd.per_instance ? sd.bad : nullptr;
@@ -1345,6 +1380,7 @@ int upload_input_box(almpc_handle* h, const double* umin, const double* umax) {
 enum : unsigned { DROP_SQP = 1u, DROP_RELIN = 2u, WAIT_STREAM = 4u };
 int begin_redesign(almpc_handle* h, unsigned what) {
     h->designed = false;
+    h->lsw.ready = false;   // (almpc_design_ltv_stagewise sets it again behind this call)
     if (what & DROP_SQP) h->sqp.ready = h->sqp.started = false;
     if (what & DROP_RELIN) h->relin.ready = false;
     HIP_TRY(h, hipSetDevice(h->device));
@@ -2803,6 +2839,41 @@ int step_structured(almpc_handle* h, const almpc_opts& o) {
     return ALMPC_OK;
 }
 
+// k_ltv_stage_prepare on the handle's stream: (xb, ub) -> the iterate buffers, ebar, qadd, the terminal-equality target.  Launch only.
+hipError_t launch_ltv_stage_prepare(almpc_handle* h, const double* xb, const double* ub) {
+    const almpc_handle::Lsw& l = h->lsw;
+    LtvStageParams p;
+    p.n = h->n; p.m = h->m; p.N = h->N; p.batch = h->batch; p.useR = h->kept.useR; p.useS = h->kept.useS;
+    p.xbar = xb; p.ubar = ub; p.xref = h->cert.xref; p.uref = h->cert.uref; p.R = h->wR; p.S = h->wS;
+    p.xbar_out = h->dXref; p.ubar_out = h->dUref; p.ebar = l.ebar; p.qadd = l.qadd; p.eqt = l.eqt;
+    const int waves = LTV_STAGE_THREADS / 64, wgs = capped_grid(h->batch, waves, 8 * h->num_cus);
+    hipLaunchKernelGGL(k_ltv_stage_prepare, dim3((unsigned)wgs), dim3(LTV_STAGE_THREADS), 0, h->stream, p);
+    return hipGetLastError();
+}
+
+// The step of an almpc_design_ltv_stagewise design, by sqp_qp_stagewise's rule: an input box alone without S goes to the primal Riccati
+// active set on the stage models, everything else to k_sgains + k_sdual; start v = 0 (the guess is ubar itself: its inputs on a bound
+// seed the working set).  Behind the solve k_ltv_stage_finish: u = ubar + e_u, x = xbar + e_x.  opts.warm_start is ignored.
+int step_ltv_stagewise(almpc_handle* h, const almpc_opts& o) {
+    SolveCall qp;
+    qp.guess = h->dUref; qp.max_iter = o.polish_max_iter;
+    if (!h->sd.ready) {
+        HIP_TRY(h, launch_riccati(h, qp));
+    } else {
+        qp.first_tier = h->nz > 48 ? 1 : 0;
+        HIP_TRY(h, launch_sgains(h));
+        HIP_TRY(h, launch_sdual(h, qp));
+    }
+    LtvStageFinishParams f;
+    f.n = h->n; f.m = h->m; f.N = h->N; f.batch = h->batch;
+    f.xbar = h->dXref; f.ubar = h->dUref; f.ex = h->dEx; f.eu = h->dEu; f.x = h->dX; f.u = h->dU;
+    const int waves = LTV_STAGE_THREADS / 64, wgs = capped_grid(h->batch, waves, 8 * h->num_cus);
+    hipLaunchKernelGGL(k_ltv_stage_finish, dim3((unsigned)wgs), dim3(LTV_STAGE_THREADS), 0, h->stream, f);
+    HIP_TRY(h, hipGetLastError());
+    h->r_has_step = true;
+    return ALMPC_OK;
+}
+
 // Structured fallback: instances the condensed path left without a certificate (status != 0: an active-set finish that ran into its cap,
 // a non-finite or indefinite condensed problem) are redone in the multiple-shooting form, from the step's own result -- deferred
 // (almpc_handle::Redo) or right behind the step
@@ -2850,7 +2921,9 @@ int run_step(almpc_handle* h, const almpc_opts& o, StepMode mode) {
     h->redo.step_serial += 1;
     h->sd.start_ws_fresh = false;
     int rc = ALMPC_OK;
-    if (h->structured) {
+    if (h->lsw.ready) {
+        rc = step_ltv_stagewise(h, o);
+    } else if (h->structured) {
         rc = step_structured(h, o);
     } else {
         Step s{h, o, mode, keep_state, lazy_redo, StepTimer(), roll_geom(h), rollout_params(h)};
@@ -3025,6 +3098,155 @@ int almpc_design_ltv(almpc_handle* h, const double* A_all, const double* B_all, 
     LtvInputs in{A_all, B_all, c_all, ebar.data(), qadd.data(), ubar, xbar, xref, uref};
     if (h->structured) return fail(h, ALMPC_ERR_UNSUPPORTED, "structured solve: time-varying designs go through almpc_sqp_fnn_* (stage models on the device)");
     return design_ltv_condensed(h, A0.data(), B0.data(), Q, R, S, P, P_per_instance, umin, umax, rho, sigma, in);
+}
+
+// ---- time-varying designs on the stage-wise solvers (almpc_design_ltv_stagewise, almpc_ltv_stagewise_update; include/almpc.h) ----
+
+// The one path both forms of both calls take: the five trajectory arrays into the handle's buffers (stage models and defects by copy,
+// host to device or device to device; a host trajectory through the staging pair), then k_ltv_stage_prepare.  Enqueues; the host form
+// waits for its uploads, the device form for nothing.
+static int ltv_stagewise_load(almpc_handle* h, const double* A_all, const double* B_all, const double* c_all, const double* xbar,
+                              const double* ubar, int on_device) {
+    almpc_handle::Lsw& l = h->lsw;
+    const size_t n = (size_t)h->n, m = (size_t)h->m, N = (size_t)h->N, b = (size_t)h->batch;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    hipStream_t st = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(h->lA, A_all, b * N * n * n * sizeof(double), kind, st));
+    HIP_TRY(h, hipMemcpyAsync(h->lB, B_all, b * N * n * m * sizeof(double), kind, st));
+    if (l.has_c) HIP_TRY(h, hipMemcpyAsync(h->lC, c_all, b * N * n * sizeof(double), kind, st));
+    const double *xb = xbar, *ub = ubar;
+    if (!on_device) {
+        HIP_TRY(h, hipMemcpyAsync(l.xst, xbar, b * (N + 1) * n * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipMemcpyAsync(l.ust, ubar, b * N * m * sizeof(double), hipMemcpyHostToDevice, st));
+        xb = l.xst; ub = l.ust;
+    }
+    HIP_TRY(h, launch_ltv_stage_prepare(h, xb, ub));
+    if (!on_device) HIP_TRY(h, hipStreamSynchronize(st));   // (the caller's host arrays are free when the call returns)
+    h->sens.stepped = false; h->sens.have = 0; h->cert.have = 0;   // (the last step belongs to the data replaced here)
+    h->r_has_step = false;
+    return ALMPC_OK;
+}
+
+int almpc_design_ltv_stagewise(almpc_handle* h, const double* A_all, const double* B_all, const double* c_all, const double* xbar,
+                               const double* ubar, const double* xref, const double* uref, const double* Q, const double* R,
+                               const double* S, const double* P, int P_per_instance, const double* umin, const double* umax,
+                               int on_device) {
+    if (!h) return ALMPC_ERR_INVALID;
+    const char* who = "design_ltv_stagewise";
+    const std::string w(who);
+    if (!h->structured)
+        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": an ALMPC_FLAG_STRUCTURED handle's call (a condensed handle: almpc_design_ltv)");
+    if (model_continuous(h))
+        return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": continuous-time models (almpc_set_model_time) are not discretised stage by stage; give discrete stage models");
+    drop_lazy_redo(h);
+    if (!A_all || !B_all || !xbar || !ubar || !Q || !R || !P || !umin || !umax)
+        return fail(h, ALMPC_ERR_INVALID, w + ": null pointer (P must be given: there is no single model to take a DARE of)");
+    const int n = h->n, m = h->m, N = h->N, nz = h->nz;
+    const size_t b = (size_t)h->batch;
+    ALMPC_TRY(check_input_box(h, umin, umax, who));
+    // the route and its shape, before anything is touched: input box alone without S -> k_riccati_t, else k_sgains + k_sdual
+    const StateBox box = state_box(h);
+    const bool useR = R[0] != 0.0, useS = useR && S && S[0] != 0.0, rows = box.min || h->terminal_eq;
+    if (!rows && !useS) {
+        if (!riccati_shape_ok(h)) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the shape is outside k_riccati (n <= 32, m <= 16, m N <= 1024, its stage buffers in LDS)");
+    } else {
+        int NT = 0, MC = 0;
+        const int nt = useS ? n + m : n;
+        if (!sdual_shape_ok(n, m, N, useS) || !sdual_pick_shape(nt, m, &NT, &MC))
+            return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": state rows / input-rate weight need the stage-wise dual solve (n + m <= 48, (N + 1)(n + m) <= 4096)");
+        if (NT > 16)
+            return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": state rows / input-rate weight need n (+ m with S) <= 16 and m <= 8 here: the table-less G = 1 builds of "
+                                                      "k_sdual ((32, 16), (48, 16): a per-instance design has no cached responses) are not launched");
+        if ((size_t)sgains_lds_doubles(nt, m) * sizeof(double) > LDS_BUDGET) return fail(h, ALMPC_ERR_UNSUPPORTED, w + ": the gain recursion does not fit LDS");
+    }
+    ALMPC_TRY(begin_redesign(h, DROP_SQP | DROP_RELIN | WAIT_STREAM));
+    const hm::mat Qm = hm::symmetrised(Q, n), Rm = hm::symmetrised(R, m), Sm = hm::symmetrised(S, m);
+    const bool p_inst = P_per_instance != 0;
+    hm::mat Pall((p_inst ? b : 1) * (size_t)n * n);
+    for (size_t i = 0; i < (p_inst ? b : 1); ++i) {
+        const hm::mat Pm = hm::symmetrised(P + i * n * n, n);
+        std::copy(Pm.begin(), Pm.end(), Pall.begin() + i * n * n);
+    }
+    almpc_handle::Lsw& l = h->lsw;
+    l.has_c = c_all != nullptr; l.sP = p_inst ? (long)n * n : 0;
+    // buffers: stage models and defects, the iterate, the prepared vectors, the host form's staging pair
+    const size_t xs = (size_t)n * (N + 1);
+    HIP_TRY(h, h->lA.grow(b * N * n * n)); HIP_TRY(h, h->lB.grow(b * N * n * m));
+    if (l.has_c) HIP_TRY(h, h->lC.grow(b * N * n)); else h->lC.reset();
+    h->lE.reset();
+    HIP_TRY(h, h->dXref.alloc(b * xs)); HIP_TRY(h, h->dUref.alloc(b * nz));
+    h->dFS.reset(); h->dV0S.reset(); h->ref_keep = false;
+    HIP_TRY(h, l.ebar.grow(b * N * n)); HIP_TRY(h, l.qadd.grow(b * nz));
+    HIP_TRY(h, l.xst.grow(b * xs)); HIP_TRY(h, l.ust.grow(b * nz));
+    if (h->terminal_eq) HIP_TRY(h, l.eqt.grow((size_t)n)); else l.eqt.reset();
+    // weights, terminal weights and the shared references on the device
+    HIP_TRY(h, h->wQ.once((size_t)n * n)); HIP_TRY(h, h->wR.once((size_t)m * m)); HIP_TRY(h, h->wS.once((size_t)m * m));
+    HIP_TRY(h, hipMemcpy(h->wQ, Qm.data(), Qm.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->wR, Rm.data(), Rm.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->wS, Sm.data(), Sm.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, h->bP.grow(b * n * n));
+    HIP_TRY(h, hipMemcpy(h->bP, Pall.data(), Pall.size() * sizeof(double), hipMemcpyHostToDevice));
+    std::vector<double> xr(xs, 0.0), ur((size_t)nz, 0.0);
+    if (xref) xr.assign(xref, xref + xr.size());
+    if (uref) ur.assign(uref, uref + ur.size());
+    HIP_TRY(h, h->cert.xref.upload(xr.data(), xr.size()));
+    HIP_TRY(h, h->cert.uref.upload(ur.data(), ur.size()));
+    ALMPC_TRY(upload_input_box(h, umin, umax));
+    h->P.assign(Pall.begin(), Pall.begin() + (size_t)n * n); h->H.clear(); h->F.clear(); h->d.clear();
+    keep_weights(h, &Qm, &Rm, Sm, useR, useS);
+    h->t_step = false; h->c_step = false; h->weighted = false;
+    // state rows as the SQP loop's stage-wise route has them: coordinates of the stage-wise trajectory, no constraint-space matrix
+    ALMPC_TRY(setup_state_rows(h, nullptr, nullptr, true));
+    h->has_box = box.min ? 1 : 0;
+    h->mc = box.min ? N * n : (h->terminal_eq ? n : 0);
+    h->xref_stride = (long)xs; h->uref_stride = nz; h->fS_stride = nz;
+    h->batched = true; h->r_batched_P = true; h->rP_stride = l.sP; h->bP_stride = l.sP;
+    h->sd.ready = false;
+    if (!rows && !useS)
+        ALMPC_TRY(riccati_weights(h, Qm, Rm, nullptr));
+    else {   // per-instance records (k_sgains, every stage), cost terms and defects' value-function terms per instance, no cached responses
+        ALMPC_TRY(sdual_setup_batched(h, Qm, Rm, useS ? &Sm : nullptr, false, box.min, box.max, h->terminal_eq != 0));
+        almpc_handle::Sd& sd = h->sd;
+        const size_t TP = (size_t)sdual_tp(sd.NT, sd.MC, N);
+        HIP_TRY(h, sd.base.grow(b * TP));
+        sd.has_base = true; sd.base_stride = (long)TP;
+        HIP_TRY(h, sd.pc.grow(b * N * sd.NT)); HIP_TRY(h, sd.ct.grow(b * N * sd.NT));
+    }
+    l.ready = true;
+    const int rc = ltv_stagewise_load(h, A_all, B_all, c_all, xbar, ubar, on_device);
+    if (rc != ALMPC_OK) { l.ready = false; return rc; }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (a design call returns with its work done; the update call is the one that does not wait)
+    h->cert.kept = true; h->cert.kept_c = l.has_c;
+    h->ltv = true;
+    h->designed = true;
+    return ALMPC_OK;
+}
+
+int almpc_ltv_stagewise_update(almpc_handle* h, const double* A_all, const double* B_all, const double* c_all, const double* xbar,
+                               const double* ubar, int on_device) {
+    if (!h) return ALMPC_ERR_INVALID;
+    if (!h->designed || !h->lsw.ready) return fail(h, ALMPC_ERR_NOT_DESIGNED, "ltv_stagewise_update before almpc_design_ltv_stagewise");
+    if (!A_all || !B_all || !xbar || !ubar) return fail(h, ALMPC_ERR_INVALID, "ltv_stagewise_update: null pointer");
+    if ((c_all != nullptr) != h->lsw.has_c)
+        return fail(h, ALMPC_ERR_INVALID, h->lsw.has_c ? "ltv_stagewise_update: c_all is NULL, but the design was given defects"
+                                                       : "ltv_stagewise_update: c_all is given, but the design had none (NULL)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    return ltv_stagewise_load(h, A_all, B_all, c_all, xbar, ubar, on_device);
+}
+
+// The vectors k_ltv_stage_prepare left for the current data, read back (any pointer may be null): ebar [batch][N][n], qadd [batch][N][m],
+// the terminal-equality target [n]
+int almpc_get_ltv_stagewise_prepared(almpc_handle* h, double* ebar, double* qadd, double* eq_target) {
+    if (!h) return ALMPC_ERR_INVALID;
+    if (!h->designed || !h->lsw.ready) return fail(h, ALMPC_ERR_NOT_DESIGNED, "get_ltv_stagewise_prepared before almpc_design_ltv_stagewise");
+    if (eq_target && !h->lsw.eqt) return fail(h, ALMPC_ERR_INVALID, "get_ltv_stagewise_prepared: the design has no terminal equality");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t b = (size_t)h->batch, N = (size_t)h->N;
+    if (ebar) HIP_TRY(h, hipMemcpy(ebar, h->lsw.ebar, b * N * h->n * sizeof(double), hipMemcpyDeviceToHost));
+    if (qadd) HIP_TRY(h, hipMemcpy(qadd, h->lsw.qadd, b * N * h->m * sizeof(double), hipMemcpyDeviceToHost));
+    if (eq_target) HIP_TRY(h, hipMemcpy(eq_target, h->lsw.eqt, (size_t)h->n * sizeof(double), hipMemcpyDeviceToHost));
+    return ALMPC_OK;
 }
 
 int almpc_get_gradient_instance(almpc_handle* h, int instance, double* q) {

@@ -303,6 +303,45 @@ int almpc_design_ltv(almpc_handle* h, const double* A_all, const double* B_all, 
 int almpc_get_gradient_instance(almpc_handle* h, int instance, double* q);
 
 /*
+ * The same design on the STAGE-WISE solvers (ALMPC_FLAG_STRUCTURED handles only): nothing is condensed, so there is no m N <= 128
+ * limit and an open-loop unstable linearisation over a long horizon is not lost.  The QP, the layouts, the branch rules (R[1,1] == 0,
+ * S[1,1] == 0) and the meaning of every NULL are almpc_design_ltv's; there is no rho / sigma because no ADMM runs.
+ * almpc_set_state_box and almpc_set_terminal_equality apply as on the SQP loop's stage-wise route: the box is on xbar + dx (stages
+ * 1..N), the terminal equality is xbar_N + dx_N = xref_N.
+ *   on_device = 0: A_all, B_all, c_all, xbar, ubar are host pointers (the call returns when they have been uploaded);
+ *   on_device = 1: they are device memory of the handle's device (almpc_update_initialization_device's convention).  The handle keeps
+ *     its own copies (device-to-device copies on its stream): the arrays must be complete before the call and may be overwritten
+ *     after almpc_synchronize.  Weights, references, P and the bounds are host pointers in both forms.
+ * almpc_design_ltv_stagewise does everything that happens once (buffers, weights, input box, state rows, the solvers' set-up) and
+ * waits for it.  almpc_ltv_stagewise_update is the per-iteration call: new trajectory data into the same design -- no allocation, no
+ * upload but the five arrays, and in the device form no host wait (copies and k_ltv_stage_prepare are enqueued).  It returns
+ * ALMPC_ERR_NOT_DESIGNED before a stage-wise LTV design and ALMPC_ERR_INVALID when c_all is NULL and the design's was not, or the
+ * other way round.  The host form of either call uploads into the handle's buffers and then runs what the device form runs.
+ * almpc_calculate(_async): an input box alone with S = 0 goes to the primal Riccati active set (k_riccati_t) on the stage models,
+ * everything else to k_sgains + k_sdual; the start is v = 0 (the guess is ubar); opts->warm_start is ignored (every call's data is a
+ * new problem around a new trajectory), and so is almpc_update_initialization: the initial state is xbar_0 (dx_0 = 0).  ALL outputs of almpc_get_results are defined: u = ubar + v, e_u = v, x = xbar + dx (the
+ * predicted states), e_x = dx -- both sums hold bit for bit --, status as on any structured handle (ALMPC_INFEASIBLE: proven).
+ * almpc_certificate_ltv, almpc_sensitivity_ltv and _vjp serve such a design within their own limits (n <= 16, m <= 16,
+ * (N + 1)(n + m) <= 1024; state rows as they refuse them); the stage models are always kept here (the solver reads them):
+ * almpc_set_keep_stage_models is not needed.
+ * Refused with ALMPC_ERR_UNSUPPORTED and the reason: a condensed handle (almpc_design_ltv is its call); continuous-time models; with
+ * an input box alone and S = 0 a shape outside k_riccati; with state rows or S a shape outside k_sdual OR one that needs its
+ * (32, 16) / (48, 16) builds, i.e. n (+ m with S) > 16 or m > 8 -- those two builds have no table of cached responses on a
+ * per-instance design and are not launched without it.  The weights are shared: there is no
+ * almpc_design_batched_weighted form.  almpc_set_reference afterwards is refused as after almpc_design_ltv.  No group form
+ * (almpc_design_ltv has none either).
+ */
+int almpc_design_ltv_stagewise(almpc_handle* h, const double* A_all, const double* B_all, const double* c_all, const double* xbar,
+                               const double* ubar, const double* xref, const double* uref, const double* Q, const double* R,
+                               const double* S, const double* P, int P_per_instance, const double* umin, const double* umax,
+                               int on_device);
+int almpc_ltv_stagewise_update(almpc_handle* h, const double* A_all, const double* B_all, const double* c_all, const double* xbar,
+                               const double* ubar, int on_device);
+/* parity hook: what k_ltv_stage_prepare left for the current data -- ebar [batch][N][n] = xbar_{k+1} - xref_{k+1}, qadd [batch][N][m]
+ * = 2 Rbar (ubar - uref) + 2 D'Sbar D ubar, eq_target [n] = xref_N (terminal equality only); any may be NULL.  Waits for the stream. */
+int almpc_get_ltv_stagewise_prepared(almpc_handle* h, double* ebar, double* qadd, double* eq_target);
+
+/*
  * SQP outer loop for a black-box Fnn model, resident on the device (BASELINE configs[4]).  The problem is the reference's
  * NonLinearProgramming branch for Fnn models (.../fnn/mpc_modeler_implementation_fnn.jl:73-189): the quadratic cost of
  * _create_quadratic_cost_function (src/sub/design_mpc.jl:405-468) subject to x[:,k+1] = fnn(x[:,k], u[:,k]) and the input box,

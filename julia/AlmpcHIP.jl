@@ -26,7 +26,7 @@ export hip_solver_def, HipModeler, AlmpcOpts, design_hip, terminal_weight, set_s
        group_sensitivity_stagewise_rate, group_sensitivity_stagewise_rate_vjp, certificate, certificate!, device_certificate,
        group_certificate, group_certificate!, set_keep_stage_models, certificate_ltv, certificate_ltv!, device_certificate_ltv,
        relin_fnn_certificate, relin_fnn_certificate!, group_relin_fnn_certificate, group_relin_fnn_certificate!,
-       sensitivity_ltv, sensitivity_ltv_vjp
+       sensitivity_ltv, sensitivity_ltv_vjp, design_ltv_stagewise!, ltv_stagewise_update!
 
 const libalmpc = get(ENV, "ALMPC_LIB", "libalmpc.so")
 
@@ -543,6 +543,60 @@ function design_ltv!(mod::HipModeler, A_all::Array{Float64,4}, B_all::Array{Floa
                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
                    mod.handle, A_all, B_all, pc, xbar, ubar, x_ref, u_ref, Q, R, S, P, 0, umin, umax, mod.opts.rho, mod.opts.sigma))
     return mod
+end
+"""
+    design_ltv_stagewise!(mod, A_all, B_all, c_all, xbar, ubar, Q, R, S, P, umin, umax; x_ref, u_ref)
+
+`design_ltv!`'s problem on the stage-wise solvers of a structured modeler (`almpc_design_ltv_stagewise`): no `m N <= 128` limit, no
+rho / sigma; `x_ref` / `u_ref` may be `nothing`.  State box and terminal equality: `set_state_rows!` first.  Afterwards `results` has
+every output: `u = ubar + v`, `e_u = v`, `x = xbar + dx`, `e_x = dx`.  The five trajectory arrays are host arrays as in `design_ltv!`,
+or -- all five (`c_all` may stay `nothing`) -- `Ptr{Float64}` into device memory of the modeler's device in the same layout
+(`on_device = 1`).  No group form.
+"""
+function design_ltv_stagewise!(mod::HipModeler, A_all, B_all, c_all, xbar, ubar, Q::Matrix{Float64}, R::Matrix{Float64},
+                               S::Union{Nothing,Matrix{Float64}}, P::Matrix{Float64}, umin::Vector{Float64}, umax::Vector{Float64};
+                               x_ref::Union{Nothing,Matrix{Float64}} = nothing, u_ref::Union{Nothing,Matrix{Float64}} = nothing)
+    on_device = ltv_stage_form(A_all, B_all, c_all, xbar, ubar)
+    null = Ptr{Float64}(C_NULL)
+    GC.@preserve A_all B_all c_all xbar ubar x_ref u_ref S check(mod.handle, ccall((:almpc_design_ltv_stagewise, libalmpc), Cint,
+                   (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Cint),
+                   mod.handle, ltv_stage_ptr(A_all), ltv_stage_ptr(B_all), ltv_stage_ptr(c_all), ltv_stage_ptr(xbar), ltv_stage_ptr(ubar),
+                   x_ref === nothing ? null : pointer(x_ref), u_ref === nothing ? null : pointer(u_ref), Q, R,
+                   S === nothing ? null : pointer(S), P, 0, umin, umax, on_device))
+    return mod
+end
+"""
+    ltv_stagewise_update!(mod, A_all, B_all, c_all, xbar, ubar)
+
+New trajectory data into the design of `design_ltv_stagewise!` (`almpc_ltv_stagewise_update`): the per-iteration call of a caller's outer
+loop.  With device pointers nothing is waited for: the arrays must be complete before the call and may be overwritten after
+`synchronize`.  `c_all` is `nothing` exactly when the design's was.
+"""
+function ltv_stagewise_update!(mod::HipModeler, A_all, B_all, c_all, xbar, ubar)
+    on_device = ltv_stage_form(A_all, B_all, c_all, xbar, ubar)
+    GC.@preserve A_all B_all c_all xbar ubar check(mod.handle, ccall((:almpc_ltv_stagewise_update, libalmpc), Cint,
+                   (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint),
+                   mod.handle, ltv_stage_ptr(A_all), ltv_stage_ptr(B_all), ltv_stage_ptr(c_all), ltv_stage_ptr(xbar), ltv_stage_ptr(ubar), on_device))
+    return mod
+end
+"parity hook (`almpc_get_ltv_stagewise_prepared`): `ebar` n x N x batch and `qadd` m x N x batch as `k_ltv_stage_prepare` left them"
+function ltv_stagewise_prepared(mod::HipModeler)
+    ebar = Array{Float64,3}(undef, mod.n, mod.N, mod.batch)
+    qadd = Array{Float64,3}(undef, mod.m, mod.N, mod.batch)
+    check(mod.handle, ccall((:almpc_get_ltv_stagewise_prepared, libalmpc), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                            mod.handle, ebar, qadd, Ptr{Float64}(C_NULL)))
+    return ebar, qadd
+end
+ltv_stage_ptr(a::Nothing) = Ptr{Float64}(C_NULL)
+ltv_stage_ptr(a::Ptr{Float64}) = a
+ltv_stage_ptr(a::Array{Float64}) = pointer(a)
+"1 when the four required trajectory arrays are device pointers, 0 when they are host arrays; a mixture is an error"
+function ltv_stage_form(A_all, B_all, c_all, xbar, ubar)
+    dev = [a isa Ptr{Float64} for a in (A_all, B_all, xbar, ubar)]
+    all(dev) || !any(dev) || throw(ArgumentError("give the trajectory arrays as host arrays or as device pointers, not both"))
+    c_all === nothing || (c_all isa Ptr{Float64}) == dev[1] || throw(ArgumentError("c_all is of the other form"))
+    return Cint(dev[1] ? 1 : 0)
 end
 "Jacobians (A_i, B_i) and values of an Fnn at `x` (n x batch), `u` (m x batch) on device `device` (the batched `proceed_system_linearization`)"
 function fnn_linearize(W_in::Matrix{Float64}, W_h::Union{Array{Float64,3},Vector{Matrix{Float64}}}, b_h::Matrix{Float64}, W_out::Matrix{Float64},
